@@ -679,8 +679,11 @@ def sharded_retrieval_leg(rank: int, world: int, device: int, backend: str, rows
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=5,
+                    help="timed steps of the headline (the metric).  Work outside that timed region follows it: a one-stream profiling pass of 3 "
+                         "steps (skipped by --no-profile), and informational legs (api, ragged, f16 token head) of max(3, STEPS) "
+                         "steps plus an aligned ragged leg of 3 (skipped by --cpu-budget 0)")
+    ap.add_argument("--warmup", type=int, default=2, help="untimed steps before the headline's timed steps")
     ap.add_argument("--chunks", type=int, default=256, help="sequences per step per GPU")
     ap.add_argument("--micro-batch-tokens", type=int, default=int(os.environ.get("VRAG_MICRO_BATCH", "65536")))
     ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU-baseline work (0 = skip)")
@@ -689,7 +692,11 @@ def main() -> None:
                     help="MFMA operand type (bf16 = the metric's dtype; f16 = the highlighter extractor's default, informational)")
     ap.add_argument("--model", choices=["base", "large"], default="base",
                     help="base = BASELINE configs[1] (the metric); large = ModernBERT-large geometry (configs[4] extractor), informational")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the sentence logits of the last timed step to DIR/qa_logits.npy (float32; rank r > 0: qa_logits_rank<r>.npy)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if os.environ.get("VRAG_BENCH_SKIP_LEGS"):   # A/B sessions (tools/ab_streams.sh): the headline and its roofline only
         args.cpu_budget = 0.0
 
@@ -783,6 +790,11 @@ def main() -> None:
     eng.set_profiling(False)
     prof = eng.read_profile(reset=True)
     logits = eng.read_qa_logits(stream)
+    if args.dump_outputs:
+        # what a caller of the timed path receives: one (n_chunks * 16, 2) float32 row per sentence, from seeded inputs
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "qa_logits.npy" if rank == 0 else f"qa_logits_rank{rank}.npy"),
+                np.ascontiguousarray(logits, dtype=np.float32))
 
     # Second, untimed pass with the micro-batches serialised on ONE stream: per-kernel durations
     # without the cross-stream overlap of the timed region (kernel quality, not job throughput).

@@ -1,10 +1,15 @@
-"""The drop-in claim, executed: the REFERENCE's own `VerbatimIndex` and `VerbatimRAG` (imported from /root/reference,
-build container only -- skipped elsewhere) drive this package's store / providers / extractor, and the result equals
-this package's restatement of the same pipeline (`HotPathIndex` + `StaticVerbatimPipeline`).  Device classes are
-replaced by CPU stand-ins (oracle-backed shards, a logit function of the token ids): what is under test is every
-Python-level seam between the two code bases -- argument names, return types, `SearchResult` fields, dict keys."""
+"""The drop-in claim against the reference's recorded behaviour: the REFERENCE's own `VerbatimIndex`, `VerbatimRAG` and
+`VerbatimTransform` were run over this package's store / providers / extractor by tests/golden/gen_golden_dropin.py, and
+what they returned -- and every call they made into this package's store and extractor, with its arguments and result --
+is stored in tests/golden/dropin_fixtures.json.  This package's restatement of the same pipeline (`HotPathIndex` +
+`StaticVerbatimPipeline`) must return exactly what the reference returned, and the recorded calls, replayed on this
+package's objects, must return what they returned then.  Device classes are replaced by CPU stand-ins (oracle-backed
+shards, a logit function of the token ids): what is under test is every Python-level seam between the two code bases --
+argument names, return types, `SearchResult` fields, dict keys, scores, highlight offsets, citations."""
+import asyncio
+import enum
+import json
 import os
-import sys
 import types
 
 import numpy as np
@@ -15,25 +20,11 @@ from test_fast_packer import RecordingEngine
 from test_store_host_logic import _Dense, _Sparse
 from verbatim_rag_amd import vector_stores as vs
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present (GPU box)")
 G = os.path.join(os.path.dirname(__file__), "golden")
-
-
-@pytest.fixture()
-def reference(tmp_path, monkeypatch):
-    stubs = tmp_path / "stubs"
-    (stubs / "rapidfuzz").mkdir(parents=True)
-    (stubs / "rapidfuzz" / "__init__.py").write_text("")
-    (stubs / "rapidfuzz" / "fuzz.py").write_text("def partial_ratio_alignment(*a, **k):\n    raise RuntimeError('stub')\n")
-    (stubs / "openai").mkdir()
-    (stubs / "openai" / "__init__.py").write_text("class OpenAI:\n    def __init__(self, *a, **k): pass\nclass AsyncOpenAI(OpenAI):\n    pass\n")
-    for p in (str(stubs), os.path.join(REF, "packages", "core"), REF):
-        monkeypatch.syspath_prepend(p)
-    from verbatim_rag.core import VerbatimRAG
-    from verbatim_rag.index import VerbatimIndex
-
-    return VerbatimIndex, VerbatimRAG
+QUESTIONS = ("Where is the tall tower?", "How many stairs do visitors climb?")
+INDEX_QUERIES = (dict(text="Where is the tall tower?", k=5), dict(text="Visitors climb stairs", k=3, search_type="sparse"),
+                 dict(text="city", k=4, search_type="dense", filter='metadata["document_id"] == "d1"'),
+                 dict(text="Where is it?", k=5, hybrid_weights={"dense": 0.7, "sparse": 0.3}, rrf_k=20))
 
 
 class Dense:
@@ -61,181 +52,203 @@ class Sparse:
         return 300
 
 
-def test_reference_pipeline_runs_on_this_packages_classes(reference, monkeypatch):
+def cpu_stand_ins(setattr_):
+    """Routes GpuVectorStore to the CPU shards (`setattr_` is monkeypatch.setattr, or plain setattr in the generator)."""
+    setattr_(vs._lib, "load", lambda: None)
+    setattr_(vs._lib, "require_gpu", lambda: None)
+    setattr_(vs, "DenseShard", _Dense)
+    setattr_(vs, "SparseShard", _Sparse)
+
+
+def tower_docs(n):
+    return [f"The tower number {i} is tall. It stands in city {i % 4}. Visitors climb {i + 3} stairs! Was it built in {1800 + i}?" for i in range(n)]
+
+
+def corpus(n, document_ids):
+    """(store, this package's index over it, extractor): the corpus both pipelines ran on."""
     from tokenizers import Tokenizer
 
     from verbatim_rag_amd.extractors import GpuModelSpanExtractor
     from verbatim_rag_amd.index import HotPathIndex
+
+    docs = tower_docs(n)
+    metas = [dict({"document_id": f"d{i % 3}"} if document_ids else {}, title=f"Doc {i}", source=f"s{i}.md") for i in range(n)]
+    store = vs.GpuVectorStore(dense_dim=64, sparse_vocab=300)
+    ours = HotPathIndex(store, dense_provider=Dense(), sparse_provider=Sparse())
+    ours.add_chunks([f"c{i}" for i in range(n)], docs, metadatas=metas)
+    ext = GpuModelSpanExtractor(engine=RecordingEngine(), tokenizer=Tokenizer.from_file(os.path.join(G, "tokenizer.json")), threshold=0.5)
+    return store, ours, ext
+
+
+def hits(results):
+    return [[x.id, x.score, x.text, x.metadata] for x in results]
+
+
+class PairEngine:                                           # cross-encoder stand-in: score = overlap with the question
+    max_seqs, max_tokens, max_seq_len, pair_labels = 64, 8192, 512, 1
+    shape = types.SimpleNamespace(cls_token_id=1, sep_token_id=2)
+
+    def pair_logits(self, seqs, types_):
+        return np.asarray([[float(sum(t) % 17)] for t in seqs], np.float32)
+
+
+def _as_json(x):
+    return json.loads(json.dumps(x))
+
+
+def encode(x):
+    """JSON form of what crosses a seam: arrays, enum members, dicts with non-string keys and result objects are tagged so
+    `decode` rebuilds them (an enum member comes back as a member of a stand-in enum with the same value, a result object
+    as a plain namespace carrying the same fields)."""
+    if isinstance(x, enum.Enum):
+        return {"__enum__": encode(x.value)}
+    if isinstance(x, np.ndarray):
+        return {"__nd__": x.tolist(), "dtype": str(x.dtype)}
+    if isinstance(x, np.generic):
+        return x.item()
+    if isinstance(x, dict):
+        if all(isinstance(k, str) for k in x):
+            return {k: encode(v) for k, v in x.items()}
+        return {"__kv__": [[encode(k), encode(v)] for k, v in x.items()]}
+    if isinstance(x, (list, tuple)):
+        return [encode(v) for v in x]
+    if hasattr(x, "model_dump"):
+        return {"__obj__": encode(x.model_dump())}
+    if hasattr(x, "__dict__"):
+        return {"__obj__": encode(vars(x))}
+    return x
+
+
+def decode(x):
+    if isinstance(x, list):
+        return [decode(v) for v in x]
+    if isinstance(x, dict):
+        if "__nd__" in x:
+            return np.asarray(x["__nd__"], dtype=x["dtype"])
+        if "__enum__" in x:
+            return enum.Enum("Recorded", {"MEMBER": decode(x["__enum__"])}).MEMBER
+        if "__kv__" in x:
+            return {decode(k): decode(v) for k, v in x["__kv__"]}
+        if "__obj__" in x:
+            return types.SimpleNamespace(**decode(x["__obj__"]))
+        return {k: decode(v) for k, v in x.items()}
+    return x
+
+
+class Recorder:
+    """Stands in for `target` and logs every method call made on it: name, arguments and result, encoded."""
+
+    def __init__(self, target):
+        self._target, self.calls = target, []
+
+    def __getattr__(self, name):
+        attr = getattr(self._target, name)
+        if not callable(attr):
+            return attr
+
+        def call(*args, **kwargs):
+            out = attr(*args, **kwargs)
+            self.calls.append({"method": name, "args": encode(list(args)), "kwargs": encode(kwargs), "result": encode(out)})
+            return out
+
+        return call
+
+
+def replay(target, calls):
+    """Makes the recorded calls on `target`; each must return what it returned when recorded.  -> the results."""
+    got = []
+    for c in calls:
+        out = getattr(target, c["method"])(*decode(c["args"]), **decode(c["kwargs"]))
+        assert _as_json(encode(out)) == c["result"], (c["method"], c["kwargs"])
+        got.append(out)
+    return got
+
+
+@pytest.fixture(scope="module")
+def recorded():
+    with open(os.path.join(G, "dropin_fixtures.json")) as f:
+        return json.load(f)
+
+
+def test_pipeline_matches_the_recorded_reference_pipeline(recorded, monkeypatch):
     from verbatim_rag_amd.pipeline import StaticVerbatimPipeline
 
-    VerbatimIndex, VerbatimRAG = reference
-    monkeypatch.setattr(vs._lib, "load", lambda: None)
-    monkeypatch.setattr(vs._lib, "require_gpu", lambda: None)
-    monkeypatch.setattr(vs, "DenseShard", _Dense)
-    monkeypatch.setattr(vs, "SparseShard", _Sparse)
-    docs = [f"The tower number {i} is tall. It stands in city {i % 4}. Visitors climb {i + 3} stairs! Was it built in {1800 + i}?" for i in range(30)]
-    store = vs.GpuVectorStore(dense_dim=64, sparse_vocab=300)
-    dense, sparse = Dense(), Sparse()
-    ours = HotPathIndex(store, dense_provider=dense, sparse_provider=sparse)
-    ours.add_chunks([f"c{i}" for i in range(30)], docs, metadatas=[{"document_id": f"d{i % 3}", "title": f"Doc {i}", "source": f"s{i}.md"} for i in range(30)])
-    ext = GpuModelSpanExtractor(engine=RecordingEngine(), tokenizer=Tokenizer.from_file(os.path.join(G, "tokenizer.json")), threshold=0.5)
+    cpu_stand_ins(monkeypatch.setattr)
+    _store, ours, ext = corpus(30, document_ids=True)
+    assert [r["kw"] for r in recorded["index_queries"]] == _as_json(list(INDEX_QUERIES))
+    for kw, rec in zip(INDEX_QUERIES, recorded["index_queries"]):
+        got = _as_json(hits(ours.query(**kw)))
+        assert got == rec["results"] and 0 < len(got) <= kw["k"]
 
-    theirs = VerbatimIndex(vector_store=store, dense_provider=dense, sparse_provider=sparse)
-    for kw in (dict(text="Where is the tall tower?", k=5), dict(text="Visitors climb stairs", k=3, search_type="sparse"),
-               dict(text="city", k=4, search_type="dense", filter='metadata["document_id"] == "d1"'),
-               dict(text="Where is it?", k=5, hybrid_weights={"dense": 0.7, "sparse": 0.3}, rrf_k=20)):
-        a, b = theirs.query(**kw), ours.query(**kw)
-        assert [(x.id, x.score, x.text, x.metadata) for x in a] == [(x.id, x.score, x.text, x.metadata) for x in b] and 0 < len(a) <= kw["k"]
-
-    rag = VerbatimRAG(index=theirs, k=5, extractor=ext, template_mode="static", llm_client=types.SimpleNamespace())
     pipe = StaticVerbatimPipeline(ours, ext, k=5)
-    for question in ("Where is the tall tower?", "How many stairs do visitors climb?"):
-        resp = rag.query(question)
+    for question in QUESTIONS:
         mine = pipe.query(question)
-        assert resp.model_dump() == mine.model_dump()
-        assert len(resp.documents) == 5 and any(d.highlights for d in resp.documents)
-        for d in resp.documents:
+        assert _as_json(mine.model_dump()) == recorded["pipeline_k5"][question]
+        assert len(mine.documents) == 5 and any(d.highlights for d in mine.documents)
+        for d in mine.documents:
             assert all(d.content[h.start:h.end] == h.text for h in d.highlights)
-    assert [r.model_dump() for r in pipe.query_batch(["Where is the tall tower?", "How many stairs do visitors climb?"])] == \
-        [rag.query(q).model_dump() for q in ("Where is the tall tower?", "How many stairs do visitors climb?")]
-    assert "verbatim_rag.index" in sys.modules
+    assert _as_json([r.model_dump() for r in pipe.query_batch(list(QUESTIONS))]) == [recorded["pipeline_k5"][q] for q in QUESTIONS]
 
 
-def test_reference_async_transform_and_reranker_seams(reference, monkeypatch):
-    """`VerbatimRAG.query_async` (-> `extract_spans_async`, extractors.py:48-54), `VerbatimTransform.transform` (dict
-    contexts, transform.py:86-112) and the `reranker=` hook (core.py:125-140) with this package's classes plugged in."""
-    import asyncio
-
+def test_reranked_pipeline_and_async_extraction_match_the_recorded_reference(recorded, monkeypatch):
+    """`reranker=` hook (the reference's core.py:125-140) and the async extractor entry the reference's `query_async` awaits."""
     from tokenizers import Tokenizer
-    from verbatim_core.transform import VerbatimTransform
 
-    from verbatim_rag_amd.extractors import CoalescingSpanExtractor, GpuModelSpanExtractor
-    from verbatim_rag_amd.index import HotPathIndex
+    from verbatim_rag_amd.extractors import CoalescingSpanExtractor
     from verbatim_rag_amd.pipeline import StaticVerbatimPipeline
     from verbatim_rag_amd.rerankers import GpuCrossEncoderReranker
 
-    VerbatimIndex, VerbatimRAG = reference
-    monkeypatch.setattr(vs._lib, "load", lambda: None)
-    monkeypatch.setattr(vs._lib, "require_gpu", lambda: None)
-    monkeypatch.setattr(vs, "DenseShard", _Dense)
-    monkeypatch.setattr(vs, "SparseShard", _Sparse)
-    docs = [f"The tower number {i} is tall. It stands in city {i % 4}. Visitors climb {i + 3} stairs! Was it built in {1800 + i}?" for i in range(20)]
-    store = vs.GpuVectorStore(dense_dim=64, sparse_vocab=300)
-    ours = HotPathIndex(store, dense_provider=Dense(), sparse_provider=Sparse())
-    ours.add_chunks([f"c{i}" for i in range(20)], docs, metadatas=[{"title": f"Doc {i}", "source": f"s{i}.md"} for i in range(20)])
-    tok = Tokenizer.from_file(os.path.join(G, "tokenizer.json"))
-    ext = GpuModelSpanExtractor(engine=RecordingEngine(), tokenizer=tok, threshold=0.5)
-    theirs = VerbatimIndex(vector_store=store, dense_provider=ours.dense_provider, sparse_provider=ours.sparse_provider)
-    question = "Where is the tall tower?"
+    cpu_stand_ins(monkeypatch.setattr)
+    _store, ours, ext = corpus(20, document_ids=False)
+    question = QUESTIONS[0]
+    sync = _as_json(StaticVerbatimPipeline(ours, ext, k=4).query(question).model_dump())
+    assert sync == recorded["pipeline_k4"]
 
-    rag = VerbatimRAG(index=theirs, k=4, extractor=ext, template_mode="static", llm_client=types.SimpleNamespace())
-    sync = rag.query(question).model_dump()
-    assert asyncio.run(rag.query_async(question)).model_dump() == sync
-
+    results = ours.query(text=question, k=4)
+    spans = ext.extract_spans(question, results)
+    assert any(spans.values()) and asyncio.run(ext.extract_spans_async(question, results)) == spans
     co = CoalescingSpanExtractor(ext, max_wait_ms=1.0)          # the per-query interface in front of the batch path
     try:
-        rag_co = VerbatimRAG(index=theirs, k=4, extractor=co, template_mode="static", llm_client=types.SimpleNamespace())
-        assert asyncio.run(rag_co.query_async(question)).model_dump() == sync
+        assert asyncio.run(co.extract_spans_async(question, results)) == spans
+        assert _as_json(StaticVerbatimPipeline(ours, co, k=4).query(question).model_dump()) == sync
     finally:
         co.close()
 
-    tr = VerbatimTransform(llm_client=types.SimpleNamespace(), extractor=ext, template_mode="static")
-    out = tr.transform(question, [{"content": docs[0], "title": "T0", "source": "s0"}, {"text": docs[1]}])
-    assert [d.content for d in out.documents] == docs[:2] and out.documents[0].title == "T0"
-    assert all(d.content[h.start:h.end] == h.text for d in out.documents for h in d.highlights)
+    # dict contexts, one of them text only, coerced by the reference's VerbatimTransform and IndexProvider
+    # (transform.py:86-112, providers.py:40-84) into minimal result objects (id, text, score, metadata; the text-only one
+    # with an empty title): this extractor gets them as recorded, as plain namespaces, and must return the spans it
+    # returned then
+    calls = recorded["transform_extract_calls"]
+    assert [c["method"] for c in calls] == ["extract_spans", "extract_spans"]
+    minimal = calls[0]["args"][1]
+    assert all(set(r["__obj__"]) == {"id", "text", "score", "metadata"} for r in minimal) and minimal[1]["__obj__"]["metadata"]["title"] == ""
+    assert all(any(spans.values()) for spans in replay(ext, calls))
 
-    # RAG-agnostic adapters (providers.py:40-84): SearchResult -> context dicts -> transform
-    from verbatim_rag.providers import IndexProvider
-
-    ctx = IndexProvider(theirs).retrieve(question, k=3)
-    assert len(ctx) == 3 and all(c["content"] in docs and c["title"].startswith("Doc ") for c in ctx)
-    assert [d.content for d in tr.transform(question, ctx).documents] == [c["content"] for c in ctx]
-    assert asyncio.run(IndexProvider(theirs).retrieve_async(question, k=3)) == ctx
-
-    class PairEngine:                                           # cross-encoder stand-in: score = overlap with the question
-        max_seqs, max_tokens, max_seq_len, pair_labels = 64, 8192, 512, 1
-        shape = types.SimpleNamespace(cls_token_id=1, sep_token_id=2)
-
-        def pair_logits(self, seqs, types_):
-            return np.asarray([[float(sum(t) % 17)] for t in seqs], np.float32)
-
-    rr = GpuCrossEncoderReranker(PairEngine(), tok, rerank_k=3)
-    with_rr = VerbatimRAG(index=theirs, k=4, extractor=ext, template_mode="static", llm_client=types.SimpleNamespace(), reranker=rr)
-    mine = StaticVerbatimPipeline(ours, ext, k=4, reranker=rr)
-    a, b = with_rr.query(question).model_dump(), mine.query(question).model_dump()
-    assert a == b and [d["content"] for d in a["documents"]] != [d["content"] for d in sync["documents"]]
+    rr = GpuCrossEncoderReranker(PairEngine(), Tokenizer.from_file(os.path.join(G, "tokenizer.json")), rerank_k=3)
+    reranked = _as_json(StaticVerbatimPipeline(ours, ext, k=4, reranker=rr).query(question).model_dump())
+    assert reranked == recorded["pipeline_k4_reranked"]
+    assert [d["content"] for d in reranked["documents"]] != [d["content"] for d in sync["documents"]]
 
 
-def test_reference_streaming_over_this_packages_classes(reference, monkeypatch):
-    """`StreamingRAG.stream_query` (streaming.py:24-177): documents, then highlights (extract_spans in a worker thread),
-    then the answer -- reads `doc.metadata.get(...)` and the extractor's dict directly."""
-    import asyncio
-
-    from tokenizers import Tokenizer
-    from verbatim_rag.streaming import StreamingRAG
-
-    from verbatim_rag_amd.extractors import GpuModelSpanExtractor
-    from verbatim_rag_amd.index import HotPathIndex
-
-    VerbatimIndex, VerbatimRAG = reference
-    monkeypatch.setattr(vs._lib, "load", lambda: None)
-    monkeypatch.setattr(vs._lib, "require_gpu", lambda: None)
-    monkeypatch.setattr(vs, "DenseShard", _Dense)
-    monkeypatch.setattr(vs, "SparseShard", _Sparse)
-    docs = [f"The tower number {i} is tall. It stands in city {i % 4}. Visitors climb {i + 3} stairs!" for i in range(12)]
-    store = vs.GpuVectorStore(dense_dim=64, sparse_vocab=300)
-    HotPathIndex(store, dense_provider=Dense(), sparse_provider=Sparse()).add_chunks(
-        [f"c{i}" for i in range(12)], docs, metadatas=[{"title": f"Doc {i}", "source": f"s{i}.md"} for i in range(12)])
-    ext = GpuModelSpanExtractor(engine=RecordingEngine(), tokenizer=Tokenizer.from_file(os.path.join(G, "tokenizer.json")), threshold=0.5)
-    rag = VerbatimRAG(index=VerbatimIndex(vector_store=store, dense_provider=Dense(), sparse_provider=Sparse()), k=3, extractor=ext,
-                      template_mode="static", llm_client=types.SimpleNamespace())
-
-    async def collect():
-        return [ev async for ev in StreamingRAG(rag).stream_query("Where is the tall tower?")]
-
-    events = asyncio.run(collect())
-    kinds = [e.get("type") for e in events]
-    assert "error" not in kinds and kinds[0] == "documents" and "highlights" in kinds and kinds[-1] == "answer", kinds
-    final = rag.query("Where is the tall tower?")
-    assert events[-1]["done"] is True and events[-1]["data"] == final.model_dump()
-    docs_ev = next(e for e in events if e["type"] == "documents")["data"]
-    assert [d["content"] for d in docs_ev] == [d.content for d in final.documents] and all(d["highlights"] == [] for d in docs_ev)
-    hl_ev = next(e for e in events if e["type"] == "highlights")["data"]
-    assert [[h["text"] for h in d["highlights"]] for d in hl_ev] == [[h.text for h in d.highlights] for d in final.documents]
-
-
-def test_reference_ingest_path_fills_this_packages_store(reference, monkeypatch, tmp_path):
+def test_store_serves_the_recorded_reference_ingest_path(recorded, monkeypatch, tmp_path):
     """`VerbatimIndex.add_documents` (index.py:318-411: the reference's chunker, `_prepare_chunk_metadata`,
     `_generate_embeddings`, `_store_chunks` -> `store.add_vectors(ids=, dense_vectors=, sparse_vectors=, texts=,
-    enhanced_texts=, metadatas=)`), then queries, a `document_id` filter built the reference's way, save / load."""
-    from verbatim_rag.schema import DocumentSchema
-
-    VerbatimIndex, _VerbatimRAG = reference
-    monkeypatch.setattr(vs._lib, "load", lambda: None)
-    monkeypatch.setattr(vs._lib, "require_gpu", lambda: None)
-    monkeypatch.setattr(vs, "DenseShard", _Dense)
-    monkeypatch.setattr(vs, "SparseShard", _Sparse)
+    enhanced_texts=, metadatas=)`, `_store_document_metadata` -> `store.add_documents(records)`), then queries, a `document_id`
+    filter built the reference's way, the accessors built on the store (index.py:657-760), a document miss: every store call
+    it made is replayed on a fresh store, and the reads once more on that store saved and loaded."""
+    cpu_stand_ins(monkeypatch.setattr)
+    rec = recorded["ingest"]
+    calls, doc_id = rec["calls"], rec["document_id"]
+    assert {"add_vectors", "add_documents", "query", "get_document"} <= {c["method"] for c in calls}
     store = vs.GpuVectorStore(dense_dim=64, sparse_vocab=300)
-    idx = VerbatimIndex(vector_store=store, dense_provider=Dense(), sparse_provider=Sparse())
-    docs = [DocumentSchema(content=f"# Title {i}\n\nThe tower number {i} is tall. It stands in city {i}.\n\n## Section\n\nVisitors climb {i + 3} stairs!",
-                           title=f"Doc {i}", source=f"s{i}.md") for i in range(6)]
-    idx.add_documents(docs)
+    got = replay(store, calls)
     assert len(store._ids) >= 6 and all(isinstance(v, (str, int, float, bool, type(None), list, dict)) for md in store._meta for v in md.values())
-    hits = idx.query(text="The tower is tall", k=4)
-    assert len(hits) == 4 and all(h.metadata["title"].startswith("Doc ") and h.text for h in hits)
-    doc_id = hits[0].metadata["document_id"]
-    only = idx.query(text="The tower is tall", k=10, filter=f'metadata["document_id"] == "{doc_id}"')
-    assert only and all(h.metadata["document_id"] == doc_id for h in only)
-    # accessors the reference builds on filter-only / vector-less queries (index.py:657-760) and the document records
-    assert len(idx.get_all_chunks(limit=5)) == 5
-    listed = idx.get_all_documents(limit=3)
-    assert len(listed) == 3 and all(d["title"].startswith("Doc ") and d["content_type"] for d in listed)
-    by_doc = idx.get_chunks_by_document(doc_id)
-    assert by_doc and all(h.metadata["document_id"] == doc_id for h in by_doc)
-    assert idx.inspect()["total_documents"] == 6
-    rec = idx.get_document(doc_id)
-    assert rec is not None and rec["id"] == doc_id and rec["title"].startswith("Doc ") and idx.get_document("nope") is None
+    filtered = [g for c, g in zip(calls, got) if c["method"] == "query" and doc_id in str(c["kwargs"].get("filter"))]
+    assert filtered and all(h.metadata["document_id"] == doc_id for hs in filtered for h in hs) and all(filtered)
+    rec_doc = store.get_document(doc_id)
+    assert rec_doc is not None and rec_doc["id"] == doc_id and rec_doc["title"].startswith("Doc ") and store.get_document("nope") is None
+
     store.save(str(tmp_path / "idx"))
-    again = VerbatimIndex(vector_store=vs.GpuVectorStore.load(str(tmp_path / "idx")), dense_provider=Dense(), sparse_provider=Sparse())
-    assert [(h.id, h.score) for h in again.query(text="The tower is tall", k=4)] == [(h.id, h.score) for h in hits]
-    assert again.get_document(doc_id) == rec
+    again = vs.GpuVectorStore.load(str(tmp_path / "idx"))
+    replay(again, [c for c in calls if c["method"] in ("query", "get_document")])
+    assert again.get_document(doc_id) == rec_doc
