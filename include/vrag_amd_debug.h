@@ -1,7 +1,7 @@
 /* vrag_amd_debug.h -- tuning / unit-test harness of the gfx950 kernels.  NOT part of the product ABI (include/vrag_amd.h):
  * these entry points exist only in libvrag_amd_dbg.so, the harness build of the same sources (verbatim-rag_amd/build.py,
  * -DVRAG_DEBUG_API: it also keeps the phase-decomposition branches of the fused kernel that the product build compiles out).
- * tools/ and tests/test_attention_unit_gpu.py load it beside the product library. */
+ * tools/, tests/test_attention_unit_gpu.py and tests/test_gemm_unit_gpu.py load it beside the product library. */
 #ifndef VRAG_AMD_DEBUG_H
 #define VRAG_AMD_DEBUG_H
 
@@ -25,6 +25,50 @@ int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, 
  * pre-scaled by head_dim^-1/2 * log2 e; vt: [H, Tp], Tp = T rounded up to 256), o [T, H] out; T = n_seqs * S. */
 int vrag_debug_attn_run(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int32_t window, int32_t f16, const uint16_t* q,
                         const uint16_t* k, const uint16_t* vt, uint16_t* o, int32_t device);
+
+/* Unit-test hook of the GEMM alone (csrc/gemm_bf16.h, every epilogue except the top-k search and EPI_NONE): host buffers in the
+ * layouts GemmParams documents, every pointer nullable (null = the GemmParams field stays null).  Row-indexed buffers hold
+ * `rows` rows (a multiple of 64, at least row0 + M rounded up to 256); the launch covers rows [row0, row0 + M) through pointers
+ * offset by row0 rows, as the encoder addresses a micro-batch (byte plane: row0 * N bytes; V^T: row0 columns; statistics:
+ * row0 of stats_ld = rows).  16-bit buffers hold bf16 or fp16 bits (f16).  Every buffer marked "in / out" is copied to the
+ * device, and back after ONE launch.  lo_out may equal lo_in (one device buffer, as the encoder aliases them). */
+typedef struct vrag_debug_gemm_args {
+  const uint16_t* A;         /* [rows, K] */
+  const uint16_t* W;         /* [N, K] */
+  const float* bias;         /* [N] */
+  const float* ln_s;         /* [N] */
+  const float* stats_in;     /* [K / 64, rows, 2] */
+  const float* res_mu;       /* [rows] */
+  const float* res_rstd;     /* [rows] */
+  const float* res_g;        /* [N] */
+  const float* res_b;        /* [N] */
+  const float* rope_cos;     /* [rope_rows, 32] */
+  const float* rope_sin;     /* [rope_rows, 32] */
+  const int32_t* pos;        /* [rows] */
+  const int32_t* tok_seq;    /* [rows] */
+  const uint8_t* lo_in;      /* [rows * N] */
+  float* out_f32;            /* in / out [rows, N] */
+  uint16_t* out_bf16;        /* in / out [rows, N] (EPI_GEGLU: [rows, N / 2]) */
+  uint16_t* q;               /* in / out [rows, hidden] */
+  uint16_t* k;               /* in / out [rows, hidden] */
+  uint16_t* vt;              /* in / out [hidden, rows] */
+  float* ln_mu;              /* in / out [rows] */
+  float* ln_rstd;            /* in / out [rows] */
+  float* ln_shift;           /* in / out [rows] */
+  float* ln_shift_prev;      /* in / out [rows] */
+  uint16_t* resid_bf16;      /* in / out [rows, N] */
+  float* stats_part;         /* in / out [N / 64, rows, 2] */
+  uint8_t* lo_out;           /* in / out [rows * N] */
+  uint32_t* splade_rows;     /* in / out [n_seqs, N] */
+  int32_t epi, M, N, K, f16, act_gelu;
+  int32_t row0, rows;
+  int32_t hidden, rope_rows, n_seqs;
+  int32_t small_rows;        /* small-batch row threshold for this call (restored afterwards); < 0 = leave it */
+  float q_scale, fin_eps;
+  int32_t config[7];         /* out: the tile configuration that ran: BM, BN, WM, WN, NS, HW, KCH */
+  int32_t f16_saturated;     /* out: an fp16 conversion of this launch clamped at +-65504 */
+} vrag_debug_gemm_args;
+int vrag_debug_gemm_run(vrag_debug_gemm_args* args, int32_t device);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,7 @@
 """The C-ABI library loads on a CPU-only box and exports every symbol include/vrag_amd.h declares."""
 import ctypes
+import shutil
+import subprocess
 import os
 import re
 
@@ -120,3 +122,34 @@ def test_one_hip_runtime_whatever_the_import_order():
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.strip().splitlines()[-1] == "1", out.stdout
+
+
+def _host_cc():
+    for cand in (os.environ.get("CC"), shutil.which("cc"), shutil.which("gcc"), shutil.which("clang"), "/opt/rocm/llvm/bin/clang"):
+        if cand and os.path.exists(cand):
+            return cand
+    return None
+
+
+@pytest.mark.skipif(_host_cc() is None, reason="no host C compiler")
+def test_debug_gemm_args_layout_matches_ctypes(tmp_path):
+    """vrag_debug_gemm_args crosses the ctypes boundary of the GEMM unit test: sizeof and every offsetof as the host C compiler
+    lays the struct out must equal _lib.DebugGemmArgs."""
+    S = _lib.DebugGemmArgs
+    names = [f[0] for f in S._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text("#include <stddef.h>\n#include <stdio.h>\n#include \"vrag_amd_debug.h\"\nint main(void) {\n"
+                   "  printf(\"sizeof %zu\\n\", sizeof(vrag_debug_gemm_args));\n"
+                   + "".join(f"  printf(\"{n} %zu\\n\", offsetof(vrag_debug_gemm_args, {n}));\n" for n in names)
+                   + "  return 0;\n}\n")
+    exe = tmp_path / "layout"
+    subprocess.run([_host_cc(), "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
+                   check=True, capture_output=True)
+    got = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    assert int(got.pop("sizeof")) == ctypes.sizeof(S)
+    assert {n: int(v) for n, v in got.items()} == {n: getattr(S, n).offset for n in names}
+    # and the header declares no field the ctypes side lacks
+    hdr = open(os.path.join(ROOT, "include", "vrag_amd_debug.h")).read()
+    body = re.sub(r"/\*.*?\*/", "", hdr[hdr.index("typedef struct vrag_debug_gemm_args"):hdr.index("} vrag_debug_gemm_args;")], flags=re.S)
+    declared = re.findall(r"\b([a-z_0-9A-Z]+)(?:\[\d+\])?\s*[,;]", body.split("{", 1)[1])
+    assert declared == names

@@ -148,7 +148,19 @@ DEBUG_SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_int32]),
     "vrag_debug_attn_ms": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "vrag_debug_qkv_attn_ms": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP]),
+    "vrag_debug_gemm_run": (C.c_int, [C.c_void_p, C.c_int32]),
 }
+
+
+class DebugGemmArgs(C.Structure):
+    """vrag_debug_gemm_args (include/vrag_amd_debug.h), field for field; tests/test_capi_abi.py checks the layout against the
+    host compiler's."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "A", "W", "bias", "ln_s", "stats_in", "res_mu", "res_rstd", "res_g", "res_b", "rope_cos", "rope_sin", "pos", "tok_seq",
+        "lo_in", "out_f32", "out_bf16", "q", "k", "vt", "ln_mu", "ln_rstd", "ln_shift", "ln_shift_prev", "resid_bf16",
+        "stats_part", "lo_out", "splade_rows")] + [(n, C.c_int32) for n in (
+        "epi", "M", "N", "K", "f16", "act_gelu", "row0", "rows", "hidden", "rope_rows", "n_seqs", "small_rows")] + [
+        ("q_scale", C.c_float), ("fin_eps", C.c_float), ("config", C.c_int32 * 7), ("f16_saturated", C.c_int32)]
 _DBG = None
 
 

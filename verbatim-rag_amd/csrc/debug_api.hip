@@ -1,5 +1,5 @@
 // Tuning / unit-test harness of the kernels (include/vrag_amd_debug.h): synthetic-operand timing loops and the attention
-// kernels' unit-test hook.  NOT part of the product library: compiled only into libvrag_amd_dbg.so (build.py, -DVRAG_DEBUG_API),
+// kernels' and the GEMM's unit-test hooks.  NOT part of the product library: compiled only into libvrag_amd_dbg.so (build.py, -DVRAG_DEBUG_API),
 // which tools/ and the attention unit test load beside libvrag_amd.so.
 #include "../../include/vrag_amd.h"
 #include "../../include/vrag_amd_debug.h"
@@ -383,6 +383,179 @@ int vrag_debug_attn_run(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int
   cleanup();
   if (e != hipSuccess) {
     set_error("debug attention run failed: %s", hipGetErrorString(e));
+    return VRAG_ERR_HIP;
+  }
+  return VRAG_OK;
+}
+
+int vrag_debug_gemm_run(vrag_debug_gemm_args* a, int32_t device) {
+  ARG_CHECK(a, "null arguments");
+  const int epi = a->epi, M = a->M, N = a->N, K = a->K;
+  ARG_CHECK(epi == EPI_F32 || epi == EPI_BF16 || epi == EPI_F32_GELU || epi == EPI_RESIDUAL || epi == EPI_GEGLU ||
+                epi == EPI_QKV_ROPE || epi == EPI_SPLADE,
+            "epilogue %d is not covered by the GEMM unit hook", epi);
+  ARG_CHECK(M > 0 && N > 0 && N % 128 == 0 && K > 0 && K % 64 == 0, "bad shape M=%d N=%d K=%d", M, N, K);
+  const int64_t Mpad = align_up(M, kRowPad);
+  ARG_CHECK(a->row0 >= 0 && a->row0 % 64 == 0 && a->rows % 64 == 0 && a->rows >= a->row0 + Mpad,
+            "rows (%d) must be a multiple of 64 holding row0 (%d) + M rounded up to %d", a->rows, a->row0, kRowPad);
+  ARG_CHECK(a->A && a->W, "A and W are required");
+  const bool in_split = a->lo_in != nullptr, out_split = a->lo_out != nullptr;
+  // every pointer the chosen epilogue dereferences must be there: the hook never launches a kernel onto a null buffer
+  switch (epi) {
+    case EPI_F32:
+    case EPI_F32_GELU: ARG_CHECK(a->out_f32, "out_f32 required"); break;
+    case EPI_BF16: ARG_CHECK(a->out_bf16, "out_bf16 required"); break;
+    case EPI_GEGLU: ARG_CHECK(a->out_bf16, "out_bf16 required"); break;
+    case EPI_RESIDUAL:
+      ARG_CHECK(a->out_f32 || (in_split && out_split), "out_f32 required unless the stream is split on both sides");
+      ARG_CHECK(!a->res_mu || (a->res_rstd && a->res_g && a->res_b), "post-LN input needs res_mu, res_rstd, res_g, res_b");
+      ARG_CHECK(!(in_split || out_split) || a->resid_bf16, "the split stream needs resid_bf16");
+      break;
+    case EPI_QKV_ROPE:
+      ARG_CHECK(a->hidden > 0 && a->hidden % 128 == 0 && N == 3 * a->hidden, "QKV: N = 3 hidden, hidden %% 128 == 0");
+      ARG_CHECK(a->q && a->k && a->vt && a->rope_cos && a->rope_sin && a->pos && a->rope_rows > 0, "QKV buffers required");
+      break;
+    case EPI_SPLADE: ARG_CHECK(a->tok_seq && a->splade_rows && a->n_seqs > 0, "SPLADE buffers required"); break;
+  }
+  ARG_CHECK(!(a->ln_mu || a->ln_rstd || a->ln_s) || (a->ln_mu && a->ln_rstd && a->ln_s), "the fold needs ln_mu, ln_rstd and ln_s");
+  ARG_CHECK(!a->stats_in || (a->ln_mu && a->ln_shift), "consumer finalisation needs ln_mu, ln_rstd, ln_s and ln_shift");
+  ARG_CHECK(!in_split || a->ln_shift_prev, "an arriving split stream needs ln_shift_prev");
+  ARG_CHECK(!out_split || a->ln_shift, "a leaving split stream needs ln_shift");
+  const size_t R = (size_t)a->rows, lo = (size_t)a->row0;
+  // indices the kernel gathers with are checked on the host: rows [row0, row0 + Mpad) are read
+  if (a->pos)
+    for (size_t r = lo; r < lo + (size_t)Mpad; ++r) ARG_CHECK(a->pos[r] >= 0 && a->pos[r] < a->rope_rows, "pos[%zu] out of range", r);
+  if (a->tok_seq)
+    for (size_t r = lo; r < lo + (size_t)Mpad; ++r)
+      ARG_CHECK(a->tok_seq[r] >= -1 && a->tok_seq[r] < a->n_seqs, "tok_seq[%zu] out of range", r);
+  if (vrag_device_count() <= device) {
+    set_error("no HIP device %d visible", device);
+    return VRAG_ERR_NO_DEVICE;
+  }
+  HIP_TRY(hipSetDevice(device));
+
+  // device copies: every buffer is followed by a 4 KiB canary that the launch must leave as it was
+  constexpr size_t kCanary = 4096;
+  constexpr unsigned char kCanaryByte = 0xA5;
+  struct Buf {
+    const void* host;
+    void* host_out;   // null = input only
+    size_t bytes;
+    const char* name;
+    char* dev;
+  };
+  const size_t H = (size_t)std::max(a->hidden, 0), NO = epi == EPI_GEGLU ? (size_t)N / 2 : (size_t)N;
+  std::vector<Buf> bufs;
+  auto add = [&](const void* h, void* h_out, size_t bytes, const char* name) -> int {
+    if (!h) return -1;
+    bufs.push_back(Buf{h, h_out, bytes, name, nullptr});
+    return (int)bufs.size() - 1;
+  };
+  const int iA = add(a->A, nullptr, R * K * 2, "A");
+  const int iW = add(a->W, nullptr, (size_t)N * K * 2, "W");
+  const int ibias = add(a->bias, nullptr, (size_t)N * 4, "bias");
+  const int ils = add(a->ln_s, nullptr, (size_t)N * 4, "ln_s");
+  const int isin = add(a->stats_in, nullptr, (size_t)(K / 64) * R * 8, "stats_in");
+  const int irmu = add(a->res_mu, nullptr, R * 4, "res_mu");
+  const int irrs = add(a->res_rstd, nullptr, R * 4, "res_rstd");
+  const int irg = add(a->res_g, nullptr, (size_t)N * 4, "res_g");
+  const int irb = add(a->res_b, nullptr, (size_t)N * 4, "res_b");
+  const int icos = add(a->rope_cos, nullptr, (size_t)a->rope_rows * 32 * 4, "rope_cos");
+  const int isn = add(a->rope_sin, nullptr, (size_t)a->rope_rows * 32 * 4, "rope_sin");
+  const int ipos = add(a->pos, nullptr, R * 4, "pos");
+  const int itok = add(a->tok_seq, nullptr, R * 4, "tok_seq");
+  const int ilo_in = add(a->lo_in, a->lo_in == a->lo_out ? a->lo_out : nullptr, R * N, "lo_in");
+  const int iof = add(a->out_f32, a->out_f32, R * N * 4, "out_f32");
+  const int iob = add(a->out_bf16, a->out_bf16, R * NO * 2, "out_bf16");
+  const int iq = add(a->q, a->q, R * H * 2, "q");
+  const int ik = add(a->k, a->k, R * H * 2, "k");
+  const int ivt = add(a->vt, a->vt, H * R * 2, "vt");
+  const int imu = add(a->ln_mu, a->ln_mu, R * 4, "ln_mu");
+  const int irs = add(a->ln_rstd, a->ln_rstd, R * 4, "ln_rstd");
+  const int ish = add(a->ln_shift, a->ln_shift, R * 4, "ln_shift");
+  const int ishp = add(a->ln_shift_prev, a->ln_shift_prev, R * 4, "ln_shift_prev");
+  const int ires = add(a->resid_bf16, a->resid_bf16, R * N * 2, "resid_bf16");
+  const int isp = add(a->stats_part, a->stats_part, (size_t)(N / 64) * R * 8, "stats_part");
+  const int ilo_out = a->lo_out == a->lo_in ? ilo_in : add(a->lo_out, a->lo_out, R * N, "lo_out");
+  const int ispl = add(a->splade_rows, a->splade_rows, (size_t)a->n_seqs * N * 4, "splade_rows");
+  auto cleanup = [&]() {
+    for (Buf& b : bufs)
+      if (b.dev) (void)hipFree(b.dev);
+  };
+  hipError_t e = hipSuccess;
+  for (Buf& b : bufs) {
+    if (e == hipSuccess) e = hipMalloc((void**)&b.dev, b.bytes + kCanary);
+    if (e == hipSuccess) e = hipMemcpy(b.dev, b.host, b.bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(b.dev + b.bytes, kCanaryByte, kCanary);
+  }
+  auto dev = [&](int i, size_t offset_bytes) -> char* { return i < 0 ? nullptr : bufs[i].dev + offset_bytes; };
+  GemmParams g{};
+  g.op_dtype = a->f16 ? kOpF16 : kOpBf16;
+  g.M = M;
+  g.N = N;
+  g.K = K;
+  g.act_gelu = a->act_gelu;
+  g.A = (const bf16_t*)dev(iA, lo * K * 2);
+  g.W = (const bf16_t*)dev(iW, 0);
+  g.bias = (const float*)dev(ibias, 0);
+  g.ln_s = (const float*)dev(ils, 0);
+  g.stats_in = (const float*)dev(isin, lo * 8);
+  g.stats_ld = (int)R;
+  g.fin_eps = a->fin_eps;
+  g.res_mu = (const float*)dev(irmu, lo * 4);
+  g.res_rstd = (const float*)dev(irrs, lo * 4);
+  g.res_g = (const float*)dev(irg, 0);
+  g.res_b = (const float*)dev(irb, 0);
+  g.rope_cos = (const float*)dev(icos, 0);
+  g.rope_sin = (const float*)dev(isn, 0);
+  g.pos = (const int*)dev(ipos, lo * 4);
+  g.hidden = (int)H;
+  g.vt_ld = (int)R;
+  g.q_scale = a->q_scale;
+  g.tok_seq = (const int*)dev(itok, lo * 4);
+  g.splade_rows = (unsigned*)dev(ispl, 0);
+  g.lo_in = (const unsigned char*)dev(ilo_in, lo * N);
+  g.lo_out = (unsigned char*)dev(ilo_out, lo * N);
+  g.out_f32 = (float*)dev(iof, lo * N * 4);
+  g.out_bf16 = (bf16_t*)dev(iob, lo * NO * 2);
+  g.q = (bf16_t*)dev(iq, lo * H * 2);
+  g.k = (bf16_t*)dev(ik, lo * H * 2);
+  g.vt = (bf16_t*)dev(ivt, lo * 2);
+  g.ln_mu = (const float*)dev(imu, lo * 4);
+  g.ln_rstd = (const float*)dev(irs, lo * 4);
+  g.ln_shift = (const float*)dev(ish, lo * 4);
+  g.ln_shift_prev = (float*)dev(ishp, lo * 4);
+  g.resid_bf16 = (bf16_t*)dev(ires, lo * N * 2);
+  g.stats_part = (float*)dev(isp, lo * 8);
+  const int thr = gemm_small_m_threshold(-1);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) {
+    (void)gemm_f16_saturated(true);
+    if (a->small_rows >= 0) gemm_small_m_threshold(a->small_rows);
+    e = launch_gemm((GemmEpi)epi, g, 0);
+    const GemmConfig c = gemm_last_config();
+    gemm_small_m_threshold(thr);
+    const int32_t cfg[7] = {c.bm, c.bn, c.wm, c.wn, c.ns, c.hw, c.kch};
+    std::memcpy(a->config, cfg, sizeof(cfg));
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) a->f16_saturated = (int32_t)gemm_f16_saturated(true);
+  std::vector<unsigned char> canary(kCanary);
+  const char* clobbered = nullptr;
+  for (Buf& b : bufs) {
+    if (e != hipSuccess) break;
+    e = hipMemcpy(canary.data(), b.dev + b.bytes, kCanary, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !clobbered && std::any_of(canary.begin(), canary.end(), [](unsigned char v) { return v != kCanaryByte; }))
+      clobbered = b.name;
+    if (e == hipSuccess && b.host_out) e = hipMemcpy(b.host_out, b.dev, b.bytes, hipMemcpyDeviceToHost);
+  }
+  cleanup();
+  if (e != hipSuccess) {
+    set_error("debug gemm run failed: %s", hipGetErrorString(e));
+    return VRAG_ERR_HIP;
+  }
+  if (clobbered) {
+    set_error("debug gemm run: the launch wrote past the end of %s", clobbered);
     return VRAG_ERR_HIP;
   }
   return VRAG_OK;

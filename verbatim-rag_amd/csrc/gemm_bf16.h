@@ -100,6 +100,14 @@ const char* gemm_kernel_name(GemmEpi epi);
 // set_to >= 0 changes the threshold (0 disables the configuration); returns the current value.
 int gemm_small_m_threshold(int set_to);
 
+// Tile configuration of the last launch_gemm on the calling thread (a host-side record written by the launcher; the GEMM unit
+// test checks with it which configuration a shape took): BM x BN tile, WM x WN waves, NS LDS stages, HW K-split waves, KCH
+// chain-ordered K-steps.
+struct GemmConfig {
+  int bm, bn, wm, wn, ns, hw, kch;
+};
+GemmConfig gemm_last_config();
+
 // True when a LayerNorm-folding GEMM over `rows` token rows takes the small-row configuration and therefore finishes the row
 // statistics itself when given `stats_in` (the caller then skips ln_stats_finalize_kernel).
 bool gemm_consumer_finalizes(int rows);

@@ -1170,6 +1170,9 @@ int gemm_small_m_threshold(int set_to) {
   return thr.load();
 }
 
+static thread_local GemmConfig t_last_config{};
+GemmConfig gemm_last_config() { return t_last_config; }
+
 // One instantiation: dynamic-LDS attribute on first use, persistent grid of at most `grid_cap` workgroups.
 template <int EPI, int BM, int BN, int WM, int WN, int NS, typename T, int HW = 0, bool KCH = false>
 static hipError_t launch_cfg(GemmParams p, int grid_cap, hipStream_t stream) {
@@ -1183,6 +1186,7 @@ static hipError_t launch_cfg(GemmParams p, int grid_cap, hipStream_t stream) {
   }
   const int nbm = (p.M + BM - 1) / BM, nbn = p.N / BN;
   p.n_tiles = nbm * nbn;
+  t_last_config = GemmConfig{BM, BN, WM, WN, NS, HW, KCH};
   hipLaunchKernelGGL((gemm_bf16_kernel<EPI, BM, BN, WM, WN, NS, T, HW, KCH>), dim3(std::min(nbm * nbn, grid_cap)), dim3((WM * WN + HW) * 64), SMEM,
                      stream, p);
   return hipGetLastError();
