@@ -329,6 +329,52 @@ int vrag_sparse_index_search_device(vrag_sparse_index* ix, const int64_t* q_indp
                                     int64_t n_map, int64_t id_base, float* out_scores /*[nq,k] device*/,
                                     int64_t* out_ids /*[nq,k] device*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Full-text (BM25) search over raw texts (csrc/fulltext.hip; the reference's Milvus BM25 function over the `text` field,
+ * verbatim_rag/vector_stores/milvus_cloud.py, bm25_k1 = 1.2, bm25_b = 0.75).  The analyzer is this library's own:
+ *   token     = a maximal run of code points that are alphanumeric (Python str.isalnum()) under the committed table
+ *               csrc/unicode_word.inc (tools/gen_unicode_word_table.py; it records its unicodedata version)
+ *   lowercase = str.lower() of each code point where that is ONE code point, else the code point as it is
+ *   term key  = 64-bit FNV-1a of the lowercased token's UTF-8 bytes.  Two distinct terms with one key merge; among 10^7 distinct
+ *               terms the chance that any two share a key is about (10^7)^2 / 2^65 = 2.7e-6.
+ *   Malformed UTF-8 decodes to U+FFFD (not alphanumeric): a byte that cannot start a sequence (one byte), and a lead byte
+ *   with the continuation bytes that follow it (up to as many as it announces) when some are missing, when the sequence is
+ *   an overlong form (C0 / C1 leads, E0 80-9F .., F0 80-8F ..), an encoded surrogate (U+D800-DFFF) or above U+10FFFF.
+ * Statistics over the LIVE rows only (vrag_text_index_set_live; a filter does not change them), recomputed on the first call
+ * after an add or a liveness change: N = live rows, avgdl = fp32(sum of their token counts / N) (a float64 division),
+ * df(t) = live rows containing t.
+ * Score, all fp32 without contraction:  K_d = k1 * ((1 - b) + b * (dl / avgdl))   (1 - b rounded to fp32 first)
+ *   score(d) = sum over the query's distinct terms in ASCENDING key order, from 0, of  w_t * ((tf * (k1 + 1)) / (tf + K_d))
+ *   with k1 + 1 an fp32 sum and w_t the caller's fp32 weight -- the store passes w_t = fp32(count of t in the query * idf64),
+ *   idf64 = ln(1 + (N - df + 0.5) / (df + 0.5)) computed on the host in float64.  The device evaluates no transcendental.
+ * Hits: rows with score > 0 that are live and in `allow`, ordered (score desc, row asc); missing hits id -1, score -inf.
+ * Rows are numbered in insertion order across vrag_text_index_add calls.  Host pointers; every call synchronises. */
+typedef struct vrag_text_index vrag_text_index;
+/* The analyzer alone: token counts per document and the keys of all tokens in text order (n_tokens of them; only written when
+ * n_tokens <= cap, else VRAG_ERR_CAPACITY with counts and n_tokens filled in).  doc_off[0] = 0, at most 4 GiB per call. */
+int vrag_text_tokenize(const uint8_t* text, const int64_t* doc_off /*[n_docs+1]*/, int32_t n_docs, int32_t device, int64_t cap,
+                       int32_t* counts /*[n_docs]*/, uint64_t* keys /*[cap]*/, int64_t* n_tokens);
+int vrag_text_index_create(float k1, float b, int32_t device, vrag_text_index** out);
+void vrag_text_index_destroy(vrag_text_index* ix);
+/* Appends n_docs rows (live) as a new segment.  fold = 1: all segments are folded into one; fold = 0: the first (main)
+ * segment stays and the new rows join the tail segment behind it. */
+int vrag_text_index_add(vrag_text_index* ix, const uint8_t* text, const int64_t* doc_off /*[n_docs+1]*/, int32_t n_docs, int32_t fold);
+/* Liveness of every row: bit r % 32 of words[r / 32]; n_rows must equal the rows added. */
+int vrag_text_index_set_live(vrag_text_index* ix, const uint32_t* words, int64_t n_rows);
+int vrag_text_index_stats(vrag_text_index* ix, int64_t* n_rows, int64_t* n_live, int64_t* sum_dl, int64_t* n_segments,
+                          int64_t* n_postings /* any may be NULL */);
+/* Query analysis on the device: the distinct terms of every query in ascending key order (query q: entries
+ * q_indptr[q] .. q_indptr[q+1]) with their count in the query and their df; n_live = N.  VRAG_ERR_CAPACITY beyond cap terms. */
+int vrag_text_index_query_terms(vrag_text_index* ix, const uint8_t* text, const int64_t* doc_off /*[nq+1]*/, int32_t nq, int64_t cap,
+                                int64_t* q_indptr /*[nq+1]*/, uint64_t* keys /*[cap]*/, int32_t* counts /*[cap]*/, int64_t* df /*[cap]*/,
+                                int64_t* n_live);
+/* Top-k (1 <= k <= 1024) of the queries given as (strictly ascending keys, fp32 weights) per query.  `allow` (host bitmap of
+ * allow_rows rows, or NULL): rows a query may return (filters); rows at or beyond allow_rows -- added after the caller built
+ * its filter -- are not allowed, and deleted rows never are. */
+int vrag_text_index_search(vrag_text_index* ix, const int64_t* q_indptr /*[nq+1]*/, const uint64_t* keys, const float* weights,
+                           int32_t nq, int32_t k, const uint32_t* allow, int64_t allow_rows, float* scores /*[nq,k]*/,
+                           int64_t* ids /*[nq,k]*/);
+
 /* Cross-shard merge of per-shard top-k lists (the reference has no sharding -- this is the step after the
  * all-gather of `[n_lists][nq][k_in]` (fp32 score, global row id) lists, each sorted by (score desc, id asc) with
  * id = -1 entries as a tail).  Writes the first k_out entries of the merged order per query (-inf / -1 padded).

@@ -949,7 +949,7 @@ __global__ void topk_seed_threshold_kernel(const u64* __restrict__ out, int nq, 
   if (q < nq) thr[q] = out[(size_t)q * k + (k - 1)];
 }
 
-static hipError_t launch_topk_merge(const u64* cand, int n_wg, int nq, int k, u64* out, hipStream_t st);
+hipError_t launch_topk_merge(const u64* cand, int n_wg, int nq, int k, u64* out, hipStream_t st);   // also csrc/fulltext.hip
 
 struct Mfma2Plan {
   long long prefix;   // rows of the threshold-seeding pass (0 = single pass)
@@ -2127,7 +2127,7 @@ __global__ __launch_bounds__(256) void topk_merge_lists_kernel(const u64* __rest
   }
 }
 
-static hipError_t launch_topk_merge(const u64* cand, int n_wg, int nq, int k, u64* out, hipStream_t st) {
+hipError_t launch_topk_merge(const u64* cand, int n_wg, int nq, int k, u64* out, hipStream_t st) {
   if (k <= MERGE_KMAX)
     hipLaunchKernelGGL(topk_merge_lists_kernel, dim3(nq), dim3(256), (size_t)256 * k * sizeof(u64), st, cand, n_wg, nq, k, out);
   else

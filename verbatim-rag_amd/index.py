@@ -70,8 +70,8 @@ class HotPathIndex:
                 if not getattr(self.vector_store, "enable_full_text", False):
                     raise ValueError("No search method available")
                 search_type = "full_text"
-        if search_type == "full_text":      # no embeddings, no rrf_k (index.py:622-631)
-            return _Plan(store_kwargs={**common, "search_type": "full_text"})
+        if search_type == "full_text":      # no embeddings, no rrf_k (index.py:622-631); the store's query_batch answers a batch
+            return _Plan(batchable=True, store_kwargs={**common, "search_type": "full_text"})
         return _Plan(embed_dense=search_type in ("dense", "hybrid") and have_d,
                      embed_sparse=search_type in ("sparse", "hybrid") and have_s,
                      batchable=search_type in ("dense", "sparse", "hybrid"),

@@ -363,6 +363,120 @@ class SparseShard:
             pass
 
 
+def _utf8_batch(texts: Sequence[str]) -> Tuple[bytes, np.ndarray]:
+    """Texts back to back as UTF-8 and their `[n + 1]` byte offsets."""
+    raw = [t.encode("utf-8", "surrogatepass") for t in texts]
+    off = np.zeros(len(raw) + 1, np.int64)
+    if raw:
+        np.cumsum([len(r) for r in raw], out=off[1:])
+    return b"".join(raw), off
+
+
+def _bitmap(mask: np.ndarray) -> np.ndarray:
+    """bool per row -> uint32 words, bit r % 32 of word r // 32 (include/vrag_amd.h, vrag_text_index_set_live)."""
+    bits = np.packbits(np.asarray(mask, dtype=bool), bitorder="little")
+    words = np.zeros((len(bits) + 3) // 4 * 4, np.uint8)
+    words[: len(bits)] = bits
+    return words.view(np.uint32)
+
+
+class TextIndex:
+    """BM25 index of raw texts in HBM (`vrag_text_index_*`, csrc/fulltext.hip): the device tokenises, builds the postings,
+    keeps the live-row statistics and scores; the host computes idf in float64 (include/vrag_amd.h states the arithmetic)."""
+
+    def __init__(self, k1: float = 1.2, b: float = 0.75, device: int = 0):
+        self._lib = _lib.load()
+        # a search is two library calls (query analysis: df and N; scoring: K_d): one hold of this lock keeps an `add` or a
+        # `set_live` from another thread out from between them, so both read one snapshot of the statistics
+        self._mu = threading.Lock()
+        self._h = C.c_void_p()
+        self.k1, self.b = float(k1), float(b)
+        _lib.check("vrag_text_index_create", self._lib.vrag_text_index_create(self.k1, self.b, device, C.byref(self._h)))
+
+    def add(self, texts: Sequence[str], fold: bool) -> None:
+        blob, off = _utf8_batch(texts)
+        with self._mu:
+            _lib.check("vrag_text_index_add", self._lib.vrag_text_index_add(
+                self._h, blob, off.ctypes.data_as(C.POINTER(C.c_int64)), len(texts), int(bool(fold))))
+
+    def set_live(self, alive: np.ndarray) -> None:
+        words = _bitmap(alive)
+        with self._mu:
+            _lib.check("vrag_text_index_set_live", self._lib.vrag_text_index_set_live(self._h, words.ctypes.data, len(alive)))
+
+    def stats(self) -> Dict[str, int]:
+        v = [C.c_int64() for _ in range(5)]
+        _lib.check("vrag_text_index_stats", self._lib.vrag_text_index_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("rows", "live", "sum_dl", "segments", "postings"), (x.value for x in v)))
+
+    def query_terms(self, queries: Sequence[str]):
+        """(indptr [Q+1], keys uint64, counts int32, df int64, N): the distinct terms of every query, ascending keys."""
+        blob, off = _utf8_batch(queries)
+        cap = max(1, len(blob))
+        indptr = np.zeros(len(queries) + 1, np.int64)
+        keys, counts, df = np.zeros(cap, np.uint64), np.zeros(cap, np.int32), np.zeros(cap, np.int64)
+        n_live = C.c_int64()
+        _lib.check("vrag_text_index_query_terms", self._lib.vrag_text_index_query_terms(
+            self._h, blob, off.ctypes.data_as(C.POINTER(C.c_int64)), len(queries), cap, indptr.ctypes.data_as(C.POINTER(C.c_int64)),
+            keys.ctypes.data, counts.ctypes.data_as(C.POINTER(C.c_int32)), df.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n_live)))
+        m = int(indptr[-1])
+        return indptr, keys[:m], counts[:m], df[:m], n_live.value
+
+    @staticmethod
+    def weights(counts: np.ndarray, df: np.ndarray, n_live: int) -> np.ndarray:
+        """w_t = fp32(count * idf), idf = ln(1 + (N - df + 0.5) / (df + 0.5)) in float64."""
+        df64 = df.astype(np.float64)
+        idf = np.log(1.0 + (float(n_live) - df64 + 0.5) / (df64 + 0.5))
+        return (counts.astype(np.float64) * idf).astype(np.float32)
+
+    def search(self, queries: Sequence[str], k: int, allow: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """`[Q, k]` scores and rows (-1 = no hit) of a batch of query texts: one device pass for the batch.  `allow`: bool per
+        row; rows beyond its length (added after it was built) are not returned."""
+        Q = len(queries)
+        scores = np.full((Q, k), -np.inf, np.float32)
+        ids = np.full((Q, k), -1, np.int64)
+        if Q == 0:
+            return scores, ids
+        words = _bitmap(allow) if allow is not None else None
+        with self._mu:
+            self._search_locked(queries, k, allow, words, scores, ids)
+        return scores, ids
+
+    def _search_locked(self, queries, k, allow, words, scores, ids) -> None:
+        Q = len(queries)
+        indptr, keys, counts, df, n_live = self.query_terms(queries)
+        w = np.ascontiguousarray(self.weights(counts, df, n_live))
+        keys = np.ascontiguousarray(keys)
+        _lib.check("vrag_text_index_search", self._lib.vrag_text_index_search(
+            self._h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), keys.ctypes.data, w.ctypes.data_as(C.POINTER(C.c_float)), Q, k,
+            words.ctypes.data if words is not None else None, len(allow) if allow is not None else 0,
+            scores.ctypes.data_as(C.POINTER(C.c_float)), ids.ctypes.data_as(C.POINTER(C.c_int64))))
+
+    def close(self):
+        if self._h:
+            self._lib.vrag_text_index_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def tokenize_keys(texts: Sequence[str], device: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """The analyzer alone (`vrag_text_tokenize`): token counts per text and every token's term key, in text order."""
+    lib = _lib.load()
+    blob, off = _utf8_batch(texts)
+    cap = max(1, len(blob))
+    counts = np.zeros(max(1, len(texts)), np.int32)
+    keys = np.zeros(cap, np.uint64)
+    n = C.c_int64()
+    _lib.check("vrag_text_tokenize", lib.vrag_text_tokenize(blob, off.ctypes.data_as(C.POINTER(C.c_int64)), len(texts), device, cap,
+                                                            counts.ctypes.data_as(C.POINTER(C.c_int32)), keys.ctypes.data, C.byref(n)))
+    return counts[: len(texts)], keys[: n.value]
+
+
 _JSON_PLAIN = (str, int, float, bool, type(None))
 _NO_METADATA: Dict[str, Any] = {}
 
@@ -724,12 +838,13 @@ class GpuVectorStore(VectorStore):
     single-GPU store.
     """
 
-    enable_full_text = False
+    enable_full_text = False  # per store: the constructor's `enable_full_text`
 
     SUBSET_CACHE = 4
     K_LIMIT = 1024          # vrag_*_index_search: lists of up to 64 per device pass, longer ones as exact pages of 64
     DEVICE_K = 64           # longest list the device-resident exchange carries (one device pass)
     SPARSE_TAIL_MIN = 65536  # rows a sparse tail segment may always hold before it is folded into the main image
+    TEXT_TAIL_MIN = 65536    # the same for the full-text index's tail segment
 
     def _use_prefilter(self) -> bool:
         if self.dense_dtype != "f32" or self.dense_prefilter is False:
@@ -741,8 +856,11 @@ class GpuVectorStore(VectorStore):
     def __init__(self, dense_dim: Optional[int] = 384, sparse_vocab: Optional[int] = 30522, enable_dense: bool = True,
                  enable_sparse: bool = True, dense_dtype: str = "f32", device: int = 0, distributed: bool = False,
                  group=None, comm=None, payload: str = "sharded", dense_headroom: float = 1.5,
-                 dense_prefilter="auto"):
-        """`dense_prefilter` (fp32 rows only): keep a bf16 image of the rows beside them so that every search streams
+                 dense_prefilter="auto", enable_full_text: bool = False, bm25_k1: float = 1.2, bm25_b: float = 0.75):
+        """`enable_full_text`: BM25 keyword search over the raw texts (milvus_cloud.py: bm25_k1 = 1.2, bm25_b = 0.75),
+        `search_type="full_text"` and the third leg of a weighted hybrid search; the texts are tokenised, indexed and
+        scored on the device (`TextIndex`).  Off by default; not yet available on a sharded store.
+        `dense_prefilter` (fp32 rows only): keep a bf16 image of the rows beside them so that every search streams
         half (small batches) or a fraction (large ones) of the bytes of the full fp32 scan and returns the same bits (`DenseShard`).  It costs
         +50 % of the dense rows' HBM.  "auto" (default) = on where the image route exists (dim % 64 == 0 and <= 768,
         csrc/topk.hip `prefilter_route_ok`), True / False force it; the choice is kept in a saved store's manifest."""
@@ -752,7 +870,12 @@ class GpuVectorStore(VectorStore):
             raise ValueError(f"dense_dtype must be 'f32' or 'bf16' (got {dense_dtype!r})")
         if payload not in ("sharded", "replicated"):
             raise ValueError(f"payload must be 'sharded' or 'replicated' (got {payload!r})")
+        if not enable_dense and not enable_sparse and not enable_full_text:      # milvus_base.py:54-56
+            raise ValueError("At least one of enable_dense, enable_sparse, or enable_full_text must be True")
+        if enable_full_text and (distributed or (comm is not None and comm.world > 1)):
+            raise ValueError("enable_full_text is not available on a sharded store (global df / N / avgdl need a collective)")
         self.enable_dense, self.enable_sparse = enable_dense, enable_sparse
+        self.enable_full_text, self.bm25_k1, self.bm25_b = bool(enable_full_text), float(bm25_k1), float(bm25_b)
         self.dense_dim, self.sparse_vocab, self.dense_dtype, self.device = dense_dim, sparse_vocab, dense_dtype, device
         self.dense_headroom = max(1.0, float(dense_headroom))
         if dense_prefilter not in ("auto", True, False):
@@ -787,6 +910,10 @@ class GpuVectorStore(VectorStore):
         self._dense_flushed = 0      # local rows already in it
         self._sparse_parts: List[Tuple[Any, int, int]] = []   # (SELL image, first local row, rows): main [+ tail]
         self._sparse_flushed = 0
+        self._text: Optional[TextIndex] = None      # BM25 index of the raw texts (local rows), main [+ tail] segments
+        self._text_flushed = 0
+        self._text_main = 0          # rows in its main segment
+        self._text_live_stale = False
         self._main_rows: np.ndarray = np.zeros(0, np.int64)   # _owned.data at the last flush
         self._owned_dev = None       # the same table in HBM (RCCL exchange): (torch tensor, rows)
         self._dirty = False
@@ -812,8 +939,9 @@ class GpuVectorStore(VectorStore):
             self._subsets.clear()
             self._dense = None              # released by their last user (DenseShard / SparseShard.__del__)
             self._sparse_parts = []
+            self._text = None
             self._owned_dev = None
-            self._dense_flushed = self._sparse_flushed = 0
+            self._dense_flushed = self._sparse_flushed = self._text_flushed = self._text_main = 0
             self._dirty = True
             if self._comm is not None and self._owns_comm:
                 self._comm.close()
@@ -918,6 +1046,7 @@ class GpuVectorStore(VectorStore):
                 rows = self._id_rows.get(key)
                 if rows is not None:
                     alive[rows] = False
+            self._text_live_stale = True
             self._drop_subsets()
 
     def _sparse_slice(self, a: int, b: int):
@@ -955,6 +1084,15 @@ class GpuVectorStore(VectorStore):
                     tail = SparseShard(self.sparse_vocab, *self._sparse_slice(main_n, n), device=self.device)
                     self._sparse_parts = [main, (tail, main_n, n - main_n)]
                 self._sparse_flushed = n
+            if self.enable_full_text and n > self._text_flushed:
+                if self._text is None:
+                    self._text = TextIndex(self.bm25_k1, self.bm25_b, self.device)
+                fold = self._text_main == 0 or n - self._text_main > max(self.TEXT_TAIL_MIN, self._text_main // 4)
+                self._text.add(self._texts[self._text_flushed:n], fold=fold)
+                if fold:
+                    self._text_main = n
+                self._text_flushed = n
+                self._text_live_stale = True
             if self._comm is not None and self._comm.on_gpu and n:
                 import torch
 
@@ -1217,8 +1355,36 @@ class GpuVectorStore(VectorStore):
             score_out[which, :want] = np.where(rows >= 0, scores, np.float32(0.0))
         return rows_out, score_out
 
+    def _text_topk(self, queries: Sequence[str], limit: int, mask: Optional[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
+        """BM25 top-`limit` of a batch of query texts among the rows that pass `mask` -- `rows [Q, limit]` (-1 = no hit)
+        and fp32 scores, as `_topk_rows`.  One device pass for the batch; the filter is a row bitmap the scoring kernel
+        reads (no subset index), the statistics are those of the live rows."""
+        if limit > self.K_LIMIT:
+            raise ValueError(f"GpuVectorStore: a search may ask for at most {self.K_LIMIT} rows per method "
+                             f"(got {limit}; hybrid search asks for 2 * top_k)")
+        with self._mu:
+            self._flush()
+            text, n = self._text, self._text_flushed
+            if text is not None and self._text_live_stale:     # the statistics follow the deletes at the next search
+                text.set_live(self._alive.data[:n])
+                self._text_live_stale = False
+        Q = len(queries)
+        rows_out = np.full((Q, limit), -1, np.int64)
+        score_out = np.zeros((Q, limit), np.float32)
+        if text is None or n == 0 or Q == 0:
+            return rows_out, score_out
+        # rows inserted after the caller built its mask lie beyond it: the library does not return them (nor any row an
+        # insert from another thread adds while this search runs, whatever `n` was)
+        if mask is not None and not mask.any():
+            return rows_out, score_out
+        scores, rows = text.search([q or "" for q in queries], limit, mask)
+        found = rows >= 0
+        rows_out[:] = np.where(found, rows, -1)
+        score_out[:] = np.where(found, scores, np.float32(0.0))
+        return rows_out, score_out
+
     def _search_batch(self, kind: str, queries: Sequence[Any], limit: int, mask: Optional[np.ndarray]) -> List[List[dict]]:
-        rows, scores = self._topk_rows(kind, queries, limit, mask)
+        rows, scores = self._text_topk(queries, limit, mask) if kind == "full_text" else self._topk_rows(kind, queries, limit, mask)
         return [[self._hit(int(r), float(v)) for r, v in zip(rows[i], scores[i]) if r >= 0] for i in range(len(queries))]
 
     def _results_batch(self, rows: np.ndarray, distances: np.ndarray) -> List[List[SearchResult]]:
@@ -1228,19 +1394,34 @@ class GpuVectorStore(VectorStore):
         return [[SearchResult(id=ids[r], score=float(d), metadata=dict(pay[r][2]), text=pay[r][0], enhanced_text=pay[r][1])
                  for r, d in zip(rows[i].tolist(), distances[i].tolist()) if r >= 0] for i in range(rows.shape[0])]
 
-    def _hybrid_batch(self, dq, sq, top_k, mask, weights, rrf_k) -> List[List[SearchResult]]:
-        """Both methods for all queries, then weighted RRF: one array merge for the whole batch, or query by query when
-        an id is falsy (such hits keep their rank but are skipped)."""
+    def _hybrid_batch(self, queries: Dict[str, Sequence[Any]], top_k, mask, weights, rrf_k) -> List[List[SearchResult]]:
+        """Every method of `queries` (method -> the batch's queries, in fusion order) for all queries, 2 * top_k rows each,
+        then weighted RRF: one array merge for the whole batch, or query by query when an id is falsy (such hits keep
+        their rank but are skipped).  A failing full-text leg is left out with a warning, as in `_hybrid_search_with_weights`;
+        with one method left, its first top_k are the answer."""
         limit = top_k * 2
-        rows_d, sc_d = self._topk_rows("dense", dq, limit, mask)
-        rows_s, sc_s = self._topk_rows("sparse", sq, limit, mask)
+        lists: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}
+        for m, q in queries.items():
+            if m != "full_text":
+                lists[m] = self._topk_rows(m, q, limit, mask)
+                continue
+            try:                                                   # as the per-query path (milvus_base.py:420-431)
+                lists[m] = self._text_topk(q, limit, mask)
+            except Exception as e:
+                logger.warning("Full text search failed: %s, excluding from hybrid", e)
+        Q = len(next(iter(queries.values())))
+        if not lists:
+            logger.warning("Hybrid search: no valid methods executed after validation")
+            return [[] for _ in range(Q)]
+        if len(lists) == 1:                                        # one method: its first top_k
+            rows, scores = next(iter(lists.values()))
+            return self._results_batch(rows[:, :top_k], scores[:, :top_k])
         if self._all_ids_truthy:
-            rows, dist = rrf_merge_rows({"dense": rows_d, "sparse": rows_s}, top_k, weights, rrf_k)
+            rows, dist = rrf_merge_rows({m: r for m, (r, _s) in lists.items()}, top_k, weights, rrf_k)
             return self._results_batch(rows, dist)
         out = []
-        for i in range(len(dq)):
-            rbm = {"dense": [self._hit(int(r), float(v)) for r, v in zip(rows_d[i], sc_d[i]) if r >= 0],
-                   "sparse": [self._hit(int(r), float(v)) for r, v in zip(rows_s[i], sc_s[i]) if r >= 0]}
+        for i in range(Q):
+            rbm = {m: [self._hit(int(r), float(v)) for r, v in zip(rows[i], sc[i]) if r >= 0] for m, (rows, sc) in lists.items()}
             out.append(self._results(merge_hybrid_results(rbm, top_k, weights, rrf_k)))
         return out
 
@@ -1274,16 +1455,18 @@ class GpuVectorStore(VectorStore):
             weights = sanitize_hybrid_weights(hybrid_weights)
             if "full_text" in weights and not self.enable_full_text:
                 weights = {k: v for k, v in weights.items() if k != "full_text"}
-            d_some, s_some = [q is not None for q in dq], [q is not None for q in sq]
-            uniform = (all(d_some) or not any(d_some)) and (all(s_some) or not any(s_some))
-            use_d, use_s = "dense" in weights and all(d_some), "sparse" in weights and all(s_some)
-            if not weights or not uniform or not (use_d or use_s):
+            d_some, s_some, t_some = [q is not None for q in dq], [q is not None for q in sq], [q is not None for q in tq]
+            uniform = all(all(x) or not any(x) for x in (d_some, s_some, t_some))
+            use = {"dense": ("dense" in weights and all(d_some), dq), "sparse": ("sparse" in weights and all(s_some), sq),
+                   "full_text": ("full_text" in weights and all(t_some), tq)}
+            queries = {m: q for m, (on, q) in use.items() if on}
+            if not weights or not uniform or not queries:
                 return [single(i) for i in range(n)]          # mixed / degenerate batches: the per-query code decides
             mask = self._mask(filter)
-            if use_d and use_s:
-                return self._hybrid_batch(dq, sq, top_k, mask, weights, rrf_k)
-            rows, scores = self._topk_rows("dense" if use_d else "sparse", dq if use_d else sq, top_k * 2, mask)
-            return self._results_batch(rows[:, :top_k], scores[:, :top_k])   # one method: its first top_k
+            return self._hybrid_batch(queries, top_k, mask, weights, rrf_k)
+        if search_type == "full_text" and self.enable_full_text and all(q for q in tq):
+            mask = self._mask(filter)
+            return self._results_batch(*self._text_topk(tq, top_k, mask))
         if search_type == "dense" and all(is_set(q) for q in dq):
             mask = self._mask(filter)
             return self._results_batch(*self._topk_rows("dense", dq, top_k, mask))
@@ -1293,7 +1476,7 @@ class GpuVectorStore(VectorStore):
         if search_type == "hybrid" and all(is_set(q) for q in dq) and all(is_set(q) for q in sq):
             mask = self._mask(filter)
             try:
-                return self._hybrid_batch(dq, sq, top_k, mask, {"dense": 0.5, "sparse": 0.5}, rrf_k)
+                return self._hybrid_batch({"dense": dq, "sparse": sq}, top_k, mask, {"dense": 0.5, "sparse": 0.5}, rrf_k)
             except Exception as e:
                 if self._world > 1:
                     raise                                  # ranks must not diverge into different collectives
@@ -1306,6 +1489,8 @@ class GpuVectorStore(VectorStore):
         """milvus_base.py:189-313.  `top_k` (2 * top_k in hybrid mode) may not exceed `K_LIMIT` = 1024."""
         if hybrid_weights is not None:
             return self._hybrid_search_with_weights(dense_query, sparse_query, text_query, top_k, filter, hybrid_weights, rrf_k)
+        if search_type == "full_text" and text_query and self.enable_full_text:   # milvus_base.py:229-230
+            return self._results(self._search("full_text", text_query, top_k, self._mask(filter)))
         if not _is_given(dense_query) and not _is_given(sparse_query):
             return self._filter_only_query(filter, top_k)
         mask = self._mask(filter)
@@ -1347,6 +1532,11 @@ class GpuVectorStore(VectorStore):
             rbm["dense"] = self._search("dense", dense_query, top_k * 2, mask)
         if "sparse" in hybrid_weights and sparse_query is not None:
             rbm["sparse"] = self._search("sparse", sparse_query, top_k * 2, mask)
+        if "full_text" in hybrid_weights and text_query is not None:           # milvus_base.py:420-431
+            try:
+                rbm["full_text"] = self._search("full_text", text_query, top_k * 2, mask)
+            except Exception as e:
+                logger.warning("Full text search failed: %s, excluding from hybrid", e)
         if len(rbm) == 0:
             logger.warning("Hybrid search: no valid methods executed after validation")
             return []
@@ -1418,7 +1608,8 @@ class GpuVectorStore(VectorStore):
                 metas = {"empty_rows": len(metas)}                             # nothing to store per row
             head = {"format": self.FORMAT, "world": self._world, "dense_dim": self.dense_dim, "sparse_vocab": self.sparse_vocab,
                     "enable_dense": self.enable_dense, "enable_sparse": self.enable_sparse, "dense_dtype": self.dense_dtype,
-                    "dense_prefilter": self.dense_prefilter, "rows": len(ids), "documents": list(self._documents.values())}
+                    "dense_prefilter": self.dense_prefilter, "enable_full_text": self.enable_full_text, "bm25_k1": self.bm25_k1,
+                    "bm25_b": self.bm25_b, "rows": len(ids), "documents": list(self._documents.values())}
             r = self._rank
 
             def put_arrays(tmp):
@@ -1487,7 +1678,8 @@ class GpuVectorStore(VectorStore):
         st = cls(dense_dim=head["dense_dim"], sparse_vocab=head["sparse_vocab"], enable_dense=head["enable_dense"],
                  enable_sparse=head["enable_sparse"], dense_dtype=head["dense_dtype"], device=device,
                  distributed=distributed, group=group, comm=comm, payload=payload,
-                 dense_prefilter=head.get("dense_prefilter", "auto"))
+                 dense_prefilter=head.get("dense_prefilter", "auto"), enable_full_text=bool(head.get("enable_full_text", False)),
+                 bm25_k1=head.get("bm25_k1", 1.2), bm25_b=head.get("bm25_b", 0.75))
         n = len(ids)
         for owned, *_ in shards:
             if len(owned) and (owned.min() < 0 or owned.max() >= n):
