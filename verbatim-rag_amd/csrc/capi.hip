@@ -18,6 +18,7 @@
 #include <map>
 #include "common.h"
 #include "gemm_bf16.h"
+#include "host_util.h"
 #include "norm_heads.h"
 
 namespace vrag {
@@ -196,11 +197,6 @@ __global__ __launch_bounds__(256) void splade_compact_kernel(const float* __rest
   if (tid == 255) counts[s] = off;   // the last thread's end offset = the row's total (its range may be empty: off = everything before it)
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
 struct Layer {
   float* attn_norm = nullptr;
   bf16_t* wqkv = nullptr;
@@ -366,23 +362,6 @@ struct vrag_encoder {
 };
 
 namespace {
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) {                                                                    \
-      set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e));          \
-      return VRAG_ERR_HIP;                                                                     \
-    }                                                                                          \
-  } while (0)
-
-#define ARG_CHECK(cond, ...)      \
-  do {                            \
-    if (!(cond)) {                \
-      set_error(__VA_ARGS__);     \
-      return VRAG_ERR_INVALID;    \
-    }                             \
-  } while (0)
 
 template <typename T>
 int dev_alloc(vrag_encoder* e, T** out, size_t count, bool zero = true) {

@@ -19,10 +19,9 @@
 #include <mutex>
 
 #include "common.h"
+#include "host_util.h"
 
 namespace vrag {
-void set_error(const char* fmt, ...);
-
 namespace {
 
 struct Rccl {

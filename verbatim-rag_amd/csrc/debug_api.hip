@@ -11,32 +11,13 @@
 
 #include "attention.h"
 #include "gemm_bf16.h"
+#include "host_util.h"
 #include "norm_heads.h"
 #include "qkv_attn.h"
 
-namespace vrag {
-void set_error(const char* fmt, ...);
-}
 using namespace vrag;
 
 static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t _e = (expr);                                                                    \
-    if (_e != hipSuccess) {                                                                    \
-      set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e));          \
-      return VRAG_ERR_HIP;                                                                     \
-    }                                                                                          \
-  } while (0)
-
-#define ARG_CHECK(cond, ...)      \
-  do {                            \
-    if (!(cond)) {                \
-      set_error(__VA_ARGS__);     \
-      return VRAG_ERR_INVALID;    \
-    }                             \
-  } while (0)
 
 extern "C" {
 

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "common.h"
+#include "host_util.h"
 
 // Every fp32 operation of this file is rounded on its own: no a * b + c is fused into an FMA (HIP's default is
 // -ffp-contract=fast, and the __fadd_rn / __fmul_rn helpers are plain operators compiled under it), so the host restatement
@@ -31,7 +32,6 @@
 #pragma clang fp contract(off)
 
 namespace vrag {
-void set_error(const char* fmt, ...);
 hipError_t launch_topk_merge(const u64* cand, int n_wg, int nq, int k, u64* out, hipStream_t st);   // csrc/topk.hip
 
 namespace uw {
@@ -601,57 +601,7 @@ __global__ void ft_bound_kernel(const u64* __restrict__ page, int nq, int kk, u6
 
 using namespace vrag;
 
-#define HIP_TRY(expr)                                                                 \
-  do {                                                                                \
-    hipError_t _e = (expr);                                                           \
-    if (_e != hipSuccess) {                                                           \
-      set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-      return VRAG_ERR_HIP;                                                            \
-    }                                                                                 \
-  } while (0)
-#define ARG_CHECK(cond, ...)   \
-  do {                         \
-    if (!(cond)) {             \
-      set_error(__VA_ARGS__);  \
-      return VRAG_ERR_INVALID; \
-    }                          \
-  } while (0)
-
 namespace {
-
-// Device allocation freed with its owner (temporaries of one call; growable buffers of a handle).
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
-  DevBuf& operator=(DevBuf&& o) noexcept {
-    if (this != &o) {
-      reset();
-      p = o.p, bytes = o.bytes;
-      o.p = nullptr, o.bytes = 0;
-    }
-    return *this;
-  }
-  ~DevBuf() { reset(); }
-  void reset() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  hipError_t alloc(size_t n) {   // fresh contents; at least 16 bytes so that empty arrays are valid pointers
-    reset();
-    n = std::max<size_t>(n, 16);
-    hipError_t e = hipMalloc(&p, n);
-    if (e == hipSuccess) bytes = n;
-    else p = nullptr;
-    return e;
-  }
-  hipError_t reserve(size_t n) { return n <= bytes ? hipSuccess : alloc(n + n / 2); }   // contents not kept
-  template <typename T> T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 struct Segment {
   long long row_lo = 0, n_rows = 0, n_keys = 0, n_post = 0;

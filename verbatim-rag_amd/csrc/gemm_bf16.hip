@@ -27,6 +27,7 @@
 // -> 8-byte 16-bit / 16-byte fp32 row-major stores, and RoPE's (d, d+32) / GeGLU's (x1, x2)
 // partners sit in the same lane and register of acc[nj][rt] / acc[nj+2][rt].
 #include "gemm_bf16.h"
+#include "host_util.h"
 
 #include <atomic>
 
@@ -1177,13 +1178,8 @@ GemmConfig gemm_last_config() { return t_last_config; }
 template <int EPI, int BM, int BN, int WM, int WN, int NS, typename T, int HW = 0, bool KCH = false>
 static hipError_t launch_cfg(GemmParams p, int grid_cap, hipStream_t stream) {
   constexpr int SMEM = NS * (BM + BN) * BK * 2;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kernel<EPI, BM, BN, WM, WN, NS, T, HW, KCH>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
+  const hipError_t e = set_max_dynamic_lds<&gemm_bf16_kernel<EPI, BM, BN, WM, WN, NS, T, HW, KCH>>(SMEM);
+  if (e != hipSuccess) return e;
   const int nbm = (p.M + BM - 1) / BM, nbn = p.N / BN;
   p.n_tiles = nbm * nbn;
   t_last_config = GemmConfig{BM, BN, WM, WN, NS, HW, KCH};

@@ -29,6 +29,7 @@
 // row, so the sequences of a group need not be neighbours in the packed buffer: the engine packs a micro-batch's sequences best fit
 // decreasing (capi.hip), whatever order they arrived in.
 // Sequences longer than 512 tokens, BERT-family encoders, launch-bound batches and poorly filled batches keep the two-kernel path.
+#include "host_util.h"
 #include "qkv_attn.h"
 
 #include <cstdlib>
@@ -503,13 +504,8 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
 
 template <bool LOCAL, bool FOLD, typename T>
 static hipError_t launch_t(const QkvAttnParams& p, hipStream_t stream) {
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&qkv_attn_kernel<LOCAL, FOLD, T>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, QA_SMEM);
-    if (e != hipSuccess) return e;
-    attr = true;
-  }
+  const hipError_t e = set_max_dynamic_lds<&qkv_attn_kernel<LOCAL, FOLD, T>>(QA_SMEM);
+  if (e != hipSuccess) return e;
   const int grid = ((p.n_groups + 7) / 8) * 8 * p.nh;
   hipLaunchKernelGGL((qkv_attn_kernel<LOCAL, FOLD, T>), dim3(grid), dim3(512), QA_SMEM, stream, p);
   return hipGetLastError();

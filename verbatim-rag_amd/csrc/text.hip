@@ -13,8 +13,9 @@
 
 #include <cstdint>
 
+#include "host_util.h"
+
 namespace vrag {
-void set_error(const char* fmt, ...);
 
 // Length in bytes of the white-space character that starts at p[0] (n bytes are readable), 0 if it is not white space.
 __device__ __forceinline__ int space_len(const unsigned char* p, long long n) {

@@ -39,9 +39,9 @@
 
 #include "common.h"
 #include "gemm_bf16.h"
+#include "host_util.h"
 
 namespace vrag {
-void set_error(const char* fmt, ...);
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 // u64 / orderable / unorderable / make_key: common.h (the tiled batched search builds the same keys in a GEMM epilogue)
@@ -988,116 +988,78 @@ static int dense_n_wg(int dtype, int dim, int nq, int k, long long size) {
   return (int)std::max<long long>(1, (size + per - 1) / per);
 }
 
+// The two-pass form of the exact and mfma2 kernels: an exact top-k of a prefix seeds a per-query entry threshold, then the main
+// pass covers the rest of the shard.  pass(lo, hi, rows per workgroup, workgroups, candidate lists) launches one row range.
+template <typename Pass>
+static hipError_t dense_seeded_passes(long long n, int nq, int k, u64* cand, hipStream_t st, u64* thr, u64* out, Pass pass) {
+  hipError_t e = hipMemsetAsync(thr, 0, (size_t)nq * sizeof(u64), st);
+  if (e != hipSuccess) return e;
+  const Mfma2Plan pl = dense_mfma2_plan(n);
+  if (pl.prefix > 0) {   // seeding pass: exact top-k of the first `prefix` rows -> per-query entry threshold for the main pass
+    e = pass(0, pl.prefix, 128, pl.n_wg0, cand);
+    if (e == hipSuccess) e = launch_topk_merge(cand, pl.n_wg0, nq, k, out, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(topk_seed_threshold_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, out, nq, k, thr);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+  }
+  return pass(pl.prefix, n, pl.per1, pl.n_wg1, cand + (size_t)pl.n_wg0 * nq * k);
+}
+
 // all passes of one search: query tiles of 4 (a final tile of 1 query uses the register path)
 static hipError_t dense_launch_all(int dtype, const void* rows, long long n, int dim, const float* dq, int nq, int k,
                                    u64* cand, int n_wg, hipStream_t st, u64* thr, u64* out, const u64* bound = nullptr,
                                    int split = 0, const unsigned* gate = nullptr) {
   const int qpp = split ? MQ / 2 : MQ;
+  constexpr int kLds = 160 * 1024;
   if (bound && dense_use_mfma(dtype, dim, nq, k)) return hipErrorInvalidValue;   // pages run with k = KMAX: scalar path only
   if (!bound && dense_use_exact(dtype, dim, k)) {
-    hipError_t me = hipMemsetAsync(thr, 0, (size_t)nq * sizeof(u64), st);
-    if (me != hipSuccess) return me;
     const int qbytes = ((XQ * (dim * 4 + 16) + 1023) / 1024) * 1024;
     const bool deep = qbytes + 6 * 16384 <= 160 * 1024;               // dim <= 384: six ring slots, else three
     const size_t ldsx = (size_t)qbytes + (deep ? 6 : 3) * 16384;
-    static bool attrx = false;
-    if (!attrx) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_topk_exact_kernel<3>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_topk_exact_kernel<6>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      attrx = true;
-    }
     const float* r32 = reinterpret_cast<const float*>(rows);
     const bool regq = dim == 768 || dim == 384;   // queries in registers; other dims keep them in LDS
     const size_t lds2 = (size_t)4 * X2SLOTS * 4096 + (size_t)256 * k * 8;
-    if (regq) {
-      static bool attrx2 = false;
-      if (!attrx2) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_topk_exact2_kernel<24>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_topk_exact2_kernel<12>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attrx2 = true;
-      }
-    }
-    auto pass = [&](long long lo, long long hi, int per, int wgs, u64* cand_base) -> hipError_t {
+    const hipError_t e = regq ? (dim == 768 ? set_max_dynamic_lds<&dense_topk_exact2_kernel<24>>(kLds) : set_max_dynamic_lds<&dense_topk_exact2_kernel<12>>(kLds))
+                              : (deep ? set_max_dynamic_lds<&dense_topk_exact_kernel<6>>(kLds) : set_max_dynamic_lds<&dense_topk_exact_kernel<3>>(kLds));
+    if (e != hipSuccess) return e;
+    return dense_seeded_passes(n, nq, k, cand, st, thr, out, [&](long long lo, long long hi, int per, int wgs, u64* cand_base) -> hipError_t {
       for (int q0 = 0; q0 < nq; q0 += XQ) {
         if (regq && dim == 768) hipLaunchKernelGGL(dense_topk_exact2_kernel<24>, dim3(wgs), dim3(256), lds2, st, r32, lo, hi, dq, nq, q0, k, cand_base, per, thr, gate);
         else if (regq) hipLaunchKernelGGL(dense_topk_exact2_kernel<12>, dim3(wgs), dim3(256), lds2, st, r32, lo, hi, dq, nq, q0, k, cand_base, per, thr, gate);
         else if (deep) hipLaunchKernelGGL(dense_topk_exact_kernel<6>, dim3(wgs), dim3(256), ldsx, st, r32, lo, hi, dim, dq, nq, q0, k, cand_base, per, thr, gate);
         else hipLaunchKernelGGL(dense_topk_exact_kernel<3>, dim3(wgs), dim3(256), ldsx, st, r32, lo, hi, dim, dq, nq, q0, k, cand_base, per, thr, gate);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) return le;
       }
       return hipSuccess;
-    };
-    const Mfma2Plan pl = dense_mfma2_plan(n);
-    if (pl.prefix > 0) {   // seeding pass: exact top-k of the first rows -> per-query entry threshold for the main pass
-      hipError_t e = pass(0, pl.prefix, 128, pl.n_wg0, cand);
-      if (e == hipSuccess) e = launch_topk_merge(cand, pl.n_wg0, nq, k, out, st);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(topk_seed_threshold_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, out, nq, k, thr);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    return pass(pl.prefix, n, pl.per1, pl.n_wg1, cand + (size_t)pl.n_wg0 * nq * k);
+    });
   }
   if (dense_use_mfma(dtype, dim, nq, k) && dense_use_mfma2(dim)) {
-    hipError_t me = hipMemsetAsync(thr, 0, (size_t)nq * sizeof(u64), st);
-    if (me != hipSuccess) return me;
     const size_t lds2 = (size_t)M2SLOTS * 16384 + (size_t)256 * k * 8;
-    static bool attr2 = false;
-    if (!attr2) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_topk_mfma2_kernel<6>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_topk_mfma2_kernel<12>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_topk_mfma2_kernel<16>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      attr2 = true;
-    }
+    const hipError_t e = dim == 384 ? set_max_dynamic_lds<&dense_topk_mfma2_kernel<6>>(kLds)
+                         : dim == 768 ? set_max_dynamic_lds<&dense_topk_mfma2_kernel<12>>(kLds) : set_max_dynamic_lds<&dense_topk_mfma2_kernel<16>>(kLds);
+    if (e != hipSuccess) return e;
     const bf16_t* r16 = reinterpret_cast<const bf16_t*>(rows);
-    auto pass = [&](long long lo, long long hi, int per, int wgs, u64* cand_base) -> hipError_t {
+    return dense_seeded_passes(n, nq, k, cand, st, thr, out, [&](long long lo, long long hi, int per, int wgs, u64* cand_base) -> hipError_t {
       for (int q0 = 0; q0 < nq; q0 += qpp) {
         if (dim == 384) hipLaunchKernelGGL(dense_topk_mfma2_kernel<6>, dim3(wgs), dim3(256), lds2, st, r16, lo, hi, dq, nq, q0, k, cand_base, per, thr, split);
         else if (dim == 768) hipLaunchKernelGGL(dense_topk_mfma2_kernel<12>, dim3(wgs), dim3(256), lds2, st, r16, lo, hi, dq, nq, q0, k, cand_base, per, thr, split);
         else hipLaunchKernelGGL(dense_topk_mfma2_kernel<16>, dim3(wgs), dim3(256), lds2, st, r16, lo, hi, dq, nq, q0, k, cand_base, per, thr, split);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) return le;
       }
       return hipSuccess;
-    };
-    const Mfma2Plan pl = dense_mfma2_plan(n);
-    if (pl.prefix > 0) {
-      // seeding pass: exact top-k of the first `prefix` rows -> per-query entry threshold for the main pass
-      hipError_t e = pass(0, pl.prefix, 128, pl.n_wg0, cand);
-      if (e == hipSuccess) e = launch_topk_merge(cand, pl.n_wg0, nq, k, out, st);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(topk_seed_threshold_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, out, nq, k, thr);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-    } else if (pl.prefix > 0) {
-      hipError_t e = pass(0, pl.prefix, 128, pl.n_wg0, cand);
-      if (e != hipSuccess) return e;
-    }
-    return pass(pl.prefix, n, pl.per1, pl.n_wg1, cand + (size_t)pl.n_wg0 * nq * k);
+    });
   }
   if (dense_use_mfma(dtype, dim, nq, k)) {
     const size_t lds = (size_t)MQ * dim * 2 + MSLOTS * 16384 + (size_t)256 * k * 8;
-    static bool attr = false;
-    if (!attr) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dense_topk_mfma_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      attr = true;
-    }
+    const hipError_t e = set_max_dynamic_lds<&dense_topk_mfma_kernel>(kLds);
+    if (e != hipSuccess) return e;
     for (int q0 = 0; q0 < nq; q0 += qpp) {
       hipLaunchKernelGGL(dense_topk_mfma_kernel, dim3(n_wg), dim3(256), lds, st, reinterpret_cast<const bf16_t*>(rows), n,
                          dim, dq, nq, q0, k, cand, split);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
+      const hipError_t le = hipGetLastError();
+      if (le != hipSuccess) return le;
     }
     return hipSuccess;
   }
@@ -2215,57 +2177,35 @@ __global__ void topk_fill_empty_kernel(float* __restrict__ scores, long long* __
 
 using namespace vrag;
 
-#define HIP_TRY(expr)                                                                 \
-  do {                                                                                \
-    hipError_t _e = (expr);                                                           \
-    if (_e != hipSuccess) {                                                           \
-      set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-      return VRAG_ERR_HIP;                                                            \
-    }                                                                                 \
-  } while (0)
-#define ARG_CHECK(cond, ...)   \
-  do {                         \
-    if (!(cond)) {             \
-      set_error(__VA_ARGS__);  \
-      return VRAG_ERR_INVALID; \
-    }                          \
-  } while (0)
-
 struct vrag_dense_index {
   int dim = 0, dtype = 0, device = 0;
   int64_t capacity = 0, size = 0;
-  void* rows = nullptr;
-  float* stage = nullptr;  // device fp32 staging for add()
+  DevArray<char> rows;     // [capacity + 512][dim] bf16 (dtype 0) or fp32 (dtype 1)
+  DevArray<float> stage;   // device fp32 staging for add()
   size_t stage_rows = 0;
   hipStream_t stream = nullptr;
   std::mutex mu;
   // scratch (grown on demand)
-  float* d_q = nullptr;
-  size_t d_q_elems = 0;
-  u64 *d_cand = nullptr, *d_out = nullptr, *d_bound = nullptr;   // d_bound: per-query page bound (k > KMAX)
-  size_t d_cand_elems = 0, d_out_elems = 0, d_bound_elems = 0;
+  DevArray<float> d_q;
+  DevArray<u64> d_cand, d_out, d_bound;   // d_bound: per-query page bound (k > KMAX)
   // tiled batched search (batches over bf16 rows: kTiledMin*): W operand of the score GEMM, candidate buffers, thresholds, flags
-  bf16_t* d_tw = nullptr;
-  u64 *d_tbuf = nullptr, *d_tthr = nullptr, *d_tdir = nullptr;   // d_tdir: [nq][rows of the first stage] one key per row
-  u64* d_tres = nullptr;   // [TRESCUE_SLICES][nq][k] per-slice lists of the rescue pass
-  size_t d_tres_elems = 0;
-  float* d_tthrs = nullptr;
-  unsigned* d_tcnt = nullptr;   // [nq] counters followed by [nq] overflow flags
-  size_t d_tw_elems = 0, d_tbuf_elems = 0, d_tthr_elems = 0, d_tthrs_elems = 0, d_tcnt_elems = 0, d_tdir_elems = 0;
-  u64* d_pfb = nullptr;            // [nq][PFCAP] candidate keys of the batch collect route (round 6: prefilter_batch_enqueue, <= 64 queries)
-  size_t d_pfb_elems = 0;
+  DevArray<bf16_t> d_tw;
+  DevArray<u64> d_tbuf, d_tthr, d_tdir;   // d_tdir: [nq][rows of the first stage] one key per row
+  DevArray<u64> d_tres;   // [TRESCUE_SLICES][nq][k] per-slice lists of the rescue pass
+  DevArray<float> d_tthrs;
+  DevArray<unsigned> d_tcnt;   // [nq] counters followed by [nq] overflow flags
+  DevArray<u64> d_pfb;             // [nq][PFCAP] candidate keys of the batch collect route (round 6: prefilter_batch_enqueue, <= 64 queries)
   // fp32 rows with a bf16 prefilter copy (dtype 2 at creation; `dtype` stays 1: the contract is the fp32 rows')
-  void* rows16 = nullptr;          // bf16 image of `rows`
-  float* d_norm2 = nullptr;        // device [2]: max squared row norm, max squared image error ||x~ - x||^2 (bits ordered as unsigned: both >= 0)
+  DevArray<bf16_t> rows16;         // bf16 image of `rows`
+  DevArray<float> d_norm2;         // device [2]: max squared row norm, max squared image error ||x~ - x||^2 (bits ordered as unsigned: both >= 0)
   float pf_stats[2] = {0.f, 0.f};  // their host copies, refreshed by add()
-  float* d_pf_eps = nullptr;       // [nq] per-query error bound of the approximate scores
-  u64* d_pf_out = nullptr;         // [nq][k] exact keys of the rescored candidates
-  unsigned* d_pf_flag = nullptr;   // [nq] 1 = the candidates do not provably contain the exact top-k
-  size_t d_pf_eps_elems = 0, d_pf_out_elems = 0, d_pf_flag_elems = 0;
-  unsigned* d_pf_cand = nullptr;   // [PFQ][PFCAP] candidate rows of the one-pass route (1 .. PFQ queries)
-  u64* d_pf_keys = nullptr;        // [PFQ][PFCAP] their exact keys
-  unsigned* d_pf_cnt = nullptr;    // [PFQ] candidate counters; [PFQ, 3 PFQ): scratch counters / flags of the prefix selection
-  u64* d_pf_thr = nullptr;         // [0, 2 PFQ): final selection's threshold outputs (unused); [2 PFQ, 3 PFQ): entry threshold keys; [3 PFQ, 4 PFQ): their scores
+  DevArray<float> d_pf_eps;        // [nq] per-query error bound of the approximate scores
+  DevArray<u64> d_pf_out;          // [nq][k] exact keys of the rescored candidates
+  DevArray<unsigned> d_pf_flag;    // [nq] 1 = the candidates do not provably contain the exact top-k
+  DevArray<unsigned> d_pf_cand;    // [PFQ][PFCAP] candidate rows of the one-pass route (1 .. PFQ queries)
+  DevArray<u64> d_pf_keys;         // [PFQ][PFCAP] their exact keys
+  DevArray<unsigned> d_pf_cnt;     // [PFQ] candidate counters; [PFQ, 3 PFQ): scratch counters / flags of the prefix selection
+  DevArray<u64> d_pf_thr;          // [0, 2 PFQ): final selection's threshold outputs (unused); [2 PFQ, 3 PFQ): entry threshold keys; [3 PFQ, 4 PFQ): their scores
   long long pf_searches = 0, pf_fallbacks = 0;
   char* h_pin = nullptr;           // pinned host staging of the one-pass route: [PFQ][dim + 1] floats up, [PFQ k + PFQ / 2] keys + flags down
   int resident_split = 0;   // the resident queries are not all bf16-exact: batched passes carry (hi, remainder) column pairs
@@ -2283,7 +2223,7 @@ struct vrag_dense_index {
 // (dim % 256 == 0), else the single-query kernel once per query for one or two.
 static int pf_onepass_max(int dim) { return dim % 256 == 0 ? PFQ : 2; }
 static bool prefilter_route_ok(const vrag_dense_index* ix, int nq, int k) {
-  if (!ix->rows16 || k > 16 || ix->size < 4096) return false;
+  if (!ix->rows16.p || k > 16 || ix->size < 4096) return false;
   if (!dense_use_exact(1, ix->dim, k)) return false;                                     // the gated fallback scan exists in the exact kernels only
   if (nq > pf_onepass_max(ix->dim) && !dense_use_tiled(0, ix->dim, nq, PFK, (long long)ix->size, kTiledMinImage)) return false;   // batches rank the image with the tiled search
   return true;
@@ -2293,28 +2233,24 @@ struct vrag_sparse_index {
   int vocab = 0, device = 0;
   int64_t n_docs = 0, nnz = 0, padded = 0;
   int n_slices = 0;
-  unsigned short* cols = nullptr;
-  float* vals = nullptr;
-  long long* slice_off = nullptr;
-  int* slice_len = nullptr;
-  unsigned* d_docid = nullptr;  // [n_docs] sorted position -> caller's document index (the row field of a key)
+  DevArray<unsigned short> cols;
+  DevArray<float> vals;
+  DevArray<long long> slice_off;
+  DevArray<int> slice_len;
+  DevArray<unsigned> d_docid;  // [n_docs] sorted position -> caller's document index (the row field of a key)
   hipStream_t stream = nullptr;
   std::mutex mu;
-  float* d_q = nullptr;
-  size_t d_q_elems = 0;
-  u64 *d_cand = nullptr, *d_out = nullptr, *d_bound = nullptr;
-  size_t d_cand_elems = 0, d_out_elems = 0, d_bound_elems = 0;
-  char* d_qcsr = nullptr;             // single-query kernels: the queries' CSR (indptr | terms | weights) as uploaded, scattered into d_q on the device
-  size_t d_qcsr_bytes = 0;
+  DevArray<float> d_q;
+  DevArray<u64> d_cand, d_out, d_bound;
+  DevArray<char> d_qcsr;              // single-query kernels: the queries' CSR (indptr | terms | weights) as uploaded, scattered into d_q on the device
   // host sources of the query uploads: they live in the handle so that a call need not wait for its own uploads before it launches
   // (the NEXT call waits for upload_done before it rewrites them; by then the event has long passed)
   std::vector<char> h_blob;
   std::vector<unsigned short> h_maps;
   std::vector<float> h_wts;
   bool upload_pending = false;
-  unsigned short* d_qmap = nullptr;   // batched kernel: [passes][vpad] term -> union id
-  float* d_qw = nullptr;              // [passes][SQB][SUW] union id -> weight per query
-  size_t d_qmap_elems = 0, d_qw_elems = 0;
+  DevArray<unsigned short> d_qmap;    // batched kernel: [passes][vpad] term -> union id
+  DevArray<float> d_qw;               // [passes][SQB][SUW] union id -> weight per query
   std::vector<int> pass_union;        // union size of every pass of the resident queries
   int pass_qb = 8;                    // queries per pass the resident tables were built for (8 or 16)
   bool last_multi = false;   // which kernel family the resident queries were prepared for
@@ -2327,19 +2263,6 @@ namespace {
 __global__ void cvt_f32_bf16_flat(const float* __restrict__ src, bf16_t* __restrict__ dst, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     dst[i] = (bf16_t)src[i];
-}
-
-template <typename T>
-int grow(T** p, size_t* have, size_t need) {
-  if (need <= *have) return VRAG_OK;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  void* q = nullptr;
-  HIP_TRY(hipMalloc(&q, need * sizeof(T)));
-  *p = reinterpret_cast<T*>(q);
-  *have = need;
-  return VRAG_OK;
 }
 
 void decode_keys(const std::vector<u64>& keys, int nq, int k, int64_t base, const int64_t* perm, float* scores,
@@ -2360,15 +2283,15 @@ void decode_keys(const std::vector<u64>& keys, int nq, int k, int64_t base, cons
 // k > KMAX: ceil(k / KMAX) passes of KMAX; `run_page(bound)` leaves the merged page keys [nq][KMAX] in d_out.
 // After each page the last key of a full page becomes that query's exclusive bound (0 = exhausted: nothing passes).
 template <typename RunPage>
-int paged_search(int nq, int k, u64** d_bound, size_t* d_bound_elems, const u64* d_out, hipStream_t st, RunPage run_page,
+int paged_search(int nq, int k, DevArray<u64>& d_bound, const DevArray<u64>& d_out, hipStream_t st, RunPage run_page,
                  float* scores, int64_t* ids) {
   int rc;
-  if ((rc = grow(d_bound, d_bound_elems, (size_t)nq))) return rc;
+  HIP_TRY(d_bound.grow((size_t)nq));
   std::vector<u64> bound((size_t)nq, ~0ull), page((size_t)nq * KMAX), all((size_t)nq * k, 0ull);
   for (int k0 = 0; k0 < k; k0 += KMAX) {
-    HIP_TRY(hipMemcpyAsync(*d_bound, bound.data(), (size_t)nq * sizeof(u64), hipMemcpyHostToDevice, st));
-    if ((rc = run_page(*d_bound))) return rc;
-    HIP_TRY(hipMemcpyAsync(page.data(), d_out, page.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(d_bound.p, bound.data(), (size_t)nq * sizeof(u64), hipMemcpyHostToDevice, st));
+    if ((rc = run_page(d_bound.p))) return rc;
+    HIP_TRY(hipMemcpyAsync(page.data(), d_out.p, page.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     bool more = false;
     for (int q = 0; q < nq; ++q) {
@@ -2417,11 +2340,11 @@ __global__ void tiled_tau_kernel(int nq, u64* __restrict__ thr_key, float* __res
   flag[q] = 0u;
 }
 
-// The tiled batched search on the resident queries (ix->d_q, fp32): leaves the [nq, k] keys in ix->d_out.  Kernels only.
+// The tiled batched search on the resident queries (ix->d_q.p, fp32): leaves the [nq, k] keys in ix->d_out.  Kernels only.
 int dense_tiled_search(vrag_dense_index* ix, int nq, int k, hipStream_t st, const void* rows_bf16 = nullptr, const TiledCollect* col = nullptr,
                        bool device_rescue = true) {
   const int dim = ix->dim, pairs = ix->resident_split;
-  if (!rows_bf16) rows_bf16 = ix->rows;
+  if (!rows_bf16) rows_bf16 = ix->rows.p;
   const int n_cols = pairs ? 2 * nq : nq;
   // up to 128 query columns: 256 x 128 tiles on a three-stage ring (64 KB of the row stream in flight per CU instead of 32: 0.63
   // instead of 0.81 ms for 64-128 queries over 1.25 M x 768 rows; from 256 columns on the 256 x 256 tiles win: 0.83 vs 0.91 ms,
@@ -2431,25 +2354,20 @@ int dense_tiled_search(vrag_dense_index* ix, int nq, int k, hipStream_t st, cons
   const int tile = n_cols <= 64 ? 2 : (n_cols <= 128 ? 1 : 0);
   const int n_pad = tile == 2 ? 64 : (tile == 1 ? 128 : (n_cols + 255) / 256 * 256);
   int rc;
-  if ((rc = grow(&ix->d_tw, &ix->d_tw_elems, (size_t)n_pad * dim))) return rc;
-  if ((rc = grow(&ix->d_tbuf, &ix->d_tbuf_elems, (size_t)nq * TCAP))) return rc;
-  if ((rc = grow(&ix->d_tthr, &ix->d_tthr_elems, (size_t)nq))) return rc;
-  if ((rc = grow(&ix->d_tthrs, &ix->d_tthrs_elems, (size_t)nq))) return rc;
-  if ((rc = grow(&ix->d_tcnt, &ix->d_tcnt_elems, (size_t)3 * nq))) return rc;   // counters, overflow flags, the rescue's slice counters
+  HIP_TRY(ix->d_tw.grow((size_t)n_pad * dim));
+  HIP_TRY(ix->d_tbuf.grow((size_t)nq * TCAP));
+  HIP_TRY(ix->d_tthr.grow((size_t)nq));
+  HIP_TRY(ix->d_tthrs.grow((size_t)nq));
+  HIP_TRY(ix->d_tcnt.grow((size_t)3 * nq));   // counters, overflow flags, the rescue's slice counters
   const int res_slices = std::max(8, std::min(TRESCUE_SLICES, 8192 / nq));
-  if (!col && (rc = grow(&ix->d_tres, &ix->d_tres_elems, (size_t)res_slices * nq * k))) return rc;
-  unsigned* ovf = ix->d_tcnt + nq;
-  hipLaunchKernelGGL(tiled_queries_kernel, dim3(n_pad), dim3(256), 0, st, ix->d_q, nq, dim, pairs, n_pad, ix->d_tw);
-  hipLaunchKernelGGL(tiled_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, nq, ix->d_tthr, ix->d_tthrs, ix->d_tcnt);
+  if (!col) HIP_TRY(ix->d_tres.grow((size_t)res_slices * nq * k));
+  unsigned* ovf = ix->d_tcnt.p + nq;
+  hipLaunchKernelGGL(tiled_queries_kernel, dim3(n_pad), dim3(256), 0, st, ix->d_q.p, nq, dim, pairs, n_pad, ix->d_tw.p);
+  hipLaunchKernelGGL(tiled_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, nq, ix->d_tthr.p, ix->d_tthrs.p, ix->d_tcnt.p);
   HIP_TRY(hipGetLastError());
   const long long n_all = (long long)ix->size;
   const long long n = col ? std::min<long long>(n_all, TCOLLECT_PREFIX) : n_all;   // collect form: the staged search covers a prefix only
-  static bool attr = false;
-  if (!attr) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&tiled_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                PFCAP * (int)sizeof(u64)));   // the largest buffer a selection sorts (PFCAP >= TCAP)
-    attr = true;
-  }
+  HIP_TRY(set_max_dynamic_lds<&tiled_select_kernel>(PFCAP * (int)sizeof(u64)));   // the largest buffer a selection sorts (PFCAP >= TCAP)
   // Rows seen grow by `ratio` per stage, and a stage admits ~k (ratio - 1) candidates per query, each one an atomic append on its
   // query's counter: at k = 64 (the prefilter's candidate lists) a ratio of 16 made the appends, not the row stream, the cost of
   // every stage (960 per query and stage)
@@ -2501,21 +2419,21 @@ int dense_tiled_search(vrag_dense_index* ix, int nq, int k, hipStream_t st, cons
     if (R && hi < n - off) hi = b.back() + std::max(R, (hi - b.back()) / R * R);   // whole rounds
     b.push_back(std::min<long long>(n - off, hi));
   }
-  if ((rc = grow(&ix->d_tdir, &ix->d_tdir_elems, (size_t)nq * (size_t)std::max(c0max, s0)))) return rc;   // the batch size's maximum, not this shard size's: no re-allocation on a later search of a grown shard
+  HIP_TRY(ix->d_tdir.grow((size_t)nq * (size_t)std::max(c0max, s0)));   // the batch size's maximum, not this shard size's: no re-allocation on a later search of a grown shard
   for (size_t stage = 0; stage + 1 < b.size(); ++stage) {
     const bool first = stage == 0;
     const long long lo = first ? 0 : b[stage], hi = first ? s0 : b[stage + 1];
     GemmParams g{};
     g.op_dtype = kOpBf16;
     g.A = reinterpret_cast<const bf16_t*>(rows_bf16) + (size_t)(skip ? 0 : lo) * dim;
-    g.W = ix->d_tw;
+    g.W = ix->d_tw.p;
     g.M = (int)(hi - lo);
     g.N = n_pad;
     g.K = dim;
-    g.topk_thr_score = ix->d_tthrs;
-    g.topk_thr_key = ix->d_tthr;
-    g.topk_cnt = ix->d_tcnt;
-    g.topk_buf = first ? ix->d_tdir : ix->d_tbuf;
+    g.topk_thr_score = ix->d_tthrs.p;
+    g.topk_thr_key = ix->d_tthr.p;
+    g.topk_cnt = ix->d_tcnt.p;
+    g.topk_buf = first ? ix->d_tdir.p : ix->d_tbuf.p;
     g.topk_cap = first ? (int)s0 : TCAP;
     g.topk_nq = nq;
     g.topk_pairs = pairs;
@@ -2527,27 +2445,27 @@ int dense_tiled_search(vrag_dense_index* ix, int nq, int k, hipStream_t st, cons
     g.topk_tile0 = (skip && !first) ? (int)(lo / 256) : 0;
     HIP_TRY(launch_gemm(EPI_TOPK, g, st));
     const bool last = first ? s0 >= n : hi >= n - off;
-    u64* const sel_out = (last && !col) ? ix->d_out : (u64*)nullptr;
+    u64* const sel_out = (last && !col) ? ix->d_out.p : (u64*)nullptr;
     if (first)
-      hipLaunchKernelGGL(tiled_select_direct_kernel, dim3(nq), dim3(TSEL_NT), (size_t)TCAP * sizeof(u64), st, ix->d_tdir, (int)s0, (int)s0, ix->d_tbuf,
-                         ix->d_tcnt, TCAP, k, ix->d_tthr, ix->d_tthrs, sel_out, ovf);
+      hipLaunchKernelGGL(tiled_select_direct_kernel, dim3(nq), dim3(TSEL_NT), (size_t)TCAP * sizeof(u64), st, ix->d_tdir.p, (int)s0, (int)s0, ix->d_tbuf.p,
+                         ix->d_tcnt.p, TCAP, k, ix->d_tthr.p, ix->d_tthrs.p, sel_out, ovf);
     else
-      hipLaunchKernelGGL(tiled_select_kernel, dim3(nq), dim3(256), (size_t)TCAP * sizeof(u64), st, ix->d_tbuf, ix->d_tcnt, TCAP, k,
-                         ix->d_tthr, ix->d_tthrs, sel_out, ovf, 0);
+      hipLaunchKernelGGL(tiled_select_kernel, dim3(nq), dim3(256), (size_t)TCAP * sizeof(u64), st, ix->d_tbuf.p, ix->d_tcnt.p, TCAP, k,
+                         ix->d_tthr.p, ix->d_tthrs.p, sel_out, ovf, 0);
     HIP_TRY(hipGetLastError());
   }
   if (col) {
-    hipLaunchKernelGGL(tiled_tau_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, nq, ix->d_tthr, ix->d_tthrs, col->eps, ix->d_tcnt, col->flag);
+    hipLaunchKernelGGL(tiled_tau_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, nq, ix->d_tthr.p, ix->d_tthrs.p, col->eps, ix->d_tcnt.p, col->flag);
     GemmParams g{};
     g.op_dtype = kOpBf16;
     g.A = reinterpret_cast<const bf16_t*>(rows_bf16);
-    g.W = ix->d_tw;
+    g.W = ix->d_tw.p;
     g.M = (int)n_all;
     g.N = n_pad;
     g.K = dim;
-    g.topk_thr_score = ix->d_tthrs;
-    g.topk_thr_key = ix->d_tthr;
-    g.topk_cnt = ix->d_tcnt;
+    g.topk_thr_score = ix->d_tthrs.p;
+    g.topk_thr_key = ix->d_tthr.p;
+    g.topk_cnt = ix->d_tcnt.p;
     g.topk_buf = col->keys;
     g.topk_cap = PFCAP;
     g.topk_nq = nq;
@@ -2561,60 +2479,126 @@ int dense_tiled_search(vrag_dense_index* ix, int nq, int k, hipStream_t st, cons
   if (!device_rescue) return VRAG_OK;   // the host call reads the overflow flags back with the lists and re-answers flagged queries through the pass kernels
   const size_t lds = (size_t)dim * sizeof(float) + (size_t)16 * k * sizeof(u64);
   hipLaunchKernelGGL(dense_tiled_rescue_kernel, dim3(nq, res_slices), dim3(256), lds, st, reinterpret_cast<const bf16_t*>(rows_bf16), n_all, dim,
-                     ix->d_q, nq, k, ovf, ix->d_tres, ix->d_tcnt + 2 * (size_t)nq, ix->d_out);
+                     ix->d_q.p, nq, k, ovf, ix->d_tres.p, ix->d_tcnt.p + 2 * (size_t)nq, ix->d_out.p);
   HIP_TRY(hipGetLastError());
   return VRAG_OK;
 }
 
-// One device pass (k <= KMAX) of a dense search: uploads the queries, runs phase 1 + the per-query merge and leaves the
-// [nq, k] keys in ix->d_out.  Returns once the query upload has been consumed (the caller's buffer may be reused); the
-// kernels are only enqueued.  Caller holds ix->mu and has set the device.
-int dense_search_enqueue(vrag_dense_index* ix, const float* queries, int nq, int k, hipStream_t st, int image = 0, const TiledCollect* col = nullptr,
-                         bool* host_rescue = nullptr) {
+// The full scan on the resident queries (ix->d_q): the pass kernels, then the per-query merge; leaves the [nq, k] keys in ix->d_out,
+// the per-query entry thresholds behind them.  Sizes its scratch (nothing is allocated on sizes an earlier search reached).
+// split: the queries ride as (value, remainder) column pairs; gate: per-query flags -- groups of queries without one leave at
+// once; bound: the page bounds of a k > KMAX search.
+int dense_scan_enqueue(vrag_dense_index* ix, int nq, int k, hipStream_t st, int split = 0, const unsigned* gate = nullptr,
+                       const u64* bound = nullptr) {
+  const int n_wg = dense_n_wg(ix->dtype, ix->dim, nq, k, ix->size);
+  HIP_TRY(ix->d_cand.grow((size_t)n_wg * nq * k));
+  HIP_TRY(ix->d_out.grow((size_t)nq * k + nq));   // + per-query entry thresholds
+  HIP_TRY(dense_launch_all(ix->dtype, ix->rows.p, (long long)ix->size, ix->dim, ix->d_q.p, nq, k, ix->d_cand.p, n_wg, st,
+                           ix->d_out.p + (size_t)nq * k, ix->d_out.p, bound, split, gate));
+  HIP_TRY(launch_topk_merge(ix->d_cand.p, n_wg, nq, k, ix->d_out.p, st));
+  HIP_TRY(hipGetLastError());
+  return VRAG_OK;
+}
+
+// Batched search over bf16 rows runs on the matrix cores with bf16 query operands: exact when every query element is a bf16
+// number; otherwise (1) the queries ride as (bf16 part, bf16 remainder) column pairs, 16 queries per pass.
+int queries_split(const vrag_dense_index* ix, const float* queries, int nq) {
+  if (ix->dtype != 0) return 0;
+  const uint32_t* bits = reinterpret_cast<const uint32_t*>(queries);
+  const size_t n_el = (size_t)nq * ix->dim;
+  for (size_t i = 0; i < n_el; ++i)
+    if (bits[i] & 0xFFFFu) return 1;
+  return 0;
+}
+
+// Routes of a dense search (k <= KMAX unless Paged):
+//   Empty             no rows: empty lists
+//   Paged             k > KMAX: ceil(k / KMAX) pages of KMAX on the scalar kernels (paged_search)
+//   PrefilterOnePass  fp32 rows with a bf16 image, 1 .. pf_onepass_max queries: one streaming pass over the image (prefilter_onepass_enqueue)
+//   PrefilterBatch    the same, larger batches: the image ranked by the tiled search (prefilter_batch_enqueue)
+//   Tiled             batches over bf16 rows: the score GEMM with the top-k epilogue (dense_tiled_search)
+//   Scan              the pass kernels (dense_scan_enqueue)
+enum class DenseRoute { Empty, Paged, PrefilterOnePass, PrefilterBatch, Tiled, Scan };
+enum class DenseCaller {
+  Host,       // vrag_dense_index_search: lists come back to the host
+  Device,     // vrag_dense_index_search_device: lists stay on the device
+  Resident,   // vrag_dense_index_run_resident: the kernels again on the queries a search left in ix->d_q
+};
+
+// The one place a dense search picks its route.  split: queries_split of the queries (Resident: ix->resident_split).
+DenseRoute dense_plan(const vrag_dense_index* ix, int nq, int k, DenseCaller caller, int split) {
+  const bool tiled = dense_use_tiled(ix->dtype, ix->dim, nq, k, (long long)ix->size, split ? kTiledMinBf16Pairs : kTiledMinBf16);
+  // run_resident repeats the kernels of a search on its resident queries: the tiled search or the full scan only (the prefilter
+  // routes stage their queries differently, and an empty shard or k > KMAX is rejected before)
+  if (caller == DenseCaller::Resident) return tiled ? DenseRoute::Tiled : DenseRoute::Scan;
+  // k > KMAX: pages of KMAX on the scalar kernels (fp32 queries; the matrix-core paths stop at k = 16).  The pages need the host
+  // between them: Paged is the host call's route, the device call rejects it.
+  if (k > KMAX) return DenseRoute::Paged;
+  // fp32 rows with a prefilter image: rank the image for candidates, re-score them exactly (see the kernels).  Where it pays: one
+  // to PFQ queries (half the bytes of the fp32 scan) and batches the tiled search takes (the shard read once instead of once per
+  // 32 queries); in between the 32-queries-per-pass exact kernel is already the faster route (prefilter_route_ok).
+  if (prefilter_route_ok(ix, nq, k)) {
+    // An index whose data keeps failing the sufficiency test (near-duplicate rows) stops trying.  Host call only: it reads the
+    // flags back and keeps the count (pf_searches / pf_fallbacks); the device call never sees them and always takes the route.
+    const bool failing = ix->pf_searches >= 32 && ix->pf_fallbacks * 4 > ix->pf_searches;
+    if (caller == DenseCaller::Device || !failing)
+      return nq <= pf_onepass_max(ix->dim) ? DenseRoute::PrefilterOnePass : DenseRoute::PrefilterBatch;
+  }
+  if (ix->size == 0) return DenseRoute::Empty;
+  return tiled ? DenseRoute::Tiled : DenseRoute::Scan;
+}
+
+template <int V> using IntC = std::integral_constant<int, V>;
+// f(IntC<DIMC>{}) with the dim-chunk constant of the single-query prefilter kernels: dim / 128 where an instantiation exists
+// (384, 768, 1024), else 0 (the generic loop)
+template <typename F>
+void with_pf_dimc(int dim, F f) {
+  switch (dim % 128 == 0 ? dim / 128 : 0) {
+    case 3: f(IntC<3>{}); break;
+    case 6: f(IntC<6>{}); break;
+    case 8: f(IntC<8>{}); break;
+    default: f(IntC<0>{});
+  }
+}
+
+// One device pass (k <= KMAX) of a dense search on route Empty, Tiled or Scan: uploads the queries, runs the route and leaves the
+// [nq, k] keys in ix->d_out.  Returns once the query upload has been consumed (the caller's buffer may be reused); the kernels
+// are only enqueued.  Caller holds ix->mu and has set the device.
+int dense_search_enqueue(vrag_dense_index* ix, const float* queries, int nq, int k, hipStream_t st, DenseRoute route, int split,
+                         int image = 0, const TiledCollect* col = nullptr, bool* host_rescue = nullptr) {
   // host_rescue (non-null: the caller reads results back anyway): set when the tiled search ran WITHOUT its device rescue pass -- the
   // caller copies the overflow flags (ix->d_tcnt + nq) with the lists and re-answers flagged queries itself
-  // image: rank the bf16 prefilter image of an fp32 index instead of its rows (the approximate pass of the prefilter route);
-  // 2 = with the queries rounded to bf16 instead of riding as (value, remainder) column pairs -- half the GEMM columns, the
+  // image (route Tiled): rank the bf16 prefilter image of an fp32 index instead of its rows (the approximate pass of the prefilter
+  // route); 2 = with the queries rounded to bf16 instead of riding as (value, remainder) column pairs -- half the GEMM columns, the
   // rounding is part of the caller's error bound
   const int dtype = image ? 0 : ix->dtype;
-  const void* rows = image ? ix->rows16 : ix->rows;
   const int n_wg = dense_n_wg(dtype, ix->dim, nq, k, ix->size);
-  int rc;
   if (ix->lists_done) HIP_TRY(hipStreamWaitEvent(st, ix->lists_done, 0));   // a device-resident search may still be reading the scratch
-  if ((rc = grow(&ix->d_q, &ix->d_q_elems, (size_t)nq * ix->dim))) return rc;
-  if ((rc = grow(&ix->d_cand, &ix->d_cand_elems, (size_t)n_wg * nq * k))) return rc;
-  if ((rc = grow(&ix->d_out, &ix->d_out_elems, (size_t)nq * k + nq))) return rc;   // + per-query entry thresholds
+  HIP_TRY(ix->d_q.grow((size_t)nq * ix->dim));
+  HIP_TRY(ix->d_cand.grow((size_t)n_wg * nq * k));   // the full scan's scratch whatever the route: run_resident may follow
+  HIP_TRY(ix->d_out.grow((size_t)nq * k + nq));      // + per-query entry thresholds
   const size_t lds = (size_t)DQT * ix->dim * sizeof(float) + (size_t)16 * DQT * k * sizeof(u64);
   ARG_CHECK(lds <= 160 * 1024, "dim/k too large for the LDS budget");
-  HIP_TRY(hipMemcpyAsync(ix->d_q, queries, (size_t)nq * ix->dim * sizeof(float), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ix->d_q.p, queries, (size_t)nq * ix->dim * sizeof(float), hipMemcpyHostToDevice, st));
   if (!ix->upload_done) HIP_TRY(hipEventCreateWithFlags(&ix->upload_done, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(ix->upload_done, st));
-  // Batched search over bf16 rows runs on the matrix cores with bf16 query operands: exact when every query element
-  // is a bf16 number; otherwise the queries ride as (bf16 part, bf16 remainder) column pairs, 16 queries per pass.
-  // Recorded for whatever kernel family serves these queries now or in a later run_resident with another (nq, k).
-  ix->resident_split = 0;
-  if (dtype == 0 && image != 2) {
-    const uint32_t* bits = reinterpret_cast<const uint32_t*>(queries);
-    const size_t n_el = (size_t)nq * ix->dim;
-    for (size_t i = 0; i < n_el; ++i)
-      if (bits[i] & 0xFFFFu) {
-        ix->resident_split = 1;
-        break;
-      }
-  }
+  ix->resident_split = split;   // for whatever kernel family serves these queries now or in a later run_resident with another (nq, k)
   HIP_TRY(hipEventSynchronize(ix->upload_done));
-  if (ix->size == 0) {
-    HIP_TRY(hipMemsetAsync(ix->d_out, 0, (size_t)nq * k * sizeof(u64), st));
-  } else if (dense_use_tiled(dtype, ix->dim, nq, k, (long long)ix->size, image ? kTiledMinImage : (ix->resident_split ? kTiledMinBf16Pairs : kTiledMinBf16))) {
-    if ((rc = dense_tiled_search(ix, nq, k, st, image ? rows : nullptr, col, host_rescue == nullptr))) return rc;
-    if (host_rescue) *host_rescue = true;
-  } else {
-    HIP_TRY(dense_launch_all(dtype, rows, (long long)ix->size, ix->dim, ix->d_q, nq, k, ix->d_cand, n_wg, st,
-                             ix->d_out + (size_t)nq * k, ix->d_out, nullptr, ix->resident_split));
-    HIP_TRY(launch_topk_merge(ix->d_cand, n_wg, nq, k, ix->d_out, st));
-    HIP_TRY(hipGetLastError());
+  switch (route) {
+    case DenseRoute::Empty:
+      HIP_TRY(hipMemsetAsync(ix->d_out.p, 0, (size_t)nq * k * sizeof(u64), st));
+      return VRAG_OK;
+    case DenseRoute::Tiled: {
+      int rc;
+      if ((rc = dense_tiled_search(ix, nq, k, st, image ? ix->rows16.p : nullptr, col, host_rescue == nullptr))) return rc;
+      if (host_rescue) *host_rescue = true;
+      return VRAG_OK;
+    }
+    case DenseRoute::Scan:
+      return dense_scan_enqueue(ix, nq, k, st, split);
+    default:
+      ARG_CHECK(false, "internal: route %d is not a single dense pass", (int)route);
   }
-  return VRAG_OK;
 }
 
 }  // namespace
@@ -2641,20 +2625,16 @@ int vrag_dense_index_create(int32_t dim, int64_t capacity, int32_t dtype, int32_
   ix->capacity = capacity;
   const size_t esz = dtype == 0 ? 2 : 4;
   // + two 256-row tiles: the tiled batched search reads whole GEMM tiles behind the last row (results of rows >= size are dropped)
-  hipError_t e = hipMalloc(&ix->rows, ((size_t)capacity + 512) * dim * esz);
+  hipError_t e = ix->rows.grow(((size_t)capacity + 512) * dim * esz);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking);
   if (e == hipSuccess && prefilter && dim % 4 == 0) {
-    e = hipMalloc(&ix->rows16, ((size_t)capacity + 512) * dim * 2);
-    if (e == hipSuccess) e = hipMalloc((void**)&ix->d_norm2, 2 * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(ix->d_norm2, 0, 2 * sizeof(float));
+    e = ix->rows16.grow(((size_t)capacity + 512) * dim);
+    if (e == hipSuccess) e = ix->d_norm2.grow(2);
+    if (e == hipSuccess) e = hipMemset(ix->d_norm2.p, 0, 2 * sizeof(float));
     if (e == hipSuccess) e = hipHostMalloc((void**)&ix->h_pin, (size_t)PFQ * (dim + 1) * sizeof(float) + (PFQ * KMAX + PFQ / 2) * sizeof(u64), 0);
   }
   ix->stage_rows = std::max<size_t>(1, ((size_t)64 << 20) / ((size_t)dim * 4));
-  if (e == hipSuccess) {
-    void* p = nullptr;
-    e = hipMalloc(&p, ix->stage_rows * dim * sizeof(float));
-    ix->stage = reinterpret_cast<float*>(p);
-  }
+  if (e == hipSuccess) e = ix->stage.grow(ix->stage_rows * dim);
   if (e != hipSuccess) {
     set_error("dense index allocation failed: %s", hipGetErrorString(e));
     vrag_dense_index_destroy(ix);
@@ -2668,21 +2648,11 @@ void vrag_dense_index_destroy(vrag_dense_index* ix) {
   if (!ix) return;
   (void)hipSetDevice(ix->device);
   (void)hipDeviceSynchronize();
-  if (ix->rows) (void)hipFree(ix->rows);
-  if (ix->stage) (void)hipFree(ix->stage);
-  if (ix->d_q) (void)hipFree(ix->d_q);
-  if (ix->d_cand) (void)hipFree(ix->d_cand);
-  if (ix->d_out) (void)hipFree(ix->d_out);
-  if (ix->d_bound) (void)hipFree(ix->d_bound);
-  for (void* p : {(void*)ix->d_tw, (void*)ix->d_tbuf, (void*)ix->d_tdir, (void*)ix->d_tres, (void*)ix->d_tthr, (void*)ix->d_tthrs, (void*)ix->d_tcnt, (void*)ix->d_pfb, ix->rows16, (void*)ix->d_norm2,
-                  (void*)ix->d_pf_eps, (void*)ix->d_pf_out, (void*)ix->d_pf_flag, (void*)ix->d_pf_cand, (void*)ix->d_pf_keys, (void*)ix->d_pf_cnt,
-                  (void*)ix->d_pf_thr})
-    if (p) (void)hipFree(p);
   if (ix->h_pin) (void)hipHostFree(ix->h_pin);
   if (ix->upload_done) (void)hipEventDestroy(ix->upload_done);
   if (ix->lists_done) (void)hipEventDestroy(ix->lists_done);
   if (ix->stream) (void)hipStreamDestroy(ix->stream);
-  delete ix;
+  delete ix;   // the device arrays free themselves
 }
 
 int64_t vrag_dense_index_size(vrag_dense_index* ix) { return ix ? ix->size : -1; }
@@ -2728,24 +2698,24 @@ int vrag_dense_index_add(vrag_dense_index* ix, const float* rows, int64_t n) {
   for (int64_t r0 = 0; r0 < n; r0 += (int64_t)ix->stage_rows) {
     const size_t nr = (size_t)std::min<int64_t>((int64_t)ix->stage_rows, n - r0);
     if (ix->dtype == 1) {
-      float* dst = reinterpret_cast<float*>(ix->rows) + (size_t)(ix->size + r0) * dim;
+      float* dst = reinterpret_cast<float*>(ix->rows.p) + (size_t)(ix->size + r0) * dim;
       HIP_TRY(hipMemcpy(dst, rows + (size_t)r0 * dim, nr * dim * sizeof(float), hipMemcpyHostToDevice));
-      if (ix->rows16) {
+      if (ix->rows16.p) {
         hipLaunchKernelGGL(prefilter_image_kernel, dim3((unsigned)((nr + 3) / 4)), dim3(256), 0, 0, dst,
-                           reinterpret_cast<bf16_t*>(ix->rows16) + (size_t)(ix->size + r0) * dim, (long long)nr, (int)dim, ix->d_norm2);
+                           reinterpret_cast<bf16_t*>(ix->rows16.p) + (size_t)(ix->size + r0) * dim, (long long)nr, (int)dim, ix->d_norm2.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());
       }
     } else {
-      HIP_TRY(hipMemcpy(ix->stage, rows + (size_t)r0 * dim, nr * dim * sizeof(float), hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(cvt_f32_bf16_flat, dim3(1024), dim3(256), 0, 0, ix->stage,
-                         reinterpret_cast<bf16_t*>(ix->rows) + (size_t)(ix->size + r0) * dim, nr * dim);
+      HIP_TRY(hipMemcpy(ix->stage.p, rows + (size_t)r0 * dim, nr * dim * sizeof(float), hipMemcpyHostToDevice));
+      hipLaunchKernelGGL(cvt_f32_bf16_flat, dim3(1024), dim3(256), 0, 0, ix->stage.p,
+                         reinterpret_cast<bf16_t*>(ix->rows.p) + (size_t)(ix->size + r0) * dim, nr * dim);
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipDeviceSynchronize());
     }
   }
   ix->size += n;
-  if (ix->rows16) HIP_TRY(hipMemcpy(ix->pf_stats, ix->d_norm2, 2 * sizeof(float), hipMemcpyDeviceToHost));
+  if (ix->rows16.p) HIP_TRY(hipMemcpy(ix->pf_stats, ix->d_norm2.p, 2 * sizeof(float), hipMemcpyDeviceToHost));
   }
   dense_warm_query_path(ix);
   return VRAG_OK;
@@ -2763,15 +2733,15 @@ int vrag_dense_index_add_device(vrag_dense_index* ix, const float* rows, int64_t
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t dim = ix->dim, off = (size_t)ix->size * dim, cnt = (size_t)n * dim;
   if (ix->dtype == 1) {
-    HIP_TRY(hipMemcpyAsync(reinterpret_cast<float*>(ix->rows) + off, rows, cnt * sizeof(float), hipMemcpyDeviceToDevice, st));
-    if (ix->rows16) {
+    HIP_TRY(hipMemcpyAsync(reinterpret_cast<float*>(ix->rows.p) + off, rows, cnt * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (ix->rows16.p) {
       hipLaunchKernelGGL(prefilter_image_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, rows,
-                         reinterpret_cast<bf16_t*>(ix->rows16) + off, (long long)n, (int)dim, ix->d_norm2);
+                         reinterpret_cast<bf16_t*>(ix->rows16.p) + off, (long long)n, (int)dim, ix->d_norm2.p);
       HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(ix->pf_stats, ix->d_norm2, 2 * sizeof(float), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(ix->pf_stats, ix->d_norm2.p, 2 * sizeof(float), hipMemcpyDeviceToHost, st));
     }
   } else {
-    hipLaunchKernelGGL(cvt_f32_bf16_flat, dim3(2048), dim3(256), 0, st, rows, reinterpret_cast<bf16_t*>(ix->rows) + off, cnt);
+    hipLaunchKernelGGL(cvt_f32_bf16_flat, dim3(2048), dim3(256), 0, st, rows, reinterpret_cast<bf16_t*>(ix->rows.p) + off, cnt);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipStreamSynchronize(st));   // ingest is not the hot path: searches on any stream may follow at once
@@ -2783,7 +2753,7 @@ int vrag_dense_index_add_device(vrag_dense_index* ix, const float* rows, int64_t
 
 // Batch route of the prefilter (nq >= 3), with `rescan` without a host decision: tiled search of the image with bf16-rounded queries -> 64
 // candidates per query -> sufficiency test + exact re-score; then the full scan behind the per-query flags (groups of 32 queries
-// without a flag leave at once) and a per-query pick.  Leaves the [nq, k] keys in ix->d_pf_out and the flags in ix->d_pf_flag.
+// without a flag leave at once) and a per-query pick.  Leaves the [nq, k] keys in ix->d_pf_out.p and the flags in ix->d_pf_flag.
 // Worst case (every query flagged: bunched scores) = the full scan plus the tiled pass.  The bound with rounded queries:
 // (prefilter_eps with the rounded-query term).
 // Per-query error bound of the image scores (see "fp32 rows, bf16 prefilter"): E ||q|| + Dq max||x~|| + 4 dim 2^-24 max||x|| ||q||,
@@ -2807,54 +2777,50 @@ static float prefilter_eps(const vrag_dense_index* ix, const float* q, bool roun
   return (float)(e * 1.001 + 1e-30);
 }
 
-static int prefilter_rescan_enqueue(vrag_dense_index* ix, int nq, int k, hipStream_t st);
+static int prefilter_rescan_enqueue(vrag_dense_index* ix, int nq, int k, hipStream_t st, const unsigned* flags);
 constexpr int kCollectMaxQueries = 256;   // 128 / 256 queries 0.99 / 1.33 -> 0.87 / 1.20 ms; 512 and 1 024 equal to the 64-candidate route (the exact chains grow with the lists): profiles/r06_collect_batch_probe.txt
 static int prefilter_batch_enqueue(vrag_dense_index* ix, const float* queries, int nq, int k, hipStream_t st, bool rescan = true) {
   int rc;
-  if ((rc = grow(&ix->d_pf_eps, &ix->d_pf_eps_elems, (size_t)nq))) return rc;
-  if ((rc = grow(&ix->d_pf_out, &ix->d_pf_out_elems, (size_t)nq * k + 1))) return rc;
-  if ((rc = grow(&ix->d_pf_flag, &ix->d_pf_flag_elems, (size_t)nq))) return rc;
+  HIP_TRY(ix->d_pf_eps.grow((size_t)nq));
+  HIP_TRY(ix->d_pf_out.grow((size_t)nq * k + 1));
+  HIP_TRY(ix->d_pf_flag.grow((size_t)nq));
   std::vector<float> eps((size_t)nq);
   for (int q = 0; q < nq; ++q) eps[q] = prefilter_eps(ix, queries + (size_t)q * ix->dim, /*rounded_query=*/true);
   if (nq <= kCollectMaxQueries) {
     // up to kCollectMaxQueries queries: the collect form of the tiled search (TiledCollect above) -- a staged search with lists
     // of k over a 65 536-row prefix, ONE pass over the shard that appends every row within 2 eps of the prefix's k-th score,
     // exact re-score of those lists, one selection (32 queries 0.79 -> 0.65 ms, 64: 0.94 -> 0.74; profiles/r06_collect_batch_probe.txt)
-    if ((rc = grow(&ix->d_pfb, &ix->d_pfb_elems, (size_t)nq * PFCAP))) return rc;
+    HIP_TRY(ix->d_pfb.grow((size_t)nq * PFCAP));
     if (!ix->upload_done) HIP_TRY(hipEventCreateWithFlags(&ix->upload_done, hipEventDisableTiming));
-    HIP_TRY(hipMemcpyAsync(ix->d_pf_eps, eps.data(), (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
-    const TiledCollect col{ix->d_pf_eps, ix->d_pfb, ix->d_pf_flag};
-    if ((rc = dense_search_enqueue(ix, queries, nq, k, st, /*image=*/2, &col))) return rc;
+    HIP_TRY(hipMemcpyAsync(ix->d_pf_eps.p, eps.data(), (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
+    const TiledCollect col{ix->d_pf_eps.p, ix->d_pfb.p, ix->d_pf_flag.p};
+    if ((rc = dense_search_enqueue(ix, queries, nq, k, st, DenseRoute::Tiled, 0, /*image=*/2, &col))) return rc;
     HIP_TRY(hipEventRecord(ix->upload_done, st));
-    hipLaunchKernelGGL(prefilter_rescore_list_kernel<true>, dim3(PFCAP / 16, nq), dim3(256), 0, st, (const unsigned*)nullptr, ix->d_tcnt,
-                       reinterpret_cast<const float*>(ix->rows), ix->dim, ix->d_q, ix->d_pfb);
-    hipLaunchKernelGGL(tiled_select_kernel, dim3(nq), dim3(256), (size_t)PFCAP * sizeof(u64), st, ix->d_pfb, ix->d_tcnt, PFCAP, k, ix->d_tthr,
-                       ix->d_tthrs, ix->d_pf_out, ix->d_pf_flag, 0);
+    hipLaunchKernelGGL(prefilter_rescore_list_kernel<true>, dim3(PFCAP / 16, nq), dim3(256), 0, st, (const unsigned*)nullptr, ix->d_tcnt.p,
+                       reinterpret_cast<const float*>(ix->rows.p), ix->dim, ix->d_q.p, ix->d_pfb.p);
+    hipLaunchKernelGGL(tiled_select_kernel, dim3(nq), dim3(256), (size_t)PFCAP * sizeof(u64), st, ix->d_pfb.p, ix->d_tcnt.p, PFCAP, k, ix->d_tthr.p,
+                       ix->d_tthrs.p, ix->d_pf_out.p, ix->d_pf_flag.p, 0);
     HIP_TRY(hipGetLastError());
   } else {
-    if ((rc = dense_search_enqueue(ix, queries, nq, PFK, st, /*image=*/2))) return rc;
-    HIP_TRY(hipMemcpyAsync(ix->d_pf_eps, eps.data(), (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
+    if ((rc = dense_search_enqueue(ix, queries, nq, PFK, st, DenseRoute::Tiled, 0, /*image=*/2))) return rc;
+    HIP_TRY(hipMemcpyAsync(ix->d_pf_eps.p, eps.data(), (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(ix->upload_done, st));
-    hipLaunchKernelGGL(prefilter_rescore_kernel, dim3(nq), dim3(64), 0, st, ix->d_out, reinterpret_cast<const float*>(ix->rows), ix->dim,
-                       ix->d_q, ix->d_pf_eps, k, PFK, ix->d_pf_out, ix->d_pf_flag);
+    hipLaunchKernelGGL(prefilter_rescore_kernel, dim3(nq), dim3(64), 0, st, ix->d_out.p, reinterpret_cast<const float*>(ix->rows.p), ix->dim,
+                       ix->d_q.p, ix->d_pf_eps.p, k, PFK, ix->d_pf_out.p, ix->d_pf_flag.p);
     HIP_TRY(hipGetLastError());
   }
-  if (rescan && (rc = prefilter_rescan_enqueue(ix, nq, k, st))) return rc;
+  if (rescan && (rc = prefilter_rescan_enqueue(ix, nq, k, st, ix->d_pf_flag.p))) return rc;
   HIP_TRY(hipEventSynchronize(ix->upload_done));   // the eps upload has left the host vector
   return VRAG_OK;
 }
 
-// The full scan behind the flags of prefilter_batch_enqueue + the per-query pick (in place in ix->d_pf_out).  A caller that reads the
-// flags on the host anyway (vrag_dense_index_search) enqueues it only when a flag is up: eighteen launches saved per batch of 256.
-static int prefilter_rescan_enqueue(vrag_dense_index* ix, int nq, int k, hipStream_t st) {
+// The full scan behind the per-query flags of a prefilter route + the per-query pick (in place in ix->d_pf_out).  A caller that reads
+// the flags on the host anyway (vrag_dense_index_search) enqueues it only when a flag is up: eighteen launches saved per batch of 256.
+static int prefilter_rescan_enqueue(vrag_dense_index* ix, int nq, int k, hipStream_t st, const unsigned* flags) {
   int rc;
-  const int n_wg = dense_n_wg(ix->dtype, ix->dim, nq, k, ix->size);
-  if ((rc = grow(&ix->d_cand, &ix->d_cand_elems, (size_t)n_wg * nq * k))) return rc;
-  HIP_TRY(dense_launch_all(ix->dtype, ix->rows, (long long)ix->size, ix->dim, ix->d_q, nq, k, ix->d_cand, n_wg, st,
-                           ix->d_out + (size_t)nq * k, ix->d_out, nullptr, 0, ix->d_pf_flag));
-  HIP_TRY(launch_topk_merge(ix->d_cand, n_wg, nq, k, ix->d_out, st));   // lists of unflagged queries: whatever the scratch held -- never picked
+  if ((rc = dense_scan_enqueue(ix, nq, k, st, 0, flags))) return rc;   // lists of unflagged queries: whatever the scratch held -- never picked
   const long long n = (long long)nq * k;
-  hipLaunchKernelGGL(prefilter_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ix->d_pf_out, ix->d_out, ix->d_pf_flag, nq, k);
+  hipLaunchKernelGGL(prefilter_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ix->d_pf_out.p, ix->d_out.p, flags, nq, k);
   HIP_TRY(hipGetLastError());
   return VRAG_OK;
 }
@@ -2867,17 +2833,10 @@ static_assert((PFPREFIX / PFROWS) * PFBEST <= PFCAP, "the entry-threshold keys s
 static int prefilter_single_enqueue(vrag_dense_index* ix, const float* dq, const float* deps, int nq, int k, u64* out_keys,
                                     unsigned* out_flags, hipStream_t st) {
   const int dim = ix->dim;
-  int rc;
-  if (!ix->d_pf_cand) {
-    size_t unused = 0;
-    if ((rc = grow(&ix->d_pf_cand, &unused, (size_t)PFQ * PFCAP))) return rc;
-    unused = 0;
-    if ((rc = grow(&ix->d_pf_keys, &unused, (size_t)PFQ * PFCAP))) return rc;
-    unused = 0;
-    if ((rc = grow(&ix->d_pf_cnt, &unused, (size_t)4 * PFQ))) return rc;
-    unused = 0;
-    if ((rc = grow(&ix->d_pf_thr, &unused, (size_t)4 * PFQ))) return rc;
-  }
+  HIP_TRY(ix->d_pf_cand.grow((size_t)PFQ * PFCAP));
+  HIP_TRY(ix->d_pf_keys.grow((size_t)PFQ * PFCAP));
+  HIP_TRY(ix->d_pf_cnt.grow((size_t)4 * PFQ));
+  HIP_TRY(ix->d_pf_thr.grow((size_t)4 * PFQ));
   const long long prefix = std::min<long long>(PFPREFIX, (long long)ix->size);
   const int n_wg0 = (int)((prefix + PFROWS - 1) / PFROWS);
   // shards of at least four prefixes: the threshold rows are a sample -- one 128-row block every size / 256 rows -- not the first 32 768
@@ -2886,74 +2845,88 @@ static int prefilter_single_enqueue(vrag_dense_index* ix, const float* dq, const
   const long long pf_rows = pf_sampled ? (long long)ix->size : prefix;
   const int per = dense_rows_per_wg((long long)ix->size);
   const int wgs = (int)(((long long)ix->size + per - 1) / per);
-  const int dimc = dim % 128 == 0 ? dim / 128 : 0;
-  const bf16_t* img = reinterpret_cast<const bf16_t*>(ix->rows16);
+  const bf16_t* img = reinterpret_cast<const bf16_t*>(ix->rows16.p);
   const size_t lds_q = (size_t)dim * sizeof(float);
   // per query q: candidate counter d_pf_cnt[q], the prefix selection's counter / overflow flag behind them, the entry threshold
   // key d_pf_thr[2 PFQ + q] and its score (float) at d_pf_thr + 3 PFQ
-  unsigned* sel_cnt = ix->d_pf_cnt + PFQ;
-  unsigned* sel_ovf = ix->d_pf_cnt + 2 * PFQ;
-  u64* kth0 = ix->d_pf_thr + 2 * PFQ;
-  float* kth_score0 = reinterpret_cast<float*>(ix->d_pf_thr + 3 * PFQ);
-#define VRAG_PF_PREFIX(DC_, Q0_, NQ_) hipLaunchKernelGGL((prefilter_prefix_kernel<DC_>), dim3(n_wg0, NQ_), dim3(256), lds_q + PFROWS * sizeof(u64), st, img, \
-                                                         pf_rows, dim, dq + (size_t)(Q0_) * dim, ix->d_pf_keys + (size_t)(Q0_) * PFCAP, ix->d_pf_cnt + (Q0_),  \
-                                                         out_flags + (Q0_), PFCAP, pf_block_stride)
+  unsigned* sel_cnt = ix->d_pf_cnt.p + PFQ;
+  unsigned* sel_ovf = ix->d_pf_cnt.p + 2 * PFQ;
+  u64* kth0 = ix->d_pf_thr.p + 2 * PFQ;
+  float* kth_score0 = reinterpret_cast<float*>(ix->d_pf_thr.p + 3 * PFQ);
   auto prefix_launch = [&](int q0, int n) {
-    if (dimc == 6) VRAG_PF_PREFIX(6, q0, n);
-    else if (dimc == 3) VRAG_PF_PREFIX(3, q0, n);
-    else if (dimc == 8) VRAG_PF_PREFIX(8, q0, n);
-    else VRAG_PF_PREFIX(0, q0, n);
+    with_pf_dimc(dim, [&](auto dc) {
+      hipLaunchKernelGGL((prefilter_prefix_kernel<dc.value>), dim3(n_wg0, n), dim3(256), lds_q + PFROWS * sizeof(u64), st, img, pf_rows, dim,
+                         dq + (size_t)q0 * dim, ix->d_pf_keys.p + (size_t)q0 * PFCAP, ix->d_pf_cnt.p + q0, out_flags + q0, PFCAP, pf_block_stride);
+    });
   };
-#undef VRAG_PF_PREFIX
   if (nq >= 2 && nq <= PFQ && dim % 256 == 0) {
     // ONE streaming pass for the batch: five launches whatever nq (entry thresholds of all queries, their selection, the collect
     // pass, the exact re-score of every list, the final selection)
     prefix_launch(0, nq);
-    hipLaunchKernelGGL(tiled_select_kernel, dim3(nq), dim3(256), (size_t)PFCAP * sizeof(u64), st, ix->d_pf_keys, sel_cnt, PFCAP, k, kth0, kth_score0,
+    hipLaunchKernelGGL(tiled_select_kernel, dim3(nq), dim3(256), (size_t)PFCAP * sizeof(u64), st, ix->d_pf_keys.p, sel_cnt, PFCAP, k, kth0, kth_score0,
                        (u64*)nullptr, sel_ovf, n_wg0 * PFBEST);
     const size_t lds_m = (size_t)(nq <= 2 ? 2 : 4) * dim * sizeof(float);
-#define VRAG_PF_COLLECT_M(DC_, QN_) hipLaunchKernelGGL((prefilter_collect_multi_kernel<DC_, QN_>), dim3(wgs), dim3(256), lds_m, st, img, (long long)ix->size, dim, dq, \
-                                                       nq, kth0, deps, ix->d_pf_cnt, ix->d_pf_cand, per)
-    const int d32 = dim / 256;
-    if (nq <= 2) {
-      if (d32 == 3) VRAG_PF_COLLECT_M(3, 2);
-      else if (d32 == 2) VRAG_PF_COLLECT_M(2, 2);
-      else if (d32 == 1) VRAG_PF_COLLECT_M(1, 2);
-      else return VRAG_ERR_INVALID;   // prefilter_route_ok admits dim <= 768 only
-    } else {
-      if (d32 == 3) VRAG_PF_COLLECT_M(3, 4);
-      else if (d32 == 2) VRAG_PF_COLLECT_M(2, 4);
-      else if (d32 == 1) VRAG_PF_COLLECT_M(1, 4);
-      else return VRAG_ERR_INVALID;
-    }
-#undef VRAG_PF_COLLECT_M
-    hipLaunchKernelGGL(prefilter_rescore_list_kernel<false>, dim3(PFCAP / 16, nq), dim3(256), 0, st, ix->d_pf_cand, ix->d_pf_cnt,
-                       reinterpret_cast<const float*>(ix->rows), dim, dq, ix->d_pf_keys);
+    auto collect_multi = [&](auto qn) {   // dim / 256 chunks, qn queries compiled in
+      auto go = [&](auto d32) {
+        hipLaunchKernelGGL((prefilter_collect_multi_kernel<d32.value, qn.value>), dim3(wgs), dim3(256), lds_m, st, img, (long long)ix->size, dim, dq,
+                           nq, kth0, deps, ix->d_pf_cnt.p, ix->d_pf_cand.p, per);
+      };
+      switch (dim / 256) {
+        case 1: go(IntC<1>{}); return true;
+        case 2: go(IntC<2>{}); return true;
+        case 3: go(IntC<3>{}); return true;
+        default: return false;   // prefilter_route_ok admits dim <= 768 only
+      }
+    };
+    if (!(nq <= 2 ? collect_multi(IntC<2>{}) : collect_multi(IntC<4>{}))) return VRAG_ERR_INVALID;
+    hipLaunchKernelGGL(prefilter_rescore_list_kernel<false>, dim3(PFCAP / 16, nq), dim3(256), 0, st, ix->d_pf_cand.p, ix->d_pf_cnt.p,
+                       reinterpret_cast<const float*>(ix->rows.p), dim, dq, ix->d_pf_keys.p);
     HIP_TRY(hipGetLastError());
   } else {
     for (int q = 0; q < nq; ++q) {
       const float* q_dev = dq + (size_t)q * dim;
-      u64* qkeys = ix->d_pf_keys + (size_t)q * PFCAP;
-      unsigned* cand = ix->d_pf_cand + (size_t)q * PFCAP;
+      u64* qkeys = ix->d_pf_keys.p + (size_t)q * PFCAP;
+      unsigned* cand = ix->d_pf_cand.p + (size_t)q * PFCAP;
       prefix_launch(q, 1);
       hipLaunchKernelGGL(tiled_select_kernel, dim3(1), dim3(256), (size_t)PFCAP * sizeof(u64), st, qkeys, sel_cnt + q, PFCAP, k, kth0 + q,
                          kth_score0 + q, (u64*)nullptr, sel_ovf + q, n_wg0 * PFBEST);
-#define VRAG_PF_COLLECT(DC_) hipLaunchKernelGGL((prefilter_collect_kernel<DC_>), dim3(wgs), dim3(256), lds_q, st, img, (long long)ix->size, dim, q_dev, kth0 + q, \
-                                                 deps + q, ix->d_pf_cnt + q, cand, per)
-      if (dimc == 6) VRAG_PF_COLLECT(6);
-      else if (dimc == 3) VRAG_PF_COLLECT(3);
-      else if (dimc == 8) VRAG_PF_COLLECT(8);
-      else VRAG_PF_COLLECT(0);
-#undef VRAG_PF_COLLECT
-      hipLaunchKernelGGL(prefilter_rescore_list_kernel<false>, dim3(PFCAP / 16, 1), dim3(256), 0, st, cand, ix->d_pf_cnt + q,
-                         reinterpret_cast<const float*>(ix->rows), dim, q_dev, qkeys);
+      with_pf_dimc(dim, [&](auto dc) {
+        hipLaunchKernelGGL((prefilter_collect_kernel<dc.value>), dim3(wgs), dim3(256), lds_q, st, img, (long long)ix->size, dim, q_dev, kth0 + q,
+                           deps + q, ix->d_pf_cnt.p + q, cand, per);
+      });
+      hipLaunchKernelGGL(prefilter_rescore_list_kernel<false>, dim3(PFCAP / 16, 1), dim3(256), 0, st, cand, ix->d_pf_cnt.p + q,
+                         reinterpret_cast<const float*>(ix->rows.p), dim, q_dev, qkeys);
       HIP_TRY(hipGetLastError());
     }
   }
-  hipLaunchKernelGGL(tiled_select_kernel, dim3(nq), dim3(256), (size_t)PFCAP * sizeof(u64), st, ix->d_pf_keys, ix->d_pf_cnt, PFCAP, k,
-                     ix->d_pf_thr, reinterpret_cast<float*>(ix->d_pf_thr + PFQ), out_keys, out_flags, 0);
+  hipLaunchKernelGGL(tiled_select_kernel, dim3(nq), dim3(256), (size_t)PFCAP * sizeof(u64), st, ix->d_pf_keys.p, ix->d_pf_cnt.p, PFCAP, k,
+                     ix->d_pf_thr.p, reinterpret_cast<float*>(ix->d_pf_thr.p + PFQ), out_keys, out_flags, 0);
   HIP_TRY(hipGetLastError());
   return VRAG_OK;
+}
+
+// One-pass route of the prefilter (1 .. pf_onepass_max queries): the fp32 queries and their error bounds go up in one pinned copy
+// (ix->h_pin, behind ix->upload_done), then prefilter_single_enqueue leaves the keys in ix->d_pf_out [nq][k] and the overflow flags
+// behind them (prefilter_onepass_flags).  Sizes the full scan's scratch too: the device call's gated rescan, and
+// vrag_dense_index_run_resident on these resident queries.  The caller waits for the upload before h_pin is written again.
+static unsigned* prefilter_onepass_flags(vrag_dense_index* ix, int nq, int k) {   // [PFQ] unsigned flags behind the keys (PFQ / 2 words)
+  return reinterpret_cast<unsigned*>(ix->d_pf_out.p + (size_t)nq * k);
+}
+static int prefilter_onepass_enqueue(vrag_dense_index* ix, const float* queries, int nq, int k, hipStream_t st) {
+  const int dim = ix->dim;
+  const int n_wg = dense_n_wg(ix->dtype, dim, nq, k, ix->size);
+  HIP_TRY(ix->d_q.grow((size_t)nq * dim + nq));
+  HIP_TRY(ix->d_pf_out.grow((size_t)nq * k + PFQ / 2));
+  HIP_TRY(ix->d_cand.grow((size_t)n_wg * nq * k));
+  HIP_TRY(ix->d_out.grow((size_t)nq * k + nq));
+  float* up = reinterpret_cast<float*>(ix->h_pin);
+  std::memcpy(up, queries, (size_t)nq * dim * sizeof(float));
+  for (int q = 0; q < nq; ++q) up[(size_t)nq * dim + q] = prefilter_eps(ix, queries + (size_t)q * dim, /*rounded_query=*/false);   // fp32 query against the image
+  HIP_TRY(hipMemcpyAsync(ix->d_q.p, up, ((size_t)nq * dim + nq) * sizeof(float), hipMemcpyHostToDevice, st));
+  if (!ix->upload_done) HIP_TRY(hipEventCreateWithFlags(&ix->upload_done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(ix->upload_done, st));
+  ix->resident_split = 0;
+  return prefilter_single_enqueue(ix, ix->d_q.p, ix->d_q.p + (size_t)nq * dim, nq, k, ix->d_pf_out.p, prefilter_onepass_flags(ix, nq, k), st);
 }
 
 int vrag_dense_index_search(vrag_dense_index* ix, const float* queries, int32_t nq, int32_t k, float* scores,
@@ -2964,15 +2937,14 @@ int vrag_dense_index_search(vrag_dense_index* ix, const float* queries, int32_t 
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ix->stream;
   if (ix->lists_done) HIP_TRY(hipStreamWaitEvent(st, ix->lists_done, 0));
-  if (k > KMAX) {   // pages of KMAX on the scalar kernels (fp32 queries; the matrix-core paths stop at k = 16)
-    const int n_wg = dense_n_wg(ix->dtype, ix->dim, nq, KMAX, ix->size);
-    int rc;
-    if ((rc = grow(&ix->d_q, &ix->d_q_elems, (size_t)nq * ix->dim))) return rc;
-    if ((rc = grow(&ix->d_cand, &ix->d_cand_elems, (size_t)n_wg * nq * KMAX))) return rc;
-    if ((rc = grow(&ix->d_out, &ix->d_out_elems, (size_t)nq * KMAX + nq))) return rc;
+  const int split = queries_split(ix, queries, nq);
+  DenseRoute route = dense_plan(ix, nq, k, DenseCaller::Host, split);
+  int rc;
+  if (route == DenseRoute::Paged) {
+    HIP_TRY(ix->d_q.grow((size_t)nq * ix->dim));
     ARG_CHECK((size_t)DQT * ix->dim * sizeof(float) + (size_t)16 * DQT * KMAX * sizeof(u64) <= 160 * 1024,
               "dim too large for the LDS budget");
-    HIP_TRY(hipMemcpyAsync(ix->d_q, queries, (size_t)nq * ix->dim * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ix->d_q.p, queries, (size_t)nq * ix->dim * sizeof(float), hipMemcpyHostToDevice, st));
     if (ix->size == 0) {
       for (size_t i = 0; i < (size_t)nq * k; ++i) {
         scores[i] = -INFINITY;
@@ -2980,68 +2952,40 @@ int vrag_dense_index_search(vrag_dense_index* ix, const float* queries, int32_t 
       }
       return VRAG_OK;
     }
-    return paged_search(nq, k, &ix->d_bound, &ix->d_bound_elems, ix->d_out, st, [&](const u64* bound) -> int {
-      HIP_TRY(dense_launch_all(ix->dtype, ix->rows, (long long)ix->size, ix->dim, ix->d_q, nq, KMAX, ix->d_cand, n_wg, st,
-                               ix->d_out + (size_t)nq * KMAX, ix->d_out, bound));
-      HIP_TRY(launch_topk_merge(ix->d_cand, n_wg, nq, KMAX, ix->d_out, st));
-      return VRAG_OK;
+    return paged_search(nq, k, ix->d_bound, ix->d_out, st, [&](const u64* bound) -> int {
+      return dense_scan_enqueue(ix, nq, KMAX, st, 0, nullptr, bound);
     }, scores, ids);
   }
-  int rc;
   std::vector<u64> keys((size_t)nq * k);
-  // fp32 rows with a prefilter image: rank the image for 64 candidates per query, re-score them exactly (see the kernels).
-  // Where it pays: one or two queries (half the bytes of the fp32 scan) and batches the tiled search takes (the shard read once
-  // instead of once per 32 queries); in between the 32-queries-per-pass exact kernel is already the faster route.  An index
-  // whose data keeps failing the sufficiency test (near-duplicate rows) stops trying.
-  const bool pf_live = prefilter_route_ok(ix, nq, k) && !(ix->pf_searches >= 32 && ix->pf_fallbacks * 4 > ix->pf_searches);
-  if (pf_live) {
-    std::vector<unsigned> flags((size_t)nq);
-    if (nq <= pf_onepass_max(ix->dim)) {
-      // one streaming pass over the image (per query, or -- two to PFQ queries, dim % 256 == 0 -- for all of them together:
-      // prefilter_single_enqueue); queries + bounds go up in one pinned copy, keys + flags come back in one
-      const int dim = ix->dim;
-      float eps[PFQ];
-      for (int q = 0; q < nq; ++q) eps[q] = prefilter_eps(ix, queries + (size_t)q * dim, /*rounded_query=*/false);   // fp32 query against the image
-      if ((rc = grow(&ix->d_q, &ix->d_q_elems, (size_t)nq * dim + nq))) return rc;
-      if ((rc = grow(&ix->d_pf_out, &ix->d_pf_out_elems, (size_t)nq * k + PFQ / 2))) return rc;
-      {   // the full scan's scratch too: vrag_dense_index_run_resident may follow on these resident queries
-        const int n_wg = dense_n_wg(ix->dtype, dim, nq, k, ix->size);
-        if ((rc = grow(&ix->d_cand, &ix->d_cand_elems, (size_t)n_wg * nq * k))) return rc;
-        if ((rc = grow(&ix->d_out, &ix->d_out_elems, (size_t)nq * k + nq))) return rc;
-      }
-      float* up = reinterpret_cast<float*>(ix->h_pin);
-      u64* down = reinterpret_cast<u64*>(ix->h_pin + (size_t)PFQ * (dim + 1) * sizeof(float));
-      std::memcpy(up, queries, (size_t)nq * dim * sizeof(float));
-      for (int q = 0; q < nq; ++q) up[(size_t)nq * dim + q] = eps[q];
-      HIP_TRY(hipMemcpyAsync(ix->d_q, up, ((size_t)nq * dim + nq) * sizeof(float), hipMemcpyHostToDevice, st));
-      ix->resident_split = 0;
-      u64* flag_word = ix->d_pf_out + (size_t)nq * k;   // [PFQ] unsigned flags behind the keys (PFQ / 2 words)
-      if ((rc = prefilter_single_enqueue(ix, ix->d_q, ix->d_q + (size_t)nq * dim, nq, k, ix->d_pf_out, reinterpret_cast<unsigned*>(flag_word), st)))
-        return rc;
-      HIP_TRY(hipMemcpyAsync(down, ix->d_pf_out, ((size_t)nq * k + PFQ / 2) * sizeof(u64), hipMemcpyDeviceToHost, st));
+  std::vector<unsigned> flags((size_t)nq);
+  if (route == DenseRoute::PrefilterBatch) {
+    // flagged queries are re-answered by the full scan behind their flags (groups of 32 without a flag leave at once), so one
+    // bunched query costs one pass, not the batch's
+    if ((rc = prefilter_batch_enqueue(ix, queries, nq, k, st, /*rescan=*/false))) return rc;
+    HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_pf_out.p, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(flags.data(), ix->d_pf_flag.p, flags.size() * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ++ix->pf_searches;
+    size_t n_bad = 0;
+    for (unsigned f : flags) n_bad += f != 0u ? 1 : 0;
+    if (n_bad * 4 > flags.size()) ++ix->pf_fallbacks;   // a quarter of the batch re-scanned: counts against the route
+    if (n_bad) {   // the flags are on the host anyway: the scan is enqueued only when one is up
+      if ((rc = prefilter_rescan_enqueue(ix, nq, k, st, ix->d_pf_flag.p))) return rc;
+      HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_pf_out.p, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
-      std::memcpy(keys.data(), down, keys.size() * sizeof(u64));
-      std::memcpy(flags.data(), down + (size_t)nq * k, (size_t)nq * sizeof(unsigned));
-    } else {
-      // batches: flagged queries are re-answered by the full scan behind their flags (groups of 32 without a flag leave at once),
-      // so one bunched query costs one pass, not the batch's
-      if ((rc = prefilter_batch_enqueue(ix, queries, nq, k, st, /*rescan=*/false))) return rc;
-      HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_pf_out, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipMemcpyAsync(flags.data(), ix->d_pf_flag, flags.size() * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      ++ix->pf_searches;
-      size_t n_bad = 0;
-      for (unsigned f : flags) n_bad += f != 0u ? 1 : 0;
-      if (n_bad * 4 > flags.size()) ++ix->pf_fallbacks;   // a quarter of the batch re-scanned: counts against the route
-      if (n_bad) {   // the flags are on the host anyway: the scan is enqueued only when one is up
-        if ((rc = prefilter_rescan_enqueue(ix, nq, k, st))) return rc;
-        HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_pf_out, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-      }
-      decode_keys(keys, nq, k, 0, nullptr, scores, ids);
-      return VRAG_OK;
     }
-    HIP_TRY(hipStreamSynchronize(st));   // also retires the query / eps uploads before the host buffers go out of scope
+    decode_keys(keys, nq, k, 0, nullptr, scores, ids);
+    return VRAG_OK;
+  }
+  if (route == DenseRoute::PrefilterOnePass) {
+    // one streaming pass over the image (per query, or -- two to PFQ queries, dim % 256 == 0 -- for all of them together:
+    // prefilter_single_enqueue); queries + bounds go up in one pinned copy, keys + flags come back in one
+    if ((rc = prefilter_onepass_enqueue(ix, queries, nq, k, st))) return rc;
+    u64* down = reinterpret_cast<u64*>(ix->h_pin + (size_t)PFQ * (ix->dim + 1) * sizeof(float));
+    HIP_TRY(hipMemcpyAsync(down, ix->d_pf_out.p, ((size_t)nq * k + PFQ / 2) * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // also retires the query / eps upload of the pinned staging
+    std::memcpy(keys.data(), down, keys.size() * sizeof(u64));
+    std::memcpy(flags.data(), down + (size_t)nq * k, (size_t)nq * sizeof(unsigned));
     ++ix->pf_searches;
     bool bad = false;
     for (unsigned f : flags) bad = bad || f != 0u;
@@ -3050,14 +2994,15 @@ int vrag_dense_index_search(vrag_dense_index* ix, const float* queries, int32_t 
       return VRAG_OK;
     }
     ++ix->pf_fallbacks;   // scores bunched within the image's error bound: the full fp32 scan answers
+    route = DenseRoute::Scan;   // (fp32 rows: the tiled search is for bf16 rows)
   }
   bool host_rescue = false;
-  if ((rc = dense_search_enqueue(ix, queries, nq, k, st, 0, nullptr, &host_rescue))) return rc;
-  HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_out, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
+  if ((rc = dense_search_enqueue(ix, queries, nq, k, st, route, split, 0, nullptr, &host_rescue))) return rc;
+  HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_out.p, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
   std::vector<unsigned> ovf;
   if (host_rescue) {
     ovf.resize((size_t)nq);
-    HIP_TRY(hipMemcpyAsync(ovf.data(), ix->d_tcnt + nq, (size_t)nq * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(ovf.data(), ix->d_tcnt.p + nq, (size_t)nq * sizeof(unsigned), hipMemcpyDeviceToHost, st));
   }
   HIP_TRY(hipStreamSynchronize(st));
   bool flagged = false;
@@ -3067,13 +3012,9 @@ int vrag_dense_index_search(vrag_dense_index* ix, const float* queries, int32_t 
     // beyond the first stage).  The flags are on the host anyway: the batch goes through the pass kernels -- per-workgroup lists,
     // nothing to overflow, 0.45 ms per 32 queries -- and the flagged queries take their lists from there (the device rescue pass
     // of the resident / sharded search walks the shard per flagged query: 2 ms for one, 8 ms for 64 of 64).
-    const int n_wg = dense_n_wg(ix->dtype, ix->dim, nq, k, ix->size);
-    HIP_TRY(dense_launch_all(ix->dtype, ix->rows, (long long)ix->size, ix->dim, ix->d_q, nq, k, ix->d_cand, n_wg, st,
-                             ix->d_out + (size_t)nq * k, ix->d_out, nullptr, ix->resident_split));
-    HIP_TRY(launch_topk_merge(ix->d_cand, n_wg, nq, k, ix->d_out, st));
-    HIP_TRY(hipGetLastError());
+    if ((rc = dense_scan_enqueue(ix, nq, k, st, ix->resident_split))) return rc;
     std::vector<u64> again((size_t)nq * k);
-    HIP_TRY(hipMemcpyAsync(again.data(), ix->d_out, again.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(again.data(), ix->d_out.p, again.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (int q = 0; q < nq; ++q)
       if (ovf[q]) std::copy(again.begin() + (size_t)q * k, again.begin() + (size_t)(q + 1) * k, keys.begin() + (size_t)q * k);
@@ -3085,49 +3026,34 @@ int vrag_dense_index_search(vrag_dense_index* ix, const float* queries, int32_t 
 int vrag_dense_index_search_device(vrag_dense_index* ix, const float* queries, int32_t nq, int32_t k, const int64_t* row_map,
                                    int64_t n_map, int64_t id_base, float* out_scores, int64_t* out_ids, void* stream) {
   ARG_CHECK(ix && queries && out_scores && out_ids && nq > 0, "bad arguments");
-  ARG_CHECK(k > 0 && k <= KMAX, "k must be in [1, %d] for a device-resident search (got %d)", KMAX, k);
+  ARG_CHECK(k > 0, "k must be in [1, %d] for a device-resident search (got %d)", KMAX, k);
   ARG_CHECK(!row_map || n_map >= 0, "negative row map length");
   std::lock_guard<std::mutex> lk(ix->mu);
   HIP_TRY(hipSetDevice(ix->device));
   // NULL = the legacy default stream, NOT the handle's own stream: the caller's next operation (the all-gather) is
   // ordered against the stream it named, and torch's default stream IS the null stream
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int split = queries_split(ix, queries, nq);
+  const DenseRoute route = dense_plan(ix, nq, k, DenseCaller::Device, split);
+  ARG_CHECK(route != DenseRoute::Paged, "k must be in [1, %d] for a device-resident search (got %d)", KMAX, k);
   int rc;
   const long long n = (long long)nq * k;
   const u64* result = nullptr;
-  if (nq > pf_onepass_max(ix->dim) && prefilter_route_ok(ix, nq, k)) {
-    // fp32 rows with a prefilter image, batch route (prefilter_batch_enqueue): nothing returns to the host
+  if (route == DenseRoute::PrefilterBatch) {
+    // nothing returns to the host: the gated rescan runs on the device
     if ((rc = prefilter_batch_enqueue(ix, queries, nq, k, st))) return rc;
-    result = ix->d_pf_out;
-  } else if (nq <= pf_onepass_max(ix->dim) && prefilter_route_ok(ix, nq, k)) {
-    // one to PFQ queries: the one-pass route, then the full scan behind the overflow flags (its workgroups leave at once when no
-    // flag is up) and the per-query pick -- as above, nothing returns to the host
-    const int dim = ix->dim;
+    result = ix->d_pf_out.p;
+  } else if (route == DenseRoute::PrefilterOnePass) {
+    // the one-pass route, then the full scan behind the overflow flags (its workgroups leave at once when no flag is up) and the
+    // per-query pick -- as above, nothing returns to the host
     if (ix->lists_done) HIP_TRY(hipStreamWaitEvent(st, ix->lists_done, 0));
-    const int n_wg = dense_n_wg(ix->dtype, dim, nq, k, ix->size);
-    if ((rc = grow(&ix->d_q, &ix->d_q_elems, (size_t)nq * dim + nq))) return rc;
-    if ((rc = grow(&ix->d_pf_out, &ix->d_pf_out_elems, (size_t)nq * k + PFQ / 2))) return rc;
-    if ((rc = grow(&ix->d_cand, &ix->d_cand_elems, (size_t)n_wg * nq * k))) return rc;
-    if ((rc = grow(&ix->d_out, &ix->d_out_elems, (size_t)nq * k + nq))) return rc;
-    float* up = reinterpret_cast<float*>(ix->h_pin);
-    std::memcpy(up, queries, (size_t)nq * dim * sizeof(float));
-    for (int q = 0; q < nq; ++q) up[(size_t)nq * dim + q] = prefilter_eps(ix, queries + (size_t)q * dim, /*rounded_query=*/false);
-    HIP_TRY(hipMemcpyAsync(ix->d_q, up, ((size_t)nq * dim + nq) * sizeof(float), hipMemcpyHostToDevice, st));
-    if (!ix->upload_done) HIP_TRY(hipEventCreateWithFlags(&ix->upload_done, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(ix->upload_done, st));
-    ix->resident_split = 0;
-    unsigned* flags = reinterpret_cast<unsigned*>(ix->d_pf_out + (size_t)nq * k);
-    if ((rc = prefilter_single_enqueue(ix, ix->d_q, ix->d_q + (size_t)nq * dim, nq, k, ix->d_pf_out, flags, st))) return rc;
-    HIP_TRY(dense_launch_all(ix->dtype, ix->rows, (long long)ix->size, dim, ix->d_q, nq, k, ix->d_cand, n_wg, st,
-                             ix->d_out + (size_t)nq * k, ix->d_out, nullptr, 0, flags));
-    HIP_TRY(launch_topk_merge(ix->d_cand, n_wg, nq, k, ix->d_out, st));
-    hipLaunchKernelGGL(prefilter_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ix->d_pf_out, ix->d_out, flags, nq, k);
-    HIP_TRY(hipGetLastError());
+    if ((rc = prefilter_onepass_enqueue(ix, queries, nq, k, st))) return rc;
+    if ((rc = prefilter_rescan_enqueue(ix, nq, k, st, prefilter_onepass_flags(ix, nq, k)))) return rc;
     HIP_TRY(hipEventSynchronize(ix->upload_done));   // the pinned staging is free for the next call
-    result = ix->d_pf_out;
+    result = ix->d_pf_out.p;
   } else {
-    if ((rc = dense_search_enqueue(ix, queries, nq, k, st))) return rc;
-    result = ix->d_out;
+    if ((rc = dense_search_enqueue(ix, queries, nq, k, st, route, split))) return rc;
+    result = ix->d_out.p;
   }
   hipLaunchKernelGGL(topk_export_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, result, n,
                      reinterpret_cast<const long long*>(row_map), (long long)n_map, (long long)id_base, out_scores,
@@ -3139,24 +3065,20 @@ int vrag_dense_index_search_device(vrag_dense_index* ix, const float* queries, i
 }
 
 // Device-resident variant for benchmarking: queries already uploaded by a previous search call;
-// runs the two kernels only (no copies, no sync).
+// runs the kernels only (no copies, no sync, no allocation).
 int vrag_dense_index_run_resident(vrag_dense_index* ix, int32_t nq, int32_t k, void* stream) {
   ARG_CHECK(ix && nq > 0 && k > 0 && k <= KMAX, "bad arguments");
   std::lock_guard<std::mutex> lk(ix->mu);
-  ARG_CHECK(ix->d_q && ix->d_q_elems >= (size_t)nq * ix->dim && ix->size > 0, "call vrag_dense_index_search once first");
+  ARG_CHECK(ix->d_q.p && ix->d_q.n >= (size_t)nq * ix->dim && ix->size > 0, "call vrag_dense_index_search once first");
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ix->stream;
-  if (dense_use_tiled(ix->dtype, ix->dim, nq, k, (long long)ix->size, ix->resident_split ? kTiledMinBf16Pairs : kTiledMinBf16)) {
-    ARG_CHECK(ix->d_out_elems >= (size_t)nq * k, "scratch too small");
+  if (dense_plan(ix, nq, k, DenseCaller::Resident, ix->resident_split) == DenseRoute::Tiled) {
+    ARG_CHECK(ix->d_out.n >= (size_t)nq * k, "scratch too small");
     return dense_tiled_search(ix, nq, k, st);
   }
   const int n_wg = dense_n_wg(ix->dtype, ix->dim, nq, k, ix->size);
-  ARG_CHECK(ix->d_cand_elems >= (size_t)n_wg * nq * k && ix->d_out_elems >= (size_t)nq * k + nq, "scratch too small");
-  HIP_TRY(dense_launch_all(ix->dtype, ix->rows, (long long)ix->size, ix->dim, ix->d_q, nq, k, ix->d_cand, n_wg, st,
-                             ix->d_out + (size_t)nq * k, ix->d_out, nullptr, ix->resident_split));
-  HIP_TRY(launch_topk_merge(ix->d_cand, n_wg, nq, k, ix->d_out, st));
-  HIP_TRY(hipGetLastError());
-  return VRAG_OK;
+  ARG_CHECK(ix->d_cand.n >= (size_t)n_wg * nq * k && ix->d_out.n >= (size_t)nq * k + nq, "scratch too small");
+  return dense_scan_enqueue(ix, nq, k, st, ix->resident_split);
 }
 
 int vrag_sparse_index_create(int32_t vocab, int64_t n_docs, const int64_t* indptr, const int32_t* indices,
@@ -3220,16 +3142,16 @@ int vrag_sparse_index_create(int32_t vocab, int64_t n_docs, const int64_t* indpt
   ix->n_slices = n_slices;
   std::vector<unsigned> docid(std::max<size_t>(1, (size_t)n_docs));
   for (int64_t p = 0; p < n_docs; ++p) docid[p] = (unsigned)perm[p];
-  hipError_t e = hipMalloc((void**)&ix->cols, cols.size() * sizeof(unsigned short));
-  if (e == hipSuccess) e = hipMalloc((void**)&ix->d_docid, docid.size() * sizeof(unsigned));
-  if (e == hipSuccess) e = hipMemcpy(ix->d_docid, docid.data(), docid.size() * sizeof(unsigned), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc((void**)&ix->vals, vals.size() * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void**)&ix->slice_off, off.size() * sizeof(long long));
-  if (e == hipSuccess) e = hipMalloc((void**)&ix->slice_len, std::max<size_t>(1, len.size()) * sizeof(int));
-  if (e == hipSuccess) e = hipMemcpy(ix->cols, cols.data(), cols.size() * sizeof(unsigned short), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(ix->vals, vals.data(), vals.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(ix->slice_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(ix->slice_len, len.data(), len.size() * sizeof(int), hipMemcpyHostToDevice);
+  hipError_t e = ix->cols.grow(cols.size());
+  if (e == hipSuccess) e = ix->d_docid.grow(docid.size());
+  if (e == hipSuccess) e = hipMemcpy(ix->d_docid.p, docid.data(), docid.size() * sizeof(unsigned), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = ix->vals.grow(vals.size());
+  if (e == hipSuccess) e = ix->slice_off.grow(off.size());
+  if (e == hipSuccess) e = ix->slice_len.grow(std::max<size_t>(1, len.size()));
+  if (e == hipSuccess) e = hipMemcpy(ix->cols.p, cols.data(), cols.size() * sizeof(unsigned short), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(ix->vals.p, vals.data(), vals.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(ix->slice_off.p, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(ix->slice_len.p, len.data(), len.size() * sizeof(int), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking);
   if (e != hipSuccess) {
     set_error("sparse index allocation failed: %s", hipGetErrorString(e));
@@ -3244,22 +3166,10 @@ void vrag_sparse_index_destroy(vrag_sparse_index* ix) {
   if (!ix) return;
   (void)hipSetDevice(ix->device);
   (void)hipDeviceSynchronize();
-  if (ix->cols) (void)hipFree(ix->cols);
-  if (ix->vals) (void)hipFree(ix->vals);
-  if (ix->slice_off) (void)hipFree(ix->slice_off);
-  if (ix->slice_len) (void)hipFree(ix->slice_len);
-  if (ix->d_q) (void)hipFree(ix->d_q);
-  if (ix->d_qcsr) (void)hipFree(ix->d_qcsr);
-  if (ix->d_qmap) (void)hipFree(ix->d_qmap);
-  if (ix->d_qw) (void)hipFree(ix->d_qw);
-  if (ix->d_cand) (void)hipFree(ix->d_cand);
-  if (ix->d_out) (void)hipFree(ix->d_out);
-  if (ix->d_bound) (void)hipFree(ix->d_bound);
-  if (ix->d_docid) (void)hipFree(ix->d_docid);
   if (ix->upload_done) (void)hipEventDestroy(ix->upload_done);
   if (ix->lists_done) (void)hipEventDestroy(ix->lists_done);
   if (ix->stream) (void)hipStreamDestroy(ix->stream);
-  delete ix;
+  delete ix;   // the device arrays free themselves
 }
 
 int vrag_sparse_index_stats(vrag_sparse_index* ix, int64_t* n_docs, int64_t* nnz, int64_t* padded_nnz) {
@@ -3304,53 +3214,39 @@ static int sparse_launch(vrag_sparse_index* ix, int nq, int k, hipStream_t st, i
     ARG_CHECK(sparse_multi_fits(ix->vocab, QB, k), "k = %d does not fit the batched pass the resident queries were prepared for", k);
     const int pad = (QB == 16 && sparse_multi_fits(ix->vocab, QB, k, 4)) ? 4 : 0;   // the kernel's own LDS layout: the tables in HBM do not change
     const size_t lds = sparse_multi_lds(ix->vocab, QB, k, pad);
-    static bool attr_m = false;
-    if (!attr_m) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&sparse_topk_multi_kernel<8, 16, 0>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&sparse_topk_multi_kernel<16, 16, 0>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&sparse_topk_multi_kernel<16, 16, 4>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr_m = true;
-    }
+    HIP_TRY((QB == 16 && pad == 4 ? set_max_dynamic_lds<&sparse_topk_multi_kernel<16, 16, 4>>(160 * 1024)
+             : QB == 16             ? set_max_dynamic_lds<&sparse_topk_multi_kernel<16, 16, 0>>(160 * 1024)
+                                    : set_max_dynamic_lds<&sparse_topk_multi_kernel<8, 16, 0>>(160 * 1024)));
     for (int q0 = 0, ps = 0; q0 < nq; q0 += QB, ++ps) {
       auto go = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(n_wg), dim3(1024), lds, st, ix->cols, ix->vals, ix->slice_off, ix->slice_len, ix->n_slices,
-                           (long long)ix->n_docs, ix->d_qmap + (size_t)ps * vpad, ix->d_qw + (size_t)ps * QB * SUW, ix->vocab,
-                           ix->pass_union[ps], nq, q0, k, slices_per_wg, ix->d_cand, ix->d_docid);
+        hipLaunchKernelGGL(kern, dim3(n_wg), dim3(1024), lds, st, ix->cols.p, ix->vals.p, ix->slice_off.p, ix->slice_len.p, ix->n_slices,
+                           (long long)ix->n_docs, ix->d_qmap.p + (size_t)ps * vpad, ix->d_qw.p + (size_t)ps * QB * SUW, ix->vocab,
+                           ix->pass_union[ps], nq, q0, k, slices_per_wg, ix->d_cand.p, ix->d_docid.p);
       };
       if (QB == 16 && pad == 4) go(&sparse_topk_multi_kernel<16, 16, 4>);
       else if (QB == 16) go(&sparse_topk_multi_kernel<16, 16, 0>);
       else go(&sparse_topk_multi_kernel<8, 16, 0>);
       HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(launch_topk_merge(ix->d_cand, n_wg, nq, k, ix->d_out, st));
+    HIP_TRY(launch_topk_merge(ix->d_cand.p, n_wg, nq, k, ix->d_out.p, st));
     HIP_TRY(hipGetLastError());
     return VRAG_OK;
   }
   const bool ldsq = (size_t)ix->vocab * sizeof(float) + (size_t)16 * k * sizeof(u64) <= 160 * 1024;
   const size_t lds = (size_t)16 * k * sizeof(u64) + (ldsq ? (size_t)ix->vocab * sizeof(float) : 0);
-  if (ldsq) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&sparse_topk_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr_set = true;
-    }
-  }
+  if (ldsq) HIP_TRY(set_max_dynamic_lds<&sparse_topk_kernel<true>>(160 * 1024));
   for (int q = 0; q < nq; ++q) {
     if (ldsq)
-      hipLaunchKernelGGL((sparse_topk_kernel<true>), dim3(n_wg), dim3(1024), lds, st, ix->cols, ix->vals, ix->slice_off,
-                         ix->slice_len, ix->n_slices, (long long)ix->n_docs, ix->d_q, ix->vocab, nq, q, k,
-                         slices_per_wg, ix->d_cand, ix->d_docid, bound);
+      hipLaunchKernelGGL((sparse_topk_kernel<true>), dim3(n_wg), dim3(1024), lds, st, ix->cols.p, ix->vals.p, ix->slice_off.p,
+                         ix->slice_len.p, ix->n_slices, (long long)ix->n_docs, ix->d_q.p, ix->vocab, nq, q, k,
+                         slices_per_wg, ix->d_cand.p, ix->d_docid.p, bound);
     else
-      hipLaunchKernelGGL((sparse_topk_kernel<false>), dim3(n_wg), dim3(1024), lds, st, ix->cols, ix->vals,
-                         ix->slice_off, ix->slice_len, ix->n_slices, (long long)ix->n_docs, ix->d_q, ix->vocab, nq, q, k,
-                         slices_per_wg, ix->d_cand, ix->d_docid, bound);
+      hipLaunchKernelGGL((sparse_topk_kernel<false>), dim3(n_wg), dim3(1024), lds, st, ix->cols.p, ix->vals.p,
+                         ix->slice_off.p, ix->slice_len.p, ix->n_slices, (long long)ix->n_docs, ix->d_q.p, ix->vocab, nq, q, k,
+                         slices_per_wg, ix->d_cand.p, ix->d_docid.p, bound);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(launch_topk_merge(ix->d_cand, n_wg, nq, k, ix->d_out, st));
+  HIP_TRY(launch_topk_merge(ix->d_cand.p, n_wg, nq, k, ix->d_out.p, st));
   HIP_TRY(hipGetLastError());
   return VRAG_OK;
 }
@@ -3364,8 +3260,8 @@ static int sparse_search_enqueue(vrag_sparse_index* ix, const int64_t* q_indptr,
   int rc;
   if (!ix->upload_done) HIP_TRY(hipEventCreateWithFlags(&ix->upload_done, hipEventDisableTiming));
   if (ix->lists_done) HIP_TRY(hipStreamWaitEvent(st, ix->lists_done, 0));
-  if ((rc = grow(&ix->d_cand, &ix->d_cand_elems, (size_t)n_wg * nq * k))) return rc;
-  if ((rc = grow(&ix->d_out, &ix->d_out_elems, (size_t)nq * k))) return rc;
+  HIP_TRY(ix->d_cand.grow((size_t)n_wg * nq * k));
+  HIP_TRY(ix->d_out.grow((size_t)nq * k));
   // Batched path: two or more queries; per pass of SQB queries the union of their terms gets ids 1 .. SUW-1, the
   // u16 map + weight tables + top-k lists must fit the LDS.
   const int vpad = (ix->vocab + 7) & ~7;
@@ -3407,21 +3303,12 @@ static int sparse_search_enqueue(vrag_sparse_index* ix, const int64_t* q_indptr,
   }
   ix->last_multi = multi;
   if (multi) {
-    auto regrow = [&](auto** ptr, size_t* have, size_t want, size_t esz) -> int {
-      if (*have >= want) return VRAG_OK;
-      if (*ptr) (void)hipFree(*ptr);
-      *ptr = nullptr;
-      *have = 0;
-      HIP_TRY(hipMalloc(reinterpret_cast<void**>(ptr), want * esz));
-      *have = want;
-      return VRAG_OK;
-    };
-    if ((rc = regrow(&ix->d_qmap, &ix->d_qmap_elems, maps.size(), sizeof(unsigned short)))) return rc;
-    if ((rc = regrow(&ix->d_qw, &ix->d_qw_elems, wts.size(), sizeof(float)))) return rc;
+    HIP_TRY(ix->d_qmap.grow(maps.size()));
+    HIP_TRY(ix->d_qw.grow(wts.size()));
     ix->pass_union = unions;
     ix->pass_qb = QB;
-    HIP_TRY(hipMemcpyAsync(ix->d_qmap, maps.data(), maps.size() * sizeof(unsigned short), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(ix->d_qw, wts.data(), wts.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ix->d_qmap.p, maps.data(), maps.size() * sizeof(unsigned short), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ix->d_qw.p, wts.data(), wts.size() * sizeof(float), hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(ix->upload_done, st));
     ix->upload_pending = true;   // the host tables stay in the handle: no wait here
     int nwg3 = 0;
@@ -3443,13 +3330,13 @@ static int sparse_search_enqueue(vrag_sparse_index* ix, const int64_t* q_indptr,
       memcpy(blob.data() + off_val, q_values + q_indptr[0], (size_t)nnz_q * sizeof(float));
     }
   }
-  if ((rc = grow(&ix->d_q, &ix->d_q_elems, (size_t)nq * ix->vocab))) return rc;
-  if ((rc = grow(&ix->d_qcsr, &ix->d_qcsr_bytes, blob.size()))) return rc;
-  HIP_TRY(hipMemsetAsync(ix->d_q, 0, (size_t)nq * ix->vocab * sizeof(float), st));
-  HIP_TRY(hipMemcpyAsync(ix->d_qcsr, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(ix->d_q.grow((size_t)nq * ix->vocab));
+  HIP_TRY(ix->d_qcsr.grow(blob.size()));
+  HIP_TRY(hipMemsetAsync(ix->d_q.p, 0, (size_t)nq * ix->vocab * sizeof(float), st));
+  HIP_TRY(hipMemcpyAsync(ix->d_qcsr.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(hipEventRecord(ix->upload_done, st));
-  hipLaunchKernelGGL(sparse_scatter_queries_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, reinterpret_cast<const long long*>(ix->d_qcsr),
-                     reinterpret_cast<const int*>(ix->d_qcsr + off_idx), reinterpret_cast<const float*>(ix->d_qcsr + off_val), nq, ix->vocab, ix->d_q);
+  hipLaunchKernelGGL(sparse_scatter_queries_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, reinterpret_cast<const long long*>(ix->d_qcsr.p),
+                     reinterpret_cast<const int*>(ix->d_qcsr.p + off_idx), reinterpret_cast<const float*>(ix->d_qcsr.p + off_val), nq, ix->vocab, ix->d_q.p);
   HIP_TRY(hipGetLastError());
   ix->upload_pending = true;   // the host blob stays in the handle: no wait here
   int nwg2 = 0;
@@ -3472,22 +3359,22 @@ int vrag_sparse_index_search(vrag_sparse_index* ix, const int64_t* q_indptr, con
     for (int q = 0; q < nq; ++q)
       for (int64_t j = q_indptr[q]; j < q_indptr[q + 1]; ++j)
         ARG_CHECK(q_indices[j] >= 0 && q_indices[j] < ix->vocab, "query %d: term id %d outside the vocabulary", q, q_indices[j]);
-    if ((rc = grow(&ix->d_cand, &ix->d_cand_elems, (size_t)n_wg * nq * KMAX))) return rc;
-    if ((rc = grow(&ix->d_out, &ix->d_out_elems, (size_t)nq * KMAX))) return rc;
+    HIP_TRY(ix->d_cand.grow((size_t)n_wg * nq * KMAX));
+    HIP_TRY(ix->d_out.grow((size_t)nq * KMAX));
     std::vector<float> qd((size_t)nq * ix->vocab, 0.f);
     for (int q = 0; q < nq; ++q)
       for (int64_t j = q_indptr[q]; j < q_indptr[q + 1]; ++j) qd[(size_t)q * ix->vocab + q_indices[j]] = q_values[j];
-    if ((rc = grow(&ix->d_q, &ix->d_q_elems, qd.size()))) return rc;
-    HIP_TRY(hipMemcpyAsync(ix->d_q, qd.data(), qd.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    HIP_TRY(ix->d_q.grow(qd.size()));
+    HIP_TRY(hipMemcpyAsync(ix->d_q.p, qd.data(), qd.size() * sizeof(float), hipMemcpyHostToDevice, st));
     ix->last_multi = false;
-    return paged_search(nq, k, &ix->d_bound, &ix->d_bound_elems, ix->d_out, st, [&](const u64* bound) -> int {
+    return paged_search(nq, k, ix->d_bound, ix->d_out, st, [&](const u64* bound) -> int {
       int nwg = 0;
       return sparse_launch(ix, nq, KMAX, st, &nwg, bound);
     }, scores, ids);   // the first page's stream sync also keeps `qd` alive until its upload has been consumed
   }
   if ((rc = sparse_search_enqueue(ix, q_indptr, q_indices, q_values, nq, k, st))) return rc;
   std::vector<u64> keys((size_t)nq * k);
-  HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_out, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_out.p, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   decode_keys(keys, nq, k, 0, nullptr, scores, ids);
   return VRAG_OK;
@@ -3505,7 +3392,7 @@ int vrag_sparse_index_search_device(vrag_sparse_index* ix, const int64_t* q_indp
   int rc;
   if ((rc = sparse_search_enqueue(ix, q_indptr, q_indices, q_values, nq, k, st))) return rc;
   const long long n = (long long)nq * k;
-  hipLaunchKernelGGL(topk_export_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ix->d_out, n,
+  hipLaunchKernelGGL(topk_export_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ix->d_out.p, n,
                      reinterpret_cast<const long long*>(row_map), (long long)n_map, (long long)id_base, out_scores,
                      reinterpret_cast<long long*>(out_ids));
   HIP_TRY(hipGetLastError());
@@ -3517,8 +3404,8 @@ int vrag_sparse_index_search_device(vrag_sparse_index* ix, const int64_t* q_indp
 int vrag_sparse_index_run_resident(vrag_sparse_index* ix, int32_t nq, int32_t k, void* stream) {
   ARG_CHECK(ix && nq > 0 && k > 0 && k <= KMAX, "bad arguments");
   std::lock_guard<std::mutex> lk(ix->mu);
-  ARG_CHECK(ix->last_multi ? (ix->d_qmap && (int)ix->pass_union.size() >= (nq + ix->pass_qb - 1) / ix->pass_qb)
-                           : (ix->d_q && ix->d_q_elems >= (size_t)nq * ix->vocab),
+  ARG_CHECK(ix->last_multi ? (ix->d_qmap.p && (int)ix->pass_union.size() >= (nq + ix->pass_qb - 1) / ix->pass_qb)
+                           : (ix->d_q.p && ix->d_q.n >= (size_t)nq * ix->vocab),
             "call vrag_sparse_index_search with at least this many queries first");
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ix->stream;
