@@ -7,7 +7,10 @@ classification head) over one batch of 256 synthetic (question, chunk) sequences
 GPU (torch.distributed / RCCL only for the barrier + max-over-ranks), every rank processes its
 own 256 chunks (weak scaling, no data-path collective: the units are independent).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps (sampled HIP-event profiling on, which gives
+`breakdown` and `roofline`) and prints the line; `--full` adds what takes runs of its own: the single-stream pass
+(`roofline.isolated_*`), the informational legs, the CPU baseline and parity (`--cpu-budget`), and for N > 1 the sharded
+retrieval leg.
 """
 from __future__ import annotations
 
@@ -680,13 +683,16 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5,
-                    help="timed steps of the headline (the metric).  Work outside that timed region follows it: a one-stream profiling pass of 3 "
-                         "steps (skipped by --no-profile), and informational legs (api, ragged, f16 token head) of max(3, STEPS) "
-                         "steps plus an aligned ragged leg of 3 (skipped by --cpu-budget 0)")
+                    help="timed steps of the headline (the metric).  With --full, work outside that timed region follows it: a one-stream "
+                         "profiling pass of 3 steps (skipped by --no-profile), and informational legs (api, ragged, f16 token head) of "
+                         "max(3, STEPS) steps plus an aligned ragged leg of 3 (skipped by --cpu-budget 0)")
     ap.add_argument("--warmup", type=int, default=2, help="untimed steps before the headline's timed steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the one-stream profiling pass, the informational legs, the CPU baseline and "
+                         "parity and, for N > 1, the sharded retrieval leg (default: the headline only)")
     ap.add_argument("--chunks", type=int, default=256, help="sequences per step per GPU")
     ap.add_argument("--micro-batch-tokens", type=int, default=int(os.environ.get("VRAG_MICRO_BATCH", "65536")))
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU-baseline work (0 = skip)")
+    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU-baseline work with --full (0 = skip it and the legs)")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--operand-dtype", choices=["bf16", "f16"], default="bf16",
                     help="MFMA operand type (bf16 = the metric's dtype; f16 = the highlighter extractor's default, informational)")
@@ -799,7 +805,7 @@ def main() -> None:
     # Second, untimed pass with the micro-batches serialised on ONE stream: per-kernel durations
     # without the cross-stream overlap of the timed region (kernel quality, not job throughput).
     iso = None
-    if not args.no_profile and rank == 0:
+    if args.full and not args.no_profile and rank == 0:
         eng.set_concurrency(1)
         eng.run(stream)
         torch.cuda.synchronize()
@@ -811,7 +817,7 @@ def main() -> None:
         iso = eng.read_profile(reset=True)
         eng.set_concurrency(2)
 
-    sharded = None   # N > 1: runs AFTER rank 0 has assembled the line (below), under a watchdog
+    sharded = None   # N > 1 with --full: runs AFTER rank 0 has assembled the line (below), under a watchdog
 
     if rank == 0:
         total_chunks = world * n_chunks * args.steps
@@ -907,7 +913,7 @@ def main() -> None:
                                     "avg_launch_ms": v["avg_launch_ms"]} for c, v in iso_cls.items()},
                     "breakdown_ms_per_step": {k: v[0] / 2 for k, v in iso.items() if v[1] > 0}}
         cpu, parity, recall, api, tok16, ragged, parity_rel, parity_prob, e2e = None, None, None, None, None, None, None, None, None
-        if world == 1 and args.cpu_budget > 0:
+        if args.full and world == 1 and args.cpu_budget > 0:
             if roof is not None:
                 roof.update(power_limited_rate(shape, min(args.micro_batch_tokens or n_chunks * SEQ, n_chunks * SEQ), local_rank, value))
             api = api_leg(eng, shape, n_chunks, steps=max(3, args.steps))
@@ -954,7 +960,7 @@ def main() -> None:
     else:
         out = None
     eng.close()
-    if world > 1:
+    if world > 1 and args.full:
         # Second timed leg (the retrieval exchange).  It is the first code of this repository to meet a real xGMI ring -- a new RCCL
         # communicator beside torch's, an all-gather on it -- so it runs under a watchdog: if it has not returned after
         # VRAG_BENCH_SHARDED_TIMEOUT seconds (default 240) rank 0 prints the line it already has, with the timeout as the leg's error,

@@ -12,9 +12,9 @@ for step in "$@"; do
   case "$step" in
     tests) python -m pytest tests -m gpu -q -x --durations=12 > "$OUT/pytest.log" 2>&1; tail -25 "$OUT/pytest.log" ;;
     smoke) python __graft_entry__.py smoke 2>&1 | tail -2 | tee "$OUT/smoke.log" ;;
-    bench) python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"; tail -c 1500 "$OUT/bench.json" ;;
-    bench_f16) python bench.py --operand-dtype f16 --cpu-budget 0 > "$OUT/bench_f16.json" 2>> "$OUT/bench.err"; cut -c1-300 "$OUT/bench_f16.json" ;;
-    bench_large) python bench.py --model large --cpu-budget 0 > "$OUT/bench_large.json" 2>> "$OUT/bench.err"; cut -c1-300 "$OUT/bench_large.json" ;;
+    bench) python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"; tail -c 1500 "$OUT/bench.json" ;;
+    bench_f16) python bench.py --full --operand-dtype f16 --cpu-budget 0 > "$OUT/bench_f16.json" 2>> "$OUT/bench.err"; cut -c1-300 "$OUT/bench_f16.json" ;;
+    bench_large) python bench.py --full --model large --cpu-budget 0 > "$OUT/bench_large.json" 2>> "$OUT/bench.err"; cut -c1-300 "$OUT/bench_large.json" ;;
     energy) python tools/energy_by_class.py --out "$OUT/energy_by_class.json" 2>&1 | tee "$OUT/energy.log" ;;
     energy_step) python tools/energy_probe.py --steps 300 > "$OUT/energy_line.json" 2>&1; cat "$OUT/energy_line.json" ;;
     profile) bash tools/profile_round.sh "$TAG/prof" ;;

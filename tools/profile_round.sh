@@ -7,9 +7,9 @@ TAG=${1:-round}
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
-python bench.py > "$OUT/bench_line.json" 2> "$OUT/bench.err"
+python bench.py --full > "$OUT/bench_line.json" 2> "$OUT/bench.err"
 cd /tmp && export TMPDIR=/tmp
-B="python $REPO/bench.py --cpu-budget 0"
+B="python $REPO/bench.py --full --cpu-budget 0"
 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -- $B --steps 3 --warmup 1 > "$OUT/kt.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -- $B --steps 2 --warmup 1 --no-profile > "$OUT/pmc_fetch.log" 2>&1
 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" -- $B --steps 2 --warmup 1 --no-profile > "$OUT/pmc_write.log" 2>&1

@@ -3,7 +3,7 @@
 text committed under profiles/.  Usage: tools/rocpd_summary.py results.db [W K] [> profiles/x.txt]
 
 With W K (the --warmup/--steps the profiled `bench.py` ran with) two more tables are printed: the
-dispatches of the timed region (micro-batches on two streams) and those of bench.py's single-stream
+dispatches of the timed region (micro-batches on two streams) and those of bench.py --full's single-stream
 pass (1 untimed + 2 profiled steps, always last) -- the phases bench.py's `roofline.timed_region`
 and `roofline` report with HIP events."""
 import os
