@@ -181,6 +181,21 @@ int vrag_encoder_set_pair_head(vrag_encoder* enc, const float* pooler_w /*[H,H]*
 int vrag_encoder_run_pair_head(vrag_encoder* enc, void* stream);
 int vrag_encoder_read_pair_logits(vrag_encoder* enc, float* logits /*[n_seqs, labels]*/, void* stream);
 
+/* Sequence-classification head of ModernBERT handles (ModernBertForSequenceClassification: the cross-encoder rerankers of
+ * the ModernBERT family, e.g. gte-reranker-modernbert-base; transformers models/modernbert/modeling_modernbert.py,
+ * ModernBertPredictionHead + classifier).  Per sequence s of the batch loaded last:
+ *   p = final_norm(h)[first token of s]                      pooling 0 (classifier_pooling "cls")
+ *     = mean of final_norm(h) over every token of s          pooling 1 ("mean"; [CLS] and [SEP]s included)
+ *   logits[s] = cls_w . LayerNorm(gelu_erf(dense_w . p + dense_b); norm_w, norm_b) + cls_b
+ * dense_b / norm_b may be NULL (classifier_bias / norm_bias false); labels 1..64; all arithmetic fp32.  BERT-family
+ * handles return VRAG_ERR_INVALID (their cross-encoder head is set_pair_head).  Setting the head again replaces it. */
+int vrag_encoder_set_seq_head(vrag_encoder* enc, const float* dense_w /*[H,H]*/, const float* dense_b /*[H] or NULL*/,
+                              const float* norm_w /*[H]*/, const float* norm_b /*[H] or NULL*/,
+                              const float* cls_w /*[labels,H]*/, const float* cls_b /*[labels]*/,
+                              int32_t num_labels, int32_t pooling /*0 = cls, 1 = mean*/);
+int vrag_encoder_run_seq_head(vrag_encoder* enc, void* stream);
+int vrag_encoder_read_seq_logits(vrag_encoder* enc, float* logits /*[n_seqs, labels]*/, void* stream);
+
 /* Packed batch: `ids` is the plain concatenation of n_seqs unpadded sequences of lengths
  * seq_lens[i] (positions restart at 0 per sequence, like the reference's B=1 forward). */
 int vrag_encoder_load_batch(vrag_encoder* enc, const int32_t* ids, const int32_t* seq_lens, int32_t n_seqs,

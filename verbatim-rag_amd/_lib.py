@@ -88,6 +88,9 @@ SIGNATURES = {
     "vrag_encoder_set_pair_head": (C.c_int, [_H, _FP, _FP, _FP, _FP, C.c_int32]),
     "vrag_encoder_run_pair_head": (C.c_int, [_H, C.c_void_p]),
     "vrag_encoder_read_pair_logits": (C.c_int, [_H, _FP, C.c_void_p]),
+    "vrag_encoder_set_seq_head": (C.c_int, [_H, _FP, _FP, _FP, _FP, _FP, _FP, C.c_int32, C.c_int32]),
+    "vrag_encoder_run_seq_head": (C.c_int, [_H, C.c_void_p]),
+    "vrag_encoder_read_seq_logits": (C.c_int, [_H, _FP, C.c_void_p]),
     "vrag_encoder_load_batch": (C.c_int, [_H, _IP, _IP, C.c_int32, C.c_void_p]),
     "vrag_encoder_run": (C.c_int, [_H, C.c_void_p]),
     "vrag_encoder_run_layers": (C.c_int, [_H, C.c_int32, C.c_void_p]),

@@ -279,6 +279,10 @@ struct vrag_encoder {
   int pr_labels = 0;
   int *d_first_row = nullptr, *h_first_row = nullptr;   // [max_seqs]
   float* d_pair_out = nullptr;                          // [max_seqs, pr_labels]
+  // sequence-classification head (arch 0: ModernBertForSequenceClassification)
+  float *sq_wdT = nullptr, *sq_bd = nullptr, *sq_wn = nullptr, *sq_bn = nullptr, *sq_wc = nullptr, *sq_bc = nullptr;
+  int sq_labels = 0, sq_pool_mean = 0;
+  float *d_sq_pooled = nullptr, *d_sq_out = nullptr;    // [max_seqs, H], [max_seqs, sq_labels]
   int i_pad = 0;        // GeGLU width padded to a multiple of 128 (2*i_pad = whole 256-wide GEMM tiles)
   int attn_w = 0;       // width of the q / k / v^T / o buffers = num_heads * 64 (> hidden_size when head_dim is 32)
   float q_scale = 0.125f * 1.4426950408889634f;  // head_dim^-1/2 * log2(e)
@@ -1567,6 +1571,70 @@ int vrag_encoder_read_pair_logits(vrag_encoder* e, float* logits, void* stream) 
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t st = pick_stream(e, stream);
   HIP_TRY(hipMemcpyAsync(logits, e->d_pair_out, (size_t)e->n_seqs * e->pr_labels * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return VRAG_OK;
+}
+
+int vrag_encoder_set_seq_head(vrag_encoder* e, const float* dense_w, const float* dense_b, const float* norm_w,
+                              const float* norm_b, const float* cls_w, const float* cls_b, int32_t num_labels, int32_t pooling) {
+  ARG_CHECK(e && dense_w && norm_w && cls_w && cls_b && num_labels > 0 && num_labels <= 64 && (pooling == 0 || pooling == 1),
+            "bad sequence head arguments");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  ARG_CHECK(e->arch == 0, "the sequence-classification head is defined for the ModernBERT encoder only "
+                          "(BERT-family cross-encoders: vrag_encoder_set_pair_head)");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  const int H = e->cfg.hidden_size;
+  // setting the head again (other biases, pooling or labels): the previous buffers go first
+  HIP_TRY(hipDeviceSynchronize());
+  for (float** p : {&e->sq_wdT, &e->sq_bd, &e->sq_wn, &e->sq_bn, &e->sq_wc, &e->sq_bc, &e->d_sq_pooled, &e->d_sq_out})
+    dev_release(e, p);
+  e->sq_labels = 0;
+  // the kernel streams the dense weight row by row of INPUT features: [out, in] (HF Linear) -> [in, out]
+  std::vector<float> wT((size_t)H * H);
+  for (int o = 0; o < H; ++o)
+    for (int i = 0; i < H; ++i) wT[(size_t)i * H + o] = dense_w[(size_t)o * H + i];
+  int rc;
+  if ((rc = upload_f32(e, &e->sq_wdT, wT.data(), (size_t)H * H))) return rc;
+  if (dense_b && (rc = upload_f32(e, &e->sq_bd, dense_b, H))) return rc;
+  if ((rc = upload_f32(e, &e->sq_wn, norm_w, H))) return rc;
+  if (norm_b && (rc = upload_f32(e, &e->sq_bn, norm_b, H))) return rc;
+  if ((rc = upload_f32(e, &e->sq_wc, cls_w, (size_t)num_labels * H))) return rc;
+  if ((rc = upload_f32(e, &e->sq_bc, cls_b, num_labels))) return rc;
+  if ((rc = dev_alloc(e, &e->d_sq_pooled, (size_t)e->cfg.max_seqs * H))) return rc;
+  if ((rc = dev_alloc(e, &e->d_sq_out, (size_t)e->cfg.max_seqs * num_labels))) return rc;
+  e->sq_pool_mean = pooling;
+  e->sq_labels = num_labels;
+  return VRAG_OK;
+}
+
+int vrag_encoder_run_seq_head(vrag_encoder* e, void* stream) {
+  int rc = check_ready(e);
+  if (rc) return rc;
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  ARG_CHECK(e->arch == 0, "the sequence-classification head is defined for the ModernBERT encoder only "
+                          "(BERT-family cross-encoders: vrag_encoder_set_pair_head)");
+  ARG_CHECK(e->sq_labels > 0, "sequence head not set (vrag_encoder_set_seq_head)");
+  ARG_CHECK(e->ran, "encoder has not run on this batch");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  hipStream_t st = pick_stream(e, stream);
+  const int ms = e->cfg.max_seqs;
+  ProfScope ps(e, VRAG_PROF_HEAD, st);
+  // first rows and lengths: the device copy load_batch made of the batch's geometry (d_seq_meta: [3][max_seqs])
+  HIP_TRY(launch_seq_head(e->h, e->final_norm, e->cfg.norm_eps, e->cfg.hidden_size, e->d_seq_meta, e->d_seq_meta + 2 * ms,
+                          e->n_seqs, e->sq_pool_mean, e->d_sq_pooled, e->sq_wdT, e->sq_bd, e->sq_wn, e->sq_bn, e->sq_wc,
+                          e->sq_bc, e->sq_labels, e->d_sq_out, st));
+  return VRAG_OK;
+}
+
+int vrag_encoder_read_seq_logits(vrag_encoder* e, float* logits, void* stream) {
+  int rc = check_ready(e);
+  if (rc) return rc;
+  ARG_CHECK(logits, "null output");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  ARG_CHECK(e->sq_labels > 0, "sequence head not set");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  hipStream_t st = pick_stream(e, stream);
+  HIP_TRY(hipMemcpyAsync(logits, e->d_sq_out, (size_t)e->n_seqs * e->sq_labels * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return VRAG_OK;
 }

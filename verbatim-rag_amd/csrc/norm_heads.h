@@ -1,5 +1,6 @@
 // HBM-bound row kernels: embedding gather + LayerNorm, LayerNorm, and the fused
-// final-LayerNorm + range-mean heads (sentence classifier / dense pooling), gfx950.
+// final-LayerNorm + range-mean heads (sentence classifier / dense pooling), the cross-encoder heads (BERT pooler,
+// ModernBERT sequence classification), gfx950.
 #pragma once
 #include "common.h"
 
@@ -44,6 +45,16 @@ hipError_t launch_ln_classifier(const float* x, const float* lnw, float eps, int
 hipError_t launch_pooler_classifier(const float* h, int H, const int* first_row, int n_seqs, const float* Wp,
                                     const float* bp, const float* Wc, const float* bc, int num_labels, float* logits,
                                     hipStream_t stream);
+
+// ModernBertForSequenceClassification head over the packed batch's sequences (first rows seq_row[s], lengths seq_len[s]):
+//   p = LN(h[first token]) * lnw                         (pool_mean == 0, classifier_pooling "cls")
+//     = mean over the sequence's tokens of LN(h) * lnw     (pool_mean == 1, "mean")
+//   logits[s][c] = Wc[c] . (LN(gelu_erf(Wd . p + bd)) * wn + bn) + bc[c]     (bd / bn may be null)
+// Two launches: the pooled rows into `pooled` [n_seqs, H] (one workgroup per sequence), then the dense layer, GELU, LayerNorm
+// and classifier for blocks of pooled rows held in LDS.  WdT is the dense weight TRANSPOSED ([in, out]); all fp32.
+hipError_t launch_seq_head(const float* h, const float* lnw, float eps, int H, const int* seq_row, const int* seq_len,
+                           int n_seqs, int pool_mean, float* pooled, const float* WdT, const float* bd, const float* wn,
+                           const float* bn, const float* Wc, const float* bc, int num_labels, float* logits, hipStream_t stream);
 
 // 1 if an fp32 -> fp16 operand conversion in this file's kernels clamped since the last reset (common.h).
 unsigned norm_heads_f16_saturated(bool reset);

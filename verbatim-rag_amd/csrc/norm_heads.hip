@@ -2,7 +2,8 @@
 // Restates nn.LayerNorm(bias=False) (transformers modeling_modernbert.py:61,70,312,314,476),
 // the embedding gather (:64-71), the reference QAModel sentence head
 // (packages/core/verbatim_core/extractor_models/model.py:82-113) and the
-// ModernBertPredictionHead norm + classifier (modeling_modernbert.py:481-490,697-699).
+// ModernBertPredictionHead norm + classifier (modeling_modernbert.py:481-490,697-699), and the
+// ModernBertForSequenceClassification head (cls / mean pooling + dense + GELU + LayerNorm + classifier).
 #include "norm_heads.h"
 
 namespace vrag {
@@ -297,6 +298,151 @@ __global__ __launch_bounds__(256) void pooler_classifier_kernel(const float* __r
   }
 }
 
+// Sequence-classification head, phase 1 (ModernBertForSequenceClassification): one workgroup per sequence, the final
+// LayerNorm per token, then the pooled row -- the first token (pool_mean == 0) or the mean over every token of the
+// sequence (the 4 waves stride the tokens, LDS reduction in a fixed order: a row does not depend on its batch mates).
+__global__ __launch_bounds__(256) void seq_pool_kernel(const float* __restrict__ h, const float* __restrict__ lnw, float eps,
+                                                        int H, const int* __restrict__ seq_row, const int* __restrict__ seq_len,
+                                                        int pool_mean, float* __restrict__ pooled) {
+  __shared__ float red[4][MAXV * 256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int s = blockIdx.x;
+  const int r0 = seq_row[s], n = pool_mean ? seq_len[s] : 1;
+  f32x4 acc[MAXV], wv[MAXV];
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  load_row(lnw, H, lane, wv);
+  // four token rows in flight per wave (a wave owns tokens wave, wave + 4, ...; the sum order depends on n only)
+  int t = wave;
+  for (; t + 12 < n; t += 16) {
+    f32x4 x[4][MAXV];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) load_row(h + (size_t)(r0 + t + 4 * u) * H, H, lane, x[u]);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      ln_row(x[u], wv, H, lane, eps);
+#pragma unroll
+      for (int i = 0; i < MAXV; ++i) acc[i] += x[u][i];
+    }
+  }
+  for (; t < n; t += 4) {
+    f32x4 x[MAXV];
+    load_row(h + (size_t)(r0 + t) * H, H, lane, x);
+    ln_row(x, wv, H, lane, eps);
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) acc[i] += x[i];
+  }
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) *reinterpret_cast<f32x4*>(&red[wave][lane * 4 + 256 * i]) = acc[i];
+  __syncthreads();
+  if (wave != 0) return;
+  const float inv_n = 1.0f / (float)n;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) {
+    const int c = lane * 4 + 256 * i;
+    if (c < H) {
+      f32x4 v = *reinterpret_cast<const f32x4*>(&red[0][c]);
+      v += *reinterpret_cast<const f32x4*>(&red[1][c]);
+      v += *reinterpret_cast<const f32x4*>(&red[2][c]);
+      v += *reinterpret_cast<const f32x4*>(&red[3][c]);
+      *reinterpret_cast<f32x4*>(pooled + (size_t)s * H + c) = v * inv_n;
+    }
+  }
+}
+
+// Phase 2: logits = Wc . LN(gelu(Wd . p + bd); wn, bn) + bc for a block of kSeqHeadRows pooled rows per workgroup.  The rows sit
+// in LDS; thread t owns the output columns t, t + 256, ... and streams the TRANSPOSED dense weight WdT[k][col] (a wave reads 256
+// contiguous bytes per k), so Wd is read once per row block, not once per sequence.  Every column is one fp32 fmaf chain over k
+// in order: a row's result does not depend on the rows it shares the block with.  The dense outputs go back into the same LDS
+// block, then one wave per row applies GELU, the LayerNorm and the classifier (wave-shuffle reduction per label).
+constexpr int kSeqHeadRows = 8;
+
+__global__ __launch_bounds__(256) void seq_head_kernel(const float* __restrict__ pooled, int n_seqs, int H,
+                                                        const float* __restrict__ WdT, const float* __restrict__ bd,
+                                                        const float* __restrict__ wn, const float* __restrict__ bn, float eps,
+                                                        const float* __restrict__ Wc, const float* __restrict__ bc,
+                                                        int num_labels, float* __restrict__ logits) {
+  __shared__ float blk[kSeqHeadRows][MAXV * 256];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int s0 = blockIdx.x * kSeqHeadRows;
+  const int nr = min(kSeqHeadRows, n_seqs - s0);
+  // pooled rows -> LDS (rows past the batch are zero: their columns are computed and never written)
+  for (int i = tid * 4; i < kSeqHeadRows * H; i += 256 * 4) {
+    const int r = i / H, c = i - r * H;   // H % 4 == 0: a float4 never straddles two rows
+    const f32x4 v = r < nr ? *reinterpret_cast<const f32x4*>(pooled + (size_t)(s0 + r) * H + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    *reinterpret_cast<f32x4*>(&blk[r][c]) = v;
+  }
+  __syncthreads();
+  float acc[kSeqHeadRows][MAXV];
+#pragma unroll
+  for (int r = 0; r < kSeqHeadRows; ++r)
+#pragma unroll
+    for (int j = 0; j < MAXV; ++j) acc[r][j] = 0.f;
+  // the next k-step's weights are loaded before this one's FMAs: a load round trip overlaps a step of arithmetic
+  float wcur[4][MAXV], wnext[4][MAXV];
+  auto load_w = [&](int k, float (&w)[4][MAXV]) {
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+      for (int j = 0; j < MAXV; ++j) {
+        const int col = tid + 256 * j;
+        w[kk][j] = (k < H && col < H) ? WdT[(size_t)(k + kk) * H + col] : 0.f;
+      }
+  };
+  load_w(0, wcur);
+  for (int k = 0; k < H; k += 4) {
+    load_w(k + 4, wnext);
+    f32x4 p[kSeqHeadRows];
+#pragma unroll
+    for (int r = 0; r < kSeqHeadRows; ++r) p[r] = *reinterpret_cast<const f32x4*>(&blk[r][k]);   // LDS broadcast
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+      for (int j = 0; j < MAXV; ++j)
+#pragma unroll
+        for (int r = 0; r < kSeqHeadRows; ++r) acc[r][j] = fmaf(p[r][kk], wcur[kk][j], acc[r][j]);
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+      for (int j = 0; j < MAXV; ++j) wcur[kk][j] = wnext[kk][j];
+  }
+  __syncthreads();   // every thread is done reading the pooled rows
+#pragma unroll
+  for (int j = 0; j < MAXV; ++j) {
+    const int col = tid + 256 * j;
+    if (col < H) {
+      const float b = bd ? bd[col] : 0.f;
+#pragma unroll
+      for (int r = 0; r < kSeqHeadRows; ++r) blk[r][col] = acc[r][j] + b;
+    }
+  }
+  __syncthreads();
+  f32x4 wv[MAXV];
+  load_row(wn, H, lane, wv);
+  for (int r = wave; r < nr; r += 4) {
+    f32x4 x[MAXV];
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+      const int c = lane * 4 + 256 * i;
+      x[i] = c < H ? *reinterpret_cast<const f32x4*>(&blk[r][c]) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) x[i][j] = gelu_erf(x[i][j]);   // gelu_erf(0) = 0: the padding lanes stay out of the LN sums
+    }
+    ln_row(x, wv, H, lane, eps, bn);
+    for (int c = 0; c < num_labels; ++c) {
+      f32x4 wc[MAXV];
+      load_row(Wc + (size_t)c * H, H, lane, wc);
+      float d = 0.f;
+#pragma unroll
+      for (int i = 0; i < MAXV; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) d += x[i][j] * wc[i][j];
+      d = wave_sum(d);
+      if (lane == 0) logits[(size_t)(s0 + r) * num_labels + c] = d + bc[c];
+    }
+  }
+}
+
 }  // namespace
 
 hipError_t launch_embed_ln(const int* ids, const float* E, const float* w, float eps, int H, int rows, float* h,
@@ -354,6 +500,19 @@ hipError_t launch_pooler_classifier(const float* h, int H, const int* first_row,
   if (H > MAXV * 256 || (H & 3)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(pooler_classifier_kernel, dim3(n_seqs), dim3(256), 0, stream, h, H, first_row, Wp, bp, Wc, bc, num_labels,
                      logits);
+  return hipGetLastError();
+}
+
+hipError_t launch_seq_head(const float* h, const float* lnw, float eps, int H, const int* seq_row, const int* seq_len,
+                           int n_seqs, int pool_mean, float* pooled, const float* WdT, const float* bd, const float* wn,
+                           const float* bn, const float* Wc, const float* bc, int num_labels, float* logits, hipStream_t stream) {
+  if (n_seqs <= 0) return hipSuccess;
+  if (H > MAXV * 256 || (H & 3) || !lnw || num_labels <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(seq_pool_kernel, dim3(n_seqs), dim3(256), 0, stream, h, lnw, eps, H, seq_row, seq_len, pool_mean, pooled);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return err;
+  hipLaunchKernelGGL(seq_head_kernel, dim3((n_seqs + kSeqHeadRows - 1) / kSeqHeadRows), dim3(256), 0, stream, pooled, n_seqs, H,
+                     WdT, bd, wn, bn, eps, Wc, bc, num_labels, logits);
   return hipGetLastError();
 }
 

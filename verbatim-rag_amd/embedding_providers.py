@@ -105,7 +105,8 @@ def load_encoder_directory(model_path: str, device: int = 0, max_tokens: int = 6
     """(engine, tokenizer, raw config) from a local HF checkpoint directory -- the local-files counterpart of the model
     names the reference hands to sentence-transformers (`SpladeProvider(model_name)`, embedding_providers.py:117-133;
     `SentenceTransformersProvider(model_name)`, :52-71).  BERT / DistilBERT checkpoints get a `BertEncoderEngine` (MLM
-    and pair heads attached when the tensors are there), ModernBERT checkpoints an `EncoderEngine` (+ MLM head).
+    and pair heads attached when the tensors are there), ModernBERT checkpoints an `EncoderEngine` (+ MLM head, or the sequence-classification
+    head when `architectures` names ModernBertForSequenceClassification).
     `splade_split_operands=False`: the MLM / SPLADE head with plain 16-bit operands (a third of the decoder work, weights within
     ~1e-2 of the fp32 head instead of 2e-5; include/vrag_amd.h vrag_encoder_set_head_precision)."""
     import json
@@ -115,18 +116,24 @@ def load_encoder_directory(model_path: str, device: int = 0, max_tokens: int = 6
     from .weights import load_bert_safetensors_dir, load_safetensors_dir
 
     with open(os.path.join(model_path, "config.json")) as f:
-        model_type = json.load(f).get("model_type")
+        raw_cfg = json.load(f)
+    model_type = raw_cfg.get("model_type")
     kw = dict(max_tokens=max_tokens, max_seqs=max_seqs, max_seq_len=max_seq_len, max_ranges=max(max_seqs, 64), device=device,
               operand_dtype=operand_dtype, **engine_kw)
     if model_type in ("bert", "distilbert"):
         shape, weights, cfg = load_bert_safetensors_dir(model_path)
         eng = engine_mod.BertEncoderEngine(shape, weights, mlm_split_operands=splade_split_operands, **kw)
     elif model_type == "modernbert":
+        seq_head = _modernbert_seq_head(model_path, raw_cfg)
         shape, tensors, cfg = load_safetensors_dir(model_path)
         eng = engine_mod.EncoderEngine(shape, tensors, **kw)
         if "head.dense.weight" in tensors and "decoder.bias" in tensors:        # ModernBertForMaskedLM: tied decoder
             eng.set_mlm_head(tensors["head.dense.weight"], tensors["head.norm.weight"], tensors["decoder.bias"],
                              tensors.get("decoder.weight"), split_operands=splade_split_operands)
+        if seq_head is not None:
+            eng.set_seq_head(tensors["head.dense.weight"], tensors["head.dense.bias"] if seq_head["dense_bias"] else None,
+                             tensors["head.norm.weight"], None, tensors["classifier.weight"], tensors["classifier.bias"],
+                             pooling=seq_head["pooling"])
     else:
         raise ValueError(f"{model_path}: model_type {model_type!r} is not bert / distilbert / modernbert")
     try:
@@ -138,6 +145,23 @@ def load_encoder_directory(model_path: str, device: int = 0, max_tokens: int = 6
 
         tokenizer = Tokenizer.from_file(os.path.join(model_path, "tokenizer.json"))
     return eng, tokenizer, cfg
+
+
+def _modernbert_seq_head(model_path: str, cfg: dict) -> Optional[dict]:
+    """The sequence-classification head a ModernBERT checkpoint carries, decided by `architectures` (never by tensor names:
+    ModernBertForTokenClassification uses the same `head.*` / `classifier.*` names) -> {"pooling", "dense_bias"} or None.
+    What the engine cannot compute is refused here, naming the config key (transformers ModernBertConfig)."""
+    if "ModernBertForSequenceClassification" not in (cfg.get("architectures") or []):
+        return None
+    if cfg.get("norm_bias", False):
+        raise ValueError(f"{model_path}: config.json norm_bias: true is not supported (the encoder's LayerNorms take no bias)")
+    act = cfg.get("classifier_activation", "gelu")
+    if act != "gelu":
+        raise ValueError(f"{model_path}: config.json classifier_activation {act!r} is not supported (only 'gelu')")
+    pooling = cfg.get("classifier_pooling", "cls")
+    if pooling not in ("cls", "mean"):
+        raise ValueError(f"{model_path}: config.json classifier_pooling {pooling!r} is not supported (only 'cls' / 'mean')")
+    return {"pooling": pooling, "dense_bias": bool(cfg.get("classifier_bias", False))}
 
 
 def _st_pooling_mode(model_path: str, default: str = "cls") -> str:

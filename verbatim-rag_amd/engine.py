@@ -163,6 +163,7 @@ class EncoderEngine:
         self.lock = threading.RLock()
         self.qa_labels = 0
         self.token_labels = 0
+        self.pair_labels = 0       # sequence-pair (cross-encoder) head: set_seq_head here, set_pair_head on BERT handles
         self.has_mlm = False
         self._n_tokens = 0
         self._n_seqs = 0
@@ -222,6 +223,40 @@ class EncoderEngine:
                    self._lib.vrag_encoder_set_mlm_head(self._h, _fp(d), _fp(n), _fp(dw) if dw is not None else None,
                                                        _fp(b) if b is not None else None))
         self.has_mlm = True
+
+    SEQ_POOLING = {"cls": 0, "mean": 1}
+
+    def set_seq_head(self, dense_w, dense_b, norm_w, norm_b, cls_w, cls_b, pooling: str = "cls") -> None:
+        """ModernBertForSequenceClassification head (`head.dense`, `head.norm`, `classifier`; `classifier_pooling`
+        "cls" | "mean"): logits = cls_w . LN(gelu(dense_w . p + dense_b); norm_w, norm_b) + cls_b over the pooled final
+        hidden state p of each sequence.  `dense_b` / `norm_b` may be None (`classifier_bias` / `norm_bias` false)."""
+        if pooling not in self.SEQ_POOLING:
+            raise ValueError(f"pooling must be 'cls' or 'mean' (got {pooling!r})")
+        opt = lambda a: _f32(a) if a is not None else None  # noqa: E731
+        p = lambda a: _fp(a) if a is not None else None  # noqa: E731
+        d, db, n, nb, w, b = _f32(dense_w), opt(dense_b), _f32(norm_w), opt(norm_b), _f32(cls_w), _f32(cls_b)
+        _lib.check("vrag_encoder_set_seq_head", self._lib.vrag_encoder_set_seq_head(
+            self._h, _fp(d), p(db), _fp(n), p(nb), _fp(w), _fp(b), w.shape[0], self.SEQ_POOLING[pooling]))
+        self.pair_labels = int(w.shape[0])
+
+    def run_seq_head(self, stream: Optional[int] = None) -> None:
+        _lib.check("vrag_encoder_run_seq_head", self._lib.vrag_encoder_run_seq_head(self._h, stream))
+
+    def read_seq_logits(self, stream: Optional[int] = None) -> np.ndarray:
+        out = np.empty((self._n_seqs, self.pair_labels), dtype=np.float32)
+        _lib.check("vrag_encoder_read_seq_logits", self._lib.vrag_encoder_read_seq_logits(self._h, _fp(out), stream))
+        return out
+
+    def pair_logits(self, sequences: Sequence[Sequence[int]], type_ids: Optional[Sequence[Sequence[int]]] = None) -> np.ndarray:
+        """[n_seqs, labels] sequence-classification logits of packed `[CLS] a [SEP] b [SEP]` sequences.  ModernBERT has no
+        token-type embedding: `type_ids` is accepted (the BERT engines' signature) and ignored."""
+        if not self.pair_labels:
+            raise ValueError("engine has no pair head (ModernBertForSequenceClassification weights or set_seq_head)")
+        with self.lock:
+            self.load_batch(sequences)
+            self.run()
+            self.run_seq_head()
+            return self.read_seq_logits()
 
     # ------------------------------------------------------------------ batch
     def load_batch(self, sequences: Sequence[Sequence[int]], stream: Optional[int] = None) -> None:

@@ -53,6 +53,18 @@ class StaticVerbatimPipeline:
             logging.warning(f"Reranker failed, using original order: {exc}")
             return results
 
+    def _apply_reranker_batch(self, questions: list, per_q: list) -> list:
+        """`[_apply_reranker(q, r) ...]` through one `rerank_batch` call (every question's pairs in shared device batches) when
+        the reranker has it; if that call raises, the per-question path runs instead, with its own failure rule."""
+        if self.reranker and hasattr(self.reranker, "rerank_batch"):
+            try:
+                return list(self.reranker.rerank_batch(questions, per_q))
+            except Exception as exc:
+                import logging
+
+                logging.warning(f"Batched reranker failed, reranking per question: {exc}")
+        return [self._apply_reranker(q, r) for q, r in zip(questions, per_q)]
+
     def query(self, question: str, k: Optional[int] = None, filter: Optional[str] = None,
               hybrid_weights: Optional[Dict[str, float]] = None, rrf_k: int = 60) -> QueryResponse:
         results = self.index.query(text=question, k=k or self.k, filter=filter, hybrid_weights=hybrid_weights, rrf_k=rrf_k)
@@ -75,7 +87,7 @@ class StaticVerbatimPipeline:
         else:
             per_q = [self.index.query(text=q, k=k or self.k, filter=filter, hybrid_weights=hybrid_weights, rrf_k=rrf_k)
                      for q in questions]
-        per_q = [self._apply_reranker(q, r) for q, r in zip(questions, per_q)]
+        per_q = self._apply_reranker_batch(questions, per_q)
         if hasattr(self.extractor, "extract_spans_batch"):
             spans_per_q = self.extractor.extract_spans_batch(questions, per_q)
         else:

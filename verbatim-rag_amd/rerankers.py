@@ -4,17 +4,24 @@ Kept: `Reranker.rerank(question, results) -> List[SearchResult]` / `rerank_async
 `text_field` handling and the head/tail split (verbatim_rag/rerankers.py:14-41), the ordering rule of
 `SentenceTransformersReranker.rerank` (`sorted(zip(scores, head), reverse=True)`, :128-134); the caller is
 `VerbatimRAG._apply_reranker` (verbatim_rag/core.py:125-140).  Replaced: sentence-transformers `CrossEncoder.predict`
-(third-party, absent here) by the HIP BERT-family encoder + pooler/classifier head on packed `[CLS] q [SEP] d [SEP]`
-pairs with token types 0 / 1 (`cross-encoder/ms-marco-MiniLM-L-6-v2` is a 6-layer, 384-wide, 12-head BERT: head_dim
-32, run on the head_dim-64 kernels with zero-padded heads).  Scores are the classifier logits; CrossEncoder applies a
-monotone activation (identity or sigmoid) to a single label, which does not change the order.
+(third-party, absent here) by the HIP encoders on packed `[CLS] q [SEP] d [SEP]` pairs: the BERT-family encoder +
+pooler/classifier head with token types 0 / 1 (`cross-encoder/ms-marco-MiniLM-L-6-v2` is a 6-layer, 384-wide, 12-head
+BERT: head_dim 32, run on the head_dim-64 kernels with zero-padded heads), or the ModernBERT encoder + the
+ModernBertForSequenceClassification head (cls / mean pooling, dense, GELU, LayerNorm, classifier; e.g.
+`gte-reranker-modernbert-base`, 8 192-token context).  Scores are the classifier logits; CrossEncoder applies a monotone
+activation (identity or sigmoid) to a single label, which does not change the order.  `rerank_batch` reranks several
+questions' results through shared device batches (the serving path of `StaticVerbatimPipeline.query_batch`).
 """
 from __future__ import annotations
 
 import asyncio
 import threading
 from abc import ABC, abstractmethod
-from typing import Any, List, Sequence, Tuple
+from typing import Any, List, Optional, Sequence, Tuple
+
+# Longest sequence the fused QKV + attention kernel takes (csrc/qkv_attn.h kFusedMaxSeq): a device batch holding one longer
+# sequence runs every layer on the separate attention kernel, so rerank_batch never mixes the two lengths in one batch.
+FUSED_ATTENTION_MAX_LEN = 512
 
 
 class Reranker(ABC):
@@ -64,23 +71,42 @@ def pack_pair(q_ids: Sequence[int], d_ids: Sequence[int], cls_id: int, sep_id: i
 
 
 class GpuCrossEncoderReranker(BaseReranker):
-    """SentenceTransformersReranker (verbatim_rag/rerankers.py:109-134) on a `BertEncoderEngine` with a pair head."""
+    """SentenceTransformersReranker (verbatim_rag/rerankers.py:109-134) on a `BertEncoderEngine` with a pair head or an
+    `EncoderEngine` (ModernBERT) with a sequence-classification head: both expose `pair_labels` and
+    `pair_logits(sequences, type_ids)`."""
 
     def __init__(self, engine: Any, tokenizer: Any, rerank_k: int = 50, text_field: str = "text", max_length: int = 512):
         super().__init__(rerank_k=rerank_k, text_field=text_field)
         if not getattr(engine, "pair_labels", 0):
-            raise ValueError("engine has no pair head (BertForSequenceClassification weights)")
+            raise ValueError("engine has no pair head (BertForSequenceClassification / ModernBertForSequenceClassification weights)")
         self.engine, self.tokenizer = engine, tokenizer
         self.max_length = min(max_length, engine.max_seq_len)
         self._lock = getattr(engine, "lock", None) or threading.Lock()   # the handle's own lock: wrappers may share it
 
     @classmethod
-    def from_directory(cls, model_path: str, device: int = 0, rerank_k: int = 50, max_length: int = 512, **kw) -> "GpuCrossEncoderReranker":
-        """`SentenceTransformersReranker(model_name)` (rerankers.py:109-134) for a `BertForSequenceClassification`
-        checkpoint on disk (e.g. a downloaded `cross-encoder/ms-marco-MiniLM-L-6-v2`)."""
+    def from_directory(cls, model_path: str, device: int = 0, rerank_k: int = 50, max_length: Optional[int] = None,
+                       operand_dtype: Optional[str] = None, **kw) -> "GpuCrossEncoderReranker":
+        """`SentenceTransformersReranker(model_name)` (rerankers.py:109-134) for a checkpoint on disk: a
+        `BertForSequenceClassification` (e.g. a downloaded `cross-encoder/ms-marco-MiniLM-L-6-v2`; defaults: 512 tokens,
+        the loader's fp16 operands) or a `ModernBertForSequenceClassification` (e.g. `gte-reranker-modernbert-base`;
+        defaults: the checkpoint's `max_position_embeddings` as CrossEncoder takes it, bf16 operands -- a pooled logit feeds
+        an ordering, like the sentence classifier's)."""
+        import json
+        import os
+
         from .embedding_providers import load_encoder_directory
 
-        engine, tokenizer, _cfg = load_encoder_directory(model_path, device=device, max_seq_len=max_length)
+        with open(os.path.join(model_path, "config.json")) as f:
+            cfg = json.load(f)
+        load_kw = {}
+        if cfg.get("model_type") == "modernbert":
+            max_length = max_length or int(cfg.get("max_position_embeddings", 8192))
+            load_kw["operand_dtype"] = operand_dtype or "bf16"
+        else:
+            max_length = max_length or 512
+            if operand_dtype:
+                load_kw["operand_dtype"] = operand_dtype
+        engine, tokenizer, _cfg = load_encoder_directory(model_path, device=device, max_seq_len=max_length, **load_kw)
         return cls(engine, tokenizer, rerank_k=rerank_k, max_length=max_length, **kw)
 
     def _ids(self, text: str) -> List[int]:
@@ -113,3 +139,64 @@ class GpuCrossEncoderReranker(BaseReranker):
         scores = self.score(question, self._get_texts(head))
         ranked = [r for _, r in sorted(zip(scores, head), reverse=True)]   # rerankers.py:133
         return ranked + tail
+
+    def _device_batches(self, packed: List[Tuple[List[int], List[int]]]) -> List[List[int]]:
+        """Indices of `packed` in device batches: ordered by packed length (similar lengths share a batch), cut at the
+        engine's max_seqs / max_tokens, and at the fused-attention limit -- pairs longer than FUSED_ATTENTION_MAX_LEN
+        go to batches of their own, so one long pair never pushes a batch of short ones off the fused kernel."""
+        order = sorted(range(len(packed)), key=lambda i: len(packed[i][0]))
+        batches: List[List[int]] = []
+        cur: List[int] = []
+        tok = 0
+        for i in order:
+            n = len(packed[i][0])
+            if n > self.engine.max_tokens:
+                raise ValueError("a single pair exceeds the engine workspace")
+            crosses = bool(cur) and len(packed[cur[-1]][0]) <= FUSED_ATTENTION_MAX_LEN < n
+            if cur and (crosses or len(cur) >= self.engine.max_seqs or tok + n > self.engine.max_tokens):
+                batches.append(cur)
+                cur, tok = [], 0
+            cur.append(i)
+            tok += n
+        if cur:
+            batches.append(cur)
+        return batches
+
+    def score_batch(self, questions: Sequence[str], texts_per_question: Sequence[Sequence[str]]) -> List[List[float]]:
+        """`[score(q, texts) for q, texts in ...]` with every question's pairs in shared device batches (`_device_batches`)."""
+        questions, texts_per_question = list(questions), list(texts_per_question)
+        if len(questions) != len(texts_per_question):
+            raise ValueError(f"{len(questions)} questions but {len(texts_per_question)} result lists")
+        sh = self.engine.shape
+        packed, owner = [], []
+        for qi, (question, texts) in enumerate(zip(questions, texts_per_question)):
+            if not texts:
+                continue
+            q = self._ids(question)
+            for t in texts:
+                packed.append(pack_pair(q, self._ids(t), sh.cls_token_id, sh.sep_token_id, self.max_length))
+                owner.append(qi)
+        scores = [0.0] * len(packed)
+        with self._lock:
+            for idx in self._device_batches(packed):
+                logits = self.engine.pair_logits([packed[i][0] for i in idx], [packed[i][1] for i in idx])
+                for i, x in zip(idx, logits[:, 0]):
+                    scores[i] = float(x)
+        per_q: List[List[float]] = [[] for _ in questions]
+        for qi, sc in zip(owner, scores):
+            per_q[qi].append(sc)
+        return per_q
+
+    def rerank_batch(self, questions: Sequence[str], results_per_question: Sequence[List[Any]]) -> List[List[Any]]:
+        """`[rerank(q, r) for q, r in zip(questions, results_per_question)]` -- same `rerank_k` head / tail split,
+        `text_field` and ordering rule -- with every question's pairs scored in shared device batches."""
+        results_per_question = list(results_per_question)
+        splits = [self._split_results(results) for results in results_per_question]
+        per_q = self.score_batch(questions, [self._get_texts(head) for head, _tail in splits])
+        out = []
+        for results, (head, tail), sc in zip(results_per_question, splits, per_q):
+            if not head:
+                out.append(results)
+                continue
+            out.append([r for _, r in sorted(zip(sc, head), reverse=True)] + tail)   # rerankers.py:133
+        return out
