@@ -240,3 +240,71 @@ def test_one_summation_order_across_the_launch_bound_residual_configurations():
         assert np.array_equal(out["k_split_512_rows"], out["tiles_128_6144_rows"]), float(np.abs(out["k_split_512_rows"] - out["tiles_128_6144_rows"]).max())
     finally:
         eng.close()
+
+
+def test_mlm_head_set_again_without_biases_drops_the_old_biases():
+    """vrag_encoder_set_mlm_head after a head with biases (vrag_encoder_set_mlm_head_ex): the new head has none, so the SPLADE rows
+    equal those of an engine that never had them."""
+    from verbatim_rag_amd.engine import BertEncoderEngine
+
+    cfg = B.BertConfig(vocab_size=1024, hidden_size=128, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256,
+                       max_position_embeddings=128)
+    W = B.random_weights(cfg, seed=21, kind="bert", std=0.05)
+    Wm = {k: v for k, v in W.items() if not k.startswith("mlm.")}
+    seqs = [np.random.default_rng(4).integers(3, cfg.vocab_size, size=n).astype(np.int32) for n in (37, 90)]
+    a = BertEncoderEngine(_shape(cfg, "bert"), W, max_tokens=512, max_seqs=4, max_seq_len=128, max_ranges=4)
+    b = BertEncoderEngine(_shape(cfg, "bert"), Wm, max_tokens=512, max_seqs=4, max_seq_len=128, max_ranges=4)
+    try:
+        rows = {}
+        for name, eng in (("a_biased", a), ("a", a), ("b", b)):
+            if name != "a_biased":
+                eng.set_mlm_head(W["mlm.dense.w"], W["mlm.ln.w"], W["mlm.dec.b"])
+            eng.load_batch(seqs)
+            eng.run()
+            eng.run_splade()
+            rows[name] = eng.read_splade()
+        assert not np.array_equal(rows["a_biased"], rows["b"])   # the biases show in the rows: the check below can fail
+        assert np.array_equal(rows["a"], rows["b"]), float(np.abs(rows["a"] - rows["b"]).max())
+    finally:
+        a.close()
+        b.close()
+
+
+def test_token_type_table_set_again_after_graph_capture():
+    """A captured layer schedule holds the token-type table's address: setting the table again must not leave a replay reading
+    the old one.  Hidden states after the re-set equal those of an engine built with the new table."""
+    from verbatim_rag_amd import _lib
+    from verbatim_rag_amd.engine import BertEncoderEngine, _fp
+    from verbatim_rag_amd.weights import bert_canonical
+
+    z = np.load(os.path.join(GOLD, "bert_pair_tiny.npz"))
+    V, H, L, NH, I, P = (int(x) for x in z["cfg"])
+    cfg = B.BertConfig(vocab_size=V, hidden_size=H, num_hidden_layers=L, num_attention_heads=NH, intermediate_size=I,
+                       max_position_embeddings=P)
+    W = bert_canonical({k[3:]: z[k] for k in z.files if k.startswith("sd:")})
+    new_types = np.ascontiguousarray(np.random.default_rng(5).normal(0.0, 0.05, W["emb.types"].shape).astype(np.float32))
+    seqs, types = [z["ids0"], z["ids1"]], [z["types0"], z["types1"]]
+
+    def hidden(eng):
+        eng.load_batch(seqs)
+        eng.load_token_types(types)
+        eng.run()
+        return eng.read_hidden(final_norm=False)
+
+    eng = BertEncoderEngine(_shape(cfg, "bert"), W, max_tokens=1024, max_seqs=8, max_seq_len=64, max_ranges=8)
+    fresh = BertEncoderEngine(_shape(cfg, "bert"), dict(W, **{"emb.types": new_types}), max_tokens=1024, max_seqs=8,
+                              max_seq_len=64, max_ranges=8)
+    try:
+        for _ in range(4):   # eager twice, then captured and replayed
+            old = hidden(eng)
+            if eng.graph_stats()[0] > 0:
+                break
+        assert eng.graph_stats()[0] > 0, "the geometry was never replayed from a graph"
+        _lib.check("vrag_encoder_set_token_types",
+                   eng._lib.vrag_encoder_set_token_types(eng._h, _fp(new_types), new_types.shape[0]))
+        got, want = hidden(eng), hidden(fresh)
+        assert not np.array_equal(old, want)   # the new table changes the result: the check below can fail
+        assert np.array_equal(got, want), float(np.abs(got - want).max())
+    finally:
+        eng.close()
+        fresh.close()

@@ -16,6 +16,7 @@
 
 #include <array>
 #include <map>
+#include <memory>
 #include "common.h"
 #include "gemm_bf16.h"
 #include "host_util.h"
@@ -198,29 +199,29 @@ __global__ __launch_bounds__(256) void splade_compact_kernel(const float* __rest
 }
 
 struct Layer {
-  float* attn_norm = nullptr;
-  bf16_t* wqkv = nullptr;
-  bf16_t* wo = nullptr;
-  float* mlp_norm = nullptr;
-  bf16_t* wi = nullptr;  // interleaved rows
-  bf16_t* wo_mlp = nullptr;
+  DevArray<float> attn_norm;
+  DevArray<bf16_t> wqkv;
+  DevArray<bf16_t> wo;
+  DevArray<float> mlp_norm;
+  DevArray<bf16_t> wi;  // interleaved rows
+  DevArray<bf16_t> wo_mlp;
   // LayerNorm gains are folded into wqkv (attn_norm, layers > 0) and wi (mlp_norm); s_* = row sums
-  float* s_qkv = nullptr;
-  float* s_wi = nullptr;
+  DevArray<float> s_qkv;
+  DevArray<float> s_wi;
   // the same Wqkv rows grouped per head, q(64) k(64) v(64), for the fused QKV + attention kernel (qkv_attn.hip)
-  bf16_t* wqkv_h = nullptr;
-  float* s_qkv_h = nullptr;
+  DevArray<bf16_t> wqkv_h;
+  DevArray<float> s_qkv_h;
 };
 
 // BERT-family layer (post-LN, biased linears, GELU MLP): TF:models/bert/modeling_bert.py:282-286,340-344,
 // models/distilbert/modeling_distilbert.py:236-239.
 struct BertLayer {
-  bf16_t *wqkv = nullptr, *wo = nullptr, *w1 = nullptr, *w2 = nullptr;
-  float *bqkv = nullptr, *bo = nullptr, *b1 = nullptr, *b2 = nullptr;
-  float *ln1_w = nullptr, *ln1_b = nullptr, *ln2_w = nullptr, *ln2_b = nullptr;
+  DevArray<bf16_t> wqkv, wo, w1, w2;
+  DevArray<float> bqkv, bo, b1, b2;
+  DevArray<float> ln1_w, ln1_b, ln2_w, ln2_b;
   // LayerNorm fold (default): wqkv (layers > 0) / w1 carry the gain of the LayerNorm that feeds them, bqkv / b1 carry
   // W . ln_bias on top of the linear bias, s_* are the row sums of the bf16 folded weights
-  float *s_qkv = nullptr, *s_w1 = nullptr;
+  DevArray<float> s_qkv, s_w1;
 };
 
 struct MicroBatch {
@@ -242,6 +243,8 @@ struct ProfRec {
 
 using namespace vrag;
 
+// Memory: every buffer is a DevArray / PinnedArray member, freed with the handle or when the head that owns it is set again.
+// The raw pointers among the members own nothing: slices of one of those arrays, a mapped word's device address, flag symbols.
 struct vrag_encoder {
   vrag_encoder_config cfg{};
   std::recursive_mutex mu;
@@ -251,88 +254,90 @@ struct vrag_encoder {
   int n_streams = 1;
   bool ln_fold = true;   // LayerNorm folded into the producer/consumer GEMM epilogues (VRAG_LN_FOLD=0: separate LN kernels)
   int fused_qkv_attn = 1;   // Wqkv GEMM + RoPE + attention in one kernel per (sequence, head) when every sequence of the micro-batch has <= 512 tokens (VRAG_FUSED_QKV_ATTN)
-  std::vector<void*> dev_allocs;
-  std::vector<void*> host_allocs;
   // fp16 clamp reports (vrag_encoder_f16_saturated): the device addresses of the five translation units' flags and one pinned,
   // device-mapped word they are gathered into by one launch
   unsigned* sat_addr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  unsigned *sat_host = nullptr, *sat_host_dev = nullptr;
+  PinnedArray<unsigned> sat_host;
+  unsigned* sat_host_dev = nullptr;   // its device address
 
   // weights
   int op_dtype = kOpBf16;   // MFMA operand type of every 16-bit buffer of this handle (cfg.operand_dtype)
   int arch = 0;  // 0 = ModernBERT (pre-LN, RoPE, GeGLU, no biases); 1 = BERT family (post-LN, biases, learned positions)
-  float* tok_emb = nullptr;
-  float* emb_norm = nullptr;
-  float* final_norm = nullptr;   // null for arch 1 (the stream is already normalised)
+  DevArray<float> tok_emb;
+  DevArray<float> emb_norm;
+  DevArray<float> final_norm;   // empty for arch 1 (the stream is already normalised)
   std::vector<Layer> layers;
   // arch 1
-  float *pos_emb = nullptr, *type_row = nullptr, *emb_norm_b = nullptr;
+  DevArray<float> pos_emb, type_row, emb_norm_b;
   std::vector<BertLayer> blayers;
-  float *mlm_dense_b = nullptr, *mlm_norm_b = nullptr;
+  DevArray<float> mlm_dense_b, mlm_norm_b;
   // sentence-pair inputs + cross-encoder head (arch 1)
-  float* type_table = nullptr;   // [n_types, H] token_type_embeddings
+  DevArray<float> type_table;   // [n_types, H] token_type_embeddings
   int n_types = 0;
-  int* d_types = nullptr;        // [cap_rows] per-token segment id of the current batch
-  int* h_types = nullptr;
+  DevArray<int> d_types;        // [cap_rows] per-token segment id of the current batch
+  PinnedArray<int> h_types;
   bool types_loaded = false;
-  float *pr_wp = nullptr, *pr_bp = nullptr, *pr_wc = nullptr, *pr_bc = nullptr;
+  DevArray<float> pr_wp, pr_bp, pr_wc, pr_bc;
   int pr_labels = 0;
-  int *d_first_row = nullptr, *h_first_row = nullptr;   // [max_seqs]
-  float* d_pair_out = nullptr;                          // [max_seqs, pr_labels]
+  DevArray<int> d_first_row;    // [max_seqs]
+  PinnedArray<int> h_first_row;
+  DevArray<float> d_pair_out;   // [max_seqs, pr_labels]
   // sequence-classification head (arch 0: ModernBertForSequenceClassification)
-  float *sq_wdT = nullptr, *sq_bd = nullptr, *sq_wn = nullptr, *sq_bn = nullptr, *sq_wc = nullptr, *sq_bc = nullptr;
+  DevArray<float> sq_wdT, sq_bd, sq_wn, sq_bn, sq_wc, sq_bc;
   int sq_labels = 0, sq_pool_mean = 0;
-  float *d_sq_pooled = nullptr, *d_sq_out = nullptr;    // [max_seqs, H], [max_seqs, sq_labels]
+  DevArray<float> d_sq_pooled, d_sq_out;    // [max_seqs, H], [max_seqs, sq_labels]
   int i_pad = 0;        // GeGLU width padded to a multiple of 128 (2*i_pad = whole 256-wide GEMM tiles)
   int attn_w = 0;       // width of the q / k / v^T / o buffers = num_heads * 64 (> hidden_size when head_dim is 32)
   float q_scale = 0.125f * 1.4426950408889634f;  // head_dim^-1/2 * log2(e)
-  float *cos_g = nullptr, *sin_g = nullptr, *cos_l = nullptr, *sin_l = nullptr;
+  DevArray<float> cos_g, sin_g, cos_l, sin_l;
   // heads
-  float *qa_w = nullptr, *qa_b = nullptr;
+  DevArray<float> qa_w, qa_b;
   int qa_labels = 0;
-  bf16_t *tk_dense = nullptr, *tk_dense_lo = nullptr;
-  float *tk_norm = nullptr, *tk_w = nullptr, *tk_b = nullptr;
+  DevArray<bf16_t> tk_dense, tk_dense_lo;
+  DevArray<float> tk_norm, tk_w, tk_b;
   int tk_labels = 0;
-  bf16_t *mlm_dense = nullptr, *mlm_dec = nullptr;
-  float *mlm_norm = nullptr, *mlm_bias = nullptr;
+  DevArray<bf16_t> mlm_dense, mlm_dec;
+  DevArray<float> mlm_norm, mlm_bias;
   int vpad = 0;
   // split-operand MLM head (vrag_encoder_set_head_precision, the default): dense weight remainder, the decoder as a
   // [vpad, 3H] image [Whi | Whi | Wlo] and the [cap_rows, 3H] operand image [xhi | xlo | xhi] its K = 3H GEMM reads
   bool mlm_split = true;
-  bf16_t *mlm_dense_lo = nullptr, *mlm_dec3 = nullptr, *splade_a3 = nullptr;
+  DevArray<bf16_t> mlm_dense_lo, mlm_dec3, splade_a3;
 
   // workspace
   int cap_rows = 0;
-  int *d_ids = nullptr, *d_pos = nullptr, *d_tokseq = nullptr;
-  int *d_packed = nullptr, *d_seq_meta = nullptr;   // the batch as handed over: ids back to back; [3][max_seqs] first row / first id / length
-  int* h_seq_meta = nullptr;
-  int4 *d_groups = nullptr, *h_groups = nullptr;   // [max_seqs * 8] wave descriptors of the fused kernel's groups
-  float* h = nullptr;
-  bf16_t *a = nullptr, *q = nullptr, *k = nullptr, *vt = nullptr, *o = nullptr, *act = nullptr;
-  float* f32tmp = nullptr;  // [cap_rows, H] final hidden / head dense output
-  float *st_part = nullptr, *ln_mu = nullptr, *ln_rstd = nullptr;  // folded-LayerNorm row statistics (ln_mu relative to ln_shift's previous value)
-  float* ln_shift = nullptr;                                        // absolute row means = the next residual epilogue's shift
-  float* ln_shift_prev = nullptr;                                   // the shift before the last advance: what the split planes in HBM are relative to
-  unsigned char* lo8 = nullptr;                                     // [cap_rows * H] byte remainder plane of the split residual stream (gemm_bf16.h: 64 x 64 blocks)
-  bool split_resid = true;                                          // VRAG_SPLIT_RESID=0: fp32 rows between all sub-layers (A/B)
-  int *d_blk_start = nullptr, *d_blk_len = nullptr, *d_blk_q0 = nullptr;     // global-layer q-blocks
+  DevArray<int> d_ids, d_pos, d_tokseq;
+  DevArray<int> d_packed, d_seq_meta;   // the batch as handed over: ids back to back; [3][max_seqs] first row / first id / length
+  PinnedArray<int> h_seq_meta;
+  DevArray<int4> d_groups;   // [max_seqs * 8] wave descriptors of the fused kernel's groups
+  PinnedArray<int4> h_groups;
+  DevArray<float> h;
+  DevArray<bf16_t> a, q, k, vt, o, act;
+  DevArray<float> f32tmp;  // [cap_rows, H] final hidden / head dense output
+  DevArray<float> st_part, ln_mu, ln_rstd;  // folded-LayerNorm row statistics (ln_mu relative to ln_shift's previous value)
+  DevArray<float> ln_shift;                 // absolute row means = the next residual epilogue's shift
+  DevArray<float> ln_shift_prev;            // the shift before the last advance: what the split planes in HBM are relative to
+  DevArray<unsigned char> lo8;              // [cap_rows * H] byte remainder plane of the split residual stream (gemm_bf16.h: 64 x 64 blocks)
+  bool split_resid = true;                  // VRAG_SPLIT_RESID=0: fp32 rows between all sub-layers (A/B)
+  DevArray<int> d_blk_start;   // owns the six q-block descriptor arrays: d_blk_start itself and the five slices behind it
+  int *d_blk_len = nullptr, *d_blk_q0 = nullptr;                             // global-layer q-blocks
   int *d_lblk_start = nullptr, *d_lblk_len = nullptr, *d_lblk_q0 = nullptr;  // banded-layer q-blocks
   int cap_blocks = 0;
-  int *d_rng_start = nullptr, *d_rng_end = nullptr;
-  float* d_rng_out = nullptr;  // [max_ranges, max(H, labels)]
-  float* d_tok_logits = nullptr;
-  unsigned* d_splade = nullptr;  // allocated with the MLM head
-  int *d_sp_cnt = nullptr, *d_sp_idx = nullptr;   // device-side compaction of the SPLADE rows (grown on demand)
-  float* d_sp_val = nullptr;
+  DevArray<int> d_rng_start, d_rng_end;
+  DevArray<float> d_rng_out;  // [max_ranges, max(H, labels)]
+  DevArray<float> d_tok_logits;
+  DevArray<unsigned> d_splade;  // allocated with the MLM head
+  DevArray<int> d_sp_cnt, d_sp_idx;   // device-side compaction of the SPLADE rows (grown on demand)
+  DevArray<float> d_sp_val;
   int sp_cap = 0;
 
   // pinned staging
-  int* h_ids = nullptr;   // the batch's ids back to back (the row image is laid out on the device, pack_layout_kernel)
-  int *h_blk_start = nullptr, *h_blk_len = nullptr, *h_blk_q0 = nullptr;
+  PinnedArray<int> h_ids;   // the batch's ids back to back (the row image is laid out on the device, pack_layout_kernel)
+  PinnedArray<int> h_blk_start;   // owns the six host descriptor arrays, as d_blk_start
+  int *h_blk_len = nullptr, *h_blk_q0 = nullptr;
   int *h_lblk_start = nullptr, *h_lblk_len = nullptr, *h_lblk_q0 = nullptr;
-  int *h_rng_start = nullptr, *h_rng_end = nullptr;
-  float* h_out = nullptr;  // generic read-back staging
-  size_t h_out_bytes = 0;
+  PinnedArray<int> h_rng_start, h_rng_end;
+  PinnedArray<float> h_out;  // generic read-back staging (grown on demand)
 
   // current batch
   int n_seqs = 0, n_tokens = 0, rows = 0, n_blocks = 0, n_ranges = 0;
@@ -363,78 +368,89 @@ struct vrag_encoder {
   int64_t prof_n[VRAG_PROF_COUNT] = {0};      // launches timed
   int64_t prof_seen[VRAG_PROF_COUNT] = {0};   // launches issued while profiling was on
   int prof_period = 1;                        // vrag_encoder_set_profiling(enabled): every enabled-th launch of a class is timed
+
+  void clear_graphs() {
+    for (auto& kv : graphs) {
+      if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
+      if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
+    }
+    graphs.clear();
+  }
+  // Streams, events and graphs go first, behind the device's last work; the arrays free themselves after this body.
+  ~vrag_encoder() {
+    (void)hipSetDevice(cfg.device);
+    (void)hipDeviceSynchronize();
+    clear_graphs();
+    for (auto& r : prof_pending) {
+      (void)hipEventDestroy(r.a);
+      (void)hipEventDestroy(r.b);
+    }
+    for (auto ev : prof_free) (void)hipEventDestroy(ev);
+    for (int i = 0; i < 4; ++i) {
+      if (aux_streams[i]) (void)hipStreamDestroy(aux_streams[i]);
+      if (ev_join[i]) (void)hipEventDestroy(ev_join[i]);
+    }
+    if (ev_fork) (void)hipEventDestroy(ev_fork);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+  }
 };
 
 namespace {
 
+// Status of a helper that has already set the error message: passed straight on.
+#define TRY(x)                     \
+  do {                             \
+    if (int rc_ = (x)) return rc_; \
+  } while (0)
+
+// `out` <- a fresh device array of `count` elements (at least 256 bytes), zero-filled unless `zero` is false; what it held is freed.
 template <typename T>
-int dev_alloc(vrag_encoder* e, T** out, size_t count, bool zero = true) {
-  void* p = nullptr;
-  const size_t bytes = std::max<size_t>(count * sizeof(T), 256);
-  HIP_TRY(hipMalloc(&p, bytes));
-  e->dev_allocs.push_back(p);
+int dev_alloc(DevArray<T>& out, size_t count, bool zero = true) {
+  static_assert(256 % sizeof(T) == 0, "the 256-byte minimum must be whole elements");
+  DevArray<T> fresh;
+  HIP_TRY(fresh.grow(std::max(count, 256 / sizeof(T))));
   if (zero) {
     // hipMemset runs on the null stream, which does NOT order against the handle's non-blocking streams: wait for it
     // here (allocations are rare), or a kernel launched right after could have its output zeroed under it.
-    HIP_TRY(hipMemset(p, 0, bytes));
+    HIP_TRY(hipMemset(fresh.p, 0, fresh.n * sizeof(T)));
     HIP_TRY(hipDeviceSynchronize());
   }
-  *out = reinterpret_cast<T*>(p);
+  out = std::move(fresh);
   return VRAG_OK;
 }
 
-// frees one tracked device allocation (a head that is set again) and clears the pointer
+// `out` <- a fresh pinned host array of `count` elements (at least 256 bytes); what it held is freed.
 template <typename T>
-void dev_release(vrag_encoder* e, T** ptr) {
-  if (!*ptr) return;
-  void* p = reinterpret_cast<void*>(*ptr);
-  for (size_t i = 0; i < e->dev_allocs.size(); ++i)
-    if (e->dev_allocs[i] == p) {
-      e->dev_allocs.erase(e->dev_allocs.begin() + (long)i);
-      (void)hipFree(p);
-      break;
-    }
-  *ptr = nullptr;
-}
-
-template <typename T>
-int host_alloc(vrag_encoder* e, T** out, size_t count) {
-  void* p = nullptr;
-  HIP_TRY(hipHostMalloc(&p, std::max<size_t>(count * sizeof(T), 256), hipHostMallocDefault));
-  e->host_allocs.push_back(p);
-  *out = reinterpret_cast<T*>(p);
+int host_alloc(PinnedArray<T>& out, size_t count) {
+  static_assert(256 % sizeof(T) == 0, "the 256-byte minimum must be whole elements");
+  PinnedArray<T> fresh;
+  HIP_TRY(fresh.grow(std::max(count, 256 / sizeof(T))));
+  out = std::move(fresh);
   return VRAG_OK;
 }
 
-int upload_f32(vrag_encoder* e, float** out, const float* src, size_t count) {
-  int rc = dev_alloc(e, out, count, false);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpy(*out, src, count * sizeof(float), hipMemcpyHostToDevice));
+// `out` <- a device copy of `count` host floats.
+int upload_f32(DevArray<float>& out, const float* src, size_t count) {
+  TRY(dev_alloc(out, count, false));
+  HIP_TRY(hipMemcpy(out.p, src, count * sizeof(float), hipMemcpyHostToDevice));
   return VRAG_OK;
 }
 
-// fp32 host matrix [rows_src, cols] -> bf16 device matrix [rows_dst, cols] (zero padded rows).
-int upload_bf16(vrag_encoder* e, bf16_t** out, const float* src, int rows_src, int cols, int rows_dst,
-                int interleave_I, float* stage, size_t stage_elems, const float* d_col_scale = nullptr,
-                float** row_sum_out = nullptr, bf16_t** out_lo = nullptr) {
-  int rc = dev_alloc(e, out, (size_t)rows_dst * cols, false);
-  if (rc) return rc;
-  bf16_t* d_lo = nullptr;
-  if (out_lo) {
-    if ((rc = dev_alloc(e, &d_lo, (size_t)rows_dst * cols, false))) return rc;
-    *out_lo = d_lo;
-  }
-  float* d_row_sum = nullptr;
-  if (row_sum_out) {
-    if ((rc = dev_alloc(e, &d_row_sum, rows_dst, true))) return rc;
-    *row_sum_out = d_row_sum;
-  }
+// fp32 host matrix [rows_src, cols] -> bf16 device matrix [rows_dst, cols] (zero padded rows), streamed through `stage`.
+int upload_bf16(vrag_encoder* e, DevArray<bf16_t>& out, const float* src, int rows_src, int cols, int rows_dst, int interleave_I,
+                const DevArray<float>& stage, const float* d_col_scale = nullptr, DevArray<float>* row_sum_out = nullptr,
+                DevArray<bf16_t>* out_lo = nullptr) {
+  TRY(dev_alloc(out, (size_t)rows_dst * cols, false));
+  if (out_lo) TRY(dev_alloc(*out_lo, (size_t)rows_dst * cols, false));
+  if (row_sum_out) TRY(dev_alloc(*row_sum_out, rows_dst, true));
+  bf16_t* d_lo = out_lo ? out_lo->p : nullptr;
+  float* d_row_sum = row_sum_out ? row_sum_out->p : nullptr;
   // stream the fp32 source through the staging buffer in row chunks
-  const int chunk_rows_max = (int)std::max<size_t>(1, stage_elems / cols);
+  const int chunk_rows_max = (int)std::max<size_t>(1, stage.n / cols);
   if (interleave_I > 0 || d_col_scale || row_sum_out || out_lo || rows_src <= chunk_rows_max) {
-    ARG_CHECK((size_t)rows_src * cols <= stage_elems, "internal: staging buffer too small");
-    HIP_TRY(hipMemcpy(stage, src, (size_t)rows_src * cols * sizeof(float), hipMemcpyHostToDevice));
-    launch_cvt_rows(e->op_dtype, dim3(rows_dst), 0, stage, *out, rows_dst, rows_src, cols, interleave_I, d_col_scale, d_row_sum,
+    ARG_CHECK((size_t)rows_src * cols <= stage.n, "internal: staging buffer too small");
+    HIP_TRY(hipMemcpy(stage.p, src, (size_t)rows_src * cols * sizeof(float), hipMemcpyHostToDevice));
+    launch_cvt_rows(e->op_dtype, dim3(rows_dst), 0, stage.p, out.p, rows_dst, rows_src, cols, interleave_I, d_col_scale, d_row_sum,
                     d_lo);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
@@ -444,9 +460,9 @@ int upload_bf16(vrag_encoder* e, bf16_t** out, const float* src, int rows_src, i
     const int nr_dst = std::min(chunk_rows_max, rows_dst - r0);
     const int nr_src = std::max(0, std::min(chunk_rows_max, rows_src - r0));
     if (nr_src > 0)
-      HIP_TRY(hipMemcpy(stage, src + (size_t)r0 * cols, (size_t)nr_src * cols * sizeof(float),
+      HIP_TRY(hipMemcpy(stage.p, src + (size_t)r0 * cols, (size_t)nr_src * cols * sizeof(float),
                         hipMemcpyHostToDevice));
-    launch_cvt_rows(e->op_dtype, dim3(nr_dst), 0, stage, *out + (size_t)r0 * cols, nr_dst, nr_src, cols, 0, nullptr, nullptr);
+    launch_cvt_rows(e->op_dtype, dim3(nr_dst), 0, stage.p, out.p + (size_t)r0 * cols, nr_dst, nr_src, cols, 0, nullptr, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
   }
@@ -504,8 +520,8 @@ struct ProfScope {
   }
 };
 
+// Called with the handle's lock held: n_seqs is written by load_batch.
 int check_ready(vrag_encoder* e) {
-  ARG_CHECK(e != nullptr, "null encoder handle");
   ARG_CHECK(e->n_seqs > 0, "no batch loaded (call vrag_encoder_load_batch first)");
   return VRAG_OK;
 }
@@ -571,8 +587,8 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
     const int r0 = mb.row0, M = mb.row1 - mb.row0;
     {
       ProfScope ps(e, VRAG_PROF_EMBED, st);
-      HIP_TRY(launch_embed_ln(e->d_ids + r0, e->tok_emb, e->emb_norm, c.norm_eps, H, M, e->h + (size_t)r0 * H,
-                              e->a + (size_t)r0 * H, st, nullptr, nullptr, nullptr, nullptr, nullptr, e->op_dtype));
+      HIP_TRY(launch_embed_ln(e->d_ids.p + r0, e->tok_emb.p, e->emb_norm.p, c.norm_eps, H, M, e->h.p + (size_t)r0 * H,
+                              e->a.p + (size_t)r0 * H, st, nullptr, nullptr, nullptr, nullptr, nullptr, e->op_dtype));
     }
     for (int l = 0; l < n_layers; ++l) {
       const Layer& L = e->layers[l];
@@ -589,12 +605,12 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       const bool more_layers = l + 1 < n_layers;   // a further layer of THIS run consumes the fold outputs
       auto layer_norm = [&](const float* gain) -> int {
         ProfScope ps(e, VRAG_PROF_LAYERNORM, st);
-        HIP_TRY(launch_layernorm(e->h + (size_t)r0 * H, gain, c.norm_eps, H, M, e->a + (size_t)r0 * H, nullptr, st, nullptr, nullptr,
+        HIP_TRY(launch_layernorm(e->h.p + (size_t)r0 * H, gain, c.norm_eps, H, M, e->a.p + (size_t)r0 * H, nullptr, st, nullptr, nullptr,
                                  e->op_dtype));
         return VRAG_OK;
       };
       if (!fold && l > 0) {
-        int rc = layer_norm(L.attn_norm);
+        int rc = layer_norm(L.attn_norm.p);
         if (rc) return rc;
       }
       // `first`: no previous mean to shift by (c = 0)
@@ -605,39 +621,39 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       // The fused kernel spends a 512-token workgroup per (sequence, head) whatever the sequence's length (waves past its end
       // idle): it wins from a mean length of ~270 tokens up and loses below (tools/bench_seq_len.py: 42.7 vs 38.6 ms per
       // 131 072-token step at 192 tokens, a tie at 256, 35.8 vs 39.9 at 512), so short-chunk batches keep the packed two-kernel path.
-      const bool fused_attn = L.wqkv_h && fused_attention_for(e, mb);
+      const bool fused_attn = L.wqkv_h.p && fused_attention_for(e, mb);
       auto finalize_stats = [&](bool first, bool for_qkv = false) -> int {
         if (consumer_stats && !(for_qkv && fused_attn)) return VRAG_OK;
         ProfScope ps(e, VRAG_PROF_LAYERNORM, st);
         hipLaunchKernelGGL(ln_stats_finalize_kernel, dim3((M + 255) / 256), dim3(256), 0, st,
-                           e->st_part + (size_t)r0 * 2, e->cap_rows, H / 64, H, c.norm_eps, M, e->ln_mu + r0,
-                           e->ln_rstd + r0, first ? (const float*)nullptr : e->ln_shift + r0, e->ln_shift + r0, e->ln_shift_prev + r0);
+                           e->st_part.p + (size_t)r0 * 2, e->cap_rows, H / 64, H, c.norm_eps, M, e->ln_mu.p + r0,
+                           e->ln_rstd.p + r0, first ? (const float*)nullptr : e->ln_shift.p + r0, e->ln_shift.p + r0, e->ln_shift_prev.p + r0);
         HIP_TRY(hipGetLastError());
         return VRAG_OK;
       };
       auto stats_for_consumer = [&](GemmParams& g) {
         if (!consumer_stats) return;
-        g.stats_in = e->st_part + (size_t)r0 * 2;
+        g.stats_in = e->st_part.p + (size_t)r0 * 2;
         g.stats_ld = e->cap_rows;
-        g.ln_shift = e->ln_shift + r0;
-        g.ln_shift_prev = e->ln_shift_prev + r0;
+        g.ln_shift = e->ln_shift.p + r0;
+        g.ln_shift_prev = e->ln_shift_prev.p + r0;
         g.fin_eps = c.norm_eps;
       };
       if (fused_attn) {
         QkvAttnParams f{};
         f.op_dtype = e->op_dtype;
-        f.x = e->a;
-        f.w = L.wqkv_h;
+        f.x = e->a.p;
+        f.w = L.wqkv_h.p;
         if (fold && l > 0) {
-          f.ln_mu = e->ln_mu;
-          f.ln_rstd = e->ln_rstd;
-          f.ln_s = L.s_qkv_h;
+          f.ln_mu = e->ln_mu.p;
+          f.ln_rstd = e->ln_rstd.p;
+          f.ln_s = L.s_qkv_h.p;
         }
-        f.rope_cos = global ? e->cos_g : e->cos_l;
-        f.rope_sin = global ? e->sin_g : e->sin_l;
+        f.rope_cos = global ? e->cos_g.p : e->cos_l.p;
+        f.rope_sin = global ? e->sin_g.p : e->sin_l.p;
         f.rope_rows = c.max_seq_len;
-        f.o = e->o;
-        f.groups = e->d_groups + (size_t)mb.grp0 * 8;
+        f.o = e->o.p;
+        f.groups = e->d_groups.p + (size_t)mb.grp0 * 8;
         f.n_groups = mb.grp1 - mb.grp0;
         f.H = H;
         f.nh = c.num_heads;
@@ -650,24 +666,24 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
-        g.A = e->a + (size_t)r0 * H;
-        g.W = L.wqkv;
+        g.A = e->a.p + (size_t)r0 * H;
+        g.W = L.wqkv.p;
         if (fold && l > 0) {  // layer 0 consumes the embedding LayerNorm output directly (no attn_norm)
-          g.ln_mu = e->ln_mu + r0;
-          g.ln_rstd = e->ln_rstd + r0;
-          g.ln_s = L.s_qkv;
+          g.ln_mu = e->ln_mu.p + r0;
+          g.ln_rstd = e->ln_rstd.p + r0;
+          g.ln_s = L.s_qkv.p;
           stats_for_consumer(g);
         }
         g.M = M;
         g.N = 3 * H;
         g.K = H;
-        g.q = e->q + (size_t)r0 * H;
-        g.k = e->k + (size_t)r0 * H;
-        g.vt = e->vt + r0;
+        g.q = e->q.p + (size_t)r0 * H;
+        g.k = e->k.p + (size_t)r0 * H;
+        g.vt = e->vt.p + r0;
         g.vt_ld = Tp;
-        g.rope_cos = global ? e->cos_g : e->cos_l;
-        g.rope_sin = global ? e->sin_g : e->sin_l;
-        g.pos = e->d_pos + r0;
+        g.rope_cos = global ? e->cos_g.p : e->cos_l.p;
+        g.rope_sin = global ? e->sin_g.p : e->sin_l.p;
+        g.pos = e->d_pos.p + r0;
         g.hidden = H;
         g.q_scale = 0.125f * 1.4426950408889634f;  // head_dim^-1/2 * log2(e): attention softmax runs in exp2 units
         ProfScope ps(e, VRAG_PROF_GEMM_QKV, st);
@@ -676,11 +692,11 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         AttnParams ap{};
         ap.op_dtype = e->op_dtype;
-        ap.q = e->q;
-        ap.k = e->k;
-        ap.vt = e->vt;
-        ap.o = e->o;
-        ap.blk_seq_start = global ? e->d_blk_start + mb.blk0 : e->d_lblk_start + mb.lblk0;
+        ap.q = e->q.p;
+        ap.k = e->k.p;
+        ap.vt = e->vt.p;
+        ap.o = e->o.p;
+        ap.blk_seq_start = global ? e->d_blk_start.p + mb.blk0 : e->d_lblk_start + mb.lblk0;
         ap.blk_seq_len = global ? e->d_blk_len + mb.blk0 : e->d_lblk_len + mb.lblk0;
         ap.blk_q0 = global ? e->d_blk_q0 + mb.blk0 : e->d_lblk_q0 + mb.lblk0;
         ap.n_blocks = global ? mb.blk1 - mb.blk0 : mb.lblk1 - mb.lblk0;
@@ -695,24 +711,24 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
-        g.A = e->o + (size_t)r0 * H;
-        g.W = L.wo;
+        g.A = e->o.p + (size_t)r0 * H;
+        g.W = L.wo.p;
         g.M = M;
         g.N = H;
         g.K = H;
-        g.out_f32 = e->h + (size_t)r0 * H;
+        g.out_f32 = e->h.p + (size_t)r0 * H;
         // The fold's per-row shift is the row's previous mean; the very first sub-layer has none, so layer 0's
         // mlp_norm runs as a stand-alone (two-pass) LayerNorm that also records the exact row means.
         const bool fold_here = fold && l > 0;
         if (fold_here) {
-          g.resid_bf16 = e->a + (size_t)r0 * H;
-          g.stats_part = e->st_part + (size_t)r0 * 2;
+          g.resid_bf16 = e->a.p + (size_t)r0 * H;
+          g.stats_part = e->st_part.p + (size_t)r0 * 2;
           g.stats_ld = e->cap_rows;
-          g.ln_shift = e->ln_shift + r0;
+          g.ln_shift = e->ln_shift.p + r0;
           if (split) {   // layers >= 1: the stream arrives split (mlp Wo of the previous layer) and leaves split (this layer's mlp Wo reads it)
-            g.lo_in = e->lo8 + (size_t)r0 * H;
-            g.lo_out = e->lo8 + (size_t)r0 * H;
-            g.ln_shift_prev = e->ln_shift_prev + r0;
+            g.lo_in = e->lo8.p + (size_t)r0 * H;
+            g.lo_out = e->lo8.p + (size_t)r0 * H;
+            g.ln_shift_prev = e->ln_shift_prev.p + r0;
           }
         }
         {
@@ -721,51 +737,51 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
         }
         if (fold && l == 0) {   // a = bf16(normalised h) without the gain (folded into Wi), ln_shift = mean(h)
           ProfScope ps(e, VRAG_PROF_LAYERNORM, st);
-          HIP_TRY(launch_layernorm(e->h + (size_t)r0 * H, nullptr, c.norm_eps, H, M, e->a + (size_t)r0 * H, nullptr, st, nullptr,
-                                   e->ln_shift + r0, e->op_dtype));
+          HIP_TRY(launch_layernorm(e->h.p + (size_t)r0 * H, nullptr, c.norm_eps, H, M, e->a.p + (size_t)r0 * H, nullptr, st, nullptr,
+                                   e->ln_shift.p + r0, e->op_dtype));
         } else {
-          int rc = fold ? finalize_stats(false) : layer_norm(L.mlp_norm);
+          int rc = fold ? finalize_stats(false) : layer_norm(L.mlp_norm.p);
           if (rc) return rc;
         }
       }
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
-        g.A = e->a + (size_t)r0 * H;
-        g.W = L.wi;
+        g.A = e->a.p + (size_t)r0 * H;
+        g.W = L.wi.p;
         if (fold && l > 0) {
-          g.ln_mu = e->ln_mu + r0;
-          g.ln_rstd = e->ln_rstd + r0;
-          g.ln_s = L.s_wi;
+          g.ln_mu = e->ln_mu.p + r0;
+          g.ln_rstd = e->ln_rstd.p + r0;
+          g.ln_s = L.s_wi.p;
           stats_for_consumer(g);
         }
         g.M = M;
         g.N = 2 * I;
         g.K = H;
-        g.out_bf16 = e->act + (size_t)r0 * I;
+        g.out_bf16 = e->act.p + (size_t)r0 * I;
         ProfScope ps(e, VRAG_PROF_GEMM_WI, st);
         HIP_TRY(launch_gemm(EPI_GEGLU, g, st));
       }
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
-        g.A = e->act + (size_t)r0 * I;
-        g.W = L.wo_mlp;
+        g.A = e->act.p + (size_t)r0 * I;
+        g.W = L.wo_mlp.p;
         g.M = M;
         g.N = H;
         g.K = I;
-        g.out_f32 = e->h + (size_t)r0 * H;
+        g.out_f32 = e->h.p + (size_t)r0 * H;
         if (fold && more_layers) {  // the next layer's attn_norm is folded into its QKV GEMM
-          g.resid_bf16 = e->a + (size_t)r0 * H;
-          g.stats_part = e->st_part + (size_t)r0 * 2;
+          g.resid_bf16 = e->a.p + (size_t)r0 * H;
+          g.stats_part = e->st_part.p + (size_t)r0 * 2;
           g.stats_ld = e->cap_rows;
-          g.ln_shift = e->ln_shift + r0;
-          if (split) g.lo_out = e->lo8 + (size_t)r0 * H;
+          g.ln_shift = e->ln_shift.p + r0;
+          if (split) g.lo_out = e->lo8.p + (size_t)r0 * H;
         }
         if (split && l > 0) {   // this layer's attention Wo left the stream split; the last layer of a run writes the fp32 rows again
-          g.lo_in = e->lo8 + (size_t)r0 * H;
-          g.ln_shift_prev = e->ln_shift_prev + r0;
-          if (!g.resid_bf16) g.resid_bf16 = e->a + (size_t)r0 * H;   // the high plane is read from there
+          g.lo_in = e->lo8.p + (size_t)r0 * H;
+          g.ln_shift_prev = e->ln_shift_prev.p + r0;
+          if (!g.resid_bf16) g.resid_bf16 = e->a.p + (size_t)r0 * H;   // the high plane is read from there
         }
         {
           ProfScope ps(e, VRAG_PROF_GEMM_WO_MLP, st);
@@ -812,20 +828,20 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
     const MicroBatch& mb = e->mbs[mbi];
     hipStream_t st = fork ? e->aux_streams[mbi % e->n_streams] : user_st;
     const int r0 = mb.row0, M = mb.row1 - mb.row0;
-    float* h = e->h + (size_t)r0 * H;
-    bf16_t* a = e->a + (size_t)r0 * H;
+    float* h = e->h.p + (size_t)r0 * H;
+    bf16_t* a = e->a.p + (size_t)r0 * H;
     {
       ProfScope ps(e, VRAG_PROF_EMBED, st);
-      HIP_TRY(launch_embed_ln(e->d_ids + r0, e->tok_emb, e->emb_norm, c.norm_eps, H, M, h, a, st, e->pos_emb,
-                              e->d_pos + r0, e->types_loaded ? e->type_table : e->type_row, e->emb_norm_b,
-                              e->types_loaded ? e->d_types + r0 : nullptr, e->op_dtype));
+      HIP_TRY(launch_embed_ln(e->d_ids.p + r0, e->tok_emb.p, e->emb_norm.p, c.norm_eps, H, M, h, a, st, e->pos_emb.p,
+                              e->d_pos.p + r0, e->types_loaded ? e->type_table.p : e->type_row.p, e->emb_norm_b.p,
+                              e->types_loaded ? e->d_types.p + r0 : nullptr, e->op_dtype));
     }
     const bool fold = e->ln_fold;
-    float* st_part = e->st_part + (size_t)r0 * 2;
+    float* st_part = e->st_part.p + (size_t)r0 * 2;
     auto finalize_stats = [&](bool first) -> int {
       ProfScope ps(e, VRAG_PROF_LAYERNORM, st);
       hipLaunchKernelGGL(ln_stats_finalize_kernel, dim3((M + 255) / 256), dim3(256), 0, st, st_part, e->cap_rows, H / 64, H, c.norm_eps, M,
-                         e->ln_mu + r0, e->ln_rstd + r0, first ? (const float*)nullptr : e->ln_shift + r0, e->ln_shift + r0, (float*)nullptr);
+                         e->ln_mu.p + r0, e->ln_rstd.p + r0, first ? (const float*)nullptr : e->ln_shift.p + r0, e->ln_shift.p + r0, (float*)nullptr);
       HIP_TRY(hipGetLastError());
       return VRAG_OK;
     };
@@ -838,23 +854,23 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
         g.A = a;
-        g.W = L.wqkv;
-        g.bias = L.bqkv;
+        g.W = L.wqkv.p;
+        g.bias = L.bqkv.p;
         if (lazy_in) {
-          g.ln_mu = e->ln_mu + r0;
-          g.ln_rstd = e->ln_rstd + r0;
-          g.ln_s = L.s_qkv;
+          g.ln_mu = e->ln_mu.p + r0;
+          g.ln_rstd = e->ln_rstd.p + r0;
+          g.ln_s = L.s_qkv.p;
         }
         g.M = M;
         g.N = 3 * Ha;
         g.K = H;
-        g.q = e->q + (size_t)r0 * Ha;
-        g.k = e->k + (size_t)r0 * Ha;
-        g.vt = e->vt + r0;
+        g.q = e->q.p + (size_t)r0 * Ha;
+        g.k = e->k.p + (size_t)r0 * Ha;
+        g.vt = e->vt.p + r0;
         g.vt_ld = Tp;
-        g.rope_cos = e->cos_g;   // all ones
-        g.rope_sin = e->sin_g;   // all zeros
-        g.pos = e->d_pos + r0;
+        g.rope_cos = e->cos_g.p;   // all ones
+        g.rope_sin = e->sin_g.p;   // all zeros
+        g.pos = e->d_pos.p + r0;
         g.hidden = Ha;
         g.q_scale = e->q_scale;
         ProfScope ps(e, VRAG_PROF_GEMM_QKV, st);
@@ -863,11 +879,11 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         AttnParams ap{};
         ap.op_dtype = e->op_dtype;
-        ap.q = e->q;
-        ap.k = e->k;
-        ap.vt = e->vt;
-        ap.o = e->o;
-        ap.blk_seq_start = e->d_blk_start + mb.blk0;
+        ap.q = e->q.p;
+        ap.k = e->k.p;
+        ap.vt = e->vt.p;
+        ap.o = e->o.p;
+        ap.blk_seq_start = e->d_blk_start.p + mb.blk0;
         ap.blk_seq_len = e->d_blk_len + mb.blk0;
         ap.blk_q0 = e->d_blk_q0 + mb.blk0;
         ap.n_blocks = mb.blk1 - mb.blk0;
@@ -881,19 +897,19 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
-        g.A = e->o + (size_t)r0 * Ha;
-        g.W = L.wo;
+        g.A = e->o.p + (size_t)r0 * Ha;
+        g.W = L.wo.p;
         g.M = M;
         g.N = H;
         g.K = Ha;
         g.out_f32 = h;
-        g.bias = L.bo;
+        g.bias = L.bo.p;
         if (lazy_in) {
           const BertLayer& P = e->blayers[l - 1];
-          g.res_mu = e->ln_shift + r0;   // absolute mean of t2 of the previous layer
-          g.res_rstd = e->ln_rstd + r0;
-          g.res_g = P.ln2_w;
-          g.res_b = P.ln2_b;
+          g.res_mu = e->ln_shift.p + r0;   // absolute mean of t2 of the previous layer
+          g.res_rstd = e->ln_rstd.p + r0;
+          g.res_g = P.ln2_w.p;
+          g.res_b = P.ln2_b.p;
         }
         if (fold) {
           g.resid_bf16 = a;
@@ -908,23 +924,23 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
         if (rc) return rc;
       } else {
         ProfScope ps(e, VRAG_PROF_LAYERNORM, st);
-        HIP_TRY(launch_layernorm(h, L.ln1_w, c.norm_eps, H, M, a, h, st, L.ln1_b, nullptr, e->op_dtype));
+        HIP_TRY(launch_layernorm(h, L.ln1_w.p, c.norm_eps, H, M, a, h, st, L.ln1_b.p, nullptr, e->op_dtype));
       }
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
         g.A = a;
-        g.W = L.w1;
+        g.W = L.w1.p;
         g.M = M;
         g.N = I;
         g.K = H;
-        g.out_bf16 = e->act + (size_t)r0 * I;
-        g.bias = L.b1;
+        g.out_bf16 = e->act.p + (size_t)r0 * I;
+        g.bias = L.b1.p;
         g.act_gelu = 1;
         if (fold) {
-          g.ln_mu = e->ln_mu + r0;
-          g.ln_rstd = e->ln_rstd + r0;
-          g.ln_s = L.s_w1;
+          g.ln_mu = e->ln_mu.p + r0;
+          g.ln_rstd = e->ln_rstd.p + r0;
+          g.ln_s = L.s_w1.p;
         }
         ProfScope ps(e, VRAG_PROF_GEMM_WI, st);
         HIP_TRY(launch_gemm(EPI_BF16, g, st));
@@ -932,18 +948,18 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
-        g.A = e->act + (size_t)r0 * I;
-        g.W = L.w2;
+        g.A = e->act.p + (size_t)r0 * I;
+        g.W = L.w2.p;
         g.M = M;
         g.N = H;
         g.K = I;
         g.out_f32 = h;
-        g.bias = L.b2;
+        g.bias = L.b2.p;
         if (fold) {
-          g.res_mu = e->ln_shift + r0;   // absolute mean of t1
-          g.res_rstd = e->ln_rstd + r0;
-          g.res_g = L.ln1_w;
-          g.res_b = L.ln1_b;
+          g.res_mu = e->ln_shift.p + r0;   // absolute mean of t1
+          g.res_rstd = e->ln_rstd.p + r0;
+          g.res_g = L.ln1_w.p;
+          g.res_b = L.ln1_b.p;
           g.resid_bf16 = a;
           g.stats_part = st_part;
           g.stats_ld = e->cap_rows;
@@ -957,7 +973,7 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       } else {
         // materialise the layer output (last layer of this run, or un-folded mode): h <- LN2(h), a <- bf16(h)
         ProfScope ps(e, VRAG_PROF_LAYERNORM, st);
-        HIP_TRY(launch_layernorm(h, L.ln2_w, c.norm_eps, H, M, a, h, st, L.ln2_b, nullptr, e->op_dtype));
+        HIP_TRY(launch_layernorm(h, L.ln2_w.p, c.norm_eps, H, M, a, h, st, L.ln2_b.p, nullptr, e->op_dtype));
       }
     }
   }
@@ -986,12 +1002,6 @@ int init_streams(vrag_encoder* e) {
 int init_workspace(vrag_encoder* e) {
   const vrag_encoder_config* cfg = &e->cfg;
   const int H = cfg->hidden_size, I = cfg->intermediate_size;
-  int rc;
-#define TRY(x)            \
-  do {                    \
-    rc = (x);             \
-    if (rc) return rc;    \
-  } while (0)
   int n_mb = 1;
   // load_batch cuts a batch into micro-batches of PACKED rows (tokens + the 8-row alignment gaps between sequences): budget
   // the pad rows between micro-batches from the same quantity (8 * max_seqs can exceed a micro-batch)
@@ -1001,79 +1011,67 @@ int init_workspace(vrag_encoder* e) {
                               kRowPad);
   const size_t R = e->cap_rows;
   e->cap_blocks = cfg->max_tokens / 128 + cfg->max_seqs + 1;  // >= blocks of either granularity
-  TRY(dev_alloc(e, &e->d_ids, R));
-  TRY(dev_alloc(e, &e->d_pos, R));
-  TRY(dev_alloc(e, &e->d_tokseq, R));
-  TRY(dev_alloc(e, &e->h, R * H));
-  TRY(dev_alloc(e, &e->a, R * H));
+  TRY(dev_alloc(e->d_ids, R));
+  TRY(dev_alloc(e->d_pos, R));
+  TRY(dev_alloc(e->d_tokseq, R));
+  TRY(dev_alloc(e->h, R * H));
+  TRY(dev_alloc(e->a, R * H));
   if (e->attn_w <= 0) e->attn_w = H;
   const size_t Ha = e->attn_w;
-  TRY(dev_alloc(e, &e->q, R * Ha));
-  TRY(dev_alloc(e, &e->k, R * Ha));
-  TRY(dev_alloc(e, &e->vt, R * Ha));
-  TRY(dev_alloc(e, &e->o, R * Ha));
+  TRY(dev_alloc(e->q, R * Ha));
+  TRY(dev_alloc(e->k, R * Ha));
+  TRY(dev_alloc(e->vt, R * Ha));
+  TRY(dev_alloc(e->o, R * Ha));
   if (e->i_pad <= 0) e->i_pad = I;
-  TRY(dev_alloc(e, &e->act, R * (size_t)e->i_pad));
-  TRY(dev_alloc(e, &e->f32tmp, R * H));
-  TRY(dev_alloc(e, &e->st_part, R * (H / 64) * 2));
-  TRY(dev_alloc(e, &e->ln_mu, R));
-  TRY(dev_alloc(e, &e->ln_rstd, R));
-  TRY(dev_alloc(e, &e->ln_shift, R));
-  TRY(dev_alloc(e, &e->ln_shift_prev, R));
-  TRY(dev_alloc(e, &e->lo8, (size_t)R * H));
+  TRY(dev_alloc(e->act, R * (size_t)e->i_pad));
+  TRY(dev_alloc(e->f32tmp, R * H));
+  TRY(dev_alloc(e->st_part, R * (H / 64) * 2));
+  TRY(dev_alloc(e->ln_mu, R));
+  TRY(dev_alloc(e->ln_rstd, R));
+  TRY(dev_alloc(e->ln_shift, R));
+  TRY(dev_alloc(e->ln_shift_prev, R));
+  TRY(dev_alloc(e->lo8, (size_t)R * H));
   // the six q-block descriptor arrays are slices of ONE buffer (host and device alike): one upload per batch
-  TRY(dev_alloc(e, &e->d_blk_start, (size_t)6 * e->cap_blocks));
-  e->d_blk_len = e->d_blk_start + e->cap_blocks;
-  e->d_blk_q0 = e->d_blk_start + 2 * e->cap_blocks;
-  e->d_lblk_start = e->d_blk_start + 3 * e->cap_blocks;
-  e->d_lblk_len = e->d_blk_start + 4 * e->cap_blocks;
-  e->d_lblk_q0 = e->d_blk_start + 5 * e->cap_blocks;
-  TRY(dev_alloc(e, &e->d_packed, (size_t)cfg->max_tokens));
-  TRY(dev_alloc(e, &e->d_seq_meta, (size_t)3 * cfg->max_seqs));
-  TRY(dev_alloc(e, &e->d_groups, (size_t)8 * cfg->max_seqs));
-  TRY(dev_alloc(e, &e->d_rng_start, cfg->max_ranges));
-  TRY(dev_alloc(e, &e->d_rng_end, cfg->max_ranges));
-  TRY(dev_alloc(e, &e->d_rng_out, (size_t)cfg->max_ranges * H));
-  TRY(host_alloc(e, &e->h_ids, R));
-  TRY(host_alloc(e, &e->h_blk_start, (size_t)6 * e->cap_blocks));
-  e->h_blk_len = e->h_blk_start + e->cap_blocks;
-  e->h_blk_q0 = e->h_blk_start + 2 * e->cap_blocks;
-  e->h_lblk_start = e->h_blk_start + 3 * e->cap_blocks;
-  e->h_lblk_len = e->h_blk_start + 4 * e->cap_blocks;
-  e->h_lblk_q0 = e->h_blk_start + 5 * e->cap_blocks;
-  TRY(host_alloc(e, &e->h_seq_meta, (size_t)3 * cfg->max_seqs));
-  TRY(host_alloc(e, &e->h_groups, (size_t)8 * cfg->max_seqs));
-  TRY(host_alloc(e, &e->h_rng_start, cfg->max_ranges));
-  TRY(host_alloc(e, &e->h_rng_end, cfg->max_ranges));
+  TRY(dev_alloc(e->d_blk_start, (size_t)6 * e->cap_blocks));
+  e->d_blk_len = e->d_blk_start.p + e->cap_blocks;
+  e->d_blk_q0 = e->d_blk_start.p + 2 * e->cap_blocks;
+  e->d_lblk_start = e->d_blk_start.p + 3 * e->cap_blocks;
+  e->d_lblk_len = e->d_blk_start.p + 4 * e->cap_blocks;
+  e->d_lblk_q0 = e->d_blk_start.p + 5 * e->cap_blocks;
+  TRY(dev_alloc(e->d_packed, (size_t)cfg->max_tokens));
+  TRY(dev_alloc(e->d_seq_meta, (size_t)3 * cfg->max_seqs));
+  TRY(dev_alloc(e->d_groups, (size_t)8 * cfg->max_seqs));
+  TRY(dev_alloc(e->d_rng_start, cfg->max_ranges));
+  TRY(dev_alloc(e->d_rng_end, cfg->max_ranges));
+  TRY(dev_alloc(e->d_rng_out, (size_t)cfg->max_ranges * H));
+  TRY(host_alloc(e->h_ids, R));
+  TRY(host_alloc(e->h_blk_start, (size_t)6 * e->cap_blocks));
+  e->h_blk_len = e->h_blk_start.p + e->cap_blocks;
+  e->h_blk_q0 = e->h_blk_start.p + 2 * e->cap_blocks;
+  e->h_lblk_start = e->h_blk_start.p + 3 * e->cap_blocks;
+  e->h_lblk_len = e->h_blk_start.p + 4 * e->cap_blocks;
+  e->h_lblk_q0 = e->h_blk_start.p + 5 * e->cap_blocks;
+  TRY(host_alloc(e->h_seq_meta, (size_t)3 * cfg->max_seqs));
+  TRY(host_alloc(e->h_groups, (size_t)8 * cfg->max_seqs));
+  TRY(host_alloc(e->h_rng_start, cfg->max_ranges));
+  TRY(host_alloc(e->h_rng_end, cfg->max_ranges));
   // pad ids everywhere so never-loaded rows embed a valid token
-  for (size_t i = 0; i < R; ++i) e->h_ids[i] = cfg->pad_token_id;
-  HIP_TRY(hipMemcpy(e->d_ids, e->h_ids, R * sizeof(int), hipMemcpyHostToDevice));
+  for (size_t i = 0; i < R; ++i) e->h_ids.p[i] = cfg->pad_token_id;
+  HIP_TRY(hipMemcpy(e->d_ids.p, e->h_ids.p, R * sizeof(int), hipMemcpyHostToDevice));
   HIP_TRY(hipDeviceSynchronize());
-#undef TRY
-  return VRAG_OK;
-}
-
-int ensure_h_out(vrag_encoder* e, size_t bytes) {
-  if (bytes <= e->h_out_bytes) return VRAG_OK;
-  void* p = nullptr;
-  HIP_TRY(hipHostMalloc(&p, bytes, hipHostMallocDefault));
-  e->host_allocs.push_back(p);
-  e->h_out = reinterpret_cast<float*>(p);
-  e->h_out_bytes = bytes;
   return VRAG_OK;
 }
 
 // Copies a padded device matrix [rows, cols] to the host and gathers the real tokens of each
 // sequence into the caller's concatenation order.
 int read_rows(vrag_encoder* e, const float* dsrc, int cols, float* out, hipStream_t st) {
-  const size_t bytes = (size_t)e->rows * cols * sizeof(float);
-  int rc = ensure_h_out(e, bytes);
-  if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(e->h_out, dsrc, bytes, hipMemcpyDeviceToHost, st));
+  const size_t n = (size_t)e->rows * cols, bytes = n * sizeof(float);
+  HIP_TRY(e->h_out.grow(n));   // the staging buffer it outgrows is freed
+  HIP_TRY(hipMemcpyAsync(e->h_out.p, dsrc, bytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   size_t o = 0;
   for (int s = 0; s < e->n_seqs; ++s) {
-    memcpy(out + o * cols, e->h_out + (size_t)e->seq_start[s] * cols, (size_t)e->seq_len[s] * cols * sizeof(float));
+    memcpy(out + o * cols, e->h_out.p + (size_t)e->seq_start[s] * cols, (size_t)e->seq_len[s] * cols * sizeof(float));
     o += e->seq_len[s];
   }
   return VRAG_OK;
@@ -1128,20 +1126,10 @@ int vrag_encoder_create(const vrag_encoder_config* cfg, const vrag_encoder_weigh
   }
   HIP_TRY(hipSetDevice(cfg->device));
 
-  vrag_encoder* e = new vrag_encoder();
+  auto owner = std::make_unique<vrag_encoder>();   // an early return frees everything built so far
+  vrag_encoder* e = owner.get();
   e->cfg = *cfg;
   e->op_dtype = cfg->operand_dtype;
-  auto fail = [&](int rc) {
-    vrag_encoder_destroy(e);
-    return rc;
-  };
-  int rc;
-#define TRY(x)                 \
-  do {                         \
-    rc = (x);                  \
-    if (rc) return fail(rc);   \
-  } while (0)
-
   TRY(init_streams(e));
 
   if (const char* lf = getenv("VRAG_LN_FOLD")) e->ln_fold = atoi(lf) != 0;
@@ -1154,29 +1142,29 @@ int vrag_encoder_create(const vrag_encoder_config* cfg, const vrag_encoder_weigh
   const int Ip = (int)align_up(I, 128);
   e->i_pad = Ip;
   const size_t stage_elems = std::max<size_t>({(size_t)3 * H * H, (size_t)2 * Ip * H, (size_t)1 << 22});
-  float* stage = nullptr;
-  TRY(dev_alloc(e, &stage, stage_elems, false));
+  DevArray<float> stage;   // freed on return
+  TRY(dev_alloc(stage, stage_elems, false));
   std::vector<float> wo_pad;  // mlp.Wo with zero columns for the padded GeGLU features
-  TRY(upload_f32(e, &e->tok_emb, w->tok_embeddings, (size_t)V * H));
-  TRY(upload_f32(e, &e->emb_norm, w->emb_norm, H));
-  TRY(upload_f32(e, &e->final_norm, w->final_norm, H));
+  TRY(upload_f32(e->tok_emb, w->tok_embeddings, (size_t)V * H));
+  TRY(upload_f32(e->emb_norm, w->emb_norm, H));
+  TRY(upload_f32(e->final_norm, w->final_norm, H));
   e->layers.resize(L);
   for (int l = 0; l < L; ++l) {
     Layer& ly = e->layers[l];
-    if (l > 0) TRY(upload_f32(e, &ly.attn_norm, w->attn_norm[l], H));
-    TRY(upload_f32(e, &ly.mlp_norm, w->mlp_norm[l], H));
+    if (l > 0) TRY(upload_f32(ly.attn_norm, w->attn_norm[l], H));
+    TRY(upload_f32(ly.mlp_norm, w->mlp_norm[l], H));
     // LayerNorm folded into the consumer GEMMs: W' = W * gain, s = row sums of bf16(W')
     const bool fold = e->ln_fold;
-    TRY(upload_bf16(e, &ly.wqkv, w->wqkv[l], 3 * H, H, 3 * H, 0, stage, stage_elems,
-                    fold && l > 0 ? ly.attn_norm : nullptr, fold && l > 0 ? &ly.s_qkv : nullptr));
+    TRY(upload_bf16(e, ly.wqkv, w->wqkv[l], 3 * H, H, 3 * H, 0, stage,
+                    fold && l > 0 ? ly.attn_norm.p : nullptr, fold && l > 0 ? &ly.s_qkv : nullptr));
     if (e->fused_qkv_attn) {
-      TRY(dev_alloc(e, &ly.wqkv_h, (size_t)3 * H * H, false));
-      if (ly.s_qkv) TRY(dev_alloc(e, &ly.s_qkv_h, (size_t)3 * H + 64));   // the kernel's 256-float DMA of a head's 192 sums reads 64 floats on
-      HIP_TRY(permute_qkv_heads(ly.wqkv, ly.s_qkv, H, cfg->num_heads, ly.wqkv_h, ly.s_qkv_h, nullptr));
+      TRY(dev_alloc(ly.wqkv_h, (size_t)3 * H * H, false));
+      if (ly.s_qkv.p) TRY(dev_alloc(ly.s_qkv_h, (size_t)3 * H + 64));   // the kernel's 256-float DMA of a head's 192 sums reads 64 floats on
+      HIP_TRY(permute_qkv_heads(ly.wqkv.p, ly.s_qkv.p, H, cfg->num_heads, ly.wqkv_h.p, ly.s_qkv_h.p, nullptr));
       HIP_TRY(hipDeviceSynchronize());   // null-stream work does not order against the handle's non-blocking streams
     }
-    TRY(upload_bf16(e, &ly.wo, w->wo[l], H, H, H, 0, stage, stage_elems));
-    TRY(upload_bf16(e, &ly.wi, w->wi[l], 2 * I, H, 2 * Ip, I, stage, stage_elems, fold ? ly.mlp_norm : nullptr,
+    TRY(upload_bf16(e, ly.wo, w->wo[l], H, H, H, 0, stage));
+    TRY(upload_bf16(e, ly.wi, w->wi[l], 2 * I, H, 2 * Ip, I, stage, fold ? ly.mlp_norm.p : nullptr,
                     fold ? &ly.s_wi : nullptr));
     const float* wo2 = w->wo_mlp[l];
     if (Ip != I) {
@@ -1184,21 +1172,20 @@ int vrag_encoder_create(const vrag_encoder_config* cfg, const vrag_encoder_weigh
       for (int r = 0; r < H; ++r) memcpy(&wo_pad[(size_t)r * Ip], wo2 + (size_t)r * I, (size_t)I * sizeof(float));
       wo2 = wo_pad.data();
     }
-    TRY(upload_bf16(e, &ly.wo_mlp, wo2, H, Ip, H, 0, stage, stage_elems));
+    TRY(upload_bf16(e, ly.wo_mlp, wo2, H, Ip, H, 0, stage));
   }
   {
     std::vector<float> cs, sn;
     rope_table(cfg->max_seq_len, cfg->rope_theta_global, cs, sn);
-    TRY(upload_f32(e, &e->cos_g, cs.data(), cs.size()));
-    TRY(upload_f32(e, &e->sin_g, sn.data(), sn.size()));
+    TRY(upload_f32(e->cos_g, cs.data(), cs.size()));
+    TRY(upload_f32(e->sin_g, sn.data(), sn.size()));
     rope_table(cfg->max_seq_len, cfg->rope_theta_local, cs, sn);
-    TRY(upload_f32(e, &e->cos_l, cs.data(), cs.size()));
-    TRY(upload_f32(e, &e->sin_l, sn.data(), sn.size()));
+    TRY(upload_f32(e->cos_l, cs.data(), cs.size()));
+    TRY(upload_f32(e->sin_l, sn.data(), sn.size()));
   }
 
   TRY(init_workspace(e));
-#undef TRY
-  *out = e;
+  *out = owner.release();
   return VRAG_OK;
 }
 
@@ -1232,7 +1219,8 @@ int vrag_bert_encoder_create(const vrag_bert_config* cfg, const vrag_bert_weight
   // head_dim-64 kernels with every head zero-padded to 64: padded q/k dims add 0 to every score, padded v dims
   // produce zeros that meet zero columns of the padded output projection -- the arithmetic is unchanged.
   const int hd = H / cfg->num_heads, Ha = cfg->num_heads * 64;
-  vrag_encoder* e = new vrag_encoder();
+  auto owner = std::make_unique<vrag_encoder>();   // an early return frees everything built so far
+  vrag_encoder* e = owner.get();
   e->arch = 1;
   e->op_dtype = cfg->operand_dtype;
   e->ln_fold = false;   // opt-in (VRAG_BERT_LN_FOLD=1): +4.5-6.4 % texts/s at 256 x 512 tokens, but one question's embedding 1.23 -> 1.30 ms (the consumer GEMMs finalise the statistics); the providers answer single questions, so the LayerNorm kernels stay the default
@@ -1258,26 +1246,16 @@ int vrag_bert_encoder_create(const vrag_bert_config* cfg, const vrag_bert_weight
     c.micro_batch_tokens = cfg->micro_batch_tokens;
     c.device = cfg->device;
   }
-  auto fail = [&](int rc) {
-    vrag_encoder_destroy(e);
-    return rc;
-  };
-  int rc;
-#define TRY(x)                 \
-  do {                         \
-    rc = (x);                  \
-    if (rc) return fail(rc);   \
-  } while (0)
   TRY(init_streams(e));
   const size_t stage_elems = std::max<size_t>({(size_t)3 * Ha * H, (size_t)I * H, (size_t)1 << 22});
-  float* stage = nullptr;
-  TRY(dev_alloc(e, &stage, stage_elems, false));
+  DevArray<float> stage;   // freed on return
+  TRY(dev_alloc(stage, stage_elems, false));
   std::vector<float> pw, pb, po;   // head-padded copies (head_dim 32 only)
-  TRY(upload_f32(e, &e->tok_emb, w->word_embeddings, (size_t)V * H));
-  TRY(upload_f32(e, &e->pos_emb, w->position_embeddings, (size_t)P * H));
-  if (w->token_type_row) TRY(upload_f32(e, &e->type_row, w->token_type_row, H));
-  TRY(upload_f32(e, &e->emb_norm, w->emb_norm_w, H));
-  TRY(upload_f32(e, &e->emb_norm_b, w->emb_norm_b, H));
+  TRY(upload_f32(e->tok_emb, w->word_embeddings, (size_t)V * H));
+  TRY(upload_f32(e->pos_emb, w->position_embeddings, (size_t)P * H));
+  if (w->token_type_row) TRY(upload_f32(e->type_row, w->token_type_row, H));
+  TRY(upload_f32(e->emb_norm, w->emb_norm_w, H));
+  TRY(upload_f32(e->emb_norm_b, w->emb_norm_b, H));
   e->blayers.resize(L);
   for (int l = 0; l < L; ++l) {
     BertLayer& ly = e->blayers[l];
@@ -1303,8 +1281,8 @@ int vrag_bert_encoder_create(const vrag_bert_config* cfg, const vrag_bert_weight
       bqkv = pb.data();
       wo = po.data();
     }
-    TRY(upload_f32(e, &ly.ln1_w, w->attn_norm_w[l], H));
-    TRY(upload_f32(e, &ly.ln1_b, w->attn_norm_b[l], H));
+    TRY(upload_f32(ly.ln1_w, w->attn_norm_w[l], H));
+    TRY(upload_f32(ly.ln1_b, w->attn_norm_b[l], H));
     // folded bias: b + W . ln_bias (the LayerNorm bias pushed through the linear layer), fp32 on the host
     auto folded_bias = [&](const float* W, const float* bvec, const float* ln_b, int rows, std::vector<float>& out) {
       out.resize(rows);
@@ -1318,71 +1296,51 @@ int vrag_bert_encoder_create(const vrag_bert_config* cfg, const vrag_bert_weight
     std::vector<float> cb;
     if (e->ln_fold && l > 0) {   // QKV consumes LN2 of the previous layer
       folded_bias(wqkv, bqkv, w->out_norm_b[l - 1], 3 * Ha, cb);
-      TRY(upload_bf16(e, &ly.wqkv, wqkv, 3 * Ha, H, 3 * Ha, 0, stage, stage_elems, e->blayers[l - 1].ln2_w, &ly.s_qkv));
-      TRY(upload_f32(e, &ly.bqkv, cb.data(), (size_t)3 * Ha));
+      TRY(upload_bf16(e, ly.wqkv, wqkv, 3 * Ha, H, 3 * Ha, 0, stage, e->blayers[l - 1].ln2_w.p, &ly.s_qkv));
+      TRY(upload_f32(ly.bqkv, cb.data(), (size_t)3 * Ha));
     } else {
-      TRY(upload_bf16(e, &ly.wqkv, wqkv, 3 * Ha, H, 3 * Ha, 0, stage, stage_elems));
-      TRY(upload_f32(e, &ly.bqkv, bqkv, (size_t)3 * Ha));
+      TRY(upload_bf16(e, ly.wqkv, wqkv, 3 * Ha, H, 3 * Ha, 0, stage));
+      TRY(upload_f32(ly.bqkv, bqkv, (size_t)3 * Ha));
     }
-    TRY(upload_bf16(e, &ly.wo, wo, H, Ha, H, 0, stage, stage_elems));
-    TRY(upload_f32(e, &ly.bo, w->bo[l], H));
+    TRY(upload_bf16(e, ly.wo, wo, H, Ha, H, 0, stage));
+    TRY(upload_f32(ly.bo, w->bo[l], H));
     if (e->ln_fold) {            // W1 consumes LN1 of this layer
       folded_bias(w->w1[l], w->b1[l], w->attn_norm_b[l], I, cb);
-      TRY(upload_bf16(e, &ly.w1, w->w1[l], I, H, I, 0, stage, stage_elems, ly.ln1_w, &ly.s_w1));
-      TRY(upload_f32(e, &ly.b1, cb.data(), I));
+      TRY(upload_bf16(e, ly.w1, w->w1[l], I, H, I, 0, stage, ly.ln1_w.p, &ly.s_w1));
+      TRY(upload_f32(ly.b1, cb.data(), I));
     } else {
-      TRY(upload_bf16(e, &ly.w1, w->w1[l], I, H, I, 0, stage, stage_elems));
-      TRY(upload_f32(e, &ly.b1, w->b1[l], I));
+      TRY(upload_bf16(e, ly.w1, w->w1[l], I, H, I, 0, stage));
+      TRY(upload_f32(ly.b1, w->b1[l], I));
     }
-    TRY(upload_bf16(e, &ly.w2, w->w2[l], H, I, H, 0, stage, stage_elems));
-    TRY(upload_f32(e, &ly.b2, w->b2[l], H));
-    TRY(upload_f32(e, &ly.ln2_w, w->out_norm_w[l], H));
-    TRY(upload_f32(e, &ly.ln2_b, w->out_norm_b[l], H));
+    TRY(upload_bf16(e, ly.w2, w->w2[l], H, I, H, 0, stage));
+    TRY(upload_f32(ly.b2, w->b2[l], H));
+    TRY(upload_f32(ly.ln2_w, w->out_norm_w[l], H));
+    TRY(upload_f32(ly.ln2_b, w->out_norm_b[l], H));
   }
   {
     // identity rotation: the QKV epilogue's RoPE becomes a no-op
     std::vector<float> cs((size_t)cfg->max_seq_len * 32, 1.0f), sn((size_t)cfg->max_seq_len * 32, 0.0f);
-    TRY(upload_f32(e, &e->cos_g, cs.data(), cs.size()));
-    TRY(upload_f32(e, &e->sin_g, sn.data(), sn.size()));
+    TRY(upload_f32(e->cos_g, cs.data(), cs.size()));
+    TRY(upload_f32(e->sin_g, sn.data(), sn.size()));
   }
   TRY(init_workspace(e));
-#undef TRY
-  *out = e;
+  *out = owner.release();
   return VRAG_OK;
 }
 
-void vrag_encoder_destroy(vrag_encoder* e) {
-  if (!e) return;
-  (void)hipSetDevice(e->cfg.device);
-  (void)hipDeviceSynchronize();
-  for (auto& r : e->prof_pending) {
-    (void)hipEventDestroy(r.a);
-    (void)hipEventDestroy(r.b);
-  }
-  for (auto ev : e->prof_free) (void)hipEventDestroy(ev);
-  for (auto& kv : e->graphs) {
-    if (kv.second.exec) (void)hipGraphExecDestroy(kv.second.exec);
-    if (kv.second.graph) (void)hipGraphDestroy(kv.second.graph);
-  }
-  for (void* p : e->dev_allocs) (void)hipFree(p);
-  for (void* p : e->host_allocs) (void)hipHostFree(p);
-  for (int i = 0; i < 4; ++i) {
-    if (e->aux_streams[i]) (void)hipStreamDestroy(e->aux_streams[i]);
-    if (e->ev_join[i]) (void)hipEventDestroy(e->ev_join[i]);
-  }
-  if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-  if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
-  delete e;
-}
+void vrag_encoder_destroy(vrag_encoder* e) { delete e; }
+
+// Setting a head (again): the device is drained, every buffer of the head's previous form is freed, and the new one is built --
+// a bias that is not given stays absent.  The label count is cleared first, so a head that fails half-way reads as not set.
 
 int vrag_encoder_set_qa_head(vrag_encoder* e, const float* w, const float* b, int32_t num_labels) {
   ARG_CHECK(e && w && b && num_labels > 0 && num_labels <= e->cfg.hidden_size, "bad qa head arguments");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
-  int rc = upload_f32(e, &e->qa_w, w, (size_t)num_labels * e->cfg.hidden_size);
-  if (rc) return rc;
-  rc = upload_f32(e, &e->qa_b, b, num_labels);
-  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  e->qa_labels = 0;
+  TRY(upload_f32(e->qa_w, w, (size_t)num_labels * e->cfg.hidden_size));
+  TRY(upload_f32(e->qa_b, b, num_labels));
   e->qa_labels = num_labels;
   return VRAG_OK;
 }
@@ -1393,17 +1351,17 @@ int vrag_encoder_set_token_head(vrag_encoder* e, const float* dense_w, const flo
             "bad token head arguments");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
+  HIP_TRY(hipDeviceSynchronize());
+  e->tk_labels = 0;
   const int H = e->cfg.hidden_size;
-  float* stage = nullptr;
-  int rc = dev_alloc(e, &stage, (size_t)H * H, false);
-  if (rc) return rc;
+  DevArray<float> stage;   // freed on return
+  TRY(dev_alloc(stage, (size_t)H * H, false));
   // dense weight as (value, remainder) operand pairs: the head GEMM then carries ~fp32 precision (see run_token_head)
-  rc = upload_bf16(e, &e->tk_dense, dense_w, H, H, H, 0, stage, (size_t)H * H, nullptr, nullptr, &e->tk_dense_lo);
-  if (rc) return rc;
-  if ((rc = upload_f32(e, &e->tk_norm, norm_w, H))) return rc;
-  if ((rc = upload_f32(e, &e->tk_w, cls_w, (size_t)num_labels * H))) return rc;
-  if ((rc = upload_f32(e, &e->tk_b, cls_b, num_labels))) return rc;
-  if ((rc = dev_alloc(e, &e->d_tok_logits, (size_t)e->cap_rows * num_labels))) return rc;
+  TRY(upload_bf16(e, e->tk_dense, dense_w, H, H, H, 0, stage, nullptr, nullptr, &e->tk_dense_lo));
+  TRY(upload_f32(e->tk_norm, norm_w, H));
+  TRY(upload_f32(e->tk_w, cls_w, (size_t)num_labels * H));
+  TRY(upload_f32(e->tk_b, cls_b, num_labels));
+  TRY(dev_alloc(e->d_tok_logits, (size_t)e->cap_rows * num_labels));
   e->tk_labels = num_labels;
   return VRAG_OK;
 }
@@ -1413,60 +1371,51 @@ int vrag_encoder_set_mlm_head_ex(vrag_encoder* e, const float* dense_w, const fl
   ARG_CHECK(e && dense_w && norm_w, "bad mlm head arguments");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
+  HIP_TRY(hipDeviceSynchronize());
+  // the previous head goes first, whichever operand form it had (vrag_encoder_set_head_precision)
+  for (DevArray<bf16_t>* p : {&e->mlm_dense, &e->mlm_dense_lo, &e->mlm_dec, &e->mlm_dec3, &e->splade_a3}) *p = DevArray<bf16_t>();
+  for (DevArray<float>* p : {&e->mlm_dense_b, &e->mlm_norm, &e->mlm_norm_b, &e->mlm_bias}) *p = DevArray<float>();
+  e->d_splade = DevArray<unsigned>();
   const int H = e->cfg.hidden_size, V = e->cfg.vocab_size;
   const int vpad = (int)align_up(V, 256);  // whole 256-wide GEMM tiles
-  const size_t stage_elems = std::max<size_t>((size_t)H * H, (size_t)1 << 22);
-  float* stage = nullptr;
-  // setting the head again (another checkpoint's, or the other operand form): the previous decoder images go first
-  HIP_TRY(hipDeviceSynchronize());
-  dev_release(e, &e->mlm_dec);
-  dev_release(e, &e->mlm_dec3);
-  dev_release(e, &e->splade_a3);
-  dev_release(e, &e->mlm_dense_lo);
-  dev_release(e, &e->mlm_dense);
-  dev_release(e, &e->mlm_bias);
-  dev_release(e, &e->d_splade);
-  int rc = dev_alloc(e, &stage, stage_elems, false);
-  if (rc) return rc;
-  if ((rc = upload_bf16(e, &e->mlm_dense, dense_w, H, H, H, 0, stage, stage_elems, nullptr, nullptr,
-                        e->mlm_split ? &e->mlm_dense_lo : nullptr)))
-    return rc;
-  if ((rc = upload_f32(e, &e->mlm_norm, norm_w, H))) return rc;
-  if (dense_b && (rc = upload_f32(e, &e->mlm_dense_b, dense_b, H))) return rc;
-  if (norm_b && (rc = upload_f32(e, &e->mlm_norm_b, norm_b, H))) return rc;
+  DevArray<float> stage;   // freed on return
+  TRY(dev_alloc(stage, std::max<size_t>((size_t)H * H, (size_t)1 << 22), false));
+  TRY(upload_bf16(e, e->mlm_dense, dense_w, H, H, H, 0, stage, nullptr, nullptr, e->mlm_split ? &e->mlm_dense_lo : nullptr));
+  TRY(upload_f32(e->mlm_norm, norm_w, H));
+  if (dense_b) TRY(upload_f32(e->mlm_dense_b, dense_b, H));
+  if (norm_b) TRY(upload_f32(e->mlm_norm_b, norm_b, H));
   if (e->mlm_split) {
     // decoder as [Whi | Whi | Wlo] rows of 3H operand values; host weights stream through the staging buffer in row chunks
-    if ((rc = dev_alloc(e, &e->mlm_dec3, (size_t)vpad * 3 * H, false))) return rc;
-    if ((rc = dev_alloc(e, &e->splade_a3, (size_t)e->cap_rows * 3 * H, true))) return rc;
+    TRY(dev_alloc(e->mlm_dec3, (size_t)vpad * 3 * H, false));
+    TRY(dev_alloc(e->splade_a3, (size_t)e->cap_rows * 3 * H, true));
     if (decoder_w) {
-      const int chunk = (int)std::max<size_t>(1, stage_elems / H);
+      const int chunk = (int)std::max<size_t>(1, stage.n / H);
       for (int r0 = 0; r0 < vpad; r0 += chunk) {
         const int nr_dst = std::min(chunk, vpad - r0), nr_src = std::max(0, std::min(chunk, V - r0));
-        if (nr_src > 0) HIP_TRY(hipMemcpy(stage, decoder_w + (size_t)r0 * H, (size_t)nr_src * H * sizeof(float), hipMemcpyHostToDevice));
-        launch_cvt_split3(e->op_dtype, 0, stage, e->mlm_dec3 + (size_t)r0 * 3 * H, nr_dst, nr_src, H);
+        if (nr_src > 0) HIP_TRY(hipMemcpy(stage.p, decoder_w + (size_t)r0 * H, (size_t)nr_src * H * sizeof(float), hipMemcpyHostToDevice));
+        launch_cvt_split3(e->op_dtype, 0, stage.p, e->mlm_dec3.p + (size_t)r0 * 3 * H, nr_dst, nr_src, H);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());
       }
     } else {   // tied decoder: the device-resident fp32 embedding table
-      launch_cvt_split3(e->op_dtype, 0, e->tok_emb, e->mlm_dec3, vpad, V, H);
+      launch_cvt_split3(e->op_dtype, 0, e->tok_emb.p, e->mlm_dec3.p, vpad, V, H);
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipDeviceSynchronize());
     }
   } else if (decoder_w) {
-    if ((rc = upload_bf16(e, &e->mlm_dec, decoder_w, V, H, vpad, 0, stage, stage_elems))) return rc;
+    TRY(upload_bf16(e, e->mlm_dec, decoder_w, V, H, vpad, 0, stage));
   } else {
     // tied decoder: convert the device-resident fp32 embedding table
-    if ((rc = dev_alloc(e, &e->mlm_dec, (size_t)vpad * H, false))) return rc;
-    launch_cvt_rows(e->op_dtype, dim3(vpad), 0, e->tok_emb, e->mlm_dec, vpad, V, H, 0, (const float*)nullptr, (float*)nullptr);
+    TRY(dev_alloc(e->mlm_dec, (size_t)vpad * H, false));
+    launch_cvt_rows(e->op_dtype, dim3(vpad), 0, e->tok_emb.p, e->mlm_dec.p, vpad, V, H, 0, (const float*)nullptr, (float*)nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
   }
-  if ((rc = dev_alloc(e, &e->mlm_bias, vpad, true))) return rc;
-  if (decoder_b) HIP_TRY(hipMemcpy(e->mlm_bias, decoder_b, (size_t)V * sizeof(float), hipMemcpyHostToDevice));
-  if ((rc = dev_alloc(e, &e->d_splade, (size_t)e->cfg.max_seqs * vpad))) return rc;
+  TRY(dev_alloc(e->mlm_bias, vpad, true));
+  if (decoder_b) HIP_TRY(hipMemcpy(e->mlm_bias.p, decoder_b, (size_t)V * sizeof(float), hipMemcpyHostToDevice));
+  TRY(dev_alloc(e->d_splade, (size_t)e->cfg.max_seqs * vpad));
   e->vpad = vpad;
   HIP_TRY(hipDeviceSynchronize());
-  dev_release(e, &stage);
   return VRAG_OK;
 }
 
@@ -1489,36 +1438,37 @@ int vrag_encoder_set_token_types(vrag_encoder* e, const float* table, int32_t n_
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   ARG_CHECK(e->arch == 1, "token types exist on BERT-family handles only");
   HIP_TRY(hipSetDevice(e->cfg.device));
-  int rc = upload_f32(e, &e->type_table, table, (size_t)n_types * e->cfg.hidden_size);
-  if (rc) return rc;
-  if (!e->d_types) {
-    if ((rc = dev_alloc(e, &e->d_types, e->cap_rows))) return rc;
-    if ((rc = host_alloc(e, &e->h_types, e->cap_rows))) return rc;
-  }
+  HIP_TRY(hipDeviceSynchronize());
+  e->clear_graphs();         // a captured layer schedule holds the old table's address (graph_replays / graph_clock go on counting)
+  e->n_types = 0;
+  e->types_loaded = false;   // segment ids were checked against the old table: vrag_encoder_load_token_types again
+  TRY(upload_f32(e->type_table, table, (size_t)n_types * e->cfg.hidden_size));
+  TRY(dev_alloc(e->d_types, e->cap_rows));
+  TRY(host_alloc(e->h_types, e->cap_rows));
   e->n_types = n_types;
   return VRAG_OK;
 }
 
 int vrag_encoder_load_token_types(vrag_encoder* e, const int32_t* types, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
-  ARG_CHECK(types, "null token types");
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  ARG_CHECK(e->type_table != nullptr, "token type table not set (vrag_encoder_set_token_types)");
+  TRY(check_ready(e));
+  ARG_CHECK(types, "null token types");
+  ARG_CHECK(e->type_table.p != nullptr, "token type table not set (vrag_encoder_set_token_types)");
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t st = pick_stream(e, stream);
   HIP_TRY(hipStreamSynchronize(st));   // a previous upload may still read the pinned staging buffer
-  memset(e->h_types, 0, (size_t)e->rows * sizeof(int));
+  memset(e->h_types.p, 0, (size_t)e->rows * sizeof(int));
   size_t src = 0;
   for (int s = 0; s < e->n_seqs; ++s) {
     for (int i = 0; i < e->seq_len[s]; ++i) {
       const int t = types[src + i];
       ARG_CHECK(t >= 0 && t < e->n_types, "token type %d outside the table (sequence %d)", t, s);
-      e->h_types[e->seq_start[s] + i] = t;
+      e->h_types.p[e->seq_start[s] + i] = t;
     }
     src += e->seq_len[s];
   }
-  HIP_TRY(hipMemcpyAsync(e->d_types, e->h_types, (size_t)e->rows * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_types.p, e->h_types.p, (size_t)e->rows * sizeof(int), hipMemcpyHostToDevice, st));
   e->types_loaded = true;
   e->ran = false;
   return VRAG_OK;
@@ -1529,48 +1479,47 @@ int vrag_encoder_set_pair_head(vrag_encoder* e, const float* pooler_w, const flo
   ARG_CHECK(e && pooler_w && pooler_b && cls_w && cls_b && num_labels > 0 && num_labels <= 64, "bad pair head arguments");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
+  HIP_TRY(hipDeviceSynchronize());
+  e->pr_labels = 0;
   const int H = e->cfg.hidden_size;
-  int rc;
-  if ((rc = upload_f32(e, &e->pr_wp, pooler_w, (size_t)H * H))) return rc;
-  if ((rc = upload_f32(e, &e->pr_bp, pooler_b, H))) return rc;
-  if ((rc = upload_f32(e, &e->pr_wc, cls_w, (size_t)num_labels * H))) return rc;
-  if ((rc = upload_f32(e, &e->pr_bc, cls_b, num_labels))) return rc;
-  if ((rc = dev_alloc(e, &e->d_pair_out, (size_t)e->cfg.max_seqs * num_labels))) return rc;
-  if (!e->d_first_row) {
-    if ((rc = dev_alloc(e, &e->d_first_row, e->cfg.max_seqs))) return rc;
-    if ((rc = host_alloc(e, &e->h_first_row, e->cfg.max_seqs))) return rc;
-  }
+  TRY(upload_f32(e->pr_wp, pooler_w, (size_t)H * H));
+  TRY(upload_f32(e->pr_bp, pooler_b, H));
+  TRY(upload_f32(e->pr_wc, cls_w, (size_t)num_labels * H));
+  TRY(upload_f32(e->pr_bc, cls_b, num_labels));
+  TRY(dev_alloc(e->d_pair_out, (size_t)e->cfg.max_seqs * num_labels));
+  TRY(dev_alloc(e->d_first_row, e->cfg.max_seqs));
+  TRY(host_alloc(e->h_first_row, e->cfg.max_seqs));
   e->pr_labels = num_labels;
   return VRAG_OK;
 }
 
 int vrag_encoder_run_pair_head(vrag_encoder* e, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
   ARG_CHECK(e->pr_labels > 0, "pair head not set (vrag_encoder_set_pair_head)");
   ARG_CHECK(e->ran, "encoder has not run on this batch");
-  ARG_CHECK(e->final_norm == nullptr, "the pair head reads an already-normalised stream (BERT-family handles)");
+  ARG_CHECK(e->final_norm.p == nullptr, "the pair head reads an already-normalised stream (BERT-family handles)");
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t st = pick_stream(e, stream);
   HIP_TRY(hipStreamSynchronize(st));
-  for (int s = 0; s < e->n_seqs; ++s) e->h_first_row[s] = e->seq_start[s];
-  HIP_TRY(hipMemcpyAsync(e->d_first_row, e->h_first_row, (size_t)e->n_seqs * sizeof(int), hipMemcpyHostToDevice, st));
+  for (int s = 0; s < e->n_seqs; ++s) e->h_first_row.p[s] = e->seq_start[s];
+  HIP_TRY(hipMemcpyAsync(e->d_first_row.p, e->h_first_row.p, (size_t)e->n_seqs * sizeof(int), hipMemcpyHostToDevice, st));
   ProfScope ps(e, VRAG_PROF_HEAD, st);
-  HIP_TRY(launch_pooler_classifier(e->h, e->cfg.hidden_size, e->d_first_row, e->n_seqs, e->pr_wp, e->pr_bp, e->pr_wc,
-                                   e->pr_bc, e->pr_labels, e->d_pair_out, st));
+  HIP_TRY(launch_pooler_classifier(e->h.p, e->cfg.hidden_size, e->d_first_row.p, e->n_seqs, e->pr_wp.p, e->pr_bp.p, e->pr_wc.p,
+                                   e->pr_bc.p, e->pr_labels, e->d_pair_out.p, st));
   return VRAG_OK;
 }
 
 int vrag_encoder_read_pair_logits(vrag_encoder* e, float* logits, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
-  ARG_CHECK(logits, "null output");
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
+  ARG_CHECK(logits, "null output");
   ARG_CHECK(e->pr_labels > 0, "pair head not set");
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t st = pick_stream(e, stream);
-  HIP_TRY(hipMemcpyAsync(logits, e->d_pair_out, (size_t)e->n_seqs * e->pr_labels * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(logits, e->d_pair_out.p, (size_t)e->n_seqs * e->pr_labels * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return VRAG_OK;
 }
@@ -1583,34 +1532,32 @@ int vrag_encoder_set_seq_head(vrag_encoder* e, const float* dense_w, const float
   ARG_CHECK(e->arch == 0, "the sequence-classification head is defined for the ModernBERT encoder only "
                           "(BERT-family cross-encoders: vrag_encoder_set_pair_head)");
   HIP_TRY(hipSetDevice(e->cfg.device));
-  const int H = e->cfg.hidden_size;
-  // setting the head again (other biases, pooling or labels): the previous buffers go first
   HIP_TRY(hipDeviceSynchronize());
-  for (float** p : {&e->sq_wdT, &e->sq_bd, &e->sq_wn, &e->sq_bn, &e->sq_wc, &e->sq_bc, &e->d_sq_pooled, &e->d_sq_out})
-    dev_release(e, p);
   e->sq_labels = 0;
+  for (DevArray<float>* p : {&e->sq_wdT, &e->sq_bd, &e->sq_wn, &e->sq_bn, &e->sq_wc, &e->sq_bc, &e->d_sq_pooled, &e->d_sq_out})
+    *p = DevArray<float>();
+  const int H = e->cfg.hidden_size;
   // the kernel streams the dense weight row by row of INPUT features: [out, in] (HF Linear) -> [in, out]
   std::vector<float> wT((size_t)H * H);
   for (int o = 0; o < H; ++o)
     for (int i = 0; i < H; ++i) wT[(size_t)i * H + o] = dense_w[(size_t)o * H + i];
-  int rc;
-  if ((rc = upload_f32(e, &e->sq_wdT, wT.data(), (size_t)H * H))) return rc;
-  if (dense_b && (rc = upload_f32(e, &e->sq_bd, dense_b, H))) return rc;
-  if ((rc = upload_f32(e, &e->sq_wn, norm_w, H))) return rc;
-  if (norm_b && (rc = upload_f32(e, &e->sq_bn, norm_b, H))) return rc;
-  if ((rc = upload_f32(e, &e->sq_wc, cls_w, (size_t)num_labels * H))) return rc;
-  if ((rc = upload_f32(e, &e->sq_bc, cls_b, num_labels))) return rc;
-  if ((rc = dev_alloc(e, &e->d_sq_pooled, (size_t)e->cfg.max_seqs * H))) return rc;
-  if ((rc = dev_alloc(e, &e->d_sq_out, (size_t)e->cfg.max_seqs * num_labels))) return rc;
+  TRY(upload_f32(e->sq_wdT, wT.data(), (size_t)H * H));
+  if (dense_b) TRY(upload_f32(e->sq_bd, dense_b, H));
+  TRY(upload_f32(e->sq_wn, norm_w, H));
+  if (norm_b) TRY(upload_f32(e->sq_bn, norm_b, H));
+  TRY(upload_f32(e->sq_wc, cls_w, (size_t)num_labels * H));
+  TRY(upload_f32(e->sq_bc, cls_b, num_labels));
+  TRY(dev_alloc(e->d_sq_pooled, (size_t)e->cfg.max_seqs * H));
+  TRY(dev_alloc(e->d_sq_out, (size_t)e->cfg.max_seqs * num_labels));
   e->sq_pool_mean = pooling;
   e->sq_labels = num_labels;
   return VRAG_OK;
 }
 
 int vrag_encoder_run_seq_head(vrag_encoder* e, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
   ARG_CHECK(e->arch == 0, "the sequence-classification head is defined for the ModernBERT encoder only "
                           "(BERT-family cross-encoders: vrag_encoder_set_pair_head)");
   ARG_CHECK(e->sq_labels > 0, "sequence head not set (vrag_encoder_set_seq_head)");
@@ -1620,21 +1567,21 @@ int vrag_encoder_run_seq_head(vrag_encoder* e, void* stream) {
   const int ms = e->cfg.max_seqs;
   ProfScope ps(e, VRAG_PROF_HEAD, st);
   // first rows and lengths: the device copy load_batch made of the batch's geometry (d_seq_meta: [3][max_seqs])
-  HIP_TRY(launch_seq_head(e->h, e->final_norm, e->cfg.norm_eps, e->cfg.hidden_size, e->d_seq_meta, e->d_seq_meta + 2 * ms,
-                          e->n_seqs, e->sq_pool_mean, e->d_sq_pooled, e->sq_wdT, e->sq_bd, e->sq_wn, e->sq_bn, e->sq_wc,
-                          e->sq_bc, e->sq_labels, e->d_sq_out, st));
+  HIP_TRY(launch_seq_head(e->h.p, e->final_norm.p, e->cfg.norm_eps, e->cfg.hidden_size, e->d_seq_meta.p, e->d_seq_meta.p + 2 * ms,
+                          e->n_seqs, e->sq_pool_mean, e->d_sq_pooled.p, e->sq_wdT.p, e->sq_bd.p, e->sq_wn.p, e->sq_bn.p, e->sq_wc.p,
+                          e->sq_bc.p, e->sq_labels, e->d_sq_out.p, st));
   return VRAG_OK;
 }
 
 int vrag_encoder_read_seq_logits(vrag_encoder* e, float* logits, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
-  ARG_CHECK(logits, "null output");
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
+  ARG_CHECK(logits, "null output");
   ARG_CHECK(e->sq_labels > 0, "sequence head not set");
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t st = pick_stream(e, stream);
-  HIP_TRY(hipMemcpyAsync(logits, e->d_sq_out, (size_t)e->n_seqs * e->sq_labels * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(logits, e->d_sq_out.p, (size_t)e->n_seqs * e->sq_labels * sizeof(float), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return VRAG_OK;
 }
@@ -1686,7 +1633,7 @@ int vrag_encoder_load_batch(vrag_encoder* e, const int32_t* ids, const int32_t* 
   int t = 0, mb_row0 = 0, mb_blk0 = 0, nblk = 0, mb_lblk0 = 0, nlblk = 0, mb_tokens = 0, mb_seq0 = 0, mb_max_len = 0;
   size_t src = 0;
   const int prev_rows = e->rows;
-  int *seq_row = e->h_seq_meta, *seq_src = e->h_seq_meta + c.max_seqs, *seq_ln = e->h_seq_meta + 2 * c.max_seqs;
+  int *seq_row = e->h_seq_meta.p, *seq_src = e->h_seq_meta.p + c.max_seqs, *seq_ln = e->h_seq_meta.p + 2 * c.max_seqs;
   for (int s = 0; s < n_seqs; ++s) {
     const int Ls = seq_lens[s];
     t = (int)align_up(t, kSeqAlign);
@@ -1707,7 +1654,7 @@ int vrag_encoder_load_batch(vrag_encoder* e, const int32_t* ids, const int32_t* 
     seq_ln[s] = Ls;
     for (int q0 = 0; q0 < Ls; q0 += attention_q_block(false)) {
       if (nblk < e->cap_blocks) {
-        e->h_blk_start[nblk] = t;
+        e->h_blk_start.p[nblk] = t;
         e->h_blk_len[nblk] = Ls;
         e->h_blk_q0[nblk] = q0;
       }
@@ -1738,7 +1685,7 @@ int vrag_encoder_load_batch(vrag_encoder* e, const int32_t* ids, const int32_t* 
     for (int64_t i = 0; i < total; ++i) {   // one vectorisable pass: copy + range check
       const int id = ids[i];
       bad |= (unsigned)((unsigned)id >= V);
-      e->h_ids[i] = id;
+      e->h_ids.p[i] = id;
     }
     if (bad) {
       size_t o = 0;
@@ -1757,7 +1704,7 @@ int vrag_encoder_load_batch(vrag_encoder* e, const int32_t* ids, const int32_t* 
     mb.grp0 = mb.grp1 = n_groups;
     if (e->arch == 1 || !e->fused_qkv_attn || mb.max_len > kFusedMaxSeq) continue;
     if (e->fused_qkv_attn != 2 && gemm_consumer_finalizes(mb.row1 - mb.row0)) continue;
-    n_groups += pack_groups_best_fit(seq_row, seq_ln, mb.seq0, mb.seq1, e->h_groups + (size_t)n_groups * 8);
+    n_groups += pack_groups_best_fit(seq_row, seq_ln, mb.seq0, mb.seq1, e->h_groups.p + (size_t)n_groups * 8);
     mb.grp1 = n_groups;
   }
   e->n_seqs = n_seqs;
@@ -1767,14 +1714,14 @@ int vrag_encoder_load_batch(vrag_encoder* e, const int32_t* ids, const int32_t* 
   e->n_ranges = 0;
   e->ran = false;
   e->types_loaded = false;   // segment ids belong to one batch
-  HIP_TRY(hipMemcpyAsync(e->d_packed, e->h_ids, (size_t)total * sizeof(int), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(e->d_seq_meta, e->h_seq_meta, (size_t)3 * c.max_seqs * sizeof(int), hipMemcpyHostToDevice, st));
-  if (n_groups > 0) HIP_TRY(hipMemcpyAsync(e->d_groups, e->h_groups, (size_t)n_groups * 8 * sizeof(int4), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_packed.p, e->h_ids.p, (size_t)total * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_seq_meta.p, e->h_seq_meta.p, (size_t)3 * c.max_seqs * sizeof(int), hipMemcpyHostToDevice, st));
+  if (n_groups > 0) HIP_TRY(hipMemcpyAsync(e->d_groups.p, e->h_groups.p, (size_t)n_groups * 8 * sizeof(int4), hipMemcpyHostToDevice, st));
   // one upload for the six descriptor arrays: from the first used entry of the first to the last used entry of the last
-  HIP_TRY(hipMemcpyAsync(e->d_blk_start, e->h_blk_start, ((size_t)5 * e->cap_blocks + nlblk) * sizeof(int), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(pack_layout_kernel, dim3((fill_to + 255) / 256), dim3(256), 0, st, e->d_packed, e->d_seq_meta,
-                     e->d_seq_meta + c.max_seqs, e->d_seq_meta + 2 * c.max_seqs, n_seqs, fill_to, c.pad_token_id, e->d_ids, e->d_pos,
-                     e->d_tokseq);
+  HIP_TRY(hipMemcpyAsync(e->d_blk_start.p, e->h_blk_start.p, ((size_t)5 * e->cap_blocks + nlblk) * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(pack_layout_kernel, dim3((fill_to + 255) / 256), dim3(256), 0, st, e->d_packed.p, e->d_seq_meta.p,
+                     e->d_seq_meta.p + c.max_seqs, e->d_seq_meta.p + 2 * c.max_seqs, n_seqs, fill_to, c.pad_token_id, e->d_ids.p, e->d_pos.p,
+                     e->d_tokseq.p);
   HIP_TRY(hipGetLastError());
   return VRAG_OK;
 }
@@ -1842,10 +1789,10 @@ static int run_layers_maybe_graphed(vrag_encoder* e, int n_layers, hipStream_t s
 }
 
 int vrag_encoder_run_layers(vrag_encoder* e, int32_t n_layers, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
-  ARG_CHECK(n_layers >= 0 && n_layers <= e->cfg.num_layers, "n_layers out of range");
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
+  ARG_CHECK(n_layers >= 0 && n_layers <= e->cfg.num_layers, "n_layers out of range");
   HIP_TRY(hipSetDevice(e->cfg.device));
   return run_layers_maybe_graphed(e, n_layers, pick_stream(e, stream));
 }
@@ -1874,10 +1821,10 @@ int vrag_encoder_run(vrag_encoder* e, void* stream) {
 
 int vrag_encoder_load_ranges(vrag_encoder* e, const int32_t* seq_idx, const int32_t* start, const int32_t* end,
                              int32_t n_ranges, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
-  ARG_CHECK(seq_idx && start && end && n_ranges > 0, "bad range arguments");
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
+  ARG_CHECK(seq_idx && start && end && n_ranges > 0, "bad range arguments");
   if (n_ranges > e->cfg.max_ranges) {
     set_error("%d ranges, handle capacity is %d", n_ranges, e->cfg.max_ranges);
     return VRAG_ERR_CAPACITY;
@@ -1890,74 +1837,74 @@ int vrag_encoder_load_ranges(vrag_encoder* e, const int32_t* seq_idx, const int3
     ARG_CHECK(s >= 0 && s < e->n_seqs, "range %d: sequence index %d out of range", i, s);
     ARG_CHECK(start[i] >= 0 && end[i] >= start[i] && end[i] < e->seq_len[s],
               "range %d: [%d, %d] is not inside sequence %d of length %d", i, start[i], end[i], s, e->seq_len[s]);
-    e->h_rng_start[i] = e->seq_start[s] + start[i];
-    e->h_rng_end[i] = e->seq_start[s] + end[i];
+    e->h_rng_start.p[i] = e->seq_start[s] + start[i];
+    e->h_rng_end.p[i] = e->seq_start[s] + end[i];
   }
   e->n_ranges = n_ranges;
-  HIP_TRY(hipMemcpyAsync(e->d_rng_start, e->h_rng_start, (size_t)n_ranges * sizeof(int), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(e->d_rng_end, e->h_rng_end, (size_t)n_ranges * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_rng_start.p, e->h_rng_start.p, (size_t)n_ranges * sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(e->d_rng_end.p, e->h_rng_end.p, (size_t)n_ranges * sizeof(int), hipMemcpyHostToDevice, st));
   return VRAG_OK;
 }
 
 int vrag_encoder_run_qa_head(vrag_encoder* e, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
   ARG_CHECK(e->qa_labels > 0, "qa head not set (vrag_encoder_set_qa_head)");
   ARG_CHECK(e->n_ranges > 0, "no ranges loaded (vrag_encoder_load_ranges)");
   ARG_CHECK(e->ran, "encoder has not run on this batch");
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t st = pick_stream(e, stream);
   ProfScope ps(e, VRAG_PROF_HEAD, st);
-  HIP_TRY(launch_range_pool(e->h, e->final_norm, e->cfg.norm_eps, e->cfg.hidden_size, e->d_rng_start, e->d_rng_end,
-                            e->n_ranges, 0, e->qa_w, e->qa_b, e->qa_labels, e->d_rng_out, st));
+  HIP_TRY(launch_range_pool(e->h.p, e->final_norm.p, e->cfg.norm_eps, e->cfg.hidden_size, e->d_rng_start.p, e->d_rng_end.p,
+                            e->n_ranges, 0, e->qa_w.p, e->qa_b.p, e->qa_labels, e->d_rng_out.p, st));
   return VRAG_OK;
 }
 
 int vrag_encoder_read_qa_logits(vrag_encoder* e, float* logits, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
-  ARG_CHECK(logits, "null output");
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
+  ARG_CHECK(logits, "null output");
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t st = pick_stream(e, stream);
-  HIP_TRY(hipMemcpyAsync(logits, e->d_rng_out, (size_t)e->n_ranges * e->qa_labels * sizeof(float),
+  HIP_TRY(hipMemcpyAsync(logits, e->d_rng_out.p, (size_t)e->n_ranges * e->qa_labels * sizeof(float),
                          hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return VRAG_OK;
 }
 
 int vrag_encoder_run_pool(vrag_encoder* e, int32_t normalize, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
   ARG_CHECK(e->n_ranges > 0, "no ranges loaded (vrag_encoder_load_ranges)");
   ARG_CHECK(e->ran, "encoder has not run on this batch");
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t st = pick_stream(e, stream);
   ProfScope ps(e, VRAG_PROF_HEAD, st);
-  HIP_TRY(launch_range_pool(e->h, e->final_norm, e->cfg.norm_eps, e->cfg.hidden_size, e->d_rng_start, e->d_rng_end,
-                            e->n_ranges, normalize ? 1 : 2, nullptr, nullptr, 0, e->d_rng_out, st));
+  HIP_TRY(launch_range_pool(e->h.p, e->final_norm.p, e->cfg.norm_eps, e->cfg.hidden_size, e->d_rng_start.p, e->d_rng_end.p,
+                            e->n_ranges, normalize ? 1 : 2, nullptr, nullptr, 0, e->d_rng_out.p, st));
   return VRAG_OK;
 }
 
 int vrag_encoder_read_pool(vrag_encoder* e, float* out, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
-  ARG_CHECK(out, "null output");
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
+  ARG_CHECK(out, "null output");
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t st = pick_stream(e, stream);
-  HIP_TRY(hipMemcpyAsync(out, e->d_rng_out, (size_t)e->n_ranges * e->cfg.hidden_size * sizeof(float),
+  HIP_TRY(hipMemcpyAsync(out, e->d_rng_out.p, (size_t)e->n_ranges * e->cfg.hidden_size * sizeof(float),
                          hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return VRAG_OK;
 }
 
 int vrag_encoder_run_token_head(vrag_encoder* e, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
   ARG_CHECK(e->tk_labels > 0, "token head not set (vrag_encoder_set_token_head)");
   ARG_CHECK(e->arch == 0, "the token-classification head is defined for the ModernBERT encoder only");
   ARG_CHECK(e->ran, "encoder has not run on this batch");
@@ -1969,10 +1916,10 @@ int vrag_encoder_run_token_head(vrag_encoder* e, void* stream) {
   // against north_star's 1e-3): the head runs with split operands -- x = x_hi + x_lo, W = W_hi + W_lo in the operand
   // type, three MFMA GEMMs accumulated in fp32 (hi.hi + lo.hi + hi.lo; lo.lo is below fp32 resolution) -- which costs
   // 3 x 2.T.H^2 FLOP, under 2 % of the encoder (tests/probes/precision_probe.py: 6.3e-3 -> 8.8e-4 on bf16 encoders).
-  bf16_t* x_lo = e->o;   // the attention output buffer is free once the layers have run (row stride H for arch 0)
-  HIP_TRY(launch_layernorm(e->h, e->final_norm, e->cfg.norm_eps, H, e->rows, e->a, nullptr, st, nullptr, nullptr, e->op_dtype, x_lo));
-  HIP_TRY(hipMemsetAsync(e->f32tmp, 0, (size_t)e->rows * H * sizeof(float), st));
-  const bf16_t* parts[3][2] = {{e->a, e->tk_dense}, {x_lo, e->tk_dense}, {e->a, e->tk_dense_lo}};
+  bf16_t* x_lo = e->o.p;   // the attention output buffer is free once the layers have run (row stride H for arch 0)
+  HIP_TRY(launch_layernorm(e->h.p, e->final_norm.p, e->cfg.norm_eps, H, e->rows, e->a.p, nullptr, st, nullptr, nullptr, e->op_dtype, x_lo));
+  HIP_TRY(hipMemsetAsync(e->f32tmp.p, 0, (size_t)e->rows * H * sizeof(float), st));
+  const bf16_t* parts[3][2] = {{e->a.p, e->tk_dense.p}, {x_lo, e->tk_dense.p}, {e->a.p, e->tk_dense_lo.p}};
   for (auto& pr : parts) {
     GemmParams g{};
     g.op_dtype = e->op_dtype;
@@ -1981,58 +1928,58 @@ int vrag_encoder_run_token_head(vrag_encoder* e, void* stream) {
     g.M = e->rows;
     g.N = H;
     g.K = H;
-    g.out_f32 = e->f32tmp;
+    g.out_f32 = e->f32tmp.p;
     HIP_TRY(launch_gemm(EPI_RESIDUAL, g, st));
   }
-  HIP_TRY(launch_ln_classifier(e->f32tmp, e->tk_norm, e->cfg.norm_eps, H, e->rows, e->tk_w, e->tk_b, e->tk_labels,
-                               e->d_tok_logits, st, nullptr, /*gelu_first=*/1));
+  HIP_TRY(launch_ln_classifier(e->f32tmp.p, e->tk_norm.p, e->cfg.norm_eps, H, e->rows, e->tk_w.p, e->tk_b.p, e->tk_labels,
+                               e->d_tok_logits.p, st, nullptr, /*gelu_first=*/1));
   return VRAG_OK;
 }
 
 int vrag_encoder_read_token_logits(vrag_encoder* e, float* logits, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
-  ARG_CHECK(logits, "null output");
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
+  ARG_CHECK(logits, "null output");
   ARG_CHECK(e->tk_labels > 0, "token head not set");
   HIP_TRY(hipSetDevice(e->cfg.device));
-  return read_rows(e, e->d_tok_logits, e->tk_labels, logits, pick_stream(e, stream));
+  return read_rows(e, e->d_tok_logits.p, e->tk_labels, logits, pick_stream(e, stream));
 }
 
 int vrag_encoder_run_splade(vrag_encoder* e, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  ARG_CHECK(e->mlm_dec != nullptr || e->mlm_dec3 != nullptr, "mlm head not set (vrag_encoder_set_mlm_head)");
+  TRY(check_ready(e));
+  ARG_CHECK(e->mlm_dec.p != nullptr || e->mlm_dec3.p != nullptr, "mlm head not set (vrag_encoder_set_mlm_head)");
   ARG_CHECK(e->ran, "encoder has not run on this batch");
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t st = pick_stream(e, stream);
   const int H = e->cfg.hidden_size;
   ProfScope ps(e, VRAG_PROF_HEAD, st);
-  const bool split = e->mlm_dec3 != nullptr;
+  const bool split = e->mlm_dec3.p != nullptr;
   // Split operands (default): every SPLADE weight is a max over tokens of log1p(relu(logit)) -- nothing averages the
   // operand rounding of the two head GEMMs away (1e-2 on a weight with plain bf16 operands, and these rows feed a sparse
   // index whose top-k is held to bit-exactness).  x = xhi + xlo and W = Whi + Wlo in the operand type; the dense layer
   // runs as three accumulating GEMMs like the token head's, the decoder as ONE GEMM over K = 3H on the operand images
   // [xhi | xlo | xhi] x [Whi | Whi | Wlo] with the SPLADE epilogue on the sum (lo.lo is below fp32 resolution).
-  bf16_t* x_lo = split ? e->o : nullptr;   // the attention output buffer is free once the layers have run
+  bf16_t* x_lo = split ? e->o.p : nullptr;   // the attention output buffer is free once the layers have run
   if (e->arch == 1) {  // post-LN stream: no final LayerNorm, just the operand copy
-    launch_cvt_rows(e->op_dtype, dim3(e->rows), st, e->h, e->a, e->rows, e->rows, H, 0, (const float*)nullptr, (float*)nullptr, x_lo);
+    launch_cvt_rows(e->op_dtype, dim3(e->rows), st, e->h.p, e->a.p, e->rows, e->rows, H, 0, (const float*)nullptr, (float*)nullptr, x_lo);
     HIP_TRY(hipGetLastError());
   } else {
-    HIP_TRY(launch_layernorm(e->h, e->final_norm, e->cfg.norm_eps, H, e->rows, e->a, nullptr, st, nullptr, nullptr, e->op_dtype, x_lo));
+    HIP_TRY(launch_layernorm(e->h.p, e->final_norm.p, e->cfg.norm_eps, H, e->rows, e->a.p, nullptr, st, nullptr, nullptr, e->op_dtype, x_lo));
   }
-  HIP_TRY(hipMemsetAsync(e->d_splade, 0, (size_t)e->n_seqs * e->vpad * sizeof(unsigned), st));
+  HIP_TRY(hipMemsetAsync(e->d_splade.p, 0, (size_t)e->n_seqs * e->vpad * sizeof(unsigned), st));
   GemmParams d{};
   d.op_dtype = e->op_dtype;
   d.M = e->rows;
   d.N = e->vpad;
-  d.bias = e->mlm_bias;
-  d.tok_seq = e->d_tokseq;
-  d.splade_rows = e->d_splade;
+  d.bias = e->mlm_bias.p;
+  d.tok_seq = e->d_tokseq.p;
+  d.splade_rows = e->d_splade.p;
   if (split) {
-    HIP_TRY(hipMemsetAsync(e->f32tmp, 0, (size_t)e->rows * H * sizeof(float), st));
-    const bf16_t* parts[3][2] = {{e->a, e->mlm_dense}, {x_lo, e->mlm_dense}, {e->a, e->mlm_dense_lo}};
+    HIP_TRY(hipMemsetAsync(e->f32tmp.p, 0, (size_t)e->rows * H * sizeof(float), st));
+    const bf16_t* parts[3][2] = {{e->a.p, e->mlm_dense.p}, {x_lo, e->mlm_dense.p}, {e->a.p, e->mlm_dense_lo.p}};
     for (int i = 0; i < 3; ++i) {
       GemmParams g{};
       g.op_dtype = e->op_dtype;
@@ -2041,30 +1988,30 @@ int vrag_encoder_run_splade(vrag_encoder* e, void* stream) {
       g.M = e->rows;
       g.N = H;
       g.K = H;
-      g.out_f32 = e->f32tmp;
-      g.bias = i == 0 ? e->mlm_dense_b : nullptr;   // BERT-family heads: the bias rides in with the first partial product
+      g.out_f32 = e->f32tmp.p;
+      g.bias = i == 0 ? e->mlm_dense_b.p : nullptr;   // BERT-family heads: the bias rides in with the first partial product
       HIP_TRY(launch_gemm(EPI_RESIDUAL, g, st));
     }
-    HIP_TRY(launch_layernorm(e->f32tmp, e->mlm_norm, e->cfg.norm_eps, H, e->rows, e->splade_a3, nullptr, st, e->mlm_norm_b, nullptr,
+    HIP_TRY(launch_layernorm(e->f32tmp.p, e->mlm_norm.p, e->cfg.norm_eps, H, e->rows, e->splade_a3.p, nullptr, st, e->mlm_norm_b.p, nullptr,
                              e->op_dtype, nullptr, /*gelu_first=*/1, /*split3=*/1));
-    d.A = e->splade_a3;
-    d.W = e->mlm_dec3;
+    d.A = e->splade_a3.p;
+    d.W = e->mlm_dec3.p;
     d.K = 3 * H;
   } else {
     GemmParams g{};
     g.op_dtype = e->op_dtype;
-    g.A = e->a;
-    g.W = e->mlm_dense;
+    g.A = e->a.p;
+    g.W = e->mlm_dense.p;
     g.M = e->rows;
     g.N = H;
     g.K = H;
-    g.out_f32 = e->f32tmp;
-    g.bias = e->mlm_dense_b;
+    g.out_f32 = e->f32tmp.p;
+    g.bias = e->mlm_dense_b.p;
     HIP_TRY(launch_gemm(EPI_F32_GELU, g, st));
-    HIP_TRY(launch_layernorm(e->f32tmp, e->mlm_norm, e->cfg.norm_eps, H, e->rows, e->a, nullptr, st, e->mlm_norm_b, nullptr,
+    HIP_TRY(launch_layernorm(e->f32tmp.p, e->mlm_norm.p, e->cfg.norm_eps, H, e->rows, e->a.p, nullptr, st, e->mlm_norm_b.p, nullptr,
                              e->op_dtype));
-    d.A = e->a;
-    d.W = e->mlm_dec;
+    d.A = e->a.p;
+    d.W = e->mlm_dec.p;
     d.K = H;
   }
   HIP_TRY(launch_gemm(EPI_SPLADE, d, st));
@@ -2072,15 +2019,15 @@ int vrag_encoder_run_splade(vrag_encoder* e, void* stream) {
 }
 
 int vrag_encoder_read_splade(vrag_encoder* e, float* rows, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
-  ARG_CHECK(rows, "null output");
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  ARG_CHECK(e->mlm_dec != nullptr || e->mlm_dec3 != nullptr, "mlm head not set");
+  TRY(check_ready(e));
+  ARG_CHECK(rows, "null output");
+  ARG_CHECK(e->mlm_dec.p != nullptr || e->mlm_dec3.p != nullptr, "mlm head not set");
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t st = pick_stream(e, stream);
   const int V = e->cfg.vocab_size;
-  HIP_TRY(hipMemcpy2DAsync(rows, (size_t)V * sizeof(float), e->d_splade, (size_t)e->vpad * sizeof(float),
+  HIP_TRY(hipMemcpy2DAsync(rows, (size_t)V * sizeof(float), e->d_splade.p, (size_t)e->vpad * sizeof(float),
                            (size_t)V * sizeof(float), e->n_seqs, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return VRAG_OK;
@@ -2088,24 +2035,25 @@ int vrag_encoder_read_splade(vrag_encoder* e, float* rows, void* stream) {
 
 int vrag_encoder_read_splade_sparse(vrag_encoder* e, float threshold, int32_t cap_per_seq, int32_t* counts,
                                     int32_t* indices, float* values, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
-  ARG_CHECK(counts && indices && values && cap_per_seq > 0 && threshold >= 0.f, "bad arguments");
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
-  ARG_CHECK(e->mlm_dec != nullptr || e->mlm_dec3 != nullptr, "mlm head not set");
+  TRY(check_ready(e));
+  ARG_CHECK(counts && indices && values && cap_per_seq > 0 && threshold >= 0.f, "bad arguments");
+  ARG_CHECK(e->mlm_dec.p != nullptr || e->mlm_dec3.p != nullptr, "mlm head not set");
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t st = pick_stream(e, stream);
-  if (cap_per_seq > e->sp_cap) {   // (re)allocate; the old buffers stay owned by the handle until destroy
-    if ((rc = dev_alloc(e, &e->d_sp_idx, (size_t)e->cfg.max_seqs * cap_per_seq, false))) return rc;
-    if ((rc = dev_alloc(e, &e->d_sp_val, (size_t)e->cfg.max_seqs * cap_per_seq, false))) return rc;
-    if (!e->d_sp_cnt && (rc = dev_alloc(e, &e->d_sp_cnt, e->cfg.max_seqs))) return rc;
+  if (cap_per_seq > e->sp_cap) {   // (re)allocate; the outgrown buffers are freed
+    e->sp_cap = 0;
+    TRY(dev_alloc(e->d_sp_idx, (size_t)e->cfg.max_seqs * cap_per_seq, false));
+    TRY(dev_alloc(e->d_sp_val, (size_t)e->cfg.max_seqs * cap_per_seq, false));
+    if (!e->d_sp_cnt.p) TRY(dev_alloc(e->d_sp_cnt, e->cfg.max_seqs));
     e->sp_cap = cap_per_seq;
   }
   const int n = e->n_seqs, cap = cap_per_seq;
-  hipLaunchKernelGGL(splade_compact_kernel, dim3(n), dim3(256), 0, st, reinterpret_cast<const float*>(e->d_splade),
-                     e->cfg.vocab_size, e->vpad, threshold, cap, e->d_sp_cnt, e->d_sp_idx, e->d_sp_val);
+  hipLaunchKernelGGL(splade_compact_kernel, dim3(n), dim3(256), 0, st, reinterpret_cast<const float*>(e->d_splade.p),
+                     e->cfg.vocab_size, e->vpad, threshold, cap, e->d_sp_cnt.p, e->d_sp_idx.p, e->d_sp_val.p);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(counts, e->d_sp_cnt, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(counts, e->d_sp_cnt.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   int worst = 0;
   for (int i = 0; i < n; ++i) worst = std::max(worst, counts[i]);
@@ -2115,27 +2063,27 @@ int vrag_encoder_read_splade_sparse(vrag_encoder* e, float threshold, int32_t ca
   }
   // only the used prefix of every row travels: rows are cap apart on the device and in the caller's buffers
   const size_t width = (size_t)std::max(worst, 1);
-  HIP_TRY(hipMemcpy2DAsync(indices, (size_t)cap * sizeof(int), e->d_sp_idx, (size_t)cap * sizeof(int), width * sizeof(int), n,
+  HIP_TRY(hipMemcpy2DAsync(indices, (size_t)cap * sizeof(int), e->d_sp_idx.p, (size_t)cap * sizeof(int), width * sizeof(int), n,
                            hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpy2DAsync(values, (size_t)cap * sizeof(float), e->d_sp_val, (size_t)cap * sizeof(float),
+  HIP_TRY(hipMemcpy2DAsync(values, (size_t)cap * sizeof(float), e->d_sp_val.p, (size_t)cap * sizeof(float),
                            width * sizeof(float), n, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return VRAG_OK;
 }
 
 int vrag_encoder_read_hidden(vrag_encoder* e, int32_t apply_final_norm, float* out, void* stream) {
-  int rc = check_ready(e);
-  if (rc) return rc;
-  ARG_CHECK(out, "null output");
+  ARG_CHECK(e, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
+  ARG_CHECK(out, "null output");
   ARG_CHECK(e->ran, "encoder has not run on this batch");
   HIP_TRY(hipSetDevice(e->cfg.device));
   hipStream_t st = pick_stream(e, stream);
   const int H = e->cfg.hidden_size;
-  const float* src = e->h;
-  if (apply_final_norm && e->final_norm) {
-    HIP_TRY(launch_layernorm(e->h, e->final_norm, e->cfg.norm_eps, H, e->rows, nullptr, e->f32tmp, st));
-    src = e->f32tmp;
+  const float* src = e->h.p;
+  if (apply_final_norm && e->final_norm.p) {
+    HIP_TRY(launch_layernorm(e->h.p, e->final_norm.p, e->cfg.norm_eps, H, e->rows, nullptr, e->f32tmp.p, st));
+    src = e->f32tmp.p;
   }
   return read_rows(e, src, H, out, st);
 }
@@ -2145,11 +2093,10 @@ int vrag_encoder_extract_qa(vrag_encoder* e, const int32_t* ids, const int32_t* 
                             int32_t n_ranges, float* logits) {
   ARG_CHECK(e != nullptr, "null encoder handle");
   std::lock_guard<std::recursive_mutex> lk(e->mu);  // the whole sequence is one critical section
-  int rc;
-  if ((rc = vrag_encoder_load_batch(e, ids, seq_lens, n_seqs, nullptr))) return rc;
-  if ((rc = vrag_encoder_load_ranges(e, rng_seq, rng_start, rng_end, n_ranges, nullptr))) return rc;
-  if ((rc = vrag_encoder_run(e, nullptr))) return rc;
-  if ((rc = vrag_encoder_run_qa_head(e, nullptr))) return rc;
+  TRY(vrag_encoder_load_batch(e, ids, seq_lens, n_seqs, nullptr));
+  TRY(vrag_encoder_load_ranges(e, rng_seq, rng_start, rng_end, n_ranges, nullptr));
+  TRY(vrag_encoder_run(e, nullptr));
+  TRY(vrag_encoder_run_qa_head(e, nullptr));
   return vrag_encoder_read_qa_logits(e, logits, nullptr);
 }
 
@@ -2162,32 +2109,29 @@ int vrag_encoder_f16_saturated(vrag_encoder* e, int32_t reset, int32_t* saturate
   HIP_TRY(hipDeviceSynchronize());
   // One launch + one stream wait instead of five synchronous symbol copies (each ~12 us: 70 us of a single question's 1.35 ms
   // embedding call sat here, tools/probes/embed_latency_probe.py).  The flags are per device, not per engine, as before.
-  if (!e->sat_host) {
-    void* h = nullptr;
-    if (hipHostMalloc(&h, sizeof(unsigned), hipHostMallocMapped) == hipSuccess) {
+  if (!e->sat_host.p) {
+    PinnedArray<unsigned> word;
+    if (word.grow(1, hipHostMallocMapped) == hipSuccess) {
       void* d = nullptr;
-      if (hipHostGetDevicePointer(&d, h, 0) == hipSuccess) {
-        e->host_allocs.push_back(h);
-        e->sat_host = reinterpret_cast<unsigned*>(h);
+      if (hipHostGetDevicePointer(&d, word.p, 0) == hipSuccess) {
+        e->sat_host = std::move(word);
         e->sat_host_dev = reinterpret_cast<unsigned*>(d);
         e->sat_addr[0] = f16_sat_flag_address();   // conversions in this file (weight packing)
         e->sat_addr[1] = gemm_f16_flag_address();
         e->sat_addr[2] = attention_f16_flag_address();
         e->sat_addr[3] = qkv_attn_f16_flag_address();
         e->sat_addr[4] = norm_heads_f16_flag_address();
-      } else {
-        (void)hipHostFree(h);
       }
     }
     (void)hipGetLastError();
   }
-  if (e->sat_host && e->sat_addr[0] && e->sat_addr[1] && e->sat_addr[2] && e->sat_addr[3] && e->sat_addr[4]) {
+  if (e->sat_host.p && e->sat_addr[0] && e->sat_addr[1] && e->sat_addr[2] && e->sat_addr[3] && e->sat_addr[4]) {
     SatFlags f;
     for (int i = 0; i < 5; ++i) f.a[i] = e->sat_addr[i];
     hipLaunchKernelGGL(f16_sat_gather_kernel, dim3(1), dim3(1), 0, e->own_stream, f, reset != 0 ? 1 : 0, e->sat_host_dev);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->own_stream));
-    *saturated = *reinterpret_cast<volatile unsigned*>(e->sat_host) ? 1 : 0;
+    *saturated = *reinterpret_cast<volatile unsigned*>(e->sat_host.p) ? 1 : 0;
     return VRAG_OK;
   }
   unsigned any = f16_sat_take(reset != 0);                 // (no mapped word or no symbol address: the per-file copies)

@@ -32,25 +32,18 @@ int vrag_debug_gemm_ms(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t ite
   }
   HIP_TRY(hipSetDevice(device));
   const size_t Mp = (size_t)align_up(M, kRowPad);
-  void *A = nullptr, *W = nullptr, *outf = nullptr, *outb = nullptr, *q = nullptr, *kk = nullptr, *vt = nullptr;
-  float *cs = nullptr, *sn = nullptr;
-  int* pos = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {A, W, outf, outb, q, kk, vt, (void*)cs, (void*)sn, (void*)pos})
-      if (p) (void)hipFree(p);
-  };
-  hipError_t e = hipMalloc(&A, Mp * K * 2);
-  if (e == hipSuccess) e = hipMalloc(&W, (size_t)N * K * 2);
-  if (e == hipSuccess) e = hipMalloc(&outf, Mp * N * 4);
-  if (e == hipSuccess) e = hipMalloc(&outb, Mp * N * 2);
-  if (e == hipSuccess) e = hipMalloc(&q, Mp * N * 2);
-  if (e == hipSuccess) e = hipMalloc(&kk, Mp * N * 2);
-  if (e == hipSuccess) e = hipMalloc(&vt, Mp * N * 2);
-  if (e == hipSuccess) e = hipMalloc((void**)&cs, 512 * 32 * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&sn, 512 * 32 * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&pos, Mp * 4);
+  DevBuf A, W, outf, outb, q, kk, vt, cs, sn, pos;
+  hipError_t e = A.alloc(Mp * K * 2);
+  if (e == hipSuccess) e = W.alloc((size_t)N * K * 2);
+  if (e == hipSuccess) e = outf.alloc(Mp * N * 4);
+  if (e == hipSuccess) e = outb.alloc(Mp * N * 2);
+  if (e == hipSuccess) e = q.alloc(Mp * N * 2);
+  if (e == hipSuccess) e = kk.alloc(Mp * N * 2);
+  if (e == hipSuccess) e = vt.alloc(Mp * N * 2);
+  if (e == hipSuccess) e = cs.alloc(512 * 32 * 4);
+  if (e == hipSuccess) e = sn.alloc(512 * 32 * 4);
+  if (e == hipSuccess) e = pos.alloc(Mp * 4);
   if (e != hipSuccess) {
-    cleanup();
     set_error("debug gemm allocation failed: %s", hipGetErrorString(e));
     return VRAG_ERR_HIP;
   }
@@ -64,42 +57,42 @@ int vrag_debug_gemm_ms(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t ite
       v = (unsigned short)(s | ex | m);
     }
     if (getenv("VRAG_DEBUG_GEMM_ZERO")) std::fill(h.begin(), h.end(), (unsigned short)0);   // probe: operand-data dependence of the clock
-    (void)hipMemcpy(A, h.data(), Mp * K * 2, hipMemcpyHostToDevice);
-    (void)hipMemcpy(W, h.data(), (size_t)N * K * 2, hipMemcpyHostToDevice);
+    (void)hipMemcpy(A.p, h.data(), Mp * K * 2, hipMemcpyHostToDevice);
+    (void)hipMemcpy(W.p, h.data(), (size_t)N * K * 2, hipMemcpyHostToDevice);
   }
-  (void)hipMemset(outf, 0, Mp * N * 4);
-  (void)hipMemset(pos, 0, Mp * 4);
-  (void)hipMemset(cs, 0, 512 * 32 * 4);
-  (void)hipMemset(sn, 0, 512 * 32 * 4);
+  (void)hipMemset(outf.p, 0, Mp * N * 4);
+  (void)hipMemset(pos.p, 0, Mp * 4);
+  (void)hipMemset(cs.p, 0, 512 * 32 * 4);
+  (void)hipMemset(sn.p, 0, 512 * 32 * 4);
   GemmParams g{};
   g.op_dtype = getenv("VRAG_DEBUG_GEMM_F16") ? kOpF16 : kOpBf16;   // same bit patterns read as fp16: finite values in [2^-15, 2^-7)
-  g.A = (const bf16_t*)A;
-  g.W = (const bf16_t*)W;
+  g.A = A.as<bf16_t>();
+  g.W = W.as<bf16_t>();
   g.M = M;
   g.N = N;
   g.K = K;
-  g.out_f32 = (float*)outf;
-  g.out_bf16 = (bf16_t*)outb;
-  g.q = (bf16_t*)q;
-  g.k = (bf16_t*)kk;
-  g.vt = (bf16_t*)vt;
+  g.out_f32 = outf.as<float>();
+  g.out_bf16 = outb.as<bf16_t>();
+  g.q = q.as<bf16_t>();
+  g.k = kk.as<bf16_t>();
+  g.vt = vt.as<bf16_t>();
   g.vt_ld = (int)Mp;
-  g.rope_cos = cs;
-  g.rope_sin = sn;
-  g.pos = pos;
+  g.rope_cos = cs.as<float>();
+  g.rope_sin = sn.as<float>();
+  g.pos = pos.as<int>();
   g.hidden = N / 3;
   g.q_scale = 0.125f;
   if (epi == EPI_RESIDUAL && !getenv("VRAG_DEBUG_GEMM_PLAIN_RESID")) {   // as the encoder launches it with the LayerNorm fold
-    g.resid_bf16 = (bf16_t*)outb;
-    g.stats_part = (float*)q;                                              // Mp * N/64 * 2 floats <= Mp * N * 2 bytes
+    g.resid_bf16 = outb.as<bf16_t>();
+    g.stats_part = q.as<float>();                                            // Mp * N/64 * 2 floats <= Mp * N * 2 bytes
     g.stats_ld = (int)Mp;
     if (getenv("VRAG_DEBUG_GEMM_SPLIT")) {   // the split residual stream on both sides (layers >= 1 of the encoder schedule)
-      g.lo_in = (const unsigned char*)kk;
-      g.lo_out = (unsigned char*)kk;
-      g.ln_shift = (const float*)pos;        // zeros
-      g.ln_shift_prev = (float*)pos;
-      (void)hipMemset(kk, 0, Mp * N * 2);
-      (void)hipMemset(outb, 0, Mp * N * 2);
+      g.lo_in = kk.as<unsigned char>();
+      g.lo_out = kk.as<unsigned char>();
+      g.ln_shift = pos.as<float>();        // zeros
+      g.ln_shift_prev = pos.as<float>();
+      (void)hipMemset(kk.p, 0, Mp * N * 2);
+      (void)hipMemset(outb.p, 0, Mp * N * 2);
     }
   }
   hipEvent_t a, b;
@@ -115,7 +108,6 @@ int vrag_debug_gemm_ms(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t ite
   (void)hipEventElapsedTime(&ms, a, b);
   (void)hipEventDestroy(a);
   (void)hipEventDestroy(b);
-  cleanup();
   if (le != hipSuccess || se != hipSuccess) {
     set_error("debug gemm failed: %s", hipGetErrorString(le != hipSuccess ? le : se));
     return VRAG_ERR_HIP;
@@ -141,21 +133,15 @@ int vrag_debug_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int3
       bl.push_back(S);
       bq.push_back(q0);
     }
-  void *q = nullptr, *k = nullptr, *vt = nullptr, *o = nullptr;
-  int *d_bs = nullptr, *d_bl = nullptr, *d_bq = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {q, k, vt, o, (void*)d_bs, (void*)d_bl, (void*)d_bq})
-      if (p) (void)hipFree(p);
-  };
-  hipError_t e = hipMalloc(&q, Tp * H * 2);
-  if (e == hipSuccess) e = hipMalloc(&k, Tp * H * 2);
-  if (e == hipSuccess) e = hipMalloc(&vt, Tp * H * 2);
-  if (e == hipSuccess) e = hipMalloc(&o, Tp * H * 2);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_bs, bs.size() * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_bl, bs.size() * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_bq, bs.size() * 4);
+  DevBuf q, k, vt, o, d_bs, d_bl, d_bq;
+  hipError_t e = q.alloc(Tp * H * 2);
+  if (e == hipSuccess) e = k.alloc(Tp * H * 2);
+  if (e == hipSuccess) e = vt.alloc(Tp * H * 2);
+  if (e == hipSuccess) e = o.alloc(Tp * H * 2);
+  if (e == hipSuccess) e = d_bs.alloc(bs.size() * 4);
+  if (e == hipSuccess) e = d_bl.alloc(bs.size() * 4);
+  if (e == hipSuccess) e = d_bq.alloc(bs.size() * 4);
   if (e != hipSuccess) {
-    cleanup();
     set_error("debug attention allocation failed: %s", hipGetErrorString(e));
     return VRAG_ERR_HIP;
   }
@@ -166,21 +152,21 @@ int vrag_debug_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int3
       x = x * 1664525u + 1013904223u;
       v = (unsigned short)(((x >> 31) << 15) | (0x3e80u + (((x >> 20) & 1) << 7)) | ((x >> 9) & 0x7f));
     }
-    (void)hipMemcpy(q, h.data(), Tp * H * 2, hipMemcpyHostToDevice);
-    (void)hipMemcpy(k, h.data(), Tp * H * 2, hipMemcpyHostToDevice);
-    (void)hipMemcpy(vt, h.data(), Tp * H * 2, hipMemcpyHostToDevice);
-    (void)hipMemcpy(d_bs, bs.data(), bs.size() * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(d_bl, bl.data(), bs.size() * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(d_bq, bq.data(), bs.size() * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(q.p, h.data(), Tp * H * 2, hipMemcpyHostToDevice);
+    (void)hipMemcpy(k.p, h.data(), Tp * H * 2, hipMemcpyHostToDevice);
+    (void)hipMemcpy(vt.p, h.data(), Tp * H * 2, hipMemcpyHostToDevice);
+    (void)hipMemcpy(d_bs.p, bs.data(), bs.size() * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(d_bl.p, bl.data(), bs.size() * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(d_bq.p, bq.data(), bs.size() * 4, hipMemcpyHostToDevice);
   }
   AttnParams ap{};
-  ap.q = (const bf16_t*)q;
-  ap.k = (const bf16_t*)k;
-  ap.vt = (const bf16_t*)vt;
-  ap.o = (bf16_t*)o;
-  ap.blk_seq_start = d_bs;
-  ap.blk_seq_len = d_bl;
-  ap.blk_q0 = d_bq;
+  ap.q = q.as<bf16_t>();
+  ap.k = k.as<bf16_t>();
+  ap.vt = vt.as<bf16_t>();
+  ap.o = o.as<bf16_t>();
+  ap.blk_seq_start = d_bs.as<int>();
+  ap.blk_seq_len = d_bl.as<int>();
+  ap.blk_q0 = d_bq.as<int>();
   ap.n_blocks = (int)bs.size();
   ap.H = H;
   ap.nh = H / 64;
@@ -200,7 +186,6 @@ int vrag_debug_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int3
   (void)hipEventElapsedTime(&ms, a, b);
   (void)hipEventDestroy(a);
   (void)hipEventDestroy(b);
-  cleanup();
   if (le != hipSuccess || se != hipSuccess) {
     set_error("debug attention failed: %s", hipGetErrorString(le != hipSuccess ? le : se));
     return VRAG_ERR_HIP;
@@ -221,24 +206,17 @@ int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, 
   const int nh = H / 64;
   std::vector<int> row(n_seqs), len(n_seqs, S);
   for (int s = 0; s < n_seqs; ++s) row[s] = s * S;
-  void *x = nullptr, *w = nullptr, *o = nullptr;
-  float *mu = nullptr, *rstd = nullptr, *lns = nullptr, *cs = nullptr;
-  int *d_row = nullptr, *d_len = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {x, w, o, (void*)mu, (void*)rstd, (void*)lns, (void*)cs, (void*)d_row, (void*)d_len})
-      if (p) (void)hipFree(p);
-  };
-  hipError_t e = hipMalloc(&x, Tp * H * 2);
-  if (e == hipSuccess) e = hipMalloc(&w, (size_t)3 * H * H * 2);
-  if (e == hipSuccess) e = hipMalloc(&o, Tp * H * 2);
-  if (e == hipSuccess) e = hipMalloc((void**)&mu, Tp * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&rstd, Tp * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&lns, ((size_t)3 * H + 64) * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&cs, (size_t)kFusedMaxSeq * 32 * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_row, (size_t)n_seqs * 8 * sizeof(int4));   // the groups' wave descriptors
-  if (e == hipSuccess) e = hipMalloc((void**)&d_len, n_seqs * 4);
+  DevBuf x, w, o, mu, rstd, lns, cs, d_row, d_len;
+  hipError_t e = x.alloc(Tp * H * 2);
+  if (e == hipSuccess) e = w.alloc((size_t)3 * H * H * 2);
+  if (e == hipSuccess) e = o.alloc(Tp * H * 2);
+  if (e == hipSuccess) e = mu.alloc(Tp * 4);
+  if (e == hipSuccess) e = rstd.alloc(Tp * 4);
+  if (e == hipSuccess) e = lns.alloc(((size_t)3 * H + 64) * 4);
+  if (e == hipSuccess) e = cs.alloc((size_t)kFusedMaxSeq * 32 * 4);
+  if (e == hipSuccess) e = d_row.alloc((size_t)n_seqs * 8 * sizeof(int4));   // the groups' wave descriptors
+  if (e == hipSuccess) e = d_len.alloc(n_seqs * 4);
   if (e != hipSuccess) {
-    cleanup();
     set_error("debug allocation failed: %s", hipGetErrorString(e));
     return VRAG_ERR_HIP;
   }
@@ -249,29 +227,29 @@ int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, 
       xs = xs * 1664525u + 1013904223u;
       v = (unsigned short)(((xs >> 31) << 15) | (0x3e80u + (((xs >> 20) & 1) << 7)) | ((xs >> 9) & 0x7f));
     }
-    (void)hipMemcpy(x, h.data(), Tp * H * 2, hipMemcpyHostToDevice);
-    (void)hipMemcpy(w, h.data(), (size_t)3 * H * H * 2, hipMemcpyHostToDevice);
+    (void)hipMemcpy(x.p, h.data(), Tp * H * 2, hipMemcpyHostToDevice);
+    (void)hipMemcpy(w.p, h.data(), (size_t)3 * H * H * 2, hipMemcpyHostToDevice);
     std::vector<float> f(std::max(Tp, (size_t)kFusedMaxSeq * 32), 0.05f);
-    (void)hipMemcpy(mu, f.data(), Tp * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(rstd, f.data(), Tp * 4, hipMemcpyHostToDevice);
-    (void)hipMemcpy(lns, f.data(), (size_t)3 * H * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(mu.p, f.data(), Tp * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(rstd.p, f.data(), Tp * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(lns.p, f.data(), (size_t)3 * H * 4, hipMemcpyHostToDevice);
     std::fill(f.begin(), f.end(), 0.7071f);
-    (void)hipMemcpy(cs, f.data(), (size_t)kFusedMaxSeq * 32 * 4, hipMemcpyHostToDevice);
+    (void)hipMemcpy(cs.p, f.data(), (size_t)kFusedMaxSeq * 32 * 4, hipMemcpyHostToDevice);
   }
   std::vector<int4> groups((size_t)n_seqs * 8);
   const int n_groups = fused_pack_groups(row.data(), len.data(), 0, n_seqs, groups.data());
-  (void)hipMemcpy(d_row, groups.data(), (size_t)n_groups * 8 * sizeof(int4), hipMemcpyHostToDevice);
+  (void)hipMemcpy(d_row.p, groups.data(), (size_t)n_groups * 8 * sizeof(int4), hipMemcpyHostToDevice);
   QkvAttnParams f{};
-  f.x = (const bf16_t*)x;
-  f.w = (const bf16_t*)w;
-  f.ln_mu = mu;
-  f.ln_rstd = rstd;
-  f.ln_s = lns;
-  f.rope_cos = cs;
-  f.rope_sin = cs;
+  f.x = x.as<bf16_t>();
+  f.w = w.as<bf16_t>();
+  f.ln_mu = mu.as<float>();
+  f.ln_rstd = rstd.as<float>();
+  f.ln_s = lns.as<float>();
+  f.rope_cos = cs.as<float>();
+  f.rope_sin = cs.as<float>();
   f.rope_rows = kFusedMaxSeq;
-  f.o = (bf16_t*)o;
-  f.groups = reinterpret_cast<const int4*>(d_row);
+  f.o = o.as<bf16_t>();
+  f.groups = d_row.as<int4>();
   f.n_groups = n_groups;
   f.H = H;
   f.nh = nh;
@@ -293,7 +271,6 @@ int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, 
   (void)hipEventElapsedTime(&ms, a, b);
   (void)hipEventDestroy(a);
   (void)hipEventDestroy(b);
-  cleanup();
   if (le != hipSuccess || se != hipSuccess) {
     set_error("debug fused attention failed: %s", hipGetErrorString(le != hipSuccess ? le : se));
     return VRAG_ERR_HIP;
@@ -319,38 +296,33 @@ int vrag_debug_attn_run(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int
       bl.push_back(S);
       bq.push_back(q0);
     }
-  void *dq = nullptr, *dk = nullptr, *dv = nullptr, *dout = nullptr;
-  int *d_bs = nullptr, *d_bl = nullptr, *d_bq = nullptr;
-  auto cleanup = [&]() {
-    for (void* p : {dq, dk, dv, dout, (void*)d_bs, (void*)d_bl, (void*)d_bq})
-      if (p) (void)hipFree(p);
-  };
-  hipError_t e = hipMalloc(&dq, Tp * H * 2);
-  if (e == hipSuccess) e = hipMalloc(&dk, Tp * H * 2);
-  if (e == hipSuccess) e = hipMalloc(&dv, Tp * H * 2);
-  if (e == hipSuccess) e = hipMalloc(&dout, Tp * H * 2);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_bs, bs.size() * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_bl, bs.size() * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_bq, bs.size() * 4);
-  if (e == hipSuccess) e = hipMemset(dq, 0, Tp * H * 2);
-  if (e == hipSuccess) e = hipMemset(dk, 0, Tp * H * 2);
-  if (e == hipSuccess) e = hipMemset(dout, 0, Tp * H * 2);
-  if (e == hipSuccess) e = hipMemcpy(dq, q, T * H * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dk, k, T * H * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dv, vt, (size_t)H * Tp * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_bs, bs.data(), bs.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_bl, bl.data(), bs.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_bq, bq.data(), bs.size() * 4, hipMemcpyHostToDevice);
+  DevBuf dq, dk, dv, dout, d_bs, d_bl, d_bq;
+  hipError_t e = dq.alloc(Tp * H * 2);
+  if (e == hipSuccess) e = dk.alloc(Tp * H * 2);
+  if (e == hipSuccess) e = dv.alloc(Tp * H * 2);
+  if (e == hipSuccess) e = dout.alloc(Tp * H * 2);
+  if (e == hipSuccess) e = d_bs.alloc(bs.size() * 4);
+  if (e == hipSuccess) e = d_bl.alloc(bs.size() * 4);
+  if (e == hipSuccess) e = d_bq.alloc(bs.size() * 4);
+  if (e == hipSuccess) e = hipMemset(dq.p, 0, Tp * H * 2);
+  if (e == hipSuccess) e = hipMemset(dk.p, 0, Tp * H * 2);
+  if (e == hipSuccess) e = hipMemset(dout.p, 0, Tp * H * 2);
+  if (e == hipSuccess) e = hipMemcpy(dq.p, q, T * H * 2, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dk.p, k, T * H * 2, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dv.p, vt, (size_t)H * Tp * 2, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_bs.p, bs.data(), bs.size() * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_bl.p, bl.data(), bs.size() * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_bq.p, bq.data(), bs.size() * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) {
     AttnParams ap{};
-    ap.q = (const bf16_t*)dq;
-    ap.k = (const bf16_t*)dk;
-    ap.vt = (const bf16_t*)dv;
-    ap.o = (bf16_t*)dout;
-    ap.blk_seq_start = d_bs;
-    ap.blk_seq_len = d_bl;
-    ap.blk_q0 = d_bq;
+    ap.q = dq.as<bf16_t>();
+    ap.k = dk.as<bf16_t>();
+    ap.vt = dv.as<bf16_t>();
+    ap.o = dout.as<bf16_t>();
+    ap.blk_seq_start = d_bs.as<int>();
+    ap.blk_seq_len = d_bl.as<int>();
+    ap.blk_q0 = d_bq.as<int>();
     ap.n_blocks = (int)bs.size();
     ap.H = H;
     ap.nh = H / 64;
@@ -360,8 +332,7 @@ int vrag_debug_attn_run(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int
     e = launch_attention(ap, local != 0, 0);
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(o, dout, T * H * 2, hipMemcpyDeviceToHost);
-  cleanup();
+  if (e == hipSuccess) e = hipMemcpy(o, dout.p, T * H * 2, hipMemcpyDeviceToHost);
   if (e != hipSuccess) {
     set_error("debug attention run failed: %s", hipGetErrorString(e));
     return VRAG_ERR_HIP;
@@ -423,13 +394,13 @@ int vrag_debug_gemm_run(vrag_debug_gemm_args* a, int32_t device) {
     void* host_out;   // null = input only
     size_t bytes;
     const char* name;
-    char* dev;
+    DevBuf dev;   // bytes + kCanary
   };
   const size_t H = (size_t)std::max(a->hidden, 0), NO = epi == EPI_GEGLU ? (size_t)N / 2 : (size_t)N;
   std::vector<Buf> bufs;
   auto add = [&](const void* h, void* h_out, size_t bytes, const char* name) -> int {
     if (!h) return -1;
-    bufs.push_back(Buf{h, h_out, bytes, name, nullptr});
+    bufs.push_back(Buf{h, h_out, bytes, name, DevBuf()});
     return (int)bufs.size() - 1;
   };
   const int iA = add(a->A, nullptr, R * K * 2, "A");
@@ -459,17 +430,13 @@ int vrag_debug_gemm_run(vrag_debug_gemm_args* a, int32_t device) {
   const int isp = add(a->stats_part, a->stats_part, (size_t)(N / 64) * R * 8, "stats_part");
   const int ilo_out = a->lo_out == a->lo_in ? ilo_in : add(a->lo_out, a->lo_out, R * N, "lo_out");
   const int ispl = add(a->splade_rows, a->splade_rows, (size_t)a->n_seqs * N * 4, "splade_rows");
-  auto cleanup = [&]() {
-    for (Buf& b : bufs)
-      if (b.dev) (void)hipFree(b.dev);
-  };
   hipError_t e = hipSuccess;
   for (Buf& b : bufs) {
-    if (e == hipSuccess) e = hipMalloc((void**)&b.dev, b.bytes + kCanary);
-    if (e == hipSuccess) e = hipMemcpy(b.dev, b.host, b.bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(b.dev + b.bytes, kCanaryByte, kCanary);
+    if (e == hipSuccess) e = b.dev.alloc(b.bytes + kCanary);
+    if (e == hipSuccess) e = hipMemcpy(b.dev.p, b.host, b.bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(b.dev.as<char>() + b.bytes, kCanaryByte, kCanary);
   }
-  auto dev = [&](int i, size_t offset_bytes) -> char* { return i < 0 ? nullptr : bufs[i].dev + offset_bytes; };
+  auto dev = [&](int i, size_t offset_bytes) -> char* { return i < 0 ? nullptr : bufs[i].dev.as<char>() + offset_bytes; };
   GemmParams g{};
   g.op_dtype = a->f16 ? kOpF16 : kOpBf16;
   g.M = M;
@@ -525,12 +492,11 @@ int vrag_debug_gemm_run(vrag_debug_gemm_args* a, int32_t device) {
   const char* clobbered = nullptr;
   for (Buf& b : bufs) {
     if (e != hipSuccess) break;
-    e = hipMemcpy(canary.data(), b.dev + b.bytes, kCanary, hipMemcpyDeviceToHost);
+    e = hipMemcpy(canary.data(), b.dev.as<char>() + b.bytes, kCanary, hipMemcpyDeviceToHost);
     if (e == hipSuccess && !clobbered && std::any_of(canary.begin(), canary.end(), [](unsigned char v) { return v != kCanaryByte; }))
       clobbered = b.name;
-    if (e == hipSuccess && b.host_out) e = hipMemcpy(b.host_out, b.dev, b.bytes, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && b.host_out) e = hipMemcpy(b.host_out, b.dev.p, b.bytes, hipMemcpyDeviceToHost);
   }
-  cleanup();
   if (e != hipSuccess) {
     set_error("debug gemm run failed: %s", hipGetErrorString(e));
     return VRAG_ERR_HIP;

@@ -33,7 +33,7 @@ void set_error(const char* fmt, ...);   // csrc/capi.hip: the message vrag_last_
 
 namespace vrag {
 
-// Device array of T owned by its holder (scratch of an index handle): freed with it.
+// Device array of T owned by its holder (scratch of an index handle, weights and workspace of an encoder): freed with it.
 template <typename T>
 struct DevArray {
   T* p = nullptr;
@@ -41,6 +41,15 @@ struct DevArray {
   DevArray() = default;
   DevArray(const DevArray&) = delete;
   DevArray& operator=(const DevArray&) = delete;
+  DevArray(DevArray&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+  DevArray& operator=(DevArray&& o) noexcept {   // frees what this array held
+    if (this != &o) {
+      if (p) (void)hipFree(p);
+      p = o.p, n = o.n;
+      o.p = nullptr, o.n = 0;
+    }
+    return *this;
+  }
   ~DevArray() {
     if (p) (void)hipFree(p);
   }
@@ -52,6 +61,39 @@ struct DevArray {
     p = nullptr;
     n = 0;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), need * sizeof(T));
+    if (e == hipSuccess) n = need;
+    else p = nullptr;
+    return e;
+  }
+};
+
+// Pinned host array of T owned by its holder (staging buffers of a handle): DevArray's shape over hipHostMalloc / hipHostFree.
+template <typename T>
+struct PinnedArray {
+  T* p = nullptr;
+  size_t n = 0;   // elements allocated
+  PinnedArray() = default;
+  PinnedArray(const PinnedArray&) = delete;
+  PinnedArray& operator=(const PinnedArray&) = delete;
+  PinnedArray(PinnedArray&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr, o.n = 0; }
+  PinnedArray& operator=(PinnedArray&& o) noexcept {   // frees what this array held
+    if (this != &o) {
+      if (p) (void)hipHostFree(p);
+      p = o.p, n = o.n;
+      o.p = nullptr, o.n = 0;
+    }
+    return *this;
+  }
+  ~PinnedArray() {
+    if (p) (void)hipHostFree(p);
+  }
+  // As DevArray::grow, with the hipHostMalloc flags of the new allocation (hipHostMallocMapped: a device-visible word).
+  hipError_t grow(size_t need, unsigned flags = hipHostMallocDefault) {
+    if (need <= n) return hipSuccess;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    n = 0;
+    hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), need * sizeof(T), flags);
     if (e == hipSuccess) n = need;
     else p = nullptr;
     return e;

@@ -112,48 +112,38 @@ extern "C" int vrag_split_sentences(const uint8_t* text, const int64_t* doc_off,
       set_error("vrag_split_sentences: document %d has a negative or > 2 GiB length", d);
       return VRAG_ERR_INVALID;
     }
-  const size_t bytes = (size_t)(doc_off[n_docs] - doc_off[0]);
-  hipError_t e = hipSetDevice(device);
-  unsigned char* d_text = nullptr;
-  long long* d_off = nullptr;
-  int *d_counts = nullptr, *d_starts = nullptr, *d_ends = nullptr;
-  hipStream_t st = nullptr;
-  auto fail = [&](hipError_t err) {
-    set_error("vrag_split_sentences: %s", hipGetErrorString(err));
-    for (void* p : {(void*)d_text, (void*)d_off, (void*)d_counts, (void*)d_starts, (void*)d_ends})
-      if (p) (void)hipFree(p);
-    if (st) (void)hipStreamDestroy(st);
-    return VRAG_ERR_HIP;
-  };
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_text, bytes + 16);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_off, (size_t)(n_docs + 1) * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_counts, (size_t)n_docs * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_starts, (size_t)n_docs * cap * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_ends, (size_t)n_docs * cap * 4);
-  if (e != hipSuccess) return fail(e);
-  // offsets are rebased to the first document so the text buffer can be a slice of a larger one
-  if (bytes) e = hipMemcpyAsync(d_text, text + doc_off[0], bytes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) {
-    if (doc_off[0] == 0) {
-      e = hipMemcpyAsync(d_off, doc_off, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, st);
-    } else {
-      set_error("vrag_split_sentences: doc_off[0] must be 0");
-      (void)fail(hipSuccess);
-      return VRAG_ERR_INVALID;
-    }
+  if (doc_off[0] != 0) {   // the offsets index the text buffer as passed: it starts at the first document
+    set_error("vrag_split_sentences: doc_off[0] must be 0");
+    return VRAG_ERR_INVALID;
   }
-  if (e != hipSuccess) return fail(e);
-  hipLaunchKernelGGL(split_sentences_kernel, dim3((n_docs + 127) / 128), dim3(128), 0, st, d_text, d_off, n_docs, cap, d_counts,
-                     d_starts, d_ends);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, (size_t)n_docs * 4, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(starts, d_starts, (size_t)n_docs * cap * 4, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(ends, d_ends, (size_t)n_docs * cap * 4, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return fail(e);
-  for (void* p : {(void*)d_text, (void*)d_off, (void*)d_counts, (void*)d_starts, (void*)d_ends}) (void)hipFree(p);
-  (void)hipStreamDestroy(st);
+  const size_t bytes = (size_t)doc_off[n_docs];
+  hipStream_t st = nullptr;
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
+  {
+    DevBuf d_text, d_off, d_counts, d_starts, d_ends;   // freed before the stream is destroyed
+    if (e == hipSuccess) e = d_text.alloc(bytes + 16);
+    if (e == hipSuccess) e = d_off.alloc((size_t)(n_docs + 1) * 8);
+    if (e == hipSuccess) e = d_counts.alloc((size_t)n_docs * 4);
+    if (e == hipSuccess) e = d_starts.alloc((size_t)n_docs * cap * 4);
+    if (e == hipSuccess) e = d_ends.alloc((size_t)n_docs * cap * 4);
+    if (e == hipSuccess && bytes) e = hipMemcpyAsync(d_text.p, text, bytes, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_off.p, doc_off, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(split_sentences_kernel, dim3((n_docs + 127) / 128), dim3(128), 0, st, d_text.as<unsigned char>(),
+                         d_off.as<long long>(), n_docs, cap, d_counts.as<int>(), d_starts.as<int>(), d_ends.as<int>());
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts.p, (size_t)n_docs * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(starts, d_starts.p, (size_t)n_docs * cap * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(ends, d_ends.p, (size_t)n_docs * cap * 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+  }
+  if (st) (void)hipStreamDestroy(st);
+  if (e != hipSuccess) {
+    set_error("vrag_split_sentences: %s", hipGetErrorString(e));
+    return VRAG_ERR_HIP;
+  }
   return VRAG_OK;
 }
 

@@ -2207,7 +2207,7 @@ struct vrag_dense_index {
   DevArray<unsigned> d_pf_cnt;     // [PFQ] candidate counters; [PFQ, 3 PFQ): scratch counters / flags of the prefix selection
   DevArray<u64> d_pf_thr;          // [0, 2 PFQ): final selection's threshold outputs (unused); [2 PFQ, 3 PFQ): entry threshold keys; [3 PFQ, 4 PFQ): their scores
   long long pf_searches = 0, pf_fallbacks = 0;
-  char* h_pin = nullptr;           // pinned host staging of the one-pass route: [PFQ][dim + 1] floats up, [PFQ k + PFQ / 2] keys + flags down
+  PinnedArray<char> h_pin;        // pinned host staging of the one-pass route: [PFQ][dim + 1] floats up, [PFQ k + PFQ / 2] keys + flags down
   int resident_split = 0;   // the resident queries are not all bf16-exact: batched passes carry (hi, remainder) column pairs
   hipEvent_t upload_done = nullptr;   // recorded behind the query upload: the host buffer is free once it has passed
   hipEvent_t lists_done = nullptr;    // recorded behind a device-resident search: the next search (any stream) waits for it before reusing the scratch
@@ -2631,7 +2631,7 @@ int vrag_dense_index_create(int32_t dim, int64_t capacity, int32_t dtype, int32_
     e = ix->rows16.grow(((size_t)capacity + 512) * dim);
     if (e == hipSuccess) e = ix->d_norm2.grow(2);
     if (e == hipSuccess) e = hipMemset(ix->d_norm2.p, 0, 2 * sizeof(float));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&ix->h_pin, (size_t)PFQ * (dim + 1) * sizeof(float) + (PFQ * KMAX + PFQ / 2) * sizeof(u64), 0);
+    if (e == hipSuccess) e = ix->h_pin.grow((size_t)PFQ * (dim + 1) * sizeof(float) + (PFQ * KMAX + PFQ / 2) * sizeof(u64), 0);
   }
   ix->stage_rows = std::max<size_t>(1, ((size_t)64 << 20) / ((size_t)dim * 4));
   if (e == hipSuccess) e = ix->stage.grow(ix->stage_rows * dim);
@@ -2648,11 +2648,10 @@ void vrag_dense_index_destroy(vrag_dense_index* ix) {
   if (!ix) return;
   (void)hipSetDevice(ix->device);
   (void)hipDeviceSynchronize();
-  if (ix->h_pin) (void)hipHostFree(ix->h_pin);
   if (ix->upload_done) (void)hipEventDestroy(ix->upload_done);
   if (ix->lists_done) (void)hipEventDestroy(ix->lists_done);
   if (ix->stream) (void)hipStreamDestroy(ix->stream);
-  delete ix;   // the device arrays free themselves
+  delete ix;   // the device and pinned arrays free themselves
 }
 
 int64_t vrag_dense_index_size(vrag_dense_index* ix) { return ix ? ix->size : -1; }
@@ -2919,7 +2918,7 @@ static int prefilter_onepass_enqueue(vrag_dense_index* ix, const float* queries,
   HIP_TRY(ix->d_pf_out.grow((size_t)nq * k + PFQ / 2));
   HIP_TRY(ix->d_cand.grow((size_t)n_wg * nq * k));
   HIP_TRY(ix->d_out.grow((size_t)nq * k + nq));
-  float* up = reinterpret_cast<float*>(ix->h_pin);
+  float* up = reinterpret_cast<float*>(ix->h_pin.p);
   std::memcpy(up, queries, (size_t)nq * dim * sizeof(float));
   for (int q = 0; q < nq; ++q) up[(size_t)nq * dim + q] = prefilter_eps(ix, queries + (size_t)q * dim, /*rounded_query=*/false);   // fp32 query against the image
   HIP_TRY(hipMemcpyAsync(ix->d_q.p, up, ((size_t)nq * dim + nq) * sizeof(float), hipMemcpyHostToDevice, st));
@@ -2981,7 +2980,7 @@ int vrag_dense_index_search(vrag_dense_index* ix, const float* queries, int32_t 
     // one streaming pass over the image (per query, or -- two to PFQ queries, dim % 256 == 0 -- for all of them together:
     // prefilter_single_enqueue); queries + bounds go up in one pinned copy, keys + flags come back in one
     if ((rc = prefilter_onepass_enqueue(ix, queries, nq, k, st))) return rc;
-    u64* down = reinterpret_cast<u64*>(ix->h_pin + (size_t)PFQ * (ix->dim + 1) * sizeof(float));
+    u64* down = reinterpret_cast<u64*>(ix->h_pin.p + (size_t)PFQ * (ix->dim + 1) * sizeof(float));
     HIP_TRY(hipMemcpyAsync(down, ix->d_pf_out.p, ((size_t)nq * k + PFQ / 2) * sizeof(u64), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));   // also retires the query / eps upload of the pinned staging
     std::memcpy(keys.data(), down, keys.size() * sizeof(u64));
