@@ -248,10 +248,10 @@ int vrag_encoder_extract_qa(vrag_encoder* enc, const int32_t* ids, const int32_t
 int vrag_encoder_graph_stats(vrag_encoder* enc, int32_t enable, int64_t* replays, int32_t* cached);
 
 /* fp16 operands (VRAG_OPERAND_F16) saturate at +-65504 instead of overflowing.  *saturated = 1 if any fp32 -> fp16
- * operand conversion on this device (weights at load time, LayerNorm-fold copies, q / k / v, GeGLU outputs, attention
+ * operand conversion of this handle (weights at load time, LayerNorm-fold copies, q / k / v, GeGLU outputs, attention
  * outputs) has had to clamp since the last reset: the logits computed meanwhile are not to be trusted -- re-run with
- * VRAG_OPERAND_BF16 (checkpoints with activation outliers beyond fp16's range; the flag is per process and device, not
- * per handle).  Synchronises the device. */
+ * VRAG_OPERAND_BF16 (checkpoints with activation outliers beyond fp16's range).  The flag is per handle: other handles
+ * on the same device neither see nor clear it.  Synchronises the device. */
 int vrag_encoder_f16_saturated(vrag_encoder* enc, int32_t reset, int32_t* saturated);
 
 /* Per-kernel-class timing with HIP events recorded on the launch stream.

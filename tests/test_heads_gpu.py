@@ -213,6 +213,16 @@ def test_highlighter_cross_query_batching_equals_per_query_calls(setup):
     assert any(len(v) > 0 for d in got for v in d.values())
 
 
+def _hot_weights(w, I):
+    """Outlier checkpoint: three GeGLU channels of layer 1 scaled x3000, so gelu(x1) * x2 leaves fp16's range."""
+    hot = {k: v.copy() for k, v in w.items()}
+    wi = hot["layers.1.mlp.Wi.weight"]                         # [2I, H]: rows 0..I-1 = x1 (gelu input), I..2I-1 = x2
+    for c in (3, 77, 150):
+        wi[c] *= 3000.0
+        wi[I + c] *= 3000.0
+    return hot
+
+
 def test_fp16_operands_report_saturation_instead_of_returning_clamped_logits(tmp_path, caplog):
     """fp16 conversions clamp at +-65504.  A checkpoint with outlier channels (here: three GeGLU channels of
     layer 1 scaled x3000, so gelu(x1) * x2 leaves fp16's range) must be REPORTED, not answered with plausible, wrong
@@ -232,12 +242,7 @@ def test_fp16_operands_report_saturation_instead_of_returning_clamped_logits(tmp
     cfg = O.EncoderConfig(**TINY)
     w = O.random_weights(cfg, seed=7)
     z = np.load(os.path.join(G, "encoder_tiny.npz"))
-    hot = {k: v.copy() for k, v in w.items()}
-    wi = hot["layers.1.mlp.Wi.weight"]                         # [2I, H]: rows 0..I-1 = x1 (gelu input), I..2I-1 = x2
-    I = cfg.intermediate_size
-    for c in (3, 77, 150):
-        wi[c] *= 3000.0
-        wi[I + c] *= 3000.0
+    hot = _hot_weights(w, cfg.intermediate_size)
     seqs = [z["ids_200"], z["ids_64"]]
 
     def run(weights, dtype):
@@ -284,6 +289,33 @@ def test_fp16_operands_report_saturation_instead_of_returning_clamped_logits(tmp
     assert got == ext_bf.extract_spans("Where is the tower?", results)
     for e in ext16.engines + ext_bf.engines:
         e.close()
+
+
+def test_fp16_clamp_report_belongs_to_the_engine_that_clamped():
+    """Two fp16 engines alive on one device, one of them on the outlier checkpoint: each reads and clears its own clamp
+    flag only -- the healthy engine neither reports nor swallows its neighbour's clamp (a provider and an extractor share
+    a device this way)."""
+    from verbatim_rag_amd.engine import EncoderEngine, ModernBertShape
+
+    cfg = O.EncoderConfig(**TINY)
+    w = O.random_weights(cfg, seed=7)
+    z = np.load(os.path.join(G, "encoder_tiny.npz"))
+    seqs = [z["ids_200"], z["ids_64"]]
+    engines = []
+    try:
+        for weights in (_hot_weights(w, cfg.intermediate_size), w):
+            engines.append(EncoderEngine(ModernBertShape(**TINY), weights, max_tokens=8192, max_seqs=64, max_seq_len=2048,
+                                         max_ranges=256, operand_dtype="f16"))
+        hot, healthy = engines
+        for eng in engines:                                    # the healthy batch runs after the clamp
+            eng.load_batch(seqs)
+            eng.run()
+        assert not healthy.f16_saturated(reset=True)
+        assert hot.f16_saturated(reset=True)
+        assert not hot.f16_saturated(reset=True)
+    finally:
+        for eng in engines:
+            eng.close()
 
 
 def test_mlm_head_can_be_set_again_in_either_operand_form(setup):

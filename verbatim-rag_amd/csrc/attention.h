@@ -18,13 +18,10 @@ struct AttnParams {
   int Tp;      // padded token rows (leading dimension of vt)
   int window;  // banded layers: keep |i-j| <= window; ignored for global layers
   int op_dtype;  // kOpBf16 / kOpF16: what q, k, vt and o hold
+  unsigned* f16_sat;  // clamp word (GemmParams::f16_sat); required for kOpF16
 };
 
 hipError_t launch_attention(const AttnParams& p, bool local, hipStream_t stream);
 int attention_q_block(bool local);  // query rows per work item (256 global / 128 banded)
-
-// 1 if an fp32 -> fp16 operand conversion in this file's kernels clamped since the last reset (common.h).
-unsigned attention_f16_saturated(bool reset);
-unsigned* attention_f16_flag_address();   // device address of this file's flag on the current device (common.h)
 
 }  // namespace vrag

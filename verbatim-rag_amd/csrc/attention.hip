@@ -271,7 +271,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const AttnParams p
       for (int g = 0; g < 4; ++g) {
         V4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = Op<T>::to(ot[u][n][4 * g + j] * inv);
+        for (int j = 0; j < 4; ++j) o[j] = Op<T>::to(ot[u][n][4 * g + j] * inv, p.f16_sat);
         *reinterpret_cast<V4*>(stg + row * 128 + (((n * 4 + g) ^ (row & 7)) << 4) + (hi << 3)) = o;
       }
   }
@@ -290,6 +290,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const AttnParams p
 int attention_q_block(bool local) { return local ? ATT_QB_LOCAL : ATT_QB_GLOBAL; }
 
 hipError_t launch_attention(const AttnParams& p, bool local, hipStream_t stream) {
+  if (p.op_dtype == kOpF16 && !p.f16_sat) return hipErrorInvalidValue;
   if (p.n_blocks <= 0) return hipSuccess;
   dim3 grid(p.n_blocks, p.nh);
   if (p.op_dtype == kOpF16) {
@@ -302,7 +303,5 @@ hipError_t launch_attention(const AttnParams& p, bool local, hipStream_t stream)
   return hipGetLastError();
 }
 
-unsigned attention_f16_saturated(bool reset) { return f16_sat_take(reset); }
-unsigned* attention_f16_flag_address() { return f16_sat_flag_address(); }
 
 }  // namespace vrag

@@ -42,7 +42,7 @@ template <typename T>
 __global__ void cvt_rows_bf16_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst_, int rows_dst,
                                      int rows_src, int cols, int interleave_I,
                                      const float* __restrict__ col_scale, float* __restrict__ row_sum,
-                                     bf16_t* __restrict__ dst_lo_ = nullptr) {
+                                     bf16_t* __restrict__ dst_lo_, unsigned* f16_sat) {
   // dst row r <- src row perm(r) (* col_scale per input column: a LayerNorm gain folded into the
   // weight); rows beyond rows_src are zero.  interleave_I > 0 applies the GeGLU interleave: each
   // 64-row group = 32 input rows (x1) then the 32 matching gate rows (x2).  row_sum[r] = sum over
@@ -64,9 +64,9 @@ __global__ void cvt_rows_bf16_kernel(const float* __restrict__ src, bf16_t* __re
   for (int c = threadIdx.x; c < cols; c += blockDim.x) {
     float v = (valid && r < rows_dst && s < rows_src) ? src[(size_t)s * cols + c] : 0.f;
     if (col_scale) v *= col_scale[c];
-    const T b = Op<T>::to(v);
+    const T b = Op<T>::to(v, f16_sat);
     dst[(size_t)r * cols + c] = b;
-    if (dst_lo) dst_lo[(size_t)r * cols + c] = Op<T>::to(v - (float)b);
+    if (dst_lo) dst_lo[(size_t)r * cols + c] = Op<T>::to(v - (float)b, f16_sat);
     acc += (float)b;
   }
   if (row_sum) {
@@ -78,35 +78,38 @@ __global__ void cvt_rows_bf16_kernel(const float* __restrict__ src, bf16_t* __re
 }
 
 static void launch_cvt_rows(int op_dtype, dim3 grid, hipStream_t st, const float* src, bf16_t* dst, int rows_dst, int rows_src,
-                            int cols, int interleave_I, const float* col_scale, float* row_sum, bf16_t* dst_lo = nullptr) {
+                            int cols, int interleave_I, const float* col_scale, float* row_sum, bf16_t* dst_lo, unsigned* f16_sat) {
   if (op_dtype == kOpF16)
     hipLaunchKernelGGL(cvt_rows_bf16_kernel<f16_t>, grid, dim3(256), 0, st, src, dst, rows_dst, rows_src, cols, interleave_I,
-                       col_scale, row_sum, dst_lo);
+                       col_scale, row_sum, dst_lo, f16_sat);
   else
     hipLaunchKernelGGL(cvt_rows_bf16_kernel<bf16_t>, grid, dim3(256), 0, st, src, dst, rows_dst, rows_src, cols, interleave_I,
-                       col_scale, row_sum, dst_lo);
+                       col_scale, row_sum, dst_lo, f16_sat);
 }
 
 // fp32 matrix rows [rows_src, cols] -> [rows_dst, 3 cols] operand image [hi | hi | lo] (zero rows beyond rows_src): the
 // weight side of a K = 3 cols split-operand GEMM whose A operand is [xhi | xlo | xhi] (norm_heads.hip layernorm_kernel,
 // split3): sum = xhi.Whi + xlo.Whi + xhi.Wlo, the three products of (xhi + xlo).(Whi + Wlo) above fp32 resolution.
 template <typename T>
-__global__ void cvt_split3_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst_, int rows_dst, int rows_src, int cols) {
+__global__ void cvt_split3_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst_, int rows_dst, int rows_src, int cols,
+                                  unsigned* f16_sat) {
   T* dst = reinterpret_cast<T*>(dst_);
   const int r = blockIdx.x;
   if (r >= rows_dst) return;
   T* row = dst + (size_t)r * 3 * cols;
   for (int c = threadIdx.x; c < cols; c += blockDim.x) {
     const float v = r < rows_src ? src[(size_t)r * cols + c] : 0.f;
-    const T hi = Op<T>::to(v);
+    const T hi = Op<T>::to(v, f16_sat);
     row[c] = hi;
     row[cols + c] = hi;
-    row[2 * cols + c] = Op<T>::to(v - (float)hi);
+    row[2 * cols + c] = Op<T>::to(v - (float)hi, f16_sat);
   }
 }
-static void launch_cvt_split3(int op_dtype, hipStream_t st, const float* src, bf16_t* dst, int rows_dst, int rows_src, int cols) {
-  if (op_dtype == kOpF16) hipLaunchKernelGGL(cvt_split3_kernel<f16_t>, dim3(rows_dst), dim3(256), 0, st, src, dst, rows_dst, rows_src, cols);
-  else hipLaunchKernelGGL(cvt_split3_kernel<bf16_t>, dim3(rows_dst), dim3(256), 0, st, src, dst, rows_dst, rows_src, cols);
+static void launch_cvt_split3(int op_dtype, hipStream_t st, const float* src, bf16_t* dst, int rows_dst, int rows_src, int cols,
+                              unsigned* f16_sat) {
+  if (op_dtype == kOpF16)
+    hipLaunchKernelGGL(cvt_split3_kernel<f16_t>, dim3(rows_dst), dim3(256), 0, st, src, dst, rows_dst, rows_src, cols, f16_sat);
+  else hipLaunchKernelGGL(cvt_split3_kernel<bf16_t>, dim3(rows_dst), dim3(256), 0, st, src, dst, rows_dst, rows_src, cols, f16_sat);
 }
 
 // Row statistics from the per-segment partial sums left by the residual GEMM epilogue.  The sums are over (h - c)
@@ -244,7 +247,7 @@ struct ProfRec {
 using namespace vrag;
 
 // Memory: every buffer is a DevArray / PinnedArray member, freed with the handle or when the head that owns it is set again.
-// The raw pointers among the members own nothing: slices of one of those arrays, a mapped word's device address, flag symbols.
+// The raw pointers among the members own nothing: slices of one of those arrays, a mapped word's device address.
 struct vrag_encoder {
   vrag_encoder_config cfg{};
   std::recursive_mutex mu;
@@ -254,9 +257,10 @@ struct vrag_encoder {
   int n_streams = 1;
   bool ln_fold = true;   // LayerNorm folded into the producer/consumer GEMM epilogues (VRAG_LN_FOLD=0: separate LN kernels)
   int fused_qkv_attn = 1;   // Wqkv GEMM + RoPE + attention in one kernel per (sequence, head) when every sequence of the micro-batch has <= 512 tokens (VRAG_FUSED_QKV_ATTN)
-  // fp16 clamp reports (vrag_encoder_f16_saturated): the device addresses of the five translation units' flags and one pinned,
-  // device-mapped word they are gathered into by one launch
-  unsigned* sat_addr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  // fp16 clamp reports (vrag_encoder_f16_saturated): the word every fp16 conversion of this handle's launches sets when it
+  // clamps, allocated at create and never moved (captured graphs hold its address), and the pinned, device-mapped word it is
+  // read back through
+  DevArray<unsigned> f16_sat;
   PinnedArray<unsigned> sat_host;
   unsigned* sat_host_dev = nullptr;   // its device address
 
@@ -451,7 +455,7 @@ int upload_bf16(vrag_encoder* e, DevArray<bf16_t>& out, const float* src, int ro
     ARG_CHECK((size_t)rows_src * cols <= stage.n, "internal: staging buffer too small");
     HIP_TRY(hipMemcpy(stage.p, src, (size_t)rows_src * cols * sizeof(float), hipMemcpyHostToDevice));
     launch_cvt_rows(e->op_dtype, dim3(rows_dst), 0, stage.p, out.p, rows_dst, rows_src, cols, interleave_I, d_col_scale, d_row_sum,
-                    d_lo);
+                    d_lo, e->f16_sat.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return VRAG_OK;
@@ -462,7 +466,8 @@ int upload_bf16(vrag_encoder* e, DevArray<bf16_t>& out, const float* src, int ro
     if (nr_src > 0)
       HIP_TRY(hipMemcpy(stage.p, src + (size_t)r0 * cols, (size_t)nr_src * cols * sizeof(float),
                         hipMemcpyHostToDevice));
-    launch_cvt_rows(e->op_dtype, dim3(nr_dst), 0, stage.p, out.p + (size_t)r0 * cols, nr_dst, nr_src, cols, 0, nullptr, nullptr);
+    launch_cvt_rows(e->op_dtype, dim3(nr_dst), 0, stage.p, out.p + (size_t)r0 * cols, nr_dst, nr_src, cols, 0, nullptr, nullptr, nullptr,
+                    e->f16_sat.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
   }
@@ -588,7 +593,7 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
     {
       ProfScope ps(e, VRAG_PROF_EMBED, st);
       HIP_TRY(launch_embed_ln(e->d_ids.p + r0, e->tok_emb.p, e->emb_norm.p, c.norm_eps, H, M, e->h.p + (size_t)r0 * H,
-                              e->a.p + (size_t)r0 * H, st, nullptr, nullptr, nullptr, nullptr, nullptr, e->op_dtype));
+                              e->a.p + (size_t)r0 * H, st, nullptr, nullptr, nullptr, nullptr, nullptr, e->op_dtype, e->f16_sat.p));
     }
     for (int l = 0; l < n_layers; ++l) {
       const Layer& L = e->layers[l];
@@ -606,7 +611,7 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       auto layer_norm = [&](const float* gain) -> int {
         ProfScope ps(e, VRAG_PROF_LAYERNORM, st);
         HIP_TRY(launch_layernorm(e->h.p + (size_t)r0 * H, gain, c.norm_eps, H, M, e->a.p + (size_t)r0 * H, nullptr, st, nullptr, nullptr,
-                                 e->op_dtype));
+                                 e->op_dtype, nullptr, 0, 0, e->f16_sat.p));
         return VRAG_OK;
       };
       if (!fold && l > 0) {
@@ -642,6 +647,7 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       if (fused_attn) {
         QkvAttnParams f{};
         f.op_dtype = e->op_dtype;
+        f.f16_sat = e->f16_sat.p;
         f.x = e->a.p;
         f.w = L.wqkv_h.p;
         if (fold && l > 0) {
@@ -666,6 +672,7 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
+        g.f16_sat = e->f16_sat.p;
         g.A = e->a.p + (size_t)r0 * H;
         g.W = L.wqkv.p;
         if (fold && l > 0) {  // layer 0 consumes the embedding LayerNorm output directly (no attn_norm)
@@ -692,6 +699,7 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         AttnParams ap{};
         ap.op_dtype = e->op_dtype;
+        ap.f16_sat = e->f16_sat.p;
         ap.q = e->q.p;
         ap.k = e->k.p;
         ap.vt = e->vt.p;
@@ -711,6 +719,7 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
+        g.f16_sat = e->f16_sat.p;
         g.A = e->o.p + (size_t)r0 * H;
         g.W = L.wo.p;
         g.M = M;
@@ -738,7 +747,7 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
         if (fold && l == 0) {   // a = bf16(normalised h) without the gain (folded into Wi), ln_shift = mean(h)
           ProfScope ps(e, VRAG_PROF_LAYERNORM, st);
           HIP_TRY(launch_layernorm(e->h.p + (size_t)r0 * H, nullptr, c.norm_eps, H, M, e->a.p + (size_t)r0 * H, nullptr, st, nullptr,
-                                   e->ln_shift.p + r0, e->op_dtype));
+                                   e->ln_shift.p + r0, e->op_dtype, nullptr, 0, 0, e->f16_sat.p));
         } else {
           int rc = fold ? finalize_stats(false) : layer_norm(L.mlp_norm.p);
           if (rc) return rc;
@@ -747,6 +756,7 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
+        g.f16_sat = e->f16_sat.p;
         g.A = e->a.p + (size_t)r0 * H;
         g.W = L.wi.p;
         if (fold && l > 0) {
@@ -765,6 +775,7 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
+        g.f16_sat = e->f16_sat.p;
         g.A = e->act.p + (size_t)r0 * I;
         g.W = L.wo_mlp.p;
         g.M = M;
@@ -834,7 +845,7 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       ProfScope ps(e, VRAG_PROF_EMBED, st);
       HIP_TRY(launch_embed_ln(e->d_ids.p + r0, e->tok_emb.p, e->emb_norm.p, c.norm_eps, H, M, h, a, st, e->pos_emb.p,
                               e->d_pos.p + r0, e->types_loaded ? e->type_table.p : e->type_row.p, e->emb_norm_b.p,
-                              e->types_loaded ? e->d_types.p + r0 : nullptr, e->op_dtype));
+                              e->types_loaded ? e->d_types.p + r0 : nullptr, e->op_dtype, e->f16_sat.p));
     }
     const bool fold = e->ln_fold;
     float* st_part = e->st_part.p + (size_t)r0 * 2;
@@ -853,6 +864,7 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
+        g.f16_sat = e->f16_sat.p;
         g.A = a;
         g.W = L.wqkv.p;
         g.bias = L.bqkv.p;
@@ -879,6 +891,7 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         AttnParams ap{};
         ap.op_dtype = e->op_dtype;
+        ap.f16_sat = e->f16_sat.p;
         ap.q = e->q.p;
         ap.k = e->k.p;
         ap.vt = e->vt.p;
@@ -897,6 +910,7 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
+        g.f16_sat = e->f16_sat.p;
         g.A = e->o.p + (size_t)r0 * Ha;
         g.W = L.wo.p;
         g.M = M;
@@ -924,11 +938,12 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
         if (rc) return rc;
       } else {
         ProfScope ps(e, VRAG_PROF_LAYERNORM, st);
-        HIP_TRY(launch_layernorm(h, L.ln1_w.p, c.norm_eps, H, M, a, h, st, L.ln1_b.p, nullptr, e->op_dtype));
+        HIP_TRY(launch_layernorm(h, L.ln1_w.p, c.norm_eps, H, M, a, h, st, L.ln1_b.p, nullptr, e->op_dtype, nullptr, 0, 0, e->f16_sat.p));
       }
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
+        g.f16_sat = e->f16_sat.p;
         g.A = a;
         g.W = L.w1.p;
         g.M = M;
@@ -948,6 +963,7 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       {
         GemmParams g{};
         g.op_dtype = e->op_dtype;
+        g.f16_sat = e->f16_sat.p;
         g.A = e->act.p + (size_t)r0 * I;
         g.W = L.w2.p;
         g.M = M;
@@ -973,7 +989,7 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       } else {
         // materialise the layer output (last layer of this run, or un-folded mode): h <- LN2(h), a <- bf16(h)
         ProfScope ps(e, VRAG_PROF_LAYERNORM, st);
-        HIP_TRY(launch_layernorm(h, L.ln2_w.p, c.norm_eps, H, M, a, h, st, L.ln2_b.p, nullptr, e->op_dtype));
+        HIP_TRY(launch_layernorm(h, L.ln2_w.p, c.norm_eps, H, M, a, h, st, L.ln2_b.p, nullptr, e->op_dtype, nullptr, 0, 0, e->f16_sat.p));
       }
     }
   }
@@ -995,6 +1011,17 @@ int init_streams(vrag_encoder* e) {
   for (int i = 0; i < 4; ++i) HIP_TRY(hipStreamCreateWithFlags(&e->aux_streams[i], hipStreamNonBlocking));
   HIP_TRY(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
   for (int i = 0; i < 4; ++i) HIP_TRY(hipEventCreateWithFlags(&e->ev_join[i], hipEventDisableTiming));
+  return VRAG_OK;
+}
+
+// The handle's fp16 clamp word (zeroed) and the mapped host word it is read back through.  Both create functions call this
+// before packing any weight, so that a clamp during packing is reported by the handle that packed.
+int init_f16_sat(vrag_encoder* e) {
+  TRY(dev_alloc(e->f16_sat, 1));
+  HIP_TRY(e->sat_host.grow(1, hipHostMallocMapped));
+  void* d = nullptr;
+  HIP_TRY(hipHostGetDevicePointer(&d, e->sat_host.p, 0));
+  e->sat_host_dev = reinterpret_cast<unsigned*>(d);
   return VRAG_OK;
 }
 
@@ -1077,18 +1104,11 @@ int read_rows(vrag_encoder* e, const float* dsrc, int cols, float* out, hipStrea
   return VRAG_OK;
 }
 
-struct SatFlags {
-  unsigned* a[5];
-};
-// one thread: OR of the translation units' clamp flags into the pinned word; a raised flag is cleared when `reset`
-__global__ void f16_sat_gather_kernel(SatFlags f, int reset, unsigned* __restrict__ out) {
-  unsigned any = 0u;
-  for (int i = 0; i < 5; ++i) {
-    const unsigned v = *f.a[i];
-    any |= v;
-    if (reset && v) *f.a[i] = 0u;
-  }
-  *out = any;
+// one thread: the handle's clamp word into the pinned word; a raised word is cleared when `reset`
+__global__ void f16_sat_read_kernel(unsigned* __restrict__ sat, int reset, unsigned* __restrict__ out) {
+  const unsigned v = *sat;
+  if (reset && v) *sat = 0u;
+  *out = v;
 }
 
 }  // namespace
@@ -1131,6 +1151,7 @@ int vrag_encoder_create(const vrag_encoder_config* cfg, const vrag_encoder_weigh
   e->cfg = *cfg;
   e->op_dtype = cfg->operand_dtype;
   TRY(init_streams(e));
+  TRY(init_f16_sat(e));
 
   if (const char* lf = getenv("VRAG_LN_FOLD")) e->ln_fold = atoi(lf) != 0;
   if (const char* sr = getenv("VRAG_SPLIT_RESID")) e->split_resid = atoi(sr) != 0;
@@ -1247,6 +1268,7 @@ int vrag_bert_encoder_create(const vrag_bert_config* cfg, const vrag_bert_weight
     c.device = cfg->device;
   }
   TRY(init_streams(e));
+  TRY(init_f16_sat(e));
   const size_t stage_elems = std::max<size_t>({(size_t)3 * Ha * H, (size_t)I * H, (size_t)1 << 22});
   DevArray<float> stage;   // freed on return
   TRY(dev_alloc(stage, stage_elems, false));
@@ -1393,12 +1415,12 @@ int vrag_encoder_set_mlm_head_ex(vrag_encoder* e, const float* dense_w, const fl
       for (int r0 = 0; r0 < vpad; r0 += chunk) {
         const int nr_dst = std::min(chunk, vpad - r0), nr_src = std::max(0, std::min(chunk, V - r0));
         if (nr_src > 0) HIP_TRY(hipMemcpy(stage.p, decoder_w + (size_t)r0 * H, (size_t)nr_src * H * sizeof(float), hipMemcpyHostToDevice));
-        launch_cvt_split3(e->op_dtype, 0, stage.p, e->mlm_dec3.p + (size_t)r0 * 3 * H, nr_dst, nr_src, H);
+        launch_cvt_split3(e->op_dtype, 0, stage.p, e->mlm_dec3.p + (size_t)r0 * 3 * H, nr_dst, nr_src, H, e->f16_sat.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());
       }
     } else {   // tied decoder: the device-resident fp32 embedding table
-      launch_cvt_split3(e->op_dtype, 0, e->tok_emb.p, e->mlm_dec3.p, vpad, V, H);
+      launch_cvt_split3(e->op_dtype, 0, e->tok_emb.p, e->mlm_dec3.p, vpad, V, H, e->f16_sat.p);
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipDeviceSynchronize());
     }
@@ -1407,7 +1429,8 @@ int vrag_encoder_set_mlm_head_ex(vrag_encoder* e, const float* dense_w, const fl
   } else {
     // tied decoder: convert the device-resident fp32 embedding table
     TRY(dev_alloc(e->mlm_dec, (size_t)vpad * H, false));
-    launch_cvt_rows(e->op_dtype, dim3(vpad), 0, e->tok_emb.p, e->mlm_dec.p, vpad, V, H, 0, (const float*)nullptr, (float*)nullptr);
+    launch_cvt_rows(e->op_dtype, dim3(vpad), 0, e->tok_emb.p, e->mlm_dec.p, vpad, V, H, 0, (const float*)nullptr, (float*)nullptr, nullptr,
+                    e->f16_sat.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
   }
@@ -1917,12 +1940,14 @@ int vrag_encoder_run_token_head(vrag_encoder* e, void* stream) {
   // type, three MFMA GEMMs accumulated in fp32 (hi.hi + lo.hi + hi.lo; lo.lo is below fp32 resolution) -- which costs
   // 3 x 2.T.H^2 FLOP, under 2 % of the encoder (tests/probes/precision_probe.py: 6.3e-3 -> 8.8e-4 on bf16 encoders).
   bf16_t* x_lo = e->o.p;   // the attention output buffer is free once the layers have run (row stride H for arch 0)
-  HIP_TRY(launch_layernorm(e->h.p, e->final_norm.p, e->cfg.norm_eps, H, e->rows, e->a.p, nullptr, st, nullptr, nullptr, e->op_dtype, x_lo));
+  HIP_TRY(launch_layernorm(e->h.p, e->final_norm.p, e->cfg.norm_eps, H, e->rows, e->a.p, nullptr, st, nullptr, nullptr, e->op_dtype,
+                           x_lo, 0, 0, e->f16_sat.p));
   HIP_TRY(hipMemsetAsync(e->f32tmp.p, 0, (size_t)e->rows * H * sizeof(float), st));
   const bf16_t* parts[3][2] = {{e->a.p, e->tk_dense.p}, {x_lo, e->tk_dense.p}, {e->a.p, e->tk_dense_lo.p}};
   for (auto& pr : parts) {
     GemmParams g{};
     g.op_dtype = e->op_dtype;
+    g.f16_sat = e->f16_sat.p;
     g.A = pr[0];
     g.W = pr[1];
     g.M = e->rows;
@@ -1964,14 +1989,17 @@ int vrag_encoder_run_splade(vrag_encoder* e, void* stream) {
   // [xhi | xlo | xhi] x [Whi | Whi | Wlo] with the SPLADE epilogue on the sum (lo.lo is below fp32 resolution).
   bf16_t* x_lo = split ? e->o.p : nullptr;   // the attention output buffer is free once the layers have run
   if (e->arch == 1) {  // post-LN stream: no final LayerNorm, just the operand copy
-    launch_cvt_rows(e->op_dtype, dim3(e->rows), st, e->h.p, e->a.p, e->rows, e->rows, H, 0, (const float*)nullptr, (float*)nullptr, x_lo);
+    launch_cvt_rows(e->op_dtype, dim3(e->rows), st, e->h.p, e->a.p, e->rows, e->rows, H, 0, (const float*)nullptr, (float*)nullptr, x_lo,
+                    e->f16_sat.p);
     HIP_TRY(hipGetLastError());
   } else {
-    HIP_TRY(launch_layernorm(e->h.p, e->final_norm.p, e->cfg.norm_eps, H, e->rows, e->a.p, nullptr, st, nullptr, nullptr, e->op_dtype, x_lo));
+    HIP_TRY(launch_layernorm(e->h.p, e->final_norm.p, e->cfg.norm_eps, H, e->rows, e->a.p, nullptr, st, nullptr, nullptr, e->op_dtype,
+                             x_lo, 0, 0, e->f16_sat.p));
   }
   HIP_TRY(hipMemsetAsync(e->d_splade.p, 0, (size_t)e->n_seqs * e->vpad * sizeof(unsigned), st));
   GemmParams d{};
   d.op_dtype = e->op_dtype;
+  d.f16_sat = e->f16_sat.p;
   d.M = e->rows;
   d.N = e->vpad;
   d.bias = e->mlm_bias.p;
@@ -1983,6 +2011,7 @@ int vrag_encoder_run_splade(vrag_encoder* e, void* stream) {
     for (int i = 0; i < 3; ++i) {
       GemmParams g{};
       g.op_dtype = e->op_dtype;
+      g.f16_sat = e->f16_sat.p;
       g.A = parts[i][0];
       g.W = parts[i][1];
       g.M = e->rows;
@@ -1993,13 +2022,14 @@ int vrag_encoder_run_splade(vrag_encoder* e, void* stream) {
       HIP_TRY(launch_gemm(EPI_RESIDUAL, g, st));
     }
     HIP_TRY(launch_layernorm(e->f32tmp.p, e->mlm_norm.p, e->cfg.norm_eps, H, e->rows, e->splade_a3.p, nullptr, st, e->mlm_norm_b.p, nullptr,
-                             e->op_dtype, nullptr, /*gelu_first=*/1, /*split3=*/1));
+                             e->op_dtype, nullptr, /*gelu_first=*/1, /*split3=*/1, e->f16_sat.p));
     d.A = e->splade_a3.p;
     d.W = e->mlm_dec3.p;
     d.K = 3 * H;
   } else {
     GemmParams g{};
     g.op_dtype = e->op_dtype;
+    g.f16_sat = e->f16_sat.p;
     g.A = e->a.p;
     g.W = e->mlm_dense.p;
     g.M = e->rows;
@@ -2009,7 +2039,7 @@ int vrag_encoder_run_splade(vrag_encoder* e, void* stream) {
     g.bias = e->mlm_dense_b.p;
     HIP_TRY(launch_gemm(EPI_F32_GELU, g, st));
     HIP_TRY(launch_layernorm(e->f32tmp.p, e->mlm_norm.p, e->cfg.norm_eps, H, e->rows, e->a.p, nullptr, st, e->mlm_norm_b.p, nullptr,
-                             e->op_dtype));
+                             e->op_dtype, nullptr, 0, 0, e->f16_sat.p));
     d.A = e->a.p;
     d.W = e->mlm_dec.p;
     d.K = H;
@@ -2106,40 +2136,13 @@ int vrag_encoder_f16_saturated(vrag_encoder* e, int32_t reset, int32_t* saturate
   ARG_CHECK(e && saturated, "null argument");
   std::lock_guard<std::recursive_mutex> lk(e->mu);
   HIP_TRY(hipSetDevice(e->cfg.device));
-  HIP_TRY(hipDeviceSynchronize());
-  // One launch + one stream wait instead of five synchronous symbol copies (each ~12 us: 70 us of a single question's 1.35 ms
-  // embedding call sat here, tools/probes/embed_latency_probe.py).  The flags are per device, not per engine, as before.
-  if (!e->sat_host.p) {
-    PinnedArray<unsigned> word;
-    if (word.grow(1, hipHostMallocMapped) == hipSuccess) {
-      void* d = nullptr;
-      if (hipHostGetDevicePointer(&d, word.p, 0) == hipSuccess) {
-        e->sat_host = std::move(word);
-        e->sat_host_dev = reinterpret_cast<unsigned*>(d);
-        e->sat_addr[0] = f16_sat_flag_address();   // conversions in this file (weight packing)
-        e->sat_addr[1] = gemm_f16_flag_address();
-        e->sat_addr[2] = attention_f16_flag_address();
-        e->sat_addr[3] = qkv_attn_f16_flag_address();
-        e->sat_addr[4] = norm_heads_f16_flag_address();
-      }
-    }
-    (void)hipGetLastError();
-  }
-  if (e->sat_host.p && e->sat_addr[0] && e->sat_addr[1] && e->sat_addr[2] && e->sat_addr[3] && e->sat_addr[4]) {
-    SatFlags f;
-    for (int i = 0; i < 5; ++i) f.a[i] = e->sat_addr[i];
-    hipLaunchKernelGGL(f16_sat_gather_kernel, dim3(1), dim3(1), 0, e->own_stream, f, reset != 0 ? 1 : 0, e->sat_host_dev);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(e->own_stream));
-    *saturated = *reinterpret_cast<volatile unsigned*>(e->sat_host.p) ? 1 : 0;
-    return VRAG_OK;
-  }
-  unsigned any = f16_sat_take(reset != 0);                 // (no mapped word or no symbol address: the per-file copies)
-  any |= gemm_f16_saturated(reset != 0);
-  any |= attention_f16_saturated(reset != 0);
-  any |= qkv_attn_f16_saturated(reset != 0);
-  any |= norm_heads_f16_saturated(reset != 0);
-  *saturated = any ? 1 : 0;
+  HIP_TRY(hipDeviceSynchronize());   // the handle's work may have been enqueued on caller streams
+  // one launch + one stream wait (a synchronous copy costs ~12 us of a single question's ~1.35 ms embedding call,
+  // tools/probes/embed_latency_probe.py)
+  hipLaunchKernelGGL(f16_sat_read_kernel, dim3(1), dim3(1), 0, e->own_stream, e->f16_sat.p, reset != 0 ? 1 : 0, e->sat_host_dev);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->own_stream));
+  *saturated = *reinterpret_cast<volatile unsigned*>(e->sat_host.p) ? 1 : 0;
   return VRAG_OK;
 }
 

@@ -21,14 +21,11 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // kernels, templated on the operand type, reinterpret them.  fp16 conversions saturate at +-65504 instead of
 // producing inf.
 constexpr int kOpBf16 = 0, kOpF16 = 1;
-// Set by any fp32 -> fp16 operand conversion that had to clamp (one copy per translation unit: no relocatable device
-// code in this build; f16_sat_take() below reads and clears the copy of the file that includes it).
-static __device__ unsigned vrag_f16_sat_flag;
 template <typename T> struct Op;
 template <> struct Op<bf16_t> {
   typedef bf16x4 v4;
   typedef bf16x8 v8;
-  static __device__ __forceinline__ bf16_t to(float v) { return (bf16_t)v; }
+  static __device__ __forceinline__ bf16_t to(float v, unsigned*) { return (bf16_t)v; }
   static __device__ __forceinline__ f32x16 mfma32(const v8& a, const v8& b, const f32x16& c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
   }
@@ -39,10 +36,11 @@ template <> struct Op<bf16_t> {
 template <> struct Op<f16_t> {
   typedef f16x4 v4;
   typedef f16x8 v8;
-  static __device__ __forceinline__ f16_t to(float v) {
+  // `sat`: the launching engine's clamp word (GemmParams::f16_sat and the like; never null for fp16 launches)
+  static __device__ __forceinline__ f16_t to(float v, unsigned* sat) {
     // a value outside fp16's range is stored as +-65504 AND reported: silently clamped activations would come back as
     // plausible, wrong logits (vrag_encoder_f16_saturated; the branch is never taken on healthy checkpoints)
-    if (__builtin_fabsf(v) > 65504.f) vrag_f16_sat_flag = 1u;
+    if (__builtin_fabsf(v) > 65504.f) *sat = 1u;
     return (f16_t)__builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);
   }
   static __device__ __forceinline__ f32x16 mfma32(const v8& a, const v8& b, const f32x16& c) {
@@ -167,27 +165,6 @@ __device__ __forceinline__ f32x4 load16_nt(const void* src) {
   return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(src));
 }
 #endif
-
-// Host side of vrag_f16_sat_flag for THIS translation unit: 1 if a conversion clamped since the last reset (synchronises
-// the device: callers use it on the read-back path, never between launches).
-static inline unsigned f16_sat_take(bool reset) {
-  unsigned v = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(vrag_f16_sat_flag), sizeof(v)) != hipSuccess) return 0;
-  if (reset && v) {
-    const unsigned zero = 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(vrag_f16_sat_flag), &zero, sizeof(zero));
-  }
-  return v;
-}
-
-// Device address of THIS translation unit's vrag_f16_sat_flag on the current device: the encoder gathers the flags of all its
-// translation units with ONE launch into a pinned word (capi.hip: vrag_encoder_f16_saturated) instead of one synchronous
-// symbol copy per file (five ~12 us copies on every fp16 call's read-back path).
-static inline unsigned* f16_sat_flag_address() {
-  void* p = nullptr;
-  if (hipGetSymbolAddress(&p, HIP_SYMBOL(vrag_f16_sat_flag)) != hipSuccess) return nullptr;
-  return reinterpret_cast<unsigned*>(p);
-}
 
 // Top-k candidate keys (csrc/topk.hip; also built by the EPI_TOPK epilogue of csrc/gemm_bf16.hip): one u64
 //   [ orderable(score) : 32 | 0xFFFFFFFF - local_row : 32 ]      (max key == best hit under (score desc, id asc))

@@ -32,7 +32,7 @@ int vrag_debug_gemm_ms(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t ite
   }
   HIP_TRY(hipSetDevice(device));
   const size_t Mp = (size_t)align_up(M, kRowPad);
-  DevBuf A, W, outf, outb, q, kk, vt, cs, sn, pos;
+  DevBuf A, W, outf, outb, q, kk, vt, cs, sn, pos, sat;
   hipError_t e = A.alloc(Mp * K * 2);
   if (e == hipSuccess) e = W.alloc((size_t)N * K * 2);
   if (e == hipSuccess) e = outf.alloc(Mp * N * 4);
@@ -43,6 +43,7 @@ int vrag_debug_gemm_ms(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t ite
   if (e == hipSuccess) e = cs.alloc(512 * 32 * 4);
   if (e == hipSuccess) e = sn.alloc(512 * 32 * 4);
   if (e == hipSuccess) e = pos.alloc(Mp * 4);
+  if (e == hipSuccess) e = sat.alloc(4);   // the fp16 clamp word (not read)
   if (e != hipSuccess) {
     set_error("debug gemm allocation failed: %s", hipGetErrorString(e));
     return VRAG_ERR_HIP;
@@ -66,6 +67,7 @@ int vrag_debug_gemm_ms(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t ite
   (void)hipMemset(sn.p, 0, 512 * 32 * 4);
   GemmParams g{};
   g.op_dtype = getenv("VRAG_DEBUG_GEMM_F16") ? kOpF16 : kOpBf16;   // same bit patterns read as fp16: finite values in [2^-15, 2^-7)
+  g.f16_sat = sat.as<unsigned>();
   g.A = A.as<bf16_t>();
   g.W = W.as<bf16_t>();
   g.M = M;
@@ -133,7 +135,7 @@ int vrag_debug_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int3
       bl.push_back(S);
       bq.push_back(q0);
     }
-  DevBuf q, k, vt, o, d_bs, d_bl, d_bq;
+  DevBuf q, k, vt, o, d_bs, d_bl, d_bq, sat;
   hipError_t e = q.alloc(Tp * H * 2);
   if (e == hipSuccess) e = k.alloc(Tp * H * 2);
   if (e == hipSuccess) e = vt.alloc(Tp * H * 2);
@@ -141,6 +143,7 @@ int vrag_debug_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int3
   if (e == hipSuccess) e = d_bs.alloc(bs.size() * 4);
   if (e == hipSuccess) e = d_bl.alloc(bs.size() * 4);
   if (e == hipSuccess) e = d_bq.alloc(bs.size() * 4);
+  if (e == hipSuccess) e = sat.alloc(4);   // the fp16 clamp word (not read)
   if (e != hipSuccess) {
     set_error("debug attention allocation failed: %s", hipGetErrorString(e));
     return VRAG_ERR_HIP;
@@ -173,6 +176,7 @@ int vrag_debug_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int3
   ap.Tp = (int)Tp;
   ap.window = window;
   ap.op_dtype = getenv("VRAG_DEBUG_GEMM_F16") ? kOpF16 : kOpBf16;
+  ap.f16_sat = sat.as<unsigned>();
   hipEvent_t a, b;
   (void)hipEventCreate(&a);
   (void)hipEventCreate(&b);
@@ -206,7 +210,7 @@ int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, 
   const int nh = H / 64;
   std::vector<int> row(n_seqs), len(n_seqs, S);
   for (int s = 0; s < n_seqs; ++s) row[s] = s * S;
-  DevBuf x, w, o, mu, rstd, lns, cs, d_row, d_len;
+  DevBuf x, w, o, mu, rstd, lns, cs, d_row, d_len, sat;
   hipError_t e = x.alloc(Tp * H * 2);
   if (e == hipSuccess) e = w.alloc((size_t)3 * H * H * 2);
   if (e == hipSuccess) e = o.alloc(Tp * H * 2);
@@ -216,6 +220,7 @@ int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, 
   if (e == hipSuccess) e = cs.alloc((size_t)kFusedMaxSeq * 32 * 4);
   if (e == hipSuccess) e = d_row.alloc((size_t)n_seqs * 8 * sizeof(int4));   // the groups' wave descriptors
   if (e == hipSuccess) e = d_len.alloc(n_seqs * 4);
+  if (e == hipSuccess) e = sat.alloc(4);   // the fp16 clamp word (not read)
   if (e != hipSuccess) {
     set_error("debug allocation failed: %s", hipGetErrorString(e));
     return VRAG_ERR_HIP;
@@ -256,6 +261,7 @@ int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, 
   f.Tp = (int)Tp;
   f.window = window;
   f.op_dtype = getenv("VRAG_DEBUG_GEMM_F16") ? kOpF16 : kOpBf16;
+  f.f16_sat = sat.as<unsigned>();
   f.q_scale = 0.125f * 1.4426950408889634f;
   f.debug_flags = flags;
   hipEvent_t a, b;
@@ -296,7 +302,7 @@ int vrag_debug_attn_run(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int
       bl.push_back(S);
       bq.push_back(q0);
     }
-  DevBuf dq, dk, dv, dout, d_bs, d_bl, d_bq;
+  DevBuf dq, dk, dv, dout, d_bs, d_bl, d_bq, sat;
   hipError_t e = dq.alloc(Tp * H * 2);
   if (e == hipSuccess) e = dk.alloc(Tp * H * 2);
   if (e == hipSuccess) e = dv.alloc(Tp * H * 2);
@@ -304,6 +310,7 @@ int vrag_debug_attn_run(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int
   if (e == hipSuccess) e = d_bs.alloc(bs.size() * 4);
   if (e == hipSuccess) e = d_bl.alloc(bs.size() * 4);
   if (e == hipSuccess) e = d_bq.alloc(bs.size() * 4);
+  if (e == hipSuccess) e = sat.alloc(4);   // the fp16 clamp word (not read)
   if (e == hipSuccess) e = hipMemset(dq.p, 0, Tp * H * 2);
   if (e == hipSuccess) e = hipMemset(dk.p, 0, Tp * H * 2);
   if (e == hipSuccess) e = hipMemset(dout.p, 0, Tp * H * 2);
@@ -329,6 +336,7 @@ int vrag_debug_attn_run(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int
     ap.Tp = (int)Tp;
     ap.window = window;
     ap.op_dtype = f16 ? kOpF16 : kOpBf16;
+    ap.f16_sat = sat.as<unsigned>();
     e = launch_attention(ap, local != 0, 0);
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -430,7 +438,9 @@ int vrag_debug_gemm_run(vrag_debug_gemm_args* a, int32_t device) {
   const int isp = add(a->stats_part, a->stats_part, (size_t)(N / 64) * R * 8, "stats_part");
   const int ilo_out = a->lo_out == a->lo_in ? ilo_in : add(a->lo_out, a->lo_out, R * N, "lo_out");
   const int ispl = add(a->splade_rows, a->splade_rows, (size_t)a->n_seqs * N * 4, "splade_rows");
-  hipError_t e = hipSuccess;
+  DevBuf sat;   // the launch's fp16 clamp word, reported in f16_saturated
+  hipError_t e = sat.alloc(4);
+  if (e == hipSuccess) e = hipMemset(sat.p, 0, 4);
   for (Buf& b : bufs) {
     if (e == hipSuccess) e = b.dev.alloc(b.bytes + kCanary);
     if (e == hipSuccess) e = hipMemcpy(b.dev.p, b.host, b.bytes, hipMemcpyHostToDevice);
@@ -439,6 +449,7 @@ int vrag_debug_gemm_run(vrag_debug_gemm_args* a, int32_t device) {
   auto dev = [&](int i, size_t offset_bytes) -> char* { return i < 0 ? nullptr : bufs[i].dev.as<char>() + offset_bytes; };
   GemmParams g{};
   g.op_dtype = a->f16 ? kOpF16 : kOpBf16;
+  g.f16_sat = sat.as<unsigned>();
   g.M = M;
   g.N = N;
   g.K = K;
@@ -478,7 +489,6 @@ int vrag_debug_gemm_run(vrag_debug_gemm_args* a, int32_t device) {
   const int thr = gemm_small_m_threshold(-1);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) {
-    (void)gemm_f16_saturated(true);
     if (a->small_rows >= 0) gemm_small_m_threshold(a->small_rows);
     e = launch_gemm((GemmEpi)epi, g, 0);
     const GemmConfig c = gemm_last_config();
@@ -487,7 +497,9 @@ int vrag_debug_gemm_run(vrag_debug_gemm_args* a, int32_t device) {
     std::memcpy(a->config, cfg, sizeof(cfg));
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) a->f16_saturated = (int32_t)gemm_f16_saturated(true);
+  unsigned saturated = 0;
+  if (e == hipSuccess) e = hipMemcpy(&saturated, sat.p, 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) a->f16_saturated = saturated ? 1 : 0;
   std::vector<unsigned char> canary(kCanary);
   const char* clobbered = nullptr;
   for (Buf& b : bufs) {

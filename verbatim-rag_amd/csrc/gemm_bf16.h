@@ -91,6 +91,7 @@ struct GemmParams {
   int op_dtype;           // kOpBf16 (0) or kOpF16 (1): what A, W and every 16-bit output hold (pointers stay typed bf16_t*)
   int n_tiles;            // filled by the launcher: output tiles walked by the persistent grid
   int act_gelu;           // EPI_BF16: apply GELU(erf) after the bias
+  unsigned* f16_sat;      // set to 1 by an fp16 conversion that clamped at +-65504 (the launching engine's word); required when op_dtype is kOpF16
 };
 
 // Launches on `stream`. Requirements: N % 128 == 0, K % 64 == 0.
@@ -111,9 +112,5 @@ GemmConfig gemm_last_config();
 // True when a LayerNorm-folding GEMM over `rows` token rows takes the small-row configuration and therefore finishes the row
 // statistics itself when given `stats_in` (the caller then skips ln_stats_finalize_kernel).
 bool gemm_consumer_finalizes(int rows);
-
-// 1 if an fp32 -> fp16 operand conversion in this file's kernels clamped since the last reset (common.h).
-unsigned gemm_f16_saturated(bool reset);
-unsigned* gemm_f16_flag_address();   // device address of this file's flag on the current device (common.h)
 
 }  // namespace vrag

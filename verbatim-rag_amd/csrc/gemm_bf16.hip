@@ -156,7 +156,7 @@ __device__ __forceinline__ void residual_split_body(const GemmParams& p, f32x4 (
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const float x = v[j >> 1][j & 1];
-          ho[j] = Op<T>::to(x);
+          ho[j] = Op<T>::to(x, p.f16_sat);
           // (x / hi - 1) / step + 128; hi = 0 (x = 0, or an fp16 underflow): 0 * inf = NaN -> byte 0 -> decodes to hi * (...) = 0;
           // an fp16 hi clamped at +-65504 saturates the byte (and Op<T>::to has raised the saturation flag)
           const float t = fmaf(x * __builtin_amdgcn_rcpf((float)ho[j]), kInv, 128.0f - kInv);
@@ -368,7 +368,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
           if (p.resid_bf16) {
             V4 o;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = Op<T>::to(v[j]);
+            for (int j = 0; j < 4; ++j) o[j] = Op<T>::to(v[j], p.f16_sat);
             store8_nt(p.resid_bf16 + (size_t)(mw + ps * 64 + row) * p.N + nw + c16 * 4, o);
           }
           if (p.stats_part) {
@@ -438,7 +438,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
             if constexpr (FOLD) v = rs * (v - mu * ls[nj][j]);
             if constexpr (BIAS) v += bs[nj][j];
             if constexpr (GELU) v = gelu_fast(v);   // BERT-family MLP: gelu(x W1^T + b1)
-            o[j] = Op<T>::to(v);
+            o[j] = Op<T>::to(v, p.f16_sat);
           }
           put_bf16(rt * 16 + l15, nj * 16 + 4 * q, o, 128);
         }
@@ -504,8 +504,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
               x2 = pk_fma(splat2(-mu), f32x2{s2[nj][2 * h], s2[nj][2 * h + 1]}, x2) * rs;
             }
             const f32x2 g = gelu_fast2(x1) * x2;
-            o[2 * h] = Op<T>::to(g[0]);
-            o[2 * h + 1] = Op<T>::to(g[1]);
+            o[2 * h] = Op<T>::to(g[0], p.f16_sat);
+            o[2 * h + 1] = Op<T>::to(g[1], p.f16_sat);
           }
           put_pair(rt * 16 + l15, nj * 16 + 4 * q, o);
         }
@@ -603,10 +603,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
                 const f32x2 c2 = {c[j0], c[j0 + 1]}, s2 = {sv[j0], sv[j0 + 1]};
                 // q*cos + rotate_half(q)*sin, rotate_half = cat(-x2, x1)  (TF:188-219)
                 const f32x2 r1 = pk_fma(-x2, s2, x1 * c2) * scale, r2 = pk_fma(x1, s2, x2 * c2) * scale;
-                o1[j0] = Op<T>::to(r1[0]);
-                o1[j0 + 1] = Op<T>::to(r1[1]);
-                o2[j0] = Op<T>::to(r2[0]);
-                o2[j0 + 1] = Op<T>::to(r2[1]);
+                o1[j0] = Op<T>::to(r1[0], p.f16_sat);
+                o1[j0 + 1] = Op<T>::to(r1[1], p.f16_sat);
+                o2[j0] = Op<T>::to(r2[0], p.f16_sat);
+                o2[j0 + 1] = Op<T>::to(r2[1], p.f16_sat);
               }
               put_bf16(rt * 16 + l15, dd, o1, 128);
               put_bf16(rt * 16 + l15, dd + 32, o2, 128);
@@ -655,8 +655,8 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
               f32x2 v = {acc[nj][rt][j0], acc[nj][rt][j0 + 1]};
               if constexpr (FOLD) v = pk_fma(f32x2{-mu4[rt][j0], -mu4[rt][j0 + 1]}, splat2(sn_), v) * f32x2{rs4[rt][j0], rs4[rt][j0 + 1]};
               if constexpr (BIAS) v += bv_;
-              o[j0] = Op<T>::to(v[0]);
-              o[j0 + 1] = Op<T>::to(v[1]);
+              o[j0] = Op<T>::to(v[0], p.f16_sat);
+              o[j0 + 1] = Op<T>::to(v[1], p.f16_sat);
             }
             put_bf16(nj * 16 + l15, rt * 16 + 4 * q, o, RB);
           }
@@ -1252,6 +1252,7 @@ static hipError_t launch_typed(GemmEpi epi, const GemmParams& p, hipStream_t str
 }
 
 hipError_t launch_gemm(GemmEpi epi, const GemmParams& p, hipStream_t stream) {
+  if (p.op_dtype == kOpF16 && !p.f16_sat) return hipErrorInvalidValue;
   if (p.M <= 0) return hipSuccess;
   if ((p.N % 128 != 0 && !(epi == EPI_TOPK && p.topk_tile == 2 && p.N == 64)) || p.K % BK != 0) return hipErrorInvalidValue;
   if ((p.lo_in || p.lo_out) && (epi != EPI_RESIDUAL || p.bias || p.res_mu || !p.resid_bf16 || (p.lo_in && !p.ln_shift_prev) || (p.lo_out && !p.ln_shift)))
@@ -1272,7 +1273,5 @@ const char* gemm_kernel_name(GemmEpi epi) {
   return epi >= 0 && epi < EPI_COUNT ? names[epi] : "?";
 }
 
-unsigned gemm_f16_saturated(bool reset) { return f16_sat_take(reset); }
-unsigned* gemm_f16_flag_address() { return f16_sat_flag_address(); }
 
 }  // namespace vrag

@@ -13,18 +13,19 @@ hipError_t launch_embed_ln(const int* ids, const float* E, const float* w, float
                            float* h, bf16_t* a, hipStream_t stream, const float* P = nullptr,
                            const int* pos = nullptr, const float* type_row = nullptr, const float* bias = nullptr,
                            const int* type_ids = nullptr,    // type_ids: per-token row of the table at type_row
-                           int op_dtype = kOpBf16);          // what `a` holds (kOpBf16 / kOpF16)
+                           int op_dtype = kOpBf16,           // what `a` holds (kOpBf16 / kOpF16)
+                           unsigned* f16_sat = nullptr);     // clamp word (GemmParams::f16_sat); required for kOpF16
 
 // out = LN(h) * w (+ bias); writes bf16 and/or fp32 (either pointer may be null; out_f32 may be h itself).
 // w == nullptr: no gain (it is folded into the consumer GEMM's weight); row_mean != nullptr: also mean(h[row]).
 // op_dtype: what out_bf16 holds (kOpBf16 / kOpF16); out_lo != nullptr: also the remainder  x - float(out_bf16)  in the
 // same type (the split-operand head GEMM multiplies both parts).  gelu_first: h is a raw dense output, gelu_erf is applied
 // before the normalisation.  split3: out_bf16 is a [rows, 3H] image [hi | lo | hi] (out_lo must be null): the A operand of a
-// K = 3H split-operand GEMM.
+// K = 3H split-operand GEMM.  f16_sat: clamp word (GemmParams::f16_sat); required for kOpF16.
 hipError_t launch_layernorm(const float* h, const float* w, float eps, int H, int rows,
                             bf16_t* out_bf16, float* out_f32, hipStream_t stream, const float* bias = nullptr,
                             float* row_mean = nullptr, int op_dtype = kOpBf16, bf16_t* out_lo = nullptr, int gelu_first = 0,
-                            int split3 = 0);
+                            int split3 = 0, unsigned* f16_sat = nullptr);
 
 // For each range r: v = mean_{t in [start[r], end[r]]} LN(h[t]) * lnw   (inclusive token range; lnw == nullptr:
 // no LayerNorm, v = mean of h -- post-LN encoders)
@@ -55,9 +56,5 @@ hipError_t launch_pooler_classifier(const float* h, int H, const int* first_row,
 hipError_t launch_seq_head(const float* h, const float* lnw, float eps, int H, const int* seq_row, const int* seq_len,
                            int n_seqs, int pool_mean, float* pooled, const float* WdT, const float* bd, const float* wn,
                            const float* bn, const float* Wc, const float* bc, int num_labels, float* logits, hipStream_t stream);
-
-// 1 if an fp32 -> fp16 operand conversion in this file's kernels clamped since the last reset (common.h).
-unsigned norm_heads_f16_saturated(bool reset);
-unsigned* norm_heads_f16_flag_address();   // device address of this file's flag on the current device (common.h)
 
 }  // namespace vrag

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int* __restrict__ i
                                                         const float* __restrict__ P, const int* __restrict__ pos,
                                                         const float* __restrict__ type_row,
                                                         const float* __restrict__ bias,
-                                                        const int* __restrict__ type_ids) {
+                                                        const int* __restrict__ type_ids, unsigned* f16_sat) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int* __restrict__ i
       *reinterpret_cast<f32x4*>(h + (size_t)row * H + c) = x[i];
       typename Op<T>::v4 o;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = Op<T>::to(x[i][j]);
+      for (int j = 0; j < 4; ++j) o[j] = Op<T>::to(x[i][j], f16_sat);
       *reinterpret_cast<typename Op<T>::v4*>(a + (size_t)row * H + c) = o;
     }
   }
@@ -106,7 +106,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* h, const fl
                                                          float eps, int H, int rows, bf16_t* __restrict__ ob,
                                                          float* of, const float* __restrict__ bias,
                                                          float* __restrict__ row_mean, bf16_t* __restrict__ ob_lo,
-                                                         int gelu_first, int split3) {
+                                                         int gelu_first, int split3, unsigned* f16_sat) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
@@ -137,8 +137,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* h, const fl
         typename Op<T>::v4 o, lo;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          o[j] = Op<T>::to(x[i][j]);
-          lo[j] = Op<T>::to(x[i][j] - (float)o[j]);   // remainder: x = o + lo to twice the operand precision
+          o[j] = Op<T>::to(x[i][j], f16_sat);
+          lo[j] = Op<T>::to(x[i][j] - (float)o[j], f16_sat);   // remainder: x = o + lo to twice the operand precision
         }
         *reinterpret_cast<typename Op<T>::v4*>(ob + (size_t)row * ld + c) = o;
         if (split3) {
@@ -447,29 +447,31 @@ __global__ __launch_bounds__(256) void seq_head_kernel(const float* __restrict__
 
 hipError_t launch_embed_ln(const int* ids, const float* E, const float* w, float eps, int H, int rows, float* h,
                            bf16_t* a, hipStream_t stream, const float* P, const int* pos, const float* type_row,
-                           const float* bias, const int* type_ids, int op_dtype) {
+                           const float* bias, const int* type_ids, int op_dtype, unsigned* f16_sat) {
+  if (op_dtype == kOpF16 && !f16_sat) return hipErrorInvalidValue;
   if (rows <= 0) return hipSuccess;
   if (H > MAXV * 256 || (H & 3) || (P && !pos)) return hipErrorInvalidValue;
   if (op_dtype == kOpF16)
     hipLaunchKernelGGL(embed_ln_kernel<f16_t>, dim3((rows + 3) / 4), dim3(256), 0, stream, ids, E, w, eps, H, rows, h, a, P, pos,
-                       type_row, bias, type_ids);
+                       type_row, bias, type_ids, f16_sat);
   else
     hipLaunchKernelGGL(embed_ln_kernel<bf16_t>, dim3((rows + 3) / 4), dim3(256), 0, stream, ids, E, w, eps, H, rows, h, a, P, pos,
-                       type_row, bias, type_ids);
+                       type_row, bias, type_ids, f16_sat);
   return hipGetLastError();
 }
 
 hipError_t launch_layernorm(const float* h, const float* w, float eps, int H, int rows, bf16_t* ob, float* of,
                             hipStream_t stream, const float* bias, float* row_mean, int op_dtype, bf16_t* ob_lo, int gelu_first,
-                            int split3) {
+                            int split3, unsigned* f16_sat) {
+  if (op_dtype == kOpF16 && !f16_sat) return hipErrorInvalidValue;
   if (rows <= 0) return hipSuccess;
   if (H > MAXV * 256 || (H & 3) || (split3 && (!ob || ob_lo))) return hipErrorInvalidValue;
   if (op_dtype == kOpF16)
     hipLaunchKernelGGL(layernorm_kernel<f16_t>, dim3((rows + 3) / 4), dim3(256), 0, stream, h, w, eps, H, rows, ob, of, bias, row_mean, ob_lo,
-                       gelu_first, split3);
+                       gelu_first, split3, f16_sat);
   else
     hipLaunchKernelGGL(layernorm_kernel<bf16_t>, dim3((rows + 3) / 4), dim3(256), 0, stream, h, w, eps, H, rows, ob, of, bias, row_mean, ob_lo,
-                       gelu_first, split3);
+                       gelu_first, split3, f16_sat);
   return hipGetLastError();
 }
 
@@ -516,7 +518,5 @@ hipError_t launch_seq_head(const float* h, const float* lnw, float eps, int H, c
   return hipGetLastError();
 }
 
-unsigned norm_heads_f16_saturated(bool reset) { return f16_sat_take(reset); }
-unsigned* norm_heads_f16_flag_address() { return f16_sat_flag_address(); }
 
 }  // namespace vrag

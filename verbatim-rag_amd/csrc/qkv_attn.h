@@ -27,6 +27,7 @@ struct QkvAttnParams {
   int op_dtype;
   float q_scale;           // head_dim^-1/2 * log2(e): the softmax runs in exp2 units
   int debug_flags;         // tuning probe (vrag_debug_qkv_attn_ms): 1 = no attention phase, 2 = no main-loop MFMAs, 4 = no operand DMA
+  unsigned* f16_sat;       // clamp word (GemmParams::f16_sat); required for kOpF16
 };
 
 hipError_t launch_qkv_attention(const QkvAttnParams& p, bool local, hipStream_t stream);
@@ -38,8 +39,5 @@ int fused_pack_groups(const int* seq_row, const int* seq_len, int seq0, int seq1
 
 // out[(h * 3 + part) * 64 + d][:] = w[part * H + h * 64 + d][:]  (and the same for the optional row-sum / bias vectors)
 hipError_t permute_qkv_heads(const bf16_t* w, const float* s, int H, int nh, bf16_t* w_out, float* s_out, hipStream_t stream);
-
-unsigned qkv_attn_f16_saturated(bool reset);
-unsigned* qkv_attn_f16_flag_address();   // device address of this file's flag on the current device (common.h)
 
 }  // namespace vrag

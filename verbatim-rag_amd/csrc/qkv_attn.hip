@@ -254,7 +254,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
           const f32x2 v = pk_fma(f32x2{-m4[r0], -m4[r0 + 1]}, splat2(lsv), f32x2{acc[8 + db][rt][r0], acc[8 + db][rt][r0 + 1]}) * f32x2{r4[r0], r4[r0 + 1]};
 #pragma unroll
           for (int e = 0; e < 2; ++e)   // keys past the end are masked to probability 0: their V must be a finite number for 0 * v to stay 0
-            vv[a * 4 + r0 + e] = qrow0 + rt * 16 + 4 * g + r0 + e < S ? Op<T>::to(v[e]) : (T)0.f;
+            vv[a * 4 + r0 + e] = qrow0 + rt * 16 + 4 * g + r0 + e < S ? Op<T>::to(v[e], p.f16_sat) : (T)0.f;
         }
       }
       const int c = wave * 8 + tp * 4 + g;   // 16-byte chunk of the row: keys 64 w + 32 tp .. + 31, slot order (see top)
@@ -297,11 +297,11 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           if constexpr (!std::is_same<T, bf16_t>::value) {
-            out[0][np * 4 + j0 + e] = live ? Op<T>::to(o1[e]) : (T)0.f;
-            out[1][np * 4 + j0 + e] = live ? Op<T>::to(o2[e]) : (T)0.f;
+            out[0][np * 4 + j0 + e] = live ? Op<T>::to(o1[e], p.f16_sat) : (T)0.f;
+            out[1][np * 4 + j0 + e] = live ? Op<T>::to(o2[e], p.f16_sat) : (T)0.f;
           } else {
-            out[0][np * 4 + j0 + e] = Op<T>::to(o1[e]);
-            out[1][np * 4 + j0 + e] = Op<T>::to(o2[e]);
+            out[0][np * 4 + j0 + e] = Op<T>::to(o1[e], p.f16_sat);
+            out[1][np * 4 + j0 + e] = Op<T>::to(o2[e], p.f16_sat);
           }
         }
       }
@@ -487,7 +487,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
       for (int db = 0; db < 4; ++db) {
         V4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = live ? Op<T>::to(ot[rt][db][j] * inv) : (T)0.f;
+        for (int j = 0; j < 4; ++j) o[j] = live ? Op<T>::to(ot[rt][db][j] * inv, p.f16_sat) : (T)0.f;
         const int c16 = db * 2 + (g >> 1);
         *reinterpret_cast<V4*>(stg + row * 128 + ((c16 ^ (row & 7)) << 4) + ((g & 1) << 3)) = o;
       }
@@ -512,6 +512,7 @@ static hipError_t launch_t(const QkvAttnParams& p, hipStream_t stream) {
 }
 
 hipError_t launch_qkv_attention(const QkvAttnParams& p, bool local, hipStream_t stream) {
+  if (p.op_dtype == kOpF16 && !p.f16_sat) return hipErrorInvalidValue;
   if (p.n_groups <= 0) return hipSuccess;
   if (p.H % 64 != 0 || p.H != p.nh * 64 || (size_t)p.Tp * p.H >= (size_t)1 << 31) return hipErrorInvalidValue;
   const bool fold = p.ln_mu != nullptr;
@@ -552,7 +553,5 @@ int fused_pack_groups(const int* seq_row, const int* seq_len, int seq0, int seq1
   return n;
 }
 
-unsigned qkv_attn_f16_saturated(bool reset) { return f16_sat_take(reset); }
-unsigned* qkv_attn_f16_flag_address() { return f16_sat_flag_address(); }
 
 }  // namespace vrag

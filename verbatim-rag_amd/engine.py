@@ -189,9 +189,10 @@ class EncoderEngine:
         return int(n.value), int(c.value)
 
     def f16_saturated(self, reset: bool = True) -> bool:
-        """True when an fp32 -> fp16 operand conversion on this device had to clamp to +-65504 since the last reset
-        (`vrag_encoder_f16_saturated`): the logits computed meanwhile are not to be trusted -- use bf16 operands for
-        that checkpoint.  Always False for bf16 handles' own work (they never convert to fp16).  Synchronises."""
+        """True when an fp32 -> fp16 operand conversion of this engine had to clamp to +-65504 since the last reset
+        (`vrag_encoder_f16_saturated`; per engine: other engines on the device neither see nor clear it): the logits
+        computed meanwhile are not to be trusted -- use bf16 operands for that checkpoint.  Always False for bf16
+        engines (they never convert to fp16).  Synchronises."""
         v = C.c_int32(0)
         _lib.check("vrag_encoder_f16_saturated", self._lib.vrag_encoder_f16_saturated(self._h, 1 if reset else 0, C.byref(v)))
         return bool(v.value)
