@@ -286,3 +286,89 @@ def test_from_directory_end_to_end(tmp_path, golden):
         assert [r.id for r in got[:6]] == [res[i].id for i in np.argsort(-ref, kind="stable")]
     finally:
         rr.engine.close()
+
+
+# x3000 on three GeGLU channel pairs of layer 1, as tests/test_heads_gpu.py::_hot_weights.  Measured on this encoder (MI355X, the
+# six golden pairs): x300 does not clamp, x1000 does (fp16 logits 6.7e-2 from the bf16 engine's), x3000 clamps with 1.2e-1 --
+# three times past the first scale that leaves fp16's range; bf16 logits stay finite up to x30000.
+HOT_SCALE = 3000.0
+
+
+def _hot_fixture(golden, scale=HOT_SCALE):
+    """The golden checkpoint with outlier channels: rows c (gelu input) and I + c (gate) of layer 1's Wi scaled, so
+    gelu(x1) * x2 leaves fp16's range.  -> (encoder weights, fixture for SH.write_checkpoint)."""
+    I = golden["cfg"].intermediate_size
+    enc = {k: v.copy() for k, v in golden["encoder"].items()}
+    wi = enc["layers.1.mlp.Wi.weight"]                         # [2I, H]
+    assert wi.shape[0] == 2 * I
+    for c in (3, 77, 120):
+        wi[c] *= scale
+        wi[I + c] *= scale
+    m = dict(golden["models"]["mean"])
+    m["state_dict"] = {**m["state_dict"], "model.layers.1.mlp.Wi.weight": wi}
+    return enc, {**golden, "encoder": enc, "models": {"mean": m}}
+
+
+def test_fp16_reranker_rebuilds_with_bf16_operands_or_raises(tmp_path, golden, caplog):
+    """A cross-encoder with fp16 operands on a checkpoint whose activations leave fp16's range must not return clamped
+    scores: built `from_directory` it switches itself to bf16 operands and scores like a reranker built with bf16; handed
+    its engine it raises.  First the premise on a bare engine -- the clamp is reported and the logits are wrong."""
+    import logging
+
+    from verbatim_rag_amd.engine import EncoderEngine
+    from verbatim_rag_amd.rerankers import GpuCrossEncoderReranker
+
+    enc, hot = _hot_fixture(golden)
+    m = hot["models"]["mean"]
+
+    def bare(dtype):
+        eng = EncoderEngine(_shape(golden["cfg"]), enc, max_tokens=16384, max_seqs=64, max_seq_len=1024, max_ranges=64,
+                            operand_dtype=dtype)
+        _set(eng, m)
+        return eng
+
+    e16, ebf = bare("f16"), bare("bf16")
+    try:
+        lg16, lgbf = e16.pair_logits(golden["ids"]), ebf.pair_logits(golden["ids"])
+        flag16, flagbf = e16.f16_saturated(reset=True), ebf.f16_saturated(reset=True)
+        print("hot checkpoint x%g: f16 clamp %s, bf16 clamp %s, max |f16 - bf16| = %.3e, bf16 finite %s"
+              % (HOT_SCALE, flag16, flagbf, float(np.abs(lg16 - lgbf).max()), bool(np.isfinite(lgbf).all())))
+        assert flag16 and not flagbf and np.isfinite(lgbf).all()
+        assert np.abs(lg16 - lgbf).max() > 1e-2                # the clamped run really was wrong, not just flagged
+    finally:
+        ebf.close()
+
+    rng = np.random.default_rng(23)
+    qs = [_text(rng, int(rng.integers(2, 8))) for _ in range(3)]
+    res = [_results(rng, 8, 10, 120) for _ in qs]
+    texts = [r.text for r in res[0]]
+    try:                                                       # handed its engine: nothing to rebuild from
+        with pytest.raises(RuntimeError, match="saturated"):
+            GpuCrossEncoderReranker(e16, _tokenizer(), max_length=1024).score(qs[0], texts)
+    finally:
+        e16.close()
+
+    d = str(tmp_path)
+    SH.write_checkpoint(d, hot, "mean")
+    made = []
+    try:
+        rr_bf = GpuCrossEncoderReranker.from_directory(d, operand_dtype="bf16")
+        made.append(rr_bf)
+        for call in ("score", "rerank_batch"):                 # a fresh fp16 reranker each: the first clamp swaps for good
+            rr = GpuCrossEncoderReranker.from_directory(d, operand_dtype="f16")
+            made.append(rr)
+            assert rr.engine.operand_dtype == "f16"
+            caplog.clear()
+            with caplog.at_level(logging.WARNING):
+                if call == "score":
+                    assert rr.score(qs[0], texts) == rr_bf.score(qs[0], texts)
+                else:
+                    got, want = rr.rerank_batch(qs, res), rr_bf.rerank_batch(qs, res)
+                    assert [[r.id for r in x] for x in got] == [[r.id for r in x] for x in want]
+                    assert rr.score_batch(qs, [[r.text for r in rs] for rs in res]) == \
+                        rr_bf.score_batch(qs, [[r.text for r in rs] for rs in res])
+            assert rr.engine.operand_dtype == "bf16" and any("saturated" in r.getMessage() for r in caplog.records)
+            assert rr._checked.locks == [rr.engine.lock]
+    finally:
+        for rr in made:
+            rr.engine.close()

@@ -12,14 +12,14 @@ embedding_providers.py:55,120; head_dim 64, or 32 as in the default dense model 
 """
 from __future__ import annotations
 
-import threading
 from abc import ABC, abstractmethod
 from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 
 from ._lib import VragError
-from .packing import TokenizerAdapter
+from .checked_engine import CheckedEngines, greedy_batches
+from .packing import TokenizerAdapter, load_tokenizer
 
 
 class DenseEmbeddingProvider(ABC):
@@ -56,48 +56,30 @@ class _EncoderProvider:
     to end against the fp32 oracle, BERT-base width: SPLADE weights 1.6e-3 (fp16) vs 1.3e-2 (bf16), dense rows 6e-5 (fp16)
     (tests/test_splade_real_vocab_gpu.py, tests/test_e2e_text_in_gpu.py).  fp16 saturates at 65504 instead of overflowing: the
     library reports every clamp, and on the first report the provider rebuilds its engine with bf16 operands (fp32's exponent
-    range) and runs the batch again -- `operand_dtype="bf16"` skips the probe; a provider that was HANDED its engine raises."""
+    range) and runs the batch again -- `operand_dtype="bf16"` skips the probe; a provider that was HANDED its engine raises
+    (the rule lives in checked_engine.py: every device batch goes through `self._checked.run`)."""
 
     def __init__(self, engine: Any, tokenizer: Any, max_length: int = 512):
-        self.engine = engine
         self.tokenizer = tokenizer
-        self.max_length = min(max_length, engine.max_seq_len)
-        self._tok = TokenizerAdapter.for_model(tokenizer, engine.shape)
-        self._lock = getattr(engine, "lock", None) or threading.Lock()   # the handle's own lock: wrappers may share it
-        self._rebuild_bf16 = None      # set by from_directory: () -> a bf16 engine of the same checkpoint
+        self._max_length = max_length
+        self._checked = CheckedEngines([engine], on_swap=self._bind)    # from_directory adds the bf16 rebuild
+        self._bind()
 
-    def _f16_clamped(self) -> bool:
-        """True = the engine was swapped for a bf16 one and the caller must run its batch again (caller holds the lock)."""
-        eng = self.engine
-        if getattr(eng, "operand_dtype", "bf16") != "f16" or not hasattr(eng, "f16_saturated") or not eng.f16_saturated(reset=True):
-            return False
-        if self._rebuild_bf16 is None:
-            raise RuntimeError("fp16 MFMA operands saturated on this checkpoint (activations beyond 65504): "
-                               "build the engine with operand_dtype='bf16'")
-        import logging
-
-        logging.getLogger(__name__).warning("fp16 MFMA operands saturated (activations beyond 65504): switching this provider to bf16 "
-                                            "operands (construct it with operand_dtype='bf16' to skip the probe)")
-        old, self.engine = self.engine, self._rebuild_bf16()
-        self._rebuild_bf16 = None
-        old.close()
-        return True
+    def _bind(self) -> None:
+        """What the provider keeps of its engine; derived again when the engine is replaced."""
+        self.engine = self._checked.engines[0]
+        self.max_length = min(self._max_length, self.engine.max_seq_len)
+        self._tok = TokenizerAdapter.for_model(self.tokenizer, self.engine.shape)
 
     def _encode(self, texts: Sequence[str]) -> List[List[int]]:
         return [self._tok.ids(t, add_special_tokens=True, max_length=self.max_length) for t in texts]
 
     def _batches(self, seqs: List[List[int]]):
-        start = 0
-        while start < len(seqs):
-            tok, end = 0, start
-            while end < len(seqs) and end - start < self.engine.max_seqs and end - start < self.engine.max_ranges \
-                    and tok + len(seqs[end]) <= self.engine.max_tokens:
-                tok += len(seqs[end])
-                end += 1
-            if end == start:
+        eng = self.engine
+        for a, b in greedy_batches([len(s) for s in seqs], eng.max_seqs, eng.max_tokens, eng.max_ranges):
+            if a == b:
                 raise ValueError("a single text exceeds the engine workspace")
-            yield start, end
-            start = end
+            yield a, b
 
 
 def load_encoder_directory(model_path: str, device: int = 0, max_tokens: int = 65536, max_seqs: int = 512,
@@ -136,15 +118,16 @@ def load_encoder_directory(model_path: str, device: int = 0, max_tokens: int = 6
                              pooling=seq_head["pooling"])
     else:
         raise ValueError(f"{model_path}: model_type {model_type!r} is not bert / distilbert / modernbert")
-    try:
-        from transformers import AutoTokenizer
+    return eng, load_tokenizer(model_path), cfg
 
-        tokenizer = AutoTokenizer.from_pretrained(model_path)
-    except Exception:
-        from tokenizers import Tokenizer
 
-        tokenizer = Tokenizer.from_file(os.path.join(model_path, "tokenizer.json"))
-    return eng, tokenizer, cfg
+def load_checked_directory(model_path: str, **load_kw):
+    """(engine, tokenizer, rebuild) for a wrapper's `from_directory`: `load_encoder_directory` plus the `rebuild` that
+    `CheckedEngines` takes -- the same checkpoint with bf16 operands, or None when the engine has no fp16 operands to clamp."""
+    engine, tokenizer, _cfg = load_encoder_directory(model_path, **load_kw)
+    if getattr(engine, "operand_dtype", "bf16") != "f16":
+        return engine, tokenizer, None
+    return engine, tokenizer, lambda: load_encoder_directory(model_path, **{**load_kw, "operand_dtype": "bf16"})[0]
 
 
 def _modernbert_seq_head(model_path: str, cfg: dict) -> Optional[dict]:
@@ -193,24 +176,23 @@ class GpuSpladeProvider(_EncoderProvider, SparseEmbeddingProvider):
     @classmethod
     def from_directory(cls, model_path: str, device: int = 0, max_length: int = 512, operand_dtype: str = "f16", **kw) -> "GpuSpladeProvider":
         """`SpladeProvider(model_name, device)` (embedding_providers.py:120-133) for a checkpoint on disk."""
-        engine, tokenizer, _cfg = load_encoder_directory(model_path, device=device, max_seq_len=max_length, operand_dtype=operand_dtype)
+        engine, tokenizer, rebuild = load_checked_directory(model_path, device=device, max_seq_len=max_length, operand_dtype=operand_dtype)
         self = cls(engine, tokenizer, max_length=max_length, **kw)
-        if operand_dtype == "f16":
-            self._rebuild_bf16 = lambda: load_encoder_directory(model_path, device=device, max_seq_len=max_length, operand_dtype="bf16")[0]
+        self._checked.rebuild = rebuild
         return self
 
     def _rows(self, texts: Sequence[str]) -> np.ndarray:
         seqs = self._encode(texts)
         out = np.empty((len(seqs), self.engine.shape.vocab_size), np.float32)
-        with self._lock:
-            for a, b in self._batches(seqs):
-                while True:
-                    self.engine.load_batch(seqs[a:b])
-                    self.engine.run()
-                    self.engine.run_splade()
-                    out[a:b] = self.engine.read_splade()
-                    if not self._f16_clamped():
-                        break
+
+        def rows(engine, a, b):
+            engine.load_batch(seqs[a:b])
+            engine.run()
+            engine.run_splade()
+            return engine.read_splade()
+
+        for a, b in self._batches(seqs):
+            out[a:b] = self._checked.run(lambda engine: rows(engine, a, b))
         return out
 
     def _dicts(self, texts: Sequence[str], threshold: float) -> List[Dict[int, float]]:
@@ -218,28 +200,28 @@ class GpuSpladeProvider(_EncoderProvider, SparseEmbeddingProvider):
         entries (e.g. an untrained model) falls back to the dense read for that batch."""
         seqs = self._encode(texts)
         out: List[Dict[int, float]] = []
-        with self._lock:
-            for a, b in self._batches(seqs):
-                while True:
-                    self.engine.load_batch(seqs[a:b])
-                    self.engine.run()
-                    self.engine.run_splade()
-                    part: List[Dict[int, float]] = []
-                    try:
-                        counts, idx, val = self.engine.read_splade_sparse(threshold, self.sparse_cap)
-                        for i in range(b - a):
-                            n = int(counts[i])
-                            part.append(dict(zip(idx[i, :n].tolist(), val[i, :n].tolist())))
-                    except VragError as exc:
-                        if exc.status != -3:   # VRAG_ERR_CAPACITY
-                            raise
-                        rows = self.engine.read_splade()
-                        for row in rows:
-                            nz = np.nonzero(row > threshold)[0]
-                            part.append({int(i): float(row[i]) for i in nz})
-                    if not self._f16_clamped():
-                        break
-                out.extend(part)
+
+        def dicts(engine, a, b):
+            engine.load_batch(seqs[a:b])
+            engine.run()
+            engine.run_splade()
+            part: List[Dict[int, float]] = []
+            try:
+                counts, idx, val = engine.read_splade_sparse(threshold, self.sparse_cap)
+                for i in range(b - a):
+                    n = int(counts[i])
+                    part.append(dict(zip(idx[i, :n].tolist(), val[i, :n].tolist())))
+            except VragError as exc:
+                if exc.status != -3:   # VRAG_ERR_CAPACITY
+                    raise
+                rows = engine.read_splade()
+                for row in rows:
+                    nz = np.nonzero(row > threshold)[0]
+                    part.append({int(i): float(row[i]) for i in nz})
+            return part
+
+        for a, b in self._batches(seqs):
+            out.extend(self._checked.run(lambda engine: dicts(engine, a, b)))
         return out
 
     def embed_text(self, text: str) -> Dict[int, float]:
@@ -271,27 +253,26 @@ class GpuDenseProvider(_EncoderProvider, DenseEmbeddingProvider):
                        normalize: bool = True, operand_dtype: str = "f16") -> "GpuDenseProvider":
         """`SentenceTransformersProvider(model_name, device)` (embedding_providers.py:55-71) for a checkpoint on disk;
         the pooling mode comes from the checkpoint's `1_Pooling/config.json` unless given."""
-        engine, tokenizer, _cfg = load_encoder_directory(model_path, device=device, max_seq_len=max_length, operand_dtype=operand_dtype)
+        engine, tokenizer, rebuild = load_checked_directory(model_path, device=device, max_seq_len=max_length, operand_dtype=operand_dtype)
         self = cls(engine, tokenizer, pooling=pooling or _st_pooling_mode(model_path), normalize=normalize, max_length=max_length)
-        if operand_dtype == "f16":
-            self._rebuild_bf16 = lambda: load_encoder_directory(model_path, device=device, max_seq_len=max_length, operand_dtype="bf16")[0]
+        self._checked.rebuild = rebuild
         return self
 
     def _rows(self, texts: Sequence[str]) -> np.ndarray:
         seqs = self._encode(texts)
         out = np.empty((len(seqs), self.engine.shape.hidden_size), np.float32)
-        with self._lock:
-            for a, b in self._batches(seqs):
-                while True:
-                    self.engine.load_batch(seqs[a:b])
-                    n = b - a
-                    ends = [0] * n if self.pooling == "cls" else [len(s) - 1 for s in seqs[a:b]]
-                    self.engine.load_ranges(list(range(n)), [0] * n, ends)
-                    self.engine.run()
-                    self.engine.run_pool(self.normalize)
-                    out[a:b] = self.engine.read_pool()
-                    if not self._f16_clamped():
-                        break
+
+        def rows(engine, a, b):
+            engine.load_batch(seqs[a:b])
+            n = b - a
+            ends = [0] * n if self.pooling == "cls" else [len(s) - 1 for s in seqs[a:b]]
+            engine.load_ranges(list(range(n)), [0] * n, ends)
+            engine.run()
+            engine.run_pool(self.normalize)
+            return engine.read_pool()
+
+        for a, b in self._batches(seqs):
+            out[a:b] = self._checked.run(lambda engine: rows(engine, a, b))
         return out
 
     def embed_text(self, text: str) -> List[float]:

@@ -20,14 +20,17 @@ import threading
 import time
 from abc import ABC, abstractmethod
 from concurrent.futures import Future
+from functools import partial
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .checked_engine import CheckedEngines, greedy_batches
 from .packing import (
     PackedSample,
     TokenizerAdapter,
     encode_question_and_sentences,
+    load_tokenizer,
     split_into_sentences,
     split_into_sentences_batch,
     valid_boundaries,
@@ -147,7 +150,10 @@ class GpuModelSpanExtractor(SpanExtractor):
     ):
         """operand_dtype: MFMA operand type of the engines this extractor builds (`EncoderEngine`): None picks "bf16" for
         the sentence-classifier format (sentence logits within 3e-4 of the fp32 reference) and "f16" for the v2 highlighter,
-        whose per-token logits need the three extra mantissa bits to stay within 1e-3."""
+        whose per-token logits need the three extra mantissa bits to stay within 1e-3.  fp16 operands saturate at 65504: every
+        device batch runs through `CheckedEngines.run` (checked_engine.py), which on the first clamp report replaces the
+        engines this extractor built by bf16 ones and runs the batch again; an extractor that was handed its engine raises,
+        which the per-chunk error handling turns into "log, no spans" -- never silently wrong."""
         self.operand_dtype = operand_dtype
         self.model_path = model_path
         self.threshold = threshold
@@ -158,7 +164,6 @@ class GpuModelSpanExtractor(SpanExtractor):
         self.qa_max_length = qa_max_length
         self.max_batch_tokens = max_batch_tokens
         self.max_batch_seqs = max_batch_seqs
-        self._lock = threading.Lock()  # callers arrive from asyncio.to_thread workers (extractors.py:54)
         # chunk text -> (sentences, per-sentence token ids): chunk texts are known at ingest and recur across
         # queries, and the reference's per-query tokenisation (2.7 ms/chunk) would cap the GPU path
         self._chunk_cache: Dict[str, tuple] = {}   # text -> _cache_entry
@@ -171,7 +176,7 @@ class GpuModelSpanExtractor(SpanExtractor):
         if engine is not None:
             if tokenizer is None:
                 raise ValueError("engine= needs tokenizer=")
-            self.engine = engine
+            engines, rebuild = [engine, *extra_engines], None
             self._format = model_format or (
                 self._FORMAT_HIGHLIGHTER if getattr(engine, "token_labels", 0) and not getattr(engine, "qa_labels", 0)
                 else self._FORMAT_QA_MODEL)
@@ -181,17 +186,15 @@ class GpuModelSpanExtractor(SpanExtractor):
                     f"model_path={model_path!r}: a local HF checkpoint directory is required (no network here); "
                     "or pass engine= and tokenizer=")
             self._format = model_format or self._detect_format(model_path)
-            self.engine = self._build_engine(model_path, dev)
-            tokenizer = tokenizer or self._load_tokenizer(model_path)
-            extra_engines = [self._build_engine(model_path, dev) for _ in range(max(1, int(n_engines)) - 1)]
-        # Further handles of the same model (own weights copy + workspace + streams): a multi-sub-batch call alternates
-        # between them from worker threads, so one handle's upload / read-back / host turnaround hides behind the
-        # other's kernels (measured 0.42 -> 0.33 s for 5000 pairs, DESIGN.md "Serving shape").
-        self.engines = [self.engine] + list(extra_engines)
-        self._locks = [getattr(e, "lock", None) or threading.Lock() for e in self.engines]   # a handle's own lock: wrappers may share it
-        self._lock = self._locks[0]
+            # Further handles of the same model (own weights copy + workspace + streams): a multi-sub-batch call alternates
+            # between them from worker threads, so one handle's upload / read-back / host turnaround hides behind the
+            # other's kernels (measured 0.42 -> 0.33 s for 5000 pairs, DESIGN.md "Serving shape").
+            engines = [self._build_engine(model_path, dev) for _ in range(max(1, int(n_engines)))]
+            rebuild = partial(self._build_engine, model_path, dev, "bf16")
+            tokenizer = tokenizer or load_tokenizer(model_path)
         self.tokenizer = tokenizer
-        self._tok = TokenizerAdapter.for_model(tokenizer, self.engine.shape)
+        self._checked = CheckedEngines(engines, rebuild, on_swap=self._bind)   # callers arrive from asyncio.to_thread workers
+        self._bind()
         logger.info("GpuModelSpanExtractor ready: format=%s device=%s", self._format, self.device)
 
     # ------------------------------------------------------------------ loading
@@ -209,13 +212,19 @@ class GpuModelSpanExtractor(SpanExtractor):
             logger.warning("Highlighter detection failed for %s: %s", model_path, exc)
         return GpuModelSpanExtractor._FORMAT_QA_MODEL
 
-    def _build_engine(self, model_path: str, dev: int):
+    def _bind(self) -> None:
+        """What the extractor keeps of its engines; derived again when they are replaced."""
+        self.engines = self._checked.engines
+        self.engine = self.engines[0]
+        self._tok = TokenizerAdapter.for_model(self.tokenizer, self.engine.shape)
+
+    def _build_engine(self, model_path: str, dev: int, operand_dtype: Optional[str] = None):
         from .engine import EncoderEngine
         from .weights import load_safetensors_dir
 
         shape, tensors, _cfg = load_safetensors_dir(model_path)
         max_seq = self.qa_max_length if self._format == self._FORMAT_QA_MODEL else self.max_length
-        dtype = self.operand_dtype or ("bf16" if self._format == self._FORMAT_QA_MODEL else "f16")
+        dtype = operand_dtype or self.operand_dtype or ("bf16" if self._format == self._FORMAT_QA_MODEL else "f16")
         eng = EncoderEngine(shape, tensors, max_tokens=self.max_batch_tokens, max_seqs=self.max_batch_seqs,
                             max_seq_len=max_seq, max_ranges=max(4096, self.max_batch_tokens // 8), device=dev,
                             operand_dtype=dtype)
@@ -225,41 +234,6 @@ class GpuModelSpanExtractor(SpanExtractor):
             eng.set_token_head(tensors["head.dense.weight"], tensors["head.norm.weight"],
                                tensors["classifier.weight"], tensors["classifier.bias"])
         return eng
-
-    def _f16_clamped(self, engine) -> bool:
-        """fp16 operands saturate at 65504 instead of overflowing; a checkpoint with activation outliers beyond that
-        would come back with plausible, wrong logits.  The library reports every clamp (`vrag_encoder_f16_saturated`):
-        on the first report the engines this extractor built are rebuilt with bf16 operands (fp32's exponent range)
-        and True is returned -- the caller runs its batch again; an extractor that was handed its engine cannot rebuild
-        it and raises (its per-chunk error handling logs the failure and returns no spans: never silently wrong)."""
-        if getattr(engine, "operand_dtype", "bf16") != "f16" or not hasattr(engine, "f16_saturated") or not engine.f16_saturated(reset=True):
-            return False
-        if self.model_path is None or not os.path.isdir(self.model_path):
-            raise RuntimeError("fp16 MFMA operands saturated on this checkpoint (activations beyond 65504): "
-                               "build the engine with operand_dtype='bf16'")
-        with self._cache_lock:
-            if self.operand_dtype != "bf16":               # the first thread to notice rebuilds; the others just retry
-                logger.warning("fp16 MFMA operands saturated on %s (activations beyond 65504): switching this extractor to "
-                               "bf16 operands (construct it with operand_dtype='bf16' to skip the probe)", self.model_path)
-                dev = int(self.device.replace("cuda:", ""))
-                self.operand_dtype = "bf16"
-                # swapped in as a whole; a call still running on an old handle keeps it alive and finishes on it
-                self.engines = [self._build_engine(self.model_path, dev) for _ in self.engines]
-                self.engine = self.engines[0]
-        return True
-
-    @staticmethod
-    def _load_tokenizer(model_path: str):
-        tj = os.path.join(model_path, "tokenizer.json")
-        try:
-            from transformers import AutoTokenizer
-
-            return AutoTokenizer.from_pretrained(model_path)
-        except Exception as e:  # fall back to the raw tokenizers file
-            logger.warning("AutoTokenizer failed for %s (%s); using tokenizers.Tokenizer", model_path, e)
-            from tokenizers import Tokenizer
-
-            return Tokenizer.from_file(tj)
 
     def _split_into_sentences(self, text: str) -> List[str]:
         return split_into_sentences(text)
@@ -464,34 +438,33 @@ class GpuModelSpanExtractor(SpanExtractor):
 
     def _run_sub_batch(self, batch, out, which: int = 0) -> None:
         """One workspace-sized batch: device logits, softmax, strict `>` threshold (extractors.py:272-275)."""
-        engine = self.engines[which]
-        with self._locks[which]:
-            try:
-                counts = np.asarray([len(b[4]) for b in batch], np.int64)
-                if hasattr(engine, "qa_logits_packed"):
-                    flat = engine.qa_logits_packed(
-                        np.concatenate([b[3] for b in batch]), np.asarray([len(b[3]) for b in batch], np.int32),
-                        np.repeat(np.arange(len(batch), dtype=np.int32), counts),
-                        np.concatenate([b[4] for b in batch]), np.concatenate([b[5] for b in batch]))
-                else:   # engines without the flat entry point
-                    flat = np.concatenate(engine.qa_logits(
-                        [b[3] for b in batch], [list(zip(b[4].tolist(), b[5].tolist())) for b in batch]))
-                if self._f16_clamped(engine):
-                    return self._run_sub_batch(batch, out, which)          # once more, on the bf16 engines
-                keep = softmax_rows(flat)[:, 1] > self.threshold
-                # selected sentences chunk by chunk, from ONE nonzero over the batch's ranges (every chunk starts as [])
-                sel = np.nonzero(keep)[0]
-                ends = np.cumsum(counts)
-                owner = np.searchsorted(ends, sel, side="right")
-                local = sel - (ends - counts)[owner]
-                picked: Dict[int, List[int]] = {}
-                for b, i in zip(owner.tolist(), local.tolist()):
-                    picked.setdefault(b, []).append(i)
-                for b, (qi, text, sents, _ids, _st, _en) in enumerate(batch):   # in batch order: a chunk listed twice keeps its last evaluation
-                    idx = picked.get(b)
-                    out[qi][text] = [sents[i] for i in idx if i < len(sents)] if idx else []
-            except Exception as exc:  # same contract as extractors.py:225-227: log, [] for the chunk(s)
-                logger.error("GPU span extraction failed: %s", exc)
+        counts = np.asarray([len(b[4]) for b in batch], np.int64)
+
+        def logits(engine):
+            if hasattr(engine, "qa_logits_packed"):
+                return engine.qa_logits_packed(
+                    np.concatenate([b[3] for b in batch]), np.asarray([len(b[3]) for b in batch], np.int32),
+                    np.repeat(np.arange(len(batch), dtype=np.int32), counts),
+                    np.concatenate([b[4] for b in batch]), np.concatenate([b[5] for b in batch]))
+            return np.concatenate(engine.qa_logits(   # engines without the flat entry point
+                [b[3] for b in batch], [list(zip(b[4].tolist(), b[5].tolist())) for b in batch]))
+
+        try:
+            flat = self._checked.run(logits, which)
+            keep = softmax_rows(flat)[:, 1] > self.threshold
+            # selected sentences chunk by chunk, from ONE nonzero over the batch's ranges (every chunk starts as [])
+            sel = np.nonzero(keep)[0]
+            ends = np.cumsum(counts)
+            owner = np.searchsorted(ends, sel, side="right")
+            local = sel - (ends - counts)[owner]
+            picked: Dict[int, List[int]] = {}
+            for b, i in zip(owner.tolist(), local.tolist()):
+                picked.setdefault(b, []).append(i)
+            for b, (qi, text, sents, _ids, _st, _en) in enumerate(batch):   # in batch order: a chunk listed twice keeps its last evaluation
+                idx = picked.get(b)
+                out[qi][text] = [sents[i] for i in idx if i < len(sents)] if idx else []
+        except Exception as exc:  # same contract as extractors.py:225-227: log, [] for the chunk(s)
+            logger.error("GPU span extraction failed: %s", exc)
 
     # ------------------------------------------------------------------ v2 highlighter path
     def _encode_windows(self, question: str, context: str):
@@ -544,38 +517,30 @@ class GpuModelSpanExtractor(SpanExtractor):
                     logger.error("Highlighter extraction failed: %s", exc)
         flat = [(ji, w) for ji, job in enumerate(jobs) for w in job[2]]
         probs = [np.zeros(job[4], dtype=np.float32) for job in jobs]
-        with self._lock:
-            start = 0
-            while start < len(flat):
-                tok = 0
-                end = start
-                while end < len(flat) and end - start < self.engine.max_seqs and \
-                        tok + len(flat[end][1][0]) <= self.engine.max_tokens:
-                    tok += len(flat[end][1][0])
-                    end += 1
-                if end == start:
-                    # one window larger than the workspace: this chunk stays without spans, the others go on (the
-                    # reference logs a failing chunk and returns [] for it, extractors.py:225-227)
-                    logger.error("Highlighter extraction failed: a window of %d tokens exceeds the engine workspace "
-                                 "(max_tokens=%d)", len(flat[start][1][0]), self.engine.max_tokens)
-                    start += 1
-                    continue
-                try:
-                    self.engine.load_batch([w[0] for _ji, w in flat[start:end]])
-                    self.engine.run()
-                    self.engine.run_token_head()
-                    logits = self.engine.read_token_logits()
-                    if self._f16_clamped(self.engine):
-                        continue                                # the engines run on bf16 operands now: this batch again
-                    p1 = softmax_rows(logits)[:, 1]
-                    o = 0
-                    for ji, (ids, (a, b), q_len) in flat[start:end]:
-                        seg = p1[o + q_len:o + q_len + (b - a)]
-                        probs[ji][a:b] = np.maximum(probs[ji][a:b], seg)
-                        o += len(ids)
-                except Exception as exc:
-                    logger.error("Highlighter extraction failed: %s", exc)
-                start = end
+        def token_logits(engine, windows):
+            engine.load_batch(windows)
+            engine.run()
+            engine.run_token_head()
+            return engine.read_token_logits()
+
+        eng = self.engine
+        for start, end in greedy_batches([len(w[0]) for _ji, w in flat], eng.max_seqs, eng.max_tokens):
+            if end == start:
+                # one window larger than the workspace: this chunk stays without spans, the others go on (the
+                # reference logs a failing chunk and returns [] for it, extractors.py:225-227)
+                logger.error("Highlighter extraction failed: a window of %d tokens exceeds the engine workspace "
+                             "(max_tokens=%d)", len(flat[start][1][0]), eng.max_tokens)
+                continue
+            try:
+                windows = [w[0] for _ji, w in flat[start:end]]
+                p1 = softmax_rows(self._checked.run(lambda engine: token_logits(engine, windows)))[:, 1]
+                o = 0
+                for ji, (ids, (a, b), q_len) in flat[start:end]:
+                    seg = p1[o + q_len:o + q_len + (b - a)]
+                    probs[ji][a:b] = np.maximum(probs[ji][a:b], seg)
+                    o += len(ids)
+            except Exception as exc:
+                logger.error("Highlighter extraction failed: %s", exc)
         for (qi, context, _w, offsets, _n), p in zip(jobs, probs):
             out[qi][context] = token_spans_to_char_spans(p, offsets, context, self.threshold, self.min_span_chars,
                                                          self.merge_gap_chars)

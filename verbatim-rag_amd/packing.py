@@ -71,6 +71,22 @@ def split_into_sentences_batch(texts: Sequence[str], device: int = 0, cap: int =
     return out
 
 
+def load_tokenizer(model_path: str) -> Any:
+    """The tokenizer of a local HF checkpoint directory: `AutoTokenizer`, or the raw `tokenizers` file when transformers
+    cannot load it (a directory that holds only tokenizer.json)."""
+    import os
+
+    try:
+        from transformers import AutoTokenizer
+
+        return AutoTokenizer.from_pretrained(model_path)
+    except Exception as e:
+        logger.warning("AutoTokenizer failed for %s (%s); using tokenizers.Tokenizer", model_path, e)
+        from tokenizers import Tokenizer
+
+        return Tokenizer.from_file(os.path.join(model_path, "tokenizer.json"))
+
+
 class TokenizerAdapter:
     """Uniform `ids(text, add_special_tokens, max_length)` over a HF fast tokenizer
     (transformers) or a raw `tokenizers.Tokenizer`; truncation like the reference's

@@ -15,9 +15,10 @@ questions' results through shared device batches (the serving path of `StaticVer
 from __future__ import annotations
 
 import asyncio
-import threading
 from abc import ABC, abstractmethod
 from typing import Any, List, Optional, Sequence, Tuple
+
+from .checked_engine import CheckedEngines, greedy_batches
 
 # Longest sequence the fused QKV + attention kernel takes (csrc/qkv_attn.h kFusedMaxSeq): a device batch holding one longer
 # sequence runs every layer on the separate attention kernel, so rerank_batch never mixes the two lengths in one batch.
@@ -73,15 +74,23 @@ def pack_pair(q_ids: Sequence[int], d_ids: Sequence[int], cls_id: int, sep_id: i
 class GpuCrossEncoderReranker(BaseReranker):
     """SentenceTransformersReranker (verbatim_rag/rerankers.py:109-134) on a `BertEncoderEngine` with a pair head or an
     `EncoderEngine` (ModernBERT) with a sequence-classification head: both expose `pair_labels` and
-    `pair_logits(sequences, type_ids)`."""
+    `pair_logits(sequences, type_ids)`.  Every `pair_logits` call goes through `CheckedEngines.run` (checked_engine.py): an
+    fp16 engine that clamped an operand is replaced by a bf16 one and the batch scored again when `from_directory` built
+    it; a reranker that was handed its engine raises instead of returning clamped scores."""
 
     def __init__(self, engine: Any, tokenizer: Any, rerank_k: int = 50, text_field: str = "text", max_length: int = 512):
         super().__init__(rerank_k=rerank_k, text_field=text_field)
         if not getattr(engine, "pair_labels", 0):
             raise ValueError("engine has no pair head (BertForSequenceClassification / ModernBertForSequenceClassification weights)")
-        self.engine, self.tokenizer = engine, tokenizer
-        self.max_length = min(max_length, engine.max_seq_len)
-        self._lock = getattr(engine, "lock", None) or threading.Lock()   # the handle's own lock: wrappers may share it
+        self.tokenizer = tokenizer
+        self._max_length = max_length
+        self._checked = CheckedEngines([engine], on_swap=self._bind)    # from_directory adds the bf16 rebuild
+        self._bind()
+
+    def _bind(self) -> None:
+        """What the reranker keeps of its engine; derived again when the engine is replaced."""
+        self.engine = self._checked.engines[0]
+        self.max_length = min(self._max_length, self.engine.max_seq_len)
 
     @classmethod
     def from_directory(cls, model_path: str, device: int = 0, rerank_k: int = 50, max_length: Optional[int] = None,
@@ -94,7 +103,7 @@ class GpuCrossEncoderReranker(BaseReranker):
         import json
         import os
 
-        from .embedding_providers import load_encoder_directory
+        from .embedding_providers import load_checked_directory
 
         with open(os.path.join(model_path, "config.json")) as f:
             cfg = json.load(f)
@@ -106,8 +115,10 @@ class GpuCrossEncoderReranker(BaseReranker):
             max_length = max_length or 512
             if operand_dtype:
                 load_kw["operand_dtype"] = operand_dtype
-        engine, tokenizer, _cfg = load_encoder_directory(model_path, device=device, max_seq_len=max_length, **load_kw)
-        return cls(engine, tokenizer, rerank_k=rerank_k, max_length=max_length, **kw)
+        engine, tokenizer, rebuild = load_checked_directory(model_path, device=device, max_seq_len=max_length, **load_kw)
+        self = cls(engine, tokenizer, rerank_k=rerank_k, max_length=max_length, **kw)
+        self._checked.rebuild = rebuild
+        return self
 
     def _ids(self, text: str) -> List[int]:
         enc = self.tokenizer.encode(text, add_special_tokens=False)
@@ -118,19 +129,16 @@ class GpuCrossEncoderReranker(BaseReranker):
         sh = self.engine.shape
         packed = [pack_pair(q, self._ids(t), sh.cls_token_id, sh.sep_token_id, self.max_length) for t in texts]
         scores: List[float] = []
-        with self._lock:
-            start = 0
-            while start < len(packed):
-                tok, end = 0, start
-                while end < len(packed) and end - start < self.engine.max_seqs and tok + len(packed[end][0]) <= self.engine.max_tokens:
-                    tok += len(packed[end][0])
-                    end += 1
-                if end == start:
-                    raise ValueError("a single pair exceeds the engine workspace")
-                logits = self.engine.pair_logits([p[0] for p in packed[start:end]], [p[1] for p in packed[start:end]])
-                scores.extend(float(x) for x in logits[:, 0])
-                start = end
+        for start, end in greedy_batches([len(p[0]) for p in packed], self.engine.max_seqs, self.engine.max_tokens):
+            if end == start:
+                raise ValueError("a single pair exceeds the engine workspace")
+            scores.extend(float(x) for x in self._pair_logits(packed, range(start, end))[:, 0])
         return scores
+
+    def _pair_logits(self, packed: List[Tuple[List[int], List[int]]], idx: Sequence[int]):
+        """One device batch, `packed[i] for i in idx`, on the current engine with the fp16 clamp report honoured."""
+        ids, types = [packed[i][0] for i in idx], [packed[i][1] for i in idx]
+        return self._checked.run(lambda engine: engine.pair_logits(ids, types))
 
     def rerank(self, question: str, results: List[Any]) -> List[Any]:
         head, tail = self._split_results(results)
@@ -177,11 +185,9 @@ class GpuCrossEncoderReranker(BaseReranker):
                 packed.append(pack_pair(q, self._ids(t), sh.cls_token_id, sh.sep_token_id, self.max_length))
                 owner.append(qi)
         scores = [0.0] * len(packed)
-        with self._lock:
-            for idx in self._device_batches(packed):
-                logits = self.engine.pair_logits([packed[i][0] for i in idx], [packed[i][1] for i in idx])
-                for i, x in zip(idx, logits[:, 0]):
-                    scores[i] = float(x)
+        for idx in self._device_batches(packed):
+            for i, x in zip(idx, self._pair_logits(packed, idx)[:, 0]):
+                scores[i] = float(x)
         per_q: List[List[float]] = [[] for _ in questions]
         for qi, sc in zip(owner, scores):
             per_q[qi].append(sc)
