@@ -378,8 +378,21 @@ int vrag_text_index_add(vrag_text_index* ix, const uint8_t* text, const int64_t*
 int vrag_text_index_set_live(vrag_text_index* ix, const uint32_t* words, int64_t n_rows);
 int vrag_text_index_stats(vrag_text_index* ix, int64_t* n_rows, int64_t* n_live, int64_t* sum_dl, int64_t* n_segments,
                           int64_t* n_postings /* any may be NULL */);
+/* A shard of a row-sharded corpus (one index per GPU, each holding some of the rows): BM25 needs N, avgdl and df(t) of the
+ * WHOLE corpus.  The caller sums (n_live, sum_dl) of vrag_text_index_stats over the shards and hands the totals back here:
+ * K_d then uses avgdl = fp32(float64(sum_dl_total) / n_live_total) -- the documented formula on the summed integers, hence the
+ * bits a single index over all the rows computes -- and vrag_text_index_query_terms reports n_live_total as N.  df stays this
+ * shard's own (the caller sums the df vectors of the shards; query_terms lists every distinct term of every query, with
+ * df = 0 for terms this shard does not hold, so the vectors of all shards line up).  vrag_text_index_stats keeps reporting
+ * this index's own rows.  (0, 0) returns the index to its own statistics.  The pair survives add, set_live and folds until it
+ * is set again; K_d is recomputed lazily by the statistics pass of the next call that needs it.  With the summed N and df in
+ * the weights and the totals in K_d, a shard scores its rows with the same fp32 operations as the single index: merging the
+ * shards' lists by (score desc, global row asc) reproduces the single index's list bit for bit. */
+int vrag_text_index_set_corpus_stats(vrag_text_index* ix, int64_t n_live_total, int64_t sum_dl_total);
 /* Query analysis on the device: the distinct terms of every query in ascending key order (query q: entries
- * q_indptr[q] .. q_indptr[q+1]) with their count in the query and their df; n_live = N.  VRAG_ERR_CAPACITY beyond cap terms. */
+ * q_indptr[q] .. q_indptr[q+1]) with their count in the query and their df; n_live = N.  VRAG_ERR_CAPACITY beyond cap terms.
+ * Every distinct term is listed whether or not the index holds it (df = 0 then, also on an index without rows): the term
+ * list depends on the query texts alone. */
 int vrag_text_index_query_terms(vrag_text_index* ix, const uint8_t* text, const int64_t* doc_off /*[nq+1]*/, int32_t nq, int64_t cap,
                                 int64_t* q_indptr /*[nq+1]*/, uint64_t* keys /*[cap]*/, int32_t* counts /*[cap]*/, int64_t* df /*[cap]*/,
                                 int64_t* n_live);
@@ -389,6 +402,17 @@ int vrag_text_index_query_terms(vrag_text_index* ix, const uint8_t* text, const 
 int vrag_text_index_search(vrag_text_index* ix, const int64_t* q_indptr /*[nq+1]*/, const uint64_t* keys, const float* weights,
                            int32_t nq, int32_t k, const uint32_t* allow, int64_t allow_rows, float* scores /*[nq,k]*/,
                            int64_t* ids /*[nq,k]*/);
+/* The same search (k <= 64: one device pass) with the result lists left in DEVICE memory, as vrag_dense_index_search_device:
+ * out_ids[q][j] = row_map[row] when `row_map` (device int64[n_map], local row -> global row) is given -- rows at or beyond
+ * n_map become -1 / -inf -- else id_base + row; missing hits -1 / -inf.  Queries, weights and `allow` are host memory (the call
+ * returns once they have been uploaded); the kernels are only enqueued on `stream` (NULL = the legacy default stream): no
+ * device->host copy.  Later calls on this index order themselves behind those kernels: a search before it reuses the
+ * workspace, the statistics pass (which also uploads a liveness change) before it rewrites K_d / the liveness bitmap,
+ * vrag_text_index_add before it replaces segments or per-row arrays, vrag_text_index_destroy before it frees anything. */
+int vrag_text_index_search_device(vrag_text_index* ix, const int64_t* q_indptr /*[nq+1]*/, const uint64_t* keys, const float* weights,
+                                  int32_t nq, int32_t k, const uint32_t* allow, int64_t allow_rows,
+                                  const int64_t* row_map /*device or NULL*/, int64_t n_map, int64_t id_base,
+                                  float* out_scores /*[nq,k] device*/, int64_t* out_ids /*[nq,k] device*/, void* stream);
 
 /* Cross-shard merge of per-shard top-k lists (the reference has no sharding -- this is the step after the
  * all-gather of `[n_lists][nq][k_in]` (fp32 score, global row id) lists, each sorted by (score desc, id asc) with

@@ -138,8 +138,11 @@ SIGNATURES = {
     "vrag_text_index_add": (C.c_int, [_H, C.c_void_p, _LP, C.c_int32, C.c_int32]),
     "vrag_text_index_set_live": (C.c_int, [_H, C.c_void_p, C.c_int64]),
     "vrag_text_index_stats": (C.c_int, [_H, _LP, _LP, _LP, _LP, _LP]),
+    "vrag_text_index_set_corpus_stats": (C.c_int, [_H, C.c_int64, C.c_int64]),
     "vrag_text_index_query_terms": (C.c_int, [_H, C.c_void_p, _LP, C.c_int32, C.c_int64, _LP, C.c_void_p, _IP, _LP, _LP]),
     "vrag_text_index_search": (C.c_int, [_H, _LP, C.c_void_p, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _FP, _LP]),
+    "vrag_text_index_search_device": (C.c_int, [_H, _LP, C.c_void_p, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
+                                                C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vrag_comm_get_unique_id": (C.c_int, [C.c_void_p]),
     "vrag_comm_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_H)]),
     "vrag_comm_destroy": (None, [_H]),

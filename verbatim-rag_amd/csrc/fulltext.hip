@@ -10,9 +10,12 @@
 //                    8 bits per pass) -> run-length encoding (rle_*): sorted unique keys, posting ranges, postings (row, tf)
 //                    in row order.  Segments: main + tail; a fold re-expands segments into records and builds one again.
 //   statistics       live_sum_kernel (N, sum dl over the liveness bitmap), kd_kernel (K_d per row), df_kernel (live rows per key).
+//                    A shard of a row-sharded corpus is handed the corpus-wide (N, sum dl) by its caller
+//                    (vrag_text_index_set_corpus_stats): kd_kernel then reads that pair instead of the shard's own.
 //   search           ft_lookup_kernel (binary search of the query keys in every segment), ft_score_kernel (one workgroup per
 //                    (query, 4096 rows): LDS accumulators, term after term with a barrier between terms, then the block's
-//                    hits sorted in LDS), the per-query merge of csrc/topk.hip; k > 64 as exact pages of 64.
+//                    hits sorted in LDS), the per-query merge of csrc/topk.hip; k > 64 as exact pages of 64;
+//                    ft_export_kernel leaves one page as (score, global row) lists in device memory for the cross-GPU exchange.
 // Integer work and fp32 scores without contraction (#pragma clang fp contract(off) below): the oracle restates them bit for bit.
 #include "../../include/vrag_amd.h"
 
@@ -597,6 +600,23 @@ __global__ void ft_bound_kernel(const u64* __restrict__ page, int nq, int kk, u6
   if (q < nq) bound[q] = page[(size_t)q * kk + kk - 1];
 }
 
+// One page of merged keys as device-resident lists (what a rank contributes to the cross-GPU exchange): fp32 score bits and
+// id = row_map[row] (the caller's local row -> global row table; a row at or beyond n_map is reported as missing) or
+// id_base + row without a table; missing hits -1 / -inf.
+__global__ void ft_export_kernel(const u64* __restrict__ keys, long long n, const long long* __restrict__ row_map, long long n_map,
+                                 long long id_base, float* __restrict__ out_scores, long long* __restrict__ out_ids) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const u64 key = keys[i];
+  long long id = -1ll;
+  if (key != 0ull) {
+    const long long row = (long long)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFu));
+    id = row_map ? (row < n_map ? row_map[row] : -1ll) : id_base + row;
+  }
+  out_scores[i] = id < 0 ? -INFINITY : unorderable((unsigned)(key >> 32));
+  out_ids[i] = id;
+}
+
 }  // namespace vrag
 
 using namespace vrag;
@@ -776,11 +796,14 @@ struct vrag_text_index {
   std::mutex mu;
   std::vector<Segment> segs;   // disjoint, ascending row ranges: main [+ tail]
   long long n_rows = 0;
-  DevBuf dl, live, kd, acc;    // token count / liveness bit / K_d per row; acc = {N, sum dl}
+  DevBuf dl, live, kd, acc;    // token count / liveness bit / K_d per row; acc = {N, sum dl} of this index, then the caller's pair
   size_t rows_cap = 0;
   std::vector<unsigned> h_live;   // host copy of the bitmap
   bool stats_dirty = true;
+  bool kd_dirty = false;          // only K_d is stale (the corpus-wide pair changed)
   unsigned long long h_acc[2] = {0, 0};
+  unsigned long long corpus[2] = {0, 0};   // vrag_text_index_set_corpus_stats: {N, sum dl} of the whole corpus, N = 0 = not set
+  hipEvent_t lists_done = nullptr;   // recorded behind a device-resident search: later work on the workspace / K_d waits for it
   // search workspace
   DevBuf q_indptr, q_keys, q_w, q_tu, cand, page, bound;
   DevBuf allow;
@@ -829,26 +852,38 @@ int fold(const std::vector<const Segment*>& parts, hipStream_t st, Segment& out)
   return build_segment(rec, 0, row_lo, n_rows, st, out);
 }
 
+// The statistics pass.  stats_dirty: N / sum dl / df of this index's live rows and K_d; kd_dirty alone (the caller's
+// corpus-wide pair changed): K_d only.  K_d reads {N, sum dl} from acc[0..1], or from the caller's pair at acc[2..3].
 int refresh_stats(vrag_text_index* ix) {
-  if (!ix->stats_dirty) return VRAG_OK;
+  if (!ix->stats_dirty && !ix->kd_dirty) return VRAG_OK;
   hipStream_t st = ix->stream;
   const long long n = ix->n_rows;
-  HIP_TRY(hipMemsetAsync(ix->acc.p, 0, 16, st));
+  const bool own = ix->stats_dirty;
+  if (ix->lists_done) HIP_TRY(hipStreamWaitEvent(st, ix->lists_done, 0));   // a device-resident search may still be reading K_d
+  if (own) HIP_TRY(hipMemsetAsync(ix->acc.p, 0, 16, st));
+  const unsigned long long* kd_stats = ix->acc.as<unsigned long long>();
+  if (ix->corpus[0]) {
+    HIP_TRY(hipMemcpyAsync(ix->acc.as<unsigned long long>() + 2, ix->corpus, 16, hipMemcpyHostToDevice, st));
+    kd_stats += 2;
+  }
   if (n) {
-    HIP_TRY(hipMemcpyAsync(ix->live.p, ix->h_live.data(), ix->h_live.size() * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(live_sum_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, ix->live.as<unsigned>(), ix->dl.as<unsigned>(), n,
-                       ix->acc.as<unsigned long long>());
-    hipLaunchKernelGGL(kd_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, ix->dl.as<unsigned>(), n, ix->acc.as<unsigned long long>(), ix->k1,
+    if (own) {
+      HIP_TRY(hipMemcpyAsync(ix->live.p, ix->h_live.data(), ix->h_live.size() * 4, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(live_sum_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, ix->live.as<unsigned>(), ix->dl.as<unsigned>(), n,
+                         ix->acc.as<unsigned long long>());
+    }
+    hipLaunchKernelGGL(kd_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, ix->dl.as<unsigned>(), n, kd_stats, ix->k1,
                        1.0f - ix->b, ix->b, ix->kd.as<float>());
-    for (const Segment& g : ix->segs)
-      if (g.n_keys)
-        hipLaunchKernelGGL(df_kernel, dim3((unsigned)std::min<long long>(4096, (g.n_keys + 3) / 4)), dim3(256), 0, st, g.pstart.as<unsigned>(),
-                           g.n_keys, g.prow.as<unsigned>(), ix->live.as<unsigned>(), g.df.as<unsigned>());
+    if (own)
+      for (const Segment& g : ix->segs)
+        if (g.n_keys)
+          hipLaunchKernelGGL(df_kernel, dim3((unsigned)std::min<long long>(4096, (g.n_keys + 3) / 4)), dim3(256), 0, st, g.pstart.as<unsigned>(),
+                             g.n_keys, g.prow.as<unsigned>(), ix->live.as<unsigned>(), g.df.as<unsigned>());
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipMemcpyAsync(ix->h_acc, ix->acc.p, 16, hipMemcpyDeviceToHost, st));
+  if (own) HIP_TRY(hipMemcpyAsync(ix->h_acc, ix->acc.p, 16, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  ix->stats_dirty = false;
+  ix->stats_dirty = ix->kd_dirty = false;
   return VRAG_OK;
 }
 
@@ -867,6 +902,71 @@ int grow_rows(vrag_text_index* ix, long long need) {
   ix->kd = std::move(kd);
   ix->rows_cap = cap;
   ix->stats_dirty = true;   // fresh liveness / K_d buffers
+  return VRAG_OK;
+}
+
+// The shape of a query batch: q_indptr from 0 and non-decreasing, every query's keys strictly ascending.
+int check_queries(const char* fn, const int64_t* q_indptr, const uint64_t* keys, const float* weights, int32_t nq) {
+  ARG_CHECK(q_indptr[0] == 0, "%s: q_indptr[0] must be 0", fn);
+  for (int32_t q = 0; q < nq; ++q) {
+    ARG_CHECK(q_indptr[q + 1] >= q_indptr[q], "%s: q_indptr must be non-decreasing", fn);
+    ARG_CHECK(q_indptr[q + 1] == q_indptr[q] || keys, "%s: null keys / weights", fn);
+    for (int64_t j = q_indptr[q] + 1; j < q_indptr[q + 1]; ++j)
+      ARG_CHECK(keys[j] > keys[j - 1], "%s: the keys of query %d must be strictly ascending", fn, q);
+  }
+  const int64_t n_terms = nq ? q_indptr[nq] : 0;
+  ARG_CHECK(n_terms == 0 || (keys && weights), "%s: null keys / weights", fn);
+  return VRAG_OK;
+}
+
+// Search workspace for nq queries and lists of k, and the batch (terms, weights, filter bitmap) uploaded on `st`.
+int search_upload(vrag_text_index* ix, const int64_t* q_indptr, const uint64_t* keys, const float* weights, int32_t nq, int32_t k,
+                  const uint32_t* allow, int64_t allow_rows, hipStream_t st, const unsigned** d_allow, long long* allow_n) {
+  const int64_t n_terms = q_indptr[nq];
+  const int n_blocks = (int)((ix->n_rows + FT_ROWS - 1) / FT_ROWS);
+  const int kk = std::min(k, 64), pages = (k + 63) / 64;
+  HIP_TRY(ix->q_indptr.reserve((size_t)(nq + 1) * 8));
+  HIP_TRY(ix->q_keys.reserve((size_t)n_terms * 8));
+  HIP_TRY(ix->q_w.reserve((size_t)n_terms * 4));
+  HIP_TRY(ix->q_tu.reserve((size_t)n_terms * FT_MAXSEG * 4));
+  HIP_TRY(ix->cand.reserve((size_t)n_blocks * nq * kk * 8));
+  HIP_TRY(ix->page.reserve((size_t)pages * nq * kk * 8));
+  HIP_TRY(ix->bound.reserve((size_t)nq * 8));
+  HIP_TRY(hipMemcpyAsync(ix->q_indptr.p, q_indptr, (size_t)(nq + 1) * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ix->q_keys.p, keys, (size_t)n_terms * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ix->q_w.p, weights, (size_t)n_terms * 4, hipMemcpyHostToDevice, st));
+  *d_allow = nullptr;
+  // rows at or beyond allow_rows (e.g. added after the caller built its filter) are not allowed
+  *allow_n = allow ? std::min<long long>(allow_rows, ix->n_rows) : 0;
+  if (allow) {
+    const size_t words = (size_t)(*allow_n + 31) / 32;   // the caller's bitmap holds at least these
+    HIP_TRY(ix->allow.reserve(words * 4));
+    if (words) HIP_TRY(hipMemcpyAsync(ix->allow.p, allow, words * 4, hipMemcpyHostToDevice, st));
+    *d_allow = ix->allow.as<unsigned>();
+  }
+  return VRAG_OK;
+}
+
+// The kernels of one search on the uploaded batch: term lookup, then per page of 64 the scoring pass and the per-query merge;
+// page p of the result is ix->page[p][nq][min(k, 64)] (keys, 0 = none).
+int search_launch(vrag_text_index* ix, int32_t nq, int64_t n_terms, int32_t k, const unsigned* d_allow, long long allow_n, hipStream_t st) {
+  const int n_blocks = (int)((ix->n_rows + FT_ROWS - 1) / FT_ROWS);
+  const int kk = std::min(k, 64), pages = (k + 63) / 64;
+  const FtSegs segs = seg_view(ix);
+  hipLaunchKernelGGL(ft_lookup_kernel, dim3(grid_of(n_terms, 256)), dim3(256), 0, st, segs, ix->q_keys.as<u64>(), (long long)n_terms,
+                     ix->q_tu.as<int>(), (long long*)nullptr);
+  HIP_TRY(hipGetLastError());
+  const float k1p1 = ix->k1 + 1.0f;
+  for (int p = 0; p < pages; ++p) {
+    u64* page = ix->page.as<u64>() + (size_t)p * nq * kk;
+    hipLaunchKernelGGL(ft_score_kernel, dim3(n_blocks, nq), dim3(FT_NT), 0, st, segs, ix->q_indptr.as<long long>(), ix->q_tu.as<int>(),
+                       ix->q_w.as<float>(), ix->kd.as<float>(), ix->live.as<unsigned>(), d_allow, allow_n, ix->n_rows, k1p1, nq, kk,
+                       p ? ix->bound.as<u64>() : nullptr, ix->cand.as<u64>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_topk_merge(ix->cand.as<u64>(), n_blocks, nq, kk, page, st));
+    if (p + 1 < pages) hipLaunchKernelGGL(ft_bound_kernel, dim3(grid_of(nq, 256)), dim3(256), 0, st, page, nq, kk, ix->bound.as<u64>());
+    HIP_TRY(hipGetLastError());
+  }
   return VRAG_OK;
 }
 
@@ -920,7 +1020,7 @@ int vrag_text_index_create(float k1, float b, int32_t device, vrag_text_index** 
   ix->k1 = k1;
   ix->b = b;
   hipError_t e = hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = ix->acc.alloc(16);
+  if (e == hipSuccess) e = ix->acc.alloc(32);
   if (e != hipSuccess) {
     vrag_text_index_destroy(ix);
     HIP_TRY(e);
@@ -934,6 +1034,10 @@ void vrag_text_index_destroy(vrag_text_index* ix) {
   (void)hipSetDevice(ix->device);
   if (ix->stream) (void)hipStreamSynchronize(ix->stream);
   hipStream_t st = ix->stream;
+  if (ix->lists_done) {
+    (void)hipEventSynchronize(ix->lists_done);
+    (void)hipEventDestroy(ix->lists_done);
+  }
   delete ix;   // DevBufs free themselves
   if (st) (void)hipStreamDestroy(st);
 }
@@ -947,6 +1051,8 @@ int vrag_text_index_add(vrag_text_index* ix, const uint8_t* text, const int64_t*
   ARG_CHECK(ix->n_rows + n_docs < 0xFFFFFF00ll, "vrag_text_index_add: more than 2^32 rows");
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t st = ix->stream;
+  // a device-resident search may still be reading the segments and the per-row arrays this call replaces
+  if (ix->lists_done) HIP_TRY(hipEventSynchronize(ix->lists_done));
   if ((rc = grow_rows(ix, ix->n_rows + n_docs)) != VRAG_OK) return rc;
   // Everything is built on the side; the index changes only once the whole call has succeeded (a failed add leaves it as it
   // was, and the same rows can be added again).
@@ -989,6 +1095,19 @@ int vrag_text_index_set_live(vrag_text_index* ix, const uint32_t* words, int64_t
   return VRAG_OK;
 }
 
+int vrag_text_index_set_corpus_stats(vrag_text_index* ix, int64_t n_live_total, int64_t sum_dl_total) {
+  ARG_CHECK(ix, "vrag_text_index_set_corpus_stats: null handle");
+  ARG_CHECK(n_live_total >= 0 && sum_dl_total >= 0 && (n_live_total > 0 || sum_dl_total == 0),
+            "vrag_text_index_set_corpus_stats: need n_live_total >= 0, sum_dl_total >= 0 and no tokens without rows (got %lld, %lld)",
+            (long long)n_live_total, (long long)sum_dl_total);
+  std::lock_guard<std::mutex> lock(ix->mu);
+  if ((unsigned long long)n_live_total == ix->corpus[0] && (unsigned long long)sum_dl_total == ix->corpus[1]) return VRAG_OK;
+  ix->corpus[0] = (unsigned long long)n_live_total;
+  ix->corpus[1] = (unsigned long long)sum_dl_total;
+  ix->kd_dirty = true;
+  return VRAG_OK;
+}
+
 int vrag_text_index_stats(vrag_text_index* ix, int64_t* n_rows, int64_t* n_live, int64_t* sum_dl, int64_t* n_segments, int64_t* n_postings) {
   ARG_CHECK(ix, "vrag_text_index_stats: null handle");
   std::lock_guard<std::mutex> lock(ix->mu);
@@ -1013,7 +1132,7 @@ int vrag_text_index_query_terms(vrag_text_index* ix, const uint8_t* text, const 
   std::lock_guard<std::mutex> lock(ix->mu);
   HIP_TRY(hipSetDevice(ix->device));
   if ((rc = refresh_stats(ix)) != VRAG_OK) return rc;
-  *n_live = (int64_t)ix->h_acc[0];
+  *n_live = (int64_t)(ix->corpus[0] ? ix->corpus[0] : ix->h_acc[0]);
   for (int32_t q = 0; q <= nq; ++q) q_indptr[q] = 0;
   if (nq == 0) return VRAG_OK;
   hipStream_t st = ix->stream;
@@ -1055,14 +1174,9 @@ int vrag_text_index_search(vrag_text_index* ix, const int64_t* q_indptr, const u
                            int32_t k, const uint32_t* allow, int64_t allow_rows, float* scores, int64_t* ids) {
   ARG_CHECK(ix && q_indptr && scores && ids && nq >= 0, "vrag_text_index_search: bad arguments");
   ARG_CHECK(k >= 1 && k <= 1024, "vrag_text_index_search: k must be in 1..1024, got %d", k);
-  ARG_CHECK(q_indptr[0] == 0, "vrag_text_index_search: q_indptr[0] must be 0");
-  for (int32_t q = 0; q < nq; ++q) {
-    ARG_CHECK(q_indptr[q + 1] >= q_indptr[q], "vrag_text_index_search: q_indptr must be non-decreasing");
-    for (int64_t j = q_indptr[q] + 1; j < q_indptr[q + 1]; ++j)
-      ARG_CHECK(keys[j] > keys[j - 1], "vrag_text_index_search: the keys of query %d must be strictly ascending", q);
-  }
+  int rc = check_queries("vrag_text_index_search", q_indptr, keys, weights, nq);
+  if (rc != VRAG_OK) return rc;
   const int64_t n_terms = nq ? q_indptr[nq] : 0;
-  ARG_CHECK(n_terms == 0 || (keys && weights), "vrag_text_index_search: null keys / weights");
   for (int64_t i = 0; i < (int64_t)nq * k; ++i) {
     scores[i] = -INFINITY;
     ids[i] = -1;
@@ -1072,45 +1186,14 @@ int vrag_text_index_search(vrag_text_index* ix, const int64_t* q_indptr, const u
   ARG_CHECK(!allow || allow_rows >= 0, "vrag_text_index_search: negative allow_rows");
   if (n_terms == 0 || ix->n_rows == 0) return VRAG_OK;
   HIP_TRY(hipSetDevice(ix->device));
-  int rc = refresh_stats(ix);
-  if (rc != VRAG_OK) return rc;
+  if ((rc = refresh_stats(ix)) != VRAG_OK) return rc;
   hipStream_t st = ix->stream;
-  const int n_blocks = (int)((ix->n_rows + FT_ROWS - 1) / FT_ROWS);
+  if (ix->lists_done) HIP_TRY(hipStreamWaitEvent(st, ix->lists_done, 0));   // a device-resident search may still be reading the workspace
   const int kk = std::min(k, 64), pages = (k + 63) / 64;
-  HIP_TRY(ix->q_indptr.reserve((size_t)(nq + 1) * 8));
-  HIP_TRY(ix->q_keys.reserve((size_t)n_terms * 8));
-  HIP_TRY(ix->q_w.reserve((size_t)n_terms * 4));
-  HIP_TRY(ix->q_tu.reserve((size_t)n_terms * FT_MAXSEG * 4));
-  HIP_TRY(ix->cand.reserve((size_t)n_blocks * nq * kk * 8));
-  HIP_TRY(ix->page.reserve((size_t)pages * nq * kk * 8));
-  HIP_TRY(ix->bound.reserve((size_t)nq * 8));
-  HIP_TRY(hipMemcpyAsync(ix->q_indptr.p, q_indptr, (size_t)(nq + 1) * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(ix->q_keys.p, keys, (size_t)n_terms * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(ix->q_w.p, weights, (size_t)n_terms * 4, hipMemcpyHostToDevice, st));
   const unsigned* d_allow = nullptr;
-  // rows at or beyond allow_rows (e.g. added after the caller built its filter) are not allowed
-  const long long allow_n = allow ? std::min<long long>(allow_rows, ix->n_rows) : 0;
-  if (allow) {
-    const size_t words = (size_t)(allow_n + 31) / 32;   // the caller's bitmap holds at least these
-    HIP_TRY(ix->allow.reserve(words * 4));
-    if (words) HIP_TRY(hipMemcpyAsync(ix->allow.p, allow, words * 4, hipMemcpyHostToDevice, st));
-    d_allow = ix->allow.as<unsigned>();
-  }
-  const FtSegs segs = seg_view(ix);
-  hipLaunchKernelGGL(ft_lookup_kernel, dim3(grid_of(n_terms, 256)), dim3(256), 0, st, segs, ix->q_keys.as<u64>(), (long long)n_terms,
-                     ix->q_tu.as<int>(), (long long*)nullptr);
-  HIP_TRY(hipGetLastError());
-  const float k1p1 = ix->k1 + 1.0f;
-  for (int p = 0; p < pages; ++p) {
-    u64* page = ix->page.as<u64>() + (size_t)p * nq * kk;
-    hipLaunchKernelGGL(ft_score_kernel, dim3(n_blocks, nq), dim3(FT_NT), 0, st, segs, ix->q_indptr.as<long long>(), ix->q_tu.as<int>(),
-                       ix->q_w.as<float>(), ix->kd.as<float>(), ix->live.as<unsigned>(), d_allow, allow_n, ix->n_rows, k1p1, nq, kk,
-                       p ? ix->bound.as<u64>() : nullptr, ix->cand.as<u64>());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(launch_topk_merge(ix->cand.as<u64>(), n_blocks, nq, kk, page, st));
-    if (p + 1 < pages) hipLaunchKernelGGL(ft_bound_kernel, dim3(grid_of(nq, 256)), dim3(256), 0, st, page, nq, kk, ix->bound.as<u64>());
-    HIP_TRY(hipGetLastError());
-  }
+  long long allow_n = 0;
+  if ((rc = search_upload(ix, q_indptr, keys, weights, nq, k, allow, allow_rows, st, &d_allow, &allow_n)) != VRAG_OK) return rc;
+  if ((rc = search_launch(ix, nq, n_terms, k, d_allow, allow_n, st)) != VRAG_OK) return rc;
   std::vector<u64> h((size_t)pages * nq * kk);
   HIP_TRY(hipMemcpyAsync(h.data(), ix->page.p, h.size() * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -1121,6 +1204,44 @@ int vrag_text_index_search(vrag_text_index* ix, const int64_t* q_indptr, const u
       scores[(size_t)q * k + i] = unorderable((unsigned)(key >> 32));
       ids[(size_t)q * k + i] = (int64_t)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFu));
     }
+  return VRAG_OK;
+}
+
+int vrag_text_index_search_device(vrag_text_index* ix, const int64_t* q_indptr, const uint64_t* keys, const float* weights, int32_t nq,
+                                  int32_t k, const uint32_t* allow, int64_t allow_rows, const int64_t* row_map, int64_t n_map,
+                                  int64_t id_base, float* out_scores, int64_t* out_ids, void* stream) {
+  ARG_CHECK(ix && q_indptr && out_scores && out_ids && nq > 0, "vrag_text_index_search_device: bad arguments");
+  ARG_CHECK(k >= 1 && k <= 64, "vrag_text_index_search_device: k must be in 1..64 for a device-resident search, got %d", k);
+  ARG_CHECK(!row_map || n_map >= 0, "vrag_text_index_search_device: negative row map length");
+  int rc = check_queries("vrag_text_index_search_device", q_indptr, keys, weights, nq);
+  if (rc != VRAG_OK) return rc;
+  const int64_t n_terms = q_indptr[nq];
+  std::lock_guard<std::mutex> lock(ix->mu);
+  ARG_CHECK(!allow || allow_rows >= 0, "vrag_text_index_search_device: negative allow_rows");
+  HIP_TRY(hipSetDevice(ix->device));
+  if ((rc = refresh_stats(ix)) != VRAG_OK) return rc;
+  // Uploads go through the handle's own stream and are waited for (the host arrays are free on return); the kernels are
+  // only enqueued on the caller's stream (NULL = the legacy default stream), which the all-gather that follows is ordered on.
+  hipStream_t up = ix->stream, st = reinterpret_cast<hipStream_t>(stream);
+  if (ix->lists_done) HIP_TRY(hipStreamWaitEvent(up, ix->lists_done, 0));
+  const long long n = (long long)nq * k;
+  if (n_terms == 0 || ix->n_rows == 0) {   // no query term or no row: every list is empty
+    HIP_TRY(ix->page.reserve((size_t)n * 8));
+    HIP_TRY(hipStreamSynchronize(up));
+    HIP_TRY(hipMemsetAsync(ix->page.p, 0, (size_t)n * 8, st));
+  } else {
+    const unsigned* d_allow = nullptr;
+    long long allow_n = 0;
+    if ((rc = search_upload(ix, q_indptr, keys, weights, nq, k, allow, allow_rows, up, &d_allow, &allow_n)) != VRAG_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(up));
+    if ((rc = search_launch(ix, nq, n_terms, k, d_allow, allow_n, st)) != VRAG_OK) return rc;
+  }
+  hipLaunchKernelGGL(ft_export_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, ix->page.as<u64>(), n,
+                     reinterpret_cast<const long long*>(row_map), (long long)n_map, (long long)id_base, out_scores,
+                     reinterpret_cast<long long*>(out_ids));
+  HIP_TRY(hipGetLastError());
+  if (!ix->lists_done) HIP_TRY(hipEventCreateWithFlags(&ix->lists_done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(ix->lists_done, st));
   return VRAG_OK;
 }
 

@@ -191,6 +191,23 @@ class ShardComm:
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
         return t.cpu().numpy().astype(bool)
 
+    def sum_int64(self, local) -> np.ndarray:
+        """Element-wise exact int64 sum of every rank's array (the corpus-wide BM25 statistics of a row-sharded store:
+        `(N, sum dl)` after a change, the `df` vector of a query batch).  Same agreement as `union_mask`: every rank
+        enters with an array of the same length -- a rank without rows contributes zeros.  Host tensors under gloo, device
+        tensors under nccl; integer addition, so the result does not depend on the reduction order."""
+        import torch
+        import torch.distributed as dist
+
+        arr = np.array(local, dtype=np.int64, copy=True).reshape(-1)
+        if arr.size == 0:                                   # the same (empty) length on every rank: nothing to add
+            return arr
+        t = torch.from_numpy(arr)
+        if self.backend == "nccl":
+            t = t.to(torch.device("cuda", self.device))
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return t.cpu().numpy()
+
     # ---------------------------------------------------------------- the exchange
     @staticmethod
     def payload_bytes(n: int) -> int:

@@ -409,8 +409,16 @@ class TextIndex:
         _lib.check("vrag_text_index_stats", self._lib.vrag_text_index_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("rows", "live", "sum_dl", "segments", "postings"), (x.value for x in v)))
 
+    def set_corpus_stats(self, n_live_total: int, sum_dl_total: int) -> None:
+        """This index is one shard of a row-sharded corpus: `K_d` and the `N` of `query_terms` come from the corpus-wide
+        totals (the sums of every shard's `stats()["live"]` / `["sum_dl"]`) until they are set again; (0, 0) = its own."""
+        with self._mu:
+            _lib.check("vrag_text_index_set_corpus_stats", self._lib.vrag_text_index_set_corpus_stats(
+                self._h, int(n_live_total), int(sum_dl_total)))
+
     def query_terms(self, queries: Sequence[str]):
-        """(indptr [Q+1], keys uint64, counts int32, df int64, N): the distinct terms of every query, ascending keys."""
+        """(indptr [Q+1], keys uint64, counts int32, df int64, N): the distinct terms of every query, ascending keys -- every
+        term of the query texts, with df = 0 for those the index does not hold."""
         blob, off = _utf8_batch(queries)
         cap = max(1, len(blob))
         indptr = np.zeros(len(queries) + 1, np.int64)
@@ -451,6 +459,32 @@ class TextIndex:
             self._h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), keys.ctypes.data, w.ctypes.data_as(C.POINTER(C.c_float)), Q, k,
             words.ctypes.data if words is not None else None, len(allow) if allow is not None else 0,
             scores.ctypes.data_as(C.POINTER(C.c_float)), ids.ctypes.data_as(C.POINTER(C.c_int64))))
+
+    def search_sharded(self, queries: Sequence[str], k: int, allow: Optional[np.ndarray], n_live_total: int, sum_df, device_out=None):
+        """A shard's part of a search over a row-sharded corpus.  The term list depends on the query texts alone, so the df
+        vectors of all shards line up: `sum_df(df) -> corpus-wide df` (one collective per batch) sits between the query
+        analysis and the scoring, and the weights come from the summed `N` and df in float64 exactly as `weights` states.
+        Returns host `[Q, k]` (scores, LOCAL rows); with `device_out = (scores ptr, ids ptr, row_map ptr or None, n_map,
+        stream)` (k <= 64) the lists are left in HBM with global rows instead (`vrag_text_index_search_device`) and None is
+        returned."""
+        Q = len(queries)
+        words = _bitmap(allow) if allow is not None else None
+        with self._mu:
+            indptr, keys, counts, df, _n = self.query_terms(queries)
+            w = np.ascontiguousarray(self.weights(counts, np.asarray(sum_df(df), dtype=np.int64), n_live_total))
+            keys = np.ascontiguousarray(keys)
+            head = (self._h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), keys.ctypes.data, w.ctypes.data_as(C.POINTER(C.c_float)), Q, k,
+                    words.ctypes.data if words is not None else None, len(allow) if allow is not None else 0)
+            if device_out is not None:
+                out_s, out_i, row_map, n_map, stream = device_out
+                _lib.check("vrag_text_index_search_device", self._lib.vrag_text_index_search_device(
+                    *head, C.c_void_p(row_map) if row_map else None, n_map, 0, C.c_void_p(out_s), C.c_void_p(out_i), stream))
+                return None
+            scores = np.full((Q, k), -np.inf, np.float32)
+            ids = np.full((Q, k), -1, np.int64)
+            _lib.check("vrag_text_index_search", self._lib.vrag_text_index_search(
+                *head, scores.ctypes.data_as(C.POINTER(C.c_float)), ids.ctypes.data_as(C.POINTER(C.c_int64))))
+            return scores, ids
 
     def close(self):
         if self._h:
@@ -835,7 +869,10 @@ class GpuVectorStore(VectorStore):
     the per-shard `[Q, k]` lists and every rank merges them on its GPU (`distributed.ShardComm`; under RCCL the lists
     never leave HBM between the local search and the merge); the texts / metadata of the merged hits then meet in one
     object gather.  `query` / `query_batch` return the same results on every rank and the same results as a
-    single-GPU store.
+    single-GPU store.  Full text on a sharded store: each rank indexes the texts of its rows; `(N, sum dl)` are summed over
+    the ranks once after every insert / delete / load and the `df` vector of a query batch once per batch
+    (`ShardComm.sum_int64`, exact integers), so every rank scores its rows with the corpus-wide statistics -- the bits of
+    the single-GPU store -- and the lists merge like the other methods'.
     """
 
     enable_full_text = False  # per store: the constructor's `enable_full_text`
@@ -859,7 +896,9 @@ class GpuVectorStore(VectorStore):
                  dense_prefilter="auto", enable_full_text: bool = False, bm25_k1: float = 1.2, bm25_b: float = 0.75):
         """`enable_full_text`: BM25 keyword search over the raw texts (milvus_cloud.py: bm25_k1 = 1.2, bm25_b = 0.75),
         `search_type="full_text"` and the third leg of a weighted hybrid search; the texts are tokenised, indexed and
-        scored on the device (`TextIndex`).  Off by default; not yet available on a sharded store.
+        scored on the device (`TextIndex`).  Off by default.  On a sharded store (`distributed=True` or a `comm`) the
+        corpus-wide BM25 statistics are summed over the ranks, which needs an initialised `torch.distributed` and a `comm`
+        with `sum_int64`: ValueError otherwise.
         `dense_prefilter` (fp32 rows only): keep a bf16 image of the rows beside them so that every search streams
         half (small batches) or a fraction (large ones) of the bytes of the full fp32 scan and returns the same bits (`DenseShard`).  It costs
         +50 % of the dense rows' HBM.  "auto" (default) = on where the image route exists (dim % 64 == 0 and <= 768,
@@ -872,8 +911,16 @@ class GpuVectorStore(VectorStore):
             raise ValueError(f"payload must be 'sharded' or 'replicated' (got {payload!r})")
         if not enable_dense and not enable_sparse and not enable_full_text:      # milvus_base.py:54-56
             raise ValueError("At least one of enable_dense, enable_sparse, or enable_full_text must be True")
-        if enable_full_text and (distributed or (comm is not None and comm.world > 1)):
-            raise ValueError("enable_full_text is not available on a sharded store (global df / N / avgdl need a collective)")
+        if enable_full_text and comm is None and distributed:
+            import torch.distributed as dist
+
+            if not (dist.is_available() and dist.is_initialized()):
+                raise ValueError("enable_full_text on a sharded store needs an initialised torch.distributed process group "
+                                 "(global df / N / avgdl are summed over the ranks)")
+        if enable_full_text and comm is not None and (comm.world > 1 or getattr(comm, "on_gpu", False)) \
+                and not callable(getattr(comm, "sum_int64", None)):
+            raise ValueError("enable_full_text on a sharded store needs a comm with sum_int64 (global df / N / avgdl are summed "
+                             "over the ranks)")
         self.enable_dense, self.enable_sparse = enable_dense, enable_sparse
         self.enable_full_text, self.bm25_k1, self.bm25_b = bool(enable_full_text), float(bm25_k1), float(bm25_b)
         self.dense_dim, self.sparse_vocab, self.dense_dtype, self.device = dense_dim, sparse_vocab, dense_dtype, device
@@ -891,6 +938,9 @@ class GpuVectorStore(VectorStore):
         self._rank = self._comm.rank if self._comm is not None else 0
         self._world = self._comm.world if self._comm is not None else 1
         self._payload_sharded = self._world > 1 and payload == "sharded"
+        # full text goes through the exchange (statistics sums + list merge) exactly where `_device_topk` does
+        self._text_sharded = self.enable_full_text and self._comm is not None and (self._world > 1 or self._comm.on_gpu)
+        self._text_totals: Optional[Tuple[int, int]] = None   # corpus-wide (N, sum dl), None = to be summed again
         # replicated on every rank, indexed by global row
         self._ids: List[str] = []
         self._alive = _Column(bool)
@@ -1047,6 +1097,7 @@ class GpuVectorStore(VectorStore):
                 if rows is not None:
                     alive[rows] = False
             self._text_live_stale = True
+            self._text_totals = None
             self._drop_subsets()
 
     def _sparse_slice(self, a: int, b: int):
@@ -1084,11 +1135,19 @@ class GpuVectorStore(VectorStore):
                     tail = SparseShard(self.sparse_vocab, *self._sparse_slice(main_n, n), device=self.device)
                     self._sparse_parts = [main, (tail, main_n, n - main_n)]
                 self._sparse_flushed = n
+            if self._text_sharded:
+                self._text_totals = None                # every rank, whatever its share of the new rows
+                if self._text is None:                  # a rank without rows still answers the query analysis
+                    self._text = TextIndex(self.bm25_k1, self.bm25_b, self.device)
             if self.enable_full_text and n > self._text_flushed:
                 if self._text is None:
                     self._text = TextIndex(self.bm25_k1, self.bm25_b, self.device)
                 fold = self._text_main == 0 or n - self._text_main > max(self.TEXT_TAIL_MIN, self._text_main // 4)
-                self._text.add(self._texts[self._text_flushed:n], fold=fold)
+                if self._payload_sharded or self._world == 1:      # the text list is indexed by local row
+                    fresh = self._texts[self._text_flushed:n]
+                else:                                              # replicated payload: by global row
+                    fresh = [self._texts[g] for g in self._owned.data[self._text_flushed:n].tolist()]
+                self._text.add(fresh, fold=fold)
                 if fold:
                     self._text_main = n
                 self._text_flushed = n
@@ -1362,6 +1421,8 @@ class GpuVectorStore(VectorStore):
         if limit > self.K_LIMIT:
             raise ValueError(f"GpuVectorStore: a search may ask for at most {self.K_LIMIT} rows per method "
                              f"(got {limit}; hybrid search asks for 2 * top_k)")
+        if self._text_sharded:
+            return self._text_topk_sharded(queries, limit, mask)
         with self._mu:
             self._flush()
             text, n = self._text, self._text_flushed
@@ -1379,6 +1440,62 @@ class GpuVectorStore(VectorStore):
             return rows_out, score_out
         scores, rows = text.search([q or "" for q in queries], limit, mask)
         found = rows >= 0
+        rows_out[:] = np.where(found, rows, -1)
+        score_out[:] = np.where(found, scores, np.float32(0.0))
+        return rows_out, score_out
+
+    def _text_topk_sharded(self, queries: Sequence[str], limit: int, mask: Optional[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
+        """`_text_topk` on a row-sharded store.  Every rank scores its own rows with the corpus-wide statistics: `(N, sum dl)`
+        summed over the ranks once after a change (cached), the `df` vector of the batch summed once per batch; the local
+        lists go through the exchange of `_device_topk` (host lists, or HBM-resident under RCCL for k <= DEVICE_K).  Every
+        branch depends on replicated state only (row count, query count, the OR-reduced mask, the summed N), so the ranks
+        meet in the same collectives; a rank without rows enters them with zeros and empty lists.  Like every search of a
+        sharded store, this route must be driven from ONE thread per rank: the statistics sum runs under the store's lock and
+        the df sum under the index's, so two threads querying on one rank could order their collectives differently from the
+        peer rank."""
+        comm = self._comm
+        with self._mu:
+            self._flush()
+            text, n_local, n = self._text, self._text_flushed, len(self._ids)
+            owned = self._owned.data[:n_local]
+            if text is not None and self._text_live_stale:
+                if n_local:
+                    text.set_live(self._alive.data[owned])
+                self._text_live_stale = False
+            if text is not None and self._text_totals is None:
+                own = text.stats()
+                tot = comm.sum_int64([own["live"], own["sum_dl"]])
+                text.set_corpus_stats(int(tot[0]), int(tot[1]))
+                self._text_totals = (int(tot[0]), int(tot[1]))
+            totals, owned_dev = self._text_totals, self._owned_dev
+        Q = len(queries)
+        rows_out = np.full((Q, limit), -1, np.int64)
+        score_out = np.zeros((Q, limit), np.float32)
+        if text is None or n == 0 or Q == 0 or totals[0] == 0:
+            return rows_out, score_out
+        if mask is not None:
+            if len(mask) != n:      # rows were inserted after the caller built its mask: they do not pass
+                mask = np.concatenate([mask, np.zeros(n - len(mask), dtype=bool)]) if len(mask) < n else mask[:n]
+            if not mask.any():
+                return rows_out, score_out
+        allow = mask[owned] if mask is not None else None       # the global-row mask at this rank's rows
+        texts = [q or "" for q in queries]
+        k = limit
+        if comm.on_gpu and k <= self.DEVICE_K:
+            import torch
+
+            stream = C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+            payload, ids_ptr, scores_ptr = comm.exchange_buffers(Q, k)
+            table, n_map = owned_dev if (owned_dev is not None and n_local) else (None, 0)
+            text.search_sharded(texts, k, allow, totals[0], comm.sum_int64,
+                                device_out=(scores_ptr, ids_ptr, table.data_ptr() if table is not None else None, min(n_map, n_local), stream))
+            scores, rows = comm.allgather_merge_device(payload, Q, k, k)
+        else:
+            scores, local = text.search_sharded(texts, k, allow, totals[0], comm.sum_int64)
+            found = (local >= 0) & (local < n_local)
+            rows = np.where(found, owned[np.where(found, local, 0)], -1) if n_local else np.full_like(local, -1)
+            scores, rows = comm.allgather_merge(np.where(rows >= 0, scores, -np.inf).astype(np.float32), rows, k)
+        found = (rows >= 0) & (rows < n)
         rows_out[:] = np.where(found, rows, -1)
         score_out[:] = np.where(found, scores, np.float32(0.0))
         return rows_out, score_out
@@ -1408,6 +1525,8 @@ class GpuVectorStore(VectorStore):
             try:                                                   # as the per-query path (milvus_base.py:420-431)
                 lists[m] = self._text_topk(q, limit, mask)
             except Exception as e:
+                if self._world > 1:
+                    raise                                  # ranks must not diverge into different collectives
                 logger.warning("Full text search failed: %s, excluding from hybrid", e)
         Q = len(next(iter(queries.values())))
         if not lists:
@@ -1536,6 +1655,8 @@ class GpuVectorStore(VectorStore):
             try:
                 rbm["full_text"] = self._search("full_text", text_query, top_k * 2, mask)
             except Exception as e:
+                if self._world > 1:
+                    raise
                 logger.warning("Full text search failed: %s, excluding from hybrid", e)
         if len(rbm) == 0:
             logger.warning("Hybrid search: no valid methods executed after validation")
