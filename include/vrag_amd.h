@@ -414,6 +414,58 @@ int vrag_text_index_search_device(vrag_text_index* ix, const int64_t* q_indptr /
                                   const int64_t* row_map /*device or NULL*/, int64_t n_map, int64_t id_base,
                                   float* out_scores /*[nq,k] device*/, int64_t* out_ids /*[nq,k] device*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * WordPiece tokenisation of raw texts (csrc/wordpiece.hip): the ids HF `tokenizers` returns for the BERT pipeline
+ * BertNormalizer -> BertPreTokenizer -> WordPiece -> `[CLS] $A [SEP]` with truncation from the right.
+ *   Code points  decoded as the full-text analyzer above decodes them (malformed UTF-8 = U+FFFD, same rules).
+ *   Per code point, from the committed table csrc/wordpiece_table.inc (tools/gen_wordpiece_table.py; it records the
+ *   unicodedata and tokenizers versions it was generated and verified with), in this order:
+ *     clean_text          U+0000, U+FFFD and every Cc / Cf code point other than tab, LF, CR vanish; a White_Space code point is
+ *                         a separator (it is one with clean_text off as well: the pre-tokenizer splits on the same set)
+ *     handle_chinese_chars a code point of the CJK ranges of BertNormalizer (4E00-9FFF, 3400-4DBF, 20000-2A6DF, 2A700-2B73F,
+ *                         2B740-2B81F, 2B920-2CEAF, F900-FAFF, 2F800-2FA1F) is a word of its own
+ *     strip_accents       the code point is replaced by its canonical decomposition (NFD) without the Mn code points; a code
+ *                         point left with nothing vanishes (it neither starts nor ends a word)
+ *     lowercase           every remaining code point is replaced by its full lowercase mapping, character by character
+ *                         (no context rule: capital sigma is always U+03C3)
+ *     punctuation         a resulting code point that is ASCII punctuation (33-47, 58-64, 91-96, 123-126) or of a category
+ *                         P* is a word of its own
+ *   A word is otherwise a maximal run of code points that are none of the above; vanished code points do not interrupt it.
+ *   A code point the table does not cover (unassigned or private use in the table's Unicode version, a non-zero combining
+ *   class without being Mn, a disagreement between the table's two sources, Hangul syllables under strip_accents) sets
+ *   needs_host for its text, as does a run of more than 64 vanished code points in front of a word: the ids written for
+ *   such a text are unspecified, and the caller tokenises it on the host.
+ *   Matching, per word of n code points:  n > max_chars_per_word -> one unk_id.  Otherwise from s = 0: the LONGEST e > s such
+ *   that the UTF-8 of code points [s, e), with `prefix` in front when s > 0, is a vocabulary piece gives that piece's id and
+ *   s = e; a position without any match turns the whole word into one unk_id.  The vocabulary is a hash table in device
+ *   memory; every hit is confirmed byte for byte against the stored piece, so a hash collision cannot change an id.
+ *   Packing: a text's ids are its words' ids in order, cut to max_length (add_special_tokens = 0) or to max_length - 2 with
+ *   cls_id in front and sep_id behind (add_special_tokens = 1, max_length >= 2); texts are written back to back.
+ * flags: VRAG_WP_LOWERCASE | VRAG_WP_STRIP_ACCENTS | VRAG_WP_CLEAN_TEXT | VRAG_WP_CHINESE_CHARS (HF's strip_accents = null
+ * means "as lowercase": the caller resolves it).  Host pointers; the call synchronises; calls on one handle are serialised. */
+#define VRAG_WP_LOWERCASE 1
+#define VRAG_WP_STRIP_ACCENTS 2
+#define VRAG_WP_CLEAN_TEXT 4
+#define VRAG_WP_CHINESE_CHARS 8
+#define VRAG_WP_MAX_CHARS_PER_WORD 128 /* largest max_chars_per_word a handle takes */
+#define VRAG_WP_MAX_BATCH_BYTES (512ll << 20) /* text bytes one vrag_wordpiece_encode call takes */
+#define VRAG_WORDPIECE_TILE_BYTES 4096 /* text bytes per workgroup of the word-boundary passes */
+typedef struct vrag_wordpiece vrag_wordpiece;
+/* Piece i of the vocabulary is vocab_blob[piece_off[i] .. piece_off[i+1]) (well-formed UTF-8, non-empty, no two alike) and
+ * has id i; `prefix` is the NUL-terminated continuing_subword_prefix ("##"). */
+int vrag_wordpiece_create(const uint8_t* vocab_blob, const int64_t* piece_off /*[n_vocab+1]*/, int32_t n_vocab, int32_t unk_id,
+                          int32_t cls_id, int32_t sep_id, const char* prefix, int32_t max_chars_per_word, int32_t flags,
+                          int32_t device, vrag_wordpiece** out);
+void vrag_wordpiece_destroy(vrag_wordpiece* h);
+/* Texts as vrag_text_tokenize takes them, at most VRAG_WP_MAX_BATCH_BYTES (512 MiB) of text per call and
+ * bytes + 2 * n_docs < 2^31 (the handle keeps 4 bytes of id scratch per text byte -- 2 GiB at the limit -- and counts ids in
+ * 32 bits).  seq_lens[d] = ids of text d (specials included), needs_host[d] = 1 when text d
+ * must be tokenised on the host, n_ids = sum of seq_lens; ids is only written when n_ids <= cap, else VRAG_ERR_CAPACITY with
+ * seq_lens, needs_host and n_ids filled in. */
+int vrag_wordpiece_encode(vrag_wordpiece* h, const uint8_t* text, const int64_t* doc_off /*[n_docs+1]*/, int32_t n_docs,
+                          int32_t add_special_tokens, int32_t max_length, int64_t cap, int32_t* ids /*[cap]*/,
+                          int32_t* seq_lens /*[n_docs]*/, uint8_t* needs_host /*[n_docs]*/, int64_t* n_ids);
+
 /* Cross-shard merge of per-shard top-k lists (the reference has no sharding -- this is the step after the
  * all-gather of `[n_lists][nq][k_in]` (fp32 score, global row id) lists, each sorted by (score desc, id asc) with
  * id = -1 entries as a tail).  Writes the first k_out entries of the merged order per query (-inf / -1 padded).

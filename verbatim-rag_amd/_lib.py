@@ -143,6 +143,10 @@ SIGNATURES = {
     "vrag_text_index_search": (C.c_int, [_H, _LP, C.c_void_p, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _FP, _LP]),
     "vrag_text_index_search_device": (C.c_int, [_H, _LP, C.c_void_p, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
                                                 C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vrag_wordpiece_create": (C.c_int, [C.c_void_p, _LP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32,
+                                        C.c_int32, C.POINTER(_H)]),
+    "vrag_wordpiece_destroy": (None, [_H]),
+    "vrag_wordpiece_encode": (C.c_int, [_H, C.c_void_p, _LP, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _IP, _IP, C.c_void_p, _LP]),
     "vrag_comm_get_unique_id": (C.c_int, [C.c_void_p]),
     "vrag_comm_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_H)]),
     "vrag_comm_destroy": (None, [_H]),

@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "host_util.h"
+#include "utf8_text.h"
 
 // Every fp32 operation of this file is rounded on its own: no a * b + c is fused into an FMA (HIP's default is
 // -ffp-contract=fast, and the __fadd_rn / __fmul_rn helpers are plain operators compiled under it), so the host restatement
@@ -44,42 +45,6 @@ namespace uw {
 }  // namespace uw
 
 // ------------------------------------------------------------------------------------ analyzer
-__device__ __forceinline__ bool is_cont(unsigned c) { return (c & 0xC0u) == 0x80u; }
-
-// Code point that starts at t[j] (bytes up to `hi` readable) and its length in bytes.  Well-formed UTF-8 decodes as usual.  A
-// byte that cannot start a sequence is U+FFFD of one byte; a lead byte with the continuation bytes that follow it (at most as
-// many as it announces) is U+FFFD when some are missing or the result is an overlong form, a surrogate or above U+10FFFF.
-// U+FFFD is not alphanumeric.
-__device__ __forceinline__ unsigned decode_at(const unsigned char* __restrict__ t, long long j, long long hi, int* len) {
-  const unsigned c = t[j];
-  *len = 1;
-  if (c < 0x80u) return c;
-  if (c < 0xC0u || c >= 0xF8u) return 0xFFFDu;
-  int need;
-  unsigned cp;
-  if (c >= 0xF0u) {
-    need = 3;
-    cp = c & 0x07u;
-  } else if (c >= 0xE0u) {
-    need = 2;
-    cp = c & 0x0Fu;
-  } else {
-    need = 1;
-    cp = c & 0x1Fu;
-  }
-  int got = 0;
-  while (got < need && j + 1 + got < hi && is_cont(t[j + 1 + got])) {
-    cp = (cp << 6) | (t[j + 1 + got] & 0x3Fu);
-    ++got;
-  }
-  *len = 1 + got;
-  if (got != need) return 0xFFFDu;
-  // overlong forms (C0 / C1 leads, E0 80-9F, F0 80-8F), encoded surrogates and values above U+10FFFF are not code points
-  const unsigned least = need == 1 ? 0x80u : need == 2 ? 0x800u : 0x10000u;
-  if (cp < least || (cp >= 0xD800u && cp <= 0xDFFFu) || cp > 0x10FFFFu) return 0xFFFDu;
-  return cp;
-}
-
 __device__ __forceinline__ bool is_alnum(unsigned cp) {
   if (cp < 0x80u) return (cp - '0' < 10u) || ((cp | 0x20u) - 'a' < 26u);
   int lo = 0, hi = VRAG_ALNUM_RANGES - 1;    // last range with start <= cp
@@ -154,41 +119,7 @@ __device__ __forceinline__ u64 token_key(const unsigned char* __restrict__ t, lo
   return h;
 }
 
-// Document of byte i: the last d with off[d] <= i (empty documents are skipped over).
-__device__ __forceinline__ int doc_of(const long long* __restrict__ off, int n_docs, long long i) {
-  int lo = 0, hi = n_docs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= i) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
 constexpr int TOK_NT = 256, TOK_BPT = 16;   // 4096 text bytes per workgroup
-
-// Exclusive scan of one value per thread over a 256-thread workgroup (wave prefix by shuffles, then the wave totals).
-__device__ __forceinline__ unsigned block_scan_256(unsigned v, unsigned* total) {
-  __shared__ unsigned wsum[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  unsigned x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) wsum[wave] = x;
-  __syncthreads();
-  unsigned before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    before += w < wave ? wsum[w] : 0u;
-    all += wsum[w];
-  }
-  __syncthreads();
-  *total = all;
-  return before + x - v;
-}
 
 // Pass 1: tokens per workgroup of text bytes (tile_cnt) and per document (doc_cnt, atomics: the counts are exact).
 __global__ __launch_bounds__(TOK_NT) void tok_count_kernel(const unsigned char* __restrict__ text, long long n_bytes,
@@ -619,6 +550,30 @@ __global__ void ft_export_kernel(const u64* __restrict__ keys, long long n, cons
 
 }  // namespace vrag
 
+namespace vrag {
+
+// out[0..n] = exclusive scan of in[0..n), out[n] = total.
+hipError_t scan_u32(const unsigned* in, long long n, unsigned* out, hipStream_t st) {
+  const long long nb = std::max<long long>(1, (n + SCAN_TILE - 1) / SCAN_TILE);
+  DevBuf sums;
+  hipError_t e = sums.alloc((size_t)(nb + 1) * 4);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(scan_reduce_kernel, dim3((unsigned)nb), dim3(SCAN_NT), 0, st, in, n, sums.as<unsigned>());
+  hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SCAN_NT), 0, st, sums.as<unsigned>(), nb);
+  hipLaunchKernelGGL(scan_down_kernel, dim3((unsigned)nb), dim3(SCAN_NT), 0, st, in, n, sums.as<unsigned>(), nb, out);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(st);   // `sums` is freed on return
+  return e;
+}
+
+hipError_t read_u32(const unsigned* dev, unsigned* host, hipStream_t st) {
+  hipError_t e = hipMemcpyAsync(host, dev, 4, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e;
+}
+
+}  // namespace vrag
+
 using namespace vrag;
 
 namespace {
@@ -640,28 +595,6 @@ struct Records {
     return e;
   }
 };
-
-inline unsigned grid_of(long long n, int nt) { return (unsigned)((n + nt - 1) / nt); }
-
-// out[0..n] = exclusive scan of in[0..n), out[n] = total.
-hipError_t scan_u32(const unsigned* in, long long n, unsigned* out, hipStream_t st) {
-  const long long nb = std::max<long long>(1, (n + SCAN_TILE - 1) / SCAN_TILE);
-  DevBuf sums;
-  hipError_t e = sums.alloc((size_t)(nb + 1) * 4);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(scan_reduce_kernel, dim3((unsigned)nb), dim3(SCAN_NT), 0, st, in, n, sums.as<unsigned>());
-  hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(SCAN_NT), 0, st, sums.as<unsigned>(), nb);
-  hipLaunchKernelGGL(scan_down_kernel, dim3((unsigned)nb), dim3(SCAN_NT), 0, st, in, n, sums.as<unsigned>(), nb, out);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(st);   // `sums` is freed on return
-  return e;
-}
-
-hipError_t read_u32(const unsigned* dev, unsigned* host, hipStream_t st) {
-  hipError_t e = hipMemcpyAsync(host, dev, 4, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  return e;
-}
 
 // Stable sort of the records by key (by_row = 0: 8 passes) or by row (passes over the bits below 2^row_bits).
 hipError_t radix_sort(Records& r, int by_row, int row_bits, hipStream_t st) {

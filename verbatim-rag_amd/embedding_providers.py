@@ -72,7 +72,7 @@ class _EncoderProvider:
         self._tok = TokenizerAdapter.for_model(self.tokenizer, self.engine.shape)
 
     def _encode(self, texts: Sequence[str]) -> List[List[int]]:
-        return [self._tok.ids(t, add_special_tokens=True, max_length=self.max_length) for t in texts]
+        return self._tok.ids_batch(list(texts), max_length=self.max_length, add_special_tokens=True)
 
     def _batches(self, seqs: List[List[int]]):
         eng = self.engine
@@ -82,13 +82,27 @@ class _EncoderProvider:
             yield a, b
 
 
+def load_model_tokenizer(model_path: str, tokenizer: str = "host", device: int = 0) -> Any:
+    """The tokenizer of a checkpoint directory: "host" = `load_tokenizer` (HF, on the caller's thread), "gpu" = a
+    `GpuWordPieceTokenizer` over the directory's tokenizer.json (ValueError for anything but the BERT WordPiece pipeline)."""
+    if tokenizer == "host":
+        return load_tokenizer(model_path)
+    if tokenizer != "gpu":
+        raise ValueError(f"tokenizer must be 'host' or 'gpu', got {tokenizer!r}")
+    from .wordpiece import GpuWordPieceTokenizer
+
+    return GpuWordPieceTokenizer.from_file(model_path, device=device)
+
+
 def load_encoder_directory(model_path: str, device: int = 0, max_tokens: int = 65536, max_seqs: int = 512,
-                           max_seq_len: int = 512, splade_split_operands: bool = True, operand_dtype: str = "f16", **engine_kw):
+                           max_seq_len: int = 512, splade_split_operands: bool = True, operand_dtype: str = "f16",
+                           tokenizer: str = "host", **engine_kw):
     """(engine, tokenizer, raw config) from a local HF checkpoint directory -- the local-files counterpart of the model
     names the reference hands to sentence-transformers (`SpladeProvider(model_name)`, embedding_providers.py:117-133;
     `SentenceTransformersProvider(model_name)`, :52-71).  BERT / DistilBERT checkpoints get a `BertEncoderEngine` (MLM
     and pair heads attached when the tensors are there), ModernBERT checkpoints an `EncoderEngine` (+ MLM head, or the sequence-classification
     head when `architectures` names ModernBertForSequenceClassification).
+    `tokenizer`: "host" or "gpu" (`load_model_tokenizer`; a wrong request is refused before the weights are read).
     `splade_split_operands=False`: the MLM / SPLADE head with plain 16-bit operands (a third of the decoder work, weights within
     ~1e-2 of the fp32 head instead of 2e-5; include/vrag_amd.h vrag_encoder_set_head_precision)."""
     import json
@@ -97,28 +111,34 @@ def load_encoder_directory(model_path: str, device: int = 0, max_tokens: int = 6
     from . import engine as engine_mod
     from .weights import load_bert_safetensors_dir, load_safetensors_dir
 
-    with open(os.path.join(model_path, "config.json")) as f:
-        raw_cfg = json.load(f)
-    model_type = raw_cfg.get("model_type")
-    kw = dict(max_tokens=max_tokens, max_seqs=max_seqs, max_seq_len=max_seq_len, max_ranges=max(max_seqs, 64), device=device,
-              operand_dtype=operand_dtype, **engine_kw)
-    if model_type in ("bert", "distilbert"):
-        shape, weights, cfg = load_bert_safetensors_dir(model_path)
-        eng = engine_mod.BertEncoderEngine(shape, weights, mlm_split_operands=splade_split_operands, **kw)
-    elif model_type == "modernbert":
-        seq_head = _modernbert_seq_head(model_path, raw_cfg)
-        shape, tensors, cfg = load_safetensors_dir(model_path)
-        eng = engine_mod.EncoderEngine(shape, tensors, **kw)
-        if "head.dense.weight" in tensors and "decoder.bias" in tensors:        # ModernBertForMaskedLM: tied decoder
-            eng.set_mlm_head(tensors["head.dense.weight"], tensors["head.norm.weight"], tensors["decoder.bias"],
-                             tensors.get("decoder.weight"), split_operands=splade_split_operands)
-        if seq_head is not None:
-            eng.set_seq_head(tensors["head.dense.weight"], tensors["head.dense.bias"] if seq_head["dense_bias"] else None,
-                             tensors["head.norm.weight"], None, tensors["classifier.weight"], tensors["classifier.bias"],
-                             pooling=seq_head["pooling"])
-    else:
-        raise ValueError(f"{model_path}: model_type {model_type!r} is not bert / distilbert / modernbert")
-    return eng, load_tokenizer(model_path), cfg
+    tok = load_model_tokenizer(model_path, tokenizer, device)
+    try:
+        with open(os.path.join(model_path, "config.json")) as f:
+            raw_cfg = json.load(f)
+        model_type = raw_cfg.get("model_type")
+        kw = dict(max_tokens=max_tokens, max_seqs=max_seqs, max_seq_len=max_seq_len, max_ranges=max(max_seqs, 64), device=device,
+                  operand_dtype=operand_dtype, **engine_kw)
+        if model_type in ("bert", "distilbert"):
+            shape, weights, cfg = load_bert_safetensors_dir(model_path)
+            eng = engine_mod.BertEncoderEngine(shape, weights, mlm_split_operands=splade_split_operands, **kw)
+        elif model_type == "modernbert":
+            seq_head = _modernbert_seq_head(model_path, raw_cfg)
+            shape, tensors, cfg = load_safetensors_dir(model_path)
+            eng = engine_mod.EncoderEngine(shape, tensors, **kw)
+            if "head.dense.weight" in tensors and "decoder.bias" in tensors:        # ModernBertForMaskedLM: tied decoder
+                eng.set_mlm_head(tensors["head.dense.weight"], tensors["head.norm.weight"], tensors["decoder.bias"],
+                                 tensors.get("decoder.weight"), split_operands=splade_split_operands)
+            if seq_head is not None:
+                eng.set_seq_head(tensors["head.dense.weight"], tensors["head.dense.bias"] if seq_head["dense_bias"] else None,
+                                 tensors["head.norm.weight"], None, tensors["classifier.weight"], tensors["classifier.bias"],
+                                 pooling=seq_head["pooling"])
+        else:
+            raise ValueError(f"{model_path}: model_type {model_type!r} is not bert / distilbert / modernbert")
+    except BaseException:
+        if hasattr(tok, "close"):      # the device tokenizer holds a GPU handle
+            tok.close()
+        raise
+    return eng, tok, cfg
 
 
 def load_checked_directory(model_path: str, **load_kw):
@@ -127,7 +147,7 @@ def load_checked_directory(model_path: str, **load_kw):
     engine, tokenizer, _cfg = load_encoder_directory(model_path, **load_kw)
     if getattr(engine, "operand_dtype", "bf16") != "f16":
         return engine, tokenizer, None
-    return engine, tokenizer, lambda: load_encoder_directory(model_path, **{**load_kw, "operand_dtype": "bf16"})[0]
+    return engine, tokenizer, lambda: load_encoder_directory(model_path, **{**load_kw, "operand_dtype": "bf16", "tokenizer": "host"})[0]
 
 
 def _modernbert_seq_head(model_path: str, cfg: dict) -> Optional[dict]:
@@ -174,9 +194,12 @@ class GpuSpladeProvider(_EncoderProvider, SparseEmbeddingProvider):
             raise ValueError("engine has no MLM head (EncoderEngine.set_mlm_head)")
 
     @classmethod
-    def from_directory(cls, model_path: str, device: int = 0, max_length: int = 512, operand_dtype: str = "f16", **kw) -> "GpuSpladeProvider":
-        """`SpladeProvider(model_name, device)` (embedding_providers.py:120-133) for a checkpoint on disk."""
-        engine, tokenizer, rebuild = load_checked_directory(model_path, device=device, max_seq_len=max_length, operand_dtype=operand_dtype)
+    def from_directory(cls, model_path: str, device: int = 0, max_length: int = 512, operand_dtype: str = "f16",
+                       tokenizer: str = "host", **kw) -> "GpuSpladeProvider":
+        """`SpladeProvider(model_name, device)` (embedding_providers.py:120-133) for a checkpoint on disk.  `tokenizer="gpu"`:
+        WordPiece on the device (wordpiece.py), same ids."""
+        engine, tokenizer, rebuild = load_checked_directory(model_path, device=device, max_seq_len=max_length, operand_dtype=operand_dtype,
+                                                            tokenizer=tokenizer)
         self = cls(engine, tokenizer, max_length=max_length, **kw)
         self._checked.rebuild = rebuild
         return self
@@ -250,10 +273,12 @@ class GpuDenseProvider(_EncoderProvider, DenseEmbeddingProvider):
 
     @classmethod
     def from_directory(cls, model_path: str, device: int = 0, max_length: int = 512, pooling: Optional[str] = None,
-                       normalize: bool = True, operand_dtype: str = "f16") -> "GpuDenseProvider":
+                       normalize: bool = True, operand_dtype: str = "f16", tokenizer: str = "host") -> "GpuDenseProvider":
         """`SentenceTransformersProvider(model_name, device)` (embedding_providers.py:55-71) for a checkpoint on disk;
-        the pooling mode comes from the checkpoint's `1_Pooling/config.json` unless given."""
-        engine, tokenizer, rebuild = load_checked_directory(model_path, device=device, max_seq_len=max_length, operand_dtype=operand_dtype)
+        the pooling mode comes from the checkpoint's `1_Pooling/config.json` unless given.  `tokenizer="gpu"`: WordPiece on the
+        device (wordpiece.py), same ids."""
+        engine, tokenizer, rebuild = load_checked_directory(model_path, device=device, max_seq_len=max_length, operand_dtype=operand_dtype,
+                                                            tokenizer=tokenizer)
         self = cls(engine, tokenizer, pooling=pooling or _st_pooling_mode(model_path), normalize=normalize, max_length=max_length)
         self._checked.rebuild = rebuild
         return self

@@ -114,6 +114,11 @@ class TokenizerAdapter:
         """Special-token ids from the tokenizer when it defines them, otherwise from the model's config.json (`shape`): a
         raw `tokenizers.Tokenizer`, or an HF fast tokenizer loaded from a directory that holds only tokenizer.json,
         knows the template but not which ids are [CLS] / [SEP]."""
+        from .wordpiece import GpuWordPieceTokenizer
+
+        if isinstance(tokenizer, GpuWordPieceTokenizer):    # offers ids / ids_batch itself, with the ids of its own vocabulary
+            return tokenizer
+
         def override(name):
             return None if isinstance(getattr(tokenizer, name, None), int) else getattr(shape, name, None)
 
@@ -132,11 +137,14 @@ class TokenizerAdapter:
         enc = self.tok(text, add_special_tokens=add_special_tokens, max_length=max_length, truncation=True)
         return list(enc["input_ids"])
 
-    def ids_batch(self, texts: Sequence[str], max_length: int) -> List[List[int]]:
+    def ids_batch(self, texts: Sequence[str], max_length: int, add_special_tokens: bool = False) -> List[List[int]]:
         """Sentences are tokenised independently with add_special_tokens=False (dataset.py:161-167),
-        so one batched call is bit-identical to the reference's per-sentence calls."""
+        so one batched call is bit-identical to the reference's per-sentence calls.  add_special_tokens=True: `ids` of
+        every text (the providers' call; a `GpuWordPieceTokenizer` answers it with one device batch instead)."""
         if not texts:
             return []
+        if add_special_tokens:
+            return [self.ids(t, add_special_tokens=True, max_length=max_length) for t in texts]
         if self._raw:
             return [list(e.ids)[:max_length] for e in self.tok.encode_batch(list(texts), add_special_tokens=False)]
         enc = self.tok(list(texts), add_special_tokens=False, max_length=max_length, truncation=True)

@@ -94,12 +94,13 @@ class GpuCrossEncoderReranker(BaseReranker):
 
     @classmethod
     def from_directory(cls, model_path: str, device: int = 0, rerank_k: int = 50, max_length: Optional[int] = None,
-                       operand_dtype: Optional[str] = None, **kw) -> "GpuCrossEncoderReranker":
+                       operand_dtype: Optional[str] = None, tokenizer: str = "host", **kw) -> "GpuCrossEncoderReranker":
         """`SentenceTransformersReranker(model_name)` (rerankers.py:109-134) for a checkpoint on disk: a
         `BertForSequenceClassification` (e.g. a downloaded `cross-encoder/ms-marco-MiniLM-L-6-v2`; defaults: 512 tokens,
         the loader's fp16 operands) or a `ModernBertForSequenceClassification` (e.g. `gte-reranker-modernbert-base`;
         defaults: the checkpoint's `max_position_embeddings` as CrossEncoder takes it, bf16 operands -- a pooled logit feeds
-        an ordering, like the sentence classifier's)."""
+        an ordering, like the sentence classifier's).  `tokenizer="gpu"` (BERT checkpoints only: a
+        ModernBERT checkpoint's byte-level BPE is refused with a ValueError): WordPiece on the device, same ids."""
         import json
         import os
 
@@ -115,7 +116,7 @@ class GpuCrossEncoderReranker(BaseReranker):
             max_length = max_length or 512
             if operand_dtype:
                 load_kw["operand_dtype"] = operand_dtype
-        engine, tokenizer, rebuild = load_checked_directory(model_path, device=device, max_seq_len=max_length, **load_kw)
+        engine, tokenizer, rebuild = load_checked_directory(model_path, device=device, max_seq_len=max_length, tokenizer=tokenizer, **load_kw)
         self = cls(engine, tokenizer, rerank_k=rerank_k, max_length=max_length, **kw)
         self._checked.rebuild = rebuild
         return self
@@ -124,10 +125,18 @@ class GpuCrossEncoderReranker(BaseReranker):
         enc = self.tokenizer.encode(text, add_special_tokens=False)
         return list(enc.ids if hasattr(enc, "ids") else enc)
 
+    def _ids_batch(self, texts: Sequence[str]) -> List[List[int]]:
+        """`[_ids(t) for t in texts]`; one device batch when the tokenizer is a `GpuWordPieceTokenizer`."""
+        from .wordpiece import GpuWordPieceTokenizer
+
+        if isinstance(self.tokenizer, GpuWordPieceTokenizer):
+            return self.tokenizer.ids_batch(list(texts), max_length=2 ** 31 - 1, add_special_tokens=False)
+        return [self._ids(t) for t in texts]
+
     def score(self, question: str, texts: Sequence[str]) -> List[float]:
-        q = self._ids(question)
         sh = self.engine.shape
-        packed = [pack_pair(q, self._ids(t), sh.cls_token_id, sh.sep_token_id, self.max_length) for t in texts]
+        q, *docs = self._ids_batch([question, *texts])
+        packed = [pack_pair(q, d, sh.cls_token_id, sh.sep_token_id, self.max_length) for d in docs]
         scores: List[float] = []
         for start, end in greedy_batches([len(p[0]) for p in packed], self.engine.max_seqs, self.engine.max_tokens):
             if end == start:
@@ -180,9 +189,9 @@ class GpuCrossEncoderReranker(BaseReranker):
         for qi, (question, texts) in enumerate(zip(questions, texts_per_question)):
             if not texts:
                 continue
-            q = self._ids(question)
-            for t in texts:
-                packed.append(pack_pair(q, self._ids(t), sh.cls_token_id, sh.sep_token_id, self.max_length))
+            q, *docs = self._ids_batch([question, *texts])
+            for d in docs:
+                packed.append(pack_pair(q, d, sh.cls_token_id, sh.sep_token_id, self.max_length))
                 owner.append(qi)
         scores = [0.0] * len(packed)
         for idx in self._device_batches(packed):
