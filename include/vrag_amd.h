@@ -466,6 +466,63 @@ int vrag_wordpiece_encode(vrag_wordpiece* h, const uint8_t* text, const int64_t*
                           int32_t add_special_tokens, int32_t max_length, int64_t cap, int32_t* ids /*[cap]*/,
                           int32_t* seq_lens /*[n_docs]*/, uint8_t* needs_host /*[n_docs]*/, int64_t* n_ids);
 
+/* ------------------------------------------------------------------------------------------
+ * Byte-level BPE tokenisation of raw texts (csrc/bpe.hip): the ids HF `tokenizers` returns for the pipeline
+ * [NFC] -> ByteLevel(add_prefix_space = false, use_regex = true) -> BPE -> `<cls> $A <sep>` with truncation from the right.
+ *   Code points  decoded as the full-text analyzer above decodes them; per code point the committed table csrc/bpe_table.inc
+ *   (tools/gen_bpe_table.py; it records the unicodedata and tokenizers versions it was generated and verified with) gives the
+ *   class L (general category L*), N (N*), W (the White_Space property) or O (anything else), NFC_Quick_Check and the
+ *   canonical combining class.
+ *   needs_host is set for a text -- its ids are then unspecified, and the caller tokenises it on the host -- that holds
+ *     a code point the table does not cover (unassigned, private use or surrogate in the table's Unicode version; U+FFFD, which
+ *     is also what ill-formed UTF-8 decodes to);
+ *     with VRAG_BPE_NFC, a code point with NFC_Quick_Check != Yes, or a code point of combining class c > 0 behind one of a
+ *     larger class (the UAX #15 quick check: any other text IS its own NFC form, and the device normalises nothing);
+ *     a pre-token of more than VRAG_BPE_MAX_WORD_BYTES bytes; a run of U+0020 that spans more than 256 tiles (1 MiB); a
+ *     contraction within 3 bytes behind a tile boundary that more than 256 U+0020 precede.
+ *   Space runs   space_run_id[n] >= 0 (2 <= n <= 64) says that the run of n U+0020 is an added token with that id (set S).  A
+ *   maximal run of r U+0020 is consumed from the left, every step taking the largest n in S that is <= what remains (HF's
+ *   leftmost-longest match); what is left over is ordinary text.  These tokens cut a text into SEGMENTS.
+ *   Pre-tokens   within a segment, the matches of the GPT-2 pattern
+ *       's|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+
+ *   as a rule local to one code point c with predecessor p and successor q in the segment.  c starts a pre-token when it
+ *   starts the segment, and otherwise
+ *     c in L: not when an ACTIVE contraction that begins 1 or 2 code points in front still covers c; always when one ends
+ *             right in front of c; else unless p is in L or is U+0020
+ *     c in N / O: unless p is of the same class or is U+0020
+ *     c in W: when p is not in W, or q exists and is not in W (the last white space in front of a non-space is left over by
+ *             `\s+(?!\S)`; U+0020 then joins the piece behind it by the rules above, any other stands alone)
+ *   An apostrophe is ACTIVE when it starts its segment or p is in L, N or W other than U+0020 (behind U+0020 or a code point of
+ *   O it is absorbed by ` ?[^\s\p{L}\p{N}]+`), and the case-sensitive suffix s, t, m, d, re, ve or ll follows it.
+ *   BPE, per pre-token: one symbol per byte (byte_id), then, while any adjacent pair is in the merge table, the pair of the lowest
+ *   rank -- the leftmost among equals -- is replaced by its merged id.  The merge table is a hash table in device memory keyed by
+ *   (left id, right id); every hit is confirmed on the full key.  With VRAG_BPE_IGNORE_MERGES a pre-token whose bytes are a
+ *   `whole` entry gets that id directly (hash of the bytes, confirmed byte for byte).
+ *   Packing as vrag_wordpiece_encode.
+ * Host pointers; the call synchronises; calls on one handle are serialised. */
+#define VRAG_BPE_NFC 1            /* the file's normalizer is NFC: prove every text NFC or flag it */
+#define VRAG_BPE_IGNORE_MERGES 2
+#define VRAG_BPE_MAX_WORD_BYTES 64 /* one pre-token per wave64, one symbol per lane */
+#define VRAG_BPE_MAX_SPACE_RUN 64  /* longest run of U+0020 that can be an added token */
+#define VRAG_BPE_MAX_BATCH_BYTES (512ll << 20) /* text bytes one vrag_bpe_encode call takes */
+#define VRAG_BPE_TILE_BYTES 4096   /* text bytes per workgroup of the boundary passes */
+typedef struct vrag_bpe vrag_bpe;
+/* Merge r (rank r, 0 <= r < n_merges < 2^26) replaces the adjacent ids (merge_left[r], merge_right[r]) by merge_id[r]; no two
+ * merges have the same pair.  byte_id[b] is the id of byte b's character of the byte-level alphabet.  space_run_id[n] as
+ * above (-1: no such token; entries 0 and 1 must be -1).  whole_*: only with VRAG_BPE_IGNORE_MERGES -- entry i is the bytes
+ * whole_blob[whole_off[i] .. whole_off[i+1]) (1 .. VRAG_BPE_MAX_WORD_BYTES of them, no two alike) with id whole_id[i].  All ids
+ * in 0 .. n_vocab - 1. */
+int vrag_bpe_create(int32_t n_vocab, const int32_t* merge_left, const int32_t* merge_right, const int32_t* merge_id, int32_t n_merges,
+                    const int32_t* byte_id /*[256]*/, const int32_t* space_run_id /*[VRAG_BPE_MAX_SPACE_RUN+1]*/,
+                    const uint8_t* whole_blob, const int64_t* whole_off /*[n_whole+1]*/, const int32_t* whole_id, int32_t n_whole,
+                    int32_t cls_id, int32_t sep_id, int32_t flags, int32_t device, vrag_bpe** out);
+void vrag_bpe_destroy(vrag_bpe* h);
+/* As vrag_wordpiece_encode: at most VRAG_BPE_MAX_BATCH_BYTES of text per call and bytes + 2 * n_docs < 2^31; seq_lens,
+ * needs_host and n_ids are always filled in, ids only when n_ids <= cap (else VRAG_ERR_CAPACITY). */
+int vrag_bpe_encode(vrag_bpe* h, const uint8_t* text, const int64_t* doc_off /*[n_docs+1]*/, int32_t n_docs,
+                    int32_t add_special_tokens, int32_t max_length, int64_t cap, int32_t* ids /*[cap]*/,
+                    int32_t* seq_lens /*[n_docs]*/, uint8_t* needs_host /*[n_docs]*/, int64_t* n_ids);
+
 /* Cross-shard merge of per-shard top-k lists (the reference has no sharding -- this is the step after the
  * all-gather of `[n_lists][nq][k_in]` (fp32 score, global row id) lists, each sorted by (score desc, id asc) with
  * id = -1 entries as a tail).  Writes the first k_out entries of the merged order per query (-inf / -1 padded).

@@ -3,7 +3,9 @@ with `tokenizer="host"` and `"gpu"`: 2 000 synthetic ~2.5 KB texts over a synthe
   per_text_loop   `TokenizerAdapter.ids` once per text (what the providers did)
   hf_encode_batch HF `tokenizers` encode_batch on 16 threads
   device          `GpuWordPieceTokenizer.encode_batch`: host->device copy of the text, kernels, device->host copy of the ids
-Writes profiles/wordpiece_bench.json (median of `--reps` runs after one warm-up)."""
+Writes profiles/wordpiece_bench.json (median of `--reps` runs after one warm-up).
+`--bpe`: the same three baselines for the byte-level BPE pipeline of the ModernBERT checkpoints (`GpuByteBpeTokenizer`) over a
+BPE vocabulary trained here on the synthetic texts, NFC + space-run tokens 2..24; writes profiles/bpe_bench.json."""
 from __future__ import annotations
 
 import argparse
@@ -18,6 +20,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "wordpiece_bench.json")
 
 
 def synth_vocab(n: int, seed: int = 0):
@@ -81,6 +84,60 @@ def synth_texts(pieces, n: int, n_bytes: int, seed: int = 1):
     return texts
 
 
+def write_bpe_tokenizer(path: str, texts, vocab_size: int) -> str:
+    """A ModernBERT-style tokenizer.json (NFC, ByteLevel, BPE, runs of 2..24 spaces as added tokens) trained on `texts`."""
+    from tokenizers import AddedToken, Tokenizer, models, normalizers, pre_tokenizers, processors, trainers
+
+    tok = Tokenizer(models.BPE())
+    tok.normalizer = normalizers.NFC()
+    tok.pre_tokenizer = pre_tokenizers.ByteLevel(add_prefix_space=False, use_regex=True)
+    tok.train_from_iterator(texts, trainers.BpeTrainer(vocab_size=vocab_size, special_tokens=["[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"],
+                                                       initial_alphabet=pre_tokenizers.ByteLevel.alphabet(), show_progress=False))
+    tok.add_tokens([AddedToken(" " * n, normalized=True) for n in range(2, 25)])
+    tok.post_processor = processors.TemplateProcessing(single="[CLS] $A [SEP]", pair="[CLS] $A [SEP] $B:1 [SEP]:1",
+                                                       special_tokens=[("[CLS]", 2), ("[SEP]", 3)])
+    tok.save(path)
+    return path
+
+
+def bench_bpe(args) -> int:
+    import numpy as np
+    from tokenizers import Tokenizer
+
+    import verbatim_rag_amd  # noqa: F401
+    from verbatim_rag_amd.bpe import GpuByteBpeTokenizer
+    from verbatim_rag_amd.packing import TokenizerAdapter
+
+    rng = random.Random(2)
+    texts = []
+    for t in synth_texts(synth_vocab(30522), args.texts, args.bytes):      # contractions, double spaces and newlines as real text has them
+        words = t.split(" ")
+        texts.append("".join(w + rng.choice(["'s", "'re", "", "", "", ""]) + rng.choice([" "] * 12 + ["  ", "\n", ". "]) for w in words))
+    with tempfile.TemporaryDirectory() as tmp:
+        path = write_bpe_tokenizer(os.path.join(tmp, "tokenizer.json"), texts[:200], args.vocab)
+        hf = Tokenizer.from_file(path)
+        gpu = GpuByteBpeTokenizer.from_file(path)
+    adapter = TokenizerAdapter(hf, sep_token_id=3, cls_token_id=2)
+    want = [adapter.ids(t, add_special_tokens=True, max_length=512) for t in texts]
+    ids, lens = gpu.encode_batch(texts)
+    assert ids.tolist() == [i for w in want for i in w] and gpu.fallback_count == 0, "device ids differ from HF's"
+    res = {"pipeline": "NFC + ByteLevel + BPE", "texts": len(texts), "mean_text_bytes": sum(len(t) for t in texts) / len(texts),
+           "vocab": gpu.vocab_size, "max_length": 512, "mean_ids_per_text": float(np.mean(lens)), "reps": args.reps,
+           "hf_threads": os.environ["RAYON_NUM_THREADS"], "ms": {}}
+    res["ms"]["per_text_loop"] = median_ms(lambda: [adapter.ids(t, add_special_tokens=True, max_length=512) for t in texts], args.reps)
+    res["ms"]["hf_encode_batch"] = median_ms(lambda: hf.encode_batch(texts, add_special_tokens=False), args.reps)
+    res["ms"]["device"] = median_ms(lambda: gpu.encode_batch(texts), args.reps)
+    res["ms"]["device_ids_as_lists"] = median_ms(lambda: gpu.ids_batch(texts, max_length=512, add_special_tokens=True), args.reps)
+    res["texts_per_s"] = {k: len(texts) / (v / 1e3) for k, v in res["ms"].items()}
+    gpu.close()
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "bpe_bench.json")
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+    return 0
+
+
 def median_ms(fn, reps):
     fn()
     times = []
@@ -97,9 +154,12 @@ def main() -> int:
     ap.add_argument("--bytes", type=int, default=2500)
     ap.add_argument("--vocab", type=int, default=30522)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wordpiece_bench.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
+    ap.add_argument("--bpe", action="store_true", help="the byte-level BPE pipeline instead (profiles/bpe_bench.json)")
     args = ap.parse_args()
     os.environ.setdefault("RAYON_NUM_THREADS", "16")
+    if args.bpe:
+        return bench_bpe(args)
     import numpy as np
     from tokenizers import Tokenizer
 

@@ -147,6 +147,10 @@ SIGNATURES = {
                                         C.c_int32, C.POINTER(_H)]),
     "vrag_wordpiece_destroy": (None, [_H]),
     "vrag_wordpiece_encode": (C.c_int, [_H, C.c_void_p, _LP, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _IP, _IP, C.c_void_p, _LP]),
+    "vrag_bpe_create": (C.c_int, [C.c_int32, _IP, _IP, _IP, C.c_int32, _IP, _IP, C.c_void_p, _LP, _IP, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_int32, C.c_int32, C.POINTER(_H)]),
+    "vrag_bpe_destroy": (None, [_H]),
+    "vrag_bpe_encode": (C.c_int, [_H, C.c_void_p, _LP, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _IP, _IP, C.c_void_p, _LP]),
     "vrag_comm_get_unique_id": (C.c_int, [C.c_void_p]),
     "vrag_comm_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_H)]),
     "vrag_comm_destroy": (None, [_H]),

@@ -1,4 +1,4 @@
-// UTF-8 decoding and the block / device scans shared by the text kernels (csrc/fulltext.hip, csrc/wordpiece.hip).
+// UTF-8 decoding and the block / device scans shared by the text kernels (csrc/fulltext.hip, csrc/wordpiece.hip, csrc/bpe.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,6 +38,32 @@ __device__ __forceinline__ unsigned decode_at(const unsigned char* __restrict__ 
   const unsigned least = need == 1 ? 0x80u : need == 2 ? 0x800u : 0x10000u;
   if (cp < least || (cp >= 0xD800u && cp <= 0xDFFFu) || cp > 0x10FFFFu) return 0xFFFDu;
   return cp;
+}
+
+// Does a code point of the text [lo, hi) start at byte i?  Every byte that is not a continuation byte does; a continuation
+// byte does when the sequence of the nearest lead byte in front of it (within 3 bytes) does not reach it (U+FFFD of one byte).
+__device__ __forceinline__ bool cp_start(const unsigned char* __restrict__ t, long long i, long long lo, long long hi) {
+  if (!is_cont(t[i])) return true;
+  for (int k = 1; k <= 3 && i - k >= lo; ++k)
+    if (!is_cont(t[i - k])) {
+      int len;
+      (void)decode_at(t, i - k, hi, &len);
+      return len <= k;
+    }
+  return true;
+}
+
+// Start byte of the code point that ends right before byte j (lo < j, j a code point start).
+__device__ __forceinline__ long long prev_start(const unsigned char* __restrict__ t, long long j, long long lo, long long hi) {
+  long long k = j - 1;
+  int back = 0;
+  while (k > lo && back < 3 && is_cont(t[k])) {
+    --k;
+    ++back;
+  }
+  int len;
+  (void)decode_at(t, k, hi, &len);
+  return k + len == j ? k : j - 1;
 }
 
 // Document of byte i: the last d with off[d] <= i (empty documents are skipped over).

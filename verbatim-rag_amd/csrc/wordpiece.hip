@@ -10,8 +10,8 @@
 //             live in the lane's scratch, so the hash of any [s, e) is two multiply-adds; greedy longest match probes an
 //             open-addressing table {hash, id} in HBM and confirms every hit against the piece's stored bytes.  A word's
 //             ids go to a scratch array at its start byte (a word never has more ids than source bytes).
-//   pack      wp_seq_len_kernel (ids per text after truncation), scans, wp_gather_kernel (one lane per word copies its
-//             ids that survive truncation), wp_special_kernel ([CLS] / [SEP]).
+//   pack      token_pack.h: pack_seq_len_kernel (ids per text after truncation), scans, pack_gather_kernel (one lane per word copies its
+//             ids that survive truncation), pack_special_kernel ([CLS] / [SEP]).
 // Integer work only; vector stores only.
 #include "../../include/vrag_amd.h"
 
@@ -24,6 +24,7 @@
 
 #include "common.h"
 #include "host_util.h"
+#include "token_pack.h"
 #include "utf8_text.h"
 
 namespace vrag {
@@ -60,32 +61,6 @@ __device__ __forceinline__ int kind_of(unsigned w, int flags, bool* notcov) {
   if (n == 0u) return K_SKIP;
   if (((flags & VRAG_WP_CHINESE_CHARS) && (cls & C_CJK)) || (cls & C_PUNCT)) return K_SOLO;
   return K_WORD;
-}
-
-// Does a code point of the text [lo, hi) start at byte i?  Every byte that is not a continuation byte does; a continuation
-// byte does when the sequence of the nearest lead byte in front of it (within 3 bytes) does not reach it (U+FFFD of one byte).
-__device__ __forceinline__ bool cp_start(const unsigned char* __restrict__ t, long long i, long long lo, long long hi) {
-  if (!is_cont(t[i])) return true;
-  for (int k = 1; k <= 3 && i - k >= lo; ++k)
-    if (!is_cont(t[i - k])) {
-      int len;
-      (void)decode_at(t, i - k, hi, &len);
-      return len <= k;
-    }
-  return true;
-}
-
-// Start byte of the code point that ends right before byte j (lo < j, j a code point start).
-__device__ __forceinline__ long long prev_start(const unsigned char* __restrict__ t, long long j, long long lo, long long hi) {
-  long long k = j - 1;
-  int back = 0;
-  while (k > lo && back < 3 && is_cont(t[k])) {
-    --k;
-    ++back;
-  }
-  int len;
-  (void)decode_at(t, k, hi, &len);
-  return k + len == j ? k : j - 1;
 }
 
 // Is the nearest code point in front of byte i that does not vanish a word character?  Gives the text up (needs_host)
@@ -309,41 +284,6 @@ __global__ __launch_bounds__(256) void wp_match_kernel(const unsigned char* __re
   if (n_tok) atomicAdd(body + d, n_tok);
 }
 
-// ids of every text after truncation, specials included
-__global__ void wp_seq_len_kernel(const unsigned* __restrict__ body, int n_docs, int special, int max_length, unsigned* __restrict__ seq_len) {
-  const int d = blockIdx.x * blockDim.x + threadIdx.x;
-  if (d >= n_docs) return;
-  const unsigned keep = (unsigned)(special ? max_length - 2 : max_length);
-  seq_len[d] = min(body[d], keep) + (special ? 2u : 0u);
-}
-
-// One lane per word: the ids of the word that lie below the text's truncation limit, at their place in the output.
-__global__ void wp_gather_kernel(const unsigned* __restrict__ wstart, const unsigned* __restrict__ wdoc, long long n_words,
-                                 const int* __restrict__ tok, const unsigned* __restrict__ tok_scan, const unsigned* __restrict__ out_off,
-                                 int special, int max_length, int* __restrict__ ids) {
-  const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (w >= n_words) return;
-  const unsigned d = wdoc[w];
-  long long lo = 0, hi = w;   // first word of text d
-  while (lo < hi) {
-    const long long mid = (lo + hi) >> 1;
-    if (wdoc[mid] < d) lo = mid + 1;
-    else hi = mid;
-  }
-  const unsigned keep = (unsigned)(special ? max_length - 2 : max_length);
-  const unsigned first = tok_scan[w] - tok_scan[lo], n = tok_scan[w + 1] - tok_scan[w];
-  int* out = ids + out_off[d] + (special ? 1 : 0);
-  const int* src = tok + wstart[w];
-  for (unsigned j = 0; j < n && first + j < keep; ++j) out[first + j] = src[j];
-}
-
-__global__ void wp_special_kernel(const unsigned* __restrict__ out_off, int n_docs, int cls_id, int sep_id, int* __restrict__ ids) {
-  const int d = blockIdx.x * blockDim.x + threadIdx.x;
-  if (d >= n_docs) return;
-  ids[out_off[d]] = cls_id;
-  ids[out_off[d + 1] - 1u] = sep_id;
-}
-
 }  // namespace wp
 }  // namespace vrag
 
@@ -552,7 +492,7 @@ int vrag_wordpiece_encode(vrag_wordpiece* h, const uint8_t* text, const int64_t*
     HIP_TRY(hipGetLastError());
     HIP_TRY(scan_u32(h->tok_cnt.p, n_words, h->tok_scan.p, st));
   }
-  hipLaunchKernelGGL(wp_seq_len_kernel, dim3(grid_of(n_docs, 256)), dim3(256), 0, st, h->body.p, (int)n_docs, special, (int)max_length,
+  hipLaunchKernelGGL(pack_seq_len_kernel, dim3(grid_of(n_docs, 256)), dim3(256), 0, st, h->body.p, (int)n_docs, special, (int)max_length,
                      h->seq_len.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(scan_u32(h->seq_len.p, n_docs, h->out_off.p, st));
@@ -564,10 +504,10 @@ int vrag_wordpiece_encode(vrag_wordpiece* h, const uint8_t* text, const int64_t*
   if ((int64_t)total <= cap && total) {
     HIP_TRY(h->ids.grow(total));
     if (n_words)
-      hipLaunchKernelGGL(wp_gather_kernel, dim3(grid_of(n_words, 256)), dim3(256), 0, st, h->wstart.p, h->wdoc.p, (long long)n_words, h->tok.p,
+      hipLaunchKernelGGL(pack_gather_kernel, dim3(grid_of(n_words, 256)), dim3(256), 0, st, h->wstart.p, h->wdoc.p, (long long)n_words, h->tok.p,
                          h->tok_scan.p, h->out_off.p, special, (int)max_length, h->ids.p);
     if (special)
-      hipLaunchKernelGGL(wp_special_kernel, dim3(grid_of(n_docs, 256)), dim3(256), 0, st, h->out_off.p, (int)n_docs, h->cls_id, h->sep_id,
+      hipLaunchKernelGGL(pack_special_kernel, dim3(grid_of(n_docs, 256)), dim3(256), 0, st, h->out_off.p, (int)n_docs, h->cls_id, h->sep_id,
                          h->ids.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(ids, h->ids.p, (size_t)total * 4, hipMemcpyDeviceToHost, st));

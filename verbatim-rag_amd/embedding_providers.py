@@ -83,14 +83,27 @@ class _EncoderProvider:
 
 
 def load_model_tokenizer(model_path: str, tokenizer: str = "host", device: int = 0) -> Any:
-    """The tokenizer of a checkpoint directory: "host" = `load_tokenizer` (HF, on the caller's thread), "gpu" = a
-    `GpuWordPieceTokenizer` over the directory's tokenizer.json (ValueError for anything but the BERT WordPiece pipeline)."""
+    """The tokenizer of a checkpoint directory: "host" = `load_tokenizer` (HF, on the caller's thread), "gpu" = a device
+    tokenizer over the directory's tokenizer.json: `GpuByteBpeTokenizer` for a BPE model behind a ByteLevel pre-tokenizer
+    (ModernBERT checkpoints), `GpuWordPieceTokenizer` for every other file (ValueError naming the component for anything but
+    the BERT WordPiece pipeline).  The dispatch only looks at `model.type` and `pre_tokenizer.type`; the class it picks reads and
+    validates the file itself, so a missing or malformed tokenizer.json is reported from here."""
     if tokenizer == "host":
         return load_tokenizer(model_path)
     if tokenizer != "gpu":
         raise ValueError(f"tokenizer must be 'host' or 'gpu', got {tokenizer!r}")
+    import json
+    import os
+
     from .wordpiece import GpuWordPieceTokenizer
 
+    path = os.path.join(model_path, "tokenizer.json") if os.path.isdir(model_path) else model_path
+    with open(path, encoding="utf-8") as f:
+        spec = json.load(f)
+    if (spec.get("model") or {}).get("type") == "BPE" and (spec.get("pre_tokenizer") or {}).get("type") == "ByteLevel":
+        from .bpe import GpuByteBpeTokenizer
+
+        return GpuByteBpeTokenizer.from_file(path, device=device)
     return GpuWordPieceTokenizer.from_file(model_path, device=device)
 
 
@@ -197,7 +210,7 @@ class GpuSpladeProvider(_EncoderProvider, SparseEmbeddingProvider):
     def from_directory(cls, model_path: str, device: int = 0, max_length: int = 512, operand_dtype: str = "f16",
                        tokenizer: str = "host", **kw) -> "GpuSpladeProvider":
         """`SpladeProvider(model_name, device)` (embedding_providers.py:120-133) for a checkpoint on disk.  `tokenizer="gpu"`:
-        WordPiece on the device (wordpiece.py), same ids."""
+        WordPiece (wordpiece.py) or, for a ModernBERT checkpoint, byte-level BPE (bpe.py) on the device, same ids."""
         engine, tokenizer, rebuild = load_checked_directory(model_path, device=device, max_seq_len=max_length, operand_dtype=operand_dtype,
                                                             tokenizer=tokenizer)
         self = cls(engine, tokenizer, max_length=max_length, **kw)
@@ -275,8 +288,8 @@ class GpuDenseProvider(_EncoderProvider, DenseEmbeddingProvider):
     def from_directory(cls, model_path: str, device: int = 0, max_length: int = 512, pooling: Optional[str] = None,
                        normalize: bool = True, operand_dtype: str = "f16", tokenizer: str = "host") -> "GpuDenseProvider":
         """`SentenceTransformersProvider(model_name, device)` (embedding_providers.py:55-71) for a checkpoint on disk;
-        the pooling mode comes from the checkpoint's `1_Pooling/config.json` unless given.  `tokenizer="gpu"`: WordPiece on the
-        device (wordpiece.py), same ids."""
+        the pooling mode comes from the checkpoint's `1_Pooling/config.json` unless given.  `tokenizer="gpu"`: WordPiece or
+        byte-level BPE on the device (wordpiece.py, bpe.py), same ids."""
         engine, tokenizer, rebuild = load_checked_directory(model_path, device=device, max_seq_len=max_length, operand_dtype=operand_dtype,
                                                             tokenizer=tokenizer)
         self = cls(engine, tokenizer, pooling=pooling or _st_pooling_mode(model_path), normalize=normalize, max_length=max_length)

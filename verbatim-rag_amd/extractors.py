@@ -117,6 +117,8 @@ class GpuModelSpanExtractor(SpanExtractor):
 
     Construct either from a local HF checkpoint directory (`model_path`: config.json +
     *.safetensors [+ tokenizer.json]) or from an already-built `engine` + `tokenizer`.
+    With `model_path`, `tokenizer` may also be "host" (the default: HF on the caller's thread) or "gpu" (the checkpoint's
+    tokenizer.json on the device, same ids; sentence-classifier format only -- the highlighter needs character offsets).
     Raises at construction when the HIP library or a GPU is missing -- there is no CPU path.
     """
 
@@ -174,8 +176,8 @@ class GpuModelSpanExtractor(SpanExtractor):
         self.device = f"cuda:{dev}"
 
         if engine is not None:
-            if tokenizer is None:
-                raise ValueError("engine= needs tokenizer=")
+            if tokenizer is None or isinstance(tokenizer, str):
+                raise ValueError("engine= needs tokenizer= (a tokenizer object)")
             engines, rebuild = [engine, *extra_engines], None
             self._format = model_format or (
                 self._FORMAT_HIGHLIGHTER if getattr(engine, "token_labels", 0) and not getattr(engine, "qa_labels", 0)
@@ -186,6 +188,18 @@ class GpuModelSpanExtractor(SpanExtractor):
                     f"model_path={model_path!r}: a local HF checkpoint directory is required (no network here); "
                     "or pass engine= and tokenizer=")
             self._format = model_format or self._detect_format(model_path)
+            if isinstance(tokenizer, str):
+                if tokenizer not in ("host", "gpu"):
+                    raise ValueError(f"tokenizer must be 'host', 'gpu' or a tokenizer object, got {tokenizer!r}")
+                if tokenizer == "gpu" and self._format == self._FORMAT_HIGHLIGHTER:
+                    raise ValueError('tokenizer="gpu" yields no character offsets, which the highlighter format needs; use tokenizer="host"')
+                # "gpu": question and sentence ids come from device batches (bpe.py / wordpiece.py) through ids / ids_batch
+                if tokenizer == "gpu":
+                    from .embedding_providers import load_model_tokenizer
+
+                    tokenizer = load_model_tokenizer(model_path, "gpu", device=dev)
+                else:
+                    tokenizer = None
             # Further handles of the same model (own weights copy + workspace + streams): a multi-sub-batch call alternates
             # between them from worker threads, so one handle's upload / read-back / host turnaround hides behind the
             # other's kernels (measured 0.42 -> 0.33 s for 5000 pairs, DESIGN.md "Serving shape").

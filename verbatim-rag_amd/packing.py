@@ -114,9 +114,10 @@ class TokenizerAdapter:
         """Special-token ids from the tokenizer when it defines them, otherwise from the model's config.json (`shape`): a
         raw `tokenizers.Tokenizer`, or an HF fast tokenizer loaded from a directory that holds only tokenizer.json,
         knows the template but not which ids are [CLS] / [SEP]."""
+        from .bpe import GpuByteBpeTokenizer
         from .wordpiece import GpuWordPieceTokenizer
 
-        if isinstance(tokenizer, GpuWordPieceTokenizer):    # offers ids / ids_batch itself, with the ids of its own vocabulary
+        if isinstance(tokenizer, (GpuWordPieceTokenizer, GpuByteBpeTokenizer)):    # offers ids / ids_batch itself, with the ids of its own vocabulary
             return tokenizer
 
         def override(name):
@@ -140,7 +141,7 @@ class TokenizerAdapter:
     def ids_batch(self, texts: Sequence[str], max_length: int, add_special_tokens: bool = False) -> List[List[int]]:
         """Sentences are tokenised independently with add_special_tokens=False (dataset.py:161-167),
         so one batched call is bit-identical to the reference's per-sentence calls.  add_special_tokens=True: `ids` of
-        every text (the providers' call; a `GpuWordPieceTokenizer` answers it with one device batch instead)."""
+        every text (the providers' call; a device tokenizer answers it with one device batch instead)."""
         if not texts:
             return []
         if add_special_tokens:

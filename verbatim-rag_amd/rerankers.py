@@ -99,8 +99,8 @@ class GpuCrossEncoderReranker(BaseReranker):
         `BertForSequenceClassification` (e.g. a downloaded `cross-encoder/ms-marco-MiniLM-L-6-v2`; defaults: 512 tokens,
         the loader's fp16 operands) or a `ModernBertForSequenceClassification` (e.g. `gte-reranker-modernbert-base`;
         defaults: the checkpoint's `max_position_embeddings` as CrossEncoder takes it, bf16 operands -- a pooled logit feeds
-        an ordering, like the sentence classifier's).  `tokenizer="gpu"` (BERT checkpoints only: a
-        ModernBERT checkpoint's byte-level BPE is refused with a ValueError): WordPiece on the device, same ids."""
+        an ordering, like the sentence classifier's).  `tokenizer="gpu"`: WordPiece (BERT checkpoints)
+        or byte-level BPE (ModernBERT checkpoints) on the device, same ids."""
         import json
         import os
 
@@ -126,10 +126,11 @@ class GpuCrossEncoderReranker(BaseReranker):
         return list(enc.ids if hasattr(enc, "ids") else enc)
 
     def _ids_batch(self, texts: Sequence[str]) -> List[List[int]]:
-        """`[_ids(t) for t in texts]`; one device batch when the tokenizer is a `GpuWordPieceTokenizer`."""
+        """`[_ids(t) for t in texts]`; one device batch when the tokenizer is a device tokenizer."""
+        from .bpe import GpuByteBpeTokenizer
         from .wordpiece import GpuWordPieceTokenizer
 
-        if isinstance(self.tokenizer, GpuWordPieceTokenizer):
+        if isinstance(self.tokenizer, (GpuWordPieceTokenizer, GpuByteBpeTokenizer)):
             return self.tokenizer.ids_batch(list(texts), max_length=2 ** 31 - 1, add_special_tokens=False)
         return [self._ids(t) for t in texts]
 
