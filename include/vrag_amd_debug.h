@@ -1,7 +1,8 @@
 /* vrag_amd_debug.h -- tuning / unit-test harness of the gfx950 kernels.  NOT part of the product ABI (include/vrag_amd.h):
  * these entry points exist only in libvrag_amd_dbg.so, the harness build of the same sources (verbatim-rag_amd/build.py,
  * -DVRAG_DEBUG_API: it also keeps the phase-decomposition branches of the fused kernel that the product build compiles out).
- * tools/, tests/test_attention_unit_gpu.py and tests/test_gemm_unit_gpu.py load it beside the product library. */
+ * tools/, tests/test_attention_unit_gpu.py, tests/test_gemm_unit_gpu.py and tests/test_qkv_attn_unit_gpu.py load it beside the
+ * product library. */
 #ifndef VRAG_AMD_DEBUG_H
 #define VRAG_AMD_DEBUG_H
 
@@ -69,6 +70,36 @@ typedef struct vrag_debug_gemm_args {
   int32_t f16_saturated;     /* out: an fp16 conversion of this launch clamped at +-65504 */
 } vrag_debug_gemm_args;
 int vrag_debug_gemm_run(vrag_debug_gemm_args* args, int32_t device);
+
+/* Unit-test hook of the fused Wqkv + RoPE + attention kernel alone (csrc/qkv_attn.hip): host buffers in, ONE launch with
+ * debug_flags = 0, outputs copied back.  w and ln_s arrive in the encoder's UNPERMUTED Wqkv layout (rows q | k | v of all heads);
+ * the hook runs permute_qkv_heads on them as the encoder does at load (ln_s with 64 readable floats behind the last head).
+ * Refused before anything is launched: null required pointers, H != 64 * nh, rows % 256 != 0, seq_len outside 1..512,
+ * seq_row % 8 != 0, overlapping sequences, and a sequence with seq_row + 64 * ceil(len / 64) > rows (a wave reads 64 WHOLE token
+ * rows, whatever its sequence's length: the encoder's row slack pays for that, the hook does not hide it). */
+typedef struct vrag_debug_qkv_attn_args {
+  const uint16_t* x;         /* [rows, H] */
+  const uint16_t* w;         /* [3 H, H] */
+  const float* ln_s;         /* [3 H], null without the fold */
+  const float* ln_mu;        /* [rows]; null = the no-fold instantiation */
+  const float* ln_rstd;      /* [rows] */
+  const float* rope_cos;     /* [rope_rows, 32] */
+  const float* rope_sin;     /* [rope_rows, 32] */
+  uint16_t* o;               /* in / out [rows, H]: copied to the device before the launch, so a canary survives where the kernel must not write */
+  const int32_t* seq_row;    /* [n_seqs] first row of each sequence */
+  const int32_t* seq_len;    /* [n_seqs] */
+  int32_t* groups_out;       /* out [n_seqs][8][4]: the wave descriptors that ran (QkvAttnParams::groups); the first n_groups * 8 are written */
+  int32_t rows, H, nh, rope_rows, n_seqs;
+  int32_t packer;            /* 0 = fused_pack_groups (first fit over consecutive sequences), 1 = the engine's best fit decreasing */
+  int32_t local, window, f16;
+  float q_scale;
+  int32_t n_groups;          /* out */
+  int32_t f16_saturated;     /* out: an fp16 conversion of this launch clamped at +-65504 */
+} vrag_debug_qkv_attn_args;
+int vrag_debug_qkv_attn_run(vrag_debug_qkv_attn_args* args, int32_t device);
+/* Host only (no GPU call): the wave descriptors either packer gives n sequences (lengths 1..512); out holds [n][8][4] int32.
+ * Returns the number of groups, or a negative status on bad arguments. */
+int vrag_debug_pack_groups(const int32_t* seq_row, const int32_t* seq_len, int32_t n, int32_t packer, int32_t* out);
 
 #ifdef __cplusplus
 }

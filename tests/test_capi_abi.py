@@ -131,16 +131,12 @@ def _host_cc():
     return None
 
 
-@pytest.mark.skipif(_host_cc() is None, reason="no host C compiler")
-def test_debug_gemm_args_layout_matches_ctypes(tmp_path):
-    """vrag_debug_gemm_args crosses the ctypes boundary of the GEMM unit test: sizeof and every offsetof as the host C compiler
-    lays the struct out must equal _lib.DebugGemmArgs."""
-    S = _lib.DebugGemmArgs
+def _check_layout(tmp_path, cname, S):
     names = [f[0] for f in S._fields_]
     src = tmp_path / "layout.c"
     src.write_text("#include <stddef.h>\n#include <stdio.h>\n#include \"vrag_amd_debug.h\"\nint main(void) {\n"
-                   "  printf(\"sizeof %zu\\n\", sizeof(vrag_debug_gemm_args));\n"
-                   + "".join(f"  printf(\"{n} %zu\\n\", offsetof(vrag_debug_gemm_args, {n}));\n" for n in names)
+                   f"  printf(\"sizeof %zu\\n\", sizeof({cname}));\n"
+                   + "".join(f"  printf(\"{n} %zu\\n\", offsetof({cname}, {n}));\n" for n in names)
                    + "  return 0;\n}\n")
     exe = tmp_path / "layout"
     subprocess.run([_host_cc(), "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
@@ -150,6 +146,19 @@ def test_debug_gemm_args_layout_matches_ctypes(tmp_path):
     assert {n: int(v) for n, v in got.items()} == {n: getattr(S, n).offset for n in names}
     # and the header declares no field the ctypes side lacks
     hdr = open(os.path.join(ROOT, "include", "vrag_amd_debug.h")).read()
-    body = re.sub(r"/\*.*?\*/", "", hdr[hdr.index("typedef struct vrag_debug_gemm_args"):hdr.index("} vrag_debug_gemm_args;")], flags=re.S)
+    body = re.sub(r"/\*.*?\*/", "", hdr[hdr.index("typedef struct " + cname):hdr.index("} " + cname + ";")], flags=re.S)
     declared = re.findall(r"\b([a-z_0-9A-Z]+)(?:\[\d+\])?\s*[,;]", body.split("{", 1)[1])
     assert declared == names
+
+
+@pytest.mark.skipif(_host_cc() is None, reason="no host C compiler")
+def test_debug_gemm_args_layout_matches_ctypes(tmp_path):
+    """vrag_debug_gemm_args crosses the ctypes boundary of the GEMM unit test: sizeof and every offsetof as the host C compiler
+    lays the struct out must equal _lib.DebugGemmArgs."""
+    _check_layout(tmp_path, "vrag_debug_gemm_args", _lib.DebugGemmArgs)
+
+
+@pytest.mark.skipif(_host_cc() is None, reason="no host C compiler")
+def test_debug_qkv_attn_args_layout_matches_ctypes(tmp_path):
+    """The same for vrag_debug_qkv_attn_args and _lib.DebugQkvAttnArgs (tests/test_qkv_attn_unit_gpu.py)."""
+    _check_layout(tmp_path, "vrag_debug_qkv_attn_args", _lib.DebugQkvAttnArgs)

@@ -13,18 +13,17 @@ the byte plane dropped, RoPE's partner d + 16, truncation).  `-rP` prints the wo
 tile configuration."""
 import ctypes as C
 import math
-from collections import defaultdict
 
 import numpy as np
 import pytest
 
 import verbatim_rag_amd  # noqa: F401
 from verbatim_rag_amd import _lib
+from unit16 import U, f32, from16, half_ulp, make_ledger, out16_bound, to16, trunc16
 
 pytestmark = pytest.mark.gpu
 
 EPI_F32, EPI_BF16, EPI_F32_GELU, EPI_RESIDUAL, EPI_GEGLU, EPI_QKV_ROPE, EPI_SPLADE = 0, 1, 2, 3, 4, 5, 6
-U = 2.0 ** -24          # fp32 unit roundoff
 BIG_ROWS = 1 << 30      # small-batch threshold that keeps every shape on the launch-bound configurations
 Q_SCALE = np.float32(0.125 * 1.4426950408889634)   # what the encoder passes: head_dim^-1/2 * log2 e
 
@@ -35,7 +34,7 @@ TILE256, TILE128 = (256, 256, 2, 4, 2, 0, 0), (128, 128, 2, 2, 2, 0, 0)
 ALL_CONFIGS = {KSPLIT: 1024, KCH64: 1024, KCH128: 256, SMALL8: 256, SMALL4: 256, TILE256: 256, TILE128: 512}
 
 _SEEN = set()                                  # (config, f16) of every launch of the module
-_WORST = defaultdict(float)                    # (form, config, f16) -> worst error / bound
+_WORST, record, control = make_ledger()        # (form, config, f16) -> worst error / bound
 
 
 def expected_config(epi, M, N, hidden=0, small_rows=8192):
@@ -49,67 +48,6 @@ def expected_config(epi, M, N, hidden=0, small_rows=8192):
     if N % 256 == 0 and M >= 256 and (epi != EPI_QKV_ROPE or hidden % 256 == 0):
         return TILE256
     return TILE128
-
-
-# ------------------------------------------------------------------ 16-bit helpers
-def to16(x, f16):
-    """float64 -> 16-bit bits (round to nearest even through fp32)."""
-    x32 = np.ascontiguousarray(x, np.float32)
-    if f16:
-        return x32.astype(np.float16).view(np.uint16)
-    u = x32.view(np.uint32)
-    return ((u + np.uint32(0x7FFF) + ((u >> 16) & 1)) >> 16).astype(np.uint16)
-
-
-def from16(b, f16):
-    b = np.ascontiguousarray(b, np.uint16)
-    if f16:
-        return b.view(np.float16).astype(np.float64)
-    return (b.astype(np.uint32) << 16).view(np.float32).astype(np.float64)
-
-
-def trunc16(x, f16):
-    """The nearest wrong kernel of a 16-bit store: round toward zero instead of to nearest even."""
-    x32 = np.ascontiguousarray(x, np.float32)
-    if not f16:
-        return from16((x32.view(np.uint32) >> 16).astype(np.uint16), False)
-    h = x32.astype(np.float16)
-    over = np.abs(h.astype(np.float64)) > np.abs(x32.astype(np.float64))
-    h[over] = np.nextafter(h[over], np.float16(0))
-    return h.astype(np.float64)
-
-
-def half_ulp(x, f16):
-    e = np.floor(np.log2(np.maximum(np.abs(x), 1e-300)))
-    return 2.0 ** (np.maximum(e, -14) - 11) if f16 else 2.0 ** (np.maximum(e, -126) - 8)
-
-
-def out16_bound(ref, e, f16):
-    return e + half_ulp(np.abs(ref) + e, f16)
-
-
-def f32(x):
-    return np.ascontiguousarray(x, np.float32)
-
-
-def record(form, cfg, f16, got, ref, bound):
-    err = np.abs(np.asarray(got, np.float64) - ref)
-    ratio = float(np.max(err / bound)) if err.size else 0.0
-    key = (form, cfg, f16)
-    _WORST[key] = max(_WORST[key], ratio)
-    bad = np.argwhere(~(err <= bound))
-    assert bad.size == 0, (f"{form} cfg={cfg} f16={f16}: {len(bad)} elements over the bound, first at {tuple(bad[0])}: "
-                           f"got {np.asarray(got).flat[np.ravel_multi_index(tuple(bad[0]), err.shape)]} "
-                           f"ref {ref.flat[np.ravel_multi_index(tuple(bad[0]), err.shape)]} worst ratio {ratio:.3g}")
-    return ratio
-
-
-def control(name, got_wrong, ref, bound, need=10.0):
-    """Negative control: the nearest wrong kernel's output must exceed the bound by `need` x somewhere."""
-    r = float(np.max(np.abs(np.asarray(got_wrong, np.float64) - ref) / bound))
-    _WORST[("control: " + name, None, None)] = r
-    assert r >= need, f"control {name}: the bound hides it (worst ratio {r:.3g} < {need})"
-    return r
 
 
 # ------------------------------------------------------------------ the hook

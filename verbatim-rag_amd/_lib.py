@@ -171,6 +171,8 @@ DEBUG_SIGNATURES = {
     "vrag_debug_attn_ms": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "vrag_debug_qkv_attn_ms": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "vrag_debug_gemm_run": (C.c_int, [C.c_void_p, C.c_int32]),
+    "vrag_debug_qkv_attn_run": (C.c_int, [C.c_void_p, C.c_int32]),
+    "vrag_debug_pack_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
 }
 
 
@@ -183,6 +185,16 @@ class DebugGemmArgs(C.Structure):
         "stats_part", "lo_out", "splade_rows")] + [(n, C.c_int32) for n in (
         "epi", "M", "N", "K", "f16", "act_gelu", "row0", "rows", "hidden", "rope_rows", "n_seqs", "small_rows")] + [
         ("q_scale", C.c_float), ("fin_eps", C.c_float), ("config", C.c_int32 * 7), ("f16_saturated", C.c_int32)]
+
+
+class DebugQkvAttnArgs(C.Structure):
+    """vrag_debug_qkv_attn_args (include/vrag_amd_debug.h), field for field; tests/test_capi_abi.py checks the layout too."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "x", "w", "ln_s", "ln_mu", "ln_rstd", "rope_cos", "rope_sin", "o", "seq_row", "seq_len", "groups_out")] + [
+        (n, C.c_int32) for n in ("rows", "H", "nh", "rope_rows", "n_seqs", "packer", "local", "window", "f16")] + [
+        ("q_scale", C.c_float), ("n_groups", C.c_int32), ("f16_saturated", C.c_int32)]
+
+
 _DBG = None
 
 

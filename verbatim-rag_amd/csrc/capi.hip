@@ -531,38 +531,6 @@ int check_ready(vrag_encoder* e) {
   return VRAG_OK;
 }
 
-// Groups of the fused QKV + attention kernel for sequences seq0 .. seq1 - 1: best-fit-decreasing bins of eight 64-token wave
-// slots over ALL of the micro-batch's sequences (a wave's descriptor carries its own first row, so the sequences of a group need
-// not be neighbours in the packed buffer -- fused_pack_groups of qkv_attn.hip, first fit over consecutive sequences, is the
-// simple form the diagnostics use).  A workgroup costs what a full one costs, and ceil(S / 64) slots per sequence is all the
-// kernel wastes then: 86 % fill for pairs of 64-512 tokens in ANY order (70 % with consecutive first fit).
-static int pack_groups_best_fit(const int* seq_row, const int* seq_len, int seq0, int seq1, int4* out) {
-  std::vector<int> by_need[9];
-  for (int s = seq0; s < seq1; ++s) by_need[std::min(8, (seq_len[s] + 63) / 64)].push_back(s);
-  std::vector<int> open_with[9];   // open groups by free slots
-  std::vector<int> used_of;        // slots taken per group
-  int n = 0;
-  for (int need = 8; need >= 1; --need)
-    for (int s : by_need[need]) {
-      int g = -1;
-      for (int room = need; room <= 8 && g < 0; ++room)   // best fit: the open group with the least room that still takes it
-        if (!open_with[room].empty()) {
-          g = open_with[room].back();
-          open_with[room].pop_back();
-        }
-      if (g < 0) {
-        g = n++;
-        used_of.push_back(0);
-        for (int w = 0; w < 8; ++w) out[g * 8 + w] = int4{0, 0, 0, 0};
-      }
-      const int used = used_of[g];
-      for (int j = 0; j < need; ++j) out[g * 8 + used + j] = int4{seq_row[s] + 64 * j, seq_len[s], used, 0};
-      used_of[g] = used + need;
-      open_with[8 - used_of[g]].push_back(g);
-    }
-  return n;
-}
-
 // Does this micro-batch take the fused Wqkv + RoPE + attention kernel (qkv_attn.hip)?  One rule for the schedule and for the
 // HIP-graph cache key: a graph captured on one path must never be replayed for a batch that takes the other.
 static bool fused_attention_for(const vrag_encoder* e, const MicroBatch& mb) {

@@ -520,4 +520,123 @@ int vrag_debug_gemm_run(vrag_debug_gemm_args* a, int32_t device) {
   return VRAG_OK;
 }
 
+int vrag_debug_pack_groups(const int32_t* seq_row, const int32_t* seq_len, int32_t n, int32_t packer, int32_t* out) {
+  ARG_CHECK(seq_row && seq_len && out && n > 0 && (packer == 0 || packer == 1), "bad arguments");
+  for (int s = 0; s < n; ++s) ARG_CHECK(seq_len[s] >= 1 && seq_len[s] <= kFusedMaxSeq, "seq_len[%d] = %d outside 1..%d", s, seq_len[s], kFusedMaxSeq);
+  static_assert(sizeof(int4) == 4 * sizeof(int32_t), "descriptor layout");
+  int4* g = reinterpret_cast<int4*>(out);
+  return packer ? pack_groups_best_fit(seq_row, seq_len, 0, n, g) : fused_pack_groups(seq_row, seq_len, 0, n, g);
+}
+
+int vrag_debug_qkv_attn_run(vrag_debug_qkv_attn_args* a, int32_t device) {
+  ARG_CHECK(a, "null arguments");
+  ARG_CHECK(a->x && a->w && a->rope_cos && a->rope_sin && a->o && a->seq_row && a->seq_len && a->groups_out, "null required pointer");
+  ARG_CHECK(!(a->ln_mu || a->ln_rstd) || (a->ln_mu && a->ln_rstd && a->ln_s), "the fold needs ln_mu, ln_rstd and ln_s");
+  ARG_CHECK(a->nh > 0 && a->H == 64 * a->nh, "H (%d) must be 64 * nh (%d)", a->H, a->nh);
+  ARG_CHECK(a->rows > 0 && a->rows % kRowPad == 0, "rows (%d) must be a positive multiple of %d", a->rows, kRowPad);
+  ARG_CHECK((int64_t)a->rows * a->H < ((int64_t)1 << 31), "rows * H must stay below 2^31");
+  ARG_CHECK(a->rope_rows > 0 && a->n_seqs > 0 && (a->packer == 0 || a->packer == 1), "bad rope_rows / n_seqs / packer");
+  ARG_CHECK(!a->local || a->window >= 0, "bad window");
+  ARG_CHECK(device >= 0, "bad device %d", device);
+  const int n = a->n_seqs;
+  for (int s = 0; s < n; ++s) {
+    const int row = a->seq_row[s], len = a->seq_len[s];
+    ARG_CHECK(len >= 1 && len <= kFusedMaxSeq, "seq_len[%d] = %d outside 1..%d", s, len, kFusedMaxSeq);
+    ARG_CHECK(row >= 0 && row % kSeqAlign == 0, "seq_row[%d] = %d must be a non-negative multiple of %d", s, row, kSeqAlign);
+    // a wave reads 64 whole token rows, whatever its sequence's length
+    ARG_CHECK((int64_t)row + 64 * ((len + 63) / 64) <= a->rows, "sequence %d (row %d, %d tokens): its last wave reads past row %d", s, row, len, a->rows);
+  }
+  {
+    std::vector<int> order(n);
+    for (int s = 0; s < n; ++s) order[s] = s;
+    std::sort(order.begin(), order.end(), [&](int l, int r) { return a->seq_row[l] < a->seq_row[r]; });
+    for (int i = 0; i + 1 < n; ++i)
+      ARG_CHECK(a->seq_row[order[i]] + a->seq_len[order[i]] <= a->seq_row[order[i + 1]], "sequences %d and %d overlap", order[i], order[i + 1]);
+  }
+  if (vrag_device_count() <= device) {
+    set_error("no HIP device %d visible", device);
+    return VRAG_ERR_NO_DEVICE;
+  }
+  HIP_TRY(hipSetDevice(device));
+  const size_t R = (size_t)a->rows, H = (size_t)a->H;
+  const bool fold = a->ln_mu != nullptr;
+  std::vector<int4> groups((size_t)n * 8);
+  const int n_groups = a->packer ? pack_groups_best_fit(a->seq_row, a->seq_len, 0, n, groups.data())
+                                 : fused_pack_groups(a->seq_row, a->seq_len, 0, n, groups.data());
+  std::memcpy(a->groups_out, groups.data(), (size_t)n_groups * 8 * sizeof(int4));
+  a->n_groups = n_groups;
+
+  constexpr size_t kCanary = 4096;   // behind o: the launch must leave it as it was
+  constexpr unsigned char kCanaryByte = 0xA5;
+  DevBuf x, w, wh, ls, lsh, mu, rstd, cs, sn, o, d_groups, sat;
+  hipError_t e = x.alloc(R * H * 2);
+  if (e == hipSuccess) e = w.alloc(3 * H * H * 2);
+  if (e == hipSuccess) e = wh.alloc(3 * H * H * 2);
+  if (e == hipSuccess) e = cs.alloc((size_t)a->rope_rows * 32 * 4);
+  if (e == hipSuccess) e = sn.alloc((size_t)a->rope_rows * 32 * 4);
+  if (e == hipSuccess) e = o.alloc(R * H * 2 + kCanary);
+  if (e == hipSuccess) e = d_groups.alloc((size_t)n_groups * 8 * sizeof(int4));
+  if (e == hipSuccess) e = sat.alloc(4);
+  if (e == hipSuccess) e = hipMemset(sat.p, 0, 4);
+  if (e == hipSuccess) e = hipMemcpy(x.p, a->x, R * H * 2, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(w.p, a->w, 3 * H * H * 2, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(cs.p, a->rope_cos, (size_t)a->rope_rows * 32 * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(sn.p, a->rope_sin, (size_t)a->rope_rows * 32 * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(o.p, a->o, R * H * 2, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(o.as<char>() + R * H * 2, kCanaryByte, kCanary);
+  if (e == hipSuccess) e = hipMemcpy(d_groups.p, groups.data(), (size_t)n_groups * 8 * sizeof(int4), hipMemcpyHostToDevice);
+  if (fold) {
+    if (e == hipSuccess) e = ls.alloc(3 * H * 4);
+    if (e == hipSuccess) e = lsh.alloc((3 * H + 64) * 4);   // the kernel's 256-float DMA of a head's 192 sums reads 64 floats on (capi.hip)
+    if (e == hipSuccess) e = mu.alloc(R * 4);
+    if (e == hipSuccess) e = rstd.alloc(R * 4);
+    if (e == hipSuccess) e = hipMemset(lsh.p, 0, (3 * H + 64) * 4);
+    if (e == hipSuccess) e = hipMemcpy(ls.p, a->ln_s, 3 * H * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(mu.p, a->ln_mu, R * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(rstd.p, a->ln_rstd, R * 4, hipMemcpyHostToDevice);
+  }
+  if (e == hipSuccess) e = permute_qkv_heads(w.as<bf16_t>(), fold ? ls.as<float>() : nullptr, (int)H, a->nh, wh.as<bf16_t>(),
+                                             fold ? lsh.as<float>() : nullptr, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) {
+    QkvAttnParams f{};
+    f.x = x.as<bf16_t>();
+    f.w = wh.as<bf16_t>();
+    f.ln_mu = fold ? mu.as<float>() : nullptr;
+    f.ln_rstd = fold ? rstd.as<float>() : nullptr;
+    f.ln_s = fold ? lsh.as<float>() : nullptr;
+    f.rope_cos = cs.as<float>();
+    f.rope_sin = sn.as<float>();
+    f.rope_rows = a->rope_rows;
+    f.o = o.as<bf16_t>();
+    f.groups = d_groups.as<int4>();
+    f.n_groups = n_groups;
+    f.H = (int)H;
+    f.nh = a->nh;
+    f.Tp = (int)R;
+    f.window = a->window;
+    f.op_dtype = a->f16 ? kOpF16 : kOpBf16;
+    f.q_scale = a->q_scale;
+    f.debug_flags = 0;
+    f.f16_sat = sat.as<unsigned>();
+    e = launch_qkv_attention(f, a->local != 0, 0);
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  unsigned saturated = 0;
+  if (e == hipSuccess) e = hipMemcpy(&saturated, sat.p, 4, hipMemcpyDeviceToHost);
+  std::vector<unsigned char> canary(kCanary);
+  if (e == hipSuccess) e = hipMemcpy(canary.data(), o.as<char>() + R * H * 2, kCanary, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(a->o, o.p, R * H * 2, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    set_error("debug fused attention run failed: %s", hipGetErrorString(e));
+    return VRAG_ERR_HIP;
+  }
+  if (std::any_of(canary.begin(), canary.end(), [](unsigned char v) { return v != kCanaryByte; })) {
+    set_error("debug fused attention run: the launch wrote past the end of o");
+    return VRAG_ERR_HIP;
+  }
+  a->f16_saturated = saturated ? 1 : 0;
+  return VRAG_OK;
+}
+
 }  // extern "C"

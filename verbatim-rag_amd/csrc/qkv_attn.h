@@ -33,9 +33,11 @@ struct QkvAttnParams {
 hipError_t launch_qkv_attention(const QkvAttnParams& p, bool local, hipStream_t stream);
 
 // Host: packs sequences seq0 .. seq1 - 1 (first rows `seq_row`, lengths `seq_len` <= kFusedMaxSeq) into groups, first fit over
-// consecutive sequences -- the simple form the diagnostics use; the engine's packer (capi.hip) is best fit decreasing over the
-// whole micro-batch.  Writes 8 descriptors per group to `out` (room for 8 * (seq1 - seq0) of them), returns the number of groups.
+// consecutive sequences -- the simple form the diagnostics use; the engine's packer (pack_groups_best_fit) is best fit decreasing
+// over the whole micro-batch.  Writes 8 descriptors per group to `out` (room for 8 * (seq1 - seq0) of them), returns the number of groups.
 int fused_pack_groups(const int* seq_row, const int* seq_len, int seq0, int seq1, int4* out);
+// The engine's packer: best-fit-decreasing bins of eight wave slots over all of the sequences, same arguments and descriptors.
+int pack_groups_best_fit(const int* seq_row, const int* seq_len, int seq0, int seq1, int4* out);
 
 // out[(h * 3 + part) * 64 + d][:] = w[part * H + h * 64 + d][:]  (and the same for the optional row-sum / bias vectors)
 hipError_t permute_qkv_heads(const bf16_t* w, const float* s, int H, int nh, bf16_t* w_out, float* s_out, hipStream_t stream);

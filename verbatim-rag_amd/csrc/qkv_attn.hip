@@ -27,13 +27,15 @@
 // masks and the key-tile walk are relative to the sequence.  A workgroup costs what a full one costs, so the schedule takes the
 // kernel when the groups are full enough (kFusedMinFillPct of 512 tokens per workgroup).  A wave's descriptor carries its own first
 // row, so the sequences of a group need not be neighbours in the packed buffer: the engine packs a micro-batch's sequences best fit
-// decreasing (capi.hip), whatever order they arrived in.
+// decreasing (pack_groups_best_fit below), whatever order they arrived in.
 // Sequences longer than 512 tokens, BERT-family encoders, launch-bound batches and poorly filled batches keep the two-kernel path.
 #include "host_util.h"
 #include "qkv_attn.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
+#include <vector>
 
 // Phase-decomposition probes of the fused kernel (vrag_debug_qkv_attn_ms, include/vrag_amd_debug.h): present in the harness build
 // only; the product build compiles every one of these branches out.
@@ -425,7 +427,14 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
         // move the reference?  (wave-uniform; steady state: no)
         bool move = false;
 #pragma unroll
-        for (int c = 0; c < 4; ++c) move = move || mx[c] > QA_LAZY || (!seen[c] && mx[c] > -INFINITY);
+        for (int c = 0; c < 4; ++c) {
+          // query rows behind the end of the sequence hold whatever follows it in the packed buffer (bf16 keeps their q): they
+          // must not time the moves of the live rows, or a sequence's bits depend on its neighbour in the buffer.  Such a row's
+          // own reference then moves only when a live row moves, so its ot / lo may run to inf or NaN (exp2 of a huge score,
+          // 0 * inf against the zeroed V): harmless -- a query is one MFMA column, and these rows are never stored
+          const bool qlive = qrow0 + 16 * c + l15 < S;
+          move = move || (qlive && (mx[c] > QA_LAZY || (!seen[c] && mx[c] > -INFINITY)));
+        }
         if (__any(move)) {
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
@@ -553,5 +562,36 @@ int fused_pack_groups(const int* seq_row, const int* seq_len, int seq0, int seq1
   return n;
 }
 
+// Groups of the fused QKV + attention kernel for sequences seq0 .. seq1 - 1: best-fit-decreasing bins of eight 64-token wave
+// slots over ALL of the micro-batch's sequences (a wave's descriptor carries its own first row, so the sequences of a group need
+// not be neighbours in the packed buffer -- fused_pack_groups above, first fit over consecutive sequences, is the
+// simple form the diagnostics use).  A workgroup costs what a full one costs, and ceil(S / 64) slots per sequence is all the
+// kernel wastes then: 86 % fill for pairs of 64-512 tokens in ANY order (70 % with consecutive first fit).
+int pack_groups_best_fit(const int* seq_row, const int* seq_len, int seq0, int seq1, int4* out) {
+  std::vector<int> by_need[9];
+  for (int s = seq0; s < seq1; ++s) by_need[std::min(8, (seq_len[s] + 63) / 64)].push_back(s);
+  std::vector<int> open_with[9];   // open groups by free slots
+  std::vector<int> used_of;        // slots taken per group
+  int n = 0;
+  for (int need = 8; need >= 1; --need)
+    for (int s : by_need[need]) {
+      int g = -1;
+      for (int room = need; room <= 8 && g < 0; ++room)   // best fit: the open group with the least room that still takes it
+        if (!open_with[room].empty()) {
+          g = open_with[room].back();
+          open_with[room].pop_back();
+        }
+      if (g < 0) {
+        g = n++;
+        used_of.push_back(0);
+        for (int w = 0; w < 8; ++w) out[g * 8 + w] = int4{0, 0, 0, 0};
+      }
+      const int used = used_of[g];
+      for (int j = 0; j < need; ++j) out[g * 8 + used + j] = int4{seq_row[s] + 64 * j, seq_len[s], used, 0};
+      used_of[g] = used + need;
+      open_with[8 - used_of[g]].push_back(g);
+    }
+  return n;
+}
 
 }  // namespace vrag
