@@ -1,8 +1,8 @@
 /* vrag_amd_debug.h -- tuning / unit-test harness of the gfx950 kernels.  NOT part of the product ABI (include/vrag_amd.h):
  * these entry points exist only in libvrag_amd_dbg.so, the harness build of the same sources (verbatim-rag_amd/build.py,
  * -DVRAG_DEBUG_API: it also keeps the phase-decomposition branches of the fused kernel that the product build compiles out).
- * tools/, tests/test_attention_unit_gpu.py, tests/test_gemm_unit_gpu.py and tests/test_qkv_attn_unit_gpu.py load it beside the
- * product library. */
+ * tools/, tests/test_attention_unit_gpu.py, tests/test_attn_unit_gpu.py, tests/test_gemm_unit_gpu.py and
+ * tests/test_qkv_attn_unit_gpu.py load it beside the product library. */
 #ifndef VRAG_AMD_DEBUG_H
 #define VRAG_AMD_DEBUG_H
 
@@ -22,8 +22,39 @@ int vrag_debug_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int3
  * main-loop MFMAs, 4 = no operand DMA (phase decomposition of the kernel's time). */
 int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int32_t window, int32_t iters, int32_t flags,
                            int32_t device, float* ms_out);
-/* Unit-test hook of the attention kernels alone: host operands in the kernels' layouts (q, k: [T, H] bf16 / fp16 bits, q
- * pre-scaled by head_dim^-1/2 * log2 e; vt: [H, Tp], Tp = T rounded up to 256), o [T, H] out; T = n_seqs * S. */
+/* Unit-test hook of the attention kernels alone (csrc/attention.hip), on the layout the encoder packs: sequences of any length
+ * >= 1 at 8-aligned rows of a `rows`-row buffer (rows = AttnParams::Tp, a multiple of 256), anything in the rows between and
+ * behind them.  Host operands in the kernels' layouts, ONE launch, o copied back; the q-block descriptors are built as
+ * vrag_encoder_set_batch builds them: one block per attention_q_block(local) rows of each sequence, in list order.
+ * Refused before anything is launched, each with its own message: null pointers, H % 64 != 0, rows % 256 != 0,
+ * rows * H >= 2^31, seq_len < 1, seq_row negative or not a multiple of 8, seq_row + seq_len > rows, overlapping sequences, a
+ * banded launch with window < 0 (or above 2^24: the band arithmetic is int), blocks_out too small for the launch.
+ * Nothing the hook accepts reads or writes outside its buffers, by the kernel's own clamps: every buffer holds rows * H
+ * elements.  Q and K are read at row min(seq_row + r, rows - 1) with r >= 0, columns head * 64 .. + 63 < H: inside [0, rows).
+ * V^T is read at row head * 64 + d < H, 8 columns from min(seq_row + c, rows - 8) with c >= 0: inside [0, rows).  O is stored
+ * at rows seq_row + g only where g < seq_len, and seq_row + seq_len <= rows is checked.  The descriptor arrays hold n_blocks
+ * entries and the grid is n_blocks x H / 64.  A sequence may therefore END ON THE LAST ROW: its last 64-key tile then runs
+ * past `rows` and all three clamps bite.  The hook also keeps 4 KiB of canary behind o and fails with VRAG_ERR_HIP if the
+ * launch touched it.
+ * Operand contract (csrc/attention.h): every K row and V^T column of the buffer must be finite; Q rows outside the
+ * sequences may hold anything. */
+typedef struct vrag_debug_attn_args {
+  const uint16_t* q;         /* [rows, H] bf16 / fp16 bits, pre-scaled by head_dim^-1/2 * log2 e */
+  const uint16_t* k;         /* [rows, H] */
+  const uint16_t* vt;        /* [H, rows] */
+  uint16_t* o;               /* in / out [rows, H]: copied to the device before the launch, so a canary survives where the kernel must not write */
+  const int32_t* seq_row;    /* [n_seqs] first row of each sequence */
+  const int32_t* seq_len;    /* [n_seqs] */
+  int32_t* blocks_out;       /* out [n_blocks][3], nullable: the q-block descriptors that ran (sequence row, sequence length, q0) */
+  int32_t rows, H, n_seqs;
+  int32_t local, window, f16;
+  int32_t blocks_cap;        /* descriptors blocks_out can hold */
+  int32_t n_blocks;          /* out */
+  int32_t f16_saturated;     /* out: the clamp word, zeroed before the launch and read back after it */
+} vrag_debug_attn_args;
+int vrag_debug_attn_run_ex(vrag_debug_attn_args* args, int32_t device);
+/* The same for the equal-length layout of tools/attn_unit.py, a thin wrapper over vrag_debug_attn_run_ex: n_seqs sequences of
+ * S tokens (S a multiple of 8) back to back from row 0; q, k, o: [T, H], T = n_seqs * S; vt: [H, Tp], Tp = T rounded up to 256. */
 int vrag_debug_attn_run(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int32_t window, int32_t f16, const uint16_t* q,
                         const uint16_t* k, const uint16_t* vt, uint16_t* o, int32_t device);
 

@@ -162,3 +162,9 @@ def test_debug_gemm_args_layout_matches_ctypes(tmp_path):
 def test_debug_qkv_attn_args_layout_matches_ctypes(tmp_path):
     """The same for vrag_debug_qkv_attn_args and _lib.DebugQkvAttnArgs (tests/test_qkv_attn_unit_gpu.py)."""
     _check_layout(tmp_path, "vrag_debug_qkv_attn_args", _lib.DebugQkvAttnArgs)
+
+
+@pytest.mark.skipif(_host_cc() is None, reason="no host C compiler")
+def test_debug_attn_args_layout_matches_ctypes(tmp_path):
+    """The same for vrag_debug_attn_args and _lib.DebugAttnArgs (tests/test_attn_unit_gpu.py)."""
+    _check_layout(tmp_path, "vrag_debug_attn_args", _lib.DebugAttnArgs)

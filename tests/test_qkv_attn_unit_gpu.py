@@ -48,7 +48,8 @@ import pytest
 
 import verbatim_rag_amd  # noqa: F401
 from verbatim_rag_amd import _lib
-from unit16 import U, f32, from16, half_ulp, make_ledger, out16_bound, to16, trunc16
+from attn_ref import attend
+from unit16 import U, f32, from16, half_ulp, make_ledger, to16, trunc16
 
 gpu = pytest.mark.gpu
 
@@ -231,58 +232,6 @@ def project(inp, f16, fold, rows_idx, pos, head, part, scale=1.0, exact=False, p
         assert np.array_equal(from16(to16(v, f16), f16), v), "the crafted operands must be exact in 16 bits"
         return v, np.zeros_like(v)
     return v, e + half_ulp(np.abs(v) + e, f16)
-
-
-def attend(q, Eq, k, Ek, v, Ev, qi, kj, S, local, window, f16, p16=None, strict=True, exact_p=None):
-    """Softmax(q k^T) v over keys with relative index kj admitted for the query at qi (j < S; banded |i - j| <= window), and
-    the per-element bound.  p16: rounding of P to apply in the reference.  exact_p ("round" / "trunc"): the crafted case whose
-    16-bit P is predictable bit for bit (test_lazy_reference): the reference rounds P itself and the bound grants P nothing."""
-    s = q @ k.T
-    ok = (kj[None, :] < S) & np.ones((len(qi), 1), bool)
-    if local:
-        ok &= np.abs(qi[:, None] - kj[None, :]) <= window
-    s = np.where(ok, s, -np.inf)
-    smax = s.max(1, keepdims=True)
-    d = s - smax
-    if exact_p:
-        # every move of the reference is an integer, so the 16-bit rounding of P = 2^(s - m) is that of 2^frac(s), whatever the
-        # schedule of the moves was; fp32 computes s - m exactly and v_exp_f32 is good to an ulp: no tie may lie that close
-        assert np.all(smax == np.round(smax)) and np.all(np.where(ok, d * 8 == np.round(d * 8), True))
-        n = np.floor(np.where(ok, d, 0.0))
-        m2 = np.exp2(np.where(ok, d, 0.0) - n)
-        lower = trunc16(m2, f16)
-        at = (m2 - lower) / (2 * half_ulp(m2, f16))
-        assert np.all((at == 0) | (np.abs(at - 0.5) > 1e-3)), "2^frac too close to a 16-bit tie"
-        m16 = lower if exact_p == "trunc" else from16(to16(m2, f16), f16)
-        p = np.where(ok, m16 * np.exp2(n), 0.0)
-    else:
-        p = np.exp2(d)
-        if p16 is not None:
-            p = p16(p)
-    w = p / p.sum(1, keepdims=True)
-    o = w @ v
-    aq, ak = np.abs(q), np.abs(k)
-    Es = Eq @ ak.T + aq @ Ek.T + Eq @ Ek.T + 2 * 66 * U * (aq @ ak.T + np.abs(smax))
-    eta = np.exp2(np.minimum(Es, 60.0)) - 1 + (2.0 ** -11 if f16 else 2.0 ** -8) + 4 * U
-    sub = 2.0 ** -25 if f16 else 0.0
-    # additions that can round: the live keys (a masked P is an exact zero); a key 2^-30 below the row's maximum adds at most
-    # its own magnitude to the error, whether it rounds away or not
-    heavy = ok & (d >= -30)
-    n_keys = (heavy if exact_p else ok).sum(1, keepdims=True)
-    light = (np.where(ok & ~heavy, w, 0.0) @ np.abs(v)) if exact_p else 0.0
-    if exact_p:
-        eta, sub = np.zeros_like(eta), 0.0
-    A = (w * eta).sum(1, keepdims=True) + ok.sum(1, keepdims=True) * sub
-    assert not strict or np.all(A < 0.5), float(A.max())   # (a control's own bound is not used)
-    A = np.minimum(A, 0.5)
-    weta = w * eta + ok * sub
-    err = np.zeros_like(o)
-    if not exact_p:
-        for i0 in range(0, len(qi), 64):   # sum_j w_j eta_j |v_j - o_i|, 64 queries at a time
-            sl = slice(i0, i0 + 64)
-            err[sl] = np.einsum("ij,ijd->id", weta[sl], np.abs(v[None, :, :] - o[sl, None, :]))
-    err = err / (1 - A) + (w * (1 + eta)) @ Ev / (1 - A) + 2 * (n_keys + 16) * U * (w @ np.abs(v)) * 2 + light + 3 * U * np.abs(o)
-    return o, out16_bound(o, err, f16)
 
 
 def reference(inp, seq, head, f16, local, fold, window, q_scale=Q_SCALE, exact=False, defect=None, prev=None, kbase=0,

@@ -168,6 +168,7 @@ DEBUG_SIGNATURES = {
     "vrag_debug_gemm_ms": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "vrag_debug_attn_run": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_int32]),
+    "vrag_debug_attn_run_ex": (C.c_int, [C.c_void_p, C.c_int32]),
     "vrag_debug_attn_ms": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "vrag_debug_qkv_attn_ms": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _FP]),
     "vrag_debug_gemm_run": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -193,6 +194,12 @@ class DebugQkvAttnArgs(C.Structure):
         "x", "w", "ln_s", "ln_mu", "ln_rstd", "rope_cos", "rope_sin", "o", "seq_row", "seq_len", "groups_out")] + [
         (n, C.c_int32) for n in ("rows", "H", "nh", "rope_rows", "n_seqs", "packer", "local", "window", "f16")] + [
         ("q_scale", C.c_float), ("n_groups", C.c_int32), ("f16_saturated", C.c_int32)]
+
+
+class DebugAttnArgs(C.Structure):
+    """vrag_debug_attn_args (include/vrag_amd_debug.h), field for field; tests/test_capi_abi.py checks the layout too."""
+    _fields_ = [(n, C.c_void_p) for n in ("q", "k", "vt", "o", "seq_row", "seq_len", "blocks_out")] + [
+        (n, C.c_int32) for n in ("rows", "H", "n_seqs", "local", "window", "f16", "blocks_cap", "n_blocks", "f16_saturated")]
 
 
 _DBG = None

@@ -2,8 +2,8 @@
 // eager/SDPA attention inside ModernBertAttention.forward
 // (transformers modeling_modernbert.py:166-185,286-299; mask: masking_utils.py:141-151).
 //
-// Work item = (sequence, query block, head): 256 rows / 4 waves on global layers, 128 rows / 2 waves
-// on banded layers; every wave owns 64 query rows (two 32-row sub-tiles that SHARE every K / V^T
+// Work item = (sequence, query block, head): 256 rows / 4 waves on global and on banded layers
+// (ATT_QB_GLOBAL, ATT_QB_LOCAL); every wave owns 64 query rows (two 32-row sub-tiles that SHARE every K / V^T
 // fragment read from LDS).  64-key tiles stream
 // through a 3-slot LDS ring by 16-byte LDS-DMA (global_load_lds), two tiles in flight, one raw
 // s_barrier per tile and a counted s_waitcnt vmcnt (never a full drain in steady state).

@@ -285,41 +285,74 @@ int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, 
   return VRAG_OK;
 }
 
-int vrag_debug_attn_run(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int32_t window, int32_t f16, const uint16_t* q,
-                        const uint16_t* k, const uint16_t* vt, uint16_t* o, int32_t device) {
-  ARG_CHECK(q && k && vt && o && n_seqs > 0 && S > 0 && S % kSeqAlign == 0 && H % 64 == 0, "bad arguments");
+int vrag_debug_attn_run_ex(vrag_debug_attn_args* a, int32_t device) {
+  ARG_CHECK(a, "null arguments");
+  ARG_CHECK(a->q && a->k && a->vt && a->o && a->seq_row && a->seq_len, "null required pointer");
+  ARG_CHECK(a->H > 0 && a->H % 64 == 0, "H (%d) must be a positive multiple of 64", a->H);
+  ARG_CHECK(a->rows > 0 && a->rows % kRowPad == 0, "rows (%d) must be a positive multiple of %d", a->rows, kRowPad);
+  ARG_CHECK((int64_t)a->rows * a->H < ((int64_t)1 << 31), "rows * H must stay below 2^31");
+  ARG_CHECK(a->n_seqs > 0, "n_seqs (%d) must be positive", a->n_seqs);
+  ARG_CHECK(!a->local || a->window >= 0, "a banded launch needs window >= 0 (got %d)", a->window);
+  ARG_CHECK(!a->local || a->window <= (1 << 24), "window (%d) above 2^24", a->window);
+  ARG_CHECK(device >= 0, "bad device %d", device);
+  const int n = a->n_seqs;
+  for (int s = 0; s < n; ++s) {
+    const int row = a->seq_row[s], len = a->seq_len[s];
+    ARG_CHECK(len >= 1, "seq_len[%d] = %d must be at least 1", s, len);
+    ARG_CHECK(row >= 0 && row % kSeqAlign == 0, "seq_row[%d] = %d must be a non-negative multiple of %d", s, row, kSeqAlign);
+    ARG_CHECK((int64_t)row + len <= a->rows, "sequence %d (row %d, %d tokens) ends past row %d", s, row, len, a->rows);
+  }
+  {
+    std::vector<int> order(n);
+    for (int s = 0; s < n; ++s) order[s] = s;
+    std::sort(order.begin(), order.end(), [&](int l, int r) { return a->seq_row[l] < a->seq_row[r]; });
+    for (int i = 0; i + 1 < n; ++i)
+      ARG_CHECK(a->seq_row[order[i]] + a->seq_len[order[i]] <= a->seq_row[order[i + 1]], "sequences %d and %d overlap", order[i], order[i + 1]);
+  }
+  // the q-block descriptors, as vrag_encoder_set_batch builds them (capi.hip): one block per attention_q_block rows of each sequence
+  const int qb = attention_q_block(a->local != 0);
+  std::vector<int> bs, bl, bq;
+  for (int s = 0; s < n; ++s)
+    for (int q0 = 0; q0 < a->seq_len[s]; q0 += qb) {
+      bs.push_back(a->seq_row[s]);
+      bl.push_back(a->seq_len[s]);
+      bq.push_back(q0);
+    }
+  const int n_blocks = (int)bs.size();
+  ARG_CHECK(!a->blocks_out || n_blocks <= a->blocks_cap, "blocks_out holds %d descriptors, the launch has %d", a->blocks_cap, n_blocks);
   if (vrag_device_count() <= device) {
     set_error("no HIP device %d visible", device);
     return VRAG_ERR_NO_DEVICE;
   }
   HIP_TRY(hipSetDevice(device));
-  const size_t T = (size_t)n_seqs * S, Tp = (size_t)align_up((int)T, kRowPad);
-  const int qb = attention_q_block(local != 0);
-  std::vector<int> bs, bl, bq;
-  for (int s = 0; s < n_seqs; ++s)
-    for (int q0 = 0; q0 < S; q0 += qb) {
-      bs.push_back(s * S);
-      bl.push_back(S);
-      bq.push_back(q0);
+  a->n_blocks = n_blocks;
+  if (a->blocks_out)
+    for (int b = 0; b < n_blocks; ++b) {
+      a->blocks_out[3 * b] = bs[b];
+      a->blocks_out[3 * b + 1] = bl[b];
+      a->blocks_out[3 * b + 2] = bq[b];
     }
+  const size_t R = (size_t)a->rows, H = (size_t)a->H;
+  constexpr size_t kCanary = 4096;   // behind o: the launch must leave it as it was
+  constexpr unsigned char kCanaryByte = 0xA5;
   DevBuf dq, dk, dv, dout, d_bs, d_bl, d_bq, sat;
-  hipError_t e = dq.alloc(Tp * H * 2);
-  if (e == hipSuccess) e = dk.alloc(Tp * H * 2);
-  if (e == hipSuccess) e = dv.alloc(Tp * H * 2);
-  if (e == hipSuccess) e = dout.alloc(Tp * H * 2);
-  if (e == hipSuccess) e = d_bs.alloc(bs.size() * 4);
-  if (e == hipSuccess) e = d_bl.alloc(bs.size() * 4);
-  if (e == hipSuccess) e = d_bq.alloc(bs.size() * 4);
-  if (e == hipSuccess) e = sat.alloc(4);   // the fp16 clamp word (not read)
-  if (e == hipSuccess) e = hipMemset(dq.p, 0, Tp * H * 2);
-  if (e == hipSuccess) e = hipMemset(dk.p, 0, Tp * H * 2);
-  if (e == hipSuccess) e = hipMemset(dout.p, 0, Tp * H * 2);
-  if (e == hipSuccess) e = hipMemcpy(dq.p, q, T * H * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dk.p, k, T * H * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dv.p, vt, (size_t)H * Tp * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_bs.p, bs.data(), bs.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_bl.p, bl.data(), bs.size() * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_bq.p, bq.data(), bs.size() * 4, hipMemcpyHostToDevice);
+  hipError_t e = dq.alloc(R * H * 2);
+  if (e == hipSuccess) e = dk.alloc(R * H * 2);
+  if (e == hipSuccess) e = dv.alloc(R * H * 2);
+  if (e == hipSuccess) e = dout.alloc(R * H * 2 + kCanary);
+  if (e == hipSuccess) e = d_bs.alloc((size_t)n_blocks * 4);
+  if (e == hipSuccess) e = d_bl.alloc((size_t)n_blocks * 4);
+  if (e == hipSuccess) e = d_bq.alloc((size_t)n_blocks * 4);
+  if (e == hipSuccess) e = sat.alloc(4);
+  if (e == hipSuccess) e = hipMemset(sat.p, 0, 4);
+  if (e == hipSuccess) e = hipMemcpy(dq.p, a->q, R * H * 2, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dk.p, a->k, R * H * 2, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dv.p, a->vt, R * H * 2, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(dout.p, a->o, R * H * 2, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(dout.as<char>() + R * H * 2, kCanaryByte, kCanary);
+  if (e == hipSuccess) e = hipMemcpy(d_bs.p, bs.data(), (size_t)n_blocks * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_bl.p, bl.data(), (size_t)n_blocks * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_bq.p, bq.data(), (size_t)n_blocks * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e == hipSuccess) {
     AttnParams ap{};
@@ -330,22 +363,60 @@ int vrag_debug_attn_run(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int
     ap.blk_seq_start = d_bs.as<int>();
     ap.blk_seq_len = d_bl.as<int>();
     ap.blk_q0 = d_bq.as<int>();
-    ap.n_blocks = (int)bs.size();
-    ap.H = H;
-    ap.nh = H / 64;
-    ap.Tp = (int)Tp;
-    ap.window = window;
-    ap.op_dtype = f16 ? kOpF16 : kOpBf16;
+    ap.n_blocks = n_blocks;
+    ap.H = (int)H;
+    ap.nh = (int)H / 64;
+    ap.Tp = (int)R;
+    ap.window = a->window;
+    ap.op_dtype = a->f16 ? kOpF16 : kOpBf16;
     ap.f16_sat = sat.as<unsigned>();
-    e = launch_attention(ap, local != 0, 0);
+    e = launch_attention(ap, a->local != 0, 0);
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(o, dout.p, T * H * 2, hipMemcpyDeviceToHost);
+  unsigned saturated = 0;
+  if (e == hipSuccess) e = hipMemcpy(&saturated, sat.p, 4, hipMemcpyDeviceToHost);
+  std::vector<unsigned char> canary(kCanary);
+  if (e == hipSuccess) e = hipMemcpy(canary.data(), dout.as<char>() + R * H * 2, kCanary, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(a->o, dout.p, R * H * 2, hipMemcpyDeviceToHost);
   if (e != hipSuccess) {
     set_error("debug attention run failed: %s", hipGetErrorString(e));
     return VRAG_ERR_HIP;
   }
+  if (std::any_of(canary.begin(), canary.end(), [](unsigned char v) { return v != kCanaryByte; })) {
+    set_error("debug attention run: the launch wrote past the end of o");
+    return VRAG_ERR_HIP;
+  }
+  a->f16_saturated = saturated ? 1 : 0;
   return VRAG_OK;
+}
+
+// The equal-length layout of tools/attn_unit.py: n_seqs sequences of S tokens back to back from row 0, zero rows behind them.
+int vrag_debug_attn_run(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int32_t window, int32_t f16, const uint16_t* q,
+                        const uint16_t* k, const uint16_t* vt, uint16_t* o, int32_t device) {
+  ARG_CHECK(q && k && vt && o && n_seqs > 0 && S > 0 && S % kSeqAlign == 0 && H > 0 && H % 64 == 0, "bad arguments");
+  ARG_CHECK((int64_t)n_seqs * S + kRowPad < ((int64_t)1 << 31) / H, "rows * H must stay below 2^31");
+  const size_t T = (size_t)n_seqs * S, Tp = (size_t)align_up((int64_t)T, kRowPad);
+  std::vector<uint16_t> hq(Tp * H, 0), hk(Tp * H, 0), ho(Tp * H, 0);
+  std::memcpy(hq.data(), q, T * H * 2);
+  std::memcpy(hk.data(), k, T * H * 2);
+  std::vector<int32_t> row(n_seqs), len(n_seqs, S);
+  for (int s = 0; s < n_seqs; ++s) row[s] = s * S;
+  vrag_debug_attn_args a{};
+  a.q = hq.data();
+  a.k = hk.data();
+  a.vt = vt;
+  a.o = ho.data();
+  a.seq_row = row.data();
+  a.seq_len = len.data();
+  a.rows = (int32_t)Tp;
+  a.H = H;
+  a.n_seqs = n_seqs;
+  a.local = local;
+  a.window = window;
+  a.f16 = f16;
+  const int status = vrag_debug_attn_run_ex(&a, device);
+  if (status == VRAG_OK) std::memcpy(o, ho.data(), T * H * 2);
+  return status;
 }
 
 int vrag_debug_gemm_run(vrag_debug_gemm_args* a, int32_t device) {
