@@ -249,7 +249,7 @@ int vrag_encoder_graph_stats(vrag_encoder* enc, int32_t enable, int64_t* replays
 
 /* fp16 operands (VRAG_OPERAND_F16) saturate at +-65504 instead of overflowing.  *saturated = 1 if any fp32 -> fp16
  * operand conversion of this handle (weights at load time, LayerNorm-fold copies, q / k / v, GeGLU outputs, attention
- * outputs) has had to clamp since the last reset: the logits computed meanwhile are not to be trusted -- re-run with
+ * outputs) has met a value outside fp16's range or NaN since the last reset: the logits computed meanwhile are not to be trusted -- re-run with
  * VRAG_OPERAND_BF16 (checkpoints with activation outliers beyond fp16's range).  The flag is per handle: other handles
  * on the same device neither see nor clear it.  Synchronises the device. */
 int vrag_encoder_f16_saturated(vrag_encoder* enc, int32_t reset, int32_t* saturated);

@@ -1,8 +1,8 @@
 /* vrag_amd_debug.h -- tuning / unit-test harness of the gfx950 kernels.  NOT part of the product ABI (include/vrag_amd.h):
  * these entry points exist only in libvrag_amd_dbg.so, the harness build of the same sources (verbatim-rag_amd/build.py,
  * -DVRAG_DEBUG_API: it also keeps the phase-decomposition branches of the fused kernel that the product build compiles out).
- * tools/, tests/test_attention_unit_gpu.py, tests/test_attn_unit_gpu.py, tests/test_gemm_unit_gpu.py and
- * tests/test_qkv_attn_unit_gpu.py load it beside the product library. */
+ * tools/, tests/test_attention_unit_gpu.py, tests/test_attn_unit_gpu.py, tests/test_gemm_unit_gpu.py,
+ * tests/test_qkv_attn_unit_gpu.py and tests/test_rows_unit_gpu.py load it beside the product library. */
 #ifndef VRAG_AMD_DEBUG_H
 #define VRAG_AMD_DEBUG_H
 
@@ -131,6 +131,77 @@ int vrag_debug_qkv_attn_run(vrag_debug_qkv_attn_args* args, int32_t device);
 /* Host only (no GPU call): the wave descriptors either packer gives n sequences (lengths 1..512); out holds [n][8][4] int32.
  * Returns the number of groups, or a negative status on bad arguments. */
 int vrag_debug_pack_groups(const int32_t* seq_row, const int32_t* seq_len, int32_t n, int32_t packer, int32_t* out);
+
+/* Unit-test hook of the row kernels alone (csrc/norm_heads.hip), one launcher per call, chosen by `op`.  Host buffers in, every
+ * pointer nullable where the launcher's is (null = the launcher gets null); exactly the launches the launcher makes (one; two for
+ * launch_seq_head).  Buffers marked "in / out" are copied to the device before the launch and back after it, also when the
+ * launcher refuses, so a canary survives where the kernel must not write.  `rows` is what the launcher calls rows, n_ranges or
+ * n_seqs.  H and rows go to the launcher UNCHECKED (H in 1..65536 and rows >= 0 only size the buffers): the launchers' own refusals
+ * (H > 1024, H % 4, split3 with out_lo or without out16, fp16 without a clamp word, P without pos, launch_seq_head without w) are
+ * part of what is tested.  launch_status returns the launcher's hipError_t; a refusing launcher makes the hook return
+ * VRAG_ERR_INVALID with launch_status set, a refusal of the hook itself leaves launch_status untouched.
+ * Refused by the hook before anything is launched, each with its own message: a null pointer the chosen kernel dereferences
+ * unconditionally, h_rows < rows where rows index h, out_rows < rows, alias_f32 together with out_f32, ids / pos / type_ids /
+ * first_row outside their tables, start < 0, end >= h_rows, start > end (the kernel would divide by zero), seq_len < 1,
+ * seq_row < 0, seq_row + seq_len > h_rows, num_labels < 1 where a classifier runs.
+ * Nothing the hook accepts reads or writes outside its buffers.  Every kernel addresses a row as base + index * H + c with
+ * c + 4 <= H (c = 4 * lane + 256 * i, masked by c < H; H % 4 == 0 or the launcher refuses) and the index is: the row number below
+ * `rows` (h_rows, out_rows >= rows are checked; the workgroup's rows at and beyond `rows` return before their first access); a
+ * gathered index checked above against its table's row count; t in [start, end] or [seq_row, seq_row + seq_len), both ends
+ * checked; a label c < num_labels into Wc / bc; k < H into WdT / Wp.  The split3 image has leading dimension 3 H and columns
+ * below 3 H, and is sized so.  Every device buffer, inputs included, is followed by 4 KiB of canary: should a launcher's refusal
+ * of H % 4 != 0 ever fail, the float4 that straddles the last row's end lands there and not outside the allocation.  The hook
+ * fails with VRAG_ERR_HIP if a launch touched any canary. */
+enum {
+  VRAG_DEBUG_ROWS_EMBED_LN = 0,
+  VRAG_DEBUG_ROWS_LAYERNORM = 1,
+  VRAG_DEBUG_ROWS_RANGE_POOL = 2,
+  VRAG_DEBUG_ROWS_LN_CLASSIFIER = 3,
+  VRAG_DEBUG_ROWS_POOLER_CLASSIFIER = 4,
+  VRAG_DEBUG_ROWS_SEQ_HEAD = 5
+};
+typedef struct vrag_debug_rows_args {
+  float* h;                  /* [h_rows, H] input rows of every op but embed_ln (ln_classifier: x); in / out with alias_f32 */
+  const int32_t* ids;        /* embed_ln [rows], in [0, vocab) */
+  const float* E;            /* embed_ln [vocab, H] */
+  const float* P;            /* embed_ln [n_pos, H]; null = no position / type rows (ModernBERT form) */
+  const int32_t* pos;        /* embed_ln [rows], in [0, n_pos) */
+  const float* type_row;     /* embed_ln [n_types, H] */
+  const int32_t* type_ids;   /* embed_ln [rows], in [0, n_types); null = row 0 */
+  const float* w;            /* [H] LayerNorm gain: embed_ln / layernorm w, lnw of the other four */
+  const float* bias;         /* [H] LayerNorm bias: embed_ln / layernorm bias, ln_classifier lnb */
+  const int32_t* start;      /* range_pool [rows] */
+  const int32_t* end;        /* range_pool [rows], inclusive */
+  const int32_t* first_row;  /* pooler_classifier [rows] */
+  const int32_t* seq_row;    /* seq_head [rows] */
+  const int32_t* seq_len;    /* seq_head [rows] */
+  const float* Wp;           /* pooler_classifier [H, H] */
+  const float* bp;           /* pooler_classifier [H] */
+  const float* WdT;          /* seq_head [H, H], transposed dense weight */
+  const float* bd;           /* seq_head [H] */
+  const float* wn;           /* seq_head [H] */
+  const float* bn;           /* seq_head [H] */
+  const float* Wc;           /* [num_labels, H] */
+  const float* bc;           /* [num_labels] */
+  float* out_f32;            /* in / out: embed_ln h and layernorm out_f32 [out_rows, H]; range_pool out [out_rows, num_labels (mode 0) or H]; the logits of the three classifiers [out_rows, num_labels] */
+  uint16_t* out16;           /* in / out: embed_ln a, layernorm out_bf16 [out_rows, H], with split3 [out_rows, 3 H] */
+  uint16_t* out_lo;          /* in / out: layernorm out_lo [out_rows, H] */
+  float* row_mean;           /* in / out: layernorm row_mean [out_rows] */
+  float* pooled;             /* in / out: seq_head pooled [out_rows, H] */
+  int32_t op, H, rows;
+  int32_t h_rows, out_rows;  /* rows h holds; rows every in / out buffer holds (>= rows) */
+  int32_t vocab, n_pos, n_types;
+  int32_t num_labels;
+  int32_t mode;              /* range_pool mode; seq_head pool_mean */
+  int32_t gelu_first, split3;
+  int32_t alias_f32;         /* layernorm: out_f32 = h itself (out_f32 must be null; h is copied back) */
+  int32_t f16;
+  int32_t no_sat;            /* the launcher gets a null clamp word (fp16: it must refuse) */
+  float eps;
+  int32_t launch_status;     /* out: the launcher's hipError_t */
+  int32_t f16_saturated;     /* out: the clamp word, zeroed before the launch and read back after it */
+} vrag_debug_rows_args;
+int vrag_debug_rows_run(vrag_debug_rows_args* args, int32_t device);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 """16-bit operand helpers and the error / bound ledger shared by the kernel unit tests (test_gemm_unit_gpu.py,
-test_qkv_attn_unit_gpu.py, test_attn_unit_gpu.py): bit-exact bf16 / fp16 conversion, the half-ulp allowance of a 16-bit store, and `record` / `control`,
+test_qkv_attn_unit_gpu.py, test_attn_unit_gpu.py, test_rows_unit_gpu.py with its references in rows_ref.py): bit-exact bf16 / fp16 conversion, the half-ulp allowance of a 16-bit store, and `record` / `control`,
 which assert a per-element bound and note the worst error / bound ratio for the module's `-rP` table."""
 from collections import defaultdict
 

@@ -174,6 +174,7 @@ DEBUG_SIGNATURES = {
     "vrag_debug_gemm_run": (C.c_int, [C.c_void_p, C.c_int32]),
     "vrag_debug_qkv_attn_run": (C.c_int, [C.c_void_p, C.c_int32]),
     "vrag_debug_pack_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "vrag_debug_rows_run": (C.c_int, [C.c_void_p, C.c_int32]),
 }
 
 
@@ -201,6 +202,18 @@ class DebugAttnArgs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("q", "k", "vt", "o", "seq_row", "seq_len", "blocks_out")] + [
         (n, C.c_int32) for n in ("rows", "H", "n_seqs", "local", "window", "f16", "blocks_cap", "n_blocks", "f16_saturated")]
 
+
+class DebugRowsArgs(C.Structure):
+    """vrag_debug_rows_args (include/vrag_amd_debug.h), field for field; tests/test_capi_abi.py checks the layout too."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "h", "ids", "E", "P", "pos", "type_row", "type_ids", "w", "bias", "start", "end", "first_row", "seq_row", "seq_len", "Wp",
+        "bp", "WdT", "bd", "wn", "bn", "Wc", "bc", "out_f32", "out16", "out_lo", "row_mean", "pooled")] + [
+        (n, C.c_int32) for n in ("op", "H", "rows", "h_rows", "out_rows", "vocab", "n_pos", "n_types", "num_labels", "mode",
+                                 "gelu_first", "split3", "alias_f32", "f16", "no_sat")] + [
+        ("eps", C.c_float), ("launch_status", C.c_int32), ("f16_saturated", C.c_int32)]
+
+
+DEBUG_ROWS_OPS = {"embed_ln": 0, "layernorm": 1, "range_pool": 2, "ln_classifier": 3, "pooler_classifier": 4, "seq_head": 5}
 
 _DBG = None
 

@@ -9,7 +9,7 @@ namespace vrag {
 // P.V MFMA, and a masked score is replaced, not skipped.  So every K row and every V^T column a launch can address -- all of
 // [0, Tp) -- must be FINITE: a NaN or inf in a V^T column behind a sequence poisons that sequence's live rows.  Q rows behind a
 // sequence may hold anything: they only feed dead query rows, which are never stored (their 0 / 0 stays in registers and does
-// not set the fp16 clamp word: a NaN compares false against 65504).  In the product the encoder guarantees it: dev_alloc
+// not set the fp16 clamp word: the store converts live rows only).  In the product the encoder guarantees it: dev_alloc
 // zero-fills q, k and vt, and every later store there is a bf16 value of finite activations or an fp16 value clamped at
 // +-65504 (Op<f16_t>::to).  The unit test (tests/test_attn_unit_gpu.py) fills those rows with finite garbage.
 struct AttnParams {

@@ -265,13 +265,14 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_fwd_kernel(const AttnParams p
     const float l_tot = l_run[u] + __shfl_xor(l_run[u], 32, 64);
     const float inv = 1.0f / l_tot;
     const int row = u * 32 + l31;
+    const bool live = qlo(u) + l31 < S;   // a dead row's 0 / 0 is never stored, and must not reach the fp16 clamp word either
 #pragma unroll
     for (int n = 0; n < 2; ++n)
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         V4 o;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = Op<T>::to(ot[u][n][4 * g + j] * inv, p.f16_sat);
+        for (int j = 0; j < 4; ++j) o[j] = live ? Op<T>::to(ot[u][n][4 * g + j] * inv, p.f16_sat) : (T)0.f;
         *reinterpret_cast<V4*>(stg + row * 128 + (((n * 4 + g) ^ (row & 7)) << 4) + (hi << 3)) = o;
       }
   }

@@ -19,7 +19,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // the same MFMA rate -- what the per-token logits of the v2 highlighter need to stay within 1e-3 of the fp32 reference,
 // tests/probes/precision_probe.py).  Both are 2 bytes: host-side buffers are typed bf16_t* whatever they hold and the
 // kernels, templated on the operand type, reinterpret them.  fp16 conversions saturate at +-65504 instead of
-// producing inf.
+// producing inf; a value outside fp16's range or NaN sets the launching engine's clamp word.
 constexpr int kOpBf16 = 0, kOpF16 = 1;
 template <typename T> struct Op;
 template <> struct Op<bf16_t> {
@@ -38,9 +38,11 @@ template <> struct Op<f16_t> {
   typedef f16x8 v8;
   // `sat`: the launching engine's clamp word (GemmParams::f16_sat and the like; never null for fp16 launches)
   static __device__ __forceinline__ f16_t to(float v, unsigned* sat) {
-    // a value outside fp16's range is stored as +-65504 AND reported: silently clamped activations would come back as
-    // plausible, wrong logits (vrag_encoder_f16_saturated; the branch is never taken on healthy checkpoints)
-    if (__builtin_fabsf(v) > 65504.f) *sat = 1u;
+    // a value outside fp16's range or NaN is stored finite AND reported: silently clamped activations would come back as
+    // plausible, wrong logits (vrag_encoder_f16_saturated; the branch is never taken on healthy checkpoints).  The negated
+    // in-range test is still one compare and is true of NaN, which `fabsf(v) > 65504` is not.  Out of range is stored as
+    // +-65504; NaN as -65504: v_med3_f32 returns the minimum of its operands when one of them is NaN.
+    if (!(__builtin_fabsf(v) <= 65504.f)) *sat = 1u;
     return (f16_t)__builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);
   }
   static __device__ __forceinline__ f32x16 mfma32(const v8& a, const v8& b, const f32x16& c) {

@@ -1,5 +1,5 @@
 // Tuning / unit-test harness of the kernels (include/vrag_amd_debug.h): synthetic-operand timing loops and the attention
-// kernels' and the GEMM's unit-test hooks.  NOT part of the product library: compiled only into libvrag_amd_dbg.so (build.py, -DVRAG_DEBUG_API),
+// kernels', the GEMM's and the row kernels' unit-test hooks.  NOT part of the product library: compiled only into libvrag_amd_dbg.so (build.py, -DVRAG_DEBUG_API),
 // which tools/ and the attention unit test load beside libvrag_amd.so.
 #include "../../include/vrag_amd.h"
 #include "../../include/vrag_amd_debug.h"
@@ -707,6 +707,187 @@ int vrag_debug_qkv_attn_run(vrag_debug_qkv_attn_args* a, int32_t device) {
     return VRAG_ERR_HIP;
   }
   a->f16_saturated = saturated ? 1 : 0;
+  return VRAG_OK;
+}
+
+int vrag_debug_rows_run(vrag_debug_rows_args* a, int32_t device) {
+  ARG_CHECK(a, "null arguments");
+  const int op = a->op, H = a->H, rows = a->rows;
+  ARG_CHECK(op >= VRAG_DEBUG_ROWS_EMBED_LN && op <= VRAG_DEBUG_ROWS_SEQ_HEAD, "op %d is not a row launcher", op);
+  ARG_CHECK(H >= 1 && H <= 65536, "H (%d) outside 1..65536: the buffers cannot be sized", H);
+  ARG_CHECK(rows >= 0, "rows (%d) is negative: the buffers cannot be sized", rows);
+  ARG_CHECK(a->out_rows >= rows, "out_rows (%d) below rows (%d)", a->out_rows, rows);
+  ARG_CHECK(device >= 0, "bad device %d", device);
+  const bool embed = op == VRAG_DEBUG_ROWS_EMBED_LN, ln = op == VRAG_DEBUG_ROWS_LAYERNORM, range = op == VRAG_DEBUG_ROWS_RANGE_POOL;
+  const bool lncls = op == VRAG_DEBUG_ROWS_LN_CLASSIFIER, pooler = op == VRAG_DEBUG_ROWS_POOLER_CLASSIFIER;
+  const bool seqh = op == VRAG_DEBUG_ROWS_SEQ_HEAD;
+  const bool classifier = lncls || pooler || seqh || (range && a->mode == 0);
+  // every pointer the chosen kernel dereferences unconditionally must be there
+  if (embed) {
+    ARG_CHECK(a->ids && a->E && a->w && a->out_f32 && a->out16, "embed_ln needs ids, E, w, out_f32 and out16");
+    ARG_CHECK(a->vocab >= 1, "vocab (%d) must be positive", a->vocab);
+    for (int r = 0; r < rows; ++r) ARG_CHECK(a->ids[r] >= 0 && a->ids[r] < a->vocab, "ids[%d] = %d outside the %d rows of E", r, a->ids[r], a->vocab);
+    if (a->P && a->pos) {
+      ARG_CHECK(a->n_pos >= 1, "n_pos (%d) must be positive", a->n_pos);
+      for (int r = 0; r < rows; ++r) ARG_CHECK(a->pos[r] >= 0 && a->pos[r] < a->n_pos, "pos[%d] = %d outside the %d rows of P", r, a->pos[r], a->n_pos);
+    }
+    if (a->P && a->type_row) {
+      ARG_CHECK(a->n_types >= 1, "n_types (%d) must be positive", a->n_types);
+      if (a->type_ids)
+        for (int r = 0; r < rows; ++r)
+          ARG_CHECK(a->type_ids[r] >= 0 && a->type_ids[r] < a->n_types, "type_ids[%d] = %d outside the %d rows of type_row", r, a->type_ids[r], a->n_types);
+    }
+  } else {
+    ARG_CHECK(a->h, "h is required");
+    ARG_CHECK(a->h_rows >= 1, "h_rows (%d) must be positive", a->h_rows);
+  }
+  if (ln || lncls) ARG_CHECK(a->h_rows >= rows, "h holds %d rows, the launch reads %d", a->h_rows, rows);
+  if (ln) ARG_CHECK(!(a->alias_f32 && a->out_f32), "alias_f32 makes h the fp32 output: out_f32 must be null");
+  if (range) {
+    ARG_CHECK(a->start && a->end && a->out_f32, "range_pool needs start, end and out_f32");
+    for (int r = 0; r < rows; ++r) {
+      ARG_CHECK(a->start[r] >= 0, "start[%d] = %d is negative", r, a->start[r]);
+      ARG_CHECK(a->end[r] < a->h_rows, "end[%d] = %d is past the last row %d of h (end is inclusive)", r, a->end[r], a->h_rows - 1);
+      ARG_CHECK(a->start[r] <= a->end[r], "range %d is empty (start %d > end %d): the kernel would divide by zero", r, a->start[r], a->end[r]);
+    }
+  }
+  if (lncls) ARG_CHECK(a->w && a->out_f32, "ln_classifier needs w and out_f32");
+  if (pooler) {
+    ARG_CHECK(a->first_row && a->Wp && a->bp && a->out_f32, "pooler_classifier needs first_row, Wp, bp and out_f32");
+    for (int r = 0; r < rows; ++r)
+      ARG_CHECK(a->first_row[r] >= 0 && a->first_row[r] < a->h_rows, "first_row[%d] = %d outside the %d rows of h", r, a->first_row[r], a->h_rows);
+  }
+  if (seqh) {
+    ARG_CHECK(a->seq_row && a->seq_len && a->pooled && a->WdT && a->wn && a->out_f32, "seq_head needs seq_row, seq_len, pooled, WdT, wn and out_f32");
+    for (int r = 0; r < rows; ++r) {
+      ARG_CHECK(a->seq_len[r] >= 1, "seq_len[%d] = %d must be at least 1", r, a->seq_len[r]);
+      ARG_CHECK(a->seq_row[r] >= 0, "seq_row[%d] = %d is negative", r, a->seq_row[r]);
+      ARG_CHECK((int64_t)a->seq_row[r] + a->seq_len[r] <= a->h_rows, "sequence %d (row %d, %d tokens) ends past the %d rows of h", r, a->seq_row[r], a->seq_len[r], a->h_rows);
+    }
+  }
+  if (classifier) {
+    ARG_CHECK(a->num_labels >= 1, "num_labels (%d) must be at least 1 where a classifier runs", a->num_labels);
+    ARG_CHECK(a->Wc && a->bc, "the classifier needs Wc and bc");
+  }
+  if (vrag_device_count() <= device) {
+    set_error("no HIP device %d visible", device);
+    return VRAG_ERR_NO_DEVICE;
+  }
+  HIP_TRY(hipSetDevice(device));
+
+  // device copies: every buffer is followed by a 4 KiB canary that the launch must leave as it was
+  constexpr size_t kCanary = 4096;
+  constexpr unsigned char kCanaryByte = 0xA5;
+  struct Buf {
+    const void* host;
+    void* host_out;   // null = input only
+    size_t bytes;
+    const char* name;
+    DevBuf dev;   // bytes + kCanary
+  };
+  std::vector<Buf> bufs;
+  auto add = [&](const void* h, void* h_out, size_t bytes, const char* name) -> int {
+    if (!h) return -1;
+    bufs.push_back(Buf{h, h_out, bytes, name, DevBuf()});
+    return (int)bufs.size() - 1;
+  };
+  const size_t R = (size_t)rows, OR = (size_t)a->out_rows, Hs = (size_t)H, L = (size_t)std::max(a->num_labels, 0);
+  const size_t out_cols = (embed || ln || (range && a->mode != 0)) ? Hs : L;
+  const bool alias = ln && a->alias_f32;
+  const int ih = embed ? -1 : add(a->h, alias ? a->h : nullptr, (size_t)a->h_rows * Hs * 4, "h");
+  const int iids = embed ? add(a->ids, nullptr, R * 4, "ids") : -1;
+  const int iE = embed ? add(a->E, nullptr, (size_t)a->vocab * Hs * 4, "E") : -1;
+  const int iP = embed ? add(a->P, nullptr, (size_t)std::max(a->n_pos, 0) * Hs * 4, "P") : -1;
+  const int ipos = embed ? add(a->pos, nullptr, R * 4, "pos") : -1;
+  const int ityp = embed ? add(a->type_row, nullptr, (size_t)std::max(a->n_types, 0) * Hs * 4, "type_row") : -1;
+  const int itid = embed ? add(a->type_ids, nullptr, R * 4, "type_ids") : -1;
+  const int iw = add(a->w, nullptr, Hs * 4, "w");
+  const int ibias = add(a->bias, nullptr, Hs * 4, "bias");
+  const int istart = range ? add(a->start, nullptr, R * 4, "start") : -1;
+  const int iend = range ? add(a->end, nullptr, R * 4, "end") : -1;
+  const int ifirst = pooler ? add(a->first_row, nullptr, R * 4, "first_row") : -1;
+  const int isrow = seqh ? add(a->seq_row, nullptr, R * 4, "seq_row") : -1;
+  const int islen = seqh ? add(a->seq_len, nullptr, R * 4, "seq_len") : -1;
+  const int iWp = pooler ? add(a->Wp, nullptr, Hs * Hs * 4, "Wp") : -1;
+  const int ibp = pooler ? add(a->bp, nullptr, Hs * 4, "bp") : -1;
+  const int iWd = seqh ? add(a->WdT, nullptr, Hs * Hs * 4, "WdT") : -1;
+  const int ibd = seqh ? add(a->bd, nullptr, Hs * 4, "bd") : -1;
+  const int iwn = seqh ? add(a->wn, nullptr, Hs * 4, "wn") : -1;
+  const int ibn = seqh ? add(a->bn, nullptr, Hs * 4, "bn") : -1;
+  const int iWc = add(a->Wc, nullptr, L * Hs * 4, "Wc");
+  const int ibc = add(a->bc, nullptr, L * 4, "bc");
+  const int iof = add(a->out_f32, a->out_f32, OR * out_cols * 4, "out_f32");
+  const int io16 = (embed || ln) ? add(a->out16, a->out16, OR * (ln && a->split3 ? 3 * Hs : Hs) * 2, "out16") : -1;
+  const int ilo = ln ? add(a->out_lo, a->out_lo, OR * Hs * 2, "out_lo") : -1;
+  const int imean = ln ? add(a->row_mean, a->row_mean, OR * 4, "row_mean") : -1;
+  const int ipool = seqh ? add(a->pooled, a->pooled, OR * Hs * 4, "pooled") : -1;
+  DevBuf sat;   // the launch's fp16 clamp word, reported in f16_saturated
+  hipError_t e = sat.alloc(4);
+  if (e == hipSuccess) e = hipMemset(sat.p, 0, 4);
+  for (Buf& b : bufs) {
+    if (e == hipSuccess) e = b.dev.alloc(b.bytes + kCanary);
+    if (e == hipSuccess && b.bytes) e = hipMemcpy(b.dev.p, b.host, b.bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(b.dev.as<char>() + b.bytes, kCanaryByte, kCanary);
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    set_error("debug rows run: staging failed: %s", hipGetErrorString(e));
+    return VRAG_ERR_HIP;
+  }
+  auto fp = [&](int i) -> float* { return i < 0 ? nullptr : bufs[i].dev.as<float>(); };
+  auto ip = [&](int i) -> int* { return i < 0 ? nullptr : bufs[i].dev.as<int>(); };
+  auto hp = [&](int i) -> bf16_t* { return i < 0 ? nullptr : bufs[i].dev.as<bf16_t>(); };
+  const int dt = a->f16 ? kOpF16 : kOpBf16;
+  unsigned* satp = a->no_sat ? nullptr : sat.as<unsigned>();
+  hipError_t le = hipSuccess;
+  switch (op) {
+    case VRAG_DEBUG_ROWS_EMBED_LN:
+      le = launch_embed_ln(ip(iids), fp(iE), fp(iw), a->eps, H, rows, fp(iof), hp(io16), 0, fp(iP), ip(ipos), fp(ityp), fp(ibias), ip(itid), dt, satp);
+      break;
+    case VRAG_DEBUG_ROWS_LAYERNORM:
+      le = launch_layernorm(fp(ih), fp(iw), a->eps, H, rows, hp(io16), alias ? fp(ih) : fp(iof), 0, fp(ibias), fp(imean), dt, hp(ilo), a->gelu_first,
+                            a->split3, satp);
+      break;
+    case VRAG_DEBUG_ROWS_RANGE_POOL:
+      le = launch_range_pool(fp(ih), fp(iw), a->eps, H, ip(istart), ip(iend), rows, a->mode, fp(iWc), fp(ibc), a->num_labels, fp(iof), 0);
+      break;
+    case VRAG_DEBUG_ROWS_LN_CLASSIFIER:
+      le = launch_ln_classifier(fp(ih), fp(iw), a->eps, H, rows, fp(iWc), fp(ibc), a->num_labels, fp(iof), 0, fp(ibias), a->gelu_first);
+      break;
+    case VRAG_DEBUG_ROWS_POOLER_CLASSIFIER:
+      le = launch_pooler_classifier(fp(ih), H, ip(ifirst), rows, fp(iWp), fp(ibp), fp(iWc), fp(ibc), a->num_labels, fp(iof), 0);
+      break;
+    default:
+      le = launch_seq_head(fp(ih), fp(iw), a->eps, H, ip(isrow), ip(islen), rows, a->mode, fp(ipool), fp(iWd), fp(ibd), fp(iwn), fp(ibn), fp(iWc),
+                           fp(ibc), a->num_labels, fp(iof), 0);
+      break;
+  }
+  a->launch_status = (int32_t)le;
+  e = hipDeviceSynchronize();
+  unsigned saturated = 0;
+  if (e == hipSuccess) e = hipMemcpy(&saturated, sat.p, 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) a->f16_saturated = saturated ? 1 : 0;
+  std::vector<unsigned char> canary(kCanary);
+  const char* clobbered = nullptr;
+  for (Buf& b : bufs) {
+    if (e != hipSuccess) break;
+    e = hipMemcpy(canary.data(), b.dev.as<char>() + b.bytes, kCanary, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !clobbered && std::any_of(canary.begin(), canary.end(), [](unsigned char v) { return v != kCanaryByte; }))
+      clobbered = b.name;
+    if (e == hipSuccess && b.host_out && b.bytes) e = hipMemcpy(b.host_out, b.dev.p, b.bytes, hipMemcpyDeviceToHost);
+  }
+  if (e != hipSuccess) {
+    set_error("debug rows run failed: %s", hipGetErrorString(e));
+    return VRAG_ERR_HIP;
+  }
+  if (clobbered) {
+    set_error("debug rows run: the launch wrote past the end of %s", clobbered);
+    return VRAG_ERR_HIP;
+  }
+  if (le != hipSuccess) {
+    set_error("debug rows run: the launcher returned %s", hipGetErrorString(le));
+    return le == hipErrorInvalidValue ? VRAG_ERR_INVALID : VRAG_ERR_HIP;
+  }
   return VRAG_OK;
 }
 

@@ -159,7 +159,6 @@ __global__ __launch_bounds__(256) void range_pool_kernel(const float* __restrict
                                                           const float* __restrict__ Wc, const float* __restrict__ bc,
                                                           int num_labels, float* __restrict__ out) {
   __shared__ float red[4][MAXV * 256];
-  __shared__ float nrm[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = blockIdx.x;
   const int s = start[r], e = end[r];
@@ -221,7 +220,6 @@ __global__ __launch_bounds__(256) void range_pool_kernel(const float* __restrict
       }
     }
   }
-  (void)nrm;
 }
 
 __global__ __launch_bounds__(256) void ln_classifier_kernel(const float* __restrict__ x_in, const float* __restrict__ lnw,
