@@ -326,6 +326,19 @@ int vrag_dense_index_run_resident(vrag_dense_index* ix, int32_t nq, int32_t k, v
 int vrag_dense_index_search_device(vrag_dense_index* ix, const float* queries /*[nq,dim] host*/, int32_t nq, int32_t k,
                                    const int64_t* row_map /*device or NULL*/, int64_t n_map, int64_t id_base,
                                    float* out_scores /*[nq,k] device*/, int64_t* out_ids /*[nq,k] device*/, void* stream);
+/* Filtered search over the RESIDENT rows (the reference's `filter` / delete semantics, index.py:723-739: Milvus filters before
+ * it searches): the top-k of exactly the rows r < min(n_allow, size) whose bit is set in `allow` (host words, bit r % 32 of word
+ * r / 32).  Rows at or beyond n_allow are excluded, so a mask built before a concurrent append stays valid.  Order, missing-hit
+ * encoding, 1 <= k <= 1024 and the exact pages of 64 are those of vrag_dense_index_search.  Scores are the sequential chain
+ * acc = fmaf(x[c], q[c], acc), c ascending, bit for bit on every index type: over the fp32 row (dtype 1 and 2 -- the bf16 image of
+ * dtype 2 is never consulted) or the bf16 row widened to fp32 (dtype 0), against the fp32 query.  The bitmap is compacted on the
+ * device into the ascending list of passing rows and the chains run over that list only: the cost follows the passing rows, not
+ * the shard.  n_allow == 0 or a mask without a set bit returns -1 / -inf lists without a launch; a null `allow` with n_allow > 0,
+ * k out of range or nq <= 0 is VRAG_ERR_INVALID before anything is launched or allocated.  Bitmap and row list live in the
+ * handle's scratch; unfiltered searches on the handle are not affected (run_resident afterwards re-runs THESE queries). */
+int vrag_dense_index_search_filtered(vrag_dense_index* ix, const float* queries /*[nq,dim] host*/, int32_t nq, int32_t k,
+                                     const uint32_t* allow /*host, bit r%32 of word r/32*/, int64_t n_allow,
+                                     float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, void* stream);
 
 /* Sparse (SPLADE) rows in CSR, term ids < vocab <= 65536; only documents sharing a term with the
  * query (score > 0) are hits, like an inverted index.  ids are CSR row numbers. */
@@ -338,6 +351,13 @@ int vrag_sparse_index_search(vrag_sparse_index* ix, const int64_t* q_indptr, con
                              const float* q_values, int32_t nq, int32_t k, float* scores /*[nq,k]*/,
                              int64_t* ids /*[nq,k]*/, void* stream);
 int vrag_sparse_index_run_resident(vrag_sparse_index* ix, int32_t nq, int32_t k, void* stream);
+/* vrag_sparse_index_search over the documents d < min(n_allow, n_docs) whose bit is set in `allow` (as
+ * vrag_dense_index_search_filtered: same bitmap, same refusals, same empty-mask answer).  The single-query SELL walk with the list
+ * insertion gated by the document's bit -- scores are fmaf(value_j, q[term_j], acc) in CSR order, a hit needs a shared term --
+ * and a 64-document slice without a passing document is skipped before its loads. */
+int vrag_sparse_index_search_filtered(vrag_sparse_index* ix, const int64_t* q_indptr, const int32_t* q_indices,
+                                      const float* q_values, int32_t nq, int32_t k, const uint32_t* allow, int64_t n_allow,
+                                      float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, void* stream);
 /* Device-resident result lists, as vrag_dense_index_search_device. */
 int vrag_sparse_index_search_device(vrag_sparse_index* ix, const int64_t* q_indptr, const int32_t* q_indices,
                                     const float* q_values, int32_t nq, int32_t k, const int64_t* row_map /*device or NULL*/,

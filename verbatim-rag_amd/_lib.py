@@ -118,6 +118,7 @@ SIGNATURES = {
     "vrag_dense_index_add": (C.c_int, [_H, _FP, C.c_int64]),
     "vrag_dense_index_add_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p]),
     "vrag_dense_index_search": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, _FP, _LP, C.c_void_p]),
+    "vrag_dense_index_search_filtered": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _FP, _LP, C.c_void_p]),
     "vrag_dense_index_run_resident": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p]),
     "vrag_dense_index_search_device": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]),
@@ -131,6 +132,8 @@ SIGNATURES = {
     "vrag_sparse_index_destroy": (None, [_H]),
     "vrag_sparse_index_stats": (C.c_int, [_H, _LP, _LP, _LP]),
     "vrag_sparse_index_search": (C.c_int, [_H, _LP, _IP, _FP, C.c_int32, C.c_int32, _FP, _LP, C.c_void_p]),
+    "vrag_sparse_index_search_filtered": (C.c_int, [_H, _LP, _IP, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _FP, _LP,
+                                                    C.c_void_p]),
     "vrag_sparse_index_run_resident": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p]),
     "vrag_text_tokenize": (C.c_int, [C.c_void_p, _LP, C.c_int32, C.c_int32, C.c_int64, _IP, C.c_void_p, _LP]),
     "vrag_text_index_create": (C.c_int, [C.c_float, C.c_float, C.c_int32, C.POINTER(_H)]),

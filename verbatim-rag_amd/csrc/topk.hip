@@ -2173,6 +2173,250 @@ __global__ void topk_fill_empty_kernel(float* __restrict__ scores, long long* __
   }
 }
 
+// ------------------------------------------------------------------------------------ filtered search (row bitmap)
+// vrag_*_index_search_filtered: the top-k of exactly the rows whose bit is set in a caller's bitmap, over the RESIDENT rows (the
+// store used to build a second shard of the passing rows from its host copies).  A route of its own -- no search kernel above
+// reads a bitmap.  Dense: the bitmap is compacted into the ascending list of passing rows (popcount + prefix scan, no atomic
+// appends: the list is the same on every run), then the exact chains run over that list only -- cost proportional to the
+// passing rows, not to the shard.  Sparse: the single-query SELL walk with the top-k insertion gated by the document's bit.
+constexpr int FWORDS = 1024;   // bitmap words per workgroup of the compaction (256 threads x one 16-byte load)
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// words: the bitmap padded with zero words to a multiple of FWORDS (the host clears the bits at and beyond the row count), so no
+// kernel below tests a bound.  blk_cnt[b] = set bits of workgroup b's words.
+__global__ __launch_bounds__(256) void filter_count_kernel(const unsigned* __restrict__ words, unsigned* __restrict__ blk_cnt) {
+  __shared__ unsigned red[4];
+  const int tid = threadIdx.x;
+  const u32x4 w = reinterpret_cast<const u32x4*>(words)[(size_t)blockIdx.x * 256 + tid];
+  unsigned c = __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((tid & 63) == 0) red[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) blk_cnt[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+// Inclusive prefix sum of one value per thread over the 256 threads of a workgroup (wave scans + the four wave totals in LDS).
+__device__ __forceinline__ unsigned block_scan_incl(unsigned v, unsigned* wave_tot) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned up = __shfl_up(v, o, 64);
+    if (lane >= o) v += up;
+  }
+  if (lane == 63) wave_tot[wave] = v;
+  __syncthreads();
+  unsigned base = 0;
+  for (int w = 0; w < wave; ++w) base += wave_tot[w];
+  __syncthreads();   // wave_tot may be rewritten by the caller's next round
+  return v + base;
+}
+
+// One workgroup: blk_off[b] = passing rows in front of workgroup b's words, blk_off[n_blk] = all of them (the list's count).
+__global__ __launch_bounds__(256) void filter_scan_kernel(const unsigned* __restrict__ blk_cnt, int n_blk, unsigned* __restrict__ blk_off) {
+  __shared__ unsigned wave_tot[4];
+  __shared__ unsigned carry_s;
+  const int tid = threadIdx.x;
+  if (tid == 0) carry_s = 0u;
+  __syncthreads();
+  for (int b0 = 0; b0 < n_blk; b0 += 256) {
+    const int b = b0 + tid;
+    const unsigned c = b < n_blk ? blk_cnt[b] : 0u;
+    const unsigned incl = block_scan_incl(c, wave_tot);
+    const unsigned carry = carry_s;
+    if (b < n_blk) blk_off[b] = carry + incl - c;
+    __syncthreads();
+    if (tid == 255) carry_s = carry + incl;
+    __syncthreads();
+  }
+  if (tid == 0) blk_off[n_blk] = carry_s;
+}
+
+// The list itself: thread t of workgroup b writes the rows of its four words behind blk_off[b] + (set bits of the threads in
+// front of it) -- words ascending, bits ascending, so the list is ascending.  A workgroup without a set bit leaves before its
+// loads (a zero word costs the one load of the count pass).
+__global__ __launch_bounds__(256) void filter_emit_kernel(const unsigned* __restrict__ words, const unsigned* __restrict__ blk_cnt,
+                                                           const unsigned* __restrict__ blk_off, unsigned* __restrict__ list) {
+  __shared__ unsigned wave_tot[4];
+  if (blk_cnt[blockIdx.x] == 0u) return;
+  const int tid = threadIdx.x;
+  const size_t w0 = ((size_t)blockIdx.x * 256 + tid) * 4;
+  const u32x4 w = reinterpret_cast<const u32x4*>(words)[(size_t)blockIdx.x * 256 + tid];
+  const unsigned c = __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]);
+  size_t pos = (size_t)blk_off[blockIdx.x] + block_scan_incl(c, wave_tot) - c;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    unsigned bits = w[j];
+    while (bits) {
+      list[pos++] = (unsigned)((w0 + j) * 32) + (unsigned)__builtin_ctz(bits);
+      bits &= bits - 1u;
+    }
+  }
+}
+
+// Exact keys of a row list: FROWS rows x FQT queries per workgroup step.  As in prefilter_rescore_list_kernel what costs is
+// fetching the scattered rows: all 256 threads stage FCH columns of the FROWS rows and of the workgroup's queries through LDS in
+// coalesced 16-byte pieces (bf16 rows are widened to fp32 on the way in: the chain's operand), then thread (row, query) runs ONE
+// serial chain  acc = fmaf(x[c], q[c], acc), c ascending  out of LDS (row stride FCH + 4 words: the 16 b128 reads of a step fall
+// in 16 different bank quartets, the queries' are broadcasts).  The step's keys go through LDS to one lane per query, which keeps
+// that query's sorted list (insert_key); the workgroup's lists leave as [workgroup][query][k] for launch_topk_merge.  Workgroups
+// stride over the groups of FROWS list entries: a launch costs what the passing rows cost.
+constexpr int FROWS = 16, FQT = 16, FCH = 256;
+template <bool F32>
+__global__ __launch_bounds__(256) void filtered_score_kernel(const unsigned* __restrict__ list, const unsigned* __restrict__ cnt_p,
+                                                              const void* __restrict__ rows_v, int dim,
+                                                              const float* __restrict__ queries, int nq, int k,
+                                                              u64* __restrict__ cand, const u64* __restrict__ bound) {
+  __shared__ __attribute__((aligned(16))) float srow[FROWS][FCH + 4];
+  __shared__ __attribute__((aligned(16))) float sq[FQT][FCH + 4];
+  __shared__ u64 lists[FQT][KMAX];
+  __shared__ u64 skey[FQT][FROWS];
+  __shared__ unsigned srid[FROWS];
+  const int tid = threadIdx.x, r = tid & (FROWS - 1), qi = tid >> 4;
+  const int q0 = blockIdx.y * FQT, nqt = min(FQT, nq - q0);
+  const unsigned n = *cnt_p;
+  const unsigned n_groups = (n + FROWS - 1) / FROWS;
+  for (int i = tid; i < FQT * k; i += 256) lists[i / k][i % k] = 0ull;
+  const u64 my_bound = (bound && qi < nqt) ? bound[q0 + qi] : ~0ull;
+  constexpr int PW = F32 ? 4 : 8;   // columns of a 16-byte piece of a row
+  for (unsigned g = blockIdx.x; g < n_groups; g += gridDim.x) {
+    const unsigned base = g * FROWS;
+    __syncthreads();   // the previous step's chains and insertions are done with srid / skey
+    if (tid < FROWS) srid[tid] = list[min(base + tid, n - 1u)];   // slots behind the list re-read its last row; their keys are dropped
+    __syncthreads();
+    float acc = 0.f;
+    for (int c0 = 0; c0 < dim; c0 += FCH) {
+      const int w = min(FCH, dim - c0);   // dim % 8 == 0 (vrag_dense_index_create)
+      const int ppr = w / PW, total = FROWS * ppr;
+      for (int p = tid; p < total; p += 256) {
+        const int rr = p / ppr, cc = PW * (p % ppr);
+        if constexpr (F32) {
+          *reinterpret_cast<f32x4*>(&srow[rr][cc]) =
+              *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(rows_v) + (size_t)srid[rr] * dim + c0 + cc);
+        } else {
+          const bf16x8 v = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(rows_v) + (size_t)srid[rr] * dim + c0 + cc);
+          f32x4 lo, hi;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            lo[j] = (float)v[j];
+            hi[j] = (float)v[4 + j];
+          }
+          *reinterpret_cast<f32x4*>(&srow[rr][cc]) = lo;
+          *reinterpret_cast<f32x4*>(&srow[rr][cc + 4]) = hi;
+        }
+      }
+      const int qpr = w / 4;
+      for (int p = tid; p < nqt * qpr; p += 256) {
+        const int qq = p / qpr, cc = 4 * (p % qpr);
+        *reinterpret_cast<f32x4*>(&sq[qq][cc]) = *reinterpret_cast<const f32x4*>(queries + (size_t)(q0 + qq) * dim + c0 + cc);
+      }
+      __syncthreads();
+      if (qi < nqt) {
+#pragma unroll 8
+        for (int c = 0; c < w; c += 4) {
+          const f32x4 xv = *reinterpret_cast<const f32x4*>(&srow[r][c]);
+          const f32x4 qv = *reinterpret_cast<const f32x4*>(&sq[qi][c]);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc = __fmaf_rn(xv[j], qv[j], acc);
+        }
+      }
+      __syncthreads();
+    }
+    skey[qi][r] = (qi < nqt && base + r < n) ? make_key_below(acc, srid[r], my_bound) : 0ull;
+    __syncthreads();
+    if (r == 0 && qi < nqt) {
+      for (int i = 0; i < FROWS; ++i) insert_key(lists[qi], k, skey[qi][i]);
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < nqt * k; i += 256) cand[((size_t)blockIdx.x * nq + q0 + i / k) * k + i % k] = lists[i / k][i % k];
+}
+
+// sparse_topk_kernel with a row bitmap: a slice position's document comes from docid[], and its bit (rows at or beyond n_allow
+// have none) gates the INSERTION only -- the chain is the unfiltered walk's.  A 64-document slice without a set bit is skipped
+// before it loads anything of the slice.
+template <bool LDSQ>
+__global__ __launch_bounds__(1024) void sparse_topk_filtered_kernel(const unsigned short* __restrict__ cols,
+                                                                     const float* __restrict__ vals,
+                                                                     const long long* __restrict__ slice_off,
+                                                                     const int* __restrict__ slice_len, int n_slices,
+                                                                     long long n_docs, const float* __restrict__ qdense, int vocab,
+                                                                     int nq, int q, int k, u64* __restrict__ cand,
+                                                                     const unsigned* __restrict__ docid,
+                                                                     const unsigned* __restrict__ allow, long long n_allow,
+                                                                     const u64* __restrict__ bound) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  u64* lists = reinterpret_cast<u64*>(smem);   // [16 waves][k], then (LDSQ) the dense query vector
+  float* sq = reinterpret_cast<float*>(smem + (size_t)16 * k * sizeof(u64));
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* qv = qdense + (size_t)q * vocab;
+  if constexpr (LDSQ) {
+    for (int i = tid; i < vocab; i += 1024) sq[i] = qv[i];
+  }
+  for (int i = tid; i < 16 * k; i += 1024) lists[i] = 0ull;
+  __syncthreads();
+  u64* mylist = lists + (size_t)wave * k;
+  for (int s = blockIdx.x + gridDim.x * wave; s < n_slices; s += gridDim.x * 16) {
+    const long long doc = (long long)s * 64 + lane;   // position in nnz-sorted order
+    unsigned did = 0u;
+    bool pass = false;
+    if (doc < n_docs) {
+      did = docid[doc];
+      pass = (long long)did < n_allow && ((allow[did >> 5] >> (did & 31u)) & 1u);
+    }
+    if (!__ballot(pass)) continue;
+    const long long off = slice_off[s];
+    const int ng = slice_len[s];   // groups of 4 terms
+    const u32x2* c = reinterpret_cast<const u32x2*>(cols + off) + lane;
+    const f32x4* v = reinterpret_cast<const f32x4*>(vals + off) + lane;
+    float acc = 0.f;
+    auto qw = [&](unsigned t) { return LDSQ ? sq[t] : qv[t]; };
+    auto consume = [&](const u32x2& cg, const f32x4& vg) {   // strictly sequential, term-order fmaf chain
+      acc = __fmaf_rn(vg[0], qw(cg[0] & 0xFFFFu), acc);
+      acc = __fmaf_rn(vg[1], qw(cg[0] >> 16), acc);
+      acc = __fmaf_rn(vg[2], qw(cg[1] & 0xFFFFu), acc);
+      acc = __fmaf_rn(vg[3], qw(cg[1] >> 16), acc);
+    };
+    int g = 0;
+    for (; g + 8 <= ng; g += 8) {
+      u32x2 cg[8];
+      f32x4 vg[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        cg[u] = __builtin_nontemporal_load(c + (size_t)(g + u) * 64);
+        vg[u] = __builtin_nontemporal_load(v + (size_t)(g + u) * 64);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) consume(cg[u], vg[u]);
+    }
+    for (; g < ng; ++g) consume(c[(size_t)g * 64], v[(size_t)g * 64]);
+    const bool hit = pass && acc > 0.f;   // inverted-index semantics: no shared term => not a hit
+    const u64 key = hit ? make_key_below(acc, did, bound ? bound[q] : ~0ull) : 0ull;
+    wave_insert_topk(mylist, k, key, lane);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int head[16];
+    for (int g = 0; g < 16; ++g) head[g] = 0;
+    u64* out = cand + ((size_t)blockIdx.x * nq + q) * k;
+    for (int i = 0; i < k; ++i) {
+      u64 best = 0ull;
+      int bg = -1;
+      for (int g = 0; g < 16; ++g) {
+        if (head[g] < k) {
+          const u64 v = lists[(size_t)g * k + head[g]];
+          if (v > best) {
+            best = v;
+            bg = g;
+          }
+        }
+      }
+      out[i] = best;
+      if (bg >= 0) ++head[bg];
+    }
+  }
+}
+
 }  // namespace vrag
 
 using namespace vrag;
@@ -2212,6 +2456,10 @@ struct vrag_dense_index {
   hipEvent_t upload_done = nullptr;   // recorded behind the query upload: the host buffer is free once it has passed
   hipEvent_t lists_done = nullptr;    // recorded behind a device-resident search: the next search (any stream) waits for it before reusing the scratch
   bool warmed = false;                // dense_warm_query_path has run (first add that brought the shard to >= 4096 rows)
+  // vrag_dense_index_search_filtered: the caller's bitmap (host staging, device copy), the compaction's per-workgroup counts and
+  // offsets ([n] counts, then [n + 1] offsets: the last one is the list's length) and the ascending list of passing rows
+  std::vector<unsigned> h_allow;
+  DevArray<unsigned> d_fallow, d_fblk, d_flist;
 };
 
 // May a search of `nq` queries take the prefilter-image route of an fp32 index?  The route's fallback -- the full fp32 scan
@@ -2256,6 +2504,8 @@ struct vrag_sparse_index {
   bool last_multi = false;   // which kernel family the resident queries were prepared for
   hipEvent_t upload_done = nullptr;   // recorded behind the query-table uploads
   hipEvent_t lists_done = nullptr;    // as in vrag_dense_index
+  std::vector<unsigned> h_allow;      // vrag_sparse_index_search_filtered: the caller's bitmap, host staging and device copy
+  DevArray<unsigned> d_fallow;
 };
 
 namespace {
@@ -3022,6 +3272,84 @@ int vrag_dense_index_search(vrag_dense_index* ix, const float* queries, int32_t 
   return VRAG_OK;
 }
 
+// Host staging of a caller's bitmap for the filtered searches: the words of rows [0, n_rows) with the bits at and beyond n_rows
+// cleared, then zero words up to a multiple of `pad`.  Returns the number of set bits.
+static long long stage_allow(std::vector<unsigned>& h, const uint32_t* allow, long long n_rows, size_t pad) {
+  const size_t n_words = (size_t)((n_rows + 31) / 32);
+  h.assign((n_words + pad - 1) / pad * pad, 0u);
+  std::memcpy(h.data(), allow, n_words * sizeof(unsigned));
+  if (n_rows % 32) h[n_words - 1] &= (1u << (n_rows % 32)) - 1u;
+  long long n_pass = 0;
+  for (size_t i = 0; i < n_words; ++i) n_pass += __builtin_popcount(h[i]);
+  return n_pass;
+}
+
+static void fill_no_hits(float* scores, int64_t* ids, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    scores[i] = -INFINITY;
+    ids[i] = -1;
+  }
+}
+
+constexpr int FILTER_WGS = 2048;   // most workgroups of the scoring pass per query tile (256 CUs x 3 resident, a few rounds)
+int vrag_dense_index_search_filtered(vrag_dense_index* ix, const float* queries, int32_t nq, int32_t k, const uint32_t* allow,
+                                     int64_t n_allow, float* scores, int64_t* ids, void* stream) {
+  ARG_CHECK(ix && queries && scores && ids && nq > 0, "bad arguments");
+  ARG_CHECK(k > 0 && k <= KPAGED_MAX, "k must be in [1, %d] (got %d)", KPAGED_MAX, k);
+  ARG_CHECK(n_allow >= 0 && (allow || n_allow == 0), "bad row bitmap (null words or a negative length)");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  HIP_TRY(hipSetDevice(ix->device));
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ix->stream;
+  if (ix->lists_done) HIP_TRY(hipStreamWaitEvent(st, ix->lists_done, 0));
+  const long long n_rows = std::min<long long>(n_allow, ix->size);   // rows appended after the mask was built are not in it
+  const long long n_pass = n_rows > 0 ? stage_allow(ix->h_allow, allow, n_rows, FWORDS) : 0;
+  if (n_pass == 0) {   // nothing passes: no launch
+    fill_no_hits(scores, ids, (size_t)nq * k);
+    return VRAG_OK;
+  }
+  const int dim = ix->dim, kk = std::min<int>(k, KMAX);
+  const int n_blk = (int)(ix->h_allow.size() / FWORDS);
+  const int n_wg = (int)std::min<long long>((n_pass + FROWS - 1) / FROWS, FILTER_WGS);
+  HIP_TRY(ix->d_fallow.grow(ix->h_allow.size()));
+  HIP_TRY(ix->d_fblk.grow((size_t)2 * n_blk + 1));
+  HIP_TRY(ix->d_flist.grow((size_t)n_pass));
+  HIP_TRY(ix->d_q.grow((size_t)nq * dim));
+  HIP_TRY(ix->d_cand.grow((size_t)n_wg * nq * kk));
+  HIP_TRY(ix->d_out.grow((size_t)nq * kk + nq));
+  HIP_TRY(hipMemcpyAsync(ix->d_fallow.p, ix->h_allow.data(), ix->h_allow.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ix->d_q.p, queries, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, st));
+  if (!ix->upload_done) HIP_TRY(hipEventCreateWithFlags(&ix->upload_done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(ix->upload_done, st));
+  ix->resident_split = 0;   // d_q holds these queries now, as plain fp32 rows
+  unsigned* blk_cnt = ix->d_fblk.p;
+  unsigned* blk_off = ix->d_fblk.p + n_blk;
+  hipLaunchKernelGGL(filter_count_kernel, dim3(n_blk), dim3(256), 0, st, ix->d_fallow.p, blk_cnt);
+  hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(256), 0, st, blk_cnt, n_blk, blk_off);
+  hipLaunchKernelGGL(filter_emit_kernel, dim3(n_blk), dim3(256), 0, st, ix->d_fallow.p, blk_cnt, blk_off, ix->d_flist.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventSynchronize(ix->upload_done));   // the caller's queries and the staged bitmap have been consumed
+  auto run = [&](const u64* bound) -> int {
+    const dim3 grid(n_wg, (nq + FQT - 1) / FQT);
+    if (ix->dtype == 1)   // dtype 2 too: the chains run over the fp32 rows, never over the bf16 image
+      hipLaunchKernelGGL(filtered_score_kernel<true>, grid, dim3(256), 0, st, ix->d_flist.p, blk_off + n_blk, ix->rows.p, dim, ix->d_q.p,
+                         nq, kk, ix->d_cand.p, bound);
+    else
+      hipLaunchKernelGGL(filtered_score_kernel<false>, grid, dim3(256), 0, st, ix->d_flist.p, blk_off + n_blk, ix->rows.p, dim, ix->d_q.p,
+                         nq, kk, ix->d_cand.p, bound);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_topk_merge(ix->d_cand.p, n_wg, nq, kk, ix->d_out.p, st));
+    return VRAG_OK;
+  };
+  if (k > KMAX) return paged_search(nq, k, ix->d_bound, ix->d_out, st, run, scores, ids);
+  int rc;
+  if ((rc = run(nullptr))) return rc;
+  std::vector<u64> keys((size_t)nq * k);
+  HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_out.p, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  decode_keys(keys, nq, k, 0, nullptr, scores, ids);
+  return VRAG_OK;
+}
+
 int vrag_dense_index_search_device(vrag_dense_index* ix, const float* queries, int32_t nq, int32_t k, const int64_t* row_map,
                                    int64_t n_map, int64_t id_base, float* out_scores, int64_t* out_ids, void* stream) {
   ARG_CHECK(ix && queries && out_scores && out_ids && nq > 0, "bad arguments");
@@ -3250,6 +3578,37 @@ static int sparse_launch(vrag_sparse_index* ix, int nq, int k, hipStream_t st, i
   return VRAG_OK;
 }
 
+// Dense query vectors [nq][vocab] in ix->d_q for the single-query kernels (plain and filtered): the (term, weight) pairs travel --
+// a few hundred bytes per query instead of 4 B x vocab (122 KB at V = 30 522: ~40 us of a 0.24 ms single-query call went into
+// building and copying zeros) -- and are scattered on the device into a cleared vector, one thread per query in the query's own
+// term order (a repeated term keeps its last value, as the host scatter did).  Caller holds ix->mu, has waited for a pending
+// upload of the handle's host buffers and has created ix->upload_done.
+static int sparse_scatter_enqueue(vrag_sparse_index* ix, const int64_t* q_indptr, const int32_t* q_indices, const float* q_values,
+                                  int nq, hipStream_t st) {
+  const int64_t nnz_q = q_indptr[nq] - q_indptr[0];
+  const size_t off_idx = (size_t)(nq + 1) * sizeof(int64_t), off_val = off_idx + (size_t)nnz_q * sizeof(int32_t);
+  std::vector<char>& blob = ix->h_blob;
+  blob.resize(off_val + (size_t)nnz_q * sizeof(float));
+  {
+    int64_t* ip = reinterpret_cast<int64_t*>(blob.data());
+    for (int q = 0; q <= nq; ++q) ip[q] = q_indptr[q] - q_indptr[0];
+    if (nnz_q > 0) {
+      memcpy(blob.data() + off_idx, q_indices + q_indptr[0], (size_t)nnz_q * sizeof(int32_t));
+      memcpy(blob.data() + off_val, q_values + q_indptr[0], (size_t)nnz_q * sizeof(float));
+    }
+  }
+  HIP_TRY(ix->d_q.grow((size_t)nq * ix->vocab));
+  HIP_TRY(ix->d_qcsr.grow(blob.size()));
+  HIP_TRY(hipMemsetAsync(ix->d_q.p, 0, (size_t)nq * ix->vocab * sizeof(float), st));
+  HIP_TRY(hipMemcpyAsync(ix->d_qcsr.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipEventRecord(ix->upload_done, st));
+  hipLaunchKernelGGL(sparse_scatter_queries_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, reinterpret_cast<const long long*>(ix->d_qcsr.p),
+                     reinterpret_cast<const int*>(ix->d_qcsr.p + off_idx), reinterpret_cast<const float*>(ix->d_qcsr.p + off_val), nq, ix->vocab, ix->d_q.p);
+  HIP_TRY(hipGetLastError());
+  ix->upload_pending = true;   // the host blob stays in the handle: no wait here
+  return VRAG_OK;
+}
+
 // One device pass (k <= KMAX) of a sparse search: query tables up, phase 1 + per-query merge enqueued, keys left in
 // ix->d_out.  Returns once the uploads have been consumed; caller holds ix->mu and has set the device.
 static int sparse_search_enqueue(vrag_sparse_index* ix, const int64_t* q_indptr, const int32_t* q_indices,
@@ -3313,31 +3672,7 @@ static int sparse_search_enqueue(vrag_sparse_index* ix, const int64_t* q_indptr,
     int nwg3 = 0;
     return sparse_launch(ix, nq, k, st, &nwg3);
   }
-  // Dense query vectors [nq][vocab] for the single-query kernels: the (term, weight) pairs travel -- a few hundred bytes per query
-  // instead of 4 B x vocab (122 KB at V = 30 522: ~40 us of a 0.24 ms single-query call went into building and copying zeros) --
-  // and are scattered on the device into a cleared vector, one thread per query in the query's own term order (a repeated term
-  // keeps its last value, as the host scatter did).
-  const int64_t nnz_q = q_indptr[nq] - q_indptr[0];
-  const size_t off_idx = (size_t)(nq + 1) * sizeof(int64_t), off_val = off_idx + (size_t)nnz_q * sizeof(int32_t);
-  std::vector<char>& blob = ix->h_blob;
-  blob.resize(off_val + (size_t)nnz_q * sizeof(float));
-  {
-    int64_t* ip = reinterpret_cast<int64_t*>(blob.data());
-    for (int q = 0; q <= nq; ++q) ip[q] = q_indptr[q] - q_indptr[0];
-    if (nnz_q > 0) {
-      memcpy(blob.data() + off_idx, q_indices + q_indptr[0], (size_t)nnz_q * sizeof(int32_t));
-      memcpy(blob.data() + off_val, q_values + q_indptr[0], (size_t)nnz_q * sizeof(float));
-    }
-  }
-  HIP_TRY(ix->d_q.grow((size_t)nq * ix->vocab));
-  HIP_TRY(ix->d_qcsr.grow(blob.size()));
-  HIP_TRY(hipMemsetAsync(ix->d_q.p, 0, (size_t)nq * ix->vocab * sizeof(float), st));
-  HIP_TRY(hipMemcpyAsync(ix->d_qcsr.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipEventRecord(ix->upload_done, st));
-  hipLaunchKernelGGL(sparse_scatter_queries_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, reinterpret_cast<const long long*>(ix->d_qcsr.p),
-                     reinterpret_cast<const int*>(ix->d_qcsr.p + off_idx), reinterpret_cast<const float*>(ix->d_qcsr.p + off_val), nq, ix->vocab, ix->d_q.p);
-  HIP_TRY(hipGetLastError());
-  ix->upload_pending = true;   // the host blob stays in the handle: no wait here
+  if ((rc = sparse_scatter_enqueue(ix, q_indptr, q_indices, q_values, nq, st))) return rc;
   int nwg2 = 0;
   return sparse_launch(ix, nq, k, st, &nwg2);
 }
@@ -3372,6 +3707,68 @@ int vrag_sparse_index_search(vrag_sparse_index* ix, const int64_t* q_indptr, con
     }, scores, ids);   // the first page's stream sync also keeps `qd` alive until its upload has been consumed
   }
   if ((rc = sparse_search_enqueue(ix, q_indptr, q_indices, q_values, nq, k, st))) return rc;
+  std::vector<u64> keys((size_t)nq * k);
+  HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_out.p, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  decode_keys(keys, nq, k, 0, nullptr, scores, ids);
+  return VRAG_OK;
+}
+
+int vrag_sparse_index_search_filtered(vrag_sparse_index* ix, const int64_t* q_indptr, const int32_t* q_indices,
+                                      const float* q_values, int32_t nq, int32_t k, const uint32_t* allow, int64_t n_allow,
+                                      float* scores, int64_t* ids, void* stream) {
+  ARG_CHECK(ix && q_indptr && scores && ids && nq > 0, "bad arguments");
+  ARG_CHECK(k > 0 && k <= KPAGED_MAX, "k must be in [1, %d] (got %d)", KPAGED_MAX, k);
+  ARG_CHECK(n_allow >= 0 && (allow || n_allow == 0), "bad row bitmap (null words or a negative length)");
+  ARG_CHECK(q_indptr[nq] == q_indptr[0] || (q_indices && q_values), "null query terms / weights");
+  for (int q = 0; q < nq; ++q)
+    for (int64_t j = q_indptr[q]; j < q_indptr[q + 1]; ++j)
+      ARG_CHECK(q_indices[j] >= 0 && q_indices[j] < ix->vocab, "query %d: term id %d outside the vocabulary", q, q_indices[j]);
+  std::lock_guard<std::mutex> lk(ix->mu);
+  HIP_TRY(hipSetDevice(ix->device));
+  hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ix->stream;
+  if (ix->lists_done) HIP_TRY(hipStreamWaitEvent(st, ix->lists_done, 0));
+  if (ix->upload_pending) {   // the previous call's uploads read the handle's host buffers
+    HIP_TRY(hipEventSynchronize(ix->upload_done));
+    ix->upload_pending = false;
+  }
+  const long long n_rows = std::min<long long>(n_allow, ix->n_docs);
+  const long long n_pass = n_rows > 0 ? stage_allow(ix->h_allow, allow, n_rows, 1) : 0;
+  if (n_pass == 0) {   // nothing passes: no launch
+    fill_no_hits(scores, ids, (size_t)nq * k);
+    return VRAG_OK;
+  }
+  const int kk = std::min<int>(k, KMAX);
+  const int slices_per_wg = sparse_slices_per_wg(ix);
+  const int n_wg = std::max(1, (ix->n_slices + slices_per_wg - 1) / slices_per_wg);
+  int rc;
+  if (!ix->upload_done) HIP_TRY(hipEventCreateWithFlags(&ix->upload_done, hipEventDisableTiming));
+  HIP_TRY(ix->d_fallow.grow(ix->h_allow.size()));
+  HIP_TRY(ix->d_cand.grow((size_t)n_wg * nq * kk));
+  HIP_TRY(ix->d_out.grow((size_t)nq * kk));
+  HIP_TRY(hipMemcpyAsync(ix->d_fallow.p, ix->h_allow.data(), ix->h_allow.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+  if ((rc = sparse_scatter_enqueue(ix, q_indptr, q_indices, q_values, nq, st))) return rc;   // its event covers the bitmap upload too
+  ix->last_multi = false;   // the resident queries are dense vectors now
+  const bool ldsq = (size_t)ix->vocab * sizeof(float) + (size_t)16 * kk * sizeof(u64) <= 160 * 1024;
+  const size_t lds = (size_t)16 * kk * sizeof(u64) + (ldsq ? (size_t)ix->vocab * sizeof(float) : 0);
+  if (ldsq) HIP_TRY(set_max_dynamic_lds<&sparse_topk_filtered_kernel<true>>(160 * 1024));
+  auto run = [&](const u64* bound) -> int {
+    for (int q = 0; q < nq; ++q) {
+      if (ldsq)
+        hipLaunchKernelGGL((sparse_topk_filtered_kernel<true>), dim3(n_wg), dim3(1024), lds, st, ix->cols.p, ix->vals.p, ix->slice_off.p,
+                           ix->slice_len.p, ix->n_slices, (long long)ix->n_docs, ix->d_q.p, ix->vocab, nq, q, kk, ix->d_cand.p,
+                           ix->d_docid.p, ix->d_fallow.p, n_rows, bound);
+      else
+        hipLaunchKernelGGL((sparse_topk_filtered_kernel<false>), dim3(n_wg), dim3(1024), lds, st, ix->cols.p, ix->vals.p,
+                           ix->slice_off.p, ix->slice_len.p, ix->n_slices, (long long)ix->n_docs, ix->d_q.p, ix->vocab, nq, q, kk,
+                           ix->d_cand.p, ix->d_docid.p, ix->d_fallow.p, n_rows, bound);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(launch_topk_merge(ix->d_cand.p, n_wg, nq, kk, ix->d_out.p, st));
+    return VRAG_OK;
+  };
+  if (k > KMAX) return paged_search(nq, k, ix->d_bound, ix->d_out, st, run, scores, ids);
+  if ((rc = run(nullptr))) return rc;
   std::vector<u64> keys((size_t)nq * k);
   HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_out.p, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));

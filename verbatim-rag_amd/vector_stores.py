@@ -222,6 +222,15 @@ def convert_hits_to_results(hits: List[dict], dynamic_fields: Optional[List[str]
 
 
 # ---------------------------------------------------------------------------- device indexes
+def _allow_words(allow_words, n_allow: int) -> np.ndarray:
+    """The bitmap of a filtered search as contiguous uint32 words; ValueError when it is shorter than `n_allow` rows (the
+    library would read past it)."""
+    words = np.ascontiguousarray(allow_words, dtype=np.uint32).reshape(-1)
+    if n_allow < 0 or len(words) * 32 < n_allow:
+        raise ValueError(f"allow_words holds {len(words) * 32} bits, n_allow = {n_allow}")
+    return words
+
+
 class DenseShard:
     """One GPU's slice of the dense corpus (rows appended in order; ids are local row numbers)."""
 
@@ -255,6 +264,19 @@ class DenseShard:
         ids = np.empty((q.shape[0], k), np.int64)
         _lib.check("vrag_dense_index_search", self._lib.vrag_dense_index_search(
             self._h, q.ctypes.data_as(_FP), q.shape[0], k, scores.ctypes.data_as(_FP), ids.ctypes.data_as(_LP), stream))
+        return scores, ids
+
+    def search_filtered(self, queries: np.ndarray, k: int, allow_words: np.ndarray, n_allow: int,
+                        stream=None) -> Tuple[np.ndarray, np.ndarray]:
+        """`search` over the rows `r < min(n_allow, len(self))` whose bit is set in `allow_words` (uint32, bit `r % 32` of
+        word `r // 32`, as `_bitmap` packs them): exact chains over the passing rows only (`vrag_dense_index_search_filtered`)."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        words = _allow_words(allow_words, n_allow)
+        scores = np.empty((q.shape[0], k), np.float32)
+        ids = np.empty((q.shape[0], k), np.int64)
+        _lib.check("vrag_dense_index_search_filtered", self._lib.vrag_dense_index_search_filtered(
+            self._h, q.ctypes.data_as(_FP), q.shape[0], k, words.ctypes.data_as(C.c_void_p), int(n_allow),
+            scores.ctypes.data_as(_FP), ids.ctypes.data_as(_LP), stream))
         return scores, ids
 
     def search_device(self, queries: np.ndarray, k: int, out_scores: int, out_ids: int, row_map: Optional[int] = None,
@@ -338,6 +360,19 @@ class SparseShard:
 
     def search(self, queries: Sequence[Dict[int, float]], k: int, stream=None):
         return self.search_csr(*dicts_to_csr(queries), k, stream)
+
+    def search_filtered(self, queries: Sequence[Dict[int, float]], k: int, allow_words: np.ndarray, n_allow: int, stream=None):
+        """`search` over the documents `d < min(n_allow, n_docs)` whose bit is set in `allow_words` (see
+        `DenseShard.search_filtered`; `vrag_sparse_index_search_filtered`)."""
+        q_indptr, q_indices, q_values = dicts_to_csr(queries)
+        words = _allow_words(allow_words, n_allow)
+        nq = len(q_indptr) - 1
+        scores = np.empty((nq, k), np.float32)
+        ids = np.empty((nq, k), np.int64)
+        _lib.check("vrag_sparse_index_search_filtered", self._lib.vrag_sparse_index_search_filtered(
+            self._h, q_indptr.ctypes.data_as(_LP), q_indices.ctypes.data_as(_IP), q_values.ctypes.data_as(_FP), nq, k,
+            words.ctypes.data_as(C.c_void_p), int(n_allow), scores.ctypes.data_as(_FP), ids.ctypes.data_as(_LP), stream))
+        return scores, ids
 
     def search_device(self, queries: Sequence[Dict[int, float]], k: int, out_scores: int, out_ids: int,
                       row_map: Optional[int] = None, n_map: int = 0, id_base: int = 0, stream=None) -> None:
@@ -893,7 +928,8 @@ class GpuVectorStore(VectorStore):
     def __init__(self, dense_dim: Optional[int] = 384, sparse_vocab: Optional[int] = 30522, enable_dense: bool = True,
                  enable_sparse: bool = True, dense_dtype: str = "f32", device: int = 0, distributed: bool = False,
                  group=None, comm=None, payload: str = "sharded", dense_headroom: float = 1.5,
-                 dense_prefilter="auto", enable_full_text: bool = False, bm25_k1: float = 1.2, bm25_b: float = 0.75):
+                 dense_prefilter="auto", enable_full_text: bool = False, bm25_k1: float = 1.2, bm25_b: float = 0.75,
+                 filter_route: str = "subset"):
         """`enable_full_text`: BM25 keyword search over the raw texts (milvus_cloud.py: bm25_k1 = 1.2, bm25_b = 0.75),
         `search_type="full_text"` and the third leg of a weighted hybrid search; the texts are tokenised, indexed and
         scored on the device (`TextIndex`).  Off by default.  On a sharded store (`distributed=True` or a `comm`) the
@@ -902,13 +938,20 @@ class GpuVectorStore(VectorStore):
         `dense_prefilter` (fp32 rows only): keep a bf16 image of the rows beside them so that every search streams
         half (small batches) or a fraction (large ones) of the bytes of the full fp32 scan and returns the same bits (`DenseShard`).  It costs
         +50 % of the dense rows' HBM.  "auto" (default) = on where the image route exists (dim % 64 == 0 and <= 768,
-        csrc/topk.hip `prefilter_route_ok`), True / False force it; the choice is kept in a saved store's manifest."""
+        csrc/topk.hip `prefilter_route_ok`), True / False force it; the choice is kept in a saved store's manifest.
+        `filter_route`: how the dense and the sparse leg answer a query whose filter (or a delete) leaves them short --
+        "subset" (default) builds and caches a second shard of just the passing rows from the host copies; "bitmap" runs
+        the filtered search of the RESIDENT shard over a row bitmap (`DenseShard.search_filtered`; no second shard is ever
+        built, and a delete costs the next query nothing but the bitmap).  Same results either way.  A store whose exchange
+        runs on the GPU (`comm.on_gpu`) keeps "subset".  A run-time choice: not written by `save`, a keyword of `load`."""
         self._lib = _lib.load()
         _lib.require_gpu()
         if dense_dtype not in ("f32", "bf16"):
             raise ValueError(f"dense_dtype must be 'f32' or 'bf16' (got {dense_dtype!r})")
         if payload not in ("sharded", "replicated"):
             raise ValueError(f"payload must be 'sharded' or 'replicated' (got {payload!r})")
+        if filter_route not in ("subset", "bitmap"):
+            raise ValueError(f"filter_route must be 'subset' or 'bitmap' (got {filter_route!r})")
         if not enable_dense and not enable_sparse and not enable_full_text:      # milvus_base.py:54-56
             raise ValueError("At least one of enable_dense, enable_sparse, or enable_full_text must be True")
         if enable_full_text and comm is None and distributed:
@@ -935,6 +978,13 @@ class GpuVectorStore(VectorStore):
 
             self._comm = ShardComm(group, device)
             self._owns_comm = True
+        self.filter_route = filter_route
+        # the route searches take: the filtered search returns host lists, which the device-resident exchange does not carry.
+        # Replicated configuration only, so every rank decides alike.
+        self._filter_route = filter_route
+        if filter_route == "bitmap" and self._comm is not None and getattr(self._comm, "on_gpu", False):
+            self._filter_route = "subset"
+            logger.info("GpuVectorStore: filter_route='bitmap' needs host result lists; the exchange runs on the GPU, keeping 'subset'")
         self._rank = self._comm.rank if self._comm is not None else 0
         self._world = self._comm.world if self._comm is not None else 1
         self._payload_sharded = self._world > 1 and payload == "sharded"
@@ -1360,6 +1410,36 @@ class GpuVectorStore(VectorStore):
                 hit = self._subsets[key] = ([(shard, 0)] if shard is not None else [], rows, dev)
             return hit
 
+    def _filtered_topk(self, kind: str, parts, queries: Sequence[Any], k: int, mask: np.ndarray):
+        """`_device_topk` among the rows that pass `mask` (global rows), on the RESIDENT segments (`filter_route="bitmap"`):
+        per segment the mask is taken at the segment's rows and packed again from its first local row (segments start at
+        arbitrary rows, so this is no word offset); rows beyond the mask do not pass.  The segments' `[Q, k]` lists are
+        merged like the unfiltered ones and, on a sharded store, meet in the host exchange."""
+        Q = len(queries)
+        comm = self._comm
+        q_in = self._unit_queries(queries) if kind == "dense" and parts else queries
+        mapping = self._main_rows
+        found_lists = []
+        for shard, base in parts:
+            seg_rows = mapping[base:base + (len(shard) if kind == "dense" else shard.n_docs)]
+            known = seg_rows < len(mask)
+            allow = known & mask[np.where(known, seg_rows, 0)]
+            sc, local = shard.search_filtered(q_in, k, _bitmap(allow), len(allow))
+            at = local + base
+            found = (local >= 0) & (at < len(mapping))
+            g = np.where(found, mapping[np.where(found, at, 0)], -1) if len(mapping) else np.full_like(local, -1)
+            found_lists.append((sc, g))
+        if not found_lists:
+            scores, rows = np.full((Q, k), -np.inf, np.float32), np.full((Q, k), -1, np.int64)
+        elif len(found_lists) == 1:
+            scores, rows = found_lists[0]
+        else:
+            scores, rows = _merge_parts(np.stack([np.where(g >= 0, sc, -np.inf).astype(np.float32) for sc, g in found_lists]),
+                                        np.stack([g for _sc, g in found_lists]), k, self.device)
+        if comm is not None and self._world > 1:
+            scores, rows = comm.allgather_merge(scores, rows, k)
+        return scores, rows
+
     def _drop_subsets(self):
         with self._mu:
             self._subsets.clear()
@@ -1370,7 +1450,8 @@ class GpuVectorStore(VectorStore):
         """Best `limit` rows per query among the rows that pass `mask`: `rows [Q, limit]` (-1 = no hit, tail only) and
         their fp32 scores.  One device pass for the whole batch over the full shard; queries that come up short because
         filtered / deleted rows took their slots (and every query when the filter passes under 1/8 of the rows) get a
-        second pass over the masked subset shard.  Every branch below depends only on replicated state and on merged
+        second pass over the masked subset shard -- or, with `filter_route="bitmap"`, the filtered search of the resident
+        shard (`_filtered_topk`; no subset shard is built in that mode).  Every branch below depends only on replicated state and on merged
         results, so the ranks of a sharded store take the same path and meet in the same collectives."""
         if limit > self.K_LIMIT:
             raise ValueError(f"GpuVectorStore: a search may ask for at most {self.K_LIMIT} rows per method "
@@ -1406,9 +1487,12 @@ class GpuVectorStore(VectorStore):
             score_out[done, :k] = np.where(rows_c[done] >= 0, scores_c[done], np.float32(0.0))
             short = ~done
         if short.any():
-            sub_parts, shard_rows, sub_dev = self._subset(kind, mask)
             which = np.nonzero(short)[0]
-            scores, rows = self._device_topk(kind, sub_parts, shard_rows, [queries[i] for i in which], want, sub_dev)
+            if self._filter_route == "bitmap":
+                scores, rows = self._filtered_topk(kind, parts, [queries[i] for i in which], want, mask)
+            else:
+                sub_parts, shard_rows, sub_dev = self._subset(kind, mask)
+                scores, rows = self._device_topk(kind, sub_parts, shard_rows, [queries[i] for i in which], want, sub_dev)
             rows = np.where((rows >= 0) & (rows < n), rows, -1)
             rows_out[which, :want] = rows
             score_out[which, :want] = np.where(rows >= 0, scores, np.float32(0.0))
@@ -1791,16 +1875,16 @@ class GpuVectorStore(VectorStore):
 
     @classmethod
     def load(cls, path: str, device: int = 0, distributed: bool = False, group=None, comm=None,
-             payload: str = "sharded") -> "GpuVectorStore":
+             payload: str = "sharded", filter_route: str = "subset") -> "GpuVectorStore":
         """Reads a directory written by `save` -- by this or an earlier revision (formats 1 - 3), by any number of
         ranks: when the world size differs from the writer's, the saved shards are put back in row order and cut
-        contiguously over the ranks that open the store."""
+        contiguously over the ranks that open the store.  `filter_route`: as the constructor's (not part of a saved store)."""
         head, ids, shards = cls._read_saved(path)
         st = cls(dense_dim=head["dense_dim"], sparse_vocab=head["sparse_vocab"], enable_dense=head["enable_dense"],
                  enable_sparse=head["enable_sparse"], dense_dtype=head["dense_dtype"], device=device,
                  distributed=distributed, group=group, comm=comm, payload=payload,
                  dense_prefilter=head.get("dense_prefilter", "auto"), enable_full_text=bool(head.get("enable_full_text", False)),
-                 bm25_k1=head.get("bm25_k1", 1.2), bm25_b=head.get("bm25_b", 0.75))
+                 bm25_k1=head.get("bm25_k1", 1.2), bm25_b=head.get("bm25_b", 0.75), filter_route=filter_route)
         n = len(ids)
         for owned, *_ in shards:
             if len(owned) and (owned.min() < 0 or owned.max() >= n):
