@@ -2,7 +2,8 @@
  * these entry points exist only in libvrag_amd_dbg.so, the harness build of the same sources (verbatim-rag_amd/build.py,
  * -DVRAG_DEBUG_API: it also keeps the phase-decomposition branches of the fused kernel that the product build compiles out).
  * tools/, tests/test_attention_unit_gpu.py, tests/test_attn_unit_gpu.py, tests/test_gemm_unit_gpu.py,
- * tests/test_qkv_attn_unit_gpu.py and tests/test_rows_unit_gpu.py load it beside the product library. */
+ * tests/test_qkv_attn_unit_gpu.py, tests/test_rows_unit_gpu.py and tests/test_glue_unit_gpu.py load it beside the product
+ * library. */
 #ifndef VRAG_AMD_DEBUG_H
 #define VRAG_AMD_DEBUG_H
 
@@ -202,6 +203,78 @@ typedef struct vrag_debug_rows_args {
   int32_t f16_saturated;     /* out: the clamp word, zeroed before the launch and read back after it */
 } vrag_debug_rows_args;
 int vrag_debug_rows_run(vrag_debug_rows_args* args, int32_t device);
+
+/* Unit-test hook of the encoder's packing and glue kernels alone (csrc/glue_kernels.h: the launchers of csrc/capi.hip, and
+ * permute_qkv_heads of csrc/qkv_attn.hip), one launcher per call, chosen by `op`.  Host buffers in, exactly the launcher's
+ * launches (one), buffers marked "in / out" copied to the device before the launch and back after it, so a canary survives where
+ * the kernel must not write.  fp16 launches (f16 != 0) return the clamp word, zeroed before the launch and read after it.
+ * Refused by the hook before anything is launched, each with its own message: a null required pointer; rows_dst, rows_src, cols,
+ * V, rows or out_rows <= 0; interleave with I <= 0; out_rows below the rows the launch covers; ld < V rounded up to 4 or
+ * ld % 4 != 0; cap < 1; n_seqs < 1, seq_row negative or not ascending, seq_len < 0, a sequence running past `rows`, seq_src
+ * negative or seq_src + seq_len beyond the n_packed ids; nh < 1 or H != 64 * nh; np * 64 != H; row0 < 0 or ld < row0 + rows.
+ * Nothing the hook accepts reads or writes outside its buffers.  Index ranges per op:
+ *   CVT_ROWS      one workgroup per row r < rows_dst (the grid).  Reads src row s < rows_src, columns c < cols (without the
+ *                 interleave s = r, else s = f or I + f with f < I checked by the kernel, and s < rows_src by its guard);
+ *                 col_scale[c]; writes dst / dst_lo [r, c] and row_sum[r]: rows below rows_dst <= out_rows.
+ *   CVT_SPLIT3    the same rows; writes dst [r, 0 .. 3 cols): the image has leading dimension 3 cols and is sized so.
+ *   LN_STATS_FINALIZE  lane r < rows reads part[(i * ld + row0 + r) * 2 + {0, 1}], i < np: below np * ld * 2 because
+ *                 row0 + rows <= ld; reads shift_in and writes mu, rstd, shift_out, shift_prev at row0 + r < ld.
+ *   PACK_LAYOUT   lane r < rows reads seq_row / seq_src / seq_len[lo], lo < n_seqs (the bisection keeps 0 <= lo < hi <= n_seqs),
+ *                 packed[seq_src[lo] + i] with 0 <= i < seq_len[lo]: below n_packed, checked; writes ids, pos, tok_seq[r],
+ *                 r < rows <= out_rows.
+ *   SPLADE_COMPACT  workgroup s < rows reads src[s * ld + v .. v + 3] with v % 4 == 0 and v < V: below s * ld + align4(V) <=
+ *                 (s + 1) * ld; writes counts[s] and idx / val[s * cap + off] only where off < cap.
+ *   PERMUTE_QKV_HEADS  workgroup orow < 3 H reads w row (orow % 192 / 64) * H + orow / 192 * 64 + orow % 64 < 3 H, columns < H,
+ *                 and s at the same index; writes w_out row orow and s_out[orow]: out_rows >= 3 H is checked.
+ * Every device buffer, inputs included, is followed by 4 KiB of canary; the hook fails with VRAG_ERR_HIP if a launch touched any. */
+enum {
+  VRAG_DEBUG_GLUE_CVT_ROWS = 0,
+  VRAG_DEBUG_GLUE_CVT_SPLIT3 = 1,
+  VRAG_DEBUG_GLUE_LN_STATS_FINALIZE = 2,
+  VRAG_DEBUG_GLUE_PACK_LAYOUT = 3,
+  VRAG_DEBUG_GLUE_SPLADE_COMPACT = 4,
+  VRAG_DEBUG_GLUE_PERMUTE_QKV_HEADS = 5
+};
+typedef struct vrag_debug_glue_args {
+  const float* src;          /* cvt_rows / cvt_split3 [rows_src, cols]; splade_compact [rows, ld] */
+  const float* col_scale;    /* cvt_rows [cols], nullable */
+  uint16_t* dst;             /* in / out: cvt_rows [out_rows, cols]; cvt_split3 [out_rows, 3 cols] */
+  uint16_t* dst_lo;          /* in / out: cvt_rows [out_rows, cols], nullable */
+  float* row_sum;            /* in / out: cvt_rows [out_rows], nullable */
+  const float* part;         /* ln_stats_finalize [np, ld, 2] */
+  float* mu;                 /* in / out: ln_stats_finalize [ld] */
+  float* rstd;               /* in / out: ln_stats_finalize [ld] */
+  const float* shift_in;     /* ln_stats_finalize [ld], nullable (must be null with alias_shift) */
+  float* shift_out;          /* in / out: ln_stats_finalize [ld]; with alias_shift also the kernel's shift_in */
+  float* shift_prev;         /* in / out: ln_stats_finalize [ld], nullable */
+  const int32_t* packed;     /* pack_layout [n_packed] ids back to back */
+  const int32_t* seq_row;    /* pack_layout [n_seqs] first row, ascending */
+  const int32_t* seq_src;    /* pack_layout [n_seqs] first id in packed */
+  const int32_t* seq_len;    /* pack_layout [n_seqs] */
+  int32_t* ids;              /* in / out: pack_layout [out_rows] */
+  int32_t* pos;              /* in / out: pack_layout [out_rows] */
+  int32_t* tok_seq;          /* in / out: pack_layout [out_rows] */
+  int32_t* counts;           /* in / out: splade_compact [out_rows] */
+  int32_t* idx;              /* in / out: splade_compact [out_rows, cap] */
+  float* val;                /* in / out: splade_compact [out_rows, cap] */
+  const uint16_t* w;         /* permute_qkv_heads [3 H, H] */
+  const float* s;            /* permute_qkv_heads [3 H], nullable */
+  uint16_t* w_out;           /* in / out: permute_qkv_heads [out_rows, H] */
+  float* s_out;              /* in / out: permute_qkv_heads [out_rows], nullable */
+  int32_t op, f16;
+  int32_t rows_dst, rows_src, cols;   /* cvt_rows / cvt_split3 */
+  int32_t interleave, I;     /* cvt_rows: interleave != 0 = the GeGLU interleave of I features (the launcher gets I, else 0) */
+  int32_t out_rows;          /* rows every in / out buffer holds, ln_stats_finalize excepted: >= rows_dst, rows or 3 H */
+  int32_t rows;              /* ln_stats_finalize, pack_layout, splade_compact: the launcher's rows / fill_to / n */
+  int32_t ld, row0, H, np;   /* ln_stats_finalize: rows of the whole buffer; the launch covers [row0, row0 + rows) through offset pointers (partials + row0 * 2, the rest + row0); splade_compact: ld; permute_qkv_heads: H */
+  int32_t nh;                /* permute_qkv_heads */
+  int32_t alias_shift;       /* ln_stats_finalize: shift_in = shift_out, one device buffer, as the encoder passes them */
+  int32_t n_seqs, n_packed, pad_id;   /* pack_layout */
+  int32_t V, cap;            /* splade_compact */
+  float thr, eps;            /* splade_compact; ln_stats_finalize */
+  int32_t f16_saturated;     /* out: the clamp word of an fp16 cvt launch */
+} vrag_debug_glue_args;
+int vrag_debug_glue_run(vrag_debug_glue_args* args, int32_t device);
 
 #ifdef __cplusplus
 }

@@ -178,6 +178,7 @@ DEBUG_SIGNATURES = {
     "vrag_debug_qkv_attn_run": (C.c_int, [C.c_void_p, C.c_int32]),
     "vrag_debug_pack_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "vrag_debug_rows_run": (C.c_int, [C.c_void_p, C.c_int32]),
+    "vrag_debug_glue_run": (C.c_int, [C.c_void_p, C.c_int32]),
 }
 
 
@@ -217,6 +218,20 @@ class DebugRowsArgs(C.Structure):
 
 
 DEBUG_ROWS_OPS = {"embed_ln": 0, "layernorm": 1, "range_pool": 2, "ln_classifier": 3, "pooler_classifier": 4, "seq_head": 5}
+
+
+class DebugGlueArgs(C.Structure):
+    """vrag_debug_glue_args (include/vrag_amd_debug.h), field for field; tests/test_capi_abi.py checks the layout too."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "src", "col_scale", "dst", "dst_lo", "row_sum", "part", "mu", "rstd", "shift_in", "shift_out", "shift_prev", "packed",
+        "seq_row", "seq_src", "seq_len", "ids", "pos", "tok_seq", "counts", "idx", "val", "w", "s", "w_out", "s_out")] + [
+        (n, C.c_int32) for n in ("op", "f16", "rows_dst", "rows_src", "cols", "interleave", "I", "out_rows", "rows", "ld", "row0",
+                                 "H", "np", "nh", "alias_shift", "n_seqs", "n_packed", "pad_id", "V", "cap")] + [
+        ("thr", C.c_float), ("eps", C.c_float), ("f16_saturated", C.c_int32)]
+
+
+DEBUG_GLUE_OPS = {"cvt_rows": 0, "cvt_split3": 1, "ln_stats_finalize": 2, "pack_layout": 3, "splade_compact": 4,
+                  "permute_qkv_heads": 5}
 
 _DBG = None
 

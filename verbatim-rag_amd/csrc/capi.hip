@@ -19,6 +19,7 @@
 #include <memory>
 #include "common.h"
 #include "gemm_bf16.h"
+#include "glue_kernels.h"
 #include "host_util.h"
 #include "norm_heads.h"
 
@@ -77,8 +78,8 @@ __global__ void cvt_rows_bf16_kernel(const float* __restrict__ src, bf16_t* __re
   }
 }
 
-static void launch_cvt_rows(int op_dtype, dim3 grid, hipStream_t st, const float* src, bf16_t* dst, int rows_dst, int rows_src,
-                            int cols, int interleave_I, const float* col_scale, float* row_sum, bf16_t* dst_lo, unsigned* f16_sat) {
+void launch_cvt_rows(int op_dtype, dim3 grid, hipStream_t st, const float* src, bf16_t* dst, int rows_dst, int rows_src, int cols,
+                     int interleave_I, const float* col_scale, float* row_sum, bf16_t* dst_lo, unsigned* f16_sat) {
   if (op_dtype == kOpF16)
     hipLaunchKernelGGL(cvt_rows_bf16_kernel<f16_t>, grid, dim3(256), 0, st, src, dst, rows_dst, rows_src, cols, interleave_I,
                        col_scale, row_sum, dst_lo, f16_sat);
@@ -105,8 +106,8 @@ __global__ void cvt_split3_kernel(const float* __restrict__ src, bf16_t* __restr
     row[2 * cols + c] = Op<T>::to(v - (float)hi, f16_sat);
   }
 }
-static void launch_cvt_split3(int op_dtype, hipStream_t st, const float* src, bf16_t* dst, int rows_dst, int rows_src, int cols,
-                              unsigned* f16_sat) {
+void launch_cvt_split3(int op_dtype, hipStream_t st, const float* src, bf16_t* dst, int rows_dst, int rows_src, int cols,
+                       unsigned* f16_sat) {
   if (op_dtype == kOpF16)
     hipLaunchKernelGGL(cvt_split3_kernel<f16_t>, dim3(rows_dst), dim3(256), 0, st, src, dst, rows_dst, rows_src, cols, f16_sat);
   else hipLaunchKernelGGL(cvt_split3_kernel<bf16_t>, dim3(rows_dst), dim3(256), 0, st, src, dst, rows_dst, rows_src, cols, f16_sat);
@@ -134,6 +135,11 @@ __global__ void ln_stats_finalize_kernel(const float* __restrict__ part, int ld,
   if (shift_prev_out) shift_prev_out[r] = c;   // what the split residual planes written before this call are relative to
   shift_out[r] = c + d;
 }
+void launch_ln_stats_finalize(hipStream_t st, const float* part, int ld, int np, int H, float eps, int rows, float* mu_rel, float* rstd,
+                              const float* shift_in, float* shift_out, float* shift_prev_out) {
+  hipLaunchKernelGGL(ln_stats_finalize_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, part, ld, np, H, eps, rows, mu_rel, rstd,
+                     shift_in, shift_out, shift_prev_out);
+}
 
 // Packing metadata on the device: the host hands over the batch as it received it -- ids back to back plus
 // (first row, first id, length) per sequence -- and this kernel lays the padding-free row image out: ids / position inside
@@ -155,6 +161,11 @@ __global__ void pack_layout_kernel(const int* __restrict__ packed, const int* __
   ids[r] = in ? packed[seq_src[lo] + i] : pad_id;
   pos[r] = in ? i : 0;
   tok_seq[r] = in ? lo : -1;
+}
+void launch_pack_layout(hipStream_t st, const int* packed, const int* seq_row, const int* seq_src, const int* seq_len, int n_seqs,
+                        int rows, int pad_id, int* ids, int* pos, int* tok_seq) {
+  hipLaunchKernelGGL(pack_layout_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, packed, seq_row, seq_src, seq_len, n_seqs, rows,
+                     pad_id, ids, pos, tok_seq);
 }
 
 // One workgroup per sequence: stable compaction of a SPLADE row (weights are >= 0) into (index, value) pairs.
@@ -199,6 +210,10 @@ __global__ __launch_bounds__(256) void splade_compact_kernel(const float* __rest
       }
   }
   if (tid == 255) counts[s] = off;   // the last thread's end offset = the row's total (its range may be empty: off = everything before it)
+}
+void launch_splade_compact(hipStream_t st, const float* rows, int n_rows, int V, int ld, float thr, int cap, int* counts, int* idx,
+                           float* val) {
+  hipLaunchKernelGGL(splade_compact_kernel, dim3(n_rows), dim3(256), 0, st, rows, V, ld, thr, cap, counts, idx, val);
 }
 
 struct Layer {
@@ -598,9 +613,9 @@ int run_layers_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
       auto finalize_stats = [&](bool first, bool for_qkv = false) -> int {
         if (consumer_stats && !(for_qkv && fused_attn)) return VRAG_OK;
         ProfScope ps(e, VRAG_PROF_LAYERNORM, st);
-        hipLaunchKernelGGL(ln_stats_finalize_kernel, dim3((M + 255) / 256), dim3(256), 0, st,
-                           e->st_part.p + (size_t)r0 * 2, e->cap_rows, H / 64, H, c.norm_eps, M, e->ln_mu.p + r0,
-                           e->ln_rstd.p + r0, first ? (const float*)nullptr : e->ln_shift.p + r0, e->ln_shift.p + r0, e->ln_shift_prev.p + r0);
+        launch_ln_stats_finalize(st, e->st_part.p + (size_t)r0 * 2, e->cap_rows, H / 64, H, c.norm_eps, M, e->ln_mu.p + r0,
+                                 e->ln_rstd.p + r0, first ? (const float*)nullptr : e->ln_shift.p + r0, e->ln_shift.p + r0,
+                                 e->ln_shift_prev.p + r0);
         HIP_TRY(hipGetLastError());
         return VRAG_OK;
       };
@@ -819,8 +834,8 @@ int run_layers_bert_locked(vrag_encoder* e, int n_layers, hipStream_t user_st) {
     float* st_part = e->st_part.p + (size_t)r0 * 2;
     auto finalize_stats = [&](bool first) -> int {
       ProfScope ps(e, VRAG_PROF_LAYERNORM, st);
-      hipLaunchKernelGGL(ln_stats_finalize_kernel, dim3((M + 255) / 256), dim3(256), 0, st, st_part, e->cap_rows, H / 64, H, c.norm_eps, M,
-                         e->ln_mu.p + r0, e->ln_rstd.p + r0, first ? (const float*)nullptr : e->ln_shift.p + r0, e->ln_shift.p + r0, (float*)nullptr);
+      launch_ln_stats_finalize(st, st_part, e->cap_rows, H / 64, H, c.norm_eps, M, e->ln_mu.p + r0, e->ln_rstd.p + r0,
+                               first ? (const float*)nullptr : e->ln_shift.p + r0, e->ln_shift.p + r0, (float*)nullptr);
       HIP_TRY(hipGetLastError());
       return VRAG_OK;
     };
@@ -1710,9 +1725,8 @@ int vrag_encoder_load_batch(vrag_encoder* e, const int32_t* ids, const int32_t* 
   if (n_groups > 0) HIP_TRY(hipMemcpyAsync(e->d_groups.p, e->h_groups.p, (size_t)n_groups * 8 * sizeof(int4), hipMemcpyHostToDevice, st));
   // one upload for the six descriptor arrays: from the first used entry of the first to the last used entry of the last
   HIP_TRY(hipMemcpyAsync(e->d_blk_start.p, e->h_blk_start.p, ((size_t)5 * e->cap_blocks + nlblk) * sizeof(int), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(pack_layout_kernel, dim3((fill_to + 255) / 256), dim3(256), 0, st, e->d_packed.p, e->d_seq_meta.p,
-                     e->d_seq_meta.p + c.max_seqs, e->d_seq_meta.p + 2 * c.max_seqs, n_seqs, fill_to, c.pad_token_id, e->d_ids.p, e->d_pos.p,
-                     e->d_tokseq.p);
+  launch_pack_layout(st, e->d_packed.p, e->d_seq_meta.p, e->d_seq_meta.p + c.max_seqs, e->d_seq_meta.p + 2 * c.max_seqs, n_seqs, fill_to,
+                     c.pad_token_id, e->d_ids.p, e->d_pos.p, e->d_tokseq.p);
   HIP_TRY(hipGetLastError());
   return VRAG_OK;
 }
@@ -2048,8 +2062,8 @@ int vrag_encoder_read_splade_sparse(vrag_encoder* e, float threshold, int32_t ca
     e->sp_cap = cap_per_seq;
   }
   const int n = e->n_seqs, cap = cap_per_seq;
-  hipLaunchKernelGGL(splade_compact_kernel, dim3(n), dim3(256), 0, st, reinterpret_cast<const float*>(e->d_splade.p),
-                     e->cfg.vocab_size, e->vpad, threshold, cap, e->d_sp_cnt.p, e->d_sp_idx.p, e->d_sp_val.p);
+  launch_splade_compact(st, reinterpret_cast<const float*>(e->d_splade.p), n, e->cfg.vocab_size, e->vpad, threshold, cap, e->d_sp_cnt.p,
+                        e->d_sp_idx.p, e->d_sp_val.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(counts, e->d_sp_cnt.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));

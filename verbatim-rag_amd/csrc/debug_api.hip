@@ -1,5 +1,5 @@
 // Tuning / unit-test harness of the kernels (include/vrag_amd_debug.h): synthetic-operand timing loops and the attention
-// kernels', the GEMM's and the row kernels' unit-test hooks.  NOT part of the product library: compiled only into libvrag_amd_dbg.so (build.py, -DVRAG_DEBUG_API),
+// kernels', the GEMM's, the row kernels' and the packing / glue kernels' unit-test hooks.  NOT part of the product library: compiled only into libvrag_amd_dbg.so (build.py, -DVRAG_DEBUG_API),
 // which tools/ and the attention unit test load beside libvrag_amd.so.
 #include "../../include/vrag_amd.h"
 #include "../../include/vrag_amd_debug.h"
@@ -11,6 +11,7 @@
 
 #include "attention.h"
 #include "gemm_bf16.h"
+#include "glue_kernels.h"
 #include "host_util.h"
 #include "norm_heads.h"
 #include "qkv_attn.h"
@@ -887,6 +888,198 @@ int vrag_debug_rows_run(vrag_debug_rows_args* a, int32_t device) {
   if (le != hipSuccess) {
     set_error("debug rows run: the launcher returned %s", hipGetErrorString(le));
     return le == hipErrorInvalidValue ? VRAG_ERR_INVALID : VRAG_ERR_HIP;
+  }
+  return VRAG_OK;
+}
+
+int vrag_debug_glue_run(vrag_debug_glue_args* a, int32_t device) {
+  ARG_CHECK(a, "null arguments");
+  const int op = a->op;
+  ARG_CHECK(op >= VRAG_DEBUG_GLUE_CVT_ROWS && op <= VRAG_DEBUG_GLUE_PERMUTE_QKV_HEADS, "op %d is not a glue launcher", op);
+  ARG_CHECK(device >= 0, "bad device %d", device);
+  const bool cvt = op == VRAG_DEBUG_GLUE_CVT_ROWS, split3 = op == VRAG_DEBUG_GLUE_CVT_SPLIT3;
+  const bool fin = op == VRAG_DEBUG_GLUE_LN_STATS_FINALIZE, pack = op == VRAG_DEBUG_GLUE_PACK_LAYOUT;
+  const bool compact = op == VRAG_DEBUG_GLUE_SPLADE_COMPACT, permute = op == VRAG_DEBUG_GLUE_PERMUTE_QKV_HEADS;
+  constexpr int kMax = 1 << 20;            // every extent, and
+  constexpr int64_t kMaxElems = 1 << 28;   // every buffer's element count: the sizes below stay far inside size_t and int
+  if (cvt || split3) {
+    ARG_CHECK(a->src && a->dst, "%s needs src and dst", cvt ? "cvt_rows" : "cvt_split3");
+    ARG_CHECK(a->rows_src > 0 && a->rows_src <= kMax, "rows_src (%d) must be in 1..%d", a->rows_src, kMax);
+    ARG_CHECK(a->cols > 0 && a->cols <= kMax, "cols (%d) must be in 1..%d", a->cols, kMax);
+    ARG_CHECK(a->rows_dst > 0 && a->rows_dst <= kMax, "rows_dst (%d) must be in 1..%d", a->rows_dst, kMax);
+    ARG_CHECK(a->out_rows >= a->rows_dst && a->out_rows <= kMax, "out_rows (%d) below rows_dst (%d)", a->out_rows, a->rows_dst);
+    ARG_CHECK((int64_t)a->rows_src * a->cols <= kMaxElems && (int64_t)a->out_rows * a->cols * 3 <= kMaxElems, "the matrices are too large for the hook");
+    if (cvt && a->interleave) ARG_CHECK(a->I > 0, "interleave: I (%d) must be positive", a->I);
+  }
+  if (fin) {
+    ARG_CHECK(a->part && a->mu && a->rstd && a->shift_out, "ln_stats_finalize needs part, mu, rstd and shift_out");
+    ARG_CHECK(!(a->alias_shift && a->shift_in), "alias_shift makes shift_out the kernel's shift_in: shift_in must be null");
+    ARG_CHECK(a->rows > 0 && a->rows <= kMax, "rows (%d) must be in 1..%d", a->rows, kMax);
+    ARG_CHECK(a->np > 0 && a->H > 0 && (int64_t)a->np * 64 == a->H, "np (%d) * 64 must be H (%d)", a->np, a->H);
+    ARG_CHECK(a->row0 >= 0 && a->ld <= kMax && (int64_t)a->ld >= (int64_t)a->row0 + a->rows,
+              "ld (%d) below row0 + rows (%d + %d)", a->ld, a->row0, a->rows);
+    ARG_CHECK((int64_t)a->np * a->ld * 2 <= kMaxElems, "the partials are too large for the hook");
+  }
+  if (pack) {
+    ARG_CHECK(a->packed && a->seq_row && a->seq_src && a->seq_len && a->ids && a->pos && a->tok_seq,
+              "pack_layout needs packed, seq_row, seq_src, seq_len, ids, pos and tok_seq");
+    ARG_CHECK(a->n_seqs >= 1 && a->n_seqs <= kMax, "n_seqs (%d) must be in 1..%d", a->n_seqs, kMax);
+    ARG_CHECK(a->rows > 0 && a->rows <= kMax, "rows (%d) must be in 1..%d", a->rows, kMax);
+    ARG_CHECK(a->out_rows >= a->rows && a->out_rows <= kMax, "out_rows (%d) below rows (%d)", a->out_rows, a->rows);
+    ARG_CHECK(a->n_packed >= 1 && a->n_packed <= (1 << 26), "n_packed (%d) must be in 1..2^26", a->n_packed);
+    for (int i = 0; i < a->n_seqs; ++i) {
+      ARG_CHECK(a->seq_row[i] >= 0, "seq_row[%d] = %d is negative", i, a->seq_row[i]);
+      ARG_CHECK(i == 0 || a->seq_row[i] > a->seq_row[i - 1], "seq_row is not ascending at %d (%d after %d)", i, a->seq_row[i], a->seq_row[i - 1]);
+      ARG_CHECK(a->seq_len[i] >= 0, "seq_len[%d] = %d is negative", i, a->seq_len[i]);
+      ARG_CHECK((int64_t)a->seq_row[i] + a->seq_len[i] <= a->rows, "sequence %d (row %d, %d tokens) runs past rows (%d)", i, a->seq_row[i], a->seq_len[i], a->rows);
+      ARG_CHECK(a->seq_src[i] >= 0 && (int64_t)a->seq_src[i] + a->seq_len[i] <= a->n_packed,
+                "sequence %d: seq_src + seq_len (%d + %d) beyond the %d packed ids", i, a->seq_src[i], a->seq_len[i], a->n_packed);
+    }
+  }
+  if (compact) {
+    ARG_CHECK(a->src && a->counts && a->idx && a->val, "splade_compact needs src, counts, idx and val");
+    ARG_CHECK(a->V > 0 && a->V <= kMax, "V (%d) must be in 1..%d", a->V, kMax);
+    ARG_CHECK(a->ld % 4 == 0 && a->ld <= kMax && a->ld >= (int)align_up(a->V, 4), "ld (%d) must be a multiple of 4 and at least V (%d) rounded up to 4", a->ld, a->V);
+    ARG_CHECK(a->cap >= 1 && a->cap <= kMax, "cap (%d) must be in 1..%d", a->cap, kMax);
+    ARG_CHECK(a->rows > 0 && a->rows <= 4096, "rows (%d) must be in 1..4096", a->rows);
+    ARG_CHECK(a->out_rows >= a->rows && a->out_rows <= 4096, "out_rows (%d) below rows (%d)", a->out_rows, a->rows);
+    ARG_CHECK((int64_t)a->rows * a->ld <= kMaxElems && (int64_t)a->out_rows * a->cap <= kMaxElems, "the rows are too large for the hook");
+  }
+  if (permute) {
+    ARG_CHECK(a->w && a->w_out, "permute_qkv_heads needs w and w_out");
+    ARG_CHECK(!a->s == !a->s_out, "s and s_out come together");
+    ARG_CHECK(a->nh >= 1 && a->nh <= 64 && a->H == 64 * a->nh, "H (%d) must be 64 * nh (%d), nh in 1..64", a->H, a->nh);
+    ARG_CHECK(a->out_rows >= 3 * a->H && a->out_rows <= kMax, "out_rows (%d) below 3 H (%d)", a->out_rows, 3 * a->H);
+  }
+  if (vrag_device_count() <= device) {
+    set_error("no HIP device %d visible", device);
+    return VRAG_ERR_NO_DEVICE;
+  }
+  HIP_TRY(hipSetDevice(device));
+
+  // device copies: every buffer is followed by a 4 KiB canary that the launch must leave as it was
+  constexpr size_t kCanary = 4096;
+  constexpr unsigned char kCanaryByte = 0xA5;
+  struct Buf {
+    const void* host;
+    void* host_out;   // null = input only
+    size_t bytes;
+    const char* name;
+    DevBuf dev;   // bytes + kCanary
+  };
+  std::vector<Buf> bufs;
+  auto add = [&](const void* h, void* h_out, size_t bytes, const char* name) -> int {
+    if (!h) return -1;
+    bufs.push_back(Buf{h, h_out, bytes, name, DevBuf()});
+    return (int)bufs.size() - 1;
+  };
+  const size_t OR = (size_t)a->out_rows, cols = (size_t)a->cols, ld = (size_t)a->ld, Hs = (size_t)a->H;
+  int isrc = -1, iscale = -1, idst = -1, ilo = -1, isum = -1, ipart = -1, imu = -1, irstd = -1, ishin = -1, ishout = -1, iprev = -1;
+  int ipacked = -1, isrow = -1, issrc = -1, islen = -1, iids = -1, ipos = -1, itok = -1, icnt = -1, iidx = -1, ival = -1;
+  int iw = -1, is = -1, iwo = -1, iso = -1;
+  if (cvt || split3) {
+    isrc = add(a->src, nullptr, (size_t)a->rows_src * cols * 4, "src");
+    idst = add(a->dst, a->dst, OR * (split3 ? 3 * cols : cols) * 2, "dst");
+  }
+  if (cvt) {
+    iscale = add(a->col_scale, nullptr, cols * 4, "col_scale");
+    ilo = add(a->dst_lo, a->dst_lo, OR * cols * 2, "dst_lo");
+    isum = add(a->row_sum, a->row_sum, OR * 4, "row_sum");
+  }
+  if (fin) {
+    ipart = add(a->part, nullptr, (size_t)a->np * ld * 2 * 4, "part");
+    imu = add(a->mu, a->mu, ld * 4, "mu");
+    irstd = add(a->rstd, a->rstd, ld * 4, "rstd");
+    ishin = add(a->shift_in, nullptr, ld * 4, "shift_in");
+    ishout = add(a->shift_out, a->shift_out, ld * 4, "shift_out");
+    iprev = add(a->shift_prev, a->shift_prev, ld * 4, "shift_prev");
+  }
+  if (pack) {
+    const size_t n = (size_t)a->n_seqs;
+    ipacked = add(a->packed, nullptr, (size_t)a->n_packed * 4, "packed");
+    isrow = add(a->seq_row, nullptr, n * 4, "seq_row");
+    issrc = add(a->seq_src, nullptr, n * 4, "seq_src");
+    islen = add(a->seq_len, nullptr, n * 4, "seq_len");
+    iids = add(a->ids, a->ids, OR * 4, "ids");
+    ipos = add(a->pos, a->pos, OR * 4, "pos");
+    itok = add(a->tok_seq, a->tok_seq, OR * 4, "tok_seq");
+  }
+  if (compact) {
+    isrc = add(a->src, nullptr, (size_t)a->rows * ld * 4, "src");
+    icnt = add(a->counts, a->counts, OR * 4, "counts");
+    iidx = add(a->idx, a->idx, OR * (size_t)a->cap * 4, "idx");
+    ival = add(a->val, a->val, OR * (size_t)a->cap * 4, "val");
+  }
+  if (permute) {
+    iw = add(a->w, nullptr, 3 * Hs * Hs * 2, "w");
+    is = add(a->s, nullptr, 3 * Hs * 4, "s");
+    iwo = add(a->w_out, a->w_out, OR * Hs * 2, "w_out");
+    iso = add(a->s_out, a->s_out, OR * 4, "s_out");
+  }
+  DevBuf sat;   // the launch's fp16 clamp word, reported in f16_saturated
+  hipError_t e = sat.alloc(4);
+  if (e == hipSuccess) e = hipMemset(sat.p, 0, 4);
+  for (Buf& b : bufs) {
+    if (e == hipSuccess) e = b.dev.alloc(b.bytes + kCanary);
+    if (e == hipSuccess && b.bytes) e = hipMemcpy(b.dev.p, b.host, b.bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(b.dev.as<char>() + b.bytes, kCanaryByte, kCanary);
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    set_error("debug glue run: staging failed: %s", hipGetErrorString(e));
+    return VRAG_ERR_HIP;
+  }
+  auto fp = [&](int i) -> float* { return i < 0 ? nullptr : bufs[i].dev.as<float>(); };
+  auto ip = [&](int i) -> int* { return i < 0 ? nullptr : bufs[i].dev.as<int>(); };
+  auto hp = [&](int i) -> bf16_t* { return i < 0 ? nullptr : bufs[i].dev.as<bf16_t>(); };
+  const int dt = a->f16 ? kOpF16 : kOpBf16;
+  switch (op) {
+    case VRAG_DEBUG_GLUE_CVT_ROWS:
+      launch_cvt_rows(dt, dim3(a->rows_dst), 0, fp(isrc), hp(idst), a->rows_dst, a->rows_src, a->cols, a->interleave ? a->I : 0,
+                      fp(iscale), fp(isum), hp(ilo), sat.as<unsigned>());
+      break;
+    case VRAG_DEBUG_GLUE_CVT_SPLIT3:
+      launch_cvt_split3(dt, 0, fp(isrc), hp(idst), a->rows_dst, a->rows_src, a->cols, sat.as<unsigned>());
+      break;
+    case VRAG_DEBUG_GLUE_LN_STATS_FINALIZE: {
+      const int r0 = a->row0;   // as the encoder addresses a micro-batch
+      float* prev = fp(iprev);
+      launch_ln_stats_finalize(0, fp(ipart) + (size_t)r0 * 2, a->ld, a->np, a->H, a->eps, a->rows, fp(imu) + r0, fp(irstd) + r0,
+                               a->alias_shift ? fp(ishout) + r0 : (ishin < 0 ? (const float*)nullptr : fp(ishin) + r0), fp(ishout) + r0,
+                               prev ? prev + r0 : nullptr);
+      break;
+    }
+    case VRAG_DEBUG_GLUE_PACK_LAYOUT:
+      launch_pack_layout(0, ip(ipacked), ip(isrow), ip(issrc), ip(islen), a->n_seqs, a->rows, a->pad_id, ip(iids), ip(ipos), ip(itok));
+      break;
+    case VRAG_DEBUG_GLUE_SPLADE_COMPACT:
+      launch_splade_compact(0, fp(isrc), a->rows, a->V, a->ld, a->thr, a->cap, ip(icnt), ip(iidx), fp(ival));
+      break;
+    default:
+      (void)permute_qkv_heads(hp(iw), fp(is), a->H, a->nh, hp(iwo), fp(iso), nullptr);
+      break;
+  }
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  unsigned saturated = 0;
+  if (e == hipSuccess) e = hipMemcpy(&saturated, sat.p, 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) a->f16_saturated = saturated ? 1 : 0;
+  std::vector<unsigned char> canary(kCanary);
+  const char* clobbered = nullptr;
+  for (Buf& b : bufs) {
+    if (e != hipSuccess) break;
+    e = hipMemcpy(canary.data(), b.dev.as<char>() + b.bytes, kCanary, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !clobbered && std::any_of(canary.begin(), canary.end(), [](unsigned char v) { return v != kCanaryByte; }))
+      clobbered = b.name;
+    if (e == hipSuccess && b.host_out && b.bytes) e = hipMemcpy(b.host_out, b.dev.p, b.bytes, hipMemcpyDeviceToHost);
+  }
+  if (e != hipSuccess) {
+    set_error("debug glue run failed: %s", hipGetErrorString(e));
+    return VRAG_ERR_HIP;
+  }
+  if (clobbered) {
+    set_error("debug glue run: the launch wrote past the end of %s", clobbered);
+    return VRAG_ERR_HIP;
   }
   return VRAG_OK;
 }
