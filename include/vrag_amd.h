@@ -303,6 +303,8 @@ int vrag_encoder_read_profile(vrag_encoder* enc, float* ms /*[VRAG_PROF_COUNT]*/
  * bf16 rows (dtype 0): one query streams the shard on the scalar kernel; two or more take the tiled score GEMM (shards of >= 4 096
  * rows, dim % 64 == 0) -- the shard read once per batch -- whose scores are exact on bf16-representable data and otherwise differ
  * from the fp32 chain by summation order.
+ * Dense rows and queries are expected to be finite: a NaN score is kept by the pass kernels (it becomes a key like any other score) and
+ * dropped by the tiled search's epilogue (no comparison with the entry threshold holds), so the routes disagree on such rows.
  */
 typedef struct vrag_dense_index vrag_dense_index;
 int vrag_dense_index_create(int32_t dim, int64_t capacity, int32_t dtype, int32_t device, vrag_dense_index** out);

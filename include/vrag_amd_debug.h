@@ -2,8 +2,8 @@
  * these entry points exist only in libvrag_amd_dbg.so, the harness build of the same sources (verbatim-rag_amd/build.py,
  * -DVRAG_DEBUG_API: it also keeps the phase-decomposition branches of the fused kernel that the product build compiles out).
  * tools/, tests/test_attention_unit_gpu.py, tests/test_attn_unit_gpu.py, tests/test_gemm_unit_gpu.py,
- * tests/test_qkv_attn_unit_gpu.py, tests/test_rows_unit_gpu.py and tests/test_glue_unit_gpu.py load it beside the product
- * library. */
+ * tests/test_qkv_attn_unit_gpu.py, tests/test_rows_unit_gpu.py, tests/test_glue_unit_gpu.py and tests/test_topk_unit_gpu.py
+ * load it beside the product library. */
 #ifndef VRAG_AMD_DEBUG_H
 #define VRAG_AMD_DEBUG_H
 
@@ -275,6 +275,76 @@ typedef struct vrag_debug_glue_args {
   int32_t f16_saturated;     /* out: the clamp word of an fp16 cvt launch */
 } vrag_debug_glue_args;
 int vrag_debug_glue_run(vrag_debug_glue_args* args, int32_t device);
+
+/* Unit-test hook of the tiled batched dense search's kernels alone (csrc/topk_kernels.h; the score stage is
+ * launch_gemm(EPI_TOPK, ...) of csrc/gemm_bf16.h), one launcher per call, chosen by `op`.  Host buffers in, exactly the launcher's
+ * launches (one), buffers marked "in / out" copied to the device before the launch and back after it, so a canary survives where
+ * the kernel must not write.  Every per-query buffer holds nq_buf >= nq queries: the rows behind nq are the caller's canary.
+ * Refused by the hook before anything is launched, each with its own message: a null required pointer; nq < 1 or nq_buf < nq;
+ * k outside 1..64 or k > cap; cap < 2; K (dim) % 64 != 0; N not 64 with tile 2, 128 with tile 1 or a multiple of 256 with tile 0;
+ * nq (2 nq with pairs) above N; M < 1; direct mode with cap < M; appending mode with a preset counter above cap (it is the carry);
+ * row_base + M beyond corpus_rows; stride or skip (> 1) together, with M % 256 != 0, in direct / appending mode respectively
+ * only, with tile 0 and N > 256 where N / 256 does not divide 256 (no whole round), or on a launch that takes a 128-row tile
+ * configuration (those do not walk the map); any corpus tile the launch would read through row_base, stride, skip or tile0 at or
+ * beyond the corpus's padded tiles, and with stride / skip at or beyond corpus_rows / 256; a selection's cap not a power of two or
+ * above 4096; the first selection's cap below its first window (min(n, 256), k > 16: min(n, 1024), rounded up to a power of two);
+ * n < 1 or n > src_stride; rescue with dim % 64 != 0, dim > 4096, n_rows < 1 or slices outside 8..64; merge with n < 1.
+ * Nothing the hook accepts reads or writes outside its buffers.  Index ranges per op:
+ *   SCORE_STAGE   A = corpus + row_base * K (stride / skip: corpus itself), W = w [N, K].  A launch of T = ceil(M / BM) row tiles
+ *                 reads whole tiles of BM rows: rows [row_base, row_base + T * BM) -- inside the allocation, which is padded to whole
+ *                 256-row tiles, checked -- or, 256-row forms with stride / skip, corpus tile t * stride / map(tile0 + t), t < M / 256,
+ *                 map(d) = d + d / (skip - 1) + 1 below 256 (skip - 1) and d + 256 beyond: below corpus_rows / 256, checked.  W is
+ *                 read in whole column tiles of BN | N.  The epilogue reads thr_score / thr_key[query] and adds to cnt[query] with
+ *                 query < nq only; direct mode stores buf[query * cap + m], m < M <= cap; appending mode stores
+ *                 buf[query * cap + slot] where slot < cap (its own test).
+ *   QUERIES       workgroup r < N (the grid) reads queries[(pairs ? r / 2 : r) * K + c] where that query < nq, c < K; writes w_out[r * K + c].
+ *   SELECT        workgroup q < nq reads cnt[q] and buf[q * cap + i], i < min(cnt[q], cap); sorts P <= cap keys in LDS (cap a power of
+ *                 two); writes buf[q * cap + i], out[q * k + i], i < k <= cap, cnt, thr_key, thr_score, ovf[q].
+ *   SELECT_DIRECT workgroup q < nq reads src[q * src_stride + i], i < n <= src_stride; LDS slots k + pos < cap by its own test, the
+ *                 first window <= cap checked; writes as SELECT.
+ *   RESCUE        grid (nq, slices).  Reads ovf[q]; corpus rows r < n_rows = n, 8 columns from c < K; queries[q * K + c]; writes
+ *                 part[(slice * nq + q) * k + i], done[q], out[q * k + i] of flagged queries; part is the hook's own scratch.
+ *   MERGE         workgroup q < nq reads src[(w * nq + q) * k + j], w < n, j < k; writes out[q * k + j].
+ *   TAU           lane q < nq reads eps[q]; writes thr_key, thr_score, cnt, ovf[q].
+ * Every device buffer, inputs included, is followed by 4 KiB of canary; the hook fails with VRAG_ERR_HIP if a launch touched any. */
+enum {
+  VRAG_DEBUG_TOPK_SCORE_STAGE = 0,
+  VRAG_DEBUG_TOPK_QUERIES = 1,
+  VRAG_DEBUG_TOPK_SELECT = 2,
+  VRAG_DEBUG_TOPK_SELECT_DIRECT = 3,
+  VRAG_DEBUG_TOPK_RESCUE = 4,
+  VRAG_DEBUG_TOPK_MERGE = 5,
+  VRAG_DEBUG_TOPK_TAU = 6
+};
+typedef struct vrag_debug_topk_args {
+  const uint16_t* corpus;    /* score_stage, rescue [corpus_rows, K] bf16 bits (the hook pads the device copy to whole 256-row tiles with zeros) */
+  const uint16_t* w;         /* score_stage [N, K] bf16 bits: the query operand (pairs: rows 2q, 2q + 1) */
+  const float* queries;      /* queries, rescue [nq, K] */
+  const float* eps;          /* tau [nq] */
+  const uint64_t* src;       /* select_direct [nq, src_stride]; merge [n, nq, k] */
+  uint16_t* w_out;           /* in / out: queries [N, K] */
+  uint64_t* buf;             /* in / out: score_stage, select, select_direct [nq_buf, cap] */
+  uint32_t* cnt;             /* in / out: score_stage, select, select_direct, tau [nq_buf] */
+  uint64_t* thr_key;         /* in / out: the same ops [nq_buf] */
+  float* thr_score;          /* in / out: the same ops [nq_buf] */
+  uint64_t* out;             /* in / out: select, select_direct (nullable), rescue, merge [nq_buf, k] */
+  uint32_t* ovf;             /* in / out: select, select_direct, tau [nq_buf]; rescue: the flags it reads */
+  uint32_t* done;            /* in / out: rescue [nq_buf] slice counters */
+  int32_t op;
+  int32_t M, N, K;           /* score_stage: GemmParams M, N, K; queries: N = n_cols_pad, K = dim; rescue: K = dim */
+  int32_t corpus_rows;
+  int32_t nq, nq_buf;
+  int32_t k, cap;
+  int32_t pairs, direct, tile;   /* GemmParams topk_pairs, topk_direct, topk_tile */
+  uint32_t row_base;         /* GemmParams topk_row_base */
+  int32_t tile_stride, tile_skip, tile0;   /* GemmParams topk_tile_stride, topk_tile_skip, topk_tile0 */
+  int32_t n;                 /* select_direct: keys per query; rescue: n_rows; merge: lists */
+  int32_t src_stride;        /* select_direct */
+  int32_t slices;            /* rescue */
+  int32_t small_rows;        /* score_stage: small-batch row threshold for this call (restored afterwards); < 0 = leave it */
+  int32_t config[7];         /* out, score_stage: the tile configuration that ran: BM, BN, WM, WN, NS, HW, KCH */
+} vrag_debug_topk_args;
+int vrag_debug_topk_run(vrag_debug_topk_args* args, int32_t device);
 
 #ifdef __cplusplus
 }

@@ -180,3 +180,9 @@ def test_debug_rows_args_layout_matches_ctypes(tmp_path):
 def test_debug_glue_args_layout_matches_ctypes(tmp_path):
     """The same for vrag_debug_glue_args and _lib.DebugGlueArgs (tests/test_glue_unit_gpu.py)."""
     _check_layout(tmp_path, "vrag_debug_glue_args", _lib.DebugGlueArgs)
+
+
+@pytest.mark.skipif(_host_cc() is None, reason="no host C compiler")
+def test_debug_topk_args_layout_matches_ctypes(tmp_path):
+    """The same for vrag_debug_topk_args and _lib.DebugTopkArgs (tests/test_topk_unit_gpu.py)."""
+    _check_layout(tmp_path, "vrag_debug_topk_args", _lib.DebugTopkArgs)

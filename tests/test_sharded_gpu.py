@@ -33,6 +33,23 @@ def test_device_merge_equals_host_statement():
         assert np.all(np.isneginf(ds[di < 0]))
 
 
+def test_device_merge_more_lists_than_lanes():
+    """65 and 256 lists: the merge wave's lanes fold four lists each; mixed -1 tails, some lists wholly empty."""
+    rng = np.random.default_rng(5)
+    for W, Q, k_in, k_out in [(65, 3, 6, 6), (65, 2, 4, 20), (256, 3, 5, 5), (256, 2, 3, 64)]:
+        s = (rng.integers(-16, 17, (W, Q, k_in)) / 16).astype(np.float32)
+        s = np.take_along_axis(s, np.argsort(-s, axis=2, kind="stable"), axis=2)
+        ids = np.stack([np.sort(rng.choice(100000, (Q, k_in), replace=False), axis=1) + 100000 * w for w in range(W)]).astype(np.int64)
+        tail = rng.integers(0, k_in + 1, (W, Q))
+        tail[::7] = 0
+        ids[np.arange(k_in)[None, None, :] >= tail[:, :, None]] = -1
+        hs, hi = merge_topk(s, ids, k_out)
+        ds, di = merge_topk_device(s, ids, k_out)
+        assert np.array_equal(hi, di), (W, Q, k_in, k_out)
+        assert np.array_equal(hs[hi >= 0], ds[di >= 0])
+        assert np.all(np.isneginf(ds[di < 0]))
+
+
 def test_device_merge_in_place_on_a_packed_gather_buffer():
     """on_device = 1 with list strides: the layout ShardComm hands over under RCCL ([ids | scores | pad] per rank)."""
     import ctypes as C

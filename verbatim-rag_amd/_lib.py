@@ -179,6 +179,7 @@ DEBUG_SIGNATURES = {
     "vrag_debug_pack_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "vrag_debug_rows_run": (C.c_int, [C.c_void_p, C.c_int32]),
     "vrag_debug_glue_run": (C.c_int, [C.c_void_p, C.c_int32]),
+    "vrag_debug_topk_run": (C.c_int, [C.c_void_p, C.c_int32]),
 }
 
 
@@ -232,6 +233,20 @@ class DebugGlueArgs(C.Structure):
 
 DEBUG_GLUE_OPS = {"cvt_rows": 0, "cvt_split3": 1, "ln_stats_finalize": 2, "pack_layout": 3, "splade_compact": 4,
                   "permute_qkv_heads": 5}
+
+
+
+class DebugTopkArgs(C.Structure):
+    """vrag_debug_topk_args (include/vrag_amd_debug.h), field for field; tests/test_capi_abi.py checks the layout too."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "corpus", "w", "queries", "eps", "src", "w_out", "buf", "cnt", "thr_key", "thr_score", "out", "ovf", "done")] + [
+        (n, C.c_int32) for n in ("op", "M", "N", "K", "corpus_rows", "nq", "nq_buf", "k", "cap", "pairs", "direct", "tile")] + [
+        ("row_base", C.c_uint32)] + [
+        (n, C.c_int32) for n in ("tile_stride", "tile_skip", "tile0", "n", "src_stride", "slices", "small_rows")] + [
+        ("config", C.c_int32 * 7)]
+
+
+DEBUG_TOPK_OPS = {"score_stage": 0, "queries": 1, "select": 2, "select_direct": 3, "rescue": 4, "merge": 5, "tau": 6}
 
 _DBG = None
 

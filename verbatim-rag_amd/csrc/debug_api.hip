@@ -1,5 +1,5 @@
 // Tuning / unit-test harness of the kernels (include/vrag_amd_debug.h): synthetic-operand timing loops and the attention
-// kernels', the GEMM's, the row kernels' and the packing / glue kernels' unit-test hooks.  NOT part of the product library: compiled only into libvrag_amd_dbg.so (build.py, -DVRAG_DEBUG_API),
+// kernels', the GEMM's, the row kernels', the packing / glue kernels' and the tiled search kernels' unit-test hooks.  NOT part of the product library: compiled only into libvrag_amd_dbg.so (build.py, -DVRAG_DEBUG_API),
 // which tools/ and the attention unit test load beside libvrag_amd.so.
 #include "../../include/vrag_amd.h"
 #include "../../include/vrag_amd_debug.h"
@@ -15,6 +15,7 @@
 #include "host_util.h"
 #include "norm_heads.h"
 #include "qkv_attn.h"
+#include "topk_kernels.h"
 
 using namespace vrag;
 
@@ -1079,6 +1080,242 @@ int vrag_debug_glue_run(vrag_debug_glue_args* a, int32_t device) {
   }
   if (clobbered) {
     set_error("debug glue run: the launch wrote past the end of %s", clobbered);
+    return VRAG_ERR_HIP;
+  }
+  return VRAG_OK;
+}
+
+int vrag_debug_topk_run(vrag_debug_topk_args* a, int32_t device) {
+  ARG_CHECK(a, "null arguments");
+  const int op = a->op;
+  ARG_CHECK(op >= VRAG_DEBUG_TOPK_SCORE_STAGE && op <= VRAG_DEBUG_TOPK_TAU, "op %d is not a tiled search launcher", op);
+  ARG_CHECK(device >= 0, "bad device %d", device);
+  const bool stage = op == VRAG_DEBUG_TOPK_SCORE_STAGE, queries = op == VRAG_DEBUG_TOPK_QUERIES, sel = op == VRAG_DEBUG_TOPK_SELECT;
+  const bool seld = op == VRAG_DEBUG_TOPK_SELECT_DIRECT, rescue = op == VRAG_DEBUG_TOPK_RESCUE, merge = op == VRAG_DEBUG_TOPK_MERGE;
+  const bool tau = op == VRAG_DEBUG_TOPK_TAU;
+  constexpr int kMax = 1 << 20;            // every extent, and
+  constexpr int64_t kMaxElems = 1 << 26;   // every buffer's element count: the sizes below stay far inside size_t and int
+  ARG_CHECK(a->nq >= 1 && a->nq <= 4096, "nq (%d) must be in 1..4096", a->nq);
+  ARG_CHECK(a->nq_buf >= a->nq && a->nq_buf <= 8192, "nq_buf (%d) below nq (%d)", a->nq_buf, a->nq);
+  if (!queries && !tau) ARG_CHECK(a->k >= 1 && a->k <= 64, "k (%d) must be in 1..64", a->k);
+  if (stage || sel || seld) {
+    ARG_CHECK(a->buf && a->cnt && a->thr_key && a->thr_score, "%s needs buf, cnt, thr_key and thr_score", stage ? "score_stage" : "the selection");
+    ARG_CHECK(a->cap >= 2 && a->cap <= kMax, "cap (%d) must be in 2..%d", a->cap, kMax);
+    ARG_CHECK(a->k <= a->cap, "k (%d) above cap (%d)", a->k, a->cap);
+    ARG_CHECK((int64_t)a->nq_buf * a->cap <= kMaxElems, "the candidate buffers are too large for the hook");
+  }
+  int bm = 256;   // rows of the tile configuration the score stage takes (launch_t of csrc/gemm_bf16.hip)
+  if (stage) {
+    ARG_CHECK(a->corpus && a->w, "score_stage needs corpus and w");
+    ARG_CHECK(a->K >= 64 && a->K <= 4096 && a->K % 64 == 0, "K (%d) must be a multiple of 64 in 64..4096", a->K);
+    ARG_CHECK((a->tile == 2 && a->N == 64) || (a->tile == 1 && a->N == 128) || (a->tile == 0 && a->N >= 256 && a->N <= 4096 && a->N % 256 == 0),
+              "N (%d) must be 64 with tile 2, 128 with tile 1 or a multiple of 256 up to 4096 with tile 0 (tile %d)", a->N, a->tile);
+    ARG_CHECK((a->pairs ? 2 * a->nq : a->nq) <= a->N, "%d query columns (nq %d%s) above N (%d)", a->pairs ? 2 * a->nq : a->nq, a->nq, a->pairs ? ", pairs" : "", a->N);
+    ARG_CHECK(a->M >= 1 && a->M <= kMax, "M (%d) must be in 1..%d", a->M, kMax);
+    ARG_CHECK(a->corpus_rows >= 1 && a->corpus_rows <= kMax && (int64_t)(a->corpus_rows + 255) * a->K <= kMaxElems,
+              "corpus_rows (%d) must be positive and the corpus fit the hook", a->corpus_rows);
+    ARG_CHECK(!a->direct || a->cap >= a->M, "direct mode: cap (%d) below M (%d)", a->cap, a->M);
+    if (!a->direct)
+      for (int q = 0; q < a->nq; ++q) ARG_CHECK(a->cnt[q] <= (uint32_t)a->cap, "cnt[%d] = %u is the carry and exceeds cap (%d)", q, a->cnt[q], a->cap);
+    const int thr = a->small_rows >= 0 ? a->small_rows : gemm_small_m_threshold(-1);
+    if (a->tile != 2) bm = a->M <= thr ? 128 : ((a->tile == 1 || a->N % 256 == 0) && a->M >= 256 ? 256 : 128);
+    const bool stride = a->tile_stride > 1, skip = a->tile_skip > 1;
+    const int64_t pad_tiles = ((int64_t)a->corpus_rows + 255) / 256, whole_tiles = a->corpus_rows / 256;
+    ARG_CHECK(a->tile_stride >= 0 && a->tile_skip >= 0 && a->tile_stride <= kMax && a->tile_skip <= kMax, "negative or huge stride / skip (%d / %d)", a->tile_stride, a->tile_skip);
+    if (stride || skip) {
+      ARG_CHECK(!(stride && skip), "stride (%d) and skip (%d) do not come together", a->tile_stride, a->tile_skip);
+      ARG_CHECK(a->M % 256 == 0, "stride / skip with M (%d) not a multiple of 256", a->M);
+      ARG_CHECK(!stride || a->direct, "stride (%d) belongs to the direct stage", a->tile_stride);
+      ARG_CHECK(!skip || !a->direct, "skip (%d) belongs to the appending stages", a->tile_skip);
+      ARG_CHECK(!(a->tile == 0 && a->N > 256 && 256 % (a->N / 256) != 0), "stride / skip with %d column tiles: no whole round", a->N / 256);
+      ARG_CHECK(bm == 256, "stride / skip on a launch that takes the 128-row tiles (M %d <= the small-batch threshold %d)", a->M, thr);
+      const int64_t T = a->M / 256;
+      if (stride) ARG_CHECK((T - 1) * a->tile_stride < whole_tiles, "stride %d: launch tile %lld reads corpus tile %lld of %lld", a->tile_stride, (long long)(T - 1), (long long)((T - 1) * a->tile_stride), (long long)whole_tiles);
+      if (skip) {
+        ARG_CHECK(a->tile0 >= 0 && a->tile0 <= kMax, "tile0 (%d) must be in 0..%d", a->tile0, kMax);
+        const int64_t d = (int64_t)a->tile0 + T - 1, s1 = a->tile_skip - 1, ct = d < 256 * s1 ? d + d / s1 + 1 : d + 256;
+        ARG_CHECK(ct < whole_tiles, "skip %d, tile0 %d: launch tile %lld reads corpus tile %lld of %lld", a->tile_skip, a->tile0, (long long)(T - 1), (long long)ct, (long long)whole_tiles);
+      }
+    } else {
+      ARG_CHECK((int64_t)a->row_base + a->M <= a->corpus_rows, "row_base + M (%u + %d) beyond corpus_rows (%d)", a->row_base, a->M, a->corpus_rows);
+      const int64_t last = (int64_t)a->row_base + ((int64_t)a->M + bm - 1) / bm * bm;   // whole tiles of bm rows are read
+      ARG_CHECK(last <= pad_tiles * 256, "the launch reads rows up to %lld of a corpus padded to %lld", (long long)last, (long long)(pad_tiles * 256));
+    }
+  }
+  if (queries) {
+    ARG_CHECK(a->queries && a->w_out, "queries needs queries and w_out");
+    ARG_CHECK(a->K >= 1 && a->K <= 4096, "K (%d) must be in 1..4096", a->K);
+    ARG_CHECK(a->N >= 1 && a->N <= 4096, "N (%d) must be in 1..4096", a->N);
+    ARG_CHECK((a->pairs ? 2 * a->nq : a->nq) <= a->N, "%d query columns above N (%d)", a->pairs ? 2 * a->nq : a->nq, a->N);
+  }
+  if (sel || seld) {
+    ARG_CHECK(a->ovf, "the selection needs ovf");
+    ARG_CHECK((a->cap & (a->cap - 1)) == 0 && a->cap <= kTiledSelectMaxCap, "the selection sorts in LDS: cap (%d) must be a power of two up to %d", a->cap, kTiledSelectMaxCap);
+  }
+  if (seld) {
+    ARG_CHECK(a->src, "select_direct needs src");
+    ARG_CHECK(a->n >= 1 && a->n <= kMax, "n (%d) must be in 1..%d", a->n, kMax);
+    ARG_CHECK(a->n <= a->src_stride && a->src_stride <= kMax, "n (%d) above src_stride (%d)", a->n, a->src_stride);
+    ARG_CHECK((int64_t)a->nq * a->src_stride <= kMaxElems, "src is too large for the hook");
+    int first = std::min(a->n, a->k > 16 ? 1024 : 256), P = 2;
+    while (P < first) P <<= 1;
+    ARG_CHECK(P <= a->cap, "select_direct: cap (%d) below the first window (%d keys)", a->cap, P);
+  }
+  if (rescue) {
+    ARG_CHECK(a->corpus && a->queries && a->ovf && a->done && a->out, "rescue needs corpus, queries, ovf, done and out");
+    ARG_CHECK(a->K >= 64 && a->K <= 4096 && a->K % 64 == 0, "rescue: dim (%d) must be a multiple of 64 in 64..4096", a->K);
+    ARG_CHECK(a->n >= 1 && a->n <= kMax && (int64_t)a->n * a->K <= kMaxElems, "rescue: n_rows (%d) must be positive and the rows fit the hook", a->n);
+    ARG_CHECK(a->corpus_rows == a->n, "rescue: corpus_rows (%d) must be n_rows (%d)", a->corpus_rows, a->n);
+    ARG_CHECK(a->slices >= 8 && a->slices <= kTiledRescueMaxSlices, "rescue: slices (%d) must be in 8..%d", a->slices, kTiledRescueMaxSlices);
+  }
+  if (merge) {
+    ARG_CHECK(a->src && a->out, "merge needs src and out");
+    ARG_CHECK(a->n >= 1 && a->n <= kMax && (int64_t)a->n * a->nq * a->k <= kMaxElems, "merge: %d lists must be positive and fit the hook", a->n);
+  }
+  if (tau) ARG_CHECK(a->thr_key && a->thr_score && a->eps && a->cnt && a->ovf, "tau needs thr_key, thr_score, eps, cnt and ovf");
+  if (vrag_device_count() <= device) {
+    set_error("no HIP device %d visible", device);
+    return VRAG_ERR_NO_DEVICE;
+  }
+  HIP_TRY(hipSetDevice(device));
+
+  // device copies: every buffer is followed by a 4 KiB canary that the launch must leave as it was
+  constexpr size_t kCanary = 4096;
+  constexpr unsigned char kCanaryByte = 0xA5;
+  struct Buf {
+    const void* host;
+    void* host_out;   // null = input only
+    size_t bytes;     // copied from the host
+    size_t pad;       // zero bytes behind them (the corpus's last tile), in front of the canary
+    const char* name;
+    DevBuf dev;
+  };
+  std::vector<Buf> bufs;
+  auto add = [&](const void* h, void* h_out, size_t bytes, const char* name, size_t pad = 0) -> int {
+    if (!h) return -1;
+    bufs.push_back(Buf{h, h_out, bytes, pad, name, DevBuf()});
+    return (int)bufs.size() - 1;
+  };
+  const size_t NB = (size_t)a->nq_buf, K = (size_t)a->K, k = (size_t)a->k, cap = (size_t)a->cap;
+  int icorpus = -1, iw = -1, iq = -1, ieps = -1, isrc = -1, iwo = -1, ibuf = -1, icnt = -1, ikey = -1, isc = -1, iout = -1, iovf = -1, idone = -1;
+  if (stage || rescue) {
+    const size_t rows = (size_t)a->corpus_rows, padded = (rows + 255) / 256 * 256;
+    icorpus = add(a->corpus, nullptr, rows * K * 2, "corpus", (padded - rows) * K * 2);
+  }
+  if (stage) iw = add(a->w, nullptr, (size_t)a->N * K * 2, "w");
+  if (queries || rescue) iq = add(a->queries, nullptr, (size_t)a->nq * K * 4, "queries");
+  if (queries) iwo = add(a->w_out, a->w_out, (size_t)a->N * K * 2, "w_out");
+  if (seld) isrc = add(a->src, nullptr, (size_t)a->nq * (size_t)a->src_stride * 8, "src");
+  if (merge) isrc = add(a->src, nullptr, (size_t)a->n * (size_t)a->nq * k * 8, "src");
+  if (stage || sel || seld) ibuf = add(a->buf, a->buf, NB * cap * 8, "buf");
+  if (stage || sel || seld || tau) {
+    icnt = add(a->cnt, a->cnt, NB * 4, "cnt");
+    ikey = add(a->thr_key, a->thr_key, NB * 8, "thr_key");
+    isc = add(a->thr_score, a->thr_score, NB * 4, "thr_score");
+  }
+  if (sel || seld || rescue || merge) iout = add(a->out, a->out, NB * k * 8, "out");
+  if (sel || seld || rescue || tau) iovf = add(a->ovf, a->ovf, NB * 4, "ovf");
+  if (tau) ieps = add(a->eps, nullptr, (size_t)a->nq * 4, "eps");
+  if (rescue) idone = add(a->done, a->done, NB * 4, "done");
+  DevBuf part;   // the rescue's per-slice lists [slices][nq][k]: scratch of the hook, with a canary of its own
+  const size_t part_bytes = rescue ? (size_t)a->slices * (size_t)a->nq * k * 8 : 0;
+  hipError_t e = hipSuccess;
+  if (rescue) {
+    e = part.alloc(part_bytes + kCanary);
+    if (e == hipSuccess) e = hipMemset(part.p, 0, part_bytes);
+    if (e == hipSuccess) e = hipMemset(part.as<char>() + part_bytes, kCanaryByte, kCanary);
+  }
+  for (Buf& b : bufs) {
+    if (e == hipSuccess) e = b.dev.alloc(b.bytes + b.pad + kCanary);
+    if (e == hipSuccess && b.bytes) e = hipMemcpy(b.dev.p, b.host, b.bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && b.pad) e = hipMemset(b.dev.as<char>() + b.bytes, 0, b.pad);
+    if (e == hipSuccess) e = hipMemset(b.dev.as<char>() + b.bytes + b.pad, kCanaryByte, kCanary);
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    set_error("debug topk run: staging failed: %s", hipGetErrorString(e));
+    return VRAG_ERR_HIP;
+  }
+  auto fp = [&](int i) -> float* { return i < 0 ? nullptr : bufs[i].dev.as<float>(); };
+  auto up = [&](int i) -> unsigned* { return i < 0 ? nullptr : bufs[i].dev.as<unsigned>(); };
+  auto kp = [&](int i) -> u64* { return i < 0 ? nullptr : bufs[i].dev.as<u64>(); };
+  auto hp = [&](int i) -> bf16_t* { return i < 0 ? nullptr : bufs[i].dev.as<bf16_t>(); };
+  switch (op) {
+    case VRAG_DEBUG_TOPK_SCORE_STAGE: {
+      GemmParams g{};
+      g.op_dtype = kOpBf16;
+      const bool mapped = a->tile_stride > 1 || a->tile_skip > 1;   // as dense_tiled_search: the map starts at the shard's first row
+      g.A = hp(icorpus) + (mapped ? (size_t)0 : (size_t)a->row_base * K);
+      g.W = hp(iw);
+      g.M = a->M;
+      g.N = a->N;
+      g.K = a->K;
+      g.topk_thr_score = fp(isc);
+      g.topk_thr_key = kp(ikey);
+      g.topk_cnt = up(icnt);
+      g.topk_buf = kp(ibuf);
+      g.topk_cap = a->cap;
+      g.topk_nq = a->nq;
+      g.topk_pairs = a->pairs;
+      g.topk_direct = a->direct;
+      g.topk_row_base = a->row_base;
+      g.topk_tile = a->tile;
+      g.topk_tile_stride = a->tile_stride;
+      g.topk_tile_skip = a->tile_skip;
+      g.topk_tile0 = a->tile0;
+      const int thr = gemm_small_m_threshold(-1);
+      if (a->small_rows >= 0) gemm_small_m_threshold(a->small_rows);
+      e = launch_gemm(EPI_TOPK, g, 0);
+      const GemmConfig c = gemm_last_config();
+      gemm_small_m_threshold(thr);
+      const int32_t cfg[7] = {c.bm, c.bn, c.wm, c.wn, c.ns, c.hw, c.kch};
+      std::memcpy(a->config, cfg, sizeof(cfg));
+      if (e == hipSuccess && c.bm != bm) {   // the bounds above were worked out for another tile form: nothing may rest on them
+        (void)hipDeviceSynchronize();
+        set_error("debug topk run: the launch took %d-row tiles, the hook expected %d", c.bm, bm);
+        return VRAG_ERR_HIP;
+      }
+      break;
+    }
+    case VRAG_DEBUG_TOPK_QUERIES:
+      e = launch_tiled_queries(fp(iq), a->nq, a->K, a->pairs, a->N, hp(iwo), 0);
+      break;
+    case VRAG_DEBUG_TOPK_SELECT:
+      e = launch_tiled_select(kp(ibuf), up(icnt), a->cap, a->k, kp(ikey), fp(isc), kp(iout), up(iovf), 0, a->nq, 0);
+      break;
+    case VRAG_DEBUG_TOPK_SELECT_DIRECT:
+      e = launch_tiled_select_direct(kp(isrc), a->src_stride, a->n, kp(ibuf), up(icnt), a->cap, a->k, kp(ikey), fp(isc), kp(iout), up(iovf), a->nq, 0);
+      break;
+    case VRAG_DEBUG_TOPK_RESCUE:
+      e = launch_dense_tiled_rescue(hp(icorpus), (long long)a->n, a->K, fp(iq), a->nq, a->k, up(iovf), part.as<u64>(), up(idone), kp(iout), a->slices, 0);
+      break;
+    case VRAG_DEBUG_TOPK_MERGE:
+      e = launch_topk_merge(kp(isrc), a->n, a->nq, a->k, kp(iout), 0);
+      break;
+    default:
+      e = launch_tiled_tau(a->nq, kp(ikey), fp(isc), fp(ieps), up(icnt), up(iovf), 0);
+      break;
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  std::vector<unsigned char> canary(kCanary);
+  const char* clobbered = nullptr;
+  auto intact = [&]() { return std::all_of(canary.begin(), canary.end(), [](unsigned char v) { return v == kCanaryByte; }); };
+  if (e == hipSuccess && rescue) {
+    e = hipMemcpy(canary.data(), part.as<char>() + part_bytes, kCanary, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !intact()) clobbered = "part";
+  }
+  for (Buf& b : bufs) {
+    if (e != hipSuccess) break;
+    e = hipMemcpy(canary.data(), b.dev.as<char>() + b.bytes + b.pad, kCanary, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && !clobbered && !intact()) clobbered = b.name;
+    if (e == hipSuccess && b.host_out && b.bytes) e = hipMemcpy(b.host_out, b.dev.p, b.bytes, hipMemcpyDeviceToHost);
+  }
+  if (e != hipSuccess) {
+    set_error("debug topk run failed: %s", hipGetErrorString(e));
+    return e == hipErrorInvalidValue ? VRAG_ERR_INVALID : VRAG_ERR_HIP;
+  }
+  if (clobbered) {
+    set_error("debug topk run: the launch wrote past the end of %s", clobbered);
     return VRAG_ERR_HIP;
   }
   return VRAG_OK;

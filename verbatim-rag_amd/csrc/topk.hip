@@ -40,6 +40,7 @@
 #include "common.h"
 #include "gemm_bf16.h"
 #include "host_util.h"
+#include "topk_kernels.h"
 
 namespace vrag {
 
@@ -949,7 +950,6 @@ __global__ void topk_seed_threshold_kernel(const u64* __restrict__ out, int nq, 
   if (q < nq) thr[q] = out[(size_t)q * k + (k - 1)];
 }
 
-hipError_t launch_topk_merge(const u64* cand, int n_wg, int nq, int k, u64* out, hipStream_t st);   // also csrc/fulltext.hip
 
 struct Mfma2Plan {
   long long prefix;   // rows of the threshold-seeding pass (0 = single pass)
@@ -1140,7 +1140,9 @@ __global__ __launch_bounds__(256) void tiled_select_kernel(u64* __restrict__ buf
     if (out) out[(size_t)q * k + i] = v;
   }
   if (tid == 0) {
-    const bool full = n >= k;
+    // fewer than k keys among the n slots (reserved slots whose key failed the key test, rows with NaN scores): no threshold, as in
+    // tiled_select_direct_kernel -- unorderable(0) is a NaN, and every later `score >= threshold` would fail for the rest of the shard
+    const bool full = n >= k && sk[k - 1] != 0ull;
     cnt[q] = (unsigned)min(n, k);
     thr_key[q] = full ? sk[k - 1] : 0ull;
     thr_score[q] = full ? unorderable((unsigned)(sk[k - 1] >> 32)) : -INFINITY;
@@ -1311,6 +1313,47 @@ __global__ __launch_bounds__(256) void dense_tiled_rescue_kernel(const bf16_t* _
   }
 }
 
+// Collect form of the tiled search (TiledCollect below): the prefix's k-th score becomes the entry threshold of the one appending pass
+__global__ void tiled_tau_kernel(int nq, u64* __restrict__ thr_key, float* __restrict__ thr_score, const float* __restrict__ eps,
+                                 unsigned* __restrict__ cnt, unsigned* __restrict__ flag) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= nq) return;
+  thr_key[q] = 0ull;                              // the key test of the append passes every key
+  thr_score[q] = thr_score[q] - 2.f * eps[q];     // -inf (fewer than k prefix rows) stays -inf: everything is a candidate
+  cnt[q] = 0u;
+  flag[q] = 0u;
+}
+
+// The launchers of csrc/topk_kernels.h: dense_tiled_search and the unit-test hook launch through them.
+hipError_t launch_tiled_queries(const float* q, int nq, int dim, int pairs, int n_cols_pad, bf16_t* w, hipStream_t st) {
+  hipLaunchKernelGGL(tiled_queries_kernel, dim3(n_cols_pad), dim3(256), 0, st, q, nq, dim, pairs, n_cols_pad, w);
+  return hipGetLastError();
+}
+hipError_t launch_tiled_select(u64* buf, unsigned* cnt, int cap, int k, u64* thr_key, float* thr_score, u64* out, unsigned* ovf,
+                               int direct_n, int nq, hipStream_t st) {
+  const hipError_t e = set_max_dynamic_lds<&tiled_select_kernel>(kTiledSelectMaxCap * (int)sizeof(u64));   // the largest buffer a selection sorts
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(tiled_select_kernel, dim3(nq), dim3(256), (size_t)cap * sizeof(u64), st, buf, cnt, cap, k, thr_key, thr_score, out, ovf, direct_n);
+  return hipGetLastError();
+}
+hipError_t launch_tiled_select_direct(const u64* src, int src_stride, int n, u64* buf, unsigned* cnt, int cap, int k, u64* thr_key,
+                                      float* thr_score, u64* out, unsigned* ovf, int nq, hipStream_t st) {
+  hipLaunchKernelGGL(tiled_select_direct_kernel, dim3(nq), dim3(TSEL_NT), (size_t)cap * sizeof(u64), st, src, src_stride, n, buf, cnt, cap, k,
+                     thr_key, thr_score, out, ovf);
+  return hipGetLastError();
+}
+static_assert(TRESCUE_SLICES == kTiledRescueMaxSlices, "the rescue's slice merge holds one list head per slice");
+hipError_t launch_dense_tiled_rescue(const bf16_t* rows, long long n_rows, int dim, const float* queries, int nq, int k,
+                                     const unsigned* ovf, u64* part, unsigned* done, u64* out, int slices, hipStream_t st) {
+  const size_t lds = (size_t)dim * sizeof(float) + (size_t)16 * k * sizeof(u64);
+  hipLaunchKernelGGL(dense_tiled_rescue_kernel, dim3(nq, slices), dim3(256), lds, st, rows, n_rows, dim, queries, nq, k, ovf, part, done, out);
+  return hipGetLastError();
+}
+hipError_t launch_tiled_tau(int nq, u64* thr_key, float* thr_score, const float* eps, unsigned* cnt, unsigned* flag, hipStream_t st) {
+  hipLaunchKernelGGL(tiled_tau_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, nq, thr_key, thr_score, eps, cnt, flag);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------ fp32 rows, bf16 prefilter
 // The store's default rows are fp32 and its contract bit-exact (scores = the oracle's sequential fmaf chain), which costs a
 // full 4-byte-per-element scan per query batch (1.03 ms for one query over 1.25 M x 768 rows).  With a bf16 image of the rows
@@ -1420,6 +1463,7 @@ __global__ __launch_bounds__(64) void prefilter_rescore_kernel(const u64* __rest
 // lists to maintain, no merge), the candidates are re-scored with the exact chain and sorted.  More candidates than the
 // list holds (flat score distributions) = fall back to the full fp32 scan.
 constexpr int PFCAP = 4096;           // candidate slots per query
+static_assert(PFCAP == kTiledSelectMaxCap && TCAP <= PFCAP, "launch_tiled_select raises the selection's LDS limit to the largest buffer");
 constexpr long long PFPREFIX = 32768; // rows ranked first for the entry threshold
 template <int DIMC>
 __global__ __launch_bounds__(256) void prefilter_collect_kernel(const bf16_t* __restrict__ rows, long long n_rows, int dim,
@@ -2580,15 +2624,6 @@ struct TiledCollect {
 };
 constexpr long long TCOLLECT_PREFIX = 65536;   // one tile round of the persistent grid
 
-__global__ void tiled_tau_kernel(int nq, u64* __restrict__ thr_key, float* __restrict__ thr_score, const float* __restrict__ eps,
-                                 unsigned* __restrict__ cnt, unsigned* __restrict__ flag) {
-  const int q = blockIdx.x * blockDim.x + threadIdx.x;
-  if (q >= nq) return;
-  thr_key[q] = 0ull;                              // the key test of the append passes every key
-  thr_score[q] = thr_score[q] - 2.f * eps[q];     // -inf (fewer than k prefix rows) stays -inf: everything is a candidate
-  cnt[q] = 0u;
-  flag[q] = 0u;
-}
 
 // The tiled batched search on the resident queries (ix->d_q.p, fp32): leaves the [nq, k] keys in ix->d_out.  Kernels only.
 int dense_tiled_search(vrag_dense_index* ix, int nq, int k, hipStream_t st, const void* rows_bf16 = nullptr, const TiledCollect* col = nullptr,
@@ -2612,12 +2647,11 @@ int dense_tiled_search(vrag_dense_index* ix, int nq, int k, hipStream_t st, cons
   const int res_slices = std::max(8, std::min(TRESCUE_SLICES, 8192 / nq));
   if (!col) HIP_TRY(ix->d_tres.grow((size_t)res_slices * nq * k));
   unsigned* ovf = ix->d_tcnt.p + nq;
-  hipLaunchKernelGGL(tiled_queries_kernel, dim3(n_pad), dim3(256), 0, st, ix->d_q.p, nq, dim, pairs, n_pad, ix->d_tw.p);
+  HIP_TRY(launch_tiled_queries(ix->d_q.p, nq, dim, pairs, n_pad, ix->d_tw.p, st));
   hipLaunchKernelGGL(tiled_init_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, nq, ix->d_tthr.p, ix->d_tthrs.p, ix->d_tcnt.p);
   HIP_TRY(hipGetLastError());
   const long long n_all = (long long)ix->size;
   const long long n = col ? std::min<long long>(n_all, TCOLLECT_PREFIX) : n_all;   // collect form: the staged search covers a prefix only
-  HIP_TRY(set_max_dynamic_lds<&tiled_select_kernel>(PFCAP * (int)sizeof(u64)));   // the largest buffer a selection sorts (PFCAP >= TCAP)
   // Rows seen grow by `ratio` per stage, and a stage admits ~k (ratio - 1) candidates per query, each one an atomic append on its
   // query's counter: at k = 64 (the prefilter's candidate lists) a ratio of 16 made the appends, not the row stream, the cost of
   // every stage (960 per query and stage)
@@ -2697,15 +2731,12 @@ int dense_tiled_search(vrag_dense_index* ix, int nq, int k, hipStream_t st, cons
     const bool last = first ? s0 >= n : hi >= n - off;
     u64* const sel_out = (last && !col) ? ix->d_out.p : (u64*)nullptr;
     if (first)
-      hipLaunchKernelGGL(tiled_select_direct_kernel, dim3(nq), dim3(TSEL_NT), (size_t)TCAP * sizeof(u64), st, ix->d_tdir.p, (int)s0, (int)s0, ix->d_tbuf.p,
-                         ix->d_tcnt.p, TCAP, k, ix->d_tthr.p, ix->d_tthrs.p, sel_out, ovf);
+      HIP_TRY(launch_tiled_select_direct(ix->d_tdir.p, (int)s0, (int)s0, ix->d_tbuf.p, ix->d_tcnt.p, TCAP, k, ix->d_tthr.p, ix->d_tthrs.p, sel_out, ovf, nq, st));
     else
-      hipLaunchKernelGGL(tiled_select_kernel, dim3(nq), dim3(256), (size_t)TCAP * sizeof(u64), st, ix->d_tbuf.p, ix->d_tcnt.p, TCAP, k,
-                         ix->d_tthr.p, ix->d_tthrs.p, sel_out, ovf, 0);
-    HIP_TRY(hipGetLastError());
+      HIP_TRY(launch_tiled_select(ix->d_tbuf.p, ix->d_tcnt.p, TCAP, k, ix->d_tthr.p, ix->d_tthrs.p, sel_out, ovf, 0, nq, st));
   }
   if (col) {
-    hipLaunchKernelGGL(tiled_tau_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, nq, ix->d_tthr.p, ix->d_tthrs.p, col->eps, ix->d_tcnt.p, col->flag);
+    HIP_TRY(launch_tiled_tau(nq, ix->d_tthr.p, ix->d_tthrs.p, col->eps, ix->d_tcnt.p, col->flag, st));
     GemmParams g{};
     g.op_dtype = kOpBf16;
     g.A = reinterpret_cast<const bf16_t*>(rows_bf16);
@@ -2727,10 +2758,8 @@ int dense_tiled_search(vrag_dense_index* ix, int nq, int k, hipStream_t st, cons
     return VRAG_OK;   // the caller re-scores and selects; overflow = its flag
   }
   if (!device_rescue) return VRAG_OK;   // the host call reads the overflow flags back with the lists and re-answers flagged queries through the pass kernels
-  const size_t lds = (size_t)dim * sizeof(float) + (size_t)16 * k * sizeof(u64);
-  hipLaunchKernelGGL(dense_tiled_rescue_kernel, dim3(nq, res_slices), dim3(256), lds, st, reinterpret_cast<const bf16_t*>(rows_bf16), n_all, dim,
-                     ix->d_q.p, nq, k, ovf, ix->d_tres.p, ix->d_tcnt.p + 2 * (size_t)nq, ix->d_out.p);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_dense_tiled_rescue(reinterpret_cast<const bf16_t*>(rows_bf16), n_all, dim, ix->d_q.p, nq, k, ovf, ix->d_tres.p,
+                                    ix->d_tcnt.p + 2 * (size_t)nq, ix->d_out.p, res_slices, st));
   return VRAG_OK;
 }
 

@@ -1,0 +1,36 @@
+// Launchers of the tiled batched dense search's own kernels (csrc/topk.hip; the score stage itself is launch_gemm(EPI_TOPK, ...)
+// of csrc/gemm_bf16.h).  Declared here so that the unit-test hook (csrc/debug_api.hip, vrag_debug_topk_run) launches the product's
+// own kernels with the product's own grids and dynamic LDS sizes: dense_tiled_search goes through the same functions.  None of
+// them checks its arguments; the launch's status is returned.
+#pragma once
+#include "common.h"
+
+namespace vrag {
+
+constexpr int kTiledSelectMaxCap = 4096;   // the largest candidate buffer a selection sorts in LDS (the prefilter's lists)
+constexpr int kTiledRescueMaxSlices = 64;  // workgroups per flagged query of the rescue pass, at most
+
+// fp32 queries [nq, dim] -> the score GEMM's W operand [n_cols_pad, dim] bf16.  pairs: rows (2q, 2q + 1) =
+// (bf16(q), bf16(q - bf16(q))); rows beyond the queries are zero.  One workgroup per row of w.
+hipError_t launch_tiled_queries(const float* q, int nq, int dim, int pairs, int n_cols_pad, bf16_t* w, hipStream_t st);
+// One workgroup per query: the first min(cnt[q], cap) keys of buf[q] (direct_n > 0: the first min(direct_n, cap)) sorted descending,
+// the best k kept in buf[q][0, k) and written to out[q][0, k) (nullable), cnt[q] = min(n, k), (thr_key, thr_score)[q] = the k-th
+// key and its score, (0, -inf) while fewer than k keys exist; ovf[q] = 1 where the count exceeded cap.  cap: a power of two,
+// 2 <= cap <= kTiledSelectMaxCap (cap keys of dynamic LDS); k <= cap.
+hipError_t launch_tiled_select(u64* buf, unsigned* cnt, int cap, int k, u64* thr_key, float* thr_score, u64* out, unsigned* ovf,
+                               int direct_n, int nq, hipStream_t st);
+// The first stage's selection: n keys per query at src[q * src_stride] (0 = no key) -> the same outputs, through windows that grow
+// 16x (k <= 16) / 4x from a first window of 256 / 1 024 keys; more than cap - k survivors of one window raise ovf[q].  cap: a power
+// of two, at least the first window and k, at most kTiledSelectMaxCap.
+hipError_t launch_tiled_select_direct(const u64* src, int src_stride, int n, u64* buf, unsigned* cnt, int cap, int k, u64* thr_key,
+                                      float* thr_score, u64* out, unsigned* ovf, int nq, hipStream_t st);
+// Flagged queries (ovf[q] != 0) re-answered over rows [n_rows, dim] bf16 by `slices` workgroups each (<= kTiledRescueMaxSlices):
+// out[q][0, k) = the exact best k; part [slices][nq][k] scratch; done [nq] slice counters, zero before and after.
+hipError_t launch_dense_tiled_rescue(const bf16_t* rows, long long n_rows, int dim, const float* queries, int nq, int k,
+                                     const unsigned* ovf, u64* part, unsigned* done, u64* out, int slices, hipStream_t st);
+// Collect form: thr_score[q] -= 2 eps[q] (-inf stays), thr_key[q] = 0, cnt[q] = 0, flag[q] = 0.
+hipError_t launch_tiled_tau(int nq, u64* thr_key, float* thr_score, const float* eps, unsigned* cnt, unsigned* flag, hipStream_t st);
+// cand [n_wg][nq][k]: per-workgroup lists sorted descending, zero tails, keys unique -> out [nq][k] the best k (also csrc/fulltext.hip).
+hipError_t launch_topk_merge(const u64* cand, int n_wg, int nq, int k, u64* out, hipStream_t st);
+
+}  // namespace vrag
