@@ -556,6 +556,22 @@ int vrag_topk_merge(const float* scores, const int64_t* ids, int32_t n_lists, in
                     int64_t score_list_stride, int64_t id_list_stride, float* out_scores, int64_t* out_ids,
                     int32_t on_device, int32_t device, void* stream);
 
+/* Weighted reciprocal-rank fusion of a batch of queries (hybrid_search.py:73-129 on row numbers; the array form is
+ * rrf_merge_rows in vector_stores.py).  rows[q] = the methods' ranked lists of query q laid side by side, l_total
+ * entries, a negative entry = a rank without a candidate (it keeps its position).  gains[p] = the float64 a candidate at
+ * position p contributes (share_m * (1.0 / (rrf_k + rank + 1)), computed by the caller).  Per query and distinct row:
+ * score = gains of its positions added one after the other in ascending position, starting from the first;
+ * order = score descending, ties by first position ascending; out_rows / out_dist = the first top_k rows and
+ * 1.0 - score, padded with -1 / 0.0.  1 <= l_total <= 4096, 1 <= top_k <= l_total, row ids < 2^32, gains finite and
+ * >= 0.  on_device as vrag_topk_merge: 1 = all pointers are device memory on `device`, the work is only enqueued on
+ * `stream`; 0 = host pointers, the call copies in and out and synchronises (and checks ids and gains).  The device form
+ * cannot read its inputs and so verifies neither: there a row id >= 2^32 is the caller's error, and what it yields differs
+ * between the regimes (l_total <= 64 compares whole ids and fuses any of them correctly; longer lists shift the id into
+ * the upper 52 bits of a sort key, where an id of 2^52 - 1 or more loses bits and is grouped with other rows or dropped). */
+int vrag_rrf_fuse(const int64_t* rows /*[nq, l_total]*/, const double* gains /*[l_total]*/, int32_t nq, int32_t l_total,
+                  int32_t top_k, int64_t* out_rows /*[nq, top_k]*/, double* out_dist /*[nq, top_k]*/,
+                  int32_t on_device, int32_t device, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The exchange step of sharded retrieval: one process per GPU, the corpus row-sharded, every rank answers the
  * (replicated) query batch on its own shard with vrag_*_index_search_device and contributes its packed lists

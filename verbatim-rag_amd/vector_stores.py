@@ -166,6 +166,38 @@ def rrf_merge_rows(rows_by_method: Dict[str, np.ndarray], top_k: int, weights: D
     return rows_out, dist
 
 
+def rrf_fuse_rows_device(rows_by_method: Dict[str, np.ndarray], top_k: int, weights: Dict[str, float],
+                         rrf_k: int = 60, device: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """`rrf_merge_rows` on the GPU (`vrag_rrf_fuse`, csrc/fuse.hip): same arguments, same `[Q, top_k]` rows (-1 padded) and
+    float64 distances, bit for bit.  The gain of every position -- `share * (1.0 / (rrf_k + rank + 1))`, the expression
+    `rrf_merge_rows` evaluates -- is computed here, so the kernel only adds float64 values in the reference's order
+    (ascending position = methods in insertion order, ranks ascending) and the division and the weights never reach it.
+    Lists of up to 4096 entries per query in all, row numbers below 2^32 (include/vrag_amd.h)."""
+    methods = list(rows_by_method)
+    if not methods:
+        raise ValueError("rrf_fuse_rows_device needs at least one method")
+    share = normalize_weights(dict.fromkeys(methods), weights)
+    lists = [np.asarray(rows_by_method[m], dtype=np.int64) for m in methods]
+    Q = lists[0].shape[0]
+    cand = np.ascontiguousarray(np.concatenate(lists, axis=1))                   # [Q, L]
+    L = cand.shape[1]
+    rows_out = np.full((Q, top_k), -1, np.int64)
+    dist = np.zeros((Q, top_k), np.float64)
+    if cand.size == 0 or top_k <= 0 or not (cand >= 0).any():
+        return rows_out, dist
+    gains = np.ascontiguousarray(np.concatenate(
+        [share.get(m, 0.0) * (1.0 / (rrf_k + np.arange(r.shape[1], dtype=np.float64) + 1)) for m, r in zip(methods, lists)]))
+    k = min(top_k, L)                                                             # the call's top_k <= l_total; the rest is padding
+    got_rows = np.empty((Q, k), np.int64)
+    got_dist = np.empty((Q, k), np.float64)
+    _lib.check("vrag_rrf_fuse", _lib.load().vrag_rrf_fuse(
+        cand.ctypes.data_as(C.c_void_p), gains.ctypes.data_as(C.c_void_p), Q, L, k, got_rows.ctypes.data_as(C.c_void_p),
+        got_dist.ctypes.data_as(C.c_void_p), 0, int(device), None))
+    rows_out[:, :k] = got_rows
+    dist[:, :k] = got_dist
+    return rows_out, dist
+
+
 def merge_hybrid_results(results_by_method: Dict[str, List[dict]], top_k: int, weights: Dict[str, float],
                          rrf_k: int = 60, log_label: str = "") -> List[dict]:
     """The per-query, dict-shaped form (hybrid_search.py:73-129): hits are dicts with an "id"; hits whose id is falsy
@@ -917,6 +949,10 @@ class GpuVectorStore(VectorStore):
     DEVICE_K = 64           # longest list the device-resident exchange carries (one device pass)
     SPARSE_TAIL_MIN = 65536  # rows a sparse tail segment may always hold before it is folded into the main image
     TEXT_TAIL_MIN = 65536    # the same for the full-text index's tail segment
+    # rrf_route="device": smallest hybrid batch that is fused on the GPU; below it the call's launch and copies cost more than numpy
+    # (2 x 20 lists on an MI355X host: 16 queries 0.044 ms host / 0.070 ms device, 64 queries 0.104 / 0.076 -- profiles/rrf_fuse_probe.txt).
+    # Both sides give the same bits, so it changes no output.
+    RRF_DEVICE_MIN_QUERIES = 64
 
     def _use_prefilter(self) -> bool:
         if self.dense_dtype != "f32" or self.dense_prefilter is False:
@@ -929,7 +965,7 @@ class GpuVectorStore(VectorStore):
                  enable_sparse: bool = True, dense_dtype: str = "f32", device: int = 0, distributed: bool = False,
                  group=None, comm=None, payload: str = "sharded", dense_headroom: float = 1.5,
                  dense_prefilter="auto", enable_full_text: bool = False, bm25_k1: float = 1.2, bm25_b: float = 0.75,
-                 filter_route: str = "subset"):
+                 filter_route: str = "subset", rrf_route: str = "host"):
         """`enable_full_text`: BM25 keyword search over the raw texts (milvus_cloud.py: bm25_k1 = 1.2, bm25_b = 0.75),
         `search_type="full_text"` and the third leg of a weighted hybrid search; the texts are tokenised, indexed and
         scored on the device (`TextIndex`).  Off by default.  On a sharded store (`distributed=True` or a `comm`) the
@@ -943,7 +979,12 @@ class GpuVectorStore(VectorStore):
         "subset" (default) builds and caches a second shard of just the passing rows from the host copies; "bitmap" runs
         the filtered search of the RESIDENT shard over a row bitmap (`DenseShard.search_filtered`; no second shard is ever
         built, and a delete costs the next query nothing but the bitmap).  Same results either way.  A store whose exchange
-        runs on the GPU (`comm.on_gpu`) keeps "subset".  A run-time choice: not written by `save`, a keyword of `load`."""
+        runs on the GPU (`comm.on_gpu`) keeps "subset".  A run-time choice: not written by `save`, a keyword of `load`.
+        `rrf_route`: where `query_batch` fuses the methods' lists of a hybrid batch -- "host" (default) in numpy
+        (`rrf_merge_rows`), "device" on the GPU (`rrf_fuse_rows_device`; batches of at least `RRF_DEVICE_MIN_QUERIES`
+        queries, smaller ones are cheaper in numpy).  Same bits either way; on a sharded store every
+        rank fuses the same merged lists itself (no collective).  The per-query paths (`query`, a store with a falsy id)
+        always fuse on the host.  A run-time choice like `filter_route`: not written by `save`, a keyword of `load`."""
         self._lib = _lib.load()
         _lib.require_gpu()
         if dense_dtype not in ("f32", "bf16"):
@@ -952,6 +993,8 @@ class GpuVectorStore(VectorStore):
             raise ValueError(f"payload must be 'sharded' or 'replicated' (got {payload!r})")
         if filter_route not in ("subset", "bitmap"):
             raise ValueError(f"filter_route must be 'subset' or 'bitmap' (got {filter_route!r})")
+        if rrf_route not in ("host", "device"):
+            raise ValueError(f"rrf_route must be 'host' or 'device' (got {rrf_route!r})")
         if not enable_dense and not enable_sparse and not enable_full_text:      # milvus_base.py:54-56
             raise ValueError("At least one of enable_dense, enable_sparse, or enable_full_text must be True")
         if enable_full_text and comm is None and distributed:
@@ -978,6 +1021,7 @@ class GpuVectorStore(VectorStore):
 
             self._comm = ShardComm(group, device)
             self._owns_comm = True
+        self.rrf_route = rrf_route
         self.filter_route = filter_route
         # the route searches take: the filtered search returns host lists, which the device-resident exchange does not carry.
         # Replicated configuration only, so every rank decides alike.
@@ -1620,7 +1664,11 @@ class GpuVectorStore(VectorStore):
             rows, scores = next(iter(lists.values()))
             return self._results_batch(rows[:, :top_k], scores[:, :top_k])
         if self._all_ids_truthy:
-            rows, dist = rrf_merge_rows({m: r for m, (r, _s) in lists.items()}, top_k, weights, rrf_k)
+            ranked = {m: r for m, (r, _s) in lists.items()}
+            if self.rrf_route == "device" and Q >= self.RRF_DEVICE_MIN_QUERIES:
+                rows, dist = rrf_fuse_rows_device(ranked, top_k, weights, rrf_k, self.device)
+            else:
+                rows, dist = rrf_merge_rows(ranked, top_k, weights, rrf_k)
             return self._results_batch(rows, dist)
         out = []
         for i in range(Q):
@@ -1875,16 +1923,17 @@ class GpuVectorStore(VectorStore):
 
     @classmethod
     def load(cls, path: str, device: int = 0, distributed: bool = False, group=None, comm=None,
-             payload: str = "sharded", filter_route: str = "subset") -> "GpuVectorStore":
+             payload: str = "sharded", filter_route: str = "subset", rrf_route: str = "host") -> "GpuVectorStore":
         """Reads a directory written by `save` -- by this or an earlier revision (formats 1 - 3), by any number of
         ranks: when the world size differs from the writer's, the saved shards are put back in row order and cut
-        contiguously over the ranks that open the store.  `filter_route`: as the constructor's (not part of a saved store)."""
+        contiguously over the ranks that open the store.  `filter_route`, `rrf_route`: as the constructor's (not part of a saved store)."""
         head, ids, shards = cls._read_saved(path)
         st = cls(dense_dim=head["dense_dim"], sparse_vocab=head["sparse_vocab"], enable_dense=head["enable_dense"],
                  enable_sparse=head["enable_sparse"], dense_dtype=head["dense_dtype"], device=device,
                  distributed=distributed, group=group, comm=comm, payload=payload,
                  dense_prefilter=head.get("dense_prefilter", "auto"), enable_full_text=bool(head.get("enable_full_text", False)),
-                 bm25_k1=head.get("bm25_k1", 1.2), bm25_b=head.get("bm25_b", 0.75), filter_route=filter_route)
+                 bm25_k1=head.get("bm25_k1", 1.2), bm25_b=head.get("bm25_b", 0.75), filter_route=filter_route,
+                 rrf_route=rrf_route)
         n = len(ids)
         for owned, *_ in shards:
             if len(owned) and (owned.min() < 0 or owned.max() >= n):
