@@ -342,6 +342,44 @@ int vrag_dense_index_search_filtered(vrag_dense_index* ix, const float* queries 
                                      const uint32_t* allow /*host, bit r%32 of word r/32*/, int64_t n_allow,
                                      float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * IVF_FLAT over a dense index (csrc/ivf.hip; the reference builds every Milvus store with index_type="IVF_FLAT", nlist and
+ * searches with search_params={"nprobe": N}: verbatim_rag/vector_stores/milvus_base.py:40-50, milvus_local.py:109-117,
+ * index.py:571).  Opt-in and APPROXIMATE in which rows it looks at, exact in what it reports about them.
+ * The handle is an overlay over a vrag_dense_index it does not own -- the base must outlive it: `nlist` fp32 centroids,
+ * list_off[nlist + 1] and list_rows[n_assigned] (uint32 row numbers of the base grouped by list, ascending inside a list).  No
+ * second image of the rows, 4 bytes per row of extra HBM; a search gathers the rows of the probed lists from the base.
+ * Assignment rule, everywhere: list(x) = argmax_c (x . c - 1/2 |c|^2), the lowest list on ties (plain fp32 sums, order unspecified).
+ *   set_centroids  takes the caller's centroids [nlist, dim] (host) instead of training; drops the lists (sync again).
+ *   train          Lloyd's k-means on the device over min(size, max_train_rows) evenly strided rows of the base (sample item i =
+ *                  row i * size / n_train); initial centroids = evenly strided sample items, no RNG; a centroid is the fp32 mean
+ *                  of its members summed in ascending row order (no floating-point atomics: two trainings of the same rows give
+ *                  the same bytes); an empty list keeps its centroid.  0 <= iters <= 1000.  Drops the lists (sync again).
+ *   sync           assigns the base's rows [n_assigned, size) and rebuilds the lists; the base's size is read under the base's lock.
+ *                  Rows appended to the base later are not searched until the next sync.
+ *   stats / read   copy out (any pointer may be NULL); read needs centroids / a sync for what it is asked for.
+ *   search         1 <= k <= 64, nprobe >= 1 (clamped to nlist), queries host fp32.  Per query: the nprobe lists with the best
+ *                  assignment scores (score desc, list asc), then the exact top-k of their rows: scores are the sequential chain
+ *                  acc = fmaf(x[c], q[c], acc), c ascending, of vrag_dense_index_search_filtered, bit for bit, order (score desc,
+ *                  id asc), missing hits -1 / -inf -- with nprobe >= nlist the result IS that call's under an all-ones bitmap.
+ *                  scanned_rows[q] (nullable) = rows in the query's probed lists.  Large nq x nprobe x k is processed in query
+ *                  slices: at most 2^22 candidate keys (32 MB), 2^24 probe scores (64 MB) and 4 096 queries
+ *                  per slice.
+ * Argument errors (null pointers, nlist outside [1, 16384], k or nprobe out of range, search or list read before a sync, a base
+ * that is not the one the overlay was created on) are VRAG_ERR_INVALID before anything is launched or allocated.  The handle
+ * has its own scratch, stream and lock. */
+typedef struct vrag_ivf_index vrag_ivf_index;
+int vrag_ivf_index_create(vrag_dense_index* base, int32_t nlist, vrag_ivf_index** out);
+void vrag_ivf_index_destroy(vrag_ivf_index* ivf);
+int vrag_ivf_index_set_centroids(vrag_ivf_index* ivf, const float* centroids /*[nlist,dim] host*/);
+int vrag_ivf_index_train(vrag_ivf_index* ivf, int32_t iters, int64_t max_train_rows);
+int vrag_ivf_index_sync(vrag_ivf_index* ivf);
+int vrag_ivf_index_stats(vrag_ivf_index* ivf, int32_t* nlist, int64_t* n_assigned, int64_t* largest_list);
+int vrag_ivf_index_read(vrag_ivf_index* ivf, float* centroids /*[nlist,dim]*/, uint32_t* list_off /*[nlist+1]*/,
+                        uint32_t* list_rows /*[n_assigned]*/);
+int vrag_ivf_index_search(vrag_ivf_index* ivf, const float* queries /*[nq,dim] host*/, int32_t nq, int32_t k, int32_t nprobe,
+                          float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, int64_t* scanned_rows /*[nq] or NULL*/, void* stream);
+
 /* Sparse (SPLADE) rows in CSR, term ids < vocab <= 65536; only documents sharing a term with the
  * query (score > 0) are hits, like an inverted index.  ids are CSR row numbers. */
 typedef struct vrag_sparse_index vrag_sparse_index;

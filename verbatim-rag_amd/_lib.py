@@ -122,6 +122,14 @@ SIGNATURES = {
     "vrag_dense_index_run_resident": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p]),
     "vrag_dense_index_search_device": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]),
+    "vrag_ivf_index_create": (C.c_int, [_H, C.c_int32, C.POINTER(_H)]),
+    "vrag_ivf_index_destroy": (None, [_H]),
+    "vrag_ivf_index_set_centroids": (C.c_int, [_H, _FP]),
+    "vrag_ivf_index_train": (C.c_int, [_H, C.c_int32, C.c_int64]),
+    "vrag_ivf_index_sync": (C.c_int, [_H]),
+    "vrag_ivf_index_stats": (C.c_int, [_H, _IP, _LP, _LP]),
+    "vrag_ivf_index_read": (C.c_int, [_H, _FP, C.c_void_p, C.c_void_p]),
+    "vrag_ivf_index_search": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, _FP, _LP, _LP, C.c_void_p]),
     "vrag_sparse_index_search_device": (C.c_int, [_H, _LP, _IP, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "vrag_pack_qa_pairs": (C.c_int, [_IP, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, _IP, C.c_int32, C.c_int32, _IP, C.c_int64,

@@ -47,26 +47,8 @@ namespace vrag {
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 // u64 / orderable / unorderable / make_key: common.h (the tiled batched search builds the same keys in a GEMM epilogue)
 
-// Paged search (k > KMAX): page p+1 only admits keys strictly below the last key of page p; keys are unique per
-// (score, row), so the pages are disjoint and their concatenation is the exact top-(pages * KMAX).
-__device__ __forceinline__ u64 make_key_below(float s, unsigned row, u64 bound) {
-  const u64 key = make_key(s, row);
-  return key < bound ? key : 0ull;
-}
-
-constexpr int KMAX = 64;        // list length of one device pass
+// make_key_below, KMAX, insert_key: topk_kernels.h (csrc/ivf.hip builds its lists with the same pieces)
 constexpr int KPAGED_MAX = 1024;  // largest k of a search call (ceil(k / KMAX) passes)
-
-// Sorted (descending) insert into list[0..k) held in LDS; called by ONE lane.
-__device__ __forceinline__ void insert_key(u64* list, int k, u64 key) {
-  if (key <= list[k - 1]) return;
-  int i = k - 1;
-  while (i > 0 && list[i - 1] < key) {
-    list[i] = list[i - 1];
-    --i;
-  }
-  list[i] = key;
-}
 
 // Maximum of one u64 per lane over the wave, the same value in every lane: DPP steps inside each row of 16 lanes (quad permutes,
 // half-row and row mirrors: VALU only), then the four row maxima through scalar lane reads -- ~40 instructions.  The
@@ -2506,6 +2488,13 @@ struct vrag_dense_index {
   DevArray<unsigned> d_fallow, d_fblk, d_flist;
 };
 
+namespace vrag {
+DenseView dense_index_view(vrag_dense_index* ix) {
+  std::lock_guard<std::mutex> lk(ix->mu);
+  return DenseView{ix->rows.p, ix->dim, ix->dtype, ix->device, ix->size};
+}
+}  // namespace vrag
+
 // May a search of `nq` queries take the prefilter-image route of an fp32 index?  The route's fallback -- the full fp32 scan
 // behind the per-query flags -- is gated only in the exact kernels (dense_topk_exact*_kernel): where those do not run
 // (dim > 768, dim % 32 != 0, VRAG_TOPK_NO_EXACT) the scan would answer EVERY query again, image pass on top.  Batches rank the
@@ -2559,20 +2548,7 @@ __global__ void cvt_f32_bf16_flat(const float* __restrict__ src, bf16_t* __restr
     dst[i] = (bf16_t)src[i];
 }
 
-void decode_keys(const std::vector<u64>& keys, int nq, int k, int64_t base, const int64_t* perm, float* scores,
-                 int64_t* ids) {
-  for (size_t i = 0; i < (size_t)nq * k; ++i) {
-    const u64 key = keys[i];
-    if (key == 0ull) {
-      scores[i] = -INFINITY;
-      ids[i] = -1;
-    } else {
-      scores[i] = unorderable((unsigned)(key >> 32));
-      const int64_t row = (int64_t)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFu));
-      ids[i] = perm ? perm[row] : base + row;
-    }
-  }
-}
+// decode_keys: topk_kernels.h
 
 // k > KMAX: ceil(k / KMAX) passes of KMAX; `run_page(bound)` leaves the merged page keys [nq][KMAX] in d_out.
 // After each page the last key of a full page becomes that query's exclusive bound (0 = exhausted: nothing passes).

@@ -3,9 +3,48 @@
 // own kernels with the product's own grids and dynamic LDS sizes: dense_tiled_search goes through the same functions.  None of
 // them checks its arguments; the launch's status is returned.
 #pragma once
+#include <cmath>
+#include <vector>
+
 #include "common.h"
 
 namespace vrag {
+
+constexpr int KMAX = 64;        // list length of one device pass
+
+// Paged search (k > KMAX): page p+1 only admits keys strictly below the last key of page p; keys are unique per
+// (score, row), so the pages are disjoint and their concatenation is the exact top-(pages * KMAX).
+__device__ __forceinline__ u64 make_key_below(float s, unsigned row, u64 bound) {
+  const u64 key = make_key(s, row);
+  return key < bound ? key : 0ull;
+}
+
+// Sorted (descending) insert into list[0..k) held in LDS; called by ONE lane.
+__device__ __forceinline__ void insert_key(u64* list, int k, u64 key) {
+  if (key <= list[k - 1]) return;
+  int i = k - 1;
+  while (i > 0 && list[i - 1] < key) {
+    list[i] = list[i - 1];
+    --i;
+  }
+  list[i] = key;
+}
+
+// Merged keys [nq][k] of a search -> the caller's lists: score and id (perm[row], or base + row), missing hits (key 0) -1 / -inf.
+inline void decode_keys(const std::vector<u64>& keys, int nq, int k, int64_t base, const int64_t* perm, float* scores,
+                        int64_t* ids) {
+  for (size_t i = 0; i < (size_t)nq * k; ++i) {
+    const u64 key = keys[i];
+    if (key == 0ull) {
+      scores[i] = -INFINITY;
+      ids[i] = -1;
+    } else {
+      scores[i] = unorderable((unsigned)(key >> 32));
+      const int64_t row = (int64_t)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFu));
+      ids[i] = perm ? perm[row] : base + row;
+    }
+  }
+}
 
 constexpr int kTiledSelectMaxCap = 4096;   // the largest candidate buffer a selection sorts in LDS (the prefilter's lists)
 constexpr int kTiledRescueMaxSlices = 64;  // workgroups per flagged query of the rescue pass, at most
@@ -33,4 +72,20 @@ hipError_t launch_tiled_tau(int nq, u64* thr_key, float* thr_score, const float*
 // cand [n_wg][nq][k]: per-workgroup lists sorted descending, zero tails, keys unique -> out [nq][k] the best k (also csrc/fulltext.hip).
 hipError_t launch_topk_merge(const u64* cand, int n_wg, int nq, int k, u64* out, hipStream_t st);
 
+
+// What another handle may know of a dense index (csrc/ivf.hip lays an inverted-file overlay over the resident rows): the rows'
+// device address, their layout and how many are in place, read under the index's lock.  dtype: 0 = bf16 rows, 1 = fp32 rows (an
+// index created with dtype 2 reports 1: `rows` are its fp32 rows).  The address is fixed for the index's lifetime; rows [0, size)
+// are never rewritten.
+struct DenseView {
+  const void* rows;
+  int dim, dtype, device;
+  long long size;
+};
+
+}  // namespace vrag
+
+struct vrag_dense_index;
+namespace vrag {
+DenseView dense_index_view(vrag_dense_index* ix);
 }  // namespace vrag

@@ -273,6 +273,7 @@ class DenseShard:
         self._lib = _lib.load()
         _lib.require_gpu()
         self.dim, self.capacity = dim, capacity
+        self.ivf: Optional["IvfOverlay"] = None    # an IVF_FLAT overlay over these rows (owned: closed before the shard)
         self._h = C.c_void_p()
         code = 0 if dtype == "bf16" else (2 if prefilter and dim % 4 == 0 else 1)
         _lib.check("vrag_dense_index_create", self._lib.vrag_dense_index_create(dim, capacity, code, device, C.byref(self._h)))
@@ -324,8 +325,113 @@ class DenseShard:
         _lib.check("vrag_dense_index_run_resident", self._lib.vrag_dense_index_run_resident(self._h, nq, k, stream))
 
     def close(self):
+        if self.ivf is not None:
+            self.ivf.close()
+            self.ivf = None
         if self._h:
             self._lib.vrag_dense_index_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+IVF_MIN_ROWS = 4096       # below this a store with index_type="IVF_FLAT" searches FLAT
+IVF_NLIST_MAX = 16384     # vrag_ivf_index_create
+IVF_MIN_LIST_ROWS = 39    # rows per list a training needs, as faiss' k-means asks for (min_points_per_centroid)
+IVF_K_MAX = 64            # vrag_ivf_index_search
+
+
+def ivf_effective_nlist(n_rows: int, nlist: int) -> int:
+    """Lists an IVF_FLAT store of `n_rows` rows is built with: 0 (= search FLAT) below `IVF_MIN_ROWS`, else the configured
+    `nlist` capped by the library's limit and by `IVF_MIN_LIST_ROWS` rows per list."""
+    if n_rows < IVF_MIN_ROWS:
+        return 0
+    return min(int(nlist), IVF_NLIST_MAX, n_rows // IVF_MIN_LIST_ROWS)
+
+
+def parse_nprobe(search_params: Optional[Dict[str, Any]], default: int) -> int:
+    """`nprobe` of a query's `search_params`: `{"nprobe": n}` as the reference's callers pass it (index.py:571) or Milvus'
+    `{"params": {"nprobe": n}}`; other keys are ignored, no `nprobe` = `default`.  ValueError unless a positive integer."""
+    value = None
+    if search_params:
+        inner = search_params.get("params")
+        if "nprobe" in search_params:
+            value = search_params["nprobe"]
+        elif isinstance(inner, dict) and "nprobe" in inner:
+            value = inner["nprobe"]
+    if value is None:
+        return default
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
+        raise ValueError(f"nprobe must be a positive integer (got {value!r})")
+    return int(value)
+
+
+def check_index_config(index_type: str, nlist: int, nprobe: int, sharded: bool) -> None:
+    """The constructor's refusals for `index_type` / `nlist` / `nprobe` (pure: no device needed)."""
+    if index_type not in ("FLAT", "IVF_FLAT"):
+        raise ValueError(f"index_type must be 'FLAT' or 'IVF_FLAT' (got {index_type!r})")
+    for name, v in (("nlist", nlist), ("nprobe", nprobe)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"{name} must be a positive integer (got {v!r})")
+    if index_type == "IVF_FLAT" and sharded:
+        raise ValueError("index_type='IVF_FLAT' is single-GPU: sharded stores (distributed=True or a comm) keep FLAT")
+
+
+class IvfOverlay:
+    """IVF_FLAT lists over a `DenseShard`'s resident rows (`vrag_ivf_index`): centroids, list offsets and row numbers only.
+    The shard must outlive it (`DenseShard.ivf` owns it and closes it first)."""
+
+    def __init__(self, shard: DenseShard, nlist: int):
+        self._lib = _lib.load()
+        self.dim, self.nlist = shard.dim, int(nlist)
+        self._h = C.c_void_p()
+        _lib.check("vrag_ivf_index_create", self._lib.vrag_ivf_index_create(shard._h, self.nlist, C.byref(self._h)))
+
+    def set_centroids(self, centroids: np.ndarray) -> None:
+        c = np.ascontiguousarray(centroids, dtype=np.float32)
+        if c.shape != (self.nlist, self.dim):
+            raise ValueError(f"centroids must be [{self.nlist}, {self.dim}]")
+        _lib.check("vrag_ivf_index_set_centroids", self._lib.vrag_ivf_index_set_centroids(self._h, c.ctypes.data_as(_FP)))
+
+    def train(self, iters: int = 10, max_train_rows: int = 1 << 62) -> None:
+        _lib.check("vrag_ivf_index_train", self._lib.vrag_ivf_index_train(self._h, int(iters), int(max_train_rows)))
+
+    def sync(self) -> None:
+        _lib.check("vrag_ivf_index_sync", self._lib.vrag_ivf_index_sync(self._h))
+
+    def stats(self) -> Dict[str, int]:
+        nlist, n, largest = C.c_int32(), C.c_int64(), C.c_int64()
+        _lib.check("vrag_ivf_index_stats", self._lib.vrag_ivf_index_stats(self._h, C.byref(nlist), C.byref(n), C.byref(largest)))
+        return {"nlist": nlist.value, "rows": n.value, "largest_list": largest.value}
+
+    def read(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(centroids `[nlist, dim]`, list_off `[nlist + 1]`, list_rows `[rows]`) after a `sync`."""
+        cent = np.empty((self.nlist, self.dim), np.float32)
+        off = np.empty(self.nlist + 1, np.uint32)
+        rows = np.empty(self.stats()["rows"], np.uint32)
+        _lib.check("vrag_ivf_index_read", self._lib.vrag_ivf_index_read(
+            self._h, cent.ctypes.data_as(_FP), off.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p) if len(rows) else None))
+        return cent, off, rows
+
+    def search(self, queries: np.ndarray, k: int, nprobe: int, stream=None, scanned: bool = False):
+        """(scores `[Q, k]`, ids `[Q, k]`) -- exact scores of the best rows of the `nprobe` nearest lists; with
+        `scanned=True` also the rows each query's lists hold."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        scores = np.empty((q.shape[0], k), np.float32)
+        ids = np.empty((q.shape[0], k), np.int64)
+        seen = np.empty(q.shape[0], np.int64) if scanned else None
+        _lib.check("vrag_ivf_index_search", self._lib.vrag_ivf_index_search(
+            self._h, q.ctypes.data_as(_FP), q.shape[0], k, int(nprobe), scores.ctypes.data_as(_FP), ids.ctypes.data_as(_LP),
+            seen.ctypes.data_as(_LP) if scanned else None, stream))
+        return (scores, ids, seen) if scanned else (scores, ids)
+
+    def close(self):
+        if self._h:
+            self._lib.vrag_ivf_index_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -965,7 +1071,8 @@ class GpuVectorStore(VectorStore):
                  enable_sparse: bool = True, dense_dtype: str = "f32", device: int = 0, distributed: bool = False,
                  group=None, comm=None, payload: str = "sharded", dense_headroom: float = 1.5,
                  dense_prefilter="auto", enable_full_text: bool = False, bm25_k1: float = 1.2, bm25_b: float = 0.75,
-                 filter_route: str = "subset", rrf_route: str = "host"):
+                 filter_route: str = "subset", rrf_route: str = "host", index_type: str = "FLAT", nlist: int = 8192,
+                 nprobe: int = 16):
         """`enable_full_text`: BM25 keyword search over the raw texts (milvus_cloud.py: bm25_k1 = 1.2, bm25_b = 0.75),
         `search_type="full_text"` and the third leg of a weighted hybrid search; the texts are tokenised, indexed and
         scored on the device (`TextIndex`).  Off by default.  On a sharded store (`distributed=True` or a `comm`) the
@@ -984,7 +1091,15 @@ class GpuVectorStore(VectorStore):
         (`rrf_merge_rows`), "device" on the GPU (`rrf_fuse_rows_device`; batches of at least `RRF_DEVICE_MIN_QUERIES`
         queries, smaller ones are cheaper in numpy).  Same bits either way; on a sharded store every
         rank fuses the same merged lists itself (no collective).  The per-query paths (`query`, a store with a falsy id)
-        always fuse on the host.  A run-time choice like `filter_route`: not written by `save`, a keyword of `load`."""
+        always fuse on the host.  A run-time choice like `filter_route`: not written by `save`, a keyword of `load`.
+        `index_type`: "FLAT" (default) = every dense query streams the whole shard, exact.  "IVF_FLAT" (the reference's Milvus
+        stores, milvus_base.py:40-50) = the dense leg looks only at the rows of the `nprobe` lists nearest to the query out of
+        `nlist` k-means lists laid over the resident shard (`IvfOverlay`; `ivf_effective_nlist` caps `nlist` for small stores
+        and keeps stores under `IVF_MIN_ROWS` rows FLAT) -- approximate in WHICH rows it finds, exact in their scores and
+        order.  `search_params={"nprobe": n}` (or Milvus' `{"params": {"nprobe": n}}`) of `query` / `query_batch` overrides
+        `nprobe` per call; n >= nlist returns the FLAT results.  Lists of more than 64 rows per method, filtered queries left
+        short and sharded stores search FLAT.  Kept in a saved store's manifest (FLAT stores write nothing new)."""
+        check_index_config(index_type, nlist, nprobe, distributed or comm is not None)
         self._lib = _lib.load()
         _lib.require_gpu()
         if dense_dtype not in ("f32", "bf16"):
@@ -1023,6 +1138,8 @@ class GpuVectorStore(VectorStore):
             self._owns_comm = True
         self.rrf_route = rrf_route
         self.filter_route = filter_route
+        self.index_type, self.nlist, self.nprobe = index_type, int(nlist), int(nprobe)
+        self._ivf_trained_rows = 0   # rows in the shard when its overlay was last trained (0 = no overlay)
         # the route searches take: the filtered search returns host lists, which the device-resident exchange does not carry.
         # Replicated configuration only, so every rank decides alike.
         self._filter_route = filter_route
@@ -1219,6 +1336,8 @@ class GpuVectorStore(VectorStore):
                 else:
                     self._dense.add(rows[self._dense_flushed:])
                 self._dense_flushed = n
+                if self.index_type == "IVF_FLAT":
+                    self._ivf_refresh(n)
             if self.enable_sparse and n > self._sparse_flushed:
                 main = self._sparse_parts[0] if self._sparse_parts else None
                 main_n = main[2] if main else 0
@@ -1251,6 +1370,38 @@ class GpuVectorStore(VectorStore):
 
                 self._owned_dev = (torch.from_numpy(np.ascontiguousarray(self._main_rows)).to(torch.device("cuda", self.device)), n)
             self._dirty = False
+
+    def _ivf_refresh(self, n: int) -> None:
+        """Keeps the IVF_FLAT overlay of the resident dense shard in step with its `n` rows (called by `_flush`, under the
+        lock): trains (10 Lloyd rounds over 64 rows per list) on the first flush that reaches `IVF_MIN_ROWS`, when the shard
+        has doubled since, and when the shard was rebuilt for capacity; every flush assigns the new rows to their lists."""
+        shard = self._dense
+        nlist_eff = ivf_effective_nlist(n, self.nlist)
+        if nlist_eff == 0:
+            return
+        current = getattr(shard, "ivf", None)
+        if current is None or n >= 2 * self._ivf_trained_rows:
+            overlay = IvfOverlay(shard, nlist_eff)
+            overlay.train(10, 64 * nlist_eff)
+            overlay.sync()
+            shard.ivf = overlay          # the overlay it replaces is released by its last user, like a replaced shard
+            self._ivf_trained_rows = n
+        else:
+            current.sync()
+
+    def ivf_stats(self) -> Optional[Dict[str, int]]:
+        """`{"nlist", "rows", "largest_list", "trained_rows"}` of the dense shard's IVF_FLAT overlay after a flush; None
+        while the store searches FLAT (index_type="FLAT", or fewer than `IVF_MIN_ROWS` rows)."""
+        with self._mu:
+            self._flush()
+            overlay = getattr(self._dense, "ivf", None)
+            if overlay is None:
+                return None
+            return dict(overlay.stats(), trained_rows=self._ivf_trained_rows)
+
+    def _nprobe_of(self, search_params: Optional[Dict[str, Any]]) -> Optional[int]:
+        """The dense leg's `nprobe` for one call; None on a FLAT store (`search_params` has nothing to say there)."""
+        return parse_nprobe(search_params, self.nprobe) if self.index_type == "IVF_FLAT" else None
 
     def _main_parts(self, kind: str):
         """(segments of the resident shard as (shard, first local row), device row table, rows in the whole store)
@@ -1353,8 +1504,8 @@ class GpuVectorStore(VectorStore):
         return [SearchResult(id=h["id"], score=h["distance"], metadata=pay[h["_row"]][2], text=pay[h["_row"]][0],
                              enhanced_text=pay[h["_row"]][1]) for h in hits]
 
-    def _search(self, kind: str, query, limit: int, mask: Optional[np.ndarray]) -> List[dict]:
-        return self._search_batch(kind, [query], limit, mask)[0]
+    def _search(self, kind: str, query, limit: int, mask: Optional[np.ndarray], nprobe: Optional[int] = None) -> List[dict]:
+        return self._search_batch(kind, [query], limit, mask, nprobe)[0]
 
     def _unit_queries(self, queries: Sequence[Any]) -> np.ndarray:
         """COSINE: unit queries against the unit rows (fp32 norm, one row at a time or all at once: same bits)."""
@@ -1363,12 +1514,13 @@ class GpuVectorStore(VectorStore):
         return rows_q / np.where(norms > 0, norms, np.float32(1.0))[:, None]
 
     def _device_topk(self, kind: str, parts, shard_rows: Optional[np.ndarray], queries: Sequence[Any], k: int,
-                     rows_dev=None):
+                     rows_dev=None, nprobe: Optional[int] = None):
         """Top-k of `queries` over one (possibly sharded) set of rows -> (`scores [Q, k]`, GLOBAL `rows [Q, k]`, -1 = no
         hit).  `parts` are this rank's segments as (shard, first local row) (empty when it holds none of the rows) and
         `shard_rows[j]` the global row of local row j (None = the resident main shard, whose append-only mapping is read
         after the search; `rows_dev` = the same table in HBM); with more than one rank the per-shard lists meet in one
-        all-gather and are merged on the GPU."""
+        all-gather and are merged on the GPU.  `nprobe` (IVF_FLAT stores, the dense leg's first pass): a shard with an overlay
+        answers lists of up to `IVF_K_MAX` rows from its `nprobe` nearest lists instead of streaming every row."""
         Q = len(queries)
         comm = self._comm
         q_in = self._unit_queries(queries) if kind == "dense" and parts else queries
@@ -1380,7 +1532,11 @@ class GpuVectorStore(VectorStore):
         else:
             found_lists = []
             for shard, base in parts:
-                sc, local = shard.search(q_in, k)          # dicts_to_csr converts sparse keys / weights to int32 / float32
+                ivf = getattr(shard, "ivf", None) if nprobe is not None and k <= IVF_K_MAX else None
+                if ivf is not None:
+                    sc, local = ivf.search(q_in, k, nprobe)
+                else:
+                    sc, local = shard.search(q_in, k)      # dicts_to_csr converts sparse keys / weights to int32 / float32
                 mapping = shard_rows if shard_rows is not None else self._main_rows
                 at = local + base
                 found = (local >= 0) & (at < len(mapping))
@@ -1490,12 +1646,13 @@ class GpuVectorStore(VectorStore):
             self._masks.clear()
 
     def _topk_rows(self, kind: str, queries: Sequence[Any], limit: int, mask: Optional[np.ndarray],
-                   _retry: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+                   _retry: int = 0, nprobe: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
         """Best `limit` rows per query among the rows that pass `mask`: `rows [Q, limit]` (-1 = no hit, tail only) and
         their fp32 scores.  One device pass for the whole batch over the full shard; queries that come up short because
         filtered / deleted rows took their slots (and every query when the filter passes under 1/8 of the rows) get a
         second pass over the masked subset shard -- or, with `filter_route="bitmap"`, the filtered search of the resident
-        shard (`_filtered_topk`; no subset shard is built in that mode).  Every branch below depends only on replicated state and on merged
+        shard (`_filtered_topk`; no subset shard is built in that mode).  `nprobe` (dense leg of an IVF_FLAT store): the full pass looks at the rows of that many
+        lists only (`_device_topk`); the second pass stays exact.  Every branch below depends only on replicated state and on merged
         results, so the ranks of a sharded store take the same path and meet in the same collectives."""
         if limit > self.K_LIMIT:
             raise ValueError(f"GpuVectorStore: a search may ask for at most {self.K_LIMIT} rows per method "
@@ -1513,9 +1670,9 @@ class GpuVectorStore(VectorStore):
         want = min(k, n_pass)
         short = np.ones(Q, dtype=bool)
         if mask is None or n_pass * 8 >= n:
-            scores, rows = self._device_topk(kind, parts, None, queries, k, rows_dev)
+            scores, rows = self._device_topk(kind, parts, None, queries, k, rows_dev, nprobe if kind == "dense" else None)
             if (rows >= n).any() and _retry < 3:      # rows inserted while this search ran took slots: search again
-                return self._topk_rows(kind, queries, limit, mask, _retry + 1)
+                return self._topk_rows(kind, queries, limit, mask, _retry + 1, nprobe)
             rows = np.where(rows < n, rows, -1)
             found = rows >= 0
             valid = found if mask is None else found & mask[np.where(found, rows, 0)]
@@ -1523,6 +1680,8 @@ class GpuVectorStore(VectorStore):
             # a sparse query can have fewer than `want` rows sharing a term: then the full pass, which returned fewer
             # than k candidates, has already seen every match
             done = (count >= want) | (found.sum(axis=1) < k) if mask is not None else np.ones(Q, dtype=bool)
+            if mask is not None and kind == "dense" and nprobe is not None:
+                done = count >= want                  # a short IVF list has not seen every row: the exact pass answers
             order = np.argsort(~valid, axis=1, kind="stable")                   # passing hits first, ranking kept
             rows_c = np.take_along_axis(rows, order, axis=1)
             scores_c = np.take_along_axis(scores, order, axis=1)
@@ -1628,8 +1787,10 @@ class GpuVectorStore(VectorStore):
         score_out[:] = np.where(found, scores, np.float32(0.0))
         return rows_out, score_out
 
-    def _search_batch(self, kind: str, queries: Sequence[Any], limit: int, mask: Optional[np.ndarray]) -> List[List[dict]]:
-        rows, scores = self._text_topk(queries, limit, mask) if kind == "full_text" else self._topk_rows(kind, queries, limit, mask)
+    def _search_batch(self, kind: str, queries: Sequence[Any], limit: int, mask: Optional[np.ndarray],
+                      nprobe: Optional[int] = None) -> List[List[dict]]:
+        rows, scores = (self._text_topk(queries, limit, mask) if kind == "full_text"
+                        else self._topk_rows(kind, queries, limit, mask, nprobe=nprobe))
         return [[self._hit(int(r), float(v)) for r, v in zip(rows[i], scores[i]) if r >= 0] for i in range(len(queries))]
 
     def _results_batch(self, rows: np.ndarray, distances: np.ndarray) -> List[List[SearchResult]]:
@@ -1639,7 +1800,8 @@ class GpuVectorStore(VectorStore):
         return [[SearchResult(id=ids[r], score=float(d), metadata=dict(pay[r][2]), text=pay[r][0], enhanced_text=pay[r][1])
                  for r, d in zip(rows[i].tolist(), distances[i].tolist()) if r >= 0] for i in range(rows.shape[0])]
 
-    def _hybrid_batch(self, queries: Dict[str, Sequence[Any]], top_k, mask, weights, rrf_k) -> List[List[SearchResult]]:
+    def _hybrid_batch(self, queries: Dict[str, Sequence[Any]], top_k, mask, weights, rrf_k,
+                      nprobe: Optional[int] = None) -> List[List[SearchResult]]:
         """Every method of `queries` (method -> the batch's queries, in fusion order) for all queries, 2 * top_k rows each,
         then weighted RRF: one array merge for the whole batch, or query by query when an id is falsy (such hits keep
         their rank but are skipped).  A failing full-text leg is left out with a warning, as in `_hybrid_search_with_weights`;
@@ -1648,7 +1810,7 @@ class GpuVectorStore(VectorStore):
         lists: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}
         for m, q in queries.items():
             if m != "full_text":
-                lists[m] = self._topk_rows(m, q, limit, mask)
+                lists[m] = self._topk_rows(m, q, limit, mask, nprobe=nprobe)
                 continue
             try:                                                   # as the per-query path (milvus_base.py:420-431)
                 lists[m] = self._text_topk(q, limit, mask)
@@ -1714,20 +1876,21 @@ class GpuVectorStore(VectorStore):
             if not weights or not uniform or not queries:
                 return [single(i) for i in range(n)]          # mixed / degenerate batches: the per-query code decides
             mask = self._mask(filter)
-            return self._hybrid_batch(queries, top_k, mask, weights, rrf_k)
+            return self._hybrid_batch(queries, top_k, mask, weights, rrf_k, self._nprobe_of(search_params))
         if search_type == "full_text" and self.enable_full_text and all(q for q in tq):
             mask = self._mask(filter)
             return self._results_batch(*self._text_topk(tq, top_k, mask))
         if search_type == "dense" and all(is_set(q) for q in dq):
             mask = self._mask(filter)
-            return self._results_batch(*self._topk_rows("dense", dq, top_k, mask))
+            return self._results_batch(*self._topk_rows("dense", dq, top_k, mask, nprobe=self._nprobe_of(search_params)))
         if search_type == "sparse" and all(is_set(q) for q in sq):
             mask = self._mask(filter)
             return self._results_batch(*self._topk_rows("sparse", sq, top_k, mask))
         if search_type == "hybrid" and all(is_set(q) for q in dq) and all(is_set(q) for q in sq):
             mask = self._mask(filter)
+            nprobe = self._nprobe_of(search_params)        # a bad nprobe is the caller's ValueError, not a failed batch
             try:
-                return self._hybrid_batch({"dense": dq, "sparse": sq}, top_k, mask, {"dense": 0.5, "sparse": 0.5}, rrf_k)
+                return self._hybrid_batch({"dense": dq, "sparse": sq}, top_k, mask, {"dense": 0.5, "sparse": 0.5}, rrf_k, nprobe)
             except Exception as e:
                 if self._world > 1:
                     raise                                  # ranks must not diverge into different collectives
@@ -1739,26 +1902,28 @@ class GpuVectorStore(VectorStore):
               hybrid_weights: Optional[Dict[str, float]] = None, rrf_k: int = 60) -> List[SearchResult]:
         """milvus_base.py:189-313.  `top_k` (2 * top_k in hybrid mode) may not exceed `K_LIMIT` = 1024."""
         if hybrid_weights is not None:
-            return self._hybrid_search_with_weights(dense_query, sparse_query, text_query, top_k, filter, hybrid_weights, rrf_k)
+            return self._hybrid_search_with_weights(dense_query, sparse_query, text_query, top_k, filter, hybrid_weights, rrf_k,
+                                                    self._nprobe_of(search_params))
         if search_type == "full_text" and text_query and self.enable_full_text:   # milvus_base.py:229-230
             return self._results(self._search("full_text", text_query, top_k, self._mask(filter)))
         if not _is_given(dense_query) and not _is_given(sparse_query):
             return self._filter_only_query(filter, top_k)
         mask = self._mask(filter)
+        nprobe = self._nprobe_of(search_params)
         if search_type == "dense" and _is_given(dense_query):
-            hits = self._search("dense", dense_query, top_k, mask)
+            hits = self._search("dense", dense_query, top_k, mask, nprobe)
         elif search_type == "sparse" and _is_given(sparse_query):
             hits = self._search("sparse", sparse_query, top_k, mask)
         elif search_type == "hybrid" and _is_given(dense_query) and _is_given(sparse_query):
             try:
-                rbm = {"dense": self._search("dense", dense_query, top_k * 2, mask),
+                rbm = {"dense": self._search("dense", dense_query, top_k * 2, mask, nprobe),
                        "sparse": self._search("sparse", sparse_query, top_k * 2, mask)}
                 hits = merge_hybrid_results(rbm, top_k, {"dense": 0.5, "sparse": 0.5}, rrf_k=rrf_k)
             except Exception as e:  # milvus_base.py:296-306
                 if self._world > 1:
                     raise
                 logger.warning("Hybrid search failed: %s, falling back to dense search", e)
-                hits = self._search("dense", dense_query, top_k, mask)
+                hits = self._search("dense", dense_query, top_k, mask, nprobe)
         else:
             raise ValueError(f"Invalid search configuration: type={search_type}, "
                              f"dense={dense_query is not None}, sparse={sparse_query is not None}")
@@ -1769,7 +1934,8 @@ class GpuVectorStore(VectorStore):
         rows = (np.arange(min(limit, len(self._ids))) if mask is None else np.nonzero(mask)[0][:limit]).astype(np.int64)
         return self._results_batch(rows[None, :], np.ones((1, len(rows))))[0]
 
-    def _hybrid_search_with_weights(self, dense_query, sparse_query, text_query, top_k, filter, hybrid_weights, rrf_k):
+    def _hybrid_search_with_weights(self, dense_query, sparse_query, text_query, top_k, filter, hybrid_weights, rrf_k,
+                                    nprobe: Optional[int] = None):
         """milvus_base.py:366-459."""
         hybrid_weights = sanitize_hybrid_weights(hybrid_weights)
         if "full_text" in hybrid_weights and not self.enable_full_text:
@@ -1780,7 +1946,7 @@ class GpuVectorStore(VectorStore):
         mask = self._mask(filter)
         rbm: Dict[str, List[dict]] = {}
         if "dense" in hybrid_weights and dense_query is not None:
-            rbm["dense"] = self._search("dense", dense_query, top_k * 2, mask)
+            rbm["dense"] = self._search("dense", dense_query, top_k * 2, mask, nprobe)
         if "sparse" in hybrid_weights and sparse_query is not None:
             rbm["sparse"] = self._search("sparse", sparse_query, top_k * 2, mask)
         if "full_text" in hybrid_weights and text_query is not None:           # milvus_base.py:420-431
@@ -1863,6 +2029,8 @@ class GpuVectorStore(VectorStore):
                     "enable_dense": self.enable_dense, "enable_sparse": self.enable_sparse, "dense_dtype": self.dense_dtype,
                     "dense_prefilter": self.dense_prefilter, "enable_full_text": self.enable_full_text, "bm25_k1": self.bm25_k1,
                     "bm25_b": self.bm25_b, "rows": len(ids), "documents": list(self._documents.values())}
+            if self.index_type != "FLAT":      # a FLAT store's manifest stays byte for byte what it was
+                head.update(index_type=self.index_type, nlist=self.nlist, nprobe=self.nprobe)
             r = self._rank
 
             def put_arrays(tmp):
@@ -1926,14 +2094,17 @@ class GpuVectorStore(VectorStore):
              payload: str = "sharded", filter_route: str = "subset", rrf_route: str = "host") -> "GpuVectorStore":
         """Reads a directory written by `save` -- by this or an earlier revision (formats 1 - 3), by any number of
         ranks: when the world size differs from the writer's, the saved shards are put back in row order and cut
-        contiguously over the ranks that open the store.  `filter_route`, `rrf_route`: as the constructor's (not part of a saved store)."""
+        contiguously over the ranks that open the store.  `filter_route`, `rrf_route`: as the constructor's (not part of a saved store).
+        An IVF_FLAT store comes back IVF_FLAT with its `nlist` / `nprobe`; its lists are trained again at the first flush
+        (training is deterministic: the same rows give the same lists)."""
         head, ids, shards = cls._read_saved(path)
         st = cls(dense_dim=head["dense_dim"], sparse_vocab=head["sparse_vocab"], enable_dense=head["enable_dense"],
                  enable_sparse=head["enable_sparse"], dense_dtype=head["dense_dtype"], device=device,
                  distributed=distributed, group=group, comm=comm, payload=payload,
                  dense_prefilter=head.get("dense_prefilter", "auto"), enable_full_text=bool(head.get("enable_full_text", False)),
                  bm25_k1=head.get("bm25_k1", 1.2), bm25_b=head.get("bm25_b", 0.75), filter_route=filter_route,
-                 rrf_route=rrf_route)
+                 rrf_route=rrf_route, index_type=head.get("index_type", "FLAT"), nlist=head.get("nlist", 8192),
+                 nprobe=head.get("nprobe", 16))
         n = len(ids)
         for owned, *_ in shards:
             if len(owned) and (owned.min() < 0 or owned.max() >= n):
