@@ -2,8 +2,8 @@
  * these entry points exist only in libvrag_amd_dbg.so, the harness build of the same sources (verbatim-rag_amd/build.py,
  * -DVRAG_DEBUG_API: it also keeps the phase-decomposition branches of the fused kernel that the product build compiles out).
  * tools/, tests/test_attention_unit_gpu.py, tests/test_attn_unit_gpu.py, tests/test_gemm_unit_gpu.py,
- * tests/test_qkv_attn_unit_gpu.py, tests/test_rows_unit_gpu.py, tests/test_glue_unit_gpu.py and tests/test_topk_unit_gpu.py
- * load it beside the product library. */
+ * tests/test_qkv_attn_unit_gpu.py, tests/test_rows_unit_gpu.py, tests/test_glue_unit_gpu.py, tests/test_topk_unit_gpu.py and
+ * tests/test_text_unit_gpu.py load it beside the product library. */
 #ifndef VRAG_AMD_DEBUG_H
 #define VRAG_AMD_DEBUG_H
 
@@ -345,6 +345,122 @@ typedef struct vrag_debug_topk_args {
   int32_t config[7];         /* out, score_stage: the tile configuration that ran: BM, BN, WM, WN, NS, HW, KCH */
 } vrag_debug_topk_args;
 int vrag_debug_topk_run(vrag_debug_topk_args* args, int32_t device);
+
+/* Unit-test hook of the full-text index build and BM25 scoring stages alone (csrc/fulltext.hip, which the harness build compiles
+ * with the hook in it), one stage per call, chosen by `op`.  Host buffers in; the hook calls the host launchers the product path
+ * calls (scan_u32, radix_passes, rle_count + rle_emit, expand_parts, stats_launch, lookup_launch, score_launch), so the kernels and
+ * grids are the product's; buffers marked "in / out" are copied to the device before the launches and back after them, so a
+ * canary survives where a kernel must not write.  Per-record, per-posting, per-key, per-row, per-term and candidate outputs are
+ * sized by a `*_buf` count >= the launch's count: what lies behind the launch's count is the caller's canary.
+ * Refused by the hook before anything is launched, each with its own message: a null required pointer; a count below 0 or above
+ * 2^22; a `*_buf` count below the count it covers; SORT with row_bits outside {0, 8, 16, 24, 32}; RLE with neither output form,
+ * with only one of ukeys / pstart, or with post_buf or keys_buf below n; n_segs outside 1..4; a segment whose pstart does not
+ * start at 0, decreases or does not end at its n_post, that has postings without keys, whose rows leave [row_lo, row_lo + n_rows)
+ * or are not strictly ascending within a key, or whose row range does not follow its predecessor's (the first starts at 0); FOLD
+ * with post_buf or keys_buf below the parts' postings; STATS / SCORE with segments reaching beyond n_rows; STATS with n_rows < 1,
+ * k1 < 0, b outside [0, 1] or a corpus pair with tokens but no rows; LOOKUP with n_terms < 1; SCORE with n_rows < 1, nq outside
+ * 1..65535, kk outside 1..64, q_indptr not from 0, decreasing or not ending at n_terms, a tu entry outside [-1, n_keys) (or not -1
+ * for a segment beyond n_segs), allow_rows outside [0, n_rows], cand_buf below blocks * nq * kk.
+ * Nothing the hook accepts reads or writes outside its buffers.  Index ranges per op (tile = 4 096):
+ *   SCAN     ceil(n / tile) workgroups (one for n = 0) read in[i], i < n (guarded); the tile sums are the launcher's own scratch;
+ *            write out[i], i <= n <= n_buf.
+ *   SORT     ceil(n / tile) workgroups per digit pass read key / row / tf[i], i < n (guarded), write the other record set at
+ *            pos < n (pos = a digit's scanned offset + rank: a permutation of 0..n-1); hist holds tiles * 256 words, offs one more.
+ *            8 passes by key, row_bits / 8 passes by row; n <= 1 launches nothing.
+ *   RLE      lane i < n reads key / row[i] and [i - 1] for i > 0; writes flags[i]; the scans write [0, n]; the scatter writes
+ *            prow / ptf / ppos / pkey[p], p = pscan[i] < n_post <= n <= post_buf, ukeys / pstart[u], u = kscan[i] < n_keys <= n <=
+ *            keys_buf; pstart[n_keys] is written by a copy; rle_tf reads ppos[p], ppos[p + 1] for p + 1 < n_post.
+ *   FOLD     expand: lane p < n_post of a part reads pstart[u], u < n_keys, ukeys[u], prow / ptf[p]; writes records at + p below the
+ *            sum of the parts' postings; then SORT by key and RLE (unit 0) over that many records.
+ *   STATS    lane r < n_rows reads live[r / 32], dl[r]; writes kd[r], r < n_rows <= rows_buf; acc[0..1] by atomics, the corpus pair
+ *            at acc[2..3]; df: wave u < n_keys reads pstart[u], pstart[u + 1], prow[p] with p below pstart[n_keys] = n_post, checked,
+ *            live[prow[p] / 32] with prow[p] < n_rows, checked; writes df[u].
+ *   LOOKUP   lane j < n_terms reads qkeys[j], keys[m] with m < n_keys and df[u], u < n_keys, of the segments below n_segs; writes
+ *            tu[j * 4 + s], s < 4, and df_out[j]: j < n_terms <= terms_buf.
+ *   SCORE    grid (ceil(n_rows / tile), nq).  Workgroup (blk, q) reads q_indptr[q], q_indptr[q + 1], tu / w[j] for j below
+ *            q_indptr[nq] = n_terms, checked; pstart[u], pstart[u + 1] with u = tu < n_keys, checked; prow / ptf[p] inside that
+ *            range; kd[row] and LDS acc[row - blk * tile] for rows of the block only (the bisection over strictly ascending rows,
+ *            checked); live[row / 32], row < n_rows; allow[row / 32] only where row < allow_rows <= n_rows; bound[q]; writes
+ *            cand[(blk * nq + q) * kk + i], i < kk: below blocks * nq * kk <= cand_buf.
+ * Every device buffer of the hook, inputs and scratch included, is followed by 4 KiB of canary; the hook fails with VRAG_ERR_HIP
+ * if a launch touched any.  (The tile sums inside scan_u32 are allocated by that launcher itself.) */
+enum {
+  VRAG_DEBUG_TEXT_SCAN = 0,
+  VRAG_DEBUG_TEXT_SORT = 1,
+  VRAG_DEBUG_TEXT_RLE = 2,
+  VRAG_DEBUG_TEXT_FOLD = 3,
+  VRAG_DEBUG_TEXT_STATS = 4,
+  VRAG_DEBUG_TEXT_LOOKUP = 5,
+  VRAG_DEBUG_TEXT_SCORE = 6
+};
+typedef struct vrag_debug_text_args {
+  const uint32_t* in;        /* scan [n] */
+  uint32_t* out;             /* in / out: scan [n_buf + 1] */
+  uint64_t* key;             /* sort: in / out [n]; rle: in [n] */
+  uint32_t* row;             /* the same */
+  uint32_t* tf;              /* the same */
+  uint64_t* ukeys;           /* in / out: rle (nullable: no segment form), fold [keys_buf] */
+  uint32_t* pstart;          /* in / out: rle (with ukeys), fold [keys_buf + 1] */
+  uint32_t* prow;            /* in / out: rle, fold [post_buf] */
+  uint32_t* ptf;             /* in / out: rle, fold [post_buf] */
+  uint64_t* pkey;            /* in / out: rle (nullable: no query form) [post_buf] */
+  const uint64_t* seg_keys[4];     /* fold, stats, lookup, score: [seg_n_keys] per segment */
+  const uint32_t* seg_pstart[4];   /* [seg_n_keys + 1] */
+  const uint32_t* seg_prow[4];     /* [seg_n_post] */
+  const uint32_t* seg_ptf[4];      /* [seg_n_post] */
+  uint32_t* seg_df[4];       /* stats: in / out [seg_n_keys]; lookup: in */
+  const uint32_t* dl;        /* stats [n_rows] */
+  const uint32_t* live;      /* stats, score [ceil(n_rows / 32)] */
+  const uint32_t* allow;     /* score [ceil(allow_rows / 32)], nullable */
+  uint64_t* acc;             /* out: stats [2] = {N, sum dl} */
+  float* kd;                 /* stats: in / out [rows_buf]; score: in [n_rows] */
+  const uint64_t* qkeys;     /* lookup [n_terms] */
+  int32_t* tu;               /* lookup: in / out [terms_buf][4]; score: in [n_terms][4] */
+  int64_t* df_out;           /* in / out: lookup [terms_buf], nullable */
+  const int64_t* q_indptr;   /* score [nq + 1] */
+  const float* w;            /* score [n_terms] */
+  const uint64_t* bound;     /* score [nq], nullable */
+  uint64_t* cand;            /* in / out: score [cand_buf] */
+  int64_t seg_n_keys[4], seg_n_post[4], seg_row_lo[4], seg_n_rows[4];
+  int64_t n, n_buf;          /* scan, sort, rle: elements / records; n_buf: scan only */
+  int64_t post_buf, keys_buf;
+  int64_t n_rows, rows_buf;
+  int64_t allow_rows;
+  int64_t n_terms, terms_buf;
+  int64_t cand_buf;
+  int64_t corpus_n, corpus_sum_dl;   /* stats: the corpus-wide pair K_d reads; corpus_n = 0 = none */
+  int64_t n_post, n_keys;    /* out: rle, fold */
+  int32_t op;
+  int32_t by_row, row_bits;  /* sort */
+  int32_t unit;              /* rle */
+  int32_t n_segs;
+  int32_t nq, kk;            /* score */
+  float k1, b;               /* stats */
+  float k1p1;                /* score: k1 + 1 */
+} vrag_debug_text_args;
+int vrag_debug_text_run(vrag_debug_text_args* args, int32_t device);
+
+/* The whole state of a text index created through THIS library's vrag_text_index_* functions, statistics refreshed first as a
+ * search refreshes them.  Two calls: with with_data = 0 only the sizes are written (n_segs, n_rows, n_live, sum_dl and the four
+ * per-segment counts); with with_data != 0 the caller passes the sizes back as it got them (refused if the index changed between
+ * the calls) and every non-null pointer receives its array: per segment keys [n_keys], pstart [n_keys + 1], prow, ptf [n_post],
+ * df [n_keys]; dl, kd [n_rows]; live [ceil(n_rows / 32)] (the device's bitmap, as the kernels read it). */
+typedef struct vrag_debug_text_index_state {
+  uint64_t* keys[2];
+  uint32_t* pstart[2];
+  uint32_t* prow[2];
+  uint32_t* ptf[2];
+  uint32_t* df[2];
+  uint32_t* dl;
+  float* kd;
+  uint32_t* live;
+  int64_t row_lo[2], seg_rows[2], n_keys[2], n_post[2];
+  int64_t n_rows, n_live, sum_dl;
+  int32_t n_segs;
+  int32_t with_data;
+} vrag_debug_text_index_state;
+struct vrag_text_index;
+int vrag_debug_text_index_read(struct vrag_text_index* ix, vrag_debug_text_index_state* state);
 
 #ifdef __cplusplus
 }

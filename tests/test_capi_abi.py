@@ -186,3 +186,15 @@ def test_debug_glue_args_layout_matches_ctypes(tmp_path):
 def test_debug_topk_args_layout_matches_ctypes(tmp_path):
     """The same for vrag_debug_topk_args and _lib.DebugTopkArgs (tests/test_topk_unit_gpu.py)."""
     _check_layout(tmp_path, "vrag_debug_topk_args", _lib.DebugTopkArgs)
+
+
+@pytest.mark.skipif(_host_cc() is None, reason="no host C compiler")
+def test_debug_text_args_layout_matches_ctypes(tmp_path):
+    """The same for vrag_debug_text_args and _lib.DebugTextArgs (tests/test_text_unit_gpu.py)."""
+    _check_layout(tmp_path, "vrag_debug_text_args", _lib.DebugTextArgs)
+
+
+@pytest.mark.skipif(_host_cc() is None, reason="no host C compiler")
+def test_debug_text_index_state_layout_matches_ctypes(tmp_path):
+    """The same for vrag_debug_text_index_state and _lib.DebugTextIndexState (tests/test_text_unit_gpu.py)."""
+    _check_layout(tmp_path, "vrag_debug_text_index_state", _lib.DebugTextIndexState)

@@ -190,6 +190,8 @@ DEBUG_SIGNATURES = {
     "vrag_debug_rows_run": (C.c_int, [C.c_void_p, C.c_int32]),
     "vrag_debug_glue_run": (C.c_int, [C.c_void_p, C.c_int32]),
     "vrag_debug_topk_run": (C.c_int, [C.c_void_p, C.c_int32]),
+    "vrag_debug_text_run": (C.c_int, [C.c_void_p, C.c_int32]),
+    "vrag_debug_text_index_read": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 
@@ -257,6 +259,31 @@ class DebugTopkArgs(C.Structure):
 
 
 DEBUG_TOPK_OPS = {"score_stage": 0, "queries": 1, "select": 2, "select_direct": 3, "rescue": 4, "merge": 5, "tau": 6}
+
+
+
+class DebugTextArgs(C.Structure):
+    """vrag_debug_text_args (include/vrag_amd_debug.h), field for field; tests/test_capi_abi.py checks the layout too."""
+    _fields_ = [(n, C.c_void_p) for n in ("in", "out", "key", "row", "tf", "ukeys", "pstart", "prow", "ptf", "pkey")] + [
+        (n, C.c_void_p * 4) for n in ("seg_keys", "seg_pstart", "seg_prow", "seg_ptf", "seg_df")] + [
+        (n, C.c_void_p) for n in ("dl", "live", "allow", "acc", "kd", "qkeys", "tu", "df_out", "q_indptr", "w", "bound", "cand")] + [
+        (n, C.c_int64 * 4) for n in ("seg_n_keys", "seg_n_post", "seg_row_lo", "seg_n_rows")] + [
+        (n, C.c_int64) for n in ("n", "n_buf", "post_buf", "keys_buf", "n_rows", "rows_buf", "allow_rows", "n_terms", "terms_buf",
+                                 "cand_buf", "corpus_n", "corpus_sum_dl", "n_post", "n_keys")] + [
+        (n, C.c_int32) for n in ("op", "by_row", "row_bits", "unit", "n_segs", "nq", "kk")] + [
+        ("k1", C.c_float), ("b", C.c_float), ("k1p1", C.c_float)]
+
+
+DEBUG_TEXT_OPS = {"scan": 0, "sort": 1, "rle": 2, "fold": 3, "stats": 4, "lookup": 5, "score": 6}
+
+
+class DebugTextIndexState(C.Structure):
+    """vrag_debug_text_index_state (include/vrag_amd_debug.h), field for field; tests/test_capi_abi.py checks the layout too."""
+    _fields_ = [(n, C.c_void_p * 2) for n in ("keys", "pstart", "prow", "ptf", "df")] + [
+        (n, C.c_void_p) for n in ("dl", "kd", "live")] + [
+        (n, C.c_int64 * 2) for n in ("row_lo", "seg_rows", "n_keys", "n_post")] + [
+        (n, C.c_int64) for n in ("n_rows", "n_live", "sum_dl")] + [("n_segs", C.c_int32), ("with_data", C.c_int32)]
+
 
 _DBG = None
 

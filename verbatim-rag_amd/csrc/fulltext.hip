@@ -596,30 +596,57 @@ struct Records {
   }
 };
 
+// Three record arrays as raw device pointers (n elements each).
+struct RecPtrs {
+  u64* key;
+  unsigned* row;
+  unsigned* tf;
+};
+
+inline int radix_tiles(long long n) { return (int)((n + RS_TILE - 1) / RS_TILE); }
+
+// The digit passes of the sort on raw arrays: pass after pass from `a` into `b` and back; hist holds radix_tiles(n) * 256
+// words, offs one more.  *in_b = the sorted records ended in `b` (an odd number of passes).  n <= 1: nothing is launched.
+hipError_t radix_passes(RecPtrs a, RecPtrs b, long long n, int by_row, int row_bits, unsigned* hist, unsigned* offs, hipStream_t st,
+                        bool* in_b) {
+  *in_b = false;
+  if (n <= 1) return hipSuccess;
+  const int n_tiles = radix_tiles(n);
+  hipError_t e;
+  const int bits = by_row ? row_bits : 64;
+  for (int shift = 0; shift < bits; shift += 8) {
+    hipLaunchKernelGGL(radix_hist_kernel, dim3(n_tiles), dim3(RS_NT), 0, st, a.key, a.row, n, by_row, shift, hist, n_tiles);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = scan_u32(hist, (long long)n_tiles * 256, offs, st)) != hipSuccess) return e;
+    hipLaunchKernelGGL(radix_scatter_kernel, dim3(n_tiles), dim3(RS_NT), 0, st, a.key, a.row, a.tf, n, by_row, shift, offs, n_tiles,
+                       b.key, b.row, b.tf);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    std::swap(a, b);
+    *in_b = !*in_b;
+  }
+  return hipStreamSynchronize(st);
+}
+
 // Stable sort of the records by key (by_row = 0: 8 passes) or by row (passes over the bits below 2^row_bits).
 hipError_t radix_sort(Records& r, int by_row, int row_bits, hipStream_t st) {
   if (r.n <= 1) return hipSuccess;
-  const int n_tiles = (int)((r.n + RS_TILE - 1) / RS_TILE);
+  const int n_tiles = radix_tiles(r.n);
   Records tmp;
   DevBuf hist, offs;
   hipError_t e = tmp.alloc(r.n);
   if (e == hipSuccess) e = hist.alloc((size_t)n_tiles * 256 * 4);
   if (e == hipSuccess) e = offs.alloc(((size_t)n_tiles * 256 + 1) * 4);
   if (e != hipSuccess) return e;
-  const int bits = by_row ? row_bits : 64;
-  for (int shift = 0; shift < bits; shift += 8) {
-    hipLaunchKernelGGL(radix_hist_kernel, dim3(n_tiles), dim3(RS_NT), 0, st, r.key.as<u64>(), r.row.as<unsigned>(), r.n, by_row, shift,
-                       hist.as<unsigned>(), n_tiles);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = scan_u32(hist.as<unsigned>(), (long long)n_tiles * 256, offs.as<unsigned>(), st)) != hipSuccess) return e;
-    hipLaunchKernelGGL(radix_scatter_kernel, dim3(n_tiles), dim3(RS_NT), 0, st, r.key.as<u64>(), r.row.as<unsigned>(), r.tf.as<unsigned>(),
-                       r.n, by_row, shift, offs.as<unsigned>(), n_tiles, tmp.key.as<u64>(), tmp.row.as<unsigned>(), tmp.tf.as<unsigned>());
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+  bool in_tmp = false;
+  e = radix_passes(RecPtrs{r.key.as<u64>(), r.row.as<unsigned>(), r.tf.as<unsigned>()},
+                   RecPtrs{tmp.key.as<u64>(), tmp.row.as<unsigned>(), tmp.tf.as<unsigned>()}, r.n, by_row, row_bits, hist.as<unsigned>(),
+                   offs.as<unsigned>(), st, &in_tmp);
+  if (in_tmp) {
     std::swap(r.key, tmp.key);
     std::swap(r.row, tmp.row);
     std::swap(r.tf, tmp.tf);
   }
-  return hipStreamSynchronize(st);
+  return e;
 }
 
 // Run-length encoding of records sorted by (key, row).  Segment form (seg != null): unique keys, posting ranges, postings;
@@ -628,6 +655,37 @@ struct Runs {
   long long n_post = 0, n_keys = 0;
   DevBuf prow, ptf, pkey;
 };
+
+// The scratch of one run-length encoding of n records: flags [n] and their exclusive scans [n + 1].
+struct RleScratch {
+  unsigned *pflag, *kflag, *pscan, *kscan;
+};
+
+// First half on raw arrays: the flags, their scans, and the counts the outputs are sized by.
+hipError_t rle_count(RecPtrs r, long long n, RleScratch s, unsigned* n_post, unsigned* n_keys, hipStream_t st) {
+  hipError_t e;
+  if (n) hipLaunchKernelGGL(rle_flags_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, r.key, r.row, n, s.pflag, s.kflag);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = scan_u32(s.pflag, n, s.pscan, st)) != hipSuccess) return e;
+  if ((e = scan_u32(s.kflag, n, s.kscan, st)) != hipSuccess) return e;
+  if ((e = read_u32(s.pscan + n, n_post, st)) != hipSuccess) return e;
+  return read_u32(s.kscan + n, n_keys, st);
+}
+
+// Second half: prow, ptf, ppos [n_post]; pkey [n_post] or null; ukeys [n_keys] and pstart [n_keys + 1], both or neither.
+// *n_post_p is copied to pstart[n_keys] on the stream: it must stay where it is until the caller has synchronised.
+hipError_t rle_emit(RecPtrs r, long long n, RleScratch s, int unit, const unsigned* n_post_p, unsigned n_keys, u64* ukeys,
+                    unsigned* pstart, unsigned* prow, unsigned* ptf, unsigned* ppos, u64* pkey, hipStream_t st) {
+  const unsigned n_post = *n_post_p;
+  if (n)
+    hipLaunchKernelGGL(rle_scatter_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, r.key, r.row, r.tf, n, s.pflag, s.pscan, s.kflag,
+                       s.kscan, unit, ukeys, pstart, prow, ptf, ppos, pkey);
+  if (unit && n_post) hipLaunchKernelGGL(rle_tf_kernel, dim3(grid_of(n_post, 256)), dim3(256), 0, st, ppos, (long long)n_post, n, ptf);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && pstart) e = hipMemcpyAsync(pstart + n_keys, n_post_p, 4, hipMemcpyHostToDevice, st);
+  return e;
+}
+
 hipError_t rle(const Records& r, int unit, Segment* seg, Runs* runs, hipStream_t st) {
   DevBuf pflag, kflag, pscan, kscan, ppos;
   hipError_t e = pflag.alloc((size_t)r.n * 4);
@@ -635,14 +693,10 @@ hipError_t rle(const Records& r, int unit, Segment* seg, Runs* runs, hipStream_t
   if (e == hipSuccess) e = pscan.alloc((size_t)(r.n + 1) * 4);
   if (e == hipSuccess) e = kscan.alloc((size_t)(r.n + 1) * 4);
   if (e != hipSuccess) return e;
-  if (r.n) hipLaunchKernelGGL(rle_flags_kernel, dim3(grid_of(r.n, 256)), dim3(256), 0, st, r.key.as<u64>(), r.row.as<unsigned>(), r.n,
-                              pflag.as<unsigned>(), kflag.as<unsigned>());
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  if ((e = scan_u32(pflag.as<unsigned>(), r.n, pscan.as<unsigned>(), st)) != hipSuccess) return e;
-  if ((e = scan_u32(kflag.as<unsigned>(), r.n, kscan.as<unsigned>(), st)) != hipSuccess) return e;
+  const RecPtrs rec{r.key.as<u64>(), r.row.as<unsigned>(), r.tf.as<unsigned>()};
+  const RleScratch scr{pflag.as<unsigned>(), kflag.as<unsigned>(), pscan.as<unsigned>(), kscan.as<unsigned>()};
   unsigned n_post = 0, n_keys = 0;
-  if ((e = read_u32(pscan.as<unsigned>() + r.n, &n_post, st)) != hipSuccess) return e;
-  if ((e = read_u32(kscan.as<unsigned>() + r.n, &n_keys, st)) != hipSuccess) return e;
+  if ((e = rle_count(rec, r.n, scr, &n_post, &n_keys, st)) != hipSuccess) return e;
   DevBuf prow, ptf, pkey, ukeys, pstart;
   e = prow.alloc((size_t)n_post * 4);
   if (e == hipSuccess) e = ptf.alloc((size_t)n_post * 4);
@@ -651,17 +705,10 @@ hipError_t rle(const Records& r, int unit, Segment* seg, Runs* runs, hipStream_t
   if (e == hipSuccess && seg) e = ukeys.alloc((size_t)n_keys * 8);
   if (e == hipSuccess && seg) e = pstart.alloc((size_t)(n_keys + 1) * 4);
   if (e != hipSuccess) return e;
-  if (r.n)
-    hipLaunchKernelGGL(rle_scatter_kernel, dim3(grid_of(r.n, 256)), dim3(256), 0, st, r.key.as<u64>(), r.row.as<unsigned>(),
-                       r.tf.as<unsigned>(), r.n, pflag.as<unsigned>(), pscan.as<unsigned>(), kflag.as<unsigned>(), kscan.as<unsigned>(),
-                       unit, seg ? ukeys.as<u64>() : nullptr, seg ? pstart.as<unsigned>() : nullptr, prow.as<unsigned>(),
-                       ptf.as<unsigned>(), ppos.as<unsigned>(), runs ? pkey.as<u64>() : nullptr);
-  if (unit && n_post)
-    hipLaunchKernelGGL(rle_tf_kernel, dim3(grid_of(n_post, 256)), dim3(256), 0, st, ppos.as<unsigned>(), (long long)n_post, r.n,
-                       ptf.as<unsigned>());
-  if ((e = hipGetLastError()) != hipSuccess) return e;
+  if ((e = rle_emit(rec, r.n, scr, unit, &n_post, n_keys, seg ? ukeys.as<u64>() : nullptr, seg ? pstart.as<unsigned>() : nullptr,
+                    prow.as<unsigned>(), ptf.as<unsigned>(), ppos.as<unsigned>(), runs ? pkey.as<u64>() : nullptr, st)) != hipSuccess)
+    return e;
   if (seg) {
-    if ((e = hipMemcpyAsync(pstart.as<unsigned>() + n_keys, &n_post, 4, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
     seg->n_keys = n_keys;
     seg->n_post = n_post;
     seg->keys = std::move(ukeys);
@@ -744,15 +791,33 @@ struct vrag_text_index {
 
 namespace {
 
-FtSegs seg_view(const vrag_text_index* ix) {
+// A segment as raw device pointers.
+struct SegPtrs {
+  u64* keys;
+  unsigned *pstart, *prow, *ptf, *df;
+  long long n_keys, n_post, row_lo, n_rows;
+};
+
+SegPtrs ptrs_of(const Segment& g) {
+  return SegPtrs{g.keys.as<u64>(), g.pstart.as<unsigned>(), g.prow.as<unsigned>(), g.ptf.as<unsigned>(), g.df.as<unsigned>(),
+                 g.n_keys, g.n_post, g.row_lo, g.n_rows};
+}
+
+FtSegs seg_view(const SegPtrs* segs, int n) {
   FtSegs v{};
-  v.n = (int)ix->segs.size();
-  for (int s = 0; s < v.n; ++s) {
-    const Segment& g = ix->segs[s];
-    v.s[s] = FtSeg{g.keys.as<u64>(), g.pstart.as<unsigned>(), g.prow.as<unsigned>(), g.ptf.as<unsigned>(), g.df.as<unsigned>(),
-                   g.n_keys, g.row_lo, g.row_lo + g.n_rows};
+  v.n = n;
+  for (int s = 0; s < n; ++s) {
+    const SegPtrs& g = segs[s];
+    v.s[s] = FtSeg{g.keys, g.pstart, g.prow, g.ptf, g.df, g.n_keys, g.row_lo, g.row_lo + g.n_rows};
   }
   return v;
+}
+
+FtSegs seg_view(const vrag_text_index* ix) {
+  SegPtrs p[FT_MAXSEG];
+  const int n = (int)ix->segs.size();
+  for (int s = 0; s < n; ++s) p[s] = ptrs_of(ix->segs[s]);
+  return seg_view(p, n);
 }
 
 // Segment of the sorted records (records sorted by key, rows ascending within a key).
@@ -765,21 +830,29 @@ int build_segment(Records& rec, int unit, long long row_lo, long long n_rows, hi
 }
 
 // One segment holding the postings of `parts` (consecutive row ranges): their records in row order, sorted stably by key.
+// The postings of the parts, part after part, back into records (rec holds the sum of their n_post).
+hipError_t expand_parts(const SegPtrs* parts, int n_parts, RecPtrs rec, hipStream_t st) {
+  long long at = 0;
+  for (int i = 0; i < n_parts; ++i) {
+    const SegPtrs& g = parts[i];
+    if (g.n_post)
+      hipLaunchKernelGGL(expand_kernel, dim3(grid_of(g.n_post, 256)), dim3(256), 0, st, g.keys, g.pstart, g.n_keys, g.prow, g.ptf, g.n_post,
+                         rec.key + at, rec.row + at, rec.tf + at);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    at += g.n_post;
+  }
+  return hipSuccess;
+}
+
 int fold(const std::vector<const Segment*>& parts, hipStream_t st, Segment& out) {
   long long total = 0;
   for (const Segment* g : parts) total += g->n_post;
   Records rec;
   HIP_TRY(rec.alloc(total));
-  long long at = 0;
-  for (const Segment* gp : parts) {
-    const Segment& g = *gp;
-    if (g.n_post)
-      hipLaunchKernelGGL(expand_kernel, dim3(grid_of(g.n_post, 256)), dim3(256), 0, st, g.keys.as<u64>(), g.pstart.as<unsigned>(), g.n_keys,
-                         g.prow.as<unsigned>(), g.ptf.as<unsigned>(), g.n_post, rec.key.as<u64>() + at, rec.row.as<unsigned>() + at,
-                         rec.tf.as<unsigned>() + at);
-    HIP_TRY(hipGetLastError());
-    at += g.n_post;
-  }
+  std::vector<SegPtrs> raw;
+  for (const Segment* g : parts) raw.push_back(ptrs_of(*g));
+  HIP_TRY(expand_parts(raw.data(), (int)raw.size(), RecPtrs{rec.key.as<u64>(), rec.row.as<unsigned>(), rec.tf.as<unsigned>()}, st));
   const long long row_lo = parts.front()->row_lo;
   const long long n_rows = parts.back()->row_lo + parts.back()->n_rows - row_lo;
   return build_segment(rec, 0, row_lo, n_rows, st, out);
@@ -787,6 +860,22 @@ int fold(const std::vector<const Segment*>& parts, hipStream_t st, Segment& out)
 
 // The statistics pass.  stats_dirty: N / sum dl / df of this index's live rows and K_d; kd_dirty alone (the caller's
 // corpus-wide pair changed): K_d only.  K_d reads {N, sum dl} from acc[0..1], or from the caller's pair at acc[2..3].
+// The launches of the statistics pass on raw arrays.  own: N / sum dl into acc[0..1] (zeroed by the caller) and df of every
+// segment with keys; K_d of the n rows always, from the pair at kd_stats.
+hipError_t stats_launch(const unsigned* live, const unsigned* dl, long long n, bool own, unsigned long long* acc,
+                        const unsigned long long* kd_stats, float k1, float b, float* kd, const SegPtrs* segs, int n_segs, hipStream_t st) {
+  if (own) hipLaunchKernelGGL(live_sum_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, live, dl, n, acc);
+  hipLaunchKernelGGL(kd_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, dl, n, kd_stats, k1, 1.0f - b, b, kd);
+  if (own)
+    for (int s = 0; s < n_segs; ++s) {
+      const SegPtrs& g = segs[s];
+      if (g.n_keys)
+        hipLaunchKernelGGL(df_kernel, dim3((unsigned)std::min<long long>(4096, (g.n_keys + 3) / 4)), dim3(256), 0, st, g.pstart, g.n_keys,
+                           g.prow, live, g.df);
+    }
+  return hipGetLastError();
+}
+
 int refresh_stats(vrag_text_index* ix) {
   if (!ix->stats_dirty && !ix->kd_dirty) return VRAG_OK;
   hipStream_t st = ix->stream;
@@ -800,19 +889,12 @@ int refresh_stats(vrag_text_index* ix) {
     kd_stats += 2;
   }
   if (n) {
-    if (own) {
-      HIP_TRY(hipMemcpyAsync(ix->live.p, ix->h_live.data(), ix->h_live.size() * 4, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(live_sum_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, ix->live.as<unsigned>(), ix->dl.as<unsigned>(), n,
-                         ix->acc.as<unsigned long long>());
-    }
-    hipLaunchKernelGGL(kd_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, ix->dl.as<unsigned>(), n, kd_stats, ix->k1,
-                       1.0f - ix->b, ix->b, ix->kd.as<float>());
-    if (own)
-      for (const Segment& g : ix->segs)
-        if (g.n_keys)
-          hipLaunchKernelGGL(df_kernel, dim3((unsigned)std::min<long long>(4096, (g.n_keys + 3) / 4)), dim3(256), 0, st, g.pstart.as<unsigned>(),
-                             g.n_keys, g.prow.as<unsigned>(), ix->live.as<unsigned>(), g.df.as<unsigned>());
-    HIP_TRY(hipGetLastError());
+    if (own) HIP_TRY(hipMemcpyAsync(ix->live.p, ix->h_live.data(), ix->h_live.size() * 4, hipMemcpyHostToDevice, st));
+    SegPtrs segs[FT_MAXSEG];
+    const int n_segs = (int)ix->segs.size();
+    for (int s = 0; s < n_segs; ++s) segs[s] = ptrs_of(ix->segs[s]);
+    HIP_TRY(stats_launch(ix->live.as<unsigned>(), ix->dl.as<unsigned>(), n, own, ix->acc.as<unsigned long long>(), kd_stats, ix->k1, ix->b,
+                         ix->kd.as<float>(), segs, n_segs, st));
   }
   if (own) HIP_TRY(hipMemcpyAsync(ix->h_acc, ix->acc.p, 16, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -882,20 +964,34 @@ int search_upload(vrag_text_index* ix, const int64_t* q_indptr, const uint64_t* 
 
 // The kernels of one search on the uploaded batch: term lookup, then per page of 64 the scoring pass and the per-query merge;
 // page p of the result is ix->page[p][nq][min(k, 64)] (keys, 0 = none).
+inline int score_blocks(long long n_rows) { return (int)((n_rows + FT_ROWS - 1) / FT_ROWS); }
+
+// Term lookup on raw arrays: tu[n_terms][FT_MAXSEG], df_out [n_terms] or null.
+hipError_t lookup_launch(const FtSegs& segs, const u64* keys, long long n_terms, int* tu, long long* df_out, hipStream_t st) {
+  hipLaunchKernelGGL(ft_lookup_kernel, dim3(grid_of(n_terms, 256)), dim3(256), 0, st, segs, keys, n_terms, tu, df_out);
+  return hipGetLastError();
+}
+
+// One page of the scoring pass on raw arrays: cand[score_blocks(n_rows)][nq][kk].
+hipError_t score_launch(const FtSegs& segs, const long long* q_indptr, const int* tu, const float* w, const float* kd, const unsigned* live,
+                        const unsigned* allow, long long allow_n, long long n_rows, float k1p1, int nq, int kk, const u64* bound, u64* cand,
+                        hipStream_t st) {
+  hipLaunchKernelGGL(ft_score_kernel, dim3(score_blocks(n_rows), nq), dim3(FT_NT), 0, st, segs, q_indptr, tu, w, kd, live, allow, allow_n,
+                     n_rows, k1p1, nq, kk, bound, cand);
+  return hipGetLastError();
+}
+
 int search_launch(vrag_text_index* ix, int32_t nq, int64_t n_terms, int32_t k, const unsigned* d_allow, long long allow_n, hipStream_t st) {
-  const int n_blocks = (int)((ix->n_rows + FT_ROWS - 1) / FT_ROWS);
+  const int n_blocks = score_blocks(ix->n_rows);
   const int kk = std::min(k, 64), pages = (k + 63) / 64;
   const FtSegs segs = seg_view(ix);
-  hipLaunchKernelGGL(ft_lookup_kernel, dim3(grid_of(n_terms, 256)), dim3(256), 0, st, segs, ix->q_keys.as<u64>(), (long long)n_terms,
-                     ix->q_tu.as<int>(), (long long*)nullptr);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(lookup_launch(segs, ix->q_keys.as<u64>(), (long long)n_terms, ix->q_tu.as<int>(), nullptr, st));
   const float k1p1 = ix->k1 + 1.0f;
   for (int p = 0; p < pages; ++p) {
     u64* page = ix->page.as<u64>() + (size_t)p * nq * kk;
-    hipLaunchKernelGGL(ft_score_kernel, dim3(n_blocks, nq), dim3(FT_NT), 0, st, segs, ix->q_indptr.as<long long>(), ix->q_tu.as<int>(),
-                       ix->q_w.as<float>(), ix->kd.as<float>(), ix->live.as<unsigned>(), d_allow, allow_n, ix->n_rows, k1p1, nq, kk,
-                       p ? ix->bound.as<u64>() : nullptr, ix->cand.as<u64>());
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(score_launch(segs, ix->q_indptr.as<long long>(), ix->q_tu.as<int>(), ix->q_w.as<float>(), ix->kd.as<float>(),
+                         ix->live.as<unsigned>(), d_allow, allow_n, ix->n_rows, k1p1, nq, kk, p ? ix->bound.as<u64>() : nullptr,
+                         ix->cand.as<u64>(), st));
     HIP_TRY(launch_topk_merge(ix->cand.as<u64>(), n_blocks, nq, kk, page, st));
     if (p + 1 < pages) hipLaunchKernelGGL(ft_bound_kernel, dim3(grid_of(nq, 256)), dim3(256), 0, st, page, nq, kk, ix->bound.as<u64>());
     HIP_TRY(hipGetLastError());
@@ -1086,9 +1182,7 @@ int vrag_text_index_query_terms(vrag_text_index* ix, const uint8_t* text, const 
   DevBuf tu, d_df;
   HIP_TRY(tu.alloc((size_t)P * FT_MAXSEG * 4));
   HIP_TRY(d_df.alloc((size_t)P * 8));
-  hipLaunchKernelGGL(ft_lookup_kernel, dim3(grid_of(P, 256)), dim3(256), 0, st, seg_view(ix), runs.pkey.as<u64>(), P, tu.as<int>(),
-                     d_df.as<long long>());
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(lookup_launch(seg_view(ix), runs.pkey.as<u64>(), P, tu.as<int>(), d_df.as<long long>(), st));
   std::vector<unsigned> qrow((size_t)P), tf((size_t)P);
   HIP_TRY(hipMemcpyAsync(qrow.data(), runs.prow.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(tf.data(), runs.ptf.p, (size_t)P * 4, hipMemcpyDeviceToHost, st));
@@ -1179,3 +1273,364 @@ int vrag_text_index_search_device(vrag_text_index* ix, const int64_t* q_indptr, 
 }
 
 }  // extern "C"
+
+#ifdef VRAG_DEBUG_API
+// ------------------------------------------------------------------------------------ unit-test hook (harness build only)
+#include <deque>
+
+#include "../../include/vrag_amd_debug.h"
+
+namespace {
+
+constexpr size_t kDbgCanary = 4096;
+constexpr unsigned char kDbgCanaryByte = 0xA5;
+constexpr long long kDbgMax = 1ll << 22;   // every count of the hook: sizes and u32 offsets stay far inside their types
+
+// Device copies of the hook's buffers, each followed by a canary the launches must leave as it was.
+struct DbgBufs {
+  struct B {
+    void* host_out;   // null = nothing is copied back
+    size_t bytes;
+    const char* name;
+    DevBuf dev;
+  };
+  std::deque<B> bufs;
+  hipError_t err = hipSuccess;
+  // `bytes` from host (null = zeros), copied back to host_out (nullable) by finish()
+  template <typename T>
+  T* add(const void* host, void* host_out, size_t bytes, const char* name) {
+    bufs.push_back(B{host_out, bytes, name, DevBuf()});
+    B& b = bufs.back();
+    if (err == hipSuccess) err = b.dev.alloc(bytes + kDbgCanary);
+    if (err == hipSuccess && bytes) err = host ? hipMemcpy(b.dev.p, host, bytes, hipMemcpyHostToDevice) : hipMemset(b.dev.p, 0, bytes);
+    if (err == hipSuccess) err = hipMemset(b.dev.as<char>() + bytes, kDbgCanaryByte, kDbgCanary);
+    return b.dev.as<T>();
+  }
+  template <typename T>
+  T* in(const void* host, size_t count, const char* name) { return add<T>(host, nullptr, count * sizeof(T), name); }
+  template <typename T>
+  T* inout(void* host, size_t count, const char* name) { return add<T>(host, host, count * sizeof(T), name); }
+  template <typename T>
+  T* scratch(size_t count, const char* name) { return add<T>(nullptr, nullptr, count * sizeof(T), name); }
+  // after the launches (e = their status): canaries checked, in / out buffers copied back
+  int finish(hipError_t e) {
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    std::vector<unsigned char> canary(kDbgCanary);
+    const char* clobbered = nullptr;
+    for (B& b : bufs) {
+      if (e != hipSuccess) break;
+      e = hipMemcpy(canary.data(), b.dev.as<char>() + b.bytes, kDbgCanary, hipMemcpyDeviceToHost);
+      if (e == hipSuccess && !clobbered && !std::all_of(canary.begin(), canary.end(), [](unsigned char v) { return v == kDbgCanaryByte; }))
+        clobbered = b.name;
+      if (e == hipSuccess && b.host_out && b.bytes) e = hipMemcpy(b.host_out, b.dev.p, b.bytes, hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) {
+      set_error("debug text run failed: %s", hipGetErrorString(e));
+      return VRAG_ERR_HIP;
+    }
+    if (clobbered) {
+      set_error("debug text run: the launch wrote past the end of %s", clobbered);
+      return VRAG_ERR_HIP;
+    }
+    return VRAG_OK;
+  }
+};
+
+// The segments of the argument block as the kernels must find them (see the header); rows_total < 0 = no bound on the rows.
+int dbg_check_segs(const vrag_debug_text_args* a, bool need_ptf, bool need_df, long long rows_total) {
+  ARG_CHECK(a->n_segs >= 1 && a->n_segs <= FT_MAXSEG, "n_segs (%d) must be in 1..%d", a->n_segs, FT_MAXSEG);
+  long long next_row = 0;
+  for (int s = 0; s < a->n_segs; ++s) {
+    const long long nk = a->seg_n_keys[s], np = a->seg_n_post[s], lo = a->seg_row_lo[s], nr = a->seg_n_rows[s];
+    ARG_CHECK(nk >= 0 && nk <= kDbgMax && np >= 0 && np <= kDbgMax && nr >= 0 && nr <= kDbgMax, "segment %d: a count is negative or above 2^22", s);
+    ARG_CHECK(lo == next_row, "segment %d: row_lo (%lld) does not follow its predecessor (%lld)", s, lo, next_row);
+    next_row = lo + nr;
+    ARG_CHECK(rows_total < 0 || next_row <= rows_total, "segment %d reaches row %lld of %lld", s, next_row, rows_total);
+    ARG_CHECK(a->seg_pstart[s] && (nk == 0 || a->seg_keys[s]) && (np == 0 || (a->seg_prow[s] && (!need_ptf || a->seg_ptf[s]))) &&
+                  (!need_df || nk == 0 || a->seg_df[s]),
+              "segment %d: null array", s);
+    ARG_CHECK(nk > 0 || np == 0, "segment %d: %lld postings without a key", s, np);
+    const uint32_t* ps = a->seg_pstart[s];
+    ARG_CHECK(ps[0] == 0u, "segment %d: pstart[0] = %u", s, ps[0]);
+    ARG_CHECK((long long)ps[nk] == np, "segment %d: pstart[n_keys] = %u, n_post = %lld", s, ps[nk], np);
+    for (long long u = 0; u < nk; ++u) {
+      ARG_CHECK(ps[u] <= ps[u + 1] && (long long)ps[u + 1] <= np, "segment %d: pstart decreases or leaves the postings at key %lld", s, u);
+      for (uint32_t p = ps[u]; p < ps[u + 1]; ++p) {
+        const long long r = a->seg_prow[s][p];
+        ARG_CHECK(r >= lo && r < lo + nr, "segment %d: posting %u has row %lld outside [%lld, %lld)", s, p, r, lo, lo + nr);
+        ARG_CHECK(p == ps[u] || a->seg_prow[s][p - 1] < a->seg_prow[s][p], "segment %d: the rows of key %lld are not strictly ascending", s, u);
+      }
+    }
+  }
+  return VRAG_OK;
+}
+
+// Device copies of the segments; df_out: df goes back to the caller (STATS).
+void dbg_stage_segs(const vrag_debug_text_args* a, DbgBufs& B, bool df_out, SegPtrs* segs) {
+  for (int s = 0; s < a->n_segs; ++s) {
+    const size_t nk = (size_t)a->seg_n_keys[s], np = (size_t)a->seg_n_post[s];
+    SegPtrs& g = segs[s];
+    g.keys = B.in<u64>(a->seg_keys[s], a->seg_keys[s] ? nk : 0, "seg_keys");
+    g.pstart = B.in<unsigned>(a->seg_pstart[s], nk + 1, "seg_pstart");
+    g.prow = B.in<unsigned>(a->seg_prow[s], a->seg_prow[s] ? np : 0, "seg_prow");
+    g.ptf = B.in<unsigned>(a->seg_ptf[s], a->seg_ptf[s] ? np : 0, "seg_ptf");
+    g.df = df_out ? B.inout<unsigned>(a->seg_df[s], a->seg_df[s] ? nk : 0, "seg_df") : B.in<unsigned>(a->seg_df[s], a->seg_df[s] ? nk : 0, "seg_df");
+    g.n_keys = (long long)nk;
+    g.n_post = (long long)np;
+    g.row_lo = a->seg_row_lo[s];
+    g.n_rows = a->seg_n_rows[s];
+  }
+}
+
+// SORT by key / row of n records held in `a` (scratch from B); returns the set that holds the result.
+hipError_t dbg_sort(DbgBufs& B, RecPtrs a, long long n, int by_row, int row_bits, RecPtrs* sorted) {
+  const size_t tiles = (size_t)radix_tiles(n), m = (size_t)n;
+  RecPtrs b{B.scratch<u64>(m, "sort scratch key"), B.scratch<unsigned>(m, "sort scratch row"), B.scratch<unsigned>(m, "sort scratch tf")};
+  unsigned* hist = B.scratch<unsigned>(tiles * 256, "sort hist");
+  unsigned* offs = B.scratch<unsigned>(tiles * 256 + 1, "sort offs");
+  *sorted = a;
+  if (B.err != hipSuccess) return B.err;
+  bool in_b = false;
+  const hipError_t e = radix_passes(a, b, n, by_row, row_bits, hist, offs, nullptr, &in_b);
+  if (in_b) *sorted = b;
+  return e;
+}
+
+// RLE of n records into the caller's output buffers (device copies sized post_buf / keys_buf, checked >= n by the caller).
+// n_post_host stays alive until finish() has synchronised.
+hipError_t dbg_rle(DbgBufs& B, vrag_debug_text_args* a, RecPtrs r, long long n, int unit, bool seg_form, bool query_form,
+                   unsigned* n_post_host) {
+  const size_t m = (size_t)n, pb = (size_t)a->post_buf, kb = (size_t)a->keys_buf;
+  RleScratch scr{B.scratch<unsigned>(m, "rle pflag"), B.scratch<unsigned>(m, "rle kflag"), B.scratch<unsigned>(m + 1, "rle pscan"),
+                 B.scratch<unsigned>(m + 1, "rle kscan")};
+  unsigned* ppos = B.scratch<unsigned>(pb, "rle ppos");
+  unsigned* prow = B.inout<uint32_t>(a->prow, pb, "prow");
+  unsigned* ptf = B.inout<uint32_t>(a->ptf, pb, "ptf");
+  u64* pkey = query_form ? B.inout<u64>(a->pkey, pb, "pkey") : nullptr;
+  u64* ukeys = seg_form ? B.inout<u64>(a->ukeys, kb, "ukeys") : nullptr;
+  unsigned* pstart = seg_form ? B.inout<uint32_t>(a->pstart, kb + 1, "pstart") : nullptr;
+  if (B.err != hipSuccess) return B.err;
+  unsigned n_keys = 0;
+  hipError_t e = rle_count(r, n, scr, n_post_host, &n_keys, nullptr);
+  if (e != hipSuccess) return e;
+  a->n_post = *n_post_host;
+  a->n_keys = n_keys;
+  if ((long long)*n_post_host > n || (long long)n_keys > n) return hipErrorUnknown;   // the scans' totals exceed the flags: nothing may rest on them
+  return rle_emit(r, n, scr, unit, n_post_host, n_keys, ukeys, pstart, prow, ptf, ppos, pkey, nullptr);
+}
+
+}  // namespace
+
+extern "C" {
+
+int vrag_debug_text_run(vrag_debug_text_args* a, int32_t device) {
+  ARG_CHECK(a, "null arguments");
+  const int op = a->op;
+  ARG_CHECK(op >= VRAG_DEBUG_TEXT_SCAN && op <= VRAG_DEBUG_TEXT_SCORE, "op %d is not a full-text stage", op);
+  ARG_CHECK(device >= 0, "bad device %d", device);
+  const bool scan = op == VRAG_DEBUG_TEXT_SCAN, sort = op == VRAG_DEBUG_TEXT_SORT, rle_op = op == VRAG_DEBUG_TEXT_RLE;
+  const bool fold_op = op == VRAG_DEBUG_TEXT_FOLD, stats = op == VRAG_DEBUG_TEXT_STATS, lookup = op == VRAG_DEBUG_TEXT_LOOKUP;
+  const bool score = op == VRAG_DEBUG_TEXT_SCORE;
+  long long total = 0;   // fold: the parts' postings
+  if (scan || sort || rle_op) ARG_CHECK(a->n >= 0 && a->n <= kDbgMax, "n (%lld) must be in 0..2^22", (long long)a->n);
+  if (scan) {
+    ARG_CHECK(a->out && (a->n == 0 || a->in), "scan needs in and out");
+    ARG_CHECK(a->n_buf >= a->n && a->n_buf <= kDbgMax, "scan: n_buf (%lld) below n (%lld)", (long long)a->n_buf, (long long)a->n);
+  }
+  if (sort) {
+    ARG_CHECK(a->n == 0 || (a->key && a->row && a->tf), "sort needs key, row and tf");
+    ARG_CHECK(!a->by_row || (a->row_bits >= 0 && a->row_bits <= 32 && a->row_bits % 8 == 0), "sort: row_bits (%d) must be 0, 8, 16, 24 or 32",
+              a->row_bits);
+  }
+  if (rle_op) {
+    ARG_CHECK(a->n == 0 || (a->key && a->row && a->tf), "rle needs key, row and tf");
+    ARG_CHECK((a->ukeys != nullptr) == (a->pstart != nullptr), "rle: ukeys and pstart come together");
+    ARG_CHECK(a->ukeys || a->pkey, "rle: neither the segment form (ukeys, pstart) nor the query form (pkey) is asked for");
+  }
+  if (fold_op) {
+    ARG_CHECK(a->ukeys && a->pstart, "fold needs ukeys and pstart");
+    const int rc = dbg_check_segs(a, true, false, -1);
+    if (rc != VRAG_OK) return rc;
+    for (int s = 0; s < a->n_segs; ++s) total += a->seg_n_post[s];
+    ARG_CHECK(total <= kDbgMax, "fold: %lld postings are too many for the hook", total);
+  }
+  if (rle_op || fold_op) {
+    const long long need = rle_op ? (long long)a->n : total;
+    ARG_CHECK(a->prow && a->ptf, "%s needs prow and ptf", rle_op ? "rle" : "fold");
+    ARG_CHECK(a->post_buf >= need && a->post_buf <= kDbgMax, "post_buf (%lld) below the records (%lld)", (long long)a->post_buf, need);
+    ARG_CHECK(a->keys_buf >= need && a->keys_buf <= kDbgMax, "keys_buf (%lld) below the records (%lld)", (long long)a->keys_buf, need);
+  }
+  if (stats || score) ARG_CHECK(a->n_rows >= 1 && a->n_rows <= kDbgMax, "n_rows (%lld) must be in 1..2^22", (long long)a->n_rows);
+  if (stats) {
+    ARG_CHECK(a->dl && a->live && a->acc && a->kd, "stats needs dl, live, acc and kd");
+    ARG_CHECK(a->rows_buf >= a->n_rows && a->rows_buf <= kDbgMax, "stats: rows_buf (%lld) below n_rows (%lld)", (long long)a->rows_buf, (long long)a->n_rows);
+    ARG_CHECK(a->k1 >= 0.f && a->b >= 0.f && a->b <= 1.f, "stats: need k1 >= 0 and 0 <= b <= 1 (got %g, %g)", a->k1, a->b);
+    ARG_CHECK(a->corpus_n >= 0 && a->corpus_sum_dl >= 0 && (a->corpus_n > 0 || a->corpus_sum_dl == 0), "stats: a corpus pair with tokens but no rows (%lld, %lld)",
+              (long long)a->corpus_n, (long long)a->corpus_sum_dl);
+    const int rc = dbg_check_segs(a, false, true, a->n_rows);
+    if (rc != VRAG_OK) return rc;
+  }
+  if (lookup) {
+    ARG_CHECK(a->n_terms >= 1 && a->n_terms <= kDbgMax, "lookup: n_terms (%lld) must be in 1..2^22", (long long)a->n_terms);
+    ARG_CHECK(a->terms_buf >= a->n_terms && a->terms_buf <= kDbgMax, "lookup: terms_buf (%lld) below n_terms (%lld)", (long long)a->terms_buf, (long long)a->n_terms);
+    ARG_CHECK(a->qkeys && a->tu, "lookup needs qkeys and tu");
+    const int rc = dbg_check_segs(a, false, true, -1);
+    if (rc != VRAG_OK) return rc;
+  }
+  int n_blocks = 0;
+  if (score) {
+    ARG_CHECK(a->q_indptr && a->kd && a->live && a->cand, "score needs q_indptr, kd, live and cand");
+    ARG_CHECK(a->nq >= 1 && a->nq <= 65535, "score: nq (%d) must be in 1..65535", a->nq);
+    ARG_CHECK(a->kk >= 1 && a->kk <= 64, "score: kk (%d) must be in 1..64", a->kk);
+    ARG_CHECK(a->n_terms >= 0 && a->n_terms <= kDbgMax, "score: n_terms (%lld) must be in 0..2^22", (long long)a->n_terms);
+    ARG_CHECK(a->n_terms == 0 || (a->tu && a->w), "score needs tu and w");
+    const int rc = dbg_check_segs(a, true, false, a->n_rows);
+    if (rc != VRAG_OK) return rc;
+    ARG_CHECK(a->q_indptr[0] == 0, "score: q_indptr[0] must be 0");
+    for (int q = 0; q < a->nq; ++q) ARG_CHECK(a->q_indptr[q + 1] >= a->q_indptr[q], "score: q_indptr decreases at query %d", q);
+    ARG_CHECK(a->q_indptr[a->nq] == a->n_terms, "score: q_indptr ends at %lld, n_terms = %lld", (long long)a->q_indptr[a->nq], (long long)a->n_terms);
+    for (long long j = 0; j < a->n_terms; ++j)
+      for (int s = 0; s < FT_MAXSEG; ++s) {
+        const long long u = a->tu[j * FT_MAXSEG + s];
+        ARG_CHECK(s < a->n_segs ? (u >= -1 && u < a->seg_n_keys[s]) : u == -1, "score: tu[%lld][%d] = %lld is no key of that segment", j, s, u);
+      }
+    ARG_CHECK(!a->allow || (a->allow_rows >= 0 && a->allow_rows <= a->n_rows), "score: allow_rows (%lld) outside [0, n_rows = %lld]",
+              (long long)a->allow_rows, (long long)a->n_rows);
+    n_blocks = score_blocks(a->n_rows);
+    ARG_CHECK(a->cand_buf >= (long long)n_blocks * a->nq * a->kk && a->cand_buf <= (1ll << 26), "score: cand_buf (%lld) below blocks * nq * kk (%lld)",
+              (long long)a->cand_buf, (long long)n_blocks * a->nq * a->kk);
+  }
+  if (vrag_device_count() <= device) {
+    set_error("no HIP device %d visible", device);
+    return VRAG_ERR_NO_DEVICE;
+  }
+  HIP_TRY(hipSetDevice(device));
+
+  DbgBufs B;
+  hipError_t e = hipSuccess;
+  unsigned n_post_host = 0;   // rle_emit copies it on the stream: alive until B.finish()
+  SegPtrs segs[FT_MAXSEG];
+  switch (op) {
+    case VRAG_DEBUG_TEXT_SCAN: {
+      const unsigned* in = B.in<uint32_t>(a->in, (size_t)a->n, "in");
+      unsigned* out = B.inout<uint32_t>(a->out, (size_t)a->n_buf + 1, "out");
+      if ((e = B.err) == hipSuccess) e = scan_u32(in, a->n, out, nullptr);
+      break;
+    }
+    case VRAG_DEBUG_TEXT_SORT: {
+      const size_t n = (size_t)a->n;
+      RecPtrs r{B.in<u64>(a->key, n, "key"), B.in<uint32_t>(a->row, n, "row"), B.in<uint32_t>(a->tf, n, "tf")};
+      RecPtrs sorted = r;
+      if ((e = B.err) == hipSuccess) e = dbg_sort(B, r, a->n, a->by_row, a->row_bits, &sorted);
+      if (e == hipSuccess) e = hipDeviceSynchronize();
+      if (e == hipSuccess && n) e = hipMemcpy(a->key, sorted.key, n * 8, hipMemcpyDeviceToHost);
+      if (e == hipSuccess && n) e = hipMemcpy(a->row, sorted.row, n * 4, hipMemcpyDeviceToHost);
+      if (e == hipSuccess && n) e = hipMemcpy(a->tf, sorted.tf, n * 4, hipMemcpyDeviceToHost);
+      break;
+    }
+    case VRAG_DEBUG_TEXT_RLE: {
+      const size_t n = (size_t)a->n;
+      RecPtrs r{B.in<u64>(a->key, n, "key"), B.in<uint32_t>(a->row, n, "row"), B.in<uint32_t>(a->tf, n, "tf")};
+      if ((e = B.err) == hipSuccess) e = dbg_rle(B, a, r, a->n, a->unit, a->ukeys != nullptr, a->pkey != nullptr, &n_post_host);
+      break;
+    }
+    case VRAG_DEBUG_TEXT_FOLD: {
+      dbg_stage_segs(a, B, false, segs);
+      const size_t n = (size_t)total;
+      RecPtrs r{B.scratch<u64>(n, "fold key"), B.scratch<unsigned>(n, "fold row"), B.scratch<unsigned>(n, "fold tf")};
+      RecPtrs sorted = r;
+      if ((e = B.err) == hipSuccess) e = expand_parts(segs, a->n_segs, r, nullptr);
+      if (e == hipSuccess) e = dbg_sort(B, r, total, 0, 0, &sorted);   // build_segment: by key, then RLE with the records' tf
+      if (e == hipSuccess) e = dbg_rle(B, a, sorted, total, 0, true, false, &n_post_host);
+      break;
+    }
+    case VRAG_DEBUG_TEXT_STATS: {
+      const size_t n = (size_t)a->n_rows, words = (n + 31) / 32;
+      dbg_stage_segs(a, B, true, segs);
+      const unsigned* dl = B.in<uint32_t>(a->dl, n, "dl");
+      const unsigned* live = B.in<uint32_t>(a->live, words, "live");
+      float* kd = B.inout<float>(a->kd, (size_t)a->rows_buf, "kd");
+      unsigned long long pair[4] = {0, 0, (unsigned long long)a->corpus_n, (unsigned long long)a->corpus_sum_dl};   // as refresh_stats lays acc out
+      unsigned long long* acc = B.in<unsigned long long>(pair, 4, "acc");
+      if ((e = B.err) == hipSuccess)
+        e = stats_launch(live, dl, a->n_rows, true, acc, acc + (a->corpus_n ? 2 : 0), a->k1, a->b, kd, segs, a->n_segs, nullptr);
+      if (e == hipSuccess) e = hipDeviceSynchronize();
+      if (e == hipSuccess) e = hipMemcpy(a->acc, acc, 16, hipMemcpyDeviceToHost);
+      break;
+    }
+    case VRAG_DEBUG_TEXT_LOOKUP: {
+      dbg_stage_segs(a, B, false, segs);
+      const u64* qk = B.in<u64>(a->qkeys, (size_t)a->n_terms, "qkeys");
+      int* tu = B.inout<int32_t>(a->tu, (size_t)a->terms_buf * FT_MAXSEG, "tu");
+      long long* df = a->df_out ? B.inout<long long>(a->df_out, (size_t)a->terms_buf, "df_out") : nullptr;
+      if ((e = B.err) == hipSuccess) e = lookup_launch(seg_view(segs, a->n_segs), qk, a->n_terms, tu, df, nullptr);
+      break;
+    }
+    default: {
+      const size_t n = (size_t)a->n_rows, nt = (size_t)a->n_terms;
+      dbg_stage_segs(a, B, false, segs);
+      const long long* qi = B.in<long long>(a->q_indptr, (size_t)a->nq + 1, "q_indptr");
+      const int* tu = B.in<int32_t>(a->tu, nt * FT_MAXSEG, "tu");
+      const float* w = B.in<float>(a->w, nt, "w");
+      const float* kd = B.in<float>(a->kd, n, "kd");
+      const unsigned* live = B.in<uint32_t>(a->live, (n + 31) / 32, "live");
+      const unsigned* allow = a->allow ? B.in<uint32_t>(a->allow, ((size_t)a->allow_rows + 31) / 32, "allow") : nullptr;
+      const u64* bound = a->bound ? B.in<u64>(a->bound, (size_t)a->nq, "bound") : nullptr;
+      u64* cand = B.inout<u64>(a->cand, (size_t)a->cand_buf, "cand");
+      if ((e = B.err) == hipSuccess)
+        e = score_launch(seg_view(segs, a->n_segs), qi, tu, w, kd, live, allow, allow ? a->allow_rows : 0, a->n_rows, a->k1p1, a->nq, a->kk, bound,
+                         cand, nullptr);
+      break;
+    }
+  }
+  return B.finish(e);
+}
+
+int vrag_debug_text_index_read(vrag_text_index* ix, vrag_debug_text_index_state* s) {
+  ARG_CHECK(ix && s, "vrag_debug_text_index_read: null arguments");
+  std::lock_guard<std::mutex> lock(ix->mu);
+  HIP_TRY(hipSetDevice(ix->device));
+  const int rc = refresh_stats(ix);
+  if (rc != VRAG_OK) return rc;
+  const int n_segs = (int)ix->segs.size();
+  if (!s->with_data) {
+    s->n_segs = n_segs;
+    s->n_rows = ix->n_rows;
+    s->n_live = (int64_t)ix->h_acc[0];
+    s->sum_dl = (int64_t)ix->h_acc[1];
+    for (int g = 0; g < 2; ++g) {
+      const Segment* seg = g < n_segs ? &ix->segs[g] : nullptr;
+      s->row_lo[g] = seg ? seg->row_lo : 0;
+      s->seg_rows[g] = seg ? seg->n_rows : 0;
+      s->n_keys[g] = seg ? seg->n_keys : 0;
+      s->n_post[g] = seg ? seg->n_post : 0;
+    }
+    return VRAG_OK;
+  }
+  ARG_CHECK(s->n_segs == n_segs && s->n_rows == ix->n_rows, "vrag_debug_text_index_read: the index changed between the two calls");
+  for (int g = 0; g < n_segs; ++g)
+    ARG_CHECK(s->row_lo[g] == ix->segs[g].row_lo && s->seg_rows[g] == ix->segs[g].n_rows && s->n_keys[g] == ix->segs[g].n_keys &&
+                  s->n_post[g] == ix->segs[g].n_post,
+              "vrag_debug_text_index_read: the index changed between the two calls (segment %d)", g);
+  hipStream_t st = ix->stream;
+  auto get = [&](void* dst, const DevBuf& src, size_t bytes) -> hipError_t {
+    return dst && bytes ? hipMemcpyAsync(dst, src.p, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
+  };
+  for (int g = 0; g < n_segs; ++g) {
+    const Segment& seg = ix->segs[g];
+    HIP_TRY(get(s->keys[g], seg.keys, (size_t)seg.n_keys * 8));
+    HIP_TRY(get(s->pstart[g], seg.pstart, (size_t)(seg.n_keys + 1) * 4));
+    HIP_TRY(get(s->prow[g], seg.prow, (size_t)seg.n_post * 4));
+    HIP_TRY(get(s->ptf[g], seg.ptf, (size_t)seg.n_post * 4));
+    HIP_TRY(get(s->df[g], seg.df, (size_t)seg.n_keys * 4));
+  }
+  const size_t n = (size_t)ix->n_rows;
+  HIP_TRY(get(s->dl, ix->dl, n * 4));
+  HIP_TRY(get(s->kd, ix->kd, n * 4));
+  HIP_TRY(get(s->live, ix->live, (n + 31) / 32 * 4));
+  HIP_TRY(hipStreamSynchronize(st));
+  return VRAG_OK;
+}
+
+}  // extern "C"
+#endif  // VRAG_DEBUG_API
