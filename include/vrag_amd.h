@@ -218,6 +218,27 @@ int vrag_encoder_read_pool(vrag_encoder* enc, float* out /*[n_ranges, H]*/, void
 /* Token-classification head: logits for every packed token, in the caller's concatenation order. */
 int vrag_encoder_run_token_head(vrag_encoder* enc, void* stream);
 int vrag_encoder_read_token_logits(vrag_encoder* enc, float* logits /*[n_tokens, labels]*/, void* stream);
+/* Span selection of the v2 highlighter over the token logits that vrag_encoder_run_token_head left in the workspace (2-label
+ * heads only, else VRAG_ERR_INVALID): the logits stay on the device, only (start, end) character spans come back.
+ *   A JOB is one (question, chunk) pair: its context tokens t = 0 .. job_off[j+1] - job_off[j] - 1 have the character offsets
+ *   offsets[job_off[j] + t] = (start, end).  WINDOW w of job win_job[w] holds the context tokens [win_a[w], win_b[w]) of that job
+ *   at the packed tokens win_first[w] ... (the caller's concatenation order, as read_token_logits returns them; a window lies
+ *   inside one sequence).  Windows are listed job by job, and within a job ascend in win_a and in win_b.
+ *   For a window token m = logit[1] - logit[0] (one fp32 subtraction); for a context token M = the maximum of m over the windows
+ *   that cover it.  The token is HOT iff M > tau -- the caller passes tau = log(thr / (1 - thr)) for `softmax(logits)[1] > thr`;
+ *   a covering window with a NaN m or with logit[1] = +inf (rows the host's softmax turns into NaN), or no covering window,
+ *   makes it cold.  Tokens with end <= start are skipped: they neither
+ *   extend nor close a run.  A maximal sequence of hot tokens that no cold token interrupts is the run [first start, max end);
+ *   a run joins the span in front of it while run.start - span.end <= merge_gap_chars (the difference may be <= 0 when tokens
+ *   share a character); a finished span with end - start < min_span_chars is dropped.
+ * counts[j] = spans of job j, always exact; spans[j][i] = (start, end) for i < counts[j], in text order.  When a count exceeds
+ * cap_per_job the call returns VRAG_ERR_CAPACITY with counts filled in and spans unspecified; the caller reads again with room.
+ * Host pointers; the call synchronises the stream. */
+int vrag_encoder_read_token_spans(vrag_encoder* enc, const int32_t* win_job /*[n_windows]*/, const int32_t* win_a, const int32_t* win_b,
+                                  const int32_t* win_first, int32_t n_windows, const int64_t* job_off /*[n_jobs+1]*/,
+                                  const int32_t* offsets /*[job_off[n_jobs], 2]*/, int32_t n_jobs, float tau, int32_t min_span_chars,
+                                  int32_t merge_gap_chars, int32_t cap_per_job, int32_t* counts /*[n_jobs]*/,
+                                  int32_t* spans /*[n_jobs, cap_per_job, 2]*/, void* stream);
 
 /* SPLADE head: rows[s][v] = max over the tokens of sequence s of log1p(relu(mlm_logit)). */
 int vrag_encoder_run_splade(vrag_encoder* enc, void* stream);
@@ -582,6 +603,17 @@ void vrag_bpe_destroy(vrag_bpe* h);
 int vrag_bpe_encode(vrag_bpe* h, const uint8_t* text, const int64_t* doc_off /*[n_docs+1]*/, int32_t n_docs,
                     int32_t add_special_tokens, int32_t max_length, int64_t cap, int32_t* ids /*[cap]*/,
                     int32_t* seq_lens /*[n_docs]*/, uint8_t* needs_host /*[n_docs]*/, int64_t* n_ids);
+/* vrag_bpe_encode plus, for id i, offsets[i] = the half-open range of code points OF ITS OWN TEXT that HF `tokenizers` reports as
+ * Encoding.offsets[i]; same capacity / needs_host protocol (offsets is written when ids is).  An id that covers the bytes
+ * [b0, b1) of its text starts at the index of the code point that holds byte b0 and ends behind the code point that holds byte
+ * b1 - 1: two ids that split one multi-byte character both report that character's (i, i + 1); a space-run token of t spaces
+ * reports (s, s + t); a VRAG_BPE_IGNORE_MERGES whole-word hit reports its pre-token; [CLS] / [SEP] report (0, 0); truncation
+ * truncates the offsets with the ids.  A text the device proves NFC is its own normalisation, so the offsets index the text as
+ * given; any other text is flagged as above. */
+int vrag_bpe_encode_offsets(vrag_bpe* h, const uint8_t* text, const int64_t* doc_off /*[n_docs+1]*/, int32_t n_docs,
+                            int32_t add_special_tokens, int32_t max_length, int64_t cap, int32_t* ids /*[cap]*/,
+                            int32_t* offsets /*[cap, 2]*/, int32_t* seq_lens /*[n_docs]*/, uint8_t* needs_host /*[n_docs]*/,
+                            int64_t* n_ids);
 
 /* Cross-shard merge of per-shard top-k lists (the reference has no sharding -- this is the step after the
  * all-gather of `[n_lists][nq][k_in]` (fp32 score, global row id) lists, each sorted by (score desc, id asc) with

@@ -462,6 +462,13 @@ typedef struct vrag_debug_text_index_state {
 struct vrag_text_index;
 int vrag_debug_text_index_read(struct vrag_text_index* ix, vrag_debug_text_index_state* state);
 
+/* Unit-test hook of span selection (csrc/spans.hip): vrag_encoder_read_token_spans with a host array of packed logits
+ * [n_tokens, 2] in place of an engine -- win_first[w] indexes its rows -- through the same checks and the same kernel. */
+int vrag_debug_token_spans(const float* logits, int64_t n_tokens, const int32_t* win_job, const int32_t* win_a, const int32_t* win_b,
+                           const int32_t* win_first, int32_t n_windows, const int64_t* job_off, const int32_t* offsets, int32_t n_jobs,
+                           float tau, int32_t min_span_chars, int32_t merge_gap_chars, int32_t cap_per_job, int32_t* counts,
+                           int32_t* spans, int32_t device);
+
 #ifdef __cplusplus
 }
 #endif

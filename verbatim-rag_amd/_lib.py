@@ -101,6 +101,8 @@ SIGNATURES = {
     "vrag_encoder_read_pool": (C.c_int, [_H, _FP, C.c_void_p]),
     "vrag_encoder_run_token_head": (C.c_int, [_H, C.c_void_p]),
     "vrag_encoder_read_token_logits": (C.c_int, [_H, _FP, C.c_void_p]),
+    "vrag_encoder_read_token_spans": (C.c_int, [_H, _IP, _IP, _IP, _IP, C.c_int32, _LP, _IP, C.c_int32, C.c_float, C.c_int32, C.c_int32,
+                                                C.c_int32, _IP, _IP, C.c_void_p]),
     "vrag_encoder_run_splade": (C.c_int, [_H, C.c_void_p]),
     "vrag_encoder_read_splade": (C.c_int, [_H, _FP, C.c_void_p]),
     "vrag_encoder_read_splade_sparse": (C.c_int, [_H, C.c_float, C.c_int32, _IP, _IP, _FP, C.c_void_p]),
@@ -162,6 +164,7 @@ SIGNATURES = {
                                   C.c_int32, C.c_int32, C.POINTER(_H)]),
     "vrag_bpe_destroy": (None, [_H]),
     "vrag_bpe_encode": (C.c_int, [_H, C.c_void_p, _LP, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _IP, _IP, C.c_void_p, _LP]),
+    "vrag_bpe_encode_offsets": (C.c_int, [_H, C.c_void_p, _LP, C.c_int32, C.c_int32, C.c_int32, C.c_int64, _IP, _IP, _IP, C.c_void_p, _LP]),
     "vrag_comm_get_unique_id": (C.c_int, [C.c_void_p]),
     "vrag_comm_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_H)]),
     "vrag_comm_destroy": (None, [_H]),
@@ -192,6 +195,8 @@ DEBUG_SIGNATURES = {
     "vrag_debug_topk_run": (C.c_int, [C.c_void_p, C.c_int32]),
     "vrag_debug_text_run": (C.c_int, [C.c_void_p, C.c_int32]),
     "vrag_debug_text_index_read": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "vrag_debug_token_spans": (C.c_int, [_FP, C.c_int64, _IP, _IP, _IP, _IP, C.c_int32, _LP, _IP, C.c_int32, C.c_float, C.c_int32, C.c_int32,
+                                         C.c_int32, _IP, _IP, C.c_int32]),
 }
 
 

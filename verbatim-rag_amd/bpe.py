@@ -124,7 +124,8 @@ def _i32(values) -> np.ndarray:
 
 
 class GpuByteBpeTokenizer:
-    """`encode_batch(texts)` -> packed int32 ids + lengths, equal to HF's; `ids(text, ...)` as `TokenizerAdapter` offers it."""
+    """`encode_batch(texts)` -> packed int32 ids + lengths, equal to HF's; `encode_batch_offsets(texts)` adds HF's character
+    offsets per id; `ids(text, ...)` as `TokenizerAdapter` offers it."""
 
     def __init__(self, spec: dict, hf_tokenizer: Any, device: int = 0, path: str = "tokenizer.json"):
         cfg = parse_spec(spec, path)
@@ -177,21 +178,34 @@ class GpuByteBpeTokenizer:
         except Exception:
             pass
 
-    def _host_ids(self, text: str, add_special_tokens: bool, max_length: int) -> List[int]:
-        body = list(self._hf.encode(text, add_special_tokens=False).ids)
-        if not add_special_tokens:
-            return body[:max_length]
-        return [self.cls_token_id] + body[:max_length - 2] + [self.sep_token_id]
-
     def encode_batch(self, texts: Sequence[str], add_special_tokens: bool = True, max_length: int = 512) -> Tuple[np.ndarray, np.ndarray]:
         """(ids int32 [sum of lengths], seq_lens int32 [n]): the texts' ids back to back, as `vrag_encoder_load_batch` takes them."""
+        ids, _offsets, seq_lens = self._encode(texts, add_special_tokens, max_length, False)
+        return ids, seq_lens
+
+    def encode_batch_offsets(self, texts: Sequence[str], add_special_tokens: bool = False,
+                             max_length: int = 512) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(ids int32 [n], offsets int32 [n, 2], seq_lens int32 [n_docs]): `encode_batch` plus, per id, the half-open range of
+        characters of its own text that HF reports as `Encoding.offsets` (include/vrag_amd.h states the rule; `(0, 0)` for
+        [CLS] / [SEP]).  A flagged text takes ids AND offsets from the HF tokenizer."""
+        return self._encode(texts, add_special_tokens, max_length, True)
+
+    def _host_encode(self, text: str, add_special_tokens: bool, max_length: int) -> Tuple[List[int], List[Tuple[int, int]]]:
+        enc = self._hf.encode(text, add_special_tokens=False)
+        keep = max_length - 2 if add_special_tokens else max_length
+        ids, offsets = list(enc.ids)[:keep], list(enc.offsets)[:keep]
+        if add_special_tokens:
+            return [self.cls_token_id] + ids + [self.sep_token_id], [(0, 0)] + offsets + [(0, 0)]
+        return ids, offsets
+
+    def _encode(self, texts: Sequence[str], add_special_tokens: bool, max_length: int, with_offsets: bool):
         texts = list(texts)
         max_length = int(max_length)
         if max_length < (2 if add_special_tokens else 0):
             raise ValueError(f"max_length {max_length} leaves no room for the special tokens")
         n = len(texts)
         if n == 0:
-            return np.zeros(0, np.int32), np.zeros(0, np.int32)
+            return np.zeros(0, np.int32), np.zeros((0, 2), np.int32), np.zeros(0, np.int32)
         if not self._h:
             raise RuntimeError("GpuByteBpeTokenizer is closed")
         raw: List[bytes] = []
@@ -213,26 +227,39 @@ class GpuByteBpeTokenizer:
         n_ids = C.c_int64(0)
         cap = int(min(len(blob) + 2 * n, max_length * n))   # no text has more ids than bytes (+ 2 specials) or than max_length
         ids = np.empty(max(cap, 1), np.int32)
-        _lib.check("vrag_bpe_encode", self._lib.vrag_bpe_encode(
-            self._h, C.cast(C.c_char_p(blob), C.c_void_p), off.ctypes.data_as(C.POINTER(C.c_int64)), n, 1 if add_special_tokens else 0,
-            max_length, cap, ids.ctypes.data_as(C.POINTER(C.c_int32)), seq_lens.ctypes.data_as(C.POINTER(C.c_int32)),
-            needs.ctypes.data_as(C.c_void_p), C.byref(n_ids)))
+        ip = C.POINTER(C.c_int32)
+        head = (self._h, C.cast(C.c_char_p(blob), C.c_void_p), off.ctypes.data_as(C.POINTER(C.c_int64)), n, 1 if add_special_tokens else 0,
+                max_length, cap, ids.ctypes.data_as(ip))
+        tail = (seq_lens.ctypes.data_as(ip), needs.ctypes.data_as(C.c_void_p), C.byref(n_ids))
+        if with_offsets:
+            offsets = np.empty((max(cap, 1), 2), np.int32)
+            _lib.check("vrag_bpe_encode_offsets", self._lib.vrag_bpe_encode_offsets(*head, offsets.ctypes.data_as(ip), *tail))
+            offsets = offsets[:n_ids.value]
+        else:
+            offsets = None
+            _lib.check("vrag_bpe_encode", self._lib.vrag_bpe_encode(*head, *tail))
         ids = ids[:n_ids.value]
         host.update(np.nonzero(needs)[0].tolist())
         if not host:
-            return ids, seq_lens
+            return ids, offsets, seq_lens
         self.fallback_count += len(host)
         starts = np.zeros(n + 1, np.int64)
         np.cumsum(seq_lens, out=starts[1:])
-        parts = []
+        parts, oparts = [], []
         for d in range(n):
             if d in host:
-                part = np.asarray(self._host_ids(texts[d], add_special_tokens, max_length), np.int32)
+                h_ids, h_off = self._host_encode(texts[d], add_special_tokens, max_length)
+                part = np.asarray(h_ids, np.int32)
                 seq_lens[d] = len(part)
+                if with_offsets:
+                    oparts.append(np.asarray(h_off, np.int32).reshape(-1, 2))
             else:
                 part = ids[starts[d]:starts[d + 1]]
+                if with_offsets:
+                    oparts.append(offsets[starts[d]:starts[d + 1]])
             parts.append(part)
-        return np.concatenate(parts).astype(np.int32, copy=False), seq_lens
+        return (np.concatenate(parts).astype(np.int32, copy=False),
+                np.concatenate(oparts).astype(np.int32, copy=False) if with_offsets else None, seq_lens)
 
     def ids_batch(self, texts: Sequence[str], max_length: int, add_special_tokens: bool = False) -> List[List[int]]:
         """As `TokenizerAdapter.ids_batch`: one list of ids per text, from one device batch."""

@@ -13,6 +13,12 @@
 //             L2-resident gather: hidden by occupancy -- the kernel holds no LDS and a handful of registers), a butterfly
 //             takes the minimum of (rank, lane), the winning lane takes the merged id and the lanes behind it move up.
 //   pack      token_pack.h, as WordPiece.
+// vrag_bpe_encode_offsets adds, on its own route only (vrag_bpe_encode launches what it always did):
+//   leads     offsets_lead_count_kernel: UTF-8 lead bytes per 16-byte lane, block scan; with the scan of the tile totals this is the
+//             number of code points in front of any byte (lane prefix + tile prefix + a popcount inside the lane's 16 bytes).
+//   merge     offsets_merge_kernel (merge_word<true>) carries a byte width per symbol lane next to `sym`; a wave prefix sum of the surviving widths
+//             gives every id its bytes, the lead counts turn them into code points of its own text.
+//   pack      pack_gather_kernel moves the (start, end) pairs with the ids.
 // Integer work only; vector stores only.
 #include "../../include/vrag_amd.h"
 
@@ -327,6 +333,42 @@ __global__ __launch_bounds__(NT) void bpe_bounds_kernel(const unsigned char* __r
     }
 }
 
+// Code points in front of a byte, per text blob: lane[g] = lead bytes of the tile in front of 16-byte lane g, tile[u] = lead bytes in
+// front of tile u.
+struct LeadIndex {
+  const unsigned* lane;
+  const unsigned* tile;
+};
+// bit j: byte b0 + j is no continuation byte (b0 16-byte aligned, the buffer is 16 bytes longer than the text)
+__device__ __forceinline__ unsigned lead_mask16(const unsigned char* __restrict__ t, long long b0) {
+  const uint4 v = *reinterpret_cast<const uint4*>(t + b0);
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+  unsigned m = 0;
+#pragma unroll
+  for (int j = 0; j < BPT; ++j)
+    if (((w[j >> 2] >> ((j & 3) * 8)) & 0xC0u) != 0x80u) m |= 1u << j;
+  return m;
+}
+// Lead bytes among bytes 0 .. x of the blob (x < n_bytes).
+__device__ __forceinline__ unsigned leads_upto(const unsigned char* __restrict__ t, const LeadIndex& li, long long x) {
+  const long long g = x >> 4;
+  return li.tile[x / VRAG_BPE_TILE_BYTES] + li.lane[g] + (unsigned)__popc(lead_mask16(t, g << 4) & ((2u << (unsigned)(x & 15)) - 1u));
+}
+
+__global__ __launch_bounds__(NT) void offsets_lead_count_kernel(const unsigned char* __restrict__ text, long long n_bytes,
+                                                            unsigned* __restrict__ lane_lead, unsigned* __restrict__ tile_cnt) {
+  const long long g = (long long)blockIdx.x * NT + threadIdx.x, b0 = g * BPT;
+  unsigned m = 0;
+  if (b0 < n_bytes) {
+    m = lead_mask16(text, b0);
+    if (n_bytes - b0 < BPT) m &= (1u << (unsigned)(n_bytes - b0)) - 1u;
+  }
+  unsigned total;
+  const unsigned before = block_scan_256((unsigned)__popc(m), &total);
+  if (b0 < n_bytes) lane_lead[g] = before;
+  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
+}
+
 struct Tables {
   const uint4* merges;          // {left, right, rank, merged}; left = 0xFFFFFFFF: empty; linear probing
   unsigned merge_mask;
@@ -360,12 +402,14 @@ __host__ __device__ inline unsigned pow_base(unsigned e) {
 // Key of a byte string in the `whole` table: sum of (byte + 1) * base^position, mixed with the length.
 __host__ __device__ inline unsigned whole_key(unsigned sum, unsigned n) { return fmix32(sum + n * 0x9E3779B1u) | 1u; }
 
-// One wave per pre-token: tok[wstart[w] + j] = its j-th id, tok_cnt[w] = how many, body[d] += tok_cnt[w].
-__global__ __launch_bounds__(256) void bpe_merge_kernel(const unsigned char* __restrict__ text, const long long* __restrict__ off, int flags,
-                                                        Tables tb, const unsigned* __restrict__ wstart, const unsigned* __restrict__ wdoc,
-                                                        const unsigned char* __restrict__ wspace, long long n_words, int* __restrict__ tok,
-                                                        unsigned* __restrict__ tok_cnt, unsigned* __restrict__ body,
-                                                        unsigned char* __restrict__ needs) {
+// One wave per pre-token (bpe_merge_kernel, offsets_merge_kernel): tok[wstart[w] + j] = its j-th id, tok_cnt[w] = how many, body[d] += tok_cnt[w].
+// OFFS: span[wstart[w] + j] = the code points [start, end) of text d that hold the bytes of that id (include/vrag_amd.h).
+template <bool OFFS>
+__device__ __forceinline__ void merge_word(const unsigned char* __restrict__ text, const long long* __restrict__ off, int flags, const Tables& tb,
+                                           const unsigned* __restrict__ wstart, const unsigned* __restrict__ wdoc,
+                                           const unsigned char* __restrict__ wspace, long long n_words, int* __restrict__ tok,
+                                           unsigned* __restrict__ tok_cnt, unsigned* __restrict__ body, unsigned char* __restrict__ needs,
+                                           const LeadIndex& li, int2* __restrict__ span) {
   const int lane = threadIdx.x & 63;
   const long long w = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= n_words) return;   // the whole wave leaves
@@ -374,8 +418,14 @@ __global__ __launch_bounds__(256) void bpe_merge_kernel(const unsigned char* __r
   const long long e = (w + 1 < n_words && wdoc[w + 1] == d) ? (long long)wstart[w + 1] : off[d + 1];
   const long long len = e - b;
   int* out = tok + b;
+  // bytes [x0, x1) of the blob as code points of text d; base = code points of the blob in front of the text (wave-uniform)
+  const unsigned base = OFFS && off[d] ? leads_upto(text, li, off[d] - 1) : 0u;
+  auto cp_span = [&](long long x0, long long x1) {
+    return make_int2((int)(leads_upto(text, li, x0) - 1u - base), (int)(leads_upto(text, li, x1 - 1) - base));
+  };
   if (wspace[w]) {
     if (lane == 0) {
+      if (OFFS) span[b] = cp_span(b, e);
       out[0] = tb.space_id[min(len, (long long)VRAG_BPE_MAX_SPACE_RUN)];
       tok_cnt[w] = 1u;
       atomicAdd(body + d, 1u);
@@ -401,6 +451,7 @@ __global__ __launch_bounds__(256) void bpe_merge_kernel(const unsigned char* __r
       const bool same = z - a == (unsigned)n && (lane >= n || tb.whole_blob[a + lane] == byte);
       if (__all(same)) {
         if (lane == 0) {
+          if (OFFS) span[b] = cp_span(b, e);
           out[0] = tb.whole_id[sl.y - 1u];
           tok_cnt[w] = 1u;
           atomicAdd(body + d, 1u);
@@ -410,6 +461,7 @@ __global__ __launch_bounds__(256) void bpe_merge_kernel(const unsigned char* __r
     }
   }
   unsigned sym = lane < n ? (unsigned)tb.byte_id[byte] : 0u;
+  unsigned wid = lane < n ? 1u : 0u;   // OFFS: bytes of the lane's symbol
   while (n > 1) {
     const unsigned right = (unsigned)__shfl_down((int)sym, 1, 64);
     unsigned rank = kNoRank, merged = 0u;
@@ -429,13 +481,41 @@ __global__ __launch_bounds__(256) void bpe_merge_kernel(const unsigned char* __r
     const int at = (int)(best & 63u);
     const unsigned m = (unsigned)__shfl((int)merged, at, 64);
     sym = lane < at ? sym : lane == at ? m : right;
+    if (OFFS) {
+      const unsigned rw = (unsigned)__shfl_down((int)wid, 1, 64);
+      wid = lane < at ? wid : lane == at ? wid + rw : rw;
+    }
     --n;
   }
   if (lane < n) out[lane] = (int)sym;
+  if (OFFS) {
+    unsigned x = lane < n ? wid : 0u;   // inclusive wave prefix sum of the surviving widths
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned y = (unsigned)__shfl_up((int)x, o, 64);
+      if (lane >= o) x += y;
+    }
+    if (lane < n) span[b + lane] = cp_span(b + x - wid, b + x);
+  }
   if (lane == 0) {
     tok_cnt[w] = (unsigned)n;
     atomicAdd(body + d, (unsigned)n);
   }
+}
+
+__global__ __launch_bounds__(256) void bpe_merge_kernel(const unsigned char* __restrict__ text, const long long* __restrict__ off, int flags,
+                                                        Tables tb, const unsigned* __restrict__ wstart, const unsigned* __restrict__ wdoc,
+                                                        const unsigned char* __restrict__ wspace, long long n_words, int* __restrict__ tok,
+                                                        unsigned* __restrict__ tok_cnt, unsigned* __restrict__ body,
+                                                        unsigned char* __restrict__ needs) {
+  merge_word<false>(text, off, flags, tb, wstart, wdoc, wspace, n_words, tok, tok_cnt, body, needs, LeadIndex{nullptr, nullptr}, nullptr);
+}
+__global__ __launch_bounds__(256) void offsets_merge_kernel(const unsigned char* __restrict__ text, const long long* __restrict__ off, int flags,
+                                                            Tables tb, const unsigned* __restrict__ wstart, const unsigned* __restrict__ wdoc,
+                                                            const unsigned char* __restrict__ wspace, long long n_words, int* __restrict__ tok,
+                                                            unsigned* __restrict__ tok_cnt, unsigned* __restrict__ body,
+                                                            unsigned char* __restrict__ needs, LeadIndex li, int2* __restrict__ span) {
+  merge_word<true>(text, off, flags, tb, wstart, wdoc, wspace, n_words, tok, tok_cnt, body, needs, li, span);
 }
 
 }  // namespace bpe
@@ -460,6 +540,9 @@ struct vrag_bpe {
   DevArray<long long> off;
   DevArray<unsigned> tile_lead, tile_trail, tile_cnt, tile_off, wstart, wdoc, tok_cnt, tok_scan, body, seq_len, out_off;
   DevArray<int> tok, ids;
+  // vrag_bpe_encode_offsets only
+  DevArray<unsigned> lane_lead, tile_lead_cnt, tile_lead_off;
+  DevArray<int2> span, offs;
 };
 
 namespace {
@@ -580,19 +663,20 @@ void vrag_bpe_destroy(vrag_bpe* h) {
   if (st) (void)hipStreamDestroy(st);
 }
 
-int vrag_bpe_encode(vrag_bpe* h, const uint8_t* text, const int64_t* doc_off, int32_t n_docs, int32_t add_special_tokens, int32_t max_length,
-                    int64_t cap, int32_t* ids, int32_t* seq_lens, uint8_t* needs_host, int64_t* n_ids) {
-  ARG_CHECK(h && doc_off && n_ids && n_docs >= 0 && cap >= 0 && (ids || cap == 0), "vrag_bpe_encode: bad arguments");
-  ARG_CHECK(n_docs == 0 || (seq_lens && needs_host), "vrag_bpe_encode: null seq_lens / needs_host");
-  ARG_CHECK(max_length >= (add_special_tokens ? 2 : 0), "vrag_bpe_encode: max_length %d leaves no room%s", max_length,
+// vrag_bpe_encode (offsets == nullptr, `fn` names the entry in messages) and vrag_bpe_encode_offsets.
+static int bpe_encode(const char* fn, vrag_bpe* h, const uint8_t* text, const int64_t* doc_off, int32_t n_docs, int32_t add_special_tokens,
+                      int32_t max_length, int64_t cap, int32_t* ids, int32_t* offsets, int32_t* seq_lens, uint8_t* needs_host, int64_t* n_ids) {
+  ARG_CHECK(h && doc_off && n_ids && n_docs >= 0 && cap >= 0 && (ids || cap == 0), "%s: bad arguments", fn);
+  ARG_CHECK(n_docs == 0 || (seq_lens && needs_host), "%s: null seq_lens / needs_host", fn);
+  ARG_CHECK(max_length >= (add_special_tokens ? 2 : 0), "%s: max_length %d leaves no room%s", fn, max_length,
             add_special_tokens ? " for the two special tokens" : "");
-  ARG_CHECK(doc_off[0] == 0, "vrag_bpe_encode: doc_off[0] must be 0");
-  for (int32_t d = 0; d < n_docs; ++d) ARG_CHECK(doc_off[d + 1] >= doc_off[d], "vrag_bpe_encode: doc_off must be non-decreasing (text %d)", d);
+  ARG_CHECK(doc_off[0] == 0, "%s: doc_off[0] must be 0", fn);
+  for (int32_t d = 0; d < n_docs; ++d) ARG_CHECK(doc_off[d + 1] >= doc_off[d], "%s: doc_off must be non-decreasing (text %d)", fn, d);
   const long long n_bytes = doc_off[n_docs];
-  ARG_CHECK(n_bytes <= VRAG_BPE_MAX_BATCH_BYTES, "vrag_bpe_encode: a batch holds at most %lld bytes of text, got %lld",
+  ARG_CHECK(n_bytes <= VRAG_BPE_MAX_BATCH_BYTES, "%s: a batch holds at most %lld bytes of text, got %lld", fn,
             (long long)VRAG_BPE_MAX_BATCH_BYTES, n_bytes);
-  ARG_CHECK(n_bytes + 2ll * n_docs < 0x7FFFFFF0ll, "vrag_bpe_encode: text bytes + 2 * n_docs must stay below 2^31");
-  ARG_CHECK(n_bytes == 0 || text, "vrag_bpe_encode: null text");
+  ARG_CHECK(n_bytes + 2ll * n_docs < 0x7FFFFFF0ll, "%s: text bytes + 2 * n_docs must stay below 2^31", fn);
+  ARG_CHECK(n_bytes == 0 || text, "%s: null text", fn);
   *n_ids = 0;
   if (n_docs == 0) return VRAG_OK;
   const int special = add_special_tokens ? 1 : 0;
@@ -620,6 +704,14 @@ int vrag_bpe_encode(vrag_bpe* h, const uint8_t* text, const int64_t* doc_off, in
                      (unsigned*)nullptr, (unsigned*)nullptr, (unsigned char*)nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(scan_u32(h->tile_cnt.p, n_tiles, h->tile_off.p, st));
+  if (offsets) {
+    HIP_TRY(h->lane_lead.grow((size_t)n_tiles * NT));
+    HIP_TRY(h->tile_lead_cnt.grow((size_t)n_tiles));
+    HIP_TRY(h->tile_lead_off.grow((size_t)n_tiles + 1));
+    hipLaunchKernelGGL(offsets_lead_count_kernel, dim3((unsigned)n_tiles), dim3(NT), 0, st, h->text.p, n_bytes, h->lane_lead.p, h->tile_lead_cnt.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(scan_u32(h->tile_lead_cnt.p, n_tiles, h->tile_lead_off.p, st));
+  }
   unsigned n_words = 0;
   HIP_TRY(read_u32(h->tile_off.p + n_tiles, &n_words, st));
   if (n_words) {
@@ -632,8 +724,15 @@ int vrag_bpe_encode(vrag_bpe* h, const uint8_t* text, const int64_t* doc_off, in
     hipLaunchKernelGGL(bpe_bounds_kernel<true>, dim3((unsigned)n_tiles), dim3(NT), 0, st, h->text.p, n_bytes, h->off.p, (int)n_docs, h->flags,
                        h->greedy, h->tile_lead.p, h->tile_trail.p, n_tiles, (unsigned*)nullptr, h->needs.p, h->tile_off.p, h->wstart.p,
                        h->wdoc.p, h->wspace.p);
-    hipLaunchKernelGGL(bpe_merge_kernel, dim3(grid_of(n_words, 4)), dim3(256), 0, st, h->text.p, h->off.p, h->flags, h->tb, h->wstart.p,
-                       h->wdoc.p, h->wspace.p, (long long)n_words, h->tok.p, h->tok_cnt.p, h->body.p, h->needs.p);
+    if (offsets) {
+      HIP_TRY(h->span.grow((size_t)n_bytes));
+      hipLaunchKernelGGL(offsets_merge_kernel, dim3(grid_of(n_words, 4)), dim3(256), 0, st, h->text.p, h->off.p, h->flags, h->tb, h->wstart.p,
+                         h->wdoc.p, h->wspace.p, (long long)n_words, h->tok.p, h->tok_cnt.p, h->body.p, h->needs.p,
+                         LeadIndex{h->lane_lead.p, h->tile_lead_off.p}, h->span.p);
+    } else {
+      hipLaunchKernelGGL(bpe_merge_kernel, dim3(grid_of(n_words, 4)), dim3(256), 0, st, h->text.p, h->off.p, h->flags, h->tb, h->wstart.p,
+                         h->wdoc.p, h->wspace.p, (long long)n_words, h->tok.p, h->tok_cnt.p, h->body.p, h->needs.p);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(scan_u32(h->tok_cnt.p, n_words, h->tok_scan.p, st));
   }
@@ -649,20 +748,42 @@ int vrag_bpe_encode(vrag_bpe* h, const uint8_t* text, const int64_t* doc_off, in
   if ((int64_t)total <= cap && total) {
     HIP_TRY(h->ids.grow(total));
     if (n_words)
-      hipLaunchKernelGGL(pack_gather_kernel, dim3(grid_of(n_words, 256)), dim3(256), 0, st, h->wstart.p, h->wdoc.p, (long long)n_words, h->tok.p,
-                         h->tok_scan.p, h->out_off.p, special, (int)max_length, h->ids.p);
+      hipLaunchKernelGGL(pack_gather_kernel<int>, dim3(grid_of(n_words, 256)), dim3(256), 0, st, h->wstart.p, h->wdoc.p, (long long)n_words,
+                         h->tok.p, h->tok_scan.p, h->out_off.p, special, (int)max_length, h->ids.p);
     if (special)
       hipLaunchKernelGGL(pack_special_kernel, dim3(grid_of(n_docs, 256)), dim3(256), 0, st, h->out_off.p, (int)n_docs, h->cls_id, h->sep_id,
                          h->ids.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(ids, h->ids.p, (size_t)total * 4, hipMemcpyDeviceToHost, st));
+    if (offsets) {   // [CLS] / [SEP] keep the (0, 0) of the memset
+      HIP_TRY(h->offs.grow(total));
+      HIP_TRY(hipMemsetAsync(h->offs.p, 0, (size_t)total * sizeof(int2), st));
+      if (n_words)
+        hipLaunchKernelGGL(pack_gather_kernel<int2>, dim3(grid_of(n_words, 256)), dim3(256), 0, st, h->wstart.p, h->wdoc.p, (long long)n_words,
+                           h->span.p, h->tok_scan.p, h->out_off.p, special, (int)max_length, h->offs.p);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemcpyAsync(offsets, h->offs.p, (size_t)total * sizeof(int2), hipMemcpyDeviceToHost, st));
+    }
   }
   HIP_TRY(hipStreamSynchronize(st));
   if ((int64_t)total > cap) {
-    set_error("vrag_bpe_encode: %u ids, cap %lld", total, (long long)cap);
+    set_error("%s: %u ids, cap %lld", fn, total, (long long)cap);
     return VRAG_ERR_CAPACITY;
   }
   return VRAG_OK;
+}
+
+int vrag_bpe_encode(vrag_bpe* h, const uint8_t* text, const int64_t* doc_off, int32_t n_docs, int32_t add_special_tokens, int32_t max_length,
+                    int64_t cap, int32_t* ids, int32_t* seq_lens, uint8_t* needs_host, int64_t* n_ids) {
+  return bpe_encode("vrag_bpe_encode", h, text, doc_off, n_docs, add_special_tokens, max_length, cap, ids, nullptr, seq_lens, needs_host, n_ids);
+}
+
+int vrag_bpe_encode_offsets(vrag_bpe* h, const uint8_t* text, const int64_t* doc_off, int32_t n_docs, int32_t add_special_tokens,
+                            int32_t max_length, int64_t cap, int32_t* ids, int32_t* offsets, int32_t* seq_lens, uint8_t* needs_host,
+                            int64_t* n_ids) {
+  ARG_CHECK(offsets, "vrag_bpe_encode_offsets: null offsets");
+  return bpe_encode("vrag_bpe_encode_offsets", h, text, doc_off, n_docs, add_special_tokens, max_length, cap, ids, offsets, seq_lens, needs_host,
+                    n_ids);
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 #include "glue_kernels.h"
 #include "host_util.h"
 #include "norm_heads.h"
+#include "spans.h"
 
 namespace vrag {
 
@@ -345,6 +346,7 @@ struct vrag_encoder {
   DevArray<int> d_rng_start, d_rng_end;
   DevArray<float> d_rng_out;  // [max_ranges, max(H, labels)]
   DevArray<float> d_tok_logits;
+  TokenSpanScratch tok_spans;   // vrag_encoder_read_token_spans
   DevArray<unsigned> d_splade;  // allocated with the MLM head
   DevArray<int> d_sp_cnt, d_sp_idx;   // device-side compaction of the SPLADE rows (grown on demand)
   DevArray<float> d_sp_val;
@@ -1951,6 +1953,33 @@ int vrag_encoder_read_token_logits(vrag_encoder* e, float* logits, void* stream)
   ARG_CHECK(e->tk_labels > 0, "token head not set");
   HIP_TRY(hipSetDevice(e->cfg.device));
   return read_rows(e, e->d_tok_logits.p, e->tk_labels, logits, pick_stream(e, stream));
+}
+
+int vrag_encoder_read_token_spans(vrag_encoder* e, const int32_t* win_job, const int32_t* win_a, const int32_t* win_b, const int32_t* win_first,
+                                  int32_t n_windows, const int64_t* job_off, const int32_t* offsets, int32_t n_jobs, float tau,
+                                  int32_t min_span_chars, int32_t merge_gap_chars, int32_t cap_per_job, int32_t* counts, int32_t* spans,
+                                  void* stream) {
+  ARG_CHECK(e, "null encoder handle");
+  std::lock_guard<std::recursive_mutex> lk(e->mu);
+  TRY(check_ready(e));
+  ARG_CHECK(e->ran, "encoder has not run on this batch");
+  ARG_CHECK(e->tk_labels == 2, "vrag_encoder_read_token_spans: the token head has %d labels, span selection needs 2", e->tk_labels);
+  ARG_CHECK(n_windows >= 0 && (n_windows == 0 || (win_first && win_a && win_b)), "vrag_encoder_read_token_spans: bad window table");
+  HIP_TRY(hipSetDevice(e->cfg.device));
+  // packed index (the caller's concatenation order) -> row of the workspace: a window lies inside one sequence
+  std::vector<int64_t> first((size_t)e->n_seqs + 1, 0);
+  for (int s = 0; s < e->n_seqs; ++s) first[s + 1] = first[s] + e->seq_len[s];
+  std::vector<int32_t> row((size_t)n_windows);
+  for (int32_t w = 0; w < n_windows; ++w) {
+    const int64_t p = win_first[w], len = (int64_t)win_b[w] - win_a[w];
+    ARG_CHECK(p >= 0 && p < first[e->n_seqs] && len >= 0, "vrag_encoder_read_token_spans: window %d starts at packed token %lld of %lld", w,
+              (long long)p, (long long)first[e->n_seqs]);
+    const int s = (int)(std::upper_bound(first.begin(), first.end(), p) - first.begin()) - 1;
+    ARG_CHECK(p + len <= first[s + 1], "vrag_encoder_read_token_spans: window %d runs over the end of sequence %d", w, s);
+    row[w] = (int32_t)(e->seq_start[s] + (p - first[s]));
+  }
+  return run_token_spans(e->tok_spans, e->d_tok_logits.p, e->rows, win_job, win_a, win_b, row.data(), n_windows, job_off, offsets, n_jobs, tau,
+                         min_span_chars, merge_gap_chars, cap_per_job, counts, spans, pick_stream(e, stream));
 }
 
 int vrag_encoder_run_splade(vrag_encoder* e, void* stream) {

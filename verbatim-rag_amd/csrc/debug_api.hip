@@ -15,6 +15,7 @@
 #include "host_util.h"
 #include "norm_heads.h"
 #include "qkv_attn.h"
+#include "spans.h"
 #include "topk_kernels.h"
 
 using namespace vrag;
@@ -1319,6 +1320,19 @@ int vrag_debug_topk_run(vrag_debug_topk_args* a, int32_t device) {
     return VRAG_ERR_HIP;
   }
   return VRAG_OK;
+}
+
+int vrag_debug_token_spans(const float* logits, int64_t n_tokens, const int32_t* win_job, const int32_t* win_a, const int32_t* win_b,
+                           const int32_t* win_first, int32_t n_windows, const int64_t* job_off, const int32_t* offsets, int32_t n_jobs, float tau,
+                           int32_t min_span_chars, int32_t merge_gap_chars, int32_t cap_per_job, int32_t* counts, int32_t* spans, int32_t device) {
+  ARG_CHECK(n_tokens >= 0 && n_tokens < 0x7FFFFFF0ll && (logits || n_tokens == 0), "vrag_debug_token_spans: bad logits");
+  HIP_TRY(hipSetDevice(device));
+  DevBuf dl;
+  HIP_TRY(dl.alloc((size_t)n_tokens * 2 * sizeof(float)));
+  if (n_tokens) HIP_TRY(hipMemcpy(dl.p, logits, (size_t)n_tokens * 2 * sizeof(float), hipMemcpyHostToDevice));
+  TokenSpanScratch ws;
+  return run_token_spans(ws, dl.as<float>(), n_tokens, win_job, win_a, win_b, win_first, n_windows, job_off, offsets, n_jobs, tau,
+                         min_span_chars, merge_gap_chars, cap_per_job, counts, spans, nullptr);
 }
 
 }  // extern "C"

@@ -14,10 +14,12 @@ static __global__ void pack_seq_len_kernel(const unsigned* __restrict__ body, in
   seq_len[d] = min(body[d], keep) + (special ? 2u : 0u);
 }
 
-// One lane per word: the ids of the word that lie below the text's truncation limit, at their place in the output.
+// One lane per word: the ids of the word that lie below the text's truncation limit, at their place in the output.  T = int for
+// the ids; the BPE tokenizer moves its per-id character offsets (int2) the same way.
+template <typename T>
 static __global__ void pack_gather_kernel(const unsigned* __restrict__ wstart, const unsigned* __restrict__ wdoc, long long n_words,
-                                 const int* __restrict__ tok, const unsigned* __restrict__ tok_scan, const unsigned* __restrict__ out_off,
-                                 int special, int max_length, int* __restrict__ ids) {
+                                 const T* __restrict__ tok, const unsigned* __restrict__ tok_scan, const unsigned* __restrict__ out_off,
+                                 int special, int max_length, T* __restrict__ ids) {
   const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= n_words) return;
   const unsigned d = wdoc[w];
@@ -29,8 +31,8 @@ static __global__ void pack_gather_kernel(const unsigned* __restrict__ wstart, c
   }
   const unsigned keep = (unsigned)(special ? max_length - 2 : max_length);
   const unsigned first = tok_scan[w] - tok_scan[lo], n = tok_scan[w + 1] - tok_scan[w];
-  int* out = ids + out_off[d] + (special ? 1 : 0);
-  const int* src = tok + wstart[w];
+  T* out = ids + out_off[d] + (special ? 1 : 0);
+  const T* src = tok + wstart[w];
   for (unsigned j = 0; j < n && first + j < keep; ++j) out[first + j] = src[j];
 }
 

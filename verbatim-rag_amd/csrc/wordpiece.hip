@@ -504,7 +504,7 @@ int vrag_wordpiece_encode(vrag_wordpiece* h, const uint8_t* text, const int64_t*
   if ((int64_t)total <= cap && total) {
     HIP_TRY(h->ids.grow(total));
     if (n_words)
-      hipLaunchKernelGGL(pack_gather_kernel, dim3(grid_of(n_words, 256)), dim3(256), 0, st, h->wstart.p, h->wdoc.p, (long long)n_words, h->tok.p,
+      hipLaunchKernelGGL(pack_gather_kernel<int>, dim3(grid_of(n_words, 256)), dim3(256), 0, st, h->wstart.p, h->wdoc.p, (long long)n_words, h->tok.p,
                          h->tok_scan.p, h->out_off.p, special, (int)max_length, h->ids.p);
     if (special)
       hipLaunchKernelGGL(pack_special_kernel, dim3(grid_of(n_docs, 256)), dim3(256), 0, st, h->out_off.p, (int)n_docs, h->cls_id, h->sep_id,

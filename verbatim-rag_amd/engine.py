@@ -309,6 +309,35 @@ class EncoderEngine:
         _lib.check("vrag_encoder_read_token_logits", self._lib.vrag_encoder_read_token_logits(self._h, _fp(out), stream))
         return out
 
+    def read_token_spans(self, win_job, win_a, win_b, win_first, job_off, offsets, tau: float, min_span_chars: int,
+                         merge_gap_chars: int, cap_per_job: int = 16, stream: Optional[int] = None):
+        """Span selection on the device over the logits `run_token_head` left in the workspace (2-label heads;
+        include/vrag_amd.h states the rule): window w holds the context tokens [win_a[w], win_b[w]) of job win_job[w] at the
+        packed tokens win_first[w] ...; offsets[job_off[j]:job_off[j + 1]] are job j's (start, end) characters per context
+        token.  Returns (counts int32 [n_jobs], spans int32 [n_jobs, cap, 2]); a job with more than cap_per_job spans makes
+        the call read again with room for the largest count."""
+        if self.token_labels != 2:
+            raise ValueError(f"span selection needs a 2-label token head, this engine's has {self.token_labels}")
+        wj, wa, wb, wf = _i32(win_job), _i32(win_a), _i32(win_b), _i32(win_first)
+        joff = np.ascontiguousarray(np.asarray(job_off, np.int64).reshape(-1))
+        offs = np.ascontiguousarray(np.asarray(offsets, np.int32).reshape(-1, 2))
+        n_jobs = len(joff) - 1
+        if not (len(wj) == len(wa) == len(wb) == len(wf)) or n_jobs < 0 or len(offs) != (int(joff[-1]) if n_jobs >= 0 else 0):
+            raise ValueError("window table / job_off / offsets do not fit together")
+        cap = max(1, int(cap_per_job))
+        while True:
+            counts = np.zeros(n_jobs, dtype=np.int32)
+            spans = np.zeros((n_jobs, cap, 2), dtype=np.int32)
+            status = self._lib.vrag_encoder_read_token_spans(
+                self._h, wj.ctypes.data_as(_IP), wa.ctypes.data_as(_IP), wb.ctypes.data_as(_IP), wf.ctypes.data_as(_IP), len(wj),
+                joff.ctypes.data_as(_lib._LP), offs.ctypes.data_as(_IP), n_jobs, float(tau), int(min_span_chars), int(merge_gap_chars),
+                cap, counts.ctypes.data_as(_IP), spans.ctypes.data_as(_IP), stream)
+            if status == -3 and n_jobs and int(counts.max()) > cap:      # VRAG_ERR_CAPACITY: counts are exact
+                cap = int(counts.max())
+                continue
+            _lib.check("vrag_encoder_read_token_spans", status)
+            return counts, spans
+
     def run_splade(self, stream: Optional[int] = None) -> None:
         _lib.check("vrag_encoder_run_splade", self._lib.vrag_encoder_run_splade(self._h, stream))
 

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import json
 import logging
+import math
 import os
 import threading
 import time
@@ -112,13 +113,25 @@ def token_spans_to_char_spans(
     return out
 
 
+def window_plan(n_ctx: int, room: int, doc_stride: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Context-token slices [a, b) of the windows `_encode_windows` cuts: `room` context tokens per window, consecutive windows
+    `max(1, room - doc_stride)` apart, the last one ends the context (one empty window for an empty context)."""
+    step = max(1, room - doc_stride)
+    n_win = 1 if n_ctx <= room else -(-(n_ctx - room) // step) + 1
+    a = np.arange(n_win, dtype=np.int64) * step
+    return a, np.minimum(n_ctx, a + room)
+
+
 class GpuModelSpanExtractor(SpanExtractor):
     """MI355X implementation of ModelSpanExtractor (extractors.py:57-279).
 
     Construct either from a local HF checkpoint directory (`model_path`: config.json +
     *.safetensors [+ tokenizer.json]) or from an already-built `engine` + `tokenizer`.
     With `model_path`, `tokenizer` may also be "host" (the default: HF on the caller's thread) or "gpu" (the checkpoint's
-    tokenizer.json on the device, same ids; sentence-classifier format only -- the highlighter needs character offsets).
+    tokenizer.json on the device, same ids; sentence-classifier format only -- the highlighter's host route needs the HF
+    tokenizer's character offsets).
+    `highlighter_route="device"` (v2 format, opt-in) tokenises contexts on the device with character offsets, keeps the window
+    logits in device memory and reads back only the selected (start, end) spans; "host" is the default.
     Raises at construction when the HIP library or a GPU is missing -- there is no CPU path.
     """
 
@@ -149,13 +162,25 @@ class GpuModelSpanExtractor(SpanExtractor):
         extra_engines: Sequence[Any] = (),
         n_engines: int = 1,
         operand_dtype: Optional[str] = None,
+        highlighter_route: str = "host",
     ):
-        """operand_dtype: MFMA operand type of the engines this extractor builds (`EncoderEngine`): None picks "bf16" for
+        """highlighter_route: "host" (default) or "device" -- the v2 format's all-GPU route (`_extract_highlighter_device`).
+        "device" needs the highlighter format, 0 < threshold < 1 (the comparison runs in logit space), a 2-label token head
+        and a tokenizer with `encode_batch_offsets` (`GpuByteBpeTokenizer`; with `model_path` it is loaded from the
+        checkpoint's tokenizer.json); anything else is a ValueError here, never a fall back to the host route.
+        operand_dtype: MFMA operand type of the engines this extractor builds (`EncoderEngine`): None picks "bf16" for
         the sentence-classifier format (sentence logits within 3e-4 of the fp32 reference) and "f16" for the v2 highlighter,
         whose per-token logits need the three extra mantissa bits to stay within 1e-3.  fp16 operands saturate at 65504: every
         device batch runs through `CheckedEngines.run` (checked_engine.py), which on the first clamp report replaces the
         engines this extractor built by bf16 ones and runs the batch again; an extractor that was handed its engine raises,
         which the per-chunk error handling turns into "log, no spans" -- never silently wrong."""
+        if highlighter_route not in ("host", "device"):
+            raise ValueError(f"highlighter_route must be 'host' or 'device', got {highlighter_route!r}")
+        device_route = highlighter_route == "device"
+        if device_route and not 0.0 < float(threshold) < 1.0:
+            raise ValueError(f'highlighter_route="device" compares logit margins with log(thr / (1 - thr)): threshold must lie '
+                             f"strictly between 0 and 1, got {threshold!r}")
+        self.highlighter_route = highlighter_route
         self.operand_dtype = operand_dtype
         self.model_path = model_path
         self.threshold = threshold
@@ -188,9 +213,18 @@ class GpuModelSpanExtractor(SpanExtractor):
                     f"model_path={model_path!r}: a local HF checkpoint directory is required (no network here); "
                     "or pass engine= and tokenizer=")
             self._format = model_format or self._detect_format(model_path)
-            if isinstance(tokenizer, str):
-                if tokenizer not in ("host", "gpu"):
-                    raise ValueError(f"tokenizer must be 'host', 'gpu' or a tokenizer object, got {tokenizer!r}")
+            if isinstance(tokenizer, str) and tokenizer not in ("host", "gpu"):
+                raise ValueError(f"tokenizer must be 'host', 'gpu' or a tokenizer object, got {tokenizer!r}")
+            if device_route:
+                self._check_device_route_format()
+                if tokenizer == "host":
+                    raise ValueError('highlighter_route="device" tokenises on the device: tokenizer must be None, "gpu" or an object '
+                                     'with encode_batch_offsets, not "host"')
+                if tokenizer is None or tokenizer == "gpu":
+                    from .embedding_providers import load_model_tokenizer
+
+                    tokenizer = load_model_tokenizer(model_path, "gpu", device=dev)
+            elif isinstance(tokenizer, str):
                 if tokenizer == "gpu" and self._format == self._FORMAT_HIGHLIGHTER:
                     raise ValueError('tokenizer="gpu" yields no character offsets, which the highlighter format needs; use tokenizer="host"')
                 # "gpu": question and sentence ids come from device batches (bpe.py / wordpiece.py) through ids / ids_batch
@@ -206,6 +240,14 @@ class GpuModelSpanExtractor(SpanExtractor):
             engines = [self._build_engine(model_path, dev) for _ in range(max(1, int(n_engines)))]
             rebuild = partial(self._build_engine, model_path, dev, "bf16")
             tokenizer = tokenizer or load_tokenizer(model_path)
+        if device_route:
+            self._check_device_route_format()
+            if not hasattr(tokenizer, "encode_batch_offsets"):
+                raise ValueError(f'highlighter_route="device" needs a tokenizer with encode_batch_offsets (GpuByteBpeTokenizer), got '
+                                 f"{type(tokenizer).__name__}")
+            labels = getattr(engines[0], "token_labels", 0)
+            if labels != 2:
+                raise ValueError(f'highlighter_route="device" selects spans from a 2-label token head, the engine\'s has {labels} labels')
         self.tokenizer = tokenizer
         self._checked = CheckedEngines(engines, rebuild, on_swap=self._bind)   # callers arrive from asyncio.to_thread workers
         self._bind()
@@ -225,6 +267,10 @@ class GpuModelSpanExtractor(SpanExtractor):
         except Exception as exc:
             logger.warning("Highlighter detection failed for %s: %s", model_path, exc)
         return GpuModelSpanExtractor._FORMAT_QA_MODEL
+
+    def _check_device_route_format(self) -> None:
+        if self._format != self._FORMAT_HIGHLIGHTER:
+            raise ValueError(f'highlighter_route="device" is a route of the highlighter format, this model is {self._format!r}')
 
     def _bind(self) -> None:
         """What the extractor keeps of its engines; derived again when they are replaced."""
@@ -261,6 +307,9 @@ class GpuModelSpanExtractor(SpanExtractor):
     # ------------------------------------------------------------------ legacy qa_model path
     def prepare_chunks(self, texts: Sequence[str]) -> None:
         """Optional ingest-time hook: pre-split and pre-tokenise chunk texts (e.g. from add_vectors)."""
+        if self.highlighter_route == "device":
+            self._context_entries([t for t in texts if t.strip()])
+            return
         self.pack_qa("", list(texts))
 
     def pack_qa(self, question: str, texts: Sequence[str]) -> Tuple[List[List[str]], List[Optional[PackedSample]]]:
@@ -514,6 +563,8 @@ class GpuModelSpanExtractor(SpanExtractor):
                                    results_per_question: Sequence[Sequence[Any]]) -> List[Dict[str, List[str]]]:
         """v2 path for several queries at once: the windows of every (question, chunk) pair share padding-free GPU
         batches (windows never see each other, so element i equals the single-query call)."""
+        if self.highlighter_route == "device":
+            return self._extract_highlighter_device(questions, results_per_question)
         out: List[Dict[str, List[str]]] = []
         jobs = []   # (query index, context, windows, offsets, context tokens)
         for qi, (question, search_results) in enumerate(zip(questions, results_per_question)):
@@ -529,6 +580,12 @@ class GpuModelSpanExtractor(SpanExtractor):
                     jobs.append((qi, context, windows, offsets, n_ctx))
                 except Exception as exc:
                     logger.error("Highlighter extraction failed: %s", exc)
+        self._run_highlighter_jobs(jobs, out)
+        return out
+
+    def _run_highlighter_jobs(self, jobs, out) -> None:
+        """Host route for `jobs` = [(query index, context, windows, offsets, context tokens)]: window logits read back,
+        softmax and window maximum in numpy, `token_spans_to_char_spans` per job into out[query index][context]."""
         flat = [(ji, w) for ji, job in enumerate(jobs) for w in job[2]]
         probs = [np.zeros(job[4], dtype=np.float32) for job in jobs]
         def token_logits(engine, windows):
@@ -558,7 +615,136 @@ class GpuModelSpanExtractor(SpanExtractor):
         for (qi, context, _w, offsets, _n), p in zip(jobs, probs):
             out[qi][context] = token_spans_to_char_spans(p, offsets, context, self.threshold, self.min_span_chars,
                                                          self.merge_gap_chars)
+
+    # ------------------------------------------------------------------ v2 highlighter path, device route
+    _NO_TRUNCATION = 2 ** 31 - 1
+
+    def _context_entries(self, texts: Sequence[str]) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """(ids int32 [n], offsets int32 [n, 2]) per context text, memoised in the chunk cache: one `encode_batch_offsets` call for
+        every text not seen before (contexts are tokenised without the question and without truncation, as `_encode_windows`
+        does on the host)."""
+        with self._cache_lock:
+            missing = [t for t in dict.fromkeys(texts) if t not in self._chunk_cache]
+            if missing:
+                ids, offs, lens = self.tokenizer.encode_batch_offsets(missing, add_special_tokens=False, max_length=self._NO_TRUNCATION)
+                if len(self._chunk_cache) + len(missing) > self._chunk_cache_size:
+                    self._chunk_cache.clear()
+                cuts = np.cumsum(lens)[:-1]
+                for t, i, o in zip(missing, np.split(ids, cuts), np.split(offs, cuts)):
+                    self._chunk_cache[t] = (i, o)
+            return [self._chunk_cache[t] for t in texts]
+
+    def _extract_highlighter_device(self, questions: Sequence[str],
+                                    results_per_question: Sequence[Sequence[Any]]) -> List[Dict[str, List[str]]]:
+        """The device route: contexts tokenised on the device with offsets (cached per chunk text), windows planned and packed with
+        numpy, one load -> run -> token head -> `read_token_spans` per device batch; only (start, end) spans come back.  Batches
+        are cut between jobs, so every window of a job is in the batch that selects its spans; a job that alone exceeds the
+        workspace takes the host route's code.  Same result dictionary as the host route."""
+        out: List[Dict[str, List[str]]] = []
+        pairs = []   # (query index, context)
+        for qi, results in enumerate(results_per_question):
+            relevant: Dict[str, List[str]] = {}
+            out.append(relevant)
+            for result in results:
+                context = getattr(result, "text", "")
+                relevant[context] = []
+                if context.strip():
+                    pairs.append((qi, context))
+        if not pairs:
+            return out
+        def one_by_one(fn, items):
+            """fn(items) as one device batch; when that fails, item by item, so that a bad text loses only itself (None, logged)."""
+            try:
+                return fn(items)
+            except Exception as exc:
+                if len(items) == 1:
+                    logger.error("Highlighter extraction failed: %s", exc)
+                    return [None]
+            return [one_by_one(fn, [item])[0] for item in items]
+
+        entries = one_by_one(self._context_entries, [c for _qi, c in pairs])
+        used = sorted({qi for qi, _c in pairs})
+        q_ids = dict(zip(used, one_by_one(
+            lambda qs: self._tok.ids_batch(qs, max_length=max(8, self.max_length // 2), add_special_tokens=True), [questions[qi] for qi in used])))
+        eng = self.engine
+        max_tokens, max_seqs = min(eng.max_tokens, self.max_batch_tokens), min(eng.max_seqs, self.max_batch_seqs)
+        jobs = []    # (query index, context, question ids, context ids, offsets, window starts, window ends)
+        sizes = []   # (tokens, windows) of every job
+        for (qi, context), entry in zip(pairs, entries):
+            q = q_ids[qi]
+            if entry is None or q is None:      # logged above: this chunk stays without spans
+                continue
+            ids, offs = entry
+            room = self.max_length - len(q) - 1
+            if room <= 0:
+                logger.error("Highlighter extraction failed: %s", "question leaves no room for context tokens")
+                continue
+            a, b = window_plan(len(ids), room, self.doc_stride)
+            jobs.append((qi, context, q, ids, offs, a, b))
+            sizes.append((int((b - a).sum()) + len(a) * (len(q) + 1), len(a)))
+        host_jobs = []
+        start = 0
+        while start < len(jobs):
+            end, tok, seqs = start, 0, 0
+            while end < len(jobs) and tok + sizes[end][0] <= max_tokens and seqs + sizes[end][1] <= max_seqs:
+                tok += sizes[end][0]
+                seqs += sizes[end][1]
+                end += 1
+            if end == start:   # this job alone exceeds a device batch: window by window through the host route's code
+                host_jobs.append(jobs[start])
+                start += 1
+                continue
+            try:
+                self._run_device_batch(jobs[start:end], tok, seqs, out)
+            except Exception as exc:
+                if end - start == 1:
+                    logger.error("Highlighter extraction failed: %s", exc)
+                for j in range(start, end) if end - start > 1 else ():      # job by job: one bad chunk loses only itself
+                    try:
+                        self._run_device_batch(jobs[j:j + 1], *sizes[j], out)
+                    except Exception as exc1:
+                        logger.error("Highlighter extraction failed: %s", exc1)
+            start = end
+        if host_jobs:
+            sep = self._tok.sep_token_id
+            self._run_highlighter_jobs(
+                [(qi, context, [(q + ids[x:y].tolist() + [sep], (x, y), len(q)) for x, y in zip(a.tolist(), b.tolist())],
+                  [tuple(o) for o in offs.tolist()], len(ids)) for qi, context, q, ids, offs, a, b in host_jobs], out)
         return out
+
+    def _run_device_batch(self, jobs, n_tokens: int, n_windows: int, out) -> None:
+        sep = self._tok.sep_token_id
+        ids = np.empty(n_tokens, np.int32)
+        seq_lens = np.empty(n_windows, np.int32)
+        win_job, win_a, win_b, win_first = (np.empty(n_windows, np.int32) for _ in range(4))
+        job_off = np.zeros(len(jobs) + 1, np.int64)
+        o = w = 0
+        for j, (_qi, _context, q, ctx, offs, a, b) in enumerate(jobs):
+            job_off[j + 1] = job_off[j] + len(ctx)
+            nq = len(q)
+            for x, y in zip(a.tolist(), b.tolist()):
+                n = nq + (y - x) + 1
+                ids[o:o + nq] = q
+                ids[o + nq:o + n - 1] = ctx[x:y]
+                ids[o + n - 1] = sep
+                seq_lens[w], win_job[w], win_a[w], win_b[w], win_first[w] = n, j, x, y, o + nq
+                o += n
+                w += 1
+        offsets = np.concatenate([job[4] for job in jobs]) if jobs else np.zeros((0, 2), np.int32)
+        thr = float(self.threshold)
+        tau = np.float32(math.log(thr / (1.0 - thr)))
+
+        def spans_of(engine):
+            engine.load_packed(ids, seq_lens)
+            engine.run()
+            engine.run_token_head()
+            return engine.read_token_spans(win_job, win_a, win_b, win_first, job_off, offsets, tau, self.min_span_chars,
+                                           self.merge_gap_chars)
+
+        counts, spans = self._checked.run(spans_of)
+        for j, (qi, context, *_rest) in enumerate(jobs):
+            found = spans[j, :counts[j]].tolist()
+            out[qi][context] = [context[x:y] for x, y in found if context[x:y].strip()]
 
 
 class CoalescingSpanExtractor(SpanExtractor):
