@@ -263,3 +263,17 @@ def test_the_second_pass_asks_for_min_k_and_passing_rows(stand_ins):
     CALLS.clear()
     assert bm.query(dense_query=dense[9].tolist(), top_k=10, search_type="dense", filter='metadata["n"] == -1') == []
     assert not CALLS                                                           # nothing passes: no search at all
+
+
+def test_the_filtered_and_the_unfiltered_route_are_one_loop(stand_ins):
+    _sub, bm, dense, sparse = _pair()
+    parts, _dev, n = bm._main_parts("sparse")
+    assert n == N and len(parts) == 2                                          # main segment + the tail at row 363
+    queries = [sparse[i] for i in (3, 362, 363, 402, 17)]
+    for k in (1, 7, 70):
+        plain_s, plain_r = bm._device_topk("sparse", parts, None, queries, k)
+        CALLS.clear()
+        filt_s, filt_r = bm._filtered_topk("sparse", parts, queries, k, np.ones(N, dtype=bool))
+        assert len(CALLS) == 2 and plain_r.shape == (len(queries), k)
+        assert np.array_equal(plain_r, filt_r) and (plain_r >= 363).any() and (plain_r < 363).any()
+        assert plain_s.dtype == filt_s.dtype == np.float32 and plain_s.tobytes() == filt_s.tobytes()

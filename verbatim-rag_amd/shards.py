@@ -1,0 +1,396 @@
+"""The device indexes of the vector store as Python objects: ctypes wrappers around the library's handles
+(include/vrag_amd.h, vrag_dense_index_* / vrag_ivf_index_* / vrag_sparse_index_* / vrag_text_index_*) and the host-side
+packing their calls need (CSR, UTF-8 batches, row bitmaps).  The store-side module that touches `ctypes`; vector_stores.py
+holds the store that routes searches to these objects.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import threading
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import _lib
+
+_FP = C.POINTER(C.c_float)
+_LP = C.POINTER(C.c_int64)
+_IP = C.POINTER(C.c_int32)
+
+
+def _fp(a: np.ndarray):       # like every `data_as` pointer, the result keeps its array alive
+    return a.ctypes.data_as(_FP)
+
+
+def _lp(a: np.ndarray):
+    return a.ctypes.data_as(_LP)
+
+
+def _ip(a: np.ndarray):
+    return a.ctypes.data_as(_IP)
+
+
+def _vp(a: np.ndarray):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _topk_out(nq: int, k: int, fill: bool = False):
+    """The `[nq, k]` outputs of a search and their ctypes pointers: (float32 scores, int64 ids, scores ptr, ids ptr).
+    Uninitialised where the library writes every slot; `fill=True` starts from "no hit" (-inf / -1) for the calls that may
+    write fewer (`TextIndex`)."""
+    if fill:
+        scores, ids = np.full((nq, k), -np.inf, np.float32), np.full((nq, k), -1, np.int64)
+    else:
+        scores, ids = np.empty((nq, k), np.float32), np.empty((nq, k), np.int64)
+    return scores, ids, _fp(scores), _lp(ids)
+
+
+class _Handle:
+    """Owner of one library handle: `_open` creates it, `close` destroys it once, and an object whose constructor failed
+    (before or inside `_open`) is collected quietly."""
+
+    _destroy = ""       # name of the library function that frees `_h`
+    _lib = None
+    _h = None
+
+    def _open(self, create: str, *args) -> None:
+        """`create(*args, &handle)`; a failed call leaves the handle null."""
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        _lib.check(create, getattr(self._lib, create)(*args, C.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _allow_words(allow_words, n_allow: int) -> np.ndarray:
+    """The bitmap of a filtered search as contiguous uint32 words; ValueError when it is shorter than `n_allow` rows (the
+    library would read past it)."""
+    words = np.ascontiguousarray(allow_words, dtype=np.uint32).reshape(-1)
+    if n_allow < 0 or len(words) * 32 < n_allow:
+        raise ValueError(f"allow_words holds {len(words) * 32} bits, n_allow = {n_allow}")
+    return words
+
+
+def _search_call(lib, fn: str, head: tuple, nq: int, k: int, allow, stream) -> Tuple[np.ndarray, np.ndarray]:
+    """`fn(*head, nq, k, scores, ids, stream)`, or with `allow = (allow_words, n_allow)` the `_filtered` entry point, which
+    takes the bitmap and its row count before the outputs."""
+    if allow is not None:
+        fn += "_filtered"
+        allow = (_vp(_allow_words(*allow)), int(allow[1]))
+    scores, ids, sp, ip = _topk_out(nq, k)
+    _lib.check(fn, getattr(lib, fn)(*head, nq, k, *(allow or ()), sp, ip, stream))
+    return scores, ids
+
+
+class DenseShard(_Handle):
+    """One GPU's slice of the dense corpus (rows appended in order; ids are local row numbers)."""
+
+    _destroy = "vrag_dense_index_destroy"
+
+    def __init__(self, dim: int, capacity: int, dtype: str = "bf16", device: int = 0, prefilter: bool = True):
+        """dtype "bf16" | "f32".  fp32 rows keep a bf16 prefilter image beside them unless `prefilter=False` (+50 % memory):
+        a search ranks the image for 64 candidates per query and re-scores those exactly -- same bits as the full fp32 scan
+        (include/vrag_amd.h, dtype 2), half the time for one query and a quarter for a batch of 256."""
+        _lib.require_gpu()
+        self.dim, self.capacity = dim, capacity
+        self.ivf: Optional["IvfOverlay"] = None    # an IVF_FLAT overlay over these rows (owned: closed before the shard)
+        code = 0 if dtype == "bf16" else (2 if prefilter and dim % 4 == 0 else 1)
+        self._open("vrag_dense_index_create", dim, capacity, code, device)
+
+    def add(self, rows: np.ndarray) -> None:
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n, {self.dim}]")
+        _lib.check("vrag_dense_index_add", self._lib.vrag_dense_index_add(self._h, _fp(rows), rows.shape[0]))
+
+    def add_device(self, ptr: int, n: int, stream=None) -> None:
+        """Rows already in HBM (`ptr`: device address of fp32 `[n, dim]` on the shard's device): no host round trip."""
+        _lib.check("vrag_dense_index_add_device", self._lib.vrag_dense_index_add_device(self._h, C.c_void_p(int(ptr)), int(n), stream))
+
+    def __len__(self) -> int:
+        return int(self._lib.vrag_dense_index_size(self._h))
+
+    def _queries(self, queries: np.ndarray) -> np.ndarray:
+        return np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+
+    def _search(self, queries, k: int, allow, stream):
+        q = self._queries(queries)
+        return _search_call(self._lib, "vrag_dense_index_search", (self._h, _fp(q)), q.shape[0], k, allow, stream)
+
+    def search(self, queries: np.ndarray, k: int, stream=None) -> Tuple[np.ndarray, np.ndarray]:
+        return self._search(queries, k, None, stream)
+
+    def search_filtered(self, queries: np.ndarray, k: int, allow_words: np.ndarray, n_allow: int,
+                        stream=None) -> Tuple[np.ndarray, np.ndarray]:
+        """`search` over the rows `r < min(n_allow, len(self))` whose bit is set in `allow_words` (uint32, bit `r % 32` of
+        word `r // 32`, as `_bitmap` packs them): exact chains over the passing rows only (`vrag_dense_index_search_filtered`)."""
+        return self._search(queries, k, (allow_words, n_allow), stream)
+
+    def search_device(self, queries: np.ndarray, k: int, out_scores: int, out_ids: int, row_map: Optional[int] = None,
+                      n_map: int = 0, id_base: int = 0, stream=None) -> None:
+        """The same search with the `[Q, k]` lists left in HBM at the device addresses `out_scores` / `out_ids`
+        (global ids through the device table `row_map`, or `id_base + row`); kernels are only enqueued on `stream`."""
+        q = self._queries(queries)
+        _lib.check("vrag_dense_index_search_device", self._lib.vrag_dense_index_search_device(
+            self._h, _fp(q), q.shape[0], k, C.c_void_p(row_map) if row_map else None, n_map, id_base,
+            C.c_void_p(out_scores), C.c_void_p(out_ids), stream))
+
+    def run_resident(self, nq: int, k: int, stream=None) -> None:
+        _lib.check("vrag_dense_index_run_resident", self._lib.vrag_dense_index_run_resident(self._h, nq, k, stream))
+
+    def close(self):
+        ivf, self.ivf = getattr(self, "ivf", None), None
+        if ivf is not None:
+            ivf.close()
+        super().close()
+
+
+class IvfOverlay(_Handle):
+    """IVF_FLAT lists over a `DenseShard`'s resident rows (`vrag_ivf_index`): centroids, list offsets and row numbers only.
+    The shard must outlive it (`DenseShard.ivf` owns it and closes it first)."""
+
+    _destroy = "vrag_ivf_index_destroy"
+
+    def __init__(self, shard: DenseShard, nlist: int):
+        self.dim, self.nlist = shard.dim, int(nlist)
+        self._open("vrag_ivf_index_create", shard._h, self.nlist)
+
+    def set_centroids(self, centroids: np.ndarray) -> None:
+        c = np.ascontiguousarray(centroids, dtype=np.float32)
+        if c.shape != (self.nlist, self.dim):
+            raise ValueError(f"centroids must be [{self.nlist}, {self.dim}]")
+        _lib.check("vrag_ivf_index_set_centroids", self._lib.vrag_ivf_index_set_centroids(self._h, _fp(c)))
+
+    def train(self, iters: int = 10, max_train_rows: int = 1 << 62) -> None:
+        _lib.check("vrag_ivf_index_train", self._lib.vrag_ivf_index_train(self._h, int(iters), int(max_train_rows)))
+
+    def sync(self) -> None:
+        _lib.check("vrag_ivf_index_sync", self._lib.vrag_ivf_index_sync(self._h))
+
+    def stats(self) -> Dict[str, int]:
+        nlist, n, largest = C.c_int32(), C.c_int64(), C.c_int64()
+        _lib.check("vrag_ivf_index_stats", self._lib.vrag_ivf_index_stats(self._h, C.byref(nlist), C.byref(n), C.byref(largest)))
+        return {"nlist": nlist.value, "rows": n.value, "largest_list": largest.value}
+
+    def read(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(centroids `[nlist, dim]`, list_off `[nlist + 1]`, list_rows `[rows]`) after a `sync`."""
+        cent = np.empty((self.nlist, self.dim), np.float32)
+        off = np.empty(self.nlist + 1, np.uint32)
+        rows = np.empty(self.stats()["rows"], np.uint32)
+        _lib.check("vrag_ivf_index_read", self._lib.vrag_ivf_index_read(self._h, _fp(cent), _vp(off), _vp(rows) if len(rows) else None))
+        return cent, off, rows
+
+    def search(self, queries: np.ndarray, k: int, nprobe: int, stream=None, scanned: bool = False):
+        """(scores `[Q, k]`, ids `[Q, k]`) -- exact scores of the best rows of the `nprobe` nearest lists; with
+        `scanned=True` also the rows each query's lists hold."""
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        scores, ids, sp, ip = _topk_out(q.shape[0], k)
+        seen = np.empty(q.shape[0], np.int64) if scanned else None
+        _lib.check("vrag_ivf_index_search", self._lib.vrag_ivf_index_search(
+            self._h, _fp(q), q.shape[0], k, int(nprobe), sp, ip, _lp(seen) if scanned else None, stream))
+        return (scores, ids, seen) if scanned else (scores, ids)
+
+
+def dicts_to_csr(rows: Sequence[Dict[int, float]]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`{term: weight}` rows -> CSR (int64 indptr, int32 terms ascending within a row, float32 weights).  One pass of
+    C-level iteration plus a lexsort: a 1 M-document ingest or a 1 000-query batch does not loop in Python per entry."""
+    from itertools import chain
+
+    n = len(rows)
+    lens = np.fromiter((len(r) for r in rows), np.int64, n)
+    indptr = np.zeros(n + 1, np.int64)
+    np.cumsum(lens, out=indptr[1:])
+    total = int(indptr[-1])
+    terms = np.fromiter(chain.from_iterable(rows), np.int64, total)                       # iterating a dict yields its keys
+    weights = np.fromiter(chain.from_iterable(r.values() for r in rows), np.float64, total)
+    i32 = np.iinfo(np.int32)
+    if total and (terms.min() < i32.min or terms.max() > i32.max):
+        # checked on the int64 keys: a term that does not fit int32 would wrap in the cast below and pass the later range checks
+        # (terms that fit but lie outside the vocabulary are rejected there, by the caller or the C layer)
+        bad = int(np.searchsorted(indptr, np.nonzero((terms < i32.min) | (terms > i32.max))[0][0], side="right") - 1)
+        raise ValueError(f"sparse vector {bad} has a term outside the int32 range")
+    order = np.lexsort((terms, np.repeat(np.arange(n, dtype=np.int64), lens)))
+    return indptr, terms[order].astype(np.int32), weights[order].astype(np.float32)
+
+
+def _csr_args(indptr, indices, values):
+    """A CSR triple as the library takes it -- (indptr ptr, indices ptr, values ptr) -- and its row count."""
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    return (_lp(indptr), _ip(indices), _fp(values)), len(indptr) - 1
+
+
+class SparseShard(_Handle):
+    """One GPU's slice of the SPLADE corpus (immutable SELL-64 image built from CSR)."""
+
+    _destroy = "vrag_sparse_index_destroy"
+
+    def __init__(self, vocab: int, indptr: np.ndarray, indices: np.ndarray, values: np.ndarray, device: int = 0):
+        _lib.require_gpu()
+        self.vocab = vocab
+        csr, self.n_docs = _csr_args(indptr, indices, values)
+        self._open("vrag_sparse_index_create", vocab, self.n_docs, *csr, device)
+
+    def stats(self) -> Dict[str, int]:
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        _lib.check("vrag_sparse_index_stats", self._lib.vrag_sparse_index_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return {"n_docs": a.value, "nnz": b.value, "padded_nnz": c.value}
+
+    def _search(self, csr, k: int, allow, stream):
+        q, nq = _csr_args(*csr)
+        return _search_call(self._lib, "vrag_sparse_index_search", (self._h, *q), nq, k, allow, stream)
+
+    def search_csr(self, q_indptr, q_indices, q_values, k: int, stream=None) -> Tuple[np.ndarray, np.ndarray]:
+        return self._search((q_indptr, q_indices, q_values), k, None, stream)
+
+    def search(self, queries: Sequence[Dict[int, float]], k: int, stream=None):
+        return self.search_csr(*dicts_to_csr(queries), k, stream)
+
+    def search_filtered(self, queries: Sequence[Dict[int, float]], k: int, allow_words: np.ndarray, n_allow: int, stream=None):
+        """`search` over the documents `d < min(n_allow, n_docs)` whose bit is set in `allow_words` (see
+        `DenseShard.search_filtered`; `vrag_sparse_index_search_filtered`)."""
+        return self._search(dicts_to_csr(queries), k, (allow_words, n_allow), stream)
+
+    def search_device(self, queries: Sequence[Dict[int, float]], k: int, out_scores: int, out_ids: int,
+                      row_map: Optional[int] = None, n_map: int = 0, id_base: int = 0, stream=None) -> None:
+        """`search` with the lists left in HBM (see DenseShard.search_device)."""
+        q, nq = _csr_args(*dicts_to_csr(queries))
+        _lib.check("vrag_sparse_index_search_device", self._lib.vrag_sparse_index_search_device(
+            self._h, *q, nq, k, C.c_void_p(row_map) if row_map else None, n_map, id_base, C.c_void_p(out_scores),
+            C.c_void_p(out_ids), stream))
+
+    def run_resident(self, nq: int, k: int, stream=None) -> None:
+        _lib.check("vrag_sparse_index_run_resident", self._lib.vrag_sparse_index_run_resident(self._h, nq, k, stream))
+
+
+def _utf8_batch(texts: Sequence[str]) -> Tuple[bytes, np.ndarray]:
+    """Texts back to back as UTF-8 and their `[n + 1]` byte offsets."""
+    raw = [t.encode("utf-8", "surrogatepass") for t in texts]
+    off = np.zeros(len(raw) + 1, np.int64)
+    if raw:
+        np.cumsum([len(r) for r in raw], out=off[1:])
+    return b"".join(raw), off
+
+
+def _bitmap(mask: np.ndarray) -> np.ndarray:
+    """bool per row -> uint32 words, bit r % 32 of word r // 32 (include/vrag_amd.h, vrag_text_index_set_live)."""
+    bits = np.packbits(np.asarray(mask, dtype=bool), bitorder="little")
+    words = np.zeros((len(bits) + 3) // 4 * 4, np.uint8)
+    words[: len(bits)] = bits
+    return words.view(np.uint32)
+
+
+class TextIndex(_Handle):
+    """BM25 index of raw texts in HBM (`vrag_text_index_*`, csrc/fulltext.hip): the device tokenises, builds the postings,
+    keeps the live-row statistics and scores; the host computes idf in float64 (include/vrag_amd.h states the arithmetic)."""
+
+    _destroy = "vrag_text_index_destroy"
+
+    def __init__(self, k1: float = 1.2, b: float = 0.75, device: int = 0):
+        # a search is two library calls (query analysis: df and N; scoring: K_d): one hold of this lock keeps an `add` or a
+        # `set_live` from another thread out from between them, so both read one snapshot of the statistics
+        self._mu = threading.Lock()
+        self.k1, self.b = float(k1), float(b)
+        self._open("vrag_text_index_create", self.k1, self.b, device)
+
+    def add(self, texts: Sequence[str], fold: bool) -> None:
+        blob, off = _utf8_batch(texts)
+        with self._mu:
+            _lib.check("vrag_text_index_add", self._lib.vrag_text_index_add(self._h, blob, _lp(off), len(texts), int(bool(fold))))
+
+    def set_live(self, alive: np.ndarray) -> None:
+        words = _bitmap(alive)
+        with self._mu:
+            _lib.check("vrag_text_index_set_live", self._lib.vrag_text_index_set_live(self._h, words.ctypes.data, len(alive)))
+
+    def stats(self) -> Dict[str, int]:
+        v = [C.c_int64() for _ in range(5)]
+        _lib.check("vrag_text_index_stats", self._lib.vrag_text_index_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("rows", "live", "sum_dl", "segments", "postings"), (x.value for x in v)))
+
+    def set_corpus_stats(self, n_live_total: int, sum_dl_total: int) -> None:
+        """This index is one shard of a row-sharded corpus: `K_d` and the `N` of `query_terms` come from the corpus-wide
+        totals (the sums of every shard's `stats()["live"]` / `["sum_dl"]`) until they are set again; (0, 0) = its own."""
+        with self._mu:
+            _lib.check("vrag_text_index_set_corpus_stats", self._lib.vrag_text_index_set_corpus_stats(
+                self._h, int(n_live_total), int(sum_dl_total)))
+
+    def query_terms(self, queries: Sequence[str]):
+        """(indptr [Q+1], keys uint64, counts int32, df int64, N): the distinct terms of every query, ascending keys -- every
+        term of the query texts, with df = 0 for those the index does not hold."""
+        blob, off = _utf8_batch(queries)
+        cap = max(1, len(blob))
+        indptr = np.zeros(len(queries) + 1, np.int64)
+        keys, counts, df = np.zeros(cap, np.uint64), np.zeros(cap, np.int32), np.zeros(cap, np.int64)
+        n_live = C.c_int64()
+        _lib.check("vrag_text_index_query_terms", self._lib.vrag_text_index_query_terms(
+            self._h, blob, _lp(off), len(queries), cap, _lp(indptr), keys.ctypes.data, _ip(counts), _lp(df), C.byref(n_live)))
+        m = int(indptr[-1])
+        return indptr, keys[:m], counts[:m], df[:m], n_live.value
+
+    @staticmethod
+    def weights(counts: np.ndarray, df: np.ndarray, n_live: int) -> np.ndarray:
+        """w_t = fp32(count * idf), idf = ln(1 + (N - df + 0.5) / (df + 0.5)) in float64."""
+        df64 = df.astype(np.float64)
+        idf = np.log(1.0 + (float(n_live) - df64 + 0.5) / (df64 + 0.5))
+        return (counts.astype(np.float64) * idf).astype(np.float32)
+
+    def search(self, queries: Sequence[str], k: int, allow: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """`[Q, k]` scores and rows (-1 = no hit) of a batch of query texts: one device pass for the batch.  `allow`: bool per
+        row; rows beyond its length (added after it was built) are not returned."""
+        if len(queries) == 0:
+            return _topk_out(0, k, fill=True)[:2]
+        return self._search(queries, k, allow, None, None)
+
+    def search_sharded(self, queries: Sequence[str], k: int, allow: Optional[np.ndarray], n_live_total: int, sum_df, device_out=None):
+        """A shard's part of a search over a row-sharded corpus.  The term list depends on the query texts alone, so the df
+        vectors of all shards line up: `sum_df(df) -> corpus-wide df` (one collective per batch) sits between the query
+        analysis and the scoring, and the weights come from the summed `N` and df in float64 exactly as `weights` states.
+        Returns host `[Q, k]` (scores, LOCAL rows); with `device_out = (scores ptr, ids ptr, row_map ptr or None, n_map,
+        stream)` (k <= 64) the lists are left in HBM with global rows instead (`vrag_text_index_search_device`) and None is
+        returned."""
+        return self._search(queries, k, allow, (sum_df, n_live_total), device_out)
+
+    def _search(self, queries, k: int, allow, corpus, device_out):
+        """Query analysis, weights (`corpus = (sum_df, n_live_total)`: from the corpus-wide df and N) and scoring under one
+        hold of the lock; `head` = the arguments the host and the device form of the scoring call share."""
+        Q = len(queries)
+        words = _bitmap(allow) if allow is not None else None
+        with self._mu:
+            indptr, keys, counts, df, n_live = self.query_terms(queries)
+            if corpus is not None:
+                df, n_live = np.asarray(corpus[0](df), dtype=np.int64), corpus[1]
+            w = np.ascontiguousarray(self.weights(counts, df, n_live))
+            keys = np.ascontiguousarray(keys)
+            head = (self._h, _lp(indptr), keys.ctypes.data, _fp(w), Q, k, words.ctypes.data if words is not None else None,
+                    len(allow) if allow is not None else 0)
+            if device_out is not None:
+                out_s, out_i, row_map, n_map, stream = device_out
+                _lib.check("vrag_text_index_search_device", self._lib.vrag_text_index_search_device(
+                    *head, C.c_void_p(row_map) if row_map else None, n_map, 0, C.c_void_p(out_s), C.c_void_p(out_i), stream))
+                return None
+            scores, ids, sp, ip = _topk_out(Q, k, fill=True)
+            _lib.check("vrag_text_index_search", self._lib.vrag_text_index_search(*head, sp, ip))
+            return scores, ids
+
+
+def tokenize_keys(texts: Sequence[str], device: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """The analyzer alone (`vrag_text_tokenize`): token counts per text and every token's term key, in text order."""
+    lib = _lib.load()
+    blob, off = _utf8_batch(texts)
+    cap = max(1, len(blob))
+    counts = np.zeros(max(1, len(texts)), np.int32)
+    keys = np.zeros(cap, np.uint64)
+    n = C.c_int64()
+    _lib.check("vrag_text_tokenize", lib.vrag_text_tokenize(blob, _lp(off), len(texts), device, cap, _ip(counts), keys.ctypes.data, C.byref(n)))
+    return counts[: len(texts)], keys[: n.value]

@@ -14,7 +14,6 @@ from __future__ import annotations
 import ctypes as C
 import json
 import logging
-import re
 import threading
 from abc import ABC, abstractmethod
 from dataclasses import dataclass
@@ -23,12 +22,14 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
+# The layers under the store, re-exported here under the names callers and tests have always used.  The store resolves
+# DenseShard / SparseShard / IvfOverlay / TextIndex through THIS module's globals at call time (tests replace them here).
+from .shards import (_FP, _IP, _LP, DenseShard, IvfOverlay, SparseShard, TextIndex, _allow_words, _bitmap,  # noqa: F401
+                     _utf8_batch, dicts_to_csr, tokenize_keys)
+from .store_filter import _FILTER_TOKEN, _typed, parse_filter  # noqa: F401
+from .store_io import _NO_METADATA, _get_strings, _put_strings, _replace_into, _write_text, read_saved  # noqa: F401
 
 logger = logging.getLogger(__name__)
-
-_FP = C.POINTER(C.c_float)
-_LP = C.POINTER(C.c_int64)
-_IP = C.POINTER(C.c_int32)
 
 
 @dataclass
@@ -253,92 +254,6 @@ def convert_hits_to_results(hits: List[dict], dynamic_fields: Optional[List[str]
     return results
 
 
-# ---------------------------------------------------------------------------- device indexes
-def _allow_words(allow_words, n_allow: int) -> np.ndarray:
-    """The bitmap of a filtered search as contiguous uint32 words; ValueError when it is shorter than `n_allow` rows (the
-    library would read past it)."""
-    words = np.ascontiguousarray(allow_words, dtype=np.uint32).reshape(-1)
-    if n_allow < 0 or len(words) * 32 < n_allow:
-        raise ValueError(f"allow_words holds {len(words) * 32} bits, n_allow = {n_allow}")
-    return words
-
-
-class DenseShard:
-    """One GPU's slice of the dense corpus (rows appended in order; ids are local row numbers)."""
-
-    def __init__(self, dim: int, capacity: int, dtype: str = "bf16", device: int = 0, prefilter: bool = True):
-        """dtype "bf16" | "f32".  fp32 rows keep a bf16 prefilter image beside them unless `prefilter=False` (+50 % memory):
-        a search ranks the image for 64 candidates per query and re-scores those exactly -- same bits as the full fp32 scan
-        (include/vrag_amd.h, dtype 2), half the time for one query and a quarter for a batch of 256."""
-        self._lib = _lib.load()
-        _lib.require_gpu()
-        self.dim, self.capacity = dim, capacity
-        self.ivf: Optional["IvfOverlay"] = None    # an IVF_FLAT overlay over these rows (owned: closed before the shard)
-        self._h = C.c_void_p()
-        code = 0 if dtype == "bf16" else (2 if prefilter and dim % 4 == 0 else 1)
-        _lib.check("vrag_dense_index_create", self._lib.vrag_dense_index_create(dim, capacity, code, device, C.byref(self._h)))
-
-    def add(self, rows: np.ndarray) -> None:
-        rows = np.ascontiguousarray(rows, dtype=np.float32)
-        if rows.ndim != 2 or rows.shape[1] != self.dim:
-            raise ValueError(f"rows must be [n, {self.dim}]")
-        _lib.check("vrag_dense_index_add", self._lib.vrag_dense_index_add(self._h, rows.ctypes.data_as(_FP), rows.shape[0]))
-
-    def add_device(self, ptr: int, n: int, stream=None) -> None:
-        """Rows already in HBM (`ptr`: device address of fp32 `[n, dim]` on the shard's device): no host round trip."""
-        _lib.check("vrag_dense_index_add_device", self._lib.vrag_dense_index_add_device(self._h, C.c_void_p(int(ptr)), int(n), stream))
-
-    def __len__(self) -> int:
-        return int(self._lib.vrag_dense_index_size(self._h))
-
-    def search(self, queries: np.ndarray, k: int, stream=None) -> Tuple[np.ndarray, np.ndarray]:
-        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
-        scores = np.empty((q.shape[0], k), np.float32)
-        ids = np.empty((q.shape[0], k), np.int64)
-        _lib.check("vrag_dense_index_search", self._lib.vrag_dense_index_search(
-            self._h, q.ctypes.data_as(_FP), q.shape[0], k, scores.ctypes.data_as(_FP), ids.ctypes.data_as(_LP), stream))
-        return scores, ids
-
-    def search_filtered(self, queries: np.ndarray, k: int, allow_words: np.ndarray, n_allow: int,
-                        stream=None) -> Tuple[np.ndarray, np.ndarray]:
-        """`search` over the rows `r < min(n_allow, len(self))` whose bit is set in `allow_words` (uint32, bit `r % 32` of
-        word `r // 32`, as `_bitmap` packs them): exact chains over the passing rows only (`vrag_dense_index_search_filtered`)."""
-        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
-        words = _allow_words(allow_words, n_allow)
-        scores = np.empty((q.shape[0], k), np.float32)
-        ids = np.empty((q.shape[0], k), np.int64)
-        _lib.check("vrag_dense_index_search_filtered", self._lib.vrag_dense_index_search_filtered(
-            self._h, q.ctypes.data_as(_FP), q.shape[0], k, words.ctypes.data_as(C.c_void_p), int(n_allow),
-            scores.ctypes.data_as(_FP), ids.ctypes.data_as(_LP), stream))
-        return scores, ids
-
-    def search_device(self, queries: np.ndarray, k: int, out_scores: int, out_ids: int, row_map: Optional[int] = None,
-                      n_map: int = 0, id_base: int = 0, stream=None) -> None:
-        """The same search with the `[Q, k]` lists left in HBM at the device addresses `out_scores` / `out_ids`
-        (global ids through the device table `row_map`, or `id_base + row`); kernels are only enqueued on `stream`."""
-        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
-        _lib.check("vrag_dense_index_search_device", self._lib.vrag_dense_index_search_device(
-            self._h, q.ctypes.data_as(_FP), q.shape[0], k, C.c_void_p(row_map) if row_map else None, n_map, id_base,
-            C.c_void_p(out_scores), C.c_void_p(out_ids), stream))
-
-    def run_resident(self, nq: int, k: int, stream=None) -> None:
-        _lib.check("vrag_dense_index_run_resident", self._lib.vrag_dense_index_run_resident(self._h, nq, k, stream))
-
-    def close(self):
-        if self.ivf is not None:
-            self.ivf.close()
-            self.ivf = None
-        if self._h:
-            self._lib.vrag_dense_index_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 IVF_MIN_ROWS = 4096       # below this a store with index_type="IVF_FLAT" searches FLAT
 IVF_NLIST_MAX = 16384     # vrag_ivf_index_create
 IVF_MIN_LIST_ROWS = 39    # rows per list a training needs, as faiss' k-means asks for (min_points_per_centroid)
@@ -381,311 +296,7 @@ def check_index_config(index_type: str, nlist: int, nprobe: int, sharded: bool) 
         raise ValueError("index_type='IVF_FLAT' is single-GPU: sharded stores (distributed=True or a comm) keep FLAT")
 
 
-class IvfOverlay:
-    """IVF_FLAT lists over a `DenseShard`'s resident rows (`vrag_ivf_index`): centroids, list offsets and row numbers only.
-    The shard must outlive it (`DenseShard.ivf` owns it and closes it first)."""
-
-    def __init__(self, shard: DenseShard, nlist: int):
-        self._lib = _lib.load()
-        self.dim, self.nlist = shard.dim, int(nlist)
-        self._h = C.c_void_p()
-        _lib.check("vrag_ivf_index_create", self._lib.vrag_ivf_index_create(shard._h, self.nlist, C.byref(self._h)))
-
-    def set_centroids(self, centroids: np.ndarray) -> None:
-        c = np.ascontiguousarray(centroids, dtype=np.float32)
-        if c.shape != (self.nlist, self.dim):
-            raise ValueError(f"centroids must be [{self.nlist}, {self.dim}]")
-        _lib.check("vrag_ivf_index_set_centroids", self._lib.vrag_ivf_index_set_centroids(self._h, c.ctypes.data_as(_FP)))
-
-    def train(self, iters: int = 10, max_train_rows: int = 1 << 62) -> None:
-        _lib.check("vrag_ivf_index_train", self._lib.vrag_ivf_index_train(self._h, int(iters), int(max_train_rows)))
-
-    def sync(self) -> None:
-        _lib.check("vrag_ivf_index_sync", self._lib.vrag_ivf_index_sync(self._h))
-
-    def stats(self) -> Dict[str, int]:
-        nlist, n, largest = C.c_int32(), C.c_int64(), C.c_int64()
-        _lib.check("vrag_ivf_index_stats", self._lib.vrag_ivf_index_stats(self._h, C.byref(nlist), C.byref(n), C.byref(largest)))
-        return {"nlist": nlist.value, "rows": n.value, "largest_list": largest.value}
-
-    def read(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """(centroids `[nlist, dim]`, list_off `[nlist + 1]`, list_rows `[rows]`) after a `sync`."""
-        cent = np.empty((self.nlist, self.dim), np.float32)
-        off = np.empty(self.nlist + 1, np.uint32)
-        rows = np.empty(self.stats()["rows"], np.uint32)
-        _lib.check("vrag_ivf_index_read", self._lib.vrag_ivf_index_read(
-            self._h, cent.ctypes.data_as(_FP), off.ctypes.data_as(C.c_void_p), rows.ctypes.data_as(C.c_void_p) if len(rows) else None))
-        return cent, off, rows
-
-    def search(self, queries: np.ndarray, k: int, nprobe: int, stream=None, scanned: bool = False):
-        """(scores `[Q, k]`, ids `[Q, k]`) -- exact scores of the best rows of the `nprobe` nearest lists; with
-        `scanned=True` also the rows each query's lists hold."""
-        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
-        scores = np.empty((q.shape[0], k), np.float32)
-        ids = np.empty((q.shape[0], k), np.int64)
-        seen = np.empty(q.shape[0], np.int64) if scanned else None
-        _lib.check("vrag_ivf_index_search", self._lib.vrag_ivf_index_search(
-            self._h, q.ctypes.data_as(_FP), q.shape[0], k, int(nprobe), scores.ctypes.data_as(_FP), ids.ctypes.data_as(_LP),
-            seen.ctypes.data_as(_LP) if scanned else None, stream))
-        return (scores, ids, seen) if scanned else (scores, ids)
-
-    def close(self):
-        if self._h:
-            self._lib.vrag_ivf_index_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def dicts_to_csr(rows: Sequence[Dict[int, float]]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """`{term: weight}` rows -> CSR (int64 indptr, int32 terms ascending within a row, float32 weights).  One pass of
-    C-level iteration plus a lexsort: a 1 M-document ingest or a 1 000-query batch does not loop in Python per entry."""
-    from itertools import chain
-
-    n = len(rows)
-    lens = np.fromiter((len(r) for r in rows), np.int64, n)
-    indptr = np.zeros(n + 1, np.int64)
-    np.cumsum(lens, out=indptr[1:])
-    total = int(indptr[-1])
-    terms = np.fromiter(chain.from_iterable(rows), np.int64, total)                       # iterating a dict yields its keys
-    weights = np.fromiter(chain.from_iterable(r.values() for r in rows), np.float64, total)
-    i32 = np.iinfo(np.int32)
-    if total and (terms.min() < i32.min or terms.max() > i32.max):
-        # checked on the int64 keys: a term that does not fit int32 would wrap in the cast below and pass the later range checks
-        # (terms that fit but lie outside the vocabulary are rejected there, by the caller or the C layer)
-        bad = int(np.searchsorted(indptr, np.nonzero((terms < i32.min) | (terms > i32.max))[0][0], side="right") - 1)
-        raise ValueError(f"sparse vector {bad} has a term outside the int32 range")
-    order = np.lexsort((terms, np.repeat(np.arange(n, dtype=np.int64), lens)))
-    return indptr, terms[order].astype(np.int32), weights[order].astype(np.float32)
-
-
-class SparseShard:
-    """One GPU's slice of the SPLADE corpus (immutable SELL-64 image built from CSR)."""
-
-    def __init__(self, vocab: int, indptr: np.ndarray, indices: np.ndarray, values: np.ndarray, device: int = 0):
-        self._lib = _lib.load()
-        _lib.require_gpu()
-        self.vocab = vocab
-        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
-        indices = np.ascontiguousarray(indices, dtype=np.int32)
-        values = np.ascontiguousarray(values, dtype=np.float32)
-        self.n_docs = len(indptr) - 1
-        self._h = C.c_void_p()
-        _lib.check("vrag_sparse_index_create", self._lib.vrag_sparse_index_create(
-            vocab, self.n_docs, indptr.ctypes.data_as(_LP), indices.ctypes.data_as(_IP), values.ctypes.data_as(_FP),
-            device, C.byref(self._h)))
-
-    def stats(self) -> Dict[str, int]:
-        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
-        _lib.check("vrag_sparse_index_stats", self._lib.vrag_sparse_index_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
-        return {"n_docs": a.value, "nnz": b.value, "padded_nnz": c.value}
-
-    def search_csr(self, q_indptr, q_indices, q_values, k: int, stream=None) -> Tuple[np.ndarray, np.ndarray]:
-        q_indptr = np.ascontiguousarray(q_indptr, dtype=np.int64)
-        q_indices = np.ascontiguousarray(q_indices, dtype=np.int32)
-        q_values = np.ascontiguousarray(q_values, dtype=np.float32)
-        nq = len(q_indptr) - 1
-        scores = np.empty((nq, k), np.float32)
-        ids = np.empty((nq, k), np.int64)
-        _lib.check("vrag_sparse_index_search", self._lib.vrag_sparse_index_search(
-            self._h, q_indptr.ctypes.data_as(_LP), q_indices.ctypes.data_as(_IP), q_values.ctypes.data_as(_FP), nq, k,
-            scores.ctypes.data_as(_FP), ids.ctypes.data_as(_LP), stream))
-        return scores, ids
-
-    def search(self, queries: Sequence[Dict[int, float]], k: int, stream=None):
-        return self.search_csr(*dicts_to_csr(queries), k, stream)
-
-    def search_filtered(self, queries: Sequence[Dict[int, float]], k: int, allow_words: np.ndarray, n_allow: int, stream=None):
-        """`search` over the documents `d < min(n_allow, n_docs)` whose bit is set in `allow_words` (see
-        `DenseShard.search_filtered`; `vrag_sparse_index_search_filtered`)."""
-        q_indptr, q_indices, q_values = dicts_to_csr(queries)
-        words = _allow_words(allow_words, n_allow)
-        nq = len(q_indptr) - 1
-        scores = np.empty((nq, k), np.float32)
-        ids = np.empty((nq, k), np.int64)
-        _lib.check("vrag_sparse_index_search_filtered", self._lib.vrag_sparse_index_search_filtered(
-            self._h, q_indptr.ctypes.data_as(_LP), q_indices.ctypes.data_as(_IP), q_values.ctypes.data_as(_FP), nq, k,
-            words.ctypes.data_as(C.c_void_p), int(n_allow), scores.ctypes.data_as(_FP), ids.ctypes.data_as(_LP), stream))
-        return scores, ids
-
-    def search_device(self, queries: Sequence[Dict[int, float]], k: int, out_scores: int, out_ids: int,
-                      row_map: Optional[int] = None, n_map: int = 0, id_base: int = 0, stream=None) -> None:
-        """`search` with the lists left in HBM (see DenseShard.search_device)."""
-        q_indptr, q_indices, q_values = dicts_to_csr(queries)
-        _lib.check("vrag_sparse_index_search_device", self._lib.vrag_sparse_index_search_device(
-            self._h, q_indptr.ctypes.data_as(_LP), q_indices.ctypes.data_as(_IP), q_values.ctypes.data_as(_FP),
-            len(q_indptr) - 1, k, C.c_void_p(row_map) if row_map else None, n_map, id_base, C.c_void_p(out_scores),
-            C.c_void_p(out_ids), stream))
-
-    def run_resident(self, nq: int, k: int, stream=None) -> None:
-        _lib.check("vrag_sparse_index_run_resident", self._lib.vrag_sparse_index_run_resident(self._h, nq, k, stream))
-
-    def close(self):
-        if self._h:
-            self._lib.vrag_sparse_index_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _utf8_batch(texts: Sequence[str]) -> Tuple[bytes, np.ndarray]:
-    """Texts back to back as UTF-8 and their `[n + 1]` byte offsets."""
-    raw = [t.encode("utf-8", "surrogatepass") for t in texts]
-    off = np.zeros(len(raw) + 1, np.int64)
-    if raw:
-        np.cumsum([len(r) for r in raw], out=off[1:])
-    return b"".join(raw), off
-
-
-def _bitmap(mask: np.ndarray) -> np.ndarray:
-    """bool per row -> uint32 words, bit r % 32 of word r // 32 (include/vrag_amd.h, vrag_text_index_set_live)."""
-    bits = np.packbits(np.asarray(mask, dtype=bool), bitorder="little")
-    words = np.zeros((len(bits) + 3) // 4 * 4, np.uint8)
-    words[: len(bits)] = bits
-    return words.view(np.uint32)
-
-
-class TextIndex:
-    """BM25 index of raw texts in HBM (`vrag_text_index_*`, csrc/fulltext.hip): the device tokenises, builds the postings,
-    keeps the live-row statistics and scores; the host computes idf in float64 (include/vrag_amd.h states the arithmetic)."""
-
-    def __init__(self, k1: float = 1.2, b: float = 0.75, device: int = 0):
-        self._lib = _lib.load()
-        # a search is two library calls (query analysis: df and N; scoring: K_d): one hold of this lock keeps an `add` or a
-        # `set_live` from another thread out from between them, so both read one snapshot of the statistics
-        self._mu = threading.Lock()
-        self._h = C.c_void_p()
-        self.k1, self.b = float(k1), float(b)
-        _lib.check("vrag_text_index_create", self._lib.vrag_text_index_create(self.k1, self.b, device, C.byref(self._h)))
-
-    def add(self, texts: Sequence[str], fold: bool) -> None:
-        blob, off = _utf8_batch(texts)
-        with self._mu:
-            _lib.check("vrag_text_index_add", self._lib.vrag_text_index_add(
-                self._h, blob, off.ctypes.data_as(C.POINTER(C.c_int64)), len(texts), int(bool(fold))))
-
-    def set_live(self, alive: np.ndarray) -> None:
-        words = _bitmap(alive)
-        with self._mu:
-            _lib.check("vrag_text_index_set_live", self._lib.vrag_text_index_set_live(self._h, words.ctypes.data, len(alive)))
-
-    def stats(self) -> Dict[str, int]:
-        v = [C.c_int64() for _ in range(5)]
-        _lib.check("vrag_text_index_stats", self._lib.vrag_text_index_stats(self._h, *[C.byref(x) for x in v]))
-        return dict(zip(("rows", "live", "sum_dl", "segments", "postings"), (x.value for x in v)))
-
-    def set_corpus_stats(self, n_live_total: int, sum_dl_total: int) -> None:
-        """This index is one shard of a row-sharded corpus: `K_d` and the `N` of `query_terms` come from the corpus-wide
-        totals (the sums of every shard's `stats()["live"]` / `["sum_dl"]`) until they are set again; (0, 0) = its own."""
-        with self._mu:
-            _lib.check("vrag_text_index_set_corpus_stats", self._lib.vrag_text_index_set_corpus_stats(
-                self._h, int(n_live_total), int(sum_dl_total)))
-
-    def query_terms(self, queries: Sequence[str]):
-        """(indptr [Q+1], keys uint64, counts int32, df int64, N): the distinct terms of every query, ascending keys -- every
-        term of the query texts, with df = 0 for those the index does not hold."""
-        blob, off = _utf8_batch(queries)
-        cap = max(1, len(blob))
-        indptr = np.zeros(len(queries) + 1, np.int64)
-        keys, counts, df = np.zeros(cap, np.uint64), np.zeros(cap, np.int32), np.zeros(cap, np.int64)
-        n_live = C.c_int64()
-        _lib.check("vrag_text_index_query_terms", self._lib.vrag_text_index_query_terms(
-            self._h, blob, off.ctypes.data_as(C.POINTER(C.c_int64)), len(queries), cap, indptr.ctypes.data_as(C.POINTER(C.c_int64)),
-            keys.ctypes.data, counts.ctypes.data_as(C.POINTER(C.c_int32)), df.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(n_live)))
-        m = int(indptr[-1])
-        return indptr, keys[:m], counts[:m], df[:m], n_live.value
-
-    @staticmethod
-    def weights(counts: np.ndarray, df: np.ndarray, n_live: int) -> np.ndarray:
-        """w_t = fp32(count * idf), idf = ln(1 + (N - df + 0.5) / (df + 0.5)) in float64."""
-        df64 = df.astype(np.float64)
-        idf = np.log(1.0 + (float(n_live) - df64 + 0.5) / (df64 + 0.5))
-        return (counts.astype(np.float64) * idf).astype(np.float32)
-
-    def search(self, queries: Sequence[str], k: int, allow: Optional[np.ndarray] = None) -> Tuple[np.ndarray, np.ndarray]:
-        """`[Q, k]` scores and rows (-1 = no hit) of a batch of query texts: one device pass for the batch.  `allow`: bool per
-        row; rows beyond its length (added after it was built) are not returned."""
-        Q = len(queries)
-        scores = np.full((Q, k), -np.inf, np.float32)
-        ids = np.full((Q, k), -1, np.int64)
-        if Q == 0:
-            return scores, ids
-        words = _bitmap(allow) if allow is not None else None
-        with self._mu:
-            self._search_locked(queries, k, allow, words, scores, ids)
-        return scores, ids
-
-    def _search_locked(self, queries, k, allow, words, scores, ids) -> None:
-        Q = len(queries)
-        indptr, keys, counts, df, n_live = self.query_terms(queries)
-        w = np.ascontiguousarray(self.weights(counts, df, n_live))
-        keys = np.ascontiguousarray(keys)
-        _lib.check("vrag_text_index_search", self._lib.vrag_text_index_search(
-            self._h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), keys.ctypes.data, w.ctypes.data_as(C.POINTER(C.c_float)), Q, k,
-            words.ctypes.data if words is not None else None, len(allow) if allow is not None else 0,
-            scores.ctypes.data_as(C.POINTER(C.c_float)), ids.ctypes.data_as(C.POINTER(C.c_int64))))
-
-    def search_sharded(self, queries: Sequence[str], k: int, allow: Optional[np.ndarray], n_live_total: int, sum_df, device_out=None):
-        """A shard's part of a search over a row-sharded corpus.  The term list depends on the query texts alone, so the df
-        vectors of all shards line up: `sum_df(df) -> corpus-wide df` (one collective per batch) sits between the query
-        analysis and the scoring, and the weights come from the summed `N` and df in float64 exactly as `weights` states.
-        Returns host `[Q, k]` (scores, LOCAL rows); with `device_out = (scores ptr, ids ptr, row_map ptr or None, n_map,
-        stream)` (k <= 64) the lists are left in HBM with global rows instead (`vrag_text_index_search_device`) and None is
-        returned."""
-        Q = len(queries)
-        words = _bitmap(allow) if allow is not None else None
-        with self._mu:
-            indptr, keys, counts, df, _n = self.query_terms(queries)
-            w = np.ascontiguousarray(self.weights(counts, np.asarray(sum_df(df), dtype=np.int64), n_live_total))
-            keys = np.ascontiguousarray(keys)
-            head = (self._h, indptr.ctypes.data_as(C.POINTER(C.c_int64)), keys.ctypes.data, w.ctypes.data_as(C.POINTER(C.c_float)), Q, k,
-                    words.ctypes.data if words is not None else None, len(allow) if allow is not None else 0)
-            if device_out is not None:
-                out_s, out_i, row_map, n_map, stream = device_out
-                _lib.check("vrag_text_index_search_device", self._lib.vrag_text_index_search_device(
-                    *head, C.c_void_p(row_map) if row_map else None, n_map, 0, C.c_void_p(out_s), C.c_void_p(out_i), stream))
-                return None
-            scores = np.full((Q, k), -np.inf, np.float32)
-            ids = np.full((Q, k), -1, np.int64)
-            _lib.check("vrag_text_index_search", self._lib.vrag_text_index_search(
-                *head, scores.ctypes.data_as(C.POINTER(C.c_float)), ids.ctypes.data_as(C.POINTER(C.c_int64))))
-            return scores, ids
-
-    def close(self):
-        if self._h:
-            self._lib.vrag_text_index_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def tokenize_keys(texts: Sequence[str], device: int = 0) -> Tuple[np.ndarray, np.ndarray]:
-    """The analyzer alone (`vrag_text_tokenize`): token counts per text and every token's term key, in text order."""
-    lib = _lib.load()
-    blob, off = _utf8_batch(texts)
-    cap = max(1, len(blob))
-    counts = np.zeros(max(1, len(texts)), np.int32)
-    keys = np.zeros(cap, np.uint64)
-    n = C.c_int64()
-    _lib.check("vrag_text_tokenize", lib.vrag_text_tokenize(blob, off.ctypes.data_as(C.POINTER(C.c_int64)), len(texts), device, cap,
-                                                            counts.ctypes.data_as(C.POINTER(C.c_int32)), keys.ctypes.data, C.byref(n)))
-    return counts[: len(texts)], keys[: n.value]
-
-
 _JSON_PLAIN = (str, int, float, bool, type(None))
-_NO_METADATA: Dict[str, Any] = {}
 
 
 def json_serialize_safe(obj: Any) -> Any:
@@ -813,204 +424,6 @@ def _merge_parts(scores: np.ndarray, rows: np.ndarray, k: int, device: int) -> T
     return merge_topk_device(scores, rows, k, device)
 
 
-# ---------------------------------------------------------------------------- filters
-_FILTER_TOKEN = re.compile(r"""\s*(?:(?P<meta>metadata\[\s*["'](?P<mkey>[^"']+)["']\s*\])|(?P<str>"[^"]*"|'[^']*')"""
-                           r"""|(?P<num>-?(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?)"""
-                           r"""|(?P<op>==|!=|<=|>=|<|>|&&|\|\||[()\[\],])|(?P<word>\w+))""")
-
-
-def _typed(value: Any):
-    """Comparison key of a metadata value or a filter literal: JSON semantics, not text -- a number equals a number
-    (2020 == 2020.0), a string equals a string ("5" != 5), booleans only booleans; anything else (None, a missing
-    key, lists, dicts) equals nothing."""
-    if isinstance(value, bool):
-        return ("b", value)
-    if isinstance(value, (int, float)):
-        return ("n", float(value))
-    if isinstance(value, str):
-        return ("s", value)
-    return None
-
-
-def parse_filter(expr: str):
-    """Compiles the subset of Milvus boolean expressions the store supports into `predicate(metadata: dict) -> bool`:
-    `field == value`, `field != value`, `field in [v, ...]`, `field < / <= / > / >= value`, combined with `and` / `&&`,
-    `or` / `||`, `not` and parentheses.  field = `metadata["key"]` (the Local dialect) or a bare `key` (the Cloud
-    dialect: index.py:735-739); value = a quoted string, a number (`7`, `-2.5`, `1e3`) or `true` / `false`.
-    Comparisons are typed like Milvus' JSON path match: numbers against numeric metadata, strings against text,
-    booleans against booleans; a missing key equals nothing (so `!=` holds for it).  Anything else raises ValueError --
-    a filter is never silently ignored."""
-    toks, pos = [], 0
-    while pos < len(expr):
-        if expr[pos:].strip() == "":
-            break
-        m = _FILTER_TOKEN.match(expr, pos)
-        if not m:
-            raise ValueError(f"GpuVectorStore: cannot parse filter at {expr[pos:]!r}")
-        pos = m.end()
-        if m.group("meta"):
-            toks.append(("field", m.group("mkey")))
-        elif m.group("str"):
-            toks.append(("val", m.group("str")[1:-1]))
-        elif m.group("num"):
-            toks.append(("val", float(m.group("num"))))
-        elif m.group("op"):
-            toks.append(("op", m.group("op")))
-        else:
-            w = m.group("word")
-            if w.lower() in ("and", "or", "not", "in"):
-                toks.append(("op", w.lower()))
-            elif w.lower() in ("true", "false"):
-                toks.append(("val", w.lower() == "true"))
-            else:
-                toks.append(("field", w))
-    i = 0
-
-    def peek():
-        return toks[i] if i < len(toks) else (None, None)
-
-    def take(kind=None, value=None):
-        nonlocal i
-        k, v = peek()
-        if k is None or (kind and k != kind) or (value is not None and v != value):
-            raise ValueError(f"GpuVectorStore: unsupported filter {expr!r}")
-        i += 1
-        return v
-
-    def comparison():
-        if peek() == ("op", "("):
-            take()
-            f = disjunction()
-            take("op", ")")
-            return f
-        if peek() == ("op", "not"):
-            take()
-            g = comparison()
-            return lambda md: not g(md)
-        key = take("field")
-        op = take("op")
-        if op in ("==", "!="):
-            want = _typed(take("val"))
-            if op == "!=":
-                return lambda md: _typed(md.get(key)) != want
-            f = lambda md: _typed(md.get(key)) == want   # noqa: E731
-            f.lookup = (key, [want])                      # lets the store answer from a per-key value index
-            return f
-        if op == "in":
-            take("op", "[")
-            vals = [_typed(take("val"))]
-            while peek() == ("op", ","):
-                take()
-                vals.append(_typed(take("val")))
-            take("op", "]")
-            vs = set(vals)
-            f = lambda md: _typed(md.get(key)) in vs      # noqa: E731
-            f.lookup = (key, vals)
-            return f
-        if op in ("<", "<=", ">", ">="):
-            import operator
-
-            cmp = {"<": operator.lt, "<=": operator.le, ">": operator.gt, ">=": operator.ge}[op]
-            kind, bound = _typed(take("val"))
-            if kind == "b":
-                raise ValueError(f"GpuVectorStore: ordering comparison with a boolean in filter {expr!r}")
-
-            def ordered(md):
-                have = _typed(md.get(key))
-                return have is not None and have[0] == kind and cmp(have[1], bound)
-            return ordered
-        raise ValueError(f"GpuVectorStore: unsupported operator {op!r} in filter {expr!r}")
-
-    def conjunction():
-        f = comparison()
-        while peek() in (("op", "and"), ("op", "&&")):
-            take()
-            g, h = f, comparison()
-            f = (lambda a, b: lambda md: a(md) and b(md))(g, h)
-        return f
-
-    def disjunction():
-        f = conjunction()
-        while peek() in (("op", "or"), ("op", "||")):
-            take()
-            g, h = f, conjunction()
-            f = (lambda a, b: lambda md: a(md) or b(md))(g, h)
-        return f
-
-    pred = disjunction()
-    if i != len(toks):
-        raise ValueError(f"GpuVectorStore: unsupported filter {expr!r}")
-    return pred
-
-
-def _replace_into(path: str, name: str, writer) -> None:
-    """Writes beside the final name and renames into place: a reader never sees half a file."""
-    import os
-
-    tmp = os.path.join(path, f".{name}.tmp{os.getpid()}")
-    writer(tmp)
-    os.replace(tmp, os.path.join(path, name))
-
-
-def _write_text(file: str, text: str) -> None:
-    with open(file, "w", encoding="utf-8", newline="") as f:
-        f.write(text)
-
-
-def _put_strings(path: str, stem: str, col: Sequence[str]) -> None:
-    """A column of strings as `{stem}.txt`: the rows joined by NUL (one C-level join / split for 10^7 rows); a column
-    holding a NUL itself or a non-string goes to `{stem}.json` instead."""
-    import os
-
-    blob = None
-    try:
-        blob = "\x00".join(col)
-        if blob.count("\x00") != max(0, len(col) - 1):
-            blob = None
-    except TypeError:
-        blob = None
-    # new file first (write beside + rename: a reader never sees the column missing), then the other extension's stale file
-    if blob is not None:
-        _replace_into(path, f"{stem}.txt", lambda tmp: _write_text(tmp, blob))
-        stale = f"{stem}.json"
-    else:
-        _replace_into(path, f"{stem}.json", lambda tmp: _write_text(tmp, json.dumps(list(col), ensure_ascii=False)))
-        stale = f"{stem}.txt"
-    if os.path.exists(os.path.join(path, stale)):
-        os.remove(os.path.join(path, stale))
-
-
-def _get_strings(path: str, stem: str, n: int) -> List[str]:
-    import os
-
-    txt, js = os.path.join(path, f"{stem}.txt"), os.path.join(path, f"{stem}.json")
-
-    def read_txt():
-        with open(txt, encoding="utf-8", newline="") as f:
-            return f.read().split("\x00") if n else []
-
-    def read_json():
-        with open(js, encoding="utf-8") as f:
-            return json.load(f)
-
-    if os.path.exists(txt) and os.path.exists(js):
-        # an overwrite was interrupted between the rename of the new file and the removal of the old one: the newer file wins;
-        # with equal timestamps (coarse clocks, restored backups) the one that holds the manifest's row count does
-        mt, mj = os.path.getmtime(txt), os.path.getmtime(js)
-        if mt != mj:
-            col = read_json() if mj > mt else read_txt()
-        else:
-            col = read_txt()
-            if len(col) != n:
-                col = read_json()
-    elif os.path.exists(txt):
-        col = read_txt()
-    else:
-        col = read_json()
-    if len(col) != n:
-        raise ValueError(f"{path}: {stem} holds {len(col)} rows, expected {n}")
-    return col
-
 
 # ---------------------------------------------------------------------------- the store
 class GpuVectorStore(VectorStore):
@@ -1028,8 +441,8 @@ class GpuVectorStore(VectorStore):
     (the reference itself only builds `metadata["document_id"] == "..."`, index.py:735-739); anything else is
     rejected loudly.  Filters and deletes act before the search like Milvus' (a selective filter still returns its
     best rows): `_topk_rows` re-runs short queries on a cached shard of just the passing rows.
-    A search may ask for at most `K_LIMIT` = 1024 rows per method (hybrid search asks for 2 * top_k, so top_k <= 512
-    there); more raises ValueError -- never a silently shorter list.
+    Every method of a search returns up to `K_LIMIT` = 1024 rows (hybrid search asks for 2 * top_k, so top_k <= 512
+    there); asking for more raises ValueError -- never a silently shorter list.
 
     Host layout (columnar, sized for 10^7 rows): ids in one list with a lazily built id -> row table for deletes; unit
     dense rows in one growing `[n, dim]` fp32 array; sparse rows as one growing CSR; liveness as a bool column.
@@ -1513,6 +926,43 @@ class GpuVectorStore(VectorStore):
         norms = np.sqrt((rows_q * rows_q).sum(axis=1, dtype=np.float32))
         return rows_q / np.where(norms > 0, norms, np.float32(1.0))[:, None]
 
+    def _segment_lists(self, parts, mapping: Optional[np.ndarray], Q: int, k: int, search_one):
+        """The segment loop of every host route -> this rank's (`scores [Q, k]`, GLOBAL `rows [Q, k]`, -1 = no hit).
+        `search_one(shard, base)` returns a segment's (scores, LOCAL rows); `mapping[j]` = global row of local row j (None =
+        the resident table).  Lists of several segments are merged on the GPU; no segment gives empty lists."""
+        found_lists = []
+        for shard, base in parts:
+            sc, local = search_one(shard, base)
+            # the resident table is read AFTER the kernel returned: every row the kernel can have seen is in it (`_flush`)
+            rows_of = mapping if mapping is not None else self._main_rows
+            at = local + base
+            found = (local >= 0) & (at < len(rows_of))
+            g = np.where(found, rows_of[np.where(found, at, 0)], -1) if len(rows_of) else np.full_like(local, -1)
+            found_lists.append((sc, g))
+        if not found_lists:
+            return np.full((Q, k), -np.inf, np.float32), np.full((Q, k), -1, np.int64)
+        if len(found_lists) == 1:
+            return found_lists[0]
+        return _merge_parts(np.stack([np.where(g >= 0, sc, -np.inf).astype(np.float32) for sc, g in found_lists]),
+                            np.stack([g for _sc, g in found_lists]), k, self.device)
+
+    def _exchange_host(self, scores: np.ndarray, rows: np.ndarray, k: int):
+        """This rank's host lists -> the lists merged over all ranks; a store without an exchange keeps its own."""
+        # The bitmap route (`_filtered_topk`) never gets here with `comm.on_gpu`: it produces host lists, which the
+        # device-resident exchange does not carry, so the constructor keeps such a store on filter_route="subset".
+        comm = self._comm
+        if comm is not None and (self._world > 1 or comm.on_gpu):
+            return comm.allgather_merge(scores, rows, k)
+        return scores, rows
+
+    def _resident_slots(self, Q: int, k: int):
+        """(current stream of the store's device, the exchange's HBM payload for `[Q, k]` lists, its ids ptr, its scores ptr)."""
+        import torch
+
+        stream = C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
+        payload, ids_ptr, scores_ptr = self._comm.exchange_buffers(Q, k)
+        return stream, payload, ids_ptr, scores_ptr
+
     def _device_topk(self, kind: str, parts, shard_rows: Optional[np.ndarray], queries: Sequence[Any], k: int,
                      rows_dev=None, nprobe: Optional[int] = None):
         """Top-k of `queries` over one (possibly sharded) set of rows -> (`scores [Q, k]`, GLOBAL `rows [Q, k]`, -1 = no
@@ -1526,44 +976,26 @@ class GpuVectorStore(VectorStore):
         q_in = self._unit_queries(queries) if kind == "dense" and parts else queries
         if comm is not None and comm.on_gpu and k <= self.DEVICE_K and (rows_dev is not None or not parts):
             return self._device_topk_resident(parts, rows_dev, q_in, Q, k)
-        if not parts:
-            scores = np.full((Q, k), -np.inf, np.float32)
-            rows = np.full((Q, k), -1, np.int64)
-        else:
-            found_lists = []
-            for shard, base in parts:
-                ivf = getattr(shard, "ivf", None) if nprobe is not None and k <= IVF_K_MAX else None
-                if ivf is not None:
-                    sc, local = ivf.search(q_in, k, nprobe)
-                else:
-                    sc, local = shard.search(q_in, k)      # dicts_to_csr converts sparse keys / weights to int32 / float32
-                mapping = shard_rows if shard_rows is not None else self._main_rows
-                at = local + base
-                found = (local >= 0) & (at < len(mapping))
-                g = np.where(found, mapping[np.where(found, at, 0)], -1) if len(mapping) else np.full_like(local, -1)
-                found_lists.append((sc, g))
-            if len(found_lists) == 1:
-                scores, rows = found_lists[0]
-            else:
-                scores, rows = _merge_parts(np.stack([np.where(g >= 0, sc, -np.inf).astype(np.float32) for sc, g in found_lists]),
-                                            np.stack([g for _sc, g in found_lists]), k, self.device)
-        if comm is not None and (self._world > 1 or comm.on_gpu):
-            scores, rows = comm.allgather_merge(scores, rows, k)
-        return scores, rows
+
+        def search_one(shard, _base):
+            ivf = getattr(shard, "ivf", None) if nprobe is not None and k <= IVF_K_MAX else None
+            if ivf is not None:
+                return ivf.search(q_in, k, nprobe)
+            return shard.search(q_in, k)               # dicts_to_csr converts sparse keys / weights to int32 / float32
+
+        return self._exchange_host(*self._segment_lists(parts, shard_rows, Q, k, search_one), k)
 
     def _device_topk_resident(self, parts, rows_dev, q_in, Q: int, k: int):
         """The RCCL form of `_device_topk`: every segment writes its `[Q, k]` lists (global rows through the device
         table) into HBM, segments are merged on the device, the payload goes through ONE all-gather and the cross-rank
         merge; only the merged result is copied to the host."""
-        import torch
-
-        comm = self._comm
-        stream = C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
-        payload, ids_ptr, scores_ptr = comm.exchange_buffers(Q, k)
+        stream, payload, ids_ptr, scores_ptr = self._resident_slots(Q, k)
         n = Q * k
         if not parts:
             _lib.check("vrag_topk_fill_empty", self._lib.vrag_topk_fill_empty(C.c_void_p(scores_ptr), C.c_void_p(ids_ptr), n, self.device, stream))
         else:
+            import torch
+
             table, n_map = rows_dev
             if len(parts) == 1:
                 slots = [(scores_ptr, ids_ptr)]
@@ -1577,7 +1009,7 @@ class GpuVectorStore(VectorStore):
                 _lib.check("vrag_topk_merge", self._lib.vrag_topk_merge(
                     C.c_void_p(seg_s.data_ptr()), C.c_void_p(seg_i.data_ptr()), len(parts), Q, k, k, 0, 0,
                     C.c_void_p(scores_ptr), C.c_void_p(ids_ptr), 1, self.device, stream))
-        return comm.allgather_merge_device(payload, Q, k, k)
+        return self._comm.allgather_merge_device(payload, Q, k, k)
 
     def _subset(self, kind: str, mask: np.ndarray):
         """A shard holding only this rank's rows that pass `mask` (Milvus filters before it searches,
@@ -1615,35 +1047,45 @@ class GpuVectorStore(VectorStore):
         per segment the mask is taken at the segment's rows and packed again from its first local row (segments start at
         arbitrary rows, so this is no word offset); rows beyond the mask do not pass.  The segments' `[Q, k]` lists are
         merged like the unfiltered ones and, on a sharded store, meet in the host exchange."""
-        Q = len(queries)
-        comm = self._comm
         q_in = self._unit_queries(queries) if kind == "dense" and parts else queries
         mapping = self._main_rows
-        found_lists = []
-        for shard, base in parts:
+
+        def search_one(shard, base):
             seg_rows = mapping[base:base + (len(shard) if kind == "dense" else shard.n_docs)]
             known = seg_rows < len(mask)
             allow = known & mask[np.where(known, seg_rows, 0)]
-            sc, local = shard.search_filtered(q_in, k, _bitmap(allow), len(allow))
-            at = local + base
-            found = (local >= 0) & (at < len(mapping))
-            g = np.where(found, mapping[np.where(found, at, 0)], -1) if len(mapping) else np.full_like(local, -1)
-            found_lists.append((sc, g))
-        if not found_lists:
-            scores, rows = np.full((Q, k), -np.inf, np.float32), np.full((Q, k), -1, np.int64)
-        elif len(found_lists) == 1:
-            scores, rows = found_lists[0]
-        else:
-            scores, rows = _merge_parts(np.stack([np.where(g >= 0, sc, -np.inf).astype(np.float32) for sc, g in found_lists]),
-                                        np.stack([g for _sc, g in found_lists]), k, self.device)
-        if comm is not None and self._world > 1:
-            scores, rows = comm.allgather_merge(scores, rows, k)
-        return scores, rows
+            return shard.search_filtered(q_in, k, _bitmap(allow), len(allow))
+
+        return self._exchange_host(*self._segment_lists(parts, mapping, len(queries), k, search_one), k)
 
     def _drop_subsets(self):
         with self._mu:
             self._subsets.clear()
             self._masks.clear()
+
+    def _check_limit(self, limit: int) -> None:
+        if limit > self.K_LIMIT:
+            raise ValueError(f"GpuVectorStore: a search may ask for at most {self.K_LIMIT} rows per method "
+                             f"(got {limit}; hybrid search asks for 2 * top_k)")
+
+    @staticmethod
+    def _fit_mask(mask: Optional[np.ndarray], n: int) -> Optional[np.ndarray]:
+        """`mask` over exactly `n` rows: rows that were inserted after the caller built it do not pass."""
+        if mask is None or len(mask) == n:
+            return mask
+        return np.concatenate([mask, np.zeros(n - len(mask), dtype=bool)]) if len(mask) < n else mask[:n]
+
+    @staticmethod
+    def _no_hits(Q: int, limit: int) -> Tuple[np.ndarray, np.ndarray]:
+        return np.full((Q, limit), -1, np.int64), np.zeros((Q, limit), np.float32)
+
+    @staticmethod
+    def _put_hits(rows_out: np.ndarray, score_out: np.ndarray, at, scores: np.ndarray, rows: np.ndarray,
+                  n: Optional[int] = None) -> None:
+        """Merged lists into the results at `at`: rows outside `[0, n)` (`n` None: negative rows) become -1, their scores 0."""
+        found = rows >= 0 if n is None else (rows >= 0) & (rows < n)
+        rows_out[at] = np.where(found, rows, -1)
+        score_out[at] = np.where(found, scores, np.float32(0.0))
 
     def _topk_rows(self, kind: str, queries: Sequence[Any], limit: int, mask: Optional[np.ndarray],
                    _retry: int = 0, nprobe: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
@@ -1654,15 +1096,11 @@ class GpuVectorStore(VectorStore):
         shard (`_filtered_topk`; no subset shard is built in that mode).  `nprobe` (dense leg of an IVF_FLAT store): the full pass looks at the rows of that many
         lists only (`_device_topk`); the second pass stays exact.  Every branch below depends only on replicated state and on merged
         results, so the ranks of a sharded store take the same path and meet in the same collectives."""
-        if limit > self.K_LIMIT:
-            raise ValueError(f"GpuVectorStore: a search may ask for at most {self.K_LIMIT} rows per method "
-                             f"(got {limit}; hybrid search asks for 2 * top_k)")
+        self._check_limit(limit)
         parts, rows_dev, n = self._main_parts(kind)
-        if mask is not None and len(mask) != n:     # rows were inserted after the caller built its mask
-            mask = np.concatenate([mask, np.zeros(n - len(mask), dtype=bool)]) if len(mask) < n else mask[:n]
+        mask = self._fit_mask(mask, n)
         Q = len(queries)
-        rows_out = np.full((Q, limit), -1, np.int64)
-        score_out = np.zeros((Q, limit), np.float32)
+        rows_out, score_out = self._no_hits(Q, limit)
         k = limit
         n_pass = n if mask is None else int(mask.sum())
         if n == 0 or Q == 0 or n_pass == 0:
@@ -1686,8 +1124,7 @@ class GpuVectorStore(VectorStore):
             rows_c = np.take_along_axis(rows, order, axis=1)
             scores_c = np.take_along_axis(scores, order, axis=1)
             rows_c[np.arange(k)[None, :] >= count[:, None]] = -1
-            rows_out[done, :k] = rows_c[done]
-            score_out[done, :k] = np.where(rows_c[done] >= 0, scores_c[done], np.float32(0.0))
+            self._put_hits(rows_out, score_out, done, scores_c[done], rows_c[done])
             short = ~done
         if short.any():
             which = np.nonzero(short)[0]
@@ -1696,29 +1133,20 @@ class GpuVectorStore(VectorStore):
             else:
                 sub_parts, shard_rows, sub_dev = self._subset(kind, mask)
                 scores, rows = self._device_topk(kind, sub_parts, shard_rows, [queries[i] for i in which], want, sub_dev)
-            rows = np.where((rows >= 0) & (rows < n), rows, -1)
-            rows_out[which, :want] = rows
-            score_out[which, :want] = np.where(rows >= 0, scores, np.float32(0.0))
+            self._put_hits(rows_out, score_out, (which, slice(0, want)), scores, rows, n)
         return rows_out, score_out
 
     def _text_topk(self, queries: Sequence[str], limit: int, mask: Optional[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
         """BM25 top-`limit` of a batch of query texts among the rows that pass `mask` -- `rows [Q, limit]` (-1 = no hit)
         and fp32 scores, as `_topk_rows`.  One device pass for the batch; the filter is a row bitmap the scoring kernel
         reads (no subset index), the statistics are those of the live rows."""
-        if limit > self.K_LIMIT:
-            raise ValueError(f"GpuVectorStore: a search may ask for at most {self.K_LIMIT} rows per method "
-                             f"(got {limit}; hybrid search asks for 2 * top_k)")
+        self._check_limit(limit)
         if self._text_sharded:
             return self._text_topk_sharded(queries, limit, mask)
         with self._mu:
-            self._flush()
-            text, n = self._text, self._text_flushed
-            if text is not None and self._text_live_stale:     # the statistics follow the deletes at the next search
-                text.set_live(self._alive.data[:n])
-                self._text_live_stale = False
+            text, n, _owned = self._text_snapshot()
         Q = len(queries)
-        rows_out = np.full((Q, limit), -1, np.int64)
-        score_out = np.zeros((Q, limit), np.float32)
+        rows_out, score_out = self._no_hits(Q, limit)
         if text is None or n == 0 or Q == 0:
             return rows_out, score_out
         # rows inserted after the caller built its mask lie beyond it: the library does not return them (nor any row an
@@ -1726,10 +1154,20 @@ class GpuVectorStore(VectorStore):
         if mask is not None and not mask.any():
             return rows_out, score_out
         scores, rows = text.search([q or "" for q in queries], limit, mask)
-        found = rows >= 0
-        rows_out[:] = np.where(found, rows, -1)
-        score_out[:] = np.where(found, scores, np.float32(0.0))
+        self._put_hits(rows_out, score_out, slice(None), scores, rows)
         return rows_out, score_out
+
+    def _text_snapshot(self):
+        """Opens both full-text routes, under the lock: flush, then (index, local rows it holds, their global rows); the
+        index's live rows, and with them its statistics, follow the deletes here."""
+        self._flush()
+        text, n_local = self._text, self._text_flushed
+        owned = self._owned.data[:n_local]
+        if text is not None and self._text_live_stale:
+            if n_local:
+                text.set_live(self._alive.data[owned])
+            self._text_live_stale = False
+        return text, n_local, owned
 
     def _text_topk_sharded(self, queries: Sequence[str], limit: int, mask: Optional[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
         """`_text_topk` on a row-sharded store.  Every rank scores its own rows with the corpus-wide statistics: `(N, sum dl)`
@@ -1742,13 +1180,8 @@ class GpuVectorStore(VectorStore):
         peer rank."""
         comm = self._comm
         with self._mu:
-            self._flush()
-            text, n_local, n = self._text, self._text_flushed, len(self._ids)
-            owned = self._owned.data[:n_local]
-            if text is not None and self._text_live_stale:
-                if n_local:
-                    text.set_live(self._alive.data[owned])
-                self._text_live_stale = False
+            text, n_local, owned = self._text_snapshot()
+            n = len(self._ids)
             if text is not None and self._text_totals is None:
                 own = text.stats()
                 tot = comm.sum_int64([own["live"], own["sum_dl"]])
@@ -1756,23 +1189,17 @@ class GpuVectorStore(VectorStore):
                 self._text_totals = (int(tot[0]), int(tot[1]))
             totals, owned_dev = self._text_totals, self._owned_dev
         Q = len(queries)
-        rows_out = np.full((Q, limit), -1, np.int64)
-        score_out = np.zeros((Q, limit), np.float32)
+        rows_out, score_out = self._no_hits(Q, limit)
         if text is None or n == 0 or Q == 0 or totals[0] == 0:
             return rows_out, score_out
-        if mask is not None:
-            if len(mask) != n:      # rows were inserted after the caller built its mask: they do not pass
-                mask = np.concatenate([mask, np.zeros(n - len(mask), dtype=bool)]) if len(mask) < n else mask[:n]
-            if not mask.any():
-                return rows_out, score_out
+        mask = self._fit_mask(mask, n)
+        if mask is not None and not mask.any():
+            return rows_out, score_out
         allow = mask[owned] if mask is not None else None       # the global-row mask at this rank's rows
         texts = [q or "" for q in queries]
         k = limit
         if comm.on_gpu and k <= self.DEVICE_K:
-            import torch
-
-            stream = C.c_void_p(torch.cuda.current_stream(torch.device("cuda", self.device)).cuda_stream)
-            payload, ids_ptr, scores_ptr = comm.exchange_buffers(Q, k)
+            stream, payload, ids_ptr, scores_ptr = self._resident_slots(Q, k)
             table, n_map = owned_dev if (owned_dev is not None and n_local) else (None, 0)
             text.search_sharded(texts, k, allow, totals[0], comm.sum_int64,
                                 device_out=(scores_ptr, ids_ptr, table.data_ptr() if table is not None else None, min(n_map, n_local), stream))
@@ -1781,10 +1208,8 @@ class GpuVectorStore(VectorStore):
             scores, local = text.search_sharded(texts, k, allow, totals[0], comm.sum_int64)
             found = (local >= 0) & (local < n_local)
             rows = np.where(found, owned[np.where(found, local, 0)], -1) if n_local else np.full_like(local, -1)
-            scores, rows = comm.allgather_merge(np.where(rows >= 0, scores, -np.inf).astype(np.float32), rows, k)
-        found = (rows >= 0) & (rows < n)
-        rows_out[:] = np.where(found, rows, -1)
-        score_out[:] = np.where(found, scores, np.float32(0.0))
+            scores, rows = self._exchange_host(np.where(rows >= 0, scores, -np.inf).astype(np.float32), rows, k)
+        self._put_hits(rows_out, score_out, slice(None), scores, rows, n)
         return rows_out, score_out
 
     def _search_batch(self, kind: str, queries: Sequence[Any], limit: int, mask: Optional[np.ndarray],
@@ -2049,45 +1474,7 @@ class GpuVectorStore(VectorStore):
 
     @staticmethod
     def _read_saved(path: str):
-        """Any on-disk format -> (head, ids, [per saved rank: (owned rows, arrays, texts, enhanced, metadatas)]).
-        Format 3 = `save` above; format 2 = `rows.json` holding ids / texts / metadata for all rows beside
-        `vectors.rank{r}.npz`; format 1 = `rows.json` + one `vectors.npz` in row order (single GPU)."""
-        import os
-
-        def get_json(name):
-            with open(os.path.join(path, name), encoding="utf-8") as f:
-                return json.load(f)
-
-        if os.path.exists(os.path.join(path, "store.json")):
-            head = get_json("store.json")
-            if head.get("format") != 3:
-                raise ValueError(f"{path}: unknown GpuVectorStore format {head.get('format')!r}")
-            ids = _get_strings(path, "ids", head["rows"])
-            shards = []
-            for r in range(head.get("world", 1)):
-                z = np.load(os.path.join(path, f"vectors.rank{r}.npz"))
-                m = len(z["owned"])
-                metas = get_json(f"metadatas.rank{r}.json")
-                if isinstance(metas, dict):
-                    metas = [_NO_METADATA] * int(metas["empty_rows"])
-                if len(metas) != m:
-                    raise ValueError(f"{path}: metadatas.rank{r} holds {len(metas)} rows, expected {m}")
-                shards.append((z["owned"], z, _get_strings(path, f"texts.rank{r}", m), _get_strings(path, f"enhanced.rank{r}", m), metas))
-            return head, ids, shards
-        rows = get_json("rows.json")
-        fmt = rows.get("format")
-        if fmt not in (1, 2):
-            raise ValueError(f"{path}: unknown GpuVectorStore format {fmt!r}")
-        ids = list(rows["ids"])
-        head = {k: rows.get(k) for k in ("dense_dim", "sparse_vocab", "enable_dense", "enable_sparse", "dense_dtype")}
-        head.update(world=rows.get("world", 1) if fmt == 2 else 1, rows=len(ids), documents=rows.get("documents", []))
-        shards = []
-        for r in range(head["world"]):
-            z = np.load(os.path.join(path, "vectors.npz" if fmt == 1 else f"vectors.rank{r}.npz"))
-            owned = np.arange(len(ids), dtype=np.int64) if fmt == 1 else z["owned"]
-            shards.append((owned, z, [rows["texts"][g] for g in owned], [rows["enhanced_texts"][g] for g in owned],
-                           [rows["metadatas"][g] for g in owned]))
-        return head, ids, shards
+        return read_saved(path)
 
     @classmethod
     def load(cls, path: str, device: int = 0, distributed: bool = False, group=None, comm=None,
