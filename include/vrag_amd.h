@@ -643,6 +643,71 @@ int vrag_rrf_fuse(const int64_t* rows /*[nq, l_total]*/, const double* gains /*[
                   int32_t on_device, int32_t device, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Row filter: the store's boolean metadata filters (store_filter.py) evaluated over typed columns in device memory
+ * (csrc/rowfilter.hip).  A column holds one metadata key of every row: kinds[r] (VRAG_FILTER_KIND_*, one byte) and payload[r]
+ * (eight bytes: the IEEE f64 bits of a number, the dictionary code of a string, 0 / 1 of a bool, 0 otherwise) -- 9 bytes of
+ * device memory per row and column.  A filter is a postfix program over LEAVES; a leaf names one column and states, per kind of
+ * stored value, what it answers (each independent of the others):
+ *   other    other_bit (0 / 1)                                   -- missing key, null, list, object
+ *   bool     bit `value` of bool_bits (bit 0 = the answer for false, bit 1 = for true)
+ *   number   num_op (VRAG_FILTER_NUM_*) against `bound`, an IEEE f64 comparison (-0.0 == 0.0, infinities ordered, NaN equals nothing)
+ *   string   str_mode VRAG_FILTER_STR_NEVER / _ALWAYS, or _TABLE: bit (code % 32) of tables[table_off + code / 32] for a code
+ *            < table_codes, 0 for a code at or beyond it (nothing past the leaf's table is ever read)
+ * ops[i] = VRAG_FILTER_OP_LEAF | (leaf index << 8) pushes a leaf's answer, _AND / _OR pop two and push one, _NOT flips the top;
+ * exactly one value must remain.  Limits: VRAG_FILTER_MAX_COLUMNS distinct columns named by the leaves, _MAX_LEAVES leaves,
+ * _MAX_OPS ops, stack depth _MAX_DEPTH (the stack is the bits of one 32-bit register per row).
+ *   append   host arrays; rows are appended behind the column's earlier rows, which are kept (geometric growth).  kinds > 3 invalid.
+ *   eval     rows [0, n_rows) of every referenced column (each must hold at least n_rows) -> out_words (host, ceil(n_rows / 32)
+ *            words, bit r % 32 of word r / 32 = row r passes, bits at and beyond n_rows zero; nothing behind those words is written).
+ *            n_rows == 0: VRAG_OK without a launch.  Synchronous.
+ * Everything is validated on the host before anything is launched or allocated (leaf columns, table ranges against n_table_words,
+ * n_rows against the columns, the op list, the limits): VRAG_ERR_INVALID with a message, out_words untouched.  The handle has its
+ * own device arrays, stream and lock. */
+#define VRAG_FILTER_MAX_COLUMNS 16
+#define VRAG_FILTER_MAX_LEAVES 64
+#define VRAG_FILTER_MAX_OPS 256
+#define VRAG_FILTER_MAX_DEPTH 32
+#define VRAG_FILTER_KIND_OTHER 0
+#define VRAG_FILTER_KIND_NUMBER 1
+#define VRAG_FILTER_KIND_STRING 2
+#define VRAG_FILTER_KIND_BOOL 3
+#define VRAG_FILTER_NUM_NEVER 0
+#define VRAG_FILTER_NUM_ALWAYS 1
+#define VRAG_FILTER_NUM_EQ 2
+#define VRAG_FILTER_NUM_NE 3
+#define VRAG_FILTER_NUM_LT 4
+#define VRAG_FILTER_NUM_LE 5
+#define VRAG_FILTER_NUM_GT 6
+#define VRAG_FILTER_NUM_GE 7
+#define VRAG_FILTER_STR_NEVER 0
+#define VRAG_FILTER_STR_ALWAYS 1
+#define VRAG_FILTER_STR_TABLE 2
+#define VRAG_FILTER_OP_LEAF 0
+#define VRAG_FILTER_OP_AND 1
+#define VRAG_FILTER_OP_OR 2
+#define VRAG_FILTER_OP_NOT 3
+typedef struct vrag_filter_leaf {
+  double bound;
+  int64_t table_off;
+  int64_t table_codes;
+  int32_t column;
+  uint8_t num_op;
+  uint8_t str_mode;
+  uint8_t bool_bits;
+  uint8_t other_bit;
+} vrag_filter_leaf;
+typedef struct vrag_row_filter vrag_row_filter;
+int vrag_row_filter_create(int32_t device, vrag_row_filter** out);
+void vrag_row_filter_destroy(vrag_row_filter* f);
+int vrag_row_filter_add_column(vrag_row_filter* f, int32_t* col_out);
+int vrag_row_filter_append(vrag_row_filter* f, int32_t col, const uint8_t* kinds /*[n] host*/, const uint64_t* payload /*[n] host*/,
+                           int64_t n);
+int vrag_row_filter_rows(vrag_row_filter* f, int32_t col, int64_t* n);
+int vrag_row_filter_eval(vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops, int32_t n_ops,
+                         const uint32_t* tables /*[n_table_words] host, NULL when 0*/, int64_t n_table_words, int64_t n_rows,
+                         uint32_t* out_words /*host*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The exchange step of sharded retrieval: one process per GPU, the corpus row-sharded, every rank answers the
  * (replicated) query batch on its own shard with vrag_*_index_search_device and contributes its packed lists
  *     payload = [ global ids  int64 x nq*k_in | scores fp32 x nq*k_in | pad to 8 bytes ]       (device memory)

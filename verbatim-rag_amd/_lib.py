@@ -69,6 +69,19 @@ class BertWeights(C.Structure):
     ]
 
 
+class FilterLeaf(C.Structure):
+    """vrag_filter_leaf (include/vrag_amd.h), field for field; tests/test_filter_program_host.py checks the layout against the host
+    compiler's."""
+    _fields_ = [("bound", C.c_double), ("table_off", C.c_int64), ("table_codes", C.c_int64), ("column", C.c_int32),
+                ("num_op", C.c_uint8), ("str_mode", C.c_uint8), ("bool_bits", C.c_uint8), ("other_bit", C.c_uint8)]
+
+
+FILTER_MAX_COLUMNS, FILTER_MAX_LEAVES, FILTER_MAX_OPS, FILTER_MAX_DEPTH = 16, 64, 256, 32   # VRAG_FILTER_MAX_*
+FILTER_KINDS = {"other": 0, "number": 1, "string": 2, "bool": 3}                                # VRAG_FILTER_KIND_*
+FILTER_NUM_OPS = {"never": 0, "always": 1, "==": 2, "!=": 3, "<": 4, "<=": 5, ">": 6, ">=": 7}  # VRAG_FILTER_NUM_*
+FILTER_STR_MODES = {"never": 0, "always": 1, "table": 2}                                        # VRAG_FILTER_STR_*
+FILTER_OPS = {"leaf": 0, "and": 1, "or": 2, "not": 3}                                           # VRAG_FILTER_OP_* (leaf index << 8)
+
 # name -> (restype, argtypes); every symbol include/vrag_amd.h declares.
 _H = C.c_void_p
 SIGNATURES = {
@@ -132,6 +145,13 @@ SIGNATURES = {
     "vrag_ivf_index_stats": (C.c_int, [_H, _IP, _LP, _LP]),
     "vrag_ivf_index_read": (C.c_int, [_H, _FP, C.c_void_p, C.c_void_p]),
     "vrag_ivf_index_search": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, _FP, _LP, _LP, C.c_void_p]),
+    "vrag_row_filter_create": (C.c_int, [C.c_int32, C.POINTER(_H)]),
+    "vrag_row_filter_destroy": (None, [_H]),
+    "vrag_row_filter_add_column": (C.c_int, [_H, _IP]),
+    "vrag_row_filter_append": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
+    "vrag_row_filter_rows": (C.c_int, [_H, C.c_int32, _LP]),
+    "vrag_row_filter_eval": (C.c_int, [_H, C.POINTER(FilterLeaf), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
+                                       C.c_void_p, C.c_void_p]),
     "vrag_sparse_index_search_device": (C.c_int, [_H, _LP, _IP, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "vrag_pack_qa_pairs": (C.c_int, [_IP, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, _IP, C.c_int32, C.c_int32, _IP, C.c_int64,

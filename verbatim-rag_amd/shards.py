@@ -200,6 +200,77 @@ class IvfOverlay(_Handle):
         return (scores, ids, seen) if scanned else (scores, ids)
 
 
+class RowFilter(_Handle):
+    """Typed metadata columns in HBM and the kernel that evaluates a filter program over them (`vrag_row_filter_*`,
+    csrc/rowfilter.hip): 9 bytes per row and column.  Columns are numbered in creation order and only ever appended to."""
+
+    _destroy = "vrag_row_filter_destroy"
+
+    def __init__(self, device: int = 0):
+        _lib.require_gpu()
+        self._open("vrag_row_filter_create", int(device))
+
+    def add_column(self) -> int:
+        col = C.c_int32()
+        _lib.check("vrag_row_filter_add_column", self._lib.vrag_row_filter_add_column(self._h, C.byref(col)))
+        return col.value
+
+    def append(self, col: int, kinds: np.ndarray, payload: np.ndarray) -> None:
+        kinds = np.ascontiguousarray(kinds, dtype=np.uint8)
+        payload = np.ascontiguousarray(payload, dtype=np.uint64)
+        if kinds.ndim != 1 or kinds.shape != payload.shape:
+            raise ValueError(f"kinds {kinds.shape} and payload {payload.shape} must be one-dimensional and equally long")
+        _lib.check("vrag_row_filter_append", self._lib.vrag_row_filter_append(self._h, int(col), _vp(kinds), _vp(payload), len(kinds)))
+
+    def rows(self, col: int) -> int:
+        n = C.c_int64()
+        _lib.check("vrag_row_filter_rows", self._lib.vrag_row_filter_rows(self._h, int(col), C.byref(n)))
+        return n.value
+
+    def eval(self, leaves: Sequence["_lib.FilterLeaf"], ops: np.ndarray, tables: np.ndarray, n_rows: int,
+             out: Optional[np.ndarray] = None, stream=None) -> np.ndarray:
+        """The program's answer for rows [0, n_rows) as uint32 words (bit r % 32 of word r // 32, tail bits zero).  `out`: a
+        uint32 array of at least ceil(n_rows / 32) words to write into (words behind those are left alone)."""
+        arr = (_lib.FilterLeaf * max(1, len(leaves)))(*leaves)
+        ops = np.ascontiguousarray(ops, dtype=np.uint32)
+        tables = np.ascontiguousarray(tables, dtype=np.uint32)
+        n_words = (max(0, int(n_rows)) + 31) // 32
+        if out is None:
+            out = np.zeros(n_words, np.uint32)
+        elif out.dtype != np.uint32 or not out.flags.c_contiguous or len(out) < n_words:
+            raise ValueError(f"out must be a contiguous uint32 array of at least {n_words} words")
+        _lib.check("vrag_row_filter_eval", self._lib.vrag_row_filter_eval(
+            self._h, arr, len(leaves), _vp(ops), len(ops), _vp(tables) if len(tables) else None, len(tables), int(n_rows),
+            _vp(out), stream))
+        return out
+
+    def eval_program(self, program, columns: Sequence[Tuple[int, "object"]], n_rows: int) -> np.ndarray:
+        """`bool[n_rows]` of a `store_filter.FilterProgram`; `columns[i]` = (this filter's column number, the
+        `store_columns.MetaColumn` whose dictionary resolves the string leaves) of `program.keys[i]`."""
+        leaves, ops, tables = program_arrays(program, columns)
+        words = self.eval(leaves, ops, tables, n_rows)
+        return np.unpackbits(words.view(np.uint8), bitorder="little")[:n_rows].astype(bool)
+
+
+def program_arrays(program, columns: Sequence[Tuple[int, "object"]]):
+    """A `FilterProgram` as the arguments of `RowFilter.eval`: (`_lib.FilterLeaf` list, ops uint32, string tables uint32).
+    A string leaf's table is its comparison applied to every string of its column's dictionary as it stands now."""
+    leaves, parts, off = [], [], 0
+    for lf in program.leaves:
+        col, meta = columns[lf.column]
+        out = _lib.FilterLeaf(bound=float(lf.bound), table_off=0, table_codes=0, column=int(col),
+                              num_op=_lib.FILTER_NUM_OPS[lf.num_op], str_mode=_lib.FILTER_STR_MODES.get(lf.str_op, 2),
+                              bool_bits=int(lf.bools[0]) | (int(lf.bools[1]) << 1), other_bit=int(lf.other))
+        if out.str_mode == 2:
+            table = meta.string_table(lf.str_op, lf.text)
+            out.table_off, out.table_codes = off, len(meta.strings)
+            parts.append(table)
+            off += len(table)
+        leaves.append(out)
+    ops = np.asarray([_lib.FILTER_OPS[op] | (i << 8) for op, i in program.ops], dtype=np.uint32)
+    return leaves, ops, np.concatenate(parts) if parts else np.zeros(0, np.uint32)
+
+
 def dicts_to_csr(rows: Sequence[Dict[int, float]]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """`{term: weight}` rows -> CSR (int64 indptr, int32 terms ascending within a row, float32 weights).  One pass of
     C-level iteration plus a lexsort: a 1 M-document ingest or a 1 000-query batch does not loop in Python per entry."""

@@ -1,8 +1,11 @@
-"""The subset of Milvus boolean filter expressions `GpuVectorStore` supports, compiled into Python predicates."""
+"""The subset of Milvus boolean filter expressions `GpuVectorStore` supports: one parser, compiled into Python predicates
+(`parse_filter`) or into a postfix program for the row-filter kernel (`compile_filter`)."""
 from __future__ import annotations
 
+import operator
 import re
-from typing import Any
+from dataclasses import dataclass, field
+from typing import Any, List, Optional, Tuple
 
 
 _FILTER_TOKEN = re.compile(r"""\s*(?:(?P<meta>metadata\[\s*["'](?P<mkey>[^"']+)["']\s*\])|(?P<str>"[^"]*"|'[^']*')"""
@@ -23,14 +26,10 @@ def _typed(value: Any):
     return None
 
 
-def parse_filter(expr: str):
-    """Compiles the subset of Milvus boolean expressions the store supports into `predicate(metadata: dict) -> bool`:
-    `field == value`, `field != value`, `field in [v, ...]`, `field < / <= / > / >= value`, combined with `and` / `&&`,
-    `or` / `||`, `not` and parentheses.  field = `metadata["key"]` (the Local dialect) or a bare `key` (the Cloud
-    dialect: index.py:735-739); value = a quoted string, a number (`7`, `-2.5`, `1e3`) or `true` / `false`.
-    Comparisons are typed like Milvus' JSON path match: numbers against numeric metadata, strings against text,
-    booleans against booleans; a missing key equals nothing (so `!=` holds for it).  Anything else raises ValueError --
-    a filter is never silently ignored."""
+def parse_filter_ast(expr: str):
+    """The parser both back ends share: `expr` -> a tree of `("cmp", key, op, want)` (op one of == != < <= > >=, `want` the
+    literal's `_typed` key), `("in", key, [want, ...])`, `("not", a)`, `("and", a, b)`, `("or", a, b)`.  Raises ValueError for
+    anything outside the grammar `parse_filter` states."""
     toks, pos = [], 0
     while pos < len(expr):
         if expr[pos:].strip() == "":
@@ -76,17 +75,11 @@ def parse_filter(expr: str):
             return f
         if peek() == ("op", "not"):
             take()
-            g = comparison()
-            return lambda md: not g(md)
+            return ("not", comparison())
         key = take("field")
         op = take("op")
         if op in ("==", "!="):
-            want = _typed(take("val"))
-            if op == "!=":
-                return lambda md: _typed(md.get(key)) != want
-            f = lambda md: _typed(md.get(key)) == want   # noqa: E731
-            f.lookup = (key, [want])                      # lets the store answer from a per-key value index
-            return f
+            return ("cmp", key, op, _typed(take("val")))
         if op == "in":
             take("op", "[")
             vals = [_typed(take("val"))]
@@ -94,41 +87,166 @@ def parse_filter(expr: str):
                 take()
                 vals.append(_typed(take("val")))
             take("op", "]")
-            vs = set(vals)
-            f = lambda md: _typed(md.get(key)) in vs      # noqa: E731
-            f.lookup = (key, vals)
-            return f
+            return ("in", key, vals)
         if op in ("<", "<=", ">", ">="):
-            import operator
-
-            cmp = {"<": operator.lt, "<=": operator.le, ">": operator.gt, ">=": operator.ge}[op]
-            kind, bound = _typed(take("val"))
-            if kind == "b":
+            want = _typed(take("val"))
+            if want[0] == "b":
                 raise ValueError(f"GpuVectorStore: ordering comparison with a boolean in filter {expr!r}")
-
-            def ordered(md):
-                have = _typed(md.get(key))
-                return have is not None and have[0] == kind and cmp(have[1], bound)
-            return ordered
+            return ("cmp", key, op, want)
         raise ValueError(f"GpuVectorStore: unsupported operator {op!r} in filter {expr!r}")
 
     def conjunction():
         f = comparison()
         while peek() in (("op", "and"), ("op", "&&")):
             take()
-            g, h = f, comparison()
-            f = (lambda a, b: lambda md: a(md) and b(md))(g, h)
+            f = ("and", f, comparison())
         return f
 
     def disjunction():
         f = conjunction()
         while peek() in (("op", "or"), ("op", "||")):
             take()
-            g, h = f, conjunction()
-            f = (lambda a, b: lambda md: a(md) or b(md))(g, h)
+            f = ("or", f, conjunction())
         return f
 
-    pred = disjunction()
+    tree = disjunction()
     if i != len(toks):
         raise ValueError(f"GpuVectorStore: unsupported filter {expr!r}")
-    return pred
+    return tree
+
+
+_ORDER = {"<": operator.lt, "<=": operator.le, ">": operator.gt, ">=": operator.ge}
+
+
+def _closure(node):
+    """A tree of `parse_filter_ast` as `predicate(metadata: dict) -> bool`."""
+    tag = node[0]
+    if tag == "not":
+        g = _closure(node[1])
+        return lambda md: not g(md)
+    if tag in ("and", "or"):
+        a, b = _closure(node[1]), _closure(node[2])
+        if tag == "and":
+            return lambda md: a(md) and b(md)
+        return lambda md: a(md) or b(md)
+    if tag == "in":
+        key, vals = node[1], node[2]
+        vs = set(vals)
+        f = lambda md: _typed(md.get(key)) in vs      # noqa: E731
+        f.lookup = (key, vals)
+        return f
+    _tag, key, op, want = node
+    if op == "!=":
+        return lambda md: _typed(md.get(key)) != want
+    if op == "==":
+        f = lambda md: _typed(md.get(key)) == want   # noqa: E731
+        f.lookup = (key, [want])                      # lets the store answer from a per-key value index
+        return f
+    cmp, (kind, bound) = _ORDER[op], want
+
+    def ordered(md):
+        have = _typed(md.get(key))
+        return have is not None and have[0] == kind and cmp(have[1], bound)
+    return ordered
+
+
+def parse_filter(expr: str):
+    """Compiles the subset of Milvus boolean expressions the store supports into `predicate(metadata: dict) -> bool`:
+    `field == value`, `field != value`, `field in [v, ...]`, `field < / <= / > / >= value`, combined with `and` / `&&`,
+    `or` / `||`, `not` and parentheses.  field = `metadata["key"]` (the Local dialect) or a bare `key` (the Cloud
+    dialect: index.py:735-739); value = a quoted string, a number (`7`, `-2.5`, `1e3`) or `true` / `false`.
+    Comparisons are typed like Milvus' JSON path match: numbers against numeric metadata, strings against text,
+    booleans against booleans; a missing key equals nothing (so `!=` holds for it).  Anything else raises ValueError --
+    a filter is never silently ignored."""
+    return _closure(parse_filter_ast(expr))
+
+
+# ---------------------------------------------------------------------------- the device back end
+# The same tree as a postfix program over LEAVES for the row-filter kernel (include/vrag_amd.h, vrag_row_filter_eval).  A leaf is
+# one comparison of one key and states what it answers for each KIND of stored value -- `_typed`'s kinds, each answer independent
+# of the others:
+#   other   (None, a list, a dict, a missing key)   a constant: 1 only for `!=`
+#   bool                                             one answer for false, one for true
+#   number                                           never / always / one IEEE f64 comparison against `bound`
+#   string                                           never / always / a Python comparison against `text`, which the store applies
+#                                                    once per distinct stored string (store_columns.MetaColumn.string_table)
+# `in [..]` is an OR of `==` leaves: a list may mix kinds.
+MAX_COLUMNS, MAX_LEAVES, MAX_OPS, MAX_DEPTH = 16, 64, 256, 32     # VRAG_FILTER_MAX_*
+STRING_COMPARE = {"==": operator.eq, "!=": operator.ne, **_ORDER}
+
+
+@dataclass(frozen=True)
+class FilterLeaf:
+    column: int                     # index into FilterProgram.keys
+    other: bool
+    bools: Tuple[bool, bool]        # (answer for false, answer for true)
+    num_op: str                     # "never" | "always" | "==" | "!=" | "<" | "<=" | ">" | ">="
+    bound: float
+    str_op: str                     # the same choices, against `text`
+    text: str
+
+
+@dataclass
+class FilterProgram:
+    keys: List[str] = field(default_factory=list)                # referenced metadata keys, in first-use order
+    leaves: List[FilterLeaf] = field(default_factory=list)
+    ops: List[Tuple[str, int]] = field(default_factory=list)     # ("leaf", i) | ("and", 0) | ("or", 0) | ("not", 0), postfix
+
+    def depth(self) -> int:
+        """Deepest the evaluation stack gets."""
+        deepest = cur = 0
+        for op, _i in self.ops:
+            cur += 1 if op == "leaf" else (-1 if op in ("and", "or") else 0)
+            deepest = max(deepest, cur)
+        return deepest
+
+    def over_limit(self) -> Optional[str]:
+        """Why the device cannot run this program (one sentence), or None when it is within every limit."""
+        for what, have, most in (("columns", len(self.keys), MAX_COLUMNS), ("leaves", len(self.leaves), MAX_LEAVES),
+                                 ("ops", len(self.ops), MAX_OPS), ("stack depth", self.depth(), MAX_DEPTH)):
+            if have > most:
+                return f"{have} {what} (the device program holds at most {most})"
+        return None
+
+
+def _leaf(column: int, op: str, want) -> FilterLeaf:
+    kind, value = want
+    differs = op == "!="                                           # the one comparison that holds between different kinds
+    rest = "always" if differs else "never"
+    return FilterLeaf(
+        column=column, other=differs,
+        bools=tuple(STRING_COMPARE[op](b, value) for b in (False, True)) if kind == "b" else (differs, differs),
+        num_op=op if kind == "n" else rest, bound=value if kind == "n" else 0.0,
+        str_op=op if kind == "s" else rest, text=value if kind == "s" else "")
+
+
+def compile_filter(expr: str) -> FilterProgram:
+    """`expr` (the grammar of `parse_filter`, the same ValueErrors) as a `FilterProgram`: evaluated over the kinds and comparison
+    keys `_typed` gives the stored values, it answers what `parse_filter(expr)` answers, row for row."""
+    prog = FilterProgram()
+
+    def push(key: str, op: str, want) -> None:
+        if key not in prog.keys:
+            prog.keys.append(key)
+        prog.leaves.append(_leaf(prog.keys.index(key), op, want))
+        prog.ops.append(("leaf", len(prog.leaves) - 1))
+
+    def emit(node) -> None:
+        tag = node[0]
+        if tag == "cmp":
+            push(node[1], node[2], node[3])
+        elif tag == "in":
+            for n, want in enumerate(node[2]):
+                push(node[1], "==", want)
+                if n:
+                    prog.ops.append(("or", 0))
+        elif tag == "not":
+            emit(node[1])
+            prog.ops.append(("not", 0))
+        else:
+            emit(node[1])
+            emit(node[2])
+            prog.ops.append((tag, 0))
+
+    emit(parse_filter_ast(expr))
+    return prog

@@ -24,9 +24,10 @@ import numpy as np
 from . import _lib
 # The layers under the store, re-exported here under the names callers and tests have always used.  The store resolves
 # DenseShard / SparseShard / IvfOverlay / TextIndex through THIS module's globals at call time (tests replace them here).
-from .shards import (_FP, _IP, _LP, DenseShard, IvfOverlay, SparseShard, TextIndex, _allow_words, _bitmap,  # noqa: F401
+from .shards import (_FP, _IP, _LP, DenseShard, IvfOverlay, RowFilter, SparseShard, TextIndex, _allow_words, _bitmap,  # noqa: F401
                      _utf8_batch, dicts_to_csr, tokenize_keys)
-from .store_filter import _FILTER_TOKEN, _typed, parse_filter  # noqa: F401
+from .store_columns import MetaColumn
+from .store_filter import _FILTER_TOKEN, _typed, compile_filter, parse_filter  # noqa: F401
 from .store_io import _NO_METADATA, _get_strings, _put_strings, _replace_into, _write_text, read_saved  # noqa: F401
 
 logger = logging.getLogger(__name__)
@@ -485,7 +486,7 @@ class GpuVectorStore(VectorStore):
                  group=None, comm=None, payload: str = "sharded", dense_headroom: float = 1.5,
                  dense_prefilter="auto", enable_full_text: bool = False, bm25_k1: float = 1.2, bm25_b: float = 0.75,
                  filter_route: str = "subset", rrf_route: str = "host", index_type: str = "FLAT", nlist: int = 8192,
-                 nprobe: int = 16):
+                 nprobe: int = 16, filter_eval: str = "host"):
         """`enable_full_text`: BM25 keyword search over the raw texts (milvus_cloud.py: bm25_k1 = 1.2, bm25_b = 0.75),
         `search_type="full_text"` and the third leg of a weighted hybrid search; the texts are tokenised, indexed and
         scored on the device (`TextIndex`).  Off by default.  On a sharded store (`distributed=True` or a `comm`) the
@@ -505,6 +506,13 @@ class GpuVectorStore(VectorStore):
         queries, smaller ones are cheaper in numpy).  Same bits either way; on a sharded store every
         rank fuses the same merged lists itself (no collective).  The per-query paths (`query`, a store with a falsy id)
         always fuse on the host.  A run-time choice like `filter_route`: not written by `save`, a keyword of `load`.
+        `filter_eval`: where the row mask of a filter that is no single `==` / `in` comparison (a range, `!=`, `and` / `or` /
+        `not`) is computed -- "host" (default) by one Python predicate call per stored row, "device" by the row-filter kernel
+        (`RowFilter`, csrc/rowfilter.hip) over typed columns of the keys the filter names: a column is built by one Python pass on
+        the first filter that names its key, extended by the rows of every later insert, and costs 9 bytes of HBM per row.  The
+        same mask bit for bit.  A filter beyond the device program's limits (16 keys, 64 comparisons, 256 operations, nesting
+        32 deep) or naming a key that holds a NaN is answered on the host (logged once per filter string).  A run-time choice like
+        `filter_route`: not written by `save`, a keyword of `load`.
         `index_type`: "FLAT" (default) = every dense query streams the whole shard, exact.  "IVF_FLAT" (the reference's Milvus
         stores, milvus_base.py:40-50) = the dense leg looks only at the rows of the `nprobe` lists nearest to the query out of
         `nlist` k-means lists laid over the resident shard (`IvfOverlay`; `ivf_effective_nlist` caps `nlist` for small stores
@@ -523,6 +531,8 @@ class GpuVectorStore(VectorStore):
             raise ValueError(f"filter_route must be 'subset' or 'bitmap' (got {filter_route!r})")
         if rrf_route not in ("host", "device"):
             raise ValueError(f"rrf_route must be 'host' or 'device' (got {rrf_route!r})")
+        if filter_eval not in ("host", "device"):
+            raise ValueError(f"filter_eval must be 'host' or 'device' (got {filter_eval!r})")
         if not enable_dense and not enable_sparse and not enable_full_text:      # milvus_base.py:54-56
             raise ValueError("At least one of enable_dense, enable_sparse, or enable_full_text must be True")
         if enable_full_text and comm is None and distributed:
@@ -551,6 +561,7 @@ class GpuVectorStore(VectorStore):
             self._owns_comm = True
         self.rrf_route = rrf_route
         self.filter_route = filter_route
+        self.filter_eval = filter_eval
         self.index_type, self.nlist, self.nprobe = index_type, int(nlist), int(nprobe)
         self._ivf_trained_rows = 0   # rows in the shard when its overlay was last trained (0 = no overlay)
         # the route searches take: the filtered search returns host lists, which the device-resident exchange does not carry.
@@ -598,6 +609,12 @@ class GpuVectorStore(VectorStore):
         self._mu = threading.RLock()
         self._masks: Dict[str, Optional[np.ndarray]] = {}
         self._value_indexes: Dict[str, Dict[Any, List[np.ndarray]]] = {}   # key -> typed value -> row segments
+        # filter_eval="device": typed columns of the keys filters have named (host side, over the rows of `_meta`), the handle
+        # that holds their device copies with each key's column number there, and the filters already reported as host-routed
+        self._meta_columns: Dict[str, MetaColumn] = {}
+        self._row_filter: Optional[RowFilter] = None
+        self._row_filter_cols: Dict[str, int] = {}
+        self._filter_fallbacks: set = set()
         self._all_ids_truthy = True
         self._documents: Dict[str, Dict[str, Any]] = {}      # document records (add_documents / get_document)
         self._subsets: Dict[Any, Tuple[Any, np.ndarray, Any]] = {}   # (kind, mask bytes) -> (subset shard, global row of each subset row, device copy)
@@ -615,6 +632,7 @@ class GpuVectorStore(VectorStore):
             self._sparse_parts = []
             self._text = None
             self._owned_dev = None
+            self._row_filter, self._row_filter_cols = None, {}    # the host columns stay: they are uploaded again on demand
             self._dense_flushed = self._sparse_flushed = self._text_flushed = self._text_main = 0
             self._dirty = True
             if self._comm is not None and self._owns_comm:
@@ -699,6 +717,8 @@ class GpuVectorStore(VectorStore):
                         fresh.setdefault(t, []).append(meta_base + j)
                 for t, rows in fresh.items():
                     index.setdefault(t, []).append(np.asarray(rows, dtype=np.int64))
+            for column in self._meta_columns.values():      # typed columns likewise: O(new rows) per insert
+                column.extend(new_meta)
 
     def _note_id(self, key, row: int) -> None:
         have = self._id_rows.get(key)
@@ -874,7 +894,9 @@ class GpuVectorStore(VectorStore):
                         if rows is not None:
                             held[rows] = True
                 else:
-                    held = np.asarray([bool(pred(md)) for md in self._meta], dtype=bool)
+                    held = self._held_device(filter) if self.filter_eval == "device" else None
+                    if held is None:
+                        held = np.asarray([bool(pred(md)) for md in self._meta], dtype=bool)
                 if self._payload_sharded:
                     passing = np.zeros(len(alive), dtype=bool)
                     passing[self._owned.data[: len(held)][held]] = True
@@ -886,6 +908,43 @@ class GpuVectorStore(VectorStore):
                 self._masks.clear()
             self._masks[key] = None if alive.all() else alive
         return self._masks[key]
+
+    def _held_device(self, filter: str) -> Optional[np.ndarray]:
+        """`filter` over the rows of `_meta` on the GPU (`filter_eval="device"`, under the lock): the filter as a postfix
+        program, the columns it names brought up to date in HBM (only rows not uploaded yet travel), its string comparisons
+        resolved against the columns' dictionaries, one kernel.  None = this filter is the host's: the program is beyond the
+        device's limits or a named column is inexact (logged once per filter string)."""
+        program = compile_filter(filter)
+        why = program.over_limit()
+        columns = []
+        for key in program.keys if why is None else ():
+            column = self._meta_columns.get(key)
+            if column is None:
+                column = self._meta_columns[key] = MetaColumn(key)
+                column.extend(self._meta)
+            if not column.exact:
+                why = f"metadata[{key!r}] holds a NaN or a number beyond float range"
+                break
+            columns.append(column)
+        if why is not None:
+            if filter not in self._filter_fallbacks:
+                if len(self._filter_fallbacks) >= 1024:
+                    self._filter_fallbacks.clear()
+                self._filter_fallbacks.add(filter)
+                logger.info("GpuVectorStore: filter %r is evaluated on the host: %s", filter, why)
+            return None
+        if self._row_filter is None:
+            self._row_filter = RowFilter(self.device)
+        device_cols = []
+        for column in columns:
+            col = self._row_filter_cols.get(column.key)
+            if col is None:
+                col = self._row_filter_cols[column.key] = self._row_filter.add_column()
+            have = self._row_filter.rows(col)
+            if have < len(column):
+                self._row_filter.append(col, column.kinds[have:], column.payload[have:])
+            device_cols.append((col, column))
+        return self._row_filter.eval_program(program, device_cols, len(self._meta))
 
     def _value_index(self, key: str) -> Dict[Any, np.ndarray]:
         """typed metadata[key] -> rows (positions in the metadata list), built once per key until the next insert: a
@@ -1478,10 +1537,11 @@ class GpuVectorStore(VectorStore):
 
     @classmethod
     def load(cls, path: str, device: int = 0, distributed: bool = False, group=None, comm=None,
-             payload: str = "sharded", filter_route: str = "subset", rrf_route: str = "host") -> "GpuVectorStore":
+             payload: str = "sharded", filter_route: str = "subset", rrf_route: str = "host",
+             filter_eval: str = "host") -> "GpuVectorStore":
         """Reads a directory written by `save` -- by this or an earlier revision (formats 1 - 3), by any number of
         ranks: when the world size differs from the writer's, the saved shards are put back in row order and cut
-        contiguously over the ranks that open the store.  `filter_route`, `rrf_route`: as the constructor's (not part of a saved store).
+        contiguously over the ranks that open the store.  `filter_route`, `rrf_route`, `filter_eval`: as the constructor's (not part of a saved store).
         An IVF_FLAT store comes back IVF_FLAT with its `nlist` / `nprobe`; its lists are trained again at the first flush
         (training is deterministic: the same rows give the same lists)."""
         head, ids, shards = cls._read_saved(path)
@@ -1491,7 +1551,7 @@ class GpuVectorStore(VectorStore):
                  dense_prefilter=head.get("dense_prefilter", "auto"), enable_full_text=bool(head.get("enable_full_text", False)),
                  bm25_k1=head.get("bm25_k1", 1.2), bm25_b=head.get("bm25_b", 0.75), filter_route=filter_route,
                  rrf_route=rrf_route, index_type=head.get("index_type", "FLAT"), nlist=head.get("nlist", 8192),
-                 nprobe=head.get("nprobe", 16))
+                 nprobe=head.get("nprobe", 16), filter_eval=filter_eval)
         n = len(ids)
         for owned, *_ in shards:
             if len(owned) and (owned.min() < 0 or owned.max() >= n):
