@@ -401,6 +401,49 @@ int vrag_ivf_index_read(vrag_ivf_index* ivf, float* centroids /*[nlist,dim]*/, u
 int vrag_ivf_index_search(vrag_ivf_index* ivf, const float* queries /*[nq,dim] host*/, int32_t nq, int32_t k, int32_t nprobe,
                           float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, int64_t* scanned_rows /*[nq] or NULL*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * SQ8 dense rows (csrc/sq8.hip): a scalar-quantised dense field -- int8 codes and one fp32 scale per row, dim + 4 bytes per
+ * row in HBM (the code stride is dim rounded up to 16 bytes, pad codes zero) -- searched with int8 queries.  Opt-in and
+ * APPROXIMATE in what a code says about its component; everything below is exact and is the contract.
+ * The rule, for an fp32 vector x[dim], a stored row and a query alike:
+ *   m = max_c |x[c]|;  s = m / 127.0f (one correctly rounded fp32 division);
+ *   code[c] = clamp(rintf(x[c] / s), -127, 127)  (fp32 division, round half to even);  m == 0: s = 0 and every code 0.
+ * Score of query q against row r:
+ *   idot = sum_c int(cq[c]) * int(cr[c])           an exact int32 (dim <= 4096: |idot| <= 4096 * 127^2 < 2^31)
+ *   score = (float)idot * (s_q * s_r)              three fp32 roundings: the conversion (nearest even), the scale product,
+ *                                                  the final product; no fused multiply-add, no reciprocal, no fast-math
+ * so every score is defined bit for bit and every route returns the same bits.  Order (score desc, id asc), ties included;
+ * missing hits -1 / -inf.  Rows and queries are expected to be finite; a scale product that underflows to zero may give -0
+ * scores and is outside the contract.
+ *   create         1 <= dim <= 4096, 0 < capacity < 2^32 - 1.
+ *   add            host fp32 rows [n, dim], staged in slabs through the device form; all of them or (VRAG_ERR_CAPACITY) none.
+ *   add_device     device fp32 rows [n, dim]; quantised on the device on `stream`, which is synchronised before the call returns.
+ *                  Rows [0, size) are never rewritten; the size is published under the handle's lock after the rows are in place.
+ *   read           rows [first_row, first_row + n) as codes [n, dim] (without the pad) and scales [n]; either pointer may be NULL.
+ *   search         1 <= k <= 1024, queries host fp32, quantised on the device by the rule.  Lists of up to 64 come from one pass;
+ *                  longer ones as exact pages of 64 (a page admits only keys below the previous page's last key).
+ *   search_filtered  the same over the rows r < min(n_allow, size) whose bit is set (bit r % 32 of word r / 32); rows at or
+ *                  beyond n_allow are excluded; an empty mask returns -1 / -inf without a launch; a NULL mask with
+ *                  n_allow > 0 is VRAG_ERR_INVALID.  The kernels skip cleared rows: the cost follows the shard, not the mask.
+ *   set_route      0 = automatic, 1 = scan kernel (streaming; v_dot4_i32_i8; a few queries per pass over the shard), 2 = tile
+ *                  kernel (v_mfma_i32_16x16x64_i8; up to 64 query columns per pass).  Automatic scans up to 4 queries and
+ *                  tiles above.  A unit-test and tuning knob: integer arithmetic makes both routes return the same bits.
+ * Argument errors are VRAG_ERR_INVALID before anything is launched or allocated; no device is VRAG_ERR_NO_DEVICE.  The handle
+ * has its own scratch, stream and lock. */
+typedef struct vrag_sq8_index vrag_sq8_index;
+int vrag_sq8_index_create(int32_t dim, int64_t capacity, int32_t device, vrag_sq8_index** out);
+void vrag_sq8_index_destroy(vrag_sq8_index* ix);
+int64_t vrag_sq8_index_size(vrag_sq8_index* ix);
+int vrag_sq8_index_add(vrag_sq8_index* ix, const float* rows /*[n,dim] host*/, int64_t n);
+int vrag_sq8_index_add_device(vrag_sq8_index* ix, const float* rows /*[n,dim] device*/, int64_t n, void* stream);
+int vrag_sq8_index_read(vrag_sq8_index* ix, int64_t first_row, int64_t n, int8_t* codes /*[n,dim] or NULL*/, float* scales /*[n] or NULL*/);
+int vrag_sq8_index_set_route(vrag_sq8_index* ix, int32_t route);
+int vrag_sq8_index_search(vrag_sq8_index* ix, const float* queries /*[nq,dim] host*/, int32_t nq, int32_t k,
+                          float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, void* stream);
+int vrag_sq8_index_search_filtered(vrag_sq8_index* ix, const float* queries /*[nq,dim] host*/, int32_t nq, int32_t k,
+                                   const uint32_t* allow /*host, bit r%32 of word r/32*/, int64_t n_allow,
+                                   float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, void* stream);
+
 /* Sparse (SPLADE) rows in CSR, term ids < vocab <= 65536; only documents sharing a term with the
  * query (score > 0) are hits, like an inverted index.  ids are CSR row numbers. */
 typedef struct vrag_sparse_index vrag_sparse_index;

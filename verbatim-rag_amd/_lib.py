@@ -145,6 +145,15 @@ SIGNATURES = {
     "vrag_ivf_index_stats": (C.c_int, [_H, _IP, _LP, _LP]),
     "vrag_ivf_index_read": (C.c_int, [_H, _FP, C.c_void_p, C.c_void_p]),
     "vrag_ivf_index_search": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, _FP, _LP, _LP, C.c_void_p]),
+    "vrag_sq8_index_create": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(_H)]),
+    "vrag_sq8_index_destroy": (None, [_H]),
+    "vrag_sq8_index_size": (C.c_int64, [_H]),
+    "vrag_sq8_index_add": (C.c_int, [_H, _FP, C.c_int64]),
+    "vrag_sq8_index_add_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p]),
+    "vrag_sq8_index_read": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "vrag_sq8_index_set_route": (C.c_int, [_H, C.c_int32]),
+    "vrag_sq8_index_search": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, _FP, _LP, C.c_void_p]),
+    "vrag_sq8_index_search_filtered": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _FP, _LP, C.c_void_p]),
     "vrag_row_filter_create": (C.c_int, [C.c_int32, C.POINTER(_H)]),
     "vrag_row_filter_destroy": (None, [_H]),
     "vrag_row_filter_add_column": (C.c_int, [_H, _IP]),

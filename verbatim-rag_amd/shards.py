@@ -154,6 +154,56 @@ class DenseShard(_Handle):
         super().close()
 
 
+class Sq8Shard(_Handle):
+    """One GPU's slice of the dense corpus as SQ8 rows (`vrag_sq8_index`, include/vrag_amd.h "SQ8 dense rows"): int8 codes
+    and one fp32 scale per row, int8 queries, integer-exact scores.  The call shapes are `DenseShard`'s."""
+
+    _destroy = "vrag_sq8_index_destroy"
+    ivf = None    # no IVF overlay over int8 rows
+
+    def __init__(self, dim: int, capacity: int, device: int = 0):
+        _lib.require_gpu()
+        self.dim, self.capacity = dim, capacity
+        self._open("vrag_sq8_index_create", dim, capacity, device)
+
+    def add(self, rows: np.ndarray) -> None:
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n, {self.dim}]")
+        _lib.check("vrag_sq8_index_add", self._lib.vrag_sq8_index_add(self._h, _fp(rows), rows.shape[0]))
+
+    def add_device(self, ptr: int, n: int, stream=None) -> None:
+        """Rows already in HBM (`ptr`: device address of fp32 `[n, dim]` on the shard's device), quantised there."""
+        _lib.check("vrag_sq8_index_add_device", self._lib.vrag_sq8_index_add_device(self._h, C.c_void_p(int(ptr)), int(n), stream))
+
+    def __len__(self) -> int:
+        return int(self._lib.vrag_sq8_index_size(self._h))
+
+    def read(self, first_row: int = 0, n: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """(codes int8 `[n, dim]`, scales float32 `[n]`) of rows `[first_row, first_row + n)`; `n=None`: up to the end."""
+        n = len(self) - first_row if n is None else int(n)
+        codes, scales = np.empty((max(n, 0), self.dim), np.int8), np.empty(max(n, 0), np.float32)
+        _lib.check("vrag_sq8_index_read", self._lib.vrag_sq8_index_read(self._h, int(first_row), n, _vp(codes), _vp(scales)))
+        return codes, scales
+
+    def set_route(self, route: int) -> None:
+        """0 = automatic, 1 = scan kernel, 2 = tile kernel: the same bits either way (a unit-test and tuning knob)."""
+        _lib.check("vrag_sq8_index_set_route", self._lib.vrag_sq8_index_set_route(self._h, int(route)))
+
+    def _search(self, queries, k: int, allow, stream):
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        return _search_call(self._lib, "vrag_sq8_index_search", (self._h, _fp(q)), q.shape[0], k, allow, stream)
+
+    def search(self, queries: np.ndarray, k: int, stream=None) -> Tuple[np.ndarray, np.ndarray]:
+        return self._search(queries, k, None, stream)
+
+    def search_filtered(self, queries: np.ndarray, k: int, allow_words: np.ndarray, n_allow: int,
+                        stream=None) -> Tuple[np.ndarray, np.ndarray]:
+        """`search` over the rows `r < min(n_allow, len(self))` whose bit is set in `allow_words` (see
+        `DenseShard.search_filtered`): the search kernels skip the other rows (`vrag_sq8_index_search_filtered`)."""
+        return self._search(queries, k, (allow_words, n_allow), stream)
+
+
 class IvfOverlay(_Handle):
     """IVF_FLAT lists over a `DenseShard`'s resident rows (`vrag_ivf_index`): centroids, list offsets and row numbers only.
     The shard must outlive it (`DenseShard.ivf` owns it and closes it first)."""

@@ -24,7 +24,7 @@ import numpy as np
 from . import _lib
 # The layers under the store, re-exported here under the names callers and tests have always used.  The store resolves
 # DenseShard / SparseShard / IvfOverlay / TextIndex through THIS module's globals at call time (tests replace them here).
-from .shards import (_FP, _IP, _LP, DenseShard, IvfOverlay, RowFilter, SparseShard, TextIndex, _allow_words, _bitmap,  # noqa: F401
+from .shards import (_FP, _IP, _LP, DenseShard, IvfOverlay, RowFilter, SparseShard, Sq8Shard, TextIndex, _allow_words, _bitmap,  # noqa: F401
                      _utf8_batch, dicts_to_csr, tokenize_keys)
 from .store_columns import MetaColumn
 from .store_filter import _FILTER_TOKEN, _typed, compile_filter, parse_filter  # noqa: F401
@@ -297,6 +297,20 @@ def check_index_config(index_type: str, nlist: int, nprobe: int, sharded: bool) 
         raise ValueError("index_type='IVF_FLAT' is single-GPU: sharded stores (distributed=True or a comm) keep FLAT")
 
 
+DENSE_DTYPES = ("f32", "bf16", "int8")
+
+
+def check_dense_dtype(dense_dtype: str, index_type: str, sharded: bool) -> None:
+    """The constructor's refusals for `dense_dtype` (pure: no device needed).  "int8" (SQ8 rows, `Sq8Shard`) has no
+    device-resident search form and no IVF overlay yet, so it is single-GPU and FLAT."""
+    if dense_dtype not in DENSE_DTYPES:
+        raise ValueError(f"dense_dtype must be 'f32', 'bf16' or 'int8' (got {dense_dtype!r})")
+    if dense_dtype == "int8" and sharded:
+        raise ValueError("dense_dtype='int8' is single-GPU: sharded stores (distributed=True or a comm) keep 'f32' or 'bf16'")
+    if dense_dtype == "int8" and index_type == "IVF_FLAT":
+        raise ValueError("dense_dtype='int8' searches FLAT: index_type='IVF_FLAT' needs 'f32' or 'bf16' rows")
+
+
 _JSON_PLAIN = (str, int, float, bool, type(None))
 
 
@@ -437,7 +451,10 @@ class GpuVectorStore(VectorStore):
     outgrows a quarter of it).  Dense rows are stored fp32 like the reference's FLOAT_VECTOR field
     (milvus_local.py:109-118): 4 * dim bytes per row in HBM (times `dense_headroom` of append room) and as much on the
     host; `dense_dtype="bf16"` halves the HBM bytes a query streams at the price of rounding the stored rows, which
-    also gives up bit-exact ranking between rows whose fp32 scores nearly tie.
+    also gives up bit-exact ranking between rows whose fp32 scores nearly tie; `dense_dtype="int8"` stores SQ8 rows
+    (`Sq8Shard`: int8 codes and one fp32 scale per row, dim + 4 bytes, half of bf16's stream) and quantises the queries by
+    the same rule -- scores are the integer-exact ones of include/vrag_amd.h "SQ8 dense rows", approximate only in what a
+    code says about its component; single-GPU and FLAT, the host keeps its fp32 rows.
     `filter` supports the comparison subset of Milvus expressions in `parse_filter`
     (the reference itself only builds `metadata["document_id"] == "..."`, index.py:735-739); anything else is
     rejected loudly.  Filters and deletes act before the search like Milvus' (a selective filter still returns its
@@ -481,6 +498,12 @@ class GpuVectorStore(VectorStore):
             return True
         return self.dense_dim is not None and self.dense_dim % 64 == 0 and self.dense_dim <= 768
 
+    def _new_dense_shard(self, capacity: int):
+        """An empty dense shard of this store's `dense_dtype` with room for `capacity` rows."""
+        if self.dense_dtype == "int8":
+            return Sq8Shard(self.dense_dim, capacity, self.device)
+        return DenseShard(self.dense_dim, capacity, self.dense_dtype, self.device, prefilter=self._use_prefilter())
+
     def __init__(self, dense_dim: Optional[int] = 384, sparse_vocab: Optional[int] = 30522, enable_dense: bool = True,
                  enable_sparse: bool = True, dense_dtype: str = "f32", device: int = 0, distributed: bool = False,
                  group=None, comm=None, payload: str = "sharded", dense_headroom: float = 1.5,
@@ -492,6 +515,8 @@ class GpuVectorStore(VectorStore):
         scored on the device (`TextIndex`).  Off by default.  On a sharded store (`distributed=True` or a `comm`) the
         corpus-wide BM25 statistics are summed over the ranks, which needs an initialised `torch.distributed` and a `comm`
         with `sum_int64`: ValueError otherwise.
+        `dense_dtype`: "f32" (default), "bf16" or "int8" (see the class docstring); "int8" with `distributed=True`, a `comm`
+        or `index_type="IVF_FLAT"` raises ValueError.  Kept in a saved store's manifest.
         `dense_prefilter` (fp32 rows only): keep a bf16 image of the rows beside them so that every search streams
         half (small batches) or a fraction (large ones) of the bytes of the full fp32 scan and returns the same bits (`DenseShard`).  It costs
         +50 % of the dense rows' HBM.  "auto" (default) = on where the image route exists (dim % 64 == 0 and <= 768,
@@ -521,10 +546,9 @@ class GpuVectorStore(VectorStore):
         `nprobe` per call; n >= nlist returns the FLAT results.  Lists of more than 64 rows per method, filtered queries left
         short and sharded stores search FLAT.  Kept in a saved store's manifest (FLAT stores write nothing new)."""
         check_index_config(index_type, nlist, nprobe, distributed or comm is not None)
+        check_dense_dtype(dense_dtype, index_type, distributed or comm is not None)
         self._lib = _lib.load()
         _lib.require_gpu()
-        if dense_dtype not in ("f32", "bf16"):
-            raise ValueError(f"dense_dtype must be 'f32' or 'bf16' (got {dense_dtype!r})")
         if payload not in ("sharded", "replicated"):
             raise ValueError(f"payload must be 'sharded' or 'replicated' (got {payload!r})")
         if filter_route not in ("subset", "bitmap"):
@@ -763,7 +787,7 @@ class GpuVectorStore(VectorStore):
                     # (re)build with head-room so later inserts append instead of re-uploading every row
                     self._dense = None                  # released now unless a search on another thread still holds it
                     self._dense_cap = max(1024, int(n * self.dense_headroom))
-                    dense = DenseShard(self.dense_dim, self._dense_cap, self.dense_dtype, self.device, prefilter=self._use_prefilter())
+                    dense = self._new_dense_shard(self._dense_cap)
                     dense.add(rows)
                     self._dense = dense
                 else:
@@ -1085,7 +1109,7 @@ class GpuVectorStore(VectorStore):
                 local = np.nonzero(known & mask[np.where(known, owned, 0)])[0] if len(owned) else np.zeros(0, np.int64)
                 shard = None
                 if len(local) and kind == "dense":
-                    shard = DenseShard(self.dense_dim, len(local), self.dense_dtype, self.device, prefilter=self._use_prefilter())
+                    shard = self._new_dense_shard(len(local))
                     shard.add(self._dense_rows.data[local])
                 elif len(local):
                     shard = SparseShard(self.sparse_vocab, *csr_take_rows(self._sp_ptr.data, self._sp_idx.data, self._sp_val.data, local),
