@@ -234,52 +234,83 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
   const float* l_mu = reinterpret_cast<const float*>(smem + QA_MU) + srow0;
   const float* l_rs = reinterpret_cast<const float*>(smem + QA_RS) + srow0;
   const float* l_ls = reinterpret_cast<const float*>(smem + QA_LS);
-  // ---- V^T third (un-swapped accumulators: lane = feature d, registers = tokens)
+  // Every table value is read from LDS ONCE per wave and kept for all of its uses (the compiler hoists none of these reads by
+  // itself: written per use they were ~128 ds_read_b128 per lane, three quarters of them re-reads, each at the head of a
+  // load -> wait -> use chain with one other wave on the SIMD to hide it).  Same operations on the same operands in the same
+  // order as the per-use form: the outputs are bit-identical.
+  // ---- V^T third (un-swapped accumulators: lane = feature d, registers = tokens): the statistics of a token pair (tp) are read
+  // once for the four feature blocks (db).  Keys past the end of the sequence are masked to probability 0, and their V must be a
+  // finite number for 0 * v to stay 0: only a wave that holds the sequence's end (or none of it) pays the select per element.
+  // The two bodies sit inside the tp loop: one branch around the whole third spills in the fold instantiations.
+  int whole = uniform(qrow0 + 64 <= S);   // wave-uniform, and opaque: the compiler must not relate it to `active` (see `mm` above)
+  asm volatile("" : "+s"(whole));
 #pragma unroll
-  for (int db = 0; db < 4; ++db) {
-    const int d = db * 16 + l15;
-    const float lsv = FOLD ? l_ls[128 + d] : 0.f;
+  for (int tp = 0; tp < 2; ++tp) {
+    f32x4 m4[2], r4[2];
 #pragma unroll
-    for (int tp = 0; tp < 2; ++tp) {
-      V8 vv;
-#pragma unroll
-      for (int a = 0; a < 2; ++a) {
-        const int rt = 2 * tp + a;
-        f32x4 m4 = {0.f, 0.f, 0.f, 0.f}, r4 = {1.f, 1.f, 1.f, 1.f};
-        if constexpr (FOLD) {
-          m4 = *reinterpret_cast<const f32x4*>(l_mu + rt * 16 + 4 * g);
-          r4 = *reinterpret_cast<const f32x4*>(l_rs + rt * 16 + 4 * g);
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {   // packed fp32, two tokens at a time
-          const int r0 = 2 * h;
-          const f32x2 v = pk_fma(f32x2{-m4[r0], -m4[r0 + 1]}, splat2(lsv), f32x2{acc[8 + db][rt][r0], acc[8 + db][rt][r0 + 1]}) * f32x2{r4[r0], r4[r0 + 1]};
-#pragma unroll
-          for (int e = 0; e < 2; ++e)   // keys past the end are masked to probability 0: their V must be a finite number for 0 * v to stay 0
-            vv[a * 4 + r0 + e] = qrow0 + rt * 16 + 4 * g + r0 + e < S ? Op<T>::to(v[e], p.f16_sat) : (T)0.f;
-        }
+    for (int a = 0; a < 2; ++a) {
+      m4[a] = f32x4{0.f, 0.f, 0.f, 0.f};
+      r4[a] = f32x4{1.f, 1.f, 1.f, 1.f};
+      if constexpr (FOLD) {
+        m4[a] = *reinterpret_cast<const f32x4*>(l_mu + (2 * tp + a) * 16 + 4 * g);
+        r4[a] = *reinterpret_cast<const f32x4*>(l_rs + (2 * tp + a) * 16 + 4 * g);
       }
-      const int c = wave * 8 + tp * 4 + g;   // 16-byte chunk of the row: keys 64 w + 32 tp .. + 31, slot order (see top)
-      *reinterpret_cast<V8*>(smem + QA_V_OFF + d * 1024 + ((c ^ l15) << 4)) = vv;
     }
+    auto v_blocks = [&](auto tail_c) {
+      constexpr bool TAIL = decltype(tail_c)::value;
+#pragma unroll
+      for (int db = 0; db < 4; ++db) {
+        const int d = db * 16 + l15;
+        const float lsv = FOLD ? l_ls[128 + d] : 0.f;   // one float, read per (tp, db): four of them kept across tp spill
+        V8 vv;
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+          const int rt = 2 * tp + a;
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {   // packed fp32, two tokens at a time
+            const int r0 = 2 * h;
+            const f32x2 v = pk_fma(f32x2{-m4[a][r0], -m4[a][r0 + 1]}, splat2(lsv), f32x2{acc[8 + db][rt][r0], acc[8 + db][rt][r0 + 1]}) * f32x2{r4[a][r0], r4[a][r0 + 1]};
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+              if constexpr (TAIL) vv[a * 4 + r0 + e] = qrow0 + rt * 16 + 4 * g + r0 + e < S ? Op<T>::to(v[e], p.f16_sat) : (T)0.f;
+              else vv[a * 4 + r0 + e] = Op<T>::to(v[e], p.f16_sat);
+            }
+          }
+        }
+        const int c = wave * 8 + tp * 4 + g;   // 16-byte chunk of the row: keys 64 w + 32 tp .. + 31, slot order (see top)
+        *reinterpret_cast<V8*>(smem + QA_V_OFF + d * 1024 + ((c ^ l15) << 4)) = vv;
+      }
+    };
+    if (whole) v_blocks(std::false_type{});
+    else v_blocks(std::true_type{});
   }
-  // ---- q and k thirds: rotate accumulators a0 .. a0 + 3 of row tile rt, out[s] = the two 8-value operand fragments
-  auto rope_rows = [&](int a0, int rt, int ls_off, float scale, V8 (&out)[2]) {
+  // ---- q and k thirds.  Once per wave: the rotary rows 0 .. 15 of the lane's token (cb / sb depend on (l15, np) only) and the
+  // fold sums of the k and the q features (lsum[0] / lsum[1]; (np, g) only).  Once per row tile: its statistics and the rotary
+  // rows 16 b, combined with cb / sb into the tile's cos / sin (angle addition) -- for k, whose rows go to LDS at once, and then
+  // for q: the k accumulators of the tile are dead by then, which is the room its cos / sin live in.
+  f32x4 cb[2], sb[2], lsum[2][2][2];
+#pragma unroll
+  for (int np = 0; np < 2; ++np) {
+    const int dd = np * 16 + 4 * g;
+    const int bsw = l15 * 128 + ((((dd >> 2) ^ ((l15 >> 1) & 7))) << 4);
+    cb[np] = *reinterpret_cast<const f32x4*>(smem + QA_CB + bsw);
+    sb[np] = *reinterpret_cast<const f32x4*>(smem + QA_SB + bsw);
+#pragma unroll
+    for (int kq = 0; kq < 2; ++kq)
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        lsum[kq][np][hf] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (FOLD) lsum[kq][np][hf] = *reinterpret_cast<const f32x4*>(l_ls + (kq == 0 ? 64 : 0) + 32 * hf + dd);
+      }
+  }
+  // rotate accumulators a0 .. a0 + 3 of row tile rt by the tile's cos / sin (c / sn), out[s] = the two 8-value operand fragments
+  auto rope_rows = [&](int a0, int rt, const f32x4 (&ls)[2][2], const f32x2 (&cs)[2][2], const f32x2 (&sns)[2][2], float mu, float rs, float scale,
+                       V8 (&out)[2]) {
     const bool live = qrow0 + rt * 16 + l15 < S;
-    const float mu = FOLD ? l_mu[rt * 16 + l15] : 0.f, rs = FOLD ? l_rs[rt * 16 + l15] : 1.f;
 #pragma unroll
     for (int np = 0; np < 2; ++np) {
-      const int dd = np * 16 + 4 * g;
-      const f32x4 ca = *reinterpret_cast<const f32x4*>(smem + QA_CA + (((qrow0 >> 4) + rt) * 32 + dd) * 4);
-      const f32x4 sa = *reinterpret_cast<const f32x4*>(smem + QA_SA + (((qrow0 >> 4) + rt) * 32 + dd) * 4);
-      const int bsw = l15 * 128 + ((((dd >> 2) ^ ((l15 >> 1) & 7))) << 4);
-      const f32x4 cb = *reinterpret_cast<const f32x4*>(smem + QA_CB + bsw);
-      const f32x4 sb = *reinterpret_cast<const f32x4*>(smem + QA_SB + bsw);
-      f32x4 l1 = {0.f, 0.f, 0.f, 0.f}, l2 = {0.f, 0.f, 0.f, 0.f};
-      if constexpr (FOLD) {
-        l1 = *reinterpret_cast<const f32x4*>(l_ls + ls_off + dd);
-        l2 = *reinterpret_cast<const f32x4*>(l_ls + ls_off + 32 + dd);
-      }
+      const f32x4& l1 = ls[np][0];
+      const f32x4& l2 = ls[np][1];
       // two columns at a time as packed fp32 (v_pk_fma_f32 / v_pk_mul_f32 on the accumulators' own register pairs; round 4):
       // this epilogue is VALU-bound, and every operation of it is FMA-class -- same operations, same order as the scalar form
 #pragma unroll
@@ -290,8 +321,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
           x1 = pk_fma(splat2(-mu), f32x2{l1[j0], l1[j0 + 1]}, x1) * rs;
           x2 = pk_fma(splat2(-mu), f32x2{l2[j0], l2[j0 + 1]}, x2) * rs;
         }
-        const f32x2 ca2 = {ca[j0], ca[j0 + 1]}, sa2 = {sa[j0], sa[j0 + 1]}, cb2 = {cb[j0], cb[j0 + 1]}, sb2 = {sb[j0], sb[j0 + 1]};
-        const f32x2 c = pk_fma(-sa2, sb2, ca2 * cb2), sn = pk_fma(ca2, sb2, sa2 * cb2);   // cos / sin of (16 b + i) f
+        const f32x2 c = cs[np][h], sn = sns[np][h];
         // q*cos + rotate_half(q)*sin, rotate_half = cat(-x2, x1)  (TF:188-219)
         const f32x2 o1 = pk_fma(-x2, sn, x1 * c) * scale, o2 = pk_fma(x1, sn, x2 * c) * scale;
         // rows past the end of the sequence are masked (keys) or never stored (queries); only the fp16 conversion cares,
@@ -309,17 +339,31 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
       }
     }
   };
+  V8 qf[4][2];
 #pragma unroll
   for (int rt = 0; rt < 4; ++rt) {
+    const float mu = FOLD ? l_mu[rt * 16 + l15] : 0.f, rs = FOLD ? l_rs[rt * 16 + l15] : 1.f;
+    f32x2 c[2][2], sn[2][2];   // cos / sin of (16 b + i) f
+#pragma unroll
+    for (int np = 0; np < 2; ++np) {
+      const int dd = np * 16 + 4 * g;
+      const f32x4 ca = *reinterpret_cast<const f32x4*>(smem + QA_CA + (((qrow0 >> 4) + rt) * 32 + dd) * 4);
+      const f32x4 sa = *reinterpret_cast<const f32x4*>(smem + QA_SA + (((qrow0 >> 4) + rt) * 32 + dd) * 4);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int j0 = 2 * h;
+        const f32x2 ca2 = {ca[j0], ca[j0 + 1]}, sa2 = {sa[j0], sa[j0 + 1]}, cb2 = {cb[np][j0], cb[np][j0 + 1]}, sb2 = {sb[np][j0], sb[np][j0 + 1]};
+        c[np][h] = pk_fma(-sa2, sb2, ca2 * cb2);
+        sn[np][h] = pk_fma(ca2, sb2, sa2 * cb2);
+      }
+    }
     V8 kf[2];
-    rope_rows(4, rt, 64, 1.0f, kf);
+    rope_rows(4, rt, lsum[0], c, sn, mu, rs, 1.0f, kf);
     const int row = srow0 + rt * 16 + l15;   // LDS slot position
 #pragma unroll
     for (int s = 0; s < 2; ++s) *reinterpret_cast<V8*>(smem + row * 128 + (((4 * s + g) ^ ((row >> 1) & 7)) << 4)) = kf[s];
+    rope_rows(0, rt, lsum[1], c, sn, mu, rs, p.q_scale, qf[rt]);
   }
-  V8 qf[4][2];
-#pragma unroll
-  for (int rt = 0; rt < 4; ++rt) rope_rows(0, rt, 0, p.q_scale, qf[rt]);
   __syncthreads();   // K and V^T of the whole sequence are in LDS
 
   // ---------------------------------------------------------------- 3. attention over the LDS-resident keys
