@@ -2,7 +2,8 @@
  * these entry points exist only in libvrag_amd_dbg.so, the harness build of the same sources (verbatim-rag_amd/build.py,
  * -DVRAG_DEBUG_API: it also keeps the phase-decomposition branches of the fused kernel that the product build compiles out).
  * tools/, tests/test_attention_unit_gpu.py, tests/test_attn_unit_gpu.py, tests/test_gemm_unit_gpu.py,
- * tests/test_qkv_attn_unit_gpu.py, tests/test_rows_unit_gpu.py, tests/test_glue_unit_gpu.py, tests/test_topk_unit_gpu.py and
+ * tests/test_qkv_attn_unit_gpu.py, tests/test_rows_unit_gpu.py, tests/test_glue_unit_gpu.py, tests/test_topk_unit_gpu.py,
+ * tests/test_topk_instantiations_gpu.py and
  * tests/test_text_unit_gpu.py load it beside the product library. */
 #ifndef VRAG_AMD_DEBUG_H
 #define VRAG_AMD_DEBUG_H
@@ -345,6 +346,56 @@ typedef struct vrag_debug_topk_args {
   int32_t config[7];         /* out, score_stage: the tile configuration that ran: BM, BN, WM, WN, NS, HW, KCH */
 } vrag_debug_topk_args;
 int vrag_debug_topk_run(vrag_debug_topk_args* args, int32_t device);
+
+/* Launch log of the dense scan, prefilter, sparse and per-query merge kernels of csrc/topk.hip, which the harness build compiles
+ * with a note in front of each of their launches (the product build has none).  Every vrag_dense_index_* / vrag_sparse_index_*
+ * call made through THIS library appends one entry (id, p0, p1) per launch, in launch order: the kernel and the template
+ * instantiation its selection code picked.  Not logged: the tiled search (vrag_debug_topk_run tests its kernels), the filtered
+ * searches, IVF, SQ8, ingest and the shard merge.  The log is per process, holds 4 096 entries and drops what comes after.
+ *   id                  kernel                                           p0, p1
+ *   DENSE_BF16          dense_topk_kernel<false, QT, DIMC>               QT, DIMC
+ *   DENSE_F32           dense_topk_kernel<true, QT, DIMC>                QT, DIMC
+ *   MFMA                dense_topk_mfma_kernel                           0, 0
+ *   MFMA2               dense_topk_mfma2_kernel<KT>                      KT, 0
+ *   EXACT               dense_topk_exact_kernel<NSLOT>                   NSLOT, 0
+ *   EXACT2              dense_topk_exact2_kernel<KT>                     KT, 0
+ *   SEED_THRESHOLD      topk_seed_threshold_kernel                       0, 0
+ *   PF_PREFIX           prefilter_prefix_kernel<DIMC>                    DIMC, 0
+ *   PF_COLLECT          prefilter_collect_kernel<DIMC>                   DIMC, 0
+ *   PF_COLLECT_MULTI    prefilter_collect_multi_kernel<DIMC32, QN>       DIMC32, QN
+ *   PF_RESCORE_LIST     prefilter_rescore_list_kernel<FROM_KEYS>         FROM_KEYS, 0
+ *   PF_RESCORE          prefilter_rescore_kernel                         0, 0
+ *   PF_COMBINE          prefilter_combine_kernel                         0, 0
+ *   SPARSE              sparse_topk_kernel<LDSQ>                         LDSQ, 0
+ *   SPARSE_SCATTER      sparse_scatter_queries_kernel                    0, 0
+ *   SPARSE_MULTI        sparse_topk_multi_kernel<QB, 16, PAD>            QB, PAD
+ *   MERGE_LISTS         topk_merge_lists_kernel                          0, 0
+ *   MERGE_SCAN          topk_merge_scan_kernel                           0, 0 */
+enum {
+  VRAG_DEBUG_TOPK_LAUNCH_DENSE_BF16 = 0,
+  VRAG_DEBUG_TOPK_LAUNCH_DENSE_F32 = 1,
+  VRAG_DEBUG_TOPK_LAUNCH_MFMA = 2,
+  VRAG_DEBUG_TOPK_LAUNCH_MFMA2 = 3,
+  VRAG_DEBUG_TOPK_LAUNCH_EXACT = 4,
+  VRAG_DEBUG_TOPK_LAUNCH_EXACT2 = 5,
+  VRAG_DEBUG_TOPK_LAUNCH_SEED_THRESHOLD = 6,
+  VRAG_DEBUG_TOPK_LAUNCH_PF_PREFIX = 7,
+  VRAG_DEBUG_TOPK_LAUNCH_PF_COLLECT = 8,
+  VRAG_DEBUG_TOPK_LAUNCH_PF_COLLECT_MULTI = 9,
+  VRAG_DEBUG_TOPK_LAUNCH_PF_RESCORE_LIST = 10,
+  VRAG_DEBUG_TOPK_LAUNCH_PF_RESCORE = 11,
+  VRAG_DEBUG_TOPK_LAUNCH_PF_COMBINE = 12,
+  VRAG_DEBUG_TOPK_LAUNCH_SPARSE = 13,
+  VRAG_DEBUG_TOPK_LAUNCH_SPARSE_SCATTER = 14,
+  VRAG_DEBUG_TOPK_LAUNCH_SPARSE_MULTI = 15,
+  VRAG_DEBUG_TOPK_LAUNCH_MERGE_LISTS = 16,
+  VRAG_DEBUG_TOPK_LAUNCH_MERGE_SCAN = 17
+};
+/* Empties the log. */
+void vrag_debug_topk_launch_log_reset(void);
+/* Copies the first min(cap, *count) entries to entries [cap][3] (nullable with cap = 0); *count = entries logged since the last
+ * reset, *overflowed != 0 = launches were dropped behind the 4 096th. */
+int vrag_debug_topk_launch_log_read(int32_t* entries, int32_t cap, int32_t* count, int32_t* overflowed);
 
 /* Unit-test hook of the full-text index build and BM25 scoring stages alone (csrc/fulltext.hip, which the harness build compiles
  * with the hook in it), one stage per call, chosen by `op`.  Host buffers in; the hook calls the host launchers the product path

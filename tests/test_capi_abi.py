@@ -45,6 +45,27 @@ def test_debug_harness_is_a_separate_library():
     _lib.load_debug()
 
 
+def test_topk_launch_log_is_harness_only_and_its_ids_match_the_header():
+    """vrag_debug_topk_launch_log_reset / _read (tests/test_topk_instantiations_gpu.py): exported by the harness library only, bound
+    together with that library's own index entry points (the log records searches made through IT), the header's enum equal to
+    _lib.DEBUG_TOPK_LAUNCH_IDS, and an empty log readable without a GPU."""
+    hdr = open(os.path.join(ROOT, "include", "vrag_amd_debug.h")).read()
+    enum = {n: int(v) for n, v in re.findall(r"VRAG_DEBUG_TOPK_LAUNCH_([A-Z0-9_]+) = (\d+)", hdr)}
+    assert enum == _lib.DEBUG_TOPK_LAUNCH_IDS and sorted(enum.values()) == list(range(len(enum)))
+    prod = ctypes.CDLL(_lib.library_path())
+    for n in ("vrag_debug_topk_launch_log_reset", "vrag_debug_topk_launch_log_read"):
+        assert n in _lib.DEBUG_SIGNATURES and not hasattr(prod, n)
+    dbg = _lib.load_debug()
+    for n, (res, args) in _lib.SIGNATURES.items():
+        if n.startswith(("vrag_dense_index_", "vrag_sparse_index_")):
+            assert getattr(dbg, n).argtypes == args and getattr(dbg, n).restype == res, n
+    dbg.vrag_debug_topk_launch_log_reset()
+    count, ovf = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    assert dbg.vrag_debug_topk_launch_log_read(None, 0, ctypes.byref(count), ctypes.byref(ovf)) == 0
+    assert (count.value, ovf.value) == (0, 0)
+    assert dbg.vrag_debug_topk_launch_log_read(None, 4, ctypes.byref(count), ctypes.byref(ovf)) == -1   # entries missing
+
+
 def test_abi_version_and_error_string():
     lib = _lib.load()
     assert lib.vrag_abi_version() == _lib.ABI_VERSION == 6

@@ -226,7 +226,14 @@ DEBUG_SIGNATURES = {
     "vrag_debug_text_index_read": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vrag_debug_token_spans": (C.c_int, [_FP, C.c_int64, _IP, _IP, _IP, _IP, C.c_int32, _LP, _IP, C.c_int32, C.c_float, C.c_int32, C.c_int32,
                                          C.c_int32, _IP, _IP, C.c_int32]),
+    "vrag_debug_topk_launch_log_reset": (None, []),
+    "vrag_debug_topk_launch_log_read": (C.c_int, [_IP, C.c_int32, _IP, _IP]),
 }
+
+# the enum of include/vrag_amd_debug.h behind vrag_debug_topk_launch_log_read (tests/test_capi_abi.py compares the two)
+DEBUG_TOPK_LAUNCH_IDS = {name: i for i, name in enumerate((
+    "DENSE_BF16", "DENSE_F32", "MFMA", "MFMA2", "EXACT", "EXACT2", "SEED_THRESHOLD", "PF_PREFIX", "PF_COLLECT", "PF_COLLECT_MULTI",
+    "PF_RESCORE_LIST", "PF_RESCORE", "PF_COMBINE", "SPARSE", "SPARSE_SCATTER", "SPARSE_MULTI", "MERGE_LISTS", "MERGE_SCAN"))}
 
 
 class DebugGemmArgs(C.Structure):
@@ -395,6 +402,12 @@ def load_debug() -> C.CDLL:
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
+        # the harness library is a full build: searches through ITS index entry points are the ones its launch log records
+        for name, (res, args) in SIGNATURES.items():
+            if name.startswith(("vrag_dense_index_", "vrag_sparse_index_")):
+                fn = getattr(lib, name)
+                fn.restype = res
+                fn.argtypes = args
         lib.vrag_last_error.restype = C.c_char_p
         lib.vrag_set_small_batch_rows.restype = C.c_int     # the harness library is a full build: its own copy of the threshold
         lib.vrag_set_small_batch_rows.argtypes = [C.c_int32]

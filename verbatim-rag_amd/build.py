@@ -31,10 +31,10 @@ def _newer(src: str, dst: str) -> bool:
 
 DEBUG_LIB_PATH = os.path.join(HERE, f"libvrag_amd_dbg_{VARIANT}.so" if VARIANT else "libvrag_amd_dbg.so")
 # Harness build (include/vrag_amd_debug.h): the product objects, except that the fused kernel keeps its phase-decomposition
-# branches and fulltext.hip carries its stage-by-stage unit-test hook (-DVRAG_DEBUG_API), plus the synthetic-operand timing
-# loops / unit-test hooks of debug_api.hip.
+# branches, fulltext.hip carries its stage-by-stage unit-test hook and topk.hip logs which kernel instantiation every search
+# launches (-DVRAG_DEBUG_API), plus the synthetic-operand timing loops / unit-test hooks of debug_api.hip.
 DEBUG_ONLY = ["debug_api.hip"]
-DEBUG_RECOMPILED = ["qkv_attn.hip", "fulltext.hip"]
+DEBUG_RECOMPILED = ["qkv_attn.hip", "fulltext.hip", "topk.hip"]
 
 
 def build_library(force: bool = False, verbose: bool = False, debug: bool = True) -> str:

@@ -8,7 +8,9 @@
 // Total order everywhere: (score desc, id asc).  A candidate is one u64 key
 //   [ orderable(score) : 32 | 0xFFFFFFFF - local_row : 32 ]      (max key == best hit)
 //
-// Routes as of the end of round 6 (every one pinned to oracle/topk_ref.c by tests/test_topk_gpu.py, test_full_size_gpu.py):
+// Routes as of the end of round 6 (every one pinned to oracle/topk_ref.c by tests/test_topk_gpu.py, test_full_size_gpu.py;
+// every template instantiation the scan, prefilter, sparse and merge routes select, with the launch log of the harness build as witness
+// of what ran, by tests/test_topk_instantiations_gpu.py):
 //   dense, bf16 rows
 //     1 query                      dense_topk_kernel: one 16-lane group per row, 16-byte loads, per-workgroup lists + merge (HBM-bound)
 //     >= 2 queries                 the TILED search (shards >= 4 096 rows, dim % 64 == 0): scores = rows x queries^T on the encoder's GEMM
@@ -41,6 +43,20 @@
 #include "gemm_bf16.h"
 #include "host_util.h"
 #include "topk_kernels.h"
+
+// Launch log of the harness build (include/vrag_amd_debug.h, vrag_debug_topk_launch_log_*): VRAG_LAUNCH_NOTE in front of every
+// launch of a dense scan, prefilter, sparse or per-query merge kernel records which kernel and which template instantiation the
+// selection code picked, so tests/test_topk_instantiations_gpu.py can say what a search ran without restating that code.  The
+// product build defines the macro empty: its object code is the same with and without the notes.
+#ifdef VRAG_DEBUG_API
+#include "../../include/vrag_amd_debug.h"
+namespace vrag {
+void topk_launch_note(int id, int p0, int p1);
+}
+#define VRAG_LAUNCH_NOTE(id, p0, p1) ::vrag::topk_launch_note(VRAG_DEBUG_TOPK_LAUNCH_##id, (p0), (p1))
+#else
+#define VRAG_LAUNCH_NOTE(id, p0, p1)
+#endif
 
 namespace vrag {
 
@@ -252,7 +268,11 @@ static hipError_t dense_launch_pass(const void* rows, long long n, int dim, cons
   const int cstr = F32 ? 64 : 128;
   const int dimc = dim % cstr == 0 ? dim / cstr : -1;
 #define VRAG_DENSE_CASE(QT_, DC_)                                                                               \
-  hipLaunchKernelGGL((dense_topk_kernel<F32, QT_, DC_>), dim3(n_wg), dim3(256), lds, st, rows, n, dim, dq, nq, q0, k, cand, per, bound)
+  do {                                                                                                          \
+    if (F32) { VRAG_LAUNCH_NOTE(DENSE_F32, QT_, DC_); }                                                         \
+    else { VRAG_LAUNCH_NOTE(DENSE_BF16, QT_, DC_); }                                                            \
+    hipLaunchKernelGGL((dense_topk_kernel<F32, QT_, DC_>), dim3(n_wg), dim3(256), lds, st, rows, n, dim, dq, nq, q0, k, cand, per, bound); \
+  } while (0)
   if (qt == 1) {
     if (dimc == 6) VRAG_DENSE_CASE(1, 6);
     else if (dimc == 3) VRAG_DENSE_CASE(1, 3);
@@ -981,6 +1001,7 @@ static hipError_t dense_seeded_passes(long long n, int nq, int k, u64* cand, hip
     e = pass(0, pl.prefix, 128, pl.n_wg0, cand);
     if (e == hipSuccess) e = launch_topk_merge(cand, pl.n_wg0, nq, k, out, st);
     if (e != hipSuccess) return e;
+    VRAG_LAUNCH_NOTE(SEED_THRESHOLD, 0, 0);
     hipLaunchKernelGGL(topk_seed_threshold_kernel, dim3((nq + 255) / 256), dim3(256), 0, st, out, nq, k, thr);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
@@ -1006,6 +1027,8 @@ static hipError_t dense_launch_all(int dtype, const void* rows, long long n, int
     if (e != hipSuccess) return e;
     return dense_seeded_passes(n, nq, k, cand, st, thr, out, [&](long long lo, long long hi, int per, int wgs, u64* cand_base) -> hipError_t {
       for (int q0 = 0; q0 < nq; q0 += XQ) {
+        if (regq) { VRAG_LAUNCH_NOTE(EXACT2, dim == 768 ? 24 : 12, 0); }
+        else { VRAG_LAUNCH_NOTE(EXACT, deep ? 6 : 3, 0); }
         if (regq && dim == 768) hipLaunchKernelGGL(dense_topk_exact2_kernel<24>, dim3(wgs), dim3(256), lds2, st, r32, lo, hi, dq, nq, q0, k, cand_base, per, thr, gate);
         else if (regq) hipLaunchKernelGGL(dense_topk_exact2_kernel<12>, dim3(wgs), dim3(256), lds2, st, r32, lo, hi, dq, nq, q0, k, cand_base, per, thr, gate);
         else if (deep) hipLaunchKernelGGL(dense_topk_exact_kernel<6>, dim3(wgs), dim3(256), ldsx, st, r32, lo, hi, dim, dq, nq, q0, k, cand_base, per, thr, gate);
@@ -1024,6 +1047,7 @@ static hipError_t dense_launch_all(int dtype, const void* rows, long long n, int
     const bf16_t* r16 = reinterpret_cast<const bf16_t*>(rows);
     return dense_seeded_passes(n, nq, k, cand, st, thr, out, [&](long long lo, long long hi, int per, int wgs, u64* cand_base) -> hipError_t {
       for (int q0 = 0; q0 < nq; q0 += qpp) {
+        VRAG_LAUNCH_NOTE(MFMA2, dim == 384 ? 6 : (dim == 768 ? 12 : 16), 0);
         if (dim == 384) hipLaunchKernelGGL(dense_topk_mfma2_kernel<6>, dim3(wgs), dim3(256), lds2, st, r16, lo, hi, dq, nq, q0, k, cand_base, per, thr, split);
         else if (dim == 768) hipLaunchKernelGGL(dense_topk_mfma2_kernel<12>, dim3(wgs), dim3(256), lds2, st, r16, lo, hi, dq, nq, q0, k, cand_base, per, thr, split);
         else hipLaunchKernelGGL(dense_topk_mfma2_kernel<16>, dim3(wgs), dim3(256), lds2, st, r16, lo, hi, dq, nq, q0, k, cand_base, per, thr, split);
@@ -1038,6 +1062,7 @@ static hipError_t dense_launch_all(int dtype, const void* rows, long long n, int
     const hipError_t e = set_max_dynamic_lds<&dense_topk_mfma_kernel>(kLds);
     if (e != hipSuccess) return e;
     for (int q0 = 0; q0 < nq; q0 += qpp) {
+      VRAG_LAUNCH_NOTE(MFMA, 0, 0);
       hipLaunchKernelGGL(dense_topk_mfma_kernel, dim3(n_wg), dim3(256), lds, st, reinterpret_cast<const bf16_t*>(rows), n,
                          dim, dq, nq, q0, k, cand, split);
       const hipError_t le = hipGetLastError();
@@ -2116,10 +2141,13 @@ __global__ __launch_bounds__(256) void topk_merge_lists_kernel(const u64* __rest
 }
 
 hipError_t launch_topk_merge(const u64* cand, int n_wg, int nq, int k, u64* out, hipStream_t st) {
-  if (k <= MERGE_KMAX)
+  if (k <= MERGE_KMAX) {
+    VRAG_LAUNCH_NOTE(MERGE_LISTS, 0, 0);
     hipLaunchKernelGGL(topk_merge_lists_kernel, dim3(nq), dim3(256), (size_t)256 * k * sizeof(u64), st, cand, n_wg, nq, k, out);
-  else
+  } else {
+    VRAG_LAUNCH_NOTE(MERGE_SCAN, 0, 0);
     hipLaunchKernelGGL(topk_merge_scan_kernel, dim3(nq), dim3(256), 0, st, cand, n_wg, nq, k, out);
+  }
   return hipGetLastError();
 }
 
@@ -2805,13 +2833,13 @@ DenseRoute dense_plan(const vrag_dense_index* ix, int nq, int k, DenseCaller cal
 
 template <int V> using IntC = std::integral_constant<int, V>;
 // f(IntC<DIMC>{}) with the dim-chunk constant of the single-query prefilter kernels: dim / 128 where an instantiation exists
-// (384, 768, 1024), else 0 (the generic loop)
+// (384, 768), else 0 (the generic loop).  No case for 1024: prefilter_route_ok admits the route only where dense_use_exact holds
+// (dim <= 768), so prefilter_*_kernel<8> could never be launched
 template <typename F>
 void with_pf_dimc(int dim, F f) {
   switch (dim % 128 == 0 ? dim / 128 : 0) {
     case 3: f(IntC<3>{}); break;
     case 6: f(IntC<6>{}); break;
-    case 8: f(IntC<8>{}); break;
     default: f(IntC<0>{});
   }
 }
@@ -3050,6 +3078,7 @@ static int prefilter_batch_enqueue(vrag_dense_index* ix, const float* queries, i
     const TiledCollect col{ix->d_pf_eps.p, ix->d_pfb.p, ix->d_pf_flag.p};
     if ((rc = dense_search_enqueue(ix, queries, nq, k, st, DenseRoute::Tiled, 0, /*image=*/2, &col))) return rc;
     HIP_TRY(hipEventRecord(ix->upload_done, st));
+    VRAG_LAUNCH_NOTE(PF_RESCORE_LIST, 1, 0);
     hipLaunchKernelGGL(prefilter_rescore_list_kernel<true>, dim3(PFCAP / 16, nq), dim3(256), 0, st, (const unsigned*)nullptr, ix->d_tcnt.p,
                        reinterpret_cast<const float*>(ix->rows.p), ix->dim, ix->d_q.p, ix->d_pfb.p);
     hipLaunchKernelGGL(tiled_select_kernel, dim3(nq), dim3(256), (size_t)PFCAP * sizeof(u64), st, ix->d_pfb.p, ix->d_tcnt.p, PFCAP, k, ix->d_tthr.p,
@@ -3059,6 +3088,7 @@ static int prefilter_batch_enqueue(vrag_dense_index* ix, const float* queries, i
     if ((rc = dense_search_enqueue(ix, queries, nq, PFK, st, DenseRoute::Tiled, 0, /*image=*/2))) return rc;
     HIP_TRY(hipMemcpyAsync(ix->d_pf_eps.p, eps.data(), (size_t)nq * sizeof(float), hipMemcpyHostToDevice, st));
     HIP_TRY(hipEventRecord(ix->upload_done, st));
+    VRAG_LAUNCH_NOTE(PF_RESCORE, 0, 0);
     hipLaunchKernelGGL(prefilter_rescore_kernel, dim3(nq), dim3(64), 0, st, ix->d_out.p, reinterpret_cast<const float*>(ix->rows.p), ix->dim,
                        ix->d_q.p, ix->d_pf_eps.p, k, PFK, ix->d_pf_out.p, ix->d_pf_flag.p);
     HIP_TRY(hipGetLastError());
@@ -3074,6 +3104,7 @@ static int prefilter_rescan_enqueue(vrag_dense_index* ix, int nq, int k, hipStre
   int rc;
   if ((rc = dense_scan_enqueue(ix, nq, k, st, 0, flags))) return rc;   // lists of unflagged queries: whatever the scratch held -- never picked
   const long long n = (long long)nq * k;
+  VRAG_LAUNCH_NOTE(PF_COMBINE, 0, 0);
   hipLaunchKernelGGL(prefilter_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ix->d_pf_out.p, ix->d_out.p, flags, nq, k);
   HIP_TRY(hipGetLastError());
   return VRAG_OK;
@@ -3109,6 +3140,7 @@ static int prefilter_single_enqueue(vrag_dense_index* ix, const float* dq, const
   float* kth_score0 = reinterpret_cast<float*>(ix->d_pf_thr.p + 3 * PFQ);
   auto prefix_launch = [&](int q0, int n) {
     with_pf_dimc(dim, [&](auto dc) {
+      VRAG_LAUNCH_NOTE(PF_PREFIX, dc.value, 0);
       hipLaunchKernelGGL((prefilter_prefix_kernel<dc.value>), dim3(n_wg0, n), dim3(256), lds_q + PFROWS * sizeof(u64), st, img, pf_rows, dim,
                          dq + (size_t)q0 * dim, ix->d_pf_keys.p + (size_t)q0 * PFCAP, ix->d_pf_cnt.p + q0, out_flags + q0, PFCAP, pf_block_stride);
     });
@@ -3122,6 +3154,7 @@ static int prefilter_single_enqueue(vrag_dense_index* ix, const float* dq, const
     const size_t lds_m = (size_t)(nq <= 2 ? 2 : 4) * dim * sizeof(float);
     auto collect_multi = [&](auto qn) {   // dim / 256 chunks, qn queries compiled in
       auto go = [&](auto d32) {
+        VRAG_LAUNCH_NOTE(PF_COLLECT_MULTI, d32.value, qn.value);
         hipLaunchKernelGGL((prefilter_collect_multi_kernel<d32.value, qn.value>), dim3(wgs), dim3(256), lds_m, st, img, (long long)ix->size, dim, dq,
                            nq, kth0, deps, ix->d_pf_cnt.p, ix->d_pf_cand.p, per);
       };
@@ -3133,6 +3166,7 @@ static int prefilter_single_enqueue(vrag_dense_index* ix, const float* dq, const
       }
     };
     if (!(nq <= 2 ? collect_multi(IntC<2>{}) : collect_multi(IntC<4>{}))) return VRAG_ERR_INVALID;
+    VRAG_LAUNCH_NOTE(PF_RESCORE_LIST, 0, 0);
     hipLaunchKernelGGL(prefilter_rescore_list_kernel<false>, dim3(PFCAP / 16, nq), dim3(256), 0, st, ix->d_pf_cand.p, ix->d_pf_cnt.p,
                        reinterpret_cast<const float*>(ix->rows.p), dim, dq, ix->d_pf_keys.p);
     HIP_TRY(hipGetLastError());
@@ -3145,9 +3179,11 @@ static int prefilter_single_enqueue(vrag_dense_index* ix, const float* dq, const
       hipLaunchKernelGGL(tiled_select_kernel, dim3(1), dim3(256), (size_t)PFCAP * sizeof(u64), st, qkeys, sel_cnt + q, PFCAP, k, kth0 + q,
                          kth_score0 + q, (u64*)nullptr, sel_ovf + q, n_wg0 * PFBEST);
       with_pf_dimc(dim, [&](auto dc) {
+        VRAG_LAUNCH_NOTE(PF_COLLECT, dc.value, 0);
         hipLaunchKernelGGL((prefilter_collect_kernel<dc.value>), dim3(wgs), dim3(256), lds_q, st, img, (long long)ix->size, dim, q_dev, kth0 + q,
                            deps + q, ix->d_pf_cnt.p + q, cand, per);
       });
+      VRAG_LAUNCH_NOTE(PF_RESCORE_LIST, 0, 0);
       hipLaunchKernelGGL(prefilter_rescore_list_kernel<false>, dim3(PFCAP / 16, 1), dim3(256), 0, st, cand, ix->d_pf_cnt.p + q,
                          reinterpret_cast<const float*>(ix->rows.p), dim, q_dev, qkeys);
       HIP_TRY(hipGetLastError());
@@ -3555,6 +3591,7 @@ static int sparse_launch(vrag_sparse_index* ix, int nq, int k, hipStream_t st, i
                            (long long)ix->n_docs, ix->d_qmap.p + (size_t)ps * vpad, ix->d_qw.p + (size_t)ps * QB * SUW, ix->vocab,
                            ix->pass_union[ps], nq, q0, k, slices_per_wg, ix->d_cand.p, ix->d_docid.p);
       };
+      VRAG_LAUNCH_NOTE(SPARSE_MULTI, QB, pad);
       if (QB == 16 && pad == 4) go(&sparse_topk_multi_kernel<16, 16, 4>);
       else if (QB == 16) go(&sparse_topk_multi_kernel<16, 16, 0>);
       else go(&sparse_topk_multi_kernel<8, 16, 0>);
@@ -3568,6 +3605,7 @@ static int sparse_launch(vrag_sparse_index* ix, int nq, int k, hipStream_t st, i
   const size_t lds = (size_t)16 * k * sizeof(u64) + (ldsq ? (size_t)ix->vocab * sizeof(float) : 0);
   if (ldsq) HIP_TRY(set_max_dynamic_lds<&sparse_topk_kernel<true>>(160 * 1024));
   for (int q = 0; q < nq; ++q) {
+    VRAG_LAUNCH_NOTE(SPARSE, ldsq ? 1 : 0, 0);
     if (ldsq)
       hipLaunchKernelGGL((sparse_topk_kernel<true>), dim3(n_wg), dim3(1024), lds, st, ix->cols.p, ix->vals.p, ix->slice_off.p,
                          ix->slice_len.p, ix->n_slices, (long long)ix->n_docs, ix->d_q.p, ix->vocab, nq, q, k,
@@ -3607,6 +3645,7 @@ static int sparse_scatter_enqueue(vrag_sparse_index* ix, const int64_t* q_indptr
   HIP_TRY(hipMemsetAsync(ix->d_q.p, 0, (size_t)nq * ix->vocab * sizeof(float), st));
   HIP_TRY(hipMemcpyAsync(ix->d_qcsr.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
   HIP_TRY(hipEventRecord(ix->upload_done, st));
+  VRAG_LAUNCH_NOTE(SPARSE_SCATTER, 0, 0);
   hipLaunchKernelGGL(sparse_scatter_queries_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, reinterpret_cast<const long long*>(ix->d_qcsr.p),
                      reinterpret_cast<const int*>(ix->d_qcsr.p + off_idx), reinterpret_cast<const float*>(ix->d_qcsr.p + off_val), nq, ix->vocab, ix->d_q.p);
   HIP_TRY(hipGetLastError());
@@ -3879,3 +3918,49 @@ int vrag_topk_merge(const float* scores, const int64_t* ids, int32_t n_lists, in
 }
 
 }  // extern "C"
+
+#ifdef VRAG_DEBUG_API
+// The harness build's launch log (see VRAG_LAUNCH_NOTE at the top): a bounded per-process list of (kernel id, p0, p1), one entry
+// per launch in launch order, behind a mutex of its own (searches of different handles may run on different threads).
+namespace {
+constexpr int kLaunchLogCap = 4096;
+std::mutex g_launch_log_mu;
+int32_t g_launch_log[kLaunchLogCap][3];
+int g_launch_log_n = 0;
+bool g_launch_log_overflowed = false;
+}  // namespace
+
+namespace vrag {
+void topk_launch_note(int id, int p0, int p1) {
+  std::lock_guard<std::mutex> lk(g_launch_log_mu);
+  if (g_launch_log_n >= kLaunchLogCap) {
+    g_launch_log_overflowed = true;
+    return;
+  }
+  int32_t* e = g_launch_log[g_launch_log_n++];
+  e[0] = id;
+  e[1] = p0;
+  e[2] = p1;
+}
+}  // namespace vrag
+
+extern "C" {
+
+void vrag_debug_topk_launch_log_reset(void) {
+  std::lock_guard<std::mutex> lk(g_launch_log_mu);
+  g_launch_log_n = 0;
+  g_launch_log_overflowed = false;
+}
+
+int vrag_debug_topk_launch_log_read(int32_t* entries, int32_t cap, int32_t* count, int32_t* overflowed) {
+  ARG_CHECK(count && overflowed && cap >= 0 && (entries || cap == 0), "bad arguments");
+  std::lock_guard<std::mutex> lk(g_launch_log_mu);
+  const int n = std::min<int>(cap, g_launch_log_n);
+  if (n > 0) std::memcpy(entries, g_launch_log, (size_t)n * 3 * sizeof(int32_t));
+  *count = g_launch_log_n;
+  *overflowed = g_launch_log_overflowed ? 1 : 0;
+  return VRAG_OK;
+}
+
+}  // extern "C"
+#endif  // VRAG_DEBUG_API
