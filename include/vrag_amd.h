@@ -326,6 +326,9 @@ int vrag_encoder_read_profile(vrag_encoder* enc, float* ms /*[VRAG_PROF_COUNT]*/
  * from the fp32 chain by summation order.
  * Dense rows and queries are expected to be finite: a NaN score is kept by the pass kernels (it becomes a key like any other score) and
  * dropped by the tiled search's epilogue (no comparison with the entry threshold holds), so the routes disagree on such rows.
+ * create: dim % 8 == 0, dim <= 4096, 0 < capacity < 2^32 - 1 rows.  The suite runs every dense route, the filtered search, the IVF
+ * overlay and both id forms of vrag_dense_index_search_device on shards that cross 2^32 elements (2^33 / 2^34 bytes: 1 052 929 x 4096
+ * and 5 596 929 x 768 rows) and row id 2^24 (16 781 569 x 64 rows, 513 blocks of the bitmap compaction): tests/test_scale_gpu.py.
  */
 typedef struct vrag_dense_index vrag_dense_index;
 int vrag_dense_index_create(int32_t dim, int64_t capacity, int32_t dtype, int32_t device, vrag_dense_index** out);

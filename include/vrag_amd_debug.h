@@ -3,7 +3,7 @@
  * -DVRAG_DEBUG_API: it also keeps the phase-decomposition branches of the fused kernel that the product build compiles out).
  * tools/, tests/test_attention_unit_gpu.py, tests/test_attn_unit_gpu.py, tests/test_gemm_unit_gpu.py,
  * tests/test_qkv_attn_unit_gpu.py, tests/test_rows_unit_gpu.py, tests/test_glue_unit_gpu.py, tests/test_topk_unit_gpu.py,
- * tests/test_topk_instantiations_gpu.py and
+ * tests/test_topk_instantiations_gpu.py, tests/test_scale_gpu.py and
  * tests/test_text_unit_gpu.py load it beside the product library. */
 #ifndef VRAG_AMD_DEBUG_H
 #define VRAG_AMD_DEBUG_H
