@@ -2,7 +2,7 @@
  * these entry points exist only in libvrag_amd_dbg.so, the harness build of the same sources (verbatim-rag_amd/build.py,
  * -DVRAG_DEBUG_API: it also keeps the phase-decomposition branches of the fused kernel that the product build compiles out).
  * tools/, tests/test_attention_unit_gpu.py, tests/test_attn_unit_gpu.py, tests/test_gemm_unit_gpu.py,
- * tests/test_qkv_attn_unit_gpu.py, tests/test_rows_unit_gpu.py, tests/test_glue_unit_gpu.py, tests/test_topk_unit_gpu.py,
+ * tests/test_qkv_attn_unit_gpu.py, tests/test_qkv_attn_band_blocks_gpu.py, tests/test_rows_unit_gpu.py, tests/test_glue_unit_gpu.py, tests/test_topk_unit_gpu.py,
  * tests/test_topk_instantiations_gpu.py, tests/test_scale_gpu.py and
  * tests/test_text_unit_gpu.py load it beside the product library. */
 #ifndef VRAG_AMD_DEBUG_H
@@ -21,7 +21,9 @@ int vrag_debug_gemm_ms(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t ite
 int vrag_debug_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int32_t window, int32_t iters, int32_t device,
                        float* ms_out);
 /* Same for the fused Wqkv + RoPE + attention kernel (csrc/qkv_attn.hip; S <= 512).  flags: 1 = no attention phase, 2 = no
- * main-loop MFMAs, 4 = no operand DMA (phase decomposition of the kernel's time). */
+ * main-loop MFMAs, 4 = no operand DMA, 8 = no O store, 16 = return behind the main loop (phase decomposition of the kernel's
+ * time); 32 = the banded kernel runs its generic tile body for every wave, never the static in-band-block bodies (FIRST / MID /
+ * LAST of csrc/qkv_attn.hip section 3): same bits, the time of the out-of-band blocks back. */
 int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int32_t window, int32_t iters, int32_t flags,
                            int32_t device, float* ms_out);
 /* Unit-test hook of the attention kernels alone (csrc/attention.hip), on the layout the encoder packs: sequences of any length
@@ -105,7 +107,7 @@ typedef struct vrag_debug_gemm_args {
 int vrag_debug_gemm_run(vrag_debug_gemm_args* args, int32_t device);
 
 /* Unit-test hook of the fused Wqkv + RoPE + attention kernel alone (csrc/qkv_attn.hip): host buffers in, ONE launch with
- * debug_flags = 0, outputs copied back.  w and ln_s arrive in the encoder's UNPERMUTED Wqkv layout (rows q | k | v of all heads);
+ * debug_flags = args->debug_flags (0, or 32: the only bit that leaves the result what it is), outputs copied back.  w and ln_s arrive in the encoder's UNPERMUTED Wqkv layout (rows q | k | v of all heads);
  * the hook runs permute_qkv_heads on them as the encoder does at load (ln_s with 64 readable floats behind the last head).
  * Refused before anything is launched: null required pointers, H != 64 * nh, rows % 256 != 0, seq_len outside 1..512,
  * seq_row % 8 != 0, overlapping sequences, and a sequence with seq_row + 64 * ceil(len / 64) > rows (a wave reads 64 WHOLE token
@@ -128,6 +130,7 @@ typedef struct vrag_debug_qkv_attn_args {
   float q_scale;
   int32_t n_groups;          /* out */
   int32_t f16_saturated;     /* out: an fp16 conversion of this launch clamped at +-65504 */
+  int32_t debug_flags;       /* 0, or 32 = generic tile body everywhere (vrag_debug_qkv_attn_ms above); anything else is refused */
 } vrag_debug_qkv_attn_args;
 int vrag_debug_qkv_attn_run(vrag_debug_qkv_attn_args* args, int32_t device);
 /* Host only (no GPU call): the wave descriptors either packer gives n sequences (lengths 1..512); out holds [n][8][4] int32.

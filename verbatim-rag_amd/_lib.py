@@ -252,7 +252,7 @@ class DebugQkvAttnArgs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in (
         "x", "w", "ln_s", "ln_mu", "ln_rstd", "rope_cos", "rope_sin", "o", "seq_row", "seq_len", "groups_out")] + [
         (n, C.c_int32) for n in ("rows", "H", "nh", "rope_rows", "n_seqs", "packer", "local", "window", "f16")] + [
-        ("q_scale", C.c_float), ("n_groups", C.c_int32), ("f16_saturated", C.c_int32)]
+        ("q_scale", C.c_float), ("n_groups", C.c_int32), ("f16_saturated", C.c_int32), ("debug_flags", C.c_int32)]
 
 
 class DebugAttnArgs(C.Structure):

@@ -611,6 +611,7 @@ int vrag_debug_qkv_attn_run(vrag_debug_qkv_attn_args* a, int32_t device) {
   ARG_CHECK((int64_t)a->rows * a->H < ((int64_t)1 << 31), "rows * H must stay below 2^31");
   ARG_CHECK(a->rope_rows > 0 && a->n_seqs > 0 && (a->packer == 0 || a->packer == 1), "bad rope_rows / n_seqs / packer");
   ARG_CHECK(!a->local || a->window >= 0, "bad window");
+  ARG_CHECK(a->debug_flags == 0 || a->debug_flags == 32, "debug_flags (%d) must be 0 or 32", a->debug_flags);
   ARG_CHECK(device >= 0, "bad device %d", device);
   const int n = a->n_seqs;
   for (int s = 0; s < n; ++s) {
@@ -691,7 +692,7 @@ int vrag_debug_qkv_attn_run(vrag_debug_qkv_attn_args* a, int32_t device) {
     f.window = a->window;
     f.op_dtype = a->f16 ? kOpF16 : kOpBf16;
     f.q_scale = a->q_scale;
-    f.debug_flags = 0;
+    f.debug_flags = a->debug_flags;
     f.f16_sat = sat.as<unsigned>();
     e = launch_qkv_attention(f, a->local != 0, 0);
   }

@@ -26,7 +26,7 @@ struct QkvAttnParams {
   int window;              // banded layers: keep |i - j| <= window
   int op_dtype;
   float q_scale;           // head_dim^-1/2 * log2(e): the softmax runs in exp2 units
-  int debug_flags;         // tuning probe (vrag_debug_qkv_attn_ms): 1 = no attention phase, 2 = no main-loop MFMAs, 4 = no operand DMA
+  int debug_flags;         // tuning probe (vrag_debug_qkv_attn_ms): 1 = no attention phase, 2 = no main-loop MFMAs, 4 = no operand DMA, 32 = generic tile body only (include/vrag_amd_debug.h)
   unsigned* f16_sat;       // clamp word (GemmParams::f16_sat); required for kOpF16
 };
 

@@ -392,15 +392,52 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
     kt_lo = max(0, qrow0 - W) >> 6;
     kt_hi = min(S - 1, qrow0 + 63 + W) >> 6;
   }
-  const int ksw = (l15 >> 1) & 7;
-  if (active && !VRAG_DBG(1)) {
-    for (int kt = kt_lo; kt <= kt_hi; ++kt) {
-      // 32-row group u against the 32-key half t2 of the tile: `cut` = some element of the 32 x 32 block is outside the band or
-      // beyond the sequence (masked element by element; a block wholly outside is simply all -inf); `dead` = the whole 64-key
-      // tile is outside for the group (no MFMA, p = 0).  Coarse on purpose: one wave-uniform branch per group, straight-line
-      // MFMA runs inside -- a branch per skipped 16 x 16 block (as attention.hip does between barriers) chops the matrix work
-      // into pieces the scheduler cannot interleave with the softmax arithmetic.
-      bool cut[2][2];
+  // Banded layers with |i - j| <= 64 (every banded layer of the model): a wave's band is the tile in front of its own, its own and
+  // the one behind it, and which 16 x 16 blocks (key block kb, column block c) of each hold an in-band element is known at compile
+  // time.  With key = 64 kt + 16 kb + 4 g + r and query = qrow0 + 16 c + l15:
+  //   QA_FIRST (kt = qrow0 / 64 - 1): in band <=> 16 kb + 4 g + r >= 16 c + l15 -- blocks kb > c whole, kb == c by the lane-only
+  //            predicate 4 g + r >= l15, kb < c not at all: 10 of 16;
+  //   QA_MID   (kt = qrow0 / 64, wave and tile inside the sequence): |q - k| <= 63 everywhere, no mask;
+  //   QA_LAST  (kt = qrow0 / 64 + 1, the tile inside the sequence): the mirror image, kb <= c, diagonal 4 g + r <= l15.
+  // A block without an in-band element was all -inf: p = exp2(-inf) = 0 and acc + 0 * v = acc, so leaving out its S-MFMAs, maxima,
+  // exp2 and (where both key blocks of a 32-key step are dead) its PV / row-sum MFMAs changes no bit.  36 of an interior wave's 48
+  // blocks remain.  The bodies are compile-time variants of the lambda below, straight-line inside: never a branch per block, which
+  // chops the matrix work into pieces the scheduler cannot interleave with the softmax arithmetic.
+  // The selection is made ONCE PER WAVE, between straight-line sequences of bodies (FIRST MID LAST for an interior wave, MID LAST
+  // for a sequence's first wave, FIRST MID for its last when that is a full one) and the loop over QA_GENERIC, today's body, for
+  // everything else: another window, a wave that holds the end of its sequence or is followed by the tile that does, a sequence of
+  // one wave.  A selection per TILE -- the four bodies as the arms of one branch inside the tile loop -- does not fit the register
+  // file: every value that lives through the loop (O^T, the row sums, Q: ~125 VGPRs) must then sit in the same registers at the end
+  // of every arm, the allocator no longer finds the 4-aligned tuples of a body that peaks near 250, and 17 .. 110 VGPRs (half of Q
+  // among them) go to scratch, reloaded per tile (profiles/r08_fused_kernel_resources.txt).  The static bodies are positions relative to the sequence, so packed groups
+  // (kbase != 0) take them too.
+  constexpr int QA_GENERIC = 0, QA_FIRST = 1, QA_MID = 2, QA_LAST = 3;
+  bool diag_first[4], diag_last[4];   // lane-only, the same for every tile
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    diag_first[r] = 4 * g + r >= l15;
+    diag_last[r] = 4 * g + r <= l15;
+  }
+  auto tile = [&](auto mode_c, const int kt) {
+    constexpr int MODE = decltype(mode_c)::value;
+    // Banded: the lane's coordinates are re-derived per tile from an opaque copy of the lane id.  Otherwise every lane-only value
+    // of one body (LDS addresses, the generic body's band limits) is hoisted in front of all of them and stays live through the
+    // others: registers this phase does not have (bf16 with the fold: one VGPR in scratch).  A dozen VALU operations per tile.
+    const int ln = [&] {
+      int v = lane;
+      if constexpr (LOCAL) asm volatile("" : "+v"(v));
+      return v;
+    }();
+    const int g = ln >> 4, l15 = ln & 15, ksw = (l15 >> 1) & 7;
+    // does key block kb hold an in-band element for column block c / does the 32-key step t2
+    auto blk = [](int c, int kb) { return MODE == QA_FIRST ? kb >= c : MODE == QA_LAST ? kb <= c : true; };
+    auto step = [&](int c, int t2) { return blk(c, 2 * t2) || blk(c, 2 * t2 + 1); };
+    // QA_GENERIC, 32-row group u against the 32-key half t2 of the tile: `cut` = some element of the 32 x 32 block is outside the
+    // band or beyond the sequence (masked element by element; a block wholly outside is simply all -inf); `dead` = the whole 64-key
+    // tile is outside for the group (no MFMA, p = 0).  Coarse on purpose: one wave-uniform branch per group, straight-line
+    // MFMA runs inside.
+    bool cut[2][2];
+    if constexpr (MODE == QA_GENERIC) {
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int q_lo = qrow0 + 32 * u;
@@ -416,34 +453,38 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
           cut[u][t2] = cut[u][t2] || outside;
         }
       }
-      V8 pf[4][2];
-      {
-        f32x4 st[4][4];   // S^T - reference: lane (l15 = query of column block c, g) holds keys 16 kb + 4 g + r
+    }
+    V8 pf[4][2];
+    {
+      f32x4 st[4][4];   // S^T - reference: lane (l15 = query of column block c, g) holds keys 16 kb + 4 g + r
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float seed = -m_run[c];
+      for (int c = 0; c < 4; ++c) {
+        const float seed = -m_run[c];
 #pragma unroll
-          for (int kb = 0; kb < 4; ++kb) st[c][kb] = f32x4{seed, seed, seed, seed};
-        }
+        for (int kb = 0; kb < 4; ++kb)
+          if (blk(c, kb)) st[c][kb] = f32x4{seed, seed, seed, seed};
+      }
 #pragma unroll
-        for (int kb = 0; kb < 4; ++kb) {
-          const char* krow = smem + ((kbase + kt) * 64 + kb * 16 + l15) * 128;   // key tile kt of THIS sequence = LDS slot kbase + kt
-          const V8 k0 = *reinterpret_cast<const V8*>(krow + ((g ^ ksw) << 4));
-          const V8 k1 = *reinterpret_cast<const V8*>(krow + (((4 + g) ^ ksw) << 4));
+      for (int kb = 0; kb < 4; ++kb) {
+        const char* krow = smem + ((kbase + kt) * 64 + kb * 16 + l15) * 128;   // key tile kt of THIS sequence = LDS slot kbase + kt
+        const V8 k0 = *reinterpret_cast<const V8*>(krow + ((g ^ ksw) << 4));
+        const V8 k1 = *reinterpret_cast<const V8*>(krow + (((4 + g) ^ ksw) << 4));
 #pragma unroll
-          for (int c = 0; c < 4; ++c) {
+        for (int c = 0; c < 4; ++c)
+          if (blk(c, kb)) {
             st[c][kb] = Op<T>::mfma16(k0, qf[c][0], st[c][kb]);
             st[c][kb] = Op<T>::mfma16(k1, qf[c][1], st[c][kb]);
           }
-        }
-        // masks and in-lane maxima (scores are relative to m_run already)
-        float mx[4];
+      }
+      // masks and in-lane maxima (scores are relative to m_run already)
+      float mx[4];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const int u = c >> 1;
-          mx[c] = -INFINITY;
+      for (int c = 0; c < 4; ++c) {
+        const int u = c >> 1;
+        mx[c] = -INFINITY;
 #pragma unroll
-          for (int t2 = 0; t2 < 2; ++t2) {
+        for (int t2 = 0; t2 < 2; ++t2) {
+          if constexpr (MODE == QA_GENERIC) {
             if (cut[u][t2]) {
               const int qi = qrow0 + 16 * c + l15;
               int lo_k = 0, hi_k = S - 1;
@@ -462,68 +503,107 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(const QkvAttnParams p)
                   st[c][2 * t2 + h2][r] = ok ? st[c][2 * t2 + h2][r] : -INFINITY;
                 }
             }
-            const f32x4& a = st[c][2 * t2];
-            const f32x4& b2 = st[c][2 * t2 + 1];
+          } else if constexpr (MODE != QA_MID) {
+            if (c >> 1 == t2) {   // the diagonal block kb == c lies in this step
+#pragma unroll
+              for (int r = 0; r < 4; ++r) st[c][c][r] = (MODE == QA_FIRST ? diag_first[r] : diag_last[r]) ? st[c][c][r] : -INFINITY;
+            }
+          }
+          const f32x4& a = st[c][2 * t2];
+          const f32x4& b2 = st[c][2 * t2 + 1];
+          if (blk(c, 2 * t2) && blk(c, 2 * t2 + 1)) {
             mx[c] = max3f(mx[c], max3f(a[0], a[1], a[2]), max3f(a[3], b2[0], b2[1]));
             mx[c] = max3f(mx[c], b2[2], b2[3]);
+          } else if (blk(c, 2 * t2)) {
+            mx[c] = max3f(mx[c], max3f(a[0], a[1], a[2]), a[3]);
+          } else if (blk(c, 2 * t2 + 1)) {
+            mx[c] = max3f(mx[c], max3f(b2[0], b2[1], b2[2]), b2[3]);
           }
         }
-        // move the reference?  (wave-uniform; steady state: no)
-        bool move = false;
+      }
+      // move the reference?  (wave-uniform; steady state: no)
+      bool move = false;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        // query rows behind the end of the sequence hold whatever follows it in the packed buffer (bf16 keeps their q): they
+        // must not time the moves of the live rows, or a sequence's bits depend on its neighbour in the buffer.  Such a row's
+        // own reference then moves only when a live row moves, so its ot / lo may run to inf or NaN (exp2 of a huge score,
+        // 0 * inf against the zeroed V): harmless -- a query is one MFMA column, and these rows are never stored
+        const bool qlive = qrow0 + 16 * c + l15 < S;
+        move = move || (qlive && (mx[c] > QA_LAZY || (!seen[c] && mx[c] > -INFINITY)));
+      }
+      if (__any(move)) {
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-          // query rows behind the end of the sequence hold whatever follows it in the packed buffer (bf16 keeps their q): they
-          // must not time the moves of the live rows, or a sequence's bits depend on its neighbour in the buffer.  Such a row's
-          // own reference then moves only when a live row moves, so its ot / lo may run to inf or NaN (exp2 of a huge score,
-          // 0 * inf against the zeroed V): harmless -- a query is one MFMA column, and these rows are never stored
-          const bool qlive = qrow0 + 16 * c + l15 < S;
-          move = move || (qlive && (mx[c] > QA_LAZY || (!seen[c] && mx[c] > -INFINITY)));
-        }
-        if (__any(move)) {
+          float m_all = fmaxf(mx[c], __shfl_xor(mx[c], 16, 64));   // over the four lane groups of the query
+          m_all = fmaxf(m_all, __shfl_xor(m_all, 32, 64));
+          const bool has = m_all > -INFINITY;
+          const float delta = seen[c] ? fmaxf(m_all, 0.f) : (has ? m_all : 0.f);
+          // a row's first reference may sit far below zero: nothing has been accumulated yet, so nothing is rescaled
+          // (2^-delta would overflow); afterwards delta >= 0 and alpha <= 1
+          const float alpha = seen[c] ? __builtin_amdgcn_exp2f(-delta) : 1.0f;
+          seen[c] = seen[c] || has;
+          m_run[c] += delta;
 #pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            float m_all = fmaxf(mx[c], __shfl_xor(mx[c], 16, 64));   // over the four lane groups of the query
-            m_all = fmaxf(m_all, __shfl_xor(m_all, 32, 64));
-            const bool has = m_all > -INFINITY;
-            const float delta = seen[c] ? fmaxf(m_all, 0.f) : (has ? m_all : 0.f);
-            // a row's first reference may sit far below zero: nothing has been accumulated yet, so nothing is rescaled
-            // (2^-delta would overflow); afterwards delta >= 0 and alpha <= 1
-            const float alpha = seen[c] ? __builtin_amdgcn_exp2f(-delta) : 1.0f;
-            seen[c] = seen[c] || has;
-            m_run[c] += delta;
-#pragma unroll
-            for (int kb = 0; kb < 4; ++kb)
+          for (int kb = 0; kb < 4; ++kb)
+            if (blk(c, kb)) {
 #pragma unroll
               for (int r = 0; r < 4; ++r) st[c][kb][r] -= delta;
+            }
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt)
+          for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
-              for (int r = 0; r < 4; ++r) ot[c][dt][r] *= alpha;
+            for (int r = 0; r < 4; ++r) ot[c][dt][r] *= alpha;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) lo[c][r] *= alpha;
-          }
+          for (int r = 0; r < 4; ++r) lo[c][r] *= alpha;
         }
-        // p = exp2(s - m) straight into the B-operand fragments of O^T += V^T . P^T: k-slot (g, j) of the 32-key step t2 is the
-        // accumulator row j & 3 of key block 2 t2 + (j >> 2)
+      }
+      // p = exp2(s - m) straight into the B-operand fragments of O^T += V^T . P^T: k-slot (g, j) of the 32-key step t2 is the
+      // accumulator row j & 3 of key block 2 t2 + (j >> 2); a key block without an in-band element beside a live one is literal zeros
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2)
+          if (step(c, t2)) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+              pf[c][t2][j] = blk(c, 2 * t2 + (j >> 2)) ? (T)__builtin_amdgcn_exp2f(st[c][2 * t2 + (j >> 2)][j & 3]) : (T)0.f;
+          }
+    }
+    // ---- O^T += V^T . P^T, l += 1 . P^T (V^T fragments read once for the four column blocks)
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (step(c, t2)) lo[c] = Op<T>::mfma16(ones, pf[c][t2], lo[c]);
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        const V8 vf = *reinterpret_cast<const V8*>(smem + QA_V_OFF + (dt * 16 + l15) * 1024 + ((((kbase + kt) * 8 + t2 * 4 + g) ^ l15) << 4));
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int t2 = 0; t2 < 2; ++t2)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pf[c][t2][j] = (T)__builtin_amdgcn_exp2f(st[c][2 * t2 + (j >> 2)][j & 3]);
+          if (step(c, t2)) ot[c][dt] = Op<T>::mfma16(vf, pf[c][t2], ot[c][dt]);
       }
-      // ---- O^T += V^T . P^T, l += 1 . P^T (V^T fragments read once for the four column blocks)
-#pragma unroll
-      for (int t2 = 0; t2 < 2; ++t2) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) lo[c] = Op<T>::mfma16(ones, pf[c][t2], lo[c]);
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-          const V8 vf = *reinterpret_cast<const V8*>(smem + QA_V_OFF + (dt * 16 + l15) * 1024 + ((((kbase + kt) * 8 + t2 * 4 + g) ^ l15) << 4));
-#pragma unroll
-          for (int c = 0; c < 4; ++c) ot[c][dt] = Op<T>::mfma16(vf, pf[c][t2], ot[c][dt]);
-        }
+    }
+  };
+  if (active && !VRAG_DBG(1)) {
+    if constexpr (LOCAL) {
+      const bool fixed = W == 64 && !VRAG_DBG(32);
+      const int own = qrow0 >> 6;
+      if (fixed && qrow0 >= 64 && qrow0 + 127 < S) {
+        tile(std::integral_constant<int, QA_FIRST>{}, own - 1);
+        tile(std::integral_constant<int, QA_MID>{}, own);
+        tile(std::integral_constant<int, QA_LAST>{}, own + 1);
+      } else if (fixed && qrow0 == 0 && 127 < S) {
+        tile(std::integral_constant<int, QA_MID>{}, own);
+        tile(std::integral_constant<int, QA_LAST>{}, own + 1);
+      } else if (fixed && qrow0 >= 64 && qrow0 + 64 == S) {
+        tile(std::integral_constant<int, QA_FIRST>{}, own - 1);
+        tile(std::integral_constant<int, QA_MID>{}, own);
+      } else {
+        for (int kt = kt_lo; kt <= kt_hi; ++kt) tile(std::integral_constant<int, QA_GENERIC>{}, kt);
       }
+    } else {
+      for (int kt = kt_lo; kt <= kt_hi; ++kt) tile(std::integral_constant<int, QA_GENERIC>{}, kt);
     }
   }
   __syncthreads();   // every wave is done with K / V^T: the K area becomes the output staging (8 KiB per wave)
