@@ -306,7 +306,11 @@ int vrag_encoder_read_profile(vrag_encoder* enc, float* ms /*[VRAG_PROF_COUNT]*/
 /* ------------------------------------------------------------------------------------------
  * Exact dot-product top-k (what the reference delegates to Milvus:
  * verbatim_rag/vector_stores/milvus_base.py:239-259, metric types milvus_local.py:109-129).
- * Order: (score desc, id asc), ties included.  Missing hits: id = -1, score = -inf.  1 <= k <= 1024 for the search
+ * Order: (score desc, id asc), ties included.  Zeros of either sign tie; the sign of a returned zero is unspecified (a tree-shaped
+ * sum gives +0 where the sequential chain gives -0; every list builder, vrag_topk_merge and the SQ8, sparse, full-text and IVF
+ * lists rank with the same keys and follow the same rule).  fp32 denormals are kept on every route, matrix-core kernels
+ * included: a denormal score is returned bit for bit and ranks by its value (tests/test_topk_special_values_gpu.py).
+ * Missing hits: id = -1, score = -inf.  1 <= k <= 1024 for the search
  * calls (Milvus' `limit`, milvus_base.py:244-277: the reference asks for top_k or 2*top_k): lists of up to 64 come from
  * one device pass, longer ones as exact pages of 64 (page p+1 admits only keys below the last key of page p) on the
  * scalar kernels with fp32 queries; `*_run_resident` re-runs a single pass (k <= 64).
@@ -315,7 +319,9 @@ int vrag_encoder_read_profile(vrag_encoder* enc, float* ms /*[VRAG_PROF_COUNT]*/
  * dtype 2 = fp32 rows (every result bit-identical to dtype 1: scores are the sequential fp32 fmaf chain over the fp32 rows)
  * plus a bf16 prefilter image of them (+50 % memory): vrag_dense_index_search, for k <= 16, ranks the image first, proves
  * from the image's MEASURED error bound that its candidates contain the exact top-k (else the full fp32 scan answers that
- * query) and re-scores them exactly -- half the bytes for a small batch, one read of the shard per batch instead of one per 32
+ * query; the bound holds for every finite fp32 row -- the norms behind it are measured on the row scaled by a power of two, so
+ * rows of magnitude 2^-75 or 2^+66 keep the route, and a row whose norm is beyond fp32 sends every query to the full scan)
+ * and re-scores them exactly -- half the bytes for a small batch, one read of the shard per batch instead of one per 32
  * queries.  Round 6 routes every batch through it: one to four queries share ONE pass over the image that collects every row
  * within twice the bound of an entry threshold (more than 4096 of them = the full scan); 5 .. 256 queries take the same idea
  * on the tiled score GEMM (thresholds from 65 536 rows -- a sample of the shard's tiles --, one appending pass, exact re-score of the lists); larger
@@ -416,8 +422,9 @@ int vrag_ivf_index_search(vrag_ivf_index* ivf, const float* queries /*[nq,dim] h
  *   score = (float)idot * (s_q * s_r)              three fp32 roundings: the conversion (nearest even), the scale product,
  *                                                  the final product; no fused multiply-add, no reciprocal, no fast-math
  * so every score is defined bit for bit and every route returns the same bits.  Order (score desc, id asc), ties included;
- * missing hits -1 / -inf.  Rows and queries are expected to be finite; a scale product that underflows to zero may give -0
- * scores and is outside the contract.
+ * missing hits -1 / -inf.  Rows and queries are expected to be finite.  A scale product that underflows to zero gives scores of
+ * +0 and -0: they tie like every zero (the sign of a returned zero is unspecified).  A row whose maximum m > 0 is so small that
+ * m / 127 underflows to 0 in fp32 has scale 0 and codes +-127 (a zero element of such a row divides 0 / 0: its code is outside the contract).
  *   create         1 <= dim <= 4096, 0 < capacity < 2^32 - 1.
  *   add            host fp32 rows [n, dim], staged in slabs through the device form; all of them or (VRAG_ERR_CAPACITY) none.
  *   add_device     device fp32 rows [n, dim]; quantised on the device on `stream`, which is synchronised before the call returns.

@@ -170,10 +170,15 @@ __device__ __forceinline__ f32x4 load16_nt(const void* src) {
 
 // Top-k candidate keys (csrc/topk.hip; also built by the EPI_TOPK epilogue of csrc/gemm_bf16.hip): one u64
 //   [ orderable(score) : 32 | 0xFFFFFFFF - local_row : 32 ]      (max key == best hit under (score desc, id asc))
+// orderable: bits above 0x80000000 (a score below zero) -> ~bits, descending in the magnitude; every other -> bits | 2^31.
+// The test is `bits > 0x80000000`, not the sign bit: -0.0 (bits 0x80000000 exactly) takes +0.0's key 2^31, so zeros of either sign
+// are ONE value of the order (the contract of include/vrag_amd.h: they tie, the id decides) and every non-zero score keeps the key
+// it always had.  Same three VALU operations as the sign-bit test (v_not, one integer compare, v_cndmask with -|bits|).  The key
+// 2^31 - 1 (what the sign-bit test made of -0.0) is never built; unorderable returns +0.0 for either zero.
 typedef unsigned long long u64;
 __device__ __forceinline__ unsigned orderable(float s) {
   const unsigned b = __builtin_bit_cast(unsigned, s);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return b > 0x80000000u ? ~b : (b | 0x80000000u);
 }
 __host__ __device__ inline float unorderable(unsigned k) {
   const unsigned b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;

@@ -1379,14 +1379,32 @@ hipError_t launch_tiled_tau(int nq, u64* thr_key, float* thr_score, const float*
 // the full fp32 scan re-answers it: correctness never rests on the data.
 constexpr int PFK = 64;   // candidates per query of a batch (the tiled search delivers 64 at no extra cost)
 
-// fp32 rows -> bf16 image + the maximum squared row norm (one wave per row)
+// The next fp32 above a finite v >= 0 (+inf stays)
+__device__ __forceinline__ float next_up(float v) {
+  return v < INFINITY ? __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v) + 1u) : v;
+}
+
+// fp32 rows -> bf16 image + the maximum row norm and the maximum norm of the image's error (one wave per row).  Both are upper
+// bounds for EVERY finite row: the squares are summed on the row scaled by a power of two that brings its largest element into
+// [0.5, 1) -- squares of the elements themselves underflow to 0 below 2^-75 and overflow above 2^64, and a bound measured from
+// them would be too small or not a number -- and it is the norms that are kept, not their squares: the norm of a finite row is
+// an fp32 number or overflows to +inf, which prefilter_eps turns into the full scan.
 __global__ __launch_bounds__(256) void prefilter_image_kernel(const float* __restrict__ src, bf16_t* __restrict__ dst, long long n_rows,
-                                                               int dim, float* __restrict__ stats /*[0] max ||x||^2, [1] max ||x~ - x||^2*/) {
+                                                               int dim, float* __restrict__ stats /*[0] max ||x||, [1] max ||x~ - x||*/) {
   const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (r >= n_rows) return;
   const float* x = src + (size_t)r * dim;
   bf16_t* y = dst + (size_t)r * dim;
+  float m = 0.f;
+  for (int c = lane * 4; c < dim; c += 256) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(x + c);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) m = fmaxf(m, fabsf(v[j]));
+  }
+  m = wave_max(m);
+  int ex = 0;
+  frexpf(m, &ex);   // m = f 2^ex, f in [0.5, 1); denormal maxima too
   float s2 = 0.f, d2 = 0.f;
   for (int c = lane * 4; c < dim; c += 256) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(x + c);
@@ -1394,16 +1412,21 @@ __global__ __launch_bounds__(256) void prefilter_image_kernel(const float* __res
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       o[j] = (bf16_t)v[j];
-      s2 = fmaf(v[j], v[j], s2);
-      const float d = v[j] - (float)o[j];   // exact in fp32: the two are within a factor two of each other
+      const float vs = ldexpf(v[j], -ex);   // exact, or below 2^-126 of the largest element
+      s2 = fmaf(vs, vs, s2);
+      const float d = ldexpf(v[j] - (float)o[j], -ex);   // the difference is exact in fp32: the two are within a factor two of each other
       d2 = fmaf(d, d, d2);
     }
     *reinterpret_cast<bf16x4*>(y + c) = o;
   }
-  s2 = wave_sum(s2) * 1.0001f;   // the sums' own rounding
-  d2 = wave_sum(d2) * 1.0001f;
-  if (lane == 0 && s2 == s2) atomicMax(reinterpret_cast<unsigned*>(stats), __builtin_bit_cast(unsigned, s2));
-  if (lane == 0 && d2 == d2) atomicMax(reinterpret_cast<unsigned*>(stats) + 1, __builtin_bit_cast(unsigned, d2));
+  if (!(m > 0.f) || !(m < INFINITY)) return;   // a zero row moves neither maximum (non-finite rows are outside the contract)
+  // 1.0001: the sums' own rounding and the root's.  dim 2^-120: what scaled elements below 2^-63 lose when their squares underflow
+  // (at most 2^-126 each) -- invisible next to s2 >= 1/4, but d2 may consist of nothing else.
+  const float nx = ldexpf(sqrtf(wave_sum(s2) * 1.0001f) * 1.0001f, ex);
+  const float nd = ldexpf(sqrtf(wave_sum(d2) * 1.0001f + (float)dim * 0x1p-120f) * 1.0001f, ex);
+  // ldexpf rounds to nearest where the result is denormal: one step up keeps the bound
+  if (lane == 0 && nx == nx) atomicMax(reinterpret_cast<unsigned*>(stats), __builtin_bit_cast(unsigned, next_up(nx)));
+  if (lane == 0 && nd == nd) atomicMax(reinterpret_cast<unsigned*>(stats) + 1, __builtin_bit_cast(unsigned, next_up(nd)));
 }
 
 // The oracle's chain  acc = fmaf(x[c], q[c], acc), c ascending from acc = 0,  for one row per lane.  The chain itself is serial;
@@ -2495,7 +2518,7 @@ struct vrag_dense_index {
   DevArray<u64> d_pfb;             // [nq][PFCAP] candidate keys of the batch collect route (round 6: prefilter_batch_enqueue, <= 64 queries)
   // fp32 rows with a bf16 prefilter copy (dtype 2 at creation; `dtype` stays 1: the contract is the fp32 rows')
   DevArray<bf16_t> rows16;         // bf16 image of `rows`
-  DevArray<float> d_norm2;         // device [2]: max squared row norm, max squared image error ||x~ - x||^2 (bits ordered as unsigned: both >= 0)
+  DevArray<float> d_norm2;         // device [2]: max row norm ||x||, max image error ||x~ - x||, upper bounds (bits ordered as unsigned: both >= 0)
   float pf_stats[2] = {0.f, 0.f};  // their host copies, refreshed by add()
   DevArray<float> d_pf_eps;        // [nq] per-query error bound of the approximate scores
   DevArray<u64> d_pf_out;          // [nq][k] exact keys of the rescored candidates
@@ -3054,9 +3077,12 @@ static float prefilter_eps(const vrag_dense_index* ix, const float* q, bool roun
       dq2 += d * d;
     }
   }
-  const double xmax = std::sqrt((double)ix->pf_stats[0]), emax = std::sqrt((double)ix->pf_stats[1]);
+  const double xmax = (double)ix->pf_stats[0], emax = (double)ix->pf_stats[1];
   const double e = emax * std::sqrt(q2) + std::sqrt(dq2) * (xmax + emax) + 4.0 * ix->dim / 16777216.0 * xmax * std::sqrt(q2);
-  return (float)(e * 1.001 + 1e-30);
+  // A row norm beyond fp32 (+inf) has no bound: +inf flags every query for the full scan.  Not NaN (0 * inf, a query that loses
+  // nothing on its way into the pass): no image score compares against a NaN threshold, and an empty list raises no flag.
+  const double eps = e * 1.001 + 1e-30;
+  return eps < 3.0e38 ? (float)eps : INFINITY;   // written so that NaN takes the second branch
 }
 
 static int prefilter_rescan_enqueue(vrag_dense_index* ix, int nq, int k, hipStream_t st, const unsigned* flags);

@@ -27,8 +27,9 @@ def shard_range(n_units: int, rank: int, world: int) -> Tuple[int, int]:
 
 def merge_topk(scores: np.ndarray, ids: np.ndarray, k: int) -> Tuple[np.ndarray, np.ndarray]:
     """Host statement of the merge (tests and CPU-only tooling; the product merges on the GPU):
-    scores/ids `[W, Q, k_in]` per-shard lists (id -1 = empty) -> `[Q, k]` by (score desc, id asc).  One lexsort for the
-    whole batch, no per-query Python loop."""
+    scores/ids `[W, Q, k_in]` per-shard lists (id -1 = empty) -> `[Q, k]` by (score desc, id asc).  Zeros of either sign tie, as
+    in the device merge (include/vrag_amd.h): the sort compares values, and -0.0 == 0.0.  One lexsort for the whole batch, no
+    per-query Python loop."""
     W, Q, kk = scores.shape
     s = np.ascontiguousarray(scores.transpose(1, 0, 2)).reshape(Q, W * kk).astype(np.float32)
     i = np.ascontiguousarray(ids.transpose(1, 0, 2)).reshape(Q, W * kk).astype(np.int64)
