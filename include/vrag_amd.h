@@ -715,7 +715,32 @@ int vrag_rrf_fuse(const int64_t* rows /*[nq, l_total]*/, const double* gains /*[
  *            n_rows == 0: VRAG_OK without a launch.  Synchronous.
  * Everything is validated on the host before anything is launched or allocated (leaf columns, table ranges against n_table_words,
  * n_rows against the columns, the op list, the limits): VRAG_ERR_INVALID with a message, out_words untouched.  The handle has its
- * own device arrays, stream and lock. */
+ * own device arrays, stream and lock.
+ *
+ * String leaves answered on the device (csrc/strmatch.hip).  A column may also hold the DICTIONARY of its strings: code c (the
+ * payload of a string row) is the UTF-8 bytes bytes[off[c] .. off[c + 1]), appended to only, codes continuing from those held.
+ * The match kernel -- one lane per dictionary string -- applies one operator and one operand text to codes [0, n_codes) and
+ * writes the table a _TABLE leaf reads (bit code % 32 of word code / 32, tail bits of the last word zero):
+ *   VRAG_FILTER_MATCH_EQ .. _GE   bytewise lexicographic comparison of the stored string with `text`, a proper prefix being
+ *                                 smaller -- for valid UTF-8 the order of the code points
+ *   VRAG_FILTER_MATCH_LIKE        `text` is a pattern as written, escapes included: `%` any run of zero or more characters, `_`
+ *                                 exactly one character (one code point), a backslash makes the next character literal; over the
+ *                                 whole string, case-sensitive, a newline a character like any other
+ * Limits: `text` at most VRAG_FILTER_MATCH_MAX_PATTERN bytes; a pattern at most VRAG_FILTER_MATCH_MAX_SEGMENTS non-empty runs
+ * between its unescaped `%`; a dictionary string shorter than 2 GiB.
+ *   append_strings  host arrays, n strings: off[0] = 0, off ascending, bytes[off[i] .. off[i + 1]) valid UTF-8 each.
+ *   strings         codes and bytes the column's dictionary holds.
+ *   match           one table to the host (out_words: ceil(n_codes / 32) words, nothing behind them written); n_codes at most
+ *                   the dictionary's codes (a prefix is fine); n_codes == 0: VRAG_OK without a launch.  Synchronous.
+ *   eval_matched    eval, with some _TABLE leaves answered by the kernel: `tables` is uploaded as eval does, then for each entry
+ *                   of `matches`, in order, leaf `leaf`'s table (its table_off, its table_codes codes, over its column's
+ *                   dictionary) is written in device memory by one match launch with operator `op` and the text
+ *                   texts[text_off .. text_off + text_len), then the program runs.  What `tables` holds in those ranges is not
+ *                   read; a table made here never travels to the host.
+ * VRAG_ERR_INVALID with a message, before anything is allocated or launched and with the outputs untouched, for: a column with
+ * fewer dictionary codes than asked for, a text over a limit, a pattern ending in a lone backslash, invalid UTF-8 in a pattern or
+ * in appended strings, offsets not ascending from 0, an unknown operator, a match whose leaf is no _TABLE leaf or whose text
+ * lies outside `texts` (a leaf's table range is checked against n_table_words as in eval). */
 #define VRAG_FILTER_MAX_COLUMNS 16
 #define VRAG_FILTER_MAX_LEAVES 64
 #define VRAG_FILTER_MAX_OPS 256
@@ -759,6 +784,32 @@ int vrag_row_filter_rows(vrag_row_filter* f, int32_t col, int64_t* n);
 int vrag_row_filter_eval(vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops, int32_t n_ops,
                          const uint32_t* tables /*[n_table_words] host, NULL when 0*/, int64_t n_table_words, int64_t n_rows,
                          uint32_t* out_words /*host*/, void* stream);
+#define VRAG_FILTER_MATCH_EQ 0
+#define VRAG_FILTER_MATCH_NE 1
+#define VRAG_FILTER_MATCH_LT 2
+#define VRAG_FILTER_MATCH_LE 3
+#define VRAG_FILTER_MATCH_GT 4
+#define VRAG_FILTER_MATCH_GE 5
+#define VRAG_FILTER_MATCH_LIKE 6
+#define VRAG_FILTER_MATCH_MAX_PATTERN 256 /* bytes of operand text */
+#define VRAG_FILTER_MATCH_MAX_SEGMENTS 16 /* LIKE: non-empty runs between the unescaped % */
+typedef struct vrag_filter_match {
+  int64_t text_off;
+  int32_t text_len;
+  int32_t leaf;
+  int32_t op;
+  int32_t pad;
+} vrag_filter_match;
+int vrag_row_filter_append_strings(vrag_row_filter* f, int32_t col, const uint8_t* bytes /*[off[n]] host*/,
+                                   const int64_t* off /*[n + 1] host, off[0] = 0*/, int64_t n);
+int vrag_row_filter_strings(vrag_row_filter* f, int32_t col, int64_t* n_codes, int64_t* n_bytes);
+int vrag_row_filter_match(vrag_row_filter* f, int32_t col, int32_t op, const uint8_t* text, int32_t text_len, int64_t n_codes,
+                          uint32_t* out_words /*host, ceil(n_codes / 32)*/, void* stream);
+int vrag_row_filter_eval_matched(vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops,
+                                 int32_t n_ops, const uint32_t* tables /*[n_table_words] host, NULL when 0*/, int64_t n_table_words,
+                                 const vrag_filter_match* matches /*[n_matches]*/, int32_t n_matches,
+                                 const uint8_t* texts /*[n_text_bytes] host*/, int64_t n_text_bytes, int64_t n_rows,
+                                 uint32_t* out_words /*host*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The exchange step of sharded retrieval: one process per GPU, the corpus row-sharded, every rank answers the

@@ -81,6 +81,15 @@ FILTER_KINDS = {"other": 0, "number": 1, "string": 2, "bool": 3}                
 FILTER_NUM_OPS = {"never": 0, "always": 1, "==": 2, "!=": 3, "<": 4, "<=": 5, ">": 6, ">=": 7}  # VRAG_FILTER_NUM_*
 FILTER_STR_MODES = {"never": 0, "always": 1, "table": 2}                                        # VRAG_FILTER_STR_*
 FILTER_OPS = {"leaf": 0, "and": 1, "or": 2, "not": 3}                                           # VRAG_FILTER_OP_* (leaf index << 8)
+FILTER_MATCH_OPS = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5, "like": 6}                  # VRAG_FILTER_MATCH_*
+FILTER_MATCH_MAX_PATTERN, FILTER_MATCH_MAX_SEGMENTS = 256, 16                                   # VRAG_FILTER_MATCH_MAX_*
+
+
+class FilterMatch(C.Structure):
+    """vrag_filter_match (include/vrag_amd.h), field for field; tests/test_like_filter_host.py checks the layout against the host
+    compiler's."""
+    _fields_ = [("text_off", C.c_int64), ("text_len", C.c_int32), ("leaf", C.c_int32), ("op", C.c_int32), ("pad", C.c_int32)]
+
 
 # name -> (restype, argtypes); every symbol include/vrag_amd.h declares.
 _H = C.c_void_p
@@ -161,6 +170,12 @@ SIGNATURES = {
     "vrag_row_filter_rows": (C.c_int, [_H, C.c_int32, _LP]),
     "vrag_row_filter_eval": (C.c_int, [_H, C.POINTER(FilterLeaf), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
                                        C.c_void_p, C.c_void_p]),
+    "vrag_row_filter_append_strings": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
+    "vrag_row_filter_strings": (C.c_int, [_H, C.c_int32, _LP, _LP]),
+    "vrag_row_filter_match": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "vrag_row_filter_eval_matched": (C.c_int, [_H, C.POINTER(FilterLeaf), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                               C.POINTER(FilterMatch), C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                               C.c_void_p]),
     "vrag_sparse_index_search_device": (C.c_int, [_H, _LP, _IP, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "vrag_pack_qa_pairs": (C.c_int, [_IP, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, _IP, C.c_int32, C.c_int32, _IP, C.c_int64,

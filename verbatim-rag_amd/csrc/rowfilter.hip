@@ -14,7 +14,9 @@
 //             column).  Two leaves on one column read the same lines again: those hit the vector cache, HBM sees 9 bytes per row
 //             and referenced column
 //   strings   a table leaf reads tables[off + code / 32] only for code < table_codes -- a code at or beyond the leaf's table (a
-//             string the table was not resolved for) does not match, and nothing behind a table is read
+//             string the table was not resolved for) does not match, and nothing behind a table is read.  A table comes from the
+//             host with the program or is written in place by the match kernel of csrc/strmatch.hip (vrag_row_filter_eval_matched);
+//             this kernel does not know which
 //   result    the wave's 64 answers are one ballot; lanes 0 and 1 store its two 32-bit words.  Lanes at and beyond n_rows read
 //             nothing and are masked out of the ballot, so the tail bits of the last group are zero.  The device buffer holds two words per group; the host copies
 //             ceil(n_rows / 32) of them
@@ -23,11 +25,9 @@
 
 #include <algorithm>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
-#include "common.h"
-#include "host_util.h"
+#include "rowfilter.h"
 
 namespace vrag {
 namespace {
@@ -110,24 +110,10 @@ __global__ __launch_bounds__(64 * RF_WAVES) void row_filter_eval_kernel(const Ev
   }
 }
 
-struct FilterColumn {
-  DevArray<unsigned char> kinds;
-  DevArray<u64> payload;
-  long long n = 0;   // rows held; the arrays' capacity is kinds.n
-};
-
 }  // namespace
 }  // namespace vrag
 
 using namespace vrag;
-
-struct vrag_row_filter {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::mutex mu;
-  std::vector<FilterColumn> cols;
-  DevArray<unsigned> d_tables, d_out;   // scratch of one eval (grown on demand)
-};
 
 extern "C" {
 
@@ -211,16 +197,21 @@ int vrag_row_filter_rows(vrag_row_filter* f, int32_t col, int64_t* n) {
   return VRAG_OK;
 }
 
-int vrag_row_filter_eval(vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops, int32_t n_ops,
-                         const uint32_t* tables, int64_t n_table_words, int64_t n_rows, uint32_t* out_words, void* stream) {
+}  // extern "C"
+
+// vrag_row_filter_eval and _eval_matched (`who` names the one called): the latter's matches fill their leaves' tables in device
+// memory between the upload of `tables` and the eval kernel.
+static int eval_program(const char* who, vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops,
+                        int32_t n_ops, const uint32_t* tables, int64_t n_table_words, const vrag_filter_match* matches, int32_t n_matches,
+                        const uint8_t* texts, int64_t n_text_bytes, int64_t n_rows, uint32_t* out_words, void* stream) {
   ARG_CHECK(f && leaves && ops, "null argument");
-  ARG_CHECK(n_leaves >= 1 && n_leaves <= VRAG_FILTER_MAX_LEAVES, "vrag_row_filter_eval: 1 <= n_leaves <= %d (got %d)",
+  ARG_CHECK(n_leaves >= 1 && n_leaves <= VRAG_FILTER_MAX_LEAVES, "%s: 1 <= n_leaves <= %d (got %d)", who,
             VRAG_FILTER_MAX_LEAVES, n_leaves);
-  ARG_CHECK(n_ops >= 1 && n_ops <= VRAG_FILTER_MAX_OPS, "vrag_row_filter_eval: 1 <= n_ops <= %d (got %d)", VRAG_FILTER_MAX_OPS, n_ops);
+  ARG_CHECK(n_ops >= 1 && n_ops <= VRAG_FILTER_MAX_OPS, "%s: 1 <= n_ops <= %d (got %d)", who, VRAG_FILTER_MAX_OPS, n_ops);
   ARG_CHECK(n_table_words >= 0 && n_table_words <= 0x7fffffffll && (n_table_words == 0 || tables),
-            "vrag_row_filter_eval: bad table array (%lld words)", (long long)n_table_words);
-  ARG_CHECK(n_rows >= 0, "vrag_row_filter_eval: negative n_rows");
-  ARG_CHECK(n_rows == 0 || out_words, "vrag_row_filter_eval: null out_words");
+            "%s: bad table array (%lld words)", who, (long long)n_table_words);
+  ARG_CHECK(n_rows >= 0, "%s: negative n_rows", who);
+  ARG_CHECK(n_rows == 0 || out_words, "%s: null out_words", who);
   EvalArgs args;
   std::memset(&args, 0, sizeof(args));
   // the op list: no underflow, depth <= 32, one value left
@@ -229,22 +220,22 @@ int vrag_row_filter_eval(vrag_row_filter* f, const vrag_filter_leaf* leaves, int
     const uint32_t code = ops[i] & 0xffu, leaf = ops[i] >> 8;
     unsigned char byte = 0;
     if (code == VRAG_FILTER_OP_LEAF) {
-      ARG_CHECK(leaf < (uint32_t)n_leaves, "vrag_row_filter_eval: ops[%d] pushes leaf %u of %d", i, leaf, n_leaves);
-      ARG_CHECK(depth < VRAG_FILTER_MAX_DEPTH, "vrag_row_filter_eval: stack deeper than %d at ops[%d]", VRAG_FILTER_MAX_DEPTH, i);
+      ARG_CHECK(leaf < (uint32_t)n_leaves, "%s: ops[%d] pushes leaf %u of %d", who, i, leaf, n_leaves);
+      ARG_CHECK(depth < VRAG_FILTER_MAX_DEPTH, "%s: stack deeper than %d at ops[%d]", who, VRAG_FILTER_MAX_DEPTH, i);
       ++depth;
       byte = (unsigned char)leaf;
     } else if (code == VRAG_FILTER_OP_AND || code == VRAG_FILTER_OP_OR) {
-      ARG_CHECK(leaf == 0 && depth >= 2, "vrag_row_filter_eval: stack underflow at ops[%d]", i);
+      ARG_CHECK(leaf == 0 && depth >= 2, "%s: stack underflow at ops[%d]", who, i);
       --depth;
       byte = code == VRAG_FILTER_OP_AND ? RF_AND : RF_OR;
     } else {
-      ARG_CHECK(code == VRAG_FILTER_OP_NOT && leaf == 0, "vrag_row_filter_eval: ops[%d] = 0x%x is no operation", i, ops[i]);
-      ARG_CHECK(depth >= 1, "vrag_row_filter_eval: stack underflow at ops[%d]", i);
+      ARG_CHECK(code == VRAG_FILTER_OP_NOT && leaf == 0, "%s: ops[%d] = 0x%x is no operation", who, i, ops[i]);
+      ARG_CHECK(depth >= 1, "%s: stack underflow at ops[%d]", who, i);
       byte = RF_NOT;
     }
     args.ops[i >> 2] |= (unsigned)byte << ((i & 3) * 8);
   }
-  ARG_CHECK(depth == 1, "vrag_row_filter_eval: the program leaves %d values on the stack (one expected)", depth);
+  ARG_CHECK(depth == 1, "%s: the program leaves %d values on the stack (one expected)", who, depth);
   args.n_ops = n_ops;
 
   std::lock_guard<std::mutex> lk(f->mu);
@@ -252,30 +243,47 @@ int vrag_row_filter_eval(vrag_row_filter* f, const vrag_filter_leaf* leaves, int
   int n_slots = 0;
   for (int l = 0; l < n_leaves; ++l) {
     const vrag_filter_leaf& in = leaves[l];
-    ARG_CHECK(in.column >= 0 && in.column < (int)f->cols.size(), "vrag_row_filter_eval: leaf %d names column %d (the filter holds %d)", l,
+    ARG_CHECK(in.column >= 0 && in.column < (int)f->cols.size(), "%s: leaf %d names column %d (the filter holds %d)", who, l,
               in.column, (int)f->cols.size());
     ARG_CHECK(in.num_op <= VRAG_FILTER_NUM_GE && in.str_mode <= VRAG_FILTER_STR_TABLE && in.bool_bits <= 3 && in.other_bit <= 1,
-              "vrag_row_filter_eval: leaf %d has a field out of range", l);
+              "%s: leaf %d has a field out of range", who, l);
     LeafDev& lf = args.leaves[l];
     if (in.str_mode == VRAG_FILTER_STR_TABLE) {
       ARG_CHECK(in.table_off >= 0 && in.table_codes >= 0 && in.table_codes <= 0xffffffffll &&
                     in.table_off <= n_table_words && (in.table_codes + 31) / 32 <= n_table_words - in.table_off,
-                "vrag_row_filter_eval: leaf %d's table (offset %lld, %lld codes) lies outside the %lld table words", l,
+                "%s: leaf %d's table (offset %lld, %lld codes) lies outside the %lld table words", who, l,
                 (long long)in.table_off, (long long)in.table_codes, (long long)n_table_words);
       lf.table_off = (unsigned)in.table_off, lf.table_codes = (unsigned)in.table_codes;
     }
     int slot = 0;
     while (slot < n_slots && slot_col[slot] != in.column) ++slot;
     if (slot == n_slots) {
-      ARG_CHECK(n_slots < VRAG_FILTER_MAX_COLUMNS, "vrag_row_filter_eval: the leaves name more than %d columns", VRAG_FILTER_MAX_COLUMNS);
+      ARG_CHECK(n_slots < VRAG_FILTER_MAX_COLUMNS, "%s: the leaves name more than %d columns", who, VRAG_FILTER_MAX_COLUMNS);
       const FilterColumn& c = f->cols[in.column];
-      ARG_CHECK(n_rows <= c.n, "vrag_row_filter_eval: n_rows = %lld but column %d holds %lld rows", (long long)n_rows, in.column, c.n);
+      ARG_CHECK(n_rows <= c.n, "%s: n_rows = %lld but column %d holds %lld rows", who, (long long)n_rows, in.column, c.n);
       slot_col[n_slots++] = in.column;
       args.kinds[slot] = c.kinds.p, args.payload[slot] = c.payload.p;
     }
     lf.bound = in.bound;
     lf.slot = (unsigned char)slot, lf.num_op = in.num_op, lf.str_mode = in.str_mode;
     lf.bits = (unsigned char)(in.other_bit | (in.bool_bits << 1));
+  }
+  ARG_CHECK(n_matches >= 0 && n_matches <= n_leaves && (n_matches == 0 || matches), "%s: 0 <= n_matches <= n_leaves (got %d)", who,
+            n_matches);
+  ARG_CHECK(n_text_bytes >= 0 && (n_text_bytes == 0 || texts), "%s: bad text array (%lld bytes)", who, (long long)n_text_bytes);
+  std::vector<MatchProg> progs((size_t)n_matches);
+  for (int m = 0; m < n_matches; ++m) {
+    const vrag_filter_match& mt = matches[m];
+    ARG_CHECK(mt.leaf >= 0 && mt.leaf < n_leaves && leaves[mt.leaf].str_mode == VRAG_FILTER_STR_TABLE,
+              "%s: match %d names leaf %d, which is no table leaf", who, m, mt.leaf);
+    ARG_CHECK(mt.text_len >= 0 && mt.text_off >= 0 && mt.text_off <= n_text_bytes && mt.text_len <= n_text_bytes - mt.text_off,
+              "%s: match %d's text (offset %lld, %d bytes) lies outside the %lld text bytes", who, m, (long long)mt.text_off,
+              mt.text_len, (long long)n_text_bytes);
+    const FilterColumn& c = f->cols[leaves[mt.leaf].column];
+    ARG_CHECK(leaves[mt.leaf].table_codes <= c.n_codes, "%s: match %d asks for %lld codes but column %d's dictionary holds %lld", who, m,
+              (long long)leaves[mt.leaf].table_codes, leaves[mt.leaf].column, c.n_codes);
+    const int rc = match_compile(who, mt.op, texts ? texts + mt.text_off : nullptr, mt.text_len, &progs[(size_t)m]);
+    if (rc != VRAG_OK) return rc;
   }
   if (n_rows == 0) return VRAG_OK;
 
@@ -286,6 +294,10 @@ int vrag_row_filter_eval(vrag_row_filter* f, const vrag_filter_leaf* leaves, int
   HIP_TRY(f->d_out.grow((size_t)n_groups * 2));
   HIP_TRY(f->d_tables.grow((size_t)std::max<long long>(n_table_words, 1)));
   if (n_table_words) HIP_TRY(hipMemcpyAsync(f->d_tables.p, tables, (size_t)n_table_words * sizeof(unsigned), hipMemcpyHostToDevice, st));
+  for (int m = 0; m < n_matches; ++m) {   // stream order: behind the upload, in front of the eval kernel
+    const vrag_filter_leaf& in = leaves[matches[m].leaf];
+    HIP_TRY(match_launch(f->cols[in.column], progs[(size_t)m], in.table_codes, f->d_tables.p + in.table_off, st));
+  }
   const unsigned blocks = (unsigned)std::min<long long>((n_groups + RF_WAVES - 1) / RF_WAVES, RF_MAX_BLOCKS);
   hipLaunchKernelGGL(row_filter_eval_kernel, dim3(blocks), dim3(64 * RF_WAVES), 0, st, args, f->d_tables.p, (long long)n_rows, n_groups,
                      f->d_out.p);
@@ -293,6 +305,21 @@ int vrag_row_filter_eval(vrag_row_filter* f, const vrag_filter_leaf* leaves, int
   HIP_TRY(hipMemcpyAsync(out_words, f->d_out.p, n_words * sizeof(unsigned), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return VRAG_OK;
+}
+
+extern "C" {
+
+int vrag_row_filter_eval(vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops, int32_t n_ops,
+                         const uint32_t* tables, int64_t n_table_words, int64_t n_rows, uint32_t* out_words, void* stream) {
+  return eval_program("vrag_row_filter_eval", f, leaves, n_leaves, ops, n_ops, tables, n_table_words, nullptr, 0, nullptr, 0, n_rows,
+                      out_words, stream);
+}
+
+int vrag_row_filter_eval_matched(vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops, int32_t n_ops,
+                                 const uint32_t* tables, int64_t n_table_words, const vrag_filter_match* matches, int32_t n_matches,
+                                 const uint8_t* texts, int64_t n_text_bytes, int64_t n_rows, uint32_t* out_words, void* stream) {
+  return eval_program("vrag_row_filter_eval_matched", f, leaves, n_leaves, ops, n_ops, tables, n_table_words, matches, n_matches, texts,
+                      n_text_bytes, n_rows, out_words, stream);
 }
 
 }  // extern "C"

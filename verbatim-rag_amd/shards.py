@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import threading
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -252,7 +252,9 @@ class IvfOverlay(_Handle):
 
 class RowFilter(_Handle):
     """Typed metadata columns in HBM and the kernel that evaluates a filter program over them (`vrag_row_filter_*`,
-    csrc/rowfilter.hip): 9 bytes per row and column.  Columns are numbered in creation order and only ever appended to."""
+    csrc/rowfilter.hip): 9 bytes per row and column.  Columns are numbered in creation order and only ever appended to.
+    A column may also hold the dictionary of its strings (`append_strings`); the match kernel (csrc/strmatch.hip) then makes
+    the answer table of a string comparison or a `LIKE` from it (`match`, `eval_program(strings="device")`)."""
 
     _destroy = "vrag_row_filter_destroy"
 
@@ -277,10 +279,51 @@ class RowFilter(_Handle):
         _lib.check("vrag_row_filter_rows", self._lib.vrag_row_filter_rows(self._h, int(col), C.byref(n)))
         return n.value
 
+    def append_strings(self, col: int, data: np.ndarray, off: np.ndarray) -> None:
+        """Appends strings to the column's dictionary: string i = the UTF-8 bytes data[off[i]:off[i + 1]], off[0] = 0; codes
+        continue from those held (`store_columns.MetaColumn.string_bytes`)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        if off.ndim != 1 or len(off) < 1 or data.ndim != 1 or (len(off) > 1 and int(off[-1]) > len(data)):
+            raise ValueError(f"off {off.shape} must hold one offset more than strings and end inside the {len(data)} bytes")
+        _lib.check("vrag_row_filter_append_strings", self._lib.vrag_row_filter_append_strings(
+            self._h, int(col), _vp(data) if len(data) else None, _vp(off), len(off) - 1))
+
+    def strings(self, col: int) -> Tuple[int, int]:
+        """(codes, bytes) of the column's dictionary on the device."""
+        n, b = C.c_int64(), C.c_int64()
+        _lib.check("vrag_row_filter_strings", self._lib.vrag_row_filter_strings(self._h, int(col), C.byref(n), C.byref(b)))
+        return n.value, b.value
+
+    def match(self, col: int, op: str, text: str, n_codes: Optional[int] = None, out: Optional[np.ndarray] = None,
+              column=None, stream=None) -> np.ndarray:
+        """`stored <op> text` for codes [0, n_codes) of the column's device dictionary (default: all of it) as the words of
+        `MetaColumn.string_table`; op one of == != < <= > >= like.  The kernel's limits are the library's
+        (`match_on_device`): a text beyond them raises VragError, unless `column` (the `MetaColumn` of the same dictionary) is
+        given -- then the host table answers, as it does for such a leaf in `eval_program`."""
+        n = self.strings(col)[0] if n_codes is None else int(n_codes)
+        n_words = (max(0, n) + 31) // 32
+        if out is None:
+            out = np.zeros(n_words, np.uint32)
+        elif out.dtype != np.uint32 or not out.flags.c_contiguous or len(out) < n_words:
+            raise ValueError(f"out must be a contiguous uint32 array of at least {n_words} words")
+        if column is not None and match_on_device(op, text) is not None:
+            if n < 0 or n > len(column.strings):
+                raise ValueError(f"n_codes = {n} but the column holds {len(column.strings)} strings")
+            answers = np.unpackbits(column.string_table(op, text).view(np.uint8), bitorder="little")[:n]
+            out[:n_words] = _bitmap(answers)[:n_words]                   # the prefix's words, tail bits zero
+            return out
+        raw = text.encode("utf-8", "surrogatepass")          # what cannot be UTF-8 is the library's to refuse
+        _lib.check("vrag_row_filter_match", self._lib.vrag_row_filter_match(
+            self._h, int(col), _lib.FILTER_MATCH_OPS[op], raw, len(raw), n, _vp(out), stream))
+        return out
+
     def eval(self, leaves: Sequence["_lib.FilterLeaf"], ops: np.ndarray, tables: np.ndarray, n_rows: int,
-             out: Optional[np.ndarray] = None, stream=None) -> np.ndarray:
+             out: Optional[np.ndarray] = None, stream=None, matches: Sequence["_lib.FilterMatch"] = (), texts: bytes = b"") -> np.ndarray:
         """The program's answer for rows [0, n_rows) as uint32 words (bit r % 32 of word r // 32, tail bits zero).  `out`: a
-        uint32 array of at least ceil(n_rows / 32) words to write into (words behind those are left alone)."""
+        uint32 array of at least ceil(n_rows / 32) words to write into (words behind those are left alone).  `matches`: table
+        leaves whose tables the match kernel writes on the device before the program runs, their operand texts in `texts`
+        (vrag_row_filter_eval_matched)."""
         arr = (_lib.FilterLeaf * max(1, len(leaves)))(*leaves)
         ops = np.ascontiguousarray(ops, dtype=np.uint32)
         tables = np.ascontiguousarray(tables, dtype=np.uint32)
@@ -289,36 +332,89 @@ class RowFilter(_Handle):
             out = np.zeros(n_words, np.uint32)
         elif out.dtype != np.uint32 or not out.flags.c_contiguous or len(out) < n_words:
             raise ValueError(f"out must be a contiguous uint32 array of at least {n_words} words")
+        if len(matches):
+            _lib.check("vrag_row_filter_eval_matched", self._lib.vrag_row_filter_eval_matched(
+                self._h, arr, len(leaves), _vp(ops), len(ops), _vp(tables) if len(tables) else None, len(tables),
+                (_lib.FilterMatch * len(matches))(*matches), len(matches), texts, len(texts), int(n_rows), _vp(out), stream))
+            return out
         _lib.check("vrag_row_filter_eval", self._lib.vrag_row_filter_eval(
             self._h, arr, len(leaves), _vp(ops), len(ops), _vp(tables) if len(tables) else None, len(tables), int(n_rows),
             _vp(out), stream))
         return out
 
-    def eval_program(self, program, columns: Sequence[Tuple[int, "object"]], n_rows: int) -> np.ndarray:
+    def eval_program(self, program, columns: Sequence[Tuple[int, "object"]], n_rows: int, strings: str = "host",
+                     kept: Optional[List[str]] = None) -> np.ndarray:
         """`bool[n_rows]` of a `store_filter.FilterProgram`; `columns[i]` = (this filter's column number, the
-        `store_columns.MetaColumn` whose dictionary resolves the string leaves) of `program.keys[i]`."""
-        leaves, ops, tables = program_arrays(program, columns)
-        words = self.eval(leaves, ops, tables, n_rows)
+        `store_columns.MetaColumn` whose dictionary resolves the string leaves) of `program.keys[i]`.
+        `strings`: who makes the tables of the string leaves -- "host" (default) `MetaColumn.string_table`, once per distinct
+        string in Python; "device" the match kernel, over the columns' dictionaries in HBM (brought up to date here: only codes
+        not uploaded yet travel).  A leaf the kernel cannot take -- its text beyond a limit or not encodable, its column
+        holding a string without a UTF-8 form -- gets a host table inside the same call; `kept` (a list) receives one sentence
+        per such leaf."""
+        if strings not in ("host", "device"):
+            raise ValueError(f"strings must be 'host' or 'device' (got {strings!r})")
+        if strings == "host":
+            leaves, ops, tables = program_arrays(program, columns)
+            words = self.eval(leaves, ops, tables, n_rows)
+            return np.unpackbits(words.view(np.uint8), bitorder="little")[:n_rows].astype(bool)
+        for col, meta in {c: (c, m) for c, m in columns}.values():
+            have = self.strings(col)[0]
+            if meta.encodable and have < len(meta.strings):
+                self.append_strings(col, *meta.string_bytes(have))
+        leaves, ops, tables, matches, texts = program_arrays(program, columns, device_strings=True, kept=kept)
+        words = self.eval(leaves, ops, tables, n_rows, matches=matches, texts=texts)
         return np.unpackbits(words.view(np.uint8), bitorder="little")[:n_rows].astype(bool)
 
 
-def program_arrays(program, columns: Sequence[Tuple[int, "object"]]):
+def match_on_device(op: str, text: str) -> Optional[str]:
+    """Why the match kernel cannot take (`op`, `text`) -- one sentence -- or None when it can (VRAG_FILTER_MATCH_MAX_*)."""
+    from .store_filter import like_segments
+
+    try:
+        raw = text.encode("utf-8")
+    except UnicodeEncodeError:
+        return f"the text {text[:40]!r} has no UTF-8 form"
+    if len(raw) > _lib.FILTER_MATCH_MAX_PATTERN:
+        return f"the text {text[:40]!r}... has {len(raw)} bytes (the match kernel takes {_lib.FILTER_MATCH_MAX_PATTERN})"
+    if op == "like" and like_segments(text) > _lib.FILTER_MATCH_MAX_SEGMENTS:
+        return f"the pattern {text[:40]!r}... has {like_segments(text)} segments between its % (the match kernel takes " \
+               f"{_lib.FILTER_MATCH_MAX_SEGMENTS})"
+    return None
+
+
+def program_arrays(program, columns: Sequence[Tuple[int, "object"]], device_strings: bool = False, kept: Optional[List[str]] = None):
     """A `FilterProgram` as the arguments of `RowFilter.eval`: (`_lib.FilterLeaf` list, ops uint32, string tables uint32).
-    A string leaf's table is its comparison applied to every string of its column's dictionary as it stands now."""
+    A string leaf's table is its comparison applied to every string of its column's dictionary as it stands now.
+    `device_strings=True` adds (`_lib.FilterMatch` list, texts bytes): a string leaf the match kernel can take gets a table
+    range of zeros and a match entry that fills it on the device; the others keep host tables, one sentence each into `kept`."""
     leaves, parts, off = [], [], 0
+    matches, texts = [], b""
     for lf in program.leaves:
         col, meta = columns[lf.column]
         out = _lib.FilterLeaf(bound=float(lf.bound), table_off=0, table_codes=0, column=int(col),
                               num_op=_lib.FILTER_NUM_OPS[lf.num_op], str_mode=_lib.FILTER_STR_MODES.get(lf.str_op, 2),
                               bool_bits=int(lf.bools[0]) | (int(lf.bools[1]) << 1), other_bit=int(lf.other))
         if out.str_mode == 2:
-            table = meta.string_table(lf.str_op, lf.text)
+            why = None
+            if device_strings:
+                why = match_on_device(lf.str_op, lf.text) if meta.encodable else \
+                    f"metadata[{meta.key!r}] holds a string without a UTF-8 form"
+                if why is not None and kept is not None:
+                    kept.append(f"{lf.str_op} {lf.text[:40]!r} on metadata[{meta.key!r}]: {why}")
+            if device_strings and why is None:
+                raw = lf.text.encode("utf-8")
+                matches.append(_lib.FilterMatch(text_off=len(texts), text_len=len(raw), leaf=len(leaves), op=_lib.FILTER_MATCH_OPS[lf.str_op]))
+                texts += raw
+                table = np.zeros((len(meta.strings) + 31) // 32, np.uint32)
+            else:
+                table = meta.string_table(lf.str_op, lf.text)
             out.table_off, out.table_codes = off, len(meta.strings)
             parts.append(table)
             off += len(table)
         leaves.append(out)
     ops = np.asarray([_lib.FILTER_OPS[op] | (i << 8) for op, i in program.ops], dtype=np.uint32)
-    return leaves, ops, np.concatenate(parts) if parts else np.zeros(0, np.uint32)
+    tables = np.concatenate(parts) if parts else np.zeros(0, np.uint32)
+    return (leaves, ops, tables, matches, texts) if device_strings else (leaves, ops, tables)
 
 
 def dicts_to_csr(rows: Sequence[Dict[int, float]]) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:

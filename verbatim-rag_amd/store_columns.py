@@ -21,11 +21,14 @@ class MetaColumn:
     """One key's column, built by one Python pass over the rows and extended by the rows of every later insert -- O(new rows),
     never a rebuild.  `exact` turns False when a value cannot be represented faithfully: a NaN (tuple equality on NaN depends on
     object identity in the closures of `parse_filter`) or an int too large for a float (`_typed` raises for it); the store then
-    answers filters on this key on the host."""
+    answers filters on this key on the host.  `encodable` turns False when a stored string has no UTF-8 form (a lone
+    surrogate): the dictionary then stays on the host, and so do the tables of this column's string comparisons -- the rest
+    of a filter that names the key still runs on the device."""
 
     def __init__(self, key: str):
         self.key = key
         self.exact = True
+        self.encodable = True
         self.strings: List[str] = []                 # code -> string
         self._codes: Dict[str, int] = {}
         self._kinds = np.empty(0, np.uint8)
@@ -67,6 +70,11 @@ class MetaColumn:
                     if code is None:
                         code = codes[value] = len(strings)
                         strings.append(value)
+                        if self.encodable and not value.isascii():
+                            try:
+                                value.encode("utf-8")
+                            except UnicodeEncodeError:
+                                self.encodable = False
                     kind, other = KIND_STRING, code
                 else:
                     kind, other = KIND_BOOL, int(value)
@@ -85,6 +93,14 @@ class MetaColumn:
         self._payload[self._n: self._n + m] = np.where(k == KIND_NUMBER, np.asarray(numbers, dtype=np.float64).view(np.uint64),
                                                        np.asarray(others, dtype=np.uint64))
         self._n += m
+
+    def string_bytes(self, first: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """The dictionary from code `first` on as the device holds it (vrag_row_filter_append_strings): (uint8 UTF-8 bytes,
+        int64 offsets `[codes + 1]` from 0), code `first + i` = bytes[off[i]:off[i + 1]].  Only for an `encodable` column."""
+        encoded = [s.encode("utf-8") for s in self.strings[first:]]
+        off = np.zeros(len(encoded) + 1, np.int64)
+        np.cumsum(np.fromiter(map(len, encoded), np.int64, len(encoded)), out=off[1:])
+        return np.frombuffer(b"".join(encoded), np.uint8), off
 
     def string_table(self, op: str, text: str) -> np.ndarray:
         """`stored <op> text` for every string of the dictionary, as bits: uint32 words, bit `code % 32` of word `code // 32`

@@ -5,6 +5,7 @@ from __future__ import annotations
 import operator
 import re
 from dataclasses import dataclass, field
+from functools import lru_cache
 from typing import Any, List, Optional, Tuple
 
 
@@ -26,10 +27,46 @@ def _typed(value: Any):
     return None
 
 
+def like_elements(pattern: str) -> List[Tuple[str, str]]:
+    """A `LIKE` pattern as elements: `("%", "")` any run of characters, `("_", "")` exactly one character, `("c", ch)` the
+    character `ch` itself.  A backslash makes the next character literal; a trailing lone backslash is a ValueError."""
+    out, i = [], 0
+    while i < len(pattern):
+        ch = pattern[i]
+        if ch == "\\":
+            if i + 1 == len(pattern):
+                raise ValueError(f"GpuVectorStore: LIKE pattern {pattern!r} ends in a lone backslash")
+            out.append(("c", pattern[i + 1]))
+            i += 2
+            continue
+        out.append((ch, "") if ch in "%_" else ("c", ch))
+        i += 1
+    return out
+
+
+def like_segments(pattern: str) -> int:
+    """Non-empty runs of `_` and literal characters between the unescaped `%` of `pattern`: what the device matcher walks
+    (VRAG_FILTER_MATCH_MAX_SEGMENTS)."""
+    kinds = "".join("%" if kind == "%" else "x" for kind, _ch in like_elements(pattern))
+    return len([run for run in kinds.split("%") if run])
+
+
+@lru_cache(maxsize=256)
+def _like_regex(pattern: str):
+    return re.compile("".join(".*" if kind == "%" else "." if kind == "_" else re.escape(ch) for kind, ch in like_elements(pattern)),
+                      re.S)
+
+
+def like_match(stored: str, pattern: str) -> bool:
+    """`stored LIKE pattern` (Milvus' pattern language): over the whole string, case-sensitive, one character = one code point,
+    a newline a character like any other."""
+    return _like_regex(pattern).fullmatch(stored) is not None
+
+
 def parse_filter_ast(expr: str):
     """The parser both back ends share: `expr` -> a tree of `("cmp", key, op, want)` (op one of == != < <= > >=, `want` the
-    literal's `_typed` key), `("in", key, [want, ...])`, `("not", a)`, `("and", a, b)`, `("or", a, b)`.  Raises ValueError for
-    anything outside the grammar `parse_filter` states."""
+    literal's `_typed` key), `("in", key, [want, ...])`, `("like", key, pattern)`, `("not", a)`, `("and", a, b)`, `("or", a, b)`
+    (`x not in [..]` is `("not", ("in", ..))`).  Raises ValueError for anything outside the grammar `parse_filter` states."""
     toks, pos = [], 0
     while pos < len(expr):
         if expr[pos:].strip() == "":
@@ -52,6 +89,10 @@ def parse_filter_ast(expr: str):
                 toks.append(("op", w.lower()))
             elif w.lower() in ("true", "false"):
                 toks.append(("val", w.lower() == "true"))
+            elif w == "LIKE":
+                toks.append(("op", "LIKE"))
+            elif w.lower() == "like":
+                toks.append(("miscased", w))        # a field name where a field may stand, an error where the keyword would
             else:
                 toks.append(("field", w))
     i = 0
@@ -76,8 +117,24 @@ def parse_filter_ast(expr: str):
         if peek() == ("op", "not"):
             take()
             return ("not", comparison())
+        if peek()[0] == "miscased":
+            toks[i] = ("field", peek()[1])
         key = take("field")
+        if peek()[0] == "miscased":
+            raise ValueError(f"GpuVectorStore: unsupported filter {expr!r}: the pattern-match keyword is LIKE, in upper case "
+                             f"(got {peek()[1]!r})")
         op = take("op")
+        if op == "LIKE":
+            pattern = take("val")
+            if not isinstance(pattern, str):
+                raise ValueError(f"GpuVectorStore: LIKE needs a quoted pattern in filter {expr!r}")
+            like_elements(pattern)                    # a trailing lone backslash is refused here
+            return ("like", key, pattern)
+        if op == "not":
+            take("op", "in")
+            op, negated = "in", True
+        else:
+            negated = False
         if op in ("==", "!="):
             return ("cmp", key, op, _typed(take("val")))
         if op == "in":
@@ -87,7 +144,7 @@ def parse_filter_ast(expr: str):
                 take()
                 vals.append(_typed(take("val")))
             take("op", "]")
-            return ("in", key, vals)
+            return ("not", ("in", key, vals)) if negated else ("in", key, vals)
         if op in ("<", "<=", ">", ">="):
             want = _typed(take("val"))
             if want[0] == "b":
@@ -135,6 +192,13 @@ def _closure(node):
         f = lambda md: _typed(md.get(key)) in vs      # noqa: E731
         f.lookup = (key, vals)
         return f
+    if tag == "like":
+        key, matches = node[1], _like_regex(node[2]).fullmatch
+
+        def like(md):
+            have = md.get(key)
+            return isinstance(have, str) and matches(have) is not None
+        return like
     _tag, key, op, want = node
     if op == "!=":
         return lambda md: _typed(md.get(key)) != want
@@ -152,12 +216,19 @@ def _closure(node):
 
 def parse_filter(expr: str):
     """Compiles the subset of Milvus boolean expressions the store supports into `predicate(metadata: dict) -> bool`:
-    `field == value`, `field != value`, `field in [v, ...]`, `field < / <= / > / >= value`, combined with `and` / `&&`,
-    `or` / `||`, `not` and parentheses.  field = `metadata["key"]` (the Local dialect) or a bare `key` (the Cloud
+    `field == value`, `field != value`, `field in [v, ...]`, `field not in [v, ...]`, `field < / <= / > / >= value`,
+    `field LIKE "pattern"`, combined with `and` / `&&`, `or` / `||`, `not` and parentheses.  field = `metadata["key"]` (the Local dialect) or a bare `key` (the Cloud
     dialect: index.py:735-739); value = a quoted string, a number (`7`, `-2.5`, `1e3`) or `true` / `false`.
     Comparisons are typed like Milvus' JSON path match: numbers against numeric metadata, strings against text,
-    booleans against booleans; a missing key equals nothing (so `!=` holds for it).  Anything else raises ValueError --
-    a filter is never silently ignored."""
+    booleans against booleans; a missing key equals nothing (so `!=` holds for it).
+    `LIKE` takes a quoted pattern in Milvus' pattern language: `%` matches any run of zero or more characters, `_` exactly one
+    character (one code point: `Z_rich` matches `Zürich`), a backslash makes the next character literal (`\\%`, `\\_`, `\\\\`; a
+    trailing lone backslash is a ValueError).  The match is over the whole string and case-sensitive, a newline is a character
+    like any other, and only a stored string can match -- so `not (title LIKE "x%")` holds for numbers, booleans, None, lists,
+    dicts and missing keys, as `not (title == "x")` does.  String literals have no escapes of their own: a pattern that needs
+    a `"` is written in `'...'`.  The keyword is the upper-case word `LIKE` only, as the reference writes it; any other casing
+    (`like`, `Like`) raises a ValueError that says so, and a metadata key named `LIKE` is written `metadata["LIKE"]`.
+    Anything else raises ValueError -- a filter is never silently ignored."""
     return _closure(parse_filter_ast(expr))
 
 
@@ -169,10 +240,11 @@ def parse_filter(expr: str):
 #   bool                                             one answer for false, one for true
 #   number                                           never / always / one IEEE f64 comparison against `bound`
 #   string                                           never / always / a Python comparison against `text`, which the store applies
-#                                                    once per distinct stored string (store_columns.MetaColumn.string_table)
-# `in [..]` is an OR of `==` leaves: a list may mix kinds.
+#                                                    once per distinct stored string (store_columns.MetaColumn.string_table) or
+#                                                    the match kernel applies to the column's dictionary in HBM (csrc/strmatch.hip)
+# `in [..]` is an OR of `==` leaves: a list may mix kinds.  `LIKE` is one leaf that only a string can answer (str_op "like").
 MAX_COLUMNS, MAX_LEAVES, MAX_OPS, MAX_DEPTH = 16, 64, 256, 32     # VRAG_FILTER_MAX_*
-STRING_COMPARE = {"==": operator.eq, "!=": operator.ne, **_ORDER}
+STRING_COMPARE = {"==": operator.eq, "!=": operator.ne, **_ORDER, "like": like_match}
 
 
 @dataclass(frozen=True)
@@ -182,7 +254,7 @@ class FilterLeaf:
     bools: Tuple[bool, bool]        # (answer for false, answer for true)
     num_op: str                     # "never" | "always" | "==" | "!=" | "<" | "<=" | ">" | ">="
     bound: float
-    str_op: str                     # the same choices, against `text`
+    str_op: str                     # the same choices and "like", against `text`
     text: str
 
 
@@ -235,6 +307,12 @@ def compile_filter(expr: str) -> FilterProgram:
         tag = node[0]
         if tag == "cmp":
             push(node[1], node[2], node[3])
+        elif tag == "like":
+            if node[1] not in prog.keys:
+                prog.keys.append(node[1])
+            prog.leaves.append(FilterLeaf(column=prog.keys.index(node[1]), other=False, bools=(False, False), num_op="never",
+                                          bound=0.0, str_op="like", text=node[2]))
+            prog.ops.append(("leaf", len(prog.leaves) - 1))
         elif tag == "in":
             for n, want in enumerate(node[2]):
                 push(node[1], "==", want)

@@ -509,7 +509,7 @@ class GpuVectorStore(VectorStore):
                  group=None, comm=None, payload: str = "sharded", dense_headroom: float = 1.5,
                  dense_prefilter="auto", enable_full_text: bool = False, bm25_k1: float = 1.2, bm25_b: float = 0.75,
                  filter_route: str = "subset", rrf_route: str = "host", index_type: str = "FLAT", nlist: int = 8192,
-                 nprobe: int = 16, filter_eval: str = "host"):
+                 nprobe: int = 16, filter_eval: str = "host", filter_strings: str = "host"):
         """`enable_full_text`: BM25 keyword search over the raw texts (milvus_cloud.py: bm25_k1 = 1.2, bm25_b = 0.75),
         `search_type="full_text"` and the third leg of a weighted hybrid search; the texts are tokenised, indexed and
         scored on the device (`TextIndex`).  Off by default.  On a sharded store (`distributed=True` or a `comm`) the
@@ -538,6 +538,13 @@ class GpuVectorStore(VectorStore):
         same mask bit for bit.  A filter beyond the device program's limits (16 keys, 64 comparisons, 256 operations, nesting
         32 deep) or naming a key that holds a NaN is answered on the host (logged once per filter string).  A run-time choice like
         `filter_route`: not written by `save`, a keyword of `load`.
+        `filter_strings` (only with `filter_eval="device"`): who applies a filter's string comparisons and `LIKE` patterns to the
+        distinct strings of a key -- "host" (default) Python, once per distinct string for every new (operator, text); "device"
+        the match kernel (csrc/strmatch.hip) over the key's string dictionary kept in HBM (its UTF-8 bytes plus 8 bytes per
+        distinct string; only new strings travel after an insert).  The same mask bit for bit.  A comparison whose text is
+        beyond the kernel's limits (256 bytes, 16 segments between a pattern's `%`) or whose key holds a string without a UTF-8
+        form keeps its host table while the rest of the filter runs on the device (logged once per filter string).  A run-time
+        choice like `filter_eval`.
         `index_type`: "FLAT" (default) = every dense query streams the whole shard, exact.  "IVF_FLAT" (the reference's Milvus
         stores, milvus_base.py:40-50) = the dense leg looks only at the rows of the `nprobe` lists nearest to the query out of
         `nlist` k-means lists laid over the resident shard (`IvfOverlay`; `ivf_effective_nlist` caps `nlist` for small stores
@@ -557,6 +564,8 @@ class GpuVectorStore(VectorStore):
             raise ValueError(f"rrf_route must be 'host' or 'device' (got {rrf_route!r})")
         if filter_eval not in ("host", "device"):
             raise ValueError(f"filter_eval must be 'host' or 'device' (got {filter_eval!r})")
+        if filter_strings not in ("host", "device"):
+            raise ValueError(f"filter_strings must be 'host' or 'device' (got {filter_strings!r})")
         if not enable_dense and not enable_sparse and not enable_full_text:      # milvus_base.py:54-56
             raise ValueError("At least one of enable_dense, enable_sparse, or enable_full_text must be True")
         if enable_full_text and comm is None and distributed:
@@ -586,6 +595,7 @@ class GpuVectorStore(VectorStore):
         self.rrf_route = rrf_route
         self.filter_route = filter_route
         self.filter_eval = filter_eval
+        self.filter_strings = filter_strings
         self.index_type, self.nlist, self.nprobe = index_type, int(nlist), int(nprobe)
         self._ivf_trained_rows = 0   # rows in the shard when its overlay was last trained (0 = no overlay)
         # the route searches take: the filtered search returns host lists, which the device-resident exchange does not carry.
@@ -968,7 +978,16 @@ class GpuVectorStore(VectorStore):
             if have < len(column):
                 self._row_filter.append(col, column.kinds[have:], column.payload[have:])
             device_cols.append((col, column))
-        return self._row_filter.eval_program(program, device_cols, len(self._meta))
+        if self.filter_strings == "host":
+            return self._row_filter.eval_program(program, device_cols, len(self._meta))
+        kept: List[str] = []
+        held = self._row_filter.eval_program(program, device_cols, len(self._meta), strings="device", kept=kept)
+        if kept and filter not in self._filter_fallbacks:
+            if len(self._filter_fallbacks) >= 1024:
+                self._filter_fallbacks.clear()
+            self._filter_fallbacks.add(filter)
+            logger.info("GpuVectorStore: filter %r keeps host tables for: %s", filter, "; ".join(kept))
+        return held
 
     def _value_index(self, key: str) -> Dict[Any, np.ndarray]:
         """typed metadata[key] -> rows (positions in the metadata list), built once per key until the next insert: a
@@ -1562,10 +1581,10 @@ class GpuVectorStore(VectorStore):
     @classmethod
     def load(cls, path: str, device: int = 0, distributed: bool = False, group=None, comm=None,
              payload: str = "sharded", filter_route: str = "subset", rrf_route: str = "host",
-             filter_eval: str = "host") -> "GpuVectorStore":
+             filter_eval: str = "host", filter_strings: str = "host") -> "GpuVectorStore":
         """Reads a directory written by `save` -- by this or an earlier revision (formats 1 - 3), by any number of
         ranks: when the world size differs from the writer's, the saved shards are put back in row order and cut
-        contiguously over the ranks that open the store.  `filter_route`, `rrf_route`, `filter_eval`: as the constructor's (not part of a saved store).
+        contiguously over the ranks that open the store.  `filter_route`, `rrf_route`, `filter_eval`, `filter_strings`: as the constructor's (not part of a saved store).
         An IVF_FLAT store comes back IVF_FLAT with its `nlist` / `nprobe`; its lists are trained again at the first flush
         (training is deterministic: the same rows give the same lists)."""
         head, ids, shards = cls._read_saved(path)
@@ -1575,7 +1594,7 @@ class GpuVectorStore(VectorStore):
                  dense_prefilter=head.get("dense_prefilter", "auto"), enable_full_text=bool(head.get("enable_full_text", False)),
                  bm25_k1=head.get("bm25_k1", 1.2), bm25_b=head.get("bm25_b", 0.75), filter_route=filter_route,
                  rrf_route=rrf_route, index_type=head.get("index_type", "FLAT"), nlist=head.get("nlist", 8192),
-                 nprobe=head.get("nprobe", 16), filter_eval=filter_eval)
+                 nprobe=head.get("nprobe", 16), filter_eval=filter_eval, filter_strings=filter_strings)
         n = len(ids)
         for owned, *_ in shards:
             if len(owned) and (owned.min() < 0 or owned.max() >= n):
