@@ -843,6 +843,42 @@ int vrag_split_sentences(const uint8_t* text, const int64_t* doc_off /*[n_docs+1
                          int32_t* counts /*[n_docs]*/, int32_t* starts /*[n_docs, cap]*/, int32_t* ends /*[n_docs, cap]*/,
                          int32_t device);
 
+/* Markdown chunking of a batch of documents (csrc/chunk.hip): the structural pass of the reference's default chunker
+ * (MarkdownChunkerProvider._md_chunker_with_ancestor_injection, verbatim_rag/chunker_providers.py:93-213) over UTF-8 bytes.
+ * All offsets are BYTE offsets inside the document; chunk borders follow a '\n', so they are code-point borders.  White space =
+ * Python's str.isspace set.  For a document of n bytes:
+ *   R1  lines start at byte 0 and behind every 0x0A, nowhere else;
+ *   R2  a line start s is a candidate when the line opens with exactly k '#' (1 <= k <= 6) and a white-space character starts at
+ *       s + k (it may be the '\n'; '#' with nothing behind it is no candidate);
+ *   R3  its match is [s, e): p = first byte at or behind s + k that starts no white-space character (possibly lines further
+ *       down), e = first 0x0A at or behind p, else n; title = [p, e) without trailing white space; level = k; the header's
+ *       exact line = [line_start, line_end) = s's own line without its '\n';
+ *   R4  in ascending order a candidate is a header iff s > e of the header accepted before it (re.finditer: a candidate inside
+ *       an earlier match is swallowed);
+ *   R5  no header: one chunk [0, n), header = -1 (also for n = 0);
+ *   R6  include_preamble and line_start of the first header > 0: first chunk [0, that line_start), header = -1;
+ *   R7  header i owns [line_start_i, block_end_i) = up to the next header's line_start or n; it becomes a chunk iff bit `level`
+ *       of split_levels is set (other blocks belong to no chunk); the stack pops while its top's level >= the header's level,
+ *       then takes the header, chunk or not;
+ *   R8  a chunk's ancestors are the stack below its header: at most five, levels strictly rising, outermost first.
+ * headers[] holds every header of the batch in document, then position order; chunks[] likewise, the chunks of document d at
+ * doc_chunk_off[d] .. doc_chunk_off[d+1]; `header` and `ancestors` index headers[] (unused ancestor slots are -1).
+ * Documents may be empty; doc_off[0] = 0; a document is under 2 GiB, a batch at most VRAG_MD_MAX_BATCH_BYTES; split_levels bits
+ * outside 1..6 are VRAG_ERR_INVALID.  n_headers / n_chunks / doc_chunk_off are always filled in; the tables only when both fit,
+ * else VRAG_ERR_CAPACITY (a document has at most one header per line that begins with '#', and one chunk more than headers).
+ * Bytes that are not valid UTF-8 are ordinary non-space bytes: the call never fails on content.  Host pointers; synchronous. */
+#define VRAG_MD_MAX_BATCH_BYTES (512ll << 20)
+typedef struct {
+  int32_t doc, level, line_start, line_end, title_start, title_end, block_end, reserved /* 0 */;
+} vrag_md_header;
+typedef struct {
+  int32_t doc, start, end, header /* index into headers[], -1 = preamble / whole document */, n_ancestors, ancestors[5];
+} vrag_md_chunk;
+int vrag_chunk_markdown(const uint8_t* text, const int64_t* doc_off /*[n_docs+1]*/, int32_t n_docs, uint32_t split_levels,
+                        int32_t include_preamble, int64_t header_cap, vrag_md_header* headers, int64_t chunk_cap,
+                        vrag_md_chunk* chunks, int64_t* n_headers, int64_t* n_chunks, int64_t* doc_chunk_off /*[n_docs+1]*/,
+                        int32_t device);
+
 /* Host-side packer of the (question, chunk) pairs of ONE question for the sentence-classification extractor -- the layout
  *   [CLS] q [SEP] s1 [SEP] s2 ... ([SEP])   with inclusive token ranges per sentence, budget = max_length - 2, sentences that do
  * not fit dropped from the first one that does not (extractor_models/dataset.py:127-243).  The question-independent pieces of a

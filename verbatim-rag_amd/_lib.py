@@ -181,6 +181,8 @@ SIGNATURES = {
     "vrag_pack_qa_pairs": (C.c_int, [_IP, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, _IP, C.c_int32, C.c_int32, _IP, C.c_int64,
                                       _LP, _LP, C.c_int64, _IP, _IP, _LP]),
     "vrag_split_sentences": (C.c_int, [C.c_void_p, _LP, C.c_int32, C.c_int32, _IP, _IP, _IP, C.c_int32]),
+    "vrag_chunk_markdown": (C.c_int, [C.c_void_p, _LP, C.c_int32, C.c_uint32, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                      _LP, _LP, _LP, C.c_int32]),
     "vrag_topk_fill_empty": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "vrag_sparse_index_create": (C.c_int, [C.c_int32, C.c_int64, _LP, _IP, _FP, C.c_int32, C.POINTER(_H)]),
     "vrag_sparse_index_destroy": (None, [_H]),

@@ -1,6 +1,9 @@
 """Glue between providers and the store for the hot path: the query dispatch of VerbatimIndex
-(verbatim_rag/index.py:552-655) and the batched embed-then-insert of chunks (:200-223,259-288,340-411; 2000-chunk embed
-batches).  Chunking / document schemas stay with the reference (out of scope); callers pass ready chunks.
+(verbatim_rag/index.py:552-655), the batched embed-then-insert of chunks (:200-223,259-288; 2000-chunk embed batches) and the
+bulk ingest of documents (`add_documents`, :128-198,225-257,290-316,340-411) in front of it: documents are chunked by a chunker
+provider -- by default chunker_providers.GpuMarkdownChunker, whose structural pass runs on the device for a whole batch of
+documents -- wrapped in the reference's document footer, embedded and stored.  The pydantic DocumentSchema flattening
+(:73-126), the chonkie chunker and documents that bring their own chunks stay with the reference; `add_chunks` takes ready chunks.
 
 The dispatch is one planning step (`_plan`) shared by the single-query and the cross-query entry points: it turns
 (search_type, hybrid_weights, which providers exist) into "which providers embed the text" plus the keyword arguments the
@@ -9,8 +12,10 @@ store receives -- the contract pinned by the `index_query_trace` fixture, which 
 """
 from __future__ import annotations
 
+import uuid
+from collections.abc import Mapping
 from dataclasses import dataclass, field
-from typing import Any, Dict, List, Optional, Sequence
+from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence
 
 from .vector_stores import SearchResult, VectorStore
 
@@ -27,16 +32,62 @@ class _Plan:
     store_kwargs: Dict[str, Any] = field(default_factory=dict)
 
 
+_FOOTER_SKIPS = {"user_id", "dataset_id", "userId"}   # never embedded (index.py:190-196)
+
+
+@dataclass
+class _Doc:
+    """What add_documents reads from a document, whatever its type."""
+    id: str
+    title: str
+    source: str
+    content: str
+    content_type: Optional[str]
+    metadata: Dict[str, Any]
+
+    @classmethod
+    def of(cls, document: Any) -> "_Doc":
+        def get(name, default=None):
+            if isinstance(document, Mapping):
+                return document.get(name, default)
+            return getattr(document, name, default)
+
+        if get("chunks"):
+            raise ValueError("add_documents chunks the documents itself; pass documents that bring their own chunks to add_chunks")
+        content = get("raw_content")
+        if content is None:
+            content = get("content")
+        content_type = get("content_type")
+        doc_id = get("id")
+        return cls(id=str(uuid.uuid4()) if doc_id is None else doc_id, title=get("title") or "", source=get("source") or "",
+                   content=content or "", content_type=getattr(content_type, "value", content_type), metadata=get("metadata") or {})
+
+    def footer(self) -> str:
+        """What follows the chunker's enhanced text in the embedded text (index.py:185-198)."""
+        parts = ["", "", "---", f"Document: {self.title or 'Unknown'}"]
+        if self.source:
+            parts.append(f"Source: {self.source}")
+        parts += [f"{key.replace('_', ' ').title()}: {value}" for key, value in self.metadata.items() if key not in _FOOTER_SKIPS]
+        return "\n".join(parts)
+
+    def chunk_metadata(self, number: int) -> Dict[str, Any]:
+        """index.py:240-257, in that key order; the document's own metadata is laid over it."""
+        return {"document_id": self.id, "title": self.title, "source": self.source, "doc_type": self.metadata.get("doc_type"),
+                "content_type": self.content_type or None, "chunk_type": "paragraph", "chunk_number": number, "page_number": 0,
+                **self.metadata}
+
+
 class HotPathIndex:
     EMBED_BATCH = 2000  # index.py:343
 
-    def __init__(self, vector_store: VectorStore, dense_provider=None, sparse_provider=None):
+    def __init__(self, vector_store: VectorStore, dense_provider=None, sparse_provider=None, chunker_provider=None):
         if dense_provider is None and sparse_provider is None:  # index.py:58-64
             if not bool(getattr(vector_store, "enable_full_text", False)):
                 raise ValueError("At least one embedding provider (dense or sparse) must be provided")
         self.vector_store = vector_store
         self.dense_provider = dense_provider
         self.sparse_provider = sparse_provider
+        self.chunker_provider = chunker_provider   # None: a GpuMarkdownChunker(), made by the first add_documents (index.py:69)
 
     # ------------------------------------------------------------------ ingest
     def _generate_embeddings(self, texts: List[str]):
@@ -56,6 +107,68 @@ class HotPathIndex:
             dense, sparse = self._generate_embeddings(enhanced_texts[a:b])
             self.vector_store.add_vectors(list(ids[a:b]), dense, sparse, list(texts[a:b]), enhanced_texts[a:b],
                                           metadatas[a:b])
+
+    def _chunk_documents(self, texts: List[str]) -> List[List[Any]]:
+        if self.chunker_provider is None:
+            from .chunker_providers import GpuMarkdownChunker
+
+            self.chunker_provider = GpuMarkdownChunker()
+        batch = getattr(self.chunker_provider, "chunk_batch", None)
+        return batch(texts) if batch is not None else [self.chunker_provider.chunk(t) for t in texts]
+
+    def add_documents(self, documents: Iterable[Any], batch_chunks: int = 2000, batch_docs: int = 500,
+                      id_factory: Optional[Callable[[], str]] = None) -> None:
+        """Documents in, stored rows out: VerbatimIndex.add_documents_bulk (index.py:340-411) with the chunker called once per
+        `batch_docs` documents (`chunk_batch`: one device call for the default chunker).  A document is a mapping or an object
+        with id, title, source, raw_content (or content), metadata and optionally content_type; one that brings its own chunks
+        belongs to `add_chunks`.  Chunks are embedded (enhanced text) and inserted as soon as `batch_chunks` of them have
+        gathered, in the middle of a document if need be; the document records go to the store's `add_documents`, if it has
+        one, once per `batch_docs` documents, deduplicated by id."""
+        new_id = id_factory or (lambda: str(uuid.uuid4()))
+        ids: List[str] = []
+        texts: List[str] = []
+        enhanced_texts: List[str] = []
+        metadatas: List[Dict[str, Any]] = []
+
+        def flush_chunks():
+            if ids:
+                dense, sparse = self._generate_embeddings(enhanced_texts)
+                self.vector_store.add_vectors(list(ids), dense, sparse, list(texts), list(enhanced_texts), list(metadatas))
+                for column in (ids, texts, enhanced_texts, metadatas):
+                    column.clear()
+
+        def flush_documents(docs: List["_Doc"]):
+            records: Dict[str, Dict[str, Any]] = {}
+            for doc in docs:
+                records.setdefault(doc.id, {"id": doc.id, "title": doc.title, "source": doc.source, "content_type": doc.content_type,
+                                            "raw_content": "", "metadata": doc.metadata})
+            if records and hasattr(self.vector_store, "add_documents"):   # index.py:299-316
+                self.vector_store.add_documents(list(records.values()))
+
+        group: List[_Doc] = []
+
+        def flush_group(last: bool = False):
+            chunked = self._chunk_documents([doc.content for doc in group]) if group else []
+            for doc, chunks in zip(group, chunked):
+                footer = doc.footer()
+                head = f"# {doc.title}\n\n\n" if doc.title else ""
+                for number, (raw, enhanced) in enumerate(chunks):
+                    ids.append(new_id())
+                    texts.append(raw)
+                    enhanced_texts.append(head + enhanced + footer)
+                    metadatas.append(doc.chunk_metadata(number))
+                    if len(ids) >= batch_chunks:
+                        flush_chunks()
+            if last:                        # the reference stores the last chunks before the last document records
+                flush_chunks()
+            flush_documents(group)
+            group.clear()
+
+        for document in documents:
+            group.append(_Doc.of(document))
+            if len(group) >= batch_docs:
+                flush_group()
+        flush_group(last=True)
 
     # ------------------------------------------------------------------ query dispatch
     def _plan(self, search_type: str, filter, search_params, hybrid_weights, rrf_k) -> _Plan:
