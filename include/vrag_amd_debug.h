@@ -38,8 +38,8 @@ int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, 
  * V^T is read at row head * 64 + d < H, 8 columns from min(seq_row + c, rows - 8) with c >= 0: inside [0, rows).  O is stored
  * at rows seq_row + g only where g < seq_len, and seq_row + seq_len <= rows is checked.  The descriptor arrays hold n_blocks
  * entries and the grid is n_blocks x H / 64.  A sequence may therefore END ON THE LAST ROW: its last 64-key tile then runs
- * past `rows` and all three clamps bite.  The hook also keeps 4 KiB of canary behind o and fails with VRAG_ERR_HIP if the
- * launch touched it.
+ * past `rows` and all three clamps bite.  Every device buffer, inputs included, is followed by 4 KiB of canary; the hook fails
+ * with VRAG_ERR_HIP if the launch touched any.
  * Operand contract (csrc/attention.h): every K row and V^T column of the buffer must be finite; Q rows outside the
  * sequences may hold anything. */
 typedef struct vrag_debug_attn_args {
@@ -111,7 +111,8 @@ int vrag_debug_gemm_run(vrag_debug_gemm_args* args, int32_t device);
  * the hook runs permute_qkv_heads on them as the encoder does at load (ln_s with 64 readable floats behind the last head).
  * Refused before anything is launched: null required pointers, H != 64 * nh, rows % 256 != 0, seq_len outside 1..512,
  * seq_row % 8 != 0, overlapping sequences, and a sequence with seq_row + 64 * ceil(len / 64) > rows (a wave reads 64 WHOLE token
- * rows, whatever its sequence's length: the encoder's row slack pays for that, the hook does not hide it). */
+ * rows, whatever its sequence's length: the encoder's row slack pays for that, the hook does not hide it).
+ * Every device buffer, inputs included, is followed by 4 KiB of canary; the hook fails with VRAG_ERR_HIP if a launch touched any. */
 typedef struct vrag_debug_qkv_attn_args {
   const uint16_t* x;         /* [rows, H] */
   const uint16_t* w;         /* [3 H, H] */
@@ -515,6 +516,12 @@ typedef struct vrag_debug_text_index_state {
 } vrag_debug_text_index_state;
 struct vrag_text_index;
 int vrag_debug_text_index_read(struct vrag_text_index* ix, vrag_debug_text_index_state* state);
+
+/* Self-test of the hooks' device staging (csrc/debug_bufs.h): stages "a" (in, 64 bytes), "b" (in / out, 100 bytes and 28 pad
+ * bytes) and "c" (scratch, empty), launches nothing, and returns what the hooks' common canary check returns.  touch 0: nothing
+ * more, VRAG_OK with b copied back as it went in; 1 / 2: a host-issued one-byte hipMemset on the first / last canary byte of b,
+ * VRAG_ERR_HIP naming b; 3: on the last pad byte of b, VRAG_OK.  Any other touch is VRAG_ERR_INVALID before the device check. */
+int vrag_debug_canary_selftest(int32_t touch, int32_t device);
 
 /* Unit-test hook of span selection (csrc/spans.hip): vrag_encoder_read_token_spans with a host array of packed logits
  * [n_tokens, 2] in place of an engine -- win_first[w] indexes its rows -- through the same checks and the same kernel. */

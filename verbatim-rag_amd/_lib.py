@@ -243,6 +243,7 @@ DEBUG_SIGNATURES = {
     "vrag_debug_text_index_read": (C.c_int, [C.c_void_p, C.c_void_p]),
     "vrag_debug_token_spans": (C.c_int, [_FP, C.c_int64, _IP, _IP, _IP, _IP, C.c_int32, _LP, _IP, C.c_int32, C.c_float, C.c_int32, C.c_int32,
                                          C.c_int32, _IP, _IP, C.c_int32]),
+    "vrag_debug_canary_selftest": (C.c_int, [C.c_int32, C.c_int32]),
     "vrag_debug_topk_launch_log_reset": (None, []),
     "vrag_debug_topk_launch_log_read": (C.c_int, [_IP, C.c_int32, _IP, _IP]),
 }

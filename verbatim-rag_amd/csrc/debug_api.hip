@@ -1,6 +1,7 @@
 // Tuning / unit-test harness of the kernels (include/vrag_amd_debug.h): synthetic-operand timing loops and the attention
 // kernels', the GEMM's, the row kernels', the packing / glue kernels' and the tiled search kernels' unit-test hooks.  NOT part of the product library: compiled only into libvrag_amd_dbg.so (build.py, -DVRAG_DEBUG_API),
-// which tools/ and the attention unit test load beside libvrag_amd.so.
+// which tools/ and the attention unit test load beside libvrag_amd.so.  Every hook stages its device buffers, and has their
+// canaries checked, through DbgBufs (debug_bufs.h).
 #include "../../include/vrag_amd.h"
 #include "../../include/vrag_amd_debug.h"
 
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "attention.h"
+#include "debug_bufs.h"
 #include "gemm_bf16.h"
 #include "glue_kernels.h"
 #include "host_util.h"
@@ -20,7 +22,60 @@
 
 using namespace vrag;
 
-static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+namespace {
+
+inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+
+// Operands of the timing loops: pseudo-random bf16 in [-1, 1), 0x3f80 | 7 mantissa bits = [1,2), minus 1.5, times 2
+void fill_bf16_lcg(std::vector<unsigned short>& h, unsigned x) {
+  for (auto& v : h) {
+    x = x * 1664525u + 1013904223u;
+    const unsigned m = (x >> 9) & 0x7f, s = (x >> 31) << 15, ex = 0x3e80u + (((x >> 20) & 1) << 7);
+    v = (unsigned short)(s | ex | m);
+  }
+}
+
+// The timing protocol of the _ms hooks: three warm-up launches, then events around `iters` launches; *ms_out = ms per launch.
+template <typename Launch>
+int time_launches(const char* what, int iters, Launch launch, float* ms_out) {
+  hipEvent_t a, b;
+  (void)hipEventCreate(&a);
+  (void)hipEventCreate(&b);
+  hipError_t le = hipSuccess;
+  for (int i = 0; i < 3 && le == hipSuccess; ++i) le = launch();
+  (void)hipEventRecord(a, 0);
+  for (int i = 0; i < iters && le == hipSuccess; ++i) le = launch();
+  (void)hipEventRecord(b, 0);
+  hipError_t se = hipEventSynchronize(b);
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, a, b);
+  (void)hipEventDestroy(a);
+  (void)hipEventDestroy(b);
+  if (le != hipSuccess || se != hipSuccess) {
+    set_error("debug %s failed: %s", what, hipGetErrorString(le != hipSuccess ? le : se));
+    return VRAG_ERR_HIP;
+  }
+  *ms_out = ms / iters;
+  return VRAG_OK;
+}
+
+// The sequences of an attention hook: at least one token each, rows aligned, inside the buffers' rows, no two overlapping.
+int check_sequences(const int32_t* seq_row, const int32_t* seq_len, int n, int rows) {
+  for (int s = 0; s < n; ++s) {
+    const int row = seq_row[s], len = seq_len[s];
+    ARG_CHECK(len >= 1, "seq_len[%d] = %d must be at least 1", s, len);
+    ARG_CHECK(row >= 0 && row % kSeqAlign == 0, "seq_row[%d] = %d must be a non-negative multiple of %d", s, row, kSeqAlign);
+    ARG_CHECK((int64_t)row + len <= rows, "sequence %d (row %d, %d tokens) ends past row %d", s, row, len, rows);
+  }
+  std::vector<int> order(n);
+  for (int s = 0; s < n; ++s) order[s] = s;
+  std::sort(order.begin(), order.end(), [&](int l, int r) { return seq_row[l] < seq_row[r]; });
+  for (int i = 0; i + 1 < n; ++i)
+    ARG_CHECK(seq_row[order[i]] + seq_len[order[i]] <= seq_row[order[i + 1]], "sequences %d and %d overlap", order[i], order[i + 1]);
+  return VRAG_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -29,11 +84,7 @@ int vrag_debug_gemm_ms(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t ite
   ARG_CHECK(epi == EPI_F32 || epi == EPI_BF16 || epi == EPI_RESIDUAL || epi == EPI_GEGLU || epi == EPI_QKV_ROPE ||
                 epi == EPI_F32_GELU || epi == EPI_NONE,
             "unsupported epilogue for the diagnostic");
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
-  HIP_TRY(hipSetDevice(device));
+  if (const int rc = use_device(device); rc != VRAG_OK) return rc;
   const size_t Mp = (size_t)align_up(M, kRowPad);
   DevBuf A, W, outf, outb, q, kk, vt, cs, sn, pos, sat;
   hipError_t e = A.alloc(Mp * K * 2);
@@ -51,15 +102,9 @@ int vrag_debug_gemm_ms(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t ite
     set_error("debug gemm allocation failed: %s", hipGetErrorString(e));
     return VRAG_ERR_HIP;
   }
-  // pseudo-random bf16 operands in [-1, 1): 0x3f80 | 7 mantissa bits = [1,2), minus 1.5, times 2
   {
     std::vector<unsigned short> h(std::max(Mp * K, (size_t)N * K));
-    unsigned x = 12345u;
-    for (auto& v : h) {
-      x = x * 1664525u + 1013904223u;
-      const unsigned m = (x >> 9) & 0x7f, s = (x >> 31) << 15, ex = 0x3e80u + (((x >> 20) & 1) << 7);
-      v = (unsigned short)(s | ex | m);
-    }
+    fill_bf16_lcg(h, 12345u);
     if (getenv("VRAG_DEBUG_GEMM_ZERO")) std::fill(h.begin(), h.end(), (unsigned short)0);   // probe: operand-data dependence of the clock
     (void)hipMemcpy(A.p, h.data(), Mp * K * 2, hipMemcpyHostToDevice);
     (void)hipMemcpy(W.p, h.data(), (size_t)N * K * 2, hipMemcpyHostToDevice);
@@ -100,35 +145,13 @@ int vrag_debug_gemm_ms(int32_t epi, int32_t M, int32_t N, int32_t K, int32_t ite
       (void)hipMemset(outb.p, 0, Mp * N * 2);
     }
   }
-  hipEvent_t a, b;
-  (void)hipEventCreate(&a);
-  (void)hipEventCreate(&b);
-  hipError_t le = hipSuccess;
-  for (int i = 0; i < 3 && le == hipSuccess; ++i) le = launch_gemm((GemmEpi)epi, g, 0);
-  (void)hipEventRecord(a, 0);
-  for (int i = 0; i < iters && le == hipSuccess; ++i) le = launch_gemm((GemmEpi)epi, g, 0);
-  (void)hipEventRecord(b, 0);
-  hipError_t se = hipEventSynchronize(b);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, a, b);
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
-  if (le != hipSuccess || se != hipSuccess) {
-    set_error("debug gemm failed: %s", hipGetErrorString(le != hipSuccess ? le : se));
-    return VRAG_ERR_HIP;
-  }
-  *ms_out = ms / iters;
-  return VRAG_OK;
+  return time_launches("gemm", iters, [&] { return launch_gemm((GemmEpi)epi, g, 0); }, ms_out);
 }
 
 int vrag_debug_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int32_t window, int32_t iters, int32_t device,
                        float* ms_out) {
   ARG_CHECK(ms_out && n_seqs > 0 && S > 0 && S % kSeqAlign == 0 && H % 64 == 0 && iters > 0, "bad arguments");
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
-  HIP_TRY(hipSetDevice(device));
+  if (const int rc = use_device(device); rc != VRAG_OK) return rc;
   const size_t T = (size_t)n_seqs * S, Tp = (size_t)align_up((int)T, kRowPad);
   const int qb = attention_q_block(local != 0);
   std::vector<int> bs, bl, bq;
@@ -153,11 +176,7 @@ int vrag_debug_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int3
   }
   {
     std::vector<unsigned short> h(Tp * H);
-    unsigned x = 777u;
-    for (auto& v : h) {   // pseudo-random bf16 in about [-1, 1), as vrag_debug_gemm_ms
-      x = x * 1664525u + 1013904223u;
-      v = (unsigned short)(((x >> 31) << 15) | (0x3e80u + (((x >> 20) & 1) << 7)) | ((x >> 9) & 0x7f));
-    }
+    fill_bf16_lcg(h, 777u);
     (void)hipMemcpy(q.p, h.data(), Tp * H * 2, hipMemcpyHostToDevice);
     (void)hipMemcpy(k.p, h.data(), Tp * H * 2, hipMemcpyHostToDevice);
     (void)hipMemcpy(vt.p, h.data(), Tp * H * 2, hipMemcpyHostToDevice);
@@ -180,35 +199,13 @@ int vrag_debug_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int3
   ap.window = window;
   ap.op_dtype = getenv("VRAG_DEBUG_GEMM_F16") ? kOpF16 : kOpBf16;
   ap.f16_sat = sat.as<unsigned>();
-  hipEvent_t a, b;
-  (void)hipEventCreate(&a);
-  (void)hipEventCreate(&b);
-  hipError_t le = hipSuccess;
-  for (int i = 0; i < 3 && le == hipSuccess; ++i) le = launch_attention(ap, local != 0, 0);
-  (void)hipEventRecord(a, 0);
-  for (int i = 0; i < iters && le == hipSuccess; ++i) le = launch_attention(ap, local != 0, 0);
-  (void)hipEventRecord(b, 0);
-  hipError_t se = hipEventSynchronize(b);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, a, b);
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
-  if (le != hipSuccess || se != hipSuccess) {
-    set_error("debug attention failed: %s", hipGetErrorString(le != hipSuccess ? le : se));
-    return VRAG_ERR_HIP;
-  }
-  *ms_out = ms / iters;
-  return VRAG_OK;
+  return time_launches("attention", iters, [&] { return launch_attention(ap, local != 0, 0); }, ms_out);
 }
 
 int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, int32_t window, int32_t iters, int32_t flags,
                            int32_t device, float* ms_out) {
   ARG_CHECK(ms_out && n_seqs > 0 && S > 0 && S <= kFusedMaxSeq && S % kSeqAlign == 0 && H % 64 == 0 && iters > 0, "bad arguments");
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
-  HIP_TRY(hipSetDevice(device));
+  if (const int rc = use_device(device); rc != VRAG_OK) return rc;
   const size_t T = (size_t)n_seqs * S, Tp = (size_t)align_up((int)T, kRowPad);
   const int nh = H / 64;
   std::vector<int> row(n_seqs), len(n_seqs, S);
@@ -230,11 +227,7 @@ int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, 
   }
   {
     std::vector<unsigned short> h(std::max(Tp * H, (size_t)3 * H * H));
-    unsigned xs = 777u;
-    for (auto& v : h) {   // pseudo-random bf16 in about [-1, 1), as vrag_debug_gemm_ms
-      xs = xs * 1664525u + 1013904223u;
-      v = (unsigned short)(((xs >> 31) << 15) | (0x3e80u + (((xs >> 20) & 1) << 7)) | ((xs >> 9) & 0x7f));
-    }
+    fill_bf16_lcg(h, 777u);
     (void)hipMemcpy(x.p, h.data(), Tp * H * 2, hipMemcpyHostToDevice);
     (void)hipMemcpy(w.p, h.data(), (size_t)3 * H * H * 2, hipMemcpyHostToDevice);
     std::vector<float> f(std::max(Tp, (size_t)kFusedMaxSeq * 32), 0.05f);
@@ -267,25 +260,7 @@ int vrag_debug_qkv_attn_ms(int32_t local, int32_t n_seqs, int32_t S, int32_t H, 
   f.f16_sat = sat.as<unsigned>();
   f.q_scale = 0.125f * 1.4426950408889634f;
   f.debug_flags = flags;
-  hipEvent_t a, b;
-  (void)hipEventCreate(&a);
-  (void)hipEventCreate(&b);
-  hipError_t le = hipSuccess;
-  for (int i = 0; i < 3 && le == hipSuccess; ++i) le = launch_qkv_attention(f, local != 0, 0);
-  (void)hipEventRecord(a, 0);
-  for (int i = 0; i < iters && le == hipSuccess; ++i) le = launch_qkv_attention(f, local != 0, 0);
-  (void)hipEventRecord(b, 0);
-  hipError_t se = hipEventSynchronize(b);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, a, b);
-  (void)hipEventDestroy(a);
-  (void)hipEventDestroy(b);
-  if (le != hipSuccess || se != hipSuccess) {
-    set_error("debug fused attention failed: %s", hipGetErrorString(le != hipSuccess ? le : se));
-    return VRAG_ERR_HIP;
-  }
-  *ms_out = ms / iters;
-  return VRAG_OK;
+  return time_launches("fused attention", iters, [&] { return launch_qkv_attention(f, local != 0, 0); }, ms_out);
 }
 
 int vrag_debug_attn_run_ex(vrag_debug_attn_args* a, int32_t device) {
@@ -299,19 +274,7 @@ int vrag_debug_attn_run_ex(vrag_debug_attn_args* a, int32_t device) {
   ARG_CHECK(!a->local || a->window <= (1 << 24), "window (%d) above 2^24", a->window);
   ARG_CHECK(device >= 0, "bad device %d", device);
   const int n = a->n_seqs;
-  for (int s = 0; s < n; ++s) {
-    const int row = a->seq_row[s], len = a->seq_len[s];
-    ARG_CHECK(len >= 1, "seq_len[%d] = %d must be at least 1", s, len);
-    ARG_CHECK(row >= 0 && row % kSeqAlign == 0, "seq_row[%d] = %d must be a non-negative multiple of %d", s, row, kSeqAlign);
-    ARG_CHECK((int64_t)row + len <= a->rows, "sequence %d (row %d, %d tokens) ends past row %d", s, row, len, a->rows);
-  }
-  {
-    std::vector<int> order(n);
-    for (int s = 0; s < n; ++s) order[s] = s;
-    std::sort(order.begin(), order.end(), [&](int l, int r) { return a->seq_row[l] < a->seq_row[r]; });
-    for (int i = 0; i + 1 < n; ++i)
-      ARG_CHECK(a->seq_row[order[i]] + a->seq_len[order[i]] <= a->seq_row[order[i + 1]], "sequences %d and %d overlap", order[i], order[i + 1]);
-  }
+  if (const int rc = check_sequences(a->seq_row, a->seq_len, n, a->rows); rc != VRAG_OK) return rc;
   // the q-block descriptors, as vrag_encoder_set_batch builds them (capi.hip): one block per attention_q_block rows of each sequence
   const int qb = attention_q_block(a->local != 0);
   std::vector<int> bs, bl, bq;
@@ -323,11 +286,7 @@ int vrag_debug_attn_run_ex(vrag_debug_attn_args* a, int32_t device) {
     }
   const int n_blocks = (int)bs.size();
   ARG_CHECK(!a->blocks_out || n_blocks <= a->blocks_cap, "blocks_out holds %d descriptors, the launch has %d", a->blocks_cap, n_blocks);
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
-  HIP_TRY(hipSetDevice(device));
+  if (const int rc = use_device(device); rc != VRAG_OK) return rc;
   a->n_blocks = n_blocks;
   if (a->blocks_out)
     for (int b = 0; b < n_blocks; ++b) {
@@ -336,61 +295,25 @@ int vrag_debug_attn_run_ex(vrag_debug_attn_args* a, int32_t device) {
       a->blocks_out[3 * b + 2] = bq[b];
     }
   const size_t R = (size_t)a->rows, H = (size_t)a->H;
-  constexpr size_t kCanary = 4096;   // behind o: the launch must leave it as it was
-  constexpr unsigned char kCanaryByte = 0xA5;
-  DevBuf dq, dk, dv, dout, d_bs, d_bl, d_bq, sat;
-  hipError_t e = dq.alloc(R * H * 2);
-  if (e == hipSuccess) e = dk.alloc(R * H * 2);
-  if (e == hipSuccess) e = dv.alloc(R * H * 2);
-  if (e == hipSuccess) e = dout.alloc(R * H * 2 + kCanary);
-  if (e == hipSuccess) e = d_bs.alloc((size_t)n_blocks * 4);
-  if (e == hipSuccess) e = d_bl.alloc((size_t)n_blocks * 4);
-  if (e == hipSuccess) e = d_bq.alloc((size_t)n_blocks * 4);
-  if (e == hipSuccess) e = sat.alloc(4);
-  if (e == hipSuccess) e = hipMemset(sat.p, 0, 4);
-  if (e == hipSuccess) e = hipMemcpy(dq.p, a->q, R * H * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dk.p, a->k, R * H * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dv.p, a->vt, R * H * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dout.p, a->o, R * H * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(dout.as<char>() + R * H * 2, kCanaryByte, kCanary);
-  if (e == hipSuccess) e = hipMemcpy(d_bs.p, bs.data(), (size_t)n_blocks * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_bl.p, bl.data(), (size_t)n_blocks * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_bq.p, bq.data(), (size_t)n_blocks * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) {
-    AttnParams ap{};
-    ap.q = dq.as<bf16_t>();
-    ap.k = dk.as<bf16_t>();
-    ap.vt = dv.as<bf16_t>();
-    ap.o = dout.as<bf16_t>();
-    ap.blk_seq_start = d_bs.as<int>();
-    ap.blk_seq_len = d_bl.as<int>();
-    ap.blk_q0 = d_bq.as<int>();
-    ap.n_blocks = n_blocks;
-    ap.H = (int)H;
-    ap.nh = (int)H / 64;
-    ap.Tp = (int)R;
-    ap.window = a->window;
-    ap.op_dtype = a->f16 ? kOpF16 : kOpBf16;
-    ap.f16_sat = sat.as<unsigned>();
-    e = launch_attention(ap, a->local != 0, 0);
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  unsigned saturated = 0;
-  if (e == hipSuccess) e = hipMemcpy(&saturated, sat.p, 4, hipMemcpyDeviceToHost);
-  std::vector<unsigned char> canary(kCanary);
-  if (e == hipSuccess) e = hipMemcpy(canary.data(), dout.as<char>() + R * H * 2, kCanary, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(a->o, dout.p, R * H * 2, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) {
-    set_error("debug attention run failed: %s", hipGetErrorString(e));
-    return VRAG_ERR_HIP;
-  }
-  if (std::any_of(canary.begin(), canary.end(), [](unsigned char v) { return v != kCanaryByte; })) {
-    set_error("debug attention run: the launch wrote past the end of o");
-    return VRAG_ERR_HIP;
-  }
-  a->f16_saturated = saturated ? 1 : 0;
-  return VRAG_OK;
+  DbgBufs B;
+  AttnParams ap{};
+  ap.q = B.in<bf16_t>(a->q, R * H, "q");
+  ap.k = B.in<bf16_t>(a->k, R * H, "k");
+  ap.vt = B.in<bf16_t>(a->vt, R * H, "vt");
+  ap.o = B.inout<bf16_t>(a->o, R * H, "o");
+  ap.blk_seq_start = B.in<int>(bs.data(), (size_t)n_blocks, "blk_seq_start");
+  ap.blk_seq_len = B.in<int>(bl.data(), (size_t)n_blocks, "blk_seq_len");
+  ap.blk_q0 = B.in<int>(bq.data(), (size_t)n_blocks, "blk_q0");
+  ap.n_blocks = n_blocks;
+  ap.H = (int)H;
+  ap.nh = (int)H / 64;
+  ap.Tp = (int)R;
+  ap.window = a->window;
+  ap.op_dtype = a->f16 ? kOpF16 : kOpBf16;
+  ap.f16_sat = B.clamp_word(&a->f16_saturated);
+  hipError_t e = B.staged();
+  if (e == hipSuccess) e = launch_attention(ap, a->local != 0, 0);
+  return B.finish("attention", e);
 }
 
 // The equal-length layout of tools/attn_unit.py: n_seqs sequences of S tokens back to back from row 0, zero rows behind them.
@@ -462,107 +385,55 @@ int vrag_debug_gemm_run(vrag_debug_gemm_args* a, int32_t device) {
   if (a->tok_seq)
     for (size_t r = lo; r < lo + (size_t)Mpad; ++r)
       ARG_CHECK(a->tok_seq[r] >= -1 && a->tok_seq[r] < a->n_seqs, "tok_seq[%zu] out of range", r);
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
-  HIP_TRY(hipSetDevice(device));
+  if (const int rc = use_device(device); rc != VRAG_OK) return rc;
 
-  // device copies: every buffer is followed by a 4 KiB canary that the launch must leave as it was
-  constexpr size_t kCanary = 4096;
-  constexpr unsigned char kCanaryByte = 0xA5;
-  struct Buf {
-    const void* host;
-    void* host_out;   // null = input only
-    size_t bytes;
-    const char* name;
-    DevBuf dev;   // bytes + kCanary
-  };
-  const size_t H = (size_t)std::max(a->hidden, 0), NO = epi == EPI_GEGLU ? (size_t)N / 2 : (size_t)N;
-  std::vector<Buf> bufs;
-  auto add = [&](const void* h, void* h_out, size_t bytes, const char* name) -> int {
-    if (!h) return -1;
-    bufs.push_back(Buf{h, h_out, bytes, name, DevBuf()});
-    return (int)bufs.size() - 1;
-  };
-  const int iA = add(a->A, nullptr, R * K * 2, "A");
-  const int iW = add(a->W, nullptr, (size_t)N * K * 2, "W");
-  const int ibias = add(a->bias, nullptr, (size_t)N * 4, "bias");
-  const int ils = add(a->ln_s, nullptr, (size_t)N * 4, "ln_s");
-  const int isin = add(a->stats_in, nullptr, (size_t)(K / 64) * R * 8, "stats_in");
-  const int irmu = add(a->res_mu, nullptr, R * 4, "res_mu");
-  const int irrs = add(a->res_rstd, nullptr, R * 4, "res_rstd");
-  const int irg = add(a->res_g, nullptr, (size_t)N * 4, "res_g");
-  const int irb = add(a->res_b, nullptr, (size_t)N * 4, "res_b");
-  const int icos = add(a->rope_cos, nullptr, (size_t)a->rope_rows * 32 * 4, "rope_cos");
-  const int isn = add(a->rope_sin, nullptr, (size_t)a->rope_rows * 32 * 4, "rope_sin");
-  const int ipos = add(a->pos, nullptr, R * 4, "pos");
-  const int itok = add(a->tok_seq, nullptr, R * 4, "tok_seq");
-  const int ilo_in = add(a->lo_in, a->lo_in == a->lo_out ? a->lo_out : nullptr, R * N, "lo_in");
-  const int iof = add(a->out_f32, a->out_f32, R * N * 4, "out_f32");
-  const int iob = add(a->out_bf16, a->out_bf16, R * NO * 2, "out_bf16");
-  const int iq = add(a->q, a->q, R * H * 2, "q");
-  const int ik = add(a->k, a->k, R * H * 2, "k");
-  const int ivt = add(a->vt, a->vt, H * R * 2, "vt");
-  const int imu = add(a->ln_mu, a->ln_mu, R * 4, "ln_mu");
-  const int irs = add(a->ln_rstd, a->ln_rstd, R * 4, "ln_rstd");
-  const int ish = add(a->ln_shift, a->ln_shift, R * 4, "ln_shift");
-  const int ishp = add(a->ln_shift_prev, a->ln_shift_prev, R * 4, "ln_shift_prev");
-  const int ires = add(a->resid_bf16, a->resid_bf16, R * N * 2, "resid_bf16");
-  const int isp = add(a->stats_part, a->stats_part, (size_t)(N / 64) * R * 8, "stats_part");
-  const int ilo_out = a->lo_out == a->lo_in ? ilo_in : add(a->lo_out, a->lo_out, R * N, "lo_out");
-  const int ispl = add(a->splade_rows, a->splade_rows, (size_t)a->n_seqs * N * 4, "splade_rows");
-  DevBuf sat;   // the launch's fp16 clamp word, reported in f16_saturated
-  hipError_t e = sat.alloc(4);
-  if (e == hipSuccess) e = hipMemset(sat.p, 0, 4);
-  for (Buf& b : bufs) {
-    if (e == hipSuccess) e = b.dev.alloc(b.bytes + kCanary);
-    if (e == hipSuccess) e = hipMemcpy(b.dev.p, b.host, b.bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(b.dev.as<char>() + b.bytes, kCanaryByte, kCanary);
-  }
-  auto dev = [&](int i, size_t offset_bytes) -> char* { return i < 0 ? nullptr : bufs[i].dev.as<char>() + offset_bytes; };
+  // device copies (DbgBufs): an absent optional buffer stays a null pointer; row0 offsets are applied to the typed pointers
+  const size_t H = (size_t)std::max(a->hidden, 0), NO = epi == EPI_GEGLU ? (size_t)N / 2 : (size_t)N, Ns = (size_t)N;
+  const bool one_lo = a->lo_in == a->lo_out;   // the split stream updated in place: one device buffer, copied back
+  DbgBufs B;
   GemmParams g{};
   g.op_dtype = a->f16 ? kOpF16 : kOpBf16;
-  g.f16_sat = sat.as<unsigned>();
   g.M = M;
   g.N = N;
   g.K = K;
   g.act_gelu = a->act_gelu;
-  g.A = (const bf16_t*)dev(iA, lo * K * 2);
-  g.W = (const bf16_t*)dev(iW, 0);
-  g.bias = (const float*)dev(ibias, 0);
-  g.ln_s = (const float*)dev(ils, 0);
-  g.stats_in = (const float*)dev(isin, lo * 8);
   g.stats_ld = (int)R;
   g.fin_eps = a->fin_eps;
-  g.res_mu = (const float*)dev(irmu, lo * 4);
-  g.res_rstd = (const float*)dev(irrs, lo * 4);
-  g.res_g = (const float*)dev(irg, 0);
-  g.res_b = (const float*)dev(irb, 0);
-  g.rope_cos = (const float*)dev(icos, 0);
-  g.rope_sin = (const float*)dev(isn, 0);
-  g.pos = (const int*)dev(ipos, lo * 4);
   g.hidden = (int)H;
   g.vt_ld = (int)R;
   g.q_scale = a->q_scale;
-  g.tok_seq = (const int*)dev(itok, lo * 4);
-  g.splade_rows = (unsigned*)dev(ispl, 0);
-  g.lo_in = (const unsigned char*)dev(ilo_in, lo * N);
-  g.lo_out = (unsigned char*)dev(ilo_out, lo * N);
-  g.out_f32 = (float*)dev(iof, lo * N * 4);
-  g.out_bf16 = (bf16_t*)dev(iob, lo * NO * 2);
-  g.q = (bf16_t*)dev(iq, lo * H * 2);
-  g.k = (bf16_t*)dev(ik, lo * H * 2);
-  g.vt = (bf16_t*)dev(ivt, lo * 2);
-  g.ln_mu = (const float*)dev(imu, lo * 4);
-  g.ln_rstd = (const float*)dev(irs, lo * 4);
-  g.ln_shift = (const float*)dev(ish, lo * 4);
-  g.ln_shift_prev = (float*)dev(ishp, lo * 4);
-  g.resid_bf16 = (bf16_t*)dev(ires, lo * N * 2);
-  g.stats_part = (float*)dev(isp, lo * 8);
-  const int thr = gemm_small_m_threshold(-1);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
+  g.A = B.in<bf16_t>(a->A, R * K, "A") + lo * K;
+  g.W = B.in<bf16_t>(a->W, Ns * K, "W");
+  g.bias = B.in_opt<float>(a->bias, Ns, "bias");
+  g.ln_s = B.in_opt<float>(a->ln_s, Ns, "ln_s");
+  g.stats_in = at(B.in_opt<float>(a->stats_in, (size_t)(K / 64) * R * 2, "stats_in"), lo * 2);
+  g.res_mu = at(B.in_opt<float>(a->res_mu, R, "res_mu"), lo);
+  g.res_rstd = at(B.in_opt<float>(a->res_rstd, R, "res_rstd"), lo);
+  g.res_g = B.in_opt<float>(a->res_g, Ns, "res_g");
+  g.res_b = B.in_opt<float>(a->res_b, Ns, "res_b");
+  g.rope_cos = B.in_opt<float>(a->rope_cos, (size_t)a->rope_rows * 32, "rope_cos");
+  g.rope_sin = B.in_opt<float>(a->rope_sin, (size_t)a->rope_rows * 32, "rope_sin");
+  g.pos = at(B.in_opt<int>(a->pos, R, "pos"), lo);
+  g.tok_seq = at(B.in_opt<int>(a->tok_seq, R, "tok_seq"), lo);
+  unsigned char* lo_in = one_lo ? B.inout_opt<unsigned char>(a->lo_out, R * Ns, "lo_in") : B.in_opt<unsigned char>(a->lo_in, R * Ns, "lo_in");
+  g.lo_in = at(lo_in, lo * Ns);
+  g.out_f32 = at(B.inout_opt<float>(a->out_f32, R * Ns, "out_f32"), lo * Ns);
+  g.out_bf16 = at(B.inout_opt<bf16_t>(a->out_bf16, R * NO, "out_bf16"), lo * NO);
+  g.q = at(B.inout_opt<bf16_t>(a->q, R * H, "q"), lo * H);
+  g.k = at(B.inout_opt<bf16_t>(a->k, R * H, "k"), lo * H);
+  g.vt = at(B.inout_opt<bf16_t>(a->vt, H * R, "vt"), lo);
+  g.ln_mu = at(B.inout_opt<float>(a->ln_mu, R, "ln_mu"), lo);
+  g.ln_rstd = at(B.inout_opt<float>(a->ln_rstd, R, "ln_rstd"), lo);
+  g.ln_shift = at(B.inout_opt<float>(a->ln_shift, R, "ln_shift"), lo);
+  g.ln_shift_prev = at(B.inout_opt<float>(a->ln_shift_prev, R, "ln_shift_prev"), lo);
+  g.resid_bf16 = at(B.inout_opt<bf16_t>(a->resid_bf16, R * Ns, "resid_bf16"), lo * Ns);
+  g.stats_part = at(B.inout_opt<float>(a->stats_part, (size_t)(N / 64) * R * 2, "stats_part"), lo * 2);
+  g.lo_out = at(one_lo ? lo_in : B.inout_opt<unsigned char>(a->lo_out, R * Ns, "lo_out"), lo * Ns);
+  g.splade_rows = B.inout_opt<unsigned>(a->splade_rows, (size_t)a->n_seqs * Ns, "splade_rows");
+  g.f16_sat = B.clamp_word(&a->f16_saturated);
+  hipError_t e = B.staged();
   if (e == hipSuccess) {
+    const int thr = gemm_small_m_threshold(-1);
     if (a->small_rows >= 0) gemm_small_m_threshold(a->small_rows);
     e = launch_gemm((GemmEpi)epi, g, 0);
     const GemmConfig c = gemm_last_config();
@@ -570,28 +441,7 @@ int vrag_debug_gemm_run(vrag_debug_gemm_args* a, int32_t device) {
     const int32_t cfg[7] = {c.bm, c.bn, c.wm, c.wn, c.ns, c.hw, c.kch};
     std::memcpy(a->config, cfg, sizeof(cfg));
   }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  unsigned saturated = 0;
-  if (e == hipSuccess) e = hipMemcpy(&saturated, sat.p, 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) a->f16_saturated = saturated ? 1 : 0;
-  std::vector<unsigned char> canary(kCanary);
-  const char* clobbered = nullptr;
-  for (Buf& b : bufs) {
-    if (e != hipSuccess) break;
-    e = hipMemcpy(canary.data(), b.dev.as<char>() + b.bytes, kCanary, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && !clobbered && std::any_of(canary.begin(), canary.end(), [](unsigned char v) { return v != kCanaryByte; }))
-      clobbered = b.name;
-    if (e == hipSuccess && b.host_out) e = hipMemcpy(b.host_out, b.dev.p, b.bytes, hipMemcpyDeviceToHost);
-  }
-  if (e != hipSuccess) {
-    set_error("debug gemm run failed: %s", hipGetErrorString(e));
-    return VRAG_ERR_HIP;
-  }
-  if (clobbered) {
-    set_error("debug gemm run: the launch wrote past the end of %s", clobbered);
-    return VRAG_ERR_HIP;
-  }
-  return VRAG_OK;
+  return B.finish("gemm", e);
 }
 
 int vrag_debug_pack_groups(const int32_t* seq_row, const int32_t* seq_len, int32_t n, int32_t packer, int32_t* out) {
@@ -614,25 +464,14 @@ int vrag_debug_qkv_attn_run(vrag_debug_qkv_attn_args* a, int32_t device) {
   ARG_CHECK(a->debug_flags == 0 || a->debug_flags == 32, "debug_flags (%d) must be 0 or 32", a->debug_flags);
   ARG_CHECK(device >= 0, "bad device %d", device);
   const int n = a->n_seqs;
+  if (const int rc = check_sequences(a->seq_row, a->seq_len, n, a->rows); rc != VRAG_OK) return rc;
   for (int s = 0; s < n; ++s) {
     const int row = a->seq_row[s], len = a->seq_len[s];
-    ARG_CHECK(len >= 1 && len <= kFusedMaxSeq, "seq_len[%d] = %d outside 1..%d", s, len, kFusedMaxSeq);
-    ARG_CHECK(row >= 0 && row % kSeqAlign == 0, "seq_row[%d] = %d must be a non-negative multiple of %d", s, row, kSeqAlign);
+    ARG_CHECK(len <= kFusedMaxSeq, "seq_len[%d] = %d outside 1..%d", s, len, kFusedMaxSeq);
     // a wave reads 64 whole token rows, whatever its sequence's length
     ARG_CHECK((int64_t)row + 64 * ((len + 63) / 64) <= a->rows, "sequence %d (row %d, %d tokens): its last wave reads past row %d", s, row, len, a->rows);
   }
-  {
-    std::vector<int> order(n);
-    for (int s = 0; s < n; ++s) order[s] = s;
-    std::sort(order.begin(), order.end(), [&](int l, int r) { return a->seq_row[l] < a->seq_row[r]; });
-    for (int i = 0; i + 1 < n; ++i)
-      ARG_CHECK(a->seq_row[order[i]] + a->seq_len[order[i]] <= a->seq_row[order[i + 1]], "sequences %d and %d overlap", order[i], order[i + 1]);
-  }
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
-  HIP_TRY(hipSetDevice(device));
+  if (const int rc = use_device(device); rc != VRAG_OK) return rc;
   const size_t R = (size_t)a->rows, H = (size_t)a->H;
   const bool fold = a->ln_mu != nullptr;
   std::vector<int4> groups((size_t)n * 8);
@@ -641,77 +480,36 @@ int vrag_debug_qkv_attn_run(vrag_debug_qkv_attn_args* a, int32_t device) {
   std::memcpy(a->groups_out, groups.data(), (size_t)n_groups * 8 * sizeof(int4));
   a->n_groups = n_groups;
 
-  constexpr size_t kCanary = 4096;   // behind o: the launch must leave it as it was
-  constexpr unsigned char kCanaryByte = 0xA5;
-  DevBuf x, w, wh, ls, lsh, mu, rstd, cs, sn, o, d_groups, sat;
-  hipError_t e = x.alloc(R * H * 2);
-  if (e == hipSuccess) e = w.alloc(3 * H * H * 2);
-  if (e == hipSuccess) e = wh.alloc(3 * H * H * 2);
-  if (e == hipSuccess) e = cs.alloc((size_t)a->rope_rows * 32 * 4);
-  if (e == hipSuccess) e = sn.alloc((size_t)a->rope_rows * 32 * 4);
-  if (e == hipSuccess) e = o.alloc(R * H * 2 + kCanary);
-  if (e == hipSuccess) e = d_groups.alloc((size_t)n_groups * 8 * sizeof(int4));
-  if (e == hipSuccess) e = sat.alloc(4);
-  if (e == hipSuccess) e = hipMemset(sat.p, 0, 4);
-  if (e == hipSuccess) e = hipMemcpy(x.p, a->x, R * H * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(w.p, a->w, 3 * H * H * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(cs.p, a->rope_cos, (size_t)a->rope_rows * 32 * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(sn.p, a->rope_sin, (size_t)a->rope_rows * 32 * 4, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(o.p, a->o, R * H * 2, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(o.as<char>() + R * H * 2, kCanaryByte, kCanary);
-  if (e == hipSuccess) e = hipMemcpy(d_groups.p, groups.data(), (size_t)n_groups * 8 * sizeof(int4), hipMemcpyHostToDevice);
-  if (fold) {
-    if (e == hipSuccess) e = ls.alloc(3 * H * 4);
-    if (e == hipSuccess) e = lsh.alloc((3 * H + 64) * 4);   // the kernel's 256-float DMA of a head's 192 sums reads 64 floats on (capi.hip)
-    if (e == hipSuccess) e = mu.alloc(R * 4);
-    if (e == hipSuccess) e = rstd.alloc(R * 4);
-    if (e == hipSuccess) e = hipMemset(lsh.p, 0, (3 * H + 64) * 4);
-    if (e == hipSuccess) e = hipMemcpy(ls.p, a->ln_s, 3 * H * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(mu.p, a->ln_mu, R * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(rstd.p, a->ln_rstd, R * 4, hipMemcpyHostToDevice);
-  }
-  if (e == hipSuccess) e = permute_qkv_heads(w.as<bf16_t>(), fold ? ls.as<float>() : nullptr, (int)H, a->nh, wh.as<bf16_t>(),
-                                             fold ? lsh.as<float>() : nullptr, nullptr);
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) {
-    QkvAttnParams f{};
-    f.x = x.as<bf16_t>();
-    f.w = wh.as<bf16_t>();
-    f.ln_mu = fold ? mu.as<float>() : nullptr;
-    f.ln_rstd = fold ? rstd.as<float>() : nullptr;
-    f.ln_s = fold ? lsh.as<float>() : nullptr;
-    f.rope_cos = cs.as<float>();
-    f.rope_sin = sn.as<float>();
-    f.rope_rows = a->rope_rows;
-    f.o = o.as<bf16_t>();
-    f.groups = d_groups.as<int4>();
-    f.n_groups = n_groups;
-    f.H = (int)H;
-    f.nh = a->nh;
-    f.Tp = (int)R;
-    f.window = a->window;
-    f.op_dtype = a->f16 ? kOpF16 : kOpBf16;
-    f.q_scale = a->q_scale;
-    f.debug_flags = a->debug_flags;
-    f.f16_sat = sat.as<unsigned>();
-    e = launch_qkv_attention(f, a->local != 0, 0);
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  unsigned saturated = 0;
-  if (e == hipSuccess) e = hipMemcpy(&saturated, sat.p, 4, hipMemcpyDeviceToHost);
-  std::vector<unsigned char> canary(kCanary);
-  if (e == hipSuccess) e = hipMemcpy(canary.data(), o.as<char>() + R * H * 2, kCanary, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(a->o, o.p, R * H * 2, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) {
-    set_error("debug fused attention run failed: %s", hipGetErrorString(e));
-    return VRAG_ERR_HIP;
-  }
-  if (std::any_of(canary.begin(), canary.end(), [](unsigned char v) { return v != kCanaryByte; })) {
-    set_error("debug fused attention run: the launch wrote past the end of o");
-    return VRAG_ERR_HIP;
-  }
-  a->f16_saturated = saturated ? 1 : 0;
-  return VRAG_OK;
+  DbgBufs B;
+  bf16_t* w = B.in<bf16_t>(a->w, 3 * H * H, "w");
+  float* ls = B.in_opt<float>(fold ? a->ln_s : nullptr, 3 * H, "ln_s");
+  bf16_t* wh = B.scratch<bf16_t>(3 * H * H, "wh");
+  float* lsh = fold ? B.scratch<float>(3 * H, "lsh", 64 * 4) : nullptr;   // the kernel's 256-float DMA of a head's 192 sums reads 64 floats on (capi.hip)
+  QkvAttnParams f{};
+  f.x = B.in<bf16_t>(a->x, R * H, "x");
+  f.w = wh;
+  f.ln_mu = B.in_opt<float>(a->ln_mu, R, "ln_mu");
+  f.ln_rstd = B.in_opt<float>(a->ln_rstd, R, "ln_rstd");
+  f.ln_s = lsh;
+  f.rope_cos = B.in<float>(a->rope_cos, (size_t)a->rope_rows * 32, "rope_cos");
+  f.rope_sin = B.in<float>(a->rope_sin, (size_t)a->rope_rows * 32, "rope_sin");
+  f.rope_rows = a->rope_rows;
+  f.o = B.inout<bf16_t>(a->o, R * H, "o");
+  f.groups = B.in<int4>(groups.data(), (size_t)n_groups * 8, "groups");
+  f.n_groups = n_groups;
+  f.H = (int)H;
+  f.nh = a->nh;
+  f.Tp = (int)R;
+  f.window = a->window;
+  f.op_dtype = a->f16 ? kOpF16 : kOpBf16;
+  f.q_scale = a->q_scale;
+  f.debug_flags = a->debug_flags;
+  f.f16_sat = B.clamp_word(&a->f16_saturated);
+  hipError_t e = B.err;
+  if (e == hipSuccess) e = permute_qkv_heads(w, ls, (int)H, a->nh, wh, lsh, nullptr);
+  if (e == hipSuccess) e = B.staged();
+  if (e == hipSuccess) e = launch_qkv_attention(f, a->local != 0, 0);
+  return B.finish("fused attention", e);
 }
 
 int vrag_debug_rows_run(vrag_debug_rows_args* a, int32_t device) {
@@ -773,121 +571,68 @@ int vrag_debug_rows_run(vrag_debug_rows_args* a, int32_t device) {
     ARG_CHECK(a->num_labels >= 1, "num_labels (%d) must be at least 1 where a classifier runs", a->num_labels);
     ARG_CHECK(a->Wc && a->bc, "the classifier needs Wc and bc");
   }
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
-  HIP_TRY(hipSetDevice(device));
+  if (const int rc = use_device(device); rc != VRAG_OK) return rc;
 
-  // device copies: every buffer is followed by a 4 KiB canary that the launch must leave as it was
-  constexpr size_t kCanary = 4096;
-  constexpr unsigned char kCanaryByte = 0xA5;
-  struct Buf {
-    const void* host;
-    void* host_out;   // null = input only
-    size_t bytes;
-    const char* name;
-    DevBuf dev;   // bytes + kCanary
-  };
-  std::vector<Buf> bufs;
-  auto add = [&](const void* h, void* h_out, size_t bytes, const char* name) -> int {
-    if (!h) return -1;
-    bufs.push_back(Buf{h, h_out, bytes, name, DevBuf()});
-    return (int)bufs.size() - 1;
-  };
+  // device copies (DbgBufs): what the chosen launcher does not take, and an absent optional buffer, stay null pointers
   const size_t R = (size_t)rows, OR = (size_t)a->out_rows, Hs = (size_t)H, L = (size_t)std::max(a->num_labels, 0);
   const size_t out_cols = (embed || ln || (range && a->mode != 0)) ? Hs : L;
-  const bool alias = ln && a->alias_f32;
-  const int ih = embed ? -1 : add(a->h, alias ? a->h : nullptr, (size_t)a->h_rows * Hs * 4, "h");
-  const int iids = embed ? add(a->ids, nullptr, R * 4, "ids") : -1;
-  const int iE = embed ? add(a->E, nullptr, (size_t)a->vocab * Hs * 4, "E") : -1;
-  const int iP = embed ? add(a->P, nullptr, (size_t)std::max(a->n_pos, 0) * Hs * 4, "P") : -1;
-  const int ipos = embed ? add(a->pos, nullptr, R * 4, "pos") : -1;
-  const int ityp = embed ? add(a->type_row, nullptr, (size_t)std::max(a->n_types, 0) * Hs * 4, "type_row") : -1;
-  const int itid = embed ? add(a->type_ids, nullptr, R * 4, "type_ids") : -1;
-  const int iw = add(a->w, nullptr, Hs * 4, "w");
-  const int ibias = add(a->bias, nullptr, Hs * 4, "bias");
-  const int istart = range ? add(a->start, nullptr, R * 4, "start") : -1;
-  const int iend = range ? add(a->end, nullptr, R * 4, "end") : -1;
-  const int ifirst = pooler ? add(a->first_row, nullptr, R * 4, "first_row") : -1;
-  const int isrow = seqh ? add(a->seq_row, nullptr, R * 4, "seq_row") : -1;
-  const int islen = seqh ? add(a->seq_len, nullptr, R * 4, "seq_len") : -1;
-  const int iWp = pooler ? add(a->Wp, nullptr, Hs * Hs * 4, "Wp") : -1;
-  const int ibp = pooler ? add(a->bp, nullptr, Hs * 4, "bp") : -1;
-  const int iWd = seqh ? add(a->WdT, nullptr, Hs * Hs * 4, "WdT") : -1;
-  const int ibd = seqh ? add(a->bd, nullptr, Hs * 4, "bd") : -1;
-  const int iwn = seqh ? add(a->wn, nullptr, Hs * 4, "wn") : -1;
-  const int ibn = seqh ? add(a->bn, nullptr, Hs * 4, "bn") : -1;
-  const int iWc = add(a->Wc, nullptr, L * Hs * 4, "Wc");
-  const int ibc = add(a->bc, nullptr, L * 4, "bc");
-  const int iof = add(a->out_f32, a->out_f32, OR * out_cols * 4, "out_f32");
-  const int io16 = (embed || ln) ? add(a->out16, a->out16, OR * (ln && a->split3 ? 3 * Hs : Hs) * 2, "out16") : -1;
-  const int ilo = ln ? add(a->out_lo, a->out_lo, OR * Hs * 2, "out_lo") : -1;
-  const int imean = ln ? add(a->row_mean, a->row_mean, OR * 4, "row_mean") : -1;
-  const int ipool = seqh ? add(a->pooled, a->pooled, OR * Hs * 4, "pooled") : -1;
-  DevBuf sat;   // the launch's fp16 clamp word, reported in f16_saturated
-  hipError_t e = sat.alloc(4);
-  if (e == hipSuccess) e = hipMemset(sat.p, 0, 4);
-  for (Buf& b : bufs) {
-    if (e == hipSuccess) e = b.dev.alloc(b.bytes + kCanary);
-    if (e == hipSuccess && b.bytes) e = hipMemcpy(b.dev.p, b.host, b.bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(b.dev.as<char>() + b.bytes, kCanaryByte, kCanary);
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    set_error("debug rows run: staging failed: %s", hipGetErrorString(e));
-    return VRAG_ERR_HIP;
-  }
-  auto fp = [&](int i) -> float* { return i < 0 ? nullptr : bufs[i].dev.as<float>(); };
-  auto ip = [&](int i) -> int* { return i < 0 ? nullptr : bufs[i].dev.as<int>(); };
-  auto hp = [&](int i) -> bf16_t* { return i < 0 ? nullptr : bufs[i].dev.as<bf16_t>(); };
+  const bool alias = ln && a->alias_f32;   // h is the fp32 output too: in / out
+  DbgBufs B;
+  float* h = embed ? nullptr : alias ? B.inout<float>(a->h, (size_t)a->h_rows * Hs, "h") : B.in<float>(a->h, (size_t)a->h_rows * Hs, "h");
+  int* ids = embed ? B.in_opt<int>(a->ids, R, "ids") : nullptr;
+  float* E = embed ? B.in_opt<float>(a->E, (size_t)a->vocab * Hs, "E") : nullptr;
+  float* P = embed ? B.in_opt<float>(a->P, (size_t)std::max(a->n_pos, 0) * Hs, "P") : nullptr;
+  int* pos = embed ? B.in_opt<int>(a->pos, R, "pos") : nullptr;
+  float* type_row = embed ? B.in_opt<float>(a->type_row, (size_t)std::max(a->n_types, 0) * Hs, "type_row") : nullptr;
+  int* type_ids = embed ? B.in_opt<int>(a->type_ids, R, "type_ids") : nullptr;
+  float* w = B.in_opt<float>(a->w, Hs, "w");
+  float* bias = B.in_opt<float>(a->bias, Hs, "bias");
+  int* start = range ? B.in_opt<int>(a->start, R, "start") : nullptr;
+  int* end = range ? B.in_opt<int>(a->end, R, "end") : nullptr;
+  int* first_row = pooler ? B.in_opt<int>(a->first_row, R, "first_row") : nullptr;
+  int* seq_row = seqh ? B.in_opt<int>(a->seq_row, R, "seq_row") : nullptr;
+  int* seq_len = seqh ? B.in_opt<int>(a->seq_len, R, "seq_len") : nullptr;
+  float* Wp = pooler ? B.in_opt<float>(a->Wp, Hs * Hs, "Wp") : nullptr;
+  float* bp = pooler ? B.in_opt<float>(a->bp, Hs, "bp") : nullptr;
+  float* WdT = seqh ? B.in_opt<float>(a->WdT, Hs * Hs, "WdT") : nullptr;
+  float* bd = seqh ? B.in_opt<float>(a->bd, Hs, "bd") : nullptr;
+  float* wn = seqh ? B.in_opt<float>(a->wn, Hs, "wn") : nullptr;
+  float* bn = seqh ? B.in_opt<float>(a->bn, Hs, "bn") : nullptr;
+  float* Wc = B.in_opt<float>(a->Wc, L * Hs, "Wc");
+  float* bc = B.in_opt<float>(a->bc, L, "bc");
+  float* out_f32 = B.inout_opt<float>(a->out_f32, OR * out_cols, "out_f32");
+  bf16_t* out16 = (embed || ln) ? B.inout_opt<bf16_t>(a->out16, OR * (ln && a->split3 ? 3 * Hs : Hs), "out16") : nullptr;
+  bf16_t* out_lo = ln ? B.inout_opt<bf16_t>(a->out_lo, OR * Hs, "out_lo") : nullptr;
+  float* row_mean = ln ? B.inout_opt<float>(a->row_mean, OR, "row_mean") : nullptr;
+  float* pooled = seqh ? B.inout_opt<float>(a->pooled, OR * Hs, "pooled") : nullptr;
+  unsigned* sat = B.clamp_word(&a->f16_saturated);
+  if (B.staged() != hipSuccess) return B.finish("rows", B.err);
   const int dt = a->f16 ? kOpF16 : kOpBf16;
-  unsigned* satp = a->no_sat ? nullptr : sat.as<unsigned>();
+  unsigned* satp = a->no_sat ? nullptr : sat;
   hipError_t le = hipSuccess;
   switch (op) {
     case VRAG_DEBUG_ROWS_EMBED_LN:
-      le = launch_embed_ln(ip(iids), fp(iE), fp(iw), a->eps, H, rows, fp(iof), hp(io16), 0, fp(iP), ip(ipos), fp(ityp), fp(ibias), ip(itid), dt, satp);
+      le = launch_embed_ln(ids, E, w, a->eps, H, rows, out_f32, out16, 0, P, pos, type_row, bias, type_ids, dt, satp);
       break;
     case VRAG_DEBUG_ROWS_LAYERNORM:
-      le = launch_layernorm(fp(ih), fp(iw), a->eps, H, rows, hp(io16), alias ? fp(ih) : fp(iof), 0, fp(ibias), fp(imean), dt, hp(ilo), a->gelu_first,
-                            a->split3, satp);
+      le = launch_layernorm(h, w, a->eps, H, rows, out16, alias ? h : out_f32, 0, bias, row_mean, dt, out_lo, a->gelu_first, a->split3, satp);
       break;
     case VRAG_DEBUG_ROWS_RANGE_POOL:
-      le = launch_range_pool(fp(ih), fp(iw), a->eps, H, ip(istart), ip(iend), rows, a->mode, fp(iWc), fp(ibc), a->num_labels, fp(iof), 0);
+      le = launch_range_pool(h, w, a->eps, H, start, end, rows, a->mode, Wc, bc, a->num_labels, out_f32, 0);
       break;
     case VRAG_DEBUG_ROWS_LN_CLASSIFIER:
-      le = launch_ln_classifier(fp(ih), fp(iw), a->eps, H, rows, fp(iWc), fp(ibc), a->num_labels, fp(iof), 0, fp(ibias), a->gelu_first);
+      le = launch_ln_classifier(h, w, a->eps, H, rows, Wc, bc, a->num_labels, out_f32, 0, bias, a->gelu_first);
       break;
     case VRAG_DEBUG_ROWS_POOLER_CLASSIFIER:
-      le = launch_pooler_classifier(fp(ih), H, ip(ifirst), rows, fp(iWp), fp(ibp), fp(iWc), fp(ibc), a->num_labels, fp(iof), 0);
+      le = launch_pooler_classifier(h, H, first_row, rows, Wp, bp, Wc, bc, a->num_labels, out_f32, 0);
       break;
     default:
-      le = launch_seq_head(fp(ih), fp(iw), a->eps, H, ip(isrow), ip(islen), rows, a->mode, fp(ipool), fp(iWd), fp(ibd), fp(iwn), fp(ibn), fp(iWc),
-                           fp(ibc), a->num_labels, fp(iof), 0);
+      le = launch_seq_head(h, w, a->eps, H, seq_row, seq_len, rows, a->mode, pooled, WdT, bd, wn, bn, Wc, bc, a->num_labels, out_f32, 0);
       break;
   }
   a->launch_status = (int32_t)le;
-  e = hipDeviceSynchronize();
-  unsigned saturated = 0;
-  if (e == hipSuccess) e = hipMemcpy(&saturated, sat.p, 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) a->f16_saturated = saturated ? 1 : 0;
-  std::vector<unsigned char> canary(kCanary);
-  const char* clobbered = nullptr;
-  for (Buf& b : bufs) {
-    if (e != hipSuccess) break;
-    e = hipMemcpy(canary.data(), b.dev.as<char>() + b.bytes, kCanary, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && !clobbered && std::any_of(canary.begin(), canary.end(), [](unsigned char v) { return v != kCanaryByte; }))
-      clobbered = b.name;
-    if (e == hipSuccess && b.host_out && b.bytes) e = hipMemcpy(b.host_out, b.dev.p, b.bytes, hipMemcpyDeviceToHost);
-  }
-  if (e != hipSuccess) {
-    set_error("debug rows run failed: %s", hipGetErrorString(e));
-    return VRAG_ERR_HIP;
-  }
-  if (clobbered) {
-    set_error("debug rows run: the launch wrote past the end of %s", clobbered);
-    return VRAG_ERR_HIP;
-  }
+  // the device is synchronised and the canaries are checked whatever the launcher said: its refusal must have touched nothing
+  if (const int rc = B.finish("rows", hipSuccess); rc != VRAG_OK) return rc;
   if (le != hipSuccess) {
     set_error("debug rows run: the launcher returned %s", hipGetErrorString(le));
     return le == hipErrorInvalidValue ? VRAG_ERR_INVALID : VRAG_ERR_HIP;
@@ -954,137 +699,73 @@ int vrag_debug_glue_run(vrag_debug_glue_args* a, int32_t device) {
     ARG_CHECK(a->nh >= 1 && a->nh <= 64 && a->H == 64 * a->nh, "H (%d) must be 64 * nh (%d), nh in 1..64", a->H, a->nh);
     ARG_CHECK(a->out_rows >= 3 * a->H && a->out_rows <= kMax, "out_rows (%d) below 3 H (%d)", a->out_rows, 3 * a->H);
   }
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
-  HIP_TRY(hipSetDevice(device));
+  if (const int rc = use_device(device); rc != VRAG_OK) return rc;
 
-  // device copies: every buffer is followed by a 4 KiB canary that the launch must leave as it was
-  constexpr size_t kCanary = 4096;
-  constexpr unsigned char kCanaryByte = 0xA5;
-  struct Buf {
-    const void* host;
-    void* host_out;   // null = input only
-    size_t bytes;
-    const char* name;
-    DevBuf dev;   // bytes + kCanary
-  };
-  std::vector<Buf> bufs;
-  auto add = [&](const void* h, void* h_out, size_t bytes, const char* name) -> int {
-    if (!h) return -1;
-    bufs.push_back(Buf{h, h_out, bytes, name, DevBuf()});
-    return (int)bufs.size() - 1;
-  };
+  // device copies (DbgBufs), staged by the case that launches on them; an absent optional buffer stays a null pointer
   const size_t OR = (size_t)a->out_rows, cols = (size_t)a->cols, ld = (size_t)a->ld, Hs = (size_t)a->H;
-  int isrc = -1, iscale = -1, idst = -1, ilo = -1, isum = -1, ipart = -1, imu = -1, irstd = -1, ishin = -1, ishout = -1, iprev = -1;
-  int ipacked = -1, isrow = -1, issrc = -1, islen = -1, iids = -1, ipos = -1, itok = -1, icnt = -1, iidx = -1, ival = -1;
-  int iw = -1, is = -1, iwo = -1, iso = -1;
-  if (cvt || split3) {
-    isrc = add(a->src, nullptr, (size_t)a->rows_src * cols * 4, "src");
-    idst = add(a->dst, a->dst, OR * (split3 ? 3 * cols : cols) * 2, "dst");
-  }
-  if (cvt) {
-    iscale = add(a->col_scale, nullptr, cols * 4, "col_scale");
-    ilo = add(a->dst_lo, a->dst_lo, OR * cols * 2, "dst_lo");
-    isum = add(a->row_sum, a->row_sum, OR * 4, "row_sum");
-  }
-  if (fin) {
-    ipart = add(a->part, nullptr, (size_t)a->np * ld * 2 * 4, "part");
-    imu = add(a->mu, a->mu, ld * 4, "mu");
-    irstd = add(a->rstd, a->rstd, ld * 4, "rstd");
-    ishin = add(a->shift_in, nullptr, ld * 4, "shift_in");
-    ishout = add(a->shift_out, a->shift_out, ld * 4, "shift_out");
-    iprev = add(a->shift_prev, a->shift_prev, ld * 4, "shift_prev");
-  }
-  if (pack) {
-    const size_t n = (size_t)a->n_seqs;
-    ipacked = add(a->packed, nullptr, (size_t)a->n_packed * 4, "packed");
-    isrow = add(a->seq_row, nullptr, n * 4, "seq_row");
-    issrc = add(a->seq_src, nullptr, n * 4, "seq_src");
-    islen = add(a->seq_len, nullptr, n * 4, "seq_len");
-    iids = add(a->ids, a->ids, OR * 4, "ids");
-    ipos = add(a->pos, a->pos, OR * 4, "pos");
-    itok = add(a->tok_seq, a->tok_seq, OR * 4, "tok_seq");
-  }
-  if (compact) {
-    isrc = add(a->src, nullptr, (size_t)a->rows * ld * 4, "src");
-    icnt = add(a->counts, a->counts, OR * 4, "counts");
-    iidx = add(a->idx, a->idx, OR * (size_t)a->cap * 4, "idx");
-    ival = add(a->val, a->val, OR * (size_t)a->cap * 4, "val");
-  }
-  if (permute) {
-    iw = add(a->w, nullptr, 3 * Hs * Hs * 2, "w");
-    is = add(a->s, nullptr, 3 * Hs * 4, "s");
-    iwo = add(a->w_out, a->w_out, OR * Hs * 2, "w_out");
-    iso = add(a->s_out, a->s_out, OR * 4, "s_out");
-  }
-  DevBuf sat;   // the launch's fp16 clamp word, reported in f16_saturated
-  hipError_t e = sat.alloc(4);
-  if (e == hipSuccess) e = hipMemset(sat.p, 0, 4);
-  for (Buf& b : bufs) {
-    if (e == hipSuccess) e = b.dev.alloc(b.bytes + kCanary);
-    if (e == hipSuccess && b.bytes) e = hipMemcpy(b.dev.p, b.host, b.bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(b.dev.as<char>() + b.bytes, kCanaryByte, kCanary);
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    set_error("debug glue run: staging failed: %s", hipGetErrorString(e));
-    return VRAG_ERR_HIP;
-  }
-  auto fp = [&](int i) -> float* { return i < 0 ? nullptr : bufs[i].dev.as<float>(); };
-  auto ip = [&](int i) -> int* { return i < 0 ? nullptr : bufs[i].dev.as<int>(); };
-  auto hp = [&](int i) -> bf16_t* { return i < 0 ? nullptr : bufs[i].dev.as<bf16_t>(); };
   const int dt = a->f16 ? kOpF16 : kOpBf16;
+  DbgBufs B;
+  unsigned* sat = B.clamp_word(&a->f16_saturated);
   switch (op) {
-    case VRAG_DEBUG_GLUE_CVT_ROWS:
-      launch_cvt_rows(dt, dim3(a->rows_dst), 0, fp(isrc), hp(idst), a->rows_dst, a->rows_src, a->cols, a->interleave ? a->I : 0,
-                      fp(iscale), fp(isum), hp(ilo), sat.as<unsigned>());
-      break;
-    case VRAG_DEBUG_GLUE_CVT_SPLIT3:
-      launch_cvt_split3(dt, 0, fp(isrc), hp(idst), a->rows_dst, a->rows_src, a->cols, sat.as<unsigned>());
-      break;
-    case VRAG_DEBUG_GLUE_LN_STATS_FINALIZE: {
-      const int r0 = a->row0;   // as the encoder addresses a micro-batch
-      float* prev = fp(iprev);
-      launch_ln_stats_finalize(0, fp(ipart) + (size_t)r0 * 2, a->ld, a->np, a->H, a->eps, a->rows, fp(imu) + r0, fp(irstd) + r0,
-                               a->alias_shift ? fp(ishout) + r0 : (ishin < 0 ? (const float*)nullptr : fp(ishin) + r0), fp(ishout) + r0,
-                               prev ? prev + r0 : nullptr);
+    case VRAG_DEBUG_GLUE_CVT_ROWS: {
+      const float* src = B.in<float>(a->src, (size_t)a->rows_src * cols, "src");
+      bf16_t* dst = B.inout<bf16_t>(a->dst, OR * cols, "dst");
+      const float* scale = B.in_opt<float>(a->col_scale, cols, "col_scale");
+      bf16_t* dst_lo = B.inout_opt<bf16_t>(a->dst_lo, OR * cols, "dst_lo");
+      float* row_sum = B.inout_opt<float>(a->row_sum, OR, "row_sum");
+      if (B.staged() == hipSuccess)
+        launch_cvt_rows(dt, dim3(a->rows_dst), 0, src, dst, a->rows_dst, a->rows_src, a->cols, a->interleave ? a->I : 0, scale, row_sum, dst_lo, sat);
       break;
     }
-    case VRAG_DEBUG_GLUE_PACK_LAYOUT:
-      launch_pack_layout(0, ip(ipacked), ip(isrow), ip(issrc), ip(islen), a->n_seqs, a->rows, a->pad_id, ip(iids), ip(ipos), ip(itok));
+    case VRAG_DEBUG_GLUE_CVT_SPLIT3: {
+      const float* src = B.in<float>(a->src, (size_t)a->rows_src * cols, "src");
+      bf16_t* dst = B.inout<bf16_t>(a->dst, OR * 3 * cols, "dst");
+      if (B.staged() == hipSuccess) launch_cvt_split3(dt, 0, src, dst, a->rows_dst, a->rows_src, a->cols, sat);
       break;
-    case VRAG_DEBUG_GLUE_SPLADE_COMPACT:
-      launch_splade_compact(0, fp(isrc), a->rows, a->V, a->ld, a->thr, a->cap, ip(icnt), ip(iidx), fp(ival));
+    }
+    case VRAG_DEBUG_GLUE_LN_STATS_FINALIZE: {
+      const size_t r0 = (size_t)a->row0;   // as the encoder addresses a micro-batch
+      const float* part = B.in<float>(a->part, (size_t)a->np * ld * 2, "part");
+      float* mu = B.inout<float>(a->mu, ld, "mu");
+      float* rstd = B.inout<float>(a->rstd, ld, "rstd");
+      const float* shift_in = B.in_opt<float>(a->shift_in, ld, "shift_in");
+      float* shift_out = B.inout<float>(a->shift_out, ld, "shift_out");
+      float* prev = B.inout_opt<float>(a->shift_prev, ld, "shift_prev");
+      if (B.staged() == hipSuccess)
+        launch_ln_stats_finalize(0, part + r0 * 2, a->ld, a->np, a->H, a->eps, a->rows, mu + r0, rstd + r0,
+                                 a->alias_shift ? shift_out + r0 : at(shift_in, r0), shift_out + r0, at(prev, r0));
       break;
-    default:
-      (void)permute_qkv_heads(hp(iw), fp(is), a->H, a->nh, hp(iwo), fp(iso), nullptr);
+    }
+    case VRAG_DEBUG_GLUE_PACK_LAYOUT: {
+      const size_t n = (size_t)a->n_seqs;
+      const int* packed = B.in<int>(a->packed, (size_t)a->n_packed, "packed");
+      const int* seq_row = B.in<int>(a->seq_row, n, "seq_row");
+      const int* seq_src = B.in<int>(a->seq_src, n, "seq_src");
+      const int* seq_len = B.in<int>(a->seq_len, n, "seq_len");
+      int* ids = B.inout<int>(a->ids, OR, "ids");
+      int* pos = B.inout<int>(a->pos, OR, "pos");
+      int* tok_seq = B.inout<int>(a->tok_seq, OR, "tok_seq");
+      if (B.staged() == hipSuccess) launch_pack_layout(0, packed, seq_row, seq_src, seq_len, a->n_seqs, a->rows, a->pad_id, ids, pos, tok_seq);
       break;
+    }
+    case VRAG_DEBUG_GLUE_SPLADE_COMPACT: {
+      const float* src = B.in<float>(a->src, (size_t)a->rows * ld, "src");
+      int* counts = B.inout<int>(a->counts, OR, "counts");
+      int* idx = B.inout<int>(a->idx, OR * (size_t)a->cap, "idx");
+      float* val = B.inout<float>(a->val, OR * (size_t)a->cap, "val");
+      if (B.staged() == hipSuccess) launch_splade_compact(0, src, a->rows, a->V, a->ld, a->thr, a->cap, counts, idx, val);
+      break;
+    }
+    default: {
+      const bf16_t* w = B.in<bf16_t>(a->w, 3 * Hs * Hs, "w");
+      const float* s = B.in_opt<float>(a->s, 3 * Hs, "s");
+      bf16_t* w_out = B.inout<bf16_t>(a->w_out, OR * Hs, "w_out");
+      float* s_out = B.inout_opt<float>(a->s_out, OR, "s_out");
+      if (B.staged() == hipSuccess) (void)permute_qkv_heads(w, s, a->H, a->nh, w_out, s_out, nullptr);
+      break;
+    }
   }
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  unsigned saturated = 0;
-  if (e == hipSuccess) e = hipMemcpy(&saturated, sat.p, 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) a->f16_saturated = saturated ? 1 : 0;
-  std::vector<unsigned char> canary(kCanary);
-  const char* clobbered = nullptr;
-  for (Buf& b : bufs) {
-    if (e != hipSuccess) break;
-    e = hipMemcpy(canary.data(), b.dev.as<char>() + b.bytes, kCanary, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && !clobbered && std::any_of(canary.begin(), canary.end(), [](unsigned char v) { return v != kCanaryByte; }))
-      clobbered = b.name;
-    if (e == hipSuccess && b.host_out && b.bytes) e = hipMemcpy(b.host_out, b.dev.p, b.bytes, hipMemcpyDeviceToHost);
-  }
-  if (e != hipSuccess) {
-    set_error("debug glue run failed: %s", hipGetErrorString(e));
-    return VRAG_ERR_HIP;
-  }
-  if (clobbered) {
-    set_error("debug glue run: the launch wrote past the end of %s", clobbered);
-    return VRAG_ERR_HIP;
-  }
-  return VRAG_OK;
+  return B.finish("glue", B.err != hipSuccess ? B.err : hipGetLastError());   // the launchers return nothing
 }
 
 int vrag_debug_topk_run(vrag_debug_topk_args* a, int32_t device) {
@@ -1175,87 +856,43 @@ int vrag_debug_topk_run(vrag_debug_topk_args* a, int32_t device) {
     ARG_CHECK(a->n >= 1 && a->n <= kMax && (int64_t)a->n * a->nq * a->k <= kMaxElems, "merge: %d lists must be positive and fit the hook", a->n);
   }
   if (tau) ARG_CHECK(a->thr_key && a->thr_score && a->eps && a->cnt && a->ovf, "tau needs thr_key, thr_score, eps, cnt and ovf");
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
-  HIP_TRY(hipSetDevice(device));
+  if (const int rc = use_device(device); rc != VRAG_OK) return rc;
 
-  // device copies: every buffer is followed by a 4 KiB canary that the launch must leave as it was
-  constexpr size_t kCanary = 4096;
-  constexpr unsigned char kCanaryByte = 0xA5;
-  struct Buf {
-    const void* host;
-    void* host_out;   // null = input only
-    size_t bytes;     // copied from the host
-    size_t pad;       // zero bytes behind them (the corpus's last tile), in front of the canary
-    const char* name;
-    DevBuf dev;
-  };
-  std::vector<Buf> bufs;
-  auto add = [&](const void* h, void* h_out, size_t bytes, const char* name, size_t pad = 0) -> int {
-    if (!h) return -1;
-    bufs.push_back(Buf{h, h_out, bytes, pad, name, DevBuf()});
-    return (int)bufs.size() - 1;
-  };
-  const size_t NB = (size_t)a->nq_buf, K = (size_t)a->K, k = (size_t)a->k, cap = (size_t)a->cap;
-  int icorpus = -1, iw = -1, iq = -1, ieps = -1, isrc = -1, iwo = -1, ibuf = -1, icnt = -1, ikey = -1, isc = -1, iout = -1, iovf = -1, idone = -1;
-  if (stage || rescue) {
-    const size_t rows = (size_t)a->corpus_rows, padded = (rows + 255) / 256 * 256;
-    icorpus = add(a->corpus, nullptr, rows * K * 2, "corpus", (padded - rows) * K * 2);
-  }
-  if (stage) iw = add(a->w, nullptr, (size_t)a->N * K * 2, "w");
-  if (queries || rescue) iq = add(a->queries, nullptr, (size_t)a->nq * K * 4, "queries");
-  if (queries) iwo = add(a->w_out, a->w_out, (size_t)a->N * K * 2, "w_out");
-  if (seld) isrc = add(a->src, nullptr, (size_t)a->nq * (size_t)a->src_stride * 8, "src");
-  if (merge) isrc = add(a->src, nullptr, (size_t)a->n * (size_t)a->nq * k * 8, "src");
-  if (stage || sel || seld) ibuf = add(a->buf, a->buf, NB * cap * 8, "buf");
-  if (stage || sel || seld || tau) {
-    icnt = add(a->cnt, a->cnt, NB * 4, "cnt");
-    ikey = add(a->thr_key, a->thr_key, NB * 8, "thr_key");
-    isc = add(a->thr_score, a->thr_score, NB * 4, "thr_score");
-  }
-  if (sel || seld || rescue || merge) iout = add(a->out, a->out, NB * k * 8, "out");
-  if (sel || seld || rescue || tau) iovf = add(a->ovf, a->ovf, NB * 4, "ovf");
-  if (tau) ieps = add(a->eps, nullptr, (size_t)a->nq * 4, "eps");
-  if (rescue) idone = add(a->done, a->done, NB * 4, "done");
-  DevBuf part;   // the rescue's per-slice lists [slices][nq][k]: scratch of the hook, with a canary of its own
-  const size_t part_bytes = rescue ? (size_t)a->slices * (size_t)a->nq * k * 8 : 0;
-  hipError_t e = hipSuccess;
-  if (rescue) {
-    e = part.alloc(part_bytes + kCanary);
-    if (e == hipSuccess) e = hipMemset(part.p, 0, part_bytes);
-    if (e == hipSuccess) e = hipMemset(part.as<char>() + part_bytes, kCanaryByte, kCanary);
-  }
-  for (Buf& b : bufs) {
-    if (e == hipSuccess) e = b.dev.alloc(b.bytes + b.pad + kCanary);
-    if (e == hipSuccess && b.bytes) e = hipMemcpy(b.dev.p, b.host, b.bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess && b.pad) e = hipMemset(b.dev.as<char>() + b.bytes, 0, b.pad);
-    if (e == hipSuccess) e = hipMemset(b.dev.as<char>() + b.bytes + b.pad, kCanaryByte, kCanary);
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    set_error("debug topk run: staging failed: %s", hipGetErrorString(e));
-    return VRAG_ERR_HIP;
-  }
-  auto fp = [&](int i) -> float* { return i < 0 ? nullptr : bufs[i].dev.as<float>(); };
-  auto up = [&](int i) -> unsigned* { return i < 0 ? nullptr : bufs[i].dev.as<unsigned>(); };
-  auto kp = [&](int i) -> u64* { return i < 0 ? nullptr : bufs[i].dev.as<u64>(); };
-  auto hp = [&](int i) -> bf16_t* { return i < 0 ? nullptr : bufs[i].dev.as<bf16_t>(); };
+  // device copies (DbgBufs): what the chosen launcher does not take, and an absent optional buffer, stay null pointers
+  const size_t NB = (size_t)a->nq_buf, K = (size_t)a->K, k = (size_t)a->k, cap = (size_t)a->cap, nq = (size_t)a->nq;
+  const size_t rows = (size_t)std::max(a->corpus_rows, 0), padded = (rows + 255) / 256 * 256;   // the last 256-row tile is read whole: zeros
+  DbgBufs B;
+  u64* part = rescue ? B.scratch<u64>((size_t)a->slices * nq * k, "part") : nullptr;   // the rescue's per-slice lists [slices][nq][k]
+  bf16_t* corpus = (stage || rescue) ? B.in<bf16_t>(a->corpus, rows * K, "corpus", (padded - rows) * K * 2) : nullptr;
+  bf16_t* w = stage ? B.in_opt<bf16_t>(a->w, (size_t)a->N * K, "w") : nullptr;
+  float* queries_d = (queries || rescue) ? B.in_opt<float>(a->queries, nq * K, "queries") : nullptr;
+  bf16_t* w_out = queries ? B.inout_opt<bf16_t>(a->w_out, (size_t)a->N * K, "w_out") : nullptr;
+  u64* src = (seld || merge) ? B.in_opt<u64>(a->src, seld ? nq * (size_t)a->src_stride : (size_t)a->n * nq * k, "src") : nullptr;
+  u64* buf = (stage || sel || seld) ? B.inout_opt<u64>(a->buf, NB * cap, "buf") : nullptr;
+  const bool has_thr = stage || sel || seld || tau;
+  unsigned* cnt = has_thr ? B.inout_opt<unsigned>(a->cnt, NB, "cnt") : nullptr;
+  u64* thr_key = has_thr ? B.inout_opt<u64>(a->thr_key, NB, "thr_key") : nullptr;
+  float* thr_score = has_thr ? B.inout_opt<float>(a->thr_score, NB, "thr_score") : nullptr;
+  u64* out = (sel || seld || rescue || merge) ? B.inout_opt<u64>(a->out, NB * k, "out") : nullptr;
+  unsigned* ovf = (sel || seld || rescue || tau) ? B.inout_opt<unsigned>(a->ovf, NB, "ovf") : nullptr;
+  float* eps = tau ? B.in_opt<float>(a->eps, nq, "eps") : nullptr;
+  unsigned* done = rescue ? B.inout_opt<unsigned>(a->done, NB, "done") : nullptr;
+  hipError_t e = B.staged();
+  if (e != hipSuccess) return B.finish("topk", e);
   switch (op) {
     case VRAG_DEBUG_TOPK_SCORE_STAGE: {
       GemmParams g{};
       g.op_dtype = kOpBf16;
       const bool mapped = a->tile_stride > 1 || a->tile_skip > 1;   // as dense_tiled_search: the map starts at the shard's first row
-      g.A = hp(icorpus) + (mapped ? (size_t)0 : (size_t)a->row_base * K);
-      g.W = hp(iw);
+      g.A = corpus + (mapped ? (size_t)0 : (size_t)a->row_base * K);
+      g.W = w;
       g.M = a->M;
       g.N = a->N;
       g.K = a->K;
-      g.topk_thr_score = fp(isc);
-      g.topk_thr_key = kp(ikey);
-      g.topk_cnt = up(icnt);
-      g.topk_buf = kp(ibuf);
+      g.topk_thr_score = thr_score;
+      g.topk_thr_key = thr_key;
+      g.topk_cnt = cnt;
+      g.topk_buf = buf;
       g.topk_cap = a->cap;
       g.topk_nq = a->nq;
       g.topk_pairs = a->pairs;
@@ -1280,47 +917,50 @@ int vrag_debug_topk_run(vrag_debug_topk_args* a, int32_t device) {
       break;
     }
     case VRAG_DEBUG_TOPK_QUERIES:
-      e = launch_tiled_queries(fp(iq), a->nq, a->K, a->pairs, a->N, hp(iwo), 0);
+      e = launch_tiled_queries(queries_d, a->nq, a->K, a->pairs, a->N, w_out, 0);
       break;
     case VRAG_DEBUG_TOPK_SELECT:
-      e = launch_tiled_select(kp(ibuf), up(icnt), a->cap, a->k, kp(ikey), fp(isc), kp(iout), up(iovf), 0, a->nq, 0);
+      e = launch_tiled_select(buf, cnt, a->cap, a->k, thr_key, thr_score, out, ovf, 0, a->nq, 0);
       break;
     case VRAG_DEBUG_TOPK_SELECT_DIRECT:
-      e = launch_tiled_select_direct(kp(isrc), a->src_stride, a->n, kp(ibuf), up(icnt), a->cap, a->k, kp(ikey), fp(isc), kp(iout), up(iovf), a->nq, 0);
+      e = launch_tiled_select_direct(src, a->src_stride, a->n, buf, cnt, a->cap, a->k, thr_key, thr_score, out, ovf, a->nq, 0);
       break;
     case VRAG_DEBUG_TOPK_RESCUE:
-      e = launch_dense_tiled_rescue(hp(icorpus), (long long)a->n, a->K, fp(iq), a->nq, a->k, up(iovf), part.as<u64>(), up(idone), kp(iout), a->slices, 0);
+      e = launch_dense_tiled_rescue(corpus, (long long)a->n, a->K, queries_d, a->nq, a->k, ovf, part, done, out, a->slices, 0);
       break;
     case VRAG_DEBUG_TOPK_MERGE:
-      e = launch_topk_merge(kp(isrc), a->n, a->nq, a->k, kp(iout), 0);
+      e = launch_topk_merge(src, a->n, a->nq, a->k, out, 0);
       break;
     default:
-      e = launch_tiled_tau(a->nq, kp(ikey), fp(isc), fp(ieps), up(icnt), up(iovf), 0);
+      e = launch_tiled_tau(a->nq, thr_key, thr_score, eps, cnt, ovf, 0);
       break;
   }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  std::vector<unsigned char> canary(kCanary);
-  const char* clobbered = nullptr;
-  auto intact = [&]() { return std::all_of(canary.begin(), canary.end(), [](unsigned char v) { return v == kCanaryByte; }); };
-  if (e == hipSuccess && rescue) {
-    e = hipMemcpy(canary.data(), part.as<char>() + part_bytes, kCanary, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && !intact()) clobbered = "part";
-  }
-  for (Buf& b : bufs) {
-    if (e != hipSuccess) break;
-    e = hipMemcpy(canary.data(), b.dev.as<char>() + b.bytes + b.pad, kCanary, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && !clobbered && !intact()) clobbered = b.name;
-    if (e == hipSuccess && b.host_out && b.bytes) e = hipMemcpy(b.host_out, b.dev.p, b.bytes, hipMemcpyDeviceToHost);
-  }
-  if (e != hipSuccess) {
-    set_error("debug topk run failed: %s", hipGetErrorString(e));
-    return e == hipErrorInvalidValue ? VRAG_ERR_INVALID : VRAG_ERR_HIP;
-  }
-  if (clobbered) {
-    set_error("debug topk run: the launch wrote past the end of %s", clobbered);
+  const int rc = B.finish("topk", e);
+  return rc == VRAG_ERR_HIP && e == hipErrorInvalidValue ? VRAG_ERR_INVALID : rc;   // a launcher's refusal
+}
+
+int vrag_debug_canary_selftest(int32_t touch, int32_t device) {
+  ARG_CHECK(touch >= 0 && touch <= 3, "touch (%d) must be in 0..3", touch);
+  if (const int rc = use_device(device); rc != VRAG_OK) return rc;
+  unsigned char ha[64], hb[100], want[100];
+  for (int i = 0; i < 100; ++i) want[i] = hb[i] = (unsigned char)(i * 7 + 1);
+  std::memset(ha, 0x11, sizeof(ha));
+  constexpr size_t kPad = 28;
+  DbgBufs B;
+  B.in<unsigned char>(ha, sizeof(ha), "a");
+  unsigned char* b = B.inout<unsigned char>(hb, sizeof(hb), "b", kPad);
+  B.scratch<unsigned>(0, "c");
+  hipError_t e = B.staged();
+  std::memset(hb, 0, sizeof(hb));   // finish() brings the staged bytes back
+  // a host-issued write of one byte inside b's own allocation: its first / last canary byte, or its last pad byte
+  const size_t at_byte[4] = {0, sizeof(hb) + kPad, sizeof(hb) + kPad + DbgBufs::kCanary - 1, sizeof(hb) + kPad - 1};
+  if (e == hipSuccess && touch) e = hipMemset(b + at_byte[touch], 0, 1);
+  const int rc = B.finish("canary selftest", e);
+  if (rc == VRAG_OK && std::memcmp(hb, want, sizeof(hb)) != 0) {
+    set_error("debug canary selftest run: b came back changed");
     return VRAG_ERR_HIP;
   }
-  return VRAG_OK;
+  return rc;
 }
 
 int vrag_debug_token_spans(const float* logits, int64_t n_tokens, const int32_t* win_job, const int32_t* win_a, const int32_t* win_b,

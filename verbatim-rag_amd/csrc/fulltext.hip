@@ -1276,65 +1276,12 @@ int vrag_text_index_search_device(vrag_text_index* ix, const int64_t* q_indptr, 
 
 #ifdef VRAG_DEBUG_API
 // ------------------------------------------------------------------------------------ unit-test hook (harness build only)
-#include <deque>
-
 #include "../../include/vrag_amd_debug.h"
+#include "debug_bufs.h"
 
 namespace {
 
-constexpr size_t kDbgCanary = 4096;
-constexpr unsigned char kDbgCanaryByte = 0xA5;
 constexpr long long kDbgMax = 1ll << 22;   // every count of the hook: sizes and u32 offsets stay far inside their types
-
-// Device copies of the hook's buffers, each followed by a canary the launches must leave as it was.
-struct DbgBufs {
-  struct B {
-    void* host_out;   // null = nothing is copied back
-    size_t bytes;
-    const char* name;
-    DevBuf dev;
-  };
-  std::deque<B> bufs;
-  hipError_t err = hipSuccess;
-  // `bytes` from host (null = zeros), copied back to host_out (nullable) by finish()
-  template <typename T>
-  T* add(const void* host, void* host_out, size_t bytes, const char* name) {
-    bufs.push_back(B{host_out, bytes, name, DevBuf()});
-    B& b = bufs.back();
-    if (err == hipSuccess) err = b.dev.alloc(bytes + kDbgCanary);
-    if (err == hipSuccess && bytes) err = host ? hipMemcpy(b.dev.p, host, bytes, hipMemcpyHostToDevice) : hipMemset(b.dev.p, 0, bytes);
-    if (err == hipSuccess) err = hipMemset(b.dev.as<char>() + bytes, kDbgCanaryByte, kDbgCanary);
-    return b.dev.as<T>();
-  }
-  template <typename T>
-  T* in(const void* host, size_t count, const char* name) { return add<T>(host, nullptr, count * sizeof(T), name); }
-  template <typename T>
-  T* inout(void* host, size_t count, const char* name) { return add<T>(host, host, count * sizeof(T), name); }
-  template <typename T>
-  T* scratch(size_t count, const char* name) { return add<T>(nullptr, nullptr, count * sizeof(T), name); }
-  // after the launches (e = their status): canaries checked, in / out buffers copied back
-  int finish(hipError_t e) {
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    std::vector<unsigned char> canary(kDbgCanary);
-    const char* clobbered = nullptr;
-    for (B& b : bufs) {
-      if (e != hipSuccess) break;
-      e = hipMemcpy(canary.data(), b.dev.as<char>() + b.bytes, kDbgCanary, hipMemcpyDeviceToHost);
-      if (e == hipSuccess && !clobbered && !std::all_of(canary.begin(), canary.end(), [](unsigned char v) { return v == kDbgCanaryByte; }))
-        clobbered = b.name;
-      if (e == hipSuccess && b.host_out && b.bytes) e = hipMemcpy(b.host_out, b.dev.p, b.bytes, hipMemcpyDeviceToHost);
-    }
-    if (e != hipSuccess) {
-      set_error("debug text run failed: %s", hipGetErrorString(e));
-      return VRAG_ERR_HIP;
-    }
-    if (clobbered) {
-      set_error("debug text run: the launch wrote past the end of %s", clobbered);
-      return VRAG_ERR_HIP;
-    }
-    return VRAG_OK;
-  }
-};
 
 // The segments of the argument block as the kernels must find them (see the header); rows_total < 0 = no bound on the rows.
 int dbg_check_segs(const vrag_debug_text_args* a, bool need_ptf, bool need_df, long long rows_total) {
@@ -1389,7 +1336,7 @@ hipError_t dbg_sort(DbgBufs& B, RecPtrs a, long long n, int by_row, int row_bits
   unsigned* hist = B.scratch<unsigned>(tiles * 256, "sort hist");
   unsigned* offs = B.scratch<unsigned>(tiles * 256 + 1, "sort offs");
   *sorted = a;
-  if (B.err != hipSuccess) return B.err;
+  if (B.staged() != hipSuccess) return B.err;
   bool in_b = false;
   const hipError_t e = radix_passes(a, b, n, by_row, row_bits, hist, offs, nullptr, &in_b);
   if (in_b) *sorted = b;
@@ -1409,7 +1356,7 @@ hipError_t dbg_rle(DbgBufs& B, vrag_debug_text_args* a, RecPtrs r, long long n, 
   u64* pkey = query_form ? B.inout<u64>(a->pkey, pb, "pkey") : nullptr;
   u64* ukeys = seg_form ? B.inout<u64>(a->ukeys, kb, "ukeys") : nullptr;
   unsigned* pstart = seg_form ? B.inout<uint32_t>(a->pstart, kb + 1, "pstart") : nullptr;
-  if (B.err != hipSuccess) return B.err;
+  if (B.staged() != hipSuccess) return B.err;
   unsigned n_keys = 0;
   hipError_t e = rle_count(r, n, scr, n_post_host, &n_keys, nullptr);
   if (e != hipSuccess) return e;
@@ -1500,11 +1447,7 @@ int vrag_debug_text_run(vrag_debug_text_args* a, int32_t device) {
     ARG_CHECK(a->cand_buf >= (long long)n_blocks * a->nq * a->kk && a->cand_buf <= (1ll << 26), "score: cand_buf (%lld) below blocks * nq * kk (%lld)",
               (long long)a->cand_buf, (long long)n_blocks * a->nq * a->kk);
   }
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
-  HIP_TRY(hipSetDevice(device));
+  if (const int rc = use_device(device); rc != VRAG_OK) return rc;
 
   DbgBufs B;
   hipError_t e = hipSuccess;
@@ -1514,14 +1457,14 @@ int vrag_debug_text_run(vrag_debug_text_args* a, int32_t device) {
     case VRAG_DEBUG_TEXT_SCAN: {
       const unsigned* in = B.in<uint32_t>(a->in, (size_t)a->n, "in");
       unsigned* out = B.inout<uint32_t>(a->out, (size_t)a->n_buf + 1, "out");
-      if ((e = B.err) == hipSuccess) e = scan_u32(in, a->n, out, nullptr);
+      if ((e = B.staged()) == hipSuccess) e = scan_u32(in, a->n, out, nullptr);
       break;
     }
     case VRAG_DEBUG_TEXT_SORT: {
       const size_t n = (size_t)a->n;
       RecPtrs r{B.in<u64>(a->key, n, "key"), B.in<uint32_t>(a->row, n, "row"), B.in<uint32_t>(a->tf, n, "tf")};
       RecPtrs sorted = r;
-      if ((e = B.err) == hipSuccess) e = dbg_sort(B, r, a->n, a->by_row, a->row_bits, &sorted);
+      if ((e = B.staged()) == hipSuccess) e = dbg_sort(B, r, a->n, a->by_row, a->row_bits, &sorted);
       if (e == hipSuccess) e = hipDeviceSynchronize();
       if (e == hipSuccess && n) e = hipMemcpy(a->key, sorted.key, n * 8, hipMemcpyDeviceToHost);
       if (e == hipSuccess && n) e = hipMemcpy(a->row, sorted.row, n * 4, hipMemcpyDeviceToHost);
@@ -1531,7 +1474,7 @@ int vrag_debug_text_run(vrag_debug_text_args* a, int32_t device) {
     case VRAG_DEBUG_TEXT_RLE: {
       const size_t n = (size_t)a->n;
       RecPtrs r{B.in<u64>(a->key, n, "key"), B.in<uint32_t>(a->row, n, "row"), B.in<uint32_t>(a->tf, n, "tf")};
-      if ((e = B.err) == hipSuccess) e = dbg_rle(B, a, r, a->n, a->unit, a->ukeys != nullptr, a->pkey != nullptr, &n_post_host);
+      if ((e = B.staged()) == hipSuccess) e = dbg_rle(B, a, r, a->n, a->unit, a->ukeys != nullptr, a->pkey != nullptr, &n_post_host);
       break;
     }
     case VRAG_DEBUG_TEXT_FOLD: {
@@ -1539,7 +1482,7 @@ int vrag_debug_text_run(vrag_debug_text_args* a, int32_t device) {
       const size_t n = (size_t)total;
       RecPtrs r{B.scratch<u64>(n, "fold key"), B.scratch<unsigned>(n, "fold row"), B.scratch<unsigned>(n, "fold tf")};
       RecPtrs sorted = r;
-      if ((e = B.err) == hipSuccess) e = expand_parts(segs, a->n_segs, r, nullptr);
+      if ((e = B.staged()) == hipSuccess) e = expand_parts(segs, a->n_segs, r, nullptr);
       if (e == hipSuccess) e = dbg_sort(B, r, total, 0, 0, &sorted);   // build_segment: by key, then RLE with the records' tf
       if (e == hipSuccess) e = dbg_rle(B, a, sorted, total, 0, true, false, &n_post_host);
       break;
@@ -1552,7 +1495,7 @@ int vrag_debug_text_run(vrag_debug_text_args* a, int32_t device) {
       float* kd = B.inout<float>(a->kd, (size_t)a->rows_buf, "kd");
       unsigned long long pair[4] = {0, 0, (unsigned long long)a->corpus_n, (unsigned long long)a->corpus_sum_dl};   // as refresh_stats lays acc out
       unsigned long long* acc = B.in<unsigned long long>(pair, 4, "acc");
-      if ((e = B.err) == hipSuccess)
+      if ((e = B.staged()) == hipSuccess)
         e = stats_launch(live, dl, a->n_rows, true, acc, acc + (a->corpus_n ? 2 : 0), a->k1, a->b, kd, segs, a->n_segs, nullptr);
       if (e == hipSuccess) e = hipDeviceSynchronize();
       if (e == hipSuccess) e = hipMemcpy(a->acc, acc, 16, hipMemcpyDeviceToHost);
@@ -1562,8 +1505,8 @@ int vrag_debug_text_run(vrag_debug_text_args* a, int32_t device) {
       dbg_stage_segs(a, B, false, segs);
       const u64* qk = B.in<u64>(a->qkeys, (size_t)a->n_terms, "qkeys");
       int* tu = B.inout<int32_t>(a->tu, (size_t)a->terms_buf * FT_MAXSEG, "tu");
-      long long* df = a->df_out ? B.inout<long long>(a->df_out, (size_t)a->terms_buf, "df_out") : nullptr;
-      if ((e = B.err) == hipSuccess) e = lookup_launch(seg_view(segs, a->n_segs), qk, a->n_terms, tu, df, nullptr);
+      long long* df = B.inout_opt<long long>(a->df_out, (size_t)a->terms_buf, "df_out");
+      if ((e = B.staged()) == hipSuccess) e = lookup_launch(seg_view(segs, a->n_segs), qk, a->n_terms, tu, df, nullptr);
       break;
     }
     default: {
@@ -1574,16 +1517,16 @@ int vrag_debug_text_run(vrag_debug_text_args* a, int32_t device) {
       const float* w = B.in<float>(a->w, nt, "w");
       const float* kd = B.in<float>(a->kd, n, "kd");
       const unsigned* live = B.in<uint32_t>(a->live, (n + 31) / 32, "live");
-      const unsigned* allow = a->allow ? B.in<uint32_t>(a->allow, ((size_t)a->allow_rows + 31) / 32, "allow") : nullptr;
-      const u64* bound = a->bound ? B.in<u64>(a->bound, (size_t)a->nq, "bound") : nullptr;
+      const unsigned* allow = B.in_opt<uint32_t>(a->allow, ((size_t)a->allow_rows + 31) / 32, "allow");
+      const u64* bound = B.in_opt<u64>(a->bound, (size_t)a->nq, "bound");
       u64* cand = B.inout<u64>(a->cand, (size_t)a->cand_buf, "cand");
-      if ((e = B.err) == hipSuccess)
+      if ((e = B.staged()) == hipSuccess)
         e = score_launch(seg_view(segs, a->n_segs), qi, tu, w, kd, live, allow, allow ? a->allow_rows : 0, a->n_rows, a->k1p1, a->nq, a->kk, bound,
                          cand, nullptr);
       break;
     }
   }
-  return B.finish(e);
+  return B.finish("text", e);
 }
 
 int vrag_debug_text_index_read(vrag_text_index* ix, vrag_debug_text_index_state* s) {
