@@ -650,6 +650,10 @@ class GpuVectorStore(VectorStore):
         self._row_filter_cols: Dict[str, int] = {}
         self._filter_fallbacks: set = set()
         self._all_ids_truthy = True
+        # replicated like `_all_ids_truthy`: no two rows share an id (the ids seen so far, until two of them do).  Rows that
+        # share an id are ONE candidate of a hybrid fusion (hybrid_search.py:73-129 keys by id); deletes leave it as it is.
+        self._ids_unique = True
+        self._id_seen: Optional[set] = set()
         self._documents: Dict[str, Dict[str, Any]] = {}      # document records (add_documents / get_document)
         self._subsets: Dict[Any, Tuple[Any, np.ndarray, Any]] = {}   # (kind, mask bytes) -> (subset shard, global row of each subset row, device copy)
 
@@ -720,6 +724,7 @@ class GpuVectorStore(VectorStore):
         new_meta = _metadata_rows(metadatas[keep])                                # milvus_base.py:108-109
         new_texts, new_enh = list(texts[keep]), list(enhanced_texts[keep])
         with self._mu:
+            self._note_unique(ids)              # first: an id that cannot be hashed leaves the store as it was
             base = len(self._ids)
             self._ids.extend(ids)
             if self._id_rows is not None:
@@ -753,6 +758,16 @@ class GpuVectorStore(VectorStore):
                     index.setdefault(t, []).append(np.asarray(rows, dtype=np.int64))
             for column in self._meta_columns.values():      # typed columns likewise: O(new rows) per insert
                 column.extend(new_meta)
+
+    def _note_unique(self, ids) -> None:
+        """Keeps `_ids_unique` in step with the ids of new rows (under the lock, or before the store is shared)."""
+        seen = self._id_seen
+        if seen is None:
+            return
+        before = len(seen)
+        seen.update(ids)
+        if len(seen) != before + len(ids):
+            self._ids_unique, self._id_seen = False, None
 
     def _note_id(self, key, row: int) -> None:
         have = self._id_rows.get(key)
@@ -1331,7 +1346,7 @@ class GpuVectorStore(VectorStore):
                       nprobe: Optional[int] = None) -> List[List[SearchResult]]:
         """Every method of `queries` (method -> the batch's queries, in fusion order) for all queries, 2 * top_k rows each,
         then weighted RRF: one array merge for the whole batch, or query by query when an id is falsy (such hits keep
-        their rank but are skipped).  A failing full-text leg is left out with a warning, as in `_hybrid_search_with_weights`;
+        their rank but are skipped) or rows share an id (they are one candidate, as in `query`).  A failing full-text leg is left out with a warning, as in `_hybrid_search_with_weights`;
         with one method left, its first top_k are the answer."""
         limit = top_k * 2
         lists: Dict[str, Tuple[np.ndarray, np.ndarray]] = {}
@@ -1352,7 +1367,7 @@ class GpuVectorStore(VectorStore):
         if len(lists) == 1:                                        # one method: its first top_k
             rows, scores = next(iter(lists.values()))
             return self._results_batch(rows[:, :top_k], scores[:, :top_k])
-        if self._all_ids_truthy:
+        if self._all_ids_truthy and self._ids_unique:
             ranked = {m: r for m, (r, _s) in lists.items()}
             if self.rrf_route == "device" and Q >= self.RRF_DEVICE_MIN_QUERIES:
                 rows, dist = rrf_fuse_rows_device(ranked, top_k, weights, rrf_k, self.device)
@@ -1632,6 +1647,7 @@ class GpuVectorStore(VectorStore):
             raise ValueError(f"{path}: the saved shards do not cover the {n} stored ids exactly once")
         st._ids = list(ids)
         st._all_ids_truthy = all(bool(x) for x in st._ids)
+        st._note_unique(st._ids)
         st._documents = {d.get("id", ""): dict(d) for d in head.get("documents", [])}
         st._alive.extend(np.ones(n, dtype=bool))
         st._owned.extend(owned)
