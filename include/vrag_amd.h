@@ -348,6 +348,22 @@ int vrag_dense_index_search(vrag_dense_index* ix, const float* queries /*[nq,dim
                             float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, void* stream);
 /* Re-runs the kernels of the last search on the device-resident queries (no copies, no sync). */
 int vrag_dense_index_run_resident(vrag_dense_index* ix, int32_t nq, int32_t k, void* stream);
+/* Compaction: drops rows in place.  `keep_words` (host) holds one bit per row, bit r % 32 of word r / 32 as in the `allow`
+ * masks: set = the row stays.  The rows that stay keep their relative order and become rows 0 .. new_size - 1; capacity is
+ * unchanged, so the reclaimed room takes appends again.  The rows -- and the bf16 prefilter image of a dtype 2 index -- are moved
+ * where they lie in HBM: nothing is re-uploaded and no second copy of the array is made.  Rows travel in waves of at most
+ * VRAG_COMPACT_BOUNCE_BYTES (csrc/compact.h) through a bounce buffer in the handle's scratch (allocated by the first compaction
+ * that moves a row): one launch gathers a wave, the next stores it, and the order of the moves is the stream's alone -- no
+ * workgroup waits for another.  The rows in front of the first cleared bit are not touched; a bitmap without a cleared bit
+ * launches nothing.  n_keep must equal the index's size: VRAG_ERR_INVALID otherwise, before anything is launched.  Runs under
+ * the handle's lock; the new size is published (and returned in *new_size) after the stream has drained.  Every search
+ * afterwards returns what an index freshly built from the kept rows returns, bit for bit: the prefilter's norm and error bounds
+ * are left as they are -- still upper bounds, and no result depends on how tight they are.  The resident queries and lists of
+ * an earlier search are invalidated: vrag_dense_index_run_resident is VRAG_ERR_INVALID until the next search.  An IVF overlay
+ * over the index is renumbered with vrag_ivf_index_remap and the same bitmap, after this call. */
+int vrag_dense_index_compact(vrag_dense_index* ix, const uint32_t* keep_words /*host*/, int64_t n_keep, int64_t* new_size);
+/* Rows [first_row, first_row + n) as fp32 (bf16 rows widened: exact); rows beyond the size are VRAG_ERR_INVALID. */
+int vrag_dense_index_read(vrag_dense_index* ix, int64_t first_row, int64_t n, float* out /*[n,dim] host*/);
 /* The same search (k <= 64) with the result lists left in DEVICE memory -- what a rank contributes to the cross-GPU
  * exchange (serves verbatim_rag/vector_stores/milvus_base.py:239-259 on a row-sharded corpus):
  * out_ids[q][j] = row_map[row] when `row_map` (device int64[n_map], the caller's local row -> global row table) is
@@ -407,6 +423,11 @@ int vrag_ivf_index_sync(vrag_ivf_index* ivf);
 int vrag_ivf_index_stats(vrag_ivf_index* ivf, int32_t* nlist, int64_t* n_assigned, int64_t* largest_list);
 int vrag_ivf_index_read(vrag_ivf_index* ivf, float* centroids /*[nlist,dim]*/, uint32_t* list_off /*[nlist+1]*/,
                         uint32_t* list_rows /*[n_assigned]*/);
+/* After vrag_dense_index_compact of the base, with the same bitmap (n_keep = the base's size before it): every entry of
+ * list_rows becomes its row's new number, the entries of dropped rows disappear, list_off is rebuilt and n_assigned becomes the
+ * number of assigned rows that stay.  The renumbering is monotonic, so every list stays ascending; the centroids are untouched
+ * and nothing is trained or assigned again.  VRAG_ERR_INVALID before a sync or when the bitmap is shorter than the lists. */
+int vrag_ivf_index_remap(vrag_ivf_index* ivf, const uint32_t* keep_words /*host*/, int64_t n_keep);
 int vrag_ivf_index_search(vrag_ivf_index* ivf, const float* queries /*[nq,dim] host*/, int32_t nq, int32_t k, int32_t nprobe,
                           float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, int64_t* scanned_rows /*[nq] or NULL*/, void* stream);
 
@@ -447,6 +468,8 @@ int64_t vrag_sq8_index_size(vrag_sq8_index* ix);
 int vrag_sq8_index_add(vrag_sq8_index* ix, const float* rows /*[n,dim] host*/, int64_t n);
 int vrag_sq8_index_add_device(vrag_sq8_index* ix, const float* rows /*[n,dim] device*/, int64_t n, void* stream);
 int vrag_sq8_index_read(vrag_sq8_index* ix, int64_t first_row, int64_t n, int8_t* codes /*[n,dim] or NULL*/, float* scales /*[n] or NULL*/);
+/* vrag_dense_index_compact for SQ8 rows: the codes (at their padded stride) and the scales move in place, same contract. */
+int vrag_sq8_index_compact(vrag_sq8_index* ix, const uint32_t* keep_words /*host*/, int64_t n_keep, int64_t* new_size);
 int vrag_sq8_index_set_route(vrag_sq8_index* ix, int32_t route);
 int vrag_sq8_index_search(vrag_sq8_index* ix, const float* queries /*[nq,dim] host*/, int32_t nq, int32_t k,
                           float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, void* stream);
@@ -781,6 +804,10 @@ int vrag_row_filter_add_column(vrag_row_filter* f, int32_t* col_out);
 int vrag_row_filter_append(vrag_row_filter* f, int32_t col, const uint8_t* kinds /*[n] host*/, const uint64_t* payload /*[n] host*/,
                            int64_t n);
 int vrag_row_filter_rows(vrag_row_filter* f, int32_t col, int64_t* n);
+/* Drops the rows whose bit is cleared (bit r % 32 of word r / 32) from the kinds and payload of EVERY column, in place, order
+ * kept (csrc/compact.h).  A column that holds fewer rows than the bitmap covers is compacted under the bitmap's prefix; one that
+ * holds more is VRAG_ERR_INVALID before anything is launched.  The string dictionaries stay as they are (codes do not change). */
+int vrag_row_filter_compact(vrag_row_filter* f, const uint32_t* keep_words /*host*/, int64_t n_keep);
 int vrag_row_filter_eval(vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops, int32_t n_ops,
                          const uint32_t* tables /*[n_table_words] host, NULL when 0*/, int64_t n_table_words, int64_t n_rows,
                          uint32_t* out_words /*host*/, void* stream);

@@ -144,6 +144,8 @@ SIGNATURES = {
     "vrag_dense_index_search": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, _FP, _LP, C.c_void_p]),
     "vrag_dense_index_search_filtered": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _FP, _LP, C.c_void_p]),
     "vrag_dense_index_run_resident": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p]),
+    "vrag_dense_index_compact": (C.c_int, [_H, C.c_void_p, C.c_int64, _LP]),
+    "vrag_dense_index_read": (C.c_int, [_H, C.c_int64, C.c_int64, _FP]),
     "vrag_dense_index_search_device": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]),
     "vrag_ivf_index_create": (C.c_int, [_H, C.c_int32, C.POINTER(_H)]),
@@ -153,6 +155,7 @@ SIGNATURES = {
     "vrag_ivf_index_sync": (C.c_int, [_H]),
     "vrag_ivf_index_stats": (C.c_int, [_H, _IP, _LP, _LP]),
     "vrag_ivf_index_read": (C.c_int, [_H, _FP, C.c_void_p, C.c_void_p]),
+    "vrag_ivf_index_remap": (C.c_int, [_H, C.c_void_p, C.c_int64]),
     "vrag_ivf_index_search": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, _FP, _LP, _LP, C.c_void_p]),
     "vrag_sq8_index_create": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(_H)]),
     "vrag_sq8_index_destroy": (None, [_H]),
@@ -160,6 +163,7 @@ SIGNATURES = {
     "vrag_sq8_index_add": (C.c_int, [_H, _FP, C.c_int64]),
     "vrag_sq8_index_add_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p]),
     "vrag_sq8_index_read": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "vrag_sq8_index_compact": (C.c_int, [_H, C.c_void_p, C.c_int64, _LP]),
     "vrag_sq8_index_set_route": (C.c_int, [_H, C.c_int32]),
     "vrag_sq8_index_search": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, _FP, _LP, C.c_void_p]),
     "vrag_sq8_index_search_filtered": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _FP, _LP, C.c_void_p]),
@@ -168,6 +172,7 @@ SIGNATURES = {
     "vrag_row_filter_add_column": (C.c_int, [_H, _IP]),
     "vrag_row_filter_append": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     "vrag_row_filter_rows": (C.c_int, [_H, C.c_int32, _LP]),
+    "vrag_row_filter_compact": (C.c_int, [_H, C.c_void_p, C.c_int64]),
     "vrag_row_filter_eval": (C.c_int, [_H, C.POINTER(FilterLeaf), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
                                        C.c_void_p, C.c_void_p]),
     "vrag_row_filter_append_strings": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),

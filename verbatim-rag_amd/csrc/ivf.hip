@@ -421,6 +421,18 @@ long long lists_of(const unsigned* a, long long n, int nlist, std::vector<unsign
   return largest;
 }
 
+// The lists of the first `size` rows from their assignments (h_assign), on the host and in HBM; under the lock.
+int publish_lists(vrag_ivf_index* ix, long long size, hipStream_t st) {
+  ix->largest = lists_of(ix->h_assign.data(), size, ix->nlist, ix->h_off, ix->h_rows, [](long long i) { return (unsigned)i; });
+  if ((size_t)size > ix->d_rows.n) HIP_TRY(ix->d_rows.grow((size_t)size + (size_t)size / 2));
+  HIP_TRY(hipMemcpyAsync(ix->d_off.p, ix->h_off.data(), ix->h_off.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+  if (size) HIP_TRY(hipMemcpyAsync(ix->d_rows.p, ix->h_rows.data(), (size_t)size * sizeof(unsigned), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  ix->n_assigned = size;
+  ix->synced = true;
+  return VRAG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -533,14 +545,23 @@ int vrag_ivf_index_sync(vrag_ivf_index* ix) {
     HIP_TRY(hipMemcpyAsync(ix->h_assign.data() + ix->n_assigned, ix->d_assign.p, (size_t)fresh * sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
-  ix->largest = lists_of(ix->h_assign.data(), size, ix->nlist, ix->h_off, ix->h_rows, [](long long i) { return (unsigned)i; });
-  if ((size_t)size > ix->d_rows.n) HIP_TRY(ix->d_rows.grow((size_t)size + (size_t)size / 2));
-  HIP_TRY(hipMemcpyAsync(ix->d_off.p, ix->h_off.data(), ix->h_off.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-  if (size) HIP_TRY(hipMemcpyAsync(ix->d_rows.p, ix->h_rows.data(), (size_t)size * sizeof(unsigned), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  ix->n_assigned = size;
-  ix->synced = true;
-  return VRAG_OK;
+  return publish_lists(ix, size, st);
+}
+
+int vrag_ivf_index_remap(vrag_ivf_index* ix, const uint32_t* keep_words, int64_t n_keep) {
+  ARG_CHECK(ix, "null argument");
+  ARG_CHECK(n_keep >= 0 && (keep_words || n_keep == 0), "bad row bitmap (null words or a negative length)");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  ARG_CHECK(ix->synced, "ivf index has no lists yet (sync first)");
+  ARG_CHECK(n_keep >= ix->n_assigned, "the bitmap covers %lld rows, the lists hold %lld", (long long)n_keep, (long long)ix->n_assigned);
+  // The lists are built from the per-row assignments (h_assign, row order): the assignments of the rows that stay, in order, are
+  // the assignments of the renumbered rows -- the map is monotonic, so every list keeps its rows' ascending order.
+  long long kept = 0;
+  for (long long r = 0; r < ix->n_assigned; ++r)
+    if ((keep_words[r >> 5] >> (r & 31)) & 1u) ix->h_assign[(size_t)kept++] = ix->h_assign[(size_t)r];
+  ix->h_assign.resize((size_t)kept);
+  HIP_TRY(hipSetDevice(ix->device));
+  return publish_lists(ix, kept, ix->stream);
 }
 
 int vrag_ivf_index_stats(vrag_ivf_index* ix, int32_t* nlist, int64_t* n_assigned, int64_t* largest_list) {

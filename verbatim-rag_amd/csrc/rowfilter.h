@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "common.h"
+#include "compact.h"
 #include "host_util.h"
 
 namespace vrag {
@@ -51,4 +52,5 @@ struct vrag_row_filter {
   std::mutex mu;
   std::vector<vrag::FilterColumn> cols;
   vrag::DevArray<unsigned> d_tables, d_out;   // scratch of one eval (grown on demand)
+  vrag::CompactScratch compact;               // vrag_row_filter_compact: its bitmap, row list and bounce buffer
 };

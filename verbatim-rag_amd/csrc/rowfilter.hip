@@ -197,6 +197,29 @@ int vrag_row_filter_rows(vrag_row_filter* f, int32_t col, int64_t* n) {
   return VRAG_OK;
 }
 
+// Drops the rows whose bit is cleared from every column, in place (csrc/compact.h).  Columns are extended lazily, so a column may
+// hold fewer rows than the bitmap covers: its rows are compacted under the bitmap's prefix.  The dictionaries hold strings, not rows.
+int vrag_row_filter_compact(vrag_row_filter* f, const uint32_t* keep_words, int64_t n_keep) {
+  ARG_CHECK(f, "null argument");
+  ARG_CHECK(n_keep >= 0 && (keep_words || n_keep == 0), "bad row bitmap (null words or a negative length)");
+  std::lock_guard<std::mutex> lk(f->mu);
+  for (const FilterColumn& c : f->cols)
+    ARG_CHECK(c.n <= n_keep, "the bitmap covers %lld rows, a column holds %lld", (long long)n_keep, (long long)c.n);
+  if (n_keep == 0 || f->cols.empty()) return VRAG_OK;
+  HIP_TRY(hipSetDevice(f->device));
+  int rc;
+  if ((rc = compact_plan(f->compact, keep_words, n_keep, f->stream))) return rc;
+  if (f->compact.n_keep == n_keep) return VRAG_OK;   // nothing to drop: no launch
+  for (FilterColumn& c : f->cols) {
+    if (c.n == 0) continue;
+    if ((rc = compact_rows(f->compact, c.kinds.p, 1, c.n, f->stream))) return rc;
+    if ((rc = compact_rows(f->compact, c.payload.p, sizeof(u64), c.n, f->stream))) return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(f->stream));
+  for (FilterColumn& c : f->cols) c.n = f->compact.kept_before(c.n);
+  return VRAG_OK;
+}
+
 }  // extern "C"
 
 // vrag_row_filter_eval and _eval_matched (`who` names the one called): the latter's matches fill their leaves' tables in device

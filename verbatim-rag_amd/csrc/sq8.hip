@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "common.h"
+#include "compact.h"
 #include "host_util.h"
 #include "topk_kernels.h"
 
@@ -341,6 +342,7 @@ struct vrag_sq8_index {
   DevArray<u64> d_cand, d_out, d_bound;
   DevArray<unsigned> d_allow;
   std::vector<unsigned> h_allow;
+  CompactScratch compact;   // vrag_sq8_index_compact: its bitmap, row list and bounce buffer
 };
 
 namespace {
@@ -525,6 +527,29 @@ int vrag_sq8_index_read(vrag_sq8_index* ix, int64_t first_row, int64_t n, int8_t
     HIP_TRY(hipMemcpy2D(codes, (size_t)ix->dim, ix->codes.p + (size_t)first_row * ix->stride, (size_t)ix->stride, (size_t)ix->dim, (size_t)n,
                         hipMemcpyDeviceToHost));
   if (scales) HIP_TRY(hipMemcpy(scales, ix->scales.p + first_row, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  return VRAG_OK;
+}
+
+// Drops the rows whose bit is cleared, in place (csrc/compact.h): the codes at their padded stride (a multiple of 16 bytes) and the
+// scales.  Every search of this handle returns host lists and has drained its stream before it let go of the lock.
+int vrag_sq8_index_compact(vrag_sq8_index* ix, const uint32_t* keep_words, int64_t n_keep, int64_t* new_size) {
+  ARG_CHECK(ix && new_size, "null argument");
+  ARG_CHECK(n_keep >= 0 && (keep_words || n_keep == 0), "bad row bitmap (null words or a negative length)");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  ARG_CHECK(n_keep == ix->size, "the bitmap covers %lld rows, the index holds %lld", (long long)n_keep, (long long)ix->size);
+  *new_size = ix->size;
+  if (n_keep == 0) return VRAG_OK;
+  HIP_TRY(hipSetDevice(ix->device));
+  hipStream_t st = ix->stream;
+  int rc;
+  if ((rc = compact_plan(ix->compact, keep_words, n_keep, st))) return rc;
+  if (ix->compact.n_keep == n_keep) return VRAG_OK;   // nothing to drop: no launch
+  HIP_TRY(hipDeviceSynchronize());   // a search on a caller's stream has returned, so it has drained; this is the belt to that
+  if ((rc = compact_rows(ix->compact, ix->codes.p, (size_t)ix->stride, n_keep, st))) return rc;
+  if ((rc = compact_rows(ix->compact, ix->scales.p, sizeof(float), n_keep, st))) return rc;
+  HIP_TRY(hipStreamSynchronize(st));   // the new size is published once every row stands where it belongs
+  ix->size = ix->compact.n_keep;
+  *new_size = ix->size;
   return VRAG_OK;
 }
 

@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "common.h"
+#include "compact.h"
 #include "gemm_bf16.h"
 #include "host_util.h"
 #include "topk_kernels.h"
@@ -2256,80 +2257,7 @@ __global__ void topk_fill_empty_kernel(float* __restrict__ scores, long long* __
 // reads a bitmap.  Dense: the bitmap is compacted into the ascending list of passing rows (popcount + prefix scan, no atomic
 // appends: the list is the same on every run), then the exact chains run over that list only -- cost proportional to the
 // passing rows, not to the shard.  Sparse: the single-query SELL walk with the top-k insertion gated by the document's bit.
-constexpr int FWORDS = 1024;   // bitmap words per workgroup of the compaction (256 threads x one 16-byte load)
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// words: the bitmap padded with zero words to a multiple of FWORDS (the host clears the bits at and beyond the row count), so no
-// kernel below tests a bound.  blk_cnt[b] = set bits of workgroup b's words.
-__global__ __launch_bounds__(256) void filter_count_kernel(const unsigned* __restrict__ words, unsigned* __restrict__ blk_cnt) {
-  __shared__ unsigned red[4];
-  const int tid = threadIdx.x;
-  const u32x4 w = reinterpret_cast<const u32x4*>(words)[(size_t)blockIdx.x * 256 + tid];
-  unsigned c = __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if ((tid & 63) == 0) red[tid >> 6] = c;
-  __syncthreads();
-  if (tid == 0) blk_cnt[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-// Inclusive prefix sum of one value per thread over the 256 threads of a workgroup (wave scans + the four wave totals in LDS).
-__device__ __forceinline__ unsigned block_scan_incl(unsigned v, unsigned* wave_tot) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned up = __shfl_up(v, o, 64);
-    if (lane >= o) v += up;
-  }
-  if (lane == 63) wave_tot[wave] = v;
-  __syncthreads();
-  unsigned base = 0;
-  for (int w = 0; w < wave; ++w) base += wave_tot[w];
-  __syncthreads();   // wave_tot may be rewritten by the caller's next round
-  return v + base;
-}
-
-// One workgroup: blk_off[b] = passing rows in front of workgroup b's words, blk_off[n_blk] = all of them (the list's count).
-__global__ __launch_bounds__(256) void filter_scan_kernel(const unsigned* __restrict__ blk_cnt, int n_blk, unsigned* __restrict__ blk_off) {
-  __shared__ unsigned wave_tot[4];
-  __shared__ unsigned carry_s;
-  const int tid = threadIdx.x;
-  if (tid == 0) carry_s = 0u;
-  __syncthreads();
-  for (int b0 = 0; b0 < n_blk; b0 += 256) {
-    const int b = b0 + tid;
-    const unsigned c = b < n_blk ? blk_cnt[b] : 0u;
-    const unsigned incl = block_scan_incl(c, wave_tot);
-    const unsigned carry = carry_s;
-    if (b < n_blk) blk_off[b] = carry + incl - c;
-    __syncthreads();
-    if (tid == 255) carry_s = carry + incl;
-    __syncthreads();
-  }
-  if (tid == 0) blk_off[n_blk] = carry_s;
-}
-
-// The list itself: thread t of workgroup b writes the rows of its four words behind blk_off[b] + (set bits of the threads in
-// front of it) -- words ascending, bits ascending, so the list is ascending.  A workgroup without a set bit leaves before its
-// loads (a zero word costs the one load of the count pass).
-__global__ __launch_bounds__(256) void filter_emit_kernel(const unsigned* __restrict__ words, const unsigned* __restrict__ blk_cnt,
-                                                           const unsigned* __restrict__ blk_off, unsigned* __restrict__ list) {
-  __shared__ unsigned wave_tot[4];
-  if (blk_cnt[blockIdx.x] == 0u) return;
-  const int tid = threadIdx.x;
-  const size_t w0 = ((size_t)blockIdx.x * 256 + tid) * 4;
-  const u32x4 w = reinterpret_cast<const u32x4*>(words)[(size_t)blockIdx.x * 256 + tid];
-  const unsigned c = __popc(w[0]) + __popc(w[1]) + __popc(w[2]) + __popc(w[3]);
-  size_t pos = (size_t)blk_off[blockIdx.x] + block_scan_incl(c, wave_tot) - c;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    unsigned bits = w[j];
-    while (bits) {
-      list[pos++] = (unsigned)((w0 + j) * 32) + (unsigned)__builtin_ctz(bits);
-      bits &= bits - 1u;
-    }
-  }
-}
+// The bitmap-to-list kernels are csrc/compact.hip's (`bitmap_row_list`): the index compaction builds the same list.
 
 // Exact keys of a row list: FROWS rows x FQT queries per workgroup step.  As in prefilter_rescore_list_kernel what costs is
 // fetching the scattered rows: all 256 threads stage FCH columns of the FROWS rows and of the workgroup's queries through LDS in
@@ -2537,6 +2465,10 @@ struct vrag_dense_index {
   // offsets ([n] counts, then [n + 1] offsets: the last one is the list's length) and the ascending list of passing rows
   std::vector<unsigned> h_allow;
   DevArray<unsigned> d_fallow, d_fblk, d_flist;
+  // vrag_dense_index_compact: its bitmap, row list and bounce buffer; and whether the resident queries and scratch of the last
+  // search still describe this index's rows (a compaction renumbers them: run_resident is refused until the next search)
+  CompactScratch compact;
+  bool resident_stale = false;
 };
 
 namespace vrag {
@@ -3250,6 +3182,7 @@ int vrag_dense_index_search(vrag_dense_index* ix, const float* queries, int32_t 
   ARG_CHECK(ix && queries && scores && ids && nq > 0, "bad arguments");
   ARG_CHECK(k > 0 && k <= KPAGED_MAX, "k must be in [1, %d] (got %d)", KPAGED_MAX, k);
   std::lock_guard<std::mutex> lk(ix->mu);
+  ix->resident_stale = false;   // this call uploads its own queries and rebuilds the scratch it reads
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ix->stream;
   if (ix->lists_done) HIP_TRY(hipStreamWaitEvent(st, ix->lists_done, 0));
@@ -3339,18 +3272,6 @@ int vrag_dense_index_search(vrag_dense_index* ix, const float* queries, int32_t 
   return VRAG_OK;
 }
 
-// Host staging of a caller's bitmap for the filtered searches: the words of rows [0, n_rows) with the bits at and beyond n_rows
-// cleared, then zero words up to a multiple of `pad`.  Returns the number of set bits.
-static long long stage_allow(std::vector<unsigned>& h, const uint32_t* allow, long long n_rows, size_t pad) {
-  const size_t n_words = (size_t)((n_rows + 31) / 32);
-  h.assign((n_words + pad - 1) / pad * pad, 0u);
-  std::memcpy(h.data(), allow, n_words * sizeof(unsigned));
-  if (n_rows % 32) h[n_words - 1] &= (1u << (n_rows % 32)) - 1u;
-  long long n_pass = 0;
-  for (size_t i = 0; i < n_words; ++i) n_pass += __builtin_popcount(h[i]);
-  return n_pass;
-}
-
 static void fill_no_hits(float* scores, int64_t* ids, size_t n) {
   for (size_t i = 0; i < n; ++i) {
     scores[i] = -INFINITY;
@@ -3365,11 +3286,12 @@ int vrag_dense_index_search_filtered(vrag_dense_index* ix, const float* queries,
   ARG_CHECK(k > 0 && k <= KPAGED_MAX, "k must be in [1, %d] (got %d)", KPAGED_MAX, k);
   ARG_CHECK(n_allow >= 0 && (allow || n_allow == 0), "bad row bitmap (null words or a negative length)");
   std::lock_guard<std::mutex> lk(ix->mu);
+  ix->resident_stale = false;   // this call uploads its own queries and rebuilds the scratch it reads
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ix->stream;
   if (ix->lists_done) HIP_TRY(hipStreamWaitEvent(st, ix->lists_done, 0));
   const long long n_rows = std::min<long long>(n_allow, ix->size);   // rows appended after the mask was built are not in it
-  const long long n_pass = n_rows > 0 ? stage_allow(ix->h_allow, allow, n_rows, FWORDS) : 0;
+  const long long n_pass = n_rows > 0 ? stage_bitmap(ix->h_allow, allow, n_rows, FWORDS) : 0;
   if (n_pass == 0) {   // nothing passes: no launch
     fill_no_hits(scores, ids, (size_t)nq * k);
     return VRAG_OK;
@@ -3388,12 +3310,8 @@ int vrag_dense_index_search_filtered(vrag_dense_index* ix, const float* queries,
   if (!ix->upload_done) HIP_TRY(hipEventCreateWithFlags(&ix->upload_done, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(ix->upload_done, st));
   ix->resident_split = 0;   // d_q holds these queries now, as plain fp32 rows
-  unsigned* blk_cnt = ix->d_fblk.p;
-  unsigned* blk_off = ix->d_fblk.p + n_blk;
-  hipLaunchKernelGGL(filter_count_kernel, dim3(n_blk), dim3(256), 0, st, ix->d_fallow.p, blk_cnt);
-  hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(256), 0, st, blk_cnt, n_blk, blk_off);
-  hipLaunchKernelGGL(filter_emit_kernel, dim3(n_blk), dim3(256), 0, st, ix->d_fallow.p, blk_cnt, blk_off, ix->d_flist.p);
-  HIP_TRY(hipGetLastError());
+  unsigned* blk_off = ix->d_fblk.p + n_blk;   // [n_blk + 1] offsets behind the [n_blk] counts
+  HIP_TRY(bitmap_row_list(ix->d_fallow.p, n_blk, ix->d_fblk.p, ix->d_flist.p, st));
   HIP_TRY(hipEventSynchronize(ix->upload_done));   // the caller's queries and the staged bitmap have been consumed
   auto run = [&](const u64* bound) -> int {
     const dim3 grid(n_wg, (nq + FQT - 1) / FQT);
@@ -3423,6 +3341,7 @@ int vrag_dense_index_search_device(vrag_dense_index* ix, const float* queries, i
   ARG_CHECK(k > 0, "k must be in [1, %d] for a device-resident search (got %d)", KMAX, k);
   ARG_CHECK(!row_map || n_map >= 0, "negative row map length");
   std::lock_guard<std::mutex> lk(ix->mu);
+  ix->resident_stale = false;   // this call uploads its own queries and rebuilds the scratch it reads
   HIP_TRY(hipSetDevice(ix->device));
   // NULL = the legacy default stream, NOT the handle's own stream: the caller's next operation (the all-gather) is
   // ordered against the stream it named, and torch's default stream IS the null stream
@@ -3464,6 +3383,7 @@ int vrag_dense_index_run_resident(vrag_dense_index* ix, int32_t nq, int32_t k, v
   ARG_CHECK(ix && nq > 0 && k > 0 && k <= KMAX, "bad arguments");
   std::lock_guard<std::mutex> lk(ix->mu);
   ARG_CHECK(ix->d_q.p && ix->d_q.n >= (size_t)nq * ix->dim && ix->size > 0, "call vrag_dense_index_search once first");
+  ARG_CHECK(!ix->resident_stale, "the index was compacted since the last search: call vrag_dense_index_search once first");
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ix->stream;
   if (dense_plan(ix, nq, k, DenseCaller::Resident, ix->resident_split) == DenseRoute::Tiled) {
@@ -3473,6 +3393,54 @@ int vrag_dense_index_run_resident(vrag_dense_index* ix, int32_t nq, int32_t k, v
   const int n_wg = dense_n_wg(ix->dtype, ix->dim, nq, k, ix->size);
   ARG_CHECK(ix->d_cand.n >= (size_t)n_wg * nq * k && ix->d_out.n >= (size_t)nq * k + nq, "scratch too small");
   return dense_scan_enqueue(ix, nq, k, st, ix->resident_split);
+}
+
+// Drops the rows whose bit is cleared, in place (csrc/compact.h): the rows and, for an index with a prefilter image, the image.
+// The image's norm and error bounds (d_norm2 / pf_stats) are maxima over every row the index has held: still upper bounds of the
+// rows that stay, and the searches' results do not depend on how tight they are.
+int vrag_dense_index_compact(vrag_dense_index* ix, const uint32_t* keep_words, int64_t n_keep, int64_t* new_size) {
+  ARG_CHECK(ix && new_size, "null argument");
+  ARG_CHECK(n_keep >= 0 && (keep_words || n_keep == 0), "bad row bitmap (null words or a negative length)");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  ARG_CHECK(n_keep == ix->size, "the bitmap covers %lld rows, the index holds %lld", (long long)n_keep, (long long)ix->size);
+  *new_size = ix->size;
+  if (n_keep == 0) return VRAG_OK;
+  HIP_TRY(hipSetDevice(ix->device));
+  hipStream_t st = ix->stream;
+  int rc;
+  if ((rc = compact_plan(ix->compact, keep_words, n_keep, st))) return rc;
+  if (ix->compact.n_keep == n_keep) return VRAG_OK;   // nothing to drop: no launch
+  // searches that only enqueue (vrag_dense_index_search_device, _run_resident) may still be reading the rows on the caller's stream
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t esz = ix->dtype == 0 ? 2 : 4;
+  if ((rc = compact_rows(ix->compact, ix->rows.p, (size_t)ix->dim * esz, n_keep, st))) return rc;
+  if (ix->rows16.p && (rc = compact_rows(ix->compact, ix->rows16.p, (size_t)ix->dim * 2, n_keep, st))) return rc;
+  HIP_TRY(hipStreamSynchronize(st));   // the new size is published once every row stands where it belongs
+  ix->size = ix->compact.n_keep;
+  ix->resident_stale = true;
+  *new_size = ix->size;
+  return VRAG_OK;
+}
+
+int vrag_dense_index_read(vrag_dense_index* ix, int64_t first_row, int64_t n, float* out) {
+  ARG_CHECK(ix && first_row >= 0 && n >= 0 && (out || n == 0), "bad arguments");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  ARG_CHECK(first_row + n <= ix->size, "rows [%lld, %lld) are not all in the index (size %lld)", (long long)first_row,
+            (long long)(first_row + n), (long long)ix->size);
+  if (n == 0) return VRAG_OK;
+  HIP_TRY(hipSetDevice(ix->device));
+  const size_t cnt = (size_t)n * ix->dim, at = (size_t)first_row * ix->dim;
+  if (ix->dtype == 1) {
+    HIP_TRY(hipMemcpy(out, reinterpret_cast<const float*>(ix->rows.p) + at, cnt * sizeof(float), hipMemcpyDeviceToHost));
+    return VRAG_OK;
+  }
+  std::vector<uint16_t> raw(cnt);   // bf16 rows: widened on the host (a bf16 is the upper half of its fp32)
+  HIP_TRY(hipMemcpy(raw.data(), reinterpret_cast<const uint16_t*>(ix->rows.p) + at, cnt * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < cnt; ++i) {
+    const uint32_t bits = (uint32_t)raw[i] << 16;
+    std::memcpy(out + i, &bits, sizeof(bits));
+  }
+  return VRAG_OK;
 }
 
 int vrag_sparse_index_create(int32_t vocab, int64_t n_docs, const int64_t* indptr, const int32_t* indices,
@@ -3803,7 +3771,7 @@ int vrag_sparse_index_search_filtered(vrag_sparse_index* ix, const int64_t* q_in
     ix->upload_pending = false;
   }
   const long long n_rows = std::min<long long>(n_allow, ix->n_docs);
-  const long long n_pass = n_rows > 0 ? stage_allow(ix->h_allow, allow, n_rows, 1) : 0;
+  const long long n_pass = n_rows > 0 ? stage_bitmap(ix->h_allow, allow, n_rows, 1) : 0;
   if (n_pass == 0) {   // nothing passes: no launch
     fill_no_hits(scores, ids, (size_t)nq * k);
     return VRAG_OK;

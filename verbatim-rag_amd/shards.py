@@ -91,6 +91,14 @@ def _search_call(lib, fn: str, head: tuple, nq: int, k: int, allow, stream) -> T
     return scores, ids
 
 
+def _compact_call(lib, fn: str, handle, keep: np.ndarray) -> int:
+    """`fn(handle, keep bitmap, len(keep), &new_size)` -> new size."""
+    keep = np.asarray(keep, dtype=bool).reshape(-1)
+    words, new_size = _bitmap(keep), C.c_int64()
+    _lib.check(fn, getattr(lib, fn)(handle, _vp(words) if len(words) else None, len(keep), C.byref(new_size)))
+    return new_size.value
+
+
 class DenseShard(_Handle):
     """One GPU's slice of the dense corpus (rows appended in order; ids are local row numbers)."""
 
@@ -147,6 +155,18 @@ class DenseShard(_Handle):
     def run_resident(self, nq: int, k: int, stream=None) -> None:
         _lib.check("vrag_dense_index_run_resident", self._lib.vrag_dense_index_run_resident(self._h, nq, k, stream))
 
+    def compact(self, keep: np.ndarray) -> int:
+        """Drops the rows whose `keep` (bool per row, `len(self)` of them) is False, in place in HBM, order kept
+        (`vrag_dense_index_compact`); returns the new size.  An IVF overlay is renumbered with `IvfOverlay.remap(keep)` afterwards."""
+        return _compact_call(self._lib, "vrag_dense_index_compact", self._h, keep)
+
+    def read(self, first_row: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Rows `[first_row, first_row + n)` as float32 `[n, dim]` (bf16 rows widened); `n=None`: up to the end."""
+        n = len(self) - first_row if n is None else int(n)
+        out = np.empty((max(n, 0), self.dim), np.float32)
+        _lib.check("vrag_dense_index_read", self._lib.vrag_dense_index_read(self._h, int(first_row), n, _fp(out)))
+        return out
+
     def close(self):
         ivf, self.ivf = getattr(self, "ivf", None), None
         if ivf is not None:
@@ -185,6 +205,10 @@ class Sq8Shard(_Handle):
         codes, scales = np.empty((max(n, 0), self.dim), np.int8), np.empty(max(n, 0), np.float32)
         _lib.check("vrag_sq8_index_read", self._lib.vrag_sq8_index_read(self._h, int(first_row), n, _vp(codes), _vp(scales)))
         return codes, scales
+
+    def compact(self, keep: np.ndarray) -> int:
+        """`DenseShard.compact` for SQ8 rows: codes and scales move in place (`vrag_sq8_index_compact`); returns the new size."""
+        return _compact_call(self._lib, "vrag_sq8_index_compact", self._h, keep)
 
     def set_route(self, route: int) -> None:
         """0 = automatic, 1 = scan kernel, 2 = tile kernel: the same bits either way (a unit-test and tuning knob)."""
@@ -239,6 +263,13 @@ class IvfOverlay(_Handle):
         _lib.check("vrag_ivf_index_read", self._lib.vrag_ivf_index_read(self._h, _fp(cent), _vp(off), _vp(rows) if len(rows) else None))
         return cent, off, rows
 
+    def remap(self, keep: np.ndarray) -> None:
+        """After `DenseShard.compact(keep)` of the shard, with the same `keep`: the lists' rows are renumbered, dropped rows
+        leave their lists, the centroids stay (`vrag_ivf_index_remap`)."""
+        keep = np.asarray(keep, dtype=bool).reshape(-1)
+        words = _bitmap(keep)
+        _lib.check("vrag_ivf_index_remap", self._lib.vrag_ivf_index_remap(self._h, _vp(words) if len(words) else None, len(keep)))
+
     def search(self, queries: np.ndarray, k: int, nprobe: int, stream=None, scanned: bool = False):
         """(scores `[Q, k]`, ids `[Q, k]`) -- exact scores of the best rows of the `nprobe` nearest lists; with
         `scanned=True` also the rows each query's lists hold."""
@@ -278,6 +309,13 @@ class RowFilter(_Handle):
         n = C.c_int64()
         _lib.check("vrag_row_filter_rows", self._lib.vrag_row_filter_rows(self._h, int(col), C.byref(n)))
         return n.value
+
+    def compact(self, keep: np.ndarray) -> None:
+        """Drops the rows whose `keep` is False from every column, in place, order kept (`vrag_row_filter_compact`); a column
+        that holds fewer rows than `keep` covers is compacted under its prefix.  The dictionaries stay."""
+        keep = np.asarray(keep, dtype=bool).reshape(-1)
+        words = _bitmap(keep)
+        _lib.check("vrag_row_filter_compact", self._lib.vrag_row_filter_compact(self._h, _vp(words) if len(words) else None, len(keep)))
 
     def append_strings(self, col: int, data: np.ndarray, off: np.ndarray) -> None:
         """Appends strings to the column's dictionary: string i = the UTF-8 bytes data[off[i]:off[i + 1]], off[0] = 0; codes

@@ -94,6 +94,13 @@ class MetaColumn:
                                                        np.asarray(others, dtype=np.uint64))
         self._n += m
 
+    def compact(self, keep: np.ndarray) -> None:
+        """Drops the rows whose `keep` is False, order kept.  The dictionary stays: codes keep their meaning (and the device copy
+        its strings), a string no row holds any more simply matches no row."""
+        at = np.nonzero(np.asarray(keep, dtype=bool)[: self._n])[0]
+        self._kinds, self._payload = self._kinds[: self._n][at].copy(), self._payload[: self._n][at].copy()
+        self._n = len(at)
+
     def string_bytes(self, first: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """The dictionary from code `first` on as the device holds it (vrag_row_filter_append_strings): (uint8 UTF-8 bytes,
         int64 offsets `[codes + 1]` from 0), code `first + i` = bytes[off[i]:off[i + 1]].  Only for an `encodable` column."""

@@ -12,6 +12,7 @@ all-gathered and merged in distributed.py (ShardedTopK).
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import json
 import logging
 import threading
@@ -297,6 +298,16 @@ def check_index_config(index_type: str, nlist: int, nprobe: int, sharded: bool) 
         raise ValueError("index_type='IVF_FLAT' is single-GPU: sharded stores (distributed=True or a comm) keep FLAT")
 
 
+def check_auto_compact(auto_compact: Optional[float], sharded: bool) -> None:
+    """The constructor's refusals for `auto_compact` (pure: no device needed)."""
+    if auto_compact is None:
+        return
+    if isinstance(auto_compact, bool) or not isinstance(auto_compact, (int, float, np.floating)) or not 0 < auto_compact < 1:
+        raise ValueError(f"auto_compact must be None or a fraction in (0, 1) (got {auto_compact!r})")
+    if sharded:
+        raise ValueError("auto_compact is single-GPU: sharded stores (distributed=True or a comm) are not compacted")
+
+
 DENSE_DTYPES = ("f32", "bf16", "int8")
 
 
@@ -440,6 +451,29 @@ def _merge_parts(scores: np.ndarray, rows: np.ndarray, k: int, device: int) -> T
 
 
 
+def _one_epoch(method):
+    """A `GpuVectorStore` search method answered from ONE epoch of the store (class docstring, "Compaction"): answered again from
+    scratch when a compaction ran meanwhile.  The epoch is read under the lock, which a running compaction holds from its first
+    change to its last; an exception counts as a moved epoch when the epoch has moved (a stale row number can point past the
+    shortened columns)."""
+
+    @functools.wraps(method)
+    def answered(self, *args, **kwargs):
+        while True:
+            with self._mu:
+                epoch = self._epoch
+            try:
+                out = method(self, *args, **kwargs)
+            except Exception:
+                if self._epoch == epoch:
+                    raise
+                continue
+            if self._epoch == epoch:
+                return out
+
+    return answered
+
+
 # ---------------------------------------------------------------------------- the store
 class GpuVectorStore(VectorStore):
     """Exact GPU search store with BaseMilvusStore's behaviour (milvus_base.py:90-127,189-459).
@@ -477,6 +511,18 @@ class GpuVectorStore(VectorStore):
     the ranks once after every insert / delete / load and the `df` vector of a query batch once per batch
     (`ShardComm.sum_int64`, exact integers), so every rank scores its rows with the corpus-wide statistics -- the bits of
     the single-GPU store -- and the lists merge like the other methods'.
+
+    Compaction: `delete` only clears a row's liveness bit; `compact()` drops the dead rows from every host column and every
+    device structure and renumbers the survivors `0 .. live - 1` in their old order -- the state `load(save())` would produce,
+    except that the resident dense rows (fp32 / bf16 rows, the prefilter image, SQ8 codes and scales) are compacted where they
+    lie in HBM (`DenseShard.compact`: no re-upload, no second copy) and an IVF overlay keeps its centroids
+    (`IvfOverlay.remap`).  The sparse images and the full-text index are rebuilt from the compacted host copies by the next
+    flush, as a fold rebuilds them.  Never implicit unless `auto_compact` is set.  Single-GPU.
+    Searches run outside the lock and decode row numbers after the device returns, and a compaction changes what a row number
+    means, so the store keeps an EPOCH: `compact()` advances it under the lock before it touches anything; `query` /
+    `query_batch` read it under the lock when they start and again when they have their answer, and answer again from scratch
+    when it has moved (an exception met on the way counts as a moved epoch when it has).  An answer is therefore entirely
+    from before a compaction or entirely from after it.  The device handles serialise a search's kernels against the move itself.
     """
 
     enable_full_text = False  # per store: the constructor's `enable_full_text`
@@ -509,7 +555,8 @@ class GpuVectorStore(VectorStore):
                  group=None, comm=None, payload: str = "sharded", dense_headroom: float = 1.5,
                  dense_prefilter="auto", enable_full_text: bool = False, bm25_k1: float = 1.2, bm25_b: float = 0.75,
                  filter_route: str = "subset", rrf_route: str = "host", index_type: str = "FLAT", nlist: int = 8192,
-                 nprobe: int = 16, filter_eval: str = "host", filter_strings: str = "host"):
+                 nprobe: int = 16, filter_eval: str = "host", filter_strings: str = "host",
+                 auto_compact: Optional[float] = None):
         """`enable_full_text`: BM25 keyword search over the raw texts (milvus_cloud.py: bm25_k1 = 1.2, bm25_b = 0.75),
         `search_type="full_text"` and the third leg of a weighted hybrid search; the texts are tokenised, indexed and
         scored on the device (`TextIndex`).  Off by default.  On a sharded store (`distributed=True` or a `comm`) the
@@ -551,7 +598,10 @@ class GpuVectorStore(VectorStore):
         and keeps stores under `IVF_MIN_ROWS` rows FLAT) -- approximate in WHICH rows it finds, exact in their scores and
         order.  `search_params={"nprobe": n}` (or Milvus' `{"params": {"nprobe": n}}`) of `query` / `query_batch` overrides
         `nprobe` per call; n >= nlist returns the FLAT results.  Lists of more than 64 rows per method, filtered queries left
-        short and sharded stores search FLAT.  Kept in a saved store's manifest (FLAT stores write nothing new)."""
+        short and sharded stores search FLAT.  Kept in a saved store's manifest (FLAT stores write nothing new).
+        `auto_compact`: None (default) = `compact()` runs only when it is called.  A fraction in (0, 1): `delete` calls it once
+        the dead rows exceed that fraction of the stored rows.  Single-GPU like `compact()`; a run-time choice, a keyword of `load`."""
+        check_auto_compact(auto_compact, distributed or comm is not None)
         check_index_config(index_type, nlist, nprobe, distributed or comm is not None)
         check_dense_dtype(dense_dtype, index_type, distributed or comm is not None)
         self._lib = _lib.load()
@@ -597,6 +647,8 @@ class GpuVectorStore(VectorStore):
         self.filter_eval = filter_eval
         self.filter_strings = filter_strings
         self.index_type, self.nlist, self.nprobe = index_type, int(nlist), int(nprobe)
+        self.auto_compact = None if auto_compact is None else float(auto_compact)
+        self._epoch = 0              # advanced by every compaction, under the lock (class docstring)
         self._ivf_trained_rows = 0   # rows in the shard when its overlay was last trained (0 = no overlay)
         # the route searches take: the filtered search returns host lists, which the device-resident exchange does not carry.
         # Replicated configuration only, so every rank decides alike.
@@ -792,6 +844,67 @@ class GpuVectorStore(VectorStore):
             self._text_live_stale = True
             self._text_totals = None
             self._drop_subsets()
+            if self.auto_compact is not None and len(alive) and 1.0 - float(alive.mean()) > self.auto_compact:
+                self.compact()
+
+    def compact(self) -> int:
+        """Drops every deleted row from the host columns and the device structures (class docstring, "Compaction"); returns the
+        number of rows reclaimed.  The rows that stay keep their order and are renumbered `0 .. len(self) - 1`.  Returns 0 and
+        touches nothing when no row is dead.  Rows inserted since the last flush are flushed first, so that the device holds
+        exactly the rows the bitmap speaks of.  ValueError on a sharded store."""
+        if self._comm is not None:
+            raise ValueError("compact() is single-GPU: sharded stores (distributed=True or a comm) keep their deleted rows until a save / load")
+        with self._mu:
+            keep = self._alive.data.copy()
+            n, live = len(keep), int(keep.sum())
+            if live == n:
+                return 0
+            self._flush()
+            self._epoch += 1                     # before anything moves: a search that sees any of it answers again
+            at = np.nonzero(keep)[0]
+            # device: the dense rows in place, the overlay renumbered, the filter columns in place; sparse images and the
+            # full-text index are dropped and rebuilt by the next flush from the compacted host copies (a SELL image is
+            # sorted by row length and the BM25 postings by term: removing rows is a rebuild either way)
+            if self._dense is not None:
+                self._dense.compact(keep)
+                overlay = getattr(self._dense, "ivf", None)
+                if overlay is not None:
+                    overlay.remap(keep)
+                self._dense_flushed = live
+            if self._row_filter is not None:
+                self._row_filter.compact(keep)
+            self._sparse_parts, self._sparse_flushed = [], 0
+            self._text, self._text_flushed, self._text_main = None, 0, 0
+            self._text_live_stale, self._text_totals = True, None
+            # host columns
+
+            def take(col):
+                box = np.empty(len(col), dtype=object)
+                box[:] = col
+                return box[at].tolist()
+
+            self._ids, self._texts, self._enh, self._meta = take(self._ids), take(self._texts), take(self._enh), take(self._meta)
+            self._alive = _Column(bool, first=np.ones(live, dtype=bool))
+            self._owned = _Column(np.int64, first=np.arange(live, dtype=np.int64))
+            self._main_rows = self._owned.data
+            if self._dense_rows is not None:
+                rows = _Column(np.float32, self.dense_dim)
+                rows.extend(self._dense_rows.data[at], adopt=True)
+                self._dense_rows = rows
+            if self.enable_sparse:
+                ptr, idx, val = csr_take_rows(self._sp_ptr.data, self._sp_idx.data, self._sp_val.data, at)
+                self._sp_ptr, self._sp_idx, self._sp_val = _Column(np.int64, first=ptr), _Column(np.int32, first=idx), _Column(np.float32, first=val)
+            for column in self._meta_columns.values():
+                column.compact(keep)
+            # what a load would derive from the surviving rows
+            self._value_indexes = {}
+            self._id_rows = None
+            self._all_ids_truthy = all(bool(x) for x in self._ids)
+            self._ids_unique, self._id_seen = True, set()
+            self._note_unique(self._ids)
+            self._drop_subsets()
+            self._dirty = self.enable_sparse or self.enable_full_text
+            return n - live
 
     def _sparse_slice(self, a: int, b: int):
         """CSR of local rows [a, b)."""
@@ -1380,6 +1493,7 @@ class GpuVectorStore(VectorStore):
             out.append(self._results(merge_hybrid_results(rbm, top_k, weights, rrf_k)))
         return out
 
+    @_one_epoch
     def query_batch(self, dense_queries: Optional[Sequence[Any]] = None, sparse_queries: Optional[Sequence[Any]] = None,
                     text_queries: Optional[Sequence[Optional[str]]] = None, top_k: int = 5, search_type: str = "hybrid",
                     filter: Optional[str] = None, search_params: Optional[Dict[str, Any]] = None,
@@ -1439,6 +1553,7 @@ class GpuVectorStore(VectorStore):
                 logger.warning("Batched hybrid search failed: %s, answering per query", e)
         return [single(i) for i in range(n)]
 
+    @_one_epoch
     def query(self, dense_query=None, sparse_query=None, text_query=None, top_k: int = 5, search_type: str = "hybrid",
               filter: Optional[str] = None, search_params: Optional[Dict[str, Any]] = None,
               hybrid_weights: Optional[Dict[str, float]] = None, rrf_k: int = 60) -> List[SearchResult]:
@@ -1596,10 +1711,10 @@ class GpuVectorStore(VectorStore):
     @classmethod
     def load(cls, path: str, device: int = 0, distributed: bool = False, group=None, comm=None,
              payload: str = "sharded", filter_route: str = "subset", rrf_route: str = "host",
-             filter_eval: str = "host", filter_strings: str = "host") -> "GpuVectorStore":
+             filter_eval: str = "host", filter_strings: str = "host", auto_compact: Optional[float] = None) -> "GpuVectorStore":
         """Reads a directory written by `save` -- by this or an earlier revision (formats 1 - 3), by any number of
         ranks: when the world size differs from the writer's, the saved shards are put back in row order and cut
-        contiguously over the ranks that open the store.  `filter_route`, `rrf_route`, `filter_eval`, `filter_strings`: as the constructor's (not part of a saved store).
+        contiguously over the ranks that open the store.  `filter_route`, `rrf_route`, `filter_eval`, `filter_strings`, `auto_compact`: as the constructor's (not part of a saved store).
         An IVF_FLAT store comes back IVF_FLAT with its `nlist` / `nprobe`; its lists are trained again at the first flush
         (training is deterministic: the same rows give the same lists)."""
         head, ids, shards = cls._read_saved(path)
@@ -1609,7 +1724,7 @@ class GpuVectorStore(VectorStore):
                  dense_prefilter=head.get("dense_prefilter", "auto"), enable_full_text=bool(head.get("enable_full_text", False)),
                  bm25_k1=head.get("bm25_k1", 1.2), bm25_b=head.get("bm25_b", 0.75), filter_route=filter_route,
                  rrf_route=rrf_route, index_type=head.get("index_type", "FLAT"), nlist=head.get("nlist", 8192),
-                 nprobe=head.get("nprobe", 16), filter_eval=filter_eval, filter_strings=filter_strings)
+                 nprobe=head.get("nprobe", 16), filter_eval=filter_eval, filter_strings=filter_strings, auto_compact=auto_compact)
         n = len(ids)
         for owned, *_ in shards:
             if len(owned) and (owned.min() < 0 or owned.max() >= n):
