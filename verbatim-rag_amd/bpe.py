@@ -10,16 +10,13 @@ encodable as UTF-8.  `fallback_count` counts the texts that went that way."""
 from __future__ import annotations
 
 import ctypes as C
-import json
-import os
 import re
 import unicodedata
 from typing import Any, Dict, List, Sequence, Tuple
 
 import numpy as np
 
-from . import _lib
-from .wordpiece import _template_ids
+from .device_tokenizer import DeviceTokenizer, _template_ids
 
 TILE_BYTES = 4096        # VRAG_BPE_TILE_BYTES: text bytes per workgroup of the boundary passes
 MAX_WORD_BYTES = 64      # VRAG_BPE_MAX_WORD_BYTES: a longer pre-token sends its text to the host
@@ -123,20 +120,17 @@ def _i32(values) -> np.ndarray:
     return np.ascontiguousarray(np.asarray(values, np.int32).reshape(-1))
 
 
-class GpuByteBpeTokenizer:
+class GpuByteBpeTokenizer(DeviceTokenizer):
     """`encode_batch(texts)` -> packed int32 ids + lengths, equal to HF's; `encode_batch_offsets(texts)` adds HF's character
     offsets per id; `ids(text, ...)` as `TokenizerAdapter` offers it."""
 
+    parse_spec = staticmethod(parse_spec)
+    _destroy_entry, _encode_entry, _offsets_entry = "vrag_bpe_destroy", "vrag_bpe_encode", "vrag_bpe_encode_offsets"
+
     def __init__(self, spec: dict, hf_tokenizer: Any, device: int = 0, path: str = "tokenizer.json"):
         cfg = parse_spec(spec, path)
-        self._hf = type(hf_tokenizer).from_str(hf_tokenizer.to_str())      # a copy: the caller's keeps its truncation / padding
-        self._hf.no_truncation()
-        self._hf.no_padding()
+        super().__init__(hf_tokenizer, cfg["cls_id"], cfg["sep_id"], cfg["n_vocab"], device)
         self._routed = re.compile("|".join(re.escape(c) for c in cfg["routed"])) if cfg["routed"] else None
-        self.cls_token_id, self.sep_token_id = cfg["cls_id"], cfg["sep_id"]
-        self.vocab_size = cfg["n_vocab"]
-        self.device = int(device)
-        self.fallback_count = 0
         left, right, merged = (_i32(x) for x in cfg["merges"])
         raw = [b for b, _i in cfg["whole"]]
         woff = np.zeros(len(raw) + 1, np.int64)
@@ -144,44 +138,13 @@ class GpuByteBpeTokenizer:
         wblob = b"".join(raw)
         wid = _i32([i for _b, i in cfg["whole"]])
         ip = C.POINTER(C.c_int32)
-        self._lib = _lib.load()
-        _lib.require_gpu()
-        handle = C.c_void_p()
-        _lib.check("vrag_bpe_create", self._lib.vrag_bpe_create(
-            self.vocab_size, left.ctypes.data_as(ip), right.ctypes.data_as(ip), merged.ctypes.data_as(ip), len(left),
-            _i32(cfg["byte_ids"]).ctypes.data_as(ip), _i32(cfg["space_ids"]).ctypes.data_as(ip),
-            C.cast(C.c_char_p(wblob), C.c_void_p), woff.ctypes.data_as(C.POINTER(C.c_int64)), wid.ctypes.data_as(ip), len(raw),
-            self.cls_token_id, self.sep_token_id, (_NFC if cfg["nfc"] else 0) | (_IGNORE_MERGES if cfg["ignore_merges"] else 0),
-            self.device, C.byref(handle)))
-        self._h = handle
+        self._create("vrag_bpe_create", self.vocab_size, left.ctypes.data_as(ip), right.ctypes.data_as(ip), merged.ctypes.data_as(ip),
+                     len(left), _i32(cfg["byte_ids"]).ctypes.data_as(ip), _i32(cfg["space_ids"]).ctypes.data_as(ip),
+                     C.cast(C.c_char_p(wblob), C.c_void_p), woff.ctypes.data_as(C.POINTER(C.c_int64)), wid.ctypes.data_as(ip), len(raw),
+                     self.cls_token_id, self.sep_token_id, (_NFC if cfg["nfc"] else 0) | (_IGNORE_MERGES if cfg["ignore_merges"] else 0))
 
-    @classmethod
-    def from_file(cls, path_or_dir: str, device: int = 0) -> "GpuByteBpeTokenizer":
-        """From a `tokenizer.json` (or the checkpoint directory that holds it).  ValueError naming the component unless the
-        file is the byte-level BPE pipeline `parse_spec` accepts."""
-        from tokenizers import Tokenizer
-
-        path = os.path.join(path_or_dir, "tokenizer.json") if os.path.isdir(path_or_dir) else path_or_dir
-        with open(path, encoding="utf-8") as f:
-            spec = json.load(f)
-        parse_spec(spec, path)      # refuse a wrong file before anything touches the device
-        return cls(spec, Tokenizer.from_file(path), device=device, path=path)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            self._lib.vrag_bpe_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def encode_batch(self, texts: Sequence[str], add_special_tokens: bool = True, max_length: int = 512) -> Tuple[np.ndarray, np.ndarray]:
-        """(ids int32 [sum of lengths], seq_lens int32 [n]): the texts' ids back to back, as `vrag_encoder_load_batch` takes them."""
-        ids, _offsets, seq_lens = self._encode(texts, add_special_tokens, max_length, False)
-        return ids, seq_lens
+    def _goes_to_host(self, texts) -> set:
+        return {d for d, t in enumerate(texts) if self._routed.search(t)} if self._routed is not None else set()
 
     def encode_batch_offsets(self, texts: Sequence[str], add_special_tokens: bool = False,
                              max_length: int = 512) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -189,83 +152,3 @@ class GpuByteBpeTokenizer:
         characters of its own text that HF reports as `Encoding.offsets` (include/vrag_amd.h states the rule; `(0, 0)` for
         [CLS] / [SEP]).  A flagged text takes ids AND offsets from the HF tokenizer."""
         return self._encode(texts, add_special_tokens, max_length, True)
-
-    def _host_encode(self, text: str, add_special_tokens: bool, max_length: int) -> Tuple[List[int], List[Tuple[int, int]]]:
-        enc = self._hf.encode(text, add_special_tokens=False)
-        keep = max_length - 2 if add_special_tokens else max_length
-        ids, offsets = list(enc.ids)[:keep], list(enc.offsets)[:keep]
-        if add_special_tokens:
-            return [self.cls_token_id] + ids + [self.sep_token_id], [(0, 0)] + offsets + [(0, 0)]
-        return ids, offsets
-
-    def _encode(self, texts: Sequence[str], add_special_tokens: bool, max_length: int, with_offsets: bool):
-        texts = list(texts)
-        max_length = int(max_length)
-        if max_length < (2 if add_special_tokens else 0):
-            raise ValueError(f"max_length {max_length} leaves no room for the special tokens")
-        n = len(texts)
-        if n == 0:
-            return np.zeros(0, np.int32), np.zeros((0, 2), np.int32), np.zeros(0, np.int32)
-        if not self._h:
-            raise RuntimeError("GpuByteBpeTokenizer is closed")
-        raw: List[bytes] = []
-        host = set()
-        for d, t in enumerate(texts):
-            try:
-                b = t.encode("utf-8")
-            except UnicodeEncodeError:          # lone surrogates
-                b = None
-            if b is None or (self._routed is not None and self._routed.search(t)):
-                host.add(d)
-                b = b""
-            raw.append(b)
-        off = np.zeros(n + 1, np.int64)
-        np.cumsum([len(b) for b in raw], out=off[1:])
-        blob = b"".join(raw)
-        seq_lens = np.empty(n, np.int32)
-        needs = np.empty(n, np.uint8)
-        n_ids = C.c_int64(0)
-        cap = int(min(len(blob) + 2 * n, max_length * n))   # no text has more ids than bytes (+ 2 specials) or than max_length
-        ids = np.empty(max(cap, 1), np.int32)
-        ip = C.POINTER(C.c_int32)
-        head = (self._h, C.cast(C.c_char_p(blob), C.c_void_p), off.ctypes.data_as(C.POINTER(C.c_int64)), n, 1 if add_special_tokens else 0,
-                max_length, cap, ids.ctypes.data_as(ip))
-        tail = (seq_lens.ctypes.data_as(ip), needs.ctypes.data_as(C.c_void_p), C.byref(n_ids))
-        if with_offsets:
-            offsets = np.empty((max(cap, 1), 2), np.int32)
-            _lib.check("vrag_bpe_encode_offsets", self._lib.vrag_bpe_encode_offsets(*head, offsets.ctypes.data_as(ip), *tail))
-            offsets = offsets[:n_ids.value]
-        else:
-            offsets = None
-            _lib.check("vrag_bpe_encode", self._lib.vrag_bpe_encode(*head, *tail))
-        ids = ids[:n_ids.value]
-        host.update(np.nonzero(needs)[0].tolist())
-        if not host:
-            return ids, offsets, seq_lens
-        self.fallback_count += len(host)
-        starts = np.zeros(n + 1, np.int64)
-        np.cumsum(seq_lens, out=starts[1:])
-        parts, oparts = [], []
-        for d in range(n):
-            if d in host:
-                h_ids, h_off = self._host_encode(texts[d], add_special_tokens, max_length)
-                part = np.asarray(h_ids, np.int32)
-                seq_lens[d] = len(part)
-                if with_offsets:
-                    oparts.append(np.asarray(h_off, np.int32).reshape(-1, 2))
-            else:
-                part = ids[starts[d]:starts[d + 1]]
-                if with_offsets:
-                    oparts.append(offsets[starts[d]:starts[d + 1]])
-            parts.append(part)
-        return (np.concatenate(parts).astype(np.int32, copy=False),
-                np.concatenate(oparts).astype(np.int32, copy=False) if with_offsets else None, seq_lens)
-
-    def ids_batch(self, texts: Sequence[str], max_length: int, add_special_tokens: bool = False) -> List[List[int]]:
-        """As `TokenizerAdapter.ids_batch`: one list of ids per text, from one device batch."""
-        ids, lens = self.encode_batch(texts, add_special_tokens=add_special_tokens, max_length=max_length)
-        cuts = np.cumsum(lens)[:-1]
-        return [part.tolist() for part in np.split(ids, cuts)] if len(lens) else []
-
-    def ids(self, text: str, add_special_tokens: bool, max_length: int) -> List[int]:
-        return self.encode_batch([text], add_special_tokens=add_special_tokens, max_length=max_length)[0].tolist()

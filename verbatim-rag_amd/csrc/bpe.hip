@@ -12,13 +12,14 @@
 //             (symbol, right neighbour) up in an open-addressing table {left, right, rank, merged} in HBM (a dependent,
 //             L2-resident gather: hidden by occupancy -- the kernel holds no LDS and a handful of registers), a butterfly
 //             takes the minimum of (rank, lane), the winning lane takes the merged id and the lanes behind it move up.
-//   pack      token_pack.h, as WordPiece.
+//   pack      token_frame.h, shared with csrc/wordpiece.hip: tokenizer_encode checks and uploads the batch, calls the passes above
+//             and launches the packing kernels of token_pack.h.
 // vrag_bpe_encode_offsets adds, on its own route only (vrag_bpe_encode launches what it always did):
 //   leads     offsets_lead_count_kernel: UTF-8 lead bytes per 16-byte lane, block scan; with the scan of the tile totals this is the
 //             number of code points in front of any byte (lane prefix + tile prefix + a popcount inside the lane's 16 bytes).
 //   merge     offsets_merge_kernel (merge_word<true>) carries a byte width per symbol lane next to `sym`; a wave prefix sum of the surviving widths
 //             gives every id its bytes, the lead counts turn them into code points of its own text.
-//   pack      pack_gather_kernel moves the (start, end) pairs with the ids.
+//   pack      the frame's second pack_gather_kernel moves the (start, end) pairs as the first moved the ids.
 // Integer work only; vector stores only.
 #include "../../include/vrag_amd.h"
 
@@ -31,7 +32,7 @@
 
 #include "common.h"
 #include "host_util.h"
-#include "token_pack.h"
+#include "token_frame.h"
 #include "utf8_text.h"
 
 namespace vrag {
@@ -524,10 +525,7 @@ __global__ __launch_bounds__(256) void offsets_merge_kernel(const unsigned char*
 using namespace vrag;
 using namespace vrag::bpe;
 
-struct vrag_bpe {
-  int device = 0, flags = 0, cls_id = 0, sep_id = 0;
-  hipStream_t stream = nullptr;
-  std::mutex mu;
+struct vrag_bpe : TokenizerBase {
   Tables tb{};
   Greedy greedy{};
   DevArray<uint4> merges;
@@ -535,26 +533,13 @@ struct vrag_bpe {
   DevArray<unsigned char> lg, cons, whole_blob;
   DevArray<uint2> whole;
   DevArray<unsigned> whole_off;
-  // workspace of one call, grown on demand
-  DevArray<unsigned char> text, needs, wspace;
-  DevArray<long long> off;
-  DevArray<unsigned> tile_lead, tile_trail, tile_cnt, tile_off, wstart, wdoc, tok_cnt, tok_scan, body, seq_len, out_off;
-  DevArray<int> tok, ids;
+  // workspace of one call beside the frame's, grown on demand
+  DevArray<unsigned char> wspace;
+  DevArray<unsigned> tile_lead, tile_trail;
   // vrag_bpe_encode_offsets only
   DevArray<unsigned> lane_lead, tile_lead_cnt, tile_lead_off;
   DevArray<int2> span, offs;
 };
-
-namespace {
-
-template <typename T>
-hipError_t upload(DevArray<T>& dst, const std::vector<T>& src, hipStream_t st) {
-  hipError_t e = dst.grow(std::max<size_t>(src.size(), 1));
-  if (e == hipSuccess && !src.empty()) e = hipMemcpyAsync(dst.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, st);
-  return e;
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -654,136 +639,62 @@ int vrag_bpe_create(int32_t n_vocab, const int32_t* merge_left, const int32_t* m
   return VRAG_OK;
 }
 
-void vrag_bpe_destroy(vrag_bpe* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  hipStream_t st = h->stream;
-  if (st) (void)hipStreamSynchronize(st);
-  delete h;   // DevArrays free themselves
-  if (st) (void)hipStreamDestroy(st);
-}
+void vrag_bpe_destroy(vrag_bpe* h) { tokenizer_destroy(h); }
 
 // vrag_bpe_encode (offsets == nullptr, `fn` names the entry in messages) and vrag_bpe_encode_offsets.
-static int bpe_encode(const char* fn, vrag_bpe* h, const uint8_t* text, const int64_t* doc_off, int32_t n_docs, int32_t add_special_tokens,
-                      int32_t max_length, int64_t cap, int32_t* ids, int32_t* offsets, int32_t* seq_lens, uint8_t* needs_host, int64_t* n_ids) {
-  ARG_CHECK(h && doc_off && n_ids && n_docs >= 0 && cap >= 0 && (ids || cap == 0), "%s: bad arguments", fn);
-  ARG_CHECK(n_docs == 0 || (seq_lens && needs_host), "%s: null seq_lens / needs_host", fn);
-  ARG_CHECK(max_length >= (add_special_tokens ? 2 : 0), "%s: max_length %d leaves no room%s", fn, max_length,
-            add_special_tokens ? " for the two special tokens" : "");
-  ARG_CHECK(doc_off[0] == 0, "%s: doc_off[0] must be 0", fn);
-  for (int32_t d = 0; d < n_docs; ++d) ARG_CHECK(doc_off[d + 1] >= doc_off[d], "%s: doc_off must be non-decreasing (text %d)", fn, d);
-  const long long n_bytes = doc_off[n_docs];
-  ARG_CHECK(n_bytes <= VRAG_BPE_MAX_BATCH_BYTES, "%s: a batch holds at most %lld bytes of text, got %lld", fn,
-            (long long)VRAG_BPE_MAX_BATCH_BYTES, n_bytes);
-  ARG_CHECK(n_bytes + 2ll * n_docs < 0x7FFFFFF0ll, "%s: text bytes + 2 * n_docs must stay below 2^31", fn);
-  ARG_CHECK(n_bytes == 0 || text, "%s: null text", fn);
-  *n_ids = 0;
-  if (n_docs == 0) return VRAG_OK;
-  const int special = add_special_tokens ? 1 : 0;
-  std::lock_guard<std::mutex> lock(h->mu);
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = h->stream;
-  const long long n_tiles = std::max<long long>(1, (n_bytes + VRAG_BPE_TILE_BYTES - 1) / VRAG_BPE_TILE_BYTES);
-  HIP_TRY(h->text.grow((size_t)n_bytes + 16));
-  HIP_TRY(h->off.grow((size_t)n_docs + 1));
-  HIP_TRY(h->needs.grow((size_t)n_docs));
-  HIP_TRY(h->body.grow((size_t)n_docs));
-  HIP_TRY(h->seq_len.grow((size_t)n_docs));
-  HIP_TRY(h->out_off.grow((size_t)n_docs + 1));
-  HIP_TRY(h->tile_lead.grow((size_t)n_tiles));
-  HIP_TRY(h->tile_trail.grow((size_t)n_tiles));
-  HIP_TRY(h->tile_cnt.grow((size_t)n_tiles));
-  HIP_TRY(h->tile_off.grow((size_t)n_tiles + 1));
-  if (n_bytes) HIP_TRY(hipMemcpyAsync(h->text.p, text, (size_t)n_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->off.p, doc_off, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(h->needs.p, 0, (size_t)n_docs, st));
-  HIP_TRY(hipMemsetAsync(h->body.p, 0, (size_t)n_docs * 4, st));
-  hipLaunchKernelGGL(bpe_tile_runs_kernel, dim3((unsigned)n_tiles), dim3(NT), 0, st, h->text.p, n_bytes, h->tile_lead.p, h->tile_trail.p);
-  hipLaunchKernelGGL(bpe_bounds_kernel<false>, dim3((unsigned)n_tiles), dim3(NT), 0, st, h->text.p, n_bytes, h->off.p, (int)n_docs, h->flags,
-                     h->greedy, h->tile_lead.p, h->tile_trail.p, n_tiles, h->tile_cnt.p, h->needs.p, (const unsigned*)nullptr,
-                     (unsigned*)nullptr, (unsigned*)nullptr, (unsigned char*)nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(scan_u32(h->tile_cnt.p, n_tiles, h->tile_off.p, st));
-  if (offsets) {
-    HIP_TRY(h->lane_lead.grow((size_t)n_tiles * NT));
-    HIP_TRY(h->tile_lead_cnt.grow((size_t)n_tiles));
-    HIP_TRY(h->tile_lead_off.grow((size_t)n_tiles + 1));
-    hipLaunchKernelGGL(offsets_lead_count_kernel, dim3((unsigned)n_tiles), dim3(NT), 0, st, h->text.p, n_bytes, h->lane_lead.p, h->tile_lead_cnt.p);
+static int bpe_encode(const char* fn, vrag_bpe* h, const EncodeArgs& a, int32_t* offsets) {
+  const int n_docs = a.n_docs;
+  auto count_pass = [&](hipStream_t st, long long n_bytes, long long n_tiles) -> int {
+    HIP_TRY(h->tile_lead.grow((size_t)n_tiles));
+    HIP_TRY(h->tile_trail.grow((size_t)n_tiles));
+    hipLaunchKernelGGL(bpe_tile_runs_kernel, dim3((unsigned)n_tiles), dim3(NT), 0, st, h->text.p, n_bytes, h->tile_lead.p, h->tile_trail.p);
+    hipLaunchKernelGGL(bpe_bounds_kernel<false>, dim3((unsigned)n_tiles), dim3(NT), 0, st, h->text.p, n_bytes, h->off.p, n_docs, h->flags,
+                       h->greedy, h->tile_lead.p, h->tile_trail.p, n_tiles, h->tile_cnt.p, h->needs.p, (const unsigned*)nullptr,
+                       (unsigned*)nullptr, (unsigned*)nullptr, (unsigned char*)nullptr);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(scan_u32(h->tile_lead_cnt.p, n_tiles, h->tile_lead_off.p, st));
-  }
-  unsigned n_words = 0;
-  HIP_TRY(read_u32(h->tile_off.p + n_tiles, &n_words, st));
-  if (n_words) {
-    HIP_TRY(h->wstart.grow(n_words));
-    HIP_TRY(h->wdoc.grow(n_words));
-    HIP_TRY(h->wspace.grow(n_words));
-    HIP_TRY(h->tok_cnt.grow(n_words));
-    HIP_TRY(h->tok_scan.grow((size_t)n_words + 1));
-    HIP_TRY(h->tok.grow((size_t)n_bytes));
-    hipLaunchKernelGGL(bpe_bounds_kernel<true>, dim3((unsigned)n_tiles), dim3(NT), 0, st, h->text.p, n_bytes, h->off.p, (int)n_docs, h->flags,
+    HIP_TRY(scan_u32(h->tile_cnt.p, n_tiles, h->tile_off.p, st));
+    if (offsets) {
+      HIP_TRY(h->lane_lead.grow((size_t)n_tiles * NT));
+      HIP_TRY(h->tile_lead_cnt.grow((size_t)n_tiles));
+      HIP_TRY(h->tile_lead_off.grow((size_t)n_tiles + 1));
+      hipLaunchKernelGGL(offsets_lead_count_kernel, dim3((unsigned)n_tiles), dim3(NT), 0, st, h->text.p, n_bytes, h->lane_lead.p, h->tile_lead_cnt.p);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(scan_u32(h->tile_lead_cnt.p, n_tiles, h->tile_lead_off.p, st));
+    }
+    return VRAG_OK;
+  };
+  auto word_pass = [&](hipStream_t st, long long n_bytes, long long n_tiles, long long n_words) -> int {
+    HIP_TRY(h->wspace.grow((size_t)n_words));
+    hipLaunchKernelGGL(bpe_bounds_kernel<true>, dim3((unsigned)n_tiles), dim3(NT), 0, st, h->text.p, n_bytes, h->off.p, n_docs, h->flags,
                        h->greedy, h->tile_lead.p, h->tile_trail.p, n_tiles, (unsigned*)nullptr, h->needs.p, h->tile_off.p, h->wstart.p,
                        h->wdoc.p, h->wspace.p);
     if (offsets) {
       HIP_TRY(h->span.grow((size_t)n_bytes));
       hipLaunchKernelGGL(offsets_merge_kernel, dim3(grid_of(n_words, 4)), dim3(256), 0, st, h->text.p, h->off.p, h->flags, h->tb, h->wstart.p,
-                         h->wdoc.p, h->wspace.p, (long long)n_words, h->tok.p, h->tok_cnt.p, h->body.p, h->needs.p,
+                         h->wdoc.p, h->wspace.p, n_words, h->tok.p, h->tok_cnt.p, h->body.p, h->needs.p,
                          LeadIndex{h->lane_lead.p, h->tile_lead_off.p}, h->span.p);
     } else {
       hipLaunchKernelGGL(bpe_merge_kernel, dim3(grid_of(n_words, 4)), dim3(256), 0, st, h->text.p, h->off.p, h->flags, h->tb, h->wstart.p,
-                         h->wdoc.p, h->wspace.p, (long long)n_words, h->tok.p, h->tok_cnt.p, h->body.p, h->needs.p);
+                         h->wdoc.p, h->wspace.p, n_words, h->tok.p, h->tok_cnt.p, h->body.p, h->needs.p);
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(scan_u32(h->tok_cnt.p, n_words, h->tok_scan.p, st));
-  }
-  hipLaunchKernelGGL(pack_seq_len_kernel, dim3(grid_of(n_docs, 256)), dim3(256), 0, st, h->body.p, (int)n_docs, special, (int)max_length,
-                     h->seq_len.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(scan_u32(h->seq_len.p, n_docs, h->out_off.p, st));
-  unsigned total = 0;
-  HIP_TRY(read_u32(h->out_off.p + n_docs, &total, st));
-  *n_ids = total;
-  HIP_TRY(hipMemcpyAsync(seq_lens, h->seq_len.p, (size_t)n_docs * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(needs_host, h->needs.p, (size_t)n_docs, hipMemcpyDeviceToHost, st));
-  if ((int64_t)total <= cap && total) {
-    HIP_TRY(h->ids.grow(total));
-    if (n_words)
-      hipLaunchKernelGGL(pack_gather_kernel<int>, dim3(grid_of(n_words, 256)), dim3(256), 0, st, h->wstart.p, h->wdoc.p, (long long)n_words,
-                         h->tok.p, h->tok_scan.p, h->out_off.p, special, (int)max_length, h->ids.p);
-    if (special)
-      hipLaunchKernelGGL(pack_special_kernel, dim3(grid_of(n_docs, 256)), dim3(256), 0, st, h->out_off.p, (int)n_docs, h->cls_id, h->sep_id,
-                         h->ids.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(ids, h->ids.p, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-    if (offsets) {   // [CLS] / [SEP] keep the (0, 0) of the memset
-      HIP_TRY(h->offs.grow(total));
-      HIP_TRY(hipMemsetAsync(h->offs.p, 0, (size_t)total * sizeof(int2), st));
-      if (n_words)
-        hipLaunchKernelGGL(pack_gather_kernel<int2>, dim3(grid_of(n_words, 256)), dim3(256), 0, st, h->wstart.p, h->wdoc.p, (long long)n_words,
-                           h->span.p, h->tok_scan.p, h->out_off.p, special, (int)max_length, h->offs.p);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(offsets, h->offs.p, (size_t)total * sizeof(int2), hipMemcpyDeviceToHost, st));
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  if ((int64_t)total > cap) {
-    set_error("%s: %u ids, cap %lld", fn, total, (long long)cap);
-    return VRAG_ERR_CAPACITY;
-  }
-  return VRAG_OK;
+    return VRAG_OK;
+  };
+  ARG_CHECK(h, "%s: bad arguments", fn);
+  const EncodeOffsets o{offsets, h->span, h->offs};
+  return tokenizer_encode(fn, VRAG_BPE_MAX_BATCH_BYTES, VRAG_BPE_TILE_BYTES, h, a, offsets ? &o : nullptr, count_pass, word_pass);
 }
 
 int vrag_bpe_encode(vrag_bpe* h, const uint8_t* text, const int64_t* doc_off, int32_t n_docs, int32_t add_special_tokens, int32_t max_length,
                     int64_t cap, int32_t* ids, int32_t* seq_lens, uint8_t* needs_host, int64_t* n_ids) {
-  return bpe_encode("vrag_bpe_encode", h, text, doc_off, n_docs, add_special_tokens, max_length, cap, ids, nullptr, seq_lens, needs_host, n_ids);
+  return bpe_encode("vrag_bpe_encode", h, {text, doc_off, n_docs, add_special_tokens, max_length, cap, ids, seq_lens, needs_host, n_ids}, nullptr);
 }
 
 int vrag_bpe_encode_offsets(vrag_bpe* h, const uint8_t* text, const int64_t* doc_off, int32_t n_docs, int32_t add_special_tokens,
                             int32_t max_length, int64_t cap, int32_t* ids, int32_t* offsets, int32_t* seq_lens, uint8_t* needs_host,
                             int64_t* n_ids) {
   ARG_CHECK(offsets, "vrag_bpe_encode_offsets: null offsets");
-  return bpe_encode("vrag_bpe_encode_offsets", h, text, doc_off, n_docs, add_special_tokens, max_length, cap, ids, offsets, seq_lens, needs_host,
-                    n_ids);
+  return bpe_encode("vrag_bpe_encode_offsets", h, {text, doc_off, n_docs, add_special_tokens, max_length, cap, ids, seq_lens, needs_host, n_ids},
+                    offsets);
 }
 
 }  // extern "C"

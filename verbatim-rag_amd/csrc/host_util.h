@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <vector>
 
 #include "../../include/vrag_amd.h"
 
@@ -66,6 +67,14 @@ struct DevArray {
     return e;
   }
 };
+
+// dst = src on stream st; an empty src still leaves a valid one-element allocation.
+template <typename T>
+hipError_t upload(DevArray<T>& dst, const std::vector<T>& src, hipStream_t st) {
+  hipError_t e = dst.grow(std::max<size_t>(src.size(), 1));
+  if (e == hipSuccess && !src.empty()) e = hipMemcpyAsync(dst.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, st);
+  return e;
+}
 
 // Pinned host array of T owned by its holder (staging buffers of a handle): DevArray's shape over hipHostMalloc / hipHostFree.
 template <typename T>

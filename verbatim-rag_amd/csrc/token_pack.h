@@ -1,6 +1,7 @@
 // The packing step shared by the device tokenizers (csrc/wordpiece.hip, csrc/bpe.hip): ids per text after truncation, the
 // surviving ids of every word at their place in the output, [CLS] / [SEP].  A word is (start byte, text); its ids lie in a
-// scratch array at its start byte, and tok_scan is the exclusive scan of the words' id counts.
+// scratch array at its start byte, and tok_scan is the exclusive scan of the words' id counts.  Launched by tokenizer_encode
+// (token_frame.h) only.
 #pragma once
 #include <hip/hip_runtime.h>
 

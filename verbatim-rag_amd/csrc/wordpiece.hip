@@ -10,8 +10,9 @@
 //             live in the lane's scratch, so the hash of any [s, e) is two multiply-adds; greedy longest match probes an
 //             open-addressing table {hash, id} in HBM and confirms every hit against the piece's stored bytes.  A word's
 //             ids go to a scratch array at its start byte (a word never has more ids than source bytes).
-//   pack      token_pack.h: pack_seq_len_kernel (ids per text after truncation), scans, pack_gather_kernel (one lane per word copies its
-//             ids that survive truncation), pack_special_kernel ([CLS] / [SEP]).
+//   pack      token_frame.h, shared with csrc/bpe.hip: tokenizer_encode checks and uploads the batch, calls the two passes above
+//             and launches token_pack.h -- pack_seq_len_kernel (ids per text after truncation), scans, pack_gather_kernel (one
+//             lane per word copies its ids that survive truncation), pack_special_kernel ([CLS] / [SEP]).
 // Integer work only; vector stores only.
 #include "../../include/vrag_amd.h"
 
@@ -24,7 +25,7 @@
 
 #include "common.h"
 #include "host_util.h"
-#include "token_pack.h"
+#include "token_frame.h"
 #include "utf8_text.h"
 
 namespace vrag {
@@ -290,19 +291,11 @@ __global__ __launch_bounds__(256) void wp_match_kernel(const unsigned char* __re
 using namespace vrag;
 using namespace vrag::wp;
 
-struct vrag_wordpiece {
-  int device = 0, flags = 0, cls_id = 0, sep_id = 0;
-  hipStream_t stream = nullptr;
-  std::mutex mu;
+struct vrag_wordpiece : TokenizerBase {
   Vocab vc{};
   DevArray<unsigned char> blob;
   DevArray<unsigned> piece_off, pw;
   DevArray<uint2> slots;
-  // workspace of one call, grown on demand
-  DevArray<unsigned char> text, needs;
-  DevArray<long long> off;
-  DevArray<unsigned> tile_cnt, tile_off, wstart, wdoc, tok_cnt, tok_scan, body, seq_len, out_off;
-  DevArray<int> tok, ids;
 };
 
 namespace {
@@ -399,16 +392,12 @@ int vrag_wordpiece_create(const uint8_t* vocab_blob, const int64_t* piece_off, i
   h->flags = flags;
   h->cls_id = cls_id;
   h->sep_id = sep_id;
-  const size_t blob_bytes = (size_t)piece_off[n_vocab];
+  const std::vector<unsigned char> blob(vocab_blob, vocab_blob + piece_off[n_vocab]);
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = h->blob.grow(blob_bytes);
-  if (e == hipSuccess) e = h->piece_off.grow(off32.size());
-  if (e == hipSuccess) e = h->pw.grow(pw.size());
-  if (e == hipSuccess) e = h->slots.grow(slots.size());
-  if (e == hipSuccess) e = hipMemcpyAsync(h->blob.p, vocab_blob, blob_bytes, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->piece_off.p, off32.data(), off32.size() * 4, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->pw.p, pw.data(), pw.size() * 4, hipMemcpyHostToDevice, h->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(h->slots.p, slots.data(), slots.size() * sizeof(uint2), hipMemcpyHostToDevice, h->stream);
+  if (e == hipSuccess) e = upload(h->blob, blob, h->stream);
+  if (e == hipSuccess) e = upload(h->piece_off, off32, h->stream);
+  if (e == hipSuccess) e = upload(h->pw, pw, h->stream);
+  if (e == hipSuccess) e = upload(h->slots, slots, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e != hipSuccess) {
     vrag_wordpiece_destroy(h);
@@ -431,93 +420,27 @@ int vrag_wordpiece_create(const uint8_t* vocab_blob, const int64_t* piece_off, i
   return VRAG_OK;
 }
 
-void vrag_wordpiece_destroy(vrag_wordpiece* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  hipStream_t st = h->stream;
-  if (st) (void)hipStreamSynchronize(st);
-  delete h;   // DevArrays free themselves
-  if (st) (void)hipStreamDestroy(st);
-}
+void vrag_wordpiece_destroy(vrag_wordpiece* h) { tokenizer_destroy(h); }
 
 int vrag_wordpiece_encode(vrag_wordpiece* h, const uint8_t* text, const int64_t* doc_off, int32_t n_docs, int32_t add_special_tokens,
                           int32_t max_length, int64_t cap, int32_t* ids, int32_t* seq_lens, uint8_t* needs_host, int64_t* n_ids) {
-  ARG_CHECK(h && doc_off && n_ids && n_docs >= 0 && cap >= 0 && (ids || cap == 0), "vrag_wordpiece_encode: bad arguments");
-  ARG_CHECK(n_docs == 0 || (seq_lens && needs_host), "vrag_wordpiece_encode: null seq_lens / needs_host");
-  ARG_CHECK(max_length >= (add_special_tokens ? 2 : 0), "vrag_wordpiece_encode: max_length %d leaves no room%s", max_length,
-            add_special_tokens ? " for [CLS] and [SEP]" : "");
-  ARG_CHECK(doc_off[0] == 0, "vrag_wordpiece_encode: doc_off[0] must be 0");
-  for (int32_t d = 0; d < n_docs; ++d)
-    ARG_CHECK(doc_off[d + 1] >= doc_off[d], "vrag_wordpiece_encode: doc_off must be non-decreasing (text %d)", d);
-  const long long n_bytes = doc_off[n_docs];
-  ARG_CHECK(n_bytes <= VRAG_WP_MAX_BATCH_BYTES, "vrag_wordpiece_encode: a batch holds at most %lld bytes of text, got %lld",
-            (long long)VRAG_WP_MAX_BATCH_BYTES, n_bytes);
-  ARG_CHECK(n_bytes + 2ll * n_docs < 0x7FFFFFF0ll, "vrag_wordpiece_encode: text bytes + 2 * n_docs must stay below 2^31");
-  ARG_CHECK(n_bytes == 0 || text, "vrag_wordpiece_encode: null text");
-  *n_ids = 0;
-  if (n_docs == 0) return VRAG_OK;
-  const int special = add_special_tokens ? 1 : 0;
-  std::lock_guard<std::mutex> lock(h->mu);
-  HIP_TRY(hipSetDevice(h->device));
-  hipStream_t st = h->stream;
-  const long long n_tiles = std::max<long long>(1, (n_bytes + VRAG_WORDPIECE_TILE_BYTES - 1) / VRAG_WORDPIECE_TILE_BYTES);
-  HIP_TRY(h->text.grow((size_t)n_bytes + 16));
-  HIP_TRY(h->off.grow((size_t)n_docs + 1));
-  HIP_TRY(h->needs.grow((size_t)n_docs));
-  HIP_TRY(h->body.grow((size_t)n_docs));
-  HIP_TRY(h->seq_len.grow((size_t)n_docs));
-  HIP_TRY(h->out_off.grow((size_t)n_docs + 1));
-  HIP_TRY(h->tile_cnt.grow((size_t)n_tiles));
-  HIP_TRY(h->tile_off.grow((size_t)n_tiles + 1));
-  if (n_bytes) HIP_TRY(hipMemcpyAsync(h->text.p, text, (size_t)n_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(h->off.p, doc_off, (size_t)(n_docs + 1) * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(h->needs.p, 0, (size_t)n_docs, st));
-  HIP_TRY(hipMemsetAsync(h->body.p, 0, (size_t)n_docs * 4, st));
-  hipLaunchKernelGGL(wp_words_kernel<false>, dim3((unsigned)n_tiles), dim3(WP_NT), 0, st, h->text.p, n_bytes, h->off.p, (int)n_docs, h->flags,
-                     h->tile_cnt.p, h->needs.p, (const unsigned*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(scan_u32(h->tile_cnt.p, n_tiles, h->tile_off.p, st));
-  unsigned n_words = 0;
-  HIP_TRY(read_u32(h->tile_off.p + n_tiles, &n_words, st));
-  if (n_words) {
-    HIP_TRY(h->wstart.grow(n_words));
-    HIP_TRY(h->wdoc.grow(n_words));
-    HIP_TRY(h->tok_cnt.grow(n_words));
-    HIP_TRY(h->tok_scan.grow((size_t)n_words + 1));
-    HIP_TRY(h->tok.grow((size_t)n_bytes));
+  auto count_pass = [&](hipStream_t st, long long n_bytes, long long n_tiles) -> int {
+    hipLaunchKernelGGL(wp_words_kernel<false>, dim3((unsigned)n_tiles), dim3(WP_NT), 0, st, h->text.p, n_bytes, h->off.p, (int)n_docs, h->flags,
+                       h->tile_cnt.p, h->needs.p, (const unsigned*)nullptr, (unsigned*)nullptr, (unsigned*)nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(scan_u32(h->tile_cnt.p, n_tiles, h->tile_off.p, st));
+    return VRAG_OK;
+  };
+  auto word_pass = [&](hipStream_t st, long long n_bytes, long long n_tiles, long long n_words) -> int {
     hipLaunchKernelGGL(wp_words_kernel<true>, dim3((unsigned)n_tiles), dim3(WP_NT), 0, st, h->text.p, n_bytes, h->off.p, (int)n_docs, h->flags,
                        (unsigned*)nullptr, h->needs.p, h->tile_off.p, h->wstart.p, h->wdoc.p);
     hipLaunchKernelGGL(wp_match_kernel, dim3(grid_of(n_words, 256)), dim3(256), 0, st, h->text.p, n_bytes, h->off.p, h->flags, h->vc,
-                       h->wstart.p, h->wdoc.p, (long long)n_words, h->tok.p, h->tok_cnt.p, h->body.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(scan_u32(h->tok_cnt.p, n_words, h->tok_scan.p, st));
-  }
-  hipLaunchKernelGGL(pack_seq_len_kernel, dim3(grid_of(n_docs, 256)), dim3(256), 0, st, h->body.p, (int)n_docs, special, (int)max_length,
-                     h->seq_len.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(scan_u32(h->seq_len.p, n_docs, h->out_off.p, st));
-  unsigned total = 0;
-  HIP_TRY(read_u32(h->out_off.p + n_docs, &total, st));
-  *n_ids = total;
-  HIP_TRY(hipMemcpyAsync(seq_lens, h->seq_len.p, (size_t)n_docs * 4, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(needs_host, h->needs.p, (size_t)n_docs, hipMemcpyDeviceToHost, st));
-  if ((int64_t)total <= cap && total) {
-    HIP_TRY(h->ids.grow(total));
-    if (n_words)
-      hipLaunchKernelGGL(pack_gather_kernel<int>, dim3(grid_of(n_words, 256)), dim3(256), 0, st, h->wstart.p, h->wdoc.p, (long long)n_words, h->tok.p,
-                         h->tok_scan.p, h->out_off.p, special, (int)max_length, h->ids.p);
-    if (special)
-      hipLaunchKernelGGL(pack_special_kernel, dim3(grid_of(n_docs, 256)), dim3(256), 0, st, h->out_off.p, (int)n_docs, h->cls_id, h->sep_id,
-                         h->ids.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(ids, h->ids.p, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  if ((int64_t)total > cap) {
-    set_error("vrag_wordpiece_encode: %u ids, cap %lld", total, (long long)cap);
-    return VRAG_ERR_CAPACITY;
-  }
-  return VRAG_OK;
+                       h->wstart.p, h->wdoc.p, n_words, h->tok.p, h->tok_cnt.p, h->body.p);
+    return VRAG_OK;
+  };
+  return tokenizer_encode("vrag_wordpiece_encode", VRAG_WP_MAX_BATCH_BYTES, VRAG_WORDPIECE_TILE_BYTES, h,
+                          {text, doc_off, n_docs, add_special_tokens, max_length, cap, ids, seq_lens, needs_host, n_ids}, nullptr,
+                          count_pass, word_pass);
 }
 
 }  // extern "C"

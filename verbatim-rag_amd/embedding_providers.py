@@ -92,19 +92,14 @@ def load_model_tokenizer(model_path: str, tokenizer: str = "host", device: int =
         return load_tokenizer(model_path)
     if tokenizer != "gpu":
         raise ValueError(f"tokenizer must be 'host' or 'gpu', got {tokenizer!r}")
-    import json
-    import os
+    from .device_tokenizer import read_spec
 
-    from .wordpiece import GpuWordPieceTokenizer
-
-    path = os.path.join(model_path, "tokenizer.json") if os.path.isdir(model_path) else model_path
-    with open(path, encoding="utf-8") as f:
-        spec = json.load(f)
+    path, spec = read_spec(model_path)
     if (spec.get("model") or {}).get("type") == "BPE" and (spec.get("pre_tokenizer") or {}).get("type") == "ByteLevel":
-        from .bpe import GpuByteBpeTokenizer
-
-        return GpuByteBpeTokenizer.from_file(path, device=device)
-    return GpuWordPieceTokenizer.from_file(model_path, device=device)
+        from .bpe import GpuByteBpeTokenizer as cls
+    else:
+        from .wordpiece import GpuWordPieceTokenizer as cls
+    return cls.from_file(path, device=device)
 
 
 def load_encoder_directory(model_path: str, device: int = 0, max_tokens: int = 65536, max_seqs: int = 512,

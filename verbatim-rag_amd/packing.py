@@ -114,10 +114,9 @@ class TokenizerAdapter:
         """Special-token ids from the tokenizer when it defines them, otherwise from the model's config.json (`shape`): a
         raw `tokenizers.Tokenizer`, or an HF fast tokenizer loaded from a directory that holds only tokenizer.json,
         knows the template but not which ids are [CLS] / [SEP]."""
-        from .bpe import GpuByteBpeTokenizer
-        from .wordpiece import GpuWordPieceTokenizer
+        from .device_tokenizer import DeviceTokenizer
 
-        if isinstance(tokenizer, (GpuWordPieceTokenizer, GpuByteBpeTokenizer)):    # offers ids / ids_batch itself, with the ids of its own vocabulary
+        if isinstance(tokenizer, DeviceTokenizer):    # offers ids / ids_batch itself, with the ids of its own vocabulary
             return tokenizer
 
         def override(name):

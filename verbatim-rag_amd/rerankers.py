@@ -127,10 +127,9 @@ class GpuCrossEncoderReranker(BaseReranker):
 
     def _ids_batch(self, texts: Sequence[str]) -> List[List[int]]:
         """`[_ids(t) for t in texts]`; one device batch when the tokenizer is a device tokenizer."""
-        from .bpe import GpuByteBpeTokenizer
-        from .wordpiece import GpuWordPieceTokenizer
+        from .device_tokenizer import DeviceTokenizer
 
-        if isinstance(self.tokenizer, (GpuWordPieceTokenizer, GpuByteBpeTokenizer)):
+        if isinstance(self.tokenizer, DeviceTokenizer):
             return self.tokenizer.ids_batch(list(texts), max_length=2 ** 31 - 1, add_special_tokens=False)
         return [self._ids(t) for t in texts]
 
