@@ -763,7 +763,32 @@ int vrag_rrf_fuse(const int64_t* rows /*[nq, l_total]*/, const double* gains /*[
  * VRAG_ERR_INVALID with a message, before anything is allocated or launched and with the outputs untouched, for: a column with
  * fewer dictionary codes than asked for, a text over a limit, a pattern ending in a lone backslash, invalid UTF-8 in a pattern or
  * in appended strings, offsets not ascending from 0, an unknown operator, a match whose leaf is no _TABLE leaf or whose text
- * lies outside `texts` (a leaf's table range is checked against n_table_words as in eval). */
+ * lies outside `texts` (a leaf's table range is checked against n_table_words as in eval).
+ *
+ * Membership in list-valued metadata (csrc/listfilter.hip; `json_contains` in store_filter.py).  A column may also hold a LIST
+ * PART: for every row the elements of its list as CSR -- row r's elements are [elem_off[r], elem_off[r + 1]) of elem_kinds /
+ * elem_payload, one (kind, payload) each in exactly the encoding of kinds / payload, strings through the column's one dictionary
+ * (so a _TABLE leaf and the match kernel serve elements unchanged).  A row whose value is no list has an empty range.  8 bytes
+ * per row + 9 bytes per element of device memory, geometric growth.  The list part is independent of the column's rows: either
+ * may be absent or shorter.
+ *   append_lists  host arrays, n rows: elem_off[0] = 0, non-decreasing, elem_off[n] elements; the rows go behind the list rows
+ *                 held and their offsets continue from the elements held.  n == 0: VRAG_OK, nothing read.
+ *   list_rows     rows and elements the column's list part holds.
+ *   eval_lists    eval_matched (same arguments, same checks, same output), and ops may also hold
+ *                 VRAG_FILTER_OP_LIST_ANY | (leaf index << 8): pushes, for row r, the OR over the elements of r's list in the
+ *                 leaf's column of what the leaf answers for the element's (kind, payload) -- other_bit, bool_bits, num_op / bound
+ *                 and str_mode / table apply per element as they do per row; a row without elements pushes 0.  A leaf that only
+ *                 LIST_ANY ops push needs its column's list part to cover n_rows, not the column's rows; a leaf that a LEAF op
+ *                 pushes (or no op) needs the rows as in eval.  A program without a LIST_ANY op runs exactly as eval_matched
+ *                 runs it, on the same kernel; one with a LIST_ANY op runs on a kernel of its own, one lane per row, each lane
+ *                 walking its row's elements up to the first match: a row with a very long list makes one lane walk alone, as
+ *                 a very long string does in the match kernel.  eval and eval_matched refuse LIST_ANY like any unknown op.
+ *   compact       a vrag_row_filter_compact that drops at least one row DROPS the list part of every column (list_rows then
+ *                 reports 0 rows, 0 elements; the memory is kept for reuse): the caller appends the compacted lists again before
+ *                 its next list filter.  One that drops nothing leaves them.  A list part of more rows than the bitmap covers is
+ *                 VRAG_ERR_INVALID like such a column.
+ * VRAG_ERR_INVALID with a message, before anything is allocated or launched and with the outputs untouched, also for: offsets
+ * not starting at 0 or decreasing, an element kind above 3, a LIST_ANY leaf whose column holds the lists of fewer than n_rows rows. */
 #define VRAG_FILTER_MAX_COLUMNS 16
 #define VRAG_FILTER_MAX_LEAVES 64
 #define VRAG_FILTER_MAX_OPS 256
@@ -787,6 +812,7 @@ int vrag_rrf_fuse(const int64_t* rows /*[nq, l_total]*/, const double* gains /*[
 #define VRAG_FILTER_OP_AND 1
 #define VRAG_FILTER_OP_OR 2
 #define VRAG_FILTER_OP_NOT 3
+#define VRAG_FILTER_OP_LIST_ANY 4 /* vrag_row_filter_eval_lists only */
 typedef struct vrag_filter_leaf {
   double bound;
   int64_t table_off;
@@ -837,6 +863,15 @@ int vrag_row_filter_eval_matched(vrag_row_filter* f, const vrag_filter_leaf* lea
                                  const vrag_filter_match* matches /*[n_matches]*/, int32_t n_matches,
                                  const uint8_t* texts /*[n_text_bytes] host*/, int64_t n_text_bytes, int64_t n_rows,
                                  uint32_t* out_words /*host*/, void* stream);
+int vrag_row_filter_append_lists(vrag_row_filter* f, int32_t col, const int64_t* elem_off /*[n + 1] host, from 0, non-decreasing*/,
+                                 const uint8_t* elem_kinds /*[elem_off[n]] host*/, const uint64_t* elem_payload /*[elem_off[n]] host*/,
+                                 int64_t n);
+int vrag_row_filter_list_rows(vrag_row_filter* f, int32_t col, int64_t* n_rows, int64_t* n_elems);
+int vrag_row_filter_eval_lists(vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops,
+                               int32_t n_ops, const uint32_t* tables /*[n_table_words] host, NULL when 0*/, int64_t n_table_words,
+                               const vrag_filter_match* matches /*[n_matches]*/, int32_t n_matches,
+                               const uint8_t* texts /*[n_text_bytes] host*/, int64_t n_text_bytes, int64_t n_rows,
+                               uint32_t* out_words /*host*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The exchange step of sharded retrieval: one process per GPU, the corpus row-sharded, every rank answers the

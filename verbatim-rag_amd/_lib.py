@@ -80,7 +80,7 @@ FILTER_MAX_COLUMNS, FILTER_MAX_LEAVES, FILTER_MAX_OPS, FILTER_MAX_DEPTH = 16, 64
 FILTER_KINDS = {"other": 0, "number": 1, "string": 2, "bool": 3}                                # VRAG_FILTER_KIND_*
 FILTER_NUM_OPS = {"never": 0, "always": 1, "==": 2, "!=": 3, "<": 4, "<=": 5, ">": 6, ">=": 7}  # VRAG_FILTER_NUM_*
 FILTER_STR_MODES = {"never": 0, "always": 1, "table": 2}                                        # VRAG_FILTER_STR_*
-FILTER_OPS = {"leaf": 0, "and": 1, "or": 2, "not": 3}                                           # VRAG_FILTER_OP_* (leaf index << 8)
+FILTER_OPS = {"leaf": 0, "and": 1, "or": 2, "not": 3, "list_any": 4}                            # VRAG_FILTER_OP_* (leaf index << 8)
 FILTER_MATCH_OPS = {"==": 0, "!=": 1, "<": 2, "<=": 3, ">": 4, ">=": 5, "like": 6}                  # VRAG_FILTER_MATCH_*
 FILTER_MATCH_MAX_PATTERN, FILTER_MATCH_MAX_SEGMENTS = 256, 16                                   # VRAG_FILTER_MATCH_MAX_*
 
@@ -181,6 +181,11 @@ SIGNATURES = {
     "vrag_row_filter_eval_matched": (C.c_int, [_H, C.POINTER(FilterLeaf), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
                                                C.POINTER(FilterMatch), C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                                C.c_void_p]),
+    "vrag_row_filter_append_lists": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "vrag_row_filter_list_rows": (C.c_int, [_H, C.c_int32, _LP, _LP]),
+    "vrag_row_filter_eval_lists": (C.c_int, [_H, C.POINTER(FilterLeaf), C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
+                                             C.POINTER(FilterMatch), C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                             C.c_void_p]),
     "vrag_sparse_index_search_device": (C.c_int, [_H, _LP, _IP, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "vrag_pack_qa_pairs": (C.c_int, [_IP, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, _IP, C.c_int32, C.c_int32, _IP, C.c_int64,

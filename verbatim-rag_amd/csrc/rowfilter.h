@@ -19,7 +19,63 @@ struct FilterColumn {
   DevArray<unsigned char> str_bytes;
   DevArray<long long> str_off;
   long long n_codes = 0, n_bytes = 0;
+  // The LIST part (csrc/listfilter.hip): rows whose value is a list, as CSR.  Row r's elements are [list_off[r], list_off[r + 1])
+  // of elem_kinds / elem_payload, encoded exactly like kinds / payload (strings through the same dictionary); a row that holds no
+  // list has an empty range.  list_off holds n_list_rows + 1 offsets once a row has arrived.  Geometric growth like the rows.
+  DevArray<long long> list_off;
+  DevArray<unsigned char> elem_kinds;
+  DevArray<u64> elem_payload;
+  long long n_list_rows = 0, n_elems = 0;
 };
+
+// The program as the eval kernels take it: a by-value kernel argument (csrc/rowfilter.hip explains the layout).
+constexpr int RF_WAVES = 4;            // waves of a workgroup
+constexpr int RF_MAX_BLOCKS = 4096;
+constexpr unsigned char RF_AND = 64, RF_OR = 65, RF_NOT = 66;   // op bytes; 0 .. 63 = push leaf
+constexpr unsigned char RF_LIST_ANY = 128;                      // 128 .. 191 = push the OR of leaf (op - 128) over the row's list elements
+
+struct LeafDev {
+  double bound;
+  unsigned table_off, table_codes;
+  unsigned char slot, num_op, str_mode, bits;   // slot: index into EvalArgs' columns; bits: bit 0 other, bit 1 bool false, bit 2 bool true
+  unsigned pad;
+};
+
+struct EvalArgs {
+  const unsigned char* kinds[VRAG_FILTER_MAX_COLUMNS];
+  const u64* payload[VRAG_FILTER_MAX_COLUMNS];
+  LeafDev leaves[VRAG_FILTER_MAX_LEAVES];
+  unsigned ops[VRAG_FILTER_MAX_OPS / 4];   // four op bytes per word, op i in byte i % 4 of word i / 4
+  int n_ops;
+};
+static_assert(sizeof(EvalArgs) <= 3072, "the program travels as a kernel argument");
+
+// One number comparison of a leaf (IEEE f64: -0.0 == 0.0, infinities ordered, NaN unordered); shared by the two eval kernels.
+__device__ __forceinline__ bool num_answer(int op, double x, double bound) {
+  switch (op) {   // wave-uniform
+    case VRAG_FILTER_NUM_ALWAYS: return true;
+    case VRAG_FILTER_NUM_EQ: return x == bound;
+    case VRAG_FILTER_NUM_NE: return x != bound;
+    case VRAG_FILTER_NUM_LT: return x < bound;
+    case VRAG_FILTER_NUM_LE: return x <= bound;
+    case VRAG_FILTER_NUM_GT: return x > bound;
+    case VRAG_FILTER_NUM_GE: return x >= bound;
+    default: return false;
+  }
+}
+
+// The list parts of the same column slots, for a program with a list op (csrc/listfilter.hip); null for a slot no list op names.
+struct ListArgs {
+  const long long* list_off[VRAG_FILTER_MAX_COLUMNS];
+  const unsigned char* elem_kinds[VRAG_FILTER_MAX_COLUMNS];
+  const u64* elem_payload[VRAG_FILTER_MAX_COLUMNS];
+};
+static_assert(sizeof(EvalArgs) + sizeof(ListArgs) <= 3584, "both travel as kernel arguments (4 KB per launch)");
+
+// csrc/listfilter.hip: the eval kernel for a program with RF_LIST_ANY ops, enqueued on `st`; same grid, same output as
+// row_filter_eval_kernel (two words per group of 64 rows at d_out).
+hipError_t list_eval_launch(const EvalArgs& a, const ListArgs& l, const unsigned* d_tables, long long n_rows, unsigned* d_out,
+                            hipStream_t st);
 
 // One string leaf compiled for the match kernel (a by-value kernel argument, copied to LDS once per workgroup).
 //   comparisons  elem[0 .. text_len) is the operand

@@ -32,39 +32,7 @@
 namespace vrag {
 namespace {
 
-constexpr int RF_WAVES = 4;            // waves of a workgroup
-constexpr int RF_MAX_BLOCKS = 4096;
-constexpr int RF_MAX_HANDLE_COLUMNS = 4096;
-constexpr unsigned char RF_AND = 64, RF_OR = 65, RF_NOT = 66;   // op bytes; 0 .. 63 = push leaf
-
-struct LeafDev {
-  double bound;
-  unsigned table_off, table_codes;
-  unsigned char slot, num_op, str_mode, bits;   // slot: index into EvalArgs' columns; bits: bit 0 other, bit 1 bool false, bit 2 bool true
-  unsigned pad;
-};
-
-struct EvalArgs {
-  const unsigned char* kinds[VRAG_FILTER_MAX_COLUMNS];
-  const u64* payload[VRAG_FILTER_MAX_COLUMNS];
-  LeafDev leaves[VRAG_FILTER_MAX_LEAVES];
-  unsigned ops[VRAG_FILTER_MAX_OPS / 4];   // four op bytes per word, op i in byte i % 4 of word i / 4
-  int n_ops;
-};
-static_assert(sizeof(EvalArgs) <= 3072, "the program travels as a kernel argument");
-
-__device__ __forceinline__ bool num_answer(int op, double x, double bound) {
-  switch (op) {   // wave-uniform
-    case VRAG_FILTER_NUM_ALWAYS: return true;
-    case VRAG_FILTER_NUM_EQ: return x == bound;
-    case VRAG_FILTER_NUM_NE: return x != bound;
-    case VRAG_FILTER_NUM_LT: return x < bound;
-    case VRAG_FILTER_NUM_LE: return x <= bound;
-    case VRAG_FILTER_NUM_GT: return x > bound;
-    case VRAG_FILTER_NUM_GE: return x >= bound;
-    default: return false;
-  }
-}
+constexpr int RF_MAX_HANDLE_COLUMNS = 4096;   // RF_WAVES, the op bytes, LeafDev, EvalArgs, num_answer: rowfilter.h (csrc/listfilter.hip shares them)
 
 __global__ __launch_bounds__(64 * RF_WAVES) void row_filter_eval_kernel(const EvalArgs a, const unsigned* __restrict__ tables,
                                                                          long long n_rows, long long n_groups,
@@ -199,17 +167,22 @@ int vrag_row_filter_rows(vrag_row_filter* f, int32_t col, int64_t* n) {
 
 // Drops the rows whose bit is cleared from every column, in place (csrc/compact.h).  Columns are extended lazily, so a column may
 // hold fewer rows than the bitmap covers: its rows are compacted under the bitmap's prefix.  The dictionaries hold strings, not rows.
+// A call that drops a row DROPS every column's list part (n_list_rows = 0; the allocation stays for the re-append): the store
+// re-appends it from its host column before the next list filter.  A CSR compaction on the device would be two more kernels for
+// arrays the host holds compacted anyway.
 int vrag_row_filter_compact(vrag_row_filter* f, const uint32_t* keep_words, int64_t n_keep) {
   ARG_CHECK(f, "null argument");
   ARG_CHECK(n_keep >= 0 && (keep_words || n_keep == 0), "bad row bitmap (null words or a negative length)");
   std::lock_guard<std::mutex> lk(f->mu);
   for (const FilterColumn& c : f->cols)
-    ARG_CHECK(c.n <= n_keep, "the bitmap covers %lld rows, a column holds %lld", (long long)n_keep, (long long)c.n);
+    ARG_CHECK(c.n <= n_keep && c.n_list_rows <= n_keep, "the bitmap covers %lld rows, a column holds %lld",
+              (long long)n_keep, (long long)std::max(c.n, c.n_list_rows));
   if (n_keep == 0 || f->cols.empty()) return VRAG_OK;
   HIP_TRY(hipSetDevice(f->device));
   int rc;
   if ((rc = compact_plan(f->compact, keep_words, n_keep, f->stream))) return rc;
   if (f->compact.n_keep == n_keep) return VRAG_OK;   // nothing to drop: no launch
+  for (FilterColumn& c : f->cols) c.n_list_rows = c.n_elems = 0;
   for (FilterColumn& c : f->cols) {
     if (c.n == 0) continue;
     if ((rc = compact_rows(f->compact, c.kinds.p, 1, c.n, f->stream))) return rc;
@@ -222,9 +195,11 @@ int vrag_row_filter_compact(vrag_row_filter* f, const uint32_t* keep_words, int6
 
 }  // extern "C"
 
-// vrag_row_filter_eval and _eval_matched (`who` names the one called): the latter's matches fill their leaves' tables in device
-// memory between the upload of `tables` and the eval kernel.
-static int eval_program(const char* who, vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops,
+// vrag_row_filter_eval, _eval_matched and _eval_lists (`who` names the one called): the matches of the latter two fill their
+// leaves' tables in device memory between the upload of `tables` and the eval kernel.  Only _eval_lists (`lists`) takes
+// VRAG_FILTER_OP_LIST_ANY; a program that holds one runs on the kernel of csrc/listfilter.hip, every other program on
+// row_filter_eval_kernel with the arguments it always had.
+static int eval_program(const char* who, bool lists, vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops,
                         int32_t n_ops, const uint32_t* tables, int64_t n_table_words, const vrag_filter_match* matches, int32_t n_matches,
                         const uint8_t* texts, int64_t n_text_bytes, int64_t n_rows, uint32_t* out_words, void* stream) {
   ARG_CHECK(f && leaves && ops, "null argument");
@@ -236,17 +211,25 @@ static int eval_program(const char* who, vrag_row_filter* f, const vrag_filter_l
   ARG_CHECK(n_rows >= 0, "%s: negative n_rows", who);
   ARG_CHECK(n_rows == 0 || out_words, "%s: null out_words", who);
   EvalArgs args;
+  ListArgs largs;
   std::memset(&args, 0, sizeof(args));
+  std::memset(&largs, 0, sizeof(largs));
   // the op list: no underflow, depth <= 32, one value left
   int depth = 0;
+  bool as_row[VRAG_FILTER_MAX_LEAVES] = {}, as_list[VRAG_FILTER_MAX_LEAVES] = {};   // how the ops push each leaf
+  bool any_list = false;
   for (int i = 0; i < n_ops; ++i) {
     const uint32_t code = ops[i] & 0xffu, leaf = ops[i] >> 8;
     unsigned char byte = 0;
-    if (code == VRAG_FILTER_OP_LEAF) {
+    if (code == VRAG_FILTER_OP_LEAF || (lists && code == VRAG_FILTER_OP_LIST_ANY)) {
       ARG_CHECK(leaf < (uint32_t)n_leaves, "%s: ops[%d] pushes leaf %u of %d", who, i, leaf, n_leaves);
       ARG_CHECK(depth < VRAG_FILTER_MAX_DEPTH, "%s: stack deeper than %d at ops[%d]", who, VRAG_FILTER_MAX_DEPTH, i);
       ++depth;
-      byte = (unsigned char)leaf;
+      if (code == VRAG_FILTER_OP_LEAF) {
+        byte = (unsigned char)leaf, as_row[leaf] = true;
+      } else {
+        byte = (unsigned char)(RF_LIST_ANY + leaf), as_list[leaf] = any_list = true;
+      }
     } else if (code == VRAG_FILTER_OP_AND || code == VRAG_FILTER_OP_OR) {
       ARG_CHECK(leaf == 0 && depth >= 2, "%s: stack underflow at ops[%d]", who, i);
       --depth;
@@ -263,6 +246,7 @@ static int eval_program(const char* who, vrag_row_filter* f, const vrag_filter_l
 
   std::lock_guard<std::mutex> lk(f->mu);
   int slot_col[VRAG_FILTER_MAX_COLUMNS];
+  bool slot_rows[VRAG_FILTER_MAX_COLUMNS] = {}, slot_lists[VRAG_FILTER_MAX_COLUMNS] = {};   // which part of the column is checked and bound
   int n_slots = 0;
   for (int l = 0; l < n_leaves; ++l) {
     const vrag_filter_leaf& in = leaves[l];
@@ -282,10 +266,20 @@ static int eval_program(const char* who, vrag_row_filter* f, const vrag_filter_l
     while (slot < n_slots && slot_col[slot] != in.column) ++slot;
     if (slot == n_slots) {
       ARG_CHECK(n_slots < VRAG_FILTER_MAX_COLUMNS, "%s: the leaves name more than %d columns", who, VRAG_FILTER_MAX_COLUMNS);
-      const FilterColumn& c = f->cols[in.column];
-      ARG_CHECK(n_rows <= c.n, "%s: n_rows = %lld but column %d holds %lld rows", who, (long long)n_rows, in.column, c.n);
       slot_col[n_slots++] = in.column;
+    }
+    const FilterColumn& c = f->cols[in.column];
+    // a leaf reads the rows of its column, unless list ops alone push it: then it reads the column's list part
+    if ((as_row[l] || !as_list[l]) && !slot_rows[slot]) {
+      ARG_CHECK(n_rows <= c.n, "%s: n_rows = %lld but column %d holds %lld rows", who, (long long)n_rows, in.column, c.n);
+      slot_rows[slot] = true;
       args.kinds[slot] = c.kinds.p, args.payload[slot] = c.payload.p;
+    }
+    if (as_list[l] && !slot_lists[slot]) {
+      ARG_CHECK(n_rows <= c.n_list_rows, "%s: n_rows = %lld but column %d holds the lists of %lld rows", who, (long long)n_rows,
+                in.column, c.n_list_rows);
+      slot_lists[slot] = true;
+      largs.list_off[slot] = c.list_off.p, largs.elem_kinds[slot] = c.elem_kinds.p, largs.elem_payload[slot] = c.elem_payload.p;
     }
     lf.bound = in.bound;
     lf.slot = (unsigned char)slot, lf.num_op = in.num_op, lf.str_mode = in.str_mode;
@@ -321,10 +315,14 @@ static int eval_program(const char* who, vrag_row_filter* f, const vrag_filter_l
     const vrag_filter_leaf& in = leaves[matches[m].leaf];
     HIP_TRY(match_launch(f->cols[in.column], progs[(size_t)m], in.table_codes, f->d_tables.p + in.table_off, st));
   }
-  const unsigned blocks = (unsigned)std::min<long long>((n_groups + RF_WAVES - 1) / RF_WAVES, RF_MAX_BLOCKS);
-  hipLaunchKernelGGL(row_filter_eval_kernel, dim3(blocks), dim3(64 * RF_WAVES), 0, st, args, f->d_tables.p, (long long)n_rows, n_groups,
-                     f->d_out.p);
-  HIP_TRY(hipGetLastError());
+  if (any_list) {
+    HIP_TRY(list_eval_launch(args, largs, f->d_tables.p, (long long)n_rows, f->d_out.p, st));
+  } else {
+    const unsigned blocks = (unsigned)std::min<long long>((n_groups + RF_WAVES - 1) / RF_WAVES, RF_MAX_BLOCKS);
+    hipLaunchKernelGGL(row_filter_eval_kernel, dim3(blocks), dim3(64 * RF_WAVES), 0, st, args, f->d_tables.p, (long long)n_rows, n_groups,
+                       f->d_out.p);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipMemcpyAsync(out_words, f->d_out.p, n_words * sizeof(unsigned), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return VRAG_OK;
@@ -334,15 +332,22 @@ extern "C" {
 
 int vrag_row_filter_eval(vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops, int32_t n_ops,
                          const uint32_t* tables, int64_t n_table_words, int64_t n_rows, uint32_t* out_words, void* stream) {
-  return eval_program("vrag_row_filter_eval", f, leaves, n_leaves, ops, n_ops, tables, n_table_words, nullptr, 0, nullptr, 0, n_rows,
+  return eval_program("vrag_row_filter_eval", false, f, leaves, n_leaves, ops, n_ops, tables, n_table_words, nullptr, 0, nullptr, 0, n_rows,
                       out_words, stream);
 }
 
 int vrag_row_filter_eval_matched(vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops, int32_t n_ops,
                                  const uint32_t* tables, int64_t n_table_words, const vrag_filter_match* matches, int32_t n_matches,
                                  const uint8_t* texts, int64_t n_text_bytes, int64_t n_rows, uint32_t* out_words, void* stream) {
-  return eval_program("vrag_row_filter_eval_matched", f, leaves, n_leaves, ops, n_ops, tables, n_table_words, matches, n_matches, texts,
-                      n_text_bytes, n_rows, out_words, stream);
+  return eval_program("vrag_row_filter_eval_matched", false, f, leaves, n_leaves, ops, n_ops, tables, n_table_words, matches, n_matches,
+                      texts, n_text_bytes, n_rows, out_words, stream);
+}
+
+int vrag_row_filter_eval_lists(vrag_row_filter* f, const vrag_filter_leaf* leaves, int32_t n_leaves, const uint32_t* ops, int32_t n_ops,
+                               const uint32_t* tables, int64_t n_table_words, const vrag_filter_match* matches, int32_t n_matches,
+                               const uint8_t* texts, int64_t n_text_bytes, int64_t n_rows, uint32_t* out_words, void* stream) {
+  return eval_program("vrag_row_filter_eval_lists", true, f, leaves, n_leaves, ops, n_ops, tables, n_table_words, matches, n_matches,
+                      texts, n_text_bytes, n_rows, out_words, stream);
 }
 
 }  // extern "C"

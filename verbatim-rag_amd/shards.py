@@ -285,7 +285,9 @@ class RowFilter(_Handle):
     """Typed metadata columns in HBM and the kernel that evaluates a filter program over them (`vrag_row_filter_*`,
     csrc/rowfilter.hip): 9 bytes per row and column.  Columns are numbered in creation order and only ever appended to.
     A column may also hold the dictionary of its strings (`append_strings`); the match kernel (csrc/strmatch.hip) then makes
-    the answer table of a string comparison or a `LIKE` from it (`match`, `eval_program(strings="device")`)."""
+    the answer table of a string comparison or a `LIKE` from it (`match`, `eval_program(strings="device")`).  And the list part
+    of its rows (`append_lists`: 8 bytes per row + 9 per element), which the "list_any" op of a program reads (`json_contains`,
+    csrc/listfilter.hip); `compact` drops the list parts, the caller appends them again."""
 
     _destroy = "vrag_row_filter_destroy"
 
@@ -310,9 +312,31 @@ class RowFilter(_Handle):
         _lib.check("vrag_row_filter_rows", self._lib.vrag_row_filter_rows(self._h, int(col), C.byref(n)))
         return n.value
 
+    def append_lists(self, col: int, elem_off: np.ndarray, elem_kinds: np.ndarray, elem_payload: np.ndarray) -> None:
+        """Appends `len(elem_off) - 1` rows to the column's list part: row i holds elements elem_off[i]:elem_off[i + 1] of
+        `elem_kinds` / `elem_payload`, elem_off[0] = 0; the device continues its offsets from the elements it holds
+        (`store_columns.MetaColumn.elem_off` of the new rows, less its first entry)."""
+        elem_off = np.ascontiguousarray(elem_off, dtype=np.int64)
+        elem_kinds = np.ascontiguousarray(elem_kinds, dtype=np.uint8)
+        elem_payload = np.ascontiguousarray(elem_payload, dtype=np.uint64)
+        if elem_off.ndim != 1 or len(elem_off) < 1 or elem_kinds.ndim != 1 or elem_kinds.shape != elem_payload.shape or \
+                int(elem_off[-1]) > len(elem_kinds):
+            raise ValueError(f"elem_off {elem_off.shape} must hold one offset more than rows and end inside the equally long "
+                             f"elem_kinds {elem_kinds.shape} and elem_payload {elem_payload.shape}")
+        _lib.check("vrag_row_filter_append_lists", self._lib.vrag_row_filter_append_lists(
+            self._h, int(col), _vp(elem_off), _vp(elem_kinds) if len(elem_kinds) else None,
+            _vp(elem_payload) if len(elem_payload) else None, len(elem_off) - 1))
+
+    def list_rows(self, col: int) -> Tuple[int, int]:
+        """(rows, elements) of the column's list part on the device."""
+        n, e = C.c_int64(), C.c_int64()
+        _lib.check("vrag_row_filter_list_rows", self._lib.vrag_row_filter_list_rows(self._h, int(col), C.byref(n), C.byref(e)))
+        return n.value, e.value
+
     def compact(self, keep: np.ndarray) -> None:
         """Drops the rows whose `keep` is False from every column, in place, order kept (`vrag_row_filter_compact`); a column
-        that holds fewer rows than `keep` covers is compacted under its prefix.  The dictionaries stay."""
+        that holds fewer rows than `keep` covers is compacted under its prefix.  The dictionaries stay.  When a row is dropped
+        the list parts are dropped whole (`list_rows` = (0, 0)): append them again from the compacted host columns."""
         keep = np.asarray(keep, dtype=bool).reshape(-1)
         words = _bitmap(keep)
         _lib.check("vrag_row_filter_compact", self._lib.vrag_row_filter_compact(self._h, _vp(words) if len(words) else None, len(keep)))
@@ -361,7 +385,8 @@ class RowFilter(_Handle):
         """The program's answer for rows [0, n_rows) as uint32 words (bit r % 32 of word r // 32, tail bits zero).  `out`: a
         uint32 array of at least ceil(n_rows / 32) words to write into (words behind those are left alone).  `matches`: table
         leaves whose tables the match kernel writes on the device before the program runs, their operand texts in `texts`
-        (vrag_row_filter_eval_matched)."""
+        (vrag_row_filter_eval_matched).  A program with a "list_any" op goes to vrag_row_filter_eval_lists, every other one to
+        the entry point it always went to."""
         arr = (_lib.FilterLeaf * max(1, len(leaves)))(*leaves)
         ops = np.ascontiguousarray(ops, dtype=np.uint32)
         tables = np.ascontiguousarray(tables, dtype=np.uint32)
@@ -370,6 +395,11 @@ class RowFilter(_Handle):
             out = np.zeros(n_words, np.uint32)
         elif out.dtype != np.uint32 or not out.flags.c_contiguous or len(out) < n_words:
             raise ValueError(f"out must be a contiguous uint32 array of at least {n_words} words")
+        if len(ops) and bool(((ops & 0xFF) == _lib.FILTER_OPS["list_any"]).any()):
+            _lib.check("vrag_row_filter_eval_lists", self._lib.vrag_row_filter_eval_lists(
+                self._h, arr, len(leaves), _vp(ops), len(ops), _vp(tables) if len(tables) else None, len(tables),
+                (_lib.FilterMatch * max(1, len(matches)))(*matches), len(matches), texts, len(texts), int(n_rows), _vp(out), stream))
+            return out
         if len(matches):
             _lib.check("vrag_row_filter_eval_matched", self._lib.vrag_row_filter_eval_matched(
                 self._h, arr, len(leaves), _vp(ops), len(ops), _vp(tables) if len(tables) else None, len(tables),

@@ -63,10 +63,15 @@ def like_match(stored: str, pattern: str) -> bool:
     return _like_regex(pattern).fullmatch(stored) is not None
 
 
+_LIST_FUNCTIONS = ("json_contains", "json_contains_any", "json_contains_all")
+
+
 def parse_filter_ast(expr: str):
     """The parser both back ends share: `expr` -> a tree of `("cmp", key, op, want)` (op one of == != < <= > >=, `want` the
-    literal's `_typed` key), `("in", key, [want, ...])`, `("like", key, pattern)`, `("not", a)`, `("and", a, b)`, `("or", a, b)`
-    (`x not in [..]` is `("not", ("in", ..))`).  Raises ValueError for anything outside the grammar `parse_filter` states."""
+    literal's `_typed` key), `("in", key, [want, ...])`, `("like", key, pattern)`, `("has", key, want)` (the list `key` holds an
+    element equal to `want`), `("not", a)`, `("and", a, b)`, `("or", a, b)` (`x not in [..]` is `("not", ("in", ..))`;
+    `json_contains_any` is nested `("or", ..)` and `json_contains_all` nested `("and", ..)` of `has` nodes).  Raises ValueError
+    for anything outside the grammar `parse_filter` states."""
     toks, pos = [], 0
     while pos < len(expr):
         if expr[pos:].strip() == "":
@@ -93,6 +98,8 @@ def parse_filter_ast(expr: str):
                 toks.append(("op", "LIKE"))
             elif w.lower() == "like":
                 toks.append(("miscased", w))        # a field name where a field may stand, an error where the keyword would
+            elif w.lower() in _LIST_FUNCTIONS:
+                toks.append(("function", w))        # a function name in front of a `(`, a field name anywhere else
             else:
                 toks.append(("field", w))
     i = 0
@@ -108,6 +115,52 @@ def parse_filter_ast(expr: str):
         i += 1
         return v
 
+    def membership():
+        """`json_contains(FIELD, VALUE)` / `json_contains_any(FIELD, [VALUE, ...])` / `json_contains_all(FIELD, [VALUE, ...])`,
+        the name taken already."""
+        name = toks[i - 1][1]
+        if name not in _LIST_FUNCTIONS and name not in [n.upper() for n in _LIST_FUNCTIONS]:
+            raise ValueError(f"GpuVectorStore: unsupported filter {expr!r}: the list functions are written json_contains, "
+                             f"json_contains_any, json_contains_all or JSON_CONTAINS, JSON_CONTAINS_ANY, JSON_CONTAINS_ALL "
+                             f"(got {name!r})")
+        name = name.lower()
+
+        def need(kind, value, what):
+            if peek() != (kind, value):
+                raise ValueError(f"GpuVectorStore: unsupported filter {expr!r}: {name} takes (field, "
+                                 f"{'value' if name == 'json_contains' else '[value, ...]'}): expected {what}")
+            take()
+
+        def value():
+            if peek()[0] != "val":
+                raise ValueError(f"GpuVectorStore: unsupported filter {expr!r}: {name} compares with a quoted string, a number or "
+                                 f"true / false (a list or an object as an element is not supported)")
+            return _typed(take())
+
+        need("op", "(", "'('")
+        if peek()[0] in ("miscased", "function"):
+            toks[i] = ("field", peek()[1])
+        if peek()[0] != "field":
+            raise ValueError(f"GpuVectorStore: unsupported filter {expr!r}: {name} takes a field first")
+        key = take()
+        need("op", ",", "','")
+        if name == "json_contains":
+            wants = [value()]
+        else:
+            need("op", "[", "a '[' that opens the list of values")
+            if peek() == ("op", "]"):
+                raise ValueError(f"GpuVectorStore: unsupported filter {expr!r}: {name} with an empty list")
+            wants = [value()]
+            while peek() == ("op", ","):
+                take()
+                wants.append(value())
+            need("op", "]", "']'")
+        need("op", ")", "')'")
+        tree = ("has", key, wants[0])
+        for want in wants[1:]:
+            tree = ("or" if name == "json_contains_any" else "and", tree, ("has", key, want))
+        return tree
+
     def comparison():
         if peek() == ("op", "("):
             take()
@@ -117,7 +170,10 @@ def parse_filter_ast(expr: str):
         if peek() == ("op", "not"):
             take()
             return ("not", comparison())
-        if peek()[0] == "miscased":
+        if peek()[0] == "function" and i + 1 < len(toks) and toks[i + 1] == ("op", "("):
+            take()
+            return membership()
+        if peek()[0] in ("miscased", "function"):
             toks[i] = ("field", peek()[1])
         key = take("field")
         if peek()[0] == "miscased":
@@ -192,6 +248,13 @@ def _closure(node):
         f = lambda md: _typed(md.get(key)) in vs      # noqa: E731
         f.lookup = (key, vals)
         return f
+    if tag == "has":
+        key, want = node[1], node[2]
+
+        def has(md):
+            have = md.get(key)
+            return isinstance(have, (list, tuple)) and any(_typed(e) == want for e in have)
+        return has                                    # no `lookup`: the per-key value index holds scalars
     if tag == "like":
         key, matches = node[1], _like_regex(node[2]).fullmatch
 
@@ -228,6 +291,18 @@ def parse_filter(expr: str):
     dicts and missing keys, as `not (title == "x")` does.  String literals have no escapes of their own: a pattern that needs
     a `"` is written in `'...'`.  The keyword is the upper-case word `LIKE` only, as the reference writes it; any other casing
     (`like`, `Like`) raises a ValueError that says so, and a metadata key named `LIKE` is written `metadata["LIKE"]`.
+    Membership in list-valued metadata stands wherever a comparison may: `json_contains(field, value)`,
+    `json_contains_any(field, [value, ...])` (some value is an element) and `json_contains_all(field, [value, ...])` (every
+    value is an element).  `json_contains(k, v)` holds iff the stored `k` is a list -- a tuple counts as one: both are a JSON
+    array, and a tuple is a list after a save / load -- and some element `e` has `_typed(e) == _typed(v)`: typed like `==`, so
+    `2020` finds `2020.0`, `"5"` does not find `5`, `true` does not find `1`; elements that are None, lists or dicts match
+    nothing.  A stored value that is no list (a missing key, a scalar, a dict) never passes, so `not json_contains(..)` holds
+    for it, as `not (k == v)` does.  A word is a function name only when it is exactly one of the three names in lower case or
+    exactly its upper-case form (`JSON_CONTAINS`, ..) and a `(` follows; anywhere else it stays a field name
+    (`json_contains == 3` filters on a key of that name), and any other casing in front of a `(` raises a ValueError that names
+    the accepted spellings.  An empty `[]`, a list or object literal as a value and a wrong number of arguments raise
+    ValueError.  These are this store's semantics, not pinned against Milvus; `array_length`, index access, `is null` /
+    `exists` and `TEXT_MATCH` are outside the grammar.
     Anything else raises ValueError -- a filter is never silently ignored."""
     return _closure(parse_filter_ast(expr))
 
@@ -243,6 +318,8 @@ def parse_filter(expr: str):
 #                                                    once per distinct stored string (store_columns.MetaColumn.string_table) or
 #                                                    the match kernel applies to the column's dictionary in HBM (csrc/strmatch.hip)
 # `in [..]` is an OR of `==` leaves: a list may mix kinds.  `LIKE` is one leaf that only a string can answer (str_op "like").
+# `has` is one `==` leaf pushed with "list_any": the OR, over the elements of the row's list, of what the leaf answers for the
+# element (0 for a row that holds no list or an empty one) -- VRAG_FILTER_OP_LIST_ANY, csrc/listfilter.hip.
 MAX_COLUMNS, MAX_LEAVES, MAX_OPS, MAX_DEPTH = 16, 64, 256, 32     # VRAG_FILTER_MAX_*
 STRING_COMPARE = {"==": operator.eq, "!=": operator.ne, **_ORDER, "like": like_match}
 
@@ -262,13 +339,13 @@ class FilterLeaf:
 class FilterProgram:
     keys: List[str] = field(default_factory=list)                # referenced metadata keys, in first-use order
     leaves: List[FilterLeaf] = field(default_factory=list)
-    ops: List[Tuple[str, int]] = field(default_factory=list)     # ("leaf", i) | ("and", 0) | ("or", 0) | ("not", 0), postfix
+    ops: List[Tuple[str, int]] = field(default_factory=list)     # ("leaf", i) | ("list_any", i) | ("and", 0) | ("or", 0) | ("not", 0), postfix
 
     def depth(self) -> int:
         """Deepest the evaluation stack gets."""
         deepest = cur = 0
         for op, _i in self.ops:
-            cur += 1 if op == "leaf" else (-1 if op in ("and", "or") else 0)
+            cur += 1 if op in ("leaf", "list_any") else (-1 if op in ("and", "or") else 0)
             deepest = max(deepest, cur)
         return deepest
 
@@ -307,6 +384,9 @@ def compile_filter(expr: str) -> FilterProgram:
         tag = node[0]
         if tag == "cmp":
             push(node[1], node[2], node[3])
+        elif tag == "has":
+            push(node[1], "==", node[2])
+            prog.ops[-1] = ("list_any", prog.ops[-1][1])
         elif tag == "like":
             if node[1] not in prog.keys:
                 prog.keys.append(node[1])

@@ -584,7 +584,10 @@ class GpuVectorStore(VectorStore):
         the first filter that names its key, extended by the rows of every later insert, and costs 9 bytes of HBM per row.  The
         same mask bit for bit.  A filter beyond the device program's limits (16 keys, 64 comparisons, 256 operations, nesting
         32 deep) or naming a key that holds a NaN is answered on the host (logged once per filter string).  A run-time choice like
-        `filter_route`: not written by `save`, a keyword of `load`.
+        `filter_route`: not written by `save`, a keyword of `load`.  A `json_contains` / `_any` / `_all` filter reads the key's
+        lists instead, kept in HBM as CSR (8 bytes per row + 9 per element, csrc/listfilter.hip): uploaded by the first list filter
+        on the key, extended after every insert, dropped by `compact()` and uploaded again by the next list filter; a NaN
+        inside a list of the key sends list filters on it to the host.
         `filter_strings` (only with `filter_eval="device"`): who applies a filter's string comparisons and `LIKE` patterns to the
         distinct strings of a key -- "host" (default) Python, once per distinct string for every new (operator, text); "device"
         the match kernel (csrc/strmatch.hip) over the key's string dictionary kept in HBM (its UTF-8 bytes plus 8 bytes per
@@ -1084,10 +1087,15 @@ class GpuVectorStore(VectorStore):
             if column is None:
                 column = self._meta_columns[key] = MetaColumn(key)
                 column.extend(self._meta)
-            if not column.exact:
+            at = program.keys.index(key)
+            pushed = {op for op, i in program.ops if op in ("leaf", "list_any") and program.leaves[i].column == at}
+            if "leaf" in pushed and not column.exact:
                 why = f"metadata[{key!r}] holds a NaN or a number beyond float range"
                 break
-            columns.append(column)
+            if "list_any" in pushed and not column.list_exact:
+                why = f"a list of metadata[{key!r}] holds a NaN or a number beyond float range"
+                break
+            columns.append((column, pushed))
         if why is not None:
             if filter not in self._filter_fallbacks:
                 if len(self._filter_fallbacks) >= 1024:
@@ -1098,13 +1106,18 @@ class GpuVectorStore(VectorStore):
         if self._row_filter is None:
             self._row_filter = RowFilter(self.device)
         device_cols = []
-        for column in columns:
+        for column, pushed in columns:
             col = self._row_filter_cols.get(column.key)
             if col is None:
                 col = self._row_filter_cols[column.key] = self._row_filter.add_column()
             have = self._row_filter.rows(col)
-            if have < len(column):
+            if "leaf" in pushed and have < len(column):
                 self._row_filter.append(col, column.kinds[have:], column.payload[have:])
+            if "list_any" in pushed:        # the list part travels with the first list filter on the key, then per insert
+                have, elems = self._row_filter.list_rows(col)
+                if have < len(column):
+                    self._row_filter.append_lists(col, column.elem_off[have:] - elems, column.elem_kinds[elems:],
+                                                  column.elem_payload[elems:])
             device_cols.append((col, column))
         if self.filter_strings == "host":
             return self._row_filter.eval_program(program, device_cols, len(self._meta))
