@@ -389,6 +389,40 @@ int vrag_dense_index_search_filtered(vrag_dense_index* ix, const float* queries 
                                      float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Grouping search over a dense index (csrc/grouped.hip; Milvus' group_by_field / group_size, which the reference's stores can pass
+ * in search_params).  The semantics are this library's own and are not pinned against Milvus.
+ * A vrag_group_column holds one int32 group code >= 0 per row of an index it does not own, in HBM, extended by appends (row r of
+ * the column describes row r of the index); it remembers the largest code + 1 (`n_codes`) and owns the scratch, the stream and the
+ * lock of the searches made with it.  Codes should be dense: a search keeps 8 * group_size * n_codes bytes of keys per query.
+ *   search_grouped   Rows considered: r < min(size of the index, size of the column) -- with a bitmap (`allow`, host words, bit r % 32
+ *                    of word r / 32, as in vrag_dense_index_search_filtered) r < n_allow as well and the bit set; allow == NULL (then
+ *                    n_allow must be 0) means every such row.  Rank those rows by (score desc, row asc); scores are the sequential
+ *                    chain acc = fmaf(x[c], q[c], acc), c ascending, of vrag_dense_index_search_filtered bit for bit (fp32 row, or
+ *                    the bf16 row widened), zeros of either sign tie.  A group's rank is that of its best row.  Per query:
+ *                    groups[g] = the code of the g-th group in that order, scores / ids [g][0 .. group_size) = that group's first
+ *                    group_size rows in that order.  Missing entries (a group with fewer rows, fewer groups than n_groups) are
+ *                    -1 / -inf, a missing group's code is -1.  The result does not depend on the order in which the device
+ *                    scores the rows: two calls return the same bytes.
+ *                    1 <= n_groups <= 64, 1 <= group_size <= VRAG_GROUPED_MAX_SIZE.  Queries are processed in slices whose keys fit
+ *                    VRAG_GROUPED_SCRATCH_BYTES; a single query that needs more is VRAG_ERR_INVALID.  Every slice scans the passing rows.
+ * Argument errors (null pointers, nq <= 0, n_groups or group_size out of range, a null bitmap with n_allow > 0, a negative code,
+ * a column on another device than the index) are VRAG_ERR_INVALID before anything is launched or allocated.  The caller keeps
+ * the column in step with the index: after vrag_dense_index_compact the column is rebuilt.  A search runs under the column's lock
+ * and the index's (taken in that order), like the other searches of the index: a compaction waits for it. */
+#define VRAG_GROUPED_MAX_SIZE 16
+#define VRAG_GROUPED_SCRATCH_BYTES (256u << 20)
+typedef struct vrag_group_column vrag_group_column;
+int vrag_group_column_create(int32_t device, vrag_group_column** out);
+void vrag_group_column_destroy(vrag_group_column* col);
+int vrag_group_column_append(vrag_group_column* col, const int32_t* codes /*[n] host*/, int64_t n);
+int64_t vrag_group_column_size(vrag_group_column* col);
+int vrag_dense_index_search_grouped(vrag_dense_index* ix, const float* queries /*[nq,dim] host*/, int32_t nq, int32_t n_groups,
+                                    int32_t group_size, vrag_group_column* column,
+                                    const uint32_t* allow /*host bitmap or NULL*/, int64_t n_allow,
+                                    float* scores /*[nq,n_groups,group_size]*/, int64_t* ids /*[nq,n_groups,group_size]*/,
+                                    int32_t* groups /*[nq,n_groups]*/, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * IVF_FLAT over a dense index (csrc/ivf.hip; the reference builds every Milvus store with index_type="IVF_FLAT", nlist and
  * searches with search_params={"nprobe": N}: verbatim_rag/vector_stores/milvus_base.py:40-50, milvus_local.py:109-117,
  * index.py:571).  Opt-in and APPROXIMATE in which rows it looks at, exact in what it reports about them.

@@ -148,6 +148,12 @@ SIGNATURES = {
     "vrag_dense_index_read": (C.c_int, [_H, C.c_int64, C.c_int64, _FP]),
     "vrag_dense_index_search_device": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                                  C.c_void_p, C.c_void_p]),
+    "vrag_dense_index_search_grouped": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_int32, _H, C.c_void_p, C.c_int64, _FP, _LP, _IP,
+                                                  C.c_void_p]),
+    "vrag_group_column_create": (C.c_int, [C.c_int32, C.POINTER(_H)]),
+    "vrag_group_column_destroy": (None, [_H]),
+    "vrag_group_column_append": (C.c_int, [_H, _IP, C.c_int64]),
+    "vrag_group_column_size": (C.c_int64, [_H]),
     "vrag_ivf_index_create": (C.c_int, [_H, C.c_int32, C.POINTER(_H)]),
     "vrag_ivf_index_destroy": (None, [_H]),
     "vrag_ivf_index_set_centroids": (C.c_int, [_H, _FP]),

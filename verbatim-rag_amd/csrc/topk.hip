@@ -2476,6 +2476,8 @@ DenseView dense_index_view(vrag_dense_index* ix) {
   std::lock_guard<std::mutex> lk(ix->mu);
   return DenseView{ix->rows.p, ix->dim, ix->dtype, ix->device, ix->size};
 }
+std::unique_lock<std::mutex> dense_index_lock(vrag_dense_index* ix) { return std::unique_lock<std::mutex>(ix->mu); }
+DenseView dense_index_view_locked(vrag_dense_index* ix) { return DenseView{ix->rows.p, ix->dim, ix->dtype, ix->device, ix->size}; }
 }  // namespace vrag
 
 // May a search of `nq` queries take the prefilter-image route of an fp32 index?  The route's fallback -- the full fp32 scan

@@ -4,6 +4,7 @@
 // them checks its arguments; the launch's status is returned.
 #pragma once
 #include <cmath>
+#include <mutex>
 #include <vector>
 
 #include "common.h"
@@ -88,4 +89,8 @@ struct DenseView {
 struct vrag_dense_index;
 namespace vrag {
 DenseView dense_index_view(vrag_dense_index* ix);
+// For a search of the index's rows that lives in another file (csrc/grouped.hip): the index's lock, held for the whole call like
+// the searches of csrc/topk.hip hold it -- a compaction, which moves rows in place, waits -- and the view read under it.
+std::unique_lock<std::mutex> dense_index_lock(vrag_dense_index* ix);
+DenseView dense_index_view_locked(vrag_dense_index* ix);
 }  // namespace vrag

@@ -143,6 +143,23 @@ class DenseShard(_Handle):
         word `r // 32`, as `_bitmap` packs them): exact chains over the passing rows only (`vrag_dense_index_search_filtered`)."""
         return self._search(queries, k, (allow_words, n_allow), stream)
 
+    def search_grouped(self, queries: np.ndarray, n_groups: int, group_size: int, column: "GroupColumn",
+                       allow_words: Optional[np.ndarray] = None, n_allow: int = 0,
+                       stream=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Grouping search (`vrag_dense_index_search_grouped`): per query the best `n_groups` groups of `column` among the rows
+        `r < min(len(self), len(column))` -- with `allow_words` those below `n_allow` whose bit is set -- each with its best
+        `group_size` rows.  Returns (scores float32 `[Q, n_groups, group_size]`, ids int64 likewise, groups int32
+        `[Q, n_groups]`); missing entries are -inf / -1 / -1."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        allow = (None, 0) if allow_words is None else (_vp(_allow_words(allow_words, n_allow)), int(n_allow))
+        scores = np.empty((nq, n_groups, group_size), np.float32)
+        ids = np.empty((nq, n_groups, group_size), np.int64)
+        groups = np.empty((nq, n_groups), np.int32)
+        _lib.check("vrag_dense_index_search_grouped", self._lib.vrag_dense_index_search_grouped(
+            self._h, _fp(q), nq, int(n_groups), int(group_size), column._h, *allow, _fp(scores), _lp(ids), _ip(groups), stream))
+        return scores, ids, groups
+
     def search_device(self, queries: np.ndarray, k: int, out_scores: int, out_ids: int, row_map: Optional[int] = None,
                       n_map: int = 0, id_base: int = 0, stream=None) -> None:
         """The same search with the `[Q, k]` lists left in HBM at the device addresses `out_scores` / `out_ids`
@@ -172,6 +189,24 @@ class DenseShard(_Handle):
         if ivf is not None:
             ivf.close()
         super().close()
+
+
+class GroupColumn(_Handle):
+    """One int32 group code (>= 0) per row of a `DenseShard`, in HBM (`vrag_group_column`): what `DenseShard.search_grouped`
+    groups by.  Appended to in row order; owns the scratch of the searches made with it."""
+
+    _destroy = "vrag_group_column_destroy"
+
+    def __init__(self, device: int = 0):
+        _lib.require_gpu()
+        self._open("vrag_group_column_create", int(device))
+
+    def append(self, codes: np.ndarray) -> None:
+        codes = np.ascontiguousarray(codes, dtype=np.int32).reshape(-1)
+        _lib.check("vrag_group_column_append", self._lib.vrag_group_column_append(self._h, _ip(codes) if len(codes) else None, len(codes)))
+
+    def __len__(self) -> int:
+        return int(self._lib.vrag_group_column_size(self._h))
 
 
 class Sq8Shard(_Handle):

@@ -15,6 +15,7 @@ import ctypes as C
 import functools
 import json
 import logging
+import re
 import threading
 from abc import ABC, abstractmethod
 from dataclasses import dataclass
@@ -25,9 +26,10 @@ import numpy as np
 from . import _lib
 # The layers under the store, re-exported here under the names callers and tests have always used.  The store resolves
 # DenseShard / SparseShard / IvfOverlay / TextIndex through THIS module's globals at call time (tests replace them here).
-from .shards import (_FP, _IP, _LP, DenseShard, IvfOverlay, RowFilter, SparseShard, Sq8Shard, TextIndex, _allow_words, _bitmap,  # noqa: F401
+from .shards import (_FP, _IP, _LP, DenseShard, GroupColumn, IvfOverlay, RowFilter, SparseShard, Sq8Shard, TextIndex, _allow_words, _bitmap,  # noqa: F401
                      _utf8_batch, dicts_to_csr, tokenize_keys)
 from .store_columns import MetaColumn
+from .store_groups import GroupCodes
 from .store_filter import _FILTER_TOKEN, _typed, compile_filter, parse_filter  # noqa: F401
 from .store_io import _NO_METADATA, _get_strings, _put_strings, _replace_into, _write_text, read_saved  # noqa: F401
 
@@ -272,7 +274,7 @@ def ivf_effective_nlist(n_rows: int, nlist: int) -> int:
 
 def parse_nprobe(search_params: Optional[Dict[str, Any]], default: int) -> int:
     """`nprobe` of a query's `search_params`: `{"nprobe": n}` as the reference's callers pass it (index.py:571) or Milvus'
-    `{"params": {"nprobe": n}}`; other keys are ignored, no `nprobe` = `default`.  ValueError unless a positive integer."""
+    `{"params": {"nprobe": n}}`; the grouping keys are `parse_grouping`'s, other keys are ignored, no `nprobe` = `default`.  ValueError unless a positive integer."""
     value = None
     if search_params:
         inner = search_params.get("params")
@@ -285,6 +287,57 @@ def parse_nprobe(search_params: Optional[Dict[str, Any]], default: int) -> int:
     if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < 1:
         raise ValueError(f"nprobe must be a positive integer (got {value!r})")
     return int(value)
+
+
+GROUP_TOP_K_MAX = 64      # vrag_dense_index_search_grouped: groups per query
+GROUP_SIZE_MAX = 16       # ... and rows per group
+_GROUP_KEYS = ("group_by_field", "group_size", "strict_group_size")
+_GROUP_FIELD = re.compile(r"""^metadata\[\s*(["'])(.+)\1\s*\]$""")
+
+
+@dataclass(frozen=True)
+class Grouping:
+    """A query's grouping request: the metadata key, rows per group, and Milvus' `strict_group_size` (accepted, no effect:
+    an exact search always returns every row a group has, up to `group_size`)."""
+    key: str
+    group_size: int = 1
+    strict: bool = False
+
+
+def parse_grouping(search_params: Optional[Dict[str, Any]]) -> Optional[Grouping]:
+    """The grouping request of a query's `search_params`: `group_by_field` (a metadata key, bare or spelled
+    `metadata["key"]`), `group_size` (default 1, at most `GROUP_SIZE_MAX`) and `strict_group_size` (a bool), at top level or
+    under `"params"` like `nprobe` (top level wins).  None when no `group_by_field` is given.  ValueError for a field that is
+    no non-empty string, a `group_size` that is no integer in range, a `strict_group_size` that is no bool, and for
+    `group_size` / `strict_group_size` without a `group_by_field`."""
+    given: Dict[str, Any] = {}
+    if search_params:
+        inner = search_params.get("params")
+        for name in _GROUP_KEYS:
+            if name in search_params:
+                given[name] = search_params[name]
+            elif isinstance(inner, dict) and name in inner:
+                given[name] = inner[name]
+    if "group_by_field" not in given:
+        if given:
+            raise ValueError(f"{sorted(given)[0]} needs a group_by_field")
+        return None
+    field = given["group_by_field"]
+    if not isinstance(field, str) or not field.strip():
+        raise ValueError(f"group_by_field must be a metadata key (got {field!r})")
+    field = field.strip()
+    spelled = _GROUP_FIELD.match(field)
+    if spelled:
+        field = spelled.group(2)
+    elif field.startswith("metadata["):
+        raise ValueError(f"group_by_field must be a metadata key or metadata[\"key\"] (got {field!r})")
+    size = given.get("group_size", 1)
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or not 1 <= size <= GROUP_SIZE_MAX:
+        raise ValueError(f"group_size must be an integer in [1, {GROUP_SIZE_MAX}] (got {size!r})")
+    strict = given.get("strict_group_size", False)
+    if not isinstance(strict, (bool, np.bool_)):
+        raise ValueError(f"strict_group_size must be a bool (got {strict!r})")
+    return Grouping(field, int(size), bool(strict))
 
 
 def check_index_config(index_type: str, nlist: int, nprobe: int, sharded: bool) -> None:
@@ -704,6 +757,10 @@ class GpuVectorStore(VectorStore):
         self._row_filter: Optional[RowFilter] = None
         self._row_filter_cols: Dict[str, int] = {}
         self._filter_fallbacks: set = set()
+        # grouping search: per key the host group codes (over the key's column in `_meta_columns`) and their device copy;
+        # both are dropped by `compact()` and rebuilt by the next grouped query on the key
+        self._group_codes: Dict[str, GroupCodes] = {}
+        self._group_cols: Dict[str, GroupColumn] = {}
         self._all_ids_truthy = True
         # replicated like `_all_ids_truthy`: no two rows share an id (the ids seen so far, until two of them do).  Rows that
         # share an id are ONE candidate of a hybrid fusion (hybrid_search.py:73-129 keys by id); deletes leave it as it is.
@@ -726,6 +783,7 @@ class GpuVectorStore(VectorStore):
             self._text = None
             self._owned_dev = None
             self._row_filter, self._row_filter_cols = None, {}    # the host columns stay: they are uploaded again on demand
+            self._group_cols = {}                                 # likewise the group codes
             self._dense_flushed = self._sparse_flushed = self._text_flushed = self._text_main = 0
             self._dirty = True
             if self._comm is not None and self._owns_comm:
@@ -876,6 +934,7 @@ class GpuVectorStore(VectorStore):
                 self._dense_flushed = live
             if self._row_filter is not None:
                 self._row_filter.compact(keep)
+            self._group_codes, self._group_cols = {}, {}    # rebuilt from the compacted columns by the next grouped query
             self._sparse_parts, self._sparse_flushed = [], 0
             self._text, self._text_flushed, self._text_main = None, 0, 0
             self._text_live_stale, self._text_totals = True, None
@@ -1526,6 +1585,12 @@ class GpuVectorStore(VectorStore):
         if not (len(dq) == len(sq) == len(tq) == n):
             raise ValueError("query_batch: dense_queries / sparse_queries / text_queries differ in length")
 
+        grouping = parse_grouping(search_params)
+        if grouping is not None:
+            self._check_grouped_call(search_type, hybrid_weights, top_k, all(_is_given(q) for q in dq),
+                                     any(not _is_given(d) and not _is_given(s) for d, s in zip(dq, sq)))
+            return self._grouped_batch(dq, top_k, filter, grouping)
+
         def single(i):
             return self.query(dense_query=dq[i], sparse_query=sq[i], text_query=tq[i], top_k=top_k, search_type=search_type,
                               filter=filter, search_params=search_params, hybrid_weights=hybrid_weights, rrf_k=rrf_k)
@@ -1570,7 +1635,14 @@ class GpuVectorStore(VectorStore):
     def query(self, dense_query=None, sparse_query=None, text_query=None, top_k: int = 5, search_type: str = "hybrid",
               filter: Optional[str] = None, search_params: Optional[Dict[str, Any]] = None,
               hybrid_weights: Optional[Dict[str, float]] = None, rrf_k: int = 60) -> List[SearchResult]:
-        """milvus_base.py:189-313.  `top_k` (2 * top_k in hybrid mode) may not exceed `K_LIMIT` = 1024."""
+        """milvus_base.py:189-313.  `top_k` (2 * top_k in hybrid mode) may not exceed `K_LIMIT` = 1024.
+        `search_params={"group_by_field": key, "group_size": g}` (`parse_grouping`) makes a dense query a grouping search: the
+        best `top_k` groups of `metadata[key]`, each with its best `g` rows, as one flat list group by group (`_grouped_batch`)."""
+        grouping = parse_grouping(search_params)
+        if grouping is not None:
+            self._check_grouped_call(search_type, hybrid_weights, top_k, _is_given(dense_query),
+                                     not _is_given(dense_query) and not _is_given(sparse_query))
+            return self._grouped_batch([dense_query], top_k, filter, grouping)[0]
         if hybrid_weights is not None:
             return self._hybrid_search_with_weights(dense_query, sparse_query, text_query, top_k, filter, hybrid_weights, rrf_k,
                                                     self._nprobe_of(search_params))
@@ -1598,6 +1670,78 @@ class GpuVectorStore(VectorStore):
             raise ValueError(f"Invalid search configuration: type={search_type}, "
                              f"dense={dense_query is not None}, sparse={sparse_query is not None}")
         return self._results(hits)
+
+    # -------------------------------------------------------------- grouping search
+    def _check_grouped_call(self, search_type: str, hybrid_weights, top_k: int, dense_given: bool, filter_only: bool) -> None:
+        """The refusals of a grouped `query` / `query_batch`: everything but a dense query on a single-GPU FLAT store of fp32 or
+        bf16 rows."""
+        supported = ("grouping search (group_by_field) is supported for search_type='dense' on a single-GPU store with "
+                     "index_type='FLAT' and dense_dtype 'f32' or 'bf16'")
+        if hybrid_weights is not None:
+            raise ValueError(f"{supported}: not with hybrid_weights")
+        if filter_only:
+            raise ValueError(f"{supported}: a filter-only call (no query vector) cannot be grouped")
+        if search_type != "dense":
+            raise ValueError(f"{supported}: not with search_type={search_type!r}")
+        if not dense_given:
+            raise ValueError(f"{supported}: it needs a dense query")
+        if not self.enable_dense:
+            raise ValueError(f"{supported}: this store has no dense field")
+        if self._comm is not None:
+            raise ValueError(f"{supported}: not on a sharded store (distributed=True or a comm)")
+        if self.index_type == "IVF_FLAT":
+            raise ValueError(f"{supported}: not with index_type='IVF_FLAT'")
+        if self.dense_dtype == "int8":
+            raise ValueError(f"{supported}: not with dense_dtype='int8'")
+        if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= top_k <= GROUP_TOP_K_MAX:
+            raise ValueError(f"a grouping search returns 1 <= top_k <= {GROUP_TOP_K_MAX} groups (got {top_k!r})")
+
+    def _group_column(self, key: str, n: int) -> GroupColumn:
+        """The device group codes of `metadata[key]` for rows `[0, n)` (under the lock, after a flush): the host codes are built
+        over the key's typed column -- the one `filter_eval="device"` keeps, or a new one, extended by every insert either way --
+        by one pass at the first grouped query on the key and by the new rows afterwards; only codes not uploaded yet travel."""
+        codes = self._group_codes.get(key)
+        if codes is None:
+            column = self._meta_columns.get(key)
+            if column is None:
+                column = self._meta_columns[key] = MetaColumn(key)
+                column.extend(self._meta)
+            codes = self._group_codes[key] = GroupCodes(column)
+        host = codes.sync()
+        if not codes.column.exact:
+            raise ValueError(f"group_by_field: metadata[{key!r}] holds a NaN or a number beyond float range; its rows cannot be grouped")
+        device = self._group_cols.get(key)
+        if device is None:
+            device = self._group_cols[key] = GroupColumn(self.device)
+        have = len(device)
+        if have < n:
+            device.append(host[have:n])
+        return device
+
+    def _grouped_batch(self, queries: Sequence[Any], top_k: int, filter: Optional[str], grouping: Grouping,
+                       _retry: int = 0) -> List[List[SearchResult]]:
+        """Grouping search for a batch of dense queries: per query the best `top_k` groups of `metadata[grouping.key]` among the
+        rows that pass `filter` (deletes excluded), each with its best `grouping.group_size` rows, flattened group by group.
+        One `DenseShard.search_grouped` call on the resident shard, whatever `filter_route` is: the mask travels as a bitmap."""
+        mask = self._mask(filter)
+        with self._mu:
+            self._flush()
+            shard, n = self._dense, len(self._ids)
+            column = self._group_column(grouping.key, n) if shard is not None and n else None
+        Q, g = len(queries), grouping.group_size
+        mask = self._fit_mask(mask, n)
+        if column is None or Q == 0 or (mask is not None and not mask.any()):
+            return [[] for _ in range(Q)]
+        allow = () if mask is None else (_bitmap(mask), n)
+        scores, local, _groups = shard.search_grouped(self._unit_queries(queries), top_k, g, column, *allow)
+        rows_of = self._main_rows       # read AFTER the kernel returned: every row the kernel can have seen is in it (`_flush`)
+        found = (local >= 0) & (local < len(rows_of))
+        rows = np.where(found, rows_of[np.where(found, local, 0)], -1) if len(rows_of) else np.full_like(local, -1)
+        if (rows >= n).any():           # rows inserted while this search ran took slots: search again
+            if _retry < 3:
+                return self._grouped_batch(queries, top_k, filter, grouping, _retry + 1)
+            rows = np.where(rows < n, rows, -1)
+        return self._results_batch(rows.reshape(Q, top_k * g), scores.reshape(Q, top_k * g))
 
     def _filter_only_query(self, filter: Optional[str], limit: int) -> List[SearchResult]:
         mask = self._mask(filter)
