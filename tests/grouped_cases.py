@@ -163,7 +163,7 @@ def scenario(make_store, load_store, tmp_dir, n_rows: int, n_queries: int, key: 
     rng = np.random.default_rng(5)
     queries = np.concatenate([M.unit_rows(rng, n_queries - 2, DIM), np.stack([first[0].dense, first[40].dense])])
     assert check(st, model, queries, key, "fresh") > 0
-    assert key in st._group_codes and len(st._group_codes[key]) == n_rows
+    assert key in st._metadata.group_codes and len(st._metadata.group_codes[key]) == n_rows
     # deletes: single rows, and every row of one document
     gone = [r.id for r in first if r.serial % 5 == 2 or r.meta.get("document_id") == "d4"]
     st.delete(gone)
@@ -171,18 +171,18 @@ def scenario(make_store, load_store, tmp_dir, n_rows: int, n_queries: int, key: 
         r.alive = r.alive and r.id not in set(gone)
     check(st, model, queries, key, "after delete", shapes=SHAPES[1:3])
     # an insert behind the built column: the codes are extended by the new rows only
-    codes_before = st._group_codes[key]
+    codes_before = st._metadata.group_codes[key]
     more = rows_of(max(n_rows // 8, 40), seed=12, first=n_rows)
     fill(st, more)
     model.rows.extend(more)
     check(st, model, queries, key, "after insert", shapes=SHAPES[1:3])
-    assert st._group_codes[key] is codes_before and len(codes_before) == len(model.rows)
+    assert st._metadata.group_codes[key] is codes_before and len(codes_before) == len(model.rows)
     # compact(): the columns are dropped and rebuilt lazily
     assert st.compact() == len(gone)
     model.rows = [r for r in model.rows if r.alive]
-    assert st._group_codes == {} and st._group_cols == {}
+    assert st._metadata.group_codes == {} and st._metadata.group_cols == {}
     check(st, model, queries, key, "after compact", shapes=SHAPES[1:3])
-    assert len(st._group_codes[key]) == len(model.rows)
+    assert len(st._metadata.group_codes[key]) == len(model.rows)
     # the typing rules, on the store
     check(st, model, queries, "year", "year", shapes=[(10, 3)], filters=FILTERS[:2])
     check(st, model, queries, "no_such_key", "missing key", shapes=[(5, 2)], filters=FILTERS[:1])
@@ -194,7 +194,7 @@ def scenario(make_store, load_store, tmp_dir, n_rows: int, n_queries: int, key: 
     st.close()
     st = load_store(path)
     model.rows = [r for r in model.rows if r.alive]
-    assert st._group_codes == {}
+    assert st._metadata.group_codes == {}
     check(st, model, queries, key, "after load", shapes=SHAPES[:2])
     st.close()
 

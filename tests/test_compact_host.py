@@ -3,6 +3,8 @@ column; what it returns; who may not call it; when `auto_compact` calls it; dele
 lands inside a filtered query; and two negative controls -- a device layer that compacts out of order, and a store whose
 epoch does not move -- that the comparisons notice.  The rows are store_model's dyadic-grid rows (entries 0, +-1/8, +-2/8: every
 score is exact and rows tie exactly, so a wrong order among equal scores shows)."""
+from operator import attrgetter
+
 import numpy as np
 import pytest
 
@@ -39,7 +41,7 @@ def _dense_answers(st, rows, flt=None, k=10):
     return [CC.answers(st.query(dense_query=r.dense.tolist(), top_k=k, search_type="dense", filter=flt)) for r in rows[:5]]
 
 
-COLUMNS = ("_ids", "_texts", "_enh", "_meta", "_all_ids_truthy", "_ids_unique", "_id_seen", "_id_rows", "_value_indexes", "_masks",
+COLUMNS = ("_ids", "_texts", "_enh", "_meta", "_all_ids_truthy", "_ids_unique", "_id_seen", "_id_rows", "_metadata.value_indexes", "_masks",
            "_subsets", "_documents")
 ARRAYS = ("_alive", "_owned", "_dense_rows", "_sp_ptr", "_sp_idx", "_sp_val")
 
@@ -61,11 +63,11 @@ def test_state_after_compact_is_the_state_after_save_and_load(tmp_path, text):
         assert st.compact() == dead > 100
         assert len(st) == len(loaded) == 310 - dead
         for name in COLUMNS:
-            assert getattr(st, name) == getattr(loaded, name), name
+            assert attrgetter(name)(st) == attrgetter(name)(loaded), name
         for name in ARRAYS:
             a, b = getattr(st, name).data, getattr(loaded, name).data
             assert a.dtype == b.dtype and np.array_equal(a, b), name
-        assert st._id_rows is None and st._value_indexes == {} and not st._ids_unique
+        assert st._id_rows is None and st._metadata.value_indexes == {} and not st._ids_unique
         # after a flush the device layers hold the same rows, and every method answers alike
         live = [r for r in rows if r.id not in set(gone) | {"id12"}]
         for kw in (dict(search_type="dense"), dict(search_type="sparse"), dict(search_type="hybrid"),

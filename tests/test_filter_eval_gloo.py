@@ -88,12 +88,12 @@ def test_store_wiring_single_rank_equals_the_host_route(caplog):
         want, host = _session(filter_eval="host")
         got, dev = _session(filter_eval="device")
         assert got == want
-        assert host._row_filter is None and not host._meta_columns
-        assert sorted(dev._meta_columns) == ["misc", "peer", "score", "source", "tag", "year"]       # the lookup filter built none of its own
-        assert dev._row_filter.evals == 3 * 6 + 3 and all(dev._row_filter.rows(c) == 230 for c in dev._row_filter_cols.values())
+        assert host._metadata.row_filter is None and not host._metadata.columns
+        assert sorted(dev._metadata.columns) == ["misc", "peer", "score", "source", "tag", "year"]       # the lookup filter built none of its own
+        assert dev._metadata.row_filter.evals == 3 * 6 + 3 and all(dev._metadata.row_filter.rows(c) == 230 for c in dev._metadata.row_filter_cols.values())
         assert any(m is not None and any(m) and not all(m) for m in want)
         # fallbacks: a NaN, a program over the limits -- answered on the host, said once per filter string, never an error
-        evals = dev._row_filter.evals
+        evals = dev._metadata.row_filter.evals
         long = " or ".join(f"year == {i}" for i in range(65))
         for st in (host, dev):
             st.add_vectors(["nan"], [[0.5] * 64], None, ["t"], [""], [{"score": float("nan"), "year": 2021}])
@@ -104,10 +104,10 @@ def test_store_wiring_single_rank_equals_the_host_route(caplog):
                 dev._drop_subsets()
         said = [r.getMessage() for r in caplog.records if "evaluated on the host" in r.getMessage()]
         assert len(said) == 2 and "NaN" in said[0] and "65 leaves" in said[1], said
-        assert dev._row_filter.evals == evals + 2                                                     # "year > 2020", twice
+        assert dev._metadata.row_filter.evals == evals + 2                                                     # "year > 2020", twice
         made = CpuRowFilter.made
         dev.close()
-        assert dev._row_filter is None and not dev._row_filter_cols
+        assert dev._metadata.row_filter is None and not dev._metadata.row_filter_cols
         assert np.array_equal(dev._mask("year > 2019"), host._mask("year > 2019")) and CpuRowFilter.made == made + 1   # uploaded again
     with stand_ins(), pytest.raises(ValueError, match="filter_eval must be 'host' or 'device'"):
         vs.GpuVectorStore(dense_dim=64, enable_sparse=False, sparse_vocab=None, filter_eval="gpu")
@@ -133,7 +133,7 @@ def _mask_worker(rank, world, port, q):
                 held = len(st._meta)
                 if got != single:
                     ok = f"payload={payload}: the masks differ from the single-rank host route"
-                elif not st._row_filter or st._row_filter.evals == 0:
+                elif not st._metadata.row_filter or st._metadata.row_filter.evals == 0:
                     ok = f"payload={payload}: the device route did not run"
                 elif (payload == "sharded") != (held < 230):
                     ok = f"payload={payload}: rank {rank} holds {held} metadata rows"

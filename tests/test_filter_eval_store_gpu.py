@@ -118,9 +118,9 @@ def test_device_filter_evaluation_equals_the_host_route(route, tmp_path, caplog)
     try:
         _compare(host, dev, dq, sq, tq, "fresh")
         # the device route did run: one column per key the compound filters name, every row uploaded; none for the lookup path
-        assert not host._meta_columns and host._row_filter is None
-        assert {"year", "source", "peer", "score", "tag", "missing_everywhere", "half", "document_id"} == set(dev._meta_columns)
-        assert all(dev._row_filter.rows(c) == N for c in dev._row_filter_cols.values())
+        assert not host._metadata.columns and host._metadata.row_filter is None
+        assert {"year", "source", "peer", "score", "tag", "missing_everywhere", "half", "document_id"} == set(dev._metadata.columns)
+        assert all(dev._metadata.row_filter.rows(c) == N for c in dev._metadata.row_filter_cols.values())
         masks = [m for m in (host._mask(f) for f in FILTERS) if m is not None]
         assert sum(bool(m.any() and not m.all()) for m in masks) >= 17       # the filters split the rows
 
@@ -128,12 +128,12 @@ def test_device_filter_evaluation_equals_the_host_route(route, tmp_path, caplog)
         metas2[3]["source"] = "a source no earlier row had"
         for st in (host, dev):
             st.add_vectors(ids2, dense2, sparse2, texts2, [""] * 137, metas2)
-        assert all(len(c) == N + 137 for c in dev._meta_columns.values())    # extended by the insert, O(new rows)
-        assert all(dev._row_filter.rows(c) == N for c in dev._row_filter_cols.values())   # ... uploaded by the next filter
+        assert all(len(c) == N + 137 for c in dev._metadata.columns.values())    # extended by the insert, O(new rows)
+        assert all(dev._metadata.row_filter.rows(c) == N for c in dev._metadata.row_filter_cols.values())   # ... uploaded by the next filter
         dq2, sq2, tq2 = dq + [dense2[3].tolist()], sq + [sparse2[3]], tq + ["row 5003"]
         _compare(host, dev, dq2, sq2, tq2, "after the insert", LATER)
         named = {"year", "source", "peer", "tag"}                              # the keys LATER's compound filters name
-        assert all(dev._row_filter.rows(c) == (N + 137 if k in named else N) for k, c in dev._row_filter_cols.items())
+        assert all(dev._metadata.row_filter.rows(c) == (N + 137 if k in named else N) for k, c in dev._metadata.row_filter_cols.items())
 
         top = [r.id for rs in dev.query_batch(dense_queries=dq2, search_type="dense", top_k=3, filter="year >= 2020") for r in rs]
         for st in (host, dev):
@@ -149,7 +149,7 @@ def test_device_filter_evaluation_equals_the_host_route(route, tmp_path, caplog)
             for flt in FILTERS:
                 a, b = fresh_host._mask(flt), loaded._mask(flt)
                 assert (a is None and b is None) or np.array_equal(a, b), flt
-            assert loaded._meta_columns and not fresh_host._meta_columns
+            assert loaded._metadata.columns and not fresh_host._metadata.columns
         finally:
             _close(fresh_host)
 
@@ -166,12 +166,12 @@ def test_device_filter_evaluation_equals_the_host_route(route, tmp_path, caplog)
                 dev._drop_subsets()                                          # the second round evaluates every mask again
         said = [r.getMessage() for r in caplog.records if "evaluated on the host" in r.getMessage()]
         assert len(said) == 2 and any("NaN" in m for m in said) and any("65 leaves" in m for m in said), said   # once per filter
-        assert not dev._meta_columns["score"].exact and dev._meta_columns["year"].exact
+        assert not dev._metadata.columns["score"].exact and dev._metadata.columns["year"].exact
     finally:
         for st in (host, dev, loaded):
             if st is not None:
                 _close(st)
-    assert dev._row_filter is None and not dev._row_filter_cols                # close() drops the RowFilter
+    assert dev._metadata.row_filter is None and not dev._metadata.row_filter_cols                # close() drops the RowFilter
 
 
 def test_filter_eval_must_be_host_or_device(tmp_path):
@@ -192,6 +192,6 @@ def test_filter_eval_must_be_host_or_device(tmp_path):
     for bad in ('metadata["x"] like "y%"', "year >", "year < true"):
         with pytest.raises(ValueError, match="GpuVectorStore: "):
             dev._mask(bad)
-    assert not dev._meta_columns
+    assert not dev._metadata.columns
     _close(dev)
     _close(st)

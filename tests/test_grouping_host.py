@@ -143,14 +143,14 @@ def test_the_filter_columns_of_a_device_evaluated_store_are_reused(monkeypatch):
     with GC.stand_ins():
         st = _make()
         GC.fill(st, rows)
-        column = st._meta_columns["document_id"] = MetaColumn("document_id")     # what filter_eval="device" would have built
+        column = st._metadata.columns["document_id"] = MetaColumn("document_id")     # what filter_eval="device" would have built
         column.extend(st._meta)
         st.query(dense_query=rows[0].dense.tolist(), top_k=3, search_type="dense", search_params={"group_by_field": "document_id"})
-        assert st._group_codes["document_id"].column is column
+        assert st._metadata.group_codes["document_id"].column is column
         GC.fill(st, GC.rows_of(10, seed=3, first=80))
         assert len(column) == 90                                     # extended by the insert, like every typed column
         st.query(dense_query=rows[0].dense.tolist(), top_k=3, search_type="dense", search_params={"group_by_field": "document_id"})
-        assert len(st._group_codes["document_id"]) == 90 and len(st._group_cols["document_id"]) == 90
+        assert len(st._metadata.group_codes["document_id"]) == 90 and len(st._metadata.group_cols["document_id"]) == 90
 
 
 def test_refusals():

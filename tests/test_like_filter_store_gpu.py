@@ -116,14 +116,14 @@ def test_like_and_not_in_filters_under_every_combination_of_options(caplog):
         assert len(said) == 2 and all("300 bytes" in m for m in said), said          # the 300-byte pattern, once per device-strings store
 
         dev = stores[("device", "device", "subset")]
-        title_col = dev._row_filter_cols["title"]
+        title_col = dev._metadata.row_filter_cols["title"]
         n_titles = len({title_of(md) for md in metas} - {None})
-        before = dev._row_filter.strings(title_col)
-        assert before[0] == n_titles == len(dev._meta_columns["title"].strings)
-        assert before[1] == sum(len(s.encode()) for s in dev._meta_columns["title"].strings)
+        before = dev._metadata.row_filter.strings(title_col)
+        assert before[0] == n_titles == len(dev._metadata.columns["title"].strings)
+        assert before[1] == sum(len(s.encode()) for s in dev._metadata.columns["title"].strings)
         plain = stores[("device", "host", "subset")]
-        assert plain._row_filter.strings(plain._row_filter_cols["title"]) == (0, 0)   # filter_strings="host" uploads no dictionary
-        assert stores[("host", "device", "subset")]._row_filter is None              # and without filter_eval="device" it has no effect
+        assert plain._metadata.row_filter.strings(plain._metadata.row_filter_cols["title"]) == (0, 0)   # filter_strings="host" uploads no dictionary
+        assert stores[("host", "device", "subset")]._metadata.row_filter is None              # and without filter_eval="device" it has no effect
 
         new_titles = ["BERT: a new title", "日本語 2025", "path/to/new.txt", "zz_new"]
         ids2, dense2, sparse2, texts2, metas2 = _rows(rng, 200, N, TITLES + new_titles)
@@ -131,12 +131,12 @@ def test_like_and_not_in_filters_under_every_combination_of_options(caplog):
             st.add_vectors(ids2, dense2, sparse2, texts2, texts2, metas2)
         ids, dense, metas = ids + ids2, np.concatenate([dense, dense2]), metas + metas2
         alive = np.ones(N + 200, dtype=bool)
-        assert dev._row_filter.strings(title_col) == before                          # nothing travels before a filter asks
+        assert dev._metadata.row_filter.strings(title_col) == before                          # nothing travels before a filter asks
         arrived = len({title_of(md) for md in metas} - {None}) - n_titles
         assert 0 < arrived <= len(new_titles)
         _check(stores, ids, dense, metas, alive, dq, "after the insert", FILTERS[:3] + FILTERS[5:8])
-        after = dev._row_filter.strings(title_col)
-        fresh = dev._meta_columns["title"].strings[n_titles:]
+        after = dev._metadata.row_filter.strings(title_col)
+        fresh = dev._metadata.columns["title"].strings[n_titles:]
         assert after == (n_titles + arrived, before[1] + sum(len(s.encode()) for s in fresh))   # only the new codes were uploaded
         assert set(fresh) <= set(new_titles)
 
@@ -145,7 +145,7 @@ def test_like_and_not_in_filters_under_every_combination_of_options(caplog):
             st.delete(gone)
         alive[[ids.index(g) for g in gone]] = False
         _check(stores, ids, dense, metas, alive, dq, "after the delete", FILTERS[:2] + FILTERS[5:6] + FILTERS[8:10])
-        assert dev._row_filter.strings(title_col) == after
+        assert dev._metadata.row_filter.strings(title_col) == after
     finally:
         for st in stores.values():
             _close(st)
@@ -174,9 +174,9 @@ def test_a_title_without_a_utf8_form_keeps_its_column_on_host_tables(caplog):
                 dev._drop_subsets()                                     # the second round evaluates the mask again
         said = [r.getMessage() for r in caplog.records if "keeps host tables" in r.getMessage()]
         assert len(said) == 1 and "UTF-8" in said[0] and "title" in said[0], said    # once per filter string, with the reason
-        assert not dev._meta_columns["title"].encodable and dev._meta_columns["lang"].encodable
-        cols = dev._row_filter_cols
-        assert dev._row_filter.strings(cols["title"]) == (0, 0) and dev._row_filter.strings(cols["lang"])[0] == 3   # the rest ran on the device
+        assert not dev._metadata.columns["title"].encodable and dev._metadata.columns["lang"].encodable
+        cols = dev._metadata.row_filter_cols
+        assert dev._metadata.row_filter.strings(cols["title"]) == (0, 0) and dev._metadata.row_filter.strings(cols["lang"])[0] == 3   # the rest ran on the device
     finally:
         for st in stores.values():
             _close(st)

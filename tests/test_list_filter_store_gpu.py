@@ -87,15 +87,15 @@ def test_every_route_gives_the_host_routes_masks_and_hits(reference, config):
         for flt in QUERIED:
             assert _searches(st, flt) == hits[flt], (config, flt)
         if config["filter_eval"] == "device":
-            rf, cols = st._row_filter, st._row_filter_cols
+            rf, cols = st._metadata.row_filter, st._metadata.row_filter_cols
             assert {"authors", "tags", "years", "flags"} <= set(cols)
             for key in ("authors", "tags", "years", "flags"):
-                assert rf.list_rows(cols[key]) == (N, int(st._meta_columns[key].elem_off[-1]))
+                assert rf.list_rows(cols[key]) == (N, int(st._metadata.columns[key].elem_off[-1]))
             assert rf.rows(cols["years"]) == 0 and rf.rows(cols["authors"]) == N     # only `authors == ..` reads scalar rows of a list key
             if config["filter_strings"] == "device":
-                assert rf.strings(cols["authors"])[0] == len(st._meta_columns["authors"].strings)
+                assert rf.strings(cols["authors"])[0] == len(st._metadata.columns["authors"].strings)
         else:
-            assert st._row_filter is None and not st._meta_columns
+            assert st._metadata.row_filter is None and not st._metadata.columns
     finally:
         _close(st)
 
@@ -110,17 +110,17 @@ def test_insert_delete_compact_and_save_load(strings, tmp_path):
     try:
         for flt in filters:
             assert np.array_equal(_mask_of(dev, flt, N), expected(flt, ROWS[:N])), flt
-        rf, cols = dev._row_filter, dev._row_filter_cols
-        assert rf.list_rows(cols["authors"]) == (N, int(dev._meta_columns["authors"].elem_off[-1]))
+        rf, cols = dev._metadata.row_filter, dev._metadata.row_filter_cols
+        assert rf.list_rows(cols["authors"]) == (N, int(dev._metadata.columns["authors"].elem_off[-1]))
         appended = []
         plain = rf.append_lists
         rf.append_lists = lambda col, off, kinds, payload: (appended.append((col, len(off) - 1)), plain(col, off, kinds, payload))[1]
         _add(dev, N, N + MORE)                                                      # the host column grows with the insert ...
-        assert len(dev._meta_columns["authors"]) == N + MORE and rf.list_rows(cols["authors"])[0] == N
+        assert len(dev._metadata.columns["authors"]) == N + MORE and rf.list_rows(cols["authors"])[0] == N
         for flt in filters:                                                         # ... the device's list part with the next list filter
             assert np.array_equal(_mask_of(dev, flt, N + MORE), expected(flt, ROWS)), flt
         for key in ("authors", "tags", "years"):
-            assert rf.list_rows(cols[key]) == (N + MORE, int(dev._meta_columns[key].elem_off[-1]))
+            assert rf.list_rows(cols[key]) == (N + MORE, int(dev._metadata.columns[key].elem_off[-1]))
         assert sorted(appended) == sorted((cols[key], MORE) for key in ("authors", "tags", "years"))   # extended, not rebuilt
         del rf.append_lists
 
@@ -135,7 +135,7 @@ def test_insert_delete_compact_and_save_load(strings, tmp_path):
         assert rf.list_rows(cols["authors"]) == (0, 0) and rf.rows(cols["source"]) == len(kept)      # dropped; the scalar rows compacted
         for flt in filters:
             assert np.array_equal(_mask_of(dev, flt, len(kept)), expected(flt, kept)), flt
-        assert rf.list_rows(cols["authors"]) == (len(kept), int(dev._meta_columns["authors"].elem_off[-1]))
+        assert rf.list_rows(cols["authors"]) == (len(kept), int(dev._metadata.columns["authors"].elem_off[-1]))
         top = dev.query(dense_query=DENSE[7].tolist(), search_type="dense", top_k=5, filter=filters[0])
         want = expected(filters[0], ROWS) & alive
         assert len(top) == 5 and all(want[int(r.id[2:])] for r in top)
@@ -188,10 +188,10 @@ def test_host_fallbacks_are_logged_once_and_stay_correct(caplog):
                 dev._drop_subsets()                                                 # the second round evaluates every mask again
         said = [r.getMessage() for r in caplog.records if "evaluated on the host" in r.getMessage()]
         assert len(said) == 2 and any("a list of metadata['tags'] holds a NaN" in m for m in said) and any("65 leaves" in m for m in said), said
-        column = dev._meta_columns["tags"]
+        column = dev._metadata.columns["tags"]
         assert column.exact and not column.list_exact                               # the scalar filter on `tags` stayed on the device
-        assert dev._row_filter.rows(dev._row_filter_cols["tags"]) == 400 and dev._row_filter.list_rows(dev._row_filter_cols["tags"]) == (0, 0)
-        assert dev._row_filter.list_rows(dev._row_filter_cols["years"])[0] == 400
+        assert dev._metadata.row_filter.rows(dev._metadata.row_filter_cols["tags"]) == 400 and dev._metadata.row_filter.list_rows(dev._metadata.row_filter_cols["tags"]) == (0, 0)
+        assert dev._metadata.row_filter.list_rows(dev._metadata.row_filter_cols["years"])[0] == 400
     finally:
         _close(dev)
 

@@ -81,8 +81,8 @@ def main():
             first, again = {}, {}
             for route, st in stores.items():
                 if route == "device":                        # every filter starts from a store without columns
-                    st._meta_columns.clear()
-                    st._row_filter, st._row_filter_cols = None, {}
+                    st._metadata.columns.clear()
+                    st._metadata.row_filter, st._metadata.row_filter_cols = None, {}
                 st._drop_subsets()
                 first[route] = clock(lambda: st._mask(flt))
                 again[route] = clock(lambda: st._mask(twin))

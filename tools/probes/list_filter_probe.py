@@ -72,7 +72,7 @@ def main():
             del metas, picks
         print(f"built the store of {n} rows in {time.perf_counter() - t0:.1f} s", flush=True)
         first = clock(lambda: st._mask('json_contains(authors, "warm-up")'))[0]      # builds the column, uploads lists and dictionary
-        elements = int(st._meta_columns["authors"].elem_off[-1])
+        elements = int(st._metadata.columns["authors"].elem_off[-1])
         lines.append(f"{n:>9} {elements:>10} {'first mask':>14} {first:>10.2f}   once: column build in Python + uploads")
         print(lines[-1], flush=True)
         times = {mode: [] for mode in MODES}

@@ -25,13 +25,13 @@ import numpy as np
 
 from . import _lib
 # The layers under the store, re-exported here under the names callers and tests have always used.  The store resolves
-# DenseShard / SparseShard / IvfOverlay / TextIndex through THIS module's globals at call time (tests replace them here).
+# DenseShard / SparseShard / IvfOverlay / TextIndex through THIS module's globals at call time (tests replace them here);
+# RowFilter / GroupColumn likewise, through the two factories it hands its `StoreMetadata`.
 from .shards import (_FP, _IP, _LP, DenseShard, GroupColumn, IvfOverlay, RowFilter, SparseShard, Sq8Shard, TextIndex, _allow_words, _bitmap,  # noqa: F401
                      _utf8_batch, dicts_to_csr, tokenize_keys)
-from .store_columns import MetaColumn
-from .store_groups import GroupCodes
 from .store_filter import _FILTER_TOKEN, _typed, compile_filter, parse_filter  # noqa: F401
 from .store_io import _NO_METADATA, _get_strings, _put_strings, _replace_into, _write_text, read_saved  # noqa: F401
+from .store_metadata import StoreMetadata
 
 logger = logging.getLogger(__name__)
 
@@ -375,6 +375,12 @@ def check_dense_dtype(dense_dtype: str, index_type: str, sharded: bool) -> None:
         raise ValueError("dense_dtype='int8' searches FLAT: index_type='IVF_FLAT' needs 'f32' or 'bf16' rows")
 
 
+def check_choice(name: str, value, a: str, b: str) -> None:
+    """The constructor's refusal for an option with two choices."""
+    if value not in (a, b):
+        raise ValueError(f"{name} must be {a!r} or {b!r} (got {value!r})")
+
+
 _JSON_PLAIN = (str, int, float, bool, type(None))
 
 
@@ -445,6 +451,13 @@ class _Column:
             self._buf = grown
         self._buf[self._n: self._n + m] = rows
         self._n += m
+
+
+def _take(col: list, at: np.ndarray) -> list:
+    """`[col[i] for i in at]` for 10^7 rows: one object-array gather instead of a Python loop."""
+    box = np.empty(len(col), dtype=object)
+    box[:] = col
+    return box[at].tolist()
 
 
 def csr_take_rows(indptr: np.ndarray, indices: np.ndarray, values: np.ndarray, rows: np.ndarray):
@@ -662,16 +675,11 @@ class GpuVectorStore(VectorStore):
         check_dense_dtype(dense_dtype, index_type, distributed or comm is not None)
         self._lib = _lib.load()
         _lib.require_gpu()
-        if payload not in ("sharded", "replicated"):
-            raise ValueError(f"payload must be 'sharded' or 'replicated' (got {payload!r})")
-        if filter_route not in ("subset", "bitmap"):
-            raise ValueError(f"filter_route must be 'subset' or 'bitmap' (got {filter_route!r})")
-        if rrf_route not in ("host", "device"):
-            raise ValueError(f"rrf_route must be 'host' or 'device' (got {rrf_route!r})")
-        if filter_eval not in ("host", "device"):
-            raise ValueError(f"filter_eval must be 'host' or 'device' (got {filter_eval!r})")
-        if filter_strings not in ("host", "device"):
-            raise ValueError(f"filter_strings must be 'host' or 'device' (got {filter_strings!r})")
+        check_choice("payload", payload, "sharded", "replicated")
+        check_choice("filter_route", filter_route, "subset", "bitmap")
+        check_choice("rrf_route", rrf_route, "host", "device")
+        check_choice("filter_eval", filter_eval, "host", "device")
+        check_choice("filter_strings", filter_strings, "host", "device")
         if not enable_dense and not enable_sparse and not enable_full_text:      # milvus_base.py:54-56
             raise ValueError("At least one of enable_dense, enable_sparse, or enable_full_text must be True")
         if enable_full_text and comm is None and distributed:
@@ -750,17 +758,11 @@ class GpuVectorStore(VectorStore):
         # under a running search.  (Sharded stores are SPMD: one caller thread per rank.)
         self._mu = threading.RLock()
         self._masks: Dict[str, Optional[np.ndarray]] = {}
-        self._value_indexes: Dict[str, Dict[Any, List[np.ndarray]]] = {}   # key -> typed value -> row segments
-        # filter_eval="device": typed columns of the keys filters have named (host side, over the rows of `_meta`), the handle
-        # that holds their device copies with each key's column number there, and the filters already reported as host-routed
-        self._meta_columns: Dict[str, MetaColumn] = {}
-        self._row_filter: Optional[RowFilter] = None
-        self._row_filter_cols: Dict[str, int] = {}
-        self._filter_fallbacks: set = set()
-        # grouping search: per key the host group codes (over the key's column in `_meta_columns`) and their device copy;
-        # both are dropped by `compact()` and rebuilt by the next grouped query on the key
-        self._group_codes: Dict[str, GroupCodes] = {}
-        self._group_cols: Dict[str, GroupColumn] = {}
+        # what is derived from the rows of `_meta`: value indexes, typed columns, group codes, and the device copies of the
+        # last two, made through the names this module holds when one is needed (header comment).  The factories close over
+        # `device`, not `self`: the store stays free of reference cycles and releases its HBM when its last user lets go
+        # (so `self.device` is assigned once, above, and never rebound: the handles would not follow it)
+        self._metadata = StoreMetadata(lambda: RowFilter(device), lambda: GroupColumn(device))
         self._all_ids_truthy = True
         # replicated like `_all_ids_truthy`: no two rows share an id (the ids seen so far, until two of them do).  Rows that
         # share an id are ONE candidate of a hybrid fusion (hybrid_search.py:73-129 keys by id); deletes leave it as it is.
@@ -782,8 +784,7 @@ class GpuVectorStore(VectorStore):
             self._sparse_parts = []
             self._text = None
             self._owned_dev = None
-            self._row_filter, self._row_filter_cols = None, {}    # the host columns stay: they are uploaded again on demand
-            self._group_cols = {}                                 # likewise the group codes
+            self._metadata.drop_device()
             self._dense_flushed = self._sparse_flushed = self._text_flushed = self._text_main = 0
             self._dirty = True
             if self._comm is not None and self._owns_comm:
@@ -858,19 +859,7 @@ class GpuVectorStore(VectorStore):
                 self._sp_val.extend(new_csr[2])
             self._dirty = True
             self._drop_subsets()
-            # value indexes that exist are extended by the new rows' values (a segment per insert, merged on the next read):
-            # rebuilding them is a Python pass over EVERY stored row, per key, after every insert
-            meta_base = len(self._meta) - len(new_meta)
-            for key, index in self._value_indexes.items():
-                fresh: Dict[Any, List[int]] = {}
-                for j, md in enumerate(new_meta):
-                    t = _typed(md.get(key))
-                    if t is not None:
-                        fresh.setdefault(t, []).append(meta_base + j)
-                for t, rows in fresh.items():
-                    index.setdefault(t, []).append(np.asarray(rows, dtype=np.int64))
-            for column in self._meta_columns.values():      # typed columns likewise: O(new rows) per insert
-                column.extend(new_meta)
+            self._metadata.extend(new_meta, len(self._meta) - len(new_meta))
 
     def _note_unique(self, ids) -> None:
         """Keeps `_ids_unique` in step with the ids of new rows (under the lock, or before the store is shared)."""
@@ -932,20 +921,12 @@ class GpuVectorStore(VectorStore):
                 if overlay is not None:
                     overlay.remap(keep)
                 self._dense_flushed = live
-            if self._row_filter is not None:
-                self._row_filter.compact(keep)
-            self._group_codes, self._group_cols = {}, {}    # rebuilt from the compacted columns by the next grouped query
+            self._metadata.compact(keep)
             self._sparse_parts, self._sparse_flushed = [], 0
             self._text, self._text_flushed, self._text_main = None, 0, 0
             self._text_live_stale, self._text_totals = True, None
             # host columns
-
-            def take(col):
-                box = np.empty(len(col), dtype=object)
-                box[:] = col
-                return box[at].tolist()
-
-            self._ids, self._texts, self._enh, self._meta = take(self._ids), take(self._texts), take(self._enh), take(self._meta)
+            self._ids, self._texts, self._enh, self._meta = (_take(col, at) for col in (self._ids, self._texts, self._enh, self._meta))
             self._alive = _Column(bool, first=np.ones(live, dtype=bool))
             self._owned = _Column(np.int64, first=np.arange(live, dtype=np.int64))
             self._main_rows = self._owned.data
@@ -956,10 +937,7 @@ class GpuVectorStore(VectorStore):
             if self.enable_sparse:
                 ptr, idx, val = csr_take_rows(self._sp_ptr.data, self._sp_idx.data, self._sp_val.data, at)
                 self._sp_ptr, self._sp_idx, self._sp_val = _Column(np.int64, first=ptr), _Column(np.int32, first=idx), _Column(np.float32, first=val)
-            for column in self._meta_columns.values():
-                column.compact(keep)
             # what a load would derive from the surviving rows
-            self._value_indexes = {}
             self._id_rows = None
             self._all_ids_truthy = all(bool(x) for x in self._ids)
             self._ids_unique, self._id_seen = True, set()
@@ -1112,13 +1090,13 @@ class GpuVectorStore(VectorStore):
                 lookup = getattr(pred, "lookup", None)
                 held = np.zeros(len(self._meta), dtype=bool)     # over the rows whose metadata this rank holds
                 if lookup is not None:      # one `==` / `in` comparison (the reference's document_id filter, index.py:735-739)
-                    index = self._value_index(lookup[0])
+                    index = self._metadata.value_index(lookup[0], self._meta)
                     for v in lookup[1]:
                         rows = index.get(v)
                         if rows is not None:
                             held[rows] = True
                 else:
-                    held = self._held_device(filter) if self.filter_eval == "device" else None
+                    held = self._metadata.held(filter, self._meta, self.filter_strings) if self.filter_eval == "device" else None
                     if held is None:
                         held = np.asarray([bool(pred(md)) for md in self._meta], dtype=bool)
                 if self._payload_sharded:
@@ -1132,82 +1110,6 @@ class GpuVectorStore(VectorStore):
                 self._masks.clear()
             self._masks[key] = None if alive.all() else alive
         return self._masks[key]
-
-    def _held_device(self, filter: str) -> Optional[np.ndarray]:
-        """`filter` over the rows of `_meta` on the GPU (`filter_eval="device"`, under the lock): the filter as a postfix
-        program, the columns it names brought up to date in HBM (only rows not uploaded yet travel), its string comparisons
-        resolved against the columns' dictionaries, one kernel.  None = this filter is the host's: the program is beyond the
-        device's limits or a named column is inexact (logged once per filter string)."""
-        program = compile_filter(filter)
-        why = program.over_limit()
-        columns = []
-        for key in program.keys if why is None else ():
-            column = self._meta_columns.get(key)
-            if column is None:
-                column = self._meta_columns[key] = MetaColumn(key)
-                column.extend(self._meta)
-            at = program.keys.index(key)
-            pushed = {op for op, i in program.ops if op in ("leaf", "list_any") and program.leaves[i].column == at}
-            if "leaf" in pushed and not column.exact:
-                why = f"metadata[{key!r}] holds a NaN or a number beyond float range"
-                break
-            if "list_any" in pushed and not column.list_exact:
-                why = f"a list of metadata[{key!r}] holds a NaN or a number beyond float range"
-                break
-            columns.append((column, pushed))
-        if why is not None:
-            if filter not in self._filter_fallbacks:
-                if len(self._filter_fallbacks) >= 1024:
-                    self._filter_fallbacks.clear()
-                self._filter_fallbacks.add(filter)
-                logger.info("GpuVectorStore: filter %r is evaluated on the host: %s", filter, why)
-            return None
-        if self._row_filter is None:
-            self._row_filter = RowFilter(self.device)
-        device_cols = []
-        for column, pushed in columns:
-            col = self._row_filter_cols.get(column.key)
-            if col is None:
-                col = self._row_filter_cols[column.key] = self._row_filter.add_column()
-            have = self._row_filter.rows(col)
-            if "leaf" in pushed and have < len(column):
-                self._row_filter.append(col, column.kinds[have:], column.payload[have:])
-            if "list_any" in pushed:        # the list part travels with the first list filter on the key, then per insert
-                have, elems = self._row_filter.list_rows(col)
-                if have < len(column):
-                    self._row_filter.append_lists(col, column.elem_off[have:] - elems, column.elem_kinds[elems:],
-                                                  column.elem_payload[elems:])
-            device_cols.append((col, column))
-        if self.filter_strings == "host":
-            return self._row_filter.eval_program(program, device_cols, len(self._meta))
-        kept: List[str] = []
-        held = self._row_filter.eval_program(program, device_cols, len(self._meta), strings="device", kept=kept)
-        if kept and filter not in self._filter_fallbacks:
-            if len(self._filter_fallbacks) >= 1024:
-                self._filter_fallbacks.clear()
-            self._filter_fallbacks.add(filter)
-            logger.info("GpuVectorStore: filter %r keeps host tables for: %s", filter, "; ".join(kept))
-        return held
-
-    def _value_index(self, key: str) -> Dict[Any, np.ndarray]:
-        """typed metadata[key] -> rows (positions in the metadata list), built once per key until the next insert: a
-        per-document filter then costs its matches, not a Python predicate call per stored row.  Rows without a
-        comparable value are in no bucket."""
-        with self._mu:
-            index = self._value_indexes.get(key)
-            if index is None:
-                buckets: Dict[Any, List[int]] = {}
-                for i, md in enumerate(self._meta):
-                    t = _typed(md.get(key))
-                    if t is not None:
-                        buckets.setdefault(t, []).append(i)
-                index = self._value_indexes[key] = {v: [np.asarray(rows, dtype=np.int64)] for v, rows in buckets.items()}
-            out = {}
-            for v, segs in index.items():       # buckets are lists of row segments (one per insert since the build): merge on read
-                if len(segs) > 1:
-                    segs[:] = [np.concatenate(segs)]
-                out[v] = segs[0]
-            return out
 
     def _hit(self, row: int, score: float) -> dict:
         """A search hit in the shape `merge_hybrid_results` works on; the entity (text, metadata copy) is attached
@@ -1696,28 +1598,6 @@ class GpuVectorStore(VectorStore):
         if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= top_k <= GROUP_TOP_K_MAX:
             raise ValueError(f"a grouping search returns 1 <= top_k <= {GROUP_TOP_K_MAX} groups (got {top_k!r})")
 
-    def _group_column(self, key: str, n: int) -> GroupColumn:
-        """The device group codes of `metadata[key]` for rows `[0, n)` (under the lock, after a flush): the host codes are built
-        over the key's typed column -- the one `filter_eval="device"` keeps, or a new one, extended by every insert either way --
-        by one pass at the first grouped query on the key and by the new rows afterwards; only codes not uploaded yet travel."""
-        codes = self._group_codes.get(key)
-        if codes is None:
-            column = self._meta_columns.get(key)
-            if column is None:
-                column = self._meta_columns[key] = MetaColumn(key)
-                column.extend(self._meta)
-            codes = self._group_codes[key] = GroupCodes(column)
-        host = codes.sync()
-        if not codes.column.exact:
-            raise ValueError(f"group_by_field: metadata[{key!r}] holds a NaN or a number beyond float range; its rows cannot be grouped")
-        device = self._group_cols.get(key)
-        if device is None:
-            device = self._group_cols[key] = GroupColumn(self.device)
-        have = len(device)
-        if have < n:
-            device.append(host[have:n])
-        return device
-
     def _grouped_batch(self, queries: Sequence[Any], top_k: int, filter: Optional[str], grouping: Grouping,
                        _retry: int = 0) -> List[List[SearchResult]]:
         """Grouping search for a batch of dense queries: per query the best `top_k` groups of `metadata[grouping.key]` among the
@@ -1727,7 +1607,7 @@ class GpuVectorStore(VectorStore):
         with self._mu:
             self._flush()
             shard, n = self._dense, len(self._ids)
-            column = self._group_column(grouping.key, n) if shard is not None and n else None
+            column = self._metadata.group_column(grouping.key, self._meta, n) if shard is not None and n else None
         Q, g = len(queries), grouping.group_size
         mask = self._fit_mask(mask, n)
         if column is None or Q == 0 or (mask is not None and not mask.any()):
@@ -1828,15 +1708,9 @@ class GpuVectorStore(VectorStore):
             # texts / metadata lists are indexed by local row, or by global row when a sharded store replicates them
             slots = local if (self._payload_sharded or self._world == 1) else owned[local]
             whole = len(slots) == len(self._texts) and (len(slots) == 0 or (slots[0] == 0 and slots[-1] == len(slots) - 1))
-
-            def take(col, at):        # col[at] for 10^7 rows: one object-array gather instead of a Python loop
-                box = np.empty(len(col), dtype=object)
-                box[:] = col
-                return box[at].tolist()
-
-            pick = (lambda col: col) if whole else (lambda col: take(col, slots))
+            pick = (lambda col: col) if whole else (lambda col: _take(col, slots))
             texts, enh, metas = pick(self._texts), pick(self._enh), pick(self._meta)
-            ids = self._ids if alive.all() else take(self._ids, np.nonzero(alive)[0])
+            ids = self._ids if alive.all() else _take(self._ids, np.nonzero(alive)[0])
             if not any(metas):
                 metas = {"empty_rows": len(metas)}                             # nothing to store per row
             head = {"format": self.FORMAT, "world": self._world, "dense_dim": self.dense_dim, "sparse_vocab": self.sparse_vocab,
