@@ -511,6 +511,23 @@ int vrag_sq8_index_search_filtered(vrag_sq8_index* ix, const float* queries /*[n
                                    const uint32_t* allow /*host, bit r%32 of word r/32*/, int64_t n_allow,
                                    float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * IVF_SQ8: the IVF overlay over an SQ8 index (csrc/ivf.hip, csrc/ivf_sq8.hip; Milvus' index_type="IVF_SQ8").  create_sq8 makes
+ * a vrag_ivf_index whose base is a vrag_sq8_index; every other vrag_ivf_index_* call then works as it does over a dense base --
+ * the same argument checks, locking, query slices and "the base must outlive the overlay" rule -- with two differences:
+ *   the vector a row stands for, for training and assignment ONLY, is  x^[c] = fl((float)code[c] * scale), one fp32 product per
+ *                  element.  The assignment rule is unchanged (argmax_c (x^ . c - 1/2 |c|^2), the lowest list on ties, plain fp32
+ *                  sums in unspecified order); a trained centroid is the fp32 mean of its members' x^ summed in ascending row
+ *                  order, so two trainings of the same rows give the same bytes.  Queries are probed as fp32 against the fp32
+ *                  centroids, as over a dense base.
+ *   search         1 <= k <= 64, nprobe >= 1 (clamped to nlist).  The queries are quantised once by the SQ8 rule; the rows of
+ *                  the probed lists are scored by the SQ8 section's score, bit for bit (v_mfma_i32_16x16x64_i8 over 16 rows x 16
+ *                  queries: the int32 dot is exact in any order).  Order (score desc, id asc), missing hits -1 / -inf.  With
+ *                  nprobe >= nlist the result IS vrag_sq8_index_search's for the same queries, on either route of that call.
+ *                  scanned_rows as above.
+ *   remap          after vrag_sq8_index_compact of the base with the same bitmap: as after vrag_dense_index_compact. */
+int vrag_ivf_index_create_sq8(vrag_sq8_index* base, int32_t nlist, vrag_ivf_index** out);
+
 /* Sparse (SPLADE) rows in CSR, term ids < vocab <= 65536; only documents sharing a term with the
  * query (score > 0) are hits, like an inverted index.  ids are CSR row numbers. */
 typedef struct vrag_sparse_index vrag_sparse_index;

@@ -155,6 +155,7 @@ SIGNATURES = {
     "vrag_group_column_append": (C.c_int, [_H, _IP, C.c_int64]),
     "vrag_group_column_size": (C.c_int64, [_H]),
     "vrag_ivf_index_create": (C.c_int, [_H, C.c_int32, C.POINTER(_H)]),
+    "vrag_ivf_index_create_sq8": (C.c_int, [_H, C.c_int32, C.POINTER(_H)]),
     "vrag_ivf_index_destroy": (None, [_H]),
     "vrag_ivf_index_set_centroids": (C.c_int, [_H, _FP]),
     "vrag_ivf_index_train": (C.c_int, [_H, C.c_int32, C.c_int64]),

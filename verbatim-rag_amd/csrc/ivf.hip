@@ -30,6 +30,11 @@
 // Scratch bound: a slice holds at most IVF_SLICE_KEYS = 2^22 candidate keys (32 MB; nprobe * k * split <= 2^22, so a slice always
 // holds at least one query), at most IVF_SLICE_SCORES = 2^24 probe scores (64 MB) and at most 4 096 queries; the group tables take
 // 72 bytes per (query, list) pair (<= 2^22 / k pairs).
+//
+// Over an SQ8 base (vrag_ivf_index_create_sq8; csrc/sq8_kernels.h) the overlay is the same handle: training and assignment read the
+// int8 rows as  x^[c] = fl((float)code[c] * scale)  (ROWS_SQ8 forms of ivf_tile_kernel and ivf_mean_kernel), the handle's column
+// count is the rows' stride (centroids and queries are padded with zero columns on their way in), the queries are quantised once
+// per search by sq8_query_kernel and the scan stage is ivf_sq8_scan_kernel (csrc/ivf_sq8.hip); probe, invert and merge are unchanged.
 #include "../../include/vrag_amd.h"
 
 #include <algorithm>
@@ -40,19 +45,25 @@
 
 #include "common.h"
 #include "host_util.h"
+#include "ivf_kernels.h"
+#include "sq8_kernels.h"
 #include "topk_kernels.h"
 
 namespace vrag {
 namespace {
 
 constexpr int IVF_NLIST_MAX = 16384;
-constexpr int IVF_QG = 16;                  // queries of one scan work item
-constexpr int IVF_ROWS = 16, IVF_CH = 256;  // rows per scan step, columns per LDS stage (filtered_score_kernel's shape)
+constexpr int IVF_CH = 256;                 // columns per LDS stage of the scan (filtered_score_kernel's shape; IVF_ROWS rows a step)
 constexpr long long IVF_SLICE_KEYS = 1ll << 22, IVF_SLICE_SCORES = 1ll << 24;
 constexpr int IVF_SLICE_QUERIES = 4096;
-constexpr int IVF_RANK_BITS = 14;           // a pair is packed (query in slice << 14) | probe rank
 constexpr int IVF_SCAN_WGS = 2048;
 constexpr int IVF_SPLIT_MAX = 64, IVF_SPLIT_WGS = 4096, IVF_SPLIT_ROWS_MAX = 2048, IVF_SPLIT_ROWS_MIN = 128;
+
+// What the rows of the base are (the handle's `dtype`): bf16 or fp32 rows of a dense index, or the int8 codes of an SQ8 index, which
+// stand for  x^[c] = fl((float)code[c] * scale)  wherever a row is trained on or assigned (never in the scan: csrc/ivf_sq8.hip).
+enum RowKind : int { ROWS_BF16 = 0, ROWS_F32 = 1, ROWS_SQ8 = 2 };
+
+__device__ __forceinline__ float sq8_code(const i32x4& v, int j) { return (float)(int)(signed char)((unsigned)v[j >> 2] >> (8 * (j & 3))); }
 
 // Row number of sample item i: row0 + i * num / den (num >= den >= 1: strictly increasing; 1 / 1 = consecutive rows).
 struct RowMap {
@@ -74,11 +85,13 @@ __global__ __launch_bounds__(64) void ivf_half_norm_kernel(const float* __restri
 // ------------------------------------------------------------------------------------ assignment / probe scores
 // S[i][c] = x_i . cent_c - half[c] for a tile of TM items x TN centroids per step: 256 threads as 16 x 16, a 4 x 4 register tile
 // each, TK columns of both operands staged transposed in LDS (a step reads two 16-byte vectors per 16 fmaf).
+// ROWS_SQ8: `dim` is the rows' stride (a multiple of 16; pad codes are zero, the centroids' pad columns too), x_scale their scales.
 // ARGMAX: grid = item tiles; the workgroup walks every centroid tile and keeps, per item, the best (score desc, list asc) ->
 // assign[i].  Otherwise: grid = (item tiles, centroid tiles) and the scores leave as scores[i][nlist].
 constexpr int TM = 64, TN = 64, TK = 32;
-template <bool F32, bool ARGMAX>
-__global__ __launch_bounds__(256) void ivf_tile_kernel(const void* __restrict__ x_v, RowMap map, long long n_items, int dim,
+template <int RK, bool ARGMAX>
+__global__ __launch_bounds__(256) void ivf_tile_kernel(const void* __restrict__ x_v, const float* __restrict__ x_scale, RowMap map,
+                                                        long long n_items, int dim,
                                                         const float* __restrict__ cent, const float* __restrict__ half, int nlist,
                                                         unsigned* __restrict__ assign, float* __restrict__ scores) {
   __shared__ __attribute__((aligned(16))) float sx[TK][TM + 4];
@@ -92,7 +105,7 @@ __global__ __launch_bounds__(256) void ivf_tile_kernel(const void* __restrict__ 
 #pragma unroll
   for (int a = 0; a < 4; ++a) best[a] = -INFINITY, bidx[a] = 0u;
   const int ct_lo = ARGMAX ? 0 : blockIdx.y, ct_hi = ARGMAX ? (nlist + TN - 1) / TN : blockIdx.y + 1;
-  constexpr int PW = F32 ? 4 : 8;   // columns of a 16-byte piece of an item's row
+  constexpr int PW = RK == ROWS_F32 ? 4 : RK == ROWS_BF16 ? 8 : 16;   // columns of a 16-byte piece of an item's row
   for (int ct = ct_lo; ct < ct_hi; ++ct) {
     const int c0 = ct * TN;
     float acc[4][4];
@@ -106,10 +119,15 @@ __global__ __launch_bounds__(256) void ivf_tile_kernel(const void* __restrict__ 
       for (int p = tid; p < TM * (w / PW); p += 256) {
         const int m = p / (w / PW), kk = PW * (p % (w / PW));
         const long long r = map.at(min(i0 + m, n_items - 1));   // items behind the end re-read the last one; their results are dropped
-        if constexpr (F32) {
+        if constexpr (RK == ROWS_F32) {
           const f32x4 v = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(x_v) + (size_t)r * dim + k0 + kk);
 #pragma unroll
           for (int j = 0; j < 4; ++j) sx[kk + j][m] = v[j];
+        } else if constexpr (RK == ROWS_SQ8) {
+          const i32x4 v = *reinterpret_cast<const i32x4*>(reinterpret_cast<const signed char*>(x_v) + (size_t)r * dim + k0 + kk);
+          const float s = x_scale[r];
+#pragma unroll
+          for (int j = 0; j < 16; ++j) sx[kk + j][m] = __fmul_rn(sq8_code(v, j), s);
         } else {
           const bf16x8 v = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const bf16_t*>(x_v) + (size_t)r * dim + k0 + kk);
 #pragma unroll
@@ -171,9 +189,10 @@ __global__ __launch_bounds__(256) void ivf_tile_kernel(const void* __restrict__ 
 // Lloyd update of one list per workgroup: thread t owns columns t, t + 256, ...; the members (base row numbers, ascending) are
 // summed one after the other in fp32 -- no atomics, the same bits on every run -- and divided by their count.  An empty list
 // keeps its centroid.
-template <bool F32>
-__global__ __launch_bounds__(256) void ivf_mean_kernel(const void* __restrict__ rows_v, int dim, const unsigned* __restrict__ off,
-                                                        const unsigned* __restrict__ members, float* __restrict__ cent) {
+template <int RK>
+__global__ __launch_bounds__(256) void ivf_mean_kernel(const void* __restrict__ rows_v, const float* __restrict__ row_scale, int dim,
+                                                        const unsigned* __restrict__ off, const unsigned* __restrict__ members,
+                                                        float* __restrict__ cent) {
   const unsigned lo = off[blockIdx.x], hi = off[blockIdx.x + 1];
   if (lo == hi) return;
   const float n = (float)(hi - lo);
@@ -182,7 +201,8 @@ __global__ __launch_bounds__(256) void ivf_mean_kernel(const void* __restrict__ 
 #pragma unroll 4
     for (unsigned m = lo; m < hi; ++m) {
       const size_t at = (size_t)members[m] * dim + c;
-      s += F32 ? reinterpret_cast<const float*>(rows_v)[at] : (float)reinterpret_cast<const bf16_t*>(rows_v)[at];
+      if constexpr (RK == ROWS_SQ8) s += __fmul_rn((float)reinterpret_cast<const signed char*>(rows_v)[at], row_scale[members[m]]);   // x^: no fused step
+      else s += RK == ROWS_F32 ? reinterpret_cast<const float*>(rows_v)[at] : (float)reinterpret_cast<const bf16_t*>(rows_v)[at];
     }
     cent[(size_t)blockIdx.x * dim + c] = s / n;
   }
@@ -364,9 +384,13 @@ __global__ __launch_bounds__(256) void ivf_scan_kernel(const void* __restrict__ 
 using namespace vrag;
 
 struct vrag_ivf_index {
-  vrag_dense_index* base = nullptr;   // not owned: it must outlive this handle
-  const void* rows = nullptr;         // the base's rows (a fixed address), their layout
-  int dim = 0, dtype = 0, device = 0;
+  vrag_dense_index* base = nullptr;   // the base, not owned, which must outlive this handle: a dense index ...
+  vrag_sq8_index* sq8_base = nullptr; // ... or an SQ8 index (dtype == ROWS_SQ8); exactly one of the two is set
+  const void* rows = nullptr;         // the base's rows or codes (a fixed address), their layout
+  const float* row_scales = nullptr;  // ROWS_SQ8: the rows' scales
+  int dim = 0;                        // columns the kernels walk = pitch of rows, centroids and queries: the SQ8 stride over an SQ8 base
+  int user_dim = 0;                   // columns of the caller's centroids and queries (== dim over a dense base)
+  int dtype = 0, device = 0;          // dtype: RowKind
   int nlist = 0;
   bool have_centroids = false, synced = false;
   long long n_assigned = 0, largest = 0;
@@ -382,9 +406,32 @@ struct vrag_ivf_index {
   DevArray<unsigned> d_probe, d_cnt, d_place, d_goff, d_item_list, d_item_n, d_item_pair;
   DevArray<unsigned long long> d_scanned;    // [nq]
   DevArray<u64> d_cand, d_out;
+  DevArray<signed char> d_qc;                // ROWS_SQ8: the queries' codes [nq][dim] and scales [nq]
+  DevArray<float> d_qs;
 };
 
 namespace {
+
+// What both kinds of base tell the overlay, read under the base's lock.
+struct BaseView {
+  const void* rows;
+  int dim;
+  long long size;
+};
+BaseView base_view(vrag_ivf_index* ix) {
+  if (ix->sq8_base) {
+    const Sq8View v = sq8_index_view(ix->sq8_base);
+    return BaseView{v.codes, v.dim, v.size};
+  }
+  const DenseView v = dense_index_view(ix->base);
+  return BaseView{v.rows, v.dim, v.size};
+}
+
+// `height` rows of `width` bytes between a host array and a device array of other pitch (the SQ8 stride pads the columns).
+hipError_t copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, hipMemcpyKind kind, hipStream_t st) {
+  if (dpitch == width && spitch == width) return hipMemcpyAsync(dst, src, width * height, kind, st);
+  return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, kind, st);
+}
 
 hipError_t half_norms(vrag_ivf_index* ix, hipStream_t st) {
   hipLaunchKernelGGL(ivf_half_norm_kernel, dim3(ix->nlist), dim3(64), 0, st, ix->d_cent.p, ix->dim, ix->d_half.p);
@@ -396,12 +443,13 @@ hipError_t assign_rows(vrag_ivf_index* ix, RowMap map, long long n, hipStream_t 
   hipError_t e = ix->d_assign.grow((size_t)n);
   if (e != hipSuccess) return e;
   const dim3 grid((unsigned)((n + TM - 1) / TM));
-  if (ix->dtype == 1)
-    hipLaunchKernelGGL((ivf_tile_kernel<true, true>), grid, dim3(256), 0, st, ix->rows, map, n, ix->dim, ix->d_cent.p, ix->d_half.p,
-                       ix->nlist, ix->d_assign.p, (float*)nullptr);
-  else
-    hipLaunchKernelGGL((ivf_tile_kernel<false, true>), grid, dim3(256), 0, st, ix->rows, map, n, ix->dim, ix->d_cent.p, ix->d_half.p,
-                       ix->nlist, ix->d_assign.p, (float*)nullptr);
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, ix->rows, ix->row_scales, map, n, ix->dim, ix->d_cent.p, ix->d_half.p, ix->nlist,
+                       ix->d_assign.p, (float*)nullptr);
+  };
+  if (ix->dtype == ROWS_F32) launch(ivf_tile_kernel<ROWS_F32, true>);
+  else if (ix->dtype == ROWS_SQ8) launch(ivf_tile_kernel<ROWS_SQ8, true>);
+  else launch(ivf_tile_kernel<ROWS_BF16, true>);
   return hipGetLastError();
 }
 
@@ -433,6 +481,23 @@ int publish_lists(vrag_ivf_index* ix, long long size, hipStream_t st) {
   return VRAG_OK;
 }
 
+// The device arrays and the stream of a handle whose base fields are set; on failure the handle is destroyed.
+int ivf_open(vrag_ivf_index* ix, vrag_ivf_index** out) {
+  hipError_t e = hipSetDevice(ix->device);
+  if (e == hipSuccess) e = ix->d_cent.grow((size_t)ix->nlist * ix->dim);
+  if (e == hipSuccess && ix->dim != ix->user_dim) e = hipMemset(ix->d_cent.p, 0, (size_t)ix->nlist * ix->dim * sizeof(float));   // the pad columns stay zero
+  if (e == hipSuccess) e = ix->d_half.grow((size_t)ix->nlist);
+  if (e == hipSuccess) e = ix->d_off.grow((size_t)ix->nlist + 1);
+  if (e == hipSuccess) e = hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking);
+  if (e != hipSuccess) {
+    set_error("ivf index allocation failed: %s", hipGetErrorString(e));
+    vrag_ivf_index_destroy(ix);
+    return VRAG_ERR_HIP;
+  }
+  *out = ix;
+  return VRAG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -443,22 +508,24 @@ int vrag_ivf_index_create(vrag_dense_index* base, int32_t nlist, vrag_ivf_index*
   ARG_CHECK(base, "null base index");
   ARG_CHECK(nlist >= 1 && nlist <= IVF_NLIST_MAX, "nlist must be in [1, %d] (got %d)", IVF_NLIST_MAX, nlist);
   const DenseView v = dense_index_view(base);
-  HIP_TRY(hipSetDevice(v.device));
   auto* ix = new vrag_ivf_index();
   ix->base = base;
-  ix->rows = v.rows, ix->dim = v.dim, ix->dtype = v.dtype, ix->device = v.device;
+  ix->rows = v.rows, ix->dim = ix->user_dim = v.dim, ix->dtype = v.dtype, ix->device = v.device;
   ix->nlist = nlist;
-  hipError_t e = ix->d_cent.grow((size_t)nlist * v.dim);
-  if (e == hipSuccess) e = ix->d_half.grow((size_t)nlist);
-  if (e == hipSuccess) e = ix->d_off.grow((size_t)nlist + 1);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    set_error("ivf index allocation failed: %s", hipGetErrorString(e));
-    vrag_ivf_index_destroy(ix);
-    return VRAG_ERR_HIP;
-  }
-  *out = ix;
-  return VRAG_OK;
+  return ivf_open(ix, out);
+}
+
+int vrag_ivf_index_create_sq8(vrag_sq8_index* base, int32_t nlist, vrag_ivf_index** out) {
+  ARG_CHECK(out, "null argument");
+  *out = nullptr;
+  ARG_CHECK(base, "null base index");
+  ARG_CHECK(nlist >= 1 && nlist <= IVF_NLIST_MAX, "nlist must be in [1, %d] (got %d)", IVF_NLIST_MAX, nlist);
+  const Sq8View v = sq8_index_view(base);
+  auto* ix = new vrag_ivf_index();
+  ix->sq8_base = base;
+  ix->rows = v.codes, ix->row_scales = v.scales, ix->dim = v.stride, ix->user_dim = v.dim, ix->dtype = ROWS_SQ8, ix->device = v.device;
+  ix->nlist = nlist;
+  return ivf_open(ix, out);
 }
 
 void vrag_ivf_index_destroy(vrag_ivf_index* ix) {
@@ -473,7 +540,8 @@ int vrag_ivf_index_set_centroids(vrag_ivf_index* ix, const float* centroids) {
   ARG_CHECK(ix && centroids, "null argument");
   std::lock_guard<std::mutex> lk(ix->mu);
   HIP_TRY(hipSetDevice(ix->device));
-  HIP_TRY(hipMemcpyAsync(ix->d_cent.p, centroids, (size_t)ix->nlist * ix->dim * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+  HIP_TRY(copy_rows(ix->d_cent.p, ix->dim * sizeof(float), centroids, ix->user_dim * sizeof(float), ix->user_dim * sizeof(float),
+                    (size_t)ix->nlist, hipMemcpyHostToDevice, ix->stream));
   HIP_TRY(half_norms(ix, ix->stream));
   HIP_TRY(hipStreamSynchronize(ix->stream));
   ix->have_centroids = true;
@@ -488,7 +556,7 @@ int vrag_ivf_index_train(vrag_ivf_index* ix, int32_t iters, int64_t max_train_ro
   ARG_CHECK(iters >= 0 && iters <= 1000, "iters must be in [0, 1000] (got %d)", iters);
   ARG_CHECK(max_train_rows >= 1, "max_train_rows must be positive");
   std::lock_guard<std::mutex> lk(ix->mu);
-  const long long size = dense_index_view(ix->base).size;
+  const long long size = base_view(ix).size;
   ARG_CHECK(size >= 1, "the base index holds no rows to train on");
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t st = ix->stream;
@@ -496,8 +564,12 @@ int vrag_ivf_index_train(vrag_ivf_index* ix, int32_t iters, int64_t max_train_ro
   const int nlist = ix->nlist, dim = ix->dim;
   const RowMap sample{0, size, n_train};   // sample item i = base row i * size / n_train
   auto update = [&]() -> hipError_t {   // every non-empty list of (d_toff, d_tmem) -> its mean
-    if (ix->dtype == 1) hipLaunchKernelGGL(ivf_mean_kernel<true>, dim3(nlist), dim3(256), 0, st, ix->rows, dim, ix->d_toff.p, ix->d_tmem.p, ix->d_cent.p);
-    else hipLaunchKernelGGL(ivf_mean_kernel<false>, dim3(nlist), dim3(256), 0, st, ix->rows, dim, ix->d_toff.p, ix->d_tmem.p, ix->d_cent.p);
+    const auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(nlist), dim3(256), 0, st, ix->rows, ix->row_scales, dim, ix->d_toff.p, ix->d_tmem.p, ix->d_cent.p);
+    };
+    if (ix->dtype == ROWS_F32) launch(ivf_mean_kernel<ROWS_F32>);
+    else if (ix->dtype == ROWS_SQ8) launch(ivf_mean_kernel<ROWS_SQ8>);
+    else launch(ivf_mean_kernel<ROWS_BF16>);
     return hipGetLastError();
   };
   std::vector<unsigned> a((size_t)n_train), off((size_t)nlist + 1), mem((size_t)nlist);
@@ -535,7 +607,7 @@ int vrag_ivf_index_sync(vrag_ivf_index* ix) {
   ARG_CHECK(ix, "null argument");
   std::lock_guard<std::mutex> lk(ix->mu);
   ARG_CHECK(ix->have_centroids, "ivf index has no centroids yet (set_centroids or train first)");
-  const long long size = dense_index_view(ix->base).size;   // read under the base's lock; rows [0, size) are in place
+  const long long size = base_view(ix).size;   // read under the base's lock; rows [0, size) are in place
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t st = ix->stream;
   if (size > ix->n_assigned) {
@@ -579,7 +651,11 @@ int vrag_ivf_index_read(vrag_ivf_index* ix, float* centroids, uint32_t* list_off
   ARG_CHECK(!centroids || ix->have_centroids, "ivf index has no centroids yet");
   ARG_CHECK(!(list_off || list_rows) || ix->synced, "ivf index has no lists yet (sync first)");
   HIP_TRY(hipSetDevice(ix->device));
-  if (centroids) HIP_TRY(hipMemcpy(centroids, ix->d_cent.p, (size_t)ix->nlist * ix->dim * sizeof(float), hipMemcpyDeviceToHost));
+  if (centroids) {
+    HIP_TRY(copy_rows(centroids, ix->user_dim * sizeof(float), ix->d_cent.p, ix->dim * sizeof(float), ix->user_dim * sizeof(float),
+                      (size_t)ix->nlist, hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+  }
   if (list_off) HIP_TRY(hipMemcpy(list_off, ix->d_off.p, ((size_t)ix->nlist + 1) * sizeof(unsigned), hipMemcpyDeviceToHost));
   if (list_rows && ix->n_assigned)
     HIP_TRY(hipMemcpy(list_rows, ix->d_rows.p, (size_t)ix->n_assigned * sizeof(unsigned), hipMemcpyDeviceToHost));
@@ -594,8 +670,8 @@ int vrag_ivf_index_search(vrag_ivf_index* ix, const float* queries, int32_t nq, 
   std::lock_guard<std::mutex> lk(ix->mu);
   ARG_CHECK(ix->synced, "ivf index has no lists yet (sync first)");
   {
-    const DenseView v = dense_index_view(ix->base);
-    ARG_CHECK(v.dim == ix->dim && v.rows == ix->rows, "the base index does not match the one this overlay was created on");
+    const BaseView v = base_view(ix);
+    ARG_CHECK(v.dim == ix->user_dim && v.rows == ix->rows, "the base index does not match the one this overlay was created on");
   }
   HIP_TRY(hipSetDevice(ix->device));
   hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : ix->stream;
@@ -629,7 +705,15 @@ int vrag_ivf_index_search(vrag_ivf_index* ix, const float* queries, int32_t nq, 
     HIP_TRY(ix->d_probe.grow((size_t)pairs_max));
     HIP_TRY((set_max_dynamic_lds<ivf_select_kernel>(IVF_NLIST_MAX * (int)sizeof(u64))));
   }
-  HIP_TRY(hipMemcpyAsync(ix->d_q.p, queries, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, st));
+  const bool sq8 = ix->dtype == ROWS_SQ8;
+  if (dim != ix->user_dim) HIP_TRY(hipMemsetAsync(ix->d_q.p, 0, (size_t)nq * dim * sizeof(float), st));   // pad columns: zero
+  HIP_TRY(copy_rows(ix->d_q.p, dim * sizeof(float), queries, ix->user_dim * sizeof(float), ix->user_dim * sizeof(float), (size_t)nq,
+                    hipMemcpyHostToDevice, st));
+  if (sq8) {   // the queries by the rows' rule, once per search; the zero pad columns change neither the scale nor a code
+    HIP_TRY(ix->d_qc.grow((size_t)nq * dim));
+    HIP_TRY(ix->d_qs.grow((size_t)nq));
+    HIP_TRY(launch_sq8_query(ix->d_q.p, nq, dim, dim, ix->d_qc.p, ix->d_qs.p, st));
+  }
   HIP_TRY(hipMemsetAsync(ix->d_scanned.p, 0, (size_t)nq * sizeof(unsigned long long), st));
   for (int q0 = 0; q0 < nq; q0 += nqs_max) {
     const int nqs = std::min(nqs_max, nq - q0);
@@ -638,8 +722,8 @@ int vrag_ivf_index_search(vrag_ivf_index* ix, const float* queries, int32_t nq, 
     const unsigned* probe = nullptr;
     if (!all) {
       const dim3 grid((nqs + TM - 1) / TM, (nlist + TN - 1) / TN);
-      hipLaunchKernelGGL((ivf_tile_kernel<true, false>), grid, dim3(256), 0, st, dq, RowMap{0, 1, 1}, (long long)nqs, dim, ix->d_cent.p,
-                         ix->d_half.p, nlist, (unsigned*)nullptr, ix->d_scores.p);
+      hipLaunchKernelGGL((ivf_tile_kernel<ROWS_F32, false>), grid, dim3(256), 0, st, dq, (const float*)nullptr, RowMap{0, 1, 1}, (long long)nqs,
+                         dim, ix->d_cent.p, ix->d_half.p, nlist, (unsigned*)nullptr, ix->d_scores.p);
       hipLaunchKernelGGL(ivf_select_kernel, dim3(nqs), dim3(1024), (size_t)cap * sizeof(u64), st, ix->d_scores.p, nlist, cap, np, ix->d_probe.p);
       HIP_TRY(hipGetLastError());
       probe = ix->d_probe.p;
@@ -651,7 +735,11 @@ int vrag_ivf_index_search(vrag_ivf_index* ix, const float* queries, int32_t nq, 
     hipLaunchKernelGGL(ivf_fill_kernel, pgrid, dim3(256), 0, st, probe, pairs, np, ix->d_cnt.p, ix->d_place.p, ix->d_goff.p, ix->d_item_list.p,
                        ix->d_item_n.p, ix->d_item_pair.p);
     const dim3 sgrid((unsigned)std::min<long long>(pairs, IVF_SCAN_WGS), split);
-    if (ix->dtype == 1)
+    if (sq8)
+      HIP_TRY(launch_ivf_sq8_scan(sgrid, reinterpret_cast<const signed char*>(ix->rows), ix->row_scales, dim, ix->d_off.p, ix->d_rows.p,
+                                  ix->d_qc.p + (size_t)q0 * dim, ix->d_qs.p + q0, nqs, k, ix->d_goff.p + nlist, ix->d_item_list.p,
+                                  ix->d_item_n.p, ix->d_item_pair.p, ix->d_cand.p, st));
+    else if (ix->dtype == ROWS_F32)
       hipLaunchKernelGGL(ivf_scan_kernel<true>, sgrid, dim3(256), 0, st, ix->rows, dim, ix->d_off.p, ix->d_rows.p, dq, nqs, k, ix->d_goff.p + nlist,
                          ix->d_item_list.p, ix->d_item_n.p, ix->d_item_pair.p, ix->d_cand.p);
     else

@@ -39,12 +39,11 @@
 #include "common.h"
 #include "compact.h"
 #include "host_util.h"
+#include "sq8_kernels.h"
 #include "topk_kernels.h"
 
 namespace vrag {
 namespace {
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SQ8_DIM_MAX = 4096;
 constexpr int SQ8_SCAN_MAX_Q = 4;
@@ -71,12 +70,6 @@ __device__ __forceinline__ int row16_sum_i32(int v) {
 
 __device__ __forceinline__ bool row_allowed(const unsigned* __restrict__ allow, long long row) {
   return !allow || ((allow[row >> 5] >> (unsigned)(row & 31)) & 1u);
-}
-
-// score = (float)idot * (s_q * s_r): the conversion, the scale product, the final product -- three roundings, no fused step
-__device__ __forceinline__ float sq8_score(int idot, float sq, float sr) {
-  const float scale = __fmul_rn(sq, sr);
-  return __fmul_rn((float)idot, scale);
 }
 
 // ------------------------------------------------------------------------------------ quantisation
@@ -396,8 +389,7 @@ int sq8_search(vrag_sq8_index* ix, const float* queries, int nq, int k, long lon
   }
   if (tile) HIP_TRY((set_max_dynamic_lds<sq8_tile_kernel>(sq8_tile_lds(KMAX))));
   HIP_TRY(hipMemcpyAsync(ix->d_q.p, queries, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(sq8_query_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, ix->d_q.p, nq, dim, stride, ix->d_qc.p, ix->d_qs.p);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(launch_sq8_query(ix->d_q.p, nq, dim, stride, ix->d_qc.p, ix->d_qs.p, st));
   // one page of kk keys per query into d_out [nq][kk]
   auto run_page = [&](const u64* bound) -> int {
     for (int q0 = 0; q0 < nq; q0 += SQ8_SLICE) {
@@ -445,6 +437,20 @@ int sq8_search(vrag_sq8_index* ix, const float* queries, int nq, int k, long lon
 }
 
 }  // namespace
+
+namespace vrag {
+
+hipError_t launch_sq8_query(const float* queries, int nq, int dim, int stride, signed char* qcodes, float* qscales, hipStream_t st) {
+  hipLaunchKernelGGL(sq8_query_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, queries, nq, dim, stride, qcodes, qscales);
+  return hipGetLastError();
+}
+
+Sq8View sq8_index_view(vrag_sq8_index* ix) {
+  std::lock_guard<std::mutex> lk(ix->mu);
+  return Sq8View{ix->codes.p, ix->scales.p, ix->stride, ix->dim, ix->device, (long long)ix->size};
+}
+
+}  // namespace vrag
 
 extern "C" {
 

@@ -214,11 +214,12 @@ class Sq8Shard(_Handle):
     and one fp32 scale per row, int8 queries, integer-exact scores.  The call shapes are `DenseShard`'s."""
 
     _destroy = "vrag_sq8_index_destroy"
-    ivf = None    # no IVF overlay over int8 rows
+    ivf = None    # an instance may own an IVF_SQ8 overlay over its rows (`IvfOverlay`: closed before the shard)
 
     def __init__(self, dim: int, capacity: int, device: int = 0):
         _lib.require_gpu()
         self.dim, self.capacity = dim, capacity
+        self.ivf: Optional["IvfOverlay"] = None
         self._open("vrag_sq8_index_create", dim, capacity, device)
 
     def add(self, rows: np.ndarray) -> None:
@@ -262,16 +263,23 @@ class Sq8Shard(_Handle):
         `DenseShard.search_filtered`): the search kernels skip the other rows (`vrag_sq8_index_search_filtered`)."""
         return self._search(queries, k, (allow_words, n_allow), stream)
 
+    def close(self):
+        ivf, self.ivf = getattr(self, "ivf", None), None
+        if ivf is not None:
+            ivf.close()
+        super().close()
+
 
 class IvfOverlay(_Handle):
-    """IVF_FLAT lists over a `DenseShard`'s resident rows (`vrag_ivf_index`): centroids, list offsets and row numbers only.
-    The shard must outlive it (`DenseShard.ivf` owns it and closes it first)."""
+    """IVF lists over a shard's resident rows (`vrag_ivf_index`): centroids, list offsets and row numbers only -- IVF_FLAT over
+    a `DenseShard`, IVF_SQ8 over an `Sq8Shard` (`vrag_ivf_index_create_sq8`: the rows are scored by the SQ8 rule).
+    The shard must outlive it (the shard's `ivf` owns it and closes it first)."""
 
     _destroy = "vrag_ivf_index_destroy"
 
-    def __init__(self, shard: DenseShard, nlist: int):
+    def __init__(self, shard: "DenseShard | Sq8Shard", nlist: int):
         self.dim, self.nlist = shard.dim, int(nlist)
-        self._open("vrag_ivf_index_create", shard._h, self.nlist)
+        self._open("vrag_ivf_index_create_sq8" if isinstance(shard, Sq8Shard) else "vrag_ivf_index_create", shard._h, self.nlist)
 
     def set_centroids(self, centroids: np.ndarray) -> None:
         c = np.ascontiguousarray(centroids, dtype=np.float32)
@@ -299,7 +307,7 @@ class IvfOverlay(_Handle):
         return cent, off, rows
 
     def remap(self, keep: np.ndarray) -> None:
-        """After `DenseShard.compact(keep)` of the shard, with the same `keep`: the lists' rows are renumbered, dropped rows
+        """After `compact(keep)` of the shard (`DenseShard` or `Sq8Shard`), with the same `keep`: the lists' rows are renumbered, dropped rows
         leave their lists, the centroids stay (`vrag_ivf_index_remap`)."""
         keep = np.asarray(keep, dtype=bool).reshape(-1)
         words = _bitmap(keep)

@@ -258,14 +258,15 @@ def convert_hits_to_results(hits: List[dict], dynamic_fields: Optional[List[str]
     return results
 
 
-IVF_MIN_ROWS = 4096       # below this a store with index_type="IVF_FLAT" searches FLAT
+IVF_INDEX_TYPES = ("IVF_FLAT", "IVF_SQ8")   # index types with lists: an `IvfOverlay` over the resident dense shard
+IVF_MIN_ROWS = 4096       # below this a store with one of them searches FLAT
 IVF_NLIST_MAX = 16384     # vrag_ivf_index_create
 IVF_MIN_LIST_ROWS = 39    # rows per list a training needs, as faiss' k-means asks for (min_points_per_centroid)
 IVF_K_MAX = 64            # vrag_ivf_index_search
 
 
 def ivf_effective_nlist(n_rows: int, nlist: int) -> int:
-    """Lists an IVF_FLAT store of `n_rows` rows is built with: 0 (= search FLAT) below `IVF_MIN_ROWS`, else the configured
+    """Lists an IVF_FLAT / IVF_SQ8 store of `n_rows` rows is built with: 0 (= search FLAT) below `IVF_MIN_ROWS`, else the configured
     `nlist` capped by the library's limit and by `IVF_MIN_LIST_ROWS` rows per list."""
     if n_rows < IVF_MIN_ROWS:
         return 0
@@ -342,13 +343,13 @@ def parse_grouping(search_params: Optional[Dict[str, Any]]) -> Optional[Grouping
 
 def check_index_config(index_type: str, nlist: int, nprobe: int, sharded: bool) -> None:
     """The constructor's refusals for `index_type` / `nlist` / `nprobe` (pure: no device needed)."""
-    if index_type not in ("FLAT", "IVF_FLAT"):
-        raise ValueError(f"index_type must be 'FLAT' or 'IVF_FLAT' (got {index_type!r})")
+    if index_type not in ("FLAT", *IVF_INDEX_TYPES):
+        raise ValueError(f"index_type must be 'FLAT', 'IVF_FLAT' or 'IVF_SQ8' (got {index_type!r})")
     for name, v in (("nlist", nlist), ("nprobe", nprobe)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
             raise ValueError(f"{name} must be a positive integer (got {v!r})")
-    if index_type == "IVF_FLAT" and sharded:
-        raise ValueError("index_type='IVF_FLAT' is single-GPU: sharded stores (distributed=True or a comm) keep FLAT")
+    if index_type in IVF_INDEX_TYPES and sharded:
+        raise ValueError(f"index_type={index_type!r} is single-GPU: sharded stores (distributed=True or a comm) keep FLAT")
 
 
 def check_auto_compact(auto_compact: Optional[float], sharded: bool) -> None:
@@ -366,13 +367,15 @@ DENSE_DTYPES = ("f32", "bf16", "int8")
 
 def check_dense_dtype(dense_dtype: str, index_type: str, sharded: bool) -> None:
     """The constructor's refusals for `dense_dtype` (pure: no device needed).  "int8" (SQ8 rows, `Sq8Shard`) has no
-    device-resident search form and no IVF overlay yet, so it is single-GPU and FLAT."""
+    device-resident search form, so it is single-GPU; its lists are index_type="IVF_SQ8", which in turn needs int8 rows."""
     if dense_dtype not in DENSE_DTYPES:
         raise ValueError(f"dense_dtype must be 'f32', 'bf16' or 'int8' (got {dense_dtype!r})")
     if dense_dtype == "int8" and sharded:
         raise ValueError("dense_dtype='int8' is single-GPU: sharded stores (distributed=True or a comm) keep 'f32' or 'bf16'")
     if dense_dtype == "int8" and index_type == "IVF_FLAT":
-        raise ValueError("dense_dtype='int8' searches FLAT: index_type='IVF_FLAT' needs 'f32' or 'bf16' rows")
+        raise ValueError("index_type='IVF_FLAT' needs 'f32' or 'bf16' rows: dense_dtype='int8' searches FLAT or index_type='IVF_SQ8'")
+    if index_type == "IVF_SQ8" and dense_dtype != "int8":
+        raise ValueError(f"index_type='IVF_SQ8' lays its lists over SQ8 rows: it needs dense_dtype='int8' (got dense_dtype={dense_dtype!r})")
 
 
 def check_choice(name: str, value, a: str, b: str) -> None:
@@ -554,7 +557,7 @@ class GpuVectorStore(VectorStore):
     also gives up bit-exact ranking between rows whose fp32 scores nearly tie; `dense_dtype="int8"` stores SQ8 rows
     (`Sq8Shard`: int8 codes and one fp32 scale per row, dim + 4 bytes, half of bf16's stream) and quantises the queries by
     the same rule -- scores are the integer-exact ones of include/vrag_amd.h "SQ8 dense rows", approximate only in what a
-    code says about its component; single-GPU and FLAT, the host keeps its fp32 rows.
+    code says about its component; single-GPU, FLAT or `index_type="IVF_SQ8"`, the host keeps its fp32 rows.
     `filter` supports the comparison subset of Milvus expressions in `parse_filter`
     (the reference itself only builds `metadata["document_id"] == "..."`, index.py:735-739); anything else is
     rejected loudly.  Filters and deletes act before the search like Milvus' (a selective filter still returns its
@@ -629,7 +632,7 @@ class GpuVectorStore(VectorStore):
         corpus-wide BM25 statistics are summed over the ranks, which needs an initialised `torch.distributed` and a `comm`
         with `sum_int64`: ValueError otherwise.
         `dense_dtype`: "f32" (default), "bf16" or "int8" (see the class docstring); "int8" with `distributed=True`, a `comm`
-        or `index_type="IVF_FLAT"` raises ValueError.  Kept in a saved store's manifest.
+        or `index_type="IVF_FLAT"` raises ValueError (its lists are `index_type="IVF_SQ8"`).  Kept in a saved store's manifest.
         `dense_prefilter` (fp32 rows only): keep a bf16 image of the rows beside them so that every search streams
         half (small batches) or a fraction (large ones) of the bytes of the full fp32 scan and returns the same bits (`DenseShard`).  It costs
         +50 % of the dense rows' HBM.  "auto" (default) = on where the image route exists (dim % 64 == 0 and <= 768,
@@ -665,7 +668,10 @@ class GpuVectorStore(VectorStore):
         stores, milvus_base.py:40-50) = the dense leg looks only at the rows of the `nprobe` lists nearest to the query out of
         `nlist` k-means lists laid over the resident shard (`IvfOverlay`; `ivf_effective_nlist` caps `nlist` for small stores
         and keeps stores under `IVF_MIN_ROWS` rows FLAT) -- approximate in WHICH rows it finds, exact in their scores and
-        order.  `search_params={"nprobe": n}` (or Milvus' `{"params": {"nprobe": n}}`) of `query` / `query_batch` overrides
+        order.  "IVF_SQ8" (Milvus' name) = the same lists over the SQ8 rows of `dense_dtype="int8"`, which it requires (ValueError
+        with any other `dense_dtype`): the rows of the probed lists are scored by the SQ8 rule, so what it reports about a row is
+        what the FLAT int8 store reports, bit for bit; everything said of IVF_FLAT here holds for it.
+        `search_params={"nprobe": n}` (or Milvus' `{"params": {"nprobe": n}}`) of `query` / `query_batch` overrides
         `nprobe` per call; n >= nlist returns the FLAT results.  Lists of more than 64 rows per method, filtered queries left
         short and sharded stores search FLAT.  Kept in a saved store's manifest (FLAT stores write nothing new).
         `auto_compact`: None (default) = `compact()` runs only when it is called.  A fraction in (0, 1): `delete` calls it once
@@ -971,7 +977,7 @@ class GpuVectorStore(VectorStore):
                 else:
                     self._dense.add(rows[self._dense_flushed:])
                 self._dense_flushed = n
-                if self.index_type == "IVF_FLAT":
+                if self._has_lists:
                     self._ivf_refresh(n)
             if self.enable_sparse and n > self._sparse_flushed:
                 main = self._sparse_parts[0] if self._sparse_parts else None
@@ -1006,8 +1012,13 @@ class GpuVectorStore(VectorStore):
                 self._owned_dev = (torch.from_numpy(np.ascontiguousarray(self._main_rows)).to(torch.device("cuda", self.device)), n)
             self._dirty = False
 
+    @property
+    def _has_lists(self) -> bool:
+        """An IVF store (IVF_FLAT over fp32 / bf16 rows, IVF_SQ8 over int8 rows): its dense shard gets an overlay."""
+        return self.index_type in IVF_INDEX_TYPES
+
     def _ivf_refresh(self, n: int) -> None:
-        """Keeps the IVF_FLAT overlay of the resident dense shard in step with its `n` rows (called by `_flush`, under the
+        """Keeps the IVF overlay of the resident dense shard in step with its `n` rows (called by `_flush`, under the
         lock): trains (10 Lloyd rounds over 64 rows per list) on the first flush that reaches `IVF_MIN_ROWS`, when the shard
         has doubled since, and when the shard was rebuilt for capacity; every flush assigns the new rows to their lists."""
         shard = self._dense
@@ -1025,7 +1036,7 @@ class GpuVectorStore(VectorStore):
             current.sync()
 
     def ivf_stats(self) -> Optional[Dict[str, int]]:
-        """`{"nlist", "rows", "largest_list", "trained_rows"}` of the dense shard's IVF_FLAT overlay after a flush; None
+        """`{"nlist", "rows", "largest_list", "trained_rows"}` of the dense shard's IVF_FLAT / IVF_SQ8 overlay after a flush; None
         while the store searches FLAT (index_type="FLAT", or fewer than `IVF_MIN_ROWS` rows)."""
         with self._mu:
             self._flush()
@@ -1036,7 +1047,7 @@ class GpuVectorStore(VectorStore):
 
     def _nprobe_of(self, search_params: Optional[Dict[str, Any]]) -> Optional[int]:
         """The dense leg's `nprobe` for one call; None on a FLAT store (`search_params` has nothing to say there)."""
-        return parse_nprobe(search_params, self.nprobe) if self.index_type == "IVF_FLAT" else None
+        return parse_nprobe(search_params, self.nprobe) if self._has_lists else None
 
     def _main_parts(self, kind: str):
         """(segments of the resident shard as (shard, first local row), device row table, rows in the whole store)
@@ -1173,7 +1184,7 @@ class GpuVectorStore(VectorStore):
         hit).  `parts` are this rank's segments as (shard, first local row) (empty when it holds none of the rows) and
         `shard_rows[j]` the global row of local row j (None = the resident main shard, whose append-only mapping is read
         after the search; `rows_dev` = the same table in HBM); with more than one rank the per-shard lists meet in one
-        all-gather and are merged on the GPU.  `nprobe` (IVF_FLAT stores, the dense leg's first pass): a shard with an overlay
+        all-gather and are merged on the GPU.  `nprobe` (IVF_FLAT / IVF_SQ8 stores, the dense leg's first pass): a shard with an overlay
         answers lists of up to `IVF_K_MAX` rows from its `nprobe` nearest lists instead of streaming every row."""
         Q = len(queries)
         comm = self._comm
@@ -1297,7 +1308,7 @@ class GpuVectorStore(VectorStore):
         their fp32 scores.  One device pass for the whole batch over the full shard; queries that come up short because
         filtered / deleted rows took their slots (and every query when the filter passes under 1/8 of the rows) get a
         second pass over the masked subset shard -- or, with `filter_route="bitmap"`, the filtered search of the resident
-        shard (`_filtered_topk`; no subset shard is built in that mode).  `nprobe` (dense leg of an IVF_FLAT store): the full pass looks at the rows of that many
+        shard (`_filtered_topk`; no subset shard is built in that mode).  `nprobe` (dense leg of an IVF_FLAT / IVF_SQ8 store): the full pass looks at the rows of that many
         lists only (`_device_topk`); the second pass stays exact.  Every branch below depends only on replicated state and on merged
         results, so the ranks of a sharded store take the same path and meet in the same collectives."""
         self._check_limit(limit)
@@ -1591,8 +1602,8 @@ class GpuVectorStore(VectorStore):
             raise ValueError(f"{supported}: this store has no dense field")
         if self._comm is not None:
             raise ValueError(f"{supported}: not on a sharded store (distributed=True or a comm)")
-        if self.index_type == "IVF_FLAT":
-            raise ValueError(f"{supported}: not with index_type='IVF_FLAT'")
+        if self._has_lists:
+            raise ValueError(f"{supported}: not with index_type={self.index_type!r}")
         if self.dense_dtype == "int8":
             raise ValueError(f"{supported}: not with dense_dtype='int8'")
         if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= top_k <= GROUP_TOP_K_MAX:
@@ -1746,7 +1757,7 @@ class GpuVectorStore(VectorStore):
         """Reads a directory written by `save` -- by this or an earlier revision (formats 1 - 3), by any number of
         ranks: when the world size differs from the writer's, the saved shards are put back in row order and cut
         contiguously over the ranks that open the store.  `filter_route`, `rrf_route`, `filter_eval`, `filter_strings`, `auto_compact`: as the constructor's (not part of a saved store).
-        An IVF_FLAT store comes back IVF_FLAT with its `nlist` / `nprobe`; its lists are trained again at the first flush
+        An IVF_FLAT / IVF_SQ8 store comes back as what it was with its `nlist` / `nprobe`; its lists are trained again at the first flush
         (training is deterministic: the same rows give the same lists)."""
         head, ids, shards = cls._read_saved(path)
         st = cls(dense_dim=head["dense_dim"], sparse_vocab=head["sparse_vocab"], enable_dense=head["enable_dense"],
