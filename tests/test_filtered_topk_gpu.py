@@ -150,7 +150,8 @@ def test_dense_filtered_equals_the_oracle_over_the_passing_rows(dtype, data, dim
                 if name == "none":
                     assert (got[1] == -1).all() and np.isneginf(got[0]).all()
             _same(sh.search_filtered(Q[:2], 5, _words(mask), n), _ref_dense(stored, Q[:2], 5, passing), (name, "class method"))
-        _same(_dense_filtered(sh, Q[:2], 5, np.ones(n, bool), n_allow=0), _ref_dense(stored, Q[:2], 5, passing[:0]), "n_allow = 0")
+        for k in (5, 65):       # nothing passes, one page and paged (the "none" mask above meets k = 1 and k = 65 too)
+            _same(_dense_filtered(sh, Q[:2], k, np.ones(n, bool), n_allow=0), _ref_dense(stored, Q[:2], k, passing[:0]), ("n_allow = 0", k))
         for (nq, k), want in zip(plain, before):
             _same(sh.search(Q[:nq], k), want, ("unfiltered after the filtered calls", nq, k))
         # a mask built before an append stays valid: rows at or beyond n_allow never appear, with or without bits for them
@@ -250,7 +251,8 @@ def test_sparse_filtered_equals_the_oracle_over_the_passing_documents(vocab, n, 
                 if name == "none":
                     assert (got[1] == -1).all() and np.isneginf(got[0]).all()
             _same(sh.search_filtered(queries[:9], 5, _words(mask), n), _ref_sparse(csr, vocab, queries[:9], 5, passing), (name, "class method"))
-        _same(_sparse_filtered(sh, queries[:2], 5, np.ones(n, bool), n_allow=0), _ref_sparse(csr, vocab, queries[:2], 5, passing[:0]), "n_allow = 0")
+        for k in (5, 65):       # nothing passes, one page and paged (the "none" mask above meets k = 1 and k = 65 too)
+            _same(_sparse_filtered(sh, queries[:2], k, np.ones(n, bool), n_allow=0), _ref_sparse(csr, vocab, queries[:2], k, passing[:0]), ("n_allow = 0", k))
         for (nq, k), want in zip(plain, before):
             _same(sh.search(queries[:nq], k), want, ("unfiltered after the filtered calls", nq, k))
     finally:

@@ -221,6 +221,19 @@ def test_library_corpus_stats_override_and_device_lists():
             assert np.array_equal(ms, want_s), k
         for (hs, hi), (ds, di) in zip(host, dev):
             assert np.array_equal(hi, di) and np.array_equal(hs, ds)
+    # a row map shorter than a hit's row: hits at or beyond n_map come back as missing (-1 / -inf), in place; the others as before
+    ix, rows, tab, k = shards[1], owners[1], table[1], 10
+    sc, local = ix.search_sharded(queries, k, None, total[0], sum_df)
+    hit_rows = np.sort(local[local >= 0])
+    short = int(hit_rows[len(hit_rows) // 2])                               # the median hit row: hits on both sides of the map's end
+    inside = (local >= 0) & (local < short)
+    assert inside.any() and (local >= short).any()
+    d_s = torch.empty((len(queries), k), dtype=torch.float32, device="cuda")
+    d_i = torch.empty((len(queries), k), dtype=torch.int64, device="cuda")
+    ix.search_sharded(queries, k, None, total[0], sum_df, device_out=(d_s.data_ptr(), d_i.data_ptr(), tab.data_ptr(), short, stream))
+    torch.cuda.synchronize()
+    assert np.array_equal(d_i.cpu().numpy(), np.where(inside, rows[np.where(inside, local, 0)], -1))
+    assert np.array_equal(d_s.cpu().numpy().view(np.uint32), np.where(inside, sc, -np.inf).astype(np.float32).view(np.uint32))
     for ix in shards:                                                       # (0, 0): back to the index's own statistics
         ix.set_corpus_stats(0, 0)
         assert ix.query_terms(queries)[4] == ix.stats()["live"]

@@ -204,8 +204,9 @@ def test_new_full_text_kernels_use_no_scratch():
     from test_full_text_host import _resources
 
     rows = _resources("fulltext.hip")
-    mine = [r for r in rows if "ft_export_kernel" in r["name"]]
-    assert len(mine) == 1, [r["name"] for r in rows]
+    assert not [r["name"] for r in rows if "export" in r["name"]]   # the text search exports through csrc/topk.hip's kernel ...
+    mine = [r for r in _resources("topk.hip") if "topk_export_keys_kernel" in r["name"]]   # ... which is held to the same
+    assert len(mine) == 1, [r["name"] for r in mine]
     # kd_kernel now reads {N, sum dl} through a pointer the host picks (the index's own pair or the corpus-wide one)
     for r in mine + [r for r in rows if "kd_kernel" in r["name"]]:
         assert int(r["ScratchSize [bytes/lane]"]) == 0 and int(r["VGPRs Spill"]) == 0 and int(r["SGPRs Spill"]) == 0, r

@@ -18,9 +18,11 @@ _FP, _LP = C.POINTER(C.c_float), C.POINTER(C.c_int64)
 NQ_MAX, EXTRA = 100, 40          # queries per data set; append room of every index
 ZERO_Q, DUP_Q = 3, 1             # the all-zero query; the query that equals the duplicated row
 
-# (dim, n, nq, k): every dim of {24, 64, 384, 768}, n of {1, 63, 257, 4097, 40000}, nq of {1, 4, 5, 17, 64, 65, 100}, k of {1, 10, 64, 65, 200}
+# (dim, n, nq, k): every dim of {24, 64, 384, 768}, n of {1, 63, 64, 128, 257, 4097, 40000}, nq of {1, 4, 5, 17, 64, 65, 100},
+# k of {1, 10, 64, 65, 128, 200, 1024}.  The pages of k > 64: (24, 64, 5, 65) a first page exactly full and an empty second;
+# (24, 128, 4, 128) two exactly full pages, the loop ends on k; (64, 257, 4, 1024) the largest k, sixteen pages, exhausted in the fifth
 CASES = [
-    (24, 1, 1, 1), (24, 63, 4, 10), (24, 257, 5, 64), (24, 4097, 100, 200),
+    (24, 1, 1, 1), (24, 63, 4, 10), (24, 257, 5, 64), (24, 4097, 100, 200), (24, 64, 5, 65), (24, 128, 4, 128), (64, 257, 4, 1024),
     (64, 63, 17, 65), (64, 257, 64, 10), (64, 4097, 65, 10), (64, 40000, 4, 64), (64, 40000, 17, 1),
     (384, 1, 5, 10), (384, 257, 100, 1), (384, 4097, 1, 200), (384, 4097, 17, 64), (384, 40000, 64, 10),
     (768, 63, 65, 200), (768, 257, 1, 10), (768, 4097, 64, 65), (768, 4097, 5, 1), (768, 40000, 100, 10), (768, 40000, 1, 64),
@@ -152,6 +154,20 @@ def test_search_equals_the_reference_on_every_route(case):
         assert np.array_equal(want[1][DUP_Q, :min(k, 9)], np.arange(40, 40 + min(k, 9))), "the duplicated rows lead their query's list"
 
 
+@pytest.mark.parametrize("k", [5, 65])
+def test_an_empty_index_answers_no_hits(k):
+    from verbatim_rag_amd.vector_stores import Sq8Shard
+
+    sh = Sq8Shard(64, 16)
+    try:
+        for route in (1, 2, 0):
+            sh.set_route(route)
+            s, i = _search(sh, _data(64, 257)[1][:3], k)
+            assert len(sh) == 0 and (i == -1).all() and np.isneginf(s).all(), route
+    finally:
+        sh.close()
+
+
 @pytest.mark.parametrize("nq", [1, 5, 64, 100])
 @pytest.mark.parametrize("dim,n,k", [(768, 4097, 10), (24, 4097, 65)])
 def test_the_two_routes_return_the_same_bits(dim, n, k, nq):
@@ -168,7 +184,7 @@ def test_the_two_routes_return_the_same_bits(dim, n, k, nq):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3. filtered search
-@pytest.mark.parametrize("dim,n,nq,k", [(24, 257, 5, 10), (768, 4097, 17, 65), (64, 40000, 65, 10), (384, 4097, 4, 200)])
+@pytest.mark.parametrize("dim,n,nq,k", [(24, 257, 5, 10), (768, 4097, 17, 65), (64, 40000, 65, 10), (384, 4097, 4, 200), (24, 64, 5, 65)])
 def test_filtered_search_equals_the_reference_over_the_passing_rows(dim, n, nq, k):
     from verbatim_rag_amd.vector_stores import _bitmap
 

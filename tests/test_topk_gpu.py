@@ -121,8 +121,9 @@ def test_dense_fewer_rows_than_k_and_empty():
     from verbatim_rag_amd.vector_stores import DenseShard
 
     sh = DenseShard(64, 100, "f32")
-    s, i = sh.search(np.ones((2, 64), np.float32), 5)
-    assert (i == -1).all() and np.isinf(s).all()
+    for k in (5, 65):       # one pass and paged
+        s, i = sh.search(np.ones((2, 64), np.float32), k)
+        assert s.shape == i.shape == (2, k) and (i == -1).all() and np.isneginf(s).all()
     sh.add(np.eye(3, 64, dtype=np.float32))
     s, i = sh.search(np.eye(1, 64, dtype=np.float32), 5)
     sh.close()

@@ -608,10 +608,7 @@ int vrag_bpe_create(int32_t n_vocab, const int32_t* merge_left, const int32_t* m
     }
     wblob.assign(whole_blob, whole_blob + whole_off[n_whole]);
   }
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   HIP_TRY(hipSetDevice(device));
   auto* h = new vrag_bpe();
   h->device = device;

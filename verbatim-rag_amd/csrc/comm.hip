@@ -118,10 +118,7 @@ int vrag_comm_create(const uint8_t* id, int32_t rank, int32_t world, int32_t dev
     return VRAG_ERR_INVALID;
   }
   *out = nullptr;
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   Rccl* R = rccl();
   if (!R) {
     set_error("RCCL not found (librccl.so; set VRAG_RCCL_LIB)");

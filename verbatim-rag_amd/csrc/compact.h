@@ -10,6 +10,7 @@
 // them at their destination, and every later wave's sources lie behind everything stored so far.  No workgroup waits for another.
 // The rows in front of the first cleared bit are not touched; a bitmap without a cleared bit launches nothing.
 #pragma once
+#include <initializer_list>
 #include <vector>
 
 #include "host_util.h"
@@ -25,16 +26,30 @@ constexpr int FWORDS = 1024;   // bitmap words per workgroup of the row-list ker
 // to a multiple of `pad`.  Returns the number of set bits.
 long long stage_bitmap(std::vector<unsigned>& h, const uint32_t* words, long long n_rows, size_t pad);
 
-// d_words (device, n_blk * FWORDS words staged as above) -> d_list: the ascending list of the rows whose bit is set (popcount +
-// prefix scan, no atomic appends: the same list on every run).  d_blk: 2 * n_blk + 1 words of scratch -- [n_blk] counts per
-// workgroup, then [n_blk + 1] offsets whose last one is the list's length.  Three launches on `st`, nothing else.
-hipError_t bitmap_row_list(const unsigned* d_words, int n_blk, unsigned* d_blk, unsigned* d_list, hipStream_t st);
+// The ascending list of the rows whose bit is set in a bitmap, in device memory, with the scratch that builds it (popcount +
+// prefix scan, no atomic appends: the same list on every run).  Owned by the handle that searches or compacts under the bitmap.
+class RowList {
+ public:
+  // h: a bitmap staged by stage_bitmap with pad = FWORDS; n_set: its set bits, at least one.
+  // reserve: every allocation of a build (a reallocation frees, and a free waits for the device), nothing enqueued -- for a caller
+  // that has work in flight it must not wait behind; build calls it itself.
+  hipError_t reserve(const std::vector<unsigned>& h, long long n_set);
+  // Uploads the words and builds the list: one copy and three launches on `st`, no wait -- `h` stays as it is until the stream has
+  // passed them (the caller syncs `st` before it lets go of `h`, on its error paths too).
+  hipError_t build(const std::vector<unsigned>& h, long long n_set, hipStream_t st);
+  const unsigned* rows() const { return d_list.p; }   // [n_set] ascending
+  const unsigned* count() const { return d_count; }   // the device word that holds n_set once the build has run
+
+ private:
+  DevArray<unsigned> d_words, d_blk, d_list;
+  const unsigned* d_count = nullptr;
+};
 
 // What one compaction needs, owned by the handle: the staged bitmap, the kept rows' list (list[j] = the source row of destination
 // j) and the bounce buffer.
 struct CompactScratch {
   std::vector<unsigned> h_words;
-  DevArray<unsigned> d_words, d_blk, d_list;
+  RowList list;
   DevArray<char> bounce;
   long long n_rows = 0, n_keep = 0, first_hole = 0;   // of the staged bitmap; first_hole = n_rows when no bit is cleared
   long long kept_before(long long row) const;         // set bits among rows [0, row)
@@ -47,5 +62,17 @@ int compact_plan(CompactScratch& s, const uint32_t* keep_words, long long n_rows
 // the launches enqueued.  Rows of a multiple of 16 bytes move as 16-byte pieces per lane (`base` 16-byte aligned), rows of 1, 4 or
 // 8 bytes as one element per lane.
 int compact_rows(CompactScratch& s, void* base, size_t row_bytes, long long n_src, hipStream_t st);
+
+// The compaction entry of a handle whose per-row arrays all hold `*size` rows, under the handle's lock: checks the bitmap (it
+// covers exactly the handle's rows), plans, and -- when a row is dropped -- waits for the device (a search that only enqueued may
+// still be reading the rows on a caller's stream), compacts every array on `st` (a null base: an array the handle does not hold),
+// drains `st` and only then publishes the new size.  *new_size = *size on every VRAG_OK return; *dropped (nullable) = rows were
+// dropped, so whatever the handle derived from the old row numbers is stale.
+struct CompactArray {
+  void* base;
+  size_t row_bytes;
+};
+int compact_arrays(CompactScratch& s, int device, hipStream_t st, const uint32_t* keep_words, int64_t n_keep, int64_t* size,
+                   int64_t* new_size, std::initializer_list<CompactArray> arrays, bool* dropped = nullptr);
 
 }  // namespace vrag

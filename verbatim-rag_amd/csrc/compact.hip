@@ -1,5 +1,5 @@
 // In-place, order-preserving row compaction under a keep-bitmap (csrc/compact.h states the contract), and the bitmap-to-row-list
-// kernels it shares with the filtered dense search (vrag_dense_index_search_filtered, csrc/topk.hip).
+// kernels (RowList) it shares with the filtered and the grouped dense search (csrc/topk.hip, csrc/grouped.hip).
 //
 // Why bounce waves.  Compaction moves row list[j] to row j with list[j] >= j.  A single launch that did this in place would need
 // every workgroup to know that the rows it overwrites have been read -- a flag another workgroup sets, and a workgroup that spins
@@ -138,12 +138,25 @@ long long stage_bitmap(std::vector<unsigned>& h, const uint32_t* words, long lon
   return n_pass;
 }
 
-hipError_t bitmap_row_list(const unsigned* d_words, int n_blk, unsigned* d_blk, unsigned* d_list, hipStream_t st) {
-  unsigned* blk_cnt = d_blk;
-  unsigned* blk_off = d_blk + n_blk;
-  hipLaunchKernelGGL(filter_count_kernel, dim3(n_blk), dim3(256), 0, st, d_words, blk_cnt);
+// d_blk: [n_blk] counts per workgroup, then [n_blk + 1] offsets whose last one is the list's length.
+hipError_t RowList::reserve(const std::vector<unsigned>& h, long long n_set) {
+  hipError_t e = d_words.grow(h.size());
+  if (e == hipSuccess) e = d_blk.grow((size_t)2 * (h.size() / FWORDS) + 1);
+  if (e == hipSuccess) e = d_list.grow((size_t)n_set);
+  return e;
+}
+
+hipError_t RowList::build(const std::vector<unsigned>& h, long long n_set, hipStream_t st) {
+  const int n_blk = (int)(h.size() / FWORDS);
+  hipError_t e = reserve(h, n_set);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_words.p, h.data(), h.size() * sizeof(unsigned), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return e;
+  unsigned* blk_cnt = d_blk.p;
+  unsigned* blk_off = d_blk.p + n_blk;
+  d_count = blk_off + n_blk;
+  hipLaunchKernelGGL(filter_count_kernel, dim3(n_blk), dim3(256), 0, st, d_words.p, blk_cnt);
   hipLaunchKernelGGL(filter_scan_kernel, dim3(1), dim3(256), 0, st, blk_cnt, n_blk, blk_off);
-  hipLaunchKernelGGL(filter_emit_kernel, dim3(n_blk), dim3(256), 0, st, d_words, blk_cnt, blk_off, d_list);
+  hipLaunchKernelGGL(filter_emit_kernel, dim3(n_blk), dim3(256), 0, st, d_words.p, blk_cnt, blk_off, d_list.p);
   return hipGetLastError();
 }
 
@@ -168,12 +181,7 @@ int compact_plan(CompactScratch& s, const uint32_t* keep_words, long long n_rows
     }
   }
   if (s.n_keep == n_rows || s.n_keep == s.first_hole) return VRAG_OK;   // nothing is cleared, or nothing behind the first hole stays
-  const int n_blk = (int)(s.h_words.size() / FWORDS);
-  HIP_TRY(s.d_words.grow(s.h_words.size()));
-  HIP_TRY(s.d_blk.grow((size_t)2 * n_blk + 1));
-  HIP_TRY(s.d_list.grow((size_t)s.n_keep));
-  HIP_TRY(hipMemcpyAsync(s.d_words.p, s.h_words.data(), s.h_words.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-  HIP_TRY(bitmap_row_list(s.d_words.p, n_blk, s.d_blk.p, s.d_list.p, st));
+  HIP_TRY(s.list.build(s.h_words, s.n_keep, st));
   return VRAG_OK;
 }
 
@@ -186,9 +194,28 @@ int compact_rows(CompactScratch& s, void* base, size_t row_bytes, long long n_sr
   char* rows = reinterpret_cast<char*>(base);
   for (long long j = s.first_hole; j < j_end; j += wave_rows) {
     const long long n = std::min(wave_rows, j_end - j);
-    HIP_TRY(move_rows_any(s.bounce.p, rows, s.d_list.p + j, n, row_bytes, st));
+    HIP_TRY(move_rows_any(s.bounce.p, rows, s.list.rows() + j, n, row_bytes, st));
     HIP_TRY(move_rows_any(rows + (size_t)j * row_bytes, s.bounce.p, nullptr, n, row_bytes, st));
   }
+  return VRAG_OK;
+}
+
+int compact_arrays(CompactScratch& s, int device, hipStream_t st, const uint32_t* keep_words, int64_t n_keep, int64_t* size,
+                   int64_t* new_size, std::initializer_list<CompactArray> arrays, bool* dropped) {
+  ARG_CHECK(n_keep >= 0 && (keep_words || n_keep == 0), "bad row bitmap (null words or a negative length)");
+  ARG_CHECK(n_keep == *size, "the bitmap covers %lld rows, the index holds %lld", (long long)n_keep, (long long)*size);
+  *new_size = *size;
+  if (n_keep == 0) return VRAG_OK;
+  HIP_TRY(hipSetDevice(device));
+  int rc;
+  if ((rc = compact_plan(s, keep_words, n_keep, st))) return rc;
+  if (s.n_keep == n_keep) return VRAG_OK;   // nothing to drop: no launch
+  HIP_TRY(hipDeviceSynchronize());
+  for (const CompactArray& a : arrays)
+    if (a.base && (rc = compact_rows(s, a.base, a.row_bytes, n_keep, st))) return rc;
+  HIP_TRY(hipStreamSynchronize(st));   // the new size is published once every row stands where it belongs
+  *size = *new_size = s.n_keep;
+  if (dropped) *dropped = true;
   return VRAG_OK;
 }
 

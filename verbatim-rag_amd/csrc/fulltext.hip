@@ -14,8 +14,8 @@
 //                    (vrag_text_index_set_corpus_stats): kd_kernel then reads that pair instead of the shard's own.
 //   search           ft_lookup_kernel (binary search of the query keys in every segment), ft_score_kernel (one workgroup per
 //                    (query, 4096 rows): LDS accumulators, term after term with a barrier between terms, then the block's
-//                    hits sorted in LDS), the per-query merge of csrc/topk.hip; k > 64 as exact pages of 64;
-//                    ft_export_kernel leaves one page as (score, global row) lists in device memory for the cross-GPU exchange.
+//                    hits sorted in LDS), the per-query merge of csrc/topk.hip; k > 64 as exact pages of 64; its export
+//                    (launch_topk_export) leaves one page as (score, global row) lists in device memory for the cross-GPU exchange.
 // Integer work and fp32 scores without contraction (#pragma clang fp contract(off) below): the oracle restates them bit for bit.
 #include "../../include/vrag_amd.h"
 
@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "host_util.h"
+#include "topk_kernels.h"
 #include "utf8_text.h"
 
 // Every fp32 operation of this file is rounded on its own: no a * b + c is fused into an FMA (HIP's default is
@@ -36,7 +37,6 @@
 #pragma clang fp contract(off)
 
 namespace vrag {
-hipError_t launch_topk_merge(const u64* cand, int n_wg, int nq, int k, u64* out, hipStream_t st);   // csrc/topk.hip
 
 namespace uw {
 #define UNICODE_WORD_STORAGE static __device__ const
@@ -531,23 +531,6 @@ __global__ void ft_bound_kernel(const u64* __restrict__ page, int nq, int kk, u6
   if (q < nq) bound[q] = page[(size_t)q * kk + kk - 1];
 }
 
-// One page of merged keys as device-resident lists (what a rank contributes to the cross-GPU exchange): fp32 score bits and
-// id = row_map[row] (the caller's local row -> global row table; a row at or beyond n_map is reported as missing) or
-// id_base + row without a table; missing hits -1 / -inf.
-__global__ void ft_export_kernel(const u64* __restrict__ keys, long long n, const long long* __restrict__ row_map, long long n_map,
-                                 long long id_base, float* __restrict__ out_scores, long long* __restrict__ out_ids) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const u64 key = keys[i];
-  long long id = -1ll;
-  if (key != 0ull) {
-    const long long row = (long long)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFu));
-    id = row_map ? (row < n_map ? row_map[row] : -1ll) : id_base + row;
-  }
-  out_scores[i] = id < 0 ? -INFINITY : unorderable((unsigned)(key >> 32));
-  out_ids[i] = id;
-}
-
 }  // namespace vrag
 
 namespace vrag {
@@ -1008,10 +991,7 @@ int vrag_text_tokenize(const uint8_t* text, const int64_t* doc_off, int32_t n_do
   ARG_CHECK(counts && n_tokens && cap >= 0 && (keys || cap == 0), "vrag_text_tokenize: bad arguments");
   int rc = check_docs(text, doc_off, n_docs);
   if (rc != VRAG_OK) return rc;
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   HIP_TRY(hipSetDevice(device));
   hipStream_t st = nullptr;
   HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -1039,10 +1019,7 @@ int vrag_text_index_create(float k1, float b, int32_t device, vrag_text_index** 
   ARG_CHECK(out, "vrag_text_index_create: null out");
   *out = nullptr;
   ARG_CHECK(k1 >= 0.f && b >= 0.f && b <= 1.f, "vrag_text_index_create: need k1 >= 0 and 0 <= b <= 1 (got %g, %g)", k1, b);
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   HIP_TRY(hipSetDevice(device));
   auto* ix = new vrag_text_index();
   ix->device = device;
@@ -1204,10 +1181,7 @@ int vrag_text_index_search(vrag_text_index* ix, const int64_t* q_indptr, const u
   int rc = check_queries("vrag_text_index_search", q_indptr, keys, weights, nq);
   if (rc != VRAG_OK) return rc;
   const int64_t n_terms = nq ? q_indptr[nq] : 0;
-  for (int64_t i = 0; i < (int64_t)nq * k; ++i) {
-    scores[i] = -INFINITY;
-    ids[i] = -1;
-  }
+  fill_no_hits(scores, ids, (size_t)nq * k);
   if (nq == 0) return VRAG_OK;
   std::lock_guard<std::mutex> lock(ix->mu);
   ARG_CHECK(!allow || allow_rows >= 0, "vrag_text_index_search: negative allow_rows");
@@ -1228,8 +1202,7 @@ int vrag_text_index_search(vrag_text_index* ix, const int64_t* q_indptr, const u
     for (int32_t i = 0; i < k; ++i) {
       const u64 key = h[((size_t)(i / 64) * nq + q) * kk + i % 64];
       if (!key) break;
-      scores[(size_t)q * k + i] = unorderable((unsigned)(key >> 32));
-      ids[(size_t)q * k + i] = (int64_t)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFu));
+      decode_key(key, &scores[(size_t)q * k + i], &ids[(size_t)q * k + i]);
     }
   return VRAG_OK;
 }
@@ -1263,12 +1236,8 @@ int vrag_text_index_search_device(vrag_text_index* ix, const int64_t* q_indptr, 
     HIP_TRY(hipStreamSynchronize(up));
     if ((rc = search_launch(ix, nq, n_terms, k, d_allow, allow_n, st)) != VRAG_OK) return rc;
   }
-  hipLaunchKernelGGL(ft_export_kernel, dim3(grid_of(n, 256)), dim3(256), 0, st, ix->page.as<u64>(), n,
-                     reinterpret_cast<const long long*>(row_map), (long long)n_map, (long long)id_base, out_scores,
-                     reinterpret_cast<long long*>(out_ids));
-  HIP_TRY(hipGetLastError());
-  if (!ix->lists_done) HIP_TRY(hipEventCreateWithFlags(&ix->lists_done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(ix->lists_done, st));
+  HIP_TRY(launch_topk_export(ix->page.as<u64>(), n, row_map, n_map, id_base, out_scores, out_ids, st));
+  HIP_TRY(record_event(ix->lists_done, st));
   return VRAG_OK;
 }
 

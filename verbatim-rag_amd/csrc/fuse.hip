@@ -163,10 +163,7 @@ extern "C" int vrag_rrf_fuse(const int64_t* rows, const double* gains, int32_t n
             FUSE_MAX_L, nq, l_total);
   ARG_CHECK(top_k >= 1 && top_k <= l_total, "vrag_rrf_fuse: top_k must be in [1, l_total = %d] (got %d)", l_total, top_k);
   ARG_CHECK(device >= 0, "vrag_rrf_fuse: negative device");
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t n_in = (size_t)nq * l_total, n_out = (size_t)nq * top_k;
   if (on_device) {

@@ -192,7 +192,7 @@ struct vrag_group_column {
   std::mutex mu;
   // scratch of vrag_dense_index_search_grouped (grown on demand)
   std::vector<unsigned> h_allow;
-  DevArray<unsigned> d_allow, d_blk, d_list;
+  RowList allow_rows;     // the ascending list of the rows that pass the caller's bitmap
   DevArray<float> d_q, d_scores;
   DevArray<u64> d_levels, d_cand, d_sel;
   DevArray<long long> d_ids;
@@ -205,10 +205,7 @@ int vrag_group_column_create(int32_t device, vrag_group_column** out) {
   ARG_CHECK(out, "null argument");
   *out = nullptr;
   ARG_CHECK(device >= 0, "vrag_group_column_create: negative device");
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   HIP_TRY(hipSetDevice(device));
   auto* c = new vrag_group_column();
   c->device = device;
@@ -283,7 +280,7 @@ int vrag_dense_index_search_grouped(vrag_dense_index* ix, const float* queries, 
             group_size, n_codes, GROUPED_SCRATCH_BYTES >> 20);
   const size_t n_out = (size_t)nq * n_groups;
   auto no_hits = [&]() {
-    for (size_t i = 0; i < n_out * group_size; ++i) scores[i] = -INFINITY, ids[i] = -1;
+    fill_no_hits(scores, ids, n_out * group_size);
     for (size_t i = 0; i < n_out; ++i) groups[i] = -1;
     return VRAG_OK;
   };
@@ -309,14 +306,9 @@ int vrag_dense_index_search_grouped(vrag_dense_index* ix, const float* queries, 
   const unsigned* list = nullptr;
   const unsigned* list_n = nullptr;
   if (allow) {
-    const int n_blk = (int)(column->h_allow.size() / FWORDS);
-    HIP_TRY(column->d_allow.grow(column->h_allow.size()));
-    HIP_TRY(column->d_blk.grow((size_t)2 * n_blk + 1));
-    HIP_TRY(column->d_list.grow((size_t)n_pass));
-    HIP_TRY(hipMemcpyAsync(column->d_allow.p, column->h_allow.data(), column->h_allow.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-    HIP_TRY(bitmap_row_list(column->d_allow.p, n_blk, column->d_blk.p, column->d_list.p, st));
-    list = column->d_list.p;
-    list_n = column->d_blk.p + 2 * n_blk;   // the last of the [n_blk + 1] offsets behind the [n_blk] counts: the list's length
+    HIP_TRY(column->allow_rows.build(column->h_allow, n_pass, st));
+    list = column->allow_rows.rows();
+    list_n = column->allow_rows.count();
   }
   for (int q0 = 0; q0 < nq; q0 += nqs_max) {
     const int nqs = std::min(nqs_max, nq - q0);

@@ -31,8 +31,25 @@ void set_error(const char* fmt, ...);   // csrc/capi.hip: the message vrag_last_
       return VRAG_ERR_INVALID;       \
     }                                \
   } while (0)
+// The entry points that take a device index: one that is not visible is refused (a negative index is each caller's own check).
+#define DEVICE_CHECK(device)                                                         \
+  do {                                                                               \
+    if (vrag_device_count() <= (device)) {                                           \
+      vrag::set_error("no HIP device %d visible (no CPU fallback)", (int)(device));  \
+      return VRAG_ERR_NO_DEVICE;                                                     \
+    }                                                                                \
+  } while (0)
 
 namespace vrag {
+
+// Records `ev` on `st`; the event (no timing) is created on its first use.  The handles' upload_done / lists_done events.
+inline hipError_t record_event(hipEvent_t& ev, hipStream_t st) {
+  if (!ev) {
+    const hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess) return e;
+  }
+  return hipEventRecord(ev, st);
+}
 
 // Device array of T owned by its holder (scratch of an index handle, weights and workspace of an encoder): freed with it.
 template <typename T>

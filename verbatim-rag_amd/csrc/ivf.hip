@@ -748,12 +748,10 @@ int vrag_ivf_index_search(vrag_ivf_index* ix, const float* queries, int32_t nq, 
     HIP_TRY(hipGetLastError());
     HIP_TRY(launch_topk_merge(ix->d_cand.p, np * split, nqs, k, ix->d_out.p + (size_t)q0 * k, st));
   }
-  std::vector<u64> keys((size_t)nq * k);
+  // the scanned-row counts ride on the one stream sync of read_lists: their copy is enqueued ahead of it
   std::vector<unsigned long long> scanned(scanned_rows ? (size_t)nq : 0);
-  HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_out.p, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
   if (scanned_rows) HIP_TRY(hipMemcpyAsync(scanned.data(), ix->d_scanned.p, scanned.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  decode_keys(keys, nq, k, 0, nullptr, scores, ids);
+  if (const int rc = read_lists(ix->d_out.p, nq, k, st, scores, ids)) return rc;
   for (size_t q = 0; q < scanned.size(); ++q) scanned_rows[q] = (int64_t)scanned[q];
   return VRAG_OK;
 }

@@ -89,10 +89,7 @@ int vrag_row_filter_create(int32_t device, vrag_row_filter** out) {
   ARG_CHECK(out, "null argument");
   *out = nullptr;
   ARG_CHECK(device >= 0, "vrag_row_filter_create: negative device");
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   HIP_TRY(hipSetDevice(device));
   auto* f = new vrag_row_filter();
   f->device = device;

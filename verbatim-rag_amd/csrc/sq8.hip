@@ -346,13 +346,6 @@ hipError_t sq8_quantize(vrag_sq8_index* ix, const float* d_rows, long long n, lo
   return hipGetLastError();
 }
 
-void sq8_no_hits(float* scores, int64_t* ids, size_t n) {
-  for (size_t i = 0; i < n; ++i) {
-    scores[i] = -INFINITY;
-    ids[i] = -1;
-  }
-}
-
 // The device form of an append, under the lock: `n` fp32 rows at the device address `d_rows` are quantised behind the rows in
 // place on `st`; the size is published after the stream has drained, so a search never sees a row that is not written yet.
 int sq8_append(vrag_sq8_index* ix, const float* d_rows, int64_t n, hipStream_t st) {
@@ -380,7 +373,6 @@ int sq8_search(vrag_sq8_index* ix, const float* queries, int nq, int k, long lon
   HIP_TRY(ix->d_qs.grow((size_t)nq));
   HIP_TRY(ix->d_cand.grow((size_t)n_wg * slice * kk));
   HIP_TRY(ix->d_out.grow((size_t)nq * kk));
-  HIP_TRY(ix->d_bound.grow((size_t)nq));
   const unsigned* d_allow = nullptr;
   if (filtered) {
     HIP_TRY(ix->d_allow.grow(ix->h_allow.size()));
@@ -391,7 +383,7 @@ int sq8_search(vrag_sq8_index* ix, const float* queries, int nq, int k, long lon
   HIP_TRY(hipMemcpyAsync(ix->d_q.p, queries, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, st));
   HIP_TRY(launch_sq8_query(ix->d_q.p, nq, dim, stride, ix->d_qc.p, ix->d_qs.p, st));
   // one page of kk keys per query into d_out [nq][kk]
-  auto run_page = [&](const u64* bound) -> int {
+  return search_lists(nq, k, ix->d_bound, ix->d_out, st, [&](const u64* bound) -> int {
     for (int q0 = 0; q0 < nq; q0 += SQ8_SLICE) {
       const int nqs = std::min(SQ8_SLICE, nq - q0);
       const signed char* qc = ix->d_qc.p + (size_t)q0 * stride;
@@ -407,33 +399,7 @@ int sq8_search(vrag_sq8_index* ix, const float* queries, int nq, int k, long lon
       HIP_TRY(launch_topk_merge(ix->d_cand.p, n_wg, nqs, kk, ix->d_out.p + (size_t)q0 * kk, st));
     }
     return VRAG_OK;
-  };
-  int rc;
-  std::vector<u64> all((size_t)nq * k, 0ull);
-  if (k <= KMAX) {
-    if ((rc = run_page(nullptr))) return rc;
-    HIP_TRY(hipMemcpyAsync(all.data(), ix->d_out.p, all.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-  } else {
-    // pages of KMAX: the last key of a full page is the next page's exclusive bound (0 = exhausted: nothing passes)
-    std::vector<u64> bound((size_t)nq, ~0ull), page((size_t)nq * KMAX);
-    for (int k0 = 0; k0 < k; k0 += KMAX) {
-      HIP_TRY(hipMemcpyAsync(ix->d_bound.p, bound.data(), (size_t)nq * sizeof(u64), hipMemcpyHostToDevice, st));
-      if ((rc = run_page(ix->d_bound.p))) return rc;
-      HIP_TRY(hipMemcpyAsync(page.data(), ix->d_out.p, page.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      bool more = false;
-      const int take = std::min(KMAX, k - k0);
-      for (int q = 0; q < nq; ++q) {
-        for (int j = 0; j < take; ++j) all[(size_t)q * k + k0 + j] = page[(size_t)q * KMAX + j];
-        bound[q] = page[(size_t)q * KMAX + KMAX - 1];
-        more = more || bound[q] != 0ull;
-      }
-      if (!more) break;
-    }
-  }
-  decode_keys(all, nq, k, 0, nullptr, scores, ids);
-  return VRAG_OK;
+  }, scores, ids);
 }
 
 }  // namespace
@@ -460,10 +426,7 @@ int vrag_sq8_index_create(int32_t dim, int64_t capacity, int32_t device, vrag_sq
   ARG_CHECK(dim >= 1 && dim <= SQ8_DIM_MAX, "dim must be in [1, %d] for an sq8 index (got %d)", SQ8_DIM_MAX, dim);
   ARG_CHECK(capacity > 0 && capacity < 0xFFFFFFFFll, "capacity out of range");
   ARG_CHECK(device >= 0, "device must not be negative");
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   HIP_TRY(hipSetDevice(device));
   auto* ix = new vrag_sq8_index();
   ix->dim = dim;
@@ -540,23 +503,9 @@ int vrag_sq8_index_read(vrag_sq8_index* ix, int64_t first_row, int64_t n, int8_t
 // scales.  Every search of this handle returns host lists and has drained its stream before it let go of the lock.
 int vrag_sq8_index_compact(vrag_sq8_index* ix, const uint32_t* keep_words, int64_t n_keep, int64_t* new_size) {
   ARG_CHECK(ix && new_size, "null argument");
-  ARG_CHECK(n_keep >= 0 && (keep_words || n_keep == 0), "bad row bitmap (null words or a negative length)");
   std::lock_guard<std::mutex> lk(ix->mu);
-  ARG_CHECK(n_keep == ix->size, "the bitmap covers %lld rows, the index holds %lld", (long long)n_keep, (long long)ix->size);
-  *new_size = ix->size;
-  if (n_keep == 0) return VRAG_OK;
-  HIP_TRY(hipSetDevice(ix->device));
-  hipStream_t st = ix->stream;
-  int rc;
-  if ((rc = compact_plan(ix->compact, keep_words, n_keep, st))) return rc;
-  if (ix->compact.n_keep == n_keep) return VRAG_OK;   // nothing to drop: no launch
-  HIP_TRY(hipDeviceSynchronize());   // a search on a caller's stream has returned, so it has drained; this is the belt to that
-  if ((rc = compact_rows(ix->compact, ix->codes.p, (size_t)ix->stride, n_keep, st))) return rc;
-  if ((rc = compact_rows(ix->compact, ix->scales.p, sizeof(float), n_keep, st))) return rc;
-  HIP_TRY(hipStreamSynchronize(st));   // the new size is published once every row stands where it belongs
-  ix->size = ix->compact.n_keep;
-  *new_size = ix->size;
-  return VRAG_OK;
+  return compact_arrays(ix->compact, ix->device, ix->stream, keep_words, n_keep, &ix->size, new_size,
+                        {{ix->codes.p, (size_t)ix->stride}, {ix->scales.p, sizeof(float)}});
 }
 
 int vrag_sq8_index_set_route(vrag_sq8_index* ix, int32_t route) {
@@ -572,7 +521,7 @@ int vrag_sq8_index_search(vrag_sq8_index* ix, const float* queries, int32_t nq, 
   ARG_CHECK(k >= 1 && k <= 1024, "k must be in [1, 1024] (got %d)", k);
   std::lock_guard<std::mutex> lk(ix->mu);
   if (ix->size == 0) {
-    sq8_no_hits(scores, ids, (size_t)nq * k);
+    fill_no_hits(scores, ids, (size_t)nq * k);
     return VRAG_OK;
   }
   HIP_TRY(hipSetDevice(ix->device));
@@ -587,15 +536,9 @@ int vrag_sq8_index_search_filtered(vrag_sq8_index* ix, const float* queries, int
   ARG_CHECK(n_allow >= 0 && (allow || n_allow == 0), "bad row bitmap (null words or a negative length)");
   std::lock_guard<std::mutex> lk(ix->mu);
   const long long n_rows = std::min<long long>(n_allow, ix->size);   // rows appended after the mask was built are not in it
-  long long n_pass = 0;
-  if (n_rows > 0) {
-    const size_t n_words = (size_t)((n_rows + 31) / 32);
-    ix->h_allow.assign(allow, allow + n_words);
-    if (n_rows % 32) ix->h_allow[n_words - 1] &= (1u << (n_rows % 32)) - 1u;
-    for (unsigned w : ix->h_allow) n_pass += __builtin_popcount(w);
-  }
+  const long long n_pass = n_rows > 0 ? stage_bitmap(ix->h_allow, allow, n_rows, 1) : 0;
   if (n_pass == 0) {   // nothing passes: no launch
-    sq8_no_hits(scores, ids, (size_t)nq * k);
+    fill_no_hits(scores, ids, (size_t)nq * k);
     return VRAG_OK;
   }
   HIP_TRY(hipSetDevice(ix->device));

@@ -88,10 +88,7 @@ extern "C" int vrag_split_sentences(const uint8_t* text, const int64_t* doc_off,
     set_error("vrag_split_sentences: bad arguments");
     return VRAG_ERR_INVALID;
   }
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   for (int d = 0; d < n_docs; ++d)
     if (doc_off[d + 1] < doc_off[d] || doc_off[d + 1] - doc_off[d] > 0x7fffffffll) {
       set_error("vrag_split_sentences: document %d has a negative or > 2 GiB length", d);

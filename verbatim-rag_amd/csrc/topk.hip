@@ -2243,6 +2243,14 @@ __global__ void topk_export_keys_kernel(const u64* __restrict__ keys, long long 
   out_ids[i] = id;
 }
 
+hipError_t launch_topk_export(const u64* keys, long long n, const int64_t* row_map, int64_t n_map, int64_t id_base, float* out_scores,
+                              int64_t* out_ids, hipStream_t st) {
+  hipLaunchKernelGGL(topk_export_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, keys, n,
+                     reinterpret_cast<const long long*>(row_map), (long long)n_map, (long long)id_base, out_scores,
+                     reinterpret_cast<long long*>(out_ids));
+  return hipGetLastError();
+}
+
 __global__ void topk_fill_empty_kernel(float* __restrict__ scores, long long* __restrict__ ids, long long n) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) {
@@ -2257,7 +2265,7 @@ __global__ void topk_fill_empty_kernel(float* __restrict__ scores, long long* __
 // reads a bitmap.  Dense: the bitmap is compacted into the ascending list of passing rows (popcount + prefix scan, no atomic
 // appends: the list is the same on every run), then the exact chains run over that list only -- cost proportional to the
 // passing rows, not to the shard.  Sparse: the single-query SELL walk with the top-k insertion gated by the document's bit.
-// The bitmap-to-list kernels are csrc/compact.hip's (`bitmap_row_list`): the index compaction builds the same list.
+// The bitmap-to-list kernels are csrc/compact.hip's (`RowList`): the index compaction builds the same list.
 
 // Exact keys of a row list: FROWS rows x FQT queries per workgroup step.  As in prefilter_rescore_list_kernel what costs is
 // fetching the scattered rows: all 256 threads stage FCH columns of the FROWS rows and of the workgroup's queries through LDS in
@@ -2461,10 +2469,9 @@ struct vrag_dense_index {
   hipEvent_t upload_done = nullptr;   // recorded behind the query upload: the host buffer is free once it has passed
   hipEvent_t lists_done = nullptr;    // recorded behind a device-resident search: the next search (any stream) waits for it before reusing the scratch
   bool warmed = false;                // dense_warm_query_path has run (first add that brought the shard to >= 4096 rows)
-  // vrag_dense_index_search_filtered: the caller's bitmap (host staging, device copy), the compaction's per-workgroup counts and
-  // offsets ([n] counts, then [n + 1] offsets: the last one is the list's length) and the ascending list of passing rows
+  // vrag_dense_index_search_filtered: the caller's bitmap (host staging) and the ascending list of passing rows
   std::vector<unsigned> h_allow;
-  DevArray<unsigned> d_fallow, d_fblk, d_flist;
+  RowList allow_rows;
   // vrag_dense_index_compact: its bitmap, row list and bounce buffer; and whether the resident queries and scratch of the last
   // search still describe this index's rows (a compaction renumbers them: run_resident is refused until the next search)
   CompactScratch compact;
@@ -2533,33 +2540,7 @@ __global__ void cvt_f32_bf16_flat(const float* __restrict__ src, bf16_t* __restr
     dst[i] = (bf16_t)src[i];
 }
 
-// decode_keys: topk_kernels.h
-
-// k > KMAX: ceil(k / KMAX) passes of KMAX; `run_page(bound)` leaves the merged page keys [nq][KMAX] in d_out.
-// After each page the last key of a full page becomes that query's exclusive bound (0 = exhausted: nothing passes).
-template <typename RunPage>
-int paged_search(int nq, int k, DevArray<u64>& d_bound, const DevArray<u64>& d_out, hipStream_t st, RunPage run_page,
-                 float* scores, int64_t* ids) {
-  int rc;
-  HIP_TRY(d_bound.grow((size_t)nq));
-  std::vector<u64> bound((size_t)nq, ~0ull), page((size_t)nq * KMAX), all((size_t)nq * k, 0ull);
-  for (int k0 = 0; k0 < k; k0 += KMAX) {
-    HIP_TRY(hipMemcpyAsync(d_bound.p, bound.data(), (size_t)nq * sizeof(u64), hipMemcpyHostToDevice, st));
-    if ((rc = run_page(d_bound.p))) return rc;
-    HIP_TRY(hipMemcpyAsync(page.data(), d_out.p, page.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    bool more = false;
-    for (int q = 0; q < nq; ++q) {
-      const int take = std::min(KMAX, k - k0);
-      for (int j = 0; j < take; ++j) all[(size_t)q * k + k0 + j] = page[(size_t)q * KMAX + j];
-      bound[q] = page[(size_t)q * KMAX + KMAX - 1];   // 0 when the page was not full
-      more = more || bound[q] != 0ull;
-    }
-    if (!more) break;
-  }
-  decode_keys(all, nq, k, 0, nullptr, scores, ids);
-  return VRAG_OK;
-}
+// The result path (fill_no_hits, decode_keys, read_lists, paged_search, search_lists): topk_kernels.h
 
 __global__ void tiled_init_kernel(int nq, u64* __restrict__ thr_key, float* __restrict__ thr_score, unsigned* __restrict__ cnt_ovf) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2820,8 +2801,7 @@ int dense_search_enqueue(vrag_dense_index* ix, const float* queries, int nq, int
   const size_t lds = (size_t)DQT * ix->dim * sizeof(float) + (size_t)16 * DQT * k * sizeof(u64);
   ARG_CHECK(lds <= 160 * 1024, "dim/k too large for the LDS budget");
   HIP_TRY(hipMemcpyAsync(ix->d_q.p, queries, (size_t)nq * ix->dim * sizeof(float), hipMemcpyHostToDevice, st));
-  if (!ix->upload_done) HIP_TRY(hipEventCreateWithFlags(&ix->upload_done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(ix->upload_done, st));
+  HIP_TRY(record_event(ix->upload_done, st));
   ix->resident_split = split;   // for whatever kernel family serves these queries now or in a later run_resident with another (nq, k)
   HIP_TRY(hipEventSynchronize(ix->upload_done));
   switch (route) {
@@ -2853,10 +2833,7 @@ int vrag_dense_index_create(int32_t dim, int64_t capacity, int32_t dtype, int32_
   ARG_CHECK(dtype >= 0 && dtype <= 2, "dtype: 0 = bf16 rows, 1 = fp32 rows, 2 = fp32 rows + bf16 prefilter image");
   const bool prefilter = dtype == 2;
   if (prefilter) dtype = 1;   // the rows, the scores and the order are the fp32 index's; the image only narrows the scan
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   HIP_TRY(hipSetDevice(device));
   auto* ix = new vrag_dense_index();
   ix->dim = dim;
@@ -3173,8 +3150,7 @@ static int prefilter_onepass_enqueue(vrag_dense_index* ix, const float* queries,
   std::memcpy(up, queries, (size_t)nq * dim * sizeof(float));
   for (int q = 0; q < nq; ++q) up[(size_t)nq * dim + q] = prefilter_eps(ix, queries + (size_t)q * dim, /*rounded_query=*/false);   // fp32 query against the image
   HIP_TRY(hipMemcpyAsync(ix->d_q.p, up, ((size_t)nq * dim + nq) * sizeof(float), hipMemcpyHostToDevice, st));
-  if (!ix->upload_done) HIP_TRY(hipEventCreateWithFlags(&ix->upload_done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(ix->upload_done, st));
+  HIP_TRY(record_event(ix->upload_done, st));
   ix->resident_split = 0;
   return prefilter_single_enqueue(ix, ix->d_q.p, ix->d_q.p + (size_t)nq * dim, nq, k, ix->d_pf_out.p, prefilter_onepass_flags(ix, nq, k), st);
 }
@@ -3197,10 +3173,7 @@ int vrag_dense_index_search(vrag_dense_index* ix, const float* queries, int32_t 
               "dim too large for the LDS budget");
     HIP_TRY(hipMemcpyAsync(ix->d_q.p, queries, (size_t)nq * ix->dim * sizeof(float), hipMemcpyHostToDevice, st));
     if (ix->size == 0) {
-      for (size_t i = 0; i < (size_t)nq * k; ++i) {
-        scores[i] = -INFINITY;
-        ids[i] = -1;
-      }
+      fill_no_hits(scores, ids, (size_t)nq * k);
       return VRAG_OK;
     }
     return paged_search(nq, k, ix->d_bound, ix->d_out, st, [&](const u64* bound) -> int {
@@ -3274,13 +3247,6 @@ int vrag_dense_index_search(vrag_dense_index* ix, const float* queries, int32_t 
   return VRAG_OK;
 }
 
-static void fill_no_hits(float* scores, int64_t* ids, size_t n) {
-  for (size_t i = 0; i < n; ++i) {
-    scores[i] = -INFINITY;
-    ids[i] = -1;
-  }
-}
-
 constexpr int FILTER_WGS = 2048;   // most workgroups of the scoring pass per query tile (256 CUs x 3 resident, a few rounds)
 int vrag_dense_index_search_filtered(vrag_dense_index* ix, const float* queries, int32_t nq, int32_t k, const uint32_t* allow,
                                      int64_t n_allow, float* scores, int64_t* ids, void* stream) {
@@ -3299,42 +3265,33 @@ int vrag_dense_index_search_filtered(vrag_dense_index* ix, const float* queries,
     return VRAG_OK;
   }
   const int dim = ix->dim, kk = std::min<int>(k, KMAX);
-  const int n_blk = (int)(ix->h_allow.size() / FWORDS);
   const int n_wg = (int)std::min<long long>((n_pass + FROWS - 1) / FROWS, FILTER_WGS);
-  HIP_TRY(ix->d_fallow.grow(ix->h_allow.size()));
-  HIP_TRY(ix->d_fblk.grow((size_t)2 * n_blk + 1));
-  HIP_TRY(ix->d_flist.grow((size_t)n_pass));
   HIP_TRY(ix->d_q.grow((size_t)nq * dim));
   HIP_TRY(ix->d_cand.grow((size_t)n_wg * nq * kk));
   HIP_TRY(ix->d_out.grow((size_t)nq * kk + nq));
-  HIP_TRY(hipMemcpyAsync(ix->d_fallow.p, ix->h_allow.data(), ix->h_allow.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
+  HIP_TRY(ix->allow_rows.reserve(ix->h_allow, n_pass));   // every allocation in front of the first enqueue
   HIP_TRY(hipMemcpyAsync(ix->d_q.p, queries, (size_t)nq * dim * sizeof(float), hipMemcpyHostToDevice, st));
-  if (!ix->upload_done) HIP_TRY(hipEventCreateWithFlags(&ix->upload_done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(ix->upload_done, st));
+  HIP_TRY(record_event(ix->upload_done, st));
   ix->resident_split = 0;   // d_q holds these queries now, as plain fp32 rows
-  unsigned* blk_off = ix->d_fblk.p + n_blk;   // [n_blk + 1] offsets behind the [n_blk] counts
-  HIP_TRY(bitmap_row_list(ix->d_fallow.p, n_blk, ix->d_fblk.p, ix->d_flist.p, st));
-  HIP_TRY(hipEventSynchronize(ix->upload_done));   // the caller's queries and the staged bitmap have been consumed
-  auto run = [&](const u64* bound) -> int {
+  // the bitmap upload and the list's launches go behind the event: the host waits for the caller's queries only.  The staged
+  // bitmap is the handle's own vector: the lock keeps it until the stream sync that ends this call, on the error path too
+  const hipError_t listed = ix->allow_rows.build(ix->h_allow, n_pass, st);
+  HIP_TRY(hipEventSynchronize(ix->upload_done));   // the caller's queries have been consumed, whatever became of the list
+  const int rc = listed != hipSuccess ? VRAG_OK : search_lists(nq, k, ix->d_bound, ix->d_out, st, [&](const u64* bound) -> int {
     const dim3 grid(n_wg, (nq + FQT - 1) / FQT);
     if (ix->dtype == 1)   // dtype 2 too: the chains run over the fp32 rows, never over the bf16 image
-      hipLaunchKernelGGL(filtered_score_kernel<true>, grid, dim3(256), 0, st, ix->d_flist.p, blk_off + n_blk, ix->rows.p, dim, ix->d_q.p,
-                         nq, kk, ix->d_cand.p, bound);
+      hipLaunchKernelGGL(filtered_score_kernel<true>, grid, dim3(256), 0, st, ix->allow_rows.rows(), ix->allow_rows.count(), ix->rows.p, dim,
+                         ix->d_q.p, nq, kk, ix->d_cand.p, bound);
     else
-      hipLaunchKernelGGL(filtered_score_kernel<false>, grid, dim3(256), 0, st, ix->d_flist.p, blk_off + n_blk, ix->rows.p, dim, ix->d_q.p,
-                         nq, kk, ix->d_cand.p, bound);
+      hipLaunchKernelGGL(filtered_score_kernel<false>, grid, dim3(256), 0, st, ix->allow_rows.rows(), ix->allow_rows.count(), ix->rows.p, dim,
+                         ix->d_q.p, nq, kk, ix->d_cand.p, bound);
     HIP_TRY(hipGetLastError());
     HIP_TRY(launch_topk_merge(ix->d_cand.p, n_wg, nq, kk, ix->d_out.p, st));
     return VRAG_OK;
-  };
-  if (k > KMAX) return paged_search(nq, k, ix->d_bound, ix->d_out, st, run, scores, ids);
-  int rc;
-  if ((rc = run(nullptr))) return rc;
-  std::vector<u64> keys((size_t)nq * k);
-  HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_out.p, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  decode_keys(keys, nq, k, 0, nullptr, scores, ids);
-  return VRAG_OK;
+  }, scores, ids);
+  if (rc != VRAG_OK || listed != hipSuccess) (void)hipStreamSynchronize(st);   // a failed call has not drained the stream yet
+  HIP_TRY(listed);
+  return rc;
 }
 
 int vrag_dense_index_search_device(vrag_dense_index* ix, const float* queries, int32_t nq, int32_t k, const int64_t* row_map,
@@ -3352,7 +3309,6 @@ int vrag_dense_index_search_device(vrag_dense_index* ix, const float* queries, i
   const DenseRoute route = dense_plan(ix, nq, k, DenseCaller::Device, split);
   ARG_CHECK(route != DenseRoute::Paged, "k must be in [1, %d] for a device-resident search (got %d)", KMAX, k);
   int rc;
-  const long long n = (long long)nq * k;
   const u64* result = nullptr;
   if (route == DenseRoute::PrefilterBatch) {
     // nothing returns to the host: the gated rescan runs on the device
@@ -3370,12 +3326,8 @@ int vrag_dense_index_search_device(vrag_dense_index* ix, const float* queries, i
     if ((rc = dense_search_enqueue(ix, queries, nq, k, st, route, split))) return rc;
     result = ix->d_out.p;
   }
-  hipLaunchKernelGGL(topk_export_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, result, n,
-                     reinterpret_cast<const long long*>(row_map), (long long)n_map, (long long)id_base, out_scores,
-                     reinterpret_cast<long long*>(out_ids));
-  HIP_TRY(hipGetLastError());
-  if (!ix->lists_done) HIP_TRY(hipEventCreateWithFlags(&ix->lists_done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(ix->lists_done, st));
+  HIP_TRY(launch_topk_export(result, (long long)nq * k, row_map, n_map, id_base, out_scores, out_ids, st));
+  HIP_TRY(record_event(ix->lists_done, st));
   return VRAG_OK;
 }
 
@@ -3402,26 +3354,13 @@ int vrag_dense_index_run_resident(vrag_dense_index* ix, int32_t nq, int32_t k, v
 // rows that stay, and the searches' results do not depend on how tight they are.
 int vrag_dense_index_compact(vrag_dense_index* ix, const uint32_t* keep_words, int64_t n_keep, int64_t* new_size) {
   ARG_CHECK(ix && new_size, "null argument");
-  ARG_CHECK(n_keep >= 0 && (keep_words || n_keep == 0), "bad row bitmap (null words or a negative length)");
   std::lock_guard<std::mutex> lk(ix->mu);
-  ARG_CHECK(n_keep == ix->size, "the bitmap covers %lld rows, the index holds %lld", (long long)n_keep, (long long)ix->size);
-  *new_size = ix->size;
-  if (n_keep == 0) return VRAG_OK;
-  HIP_TRY(hipSetDevice(ix->device));
-  hipStream_t st = ix->stream;
-  int rc;
-  if ((rc = compact_plan(ix->compact, keep_words, n_keep, st))) return rc;
-  if (ix->compact.n_keep == n_keep) return VRAG_OK;   // nothing to drop: no launch
-  // searches that only enqueue (vrag_dense_index_search_device, _run_resident) may still be reading the rows on the caller's stream
-  HIP_TRY(hipDeviceSynchronize());
   const size_t esz = ix->dtype == 0 ? 2 : 4;
-  if ((rc = compact_rows(ix->compact, ix->rows.p, (size_t)ix->dim * esz, n_keep, st))) return rc;
-  if (ix->rows16.p && (rc = compact_rows(ix->compact, ix->rows16.p, (size_t)ix->dim * 2, n_keep, st))) return rc;
-  HIP_TRY(hipStreamSynchronize(st));   // the new size is published once every row stands where it belongs
-  ix->size = ix->compact.n_keep;
-  ix->resident_stale = true;
-  *new_size = ix->size;
-  return VRAG_OK;
+  bool dropped = false;
+  const int rc = compact_arrays(ix->compact, ix->device, ix->stream, keep_words, n_keep, &ix->size, new_size,
+                                {{ix->rows.p, (size_t)ix->dim * esz}, {ix->rows16.p, (size_t)ix->dim * 2}}, &dropped);
+  if (dropped) ix->resident_stale = true;
+  return rc;
 }
 
 int vrag_dense_index_read(vrag_dense_index* ix, int64_t first_row, int64_t n, float* out) {
@@ -3451,10 +3390,7 @@ int vrag_sparse_index_create(int32_t vocab, int64_t n_docs, const int64_t* indpt
   *out = nullptr;
   ARG_CHECK(vocab > 0 && vocab <= 65536, "vocab must be <= 65536 (u16 term ids), got %d", vocab);
   ARG_CHECK(n_docs < 0xFFFFFFFFll - 64, "too many documents");
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   HIP_TRY(hipSetDevice(device));
   const int64_t nnz = indptr[n_docs];
   ARG_CHECK(nnz == 0 || (indices && values), "null indices/values");
@@ -3728,7 +3664,6 @@ int vrag_sparse_index_search(vrag_sparse_index* ix, const int64_t* q_indptr, con
   if (ix->lists_done) HIP_TRY(hipStreamWaitEvent(st, ix->lists_done, 0));
   const int slices_per_wg = sparse_slices_per_wg(ix);
   const int n_wg = std::max(1, (ix->n_slices + slices_per_wg - 1) / slices_per_wg);
-  int rc;
   if (k > KMAX) {   // pages of KMAX on the single-query kernel
     for (int q = 0; q < nq; ++q)
       for (int64_t j = q_indptr[q]; j < q_indptr[q + 1]; ++j)
@@ -3746,12 +3681,8 @@ int vrag_sparse_index_search(vrag_sparse_index* ix, const int64_t* q_indptr, con
       return sparse_launch(ix, nq, KMAX, st, &nwg, bound);
     }, scores, ids);   // the first page's stream sync also keeps `qd` alive until its upload has been consumed
   }
-  if ((rc = sparse_search_enqueue(ix, q_indptr, q_indices, q_values, nq, k, st))) return rc;
-  std::vector<u64> keys((size_t)nq * k);
-  HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_out.p, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  decode_keys(keys, nq, k, 0, nullptr, scores, ids);
-  return VRAG_OK;
+  if (const int rc = sparse_search_enqueue(ix, q_indptr, q_indices, q_values, nq, k, st)) return rc;
+  return read_lists(ix->d_out.p, nq, k, st, scores, ids);
 }
 
 int vrag_sparse_index_search_filtered(vrag_sparse_index* ix, const int64_t* q_indptr, const int32_t* q_indices,
@@ -3781,18 +3712,17 @@ int vrag_sparse_index_search_filtered(vrag_sparse_index* ix, const int64_t* q_in
   const int kk = std::min<int>(k, KMAX);
   const int slices_per_wg = sparse_slices_per_wg(ix);
   const int n_wg = std::max(1, (ix->n_slices + slices_per_wg - 1) / slices_per_wg);
-  int rc;
   if (!ix->upload_done) HIP_TRY(hipEventCreateWithFlags(&ix->upload_done, hipEventDisableTiming));
   HIP_TRY(ix->d_fallow.grow(ix->h_allow.size()));
   HIP_TRY(ix->d_cand.grow((size_t)n_wg * nq * kk));
   HIP_TRY(ix->d_out.grow((size_t)nq * kk));
   HIP_TRY(hipMemcpyAsync(ix->d_fallow.p, ix->h_allow.data(), ix->h_allow.size() * sizeof(unsigned), hipMemcpyHostToDevice, st));
-  if ((rc = sparse_scatter_enqueue(ix, q_indptr, q_indices, q_values, nq, st))) return rc;   // its event covers the bitmap upload too
+  if (const int rc = sparse_scatter_enqueue(ix, q_indptr, q_indices, q_values, nq, st)) return rc;   // its event covers the bitmap upload too
   ix->last_multi = false;   // the resident queries are dense vectors now
   const bool ldsq = (size_t)ix->vocab * sizeof(float) + (size_t)16 * kk * sizeof(u64) <= 160 * 1024;
   const size_t lds = (size_t)16 * kk * sizeof(u64) + (ldsq ? (size_t)ix->vocab * sizeof(float) : 0);
   if (ldsq) HIP_TRY(set_max_dynamic_lds<&sparse_topk_filtered_kernel<true>>(160 * 1024));
-  auto run = [&](const u64* bound) -> int {
+  return search_lists(nq, k, ix->d_bound, ix->d_out, st, [&](const u64* bound) -> int {
     for (int q = 0; q < nq; ++q) {
       if (ldsq)
         hipLaunchKernelGGL((sparse_topk_filtered_kernel<true>), dim3(n_wg), dim3(1024), lds, st, ix->cols.p, ix->vals.p, ix->slice_off.p,
@@ -3806,14 +3736,7 @@ int vrag_sparse_index_search_filtered(vrag_sparse_index* ix, const int64_t* q_in
     }
     HIP_TRY(launch_topk_merge(ix->d_cand.p, n_wg, nq, kk, ix->d_out.p, st));
     return VRAG_OK;
-  };
-  if (k > KMAX) return paged_search(nq, k, ix->d_bound, ix->d_out, st, run, scores, ids);
-  if ((rc = run(nullptr))) return rc;
-  std::vector<u64> keys((size_t)nq * k);
-  HIP_TRY(hipMemcpyAsync(keys.data(), ix->d_out.p, keys.size() * sizeof(u64), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  decode_keys(keys, nq, k, 0, nullptr, scores, ids);
-  return VRAG_OK;
+  }, scores, ids);
 }
 
 int vrag_sparse_index_search_device(vrag_sparse_index* ix, const int64_t* q_indptr, const int32_t* q_indices,
@@ -3827,13 +3750,8 @@ int vrag_sparse_index_search_device(vrag_sparse_index* ix, const int64_t* q_indp
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);   // NULL = the legacy default stream (see the dense form)
   int rc;
   if ((rc = sparse_search_enqueue(ix, q_indptr, q_indices, q_values, nq, k, st))) return rc;
-  const long long n = (long long)nq * k;
-  hipLaunchKernelGGL(topk_export_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, ix->d_out.p, n,
-                     reinterpret_cast<const long long*>(row_map), (long long)n_map, (long long)id_base, out_scores,
-                     reinterpret_cast<long long*>(out_ids));
-  HIP_TRY(hipGetLastError());
-  if (!ix->lists_done) HIP_TRY(hipEventCreateWithFlags(&ix->lists_done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(ix->lists_done, st));
+  HIP_TRY(launch_topk_export(ix->d_out.p, (long long)nq * k, row_map, n_map, id_base, out_scores, out_ids, st));
+  HIP_TRY(record_event(ix->lists_done, st));
   return VRAG_OK;
 }
 
@@ -3852,10 +3770,7 @@ int vrag_sparse_index_run_resident(vrag_sparse_index* ix, int32_t nq, int32_t k,
 // An empty contribution to the exchange (a rank that holds none of the rows): -inf / -1 lists in device memory.
 int vrag_topk_fill_empty(float* scores, int64_t* ids, int64_t n, int32_t device, void* stream) {
   ARG_CHECK(scores && ids && n > 0, "bad arguments");
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   HIP_TRY(hipSetDevice(device));
   hipLaunchKernelGGL(topk_fill_empty_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                      scores, reinterpret_cast<long long*>(ids), (long long)n);
@@ -3869,10 +3784,7 @@ int vrag_topk_merge(const float* scores, const int64_t* ids, int32_t n_lists, in
                     int32_t device, void* stream) {
   ARG_CHECK(scores && ids && out_scores && out_ids, "null argument");
   ARG_CHECK(n_lists >= 1 && n_lists <= 256 && nq >= 1 && k_in >= 1 && k_out >= 1, "bad list geometry (1 <= n_lists <= 256)");
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   HIP_TRY(hipSetDevice(device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const size_t per = (size_t)nq * k_in, n_out = (size_t)nq * k_out;

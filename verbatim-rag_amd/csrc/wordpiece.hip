@@ -382,10 +382,7 @@ int vrag_wordpiece_create(const uint8_t* vocab_blob, const int64_t* piece_off, i
   std::vector<unsigned> pw(kMaxChars + 1);
   pw[0] = 1u;
   for (int k = 1; k <= kMaxChars; ++k) pw[k] = pw[k - 1] * kHashBase;
-  if (vrag_device_count() <= device) {
-    set_error("no HIP device %d visible (no CPU fallback)", device);
-    return VRAG_ERR_NO_DEVICE;
-  }
+  DEVICE_CHECK(device);
   HIP_TRY(hipSetDevice(device));
   auto* h = new vrag_wordpiece();
   h->device = device;
