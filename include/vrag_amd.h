@@ -528,6 +528,59 @@ int vrag_sq8_index_search_filtered(vrag_sq8_index* ix, const float* queries /*[n
  *   remap          after vrag_sq8_index_compact of the base with the same bitmap: as after vrag_dense_index_compact. */
 int vrag_ivf_index_create_sq8(vrag_sq8_index* base, int32_t nlist, vrag_ivf_index** out);
 
+/* ------------------------------------------------------------------------------------------
+ * PQ dense rows (csrc/pq.hip; Milvus' PQ codes, searched FLAT): a product-quantised dense field -- the vector is cut into m
+ * sub-vectors of dsub = dim / m components and each is stored as the 8-bit number of the nearest of that sub-space's 256
+ * centroids: m bytes per row in HBM (the code stride is m rounded up to 16 bytes, pad bytes zero).  Opt-in and APPROXIMATE in
+ * what a code says about its sub-vector; everything below is exact and is the contract.
+ *   chain(u, v)    acc = 0; acc = fmaf(u[t], v[t], acc) for t ascending over the dsub components (the dense oracle's chain).
+ *   codebooks      cb[m][256][dsub] fp32;  h[j][c] = 0.5f * chain(cb[j][c], cb[j][c]).
+ *   encoding       of sub-vector j of a vector x:  a(c) = chain(x_j, cb[j][c]) - h[j][c]  (one fp32 subtraction after the chain);
+ *                  code[j] = argmax_c a(c), the lowest c on ties (the nearest centroid in L2, up to rounding).
+ *   score          of query q against row r:  LUT[j][c] = chain(q_j, cb[j][c]);
+ *                  score = (((0 + LUT[0][code_r[0]]) + LUT[1][code_r[1]]) + ...), fp32 additions with j ascending, never
+ *                  reassociated, no fast-math -- the dot product of q with the row's centroids, defined bit for bit.
+ * Order (score desc, id asc), ties included (rows with equal codes tie exactly: ties are common); missing hits -1 / -inf.  Zeros
+ * tie and the sign of a returned zero is unspecified, as for SQ8.  Rows, queries and codebooks are expected to be finite.
+ *   create         1 <= dim <= 4096, 1 <= m <= 128, dim % m == 0, dsub <= 64, 0 < capacity < 2^32 - 1.  No codebooks yet.
+ *   set_codebooks  host cb [m, 256, dsub].  read_codebooks returns the bytes in place (set or trained).
+ *   train          Lloyd's k-means per sub-space on the device over host sample rows [n, dim], 0 <= iters <= 1000, no random
+ *                  numbers: the initial centroid c of every sub-space is sample row c * n / 256 (integer division); a round
+ *                  assigns every sample row by the encoding rule, then a centroid becomes the sequential fp32 sum of its members'
+ *                  sub-vectors in ascending row order (starting from 0), divided once (correctly rounded) by (float)count; an
+ *                  empty cluster keeps its centroid.  Two trainings of the same rows give the same bytes, and so does a numpy
+ *                  restatement.  set_codebooks and train are VRAG_ERR_INVALID once the index holds rows: the codes in place
+ *                  were made with the codebooks in place.
+ *   add, add_device, search, search_filtered   VRAG_ERR_INVALID before codebooks exist.
+ *   add            host fp32 rows [n, dim], staged in slabs through the device form; all of them or (VRAG_ERR_CAPACITY) none.
+ *   add_device     device fp32 rows [n, dim]; encoded on the device on `stream`, which is synchronised before the call returns.
+ *                  Rows [0, size) are never rewritten; the size is published under the handle's lock after the rows are in place.
+ *   read           rows [first_row, first_row + n) as codes [n, m] (without the pad).
+ *   compact        vrag_sq8_index_compact's contract: the codes (at their padded stride) move in place, the codebooks stay.
+ *   search         1 <= k <= 1024, queries host fp32; the tables are built on the device.  Lists of up to 64 come from one pass;
+ *                  longer ones as exact pages of 64 (a page admits only keys below the previous page's last key).
+ *   search_filtered  the same over the rows r < min(n_allow, size) whose bit is set (bit r % 32 of word r / 32); rows at or
+ *                  beyond n_allow are excluded; an empty mask returns -1 / -inf without a launch; a NULL mask with
+ *                  n_allow > 0 is VRAG_ERR_INVALID.  The kernel skips cleared rows: the cost follows the shard, not the mask.
+ * Argument errors are VRAG_ERR_INVALID before anything is launched or allocated; no device is VRAG_ERR_NO_DEVICE.  The handle
+ * has its own scratch, stream and lock. */
+typedef struct vrag_pq_index vrag_pq_index;
+int vrag_pq_index_create(int32_t dim, int32_t m, int64_t capacity, int32_t device, vrag_pq_index** out);
+void vrag_pq_index_destroy(vrag_pq_index* ix);
+int64_t vrag_pq_index_size(vrag_pq_index* ix);
+int vrag_pq_index_set_codebooks(vrag_pq_index* ix, const float* cb /*[m,256,dsub] host*/);
+int vrag_pq_index_read_codebooks(vrag_pq_index* ix, float* cb /*[m,256,dsub] host*/);
+int vrag_pq_index_train(vrag_pq_index* ix, const float* rows /*[n,dim] host*/, int64_t n, int32_t iters);
+int vrag_pq_index_add(vrag_pq_index* ix, const float* rows /*[n,dim] host*/, int64_t n);
+int vrag_pq_index_add_device(vrag_pq_index* ix, const float* rows /*[n,dim] device*/, int64_t n, void* stream);
+int vrag_pq_index_read(vrag_pq_index* ix, int64_t first_row, int64_t n, uint8_t* codes /*[n,m]*/);
+int vrag_pq_index_compact(vrag_pq_index* ix, const uint32_t* keep_words /*host*/, int64_t n_keep, int64_t* new_size);
+int vrag_pq_index_search(vrag_pq_index* ix, const float* queries /*[nq,dim] host*/, int32_t nq, int32_t k,
+                         float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, void* stream);
+int vrag_pq_index_search_filtered(vrag_pq_index* ix, const float* queries /*[nq,dim] host*/, int32_t nq, int32_t k,
+                                  const uint32_t* allow /*host, bit r%32 of word r/32*/, int64_t n_allow,
+                                  float* scores /*[nq,k]*/, int64_t* ids /*[nq,k]*/, void* stream);
+
 /* Sparse (SPLADE) rows in CSR, term ids < vocab <= 65536; only documents sharing a term with the
  * query (score > 0) are hits, like an inverted index.  ids are CSR row numbers. */
 typedef struct vrag_sparse_index vrag_sparse_index;

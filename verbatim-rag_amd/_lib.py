@@ -174,6 +174,18 @@ SIGNATURES = {
     "vrag_sq8_index_set_route": (C.c_int, [_H, C.c_int32]),
     "vrag_sq8_index_search": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, _FP, _LP, C.c_void_p]),
     "vrag_sq8_index_search_filtered": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _FP, _LP, C.c_void_p]),
+    "vrag_pq_index_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.POINTER(_H)]),
+    "vrag_pq_index_destroy": (None, [_H]),
+    "vrag_pq_index_size": (C.c_int64, [_H]),
+    "vrag_pq_index_set_codebooks": (C.c_int, [_H, _FP]),
+    "vrag_pq_index_read_codebooks": (C.c_int, [_H, _FP]),
+    "vrag_pq_index_train": (C.c_int, [_H, _FP, C.c_int64, C.c_int32]),
+    "vrag_pq_index_add": (C.c_int, [_H, _FP, C.c_int64]),
+    "vrag_pq_index_add_device": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p]),
+    "vrag_pq_index_read": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_void_p]),
+    "vrag_pq_index_compact": (C.c_int, [_H, C.c_void_p, C.c_int64, _LP]),
+    "vrag_pq_index_search": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, _FP, _LP, C.c_void_p]),
+    "vrag_pq_index_search_filtered": (C.c_int, [_H, _FP, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _FP, _LP, C.c_void_p]),
     "vrag_row_filter_create": (C.c_int, [C.c_int32, C.POINTER(_H)]),
     "vrag_row_filter_destroy": (None, [_H]),
     "vrag_row_filter_add_column": (C.c_int, [_H, _IP]),

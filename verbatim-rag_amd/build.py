@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 # VRAG_BUILD_VARIANT=<tag> (tuning experiments only): objects under build_<tag>/, library libvrag_amd_<tag>.so -- load it with VRAG_AMD_LIB
 VARIANT = os.environ.get("VRAG_BUILD_VARIANT", "")
 LIB_PATH = os.path.join(HERE, f"libvrag_amd_{VARIANT}.so" if VARIANT else "libvrag_amd.so")
-SOURCES = ["gemm_bf16.hip", "attention.hip", "qkv_attn.hip", "norm_heads.hip", "topk.hip", "compact.hip", "grouped.hip", "ivf.hip", "ivf_sq8.hip", "sq8.hip", "rowfilter.hip", "listfilter.hip", "strmatch.hip", "fuse.hip", "fulltext.hip", "wordpiece.hip", "bpe.hip", "spans.hip", "text.hip", "chunk.hip", "comm.hip", "capi.hip"]
+SOURCES = ["gemm_bf16.hip", "attention.hip", "qkv_attn.hip", "norm_heads.hip", "topk.hip", "compact.hip", "grouped.hip", "ivf.hip", "ivf_sq8.hip", "sq8.hip", "pq.hip", "rowfilter.hip", "listfilter.hip", "strmatch.hip", "fuse.hip", "fulltext.hip", "wordpiece.hip", "bpe.hip", "spans.hip", "text.hip", "chunk.hip", "comm.hip", "capi.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 FLAGS += os.environ.get("VRAG_HIPCC_FLAGS", "").split()  # tuning experiments only
 

@@ -270,6 +270,78 @@ class Sq8Shard(_Handle):
         super().close()
 
 
+class PqShard(_Handle):
+    """One GPU's slice of the dense corpus as PQ rows (`vrag_pq_index`, include/vrag_amd.h "PQ dense rows"): `m` code bytes per
+    row, scored through a per-query look-up table.  The call shapes are `DenseShard`'s, plus the codebooks: a new shard has none
+    and refuses rows and searches until `train` or `set_codebooks` has run; they are frozen once it holds rows."""
+
+    _destroy = "vrag_pq_index_destroy"
+    ivf = None    # no overlay over PQ rows (the attribute the store's search path reads on every dense shard)
+
+    def __init__(self, dim: int, m: int, capacity: int, device: int = 0):
+        _lib.require_gpu()
+        self.dim, self.m, self.capacity = dim, int(m), capacity
+        self._open("vrag_pq_index_create", dim, self.m, capacity, device)
+
+    def _rows(self, rows: np.ndarray) -> np.ndarray:
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.ndim != 2 or rows.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n, {self.dim}]")
+        return rows
+
+    def train(self, rows: np.ndarray, iters: int = 10) -> None:
+        """Lloyd's k-means per sub-space over the sample `rows` (deterministic: no random numbers, `vrag_pq_index_train`)."""
+        rows = self._rows(rows)
+        _lib.check("vrag_pq_index_train", self._lib.vrag_pq_index_train(self._h, _fp(rows), rows.shape[0], int(iters)))
+
+    def set_codebooks(self, codebooks: np.ndarray) -> None:
+        cb = np.ascontiguousarray(codebooks, dtype=np.float32)
+        if cb.shape != (self.m, 256, self.dim // self.m):
+            raise ValueError(f"codebooks must be [{self.m}, 256, {self.dim // self.m}]")
+        _lib.check("vrag_pq_index_set_codebooks", self._lib.vrag_pq_index_set_codebooks(self._h, _fp(cb)))
+
+    def codebooks(self) -> np.ndarray:
+        """float32 `[m, 256, dim // m]`, the bytes in place."""
+        cb = np.empty((self.m, 256, self.dim // self.m), np.float32)
+        _lib.check("vrag_pq_index_read_codebooks", self._lib.vrag_pq_index_read_codebooks(self._h, _fp(cb)))
+        return cb
+
+    def add(self, rows: np.ndarray) -> None:
+        rows = self._rows(rows)
+        _lib.check("vrag_pq_index_add", self._lib.vrag_pq_index_add(self._h, _fp(rows), rows.shape[0]))
+
+    def add_device(self, ptr: int, n: int, stream=None) -> None:
+        """Rows already in HBM (`ptr`: device address of fp32 `[n, dim]` on the shard's device), encoded there."""
+        _lib.check("vrag_pq_index_add_device", self._lib.vrag_pq_index_add_device(self._h, C.c_void_p(int(ptr)), int(n), stream))
+
+    def __len__(self) -> int:
+        return int(self._lib.vrag_pq_index_size(self._h))
+
+    def read(self, first_row: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Codes uint8 `[n, m]` of rows `[first_row, first_row + n)`; `n=None`: up to the end."""
+        n = len(self) - first_row if n is None else int(n)
+        codes = np.empty((max(n, 0), self.m), np.uint8)
+        _lib.check("vrag_pq_index_read", self._lib.vrag_pq_index_read(self._h, int(first_row), n, _vp(codes)))
+        return codes
+
+    def compact(self, keep: np.ndarray) -> int:
+        """`DenseShard.compact` for PQ rows: the codes move in place (`vrag_pq_index_compact`); returns the new size."""
+        return _compact_call(self._lib, "vrag_pq_index_compact", self._h, keep)
+
+    def _search(self, queries, k: int, allow, stream):
+        q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, self.dim)
+        return _search_call(self._lib, "vrag_pq_index_search", (self._h, _fp(q)), q.shape[0], k, allow, stream)
+
+    def search(self, queries: np.ndarray, k: int, stream=None) -> Tuple[np.ndarray, np.ndarray]:
+        return self._search(queries, k, None, stream)
+
+    def search_filtered(self, queries: np.ndarray, k: int, allow_words: np.ndarray, n_allow: int,
+                        stream=None) -> Tuple[np.ndarray, np.ndarray]:
+        """`search` over the rows `r < min(n_allow, len(self))` whose bit is set in `allow_words` (see
+        `DenseShard.search_filtered`): the scan skips the other rows (`vrag_pq_index_search_filtered`)."""
+        return self._search(queries, k, (allow_words, n_allow), stream)
+
+
 class IvfOverlay(_Handle):
     """IVF lists over a shard's resident rows (`vrag_ivf_index`): centroids, list offsets and row numbers only -- IVF_FLAT over
     a `DenseShard`, IVF_SQ8 over an `Sq8Shard` (`vrag_ivf_index_create_sq8`: the rows are scored by the SQ8 rule).

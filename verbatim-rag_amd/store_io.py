@@ -79,6 +79,24 @@ def _get_strings(path: str, stem: str, n: int) -> List[str]:
     return col
 
 
+def put_pq_codebooks(arrays: Dict[str, np.ndarray], codebooks, trained_rows: int) -> None:
+    """The frozen codebooks of an index_type="PQ" store as one more array of the rank's `vectors.rank{r}.npz` (and the size of
+    the sample they were trained on); a store that has not trained yet writes neither."""
+    if codebooks is not None:
+        arrays["pq_codebooks"] = np.ascontiguousarray(codebooks, dtype=np.float32)
+        arrays["pq_trained_rows"] = np.asarray([int(trained_rows)], dtype=np.int64)
+
+
+def get_pq_codebooks(arrays, m: int, dense_dim: int):
+    """(codebooks float32 `[m, 256, dense_dim // m]` or None, trained rows) from the arrays `put_pq_codebooks` wrote into."""
+    if "pq_codebooks" not in arrays:
+        return None, 0
+    cb = np.ascontiguousarray(arrays["pq_codebooks"], dtype=np.float32)
+    if cb.shape != (m, 256, dense_dim // m):
+        raise ValueError(f"saved PQ codebooks have shape {cb.shape}, expected {(m, 256, dense_dim // m)}")
+    return cb, int(np.asarray(arrays["pq_trained_rows"]).reshape(-1)[0]) if "pq_trained_rows" in arrays else 0
+
+
 def read_saved(path: str):
     """Any on-disk format -> (head, ids, [per saved rank: (owned rows, arrays, texts, enhanced, metadatas)]).
     Format 3 = `GpuVectorStore.save`; format 2 = `rows.json` holding ids / texts / metadata for all rows beside

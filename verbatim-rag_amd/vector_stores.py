@@ -27,10 +27,11 @@ from . import _lib
 # The layers under the store, re-exported here under the names callers and tests have always used.  The store resolves
 # DenseShard / SparseShard / IvfOverlay / TextIndex through THIS module's globals at call time (tests replace them here);
 # RowFilter / GroupColumn likewise, through the two factories it hands its `StoreMetadata`.
-from .shards import (_FP, _IP, _LP, DenseShard, GroupColumn, IvfOverlay, RowFilter, SparseShard, Sq8Shard, TextIndex, _allow_words, _bitmap,  # noqa: F401
+from .shards import (_FP, _IP, _LP, DenseShard, GroupColumn, IvfOverlay, PqShard, RowFilter, SparseShard, Sq8Shard, TextIndex, _allow_words, _bitmap,  # noqa: F401
                      _utf8_batch, dicts_to_csr, tokenize_keys)
 from .store_filter import _FILTER_TOKEN, _typed, compile_filter, parse_filter  # noqa: F401
-from .store_io import _NO_METADATA, _get_strings, _put_strings, _replace_into, _write_text, read_saved  # noqa: F401
+from .store_io import (_NO_METADATA, _get_strings, _put_strings, _replace_into, _write_text, get_pq_codebooks,  # noqa: F401
+                       put_pq_codebooks, read_saved)
 from .store_metadata import StoreMetadata
 
 logger = logging.getLogger(__name__)
@@ -263,6 +264,10 @@ IVF_MIN_ROWS = 4096       # below this a store with one of them searches FLAT
 IVF_NLIST_MAX = 16384     # vrag_ivf_index_create
 IVF_MIN_LIST_ROWS = 39    # rows per list a training needs, as faiss' k-means asks for (min_points_per_centroid)
 IVF_K_MAX = 64            # vrag_ivf_index_search
+PQ_MIN_ROWS = 256 * IVF_MIN_LIST_ROWS   # below this an index_type="PQ" store keeps exact fp32 rows: 256 centroids per sub-space to train
+PQ_TRAIN_ROWS_MAX = 65536   # rows of the training sample, evenly strided over the host rows (a first choice: not swept)
+PQ_TRAIN_ITERS = 10         # Lloyd rounds of that training (a first choice: not swept)
+PQ_M_MAX, PQ_DSUB_MAX = 128, 64   # vrag_pq_index_create
 
 
 def ivf_effective_nlist(n_rows: int, nlist: int) -> int:
@@ -341,15 +346,33 @@ def parse_grouping(search_params: Optional[Dict[str, Any]]) -> Optional[Grouping
     return Grouping(field, int(size), bool(strict))
 
 
-def check_index_config(index_type: str, nlist: int, nprobe: int, sharded: bool) -> None:
-    """The constructor's refusals for `index_type` / `nlist` / `nprobe` (pure: no device needed)."""
-    if index_type not in ("FLAT", *IVF_INDEX_TYPES):
-        raise ValueError(f"index_type must be 'FLAT', 'IVF_FLAT' or 'IVF_SQ8' (got {index_type!r})")
+def check_index_config(index_type: str, nlist: int, nprobe: int, sharded: bool, m: Optional[int] = None, nbits: int = 8,
+                       dense_dim: Optional[int] = None) -> None:
+    """The constructor's refusals for `index_type` / `nlist` / `nprobe` and, for index_type="PQ", `m` / `nbits` (pure: no
+    device needed)."""
+    if index_type not in ("FLAT", *IVF_INDEX_TYPES, "PQ"):
+        raise ValueError(f"index_type must be 'FLAT', 'IVF_FLAT', 'IVF_SQ8' or 'PQ' (got {index_type!r})")
     for name, v in (("nlist", nlist), ("nprobe", nprobe)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
             raise ValueError(f"{name} must be a positive integer (got {v!r})")
     if index_type in IVF_INDEX_TYPES and sharded:
         raise ValueError(f"index_type={index_type!r} is single-GPU: sharded stores (distributed=True or a comm) keep FLAT")
+    if index_type != "PQ":
+        if m is not None:
+            raise ValueError(f"m is the number of sub-vectors of index_type='PQ': not with index_type={index_type!r}")
+        return
+    if sharded:
+        raise ValueError("index_type='PQ' is single-GPU: sharded stores (distributed=True or a comm) keep FLAT")
+    if isinstance(nbits, bool) or not isinstance(nbits, (int, np.integer)) or nbits != 8:
+        raise ValueError(f"index_type='PQ' stores 8-bit codes: nbits must be 8 (got {nbits!r})")
+    if m is None:
+        raise ValueError("index_type='PQ' needs m, the number of sub-vectors (code bytes per row)")
+    if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 1 <= m <= PQ_M_MAX:
+        raise ValueError(f"m must be an integer in [1, {PQ_M_MAX}] (got {m!r})")
+    if not isinstance(dense_dim, (int, np.integer)) or dense_dim < 1 or dense_dim % m != 0:
+        raise ValueError(f"m must divide dense_dim (got m={m!r}, dense_dim={dense_dim!r})")
+    if dense_dim // m > PQ_DSUB_MAX:
+        raise ValueError(f"a PQ sub-vector holds at most {PQ_DSUB_MAX} components: dense_dim={dense_dim!r} / m={m!r} is more")
 
 
 def check_auto_compact(auto_compact: Optional[float], sharded: bool) -> None:
@@ -376,6 +399,8 @@ def check_dense_dtype(dense_dtype: str, index_type: str, sharded: bool) -> None:
         raise ValueError("index_type='IVF_FLAT' needs 'f32' or 'bf16' rows: dense_dtype='int8' searches FLAT or index_type='IVF_SQ8'")
     if index_type == "IVF_SQ8" and dense_dtype != "int8":
         raise ValueError(f"index_type='IVF_SQ8' lays its lists over SQ8 rows: it needs dense_dtype='int8' (got dense_dtype={dense_dtype!r})")
+    if index_type == "PQ" and dense_dtype != "f32":
+        raise ValueError(f"index_type='PQ' encodes fp32 rows: it needs dense_dtype='f32' (got dense_dtype={dense_dtype!r})")
 
 
 def check_choice(name: str, value, a: str, b: str) -> None:
@@ -617,6 +642,10 @@ class GpuVectorStore(VectorStore):
         """An empty dense shard of this store's `dense_dtype` with room for `capacity` rows."""
         if self.dense_dtype == "int8":
             return Sq8Shard(self.dense_dim, capacity, self.device)
+        if self._pq_codebooks is not None:      # a trained PQ store: every shard it builds carries the frozen codebooks
+            shard = PqShard(self.dense_dim, self.m, capacity, self.device)
+            shard.set_codebooks(self._pq_codebooks)
+            return shard
         return DenseShard(self.dense_dim, capacity, self.dense_dtype, self.device, prefilter=self._use_prefilter())
 
     def __init__(self, dense_dim: Optional[int] = 384, sparse_vocab: Optional[int] = 30522, enable_dense: bool = True,
@@ -625,7 +654,7 @@ class GpuVectorStore(VectorStore):
                  dense_prefilter="auto", enable_full_text: bool = False, bm25_k1: float = 1.2, bm25_b: float = 0.75,
                  filter_route: str = "subset", rrf_route: str = "host", index_type: str = "FLAT", nlist: int = 8192,
                  nprobe: int = 16, filter_eval: str = "host", filter_strings: str = "host",
-                 auto_compact: Optional[float] = None):
+                 auto_compact: Optional[float] = None, m: Optional[int] = None, nbits: int = 8):
         """`enable_full_text`: BM25 keyword search over the raw texts (milvus_cloud.py: bm25_k1 = 1.2, bm25_b = 0.75),
         `search_type="full_text"` and the third leg of a weighted hybrid search; the texts are tokenised, indexed and
         scored on the device (`TextIndex`).  Off by default.  On a sharded store (`distributed=True` or a `comm`) the
@@ -674,10 +703,19 @@ class GpuVectorStore(VectorStore):
         `search_params={"nprobe": n}` (or Milvus' `{"params": {"nprobe": n}}`) of `query` / `query_batch` overrides
         `nprobe` per call; n >= nlist returns the FLAT results.  Lists of more than 64 rows per method, filtered queries left
         short and sharded stores search FLAT.  Kept in a saved store's manifest (FLAT stores write nothing new).
+        "PQ" with `m` (and `nbits=8`, the one width) = product-quantised rows (`PqShard`, include/vrag_amd.h "PQ dense rows"): `m`
+        code bytes per row in HBM instead of 4 `dense_dim`, every query scored through a look-up table -- approximate in what a
+        code says about its sub-vector, exact and bit-defined in everything else.  `m` must divide `dense_dim` (at most 64
+        components per sub-vector, `m` <= 128); it needs `dense_dtype="f32"` and a single GPU (ValueError otherwise).  Below
+        `PQ_MIN_ROWS` rows the store keeps the exact fp32 `DenseShard`; the flush that reaches it trains the codebooks on at most
+        `PQ_TRAIN_ROWS_MAX` evenly strided host rows (`PQ_TRAIN_ITERS` Lloyd rounds, deterministic) and swaps a `PqShard` in.
+        The codebooks are frozen from then on: later inserts, shards rebuilt for capacity and filter-subset shards use them, so
+        both `filter_route`s return the same bits; `save` writes them and `load` never retrains.  `pq_stats()` tells which state
+        the store is in.  Grouping searches are refused.
         `auto_compact`: None (default) = `compact()` runs only when it is called.  A fraction in (0, 1): `delete` calls it once
         the dead rows exceed that fraction of the stored rows.  Single-GPU like `compact()`; a run-time choice, a keyword of `load`."""
         check_auto_compact(auto_compact, distributed or comm is not None)
-        check_index_config(index_type, nlist, nprobe, distributed or comm is not None)
+        check_index_config(index_type, nlist, nprobe, distributed or comm is not None, m, nbits, dense_dim)
         check_dense_dtype(dense_dtype, index_type, distributed or comm is not None)
         self._lib = _lib.load()
         _lib.require_gpu()
@@ -720,6 +758,9 @@ class GpuVectorStore(VectorStore):
         self.auto_compact = None if auto_compact is None else float(auto_compact)
         self._epoch = 0              # advanced by every compaction, under the lock (class docstring)
         self._ivf_trained_rows = 0   # rows in the shard when its overlay was last trained (0 = no overlay)
+        self.m, self.nbits = (int(m), 8) if index_type == "PQ" else (None, None)
+        self._pq_codebooks: Optional[np.ndarray] = None   # float32 [m, 256, dense_dim // m] once trained (or loaded): frozen
+        self._pq_trained_rows = 0    # rows of the sample they were trained on
         # the route searches take: the filtered search returns host lists, which the device-resident exchange does not carry.
         # Replicated configuration only, so every rank decides alike.
         self._filter_route = filter_route
@@ -967,6 +1008,9 @@ class GpuVectorStore(VectorStore):
             self._main_rows = self._owned.data
             if self.enable_dense and n > self._dense_flushed:
                 rows = self._dense_rows.data
+                if self.index_type == "PQ" and self._pq_codebooks is None and n >= PQ_MIN_ROWS:
+                    self._pq_train(rows)
+                    self._dense = None                  # the exact shard goes: the PQ shard is built from the host rows below
                 if self._dense is None or n > self._dense_cap:
                     # (re)build with head-room so later inserts append instead of re-uploading every row
                     self._dense = None                  # released now unless a search on another thread still holds it
@@ -1011,6 +1055,29 @@ class GpuVectorStore(VectorStore):
 
                 self._owned_dev = (torch.from_numpy(np.ascontiguousarray(self._main_rows)).to(torch.device("cuda", self.device)), n)
             self._dirty = False
+
+    def _pq_train(self, rows: np.ndarray) -> None:
+        """The codebooks of an index_type="PQ" store, once (called by `_flush`, under the lock, by the flush that reaches
+        `PQ_MIN_ROWS`): trained on at most `PQ_TRAIN_ROWS_MAX` evenly strided host rows by a `PqShard` made for it, read back and
+        frozen -- every shard the store builds from here on gets them through `set_codebooks` (`_new_dense_shard`)."""
+        n = len(rows)
+        take = min(n, PQ_TRAIN_ROWS_MAX)
+        sample = rows if take == n else rows[(np.arange(take, dtype=np.int64) * n) // take]
+        trainer = PqShard(self.dense_dim, self.m, 1, self.device)
+        trainer.train(sample, PQ_TRAIN_ITERS)
+        self._pq_codebooks = np.ascontiguousarray(trainer.codebooks(), dtype=np.float32)
+        self._pq_trained_rows = take
+        trainer.close()
+        self._drop_subsets()                            # subsets built from exact rows would answer with other bits
+
+    def pq_stats(self) -> Optional[Dict[str, int]]:
+        """`{"m", "rows", "trained_rows"}` of an index_type="PQ" store whose dense field is a `PqShard` after a flush; None while
+        the store searches exact rows (another index_type, or fewer than `PQ_MIN_ROWS` rows so far)."""
+        with self._mu:
+            self._flush()
+            if self._pq_codebooks is None or self._dense is None:
+                return None
+            return {"m": self.m, "rows": len(self._dense), "trained_rows": self._pq_trained_rows}
 
     @property
     def _has_lists(self) -> bool:
@@ -1606,6 +1673,8 @@ class GpuVectorStore(VectorStore):
             raise ValueError(f"{supported}: not with index_type={self.index_type!r}")
         if self.dense_dtype == "int8":
             raise ValueError(f"{supported}: not with dense_dtype='int8'")
+        if self.index_type == "PQ":
+            raise ValueError(f"{supported}: not with index_type='PQ'")
         if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 1 <= top_k <= GROUP_TOP_K_MAX:
             raise ValueError(f"a grouping search returns 1 <= top_k <= {GROUP_TOP_K_MAX} groups (got {top_k!r})")
 
@@ -1730,6 +1799,9 @@ class GpuVectorStore(VectorStore):
                     "bm25_b": self.bm25_b, "rows": len(ids), "documents": list(self._documents.values())}
             if self.index_type != "FLAT":      # a FLAT store's manifest stays byte for byte what it was
                 head.update(index_type=self.index_type, nlist=self.nlist, nprobe=self.nprobe)
+            if self.index_type == "PQ":
+                head.update(m=self.m, nbits=self.nbits)
+                put_pq_codebooks(arrays, self._pq_codebooks, self._pq_trained_rows)
             r = self._rank
 
             def put_arrays(tmp):
@@ -1766,7 +1838,10 @@ class GpuVectorStore(VectorStore):
                  dense_prefilter=head.get("dense_prefilter", "auto"), enable_full_text=bool(head.get("enable_full_text", False)),
                  bm25_k1=head.get("bm25_k1", 1.2), bm25_b=head.get("bm25_b", 0.75), filter_route=filter_route,
                  rrf_route=rrf_route, index_type=head.get("index_type", "FLAT"), nlist=head.get("nlist", 8192),
-                 nprobe=head.get("nprobe", 16), filter_eval=filter_eval, filter_strings=filter_strings, auto_compact=auto_compact)
+                 nprobe=head.get("nprobe", 16), filter_eval=filter_eval, filter_strings=filter_strings, auto_compact=auto_compact,
+                 m=head.get("m"), nbits=head.get("nbits", 8))
+        if st.index_type == "PQ":                                 # trained codebooks come back as they were: never retrained
+            st._pq_codebooks, st._pq_trained_rows = get_pq_codebooks(shards[0][1] if shards else {}, st.m, st.dense_dim)
         n = len(ids)
         for owned, *_ in shards:
             if len(owned) and (owned.min() < 0 or owned.max() >= n):
